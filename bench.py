@@ -4,6 +4,8 @@ synthetic 4096 x 4096, 8-layer image (BASELINE.json; SURVEY 8(d) generator, seed
 
   python bench.py --gpus N --steps K --warmup W          (N > 1 is launched by torch.distributed.run, one rank per GPU)
   python bench.py --size 2048 --upto 3                    (BASELINE config C2: stages 02 + 03 only, raster kernels vs the HBM roofline)
+  python bench.py --full                                  (adds the legs listed under "Extra objects" below)
+  python bench.py --dump-outputs DIR                      (after the timed steps: what the last timed step returned, as DIR/<name>.npy)
 
 A "step" is one pass of the whole hot path over one image whose pixels are already resident in HBM (orip_set_image is
 outside the timed region).  Nothing is cached between steps: every step re-runs the k-means fit, all raster stages, the
@@ -12,7 +14,12 @@ contour walk, both dedup stages and the plot ordering, and ends with every op li
 With N > 1 the single image is processed by all ranks together (colour-layer sharding), so the scaling is
 "strong"; the timed region is bracketed by a barrier + device sync and the max over ranks is reported.
 
-One JSON line on rank 0.  Extra objects:
+One JSON line on rank 0.  A plain run sets up, warms up, times the steps and prints the line (with N > 1 it adds `per_rank`).
+--dump-outputs DIR writes, per owned layer l, what a caller of the timed path holds after its last step, in float64 (exact for the
+integer data): ops_<l>.npy (the op rows of stage 12, int32 [n, 5]: type, line index, flip, x, y), lines_off_<l>.npy and lines_pts_<l>.npy
+(the flat line list of stage 10, off int64 [n + 1] and points int32 [total, 2]); with --upto 3 centers.npy (the k-means centres) and
+edges_<l>.npy (the layer's edge plane, flattened, in float32).  Over 64 MB in all, every file of more than 64 KB keeps a fixed, seeded sample of its rows.
+Extra objects, with --full only (each one runs after the timed steps):
   inclusive    -- the same step with the upload of the image inside the timed region as well: SURVEY 8(d)'s "host pixels -> ops
                   lists in host memory" (PCIe-inclusive on both ends; `value` has the input resident, as the bench contract asks)
   c2           -- BASELINE config C2 in the same run: 2048 x 2048, 8 layers, stages 02 + 03 only, with the raster kernel groups'
@@ -32,6 +39,7 @@ import json
 import os
 import sys
 import time
+import zlib
 
 os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")   # one hardware queue per layer lane (see orip/lib.py); before torch / HIP start
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -40,6 +48,7 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0     # MI355X_MICROARCH.md: HBM3E peak 8 TB/s
 PMC_FILE = os.path.join(ROOT, "profiles", "r03_pmc_traffic.json")
+DUMP_LIMIT = 64_000_000  # bytes of all --dump-outputs files together
 
 
 def csrc_digest() -> str:
@@ -76,6 +85,27 @@ PMC_NAMES = {"k_trace": ["k_trace"], "k_write_walks": ["k_vown"], "k_lab_assign"
              "k_morph_bits": ["k_morph_bits"], "k_thin_bits": ["k_thin_bits04"], "k_skel_state": ["k_bits_to_skel_state"]}
 
 
+def dump_outputs(out_dir, arrays, limit):
+    """arrays: name -> float32 / float64 array.  Writes out_dir/<name>.npy; over `limit` bytes in all, every array of more than
+    64 KB keeps the same fraction of its rows, picked by a generator seeded with its name (the same rows in every run of the same
+    output sizes), and the smaller ones are written whole."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    small = 64 << 10
+    whole = sum(a.nbytes for a in arrays.values() if a.nbytes <= small)
+    large = sum(a.nbytes for a in arrays.values()) - whole
+    budget = limit - 128 * len(arrays) - whole         # less the .npy headers and the arrays written whole
+    frac = 1.0 if large <= budget else budget / large
+    written = 0
+    for name, a in sorted(arrays.items()):
+        if frac < 1.0 and a.nbytes > small:
+            idx = np.random.default_rng(zlib.crc32(name.encode())).choice(len(a), max(1, int(len(a) * frac)), replace=False)
+            a = a[np.sort(idx)]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written += a.nbytes
+    return {"dir": out_dir, "files": len(arrays), "bytes": written, "sampled": frac < 1.0}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -84,10 +114,14 @@ def main():
     ap.add_argument("--size", type=int, default=4096, help="image side (BASELINE: 4096)")
     ap.add_argument("--layers", type=int, default=8, help="colour layers (BASELINE: 8)")
     ap.add_argument("--upto", type=int, default=12, choices=[3, 12], help="3: stages 02 + 03 only (BASELINE config C2, use with --size 2048)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-c2", action="store_true", help="skip the BASELINE config C2 leg (counter passes: its 2048^2 launches would mix into the per-launch averages)")
-    ap.add_argument("--in-flight", type=int, default=2, help="extra leg at N = 1: this many images in flight on the card, one context each (0 / 1: skip)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also run the inclusive, roofline, pipelined, C2 and CPU baseline legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step returned as DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline leg")
+    ap.add_argument("--no-c2", action="store_true", help="with --full: skip the BASELINE config C2 leg (counter passes: its 2048^2 launches would mix into the per-launch averages)")
+    ap.add_argument("--in-flight", type=int, default=2, help="with --full, extra leg at N = 1: this many images in flight on the card, one context each (0 / 1: skip)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0")); world = int(os.environ.get("WORLD_SIZE", "1")); local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -117,10 +151,27 @@ def main():
     from orip import stages as S
     from orip.synth import synth_image, layer_names
 
+    class RecordingDevice(Device):
+        """Keeps the host arrays the timed path hands its caller: each layer's op rows (stage 12) and flat line list (stage 10), by local layer index."""
+        def __init__(self, device_id):
+            super().__init__(device_id)
+            self.received = {}
+
+        def plot_order(self, layer, R_insert):
+            ops = super().plot_order(layer, R_insert)
+            self.received[("ops", layer)] = ops
+            return ops
+
+        def get_polys_flat(self, slot, layer):
+            off, pts = super().get_polys_flat(slot, layer)
+            if slot == L.SLOT_LINES_CROSS:
+                self.received[("lines", layer)] = (off, pts)
+            return off, pts
+
     H = W = args.size; K = args.layers
     img = synth_image(H, W, K)
     cfg = Config(); cfg.color_names = layer_names(K)
-    dev = Device(local_rank)
+    dev = RecordingDevice(local_rank)
     comm = P.make_comm(dev, rank, world, coll_device) if world > 1 else None
     dev.set_image(img)      # input resident in HBM before the timed region
 
@@ -133,8 +184,10 @@ def main():
     rank_times = {}             # N > 1: this rank's stage times of the LAST step (orip.parallel.run_path_sharded)
 
     def step(fetch=False):
+        dev.received.clear()
         if args.upto == 3:
             centers, _ = dev.kmeans_fit(S.subsample_indices(H * W), K)
+            dev.received["centers"] = centers
             dev.extract_layers(centers, want_counts=False)
             S._detect_edges_resident(dev, cfg)
             dev.sync()
@@ -168,9 +221,27 @@ def main():
     ms_per_step = elapsed / max(1, args.steps) * 1e3
     value = (H * W / 1e6) * args.steps / elapsed
 
+    # ---- what the last timed step returned (N > 1: every rank writes its own layers, under their global ids, within its share of the limit)
+    if args.dump_outputs and (args.upto == 12 or rank == 0):
+        arrays = {}
+        if args.upto == 3:
+            arrays["centers"] = np.asarray(dev.received["centers"], np.float64)
+            for l in range(K):
+                arrays[f"edges_{l:02d}"] = dev.get_edges(l).reshape(-1).astype(np.float32)
+        else:
+            glob_id = P.owned_layers(K, rank, world) if world > 1 else list(range(K))
+            for (kind, i), v in dev.received.items():
+                if kind == "ops":
+                    arrays[f"ops_{glob_id[i]:02d}"] = v.astype(np.float64)
+                else:
+                    arrays[f"lines_off_{glob_id[i]:02d}"] = v[0].astype(np.float64)
+                    arrays[f"lines_pts_{glob_id[i]:02d}"] = v[1].astype(np.float64)
+        dumped = dump_outputs(args.dump_outputs, arrays, DUMP_LIMIT // (world if args.upto == 12 else 1))
+        print(f"bench.py: rank {rank} wrote {dumped}", file=sys.stderr, flush=True)
+
     # ---- inclusive leg: host pixels -> every op list and its line points in host memory, same barrier bracket
     inclusive = None
-    if args.upto == 12:
+    if args.full and args.upto == 12:
         n_inc = max(1, min(3, args.steps))
         barrier()
         t1 = time.perf_counter()
@@ -185,10 +256,11 @@ def main():
 
     # ---- roofline leg: one extra profiled step (HIP events around every launch on the library's stream); not timed above
     roofline = None; groups_out = {}
-    if rank == 0:
+    if args.full and rank == 0:
         dev.prof_enable(True); dev.prof_reset()
-    step()          # every rank takes part (the step holds collectives when N > 1); only rank 0 records events
-    if rank == 0:
+    if args.full:
+        step()      # every rank takes part (the step holds collectives when N > 1); only rank 0 records events
+    if args.full and rank == 0:
         dev.prof_enable(False)
         Keff = K if world == 1 else len(P.owned_layers(K, rank, world))
         n_points = sum(dev.polys_size(L.SLOT_CONTOURS, l)[1] for l in range(Keff)) if args.upto == 12 else 0
@@ -233,7 +305,7 @@ def main():
     # ---- pipelined leg (N = 1 only, reported next to `value`, never as `value`): M images in flight, one context and one host thread each.
     # A step alone leaves the card nearly idle while the walks of the heavy layers run; a second image fills that window.
     pipelined = None
-    if world == 1 and args.upto == 12 and args.in_flight > 1:
+    if args.full and world == 1 and args.upto == 12 and args.in_flight > 1:
         import threading
         try:
             devs = [dev] + [Device(local_rank) for _ in range(args.in_flight - 1)]
@@ -268,7 +340,7 @@ def main():
 
     # ---- BASELINE config C2 in the same run (rank 0, N = 1, default size only): 2048^2 x 8, stages 02 + 03, raster kernel groups vs the HBM peak
     c2 = None
-    if rank == 0 and world == 1 and args.upto == 12 and H == 4096 and not args.no_c2:
+    if args.full and rank == 0 and world == 1 and args.upto == 12 and H == 4096 and not args.no_c2:
         try:
             H2 = W2 = 2048
             img2 = synth_image(H2, W2, K)
@@ -304,7 +376,7 @@ def main():
 
     # ---- CPU baseline legs (rank 0, N = 1 only): the oracle as a "port", bounded sample, single thread and layer threads
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle import oracle as O
         crop = min(1024, H)
         sub = np.ascontiguousarray(img[:crop, :crop])
@@ -331,8 +403,9 @@ def main():
             "scaling": "strong", "vs_baseline": None, "dtype": "u8/i32 raster + f32/f64 geometry", "data": "synthetic",
             "config": {"workload": f"{W}x{H} BGR image, {K} colour layers, {stages}", "parallelism": f"layer-sharded x{world}" if world > 1 else "one GPU, one pipeline per colour layer",
                        "ops_last_step_rank0": int(n_ops), "exchange": (comm.kind if comm is not None else "none")},
-            "inclusive": inclusive, "pipelined": pipelined, "roofline": roofline, "kernel_groups": groups_out, "c2": c2, "cpu_baseline": cpu,
         }
+        if args.full:
+            out.update(inclusive=inclusive, pipelined=pipelined, roofline=roofline, kernel_groups=groups_out, c2=c2, cpu_baseline=cpu)
         if per_rank is not None:
             out["per_rank"] = per_rank          # host-side stage times of every rank in the last timed step (orip.parallel.run_path_sharded)
         if world > 1 and n_vis < world:

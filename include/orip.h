@@ -174,6 +174,24 @@ int orip_get_ops(orip_ctx* ctx, int layer, int32_t* ops5);
 int orip_stream_codes(orip_ctx* ctx, const int32_t* moves /* [n,4] */, int64_t n, int64_t* total_steps);
 int orip_stream_codes_fetch(orip_ctx* ctx, int64_t* off_out /* [n+1] */, uint8_t* codes_out /* [total] */);
 
+/* ---- after the path: 14_preview_stream.py, headless (shared/omnirevolve_plotter_stream_previewer.py -o out.png) ----
+ * Decodes the n stream bytes, replays every command (position (0, 0), pen up, colour 0 at the start) and draws what the pen draws on an
+ * rh x rw surface: canvas W x H steps scaled uniformly and centred (the previewer's _rebuild_render_surface / _steps_to_px, IEEE double), pen-down
+ * steps as 1-px lines, taps as discs of tap_radius px, palette_rgb[3 * min(colour, 3) ..] per colour index, the last command to draw a pixel sets it.
+ * flags: ORIP_SP_INVERT_Y | ORIP_SP_CLIP (clip to the workspace rect, else to the surface) | ORIP_SP_TAPS (draw taps) | ORIP_SP_BG_WHITE.
+ * Lines are pixel-exact to the previewer wherever the step scale is <= 1; above that, and for the disc, csrc/stream_preview.hip states what is drawn.
+ * stats receives ORIP_STREAM_STATS int64 in this order: total_bytes, service_bytes, step_bytes, single_steps, double_steps, steps_total,
+ * pen_down_segments, taps, color_changes, speed_changes, eof_seen, tail_after_eof, off_canvas_draws, final_x, final_y (the previewer's Statistics),
+ * unknown_service_bytes, commands.  Errors (no fault): n < 0 or above INT32_MAX / 2 (step positions are int32), W or H < 1, rw or rh outside
+ * 1..ORIP_PREVIEW_MAX_SIDE, tap_radius outside 1..1024, unknown flags, NULL pointers.  Two-call pattern: the image stays resident, the fetch copies
+ * it out as uint8 [rh, rw, 3] RGB. */
+#define ORIP_STREAM_STATS 17
+#define ORIP_PREVIEW_MAX_SIDE 16384
+enum { ORIP_SP_INVERT_Y = 1, ORIP_SP_CLIP = 2, ORIP_SP_TAPS = 4, ORIP_SP_BG_WHITE = 8 };
+int orip_stream_preview(orip_ctx* ctx, const uint8_t* data, int64_t n, int W, int H, int rw, int rh, int flags, const uint8_t* palette_rgb /* [12] */,
+                        int tap_radius, int64_t* stats /* [ORIP_STREAM_STATS] */);
+int orip_stream_preview_fetch(orip_ctx* ctx, uint8_t* rgb /* [rh, rw, 3] */);
+
 /* ---- multi-GPU exchange (no counterpart in the reference, which is a single process) ----
  * One process per GPU; rank r owns the cluster layers {l : l % world == r} for stages 03-08 and 12.  Stage 10 is replicated and needs
  * every layer's stage-08 lists (10:236-267): orip_bcast_layer sends LINES_INTRA / TAPS_INTRA of one layer from its owner to all ranks

@@ -187,6 +187,8 @@ struct orip_ctx {
     DBuf comm_sizes;
     // 13_build_stream: moves and their direction codes (stream.hip), resident between orip_stream_codes and the fetch
     DBuf stream_segs, stream_off, stream_codes; int64_t stream_n = 0, stream_total = 0;
+    // 14_preview_stream: stream bytes, tile products / prefixes / totals / counters, key plane, RGB image (stream_preview.hip), resident until the fetch
+    DBuf sp_data, sp_agg, sp_keys, sp_rgb; int sp_rw = 0, sp_rh = 0; bool sp_ready = false;
     DBuf resize_src, resize_dst;                       // raster01.hip staging
     int memo_pre_K = 0, memo_pre_H = 0, memo_pre_W = 0; // orip_contours_reserve cleared this many memo planes of an H x W image
     // profiling

@@ -272,6 +272,18 @@ class Device:
         self._ck(self.L.orip_stream_codes_fetch(self.h, _p(off), _p(codes)))
         return off, codes[:total.value]
 
+    def stream_preview(self, data, W: int, H: int, rw: int, rh: int, flags: int, palette, tap_radius: int) -> Tuple[np.ndarray, dict]:
+        """decode + replay + draw a plotter stream (include/orip.h: orip_stream_preview) -> (rgb uint8 [rh, rw, 3], statistics dict);
+        rw x rh is the surface as drawn (orip.stream_preview.render_size applies the previewer's clamp)"""
+        from .stream_preview import STAT_FIELDS
+        d = np.ascontiguousarray(np.frombuffer(bytes(data), np.uint8) if isinstance(data, (bytes, bytearray)) else data, np.uint8).reshape(-1)
+        pal = np.ascontiguousarray(np.asarray(palette, np.int64).reshape(4, 3), np.uint8)
+        st = np.zeros(len(STAT_FIELDS), np.int64)
+        self._ck(self.L.orip_stream_preview(self.h, _p(d) if len(d) else None, len(d), int(W), int(H), int(rw), int(rh), int(flags), _p(pal), int(tap_radius), _p(st)))
+        rgb = np.zeros((int(rh), int(rw), 3), np.uint8)
+        self._ck(self.L.orip_stream_preview_fetch(self.h, _p(rgb)))
+        return rgb, {k: int(v) for k, v in zip(STAT_FIELDS, st)}
+
     # ---- multi-GPU exchange (RCCL inside liborip.so)
     def comm_unique_id(self) -> bytes:
         buf = (C.c_uint8 * _l.COMM_ID_BYTES)()

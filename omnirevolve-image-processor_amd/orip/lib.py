@@ -63,6 +63,7 @@ SIGNATURES = {
     "orip_preview_cover": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "orip_has_variants": (_i32, []),
     "orip_stream_codes": (_i32, [_vp, _vp, _i64, _P(_i64)]), "orip_stream_codes_fetch": (_i32, [_vp, _vp, _vp]),
+    "orip_stream_preview": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp]), "orip_stream_preview_fetch": (_i32, [_vp, _vp]),
     "orip_comm_unique_id": (_i32, [_vp]), "orip_comm_init": (_i32, [_vp, _vp, _i32, _i32]), "orip_comm_destroy": (_i32, [_vp]),
     "orip_bcast_layer": (_i32, [_vp, _i32, _i32]),
 }

@@ -1,6 +1,6 @@
 # pipeline.py -- runner with the reference's contract (pipeline.py:66-224) for the stages this repository provides:
-# one subprocess per stage, CONFIG_PATH in the environment, stdout streamed, non-zero exit aborts.  A stage this repository
-# does not provide (14 stream preview) is run from --ref-dir (the reference's own script) when given, otherwise skipped with a notice.
+# one subprocess per stage, CONFIG_PATH in the environment, stdout streamed, non-zero exit aborts.  Every stage 01-14 is provided here (14 is the
+# headless stream preview); a stage missing from this directory would be run from --ref-dir (the reference's own script) when given, otherwise skipped.
 import argparse
 import json
 import os

@@ -92,6 +92,7 @@ extern "C" int orip_prof_get(orip_ctx* c, const char* kernel, double* total_ms, 
 extern "C" int orip_set_layer_count(orip_ctx* c, int K) {
     orip_enter(c);
     if (K < 1 || K > ORIP_MAX_LAYERS) ORIP_FAIL(c, "K=%d out of range", K);
+    ORIP_TRY(orip_contours_invalidate(c));
     c->K = K;
     return 0;
 }
@@ -125,7 +126,8 @@ extern "C" int orip_set_polys(orip_ctx* c, int slot, int layer, int64_t n, const
     DPolys& P = c->polys[slot][layer];
     int64_t total = n ? off[n] : 0;
     { LaneRes::Prefetch08& F = c->ln[layer + 1].pf08;       // a prefetch of stage 08 still reading this layer's lists on its side stream: let it finish first
-      if (F.pending) { HIPC(c, hipEventSynchronize(c->ln[layer + 1].ev3)); } }
+      if (F.pending) { HIPC(c, hipEventSynchronize(c->ln[layer + 1].ev3)); }
+      if (slot == ORIP_SLOT_SCALED || slot == ORIP_SLOT_SORTED) F.valid = false; }      // it was computed on the list replaced here (src_off: its offsets)
     HIPC(c, P.off.ensure((size_t)(n + 1) * 8 + 64));
     HIPC(c, P.pts.ensure((size_t)std::max<int64_t>(total, 1) * 8 + 64));
     if (n) HIPC(c, hipMemcpyAsync(P.off.p, off, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, LN(c).stream));

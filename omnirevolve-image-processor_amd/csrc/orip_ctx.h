@@ -134,6 +134,9 @@ struct orip_ctx;
 void orip_enter(orip_ctx* c);
 #define ORIP_LANE_CROSS (ORIP_MAX_LAYERS + 1)
 void orip_contours_free(orip_ctx* c);
+// stage 04's schedule (orip_contours_prepare) no longer describes the resident state: waits for traces still in flight, then later orip_contours_layer
+// calls fail until the next prepare (raster04.hip)
+int orip_contours_invalidate(orip_ctx* c);
 // A lane (stream + scratch that grows with hipFree / hipMalloc) serves ONE call at a time: two host threads on one lane would free
 // buffers under each other's kernels (the r01 memory access fault of the sharded path: a stage-12 call addressed by the GLOBAL layer id
 // landed on the lane of another layer's running 04->08 pipeline).  LaneGuard claims the lane for the calling thread and the entry

@@ -128,6 +128,7 @@ extern "C" int orip_resize_area(orip_ctx* c, const uint8_t* src, int H, int W, i
     HIPC(c, c->resize_src.ensure(nsrc + 16));
     uint8_t* out;
     if (as_image) {
+        ORIP_TRY(orip_contours_invalidate(c));
         c->mask_bits = nullptr;
         ORIP_TRY(orip_raster02_lab_tables(c));
         HIPC(c, c->image.ensure(ndst + 16));

@@ -893,6 +893,7 @@ int orip_morph_open_close(orip_ctx* c, const u8* src, u8* dst, int K, int shape,
 // ------------------------------------------------------------------------------------------------
 extern "C" int orip_set_image(orip_ctx* c, const uint8_t* bgr, int H, int W) {
     orip_enter(c);
+    ORIP_TRY(orip_contours_invalidate(c));
     c->mask_bits = nullptr;
     if (!bgr || H <= 0 || W <= 0) ORIP_FAIL(c, "bad image %dx%d", W, H);
     ORIP_TRY(orip_raster02_lab_tables(c));
@@ -905,6 +906,7 @@ extern "C" int orip_set_image(orip_ctx* c, const uint8_t* bgr, int H, int W) {
 extern "C" int orip_lab_of(orip_ctx* c, const int64_t* idx, int64_t n, uint8_t* lab_out) {
     orip_enter(c);
     if (!c->image.p) ORIP_FAIL(c, "no image set");
+    ORIP_TRY(orip_contours_invalidate(c));       // (the index list goes to tmpC, the state bytes of stage 04's schedule)
     if (!idx) n = (int64_t)c->H * c->W;
     HIPC(c, c->tmpB.ensure((size_t)n * 3 + 16));
     if (idx) { HIPC(c, c->tmpC.ensure((size_t)n * 8)); HIPC(c, hipMemcpyAsync(c->tmpC.p, idx, (size_t)n * 8, hipMemcpyHostToDevice, LN(c).stream)); }
@@ -922,6 +924,7 @@ static int kmeans_fit_impl(orip_ctx* c, bool rgb, const int64_t* sample_idx, int
     c->mask_bits = nullptr;
     if (!c->image.p) ORIP_FAIL(c, "no image set");
     if (K < 1 || K > ORIP_MAX_LAYERS) ORIP_FAIL(c, "K=%d out of range 1..%d", K, ORIP_MAX_LAYERS);
+    ORIP_TRY(orip_contours_invalidate(c));       // (the sample indices go to tmpC)
     int64_t N = sample_idx ? n_idx : (int64_t)c->H * c->W;
     if (N < K || N > 0x7fffffff) ORIP_FAIL(c, "bad sample count %lld", (long long)N);
     HIPC(c, c->tmpB.ensure((size_t)N * 3 + 16));
@@ -1037,6 +1040,7 @@ extern "C" int orip_extract_layers(orip_ctx* c, const float* centers, int K, int
     orip_enter(c);
     if (!c->image.p) ORIP_FAIL(c, "no image set");
     if (K < 1 || K > ORIP_MAX_LAYERS) ORIP_FAIL(c, "K=%d out of range", K);
+    ORIP_TRY(orip_contours_invalidate(c));
     int H = c->H, W = c->W; int64_t npx = (int64_t)H * W;
     // order = argsort(L) (stable), lut[order] = arange (02:121-127)
     std::vector<int> order(K);
@@ -1087,6 +1091,7 @@ extern "C" int orip_set_masks(orip_ctx* c, const uint8_t* masks, int K, int H, i
     orip_enter(c);
     c->mask_bits = nullptr;
     if (K < 1 || K > ORIP_MAX_LAYERS || H <= 0 || W <= 0) ORIP_FAIL(c, "bad shape");
+    ORIP_TRY(orip_contours_invalidate(c));
     c->H = H; c->W = W; c->K = K;
     HIPC(c, c->masks.ensure((size_t)H * W * K));
     HIPC(c, hipMemcpyAsync(c->masks.p, masks, (size_t)H * W * K, hipMemcpyHostToDevice, LN(c).stream));
@@ -1098,6 +1103,7 @@ extern "C" int orip_keep_layers(orip_ctx* c, const int32_t* layers, int n) {
     c->edge_bits = nullptr;
     c->mask_bits = nullptr;
     if (!c->masks.p || n < 1 || n > c->K) ORIP_FAIL(c, "bad layer subset (n=%d, K=%d)", n, c->K);
+    ORIP_TRY(orip_contours_invalidate(c));
     size_t plane = (size_t)c->H * c->W;
     for (int i = 0; i < n; i++) {
         if (layers[i] < i || layers[i] >= c->K || (i && layers[i] <= layers[i - 1])) ORIP_FAIL(c, "layer subset must be strictly increasing and within range");

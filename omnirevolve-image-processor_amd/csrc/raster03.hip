@@ -432,6 +432,7 @@ extern "C" int orip_detect_edges(orip_ctx* c, int morph_k, int open_iters, int c
     orip_enter(c);
     if (!c->masks.p || c->K < 1) ORIP_FAIL(c, "no masks resident (run orip_extract_layers or orip_set_masks)");
     if (gauss_k != 3 && gauss_k != 5 && gauss_k != 7) ORIP_FAIL(c, "GaussianBlur kernel size %d unsupported (3, 5, 7)", gauss_k);
+    ORIP_TRY(orip_contours_invalidate(c));        // (stage 03 rewrites tmpC, the state bytes of stage 04's schedule)
     int H = c->H, W = c->W, K = c->K; size_t plane = (size_t)H * W;
     if (low > high) std::swap(low, high);
     HIPC(c, c->edges.ensure(plane * K));
@@ -493,6 +494,7 @@ extern "C" int orip_set_edges(orip_ctx* c, const uint8_t* edges, int K, int H, i
     orip_enter(c);
     c->edge_bits = nullptr;
     if (K < 1 || K > ORIP_MAX_LAYERS || H <= 0 || W <= 0) ORIP_FAIL(c, "bad shape");
+    ORIP_TRY(orip_contours_invalidate(c));
     c->H = H; c->W = W; c->K = K;
     HIPC(c, c->edges.ensure((size_t)H * W * K));
     HIPC(c, hipMemcpyAsync(c->edges.p, edges, (size_t)H * W * K, hipMemcpyHostToDevice, LN(c).stream));

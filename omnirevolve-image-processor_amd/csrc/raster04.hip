@@ -473,6 +473,23 @@ struct Prep04 {
     bool chains = false;                            // forced stretches are listed (cref / cpix) and flagged in the state plane
 };
 void orip_contours_free(orip_ctx* c) { delete static_cast<Prep04*>(c->prep04); c->prep04 = nullptr; }
+// The schedule reads the state bytes (tmpC), chain lists and keys of lane 0's scratch, which the raster stages and the next prepare rewrite: a trace
+// that prepare enqueued and nobody finished may still be running on its lane, so that lane is waited for first (the resident chain finishes every
+// layer it traced, so nothing waits there).  Called by every entry point that replaces the image, masks, edges or layer count, and by prepare.
+int orip_contours_invalidate(orip_ctx* c) {
+    Prep04* R = static_cast<Prep04*>(c->prep04);
+    if (!R) return 0;
+    R->ready = false;
+    for (int l = 0; l < ORIP_MAX_LAYERS; l++)
+        if (R->launched[l]) { HIPC(c, hipStreamSynchronize(c->ln[l + 1].stream)); R->launched[l] = false; }
+    return 0;
+}
+// initial log capacity factor of a trace (ORIP_TRACE_LOG_F: a test hook that makes the overflow retry of trace_finish run)
+static unsigned trace_log_f0() {
+    const char* e = getenv("ORIP_TRACE_LOG_F");
+    const int f = e ? atoi(e) : 0;
+    return f >= 1 && f <= 64 ? (unsigned)f : 64u;
+}
 
 __global__ __launch_bounds__(256) void k_comp_order_keys(const unsigned* __restrict__ keys, const unsigned* __restrict__ cs, unsigned nc, unsigned long long* __restrict__ k, unsigned* __restrict__ idx) {
     unsigned c = blockIdx.x * 256 + threadIdx.x;
@@ -497,6 +514,7 @@ extern "C" int orip_contours_reserve(orip_ctx* c, int K) {
     orip_enter(c);
     if (!c->image.p || c->H <= 0 || c->W <= 0) ORIP_FAIL(c, "no image set");
     if (K < 1 || K > ORIP_MAX_LAYERS) ORIP_FAIL(c, "K=%d out of range 1..%d", K, ORIP_MAX_LAYERS);
+    ORIP_TRY(orip_contours_invalidate(c));
     const size_t plane = (size_t)c->H * c->W;
     c->memo_pre_K = 0;
     HIPC(c, LN(c).vtmp[6].ensure(plane * (size_t)K * 8 * 4 + 64));
@@ -515,8 +533,9 @@ extern "C" int orip_contours_prepare(orip_ctx* c) {
     const int H = c->H, W = c->W, K = c->K;
     if (H > 8192 || W > 8192) ORIP_FAIL(c, "image %dx%d exceeds the 8192x8192 limit of the component key packing", W, H);
     if (!c->prep04) c->prep04 = new Prep04();
+    ORIP_TRY(orip_contours_invalidate(c));      // (traces of the previous prepare still in flight write the lane-0 state rewritten below)
     Prep04& R = *static_cast<Prep04*>(c->prep04);
-    R.ready = false; R.K = K;
+    R.K = K;
     for (int l = 0; l < ORIP_MAX_LAYERS; l++) { R.launched[l] = false; R.F[l] = 0; R.memo_clear[l] = false; }
     const size_t plane = (size_t)H * W; const int64_t n = (int64_t)plane * K;
     // the memo planes (one word per pixel and incoming direction, 0.5 GB per layer at 4096^2) are cleared on the layer lanes, not in front of
@@ -703,7 +722,7 @@ extern "C" int orip_contours_prepare(orip_ctx* c) {
             LaneGuard g(c, l + 1);
             if (!g.ok) continue;
             HIPC(c, orip_pf08_drain(c));
-            ORIP_TRY(trace_launch(c, R, l, 64));
+            ORIP_TRY(trace_launch(c, R, l, trace_log_f0()));
         }
     return 0;
 }
@@ -728,8 +747,11 @@ static int trace_launch(orip_ctx* c, Prep04& R, int layer, unsigned F) {
     A.cap_factor = F; A.comp_order = R.order + c0; A.nc = NCl;
     int* d_over = LN(c).flags.as<int>() + 20; A.overflow = d_over;
     if (R.chains) HIPC(c, hipStreamWaitEvent(LN(c).stream, c->ln[0].ev3, 0));            // the chain lists and flags (orip_contours_prepare, side stream)
-    if (!R.memo_clear[layer]) HIPC(c, hipMemsetAsync(A.memo + plane * 8 * layer, 0, plane * 8 * 4, LN(c).stream));
-    R.memo_clear[layer] = false;                     // a retry (or a second trace without prepare) clears it itself
+    if (!R.memo_clear[layer]) {                      // a retry, or a second trace of the layer after one prepare: the previous walk left its memo
+        HIPC(c, hipMemsetAsync(A.memo + plane * 8 * layer, 0, plane * 8 * 4, LN(c).stream));          // entries and the ST_VIS bits of every
+        hipLaunchKernelGGL(k_clear_visited_layer, dim3(cdiv(Ml, 256)), dim3(256), 0, LN(c).stream, A.st + plane * layer, A.lin + b0, (int64_t)Ml);   // pixel it reached
+    }
+    R.memo_clear[layer] = false;
     HIPC(c, hipMemsetAsync(A.winfo + 2 * (size_t)b0, 0, (size_t)2 * Ml * sizeof(WalkInfo), LN(c).stream));
     HIPC(c, hipMemsetAsync(d_over, 0, 4, LN(c).stream));
     if (getenv("ORIP_WALK_DBG")) {          // per-component counters (walks, steps, memo hits, closed cycles, tile loads, size)
@@ -746,7 +768,6 @@ static int trace_finish(orip_ctx* c, Prep04& R, int layer) {
     const unsigned c0 = R.layer_first[layer], c1 = R.layer_first[layer + 1];
     const unsigned b0 = R.h_cs[c0], b1 = R.h_cs[c1];
     const unsigned Ml = b1 - b0;
-    const size_t plane = (size_t)R.A.plane;
     dim3 block(256);
     int* d_over = LN(c).flags.as<int>() + 20;
     // offsets: exclusive scans over the layer's walk slots (slot order == output order: components by rank, endpoint walks then leftovers, each in raster order)
@@ -787,8 +808,7 @@ static int trace_finish(orip_ctx* c, Prep04& R, int layer) {
     HIPC(c, hipStreamSynchronize(LN(c).stream));
     if (!h_tot.pad) break;
     if (h_tot.pad == 2) ORIP_FAIL(c, "internal error: the walker of layer %d stopped making progress", layer);
-    hipLaunchKernelGGL(k_clear_visited_layer, dim3(cdiv(Ml, 256)), block, 0, LN(c).stream, R.A.st + plane * layer, R.A.lin + b0, (int64_t)Ml);   // retry with larger logs
-    ORIP_TRY(trace_launch(c, R, layer, R.F[layer] * 4));
+    ORIP_TRY(trace_launch(c, R, layer, R.F[layer] * 4));      // retry with larger logs
     }
     if (getenv("ORIP_WALK_DBG")) {
         const unsigned NCl = c1 - c0;
@@ -837,7 +857,7 @@ int orip_contours_layer_impl(orip_ctx* c, int layer, bool sync) {
     if (layer < 0 || layer >= R->K) ORIP_FAIL(c, "bad layer %d (prepared for %d layers)", layer, R->K);
     if (R->M == 0 || R->layer_first[layer] == R->layer_first[layer + 1]) return 0;
     ORIP_LANE(c, layer + 1);
-    if (!R->launched[layer]) ORIP_TRY(trace_launch(c, *R, layer, 64));      // (normally enqueued by orip_contours_prepare already)
+    if (!R->launched[layer]) ORIP_TRY(trace_launch(c, *R, layer, trace_log_f0()));      // (normally enqueued by orip_contours_prepare already)
     ORIP_TRY(trace_finish(c, *R, layer));
     if (sync) HIPC(c, hipStreamSynchronize(LN(c).stream));
     return 0;
@@ -853,7 +873,7 @@ extern "C" int orip_find_contours(orip_ctx* c) {
     Prep04& R = *static_cast<Prep04*>(c->prep04);
     if (R.M == 0) return 0;
     // every layer's trace is enqueued on its own stream first, so the long serial walks of all layers overlap
-    for (int l = 0; l < R.K; l++) if (R.layer_first[l] != R.layer_first[l + 1] && !R.launched[l]) { ORIP_LANE(c, l + 1); ORIP_TRY(trace_launch(c, R, l, 64)); }
+    for (int l = 0; l < R.K; l++) if (R.layer_first[l] != R.layer_first[l + 1] && !R.launched[l]) { ORIP_LANE(c, l + 1); ORIP_TRY(trace_launch(c, R, l, trace_log_f0())); }
     for (int l = 0; l < R.K; l++) if (R.launched[l]) { ORIP_LANE(c, l + 1); ORIP_TRY(trace_finish(c, R, l)); HIPC(c, hipStreamSynchronize(LN(c).stream)); }
     return 0;
 }

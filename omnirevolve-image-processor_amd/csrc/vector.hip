@@ -42,8 +42,9 @@ int orip_polys_materialize(orip_ctx* c, DPolys& P) {
 int orip_scale_vectors_impl(orip_ctx* c, int layer, float sx, float sy, float dx, float dy, bool sync) {
     if (layer < 0 || layer >= ORIP_MAX_LAYERS) ORIP_FAIL(c, "bad layer %d", layer);
     ORIP_LANE(c, layer + 1);
+    LN(c).pf08.valid = false;          // stage 08's prefetch read the scaled list rewritten here
     DPolys& S = c->polys[ORIP_SLOT_CONTOURS][layer]; DPolys& D = c->polys[ORIP_SLOT_SCALED][layer];
-    D.n = S.n; D.total = S.total;
+    D.n = S.n; D.total = S.total; D.pf_tag = 0;
     if (is_coded(S) && !S.scaled) {
         // walk-coded contours: the scaled list is the same walks over scaled copies of the two small point tables (own points, log pixels) --
         // _scale_one runs over ~1e6 distinct points of a heavy layer instead of its 2.8e8 list points

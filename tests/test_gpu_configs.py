@@ -15,7 +15,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 from oracle import oracle as O
-from util import same_polys
+from util import cfgobj as _cfgobj, compare_resident as _compare_resident, compare_ops as _compare_ops
 
 
 @pytest.fixture(scope="module")
@@ -24,48 +24,6 @@ def dev():
     d = Device(0)
     yield d
     d.close()
-
-
-def _cfgobj(d):
-    from orip.config import Config
-    c = Config()
-    for k, v in d.items():
-        setattr(c, k, v)
-    return c
-
-
-def _compare_resident(dev, cfgd, want, upto=12):
-    """every artefact left on the device by S.run_path against the oracle's run_pipeline result"""
-    from orip import lib as L, stages as S
-    cfg = _cfgobj(cfgd)
-    lnames = S.cluster_names(cfg)
-    assert np.array_equal(dev.get_labels(), want["labels"].astype(np.uint8))
-    for l, n in enumerate(lnames):
-        assert np.array_equal(dev.get_mask(l), want["masks"][n]), ("mask", n)
-        if upto >= 3:
-            assert np.array_equal(dev.get_edges(l), want["edges"][n]), ("edges", n)
-        if upto < 12:
-            continue
-        assert same_polys(dev.get_polys(L.SLOT_CONTOURS, l), want["contours"][n]), ("contours", n)
-        assert same_polys(dev.get_polys(L.SLOT_SCALED, l), want["scaled"][n]), ("scaled", n)
-        assert same_polys(dev.get_polys(L.SLOT_SORTED, l), want["sorted"][n]), ("sorted", n)
-        assert same_polys(dev.get_polys(L.SLOT_LINES_INTRA, l), want["intra"][n][0]), ("lines_intra", n)
-        assert dev.get_taps(L.TAPS_INTRA, l) == want["intra"][n][1], ("taps_intra", n)
-        assert same_polys(dev.get_polys(L.SLOT_LINES_CROSS, l), want["cross"][n][0]), ("lines_cross", n)
-        assert dev.get_taps(L.TAPS_CROSS, l) == want["cross"][n][1], ("taps_cross", n)
-
-
-def _compare_ops(ops, want_ops, names):
-    for n in names:
-        assert len(ops[n]) == len(want_ops[n]), n
-        for a, b in zip(ops[n], want_ops[n]):
-            assert a["type"] == b["type"]
-            if a["type"] == "line":
-                assert np.array_equal(a["points"], b["points"]), n
-            else:
-                assert (a["x"], a["y"]) == (b["x"], b["y"]), n
-    dg, tg = O.path_length(ops); dw, tw = O.path_length(want_ops)
-    assert abs(dg + tg - dw - tw) <= 1e-3 * (dw + tw)      # north_star: plotted path length within 1e-3 relative
 
 
 @pytest.mark.parametrize("case", [(512, 512, 4, "C1"), (512, 512, 8, "bench crop")], ids=lambda c: f"{c[0]}x{c[1]}x{c[2]}")

@@ -51,21 +51,42 @@ def _digest(dev, cfg):
     return out
 
 
-def test_schedules_and_kernel_variants_agree(setup, monkeypatch):
+# paths the default library takes where the fast kernels do not apply (forced here); VARIANT_SWITCHES select replaced kernels that only the variants
+# build carries (`make -C csrc variants`, ORIP_LIB_VARIANTS=1) and read as not set with the default library
+FALLBACK_SWITCHES = ("ORIP_TAIL_SEQ", "ORIP_NN_NOGRID", "ORIP_PLOT_1WG", "ORIP_TAPS_1WG", "ORIP_MORPH_BYTES", "ORIP_CCL_BYTES", "ORIP_HASH_SORT", "ORIP_NO_CHAINS",
+                     "ORIP_NO_PREFETCH08", "ORIP_CAPS_FULL", "ORIP_CAPPREV_SCAN", "ORIP_NN_NOASM", "ORIP_ARC_POINTS", "ORIP_ZS_LAUNCHES")
+VARIANT_SWITCHES = ("ORIP_KMEANS_1WG", "ORIP_THIN_BYTES", "ORIP_CUM_CHAIN")
+
+
+def _digests_under(dev, cfg, img, monkeypatch, envs):
     from orip import parallel as P
-    dev, cfg, img = setup
     digests = []
-    # (ORIP_KMEANS_1WG, ORIP_THIN_BYTES, ORIP_CUM_CHAIN select replaced kernels that only the variants build carries -- `make -C csrc variants`,
-    # ORIP_LIB_VARIANTS=1 -- and read as not set with the default library; the other switches force paths the default library falls back to)
-    for env in [{}, {"ORIP_SERIAL_LAYERS": "1"}, {"ORIP_KMEANS_1WG": "1", "ORIP_TAIL_SEQ": "1", "ORIP_NN_NOGRID": "1", "ORIP_PLOT_1WG": "1", "ORIP_TAPS_1WG": "1", "ORIP_MORPH_BYTES": "1", "ORIP_THIN_BYTES": "1", "ORIP_CCL_BYTES": "1", "ORIP_HASH_SORT": "1", "ORIP_NO_CHAINS": "1", "ORIP_NO_PREFETCH08": "1", "ORIP_CAPS_FULL": "1", "ORIP_CAPPREV_SCAN": "1", "ORIP_CUM_CHAIN": "1", "ORIP_NN_NOASM": "1", "ORIP_ARC_POINTS": "1", "ORIP_ZS_LAUNCHES": "1"}]:
-        for k in ("ORIP_SERIAL_LAYERS", "ORIP_KMEANS_1WG", "ORIP_TAIL_SEQ", "ORIP_NN_NOGRID", "ORIP_PLOT_1WG", "ORIP_TAPS_1WG", "ORIP_MORPH_BYTES", "ORIP_THIN_BYTES", "ORIP_CCL_BYTES", "ORIP_HASH_SORT", "ORIP_NO_CHAINS", "ORIP_NO_PREFETCH08", "ORIP_CAPS_FULL", "ORIP_CAPPREV_SCAN", "ORIP_CUM_CHAIN", "ORIP_NN_NOASM", "ORIP_ARC_POINTS", "ORIP_ZS_LAUNCHES"):
+    for env in envs:
+        for k in ("ORIP_SERIAL_LAYERS",) + FALLBACK_SWITCHES + VARIANT_SWITCHES:
             monkeypatch.delenv(k, raising=False)
-        for k, v in env.items():
-            monkeypatch.setenv(k, v)
+        for k in env:
+            monkeypatch.setenv(k, "1")
         dev.set_image(img)
         P.run_path_sharded(dev, cfg, H, W, 0, 1)
         digests.append(_digest(dev, cfg))
+    return digests
+
+
+def test_schedules_and_kernel_variants_agree(setup, monkeypatch):
+    dev, cfg, img = setup
+    digests = _digests_under(dev, cfg, img, monkeypatch, [(), ("ORIP_SERIAL_LAYERS",), FALLBACK_SWITCHES])
     assert digests[0] == digests[1] == digests[2]
+
+
+def test_replaced_kernel_variants_agree(setup, monkeypatch):
+    """The replaced kernels of the variants build (one-workgroup k-means, byte-plane thinning, serial cumulative-length chain) give the same
+    artefacts as the default kernels.  With the default library their switches read as not set."""
+    from orip import lib as L
+    if not L.has_variants():
+        pytest.skip("variants build not loaded")
+    dev, cfg, img = setup
+    digests = _digests_under(dev, cfg, img, monkeypatch, [(), FALLBACK_SWITCHES + VARIANT_SWITCHES])
+    assert digests[0] == digests[1]
 
 
 def test_contours_lie_on_the_skeleton_and_scaled_points_on_the_canvas(setup):

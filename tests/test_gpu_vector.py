@@ -228,10 +228,7 @@ def test_stage08_tail_simulation_both_forms(dev, monkeypatch):
         assert same_polys(got_l, want_l), (seq, len(got_l), len(want_l))
 
 
-def test_stage08_cumulative_lengths_long_polylines(dev, monkeypatch):
-    """np.cumsum of float32 segment lengths (08:58) for polylines long enough for the wave kernels: the integer-scan form (binade by binade,
-    real float adds only at binade crossings and round-half ties) and the serial chain of wave-shifted adds must both give the oracle's lines."""
-    from orip import stages as S
+def _long_polylines_case():
     rng = np.random.default_rng(2024)
     cfgd = dict(O.DEFAULTS, pixels_per_mm=10)
     cfg = _cfgobj(cfgd)
@@ -245,15 +242,33 @@ def test_stage08_cumulative_lengths_long_polylines(dev, monkeypatch):
         polys.append(p.astype(np.int32).reshape(-1, 1, 2))
     base = np.cumsum(rng.integers(-1, 2, (300, 2)), axis=0) + np.array([W // 2, H // 2])
     polys.append(np.concatenate([base, base[::-1]] * 40).astype(np.int32).reshape(-1, 1, 2))         # a bounce tail: the same cycle again and again
+    return polys, cfgd, cfg
+
+
+def test_stage08_cumulative_lengths_long_polylines(dev, monkeypatch):
+    """np.cumsum of float32 segment lengths (08:58) for polylines long enough for the wave kernels: the integer-scan form (binade by binade,
+    real float adds only at binade crossings and round-half ties) must give the oracle's lines."""
+    from orip import stages as S
+    polys, cfgd, cfg = _long_polylines_case()
     want_l, want_t = O.stage08_layer(polys, O.derived08(cfgd))
-    for chain in [False, True]:
-        if chain:
-            monkeypatch.setenv("ORIP_CUM_CHAIN", "1")
-        else:
-            monkeypatch.delenv("ORIP_CUM_CHAIN", raising=False)
-        got_l, got_t = S.dedup_layer(polys, cfg, dev)
-        assert got_t == want_t, chain
-        assert same_polys(got_l, want_l), (chain, len(got_l), len(want_l))
+    monkeypatch.delenv("ORIP_CUM_CHAIN", raising=False)
+    got_l, got_t = S.dedup_layer(polys, cfg, dev)
+    assert got_t == want_t
+    assert same_polys(got_l, want_l), (len(got_l), len(want_l))
+
+
+def test_stage08_cumulative_lengths_chain_variant(dev, monkeypatch):
+    """The serial chain of wave-shifted adds that the integer-scan form replaced (ORIP_CUM_CHAIN, variants build only: with the default library
+    the switch reads as not set and this would compare the scan form with itself) gives the oracle's lines as well."""
+    from orip import lib as L, stages as S
+    if not L.has_variants():
+        pytest.skip("variants build not loaded")
+    polys, cfgd, cfg = _long_polylines_case()
+    want_l, want_t = O.stage08_layer(polys, O.derived08(cfgd))
+    monkeypatch.setenv("ORIP_CUM_CHAIN", "1")
+    got_l, got_t = S.dedup_layer(polys, cfg, dev)
+    assert got_t == want_t
+    assert same_polys(got_l, want_l), (len(got_l), len(want_l))
 
 
 @pytest.mark.parametrize("tag", ["a", "b"])

@@ -1,15 +1,24 @@
 // csrc/orip_ctx.h -- device context of liborip.so (gfx950 only).
 #pragma once
-// Kernel variants that newer ones have REPLACED and that nothing falls back to (the one-workgroup k-means fit, byte-plane thinning, the first grid greedy
-// kernel, the sequential tail simulation, the serial float chain of the cumulative lengths) are compiled into a variants build only (`make variants` ->
-// liborip_variants.so, -DORIP_VARIANTS): there their switches (ORIP_KMEANS_1WG, ORIP_THIN_BYTES, ORIP_NN_OLDGRID / ORIP_NN_DBG, ORIP_TAIL_OLDSIM,
-// ORIP_CUM_CHAIN) select them for the agreement tests; in the default library the switches read as not set.  (The other switches force paths the default
-// library needs anyway: byte morphology / CCL / NMS for inputs the bit-plane kernels do not take, the LDS-less greedy / plot-order kernels for large lists.)
-#ifdef ORIP_VARIANTS
-#define ORIP_VARIANT(name) (getenv(name) != nullptr)
-#else
-#define ORIP_VARIANT(name) false
-#endif
+// Environment switches that force a path, and the input that takes the same path without them.  The rule: a switch may only force a path that
+// some input reaches anyway (the tests then check it against the default one); a path that no input reaches is deleted, not kept behind a switch.
+//   ORIP_MORPH_BYTES       byte-plane morphology                      non-binary explicit masks
+//   ORIP_PACK_BYTES        byte-wise bit-plane packing / unpacking    W % 64 != 0
+//   ORIP_NMS_BYTES         byte-plane blur + NMS                      gauss_k != 3, or H / W below 8
+//   ORIP_NN_NOGRID         greedy order without the grid kernel       list sizes beyond the LDS / grid limits
+//   ORIP_PLOT_1WG          plot order without the LDS kernel          list sizes beyond the LDS limit
+//   ORIP_TAPS_1WG          sequential taps without the LDS kernel     list sizes beyond the LDS limit
+//   ORIP_HASH_SORT         stage-08 near test through sorted buckets  its size condition
+//   ORIP_TAIL_SEQ          sequential tail replay of every polyline   its redo condition
+//   ORIP_CAPPREV_SCAN      previous in-canvas sample by a scan        a polyline leaves the canvas
+//   ORIP_ARC_POINTS        stage-07 arc lengths from the points       explicit lists from set_polys
+//   ORIP_NO_PREFETCH08     no stage-08 prefetch under stage 07        explicit lists from set_polys
+//   ORIP_NN_NOASM          compiled greedy step                       the compiled step is the asm loop's fallback
+//   ORIP_NO_CHAINS         per-pixel stepping of the walker           chains shorter than ORIP_CHAIN_MIN
+//   ORIP_TRACE_LATE        traces started by orip_contours_layer      a lane held by another thread
+//   ORIP_PAINT_SEPARABLE   separable line painting in stage 10        its radius and size conditions
+// Debug and test hooks, which change no result: ORIP_CAPS_TINY, ORIP_COMP_CAPS, ORIP_TIME08, ORIP_TIME10, ORIP_WALK_DBG, ORIP_NN_DBG2, ORIP_TAIL_DBG,
+// ORIP_ALLOC_DBG, ORIP_TRACE_LOG_F, ORIP_SERIAL_LAYERS.
 
 #include <hip/hip_runtime.h>
 #include <cstdint>

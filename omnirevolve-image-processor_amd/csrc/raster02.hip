@@ -162,11 +162,10 @@ __global__ void k_count_labels(const u8* __restrict__ labels, int64_t n, unsigne
 }
 
 // ------------------------------------------------------------------------------------------------
-// cv2.kmeans as ONE persistent 1024-thread workgroup.  Samples are u8 Lab triples,
-// so kmeans++ works on exact integers; the sequential scans of the CPU algorithm are replaced by
-// order-independent exact equivalents (see DESIGN.md "kmeans_fit").
+// cv2.kmeans.  Samples are u8 Lab triples, so kmeans++ works on exact integers; the
+// sequential scans of the CPU algorithm are replaced by order-independent exact equivalents (see
+// DESIGN.md "kmeans_fit").
 // ------------------------------------------------------------------------------------------------
-#define KM_T 1024
 struct KmState { unsigned long long rng; };
 
 __device__ __forceinline__ unsigned km_next(unsigned long long& st) {
@@ -177,26 +176,6 @@ __device__ __forceinline__ double km_double(unsigned long long& st) {
     unsigned t = km_next(st);
     unsigned long long v = ((unsigned long long)t << 32) | km_next(st);
     return (double)v * 5.4210108624275221700372640043497e-20;
-}
-
-__device__ __forceinline__ long long block_sum_ll(long long v, long long* red) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    long long r = 0;
-    for (int w = 0; w < KM_T / 64; w++) r += red[w];
-    return r;
-}
-// deterministic (fixed tree) double sum
-__device__ __forceinline__ double block_sum_d(double v, double* red) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double r = 0;
-    for (int w = 0; w < KM_T / 64; w++) r += red[w];
-    return r;
 }
 
 __device__ __forceinline__ int isq3(const u8* a, const u8* b) {
@@ -210,187 +189,11 @@ __device__ __forceinline__ float fsq3(const u8* a, const float* c) {
     return s;
 }
 
-#ifdef ORIP_VARIANTS      // replaced variant (ORIP_KMEANS_1WG): variants build only (make variants)
-__global__ __launch_bounds__(KM_T) void k_kmeans_fit(const u8* __restrict__ data, int N, int K, int attempts, int maxCount,
-                                                      double epsilon, int32_t* __restrict__ dist0, int32_t* __restrict__ dist1,
-                                                      int32_t* __restrict__ dist2, int32_t* __restrict__ labels,
-                                                      float* __restrict__ centers_out, double* __restrict__ compact_out,
-                                                      int* __restrict__ status) {
-    __shared__ long long red[KM_T / 64];
-    __shared__ double redd[KM_T / 64];
-    __shared__ long long part[KM_T];
-    __shared__ float centers[ORIP_MAX_LAYERS * 3], old_centers[ORIP_MAX_LAYERS * 3];
-    __shared__ int csum[KM_T / 64][ORIP_MAX_LAYERS * 4];
-    __shared__ long long tot[ORIP_MAX_LAYERS * 4];
-    __shared__ int sh_ci, sh_flag;
-    __shared__ int pp_idx[ORIP_MAX_LAYERS];
-    __shared__ unsigned long long sh_key;
-    const int tid = threadIdx.x, wave = tid >> 6;
-    const int chunk = (N + KM_T - 1) / KM_T;
-    const int lo = min(N, tid * chunk), hi = min(N, lo + chunk);
-    unsigned long long rng = 0xffffffffULL;   // identical in every thread
-    double best_compact = 1.79769313486231570815e+308;
-    int32_t *dist = dist0, *tdist = dist1, *tdist2 = dist2;
-
-    for (int a = 0; a < attempts; a++) {
-        double compactness = 0;
-        for (int iter = 0;;) {
-            double max_shift = iter == 0 ? 1.79769313486231570815e+308 : 0.0;
-            // swap(centers, old_centers)
-            __syncthreads();
-            if (tid < K * 3) { float t = centers[tid]; centers[tid] = old_centers[tid]; old_centers[tid] = t; }
-            __syncthreads();
-            if (iter == 0) {
-                // ---------------- generateCentersPP ----------------
-                int c0 = (int)(km_next(rng) % (unsigned)N);
-                if (tid == 0) pp_idx[0] = c0;
-                long long ls = 0;
-                for (int i = tid; i < N; i += KM_T) { int d = isq3(data + 3 * i, data + 3 * c0); dist[i] = d; ls += d; }
-                long long sum0 = block_sum_ll(ls, red);
-                for (int k = 1; k < K; k++) {
-                    long long bestSum = 0x7fffffffffffffffLL; int bestCenter = -1;
-                    for (int j = 0; j < 3; j++) {
-                        double p = km_double(rng) * (double)sum0;
-                        // ci = first index with inclusive prefix >= p, else N-1   (exact)
-                        long long cs = 0;
-                        for (int i = lo; i < hi; i++) cs += dist[i];
-                        part[tid] = cs;
-                        __syncthreads();
-                        if (tid == 0) {
-                            long long run = 0; int ci = N - 1; int t;
-                            for (t = 0; t < KM_T; t++) { if ((double)(run + part[t]) >= p) break; run += part[t]; }
-                            if (t < KM_T) {
-                                int l2 = min(N, t * chunk), h2 = min(N, l2 + chunk);
-                                for (int i = l2; i < h2; i++) { run += dist[i]; if ((double)run >= p) { ci = i; break; } }
-                            }
-                            // p <= 0 before any subtraction cannot happen (p>0 unless sum0==0); sum0==0: loop never breaks -> N-1
-                            if (ci > N - 1) ci = N - 1;
-                            sh_ci = ci;
-                        }
-                        __syncthreads();
-                        int ci = sh_ci;
-                        long long s = 0;
-                        for (int i = tid; i < N; i += KM_T) { int d = min(isq3(data + 3 * i, data + 3 * ci), dist[i]); tdist2[i] = d; s += d; }
-                        long long S = block_sum_ll(s, red);
-                        if (S < bestSum) { bestSum = S; bestCenter = ci; int32_t* t = tdist; tdist = tdist2; tdist2 = t; }
-                    }
-                    if (tid == 0) pp_idx[k] = bestCenter;
-                    sum0 = bestSum;
-                    { int32_t* t = dist; dist = tdist; tdist = t; }
-                    __syncthreads();
-                }
-                __syncthreads();
-                if (tid < K * 3) centers[tid] = (float)data[3 * pp_idx[tid / 3] + tid % 3];
-                __syncthreads();
-            } else {
-                // ---------------- recompute centres from labels ----------------
-                for (int i = tid; i < (KM_T / 64) * ORIP_MAX_LAYERS * 4; i += KM_T) (&csum[0][0])[i] = 0;
-                __syncthreads();
-                for (int i = tid; i < N; i += KM_T) {
-                    int k = labels[i];
-                    atomicAdd(&csum[wave][k * 4 + 0], (int)data[3 * i]);
-                    atomicAdd(&csum[wave][k * 4 + 1], (int)data[3 * i + 1]);
-                    atomicAdd(&csum[wave][k * 4 + 2], (int)data[3 * i + 2]);
-                    atomicAdd(&csum[wave][k * 4 + 3], 1);
-                }
-                __syncthreads();
-                if (tid < K * 4) { long long t = 0; for (int w = 0; w < KM_T / 64; w++) t += csum[w][tid]; tot[tid] = t; }
-                __syncthreads();
-                // float accumulation in sample order is exact (== integer sum) while every partial sum < 2^24
-                if (tid == 0) {
-                    int bad = 0;
-                    for (int k = 0; k < K; k++) for (int j = 0; j < 3; j++) if (tot[k * 4 + j] >= (1LL << 24)) bad = 1;
-                    sh_flag = bad;
-                }
-                __syncthreads();
-                if (sh_flag) {
-                    // rare slow path: literal sequential float32 accumulation by one lane
-                    if (tid == 0) {
-                        float acc[ORIP_MAX_LAYERS * 3];
-                        for (int q = 0; q < K * 3; q++) acc[q] = 0.f;
-                        for (int i = 0; i < N; i++) { int k = labels[i]; for (int j = 0; j < 3; j++) acc[k * 3 + j] = __fadd_rn(acc[k * 3 + j], (float)data[3 * i + j]); }
-                        for (int q = 0; q < K * 3; q++) centers[q] = acc[q];
-                    }
-                } else if (tid < K * 3) centers[tid] = (float)tot[(tid / 3) * 4 + tid % 3];
-                __syncthreads();
-                // empty-cluster repair (sequential over k, as the reference)
-                for (int k = 0; k < K; k++) {
-                    if (tot[k * 4 + 3] != 0) continue;      // uniform branch (shared)
-                    int max_k = 0;
-                    for (int k1 = 1; k1 < K; k1++) if (tot[max_k * 4 + 3] < tot[k1 * 4 + 3]) max_k = k1;
-                    float nb[3]; float scale = 1.f / (float)tot[max_k * 4 + 3];
-                    for (int j = 0; j < 3; j++) nb[j] = __fmul_rn(centers[max_k * 3 + j], scale);
-                    // farthest point: max_dist <= dist  => last index among maxima
-                    unsigned long long key = 0;
-                    for (int i = tid; i < N; i += KM_T) {
-                        if (labels[i] != max_k) continue;
-                        float d = fsq3(data + 3 * i, nb);
-                        unsigned long long kk = ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)i;
-                        if (kk >= key) key = kk;
-                    }
-                    if (tid == 0) sh_key = 0;
-                    __syncthreads();
-                    atomicMax(&sh_key, key);
-                    __syncthreads();
-                    int far_i = (int)(sh_key & 0xffffffffu);
-                    __syncthreads();
-                    if (tid == 0) {
-                        tot[max_k * 4 + 3]--; tot[k * 4 + 3]++; labels[far_i] = k;
-                        for (int j = 0; j < 3; j++) {
-                            float v = (float)data[3 * far_i + j];
-                            centers[max_k * 3 + j] = __fsub_rn(centers[max_k * 3 + j], v);
-                            centers[k * 3 + j] = __fadd_rn(centers[k * 3 + j], v);
-                        }
-                    }
-                    __syncthreads();
-                }
-                if (tid == 0) {
-                    for (int k = 0; k < K; k++) {
-                        float scale = 1.f / (float)tot[k * 4 + 3];
-                        for (int j = 0; j < 3; j++) centers[k * 3 + j] = __fmul_rn(centers[k * 3 + j], scale);
-                        if (iter > 0) {
-                            double d = 0;
-                            for (int j = 0; j < 3; j++) { double t = (double)__fsub_rn(centers[k * 3 + j], old_centers[k * 3 + j]); d = __dadd_rn(d, __dmul_rn(t, t)); }
-                            max_shift = fmax(max_shift, d);
-                        }
-                    }
-                    redd[0] = max_shift;
-                }
-                __syncthreads();
-                max_shift = redd[0];
-                __syncthreads();
-            }
-            ++iter;
-            bool last = (iter == max(maxCount, 2)) || (max_shift <= epsilon);
-            if (last) {
-                double s = 0;
-                for (int i = tid; i < N; i += KM_T) s += (double)fsq3(data + 3 * i, &centers[3 * labels[i]]);
-                compactness = block_sum_d(s, redd);
-                break;
-            } else {
-                for (int i = tid; i < N; i += KM_T) {
-                    float md = 0.f; int kb = 0;
-                    for (int k = 0; k < K; k++) { float d = fsq3(data + 3 * i, &centers[3 * k]); if (k == 0 || md > d) { md = d; kb = k; } }
-                    labels[i] = kb;
-                }
-                __syncthreads();
-            }
-        }
-        if (compactness < best_compact) {
-            best_compact = compactness;
-            if (tid < K * 3) centers_out[tid] = centers[tid];
-        }
-        __syncthreads();
-    }
-    if (tid == 0) { *compact_out = best_compact; *status = 0; }
-}
-#endif
-
 // ------------------------------------------------------------------------------------------------
-// The same fit spread over KMB_B workgroups with a device-wide barrier between phases (the single workgroup above spends 13 ms
-// of pure ALU time on one CU at the head of the whole path).  Every workgroup executes the same control flow: all decisions
-// are taken from values that every block reads from global memory after a barrier.  Integer sums are order-free; the only
-// floating-point reduction (compactness) is still evaluated by workgroup 0 with the tree of the 1024-thread version.
+// The fit spread over KMB_B workgroups with a device-wide barrier between phases (a single workgroup spends 13 ms of pure ALU
+// time on one CU at the head of the whole path).  Every workgroup executes the same control flow: all decisions are taken from
+// values that every block reads from global memory after a barrier.  Integer sums are order-free; the only floating-point
+// reduction (compactness) is evaluated by workgroup 0 with the fixed tree of a 1024-thread workgroup.
 // ------------------------------------------------------------------------------------------------
 #define KMB_B 64
 #define KMB_T 256
@@ -653,7 +456,7 @@ __global__ __launch_bounds__(KMB_T) void k_kmeans_fit_mb(const u8* __restrict__ 
                 for (int i = gtid; i < N; i += gsz) dd[i] = (double)fsq3(data + 3 * i, &centers[3 * labels[i]]);
                 km_grid_sync(G);
                 if (bid == 0) {
-                    // the reduction tree of the 1024-thread version: strided partials, shfl_down tree per 64, then 16 sequential adds
+                    // the reduction tree of a 1024-thread workgroup: strided partials, shfl_down tree per 64, then 16 sequential adds
                     for (int v = tid; v < 1024; v += KMB_T) { double s = 0; for (int i = v; i < N; i += 1024) s += dd[i]; ptree[v] = s; }
                     __syncthreads();
                     for (int o = 32; o > 0; o >>= 1) {
@@ -937,61 +740,37 @@ static int kmeans_fit_impl(orip_ctx* c, bool rgb, const int64_t* sample_idx, int
         hipLaunchKernelGGL(k_lab_gather, dim3(std::min<int64_t>(2048, cdiv(N, 256))), dim3(256), 0, LN(c).stream, c->image.as<u8>(),
                            sample_idx ? c->tmpC.as<int64_t>() : nullptr, N, c->tmpB.as<u8>(), c->lab_tabs.as<LabTabs>());
     }
-    HIPC(c, c->tmpD.ensure((size_t)N * 4 * 4 + 256));
-    int32_t* base = c->tmpD.as<int32_t>();
-    HIPC(c, LN(c).flags.ensure(1024));
+    HIPC(c, c->tmpD.ensure((size_t)N * 4 * 4 + 256));     // (later stages find tmpD and the lane's flags at least this large: some
+    HIPC(c, LN(c).flags.ensure(1024));                      // users of the flags do not ensure them themselves)
     attempts = std::max(attempts, 1);
     double epsilon = std::max(eps, 0.0); epsilon *= epsilon;
     int maxCount = std::min(std::max(max_iter, 2), 100);
     if (K == 1) { attempts = 1; maxCount = 2; }
-    float* d_centers = (float*)((char*)LN(c).flags.p + 256);
-    double* d_comp = (double*)((char*)LN(c).flags.p + 512);
-    int* d_status = (int*)LN(c).flags.p;
-    HIPC(c, hipMemsetAsync(LN(c).flags.p, 0xff, 4, LN(c).stream));
-#ifdef ORIP_VARIANTS
-    if (ORIP_VARIANT("ORIP_KMEANS_1WG")) {          // the single-workgroup version (test hook: both must give the same centres)
-        ProfScope ps(c, "k_kmeans_fit");
-        hipLaunchKernelGGL(k_kmeans_fit, dim3(1), dim3(KM_T), 0, LN(c).stream, c->tmpB.as<u8>(), (int)N, K, attempts, maxCount, epsilon,
-                           base, base + N, base + 2 * N, base + 3 * N, d_centers, d_comp, d_status);
-    } else
-#endif
+    const int groups = std::min(attempts, 4);
+    HIPC(c, c->tmpD.ensure((size_t)N * 4 * 2 * groups + 256));
+    int32_t* base = c->tmpD.as<int32_t>();
+    const size_t per = (size_t)N * 8 + (size_t)KMB_B * KMB_T * 8;
+    HIPC(c, c->tmpA.ensure(per * groups + (sizeof(KmGlobal) + sizeof(KmResult)) * groups + 256));
+    double* dd = c->tmpA.as<double>(); long long* parts = (long long*)(dd + (size_t)N * groups);
+    KmGlobal* G = (KmGlobal*)(parts + (size_t)KMB_B * KMB_T * groups); KmResult* res = (KmResult*)(G + groups);
+    HIPC(c, hipMemsetAsync(G, 0, sizeof(KmGlobal) * groups, LN(c).stream));
+    HIPC(c, hipMemsetAsync(res, 0xff, sizeof(KmResult) * groups, LN(c).stream));
     {
-        const int groups = std::min(attempts, 4);
-        HIPC(c, c->tmpD.ensure((size_t)N * 4 * 2 * groups + 256));
-        base = c->tmpD.as<int32_t>();
-        const size_t per = (size_t)N * 8 + (size_t)KMB_B * KMB_T * 8;
-        HIPC(c, c->tmpA.ensure(per * groups + (sizeof(KmGlobal) + sizeof(KmResult)) * groups + 256));
-        double* dd = c->tmpA.as<double>(); long long* parts = (long long*)(dd + (size_t)N * groups);
-        KmGlobal* G = (KmGlobal*)(parts + (size_t)KMB_B * KMB_T * groups); KmResult* res = (KmResult*)(G + groups);
-        HIPC(c, hipMemsetAsync(G, 0, sizeof(KmGlobal) * groups, LN(c).stream));
-        HIPC(c, hipMemsetAsync(res, 0xff, sizeof(KmResult) * groups, LN(c).stream));
-        {
-            ProfScope ps(c, "k_kmeans_fit");
-            hipLaunchKernelGGL(k_kmeans_fit_mb, dim3(KMB_B * groups), dim3(KMB_T), 0, LN(c).stream, c->tmpB.as<u8>(), (int)N, K, attempts, groups, maxCount, epsilon,
-                               base, base + (size_t)N * groups, dd, parts, res, G);
-        }
-        HIPC(c, hipGetLastError());
-        KmResult hr[4];
-        HIPC(c, hipMemcpyAsync(hr, res, sizeof(KmResult) * groups, hipMemcpyDeviceToHost, LN(c).stream));
-        HIPC(c, hipStreamSynchronize(LN(c).stream));
-        int bg = -1;
-        for (int g = 0; g < groups; g++) {
-            if (hr[g].status != 0) ORIP_FAIL(c, "kmeans kernel did not complete (group %d, status %d)", g, hr[g].status);
-            if (bg < 0 || hr[g].compact < hr[bg].compact || (hr[g].compact == hr[bg].compact && hr[g].attempt < hr[bg].attempt)) bg = g;
-        }
-        memcpy(centers_out, hr[bg].cen, sizeof(float) * K * 3);
-        if (compactness_out) *compactness_out = hr[bg].compact;
-        return 0;
+        ProfScope ps(c, "k_kmeans_fit");
+        hipLaunchKernelGGL(k_kmeans_fit_mb, dim3(KMB_B * groups), dim3(KMB_T), 0, LN(c).stream, c->tmpB.as<u8>(), (int)N, K, attempts, groups, maxCount, epsilon,
+                           base, base + (size_t)N * groups, dd, parts, res, G);
     }
     HIPC(c, hipGetLastError());
-    struct { float cen[ORIP_MAX_LAYERS * 3]; } hc; double comp; int st;
-    HIPC(c, hipMemcpyAsync(hc.cen, d_centers, sizeof(float) * K * 3, hipMemcpyDeviceToHost, LN(c).stream));
-    HIPC(c, hipMemcpyAsync(&comp, d_comp, 8, hipMemcpyDeviceToHost, LN(c).stream));
-    HIPC(c, hipMemcpyAsync(&st, d_status, 4, hipMemcpyDeviceToHost, LN(c).stream));
+    KmResult hr[4];
+    HIPC(c, hipMemcpyAsync(hr, res, sizeof(KmResult) * groups, hipMemcpyDeviceToHost, LN(c).stream));
     HIPC(c, hipStreamSynchronize(LN(c).stream));
-    if (st != 0) ORIP_FAIL(c, "kmeans kernel did not complete (status %d)", st);
-    memcpy(centers_out, hc.cen, sizeof(float) * K * 3);
-    if (compactness_out) *compactness_out = comp;
+    int bg = -1;
+    for (int g = 0; g < groups; g++) {
+        if (hr[g].status != 0) ORIP_FAIL(c, "kmeans kernel did not complete (group %d, status %d)", g, hr[g].status);
+        if (bg < 0 || hr[g].compact < hr[bg].compact || (hr[g].compact == hr[bg].compact && hr[g].attempt < hr[bg].attempt)) bg = g;
+    }
+    memcpy(centers_out, hr[bg].cen, sizeof(float) * K * 3);
+    if (compactness_out) *compactness_out = hr[bg].compact;
     return 0;
 }
 

@@ -3,15 +3,15 @@
 //   k_blur_sobel_nms : cv2.GaussianBlur((k,k),0) + Canny front half (Sobel 3x3, L1 magnitude, NMS) fused in LDS
 //   hysteresis       : Canny back half as 8-connected components of candidate pixels (union-find CCL),
 //                      a component is an edge iff it holds a strong pixel (order independent)
-// Also hosts the generic union-find CCL kernels reused by stage 04.
+// Also hosts the bit-plane union-find CCL (orip_ccl_bits) reused by stage 04.
 #include "orip_ctx.h"
 #include <algorithm>
 
 int orip_morph_open_close(orip_ctx* c, const u8* src, u8* dst, int K, int shape, int k, int open_iters, int close_iters, bool labels_mode, bool unpack = true);
 
 // ------------------------------------------------------------------------------------------------
-// Gaussian (fixed tables) + Sobel + NMS.  Output map: 0 weak candidate, 1 not an edge,
-// 2 strong.  Tile 64x16 outputs; LDS: mask tile (halo r+2), blurred tile (halo 2), magnitude (halo 1).
+// Gaussian (fixed tables) + Sobel + NMS.  Output: two bit planes, candidates (weak or
+// strong) and strong pixels.  Tile 64x16 outputs; LDS: mask tile (halo r+2), blurred tile (halo 2), magnitude (halo 1).
 // ------------------------------------------------------------------------------------------------
 #define ET_X 64
 #define ET_Y 16
@@ -23,7 +23,7 @@ __device__ __forceinline__ int reflect101(int p, int n) {
     return p;
 }
 
-__global__ __launch_bounds__(256) void k_blur_sobel_nms(const u8* __restrict__ masks, u8* __restrict__ map, int H, int W, int gk, int low, int high,
+__global__ __launch_bounds__(256) void k_blur_sobel_nms(const u8* __restrict__ masks, int H, int W, int gk, int low, int high,
                                                         unsigned long long* __restrict__ cand_bits, unsigned long long* __restrict__ strong_bits, int Ww) {
     __shared__ u8 M[ET_Y + 2 * EH_MAX][ET_X + 2 * EH_MAX];
     __shared__ u8 B[ET_Y + 4][ET_X + 4];
@@ -31,7 +31,6 @@ __global__ __launch_bounds__(256) void k_blur_sobel_nms(const u8* __restrict__ m
     const int r = gk >> 1, hm = r + 2;
     const size_t plane = (size_t)H * W;
     const u8* src = masks + plane * blockIdx.z;
-    u8* dst = map + plane * blockIdx.z;
     const int x0 = blockIdx.x * ET_X, y0 = blockIdx.y * ET_Y;
     const int mw = ET_X + 2 * hm, mh = ET_Y + 2 * hm;
     for (int i = threadIdx.x; i < mw * mh; i += blockDim.x) {
@@ -98,14 +97,12 @@ __global__ __launch_bounds__(256) void k_blur_sobel_nms(const u8* __restrict__ m
                 }
                 if (keep) res = (m > high) ? 2 : 0;
             }
-            if (map) dst[(size_t)y * W + x] = res;
         }
-        if (cand_bits) {          // candidate (weak or strong) and strong planes, one word per wave
-            const unsigned long long cm = __ballot(in && res != 1), sm = __ballot(in && res == 2);
-            if ((threadIdx.x & 63) == 0 && y < H) {
-                const size_t w = (size_t)H * Ww * blockIdx.z + (size_t)y * Ww + (x0 >> 6);
-                cand_bits[w] = cm; strong_bits[w] = sm;
-            }
+        // candidate (weak or strong) and strong planes, one word per wave
+        const unsigned long long cm = __ballot(in && res != 1), sm = __ballot(in && res == 2);
+        if ((threadIdx.x & 63) == 0 && y < H) {
+            const size_t w = (size_t)H * Ww * blockIdx.z + (size_t)y * Ww + (x0 >> 6);
+            cand_bits[w] = cm; strong_bits[w] = sm;
         }
     }
 }
@@ -238,82 +235,6 @@ __device__ __forceinline__ void uf_unite(int* L, int a, int b) {
     } while (!done);
 }
 
-// fgtest: 0 -> fg = (img != bg_value);  grid.z = layer
-__global__ __launch_bounds__(256) void k_ccl_init(const u8* __restrict__ img, int* __restrict__ par, int H, int W, int bg_value) {
-    const int Wb = (W + 1) >> 1, Hb = (H + 1) >> 1;
-    const size_t plane = (size_t)H * W, pplane = (size_t)Wb * Hb * 4;
-    const u8* s = img + plane * blockIdx.z; int* L = par + pplane * blockIdx.z;
-    int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (x >= W || y >= H) return;
-    // only foreground entries are ever read (union-find chains stay inside the foreground, every consumer tests the pixel first),
-    // so the 4-byte parents of the background -- 98 % of the plane -- are not written at all
-    if (s[(size_t)y * W + x] != bg_value) { const int id = px_id(y, x, Wb); L[id] = id; }
-}
-__global__ __launch_bounds__(256) void k_ccl_merge(const u8* __restrict__ img, int* __restrict__ par, int H, int W, int bg_value) {
-    const int Wb = (W + 1) >> 1, Hb = (H + 1) >> 1;
-    const size_t plane = (size_t)H * W, pplane = (size_t)Wb * Hb * 4;
-    const u8* s = img + plane * blockIdx.z; int* L = par + pplane * blockIdx.z;
-    int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (x >= W || y >= H) return;
-    if (s[(size_t)y * W + x] == bg_value) return;
-    int id = px_id(y, x, Wb);
-    if (x > 0 && s[(size_t)y * W + x - 1] != bg_value) uf_unite(L, id, px_id(y, x - 1, Wb));
-    if (y > 0) {
-        const u8* up = s + (size_t)(y - 1) * W;
-        if (x > 0 && up[x - 1] != bg_value) uf_unite(L, id, px_id(y - 1, x - 1, Wb));
-        if (up[x] != bg_value) uf_unite(L, id, px_id(y - 1, x, Wb));
-        if (x + 1 < W && up[x + 1] != bg_value) uf_unite(L, id, px_id(y - 1, x + 1, Wb));
-    }
-}
-// plane-aware flatten
-__global__ __launch_bounds__(256) void k_ccl_flatten2(const u8* __restrict__ img, int* __restrict__ par, int H, int W, int bg_value) {
-    const int Wb = (W + 1) >> 1, Hb = (H + 1) >> 1;
-    const size_t plane = (size_t)H * W, pplane = (size_t)Wb * Hb * 4;
-    const u8* s = img + plane * blockIdx.z; int* L = par + pplane * blockIdx.z;
-    int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (x >= W || y >= H) return;
-    if (s[(size_t)y * W + x] == bg_value) return;
-    const int id = px_id(y, x, Wb);
-    L[id] = uf_find(L, id);
-}
-// ---- 16 pixels per thread (rows that are multiples of 16 wide): the planes are ~98 % background, and a thread whose sixteen bytes
-// are all background returns after one 16-byte load; the rest is the same union-find as above.  mode 0: init, 1: merge, 2: flatten.
-__global__ __launch_bounds__(256) void k_ccl16(const u8* __restrict__ img, int* __restrict__ par, int H, int W, int bg_value, int mode) {
-    const int Wb = (W + 1) >> 1, Hb = (H + 1) >> 1, W16 = W >> 4;
-    const size_t plane = (size_t)H * W, pplane = (size_t)Wb * Hb * 4;
-    const u8* s = img + plane * blockIdx.z; int* L = par + pplane * blockIdx.z;
-    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (t >= (size_t)H * W16) return;
-    const int y = (int)(t / W16), x0 = (int)(t % W16) * 16;
-    const uint4 cur = *reinterpret_cast<const uint4*>(s + (size_t)y * W + x0);
-    const unsigned splat = 0x01010101u * (unsigned)bg_value;
-    if (cur.x == splat && cur.y == splat && cur.z == splat && cur.w == splat) return;
-    const unsigned cw[4] = {cur.x, cur.y, cur.z, cur.w};
-    auto CUR = [&](int j) -> int { return (int)((cw[j >> 2] >> (8 * (j & 3))) & 0xffu); };
-    if (mode == 0) { for (int j = 0; j < 16; j++) if (CUR(j) != bg_value) { const int id = px_id(y, x0 + j, Wb); L[id] = id; } return; }
-    if (mode == 2) { for (int j = 0; j < 16; j++) if (CUR(j) != bg_value) { const int id = px_id(y, x0 + j, Wb); L[id] = uf_find(L, id); } return; }
-    // merge: left neighbour and the three upper neighbours of every foreground pixel
-    const int left = x0 > 0 ? (int)s[(size_t)y * W + x0 - 1] : bg_value;
-    unsigned uw[4] = {splat, splat, splat, splat}; int ul = bg_value, ur = bg_value;
-    if (y > 0) {
-        const u8* up = s + (size_t)(y - 1) * W;
-        const uint4 u = *reinterpret_cast<const uint4*>(up + x0);
-        uw[0] = u.x; uw[1] = u.y; uw[2] = u.z; uw[3] = u.w;
-        if (x0 > 0) ul = up[x0 - 1];
-        if (x0 + 16 < W) ur = up[x0 + 16];
-    }
-    auto UP = [&](int j) -> int { return j < 0 ? ul : (j > 15 ? ur : (int)((uw[j >> 2] >> (8 * (j & 3))) & 0xffu)); };
-    for (int j = 0; j < 16; j++) {
-        if (CUR(j) == bg_value) continue;
-        const int x = x0 + j, id = px_id(y, x, Wb);
-        if ((j > 0 ? CUR(j - 1) : left) != bg_value) uf_unite(L, id, px_id(y, x - 1, Wb));
-        if (y > 0) {
-            if (UP(j - 1) != bg_value) uf_unite(L, id, px_id(y - 1, x - 1, Wb));
-            if (UP(j) != bg_value) uf_unite(L, id, px_id(y - 1, x, Wb));
-            if (UP(j + 1) != bg_value) uf_unite(L, id, px_id(y - 1, x + 1, Wb));
-        }
-    }
-}
 // components of bit planes (one bit per pixel, 64 per word, blockIdx.z = layer): a thread owns a word, returns at once when it is
 // empty and walks its set bits otherwise.  Same ids (block raster) and the same union-find as above.  mode 0 init, 1 merge, 2 flatten.
 __global__ __launch_bounds__(256) void k_ccl_bits(const unsigned long long* __restrict__ bits, int* __restrict__ par, int H, int W, int Ww, int mode) {
@@ -350,46 +271,6 @@ int orip_ccl_bits(orip_ctx* c, const unsigned long long* bits, int* par, int K) 
     { ProfScope ps(c, "k_ccl_flatten"); hipLaunchKernelGGL(k_ccl_bits, g, block, 0, LN(c).stream, bits, par, H, W, Ww, 2); }
     HIPC(c, hipGetLastError());
     return 0;
-}
-
-int orip_ccl(orip_ctx* c, const u8* img, int* par, int K, int bg_value) {
-    int H = c->H, W = c->W;
-    dim3 grid(cdiv(W, 64), cdiv(H, 4), K), block(256);
-    if ((W & 15) == 0 && !getenv("ORIP_CCL_BYTES")) {
-        dim3 g16((unsigned)cdiv((int64_t)H * (W >> 4), 256), 1, K);
-        { ProfScope ps(c, "k_ccl_init"); hipLaunchKernelGGL(k_ccl16, g16, block, 0, LN(c).stream, img, par, H, W, bg_value, 0); }
-        { ProfScope ps(c, "k_ccl_merge"); hipLaunchKernelGGL(k_ccl16, g16, block, 0, LN(c).stream, img, par, H, W, bg_value, 1); }
-        { ProfScope ps(c, "k_ccl_flatten"); hipLaunchKernelGGL(k_ccl16, g16, block, 0, LN(c).stream, img, par, H, W, bg_value, 2); }
-        HIPC(c, hipGetLastError());
-        return 0;
-    }
-    { ProfScope ps(c, "k_ccl_init"); hipLaunchKernelGGL(k_ccl_init, grid, block, 0, LN(c).stream, img, par, H, W, bg_value); }
-    { ProfScope ps(c, "k_ccl_merge"); hipLaunchKernelGGL(k_ccl_merge, grid, block, 0, LN(c).stream, img, par, H, W, bg_value); }
-    { ProfScope ps(c, "k_ccl_flatten"); hipLaunchKernelGGL(k_ccl_flatten2, grid, block, 0, LN(c).stream, img, par, H, W, bg_value); }
-    HIPC(c, hipGetLastError());
-    return 0;
-}
-
-// hysteresis: mark roots that hold a strong pixel, then edge = candidate && marked(root)
-__global__ __launch_bounds__(256) void k_hyst_mark(const u8* __restrict__ map, const int* __restrict__ par, u8* __restrict__ strong_root, int H, int W) {
-    const int Wb = (W + 1) >> 1, Hb = (H + 1) >> 1;
-    const size_t plane = (size_t)H * W, pplane = (size_t)Wb * Hb * 4;
-    int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (x >= W || y >= H) return;
-    if (map[plane * blockIdx.z + (size_t)y * W + x] != 2) return;
-    int root = par[pplane * blockIdx.z + px_id(y, x, Wb)];
-    strong_root[pplane * blockIdx.z + root] = 1;
-}
-__global__ __launch_bounds__(256) void k_hyst_out(const u8* __restrict__ map, const int* __restrict__ par, const u8* __restrict__ strong_root,
-                                                   u8* __restrict__ edges, int H, int W) {
-    const int Wb = (W + 1) >> 1, Hb = (H + 1) >> 1;
-    const size_t plane = (size_t)H * W, pplane = (size_t)Wb * Hb * 4;
-    int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (x >= W || y >= H) return;
-    size_t o = plane * blockIdx.z + (size_t)y * W + x;
-    u8 v = 0;
-    if (map[o] != 1) { int root = par[pplane * blockIdx.z + px_id(y, x, Wb)]; v = strong_root[pplane * blockIdx.z + root] ? 255 : 0; }
-    edges[o] = v;
 }
 
 // hysteresis on bit planes: roots of components that hold a strong pixel, then edge = candidate whose root is marked
@@ -432,14 +313,14 @@ extern "C" int orip_detect_edges(orip_ctx* c, int morph_k, int open_iters, int c
     orip_enter(c);
     if (!c->masks.p || c->K < 1) ORIP_FAIL(c, "no masks resident (run orip_extract_layers or orip_set_masks)");
     if (gauss_k != 3 && gauss_k != 5 && gauss_k != 7) ORIP_FAIL(c, "GaussianBlur kernel size %d unsupported (3, 5, 7)", gauss_k);
-    ORIP_TRY(orip_contours_invalidate(c));        // (stage 03 rewrites tmpC, the state bytes of stage 04's schedule)
+    ORIP_TRY(orip_contours_invalidate(c));        // (new edges: stage 04's schedule no longer describes them)
     int H = c->H, W = c->W, K = c->K; size_t plane = (size_t)H * W;
     if (low > high) std::swap(low, high);
     HIPC(c, c->edges.ensure(plane * K));
     HIPC(c, c->tmpB.ensure(plane * K));   // morphed masks
-    HIPC(c, c->tmpC.ensure(plane * K));   // NMS map
+    HIPC(c, c->tmpC.ensure(plane * K));   // (not written here: stage 04's state bytes, sized with the other planes)
     // binary masks + 3x3 Gaussian: the NMS kernel reads the morphed bit planes, no byte plane in between
-    const bool nms_from_bits = gauss_k == 3 && W >= 8 && H >= 8 && !getenv("ORIP_CCL_BYTES") && !getenv("ORIP_NMS_BYTES");
+    const bool nms_from_bits = gauss_k == 3 && W >= 8 && H >= 8 && !getenv("ORIP_NMS_BYTES");
     c->morphed_bits = nullptr;
     ORIP_TRY(orip_morph_open_close(c, c->masks.as<u8>(), c->tmpB.as<u8>(), K, 2, morph_k, open_iters, close_iters, false, !nms_from_bits));
     dim3 grid(cdiv(W, ET_X), cdiv(H, ET_Y), K), block(256);
@@ -447,38 +328,27 @@ extern "C" int orip_detect_edges(orip_ctx* c, int morph_k, int open_iters, int c
     HIPC(c, c->tmpD.ensure(pplane * K * sizeof(int)));
     HIPC(c, LN(c).tmpE.ensure(pplane * K));
     c->edge_bits = nullptr;
-    if (!getenv("ORIP_CCL_BYTES")) {
-        // candidates are ~2 % of the pixels: NMS leaves two bit planes (candidate, strong); components, strong roots and edges are
-        // computed from words; the edge bit planes stay for stage 04's thinning
-        const int Ww = (W + 63) >> 6; const size_t nw = (size_t)H * Ww;
-        HIPC(c, LN(c).vtmp[11].ensure(nw * K * 16 + 64));
-        HIPC(c, LN(c).vtmp[10].ensure(nw * K * 16 + 64));
-        unsigned long long* cand = LN(c).vtmp[11].as<unsigned long long>(); unsigned long long* strong = cand + nw * K;
-        unsigned long long* ebits = LN(c).vtmp[10].as<unsigned long long>();
-        if (nms_from_bits && c->morphed_bits) {
-            ProfScope ps(c, "k_blur_sobel_nms");
-            hipLaunchKernelGGL(k_nms_bits3, dim3(cdiv(W, NB_TX), cdiv(H, NB_TY), K), block, 0, LN(c).stream, (const unsigned long long*)c->morphed_bits, H, W, Ww, low, high, cand, strong);
-        } else { ProfScope ps(c, "k_blur_sobel_nms"); hipLaunchKernelGGL(k_blur_sobel_nms, grid, block, 0, LN(c).stream, c->tmpB.as<u8>(), (u8*)nullptr, H, W, gauss_k, low, high, cand, strong, Ww); }
-        c->morphed_bits = nullptr;
-        ORIP_TRY(orip_ccl_bits(c, cand, c->tmpD.as<int>(), K));
-        HIPC(c, hipMemsetAsync(LN(c).tmpE.p, 0, pplane * K, LN(c).stream));
-        dim3 gw((unsigned)cdiv((int64_t)nw, 256), 1, K);
-        { ProfScope ps(c, "k_hyst_mark"); hipLaunchKernelGGL(k_hyst_bits_mark, gw, block, 0, LN(c).stream, strong, c->tmpD.as<int>(), LN(c).tmpE.as<u8>(), H, W, Ww); }
-        { ProfScope ps(c, "k_hyst_out"); hipLaunchKernelGGL(k_hyst_bits_out, gw, block, 0, LN(c).stream, cand, c->tmpD.as<int>(), LN(c).tmpE.as<u8>(), ebits, H, W, Ww); }
-        if ((W & 63) == 0 && !getenv("ORIP_PACK_BYTES")) hipLaunchKernelGGL(k_bits_expand16, dim3((unsigned)cdiv((int64_t)H * Ww * 4, 256), 1, K), block, 0, LN(c).stream, ebits, c->edges.as<u8>(), (size_t)H * Ww);
-        else hipLaunchKernelGGL(k_bits_to_bytes03, gw, block, 0, LN(c).stream, ebits, c->edges.as<u8>(), H, W, Ww);
-        HIPC(c, hipGetLastError());
-        c->edge_bits = ebits;
-        return 0;
-    }
-    { ProfScope ps(c, "k_blur_sobel_nms"); hipLaunchKernelGGL(k_blur_sobel_nms, grid, block, 0, LN(c).stream, c->tmpB.as<u8>(), c->tmpC.as<u8>(), H, W, gauss_k, low, high, (unsigned long long*)nullptr, (unsigned long long*)nullptr, 0); }
-    HIPC(c, hipGetLastError());
-    ORIP_TRY(orip_ccl(c, c->tmpC.as<u8>(), c->tmpD.as<int>(), K, 1));
+    // candidates are ~2 % of the pixels: NMS leaves two bit planes (candidate, strong); components, strong roots and edges are
+    // computed from words; the edge bit planes stay for stage 04's thinning
+    const int Ww = (W + 63) >> 6; const size_t nw = (size_t)H * Ww;
+    HIPC(c, LN(c).vtmp[11].ensure(nw * K * 16 + 64));
+    HIPC(c, LN(c).vtmp[10].ensure(nw * K * 16 + 64));
+    unsigned long long* cand = LN(c).vtmp[11].as<unsigned long long>(); unsigned long long* strong = cand + nw * K;
+    unsigned long long* ebits = LN(c).vtmp[10].as<unsigned long long>();
+    if (nms_from_bits && c->morphed_bits) {
+        ProfScope ps(c, "k_blur_sobel_nms");
+        hipLaunchKernelGGL(k_nms_bits3, dim3(cdiv(W, NB_TX), cdiv(H, NB_TY), K), block, 0, LN(c).stream, (const unsigned long long*)c->morphed_bits, H, W, Ww, low, high, cand, strong);
+    } else { ProfScope ps(c, "k_blur_sobel_nms"); hipLaunchKernelGGL(k_blur_sobel_nms, grid, block, 0, LN(c).stream, c->tmpB.as<u8>(), H, W, gauss_k, low, high, cand, strong, Ww); }
+    c->morphed_bits = nullptr;
+    ORIP_TRY(orip_ccl_bits(c, cand, c->tmpD.as<int>(), K));
     HIPC(c, hipMemsetAsync(LN(c).tmpE.p, 0, pplane * K, LN(c).stream));
-    dim3 g2(cdiv(W, 64), cdiv(H, 4), K);
-    { ProfScope ps(c, "k_hyst_mark"); hipLaunchKernelGGL(k_hyst_mark, g2, block, 0, LN(c).stream, c->tmpC.as<u8>(), c->tmpD.as<int>(), LN(c).tmpE.as<u8>(), H, W); }
-    { ProfScope ps(c, "k_hyst_out"); hipLaunchKernelGGL(k_hyst_out, g2, block, 0, LN(c).stream, c->tmpC.as<u8>(), c->tmpD.as<int>(), LN(c).tmpE.as<u8>(), c->edges.as<u8>(), H, W); }
+    dim3 gw((unsigned)cdiv((int64_t)nw, 256), 1, K);
+    { ProfScope ps(c, "k_hyst_mark"); hipLaunchKernelGGL(k_hyst_bits_mark, gw, block, 0, LN(c).stream, strong, c->tmpD.as<int>(), LN(c).tmpE.as<u8>(), H, W, Ww); }
+    { ProfScope ps(c, "k_hyst_out"); hipLaunchKernelGGL(k_hyst_bits_out, gw, block, 0, LN(c).stream, cand, c->tmpD.as<int>(), LN(c).tmpE.as<u8>(), ebits, H, W, Ww); }
+    if ((W & 63) == 0 && !getenv("ORIP_PACK_BYTES")) hipLaunchKernelGGL(k_bits_expand16, dim3((unsigned)cdiv((int64_t)H * Ww * 4, 256), 1, K), block, 0, LN(c).stream, ebits, c->edges.as<u8>(), (size_t)H * Ww);
+    else hipLaunchKernelGGL(k_bits_to_bytes03, gw, block, 0, LN(c).stream, ebits, c->edges.as<u8>(), H, W, Ww);
     HIPC(c, hipGetLastError());
+    c->edge_bits = ebits;
     return 0;
 }
 

@@ -1,8 +1,8 @@
 // csrc/raster04.hip -- stage 04 (04_find_contours.py vectorize_layer, 04:214-230) on gfx950:
-//   k_thin_sub        : one Zhang-Suen sub-iteration with the reference's rotated neighbour numbering (04:50-93)
+//   k_thin_bits04     : one Zhang-Suen sub-iteration on bit planes with the reference's rotated neighbour numbering (04:50-93)
 //   CCL               : union-find kernels of raster03.hip (component order = block-raster)
-//   k_skel_state      : per-pixel state byte (fg, endpoint deg==1, junction deg>=3)          (04:128-130)
-//   k_compact_*       : wavefront ballot / prefix-sum compaction of skeleton pixels in raster order (04:144,174)
+//   k_bits_to_skel_state : skeleton bytes and per-pixel state byte (fg, endpoint deg==1, junction deg>=3)  (04:128-130)
+//   k_compact_*_bits  : popcount / prefix-sum compaction of skeleton pixels in raster order (04:144,174)
 //   radix sort        : rocPRIM stable sort of (layer, component root) keys -> per-component pixel lists
 //   k_trace / k_write_walks : the centerline walker (walker.h), exact serial semantics (04:137-205): one wave per component
 //                       runs twice (count, then write); the guard-bounded "bounce" tails of phase-2 walks are
@@ -13,105 +13,14 @@
 #include <algorithm>
 #include <cstdlib>
 
-int orip_ccl(orip_ctx* c, const u8* img, int* par, int K, int bg_value);
 int orip_ccl_bits(orip_ctx* c, const unsigned long long* bits, int* par, int K);
 
 // ------------------------------------------------------------------------------------------------
-// Thinning.  P2..P9 offsets (dy,dx) derived from the _shift() arguments at 04:53-55.
+// Ordered compaction (raster order inside a layer, layers in order) of the thinned BIT planes ([K][H][Ww] words; a set bit = a skeleton
+// pixel = ST_FG in the state plane): a thread owns a word, a block 256 consecutive words of the flattened planes; popcounts, a shuffle scan
+// inside the wave, LDS across the 4 waves of a block, block offsets from an exclusive scan of per-block counts.  (Reading the state bytes
+// instead is 134 MB at 4096^2 x 8, 0.43 ms in front of the walks; the planes are 16 MB and almost empty.)
 // ------------------------------------------------------------------------------------------------
-#ifdef ORIP_VARIANTS      // replaced variant (ORIP_THIN_BYTES): variants build only (make variants)
-__global__ __launch_bounds__(256) void k_thin_sub(const u8* __restrict__ src, u8* __restrict__ dst, int H, int W, int sub, int* __restrict__ changed) {
-    const size_t plane = (size_t)H * W;
-    const u8* s = src + plane * blockIdx.z; u8* d = dst + plane * blockIdx.z;
-    int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (x >= W || y >= H) return;
-    size_t o = (size_t)y * W + x;
-    u8 v = s[o];
-    if (v) {
-        auto g = [&](int dy, int dx) -> int { int yy = y + dy, xx = x + dx; return (yy >= 0 && yy < H && xx >= 0 && xx < W && s[(size_t)yy * W + xx]) ? 1 : 0; };
-        int P2 = g(1, 0), P3 = g(1, -1), P4 = g(0, -1), P5 = g(-1, -1), P6 = g(-1, 0), P7 = g(-1, 1), P8 = g(0, 1), P9 = g(1, 1);
-        int Bn = P2 + P3 + P4 + P5 + P6 + P7 + P8 + P9;
-        int A = (!P2 && P3) + (!P3 && P4) + (!P4 && P5) + (!P5 && P6) + (!P6 && P7) + (!P7 && P8) + (!P8 && P9) + (!P9 && P2);
-        bool cnd = sub == 0 ? (P2 * P4 * P6 == 0 && P4 * P6 * P8 == 0) : (P2 * P4 * P8 == 0 && P2 * P6 * P8 == 0);
-        if (A == 1 && Bn >= 2 && Bn <= 6 && cnd) { v = 0; *changed = 1; }
-    }
-    d[o] = v ? 255 : 0;
-}
-#endif
-
-// ------------------------------------------------------------------------------------------------
-// state byte (walker.h): ST_FG, ST_VIS, ST_END (deg == 1), ST_JUN (deg >= 3)
-// ------------------------------------------------------------------------------------------------
-#ifdef ORIP_VARIANTS      // replaced variant (ORIP_THIN_BYTES): variants build only (make variants)
-__global__ __launch_bounds__(256) void k_skel_state(const u8* __restrict__ skel, u8* __restrict__ st, int H, int W) {
-    const size_t plane = (size_t)H * W;
-    const u8* s = skel + plane * blockIdx.z; u8* d = st + plane * blockIdx.z;
-    int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (x >= W || y >= H) return;
-    size_t o = (size_t)y * W + x;
-    u8 v = 0;
-    if (s[o]) {
-        int deg = 0;
-        for (int dy = -1; dy <= 1; dy++)
-            for (int dx = -1; dx <= 1; dx++) {
-                if (!dy && !dx) continue;
-                int yy = y + dy, xx = x + dx;
-                if (yy >= 0 && yy < H && xx >= 0 && xx < W && s[(size_t)yy * W + xx]) deg++;
-            }
-        v = ST_FG | (deg == 1 ? ST_END : 0) | (deg >= 3 ? ST_JUN : 0) | (deg == 2 ? ST_DEG2 : 0);
-    }
-    d[o] = v;
-}
-#endif
-
-// ------------------------------------------------------------------------------------------------
-// Ordered compaction (raster order inside a layer, layers in order): ballot + popcount inside the wave,
-// LDS across the 4 waves of a block, block offsets from an exclusive scan of per-block counts.
-// One block = 1024 consecutive pixels of the flattened [K,H,W] array (4 per thread via one dword load).
-// ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_compact_count(const u8* __restrict__ st, int64_t n, unsigned* __restrict__ counts) {
-    __shared__ unsigned wsum[4];
-    int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
-    unsigned cnt = 0;
-    if (i + 3 < n) { uint32_t w = *reinterpret_cast<const uint32_t*>(st + i); cnt = __popc(w & 0x80808080u); }        // ST_FG of four state bytes
-    else for (int j = 0; j < 4; j++) if (i + j < n && (st[i + j] & ST_FG)) cnt++;
-    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_down(cnt, o, 64);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) counts[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-}
-__global__ __launch_bounds__(256) void k_compact_write(const u8* __restrict__ st, const int* __restrict__ par, int64_t n, int H, int W,
-                                                       const unsigned* __restrict__ block_off, unsigned* __restrict__ keys, unsigned* __restrict__ lin) {
-    __shared__ unsigned wsum[4];
-    const int64_t plane = (int64_t)H * W;
-    const int Wb = (W + 1) >> 1, Hb = (H + 1) >> 1; const int64_t pplane = (int64_t)Wb * Hb * 4;
-    int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
-    unsigned f[4]; unsigned cnt = 0;
-    for (int j = 0; j < 4; j++) { f[j] = (i + j < n && (st[i + j] & ST_FG)) ? 1u : 0u; cnt += f[j]; }
-    // inclusive scan of cnt across the wave via shuffles, then across waves via LDS
-    unsigned inc = cnt;
-    const int lane = threadIdx.x & 63;
-    for (int o = 1; o < 64; o <<= 1) { unsigned t = __shfl_up(inc, o, 64); if (lane >= o) inc += t; }
-    if (lane == 63) wsum[threadIdx.x >> 6] = inc;
-    __syncthreads();
-    unsigned base = block_off[blockIdx.x];
-    for (int w = 0; w < (int)(threadIdx.x >> 6); w++) base += wsum[w];
-    unsigned pos = base + inc - cnt;
-    for (int j = 0; j < 4; j++) {
-        if (!f[j]) continue;
-        int64_t g = i + j; int layer = (int)(g / plane); int64_t p = g - (int64_t)layer * plane;
-        int y = (int)(p / W), x = (int)(p % W);
-        int id = (((y >> 1) * Wb + (x >> 1)) << 2) | ((y & 1) << 1) | (x & 1);
-        unsigned root = (unsigned)par[pplane * layer + id];
-        keys[pos] = ((unsigned)layer << 26) | root;
-        lin[pos] = (unsigned)p;
-        pos++;
-    }
-}
-
-// The same compaction from the thinned BIT planes ([K][H][Ww] words; a set bit = a skeleton pixel = ST_FG in the state plane): a thread owns a word, a
-// block 256 consecutive words of the flattened planes, i.e. the same (layer, row, column) order.  The byte form read 134 MB of state bytes at 4096^2 x 8,
-// four per thread (0.43 ms in front of the walks); the planes are 16 MB and almost empty.
 __global__ __launch_bounds__(256) void k_compact_count_bits(const unsigned long long* __restrict__ bits, size_t nwords, unsigned* __restrict__ counts) {
     __shared__ unsigned wsum[4];
     const size_t wi = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -262,7 +171,7 @@ static int excl_scan(orip_ctx* c, const T* in, T* out, size_t n, DBuf& tmp) {
 // ---- thinning_zhangsuen (04:35-99) and the state bytes on bit planes: one bit per pixel, 64 pixels per word, blockIdx.z = layer.
 // The reference numbers the neighbours from the south (P2 = (y+1, x), then clockwise as seen with y down: SW, W, NW, N, NE, E, SE);
 // A(p) counts transitions around the same cycle wherever it starts, B(p) is symmetric, only the two product conditions differ from
-// the usual orientation.  Bit-sliced evaluation as in stage 08-B (vector08.hip: k_zs_bits).
+// the usual orientation.  Bit-sliced evaluation as in stage 08-B (vector08.hip: zs_word_del).
 __global__ __launch_bounds__(256) void k_bytes_to_bits04(const u8* __restrict__ src, unsigned long long* __restrict__ bits, int H, int W, int Ww) {
     const size_t nw = (size_t)H * Ww, w0 = ((size_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 64;
     if (w0 >= nw) return;
@@ -372,35 +281,11 @@ __global__ __launch_bounds__(256) void k_bits_to_skel_state(const unsigned long 
 
 // ------------------------------------------------------------------------------------------------
 // Forced stretches (walker.h: ST_CHAIN): maximal chains of degree-2 skeleton pixels, listed when at least ORIP_CHAIN_MIN long.
-//   k_chain_ends : a degree-2 pixel with a neighbour that is not degree-2 ends a chain
+//   k_chain_ends_bits: a degree-2 pixel with a skeleton neighbour that is not degree-2 ends a chain (from the bit planes, 64 pixels at a time)
 //   k_chain_build: one thread per end pixel walks its chain (each pixel has exactly one way on); the end with the smaller pixel index
 //                  owns the chain, takes room in cpix with one atomic, walks it again and writes cpix / cref / the state flags
 // Runs on lane 0's side stream underneath the component labelling; the traces wait for it.
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_chain_ends(const u8* __restrict__ st, int H, int W, int64_t n, unsigned* __restrict__ ends, unsigned* __restrict__ n_ends, unsigned cap) {
-    const int64_t i4 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
-    if (i4 >= n) return;
-    uint32_t w4 = 0;
-    if (i4 + 3 < n) w4 = *reinterpret_cast<const uint32_t*>(st + i4); else for (int j = 0; j < 4 && i4 + j < n; j++) w4 |= (uint32_t)st[i4 + j] << (8 * j);
-    if (!(w4 & 0x04040404u)) return;
-    const int64_t plane = (int64_t)H * W;
-    for (int j = 0; j < 4; j++) {
-        if (!((w4 >> (8 * j)) & ST_DEG2)) continue;
-        const int64_t g = i4 + j; const int layer = (int)(g / plane); const int64_t p = g - (int64_t)layer * plane;
-        const int y = (int)(p / W), x = (int)(p % W);
-        const u8* s = st + plane * layer;
-        bool end = false;
-        for (int dy = -1; dy <= 1; dy++) for (int dx = -1; dx <= 1; dx++) {
-            if (!dy && !dx) continue;
-            const int yy = y + dy, xx = x + dx;
-            if (yy < 0 || yy >= H || xx < 0 || xx >= W) continue;
-            const u8 v = s[(size_t)yy * W + xx];
-            if ((v & ST_FG) && !(v & ST_DEG2)) end = true;
-        }
-        if (end) { const unsigned k = atomicAdd(n_ends, 1u); if (k < cap) ends[k] = ((unsigned)layer << 26) | (unsigned)p; }
-    }
-}
-// the same from the bit planes: a word of 64 pixels at a time -- ends = degree-2 pixels with a skeleton neighbour that is not degree-2
 __global__ __launch_bounds__(256) void k_chain_ends_bits(const unsigned long long* __restrict__ bits, const unsigned long long* __restrict__ d2bits, int H, int W, int Ww,
                                                           unsigned* __restrict__ ends, unsigned* __restrict__ n_ends, unsigned cap) {
     const size_t nw = (size_t)H * Ww, wi = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -550,56 +435,35 @@ extern "C" int orip_contours_prepare(orip_ctx* c) {
         }
         R.memo_clear[l] = true;
     }
-    // ---- thinning_zhangsuen (04:35-99): <=120 iterations of two sub-iterations, until nothing is deleted
+    // ---- thinning_zhangsuen (04:35-99): <=120 iterations of two sub-iterations, until nothing is deleted.  On bit planes (2 MB per 4096^2
+    // layer): pack, iterate, then skeleton and state bytes in one unpacking pass
     HIPC(c, c->skel.ensure(plane * K + 16));
     HIPC(c, c->tmpB.ensure(plane * K + 16));
     HIPC(c, LN(c).flags.ensure(1024));
-    int* d_changed = LN(c).flags.as<int>() + 8; (void)d_changed;
-    dim3 g2(cdiv(W, 64), cdiv(H, 4), K), block(256);
+    dim3 block(256);
     const int Wb = (W + 1) >> 1, Hb = (H + 1) >> 1; const size_t pplane = (size_t)Wb * Hb * 4;
     HIPC(c, c->tmpC.ensure(plane * K + 16));   // state bytes
-    const unsigned long long* d2_plane = nullptr;   // degree-2 pixels as a bit plane (bit-plane thinning path only)
-    if (!ORIP_VARIANT("ORIP_THIN_BYTES")) {
-        // bit planes: 2 MB per 4096^2 layer; pack, iterate, then skeleton and state bytes in one unpacking pass
-        const int Ww = (W + 63) >> 6; const size_t nw = (size_t)H * Ww;
-        HIPC(c, LN(c).vtmp[10].ensure(nw * K * 16 + 64));
-        unsigned long long* bA = LN(c).vtmp[10].as<unsigned long long>(); unsigned long long* bB = bA + nw * K;
-        dim3 gw((unsigned)cdiv((int64_t)nw, 256), 1, K);
-        if (c->edge_bits != (const void*)bA) hipLaunchKernelGGL(k_bytes_to_bits04, gw, block, 0, LN(c).stream, c->edges.as<u8>(), bA, H, W, Ww);   // stage 03 may have left them
-        c->edge_bits = nullptr;
-        // two iterations per round trip to the host, each with its own flag (an iteration after an unchanged one changes nothing either)
-        int* d_ch2 = LN(c).flags.as<int>() + 212;
-        for (int it = 0; it < 120; it += 2) {
-            HIPC(c, hipMemsetAsync(d_ch2, 0, 8, LN(c).stream));
-            for (int b = 0; b < 2; b++) {
-                { ProfScope ps(c, "k_thin_bits"); hipLaunchKernelGGL(k_thin_bits04, gw, block, 0, LN(c).stream, bA, bB, H, Ww, 0, d_ch2 + b); }
-                { ProfScope ps(c, "k_thin_bits"); hipLaunchKernelGGL(k_thin_bits04, gw, block, 0, LN(c).stream, bB, bA, H, Ww, 1, d_ch2 + b); }
-            }
-            int h_changed[2] = {0, 0};
-            HIPC(c, hipMemcpyAsync(h_changed, d_ch2, 8, hipMemcpyDeviceToHost, LN(c).stream));
-            HIPC(c, hipStreamSynchronize(LN(c).stream));
-            if (!(h_changed[0] && h_changed[1])) break;
+    const int Ww = (W + 63) >> 6; const size_t nw = (size_t)H * Ww, nwords = nw * K;
+    HIPC(c, LN(c).vtmp[10].ensure(nw * K * 16 + 64));
+    unsigned long long* bA = LN(c).vtmp[10].as<unsigned long long>(); unsigned long long* bB = bA + nw * K;
+    dim3 gw((unsigned)cdiv((int64_t)nw, 256), 1, K);
+    if (c->edge_bits != (const void*)bA) hipLaunchKernelGGL(k_bytes_to_bits04, gw, block, 0, LN(c).stream, c->edges.as<u8>(), bA, H, W, Ww);   // stage 03 may have left them
+    c->edge_bits = nullptr;
+    // two iterations per round trip to the host, each with its own flag (an iteration after an unchanged one changes nothing either)
+    int* d_ch2 = LN(c).flags.as<int>() + 212;
+    for (int it = 0; it < 120; it += 2) {
+        HIPC(c, hipMemsetAsync(d_ch2, 0, 8, LN(c).stream));
+        for (int b = 0; b < 2; b++) {
+            { ProfScope ps(c, "k_thin_bits"); hipLaunchKernelGGL(k_thin_bits04, gw, block, 0, LN(c).stream, bA, bB, H, Ww, 0, d_ch2 + b); }
+            { ProfScope ps(c, "k_thin_bits"); hipLaunchKernelGGL(k_thin_bits04, gw, block, 0, LN(c).stream, bB, bA, H, Ww, 1, d_ch2 + b); }
         }
-        { ProfScope ps(c, "k_skel_state"); hipLaunchKernelGGL(k_bits_to_skel_state, gw, block, 0, LN(c).stream, bA, c->skel.as<u8>(), c->tmpC.as<u8>(), H, W, Ww, bB); }
-        d2_plane = bB;                                   // (the second thinning plane is free now)
+        int h_changed[2] = {0, 0};
+        HIPC(c, hipMemcpyAsync(h_changed, d_ch2, 8, hipMemcpyDeviceToHost, LN(c).stream));
+        HIPC(c, hipStreamSynchronize(LN(c).stream));
+        if (!(h_changed[0] && h_changed[1])) break;
     }
-#ifdef ORIP_VARIANTS
-    else {
-        // iteration 1 reads the edges; ping-pong skel <-> tmpB so that the result always lands in skel
-        const u8* cur = c->edges.as<u8>();
-        for (int it = 0; it < 120; it++) {
-            HIPC(c, hipMemsetAsync(d_changed, 0, 4, LN(c).stream));
-            { ProfScope ps(c, "k_thin_sub"); hipLaunchKernelGGL(k_thin_sub, g2, block, 0, LN(c).stream, cur, c->tmpB.as<u8>(), H, W, 0, d_changed); }
-            { ProfScope ps(c, "k_thin_sub"); hipLaunchKernelGGL(k_thin_sub, g2, block, 0, LN(c).stream, c->tmpB.as<u8>(), c->skel.as<u8>(), H, W, 1, d_changed); }
-            cur = c->skel.as<u8>();
-            int h_changed = 0;
-            HIPC(c, hipMemcpyAsync(&h_changed, d_changed, 4, hipMemcpyDeviceToHost, LN(c).stream));
-            HIPC(c, hipStreamSynchronize(LN(c).stream));
-            if (!h_changed) break;
-        }
-        { ProfScope ps(c, "k_skel_state"); hipLaunchKernelGGL(k_skel_state, g2, block, 0, LN(c).stream, c->skel.as<u8>(), c->tmpC.as<u8>(), H, W); }
-    }
-#endif
+    // bA: the thinned planes; bB (the second thinning plane is free now): the degree-2 pixels
+    { ProfScope ps(c, "k_skel_state"); hipLaunchKernelGGL(k_bits_to_skel_state, gw, block, 0, LN(c).stream, bA, c->skel.as<u8>(), c->tmpC.as<u8>(), H, W, Ww, bB); }
     // ---- forced stretches (walker.h: ST_CHAIN), on the side stream underneath the component work below; the traces wait for ev3.
     // Sized from the skeleton of the previous prepare of this context (a resident chain repeats itself), else from the pixel count: chains
     // that do not fit are simply not listed (k_chain_build), the walker then steps through them as before.
@@ -617,28 +481,19 @@ extern "C" int orip_contours_prepare(orip_ctx* c) {
         HIPC(c, hipMemsetAsync(cpix, 0xff, (size_t)cap_cpix * 4, s2));             // sentinels everywhere, 64 of them in front of the first chain
         const unsigned init[2] = {0u, 64u};
         HIPC(c, hipMemcpyAsync(d_cn, init, 8, hipMemcpyHostToDevice, s2));
-        if (d2_plane) {
-            const int Ww = (W + 63) >> 6;
-            hipLaunchKernelGGL(k_chain_ends_bits, dim3((unsigned)cdiv((int64_t)H * Ww, 256), 1, K), block, 0, s2, LN(c).vtmp[10].as<unsigned long long>(), d2_plane, H, W, Ww, ends, d_cn, cap_ends);
-        } else hipLaunchKernelGGL(k_chain_ends, dim3(cdiv(cdiv(n, 4), 256)), block, 0, s2, c->tmpC.as<u8>(), H, W, n, ends, d_cn, cap_ends);
+        hipLaunchKernelGGL(k_chain_ends_bits, dim3((unsigned)cdiv((int64_t)H * Ww, 256), 1, K), block, 0, s2, bA, bB, H, W, Ww, ends, d_cn, cap_ends);
         hipLaunchKernelGGL(k_chain_build, dim3(cdiv(cap_ends, 64)), dim3(64), 0, s2, c->tmpC.as<u8>(), H, W, ends, d_cn, cap_ends, cpix, c->cref.as<unsigned>(), d_cn + 1, cap_cpix - 64u);
         HIPC(c, hipEventRecord(LN(c).ev3, s2));
     }
-    // ---- components (from the thinned bit planes when they exist)
+    // ---- components of the thinned bit planes
     HIPC(c, c->tmpD.ensure(pplane * K * sizeof(int)));
-    if (!ORIP_VARIANT("ORIP_THIN_BYTES") && !getenv("ORIP_CCL_BYTES")) ORIP_TRY(orip_ccl_bits(c, LN(c).vtmp[10].as<unsigned long long>(), c->tmpD.as<int>(), K));
-    else ORIP_TRY(orip_ccl(c, c->skel.as<u8>(), c->tmpD.as<int>(), K, 0));
+    ORIP_TRY(orip_ccl_bits(c, bA, c->tmpD.as<int>(), K));
     // ---- ordered compaction
-    const bool from_bits = !ORIP_VARIANT("ORIP_THIN_BYTES") && !getenv("ORIP_COMPACT_BYTES");       // the thinned bit planes are in vtmp[10]
-    const int Wwc = (W + 63) >> 6; const size_t nwc = (size_t)H * Wwc, nwords = nwc * K;
-    const unsigned long long* sk_bits = LN(c).vtmp[10].as<unsigned long long>();
-    const int nblk = from_bits ? (int)cdiv((int64_t)nwords, 256) : cdiv(n, 1024);
+    const int nblk = (int)cdiv((int64_t)nwords, 256);
     HIPC(c, LN(c).tmpE.ensure((size_t)(nblk + 1) * 2 * sizeof(unsigned) + 64));
     unsigned* d_cnt = LN(c).tmpE.as<unsigned>(); unsigned* d_boff = d_cnt + nblk + 1;
     HIPC(c, hipMemsetAsync(d_cnt + nblk, 0, sizeof(unsigned), LN(c).stream));
-    { ProfScope ps(c, "k_compact_count");
-      if (from_bits) hipLaunchKernelGGL(k_compact_count_bits, dim3(nblk), block, 0, LN(c).stream, sk_bits, nwords, d_cnt);
-      else hipLaunchKernelGGL(k_compact_count, dim3(nblk), block, 0, LN(c).stream, c->tmpC.as<u8>(), n, d_cnt); }
+    { ProfScope ps(c, "k_compact_count"); hipLaunchKernelGGL(k_compact_count_bits, dim3(nblk), block, 0, LN(c).stream, bA, nwords, d_cnt); }
     ORIP_TRY(excl_scan<unsigned>(c, d_cnt, d_boff, (size_t)nblk + 1, LN(c).tmpF));
     unsigned M = 0;
     HIPC(c, hipMemcpyAsync(&M, d_boff + nblk, sizeof(unsigned), hipMemcpyDeviceToHost, LN(c).stream));
@@ -653,9 +508,7 @@ extern "C" int orip_contours_prepare(orip_ctx* c) {
     // keys / lin (double buffers for the sort)
     HIPC(c, LN(c).vtmp[0].ensure((size_t)M * 4 * 4 + 64));
     unsigned* keys_in = LN(c).vtmp[0].as<unsigned>(); unsigned* lin_in = keys_in + M; unsigned* keys = lin_in + M; unsigned* lin = keys + M;
-    { ProfScope ps(c, "k_compact_write");
-      if (from_bits) hipLaunchKernelGGL(k_compact_write_bits, dim3(nblk), block, 0, LN(c).stream, sk_bits, c->tmpD.as<int>(), nwords, nwc, H, W, Wwc, d_boff, keys_in, lin_in);
-      else hipLaunchKernelGGL(k_compact_write, dim3(nblk), block, 0, LN(c).stream, c->tmpC.as<u8>(), c->tmpD.as<int>(), n, H, W, d_boff, keys_in, lin_in); }
+    { ProfScope ps(c, "k_compact_write"); hipLaunchKernelGGL(k_compact_write_bits, dim3(nblk), block, 0, LN(c).stream, bA, c->tmpD.as<int>(), nwords, nw, H, W, Ww, d_boff, keys_in, lin_in); }
     {
         size_t bytes = 0;
         HIPC(c, rocprim::radix_sort_pairs(nullptr, bytes, keys_in, keys, lin_in, lin, (size_t)M, 0, 30, LN(c).stream));

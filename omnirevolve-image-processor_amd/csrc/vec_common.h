@@ -596,131 +596,6 @@ __device__ __forceinline__ unsigned long long wave_min_key(unsigned long long v)
     unsigned rl = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, 63), rh = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), 63);
     return ((unsigned long long)rh << 32) | rl;
 }
-// Grid-pruned variant (same selection rule, same tie-break, n <= 11000 or so and int16 coordinates): the entry points (start of
-// every polyline, end of every polyline that may be entered reversed) are bucketed into a G x G grid held in LDS next to the end
-// points.  A greedy step scans the (2r+1)^2 cells around the cursor, r = 1, 3, 7, ...; it is final as soon as the best squared
-// distance is below the squared gap between the cursor and the nearest unscanned cell (every unscanned entry is at least that far,
-// so it can neither win nor tie), or the window covers the grid.  The chain of steps is strictly serial and a step looks at a few
-// dozen entries, so ONE wavefront runs it: no barriers, no cross-wave exchange, and no other wave competing for the SIMD.
-#ifdef ORIP_VARIANTS      // replaced variant (ORIP_NN_OLDGRID / ORIP_NN_DBG): variants build only (make variants)
-__global__ __launch_bounds__(64) void k_greedy_nn_grid(const NNEnds* __restrict__ ends, int n, const int* __restrict__ sel, int skip_if, int need_any, int rule07, int G,
-                                                        int32_t* __restrict__ order, uint8_t* __restrict__ flips, unsigned long long* __restrict__ dbg) {
-    ORIP_NN_GATE(sel, skip_if, need_any)
-    extern __shared__ __align__(16) unsigned char smem[];
-    // end points relative to the bounding-box origin (0 <= v < 2^14: differences, hence all float distances, are unchanged);
-    // bit 15 of .x = used, bit 15 of .y = closed under rule07 (entered at the start only)
-    ushort4* P = reinterpret_cast<ushort4*>(smem);                                 // (sx, sy, ex, ey)
-    unsigned* cst = reinterpret_cast<unsigned*>(P + n);                            // G*G + 1 cell starts
-    uint16_t* Eid = reinterpret_cast<uint16_t*>(cst + (G * G + 1));                // entries sorted by cell: idx << 1 | end
-    __shared__ uint16_t ring[64];                                                  // (index << 1 | flip) of the last steps: results leave in batches of 64,
-                                                                                   // a store per step would stall the chain on every later s_waitcnt vmcnt
-    const int lane = threadIdx.x;
-    // ---- bounding box
-    int mnx = 0x7fffffff, mny = 0x7fffffff, mxx = -0x7fffffff, mxy = -0x7fffffff;
-    for (int i = lane; i < n; i += 64) {
-        NNEnds e = ends[i];
-        mnx = min(mnx, min(e.sx, e.ex)); mxx = max(mxx, max(e.sx, e.ex)); mny = min(mny, min(e.sy, e.ey)); mxy = max(mxy, max(e.sy, e.ey));
-    }
-    for (int o = 32; o > 0; o >>= 1) { mnx = min(mnx, __shfl_xor(mnx, o, 64)); mny = min(mny, __shfl_xor(mny, o, 64)); mxx = max(mxx, __shfl_xor(mxx, o, 64)); mxy = max(mxy, __shfl_xor(mxy, o, 64)); }
-    const int ox = mnx, oy = mny;
-    for (int i = lane; i < n; i += 64) {
-        NNEnds e = ends[i];
-        P[i] = make_ushort4((unsigned short)((e.sx - ox) | (i == seed ? 0x8000 : 0)), (unsigned short)((e.sy - oy) | ((rule07 && e.closed) ? 0x8000 : 0)),
-                            (unsigned short)(e.ex - ox), (unsigned short)(e.ey - oy));
-    }
-    for (int i = lane; i <= G * G; i += 64) cst[i] = 0;
-    __syncthreads();
-    int sh = 0; while (((max(mxx - mnx, mxy - mny)) >> sh) >= G) sh++;                // power-of-two cells: v >> sh < G for every end point
-    const int cs = 1 << sh;
-    // ---- counting sort of the entries by cell
-    for (int i = lane; i < n; i += 64) {
-        const ushort4 e = P[i];
-        atomicAdd(&cst[((e.y & 0x7fff) >> sh) * G + ((e.x & 0x7fff) >> sh)], 1u);
-        if (!(e.y & 0x8000)) atomicAdd(&cst[(e.w >> sh) * G + (e.z >> sh)], 1u);
-    }
-    __syncthreads();
-    {   // exclusive scan of the G*G counts: a run of consecutive cells per lane
-        const int per = (G * G + 63) / 64, c0 = lane * per, c1 = min(G * G, c0 + per);
-        unsigned s = 0;
-        for (int cc = c0; cc < c1; cc++) s += cst[cc];
-        unsigned inc = s;
-        for (int o = 1; o < 64; o <<= 1) { unsigned t = __shfl_up(inc, o, 64); if (lane >= o) inc += t; }
-        unsigned run = inc - s;
-        for (int cc = c0; cc < c1; cc++) { unsigned v = cst[cc]; cst[cc] = run; run += v; }
-        if (lane == 63) cst[G * G] = inc;
-    }
-    __syncthreads();
-    for (int i = lane; i < n; i += 64) {         // scatter; cst[c] ends up as the END of cell c, i.e. start(c) = c ? cst[c-1] : 0
-        const ushort4 e = P[i];
-        Eid[atomicAdd(&cst[((e.y & 0x7fff) >> sh) * G + ((e.x & 0x7fff) >> sh)], 1u)] = (uint16_t)(i << 1);
-        if (!(e.y & 0x8000)) Eid[atomicAdd(&cst[(e.w >> sh) * G + (e.z >> sh)], 1u)] = (uint16_t)((i << 1) | 1);
-    }
-    int cx, cy;                                   // cursor, relative to the origin as well
-    { const ushort4 e = P[seed]; if (e.y & 0x8000) { cx = e.x & 0x7fff; cy = e.y & 0x7fff; } else { cx = e.z; cy = e.w; } }
-    if (lane == 0) ring[0] = (uint16_t)(seed << 1);
-    __syncthreads();
-    int prev = seed;
-    unsigned long long d_rounds = 0, d_scanned = 0, d_full = 0;
-    for (int step = 1; step < n; step++) {
-        const int gx = cx >> sh, gy = cy >> sh;
-        unsigned long long best = ~0ULL;
-        for (int r = 1;; r = 2 * r + 1) {
-            const int x0 = max(0, gx - r), x1 = min(G - 1, gx + r), y0 = max(0, gy - r), y1 = min(G - 1, gy + r);
-            unsigned long long mine = ~0ULL;
-            auto consider = [&](unsigned q) {
-                const unsigned id = Eid[q]; const int i = (int)(id >> 1);
-                const ushort4 e = P[i];
-                if ((e.x & 0x8000) || i == prev) return;
-                float v = (id & 1) ? nn_d2((int)e.z, (int)e.w, cx, cy) : nn_d2((int)(e.x & 0x7fff), (int)(e.y & 0x7fff), cx, cy);
-                unsigned long long key = ((unsigned long long)__float_as_uint(v) << 32) | (unsigned)i;
-                if (key < mine) mine = key;
-            };
-            if (y1 - y0 <= 2) {
-                // up to three rows: lanes 0..2 fetch the entry ranges of the rows, then all lanes share the concatenated entries
-                unsigned lo_l = 0, n_l = 0;
-                if (lane <= y1 - y0) { const int c0 = (y0 + lane) * G + x0, c1 = (y0 + lane) * G + x1; lo_l = c0 ? cst[c0 - 1] : 0u; n_l = cst[c1] - lo_l; }
-                const unsigned lo0 = (unsigned)__builtin_amdgcn_readlane((int)lo_l, 0), n0 = (unsigned)__builtin_amdgcn_readlane((int)n_l, 0);
-                const unsigned lo1 = (unsigned)__builtin_amdgcn_readlane((int)lo_l, 1), n1 = (unsigned)__builtin_amdgcn_readlane((int)n_l, 1);
-                const unsigned lo2 = (unsigned)__builtin_amdgcn_readlane((int)lo_l, 2), n2 = (unsigned)__builtin_amdgcn_readlane((int)n_l, 2);
-                const unsigned total = n0 + n1 + n2;
-                if (dbg) d_scanned += total;
-                for (unsigned t = lane; t < total; t += 64) consider(t < n0 ? lo0 + t : (t - n0 < n1 ? lo1 + (t - n0) : lo2 + (t - n0 - n1)));
-            } else
-            for (int row = y0; row <= y1; row++) {
-                const int c0 = row * G + x0, c1 = row * G + x1;
-                const unsigned lo = c0 ? cst[c0 - 1] : 0u, hi = cst[c1];
-                if (dbg) d_scanned += hi - lo;
-                for (unsigned q = lo + lane; q < hi; q += 64) consider(q);
-            }
-            mine = wave_min_key(mine);
-            best = mine;
-            if (dbg) d_rounds++;
-            if (x0 == 0 && y0 == 0 && x1 == G - 1 && y1 == G - 1) { if (dbg) d_full++; break; }     // everything scanned
-            if (best != ~0ULL) {
-                int gap = 0x7fff;                                                    // distance to the nearest unscanned cell, over the open sides
-                if (x0 > 0) gap = min(gap, cx - (x0 << sh) + 1);
-                if (x1 < G - 1) gap = min(gap, ((x1 + 1) << sh) - cx);
-                if (y0 > 0) gap = min(gap, cy - (y0 << sh) + 1);
-                if (y1 < G - 1) gap = min(gap, ((y1 + 1) << sh) - cy);
-                const float bd = __uint_as_float((unsigned)(best >> 32));
-                if ((double)bd * (1.0 + 1e-6) < (double)(gap * gap)) break;          // gap < 2^15: the square is exact in int
-            }
-        }
-        const int bi = (int)(best & 0xffffffffu);
-        const ushort4 e = P[bi];
-        const int sx = e.x & 0x7fff, sy = e.y & 0x7fff;
-        float ds = nn_d2(sx, sy, cx, cy), de = nn_d2((int)e.z, (int)e.w, cx, cy);
-        const bool cl = (e.y & 0x8000) != 0;
-        const bool flip = cl ? false : !(ds <= de);
-        if (lane == 0) { P[bi].x = (unsigned short)(e.x | 0x8000); ring[step & 63] = (uint16_t)((bi << 1) | (flip ? 1 : 0)); }
-        if ((step & 63) == 63) { const unsigned v = ring[lane]; order[step - 63 + lane] = (int32_t)(v >> 1); flips[step - 63 + lane] = (uint8_t)(v & 1u); }
-        if (cl || flip) { cx = sx; cy = sy; } else { cx = e.z; cy = e.w; }
-        prev = bi;
-    }
-    { const int done = n & ~63; if (done + lane < n) { const unsigned v = ring[lane]; order[done + lane] = (int32_t)(v >> 1); flips[done + lane] = (uint8_t)(v & 1u); } }
-    if (dbg && lane == 0) { dbg[0] = d_rounds; dbg[1] = d_scanned; dbg[2] = d_full; dbg[3] = (unsigned long long)cs; }
-}
-#endif
 
 // ---- descriptor-driven gather: output polyline k = src points [begin[k], begin[k]+len[k]) (reversed if rev[k]) ----
 struct GatherDesc { int64_t begin; int64_t len; int32_t rev; int32_t src; };     // src: index of the source polyline (walk-coded sources are addressed by polyline, not by point)
@@ -1216,9 +1091,15 @@ __device__ __forceinline__ int nn_asm_steps(int& cx, int& cy, int& step, unsigne
     return ev;
 }
 
-// The same search with a step written for the way a lone wave executes (one instruction per ~4.5 cycles, +16..20 cycles whenever the scalar
-// unit consumes a value produced by a vector instruction, every exec-mask juggle of divergent control flow a handful of both):
-// k_greedy_nn_grid's step compiles to ~350 instructions with divergent loops around uniform values = 1.1 us per step.  Here
+// Grid-pruned search (same selection rule, same tie-break, n <= 11000 or so and int16 coordinates): the entry points (start of every
+// polyline, end of every polyline that may be entered reversed) are bucketed into a G x G grid held in LDS next to the end points.  A greedy
+// step scans the (2r+1)^2 cells around the cursor, r = 1, 3, 7, ...; it is final as soon as the best squared distance is below the squared
+// gap between the cursor and the nearest unscanned cell (every unscanned entry is at least that far, so it can neither win nor tie), or the
+// window covers the grid.  The chain of steps is strictly serial and a step looks at a few dozen entries, so ONE wavefront runs it: no
+// barriers, no cross-wave exchange, and no other wave competing for the SIMD.
+// The step is written for the way a lone wave executes (one instruction per ~4.5 cycles, +16..20 cycles whenever the scalar unit consumes
+// a value produced by a vector instruction, every exec-mask juggle of divergent control flow a handful of both): a straightforward step
+// compiles to ~350 instructions with divergent loops around uniform values = 1.1 us per step.  Here
 //   * everything that is the same in all lanes (cursor, window, cell ranges, winner) is kept in SGPRs explicitly (v_readfirstlane);
 //   * the candidates of the 3x3 window are evaluated without branches: every lane maps its ordinal to an entry with selects, entries
 //     beyond the end take the pattern 0xffffffff; a candidate is a 2-byte entry + one 8-byte LDS read (both end points packed);
@@ -1432,9 +1313,6 @@ static int vreorder(orip_ctx* c, DPolys& src, DPolys& dst, int kind, ReorderHook
     static std::atomic<int> attr_err{0};
     std::call_once(attr_once, [] {
         orip_max_lds(k_greedy_nn_lds, 150 * 1024, attr_err);
-#ifdef ORIP_VARIANTS
-        orip_max_lds(k_greedy_nn_grid, 158 * 1024, attr_err);
-#endif
         orip_max_lds(k_greedy_nn_fast, 158 * 1024, attr_err);
     });
     if (attr_err.load()) ORIP_FAIL(c, "hipFuncSetAttribute(greedy kernels) failed: %s", hipGetErrorString((hipError_t)attr_err.load()));
@@ -1447,19 +1325,10 @@ static int vreorder(orip_ctx* c, DPolys& src, DPolys& dst, int kind, ReorderHook
     {
         ProfScope ps(c, "k_greedy_nn");
         if (grid_ok) {
-#ifdef ORIP_VARIANTS
-            unsigned long long* dbg = ORIP_VARIANT("ORIP_NN_DBG") ? LN(c).flags.as<unsigned long long>() + 64 : nullptr;
-            if (dbg || ORIP_VARIANT("ORIP_NN_OLDGRID")) {
-                hipLaunchKernelGGL(k_greedy_nn_grid, dim3(1), dim3(64), lds_grid, LN(c).stream, ends, (int)n, d_seed, 3, 0, r07, G, order, flips, dbg);
-                if (dbg) { unsigned long long h[4]; hipStreamSynchronize(LN(c).stream); hipMemcpy(h, dbg, 32, hipMemcpyDeviceToHost); fprintf(stderr, "[nn dbg] kind %d n %lld G %d cell %llu: rounds %llu scanned %llu full %llu\n", kind, (long long)n, G, h[3], h[0], h[1], h[2]); }
-            } else
-#endif
-            {
-                unsigned long long* dbg2 = getenv("ORIP_NN_DBG2") ? LN(c).flags.as<unsigned long long>() + 64 : nullptr;
-                if (dbg2) hipMemsetAsync(dbg2, 0, 80, LN(c).stream);
-                hipLaunchKernelGGL(k_greedy_nn_fast, dim3(1), dim3(64), lds_grid + 4, LN(c).stream, ends, (int)n, d_seed, 3, 0, r07, G, order, flips, getenv("ORIP_NN_NOASM") ? 1 : 0, dbg2);
-                if (dbg2) { unsigned long long h[10]; hipStreamSynchronize(LN(c).stream); hipMemcpy(h, dbg2, 80, hipMemcpyDeviceToHost); fprintf(stderr, "[nn dbg2] kind %d n %lld G %d: %llu steps by the compiled code (empty %llu, all used %llu, gap %llu; asm steps from cached candidates: one per lane %llu, two per lane %llu; with more than 128 candidates %llu), %llu asm entries, cycles asm %llu compiled %llu\n", kind, (long long)n, G, h[0], h[5], h[7], h[8], h[4], h[6], h[9], h[1], h[2], h[3]); hipMemsetAsync(dbg2, 0, 80, LN(c).stream); }
-            }
+            unsigned long long* dbg2 = getenv("ORIP_NN_DBG2") ? LN(c).flags.as<unsigned long long>() + 64 : nullptr;
+            if (dbg2) hipMemsetAsync(dbg2, 0, 80, LN(c).stream);
+            hipLaunchKernelGGL(k_greedy_nn_fast, dim3(1), dim3(64), lds_grid + 4, LN(c).stream, ends, (int)n, d_seed, 3, 0, r07, G, order, flips, getenv("ORIP_NN_NOASM") ? 1 : 0, dbg2);
+            if (dbg2) { unsigned long long h[10]; hipStreamSynchronize(LN(c).stream); hipMemcpy(h, dbg2, 80, hipMemcpyDeviceToHost); fprintf(stderr, "[nn dbg2] kind %d n %lld G %d: %llu steps by the compiled code (empty %llu, all used %llu, gap %llu; asm steps from cached candidates: one per lane %llu, two per lane %llu; with more than 128 candidates %llu), %llu asm entries, cycles asm %llu compiled %llu\n", kind, (long long)n, G, h[0], h[5], h[7], h[8], h[4], h[6], h[9], h[1], h[2], h[3]); hipMemsetAsync(dbg2, 0, 80, LN(c).stream); }
         }
         // Behind the grid kernel only ONE more launch, and a light one (256 threads, no dynamic LDS): a kernel that merely checks its flag and
         // returns still waits for a CU with room for its whole workgroup -- 0.5 ms for 1024 threads or 150 KB of LDS next to the other layers' work.

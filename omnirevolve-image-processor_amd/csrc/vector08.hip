@@ -62,17 +62,11 @@ __global__ __launch_bounds__(256) void k_compact_desc(const unsigned* __restrict
 }
 
 // ================================================================= A2: resample (08:53-64)
-// (preprocessor conditionals cannot sit inside ORIP_WITH_SRC's macro argument: the variants build's launch of the serial-chain form is a macro of its own)
-#ifdef ORIP_VARIANTS
-#define ORIP_CUM_CHAIN_LAUNCH(SRC_T) if (ORIP_VARIANT("ORIP_CUM_CHAIN")) { chain = true; hipLaunchKernelGGL((k_cumlen_long2<SRC_T, true>), dim3((unsigned)std::min<int64_t>(nk, 8192), 1), dim3(64), 0, LN(c).stream, sv, nk, step, cum, (int64_t)0, info, ord, 0, (const float*)nullptr); }
-#else
-#define ORIP_CUM_CHAIN_LAUNCH(SRC_T)
-#endif
 #define ORIP_LONG_CUM 128      // polylines above this many points get a wavefront for their cumulative lengths (k_cumlen_long2)
 struct RsInfo { int64_t n_eff; double total; unsigned m; unsigned pass; };
 // sequential float32 cumsum per polyline (np.cumsum): one lane per short polyline; long polylines (k_cumlen_long2) use one
-// wavefront: 64 segment lengths are computed / loaded by the lanes, the strictly sequential chain of float adds then runs
-// over them with v_readlane (the order of additions, and therefore every rounding, is the reference's)
+// wavefront: 64 segment lengths are computed / loaded by the lanes and summed with the roundings of the sequential chain of
+// float adds (cum_window below), so every partial sum is the reference's
 __device__ __forceinline__ void rs_finish(RsInfo& r, float acc, int64_t n, double step) {
     r.total = (double)acc;
     if (r.total <= step) { r.pass = 1; r.m = (unsigned)n; }
@@ -204,7 +198,7 @@ __device__ __forceinline__ int2 lane_succ(const int2 v, const int2 last, int lan
 // One wavefront reads one long polyline in one direction: slot-th of n_slots waves of that direction, longest polylines first (ord).
 // seg != nullptr (prefetch08): the float32 length of every segment is already there (k_seglen), so a reading costs 4 bytes per segment instead of
 // turning (polyline, index) into a point again (~25 instructions; the launches are bound by instruction issue).
-template <class Src, bool CHAIN>
+template <class Src>
 __device__ __forceinline__ void cumlen_long_wave(const Src& src, int64_t n_polys, double step, float* __restrict__ cum, int64_t rev_off, RsInfo* __restrict__ info,
                                                  const unsigned* __restrict__ ord, const bool rev, const float* __restrict__ seg, int64_t slot, int64_t n_slots, const int lane) {
     for (int64_t rr = slot; rr < n_polys; rr += n_slots) {
@@ -255,15 +249,7 @@ __device__ __forceinline__ void cumlen_long_wave(const Src& src, int64_t n_polys
 #pragma unroll
             for (int w = 0; w < 4; w++) {
                 const int64_t k = base + 64 * w + lane;
-                float pv;
-                if (CHAIN) {                                          // the strictly sequential float sums as 63 wave-shifted adds
-                    float dv = (lane == 0) ? __fadd_rn(acc, cur[w]) : cur[w];
-                    pv = dv;
-#pragma unroll
-                    for (int j = 1; j < 64; j++)
-                        pv = __fadd_rn(__int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(pv), 0x138 /* wave_shr:1 */, 0xf, 0xf, true)), dv);
-                    acc = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(pv), 63));
-                } else { pv = cum_window(cur[w], lane, cE, cM); acc = cum_state_value(cE, cM); }
+                const float pv = cum_window(cur[w], lane, cE, cM); acc = cum_state_value(cE, cM);
                 if (k < ns) s[k + 1] = pv;
             }
             lengths(base + 256, rp, rf, cur);
@@ -271,10 +257,10 @@ __device__ __forceinline__ void cumlen_long_wave(const Src& src, int64_t n_polys
         if (lane == 0) { rs_finish(r, acc, r.n_eff, step); info[rev ? n_polys + i : i] = r; }
     }
 }
-template <class Src, bool CHAIN>
+template <class Src>
 __global__ __launch_bounds__(64) void k_cumlen_long2(Src src, int64_t n_polys, double step, float* __restrict__ cum, int64_t rev_off, RsInfo* __restrict__ info, const unsigned* __restrict__ ord,
                                                      int dir0, const float* __restrict__ seg) {
-    cumlen_long_wave<Src, CHAIN>(src, n_polys, step, cum, rev_off, info, ord, ((blockIdx.y + (unsigned)dir0) & 1u) != 0, seg, blockIdx.x, gridDim.x, threadIdx.x);
+    cumlen_long_wave<Src>(src, n_polys, step, cum, rev_off, info, ord, ((blockIdx.y + (unsigned)dir0) & 1u) != 0, seg, blockIdx.x, gridDim.x, threadIdx.x);
 }
 // prefetch08: float32 length of EVERY segment of the long polylines (seg[off[i] + k] = |P(k + 1) - P(k)|, k < len(i) - 1) and the bounding box of their open
 // views (points [0, bb[i].n); bb[i] holds the first point's box on entry: k_poly_features), fully parallel: a wave takes 64 windows of 64 consecutive points
@@ -479,73 +465,12 @@ __global__ __launch_bounds__(256) void k_sample_dist(const unsigned* __restrict_
 }
 
 // ================================================================= A3: tail simulation (08:139-155)
-// The tail length is a float64 running sum with data-dependent pops: strictly sequential per polyline.  One WAVEFRONT per
-// polyline: the distances are loaded 64 at a time (coalesced) and the wave-uniform recurrence picks them out of the lanes with
-// v_readlane, for the push stream and for the pop stream; the pop counts go back to memory 64 at a time.
-__device__ __forceinline__ double rl_f64(double v, int lane) {
-    int lo = __builtin_amdgcn_readlane(__double2loint(v), lane), hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
-    return __hiloint2double(hi, lo);
-}
-#ifdef ORIP_VARIANTS      // replaced variant (ORIP_TAIL_OLDSIM): variants build only (make variants)
-__global__ __launch_bounds__(64) void k_tail_sim(const unsigned* __restrict__ sbase, int64_t n_rank, double tail_len_px, SampleArrs A, unsigned* __restrict__ npop, const unsigned* __restrict__ only) {
-    __shared__ double ring[2048];
-    __shared__ unsigned npst[1024 + 64];
-    const unsigned lane = threadIdx.x;
-    for (int64_t r = blockIdx.x; r < n_rank; r += gridDim.x) {
-        if (only && !only[r]) continue;       // only the polylines the parallel version could not decide
-        const unsigned b = sbase[r], e = sbase[r + 1];
-        if (e <= b) continue;
-        const double* D = A.dprev + b; unsigned* NP = npop + b;
-        const unsigned m = e - b;
-        // The distances pass through an LDS ring of two 1024-sample chunks (the chunk of j and the one before it) and the pop counts
-        // through an LDS stage: global memory is touched once per chunk, in bulk.  (Windows loaded from or stored to global memory
-        // inside the sample loop made the wave wait for a memory round trip every 64 samples: most of the kernel's time.)  The 64-value
-        // windows the recurrence picks from come out of the ring; a head that trails by more than a chunk reads global memory.
-        constexpr unsigned C = 1024u, RM = 2u * C - 1u;
-        auto fill = [&](unsigned c0) {           // 16 independent loads per lane in flight, then the LDS writes (slots past m: the last value, never used)
-            double tmp[16];
-#pragma unroll
-            for (int u = 0; u < 16; u++) { const unsigned idx = c0 + lane + 64u * u; tmp[u] = D[idx < m ? idx : m - 1]; }
-#pragma unroll
-            for (int u = 0; u < 16; u++) ring[(c0 + lane + 64u * u) & RM] = tmp[u];
-        };
-        auto flush = [&](unsigned c0, unsigned cnt) { for (unsigned t = lane; t < cnt; t += 64u) NP[c0 + t] = npst[t]; };
-        fill(0);
-        unsigned head = 0, jw = 0, hw = 0xffffffffu, cs = 0;
-        double dj = ring[lane], dh = 0.0;
-        double tail_len = 0.0; unsigned nv = 0;
-        for (unsigned j = 0; j < m; j++) {
-            if (j - jw == 64u) {                     // next push window
-                npst[jw - cs + lane] = nv;
-                jw += 64u;
-                if (jw - cs == C) { flush(cs, C); cs += C; fill(cs); }
-                dj = ring[(jw + lane) & RM];
-            }
-            if (j > head) tail_len = __dadd_rn(tail_len, rl_f64(dj, (int)(j - jw)));
-            while (head <= j && __builtin_amdgcn_ballot_w64(tail_len > tail_len_px) != 0) {
-                head++;
-                if (head <= j) {
-                    const unsigned w = head & ~63u;
-                    if (w != hw) {
-                        hw = w;
-                        if (w + C >= cs) dh = ring[(w + lane) & RM];                       // the chunk of j or the one before it
-                        else { const unsigned idx = w + (unsigned)lane; dh = D[idx < m ? idx : m - 1]; }
-                    }
-                    tail_len = __dsub_rn(tail_len, rl_f64(dh, (int)(head - w)));
-                } else tail_len = 0.0;
-            }
-            nv = ((unsigned)lane == (j & 63u)) ? head : nv;
-        }
-        npst[jw - cs + lane] = nv;
-        flush(cs, m - cs);
-    }
-}
-#endif
+// The tail length is a float64 running sum with data-dependent pops: strictly sequential per polyline.
 // ---- the sequential simulation, replayed.  k_tail_par leaves for every sample the head the queue WOULD have if every comparison were
 // decided by exact arithmetic; the reference decides them with a float64 running sum whose roundings depend on the whole history of pushes
 // and pops.  Given the heads, that history is a fixed list of operations (+d[j], then -d[h] for every popped h), and its value after every
-// operation is a prefix sum with SEQUENTIAL rounding -- which 64 lanes evaluate as 63 wave-shifted adds (lane i is final after step i,
-// exactly as k_cumlen_long2 could for float32).  So a wavefront replays 64 operations at a time instead of deciding one comparison per
+// operation is a prefix sum with SEQUENTIAL rounding -- which 64 lanes evaluate as 63 wave-shifted adds (lane i is final after step i).
+// So a wavefront replays 64 operations at a time instead of deciding one comparison per
 // ~400 cycles, then checks the predicted heads against the reference's loop conditions with the running values it now has (after the last
 // pop: not > T; before it: > T).  Samples up to the first one that fails the check are final; that one is decided by the plain loop, and
 // the replay goes on from there with heads that can only have moved forward (running maximum).  Whatever the prediction was, a sample
@@ -642,7 +567,7 @@ __global__ __launch_bounds__(64) void k_tail_replay(const unsigned* __restrict__
 // found by binary search.  The reference compares a float64 running sum with its own rounding history; both that sum and S[j]-S[h]
 // are within ~1e-8 px of the real sum for polylines shorter than 2^22 px (ulp(2^22) * <64 additions per scan path; 2 ulp(256) per
 // push/pop over < 2^20 samples), so a comparison that clears the threshold by more than ORIP_TAIL_EPS is the reference's decision.
-// Any sample that is closer marks its polyline, and marked polylines are redone by the sequential k_tail_sim.
+// Any sample that is closer marks its polyline, and marked polylines are redone by the sequential simulation (k_tail_replay).
 #define ORIP_TAIL_EPS 1e-6
 __global__ __launch_bounds__(256) void k_tail_par(const unsigned* __restrict__ sbase, const unsigned* __restrict__ rank, const double* __restrict__ S, unsigned MS, double T,
                                                    unsigned* __restrict__ npop, unsigned* __restrict__ redo) {
@@ -744,30 +669,6 @@ __global__ __launch_bounds__(256) void k_caps_insert(SampleArrs A, const unsigne
             if (cur == 0) { unsigned long long old = atomicCAS(&tab[hh].key, 0ULL, key[u]); if (old == 0 || old == key[u]) cur = key[u]; else cur = old; }
             if (cur == key[u]) { if (s.z > g[u]) atomicMin(&tab[hh].val, g[u]); break; }    // the minimum only decreases: a stale read can only cost a useless atomic
             hh = (hh + 1) & tmask;
-        }
-    }
-}
-__global__ __launch_bounds__(256) void k_caps_stamp(const CapSlot* __restrict__ tab, unsigned long long tsize,
-                                                     int rad, unsigned* __restrict__ firstseq, int W, int H) {
-    const int lane = threadIdx.x & 63;
-    const long long r2 = (long long)rad * rad;
-    unsigned long long wave = ((unsigned long long)blockIdx.x * 256 + threadIdx.x) >> 6, nwaves = ((unsigned long long)gridDim.x * 256) >> 6;
-    for (unsigned long long s0 = wave * 64; s0 < tsize; s0 += nwaves * 64) {
-        const uint4 sl = (s0 + lane < tsize) ? reinterpret_cast<const uint4*>(tab)[s0 + lane] : make_uint4(0u, 0u, 0u, 0u);
-        unsigned long long k = ((unsigned long long)sl.y << 32) | sl.x;
-        unsigned v = sl.z;
-        unsigned long long occ = __ballot(k != 0);
-        while (occ) {
-            int src = __ffsll((long long)occ) - 1; occ &= occ - 1;
-            unsigned long long kk = __shfl(k, src, 64) - 1ULL; unsigned seq = __shfl(v, src, 64);
-            unsigned long long a = kk >> 28, b = kk & ((1ULL << 28) - 1);
-            int x0 = (int)(a >> 14), y0 = (int)(a & 16383), x1 = (int)(b >> 14), y1 = (int)(b & 16383);
-            int bx0 = max(0, min(x0, x1) - rad), bx1 = min(W - 1, max(x0, x1) + rad), by0 = max(0, min(y0, y1) - rad), by1 = min(H - 1, max(y0, y1) + rad);
-            int bw = bx1 - bx0 + 1, bh = by1 - by0 + 1;
-            for (int i = lane; i < bw * bh; i += 64) {
-                int x = bx0 + i % bw, y = by0 + i / bw;
-                if (vs::in_capsule(x, y, x0, y0, x1, y1, r2)) atomicMin(&firstseq[(size_t)y * W + x], seq);
-            }
         }
     }
 }
@@ -1007,42 +908,10 @@ __global__ __launch_bounds__(256) void k_stamp_groups(const int64_t* __restrict_
         }
     }
 }
-// mask of the stamped raster + list of the 64x4 tiles that hold foreground (thinning only ever clears pixels, so the other tiles stay empty)
-#ifdef ORIP_VARIANTS      // replaced variant (ORIP_THIN_BYTES): variants build only (make variants)
-__global__ __launch_bounds__(256) void k_gid_to_mask(const unsigned* __restrict__ gid, u8* __restrict__ m, int H, int W, unsigned* __restrict__ tiles, unsigned* __restrict__ ntiles) {
-    int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    int fg = 0;
-    if (x < W && y < H) { size_t o = (size_t)y * W + x; fg = gid[o] ? 1 : 0; m[o] = fg ? 255 : 0; }
-    if (__syncthreads_or(fg) && threadIdx.x == 0) tiles[atomicAdd(ntiles, 1u)] = blockIdx.y * gridDim.x + blockIdx.x;
-}
-#endif
-// standard-orientation Zhang-Suen sub-iteration (08:349-366) over the listed tiles
-#ifdef ORIP_VARIANTS      // replaced variant (ORIP_THIN_BYTES): variants build only (make variants)
-__global__ __launch_bounds__(256) void k_zs_sub(const u8* __restrict__ s, u8* __restrict__ d, int H, int W, int sub, int* __restrict__ changed,
-                                                 const unsigned* __restrict__ tiles, const unsigned* __restrict__ ntiles, int gx) {
-    const unsigned nt = *ntiles;
-    for (unsigned ti = blockIdx.x; ti < nt; ti += gridDim.x) {
-        const unsigned t = tiles[ti];
-        int x = (int)(t % gx) * 64 + (threadIdx.x & 63), y = (int)(t / gx) * 4 + (threadIdx.x >> 6);
-        if (x >= W || y >= H) continue;
-        size_t o = (size_t)y * W + x;
-        u8 v = s[o];
-        if (v) {
-            auto g = [&](int dy, int dx) -> int { int yy = y + dy, xx = x + dx; return (yy >= 0 && yy < H && xx >= 0 && xx < W && s[(size_t)yy * W + xx]) ? 1 : 0; };
-            int P2 = g(-1, 0), P3 = g(-1, 1), P4 = g(0, 1), P5 = g(1, 1), P6 = g(1, 0), P7 = g(1, -1), P8 = g(0, -1), P9 = g(-1, -1);
-            int Bn = P2 + P3 + P4 + P5 + P6 + P7 + P8 + P9;
-            int A = (!P2 && P3) + (!P3 && P4) + (!P4 && P5) + (!P5 && P6) + (!P6 && P7) + (!P7 && P8) + (!P8 && P9) + (!P9 && P2);
-            bool cnd = sub == 0 ? (P2 * P4 * P6 == 0 && P4 * P6 * P8 == 0) : (P2 * P4 * P8 == 0 && P2 * P6 * P8 == 0);
-            if (A == 1 && Bn >= 2 && Bn <= 6 && cnd) { v = 0; *changed = 1; }
-        }
-        d[o] = v ? 255 : 0;
-    }
-}
-#endif
-// ---- the same thinning on bit planes (one bit per pixel, 64 pixels per word; the padded canvas is 12.8 MB, i.e. cache-resident).
-// A sub-iteration evaluates the Zhang-Suen conditions for 64 pixels at once with bit-sliced logic: the eight neighbour planes come
-// from the three rows by word shifts, B = P2+...+P9 from a carry-save adder tree, A == 1 ("exactly one 0->1 transition") from a
-// one/two accumulator.  Same conditions as k_zs_sub (08:349-366), out-of-image pixels are background.
+// ---- standard-orientation Zhang-Suen thinning (08:349-366) on bit planes (one bit per pixel, 64 pixels per word; the padded canvas is
+// 12.8 MB, i.e. cache-resident).  A sub-iteration evaluates the conditions for 64 pixels at once with bit-sliced logic: the eight neighbour
+// planes come from the three rows by word shifts, B = P2+...+P9 from a carry-save adder tree, A == 1 ("exactly one 0->1 transition") from
+// a one/two accumulator.  Out-of-image pixels are background.
 __global__ __launch_bounds__(256) void k_gid_to_bits(const unsigned* __restrict__ gid, unsigned long long* __restrict__ bits, int H, int W, int Ww) {
     // a wave packs 64 consecutive words: one coalesced 256-byte read + one ballot per word, then one coalesced write of the 64 words
     const size_t w0 = ((size_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 64, nw = (size_t)H * Ww;
@@ -1092,17 +961,6 @@ __device__ __forceinline__ unsigned long long zs_word_del(unsigned long long M, 
     const unsigned long long Aok = one & ~two;
     const unsigned long long cnd = sub == 0 ? (~(P2 & P4 & P6) & ~(P4 & P6 & P8)) : (~(P2 & P4 & P8) & ~(P2 & P6 & P8));
     return M & Aok & Bok & cnd;
-}
-__global__ __launch_bounds__(256) void k_zs_bits(const unsigned long long* __restrict__ s, unsigned long long* __restrict__ d, int H, int Ww, int sub, int* __restrict__ changed) {
-    const size_t wi = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (wi >= (size_t)H * Ww) return;
-    const int y = (int)(wi / Ww), xw = (int)(wi % Ww);
-    const unsigned long long M = s[wi];
-    if (!M) { d[wi] = 0; return; }
-    auto W64 = [&](int yy, int xx) -> unsigned long long { return (yy < 0 || yy >= H || xx < 0 || xx >= Ww) ? 0ULL : s[(size_t)yy * Ww + xx]; };
-    const unsigned long long del = zs_word_del(M, W64(y - 1, xw), W64(y - 1, xw - 1), W64(y - 1, xw + 1), W64(y, xw - 1), W64(y, xw + 1), W64(y + 1, xw), W64(y + 1, xw - 1), W64(y + 1, xw + 1), sub);
-    if (del) *changed = 1;
-    d[wi] = M & ~del;
 }
 // `iters` whole iterations (two sub-iterations each) in ONE launch: a block keeps a tile of 64 rows x 2 words plus a halo of ZS_HALO rows / one word on
 // every side in LDS and runs the sub-iterations there.  A sub-iteration reads the 3x3 neighbourhood, so after t of them the tile is exact everywhere at
@@ -1154,32 +1012,7 @@ __global__ __launch_bounds__(256) void k_zs_tile(const unsigned long long* __res
         if (y < H && xw < Ww) d[(size_t)y * Ww + xw] = empty ? 0ULL : T[cur][r][wx];
     }
 }
-// plain (linear id) union-find CCL on the padded raster
-#ifdef ORIP_VARIANTS      // replaced variant (ORIP_THIN_BYTES): variants build only (make variants)
-__global__ __launch_bounds__(256) void k_ccl2_init(const u8* __restrict__ s, int* __restrict__ L, int H, int W) {
-    int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (x >= W || y >= H) return;
-    int id = y * W + x; if (s[id]) L[id] = id;          // background parents are never read: not written either
-}
-#endif
-#ifdef ORIP_VARIANTS      // replaced variant (ORIP_THIN_BYTES): variants build only (make variants)
-__global__ __launch_bounds__(256) void k_ccl2_merge(const u8* __restrict__ s, int* __restrict__ L, int H, int W) {
-    int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (x >= W || y >= H) return;
-    int id = y * W + x;
-    if (!s[id]) return;
-    if (x > 0 && s[id - 1]) uunite(L, id, id - 1);
-    if (y > 0) {
-        if (x > 0 && s[id - W - 1]) uunite(L, id, id - W - 1);
-        if (s[id - W]) uunite(L, id, id - W);
-        if (x + 1 < W && s[id - W + 1]) uunite(L, id, id - W + 1);
-    }
-}
-#endif
-#ifdef ORIP_VARIANTS      // replaced variant (ORIP_THIN_BYTES): variants build only (make variants)
-__global__ __launch_bounds__(256) void k_ccl2_flatten(const u8* __restrict__ s, int* __restrict__ L, int n) { int i = blockIdx.x * 256 + threadIdx.x; if (i < n && s[i]) L[i] = ufind(L, i); }
-#endif
-// the same union-find driven from the thinned bit plane: a thread owns a 64-pixel word, returns at once when it is empty (the
+// plain (linear id) union-find CCL on the padded raster, driven from the thinned bit plane: a thread owns a 64-pixel word, returns at once when it is empty (the
 // skeleton fills ~1 % of the canvas) and walks its set bits otherwise.  mode 0: init, 1: merge, 2: flatten.
 __global__ __launch_bounds__(256) void k_ccl2_bits(const unsigned long long* __restrict__ bits, int* __restrict__ L, int H, int W, int Ww, int mode) {
     const size_t wi = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -1205,31 +1038,8 @@ __global__ __launch_bounds__(256) void k_ccl2_bits(const unsigned long long* __r
         if ((hasNE >> j) & 1ULL) uunite(L, id, id - W + 1);
     }
 }
-// ordered compaction of skeleton pixels (count / write), 1024 px per block
-__global__ __launch_bounds__(256) void k_sk_count(const u8* __restrict__ s, int64_t n, unsigned* __restrict__ counts) {
-    __shared__ unsigned ws[4];
-    int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4; unsigned c = 0;
-    for (int j = 0; j < 4; j++) if (i + j < n && s[i + j]) c++;
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o, 64);
-    if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) counts[blockIdx.x] = ws[0] + ws[1] + ws[2] + ws[3];
-}
-__global__ __launch_bounds__(256) void k_sk_write(const u8* __restrict__ s, const int* __restrict__ L, int64_t n, const unsigned* __restrict__ boff, unsigned* __restrict__ keys, unsigned* __restrict__ lin) {
-    __shared__ unsigned ws[4];
-    int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4; unsigned f[4], c = 0;
-    for (int j = 0; j < 4; j++) { f[j] = (i + j < n && s[i + j]) ? 1u : 0u; c += f[j]; }
-    unsigned inc = c; const int lane = threadIdx.x & 63;
-    for (int o = 1; o < 64; o <<= 1) { unsigned t = __shfl_up(inc, o, 64); if (lane >= o) inc += t; }
-    if (lane == 63) ws[threadIdx.x >> 6] = inc;
-    __syncthreads();
-    unsigned base = boff[blockIdx.x];
-    for (int w = 0; w < (int)(threadIdx.x >> 6); w++) base += ws[w];
-    unsigned pos = base + inc - c;
-    for (int j = 0; j < 4; j++) if (f[j]) { keys[pos] = (unsigned)L[i + j]; lin[pos] = (unsigned)(i + j); pos++; }
-}
-// the same ordered list from the thinned BIT plane (a word per thread, [Hp][Wwp] words; pixel index on the padded raster = y * Wp + x): 1 bit instead of
-// 1 byte per canvas pixel read, and almost every word is empty
+// ordered compaction of the skeleton pixels (count / write) from the thinned BIT plane (a word per thread, [Hp][Wwp] words; pixel index on the
+// padded raster = y * Wp + x): 1 bit per canvas pixel read, and almost every word is empty
 __global__ __launch_bounds__(256) void k_sk_count_bits(const unsigned long long* __restrict__ b, size_t nwords, unsigned* __restrict__ counts) {
     __shared__ unsigned ws[4];
     const size_t wi = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -1649,11 +1459,7 @@ static int prefetch08(orip_ctx* c, const orip_params08& P, DPolys& S, const Poly
         HIPC(c, hipEventRecord(LN(c).ev4, LN(c).stream));
         { ProfScope ps(c, "k_cumlen"); hipLaunchKernelGGL(k_cumlen2<VSrc>, dim3(cdiv(2 * n, 128)), dim3(128), 0, LN(c).stream, sS, feat07, n, step, cum, total, inf); }
         if (total > ORIP_LONG_CUM) { ProfScope ps(c, "k_cumlen_long"); const dim3 grid((unsigned)std::min<int64_t>(n, 8192), 2);       // both readings side by side
-#ifdef ORIP_VARIANTS
-            if (ORIP_VARIANT("ORIP_CUM_CHAIN")) hipLaunchKernelGGL((k_cumlen_long2<VSrc, true>), grid, dim3(64), 0, LN(c).stream, sS, n, step, cum, total, inf, ordl, 0, (const float*)seg);
-            else
-#endif
-            hipLaunchKernelGGL((k_cumlen_long2<VSrc, false>), grid, dim3(64), 0, LN(c).stream, sS, n, step, cum, total, inf, ordl, 0, (const float*)seg); }
+            hipLaunchKernelGGL(k_cumlen_long2<VSrc>, grid, dim3(64), 0, LN(c).stream, sS, n, step, cum, total, inf, ordl, 0, (const float*)seg); }
         HIPC(c, hipGetLastError());
         HIPC(c, hipEventRecord(LN(c).ev3, LN(c).stream));
     }
@@ -1772,9 +1578,7 @@ extern "C" int orip_dedup_layer(orip_ctx* c, int layer, const orip_params08* prm
         HIPC(c, hipMemcpyAsync(cumoff, kept0.p.off.p, (size_t)(nk + 1) * 8, hipMemcpyDeviceToDevice, LN(c).stream));
         { ProfScope ps(c, "k_cumlen"); ORIP_WITH_SRC(c, kept0.p, sv, { hipLaunchKernelGGL(k_cumlen<decltype(sv)>, dim3(cdiv(nk, 128)), dim3(128), 0, LN(c).stream, sv, nk, step, cum, info); }); }
         if (kept0.p.total > ORIP_LONG_CUM) { ProfScope ps(c, "k_cumlen_long"); ORIP_WITH_SRC(c, kept0.p, sv, {
-                bool chain = false;
-                ORIP_CUM_CHAIN_LAUNCH(decltype(sv))
-                if (!chain) hipLaunchKernelGGL((k_cumlen_long2<decltype(sv), false>), dim3((unsigned)std::min<int64_t>(nk, 8192), 1), dim3(64), 0, LN(c).stream, sv, nk, step, cum, (int64_t)0, info, ord, 0, (const float*)nullptr); }); }
+                hipLaunchKernelGGL(k_cumlen_long2<decltype(sv)>, dim3((unsigned)std::min<int64_t>(nk, 8192), 1), dim3(64), 0, LN(c).stream, sv, nk, step, cum, (int64_t)0, info, ord, 0, (const float*)nullptr); }); }
         }
         tick("cumlen");
         HIPC(c, hipMemsetAsync(sbase + nk + 1, 0, 4, LN(c).stream));
@@ -1794,17 +1598,13 @@ extern "C" int orip_dedup_layer(orip_ctx* c, int layer, const orip_params08* prm
             unsigned* ckin = LN(c).vtmp[5].as<unsigned>(); unsigned* ckout = ckin + MS; unsigned* cvin = ckout + MS; unsigned* cvout = cvin + MS;
             const double cell = P.grid_stride > 0 ? P.grid_stride : std::max(4.0, P.col_rad); const double inv = 1.0 / cell;
             int2* hints = (int2*)(LN(c).vtmp[5].as<uint8_t>() + (((size_t)MS * 24 + 63) & ~(size_t)63));
-            // canvas of first stamps: read at sample pixels only, so k_samples initialises exactly those and marks them in a bit plane (ORIP_CAPS_FULL: whole canvas, as before)
-            const bool bits_path = !getenv("ORIP_CAPS_FULL");
+            // canvas of first stamps: read at sample pixels only, so k_samples initialises exactly those and marks them in a bit plane
             const int Wq = (W + 63) >> 6;
             HIPC(c, LN(c).canvas.ensure((size_t)W * H * 4 + 64));
             unsigned* firstseq = LN(c).canvas.as<unsigned>();
-            unsigned long long* pixbits = nullptr;
-            if (bits_path) {
-                HIPC(c, LN(c).pixbits.ensure((size_t)Wq * H * 8 + 64));
-                pixbits = LN(c).pixbits.as<unsigned long long>();
-                HIPC(c, hipMemsetAsync(pixbits, 0, (size_t)Wq * H * 8, LN(c).stream));
-            } else HIPC(c, hipMemsetAsync(firstseq, 0xff, (size_t)W * H * 4, LN(c).stream));
+            HIPC(c, LN(c).pixbits.ensure((size_t)Wq * H * 8 + 64));
+            unsigned long long* pixbits = LN(c).pixbits.as<unsigned long long>();
+            HIPC(c, hipMemsetAsync(pixbits, 0, (size_t)Wq * H * 8, LN(c).stream));
             hipLaunchKernelGGL(k_sample_hints, dim3(cdiv(nb, 256)), dim3(256), 0, LN(c).stream, cumoff, cum, info, ord, sbase, nk, MS, step, nb, hints);
             { ProfScope ps(c, "k_samples"); ORIP_WITH_SRC(c, kept0.p, sv, { hipLaunchKernelGGL(k_samples<decltype(sv)>, dim3(cdiv(nb, 4)), dim3(256), 0, LN(c).stream, sv, cumoff, cum, info, ord, sbase, nk, MS, step, W, H, A, inv, (unsigned*)nullptr, (unsigned*)nullptr, hints, (unsigned)nb, pixbits, Wq, firstseq); }); }
             tick("samples");
@@ -1824,10 +1624,6 @@ extern "C" int orip_dedup_layer(orip_ctx* c, int layer, const orip_params08* prm
                 // the sequential redo only feeds the acceptance test (A6): it runs on the lane's side stream under the capsule / hash work
                 HIPC(c, hipEventRecord(LN(c).ev2, LN(c).stream));
                 HIPC(c, hipStreamWaitEvent(LN(c).stream2, LN(c).ev2, 0));
-#ifdef ORIP_VARIANTS
-                if (ORIP_VARIANT("ORIP_TAIL_OLDSIM")) hipLaunchKernelGGL(k_tail_sim, dim3((unsigned)std::min<int64_t>(nk, 65535)), dim3(64), 0, LN(c).stream2, sbase, nk, P.tail_len_px, A, npop, only);
-                else
-#endif
                 hipLaunchKernelGGL(k_tail_replay, dim3((unsigned)std::min<int64_t>(nk, 65535)), dim3(64), 0, LN(c).stream2, sbase, nk, P.tail_len_px, A, npop, only);
                 HIPC(c, hipEventRecord(LN(c).ev3, LN(c).stream2));
             }
@@ -1870,10 +1666,9 @@ extern "C" int orip_dedup_layer(orip_ctx* c, int layer, const orip_params08* prm
             {
                 ProfScope ps(c, "k_caps_stamp");
                 const dim3 sg((unsigned)std::min<unsigned long long>(tsize / 64 / 4 + 1, 16384));
-                if (bits_path) hipLaunchKernelGGL(k_caps_stamp_bits, sg, dim3(256), 0, LN(c).stream, tab, tsize, P.brush_forbid / 2, firstseq, W, H, pixbits, Wq, d_dist);
-                else hipLaunchKernelGGL(k_caps_stamp, sg, dim3(256), 0, LN(c).stream, tab, tsize, P.brush_forbid / 2, firstseq, W, H);
+                hipLaunchKernelGGL(k_caps_stamp_bits, sg, dim3(256), 0, LN(c).stream, tab, tsize, P.brush_forbid / 2, firstseq, W, H, pixbits, Wq, d_dist);
             }
-            caps_counted = bits_path;
+            caps_counted = true;
             tick("caps");
             // ---- A5 / A6: cheap test of every sample, then _PointHash.near for the survivors
             {
@@ -1940,88 +1735,50 @@ extern "C" int orip_dedup_layer(orip_ctx* c, int layer, const orip_params08* prm
         unsigned* gid = LN(c).canvas.as<unsigned>();
         HIPC(c, hipMemsetAsync(gid, 0, Np * 4, LN(c).stream));
         { ProfScope ps(c, "k_stamp_groups"); hipLaunchKernelGGL(k_stamp_groups, dim3(8192), dim3(256), 0, LN(c).stream, lines2.p.off.as<int64_t>(), lines2.p.pts.as<int32_t>(), n2, lines2.p.total, par, rad, gid, Wp, Hp); }
-        dim3 g2(cdiv(Wp, 64), cdiv(Hp, 4)), blk(256);
-        const size_t ntile_max = (size_t)g2.x * g2.y;
+        dim3 blk(256);
+        const size_t ntile_max = (size_t)cdiv(Wp, 64) * cdiv(Hp, 4);
         const int Wwp = (Wp + 63) >> 6; const size_t nwords = (size_t)Hp * Wwp;
         HIPC(c, LN(c).vtmp[9].ensure(Np * 2 + ntile_max * 4 + nwords * 16 + 256));
-        u8* skA = LN(c).vtmp[9].as<u8>(); u8* skB = skA + Np; unsigned* tiles = (unsigned*)(skB + ((Np + 15) & ~(size_t)15));
-        unsigned long long* bA = (unsigned long long*)(tiles + ((ntile_max + 3) & ~(size_t)3)); unsigned long long* bB = bA + nwords;
-        int* d_changed = LN(c).flags.as<int>() + 48; unsigned* d_ntiles = LN(c).flags.as<unsigned>() + 52; (void)d_changed; (void)d_ntiles;      // (byte-plane thinning: variants build)
-        if (!ORIP_VARIANT("ORIP_THIN_BYTES")) {
-            const dim3 gwd((unsigned)cdiv((int64_t)nwords, 256));
-            hipLaunchKernelGGL(k_gid_to_bits, gwd, blk, 0, LN(c).stream, gid, bA, Hp, Wp, Wwp);      // 4 waves x 64 words per block
-            tick("raster");
-            // Twelve iterations before the first round trip to the host (16-px lines thin in 9 .. 12), four per round trip after that, each iteration with
-            // its own flag: an iteration after the first unchanged one changes nothing either, so running to the end of a batch leaves the image the
-            // reference's loop stops with (48 iterations at most: the same cap)
-            int* d_chg = LN(c).flags.as<int>() + 240;
-            for (int it = 0; it < 48; ) {
-                const int nb = it == 0 ? 12 : 4;
-                HIPC(c, hipMemsetAsync(d_chg, 0, 48, LN(c).stream));
-                if (!getenv("ORIP_ZS_LAUNCHES")) {          // the whole batch in one launch, tile by tile in LDS (ORIP_ZS_LAUNCHES=1: one launch per sub-iteration, as before)
-                    ProfScope ps(c, "k_zs_sub");
-                    hipLaunchKernelGGL(k_zs_tile, dim3((unsigned)cdiv(Wwp, 2), (unsigned)cdiv(Hp, ZS_TR)), blk, 0, LN(c).stream, bA, bB, Hp, Wwp, nb, d_chg);
-                    std::swap(bA, bB);
-                } else
-                for (int b = 0; b < nb; b++) {
-                    { ProfScope ps(c, "k_zs_sub"); hipLaunchKernelGGL(k_zs_bits, gwd, blk, 0, LN(c).stream, bA, bB, Hp, Wwp, 0, d_chg + b); }
-                    { ProfScope ps(c, "k_zs_sub"); hipLaunchKernelGGL(k_zs_bits, gwd, blk, 0, LN(c).stream, bB, bA, Hp, Wwp, 1, d_chg + b); }
-                }
-                int ch[12] = {0}; ORIP_TRY(vread(c, ch, d_chg, 12));
-                bool all = true; for (int b = 0; b < nb; b++) all = all && ch[b] != 0;
-                if (!all) break;
-                it += nb;
-            }
-            hipLaunchKernelGGL(k_bits_to_mask, gwd, blk, 0, LN(c).stream, bA, skA, Hp, Wp, Wwp);
-        }
-#ifdef ORIP_VARIANTS
-        else {
-        HIPC(c, hipMemsetAsync(d_ntiles, 0, 4, LN(c).stream));
-        HIPC(c, hipMemsetAsync(skB, 0, Np, LN(c).stream));
-        hipLaunchKernelGGL(k_gid_to_mask, g2, blk, 0, LN(c).stream, gid, skA, Hp, Wp, tiles, d_ntiles);
+        // skA: skeleton bytes; bA / bB: the thinning bit planes at byte offset 2 Np + 4 ntile_max (each term rounded up), where this scratch always had them
+        u8* skA = LN(c).vtmp[9].as<u8>();
+        unsigned long long* bA = (unsigned long long*)(skA + Np + ((Np + 15) & ~(size_t)15) + ((ntile_max + 3) & ~(size_t)3) * 4); unsigned long long* bB = bA + nwords;
+        const dim3 gwd((unsigned)cdiv((int64_t)nwords, 256));
+        hipLaunchKernelGGL(k_gid_to_bits, gwd, blk, 0, LN(c).stream, gid, bA, Hp, Wp, Wwp);      // 4 waves x 64 words per block
         tick("raster");
-        const dim3 gz((unsigned)std::min<size_t>(ntile_max, 16384));
-        for (int it = 0; it < 48; it++) {
-            HIPC(c, hipMemsetAsync(d_changed, 0, 4, LN(c).stream));
-            { ProfScope ps(c, "k_zs_sub"); hipLaunchKernelGGL(k_zs_sub, gz, blk, 0, LN(c).stream, skA, skB, Hp, Wp, 0, d_changed, tiles, d_ntiles, (int)g2.x); }
-            { ProfScope ps(c, "k_zs_sub"); hipLaunchKernelGGL(k_zs_sub, gz, blk, 0, LN(c).stream, skB, skA, Hp, Wp, 1, d_changed, tiles, d_ntiles, (int)g2.x); }
-            int ch = 0; ORIP_TRY(vread(c, &ch, d_changed));
-            if (!ch) break;
+        // Twelve iterations before the first round trip to the host (16-px lines thin in 9 .. 12), four per round trip after that, each iteration with
+        // its own flag: an iteration after the first unchanged one changes nothing either, so running to the end of a batch leaves the image the
+        // reference's loop stops with (48 iterations at most: the same cap).  A batch is one launch, tile by tile in LDS.
+        int* d_chg = LN(c).flags.as<int>() + 240;
+        for (int it = 0; it < 48; ) {
+            const int nb = it == 0 ? 12 : 4;
+            HIPC(c, hipMemsetAsync(d_chg, 0, 48, LN(c).stream));
+            { ProfScope ps(c, "k_zs_sub"); hipLaunchKernelGGL(k_zs_tile, dim3((unsigned)cdiv(Wwp, 2), (unsigned)cdiv(Hp, ZS_TR)), blk, 0, LN(c).stream, bA, bB, Hp, Wwp, nb, d_chg); }
+            std::swap(bA, bB);
+            int ch[12] = {0}; ORIP_TRY(vread(c, ch, d_chg, 12));
+            bool all = true; for (int b = 0; b < nb; b++) all = all && ch[b] != 0;
+            if (!all) break;
+            it += nb;
         }
-        }
-#endif
+        hipLaunchKernelGGL(k_bits_to_mask, gwd, blk, 0, LN(c).stream, bA, skA, Hp, Wp, Wwp);
         tick("thin");
-        // components
+        // components of the thinned bit plane (bA)
         HIPC(c, LN(c).vtmp[10].ensure(Np * 4 + 64));
         int* L2 = LN(c).vtmp[10].as<int>();
-        if (!ORIP_VARIANT("ORIP_THIN_BYTES")) {      // bA holds the thinned bit plane
-            const dim3 gwd((unsigned)cdiv((int64_t)nwords, 256));
-            hipLaunchKernelGGL(k_ccl2_bits, gwd, blk, 0, LN(c).stream, bA, L2, Hp, Wp, Wwp, 0);
-            { ProfScope ps(c, "k_ccl2_merge"); hipLaunchKernelGGL(k_ccl2_bits, gwd, blk, 0, LN(c).stream, bA, L2, Hp, Wp, Wwp, 1); }
-            hipLaunchKernelGGL(k_ccl2_bits, gwd, blk, 0, LN(c).stream, bA, L2, Hp, Wp, Wwp, 2);
-        }
-#ifdef ORIP_VARIANTS
-        else {
-        hipLaunchKernelGGL(k_ccl2_init, g2, blk, 0, LN(c).stream, skA, L2, Hp, Wp);
-        { ProfScope ps(c, "k_ccl2_merge"); hipLaunchKernelGGL(k_ccl2_merge, g2, blk, 0, LN(c).stream, skA, L2, Hp, Wp); }
-        hipLaunchKernelGGL(k_ccl2_flatten, dim3(cdiv(Np, 256)), blk, 0, LN(c).stream, skA, L2, (int)Np);
-        }
-#endif
+        hipLaunchKernelGGL(k_ccl2_bits, gwd, blk, 0, LN(c).stream, bA, L2, Hp, Wp, Wwp, 0);
+        { ProfScope ps(c, "k_ccl2_merge"); hipLaunchKernelGGL(k_ccl2_bits, gwd, blk, 0, LN(c).stream, bA, L2, Hp, Wp, Wwp, 1); }
+        hipLaunchKernelGGL(k_ccl2_bits, gwd, blk, 0, LN(c).stream, bA, L2, Hp, Wp, Wwp, 2);
         tick("c:ccl");
-        const bool sk_bits = !ORIP_VARIANT("ORIP_THIN_BYTES") && !getenv("ORIP_SK_BYTES");          // the thinned bit plane is in bA
-        const int nblk = sk_bits ? (int)cdiv((int64_t)nwords, 256) : cdiv((int64_t)Np, 1024);
+        const int nblk = (int)cdiv((int64_t)nwords, 256);
         HIPC(c, LN(c).vtmp[0].ensure((size_t)(nblk + 1) * 8 + 64));
         unsigned* bc = LN(c).vtmp[0].as<unsigned>(); unsigned* bo = bc + (nblk + 1);
         HIPC(c, hipMemsetAsync(bc + nblk, 0, 4, LN(c).stream));
-        if (sk_bits) hipLaunchKernelGGL(k_sk_count_bits, dim3(nblk), blk, 0, LN(c).stream, bA, nwords, bc);
-        else hipLaunchKernelGGL(k_sk_count, dim3(nblk), blk, 0, LN(c).stream, skA, (int64_t)Np, bc);
+        hipLaunchKernelGGL(k_sk_count_bits, dim3(nblk), blk, 0, LN(c).stream, bA, nwords, bc);
         ORIP_TRY(vscan_excl<unsigned>(c, bc, bo, (size_t)nblk + 1));
         unsigned M = 0; ORIP_TRY(vread(c, &M, bo + nblk));
         if (M > 0) {
             HIPC(c, LN(c).vtmp[1].ensure((size_t)M * 16 + 64));
             unsigned* kin = LN(c).vtmp[1].as<unsigned>(); unsigned* lin_in = kin + M; unsigned* keys = lin_in + M; unsigned* lin = keys + M;
-            if (sk_bits) hipLaunchKernelGGL(k_sk_write_bits, dim3(nblk), blk, 0, LN(c).stream, bA, L2, nwords, Wp, Wwp, bo, kin, lin_in);
-            else hipLaunchKernelGGL(k_sk_write, dim3(nblk), blk, 0, LN(c).stream, skA, L2, (int64_t)Np, bo, kin, lin_in);
+            hipLaunchKernelGGL(k_sk_write_bits, dim3(nblk), blk, 0, LN(c).stream, bA, L2, nwords, Wp, Wwp, bo, kin, lin_in);
             ORIP_TRY((vsort_pairs<unsigned, unsigned>(c, kin, keys, lin_in, lin, (size_t)M, 0, 27)));
             HIPC(c, LN(c).vtmp[3].ensure((size_t)(M + 1) * 8 + 64));
             unsigned* head = LN(c).vtmp[3].as<unsigned>(); unsigned* hs = head + (M + 1);

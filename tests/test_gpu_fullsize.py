@@ -7,8 +7,8 @@
 
 Size-independent properties, no oracle involved:
 
-* schedule independence: the per-layer pipelines (default), one-layer-at-a-time execution and the single-workgroup
-  k-means must all produce byte-identical lines, taps and ops for every layer (checksums of every artefact);
+* schedule independence: the per-layer pipelines (default), one-layer-at-a-time execution and every fallback path forced
+  at once must all produce byte-identical lines, taps and ops for every layer (checksums of every artefact);
 * stage 04: every contour point is a skeleton pixel of its layer, consecutive points are 8-neighbours, >= 5 points (04:224);
 * stage 05: every scaled point lies inside the margins of the canvas (05:63-96);
 * stage 12: the ops of a layer are a permutation of its lines (each exactly once, possibly flipped) and taps (12:85-187).
@@ -51,18 +51,16 @@ def _digest(dev, cfg):
     return out
 
 
-# paths the default library takes where the fast kernels do not apply (forced here); VARIANT_SWITCHES select replaced kernels that only the variants
-# build carries (`make -C csrc variants`, ORIP_LIB_VARIANTS=1) and read as not set with the default library
-FALLBACK_SWITCHES = ("ORIP_TAIL_SEQ", "ORIP_NN_NOGRID", "ORIP_PLOT_1WG", "ORIP_TAPS_1WG", "ORIP_MORPH_BYTES", "ORIP_CCL_BYTES", "ORIP_HASH_SORT", "ORIP_NO_CHAINS",
-                     "ORIP_NO_PREFETCH08", "ORIP_CAPS_FULL", "ORIP_CAPPREV_SCAN", "ORIP_NN_NOASM", "ORIP_ARC_POINTS", "ORIP_ZS_LAUNCHES")
-VARIANT_SWITCHES = ("ORIP_KMEANS_1WG", "ORIP_THIN_BYTES", "ORIP_CUM_CHAIN")
+# paths the default library takes where the fast kernels do not apply (forced here)
+FALLBACK_SWITCHES = ("ORIP_TAIL_SEQ", "ORIP_NN_NOGRID", "ORIP_PLOT_1WG", "ORIP_TAPS_1WG", "ORIP_MORPH_BYTES", "ORIP_HASH_SORT", "ORIP_NO_CHAINS",
+                     "ORIP_NO_PREFETCH08", "ORIP_CAPPREV_SCAN", "ORIP_NN_NOASM", "ORIP_ARC_POINTS")
 
 
 def _digests_under(dev, cfg, img, monkeypatch, envs):
     from orip import parallel as P
     digests = []
     for env in envs:
-        for k in ("ORIP_SERIAL_LAYERS",) + FALLBACK_SWITCHES + VARIANT_SWITCHES:
+        for k in ("ORIP_SERIAL_LAYERS",) + FALLBACK_SWITCHES:
             monkeypatch.delenv(k, raising=False)
         for k in env:
             monkeypatch.setenv(k, "1")
@@ -76,17 +74,6 @@ def test_schedules_and_kernel_variants_agree(setup, monkeypatch):
     dev, cfg, img = setup
     digests = _digests_under(dev, cfg, img, monkeypatch, [(), ("ORIP_SERIAL_LAYERS",), FALLBACK_SWITCHES])
     assert digests[0] == digests[1] == digests[2]
-
-
-def test_replaced_kernel_variants_agree(setup, monkeypatch):
-    """The replaced kernels of the variants build (one-workgroup k-means, byte-plane thinning, serial cumulative-length chain) give the same
-    artefacts as the default kernels.  With the default library their switches read as not set."""
-    from orip import lib as L
-    if not L.has_variants():
-        pytest.skip("variants build not loaded")
-    dev, cfg, img = setup
-    digests = _digests_under(dev, cfg, img, monkeypatch, [(), FALLBACK_SWITCHES + VARIANT_SWITCHES])
-    assert digests[0] == digests[1]
 
 
 def test_contours_lie_on_the_skeleton_and_scaled_points_on_the_canvas(setup):

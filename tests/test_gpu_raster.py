@@ -63,37 +63,15 @@ def _kmeans_cases():
             (np.repeat(rng.integers(0, 256, (3, 1, 3), dtype=np.uint8), 4000, axis=1).reshape(100, 120, 3), 6)]
 
 
-def test_kmeans_both_kernels_agree(dev, monkeypatch):
+def test_kmeans_both_kernels_agree(dev):
     """The fit runs spread over groups of 64 workgroups with a device-wide barrier each: the oracle's centres, also with a cluster that
-    empties.  (The single-workgroup version it replaced: test_kmeans_1wg_variant_agrees.)"""
-    monkeypatch.delenv("ORIP_KMEANS_1WG", raising=False)
+    empties."""
     for img, K in _kmeans_cases():
         dev.set_image(np.ascontiguousarray(img))
         a, _ = dev.kmeans_fit(None, K)
         lab = O.bgr2lab(np.ascontiguousarray(img)).reshape(-1, 3).astype(np.float32)
         want, _ = O.kmeans(lab, K)
         assert np.array_equal(a, want)
-
-
-def test_kmeans_1wg_variant_agrees(dev, monkeypatch):
-    """The single-workgroup fit is kept behind ORIP_KMEANS_1WG in the variants build only (`make -C csrc variants`, ORIP_LIB_VARIANTS=1): same
-    centres and the same compactness (fixed reduction tree) as the default fit, and the oracle's centres.  With the default library the switch
-    reads as not set and the comparison would hold a kernel against itself."""
-    from orip import lib as L
-    if not L.has_variants():
-        pytest.skip("variants build not loaded")
-    for img, K in _kmeans_cases():
-        dev.set_image(np.ascontiguousarray(img))
-        monkeypatch.delenv("ORIP_KMEANS_1WG", raising=False)
-        a, ca = dev.kmeans_fit(None, K)
-        monkeypatch.setenv("ORIP_KMEANS_1WG", "1")
-        b, cb = dev.kmeans_fit(None, K)
-        monkeypatch.delenv("ORIP_KMEANS_1WG", raising=False)
-        assert np.array_equal(a, b)
-        assert ca == cb
-        lab = O.bgr2lab(np.ascontiguousarray(img)).reshape(-1, 3).astype(np.float32)
-        want, _ = O.kmeans(lab, K)
-        assert np.array_equal(b, want)
 
 
 @pytest.mark.parametrize("case", [(128, 128, 4, None), (255, 193, 8, 4.0), (512, 512, 8, None), (64, 1030, 3, 2.0)])

@@ -245,27 +245,12 @@ def _long_polylines_case():
     return polys, cfgd, cfg
 
 
-def test_stage08_cumulative_lengths_long_polylines(dev, monkeypatch):
+def test_stage08_cumulative_lengths_long_polylines(dev):
     """np.cumsum of float32 segment lengths (08:58) for polylines long enough for the wave kernels: the integer-scan form (binade by binade,
     real float adds only at binade crossings and round-half ties) must give the oracle's lines."""
     from orip import stages as S
     polys, cfgd, cfg = _long_polylines_case()
     want_l, want_t = O.stage08_layer(polys, O.derived08(cfgd))
-    monkeypatch.delenv("ORIP_CUM_CHAIN", raising=False)
-    got_l, got_t = S.dedup_layer(polys, cfg, dev)
-    assert got_t == want_t
-    assert same_polys(got_l, want_l), (len(got_l), len(want_l))
-
-
-def test_stage08_cumulative_lengths_chain_variant(dev, monkeypatch):
-    """The serial chain of wave-shifted adds that the integer-scan form replaced (ORIP_CUM_CHAIN, variants build only: with the default library
-    the switch reads as not set and this would compare the scan form with itself) gives the oracle's lines as well."""
-    from orip import lib as L, stages as S
-    if not L.has_variants():
-        pytest.skip("variants build not loaded")
-    polys, cfgd, cfg = _long_polylines_case()
-    want_l, want_t = O.stage08_layer(polys, O.derived08(cfgd))
-    monkeypatch.setenv("ORIP_CUM_CHAIN", "1")
     got_l, got_t = S.dedup_layer(polys, cfg, dev)
     assert got_t == want_t
     assert same_polys(got_l, want_l), (len(got_l), len(want_l))

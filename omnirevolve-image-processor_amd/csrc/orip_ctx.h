@@ -114,14 +114,75 @@ struct DTaps {
 
 struct ProfEntry { double ms = 0; int64_t launches = 0; };
 
+// One device scratch layout, stated once: take() registers typed arrays in order, commit() sizes the buffer (the arrays, their alignment padding and
+// `tail` bytes of slack that wide loads past the last element may touch) and assigns every pointer.  An array starts at a multiple of max(16, alignof(T),
+// align); arrays that a kernel or one read-back addresses from a common base are ONE take.  No heap; at most CAP arrays.
+struct Carve { enum { CAP = 16 };
+    struct { void* pp; size_t off; } slot[CAP]; int n = 0; size_t total = 0;
+    template <class T> void take(T*& ptr, size_t count, size_t align = 16) {
+        if (alignof(T) > align) align = alignof(T);
+        total = (total + align - 1) / align * align;
+        if (n < CAP) { slot[n].pp = &ptr; slot[n].off = total; }
+        n++; total += count * sizeof(T);
+    }
+    template <class... T> void each(size_t count, T*&... ptrs) { (take(ptrs, count), ...); }      // several arrays of one length
+    hipError_t commit(DBuf& buf, size_t tail_bytes) {
+        const hipError_t e = n > CAP ? hipErrorInvalidValue : buf.ensure(total + tail_bytes);
+        for (int i = 0; e == hipSuccess && i < n; i++) { void* a = (char*)buf.p + slot[i].off; memcpy(slot[i].pp, &a, sizeof a); }
+        return e;
+    }
+};
+
+// Every word of LaneRes::flags: small device-side results (counts, change / overflow flags) that the host reads back or a later kernel of the same call
+// consumes.  Each use has its own member, so two uses never share bytes; nothing aliases on purpose.  orip_create allocates and zeroes the buffer of every
+// lane (all lanes exist from then on), but NO use relies on that zero: each word below is cleared, copied or written whole by its own call before it is read.
+struct LaneFlags {
+    // lane 0: raster stages
+    int not_binary;                                         // 02 orip_morph_open_close: some byte of an explicit mask is neither 0 nor 255
+    uint8_t palette[ORIP_MAX_LAYERS * 3];                   // 02 orip_assign_palette: the K RGB triples
+    alignas(8) unsigned long long palette_counts[ORIP_MAX_LAYERS];   // 02 orip_assign_palette: pixels per label
+    alignas(8) unsigned long long label_counts[ORIP_MAX_LAYERS];     // 02 orip_extract_layers: pixels per label
+    int thin_changed[2];                                    // 04 prepare: per thinning iteration of a batch, something was deleted
+    unsigned chain_counts[2];                               // 04 prepare (side stream): {chain ends, cpix entries}
+    // layer lanes
+    int trace_overflow;                                     // 04 trace: a log ran full (set by k_trace, read by trace_finish -- possibly in a later call)
+    int nn_seed[2];                                         // vreorder (07 / 08 / 10 on its lane): seed polyline, coordinate-range flags
+    alignas(8) unsigned long long nn_dbg2[10];              // vreorder: ORIP_NN_DBG2 counters of the grid greedy
+    int caps_overflow;                                      // 08-A4: the capsule table ran full
+    unsigned caps_distinct;                                 // 08-A4: distinct capsules (read back at the end of orip_dedup_layer -> caps_hint)
+    unsigned accept_survivors;                              // 08-A5: samples the cheap test leaves for the near test
+    alignas(8) unsigned long long accept_work;              // 08-A5: candidate pairs of the direct near test
+    int zs_changed[12];                                     // 08-B: per thinning iteration of a batch, something was deleted
+    unsigned comp_counts[3];                                // 08-B: work-list cursors of the three component classes
+    int taps_kept;                                          // 10 (ORIP_LANE_CROSS): sequential taps accepted
+    int plot_ops;                                           // 12: ops written
+};
+static_assert(sizeof(LaneFlags) <= 4096, "LaneRes::flags is 4096 bytes, allocated and zeroed by orip_create");
+
 // Per-lane resources.  Lane 0 serves the raster stages and the cross-layer stage 10; lane l+1 serves the per-layer vector
 // stages (05, 07, 08, 12) of layer l, so that different layers can be driven concurrently from different host threads,
 // each on its own HIP stream with its own scratch (the serial kernels of one layer then overlap with those of the others).
+// Lifetimes.  A buffer is FREE BETWEEN ENTRY POINTS (any call on the lane may resize and overwrite it) unless this table names it; a named vtmp slot is only
+// ever indexed by its constant on that lane.
+//   lane 0  vtmp[VT0_MEMO]       memo planes of the walker     orip_contours_reserve (cleared there) or orip_contours_prepare -> last trace of the prepare
+//   lane 0  vtmp[VT0_EDGE_BITS]  bit planes of `edges`         orip_detect_edges (c->edge_bits) -> the next orip_contours_prepare, which thins in them
+//   lane 0  vtmp[VT0_KEYS, VT0_COMP_START, VT0_ORDER, VT0_LOG_USED, VT0_WINFO]  the stage-04 schedule (Prep04::A, Prep04::order: keys / lin of the skeleton, first
+//           pixel of each component, largest-first component order, log entries used per component, two WalkInfo per pixel): orip_contours_prepare -> the last
+//           orip_contours_layer of that prepare (every layer's k_trace / trace_finish reads them from its own lane); orip_contours_invalidate ends the lifetime
+//   lane l+1 vtmp[VTL_STEPLOG], flags.trace_overflow  step log and overflow flag of the layer's trace: trace_launch (orip_contours_prepare, or
+//           orip_contours_layer) -> trace_finish (orip_contours_layer).  Stage 08-B takes the same slot: it must not run on the lane in between
+//   lane l+1 vtmp[VT_LEAVES], tmpF  perimeter leaves and sort scratch of Prefetch08: side-stream work of orip_sort_contours -> ev4 (split_small) or
+//           orip_pf08_drain of the next call (the main stream of orip_sort_contours itself goes behind ev4 before it uses tmpF again)
+//   lane l+1 pf08.*              own buffers of Prefetch08; src_off points into the SCALED list's offsets (c->polys), valid while pf08.tag matches the list's pf_tag
+//   ORIP_LANE_CROSS canvas       forbidden raster of stage 10  orip_dedup_cross_begin (cleared there) -> the last orip_dedup_cross_layer* call of that pass
+//   Everything else -- tp[], pixbits, tmpE, canvas on the other lanes, the other vtmp slots, the rest of flags -- is free between entry points.
+enum { VT0_KEYS = 0, VT0_COMP_START = 2, VT0_ORDER = 3, VT0_MEMO = 6, VT0_LOG_USED = 7, VT0_WINFO = 8, VT0_EDGE_BITS = 10,     // lane 0
+       VTL_STEPLOG = 9, VT_LEAVES = 11 };       // layer lanes (VT_LEAVES: wherever vfeatures runs -- its perimeter leaves, and those of the stage-08 prefetch)
 struct LaneRes {
     hipStream_t stream = 0;
     hipStream_t stream2 = 0;              // side stream of the lane (work that may overlap the main chain), fenced with ev2 / ev3
     hipEvent_t ev2 = nullptr, ev3 = nullptr, ev4 = nullptr;   // (ev4 / ev3: features / everything of stage 08's prefetch)
-    DBuf vtmp[12], tmpE, tmpF, flags, canvas;
+    DBuf vtmp[12], tmpE, tmpF, flags, canvas;             // flags: one LaneFlags
     DBuf pixbits;                         // stage 08-A: one bit per canvas pixel that is the rounded position of a sample
     unsigned caps_hint = 0;               // distinct capsules of the lane's last stage-08-A run (sizes the next run's table)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -219,6 +280,16 @@ inline hipError_t orip_pf08_drain(orip_ctx* c) {           // the claimed lane's
     return hipStreamWaitEvent(l.stream, l.ev3, 0);
 }
 inline LaneGuard::~LaneGuard() { if (ok) orip_tls_lane = prev; if (owner) c->lane_owner[lane].store(0); }
+// lane 0's vtmp[VT0_EDGE_BITS]: two sets of bit planes, `nwords` words each.  Stage 03 leaves the edges in the first; stage 04 thins between the two.
+static inline hipError_t orip_edge_planes(orip_ctx* c, size_t nwords, unsigned long long*& a, unsigned long long*& b) {
+    Carve L; L.each(nwords, a, b); return L.commit(LN(c).vtmp[VT0_EDGE_BITS], 64);
+}
+// rocPRIM's query-then-run idiom, spelled once: run(tmp, bytes) is called with tmp == nullptr to learn the size, the lane's tmpF grows to it, then it runs
+template <class F> static inline hipError_t orip_with_tmp(orip_ctx* c, F&& run) {
+    size_t bytes = 0; hipError_t e = run((void*)nullptr, bytes);
+    if (e == hipSuccess) e = LN(c).tmpF.ensure(bytes + 16);
+    return e == hipSuccess ? run(LN(c).tmpF.p, bytes) : e;
+}
 
 #if defined(__HIPCC__)
 // one bit per pixel -> 0 / 255 bytes, 16 pixels (ONE 16-byte store) per thread: rows that are multiples of 64 wide (nw words per plane = H * W / 64),

@@ -644,7 +644,7 @@ int orip_morph_open_close(orip_ctx* c, const u8* src, u8* dst, int K, int shape,
     const bool have_bits = !labels_mode && c->mask_bits != nullptr && src == c->masks.as<u8>() && !getenv("ORIP_MORPH_BYTES");   // stage 02 left them
     bool binary = labels_mode || have_bits;
     if (!binary && !getenv("ORIP_MORPH_BYTES")) {
-        int* d_flag = LN(c).flags.as<int>() + 12;
+        int* d_flag = &LN(c).flags.as<LaneFlags>()->not_binary;
         HIPC(c, hipMemsetAsync(d_flag, 0, 4, LN(c).stream));
         hipLaunchKernelGGL(k_not_binary, dim3((unsigned)cdiv((int64_t)(plane * K), 4096)), dim3(256), 0, LN(c).stream, src, plane * K, d_flag);
         int h = 1; HIPC(c, hipMemcpyAsync(&h, d_flag, 4, hipMemcpyDeviceToHost, LN(c).stream)); HIPC(c, hipStreamSynchronize(LN(c).stream));
@@ -740,8 +740,7 @@ static int kmeans_fit_impl(orip_ctx* c, bool rgb, const int64_t* sample_idx, int
         hipLaunchKernelGGL(k_lab_gather, dim3(std::min<int64_t>(2048, cdiv(N, 256))), dim3(256), 0, LN(c).stream, c->image.as<u8>(),
                            sample_idx ? c->tmpC.as<int64_t>() : nullptr, N, c->tmpB.as<u8>(), c->lab_tabs.as<LabTabs>());
     }
-    HIPC(c, c->tmpD.ensure((size_t)N * 4 * 4 + 256));     // (later stages find tmpD and the lane's flags at least this large: some
-    HIPC(c, LN(c).flags.ensure(1024));                      // users of the flags do not ensure them themselves)
+    HIPC(c, c->tmpD.ensure((size_t)N * 4 * 4 + 256));     // (later stages find tmpD at least this large)
     attempts = std::max(attempts, 1);
     double epsilon = std::max(eps, 0.0); epsilon *= epsilon;
     int maxCount = std::min(std::max(max_iter, 2), 100);
@@ -792,8 +791,7 @@ extern "C" int orip_assign_palette(orip_ctx* c, const uint8_t* palette_rgb, int 
     const int64_t npx = (int64_t)c->H * c->W;
     hipStream_t s = LN(c).stream;
     HIPC(c, c->labels.ensure((size_t)npx + 16));
-    HIPC(c, LN(c).flags.ensure(1024));
-    u8* d_pal = (u8*)LN(c).flags.p + 768;
+    LaneFlags* fl = LN(c).flags.as<LaneFlags>(); u8* d_pal = fl->palette;
     HIPC(c, hipMemcpyAsync(d_pal, palette_rgb, (size_t)K * 3, hipMemcpyHostToDevice, s));
     {
         ProfScope ps(c, "k_assign_palette");
@@ -801,8 +799,8 @@ extern "C" int orip_assign_palette(orip_ctx* c, const uint8_t* palette_rgb, int 
     }
     HIPC(c, hipGetLastError());
     if (counts_out) {
-        unsigned long long* d_counts = (unsigned long long*)((char*)LN(c).flags.p + 512);
-        HIPC(c, hipMemsetAsync(d_counts, 0, sizeof(unsigned long long) * ORIP_MAX_LAYERS, s));
+        unsigned long long* d_counts = fl->palette_counts;
+        HIPC(c, hipMemsetAsync(d_counts, 0, sizeof(LaneFlags::palette_counts), s));
         hipLaunchKernelGGL(k_count_labels, dim3(512), dim3(256), 0, s, c->labels.as<u8>(), npx, d_counts);
         unsigned long long h[ORIP_MAX_LAYERS];
         HIPC(c, hipMemcpyAsync(h, d_counts, sizeof(h), hipMemcpyDeviceToHost, s));
@@ -839,8 +837,7 @@ extern "C" int orip_extract_layers(orip_ctx* c, const float* centers, int K, int
     }
     HIPC(c, hipGetLastError());
     if (counts_out) {
-        HIPC(c, LN(c).flags.ensure(1024));
-        unsigned long long* d_cnt = (unsigned long long*)((char*)LN(c).flags.p + 768);
+        unsigned long long* d_cnt = LN(c).flags.as<LaneFlags>()->label_counts;
         HIPC(c, hipMemsetAsync(d_cnt, 0, ORIP_MAX_LAYERS * 8, LN(c).stream));
         hipLaunchKernelGGL(k_count_labels, dim3(1024), dim3(256), 0, LN(c).stream, c->labels.as<u8>(), npx, d_cnt);
         unsigned long long h[ORIP_MAX_LAYERS];

@@ -331,10 +331,9 @@ extern "C" int orip_detect_edges(orip_ctx* c, int morph_k, int open_iters, int c
     // candidates are ~2 % of the pixels: NMS leaves two bit planes (candidate, strong); components, strong roots and edges are
     // computed from words; the edge bit planes stay for stage 04's thinning
     const int Ww = (W + 63) >> 6; const size_t nw = (size_t)H * Ww;
-    HIPC(c, LN(c).vtmp[11].ensure(nw * K * 16 + 64));
-    HIPC(c, LN(c).vtmp[10].ensure(nw * K * 16 + 64));
-    unsigned long long* cand = LN(c).vtmp[11].as<unsigned long long>(); unsigned long long* strong = cand + nw * K;
-    unsigned long long* ebits = LN(c).vtmp[10].as<unsigned long long>();
+    unsigned long long *cand, *strong, *ebits, *thin2;
+    { Carve L; L.each(nw * K, cand, strong); HIPC(c, L.commit(LN(c).vtmp[11], 64)); }
+    HIPC(c, orip_edge_planes(c, nw * K, ebits, thin2));      // (thin2: stage 04's second thinning plane, sized here so that the buffer stays where it is)
     if (nms_from_bits && c->morphed_bits) {
         ProfScope ps(c, "k_blur_sobel_nms");
         hipLaunchKernelGGL(k_nms_bits3, dim3(cdiv(W, NB_TX), cdiv(H, NB_TY), K), block, 0, LN(c).stream, (const unsigned long long*)c->morphed_bits, H, W, Ww, low, high, cand, strong);

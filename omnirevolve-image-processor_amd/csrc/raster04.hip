@@ -156,17 +156,6 @@ __global__ __launch_bounds__(64) void k_vown(WalkArgs A, const unsigned* __restr
     }
 }
 
-// ------------------------------------------------------------------------------------------------
-// rocPRIM helpers
-// ------------------------------------------------------------------------------------------------
-template <class T>
-static int excl_scan(orip_ctx* c, const T* in, T* out, size_t n, DBuf& tmp) {
-    size_t bytes = 0;
-    HIPC(c, rocprim::exclusive_scan(nullptr, bytes, in, out, T(0), n, rocprim::plus<T>(), LN(c).stream));
-    HIPC(c, tmp.ensure(bytes + 16));
-    HIPC(c, rocprim::exclusive_scan(tmp.p, bytes, in, out, T(0), n, rocprim::plus<T>(), LN(c).stream));
-    return 0;
-}
 
 // ---- thinning_zhangsuen (04:35-99) and the state bytes on bit planes: one bit per pixel, 64 pixels per word, blockIdx.z = layer.
 // The reference numbers the neighbours from the south (P2 = (y+1, x), then clockwise as seen with y down: SW, W, NW, N, NE, E, SE);
@@ -394,7 +383,7 @@ __global__ __launch_bounds__(256) void k_kept_slots_base(const unsigned* __restr
 // sorted by component, the per-layer schedule.  Runs on lane 0 and ends synchronised.
 // Hint for the resident chain: the image is set and K layers will be traced.  Clears the K memo planes on the layer lanes NOW -- at the start of a
 // step the card is idle but for the k-means fit, whereas 4 GB of fills issued from orip_contours_prepare run into stages 02 / 03 -- and
-// orip_contours_prepare then skips its own clearing.  Nothing else touches lane 0's vtmp[6] in between.
+// orip_contours_prepare then skips its own clearing (the planes' lifetime: orip_ctx.h, LaneRes).
 extern "C" int orip_contours_reserve(orip_ctx* c, int K) {
     orip_enter(c);
     if (!c->image.p || c->H <= 0 || c->W <= 0) ORIP_FAIL(c, "no image set");
@@ -402,10 +391,10 @@ extern "C" int orip_contours_reserve(orip_ctx* c, int K) {
     ORIP_TRY(orip_contours_invalidate(c));
     const size_t plane = (size_t)c->H * c->W;
     c->memo_pre_K = 0;
-    HIPC(c, LN(c).vtmp[6].ensure(plane * (size_t)K * 8 * 4 + 64));
+    HIPC(c, LN(c).vtmp[VT0_MEMO].ensure(plane * (size_t)K * 8 * 4 + 64));
     for (int l = 0; l < K; l++) {
         ORIP_LANE(c, l + 1);
-        HIPC(c, hipMemsetAsync(c->ln[0].vtmp[6].as<unsigned>() + plane * 8 * l, 0, plane * 8 * 4, LN(c).stream));
+        HIPC(c, hipMemsetAsync(c->ln[0].vtmp[VT0_MEMO].as<unsigned>() + plane * 8 * l, 0, plane * 8 * 4, LN(c).stream));
     }
     c->memo_pre_K = K; c->memo_pre_H = c->H; c->memo_pre_W = c->W;
     return 0;
@@ -427,11 +416,11 @@ extern "C" int orip_contours_prepare(orip_ctx* c) {
     // every layer's trace: by orip_contours_reserve at the start of the step when the caller gave that hint, else now, underneath the raster work below
     const bool pre = c->memo_pre_K >= K && c->memo_pre_H == H && c->memo_pre_W == W;
     c->memo_pre_K = 0;
-    HIPC(c, LN(c).vtmp[6].ensure(plane * (size_t)K * 8 * 4 + 64));
+    HIPC(c, LN(c).vtmp[VT0_MEMO].ensure(plane * (size_t)K * 8 * 4 + 64));
     for (int l = 0; l < K; l++) {
         if (!pre) {
             ORIP_LANE(c, l + 1);
-            HIPC(c, hipMemsetAsync(c->ln[0].vtmp[6].as<unsigned>() + plane * 8 * l, 0, plane * 8 * 4, LN(c).stream));
+            HIPC(c, hipMemsetAsync(c->ln[0].vtmp[VT0_MEMO].as<unsigned>() + plane * 8 * l, 0, plane * 8 * 4, LN(c).stream));
         }
         R.memo_clear[l] = true;
     }
@@ -439,18 +428,18 @@ extern "C" int orip_contours_prepare(orip_ctx* c) {
     // layer): pack, iterate, then skeleton and state bytes in one unpacking pass
     HIPC(c, c->skel.ensure(plane * K + 16));
     HIPC(c, c->tmpB.ensure(plane * K + 16));
-    HIPC(c, LN(c).flags.ensure(1024));
+    LaneFlags* fl = LN(c).flags.as<LaneFlags>();
     dim3 block(256);
     const int Wb = (W + 1) >> 1, Hb = (H + 1) >> 1; const size_t pplane = (size_t)Wb * Hb * 4;
     HIPC(c, c->tmpC.ensure(plane * K + 16));   // state bytes
     const int Ww = (W + 63) >> 6; const size_t nw = (size_t)H * Ww, nwords = nw * K;
-    HIPC(c, LN(c).vtmp[10].ensure(nw * K * 16 + 64));
-    unsigned long long* bA = LN(c).vtmp[10].as<unsigned long long>(); unsigned long long* bB = bA + nw * K;
+    unsigned long long *bA, *bB;
+    HIPC(c, orip_edge_planes(c, nwords, bA, bB));
     dim3 gw((unsigned)cdiv((int64_t)nw, 256), 1, K);
     if (c->edge_bits != (const void*)bA) hipLaunchKernelGGL(k_bytes_to_bits04, gw, block, 0, LN(c).stream, c->edges.as<u8>(), bA, H, W, Ww);   // stage 03 may have left them
     c->edge_bits = nullptr;
     // two iterations per round trip to the host, each with its own flag (an iteration after an unchanged one changes nothing either)
-    int* d_ch2 = LN(c).flags.as<int>() + 212;
+    int* d_ch2 = fl->thin_changed;
     for (int it = 0; it < 120; it += 2) {
         HIPC(c, hipMemsetAsync(d_ch2, 0, 8, LN(c).stream));
         for (int b = 0; b < 2; b++) {
@@ -474,7 +463,7 @@ extern "C" int orip_contours_prepare(orip_ctx* c) {
         HIPC(c, c->cref.ensure(plane * (size_t)K * 4 + 64));
         HIPC(c, c->cpix.ensure((size_t)cap_cpix * 4 + (size_t)cap_ends * 4 + 64));
         unsigned* cpix = c->cpix.as<unsigned>(); unsigned* ends = cpix + cap_cpix;
-        unsigned* d_cn = LN(c).flags.as<unsigned>() + 232;                          // {ends, cpix entries}
+        unsigned* d_cn = fl->chain_counts;
         hipStream_t s2 = LN(c).stream2;
         HIPC(c, hipEventRecord(LN(c).ev2, LN(c).stream));                            // the state bytes
         HIPC(c, hipStreamWaitEvent(s2, LN(c).ev2, 0));
@@ -490,11 +479,10 @@ extern "C" int orip_contours_prepare(orip_ctx* c) {
     ORIP_TRY(orip_ccl_bits(c, bA, c->tmpD.as<int>(), K));
     // ---- ordered compaction
     const int nblk = (int)cdiv((int64_t)nwords, 256);
-    HIPC(c, LN(c).tmpE.ensure((size_t)(nblk + 1) * 2 * sizeof(unsigned) + 64));
-    unsigned* d_cnt = LN(c).tmpE.as<unsigned>(); unsigned* d_boff = d_cnt + nblk + 1;
+    unsigned *d_cnt, *d_boff; { Carve L; L.each(nblk + 1, d_cnt, d_boff); HIPC(c, L.commit(LN(c).tmpE, 64)); }
     HIPC(c, hipMemsetAsync(d_cnt + nblk, 0, sizeof(unsigned), LN(c).stream));
     { ProfScope ps(c, "k_compact_count"); hipLaunchKernelGGL(k_compact_count_bits, dim3(nblk), block, 0, LN(c).stream, bA, nwords, d_cnt); }
-    ORIP_TRY(excl_scan<unsigned>(c, d_cnt, d_boff, (size_t)nblk + 1, LN(c).tmpF));
+    HIPC(c, orip_with_tmp(c, [&](void* tmp, size_t& bytes) { return rocprim::exclusive_scan(tmp, bytes, (const unsigned*)d_cnt, d_boff, 0u, (size_t)nblk + 1, rocprim::plus<unsigned>(), LN(c).stream); }));
     unsigned M = 0;
     HIPC(c, hipMemcpyAsync(&M, d_boff + nblk, sizeof(unsigned), hipMemcpyDeviceToHost, LN(c).stream));
     HIPC(c, hipStreamSynchronize(LN(c).stream));
@@ -506,39 +494,32 @@ extern "C" int orip_contours_prepare(orip_ctx* c) {
     R.M = M; R.NC = 0;
     if (M == 0) { HIPC(c, hipStreamSynchronize(LN(c).stream)); R.ready = true; return 0; }
     // keys / lin (double buffers for the sort)
-    HIPC(c, LN(c).vtmp[0].ensure((size_t)M * 4 * 4 + 64));
-    unsigned* keys_in = LN(c).vtmp[0].as<unsigned>(); unsigned* lin_in = keys_in + M; unsigned* keys = lin_in + M; unsigned* lin = keys + M;
+    unsigned *keys_in, *lin_in, *keys, *lin;
+    { Carve L; L.each(M, keys_in, lin_in, keys, lin); HIPC(c, L.commit(LN(c).vtmp[VT0_KEYS], 64)); }
     { ProfScope ps(c, "k_compact_write"); hipLaunchKernelGGL(k_compact_write_bits, dim3(nblk), block, 0, LN(c).stream, bA, c->tmpD.as<int>(), nwords, nw, H, W, Ww, d_boff, keys_in, lin_in); }
-    {
-        size_t bytes = 0;
-        HIPC(c, rocprim::radix_sort_pairs(nullptr, bytes, keys_in, keys, lin_in, lin, (size_t)M, 0, 30, LN(c).stream));
-        HIPC(c, LN(c).tmpF.ensure(bytes + 16));
-        ProfScope ps(c, "radix_sort_pairs");
-        HIPC(c, rocprim::radix_sort_pairs(LN(c).tmpF.p, bytes, keys_in, keys, lin_in, lin, (size_t)M, 0, 30, LN(c).stream));
-    }
+    { ProfScope ps(c, "radix_sort_pairs"); HIPC(c, orip_with_tmp(c, [&](void* tmp, size_t& bytes) { return rocprim::radix_sort_pairs(tmp, bytes, keys_in, keys, lin_in, lin, (size_t)M, 0, 30, LN(c).stream); })); }
     // ---- component segmentation
-    HIPC(c, LN(c).vtmp[1].ensure((size_t)M * 2 * 4 + 64));
-    unsigned* head = LN(c).vtmp[1].as<unsigned>(); unsigned* head_scan = head + M;
+    unsigned *head, *head_scan; { Carve L; L.each(M, head, head_scan); HIPC(c, L.commit(LN(c).vtmp[1], 64)); }
     hipLaunchKernelGGL(k_heads, dim3(cdiv(M, 256)), block, 0, LN(c).stream, keys, (int64_t)M, head);
-    ORIP_TRY(excl_scan<unsigned>(c, head, head_scan, (size_t)M, LN(c).tmpF));
+    HIPC(c, orip_with_tmp(c, [&](void* tmp, size_t& bytes) { return rocprim::exclusive_scan(tmp, bytes, (const unsigned*)head, head_scan, 0u, (size_t)M, rocprim::plus<unsigned>(), LN(c).stream); }));
     unsigned last2[2];
     HIPC(c, hipMemcpyAsync(&last2[0], head_scan + (M - 1), 4, hipMemcpyDeviceToHost, LN(c).stream));
     HIPC(c, hipMemcpyAsync(&last2[1], head + (M - 1), 4, hipMemcpyDeviceToHost, LN(c).stream));
     HIPC(c, hipStreamSynchronize(LN(c).stream));
     const unsigned NC = last2[0] + last2[1];
     R.NC = NC;
-    HIPC(c, LN(c).vtmp[2].ensure((size_t)(NC + 2) * 4 + 64));
-    unsigned* comp_start = LN(c).vtmp[2].as<unsigned>();
+    HIPC(c, LN(c).vtmp[VT0_COMP_START].ensure((size_t)(NC + 2) * 4 + 64));
+    unsigned* comp_start = LN(c).vtmp[VT0_COMP_START].as<unsigned>();
     hipLaunchKernelGGL(k_comp_starts, dim3(cdiv(M, 256)), block, 0, LN(c).stream, head, head_scan, (int64_t)M, comp_start, NC);
     R.h_cs.assign(NC + 1, 0); std::vector<unsigned> h_keyfirst(NC);
     HIPC(c, hipMemcpyAsync(R.h_cs.data(), comp_start, (size_t)(NC + 1) * 4, hipMemcpyDeviceToHost, LN(c).stream));
     // layer of each component (key of its first element)
-    HIPC(c, LN(c).vtmp[3].ensure((size_t)NC * 4 + 64));
+    HIPC(c, LN(c).vtmp[VT0_ORDER].ensure((size_t)NC * 4 + 64));       // (first the layer of each component, then the schedule)
     WalkArgs& A = R.A; memset(&A, 0, sizeof(A));
     A.H = H; A.W = W; A.plane = (int64_t)plane; A.st = c->tmpC.as<u8>(); A.keys = keys; A.lin = lin; A.comp_start = comp_start; A.nc = NC;
     if (R.chains) { A.cref = c->cref.as<unsigned>(); A.cpix = c->cpix.as<unsigned>(); }
-    hipLaunchKernelGGL(k_gather_head_layers, dim3(cdiv(NC, 256)), block, 0, LN(c).stream, keys, comp_start, NC, LN(c).vtmp[3].as<unsigned>());
-    HIPC(c, hipMemcpyAsync(h_keyfirst.data(), LN(c).vtmp[3].p, (size_t)NC * 4, hipMemcpyDeviceToHost, LN(c).stream));
+    hipLaunchKernelGGL(k_gather_head_layers, dim3(cdiv(NC, 256)), block, 0, LN(c).stream, keys, comp_start, NC, LN(c).vtmp[VT0_ORDER].as<unsigned>());
+    HIPC(c, hipMemcpyAsync(h_keyfirst.data(), LN(c).vtmp[VT0_ORDER].p, (size_t)NC * 4, hipMemcpyDeviceToHost, LN(c).stream));
     HIPC(c, hipStreamSynchronize(LN(c).stream));
     std::vector<unsigned>& layer_first = R.layer_first; layer_first.assign(K + 1, NC);
     for (unsigned i = NC; i-- > 0;) layer_first[h_keyfirst[i]] = i;
@@ -547,23 +528,18 @@ extern "C" int orip_contours_prepare(orip_ctx* c) {
     for (int l = 0; l < K; l++) A.total_fg[l] = (long long)R.h_cs[layer_first[l + 1]] - (long long)R.h_cs[layer_first[l]];
     // per-layer largest-first schedule: components sorted by (layer, size descending); layer l owns order[layer_first[l] .. layer_first[l+1])
     {
-        HIPC(c, LN(c).vtmp[5].ensure((size_t)NC * 24 + 64));
-        unsigned long long* kin = LN(c).vtmp[5].as<unsigned long long>(); unsigned long long* kout = kin + NC; unsigned* idin = (unsigned*)(kout + NC); unsigned* idout = idin + NC;
+        unsigned long long *kin, *kout; unsigned *idin, *idout;
+        { Carve L; L.each(NC, kin, kout, idin, idout); HIPC(c, L.commit(LN(c).vtmp[5], 64)); }
         hipLaunchKernelGGL(k_comp_order_keys, dim3(cdiv(NC, 256)), block, 0, LN(c).stream, keys, comp_start, NC, kin, idin);
-        size_t bytes = 0;
-        HIPC(c, rocprim::radix_sort_pairs(nullptr, bytes, kin, kout, idin, idout, (size_t)NC, 0, 40, LN(c).stream));
-        HIPC(c, LN(c).tmpF.ensure(bytes + 16));
-        HIPC(c, rocprim::radix_sort_pairs(LN(c).tmpF.p, bytes, kin, kout, idin, idout, (size_t)NC, 0, 40, LN(c).stream));
-        HIPC(c, LN(c).vtmp[3].ensure((size_t)NC * 4 + 64));
-        HIPC(c, hipMemcpyAsync(LN(c).vtmp[3].p, idout, (size_t)NC * 4, hipMemcpyDeviceToDevice, LN(c).stream));
-        R.order = LN(c).vtmp[3].as<unsigned>();
+        HIPC(c, orip_with_tmp(c, [&](void* tmp, size_t& bytes) { return rocprim::radix_sort_pairs(tmp, bytes, kin, kout, idin, idout, (size_t)NC, 0, 40, LN(c).stream); }));
+        R.order = LN(c).vtmp[VT0_ORDER].as<unsigned>();
+        HIPC(c, hipMemcpyAsync(LN(c).vtmp[VT0_ORDER].p, idout, (size_t)NC * 4, hipMemcpyDeviceToDevice, LN(c).stream));
     }
     // shared trace state: memo plane (one word per pixel and incoming direction) and walk records (two slots per skeleton pixel)
-    HIPC(c, LN(c).vtmp[6].ensure(plane * (size_t)K * 8 * 4 + 64));
-    HIPC(c, LN(c).vtmp[8].ensure((size_t)2 * M * sizeof(WalkInfo) + 64));
-    A.memo = LN(c).vtmp[6].as<unsigned>(); A.winfo = LN(c).vtmp[8].as<WalkInfo>();
-    HIPC(c, LN(c).vtmp[7].ensure((size_t)(NC + 1) * 4 + 64));
-    A.log_used = LN(c).vtmp[7].as<unsigned>();         // written by every component's trace
+    HIPC(c, LN(c).vtmp[VT0_WINFO].ensure((size_t)2 * M * sizeof(WalkInfo) + 64));
+    A.memo = LN(c).vtmp[VT0_MEMO].as<unsigned>(); A.winfo = LN(c).vtmp[VT0_WINFO].as<WalkInfo>();       // (the memo planes were sized where they were cleared)
+    HIPC(c, LN(c).vtmp[VT0_LOG_USED].ensure((size_t)(NC + 1) * 4 + 64));
+    A.log_used = LN(c).vtmp[VT0_LOG_USED].as<unsigned>();         // written by every component's trace
     HIPC(c, hipStreamSynchronize(LN(c).stream));
     R.ready = true;
     // The layers' traces start right here, from the calling thread, each on its layer's lane: the walks head every layer's chain, and the hand-over to the
@@ -593,12 +569,12 @@ static int trace_launch(orip_ctx* c, Prep04& R, int layer, unsigned F) {
     WalkStore& WS = c->wstore[layer];
     WS.epoch++; WS.n = 0;                              // walk-coded lists built on the previous trace of this layer are stale from here on
     HIPC(c, WS.log.ensure(nlog * 16 + 64));
-    HIPC(c, LN(c).vtmp[9].ensure(nstep + 64));
+    HIPC(c, LN(c).vtmp[VTL_STEPLOG].ensure(nstep + 64));
     WalkArgs A = R.A;
     A.logbuf = WS.log.as<unsigned>() - 4 * ((size_t)F * b0 + (size_t)64 * c0);
-    A.steplog = LN(c).vtmp[9].as<u8>() - ((size_t)F * b0 + (size_t)256 * c0);
+    A.steplog = LN(c).vtmp[VTL_STEPLOG].as<u8>() - ((size_t)F * b0 + (size_t)256 * c0);
     A.cap_factor = F; A.comp_order = R.order + c0; A.nc = NCl;
-    int* d_over = LN(c).flags.as<int>() + 20; A.overflow = d_over;
+    int* d_over = &LN(c).flags.as<LaneFlags>()->trace_overflow; A.overflow = d_over;
     if (R.chains) HIPC(c, hipStreamWaitEvent(LN(c).stream, c->ln[0].ev3, 0));            // the chain lists and flags (orip_contours_prepare, side stream)
     if (!R.memo_clear[layer]) {                      // a retry, or a second trace of the layer after one prepare: the previous walk left its memo
         HIPC(c, hipMemsetAsync(A.memo + plane * 8 * layer, 0, plane * 8 * 4, LN(c).stream));          // entries and the ST_VIS bits of every
@@ -607,9 +583,9 @@ static int trace_launch(orip_ctx* c, Prep04& R, int layer, unsigned F) {
     R.memo_clear[layer] = false;
     HIPC(c, hipMemsetAsync(A.winfo + 2 * (size_t)b0, 0, (size_t)2 * Ml * sizeof(WalkInfo), LN(c).stream));
     HIPC(c, hipMemsetAsync(d_over, 0, 4, LN(c).stream));
-    if (getenv("ORIP_WALK_DBG")) {          // per-component counters (walks, steps, memo hits, closed cycles, tile loads, size)
-        HIPC(c, LN(c).vtmp[11].ensure((size_t)NCl * 256 + 64)); HIPC(c, hipMemsetAsync(LN(c).vtmp[11].p, 0, (size_t)NCl * 256, LN(c).stream));
-        A.dbg = LN(c).vtmp[11].as<unsigned long long>() - 32ull * c0;
+    if (getenv("ORIP_WALK_DBG")) {          // per-component counters (walks, steps, memo hits, closed cycles, tile loads, size), in the leaves' slot until trace_finish
+        HIPC(c, LN(c).vtmp[VT_LEAVES].ensure((size_t)NCl * 256 + 64)); HIPC(c, hipMemsetAsync(LN(c).vtmp[VT_LEAVES].p, 0, (size_t)NCl * 256, LN(c).stream));
+        A.dbg = LN(c).vtmp[VT_LEAVES].as<unsigned long long>() - 32ull * c0;
     }
     { ProfScope ps(c, "k_trace"); hipLaunchKernelGGL(k_trace, dim3(NCl), dim3(64), 0, LN(c).stream, A); }
     HIPC(c, hipGetLastError());
@@ -622,30 +598,23 @@ static int trace_finish(orip_ctx* c, Prep04& R, int layer) {
     const unsigned b0 = R.h_cs[c0], b1 = R.h_cs[c1];
     const unsigned Ml = b1 - b0;
     dim3 block(256);
-    int* d_over = LN(c).flags.as<int>() + 20;
+    int* d_over = &LN(c).flags.as<LaneFlags>()->trace_overflow;
     // offsets: exclusive scans over the layer's walk slots (slot order == output order: components by rank, endpoint walks then leftovers, each in raster order)
     // Nothing waits for the trace first: the sizing kernels are enqueued behind it and the one read below brings its overflow flag along
     // with the totals (an overflowed trace -- rare: the logs hold 64 entries per skeleton pixel -- is redone with larger logs).
     const unsigned nslots = 2u * Ml, sl0 = 2u * b0;
     const size_t ns1 = (size_t)nslots + 1;
-    HIPC(c, LN(c).vtmp[4].ensure(ns1 * 2 * sizeof(WSum) + 256));
-    WSum* ws = LN(c).vtmp[4].as<WSum>(); WSum* wo = ws + ns1;
+    WSum *ws, *wo; { Carve L; L.each(ns1, ws, wo); HIPC(c, L.commit(LN(c).vtmp[4], 256)); }
     WalkStore& WS = c->wstore[layer];
     WSum h_tot; unsigned log_shift = 0; WalkArgs A;
     for (;;) {
     log_shift = (unsigned)((size_t)R.F[layer] * b0 + (size_t)64 * c0);
     A = R.A;                        // the layer's logs as the trace addressed them (walk_close_tail / vwalk_pieces follow the recorded trajectories)
     A.logbuf = WS.log.as<unsigned>() - 4 * (size_t)log_shift;
-    A.steplog = LN(c).vtmp[9].as<u8>() - ((size_t)R.F[layer] * b0 + (size_t)256 * c0);
+    A.steplog = LN(c).vtmp[VTL_STEPLOG].as<u8>() - ((size_t)R.F[layer] * b0 + (size_t)256 * c0);
     A.cap_factor = R.F[layer]; A.overflow = d_over;
     hipLaunchKernelGGL(k_winfo_lens, dim3(cdiv(nslots + 1, 256)), block, 0, LN(c).stream, A, sl0, nslots, ws);
-    {
-        size_t bytes = 0; WSum zero; zero.pts = 0; zero.paths = zero.own = zero.pieces = zero.pad = 0;
-        HIPC(c, rocprim::exclusive_scan(nullptr, bytes, ws, wo, zero, ns1, rocprim::plus<WSum>(), LN(c).stream));
-        HIPC(c, LN(c).tmpF.ensure(bytes + 16));
-        HIPC(c, rocprim::exclusive_scan(LN(c).tmpF.p, bytes, ws, wo, zero, ns1, rocprim::plus<WSum>(), LN(c).stream));
-    }
-    A.overflow = d_over;
+    { WSum zero; zero.pts = 0; zero.paths = zero.own = zero.pieces = zero.pad = 0; HIPC(c, orip_with_tmp(c, [&](void* tmp, size_t& bytes) { return rocprim::exclusive_scan(tmp, bytes, ws, wo, zero, ns1, rocprim::plus<WSum>(), LN(c).stream); })); }
     hipLaunchKernelGGL(k_totals_flag, dim3(1), dim3(1), 0, LN(c).stream, d_over, &wo[nslots].pad);
     HIPC(c, hipMemcpyAsync(&h_tot, wo + nslots, sizeof(WSum), hipMemcpyDeviceToHost, LN(c).stream));
     // pixels of the log entries in use (needs nothing from the scan: it runs while the host waits for the totals)
@@ -666,7 +635,7 @@ static int trace_finish(orip_ctx* c, Prep04& R, int layer) {
     if (getenv("ORIP_WALK_DBG")) {
         const unsigned NCl = c1 - c0;
         std::vector<unsigned long long> h((size_t)NCl * 32);
-        HIPC(c, hipMemcpy(h.data(), LN(c).vtmp[11].p, h.size() * 8, hipMemcpyDeviceToHost));
+        HIPC(c, hipMemcpy(h.data(), LN(c).vtmp[VT_LEAVES].p, h.size() * 8, hipMemcpyDeviceToHost));
         unsigned long long tot[32] = {0}; size_t big = 0;
         for (size_t i = 0; i < h.size(); i++) tot[i % 32] += h[i];
         for (size_t i = 0; i < NCl; i++) if (h[i * 32 + 7] > h[big * 32 + 7]) big = i;

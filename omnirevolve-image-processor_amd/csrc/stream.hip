@@ -57,10 +57,7 @@ extern "C" int orip_stream_codes(orip_ctx* c, const int32_t* segs, int64_t n, in
     unsigned long long* cnt = c->stream_off.as<unsigned long long>() + (n + 1); unsigned long long* off = c->stream_off.as<unsigned long long>();
     HIPC(c, hipMemcpyAsync(c->stream_segs.p, segs, (size_t)n * 16, hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(k_seg_counts, dim3(cdiv(n + 1, 256)), dim3(256), 0, s, c->stream_segs.as<int4>(), n, cnt);
-    size_t bytes = 0;
-    HIPC(c, rocprim::exclusive_scan(nullptr, bytes, cnt, off, 0ull, (size_t)n + 1, rocprim::plus<unsigned long long>(), s));
-    HIPC(c, LN(c).tmpF.ensure(bytes + 16));
-    HIPC(c, rocprim::exclusive_scan(LN(c).tmpF.p, bytes, cnt, off, 0ull, (size_t)n + 1, rocprim::plus<unsigned long long>(), s));
+    HIPC(c, orip_with_tmp(c, [&](void* tmp, size_t& bytes) { return rocprim::exclusive_scan(tmp, bytes, cnt, off, 0ull, (size_t)n + 1, rocprim::plus<unsigned long long>(), s); }));
     unsigned long long h_total = 0;
     HIPC(c, hipMemcpyAsync(&h_total, off + n, 8, hipMemcpyDeviceToHost, s));
     HIPC(c, hipStreamSynchronize(s));

@@ -5,6 +5,8 @@
 #include "vsrc.h"
 #include <rocprim/rocprim.hpp>
 #include <algorithm>
+#include <chrono>
+#include <string>
 
 namespace {   // every TU that includes this header gets its own copy of the kernels (internal linkage)
 
@@ -36,21 +38,15 @@ static int vscan_excl(orip_ctx* c, const T* in, T* out, size_t n) {
         HIPC(c, hipGetLastError());
         return 0;
     }
-    size_t bytes = 0;
-    HIPC(c, rocprim::exclusive_scan(nullptr, bytes, in, out, T(0), n, rocprim::plus<T>(), LN(c).stream));
-    HIPC(c, LN(c).tmpF.ensure(bytes + 16));
-    HIPC(c, rocprim::exclusive_scan(LN(c).tmpF.p, bytes, in, out, T(0), n, rocprim::plus<T>(), LN(c).stream));
+    HIPC(c, orip_with_tmp(c, [&](void* tmp, size_t& bytes) { return rocprim::exclusive_scan(tmp, bytes, in, out, T(0), n, rocprim::plus<T>(), LN(c).stream); }));
     return 0;
 }
 template <class K, class V>
 static int vsort_pairs(orip_ctx* c, const K* kin, K* kout, const V* vin, V* vout, size_t n, int begin_bit, int end_bit, bool desc = false) {
     if (n == 0) return 0;
-    size_t bytes = 0;
-    if (!desc) HIPC(c, rocprim::radix_sort_pairs(nullptr, bytes, kin, kout, vin, vout, n, begin_bit, end_bit, LN(c).stream));
-    else HIPC(c, rocprim::radix_sort_pairs_desc(nullptr, bytes, kin, kout, vin, vout, n, begin_bit, end_bit, LN(c).stream));
-    HIPC(c, LN(c).tmpF.ensure(bytes + 16));
-    if (!desc) HIPC(c, rocprim::radix_sort_pairs(LN(c).tmpF.p, bytes, kin, kout, vin, vout, n, begin_bit, end_bit, LN(c).stream));
-    else HIPC(c, rocprim::radix_sort_pairs_desc(LN(c).tmpF.p, bytes, kin, kout, vin, vout, n, begin_bit, end_bit, LN(c).stream));
+    HIPC(c, orip_with_tmp(c, [&](void* tmp, size_t& bytes) {
+        return !desc ? rocprim::radix_sort_pairs(tmp, bytes, kin, kout, vin, vout, n, begin_bit, end_bit, LN(c).stream)
+                     : rocprim::radix_sort_pairs_desc(tmp, bytes, kin, kout, vin, vout, n, begin_bit, end_bit, LN(c).stream); }));
     return 0;
 }
 template <class T>
@@ -59,6 +55,17 @@ static int vread(orip_ctx* c, T* host, const T* dev, size_t n = 1) {
     HIPC(c, hipStreamSynchronize(LN(c).stream));
     return 0;
 }
+// ORIP_TIME08 / ORIP_TIME10 (debug): wall times of a call's phases.  Every lap waits for the lane's stream, so a timed run is not a concurrent one.
+struct PhaseTimer {
+    orip_ctx* c; const bool on; std::string log; std::chrono::steady_clock::time_point prev;
+    PhaseTimer(orip_ctx* ctx, const char* env) : c(ctx), on(getenv(env) != nullptr), prev(std::chrono::steady_clock::now()) {}
+    double lap() {          // ms since the previous lap
+        if (on) hipStreamSynchronize(LN(c).stream);
+        const auto t = std::chrono::steady_clock::now(); const double ms = std::chrono::duration<double, std::milli>(t - prev).count(); prev = t;
+        return ms;
+    }
+    void tick(const char* name) { if (on) { char b[64]; snprintf(b, sizeof b, " %s %.2f", name, lap()); log += b; } }
+};
 
 // ---- per-polyline features ----
 struct PolyFeat {
@@ -453,9 +460,9 @@ template <class Src>
 static int vfeatures_long(orip_ctx* c, const Src& src, int64_t n, int64_t total, int what, PolyFeat* feat, float* per_rev) {
     if (n == 0 || total <= ORIP_LONG_POLY) return 0;
     const size_t nleaf = (size_t)(total >> 6) + 2 * (size_t)n + 8;
-    HIPC(c, LN(c).vtmp[11].ensure(nleaf * sizeof(float) * ((what & 32) ? 2 : 1) + (size_t)n * 16 + 64));
-    float* leafbuf = LN(c).vtmp[11].as<float>(); float* leafbuf_rev = (what & 32) ? leafbuf + nleaf : nullptr;
-    unsigned* kin = reinterpret_cast<unsigned*>(leafbuf + nleaf * ((what & 32) ? 2 : 1)); unsigned* kout = kin + n; unsigned* vin = kout + n; unsigned* vout = vin + n;
+    float* leafbuf; unsigned *kin, *kout, *vin, *vout;
+    { Carve L; L.take(leafbuf, nleaf * ((what & 32) ? 2 : 1)); L.each(n, kin, kout, vin, vout); HIPC(c, L.commit(LN(c).vtmp[VT_LEAVES], 64)); }      // (leafbuf: forward leaves, then the reversed reading's)
+    float* leafbuf_rev = (what & 32) ? leafbuf + nleaf : nullptr;
     hipLaunchKernelGGL(k_len_keys, dim3(cdiv(n, 256)), dim3(256), 0, LN(c).stream, src.off, n, kin, vin);
     ORIP_TRY((vsort_pairs<unsigned, unsigned>(c, kin, kout, vin, vout, (size_t)n, 0, 32, true)));
     ProfScope ps(c, "k_poly_features_long");
@@ -1288,12 +1295,8 @@ static int vreorder(orip_ctx* c, DPolys& src, DPolys& dst, int kind, ReorderHook
     int64_t n = src.n;
     if (n == 0) { dst.n = 0; dst.total = 0; dst.set_explicit(); HIPC(c, dst.off.ensure(64)); HIPC(c, hipMemsetAsync(dst.off.p, 0, 8, LN(c).stream)); return 0; }
     if (n > 0x7fffffff) ORIP_FAIL(c, "too many polylines");
-    HIPC(c, LN(c).vtmp[6].ensure((size_t)n * (sizeof(PolyFeat) + sizeof(NNEnds) + sizeof(GatherDesc) + 4 + 2) + 256));
-    PolyFeat* feat = LN(c).vtmp[6].as<PolyFeat>();
-    NNEnds* ends = (NNEnds*)(feat + n);
-    GatherDesc* desc = (GatherDesc*)(ends + n);
-    int32_t* order = (int32_t*)(desc + n);
-    uint8_t* flips = (uint8_t*)(order + n); uint8_t* used = flips + n;
+    PolyFeat* feat; NNEnds* ends; GatherDesc* desc; int32_t* order; uint8_t *flips, *used;
+    { Carve L; L.each(n, feat, ends, desc, order, flips, used); HIPC(c, L.commit(LN(c).vtmp[6], 256)); }
     int what = kind == 7 ? 4 : (kind == 8 ? 1 : 8);
     if (kind == 7 && is_coded(src) && src.vident && !getenv("ORIP_ARC_POINTS")) {      // whole walks: the long contours' arc lengths from the walk records
         VSrc vs_; ORIP_TRY(vsrc_of(c, src, vs_));
@@ -1302,7 +1305,7 @@ static int vreorder(orip_ctx* c, DPolys& src, DPolys& dst, int kind, ReorderHook
         HIPC(c, hipGetLastError());
     } else ORIP_TRY(vfeatures(c, src, what, feat));
     ORIP_WITH_SRC(c, src, ps, { hipLaunchKernelGGL(k_ends_from_feat<decltype(ps)>, dim3(cdiv(n, 256)), dim3(256), 0, LN(c).stream, feat, n, kind == 7 ? 1 : 0, ps, ends); });
-    int* d_seed = LN(c).flags.as<int>() + 32;
+    LaneFlags* fl = LN(c).flags.as<LaneFlags>(); int* d_seed = fl->nn_seed;
     hipLaunchKernelGGL(k_argmax_feat, dim3(1), dim3(256), 0, LN(c).stream, feat, (int)n, kind == 8 ? 0 : 1, d_seed, ends);      // seed and coordinate-range flags in one pass
     const size_t lds = (size_t)n * 9 + 16;
     // grid side: as fine as LDS allows (cells are powers of two, so twice the side is four times fewer candidates per window),
@@ -1325,7 +1328,7 @@ static int vreorder(orip_ctx* c, DPolys& src, DPolys& dst, int kind, ReorderHook
     {
         ProfScope ps(c, "k_greedy_nn");
         if (grid_ok) {
-            unsigned long long* dbg2 = getenv("ORIP_NN_DBG2") ? LN(c).flags.as<unsigned long long>() + 64 : nullptr;
+            unsigned long long* dbg2 = getenv("ORIP_NN_DBG2") ? fl->nn_dbg2 : nullptr;
             if (dbg2) hipMemsetAsync(dbg2, 0, 80, LN(c).stream);
             hipLaunchKernelGGL(k_greedy_nn_fast, dim3(1), dim3(64), lds_grid + 4, LN(c).stream, ends, (int)n, d_seed, 3, 0, r07, G, order, flips, getenv("ORIP_NN_NOASM") ? 1 : 0, dbg2);
             if (dbg2) { unsigned long long h[10]; hipStreamSynchronize(LN(c).stream); hipMemcpy(h, dbg2, 80, hipMemcpyDeviceToHost); fprintf(stderr, "[nn dbg2] kind %d n %lld G %d: %llu steps by the compiled code (empty %llu, all used %llu, gap %llu; asm steps from cached candidates: one per lane %llu, two per lane %llu; with more than 128 candidates %llu), %llu asm entries, cycles asm %llu compiled %llu\n", kind, (long long)n, G, h[0], h[5], h[7], h[8], h[4], h[6], h[9], h[1], h[2], h[3]); hipMemsetAsync(dbg2, 0, 80, LN(c).stream); }

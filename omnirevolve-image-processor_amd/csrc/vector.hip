@@ -336,13 +336,12 @@ extern "C" int orip_plot_order(orip_ctx* c, int layer, double R_insert, int64_t*
     c->n_ops[layer] = 0; *n_ops = 0;
     if (nl + nt == 0) return 0;
     if (nl + nt > 0x3fffffff) ORIP_FAIL(c, "too many ops");
-    HIPC(c, LN(c).vtmp[6].ensure((size_t)std::max<int64_t>(nl, 1) * sizeof(PolyFeat) + (size_t)(nl + nt) + 256));
-    PolyFeat* feat = LN(c).vtmp[6].as<PolyFeat>();
-    uint8_t* alive_l = (uint8_t*)(feat + std::max<int64_t>(nl, 1)); uint8_t* alive_t = alive_l + nl;
+    PolyFeat* feat; uint8_t *alive_l, *alive_t;
+    { Carve S; S.take(feat, std::max<int64_t>(nl, 1)); S.take(alive_l, nl); S.take(alive_t, nt); HIPC(c, S.commit(LN(c).vtmp[6], 256)); }
     HIPC(c, c->ops[layer].ensure((size_t)(nl + nt) * 20 + 64));
     HIPC(c, T.xy.ensure(64));
     if (nl) ORIP_TRY(vfeatures(c, L, 2, feat));
-    int* d_n = LN(c).flags.as<int>() + 40;
+    int* d_n = &LN(c).flags.as<LaneFlags>()->plot_ops;
     const size_t lds = (size_t)nl * 17 + (size_t)nt * 9 + 64;
     if (lds <= 150 * 1024 && !getenv("ORIP_PLOT_1WG")) {
         static std::once_flag attr_once;            // several layer threads may arrive here together

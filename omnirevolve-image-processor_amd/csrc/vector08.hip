@@ -1451,8 +1451,8 @@ static int prefetch08(orip_ctx* c, const orip_params08& P, DPolys& S, const Poly
             { ProfScope ps(c, "k_seglen"); hipLaunchKernelGGL(k_seglen<VSrc>, dim3((unsigned)cdiv(total, 4 * 63 * 64)), dim3(256), 0, LN(c).stream, sS, n, total, seg, ff); }
             if (total > ORIP_LONG_POLY) { ProfScope ps(c, "k_poly_features_long");
                 const size_t nleaf = (size_t)(total >> 6) + 2 * (size_t)n + 8;
-                HIPC(c, LN(c).vtmp[11].ensure(nleaf * sizeof(float) * 2 + 64));
-                float* leafbuf = LN(c).vtmp[11].as<float>(); float* leafbuf_rev = leafbuf + nleaf;
+                HIPC(c, LN(c).vtmp[VT_LEAVES].ensure(nleaf * sizeof(float) * 2 + 64));
+                float* leafbuf = LN(c).vtmp[VT_LEAVES].as<float>(); float* leafbuf_rev = leafbuf + nleaf;      // (one array: forward leaves, then the reversed reading's)
                 hipLaunchKernelGGL(k_perim_leaves_seg, dim3((unsigned)cdiv((int64_t)nleaf * 8, 256)), dim3(256), 0, LN(c).stream, sS.off, n, ff, seg, leafbuf, leafbuf_rev, (int64_t)nleaf);
                 hipLaunchKernelGGL((k_poly_features_long<VSrc, true>), dim3((unsigned)std::min<int64_t>(n, 4096)), dim3(256), 0, LN(c).stream, sS, n, 1 | 16 | 32 | 64, ff, leafbuf, ordl, per_rev, leafbuf_rev, seg); }
         }
@@ -1480,9 +1480,8 @@ int split_small(orip_ctx* c, DPolys& src, const orip_params08& P, DPolys& kept, 
     HIPC(c, kept.off.ensure(64)); HIPC(c, hipMemsetAsync(kept.off.p, 0, 8, LN(c).stream));
     int64_t n = src.n;
     if (n == 0) return 0;
-    HIPC(c, LN(c).vtmp[2].ensure((size_t)(n + 1) * (16 + 8 + 2 * sizeof(GatherDesc)) + 256));
-    unsigned* is_tap = LN(c).vtmp[2].as<unsigned>(); unsigned* is_keep = is_tap + (n + 1); unsigned* tap_scan = is_keep + (n + 1); unsigned* keep_scan = tap_scan + (n + 1);
-    int2* tap_xy = (int2*)(keep_scan + (n + 1)); GatherDesc* kd = (GatherDesc*)(tap_xy + (n + 1)); GatherDesc* kd2 = kd + (n + 1);
+    unsigned *is_tap, *is_keep, *tap_scan, *keep_scan; int2* tap_xy; GatherDesc *kd, *kd2;
+    { Carve L; L.each(n + 1, is_tap, is_keep, tap_scan, keep_scan, tap_xy, kd, kd2); HIPC(c, L.commit(LN(c).vtmp[2], 256)); }
     HIPC(c, LN(c).vtmp[10].ensure((size_t)n * sizeof(PolyFeat) + 64));
     PolyFeat* sfeat = LN(c).vtmp[10].as<PolyFeat>();
     if (is_coded(src) && P.tap_max_v > 64) ORIP_TRY(orip_polys_materialize(c, src));      // the walk-coded tap test copies <= 64 vertices (default tap_max_vertices: 50)
@@ -1523,64 +1522,43 @@ int orip_prefetch08(orip_ctx* c, void* prm, DPolys& scaled, const void* feat07) 
     return prefetch08(c, *static_cast<const orip_params08*>(prm), scaled, static_cast<const PolyFeat*>(feat07));
 }
 
-extern "C" int orip_dedup_layer(orip_ctx* c, int layer, const orip_params08* prm) {
-    orip_enter(c);
-    if (!prm || layer < 0 || layer >= ORIP_MAX_LAYERS) ORIP_FAIL(c, "bad arguments");
-    const orip_params08 P = *prm;
+// Stage 08-A (A0 .. A7): the kept polylines resampled, stamped and tested -> lines2 (tp[2]) and the layer's taps.  caps_counted: flags.caps_distinct holds this run's count.
+static int dedup08_a(orip_ctx* c, int layer, const orip_params08& P, DPolys& S, DTaps& TOUT, PhaseTimer& T, bool& caps_counted) {
     const int W = P.W, H = P.H;
-    ORIP_LANE_NODRAIN(c, layer + 1);       // stage 08 waits for the parts of its prefetch where it picks them up (split_small, A2)
-    if (W <= 0 || H <= 0 || W > 16383 || H > 16383) ORIP_FAIL(c, "canvas %dx%d out of range", W, H);
-    if (!(P.sample_step * 2.0 < P.max_jump)) ORIP_FAIL(c, "dedup_sample_step must be < max_join_jump_px / 2 (stage-A segments are assumed jump-free)");
-    DPolys& S = c->polys[ORIP_SLOT_SORTED][layer]; DPolys& OUT = c->polys[ORIP_SLOT_LINES_INTRA][layer]; DTaps& TOUT = c->taps[ORIP_TAPS_INTRA][layer];
-    OUT.n = 0; OUT.total = 0; OUT.set_explicit(); TOUT.n = 0;
-    HIPC(c, OUT.off.ensure(64)); HIPC(c, hipMemsetAsync(OUT.off.p, 0, 8, LN(c).stream));
-    HIPC(c, TOUT.xy.ensure(64));
-    if (S.n == 0) return 0;
-    struct Ref { DPolys& p; }; Ref kept0{LN(c).tp[0]}, cleaned{LN(c).tp[1]}, lines2{LN(c).tp[2]}, merged{LN(c).tp[3]};
-    for (Ref* r : {&kept0, &cleaned, &lines2, &merged}) { r->p.n = 0; r->p.total = 0; r->p.set_explicit(); }
-    int64_t nt0 = 0, nt2 = 0;
-    bool caps_counted = false;
-    const bool tdbg = getenv("ORIP_TIME08") != nullptr;      // debug: per-phase wall times of this layer (adds stream syncs)
-    std::string tlog; auto tprev = std::chrono::steady_clock::now();
-    auto tick = [&](const char* name) {
-        if (!tdbg) return;
-        hipStreamSynchronize(LN(c).stream);
-        auto t = std::chrono::steady_clock::now(); char b[64];
-        snprintf(b, sizeof b, " %s %.2f", name, std::chrono::duration<double, std::milli>(t - tprev).count()); tlog += b; tprev = t;
-    };
+    DPolys& kept0 = LN(c).tp[0]; DPolys& cleaned = LN(c).tp[1]; DPolys& lines2 = LN(c).tp[2];
+    LaneFlags* fl = LN(c).flags.as<LaneFlags>(); int64_t nt0 = 0, nt2 = 0;
     // ---- A0
     HIPC(c, LN(c).vtmp[6].ensure((size_t)S.n * sizeof(PolyFeat) + 64));
     PolyFeat* feat = LN(c).vtmp[6].as<PolyFeat>();       // open-view features of the kept polylines (perimeter: A1)
-    ORIP_TRY(split_small(c, S, P, kept0.p, TOUT.xy, 0, &nt0, feat));
-    const int64_t nk = kept0.p.n;
-    tick("split");
+    ORIP_TRY(split_small(c, S, P, kept0, TOUT.xy, 0, &nt0, feat));
+    const int64_t nk = kept0.n;
+    T.tick("split");
     if (nk > 0) {
-        if (kept0.p.total > 0x7fffffff) ORIP_FAIL(c, "layer too large");
+        if (kept0.total > 0x7fffffff) ORIP_FAIL(c, "layer too large");
         // ---- A1: order by perimeter, descending, stable
-        tick("feat");
-        HIPC(c, LN(c).vtmp[0].ensure((size_t)nk * 16 + (size_t)(nk + 1) * 8 + (size_t)nk * sizeof(RsInfo) + 256));
-        float* kin = LN(c).vtmp[0].as<float>(); float* kout = kin + nk; unsigned* vin = (unsigned*)(kout + nk); unsigned* ord = vin + nk;
-        unsigned* mr = ord + nk; unsigned* sbase = mr + (nk + 1); RsInfo* info = (RsInfo*)(sbase + (nk + 1) + 2);   // (6 nk + 4) dwords: 8-byte aligned
+        T.tick("feat");
+        float *kin, *kout; unsigned *vin, *ord, *mr, *sbase; RsInfo* info;
+        { Carve L; L.each(nk, kin, kout, vin, ord); L.take(mr, nk + 1);
+          L.take(sbase, nk + 2); L.take(info, nk); HIPC(c, L.commit(LN(c).vtmp[0], 256)); }      // sbase: nk + 1 sample bases, then the any-out word (one read-back fetches both)
         hipLaunchKernelGGL(k_fill_per, dim3(cdiv(nk, 256)), dim3(256), 0, LN(c).stream, feat, nk, kin, vin);
         ORIP_TRY((vsort_pairs<float, unsigned>(c, kin, kout, vin, ord, (size_t)nk, 0, 32, true)));
-        tick("A0-1");
+        T.tick("A0-1");
         // ---- A2: resample
         const double step = std::max(1.0, P.sample_step);
         const LaneRes::Prefetch08& F = LN(c).pf08;
-        const bool picked = is_coded(kept0.p) && kept0.p.pf_tag && F.valid && F.tag == kept0.p.pf_tag && F.step == step && !kept0.p.vident;
+        const bool picked = is_coded(kept0) && kept0.pf_tag && F.valid && F.tag == kept0.pf_tag && F.step == step && !kept0.vident;
         HIPC(c, orip_pf08_drain(c));          // the cumulative lengths of the prefetch (ev3), if nobody has waited for them yet
-        HIPC(c, LN(c).vtmp[1].ensure((picked ? 0 : (size_t)kept0.p.total * 4) + (size_t)(nk + 1) * 8 + 128));
-        int64_t* cumoff = LN(c).vtmp[1].as<int64_t>(); float* cum = reinterpret_cast<float*>(cumoff + (nk + 2));
+        int64_t* cumoff; float* cum; { Carve L; L.take(cumoff, nk + 1); L.take(cum, picked ? 0 : kept0.total); HIPC(c, L.commit(LN(c).vtmp[1], 128)); }
         if (picked) {       // cumulative lengths and sample counts were taken under stage 07's greedy, per walk and direction: pick this list's
             cum = F.cum.as<float>();
-            hipLaunchKernelGGL(k_pf_pick_info, dim3(cdiv(nk, 256)), dim3(256), 0, LN(c).stream, kept0.p.vview.as<VView>(), nk, F.info.as<RsInfo>(), F.n, F.src_off, F.src_off, F.tot_f, info, cumoff);
+            hipLaunchKernelGGL(k_pf_pick_info, dim3(cdiv(nk, 256)), dim3(256), 0, LN(c).stream, kept0.vview.as<VView>(), nk, F.info.as<RsInfo>(), F.n, F.src_off, F.src_off, F.tot_f, info, cumoff);
         } else {
-        HIPC(c, hipMemcpyAsync(cumoff, kept0.p.off.p, (size_t)(nk + 1) * 8, hipMemcpyDeviceToDevice, LN(c).stream));
-        { ProfScope ps(c, "k_cumlen"); ORIP_WITH_SRC(c, kept0.p, sv, { hipLaunchKernelGGL(k_cumlen<decltype(sv)>, dim3(cdiv(nk, 128)), dim3(128), 0, LN(c).stream, sv, nk, step, cum, info); }); }
-        if (kept0.p.total > ORIP_LONG_CUM) { ProfScope ps(c, "k_cumlen_long"); ORIP_WITH_SRC(c, kept0.p, sv, {
+        HIPC(c, hipMemcpyAsync(cumoff, kept0.off.p, (size_t)(nk + 1) * 8, hipMemcpyDeviceToDevice, LN(c).stream));
+        { ProfScope ps(c, "k_cumlen"); ORIP_WITH_SRC(c, kept0, sv, { hipLaunchKernelGGL(k_cumlen<decltype(sv)>, dim3(cdiv(nk, 128)), dim3(128), 0, LN(c).stream, sv, nk, step, cum, info); }); }
+        if (kept0.total > ORIP_LONG_CUM) { ProfScope ps(c, "k_cumlen_long"); ORIP_WITH_SRC(c, kept0, sv, {
                 hipLaunchKernelGGL(k_cumlen_long2<decltype(sv)>, dim3((unsigned)std::min<int64_t>(nk, 8192), 1), dim3(64), 0, LN(c).stream, sv, nk, step, cum, (int64_t)0, info, ord, 0, (const float*)nullptr); }); }
         }
-        tick("cumlen");
+        T.tick("cumlen");
         HIPC(c, hipMemsetAsync(sbase + nk + 1, 0, 4, LN(c).stream));
         hipLaunchKernelGGL(k_rank_counts, dim3(cdiv(nk + 1, 256)), dim3(256), 0, LN(c).stream, info, ord, nk, mr, feat, W, H, sbase + nk + 1);
         ORIP_TRY(vscan_excl<unsigned>(c, mr, sbase, (size_t)nk + 1));
@@ -1589,15 +1567,14 @@ extern "C" int orip_dedup_layer(orip_ctx* c, int layer, const orip_params08* prm
         const unsigned MS = ms_out[0]; const bool any_out = ms_out[1] != 0 || getenv("ORIP_CAPPREV_SCAN");
         if (MS > 0) {
             if (MS > 0x7ffffff0u) ORIP_FAIL(c, "too many samples");
-            if (tdbg) { char b[48]; snprintf(b, sizeof b, " [MS %u]", MS); tlog += b; }
-            HIPC(c, LN(c).vtmp[3].ensure((size_t)MS * (8 + 8 + 8 + 4 + 4 + 4 + 1 + 4 + 4 + 8 + 1) + 1024));
-            SampleArrs A; A.sx = LN(c).vtmp[3].as<double>(); A.sy = A.sx + MS; A.dprev = A.sy + MS; A.xi = (int*)(A.dprev + MS); A.yi = A.xi + MS; A.rank = (unsigned*)(A.yi + MS);
-            unsigned* npop = A.rank + MS; int* capprev = (int*)(npop + MS); int2* spt = (int2*)(capprev + MS + (MS & 1)); A.inc = (uint8_t*)(spt + MS); uint8_t* sflag = A.inc + MS;
+            if (T.on) { char b[48]; snprintf(b, sizeof b, " [MS %u]", MS); T.log += b; }
+            SampleArrs A; unsigned* npop; int* capprev; int2* spt; uint8_t* sflag;
+            { Carve L; L.each(MS, A.sx, A.sy, A.dprev, A.xi, A.yi, A.rank, npop, capprev, spt, A.inc, sflag); HIPC(c, L.commit(LN(c).vtmp[3], 1024)); }
             const unsigned nb = (unsigned)cdiv(MS, 256);
-            HIPC(c, LN(c).vtmp[5].ensure((size_t)MS * 24 + 64 + (size_t)(nb + 1) * 8));
-            unsigned* ckin = LN(c).vtmp[5].as<unsigned>(); unsigned* ckout = ckin + MS; unsigned* cvin = ckout + MS; unsigned* cvout = cvin + MS;
+            unsigned *ckin, *ckout, *cvin, *cvout; int2* hints;
+            { Carve L; L.each(MS, ckin, ckout, cvin, cvout); L.take(hints, nb + 1, 64);
+              HIPC(c, L.commit(LN(c).vtmp[5], 64 + (size_t)MS * 8)); }      // (8 MS: what two retired arrays took; no request shrinks with the layouts' restatement)
             const double cell = P.grid_stride > 0 ? P.grid_stride : std::max(4.0, P.col_rad); const double inv = 1.0 / cell;
-            int2* hints = (int2*)(LN(c).vtmp[5].as<uint8_t>() + (((size_t)MS * 24 + 63) & ~(size_t)63));
             // canvas of first stamps: read at sample pixels only, so k_samples initialises exactly those and marks them in a bit plane
             const int Wq = (W + 63) >> 6;
             HIPC(c, LN(c).canvas.ensure((size_t)W * H * 4 + 64));
@@ -1606,17 +1583,13 @@ extern "C" int orip_dedup_layer(orip_ctx* c, int layer, const orip_params08* prm
             unsigned long long* pixbits = LN(c).pixbits.as<unsigned long long>();
             HIPC(c, hipMemsetAsync(pixbits, 0, (size_t)Wq * H * 8, LN(c).stream));
             hipLaunchKernelGGL(k_sample_hints, dim3(cdiv(nb, 256)), dim3(256), 0, LN(c).stream, cumoff, cum, info, ord, sbase, nk, MS, step, nb, hints);
-            { ProfScope ps(c, "k_samples"); ORIP_WITH_SRC(c, kept0.p, sv, { hipLaunchKernelGGL(k_samples<decltype(sv)>, dim3(cdiv(nb, 4)), dim3(256), 0, LN(c).stream, sv, cumoff, cum, info, ord, sbase, nk, MS, step, W, H, A, inv, (unsigned*)nullptr, (unsigned*)nullptr, hints, (unsigned)nb, pixbits, Wq, firstseq); }); }
-            tick("samples");
+            { ProfScope ps(c, "k_samples"); ORIP_WITH_SRC(c, kept0, sv, { hipLaunchKernelGGL(k_samples<decltype(sv)>, dim3(cdiv(nb, 4)), dim3(256), 0, LN(c).stream, sv, cumoff, cum, info, ord, sbase, nk, MS, step, W, H, A, inv, (unsigned*)nullptr, (unsigned*)nullptr, hints, (unsigned)nb, pixbits, Wq, firstseq); }); }
+            T.tick("samples");
             // ---- A3
             {
-                HIPC(c, LN(c).vtmp[8].ensure((size_t)MS * 8 + (size_t)(nk + 1) * 4 + 64));
-                double* S = LN(c).vtmp[8].as<double>(); unsigned* redo = (unsigned*)(S + MS);
+                double* S; unsigned* redo; { Carve L; L.take(S, MS); L.take(redo, nk + 1); HIPC(c, L.commit(LN(c).vtmp[8], 64)); }
                 HIPC(c, hipMemsetAsync(redo, 0, (size_t)(nk + 1) * 4, LN(c).stream));
-                size_t bytes = 0;
-                HIPC(c, rocprim::inclusive_scan_by_key(nullptr, bytes, A.rank, A.dprev, S, (size_t)MS, rocprim::plus<double>(), rocprim::equal_to<unsigned>(), LN(c).stream));
-                HIPC(c, LN(c).tmpF.ensure(bytes + 16));
-                HIPC(c, rocprim::inclusive_scan_by_key(LN(c).tmpF.p, bytes, A.rank, A.dprev, S, (size_t)MS, rocprim::plus<double>(), rocprim::equal_to<unsigned>(), LN(c).stream));
+                HIPC(c, orip_with_tmp(c, [&](void* tmp, size_t& bytes) { return rocprim::inclusive_scan_by_key(tmp, bytes, A.rank, A.dprev, S, (size_t)MS, rocprim::plus<double>(), rocprim::equal_to<unsigned>(), LN(c).stream); }));
                 ProfScope ps(c, "k_tail_sim");
                 hipLaunchKernelGGL(k_tail_par, dim3(cdiv(MS, 256)), dim3(256), 0, LN(c).stream, sbase, A.rank, S, MS, P.tail_len_px, npop, redo);
                 if (getenv("ORIP_TAIL_DBG")) { std::vector<unsigned> h(nk), sb(nk + 1); hipStreamSynchronize(LN(c).stream); hipMemcpy(h.data(), redo, nk * 4, hipMemcpyDeviceToHost); hipMemcpy(sb.data(), sbase, (nk + 1) * 4, hipMemcpyDeviceToHost); unsigned long long nf = 0, sf = 0, mx = 0; for (int64_t q = 0; q < nk; q++) if (h[q]) { nf++; sf += sb[q + 1] - sb[q]; mx = std::max<unsigned long long>(mx, sb[q + 1] - sb[q]); } fprintf(stderr, "[tail dbg] layer %d: %llu of %lld polylines redone, %llu of %u samples, longest redone %llu\n", layer, nf, (long long)nk, sf, MS, mx); }
@@ -1629,17 +1602,13 @@ extern "C" int orip_dedup_layer(orip_ctx* c, int layer, const orip_params08* prm
             }
             if (any_out)
             {
-                HIPC(c, LN(c).vtmp[8].ensure((size_t)MS * 8 + (size_t)(nk + 1) * 4 + 64));
-                unsigned* lastin = LN(c).vtmp[8].as<unsigned>();            // the prefix sums of the tail simulation are no longer needed
+                unsigned* lastin = LN(c).vtmp[8].as<unsigned>();            // MS words over S: the prefix sums of the tail simulation are no longer needed
                 auto vin = rocprim::make_transform_iterator(rocprim::counting_iterator<unsigned>(0u), IncIndex{A.inc});
-                size_t bytes = 0;
-                HIPC(c, rocprim::inclusive_scan_by_key(nullptr, bytes, A.rank, vin, lastin, (size_t)MS, rocprim::maximum<unsigned>(), rocprim::equal_to<unsigned>(), LN(c).stream));
-                HIPC(c, LN(c).tmpF.ensure(bytes + 16));
-                HIPC(c, rocprim::inclusive_scan_by_key(LN(c).tmpF.p, bytes, A.rank, vin, lastin, (size_t)MS, rocprim::maximum<unsigned>(), rocprim::equal_to<unsigned>(), LN(c).stream));
+                HIPC(c, orip_with_tmp(c, [&](void* tmp, size_t& bytes) { return rocprim::inclusive_scan_by_key(tmp, bytes, A.rank, vin, lastin, (size_t)MS, rocprim::maximum<unsigned>(), rocprim::equal_to<unsigned>(), LN(c).stream); }));
                 hipLaunchKernelGGL(k_capprev, dim3(cdiv(MS, 256)), dim3(256), 0, LN(c).stream, sbase, MS, A, lastin, capprev);
             }
             else capprev = nullptr;       // every sample is on the canvas: "the previous in-canvas sample" is simply the previous one (k_caps_insert)
-            tick("tail");
+            T.tick("tail");
             // ---- A4: de-duplicated capsules -> min-sequence canvas
             // The table only has to hold the DISTINCT capsules (retraced paths repeat theirs many times).  Their number is not known in advance:
             // start from what this lane saw last time (a resident chain repeats itself; 3 slots per capsule), else from a quarter of the sample
@@ -1650,8 +1619,7 @@ extern "C" int orip_dedup_layer(orip_ctx* c, int layer, const orip_params08* prm
             tsize = std::min(tsize, tfull);
             if (getenv("ORIP_CAPS_TINY")) tsize = 1024;            // test hook: exercise the growth path
             CapSlot* tab = nullptr;
-            int* d_ovf = LN(c).flags.as<int>() + 62;
-            unsigned* d_dist = LN(c).flags.as<unsigned>() + 126;
+            int* d_ovf = &fl->caps_overflow; unsigned* d_dist = &fl->caps_distinct;
             for (;; tsize = std::min(tfull, tsize * 4)) {
                 HIPC(c, LN(c).vtmp[4].ensure((size_t)tsize * 16 + 64));
                 tab = LN(c).vtmp[4].as<CapSlot>();
@@ -1669,13 +1637,12 @@ extern "C" int orip_dedup_layer(orip_ctx* c, int layer, const orip_params08* prm
                 hipLaunchKernelGGL(k_caps_stamp_bits, sg, dim3(256), 0, LN(c).stream, tab, tsize, P.brush_forbid / 2, firstseq, W, H, pixbits, Wq, d_dist);
             }
             caps_counted = true;
-            tick("caps");
+            T.tick("caps");
             // ---- A5 / A6: cheap test of every sample, then _PointHash.near for the survivors
             {
                 HIPC(c, hipStreamWaitEvent(LN(c).stream, LN(c).ev3, 0));       // pop counts of the redone polylines
-                unsigned* surv = LN(c).vtmp[8].as<unsigned>();                  // (the scan results kept there have been consumed by k_capprev)
-                unsigned* d_ns = LN(c).flags.as<unsigned>() + 60;               // survivor count; the work sum is an 8-byte word of its own
-                unsigned long long* d_work = reinterpret_cast<unsigned long long*>(LN(c).flags.as<unsigned>() + 124);
+                unsigned* surv = LN(c).vtmp[8].as<unsigned>();                  // MS words again (the scan results kept there have been consumed by k_capprev)
+                unsigned* d_ns = &fl->accept_survivors; unsigned long long* d_work = &fl->accept_work;
                 HIPC(c, hipMemsetAsync(d_ns, 0, 4, LN(c).stream));
                 HIPC(c, hipMemsetAsync(d_work, 0, 8, LN(c).stream));
                 { ProfScope ps(c, "k_accept"); hipLaunchKernelGGL(k_accept_pre, dim3(cdiv(MS, 1024)), dim3(256), 0, LN(c).stream, A, sbase, npop, MS, firstseq, W, spt, sflag, surv, d_ns, d_work); }
@@ -1683,188 +1650,195 @@ extern "C" int orip_dedup_layer(orip_ctx* c, int layer, const orip_params08* prm
                 const double R2 = P.col_rad * P.col_rad;
                 // without the hash when it gives the hash's answer (cell >= radius) and costs less than sorting every sample into buckets
                 const bool brute = cell >= P.col_rad && h_work <= 64ull * (unsigned long long)MS && !getenv("ORIP_HASH_SORT");
-                if (tdbg) { char b2[64]; snprintf(b2, sizeof b2, " [near work %llu %s]", h_work, brute ? "direct" : "buckets"); tlog += b2; }
+                if (T.on) { char b2[64]; snprintf(b2, sizeof b2, " [near work %llu %s]", h_work, brute ? "direct" : "buckets"); T.log += b2; }
                 if (brute) {
                     ProfScope ps(c, "k_accept");
                     hipLaunchKernelGGL(k_accept_brute, dim3((unsigned)std::min<unsigned>(cdiv(MS, 256), 16384u)), dim3(256), 0, LN(c).stream, A, sbase, npop, R2, surv, d_ns, sflag);
                 } else {
                     // (polyline, cell) buckets in pop order: the samples of a polyline are contiguous, so its hash is its own range sorted by cell key
                     hipLaunchKernelGGL(k_cell_keys, dim3(cdiv(MS, 256)), dim3(256), 0, LN(c).stream, A, MS, inv, ckin, cvin);
-                    {
-                        ProfScope ps(c, "sort_cells");
-                        size_t bytes = 0;
-                        HIPC(c, rocprim::segmented_radix_sort_pairs(nullptr, bytes, ckin, ckout, cvin, cvout, (unsigned)MS, (unsigned)nk, sbase, sbase + 1, 0u, 32u, LN(c).stream));
-                        HIPC(c, LN(c).tmpF.ensure(bytes + 16));
-                        HIPC(c, rocprim::segmented_radix_sort_pairs(LN(c).tmpF.p, bytes, ckin, ckout, cvin, cvout, (unsigned)MS, (unsigned)nk, sbase, sbase + 1, 0u, 32u, LN(c).stream));
-                    }
+                    { ProfScope ps(c, "sort_cells"); HIPC(c, orip_with_tmp(c, [&](void* tmp, size_t& bytes) { return rocprim::segmented_radix_sort_pairs(tmp, bytes, ckin, ckout, cvin, cvout, (unsigned)MS, (unsigned)nk, sbase, sbase + 1, 0u, 32u, LN(c).stream); })); }
                     ProfScope ps(c, "k_accept");
                     hipLaunchKernelGGL(k_accept, dim3((unsigned)std::min<unsigned>(cdiv(MS, 256), 16384u)), dim3(256), 0, LN(c).stream, A, sbase, npop, inv, R2, ckout, cvout, surv, d_ns, sflag);
                 }
             }
             HIPC(c, hipGetLastError());
-            tick("accept");
-            ORIP_TRY(orip_runs_to_polys(c, spt, sflag, MS, cleaned.p));
-            tick("runs");
+            T.tick("accept");
+            ORIP_TRY(orip_runs_to_polys(c, spt, sflag, MS, cleaned));
+            T.tick("runs");
         }
         // ---- A7
-        ORIP_TRY(split_small(c, cleaned.p, P, lines2.p, TOUT.xy, nt0, &nt2));
+        ORIP_TRY(split_small(c, cleaned, P, lines2, TOUT.xy, nt0, &nt2));
     }
     TOUT.n = nt0 + nt2;
-    tick("A7");
-    // ---- B
-    DPolys* fin = &lines2.p;
-    const int64_t n2 = lines2.p.n;
-    if (P.post_on && n2 > 0) {
-        if (n2 > 0x3fffffff) ORIP_FAIL(c, "too many lines");
-        const int Wp = W + 2 * PAD8, Hp = H + 2 * PAD8; const size_t Np = (size_t)Wp * Hp;
-        if (Np >= (1ull << 27)) ORIP_FAIL(c, "canvas too large for stage 08-B index packing");
-        const int exp = P.post_brush * 2 + 6, rad = std::max(1, P.post_brush) / 2;
-        HIPC(c, LN(c).vtmp[6].ensure((size_t)n2 * sizeof(PolyFeat) + (size_t)(n2 + 1) * (4 + 4 + 4) + (size_t)n2 * sizeof(GroupInfo) + 256));
-        PolyFeat* f2 = LN(c).vtmp[6].as<PolyFeat>(); int* par = (int*)(f2 + n2); unsigned* is_root = (unsigned*)(par + (n2 + 1)); unsigned* root_scan = is_root + (n2 + 1);
-        GroupInfo* grp = (GroupInfo*)(root_scan + (n2 + 1) + ((3 * (n2 + 1)) & 1));
-        ORIP_TRY(vfeatures(c, lines2.p, 1, f2));
-        hipLaunchKernelGGL(k_iota, dim3(cdiv(n2, 256)), dim3(256), 0, LN(c).stream, par, (int)n2);
-        { ProfScope ps(c, "k_bbox_pairs"); hipLaunchKernelGGL(k_bbox_pairs, dim3((unsigned)std::min<int64_t>(n2, 8192)), dim3(256), 0, LN(c).stream, f2, (int)n2, exp, par); }
-        hipLaunchKernelGGL(k_group_init, dim3(cdiv(n2, 256)), dim3(256), 0, LN(c).stream, grp, (int)n2);
-        hipLaunchKernelGGL(k_group_accum, dim3(cdiv(n2 + 1, 256)), dim3(256), 0, LN(c).stream, f2, (int)n2, exp, par, grp, is_root);
-        ORIP_TRY(vscan_excl<unsigned>(c, is_root, root_scan, (size_t)n2 + 1));
-        hipLaunchKernelGGL(k_group_finish, dim3(cdiv(n2, 256)), dim3(256), 0, LN(c).stream, f2, (int)n2, is_root, root_scan, grp);
-        tick("groups");
-        // raster
-        HIPC(c, LN(c).canvas.ensure(Np * 4 + 64));
-        unsigned* gid = LN(c).canvas.as<unsigned>();
-        HIPC(c, hipMemsetAsync(gid, 0, Np * 4, LN(c).stream));
-        { ProfScope ps(c, "k_stamp_groups"); hipLaunchKernelGGL(k_stamp_groups, dim3(8192), dim3(256), 0, LN(c).stream, lines2.p.off.as<int64_t>(), lines2.p.pts.as<int32_t>(), n2, lines2.p.total, par, rad, gid, Wp, Hp); }
-        dim3 blk(256);
-        const size_t ntile_max = (size_t)cdiv(Wp, 64) * cdiv(Hp, 4);
-        const int Wwp = (Wp + 63) >> 6; const size_t nwords = (size_t)Hp * Wwp;
-        HIPC(c, LN(c).vtmp[9].ensure(Np * 2 + ntile_max * 4 + nwords * 16 + 256));
-        // skA: skeleton bytes; bA / bB: the thinning bit planes at byte offset 2 Np + 4 ntile_max (each term rounded up), where this scratch always had them
-        u8* skA = LN(c).vtmp[9].as<u8>();
-        unsigned long long* bA = (unsigned long long*)(skA + Np + ((Np + 15) & ~(size_t)15) + ((ntile_max + 3) & ~(size_t)3) * 4); unsigned long long* bB = bA + nwords;
-        const dim3 gwd((unsigned)cdiv((int64_t)nwords, 256));
-        hipLaunchKernelGGL(k_gid_to_bits, gwd, blk, 0, LN(c).stream, gid, bA, Hp, Wp, Wwp);      // 4 waves x 64 words per block
-        tick("raster");
-        // Twelve iterations before the first round trip to the host (16-px lines thin in 9 .. 12), four per round trip after that, each iteration with
-        // its own flag: an iteration after the first unchanged one changes nothing either, so running to the end of a batch leaves the image the
-        // reference's loop stops with (48 iterations at most: the same cap).  A batch is one launch, tile by tile in LDS.
-        int* d_chg = LN(c).flags.as<int>() + 240;
-        for (int it = 0; it < 48; ) {
-            const int nb = it == 0 ? 12 : 4;
-            HIPC(c, hipMemsetAsync(d_chg, 0, 48, LN(c).stream));
-            { ProfScope ps(c, "k_zs_sub"); hipLaunchKernelGGL(k_zs_tile, dim3((unsigned)cdiv(Wwp, 2), (unsigned)cdiv(Hp, ZS_TR)), blk, 0, LN(c).stream, bA, bB, Hp, Wwp, nb, d_chg); }
-            std::swap(bA, bB);
-            int ch[12] = {0}; ORIP_TRY(vread(c, ch, d_chg, 12));
-            bool all = true; for (int b = 0; b < nb; b++) all = all && ch[b] != 0;
-            if (!all) break;
-            it += nb;
-        }
-        hipLaunchKernelGGL(k_bits_to_mask, gwd, blk, 0, LN(c).stream, bA, skA, Hp, Wp, Wwp);
-        tick("thin");
-        // components of the thinned bit plane (bA)
-        HIPC(c, LN(c).vtmp[10].ensure(Np * 4 + 64));
-        int* L2 = LN(c).vtmp[10].as<int>();
-        hipLaunchKernelGGL(k_ccl2_bits, gwd, blk, 0, LN(c).stream, bA, L2, Hp, Wp, Wwp, 0);
-        { ProfScope ps(c, "k_ccl2_merge"); hipLaunchKernelGGL(k_ccl2_bits, gwd, blk, 0, LN(c).stream, bA, L2, Hp, Wp, Wwp, 1); }
-        hipLaunchKernelGGL(k_ccl2_bits, gwd, blk, 0, LN(c).stream, bA, L2, Hp, Wp, Wwp, 2);
-        tick("c:ccl");
-        const int nblk = (int)cdiv((int64_t)nwords, 256);
-        HIPC(c, LN(c).vtmp[0].ensure((size_t)(nblk + 1) * 8 + 64));
-        unsigned* bc = LN(c).vtmp[0].as<unsigned>(); unsigned* bo = bc + (nblk + 1);
-        HIPC(c, hipMemsetAsync(bc + nblk, 0, 4, LN(c).stream));
-        hipLaunchKernelGGL(k_sk_count_bits, dim3(nblk), blk, 0, LN(c).stream, bA, nwords, bc);
-        ORIP_TRY(vscan_excl<unsigned>(c, bc, bo, (size_t)nblk + 1));
-        unsigned M = 0; ORIP_TRY(vread(c, &M, bo + nblk));
-        if (M > 0) {
-            HIPC(c, LN(c).vtmp[1].ensure((size_t)M * 16 + 64));
-            unsigned* kin = LN(c).vtmp[1].as<unsigned>(); unsigned* lin_in = kin + M; unsigned* keys = lin_in + M; unsigned* lin = keys + M;
-            hipLaunchKernelGGL(k_sk_write_bits, dim3(nblk), blk, 0, LN(c).stream, bA, L2, nwords, Wp, Wwp, bo, kin, lin_in);
-            ORIP_TRY((vsort_pairs<unsigned, unsigned>(c, kin, keys, lin_in, lin, (size_t)M, 0, 27)));
-            HIPC(c, LN(c).vtmp[3].ensure((size_t)(M + 1) * 8 + 64));
-            unsigned* head = LN(c).vtmp[3].as<unsigned>(); unsigned* hs = head + (M + 1);
-            hipLaunchKernelGGL(k_heads2, dim3(cdiv(M + 1, 256)), blk, 0, LN(c).stream, keys, (int64_t)M, head);
-            ORIP_TRY(vscan_excl<unsigned>(c, head, hs, (size_t)M + 1));
-            unsigned NC = 0; ORIP_TRY(vread(c, &NC, hs + M));
-            HIPC(c, LN(c).vtmp[4].ensure((size_t)(NC + 1) * (4 + 8 + 8 + 4 + 4 + 4 + 4 + 4) + (size_t)NC * sizeof(GatherDesc) + 256));
-            unsigned long long* ckin = LN(c).vtmp[4].as<unsigned long long>(); unsigned long long* ckout = ckin + (NC + 1);
-            unsigned* cs = (unsigned*)(ckout + (NC + 1)); unsigned* cidx = cs + (NC + 2); unsigned* corder = cidx + (NC + 1); unsigned* outcnt = corder + (NC + 1);
-            unsigned* oflag = outcnt + (NC + 1); unsigned* oscan = oflag + (NC + 1); GatherDesc* pd = (GatherDesc*)(oscan + (NC + 1) + ((6 * (NC + 1) + 1) & 1) + 2);
-            hipLaunchKernelGGL(k_comp_starts2, dim3(cdiv(M, 256)), blk, 0, LN(c).stream, head, hs, (int64_t)M, cs, NC);
-            tick("c:sort");
-            hipLaunchKernelGGL(k_nearest_anchor, dim3(cdiv(M, 256)), blk, 0, LN(c).stream, lin, (int64_t)M, gid, Wp, grp);
-            tick("c:anchor");
-            hipLaunchKernelGGL(k_comp_keys, dim3(cdiv(NC, 128)), dim3(128), 0, LN(c).stream, cs, NC, lin, gid, Wp, grp, ckin, cidx);
-            ORIP_TRY((vsort_pairs<unsigned long long, unsigned>(c, ckin, ckout, cidx, corder, (size_t)NC, 0, 64)));
-            tick("comps");
-            // per-component path, resample, RDP
-            {
-                const double stp = P.post_step;
-                if (!(stp >= 1.0)) ORIP_FAIL(c, "postmerge_resample_step must be >= 1");
-                const double ratio = std::min(1.0, 1.41422 / stp);          // resample points per component pixel
-                auto pcap_of = [&](unsigned cap) { return (unsigned)(cap * ratio) + (unsigned)stp + 4u; };
-                auto cap_of = [&](size_t budget) {                             // bytes: 25/node + 13/resample point
-                    unsigned cap = (unsigned)((budget - 13.0 * (stp + 4.0) - 64.0) / (25.0 + 13.0 * ratio));
-                    return std::min(cap, 65000u) & ~7u;
-                };
-                const size_t lds0 = 32 * 1024, lds1 = 160 * 1024;
-                unsigned cap0 = cap_of(lds0), cap1 = cap_of(lds1);
-                if (const char* ov = getenv("ORIP_COMP_CAPS")) {          // test hook: force components into the larger classes
-                    unsigned a = 0, b2 = 0; if (sscanf(ov, "%u,%u", &a, &b2) == 2 && a >= 8 && a <= b2) { cap0 = std::min(cap0, a & ~7u); cap1 = std::min(cap1, b2 & ~7u); }
-                }
-                auto lds_bytes = [&](unsigned cap) { return (size_t)cap * 25 + (size_t)pcap_of(cap) * 13 + 16; };
-                // scratch: cid canvas (reuses the BFS canvas), nbr, class lists, global-class work arrays
-                HIPC(c, LN(c).vtmp[5].ensure(Np * 4 + (size_t)M * (32 + 4 + 4 + 4 + 8 + 8 + 1 + 1 + 8) + (size_t)(NC + 1) * 12 + 1024));
-                unsigned char* bump = LN(c).vtmp[5].as<unsigned char>();
-                auto take = [&](size_t bytes) { unsigned char* r = bump; bump += (bytes + 15) & ~(size_t)15; return r; };
-                unsigned* cid = (unsigned*)take(Np * 4); unsigned* nbr = (unsigned*)take((size_t)M * 32);
-                CompScratch X; X.prev = (unsigned*)take((size_t)M * 4); X.que = (unsigned*)take((size_t)M * 4); X.cum = (float*)take((size_t)M * 4);
-                X.P = (float2*)take((size_t)M * 8); X.stk = (int2*)take((size_t)M * 8); int2* outpts = (int2*)take((size_t)M * 8);
-                unsigned* l0 = (unsigned*)take((size_t)(NC + 1) * 4); unsigned* l1 = (unsigned*)take((size_t)(NC + 1) * 4); unsigned* l2 = (unsigned*)take((size_t)(NC + 1) * 4);
-                X.seen = (u8*)take(M); X.keep = (u8*)take(M);
-                unsigned* counts = LN(c).flags.as<unsigned>() + 56;
-                HIPC(c, hipMemsetAsync(counts, 0, 12, LN(c).stream));
-                hipLaunchKernelGGL(k_cid_fill, dim3(cdiv(M, 256)), blk, 0, LN(c).stream, lin, M, cid);
-                hipLaunchKernelGGL(k_nbr_build, dim3((unsigned)cdiv((int64_t)M * 8, 256)), blk, 0, LN(c).stream, lin, M, skA, cid, Wp, Hp, nbr);
-                hipLaunchKernelGGL(k_comp_classes, dim3(cdiv(NC, 256)), blk, 0, LN(c).stream, corder, NC, cs, cap0, cap1, std::max(2, P.post_minlen), counts, l0, l1, l2, outcnt);
-                CompArgs A; A.corder = corder; A.cs = cs; A.lin = lin; A.gid = gid; A.g = grp; A.cid = cid; A.nbr = nbr; A.Wp = Wp; A.min_len = P.post_minlen; A.step = stp;
-                A.eps = (float)P.post_eps; A.outpts = outpts; A.outcnt = outcnt;
-                static std::once_flag attr_once;            // several layer threads may arrive here together
-                static std::atomic<int> attr_err{0};
-                std::call_once(attr_once, [&] { orip_max_lds(k_comp_paths_lds, (int)lds1, attr_err); });
-                if (attr_err.load()) ORIP_FAIL(c, "hipFuncSetAttribute(k_comp_paths_lds) failed: %s", hipGetErrorString((hipError_t)attr_err.load()));
-                ProfScope ps(c, "k_comp_paths");
-                // the few large components are long serial chains: they start on the side stream while the many small ones run here
-                HIPC(c, hipEventRecord(LN(c).ev2, LN(c).stream));
-                HIPC(c, hipStreamWaitEvent(LN(c).stream2, LN(c).ev2, 0));
-                hipLaunchKernelGGL(k_comp_paths_lds, dim3(std::min(NC, 1024u)), dim3(64), lds_bytes(cap1), LN(c).stream2, A, l1, counts + 1, cap1, pcap_of(cap1));
-                hipLaunchKernelGGL(k_comp_paths_glb, dim3(std::min(NC, 1024u)), dim3(64), 0, LN(c).stream2, A, l2, counts + 2, X);
-                HIPC(c, hipEventRecord(LN(c).ev3, LN(c).stream2));
-                hipLaunchKernelGGL(k_comp_paths_lds, dim3(std::min(NC, 8192u)), dim3(64), lds_bytes(cap0), LN(c).stream, A, l0, counts + 0, cap0, pcap_of(cap0));
-                HIPC(c, hipStreamWaitEvent(LN(c).stream, LN(c).ev3, 0));
-                tick("paths");
-                hipLaunchKernelGGL(k_flag_nonzero, dim3(cdiv(NC + 1, 256)), blk, 0, LN(c).stream, outcnt, NC, oflag);
-                ORIP_TRY(vscan_excl<unsigned>(c, oflag, oscan, (size_t)NC + 1));
-                unsigned NP = 0; ORIP_TRY(vread(c, &NP, oscan + NC));
-                merged.p.n = 0; merged.p.total = 0; merged.p.set_explicit();
-                HIPC(c, merged.p.off.ensure(64)); HIPC(c, hipMemsetAsync(merged.p.off.p, 0, 8, LN(c).stream));
-                if (NP) {
-                    hipLaunchKernelGGL(k_path_desc, dim3(cdiv(NC, 256)), blk, 0, LN(c).stream, corder, cs, outcnt, oflag, oscan, NC, pd);
-                    ORIP_TRY(vgather(c, pd, NP, reinterpret_cast<const int32_t*>(outpts), merged.p));
-                }
-            }
-        } else { merged.p.n = 0; merged.p.total = 0; merged.p.set_explicit(); HIPC(c, merged.p.off.ensure(64)); HIPC(c, hipMemsetAsync(merged.p.off.p, 0, 8, LN(c).stream)); }
-        HIPC(c, hipGetLastError());
-        fin = &merged.p;
+    return 0;
+}
+// Stage 08-B: post-processing of lines2 (n2 > 0 of them) -> merged (tp[3])
+static int dedup08_b(orip_ctx* c, const orip_params08& P, PhaseTimer& T) {
+    const int W = P.W, H = P.H;
+    DPolys& lines2 = LN(c).tp[2]; DPolys& merged = LN(c).tp[3];
+    const int64_t n2 = lines2.n;
+    if (n2 > 0x3fffffff) ORIP_FAIL(c, "too many lines");
+    const int Wp = W + 2 * PAD8, Hp = H + 2 * PAD8; const size_t Np = (size_t)Wp * Hp;
+    if (Np >= (1ull << 27)) ORIP_FAIL(c, "canvas too large for stage 08-B index packing");
+    const int exp = P.post_brush * 2 + 6, rad = std::max(1, P.post_brush) / 2;
+    PolyFeat* f2; int* par; unsigned *is_root, *root_scan; GroupInfo* grp;
+    { Carve L; L.take(f2, n2); L.each(n2 + 1, par, is_root, root_scan); L.take(grp, n2); HIPC(c, L.commit(LN(c).vtmp[6], 256)); }
+    ORIP_TRY(vfeatures(c, lines2, 1, f2));
+    hipLaunchKernelGGL(k_iota, dim3(cdiv(n2, 256)), dim3(256), 0, LN(c).stream, par, (int)n2);
+    { ProfScope ps(c, "k_bbox_pairs"); hipLaunchKernelGGL(k_bbox_pairs, dim3((unsigned)std::min<int64_t>(n2, 8192)), dim3(256), 0, LN(c).stream, f2, (int)n2, exp, par); }
+    hipLaunchKernelGGL(k_group_init, dim3(cdiv(n2, 256)), dim3(256), 0, LN(c).stream, grp, (int)n2);
+    hipLaunchKernelGGL(k_group_accum, dim3(cdiv(n2 + 1, 256)), dim3(256), 0, LN(c).stream, f2, (int)n2, exp, par, grp, is_root);
+    ORIP_TRY(vscan_excl<unsigned>(c, is_root, root_scan, (size_t)n2 + 1));
+    hipLaunchKernelGGL(k_group_finish, dim3(cdiv(n2, 256)), dim3(256), 0, LN(c).stream, f2, (int)n2, is_root, root_scan, grp);
+    T.tick("groups");
+    // raster
+    HIPC(c, LN(c).canvas.ensure(Np * 4 + 64));
+    unsigned* gid = LN(c).canvas.as<unsigned>();
+    HIPC(c, hipMemsetAsync(gid, 0, Np * 4, LN(c).stream));
+    { ProfScope ps(c, "k_stamp_groups"); hipLaunchKernelGGL(k_stamp_groups, dim3(8192), dim3(256), 0, LN(c).stream, lines2.off.as<int64_t>(), lines2.pts.as<int32_t>(), n2, lines2.total, par, rad, gid, Wp, Hp); }
+    dim3 blk(256);
+    const size_t ntile_max = (size_t)cdiv(Wp, 64) * cdiv(Hp, 4);
+    const int Wwp = (Wp + 63) >> 6; const size_t nwords = (size_t)Hp * Wwp;
+    u8* skA; unsigned long long *bA, *bB;       // skeleton bytes; the two thinning bit planes
+    { Carve L; L.take(skA, Np); L.each(nwords, bA, bB);
+      HIPC(c, L.commit(LN(c).vtmp[VTL_STEPLOG], 256 + Np + ntile_max * 4)); }      // (Np + 4 ntile_max: what a second byte plane and a tile list took; no request shrinks here)
+    const dim3 gwd((unsigned)cdiv((int64_t)nwords, 256));
+    hipLaunchKernelGGL(k_gid_to_bits, gwd, blk, 0, LN(c).stream, gid, bA, Hp, Wp, Wwp);      // 4 waves x 64 words per block
+    T.tick("raster");
+    // Twelve iterations before the first round trip to the host (16-px lines thin in 9 .. 12), four per round trip after that, each iteration with
+    // its own flag: an iteration after the first unchanged one changes nothing either, so running to the end of a batch leaves the image the
+    // reference's loop stops with (48 iterations at most: the same cap).  A batch is one launch, tile by tile in LDS.
+    int* d_chg = LN(c).flags.as<LaneFlags>()->zs_changed;
+    for (int it = 0; it < 48; ) {
+        const int nb = it == 0 ? 12 : 4;
+        HIPC(c, hipMemsetAsync(d_chg, 0, sizeof(LaneFlags::zs_changed), LN(c).stream));
+        { ProfScope ps(c, "k_zs_sub"); hipLaunchKernelGGL(k_zs_tile, dim3((unsigned)cdiv(Wwp, 2), (unsigned)cdiv(Hp, ZS_TR)), blk, 0, LN(c).stream, bA, bB, Hp, Wwp, nb, d_chg); }
+        std::swap(bA, bB);
+        int ch[12] = {0}; ORIP_TRY(vread(c, ch, d_chg, 12));
+        bool all = true; for (int b = 0; b < nb; b++) all = all && ch[b] != 0;
+        if (!all) break;
+        it += nb;
     }
-    tick("gather");
+    hipLaunchKernelGGL(k_bits_to_mask, gwd, blk, 0, LN(c).stream, bA, skA, Hp, Wp, Wwp);
+    T.tick("thin");
+    // components of the thinned bit plane (bA)
+    HIPC(c, LN(c).vtmp[10].ensure(Np * 4 + 64));
+    int* L2 = LN(c).vtmp[10].as<int>();
+    hipLaunchKernelGGL(k_ccl2_bits, gwd, blk, 0, LN(c).stream, bA, L2, Hp, Wp, Wwp, 0);
+    { ProfScope ps(c, "k_ccl2_merge"); hipLaunchKernelGGL(k_ccl2_bits, gwd, blk, 0, LN(c).stream, bA, L2, Hp, Wp, Wwp, 1); }
+    hipLaunchKernelGGL(k_ccl2_bits, gwd, blk, 0, LN(c).stream, bA, L2, Hp, Wp, Wwp, 2);
+    T.tick("c:ccl");
+    const int nblk = (int)cdiv((int64_t)nwords, 256);
+    unsigned *bc, *bo; { Carve L; L.each(nblk + 1, bc, bo); HIPC(c, L.commit(LN(c).vtmp[0], 64)); }
+    HIPC(c, hipMemsetAsync(bc + nblk, 0, 4, LN(c).stream));
+    hipLaunchKernelGGL(k_sk_count_bits, dim3(nblk), blk, 0, LN(c).stream, bA, nwords, bc);
+    ORIP_TRY(vscan_excl<unsigned>(c, bc, bo, (size_t)nblk + 1));
+    unsigned M = 0; ORIP_TRY(vread(c, &M, bo + nblk));
+    if (M > 0) {
+        unsigned *kin, *lin_in, *keys, *lin;
+        { Carve L; L.each(M, kin, lin_in, keys, lin); HIPC(c, L.commit(LN(c).vtmp[1], 64)); }
+        hipLaunchKernelGGL(k_sk_write_bits, dim3(nblk), blk, 0, LN(c).stream, bA, L2, nwords, Wp, Wwp, bo, kin, lin_in);
+        ORIP_TRY((vsort_pairs<unsigned, unsigned>(c, kin, keys, lin_in, lin, (size_t)M, 0, 27)));
+        unsigned *head, *hs; { Carve L; L.each((size_t)M + 1, head, hs); HIPC(c, L.commit(LN(c).vtmp[3], 64)); }
+        hipLaunchKernelGGL(k_heads2, dim3(cdiv(M + 1, 256)), blk, 0, LN(c).stream, keys, (int64_t)M, head);
+        ORIP_TRY(vscan_excl<unsigned>(c, head, hs, (size_t)M + 1));
+        unsigned NC = 0; ORIP_TRY(vread(c, &NC, hs + M));
+        const size_t nc1 = (size_t)NC + 1;
+        unsigned long long *ckin, *ckout; unsigned *cs, *cidx, *corder, *outcnt, *oflag, *oscan; GatherDesc* pd;
+        { Carve L; L.each(nc1, ckin, ckout); L.take(cs, nc1 + 1);
+          L.each(nc1, cidx, corder, outcnt, oflag, oscan); L.take(pd, NC); HIPC(c, L.commit(LN(c).vtmp[4], 256)); }
+        hipLaunchKernelGGL(k_comp_starts2, dim3(cdiv(M, 256)), blk, 0, LN(c).stream, head, hs, (int64_t)M, cs, NC);
+        T.tick("c:sort");
+        hipLaunchKernelGGL(k_nearest_anchor, dim3(cdiv(M, 256)), blk, 0, LN(c).stream, lin, (int64_t)M, gid, Wp, grp);
+        T.tick("c:anchor");
+        hipLaunchKernelGGL(k_comp_keys, dim3(cdiv(NC, 128)), dim3(128), 0, LN(c).stream, cs, NC, lin, gid, Wp, grp, ckin, cidx);
+        ORIP_TRY((vsort_pairs<unsigned long long, unsigned>(c, ckin, ckout, cidx, corder, (size_t)NC, 0, 64)));
+        T.tick("comps");
+        // per-component path, resample, RDP
+        {
+            const double stp = P.post_step;
+            if (!(stp >= 1.0)) ORIP_FAIL(c, "postmerge_resample_step must be >= 1");
+            const double ratio = std::min(1.0, 1.41422 / stp);          // resample points per component pixel
+            auto pcap_of = [&](unsigned cap) { return (unsigned)(cap * ratio) + (unsigned)stp + 4u; };
+            auto cap_of = [&](size_t budget) {                             // bytes: 25/node + 13/resample point
+                unsigned cap = (unsigned)((budget - 13.0 * (stp + 4.0) - 64.0) / (25.0 + 13.0 * ratio));
+                return std::min(cap, 65000u) & ~7u;
+            };
+            const size_t lds0 = 32 * 1024, lds1 = 160 * 1024;
+            unsigned cap0 = cap_of(lds0), cap1 = cap_of(lds1);
+            if (const char* ov = getenv("ORIP_COMP_CAPS")) {          // test hook: force components into the larger classes
+                unsigned a = 0, b2 = 0; if (sscanf(ov, "%u,%u", &a, &b2) == 2 && a >= 8 && a <= b2) { cap0 = std::min(cap0, a & ~7u); cap1 = std::min(cap1, b2 & ~7u); }
+            }
+            auto lds_bytes = [&](unsigned cap) { return (size_t)cap * 25 + (size_t)pcap_of(cap) * 13 + 16; };
+            // scratch: cid canvas (reuses the BFS canvas), nbr, class lists, global-class work arrays
+            unsigned *cid, *nbr, *l0, *l1, *l2; int2* outpts; CompScratch X;
+            { Carve L; L.take(cid, Np); L.take(nbr, (size_t)M * 8); L.each(M, X.prev, X.que, X.cum, X.P, X.stk);
+              L.take(outpts, M); L.each(nc1, l0, l1, l2); L.each(M, X.seen, X.keep); HIPC(c, L.commit(LN(c).vtmp[5], 1024)); }
+            unsigned* counts = LN(c).flags.as<LaneFlags>()->comp_counts;
+            HIPC(c, hipMemsetAsync(counts, 0, sizeof(LaneFlags::comp_counts), LN(c).stream));
+            hipLaunchKernelGGL(k_cid_fill, dim3(cdiv(M, 256)), blk, 0, LN(c).stream, lin, M, cid);
+            hipLaunchKernelGGL(k_nbr_build, dim3((unsigned)cdiv((int64_t)M * 8, 256)), blk, 0, LN(c).stream, lin, M, skA, cid, Wp, Hp, nbr);
+            hipLaunchKernelGGL(k_comp_classes, dim3(cdiv(NC, 256)), blk, 0, LN(c).stream, corder, NC, cs, cap0, cap1, std::max(2, P.post_minlen), counts, l0, l1, l2, outcnt);
+            CompArgs A; A.corder = corder; A.cs = cs; A.lin = lin; A.gid = gid; A.g = grp; A.cid = cid; A.nbr = nbr; A.Wp = Wp; A.min_len = P.post_minlen; A.step = stp;
+            A.eps = (float)P.post_eps; A.outpts = outpts; A.outcnt = outcnt;
+            static std::once_flag attr_once;            // several layer threads may arrive here together
+            static std::atomic<int> attr_err{0};
+            std::call_once(attr_once, [&] { orip_max_lds(k_comp_paths_lds, (int)lds1, attr_err); });
+            if (attr_err.load()) ORIP_FAIL(c, "hipFuncSetAttribute(k_comp_paths_lds) failed: %s", hipGetErrorString((hipError_t)attr_err.load()));
+            ProfScope ps(c, "k_comp_paths");
+            // the few large components are long serial chains: they start on the side stream while the many small ones run here
+            HIPC(c, hipEventRecord(LN(c).ev2, LN(c).stream));
+            HIPC(c, hipStreamWaitEvent(LN(c).stream2, LN(c).ev2, 0));
+            hipLaunchKernelGGL(k_comp_paths_lds, dim3(std::min(NC, 1024u)), dim3(64), lds_bytes(cap1), LN(c).stream2, A, l1, counts + 1, cap1, pcap_of(cap1));
+            hipLaunchKernelGGL(k_comp_paths_glb, dim3(std::min(NC, 1024u)), dim3(64), 0, LN(c).stream2, A, l2, counts + 2, X);
+            HIPC(c, hipEventRecord(LN(c).ev3, LN(c).stream2));
+            hipLaunchKernelGGL(k_comp_paths_lds, dim3(std::min(NC, 8192u)), dim3(64), lds_bytes(cap0), LN(c).stream, A, l0, counts + 0, cap0, pcap_of(cap0));
+            HIPC(c, hipStreamWaitEvent(LN(c).stream, LN(c).ev3, 0));
+            T.tick("paths");
+            hipLaunchKernelGGL(k_flag_nonzero, dim3(cdiv(NC + 1, 256)), blk, 0, LN(c).stream, outcnt, NC, oflag);
+            ORIP_TRY(vscan_excl<unsigned>(c, oflag, oscan, (size_t)NC + 1));
+            unsigned NP = 0; ORIP_TRY(vread(c, &NP, oscan + NC));
+            merged.n = 0; merged.total = 0; merged.set_explicit();
+            HIPC(c, merged.off.ensure(64)); HIPC(c, hipMemsetAsync(merged.off.p, 0, 8, LN(c).stream));
+            if (NP) {
+                hipLaunchKernelGGL(k_path_desc, dim3(cdiv(NC, 256)), blk, 0, LN(c).stream, corder, cs, outcnt, oflag, oscan, NC, pd);
+                ORIP_TRY(vgather(c, pd, NP, reinterpret_cast<const int32_t*>(outpts), merged));
+            }
+        }
+    } else { merged.n = 0; merged.total = 0; merged.set_explicit(); HIPC(c, merged.off.ensure(64)); HIPC(c, hipMemsetAsync(merged.off.p, 0, 8, LN(c).stream)); }
+    HIPC(c, hipGetLastError());
+    return 0;
+}
+
+extern "C" int orip_dedup_layer(orip_ctx* c, int layer, const orip_params08* prm) {
+    orip_enter(c);
+    if (!prm || layer < 0 || layer >= ORIP_MAX_LAYERS) ORIP_FAIL(c, "bad arguments");
+    const orip_params08 P = *prm;
+    const int W = P.W, H = P.H;
+    ORIP_LANE_NODRAIN(c, layer + 1);       // stage 08 waits for the parts of its prefetch where it picks them up (split_small, A2)
+    if (W <= 0 || H <= 0 || W > 16383 || H > 16383) ORIP_FAIL(c, "canvas %dx%d out of range", W, H);
+    if (!(P.sample_step * 2.0 < P.max_jump)) ORIP_FAIL(c, "dedup_sample_step must be < max_join_jump_px / 2 (stage-A segments are assumed jump-free)");
+    DPolys& S = c->polys[ORIP_SLOT_SORTED][layer]; DPolys& OUT = c->polys[ORIP_SLOT_LINES_INTRA][layer]; DTaps& TOUT = c->taps[ORIP_TAPS_INTRA][layer];
+    OUT.n = 0; OUT.total = 0; OUT.set_explicit(); TOUT.n = 0;
+    HIPC(c, OUT.off.ensure(64)); HIPC(c, hipMemsetAsync(OUT.off.p, 0, 8, LN(c).stream));
+    HIPC(c, TOUT.xy.ensure(64));
+    if (S.n == 0) return 0;
+    DPolys& kept0 = LN(c).tp[0]; DPolys& cleaned = LN(c).tp[1]; DPolys& lines2 = LN(c).tp[2]; DPolys& merged = LN(c).tp[3];
+    for (DPolys* t : {&kept0, &cleaned, &lines2, &merged}) { t->n = 0; t->total = 0; t->set_explicit(); }
+    bool caps_counted = false; PhaseTimer T(c, "ORIP_TIME08");        // debug: per-phase wall times of this layer (adds stream syncs)
+    ORIP_TRY(dedup08_a(c, layer, P, S, TOUT, T, caps_counted));
+    T.tick("A7");
+    DPolys* fin = &lines2;
+    if (P.post_on && lines2.n > 0) { ORIP_TRY(dedup08_b(c, P, T)); fin = &merged; }
+    T.tick("gather");
     // ---- C
     ORIP_TRY(vreorder(c, *fin, OUT, 8));
-    unsigned h_dist = 0;
-    if (caps_counted) HIPC(c, hipMemcpyAsync(&h_dist, LN(c).flags.as<unsigned>() + 126, 4, hipMemcpyDeviceToHost, LN(c).stream));
+    unsigned h_dist = 0; if (caps_counted) HIPC(c, hipMemcpyAsync(&h_dist, &LN(c).flags.as<LaneFlags>()->caps_distinct, 4, hipMemcpyDeviceToHost, LN(c).stream));
     HIPC(c, hipStreamSynchronize(LN(c).stream));
-    if (caps_counted) { LN(c).caps_hint = h_dist; if (tdbg) { char b[48]; snprintf(b, sizeof b, " [caps distinct %u]", h_dist); tlog += b; } }
-    tick("reorder");
-    if (tdbg) fprintf(stderr, "[time08] layer %d (in %lld polys %lld pts, kept %lld pts, cleaned %lld/%lld, lines2 %lld/%lld):%s\n", layer, (long long)S.n, (long long)S.total, (long long)kept0.p.total, (long long)cleaned.p.n, (long long)cleaned.p.total, (long long)lines2.p.n, (long long)lines2.p.total, tlog.c_str());
+    if (caps_counted) { LN(c).caps_hint = h_dist; if (T.on) { char b[48]; snprintf(b, sizeof b, " [caps distinct %u]", h_dist); T.log += b; } }
+    T.tick("reorder");
+    if (T.on) fprintf(stderr, "[time08] layer %d (in %lld polys %lld pts, kept %lld pts, cleaned %lld/%lld, lines2 %lld/%lld):%s\n", layer, (long long)S.n, (long long)S.total, (long long)kept0.total, (long long)cleaned.n, (long long)cleaned.total, (long long)lines2.n, (long long)lines2.total, T.log.c_str());
     return 0;
 }
 

@@ -97,8 +97,7 @@ int orip_runs_to_polys(orip_ctx* c, const int2* spt, const uint8_t* sflag, unsig
     dst.n = 0; dst.total = 0; dst.set_explicit();
     HIPC(c, dst.off.ensure(64)); HIPC(c, hipMemsetAsync(dst.off.p, 0, 8, LN(c).stream));
     if (n_slots == 0) return 0;
-    HIPC(c, LN(c).vtmp[7].ensure((size_t)n_slots * 8 + 64));
-    unsigned* start = LN(c).vtmp[7].as<unsigned>(); unsigned* start_scan = start + n_slots;
+    unsigned *start, *start_scan; { Carve L; L.each(n_slots, start, start_scan); HIPC(c, L.commit(LN(c).vtmp[7], 64)); }
     hipLaunchKernelGGL(k_run_starts, dim3(cdiv(n_slots, 256)), dim3(256), 0, LN(c).stream, sflag, n_slots, start);
     ORIP_TRY(vscan_excl<unsigned>(c, start, start_scan, n_slots));
     unsigned a[2];
@@ -106,9 +105,8 @@ int orip_runs_to_polys(orip_ctx* c, const int2* spt, const uint8_t* sflag, unsig
     ORIP_TRY(vread(c, &a[1], start + (n_slots - 1)));
     unsigned n_runs = a[0] + a[1];
     if (n_runs == 0) return 0;
-    HIPC(c, LN(c).vtmp[8].ensure((size_t)(n_runs + 1) * 16 + (size_t)n_runs * sizeof(GatherDesc) + 256));
-    unsigned* rlen = LN(c).vtmp[8].as<unsigned>(); unsigned* rbegin = rlen + (n_runs + 1); unsigned* keep = rbegin + (n_runs + 1); unsigned* keep_scan = keep + (n_runs + 1);
-    GatherDesc* desc = (GatherDesc*)(keep_scan + (n_runs + 1) + 2);
+    unsigned *rlen, *rbegin, *keep, *keep_scan; GatherDesc* desc;
+    { Carve L; L.each((size_t)n_runs + 1, rlen, rbegin, keep, keep_scan); L.take(desc, n_runs); HIPC(c, L.commit(LN(c).vtmp[8], 256)); }
     HIPC(c, hipMemsetAsync(rlen, 0, (size_t)(n_runs + 1) * 4, LN(c).stream));
     hipLaunchKernelGGL(k_run_accum, dim3(cdiv(n_slots, 256)), dim3(256), 0, LN(c).stream, sflag, start, start_scan, n_slots, rlen, rbegin);
     hipLaunchKernelGGL(k_run_keep, dim3(cdiv(n_runs + 1, 256)), dim3(256), 0, LN(c).stream, rlen, n_runs, 2u, keep);
@@ -434,14 +432,9 @@ static int dedup_cross_layer_impl(orip_ctx* c, int src_layer, int layer, bool re
     const int rad_taps = (int)std::max<long long>(1, vs::round_half_even(P.D_taps / 2.0));
     u8* forb = LN(c).canvas.as<u8>();
     const int occ_w = (Wp + 63) >> 6, occ_h = (Hp + 31) >> 5;
-    HIPC(c, LN(c).vtmp[9].ensure((size_t)Wp * Hp * 2 + (size_t)occ_w * occ_h + 64));
-    u8* seeds = LN(c).vtmp[9].as<u8>(); u8* hd = seeds + (size_t)Wp * Hp; u8* occ = hd + (size_t)Wp * Hp;
-    const bool tdbg = getenv("ORIP_TIME10") != nullptr;
-    auto now = [&]() { hipStreamSynchronize(LN(c).stream); return std::chrono::steady_clock::now(); };
-    auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-    {
-
-        auto t0 = tdbg ? now() : std::chrono::steady_clock::time_point();
+    u8 *seeds, *hd, *occ; { Carve L; L.each((size_t)Wp * Hp, seeds, hd); L.take(occ, (size_t)occ_w * occ_h); HIPC(c, L.commit(LN(c).vtmp[9], 64)); }
+    PhaseTimer T(c, "ORIP_TIME10");
+    { T.lap();
         if (layer < 0 || layer >= ORIP_MAX_LAYERS) ORIP_FAIL(c, "bad layer %d", layer);
         DPolys& Lin = c->polys[ORIP_SLOT_LINES_INTRA][src_layer]; DPolys& Lout = c->polys[ORIP_SLOT_LINES_CROSS][layer];
         DTaps& Tin = c->taps[ORIP_TAPS_INTRA][src_layer]; DTaps& Tout = c->taps[ORIP_TAPS_CROSS][layer];
@@ -451,27 +444,25 @@ static int dedup_cross_layer_impl(orip_ctx* c, int src_layer, int layer, bool re
         ORIP_TRY(orip_polys_materialize(c, Lin));      // stage 08 leaves explicit lists; a walk-coded one set up by hand is expanded first
         if (Lin.n > 0 && Lin.total > 0) {
             if (Lin.total > 0x7fffffff) ORIP_FAIL(c, "layer too large");
-            HIPC(c, LN(c).vtmp[0].ensure((size_t)(Lin.total + 1) * 9 + 64));
-            unsigned* cnt = LN(c).vtmp[0].as<unsigned>(); unsigned* base = cnt + (Lin.total + 1); uint8_t* fop = (uint8_t*)(base + (Lin.total + 1));
+            unsigned *cnt, *base; uint8_t* fop;
+            { Carve L; L.each(Lin.total + 1, cnt, base, fop); HIPC(c, L.commit(LN(c).vtmp[0], 64)); }
             HIPC(c, hipMemsetAsync(cnt + Lin.total, 0, 4, LN(c).stream));
             hipLaunchKernelGGL(k_cut_counts, dim3((unsigned)std::min<int64_t>(Lin.n, 65535)), dim3(256), 0, LN(c).stream, Lin.off.as<int64_t>(), Lin.pts.as<int32_t>(), Lin.n, P.step_px, cnt, fop);
             ORIP_TRY(vscan_excl<unsigned>(c, cnt, base, (size_t)Lin.total + 1));
             unsigned n_slots = 0;
             ORIP_TRY(vread(c, &n_slots, base + Lin.total));
             if (n_slots) {
-                HIPC(c, LN(c).vtmp[1].ensure((size_t)n_slots * 9 + 64));
-                int2* spt = LN(c).vtmp[1].as<int2>(); uint8_t* sflag = (uint8_t*)(spt + n_slots);
+                int2* spt; uint8_t* sflag; { Carve L; L.each(n_slots, spt, sflag); HIPC(c, L.commit(LN(c).vtmp[1], 64)); }
                 { ProfScope ps(c, "k_cut_slots"); hipLaunchKernelGGL(k_cut_slots, dim3(cdiv(n_slots, 256)), dim3(256), 0, LN(c).stream, Lin.pts.as<int32_t>(), cnt, base, Lin.total, fop, n_slots, forb, H, W, spt, sflag); }
                 ORIP_TRY(orip_runs_to_polys(c, spt, sflag, n_slots, cut));
             }
         }
-        auto t1 = tdbg ? now() : t0;
+        const double ms_cut = T.lap();
         // ---- 2,3) jumps are the identity; tiny lines -> taps / dropped
         int64_t n_tap_lines = 0;
         keepl.n = 0; keepl.total = 0; keepl.set_explicit();
-        HIPC(c, LN(c).vtmp[2].ensure((size_t)(cut.n + 1) * (16 + 8 + sizeof(GatherDesc)) + 256));
-        unsigned* is_tap = LN(c).vtmp[2].as<unsigned>(); unsigned* is_keep = is_tap + (cut.n + 1); unsigned* tap_scan = is_keep + (cut.n + 1); unsigned* keep_scan = tap_scan + (cut.n + 1);
-        int2* tap_xy = (int2*)(keep_scan + (cut.n + 1)); GatherDesc* kd = (GatherDesc*)(tap_xy + (cut.n + 1));
+        unsigned *is_tap, *is_keep, *tap_scan, *keep_scan; int2* tap_xy; GatherDesc* kd;
+        { Carve L; L.each(cut.n + 1, is_tap, is_keep, tap_scan, keep_scan, tap_xy, kd); HIPC(c, L.commit(LN(c).vtmp[2], 256)); }
         int64_t n_seq = Tin.n;
         if (cut.n > 0) {
             HIPC(c, LN(c).vtmp[10].ensure((size_t)cut.n * sizeof(PolyFeat) + 64));
@@ -491,11 +482,10 @@ static int dedup_cross_layer_impl(orip_ctx* c, int src_layer, int layer, bool re
         }
         // taps_seq = taps_in + taps_from_lines
         n_seq = Tin.n + n_tap_lines;
-        HIPC(c, LN(c).vtmp[3].ensure((size_t)(n_seq + 1) * 16 + 64));
-        int2* seq = LN(c).vtmp[3].as<int2>(); int2* acc = seq + (n_seq + 1);
+        int2 *seq, *acc; { Carve L; L.each(n_seq + 1, seq, acc); HIPC(c, L.commit(LN(c).vtmp[3], 64)); }
         if (Tin.n) HIPC(c, hipMemcpyAsync(seq, Tin.xy.p, (size_t)Tin.n * 8, hipMemcpyDeviceToDevice, LN(c).stream));
         if (n_tap_lines) hipLaunchKernelGGL(k_compact_sel, dim3(cdiv(cut.n, 256)), dim3(256), 0, LN(c).stream, is_tap, tap_scan, cut.n, cut.off.as<int64_t>(), (GatherDesc*)nullptr, tap_xy, seq + Tin.n);
-        auto t2 = tdbg ? now() : t0;
+        const double ms_tiny = T.lap();
         // ---- 4) reorder (or hand the kept lines over as they are: orip_dedup_cross_layer_deferred)
         if (reorder_now) { ORIP_TRY(vreorder(c, keepl, Lout, 10)); c->cross_unordered[layer] = false; }
         else {
@@ -508,7 +498,7 @@ static int dedup_cross_layer_impl(orip_ctx* c, int src_layer, int layer, bool re
             HIPC(c, keepl.off.ensure(c->hw_cross_off)); HIPC(c, keepl.pts.ensure(c->hw_cross_pts));
             c->cross_unordered[layer] = true;
         }
-        auto t3 = tdbg ? now() : t0;
+        const double ms_reorder = T.lap();
         // ---- 5) paint lines (exact disc dilation of all vertices)
         // The usual case after stage 08 (tens of thousands of vertices on a 100-Mpixel canvas): discs written directly, each vertex only what its
         // predecessor's disc does not hold (k_stamp_chain).  The separable passes below cost three sweeps of the whole canvas whatever the number
@@ -524,12 +514,12 @@ static int dedup_cross_layer_impl(orip_ctx* c, int src_layer, int layer, bool re
             { ProfScope ps(c, "k_row_hdist"); hipLaunchKernelGGL(k_row_hdist, dim3(Hp), dim3(64), 0, LN(c).stream, seeds, hd, Hp, Wp); }
             { ProfScope ps(c, "k_col_cover"); hipLaunchKernelGGL(k_col_cover, dim3(cdiv(W, CC_TX), cdiv(H, CC_TY)), dim3(256), 0, LN(c).stream, hd, forb, H, W, Hp, Wp, rad_lines, occ, occ_w, occ_h); }
         }
-        auto t4 = tdbg ? now() : t0;
+        const double ms_paint = T.lap();
         // ---- 6) sequential taps
         Tout.n = 0;
         HIPC(c, Tout.xy.ensure((size_t)std::max<int64_t>(n_seq, 1) * 8 + 64));
         if (n_seq > 0) {
-            int* d_n = LN(c).flags.as<int>() + 44;
+            int* d_n = &LN(c).flags.as<LaneFlags>()->taps_kept;
             const size_t lds_t = (size_t)n_seq * 17 + 64;
             if (lds_t <= 150 * 1024 && !getenv("ORIP_TAPS_1WG")) {
                 static std::once_flag attr_once;            // several layer threads may arrive here together
@@ -549,7 +539,7 @@ static int dedup_cross_layer_impl(orip_ctx* c, int src_layer, int layer, bool re
         }
         HIPC(c, hipGetLastError());
         HIPC(c, hipStreamSynchronize(LN(c).stream));
-        if (tdbg) { auto t5 = now(); fprintf(stderr, "[time10] layer %d: cut %.2f  tiny/taps %.2f  reorder %.2f  paint %.2f  taps %.2f ms (lines in %lld pts %lld -> out %lld pts %lld)\n", layer, ms(t0, t1), ms(t1, t2), ms(t2, t3), ms(t3, t4), ms(t4, t5), (long long)Lin.n, (long long)Lin.total, (long long)Lout.n, (long long)Lout.total); }
+        if (T.on) { const double ms_taps = T.lap(); fprintf(stderr, "[time10] layer %d: cut %.2f  tiny/taps %.2f  reorder %.2f  paint %.2f  taps %.2f ms (lines in %lld pts %lld -> out %lld pts %lld)\n", layer, ms_cut, ms_tiny, ms_reorder, ms_paint, ms_taps, (long long)Lin.n, (long long)Lin.total, (long long)Lout.n, (long long)Lout.total); }
     }
     return 0;
 }

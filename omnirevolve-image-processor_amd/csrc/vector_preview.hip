@@ -61,8 +61,9 @@ extern "C" int orip_preview_cover(orip_ctx* c, int slot, int layer, int taps_whi
         ORIP_FAIL(c, "bad arguments");
     const int64_t np = (int64_t)W * H;
     HIPC(c, LN(c).canvas.ensure((size_t)np * 4 + 64));
-    HIPC(c, LN(c).vtmp[0].ensure((size_t)np + 64));
-    int* plane = LN(c).canvas.as<int>(); uint8_t* packed = LN(c).vtmp[0].as<uint8_t>();
+    DBuf& pk = LN(c).vtmp[VT0_KEYS];       // lane 0 (no lane is claimed here): a preview between orip_contours_prepare and the layers' traces overwrites the schedule
+    HIPC(c, pk.ensure((size_t)np + 64));
+    int* plane = LN(c).canvas.as<int>(); uint8_t* packed = pk.as<uint8_t>();
     if (line_cov) {
         DPolys& P = c->polys[slot][layer];
         HIPC(c, hipMemsetAsync(plane, 0, (size_t)np * 4, LN(c).stream));

@@ -58,8 +58,14 @@ typedef struct {
 } orip_params10;
 
 /* ---- context ---- */
+/* The first orip_create of the process makes sure, before its first HIP call, that GPU_MAX_HW_QUEUES holds at least 16 (the layer schedule needs its
+   streams on separate hardware queues): unset, empty, not a number or a smaller number becomes 16, a number from 16 to 32 is kept, and no value above 32
+   is ever written.  This only takes effect when that call is the process's first HIP call; a host that initialised HIP earlier keeps what it had. */
 int orip_create(int device_id, orip_ctx** out);
 void orip_destroy(orip_ctx* ctx);
+/* what the first orip_create of the process found in GPU_MAX_HW_QUEUES (-1: unset, empty or not a number) and the number it left there; -1, -1 before
+   any orip_create.  Either pointer may be NULL.  No context needed: a tool or test states with it which schedule a number was measured on. */
+void orip_hw_queues(int* found, int* left);
 const char* orip_last_error(orip_ctx* ctx);
 int orip_sync(orip_ctx* ctx);
 /* HIP-event timing of the named raster kernel since the last reset: total ms and launch count (bench.py roofline) */

@@ -9,12 +9,41 @@ void orip_enter(orip_ctx* c) {
     if (c) hipSetDevice(c->device);      // cheap (thread-local in the runtime); not cached here: the host application may switch devices too
 }
 
+// What to leave in GPU_MAX_HW_QUEUES, from its current value and the number the library wants: unset, empty, not a number or a number below `want`
+// -> `want`; anything else is left alone (returns 0: do not write).  Never returns more than ORIP_HW_QUEUES_MAX.  *found: the number read, -1 if none.
+static int orip_queue_decision(const char* cur, int want, int* found) {
+    *found = -1;
+    if (want > ORIP_HW_QUEUES_MAX) want = ORIP_HW_QUEUES_MAX;
+    if (cur && *cur) {
+        char* end = nullptr;
+        const long v = strtol(cur, &end, 10);
+        if (end != cur && *end == 0 && v >= 0 && v <= 0x7fffffffL) *found = (int)v;
+    }
+    return *found >= want ? 0 : want;
+}
+static std::once_flag queue_once;
+static int queue_found = -1, queue_left = -1;       // what the first orip_create of the process found in the variable and what it left there
+static void orip_claim_queues() {
+    std::call_once(queue_once, [] {
+        int found = -1;
+        const int put = orip_queue_decision(getenv("GPU_MAX_HW_QUEUES"), ORIP_HW_QUEUES_WANTED, &found);
+        if (put) { char b[16]; snprintf(b, sizeof b, "%d", put); setenv("GPU_MAX_HW_QUEUES", b, 1); }
+        queue_found = found; queue_left = put ? put : found;
+    });
+}
+extern "C" void orip_hw_queues(int* found, int* left) {
+    if (found) *found = queue_found;
+    if (left) *left = queue_left;
+}
+
 extern "C" int orip_create(int device_id, orip_ctx** out) {
     if (!out) return -1;
     *out = nullptr;
-    // one hardware queue per lane where the runtime still accepts it (HIP multiplexes streams onto GPU_MAX_HW_QUEUES = 4 queues by
-    // default, and kernels that share a queue run one after the other): only effective when this is the process's first HIP call
-    setenv("GPU_MAX_HW_QUEUES", "16", 0);
+    // Before the first HIP call: the hardware queues the layer schedule needs (orip_ctx.h: ORIP_HW_QUEUES_WANTED).  A smaller number that a launcher put
+    // into the variable is overridden -- such a default (HIP's own is 4) serialises the layers' lone-wave kernels behind each other: 122 against 74 ms per
+    // step at 4096^2 x 8 -- a larger one, up to ORIP_HW_QUEUES_MAX, is kept.  Only effective when this is the process's first HIP call: a host that
+    // initialised HIP earlier keeps the queues it had.
+    orip_claim_queues();
     orip_alloc_dbg = getenv("ORIP_ALLOC_DBG") != nullptr;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return -2;   // no GPU: fail loudly, there is no CPU path

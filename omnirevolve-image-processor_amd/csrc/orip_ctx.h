@@ -198,6 +198,11 @@ struct LaneRes {
 };
 extern thread_local int orip_tls_lane;
 #define LN(c) ((c)->ln[orip_tls_lane])
+// Hardware queues.  HIP multiplexes its streams onto GPU_MAX_HW_QUEUES hardware queues (4 when nothing is set) and kernels of different streams that
+// share a queue run one after the other; the layer schedule is full of lone-wave kernels that hold a queue for milliseconds (k_trace, k_greedy_nn_fast),
+// so it needs its active streams on separate queues.  The first orip_create of the process leaves at least ORIP_HW_QUEUES_WANTED in the variable
+// (orip_api.hip: orip_queue_decision); it never writes more than ORIP_HW_QUEUES_MAX.  16 against 20: DESIGN 8.
+enum { ORIP_HW_QUEUES_WANTED = 16, ORIP_HW_QUEUES_MAX = 32 };
 // HIP's current device is per host thread: every entry point selects the context's GPU for the calling thread (the layer pipelines
 // call in from pool threads, which would otherwise allocate and launch on device 0 of a multi-GPU node)
 struct orip_ctx;

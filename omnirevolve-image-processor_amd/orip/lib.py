@@ -11,6 +11,10 @@ LIB_PATH = os.path.join(_PKG, "liborip.so")
 # One hardware queue per lane (layer pipelines, raster stages, stage 10): HIP multiplexes its streams onto GPU_MAX_HW_QUEUES
 # (default 4) hardware queues and kernels sharing a queue run one after the other, so a short kernel of one layer would wait
 # behind a long walk of another.  Must be in the environment before the HIP runtime initialises (bench.py sets it before torch).
+# This line only fills an unset variable, for a host that starts HIP (torch) between this import and its first Device.  The request that
+# always holds is the library's own: the first orip_create of the process overrides a value below 16 that a launcher set (such a default
+# costs a third of the step: 122 against 74 ms at 4096^2 x 8) and keeps one from 16 to 32; it only takes effect when that call is the
+# process's first HIP call (a host that initialised HIP earlier keeps what it had).  orip_hw_queues reports what it found and left.
 os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 
 MAX_LAYERS = 16
@@ -37,7 +41,7 @@ _P = C.POINTER
 
 # name -> (restype, argtypes); every symbol include/orip.h declares
 SIGNATURES = {
-    "orip_create": (_i32, [_i32, _P(_vp)]), "orip_destroy": (None, [_vp]), "orip_last_error": (_cp, [_vp]), "orip_sync": (_i32, [_vp]),
+    "orip_create": (_i32, [_i32, _P(_vp)]), "orip_destroy": (None, [_vp]), "orip_hw_queues": (None, [_P(_i32), _P(_i32)]), "orip_last_error": (_cp, [_vp]), "orip_sync": (_i32, [_vp]),
     "orip_prof_reset": (_i32, [_vp]), "orip_prof_get": (_i32, [_vp, _cp, _P(_f64), _P(_i64)]), "orip_prof_enable": (_i32, [_vp, _i32]),
     "orip_resize_area": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32]),
     "orip_set_image": (_i32, [_vp, _vp, _i32, _i32]), "orip_lab_of": (_i32, [_vp, _vp, _i64, _vp]),

@@ -93,7 +93,13 @@ struct DPolys {
     uint64_t pf_tag = 0;        // != 0: the list is a permutation-with-flips of the list LaneRes::pf08 (same tag) was computed on
     bool scaled = false;        // reads the scaled tables of the WalkStore
     void set_explicit() { virt = false; pts_ok = true; pf_tag = 0; }
+    hipError_t clear(hipStream_t s) {      // the empty explicit list: no polylines, off[0] = 0
+        n = 0; total = 0; set_explicit();
+        const hipError_t e = off.ensure(64);
+        return e == hipSuccess ? hipMemsetAsync(off.p, 0, 8, s) : e;
+    }
 };
+static inline bool is_coded(const DPolys& P) { return P.virt && !P.pts_ok; }      // walk-coded and not expanded: the points come from the walk records
 // What stage 04 leaves per layer (raster04.hip: trace_finish) and every walk-coded list of the layer reads
 struct WalkStore {
     DBuf log;                   // the trace's state log (walker.h: 4 words per entry)
@@ -187,7 +193,7 @@ struct LaneRes {
     unsigned caps_hint = 0;               // distinct capsules of the lane's last stage-08-A run (sizes the next run's table)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     DPolys tp[6];   // persistent temporaries of the vector stages (no hipFree in steady state: hipFree synchronises the device)
-    // stage 08's order-independent front, computed on the side stream while stage 07's greedy chain runs (vector08.hip: prefetch08)
+    // stage 08's order-independent front, computed on the side stream while stage 07's greedy chain runs (vector08.hip: orip_prefetch08)
     struct Prefetch08 {
         bool pending = false;          // side-stream work the lane's main stream has not waited for yet (orip_pf08_drain)
         bool valid = false; uint64_t tag = 0; int64_t n = 0; int64_t tot_f = 0; double step = 0;
@@ -224,7 +230,7 @@ struct LaneGuard {
 #define ORIP_LANE_NODRAIN(ctx, lane_id)                                                                                      \
     LaneGuard _lane_guard((ctx), (lane_id));                                                                                 \
     if (!_lane_guard.ok) ORIP_FAIL(ctx, "lane %d is busy: another call is using this layer's stream and scratch", (int)(lane_id))
-// Stage 08's prefetch (vector08.hip: prefetch08) may still be running on the lane's side stream when stage 07 returns: stage 08 waits for its parts where it
+// Stage 08's prefetch (vector08.hip: orip_prefetch08) may still be running on the lane's side stream when stage 07 returns: stage 08 waits for its parts where it
 // consumes them; every other call that claims the lane puts its main stream behind the whole of it first (it reads the scaled list and the lane's scratch).
 #define ORIP_LANE(ctx, lane_id)                                                                                              \
     ORIP_LANE_NODRAIN(ctx, lane_id);                                                                                         \
@@ -296,19 +302,8 @@ template <class F> static inline hipError_t orip_with_tmp(orip_ctx* c, F&& run) 
     return e == hipSuccess ? run(LN(c).tmpF.p, bytes) : e;
 }
 
-#if defined(__HIPCC__)
-// one bit per pixel -> 0 / 255 bytes, 16 pixels (ONE 16-byte store) per thread: rows that are multiples of 64 wide (nw words per plane = H * W / 64),
-// blockIdx.z = plane.  Four bits become four bytes by a multiply that drops bit i at position 8 i (n * (1 + 2^7 + 2^14 + 2^21), no carries) and a mask.
-static __global__ __launch_bounds__(256) void k_bits_expand16(const unsigned long long* __restrict__ bits, uint8_t* __restrict__ dst, size_t nw) {
-    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (t >= nw * 4) return;
-    const unsigned long long w = bits[nw * blockIdx.z + (t >> 2)];
-    const unsigned n16 = (unsigned)(w >> ((t & 3) * 16)) & 0xffffu;
-    auto four = [](unsigned n4) { return (((n4 & 0xfu) * 0x00204081u) & 0x01010101u) * 0xffu; };
-    uint4 o; o.x = four(n16); o.y = four(n16 >> 4); o.z = four(n16 >> 8); o.w = four(n16 >> 12);
-    reinterpret_cast<uint4*>(dst + nw * 64 * blockIdx.z)[t] = o;
-}
-#endif
+// K bit planes of nw words each -> 0 / 255 byte planes, for rows that are multiples of 64 wide; enqueued on the calling lane's stream (raster02.hip)
+void orip_bits_expand16(orip_ctx* c, const unsigned long long* bits, uint8_t* dst, size_t nw, int K);
 // Time one kernel launch with HIP events on ctx->stream when profiling is enabled (bench.py roofline leg).
 struct ProfScope {
     orip_ctx* c; const char* name;
@@ -337,6 +332,8 @@ int orip_raster02_lab_tables(orip_ctx* c);
 int orip_contours_layer_impl(orip_ctx* c, int layer, bool sync);
 int orip_scale_vectors_impl(orip_ctx* c, int layer, float sx, float sy, float dx, float dy, bool sync);
 int orip_sort_contours_impl(orip_ctx* c, int layer, bool sync, const orip_params08* prm_for_prefetch = nullptr);
-int orip_prefetch08(orip_ctx* c, void* prm, DPolys& scaled, const void* feat07);
-// explicit points of a walk-coded list (no-op for explicit lists); on the calling lane's stream, not synchronised (vector.hip)
+// stage 08's order-independent front on the lane's side stream, called by stage 07 under its greedy chain with the features it has computed (vector08.hip)
+struct PolyFeat;
+int orip_prefetch08(orip_ctx* c, const orip_params08& prm, DPolys& scaled, const PolyFeat* feat07);
+// explicit points of a walk-coded list (no-op for explicit lists); on the calling lane's stream, not synchronised (vector_common.hip)
 int orip_polys_materialize(orip_ctx* c, DPolys& P);

@@ -590,6 +590,20 @@ __global__ __launch_bounds__(256) void k_bits_unpack(const unsigned long long* _
         d[q] = ((bits[((size_t)layer * H + y) * Ww + (x >> 6)] >> (x & 63)) & 1ULL) ? 255 : 0;
     }
 }
+// one bit per pixel -> 0 / 255 bytes, 16 pixels (ONE 16-byte store) per thread: rows that are multiples of 64 wide (nw words per plane = H * W / 64),
+// blockIdx.z = plane.  Four bits become four bytes by a multiply that drops bit i at position 8 i (n * (1 + 2^7 + 2^14 + 2^21), no carries) and a mask.
+__global__ __launch_bounds__(256) void k_bits_expand16(const unsigned long long* __restrict__ bits, uint8_t* __restrict__ dst, size_t nw) {
+    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= nw * 4) return;
+    const unsigned long long w = bits[nw * blockIdx.z + (t >> 2)];
+    const unsigned n16 = (unsigned)(w >> ((t & 3) * 16)) & 0xffffu;
+    auto four = [](unsigned n4) { return (((n4 & 0xfu) * 0x00204081u) & 0x01010101u) * 0xffu; };
+    uint4 o; o.x = four(n16); o.y = four(n16 >> 4); o.z = four(n16 >> 8); o.w = four(n16 >> 12);
+    reinterpret_cast<uint4*>(dst + nw * 64 * blockIdx.z)[t] = o;
+}
+void orip_bits_expand16(orip_ctx* c, const unsigned long long* bits, uint8_t* dst, size_t nw, int K) {      // (stage 03 expands its edge planes with it too)
+    hipLaunchKernelGGL(k_bits_expand16, dim3((unsigned)cdiv((int64_t)nw * 4, 256), 1, K), dim3(256), 0, LN(c).stream, bits, dst, nw);
+}
 __global__ __launch_bounds__(256) void k_morph_bits(const unsigned long long* __restrict__ src, unsigned long long* __restrict__ dst, int H, int W, int Ww, int k,
                                                      unsigned long long se, int dilate) {
     const int layer = blockIdx.z;
@@ -664,7 +678,7 @@ int orip_morph_open_close(orip_ctx* c, const u8* src, u8* dst, int K, int shape,
             hipLaunchKernelGGL(k_morph_bits, gw, block, 0, LN(c).stream, A, B, H, W, Ww, k, se, passes[i] == 1 ? 1 : 0);
             std::swap(A, B);
         }
-        if (unpack && (W & 63) == 0 && !getenv("ORIP_PACK_BYTES")) hipLaunchKernelGGL(k_bits_expand16, dim3((unsigned)cdiv((int64_t)nw * 4, 256), 1, K), block, 0, LN(c).stream, A, dst, nw);
+        if (unpack && (W & 63) == 0 && !getenv("ORIP_PACK_BYTES")) orip_bits_expand16(c, A, dst, nw, K);
         else if (unpack) hipLaunchKernelGGL(k_bits_unpack, dim3((unsigned)cdiv((int64_t)plane, 1024), 1, K), block, 0, LN(c).stream, A, dst, H, W, Ww);
         else c->morphed_bits = A;
         HIPC(c, hipGetLastError());

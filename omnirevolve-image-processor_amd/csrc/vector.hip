@@ -23,20 +23,6 @@ __global__ __launch_bounds__(256) void k_scale_ents(const unsigned* __restrict__
     }
 }
 
-// explicit points of a walk-coded list, on request (orip_get_polys, consumers that read int32 pairs); enqueued on the calling lane's stream
-int orip_polys_materialize(orip_ctx* c, DPolys& P) {
-    if (!is_coded(P)) return 0;
-    VSrc src; ORIP_TRY(vsrc_of(c, P, src));
-    HIPC(c, P.pts.ensure((size_t)std::max<int64_t>(P.total, 1) * 8 + 64));
-    if (P.n > 0 && P.total > 0) {
-        ProfScope ps(c, "k_expand_pts");
-        hipLaunchKernelGGL(k_expand_pts<VSrc>, dim3((unsigned)cdiv(P.total, 4096)), dim3(256), 0, LN(c).stream, src, P.n, reinterpret_cast<int2*>(P.pts.p), P.total);
-    }
-    HIPC(c, hipGetLastError());
-    P.pts_ok = true;
-    return 0;
-}
-
 // `sync`: the public entry points return with the lane's stream drained (the caller may read the slot from another lane next);
 // orip_layer_front chains the stages of a layer on one stream and skips the waits in between
 int orip_scale_vectors_impl(orip_ctx* c, int layer, float sx, float sy, float dx, float dy, bool sync) {
@@ -87,14 +73,13 @@ extern "C" int orip_scale_vectors(orip_ctx* c, int layer, float sx, float sy, fl
     return orip_scale_vectors_impl(c, layer, sx, sy, dx, dy, true);
 }
 
-static int hook_prefetch08(orip_ctx* c, void* arg, DPolys& src, const PolyFeat* feat) { return orip_prefetch08(c, arg, src, feat); }
 int orip_sort_contours_impl(orip_ctx* c, int layer, bool sync, const orip_params08* prm_for_prefetch) {
     if (layer < 0 || layer >= ORIP_MAX_LAYERS) ORIP_FAIL(c, "bad layer %d", layer);
     ORIP_LANE(c, layer + 1);
     LN(c).pf08.valid = false;
     DPolys& S = c->polys[ORIP_SLOT_SCALED][layer]; DPolys& D = c->polys[ORIP_SLOT_SORTED][layer];
     const bool pf = prm_for_prefetch && is_coded(S) && S.vident && S.n > 0 && !getenv("ORIP_NO_PREFETCH08");
-    ORIP_TRY(vreorder(c, S, D, 7, pf ? hook_prefetch08 : nullptr, (void*)prm_for_prefetch));
+    ORIP_TRY(vreorder(c, S, D, 7, pf ? prm_for_prefetch : nullptr));
     if (pf && LN(c).pf08.valid) D.pf_tag = LN(c).pf08.tag;
     if (sync) HIPC(c, hipStreamSynchronize(LN(c).stream));
     return 0;
@@ -216,6 +201,18 @@ __global__ __launch_bounds__(1024) void k_plot_order(const PolyFeat* __restrict_
     (void)found;
 }
 
+// minimum of a 64-bit key over the wavefront with DPP row shifts / broadcasts (no LDS round trips); every lane gets the result
+__device__ __forceinline__ unsigned long long wave_min_key(unsigned long long v) {
+#define ORIP_DPP_MIN(ctrl, rmask) { \
+        unsigned lo_ = (unsigned)__builtin_amdgcn_update_dpp((int)0xffffffffu, (int)(unsigned)v, ctrl, rmask, 0xf, false); \
+        unsigned hi_ = (unsigned)__builtin_amdgcn_update_dpp((int)0xffffffffu, (int)(unsigned)(v >> 32), ctrl, rmask, 0xf, false); \
+        unsigned long long t_ = ((unsigned long long)hi_ << 32) | lo_; if (t_ < v) v = t_; }
+    ORIP_DPP_MIN(0x111, 0xf) ORIP_DPP_MIN(0x112, 0xf) ORIP_DPP_MIN(0x114, 0xf) ORIP_DPP_MIN(0x118, 0xf)      // row_shr 1, 2, 4, 8
+    ORIP_DPP_MIN(0x142, 0xa) ORIP_DPP_MIN(0x143, 0xc)                                                          // row_bcast 15, 31
+#undef ORIP_DPP_MIN
+    unsigned rl = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, 63), rh = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), 63);
+    return ((unsigned long long)rh << 32) | rl;
+}
 // The same greedy as ONE wavefront over LDS-resident end points, taps and alive flags (a layer has a few hundred to a few thousand
 // ops): every choice is a 64-wide scan + DPP minimum with no barrier and no global-memory round trip; the ops leave through a
 // 64-entry ring.  Same keys, same tie-breaks (line k start, line k end, ..., then taps; exact integer d^2).

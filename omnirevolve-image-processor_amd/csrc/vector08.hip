@@ -10,6 +10,7 @@
 // Stage B (_post_skeleton_merge, 08:376-469) runs all clusters at once on one padded canvas: clusters are >= 76 px apart
 // in one axis, so per-ROI rasterise / thin / label equals whole-canvas rasterise / thin / label (DESIGN.md "stage 08-B").
 #include "vec_common.h"
+#include <rocprim/rocprim.hpp>
 #include <chrono>
 #include <string>
 #include <type_traits>
@@ -146,7 +147,7 @@ __device__ __forceinline__ float cum_window(float dval, int lane, unsigned& E, u
     return __uint_as_float(out);
 }
 __device__ __forceinline__ float cum_state_value(unsigned E, unsigned M) { return __uint_as_float((E << 23) | (M & 0x7fffffu)); }
-// ---- both reading directions of every polyline in one launch (prefetch08): the reversed polyline has the same segment lengths in
+// ---- both reading directions of every polyline in one launch (orip_prefetch08): the reversed polyline has the same segment lengths in
 // reverse order, and its float32 running sum is a second, independent serial chain -- two chains interleave in one wavefront for the
 // price of one (a dependent add waits ~10 cycles for its predecessor anyway).  Forward = the polyline as split_small keeps it (opened
 // when closed); reversed = all its points backwards (stage 07 never flips a closed contour, so closed ones get no reversed entry).
@@ -196,7 +197,7 @@ __device__ __forceinline__ int2 lane_succ(const int2 v, const int2 last, int lan
     return r;
 }
 // One wavefront reads one long polyline in one direction: slot-th of n_slots waves of that direction, longest polylines first (ord).
-// seg != nullptr (prefetch08): the float32 length of every segment is already there (k_seglen), so a reading costs 4 bytes per segment instead of
+// seg != nullptr (orip_prefetch08): the float32 length of every segment is already there (k_seglen), so a reading costs 4 bytes per segment instead of
 // turning (polyline, index) into a point again (~25 instructions; the launches are bound by instruction issue).
 template <class Src>
 __device__ __forceinline__ void cumlen_long_wave(const Src& src, int64_t n_polys, double step, float* __restrict__ cum, int64_t rev_off, RsInfo* __restrict__ info,
@@ -262,7 +263,7 @@ __global__ __launch_bounds__(64) void k_cumlen_long2(Src src, int64_t n_polys, d
                                                      int dir0, const float* __restrict__ seg) {
     cumlen_long_wave<Src>(src, n_polys, step, cum, rev_off, info, ord, ((blockIdx.y + (unsigned)dir0) & 1u) != 0, seg, blockIdx.x, gridDim.x, threadIdx.x);
 }
-// prefetch08: float32 length of EVERY segment of the long polylines (seg[off[i] + k] = |P(k + 1) - P(k)|, k < len(i) - 1) and the bounding box of their open
+// orip_prefetch08: float32 length of EVERY segment of the long polylines (seg[off[i] + k] = |P(k + 1) - P(k)|, k < len(i) - 1) and the bounding box of their open
 // views (points [0, bb[i].n); bb[i] holds the first point's box on entry: k_poly_features), fully parallel: a wave takes 64 windows of 64 consecutive points
 // of the FLAT point list, advancing by 63, so the far end of a lane's segment is the point in the next lane and every lane's cursor stays on consecutive
 // points of (mostly) one polyline.  Both readings' cumulative lengths then run side by side from these lengths (one launch) instead of
@@ -1417,7 +1418,8 @@ struct StreamSwap {       // everything issued while this lives goes to the lane
     ~StreamSwap() { std::swap(l.stream, l.stream2); }
 };
 static std::atomic<uint64_t> g_pf_tag{1};
-static int prefetch08(orip_ctx* c, const orip_params08& P, DPolys& S, const PolyFeat* feat07) {
+}  // namespace
+int orip_prefetch08(orip_ctx* c, const orip_params08& P, DPolys& S, const PolyFeat* feat07) {
     LaneRes::Prefetch08& F = LN(c).pf08;
     F.valid = false;
     const int64_t n = S.n, total = S.total;
@@ -1434,14 +1436,13 @@ static int prefetch08(orip_ctx* c, const orip_params08& P, DPolys& S, const Poly
         PolyFeat* ff = F.feat.as<PolyFeat>(); float* per_rev = reinterpret_cast<float*>(ff + n); RsInfo* inf = F.info.as<RsInfo>(); float* cum = F.cum.as<float>();
         VSrc sS; ORIP_TRY(vsrc_of(c, S, sS));
         // per-polyline fields first (open view, end points; bounding box and perimeters of the short ones): one thread per polyline
-        hipLaunchKernelGGL(k_poly_features<VSrc>, dim3(cdiv(n, 128)), dim3(128), 0, LN(c).stream, sS, n, 1 | 16 | 32, ff, per_rev);
+        vfeatures_short(c, sS, n, 1 | 16 | 32, ff, per_rev);
         // A2 (the long polylines): cumulative lengths of both readings, longest first.  k_seglen fetches the points (once each) and leaves every segment's
         // float32 length in F.seg and the open view's bounding box in ff; both readings and the perimeter sums (A0 / A1, forwards and backwards) then
         // read 4 bytes per segment instead of turning (polyline, index) into a point again.
         unsigned* kin = F.ord.as<unsigned>(); unsigned* kout = kin + n; unsigned* vin = kout + n; unsigned* ordl = vin + n;
         float* seg = F.seg.as<float>();
-        hipLaunchKernelGGL(k_len_keys, dim3(cdiv(n, 256)), dim3(256), 0, LN(c).stream, S.off.as<int64_t>(), n, kin, vin);
-        ORIP_TRY((vsort_pairs<unsigned, unsigned>(c, kin, kout, vin, ordl, (size_t)n, 0, 32, true)));
+        ORIP_TRY(vlen_order(c, S.off.as<int64_t>(), n, kin, kout, vin, ordl));
         // (the sort borrows the lane's scan / sort scratch: the main stream, which sits in the greedy chain for milliseconds yet, takes it back behind this point)
         HIPC(c, hipEventRecord(LN(c).ev4, LN(c).stream));
         HIPC(c, hipStreamWaitEvent(LN(c).stream2 /* the main stream while the swap lives */, LN(c).ev4, 0));
@@ -1449,12 +1450,7 @@ static int prefetch08(orip_ctx* c, const orip_params08& P, DPolys& S, const Poly
         // up a dozen launches and a host read later, follow (ev3).
         if (total > ORIP_LONG_CUM) {
             { ProfScope ps(c, "k_seglen"); hipLaunchKernelGGL(k_seglen<VSrc>, dim3((unsigned)cdiv(total, 4 * 63 * 64)), dim3(256), 0, LN(c).stream, sS, n, total, seg, ff); }
-            if (total > ORIP_LONG_POLY) { ProfScope ps(c, "k_poly_features_long");
-                const size_t nleaf = (size_t)(total >> 6) + 2 * (size_t)n + 8;
-                HIPC(c, LN(c).vtmp[VT_LEAVES].ensure(nleaf * sizeof(float) * 2 + 64));
-                float* leafbuf = LN(c).vtmp[VT_LEAVES].as<float>(); float* leafbuf_rev = leafbuf + nleaf;      // (one array: forward leaves, then the reversed reading's)
-                hipLaunchKernelGGL(k_perim_leaves_seg, dim3((unsigned)cdiv((int64_t)nleaf * 8, 256)), dim3(256), 0, LN(c).stream, sS.off, n, ff, seg, leafbuf, leafbuf_rev, (int64_t)nleaf);
-                hipLaunchKernelGGL((k_poly_features_long<VSrc, true>), dim3((unsigned)std::min<int64_t>(n, 4096)), dim3(256), 0, LN(c).stream, sS, n, 1 | 16 | 32 | 64, ff, leafbuf, ordl, per_rev, leafbuf_rev, seg); }
+            if (total > ORIP_LONG_POLY) ORIP_TRY(vfeatures_long_seg(c, sS, n, total, ff, ordl, per_rev, seg));
         }
         HIPC(c, hipEventRecord(LN(c).ev4, LN(c).stream));
         { ProfScope ps(c, "k_cumlen"); hipLaunchKernelGGL(k_cumlen2<VSrc>, dim3(cdiv(2 * n, 128)), dim3(128), 0, LN(c).stream, sS, feat07, n, step, cum, total, inf); }
@@ -1467,6 +1463,7 @@ static int prefetch08(orip_ctx* c, const orip_params08& P, DPolys& S, const Poly
     F.valid = true; F.tag = g_pf_tag.fetch_add(1); F.n = n; F.tot_f = total; F.step = step; F.src_off = S.off.as<int64_t>();
     return 0;
 }
+namespace {
 
 // split_small_and_taps on a DPolys -> kept (opened) + taps appended to tapbuf at tap_base
 __global__ __launch_bounds__(256) void k_compact_feat(const unsigned* __restrict__ flag, const unsigned* __restrict__ scan, int64_t n, const PolyFeat* __restrict__ in, PolyFeat* __restrict__ out) {
@@ -1476,8 +1473,8 @@ __global__ __launch_bounds__(256) void k_compact_feat(const unsigned* __restrict
 // kept_feat (optional, room for src.n entries): features of the kept polylines' open views (bbox + numpy perimeter), so the caller
 // does not have to read the points again
 int split_small(orip_ctx* c, DPolys& src, const orip_params08& P, DPolys& kept, DBuf& tapbuf, int64_t tap_base, int64_t* n_taps_out, PolyFeat* kept_feat = nullptr) {
-    kept.n = 0; kept.total = 0; kept.set_explicit(); *n_taps_out = 0;
-    HIPC(c, kept.off.ensure(64)); HIPC(c, hipMemsetAsync(kept.off.p, 0, 8, LN(c).stream));
+    *n_taps_out = 0;
+    HIPC(c, kept.clear(LN(c).stream));
     int64_t n = src.n;
     if (n == 0) return 0;
     unsigned *is_tap, *is_keep, *tap_scan, *keep_scan; int2* tap_xy; GatherDesc *kd, *kd2;
@@ -1517,10 +1514,6 @@ __global__ __launch_bounds__(256) void k_fill_per(const PolyFeat* __restrict__ f
 
 
 }  // namespace
-
-int orip_prefetch08(orip_ctx* c, void* prm, DPolys& scaled, const void* feat07) {
-    return prefetch08(c, *static_cast<const orip_params08*>(prm), scaled, static_cast<const PolyFeat*>(feat07));
-}
 
 // Stage 08-A (A0 .. A7): the kept polylines resampled, stamped and tested -> lines2 (tp[2]) and the layer's taps.  caps_counted: flags.caps_distinct holds this run's count.
 static int dedup08_a(orip_ctx* c, int layer, const orip_params08& P, DPolys& S, DTaps& TOUT, PhaseTimer& T, bool& caps_counted) {
@@ -1799,14 +1792,13 @@ static int dedup08_b(orip_ctx* c, const orip_params08& P, PhaseTimer& T) {
             hipLaunchKernelGGL(k_flag_nonzero, dim3(cdiv(NC + 1, 256)), blk, 0, LN(c).stream, outcnt, NC, oflag);
             ORIP_TRY(vscan_excl<unsigned>(c, oflag, oscan, (size_t)NC + 1));
             unsigned NP = 0; ORIP_TRY(vread(c, &NP, oscan + NC));
-            merged.n = 0; merged.total = 0; merged.set_explicit();
-            HIPC(c, merged.off.ensure(64)); HIPC(c, hipMemsetAsync(merged.off.p, 0, 8, LN(c).stream));
+            HIPC(c, merged.clear(LN(c).stream));
             if (NP) {
                 hipLaunchKernelGGL(k_path_desc, dim3(cdiv(NC, 256)), blk, 0, LN(c).stream, corder, cs, outcnt, oflag, oscan, NC, pd);
                 ORIP_TRY(vgather(c, pd, NP, reinterpret_cast<const int32_t*>(outpts), merged));
             }
         }
-    } else { merged.n = 0; merged.total = 0; merged.set_explicit(); HIPC(c, merged.off.ensure(64)); HIPC(c, hipMemsetAsync(merged.off.p, 0, 8, LN(c).stream)); }
+    } else HIPC(c, merged.clear(LN(c).stream));
     HIPC(c, hipGetLastError());
     return 0;
 }
@@ -1820,8 +1812,8 @@ extern "C" int orip_dedup_layer(orip_ctx* c, int layer, const orip_params08* prm
     if (W <= 0 || H <= 0 || W > 16383 || H > 16383) ORIP_FAIL(c, "canvas %dx%d out of range", W, H);
     if (!(P.sample_step * 2.0 < P.max_jump)) ORIP_FAIL(c, "dedup_sample_step must be < max_join_jump_px / 2 (stage-A segments are assumed jump-free)");
     DPolys& S = c->polys[ORIP_SLOT_SORTED][layer]; DPolys& OUT = c->polys[ORIP_SLOT_LINES_INTRA][layer]; DTaps& TOUT = c->taps[ORIP_TAPS_INTRA][layer];
-    OUT.n = 0; OUT.total = 0; OUT.set_explicit(); TOUT.n = 0;
-    HIPC(c, OUT.off.ensure(64)); HIPC(c, hipMemsetAsync(OUT.off.p, 0, 8, LN(c).stream));
+    TOUT.n = 0;
+    HIPC(c, OUT.clear(LN(c).stream));
     HIPC(c, TOUT.xy.ensure(64));
     if (S.n == 0) return 0;
     DPolys& kept0 = LN(c).tp[0]; DPolys& cleaned = LN(c).tp[1]; DPolys& lines2 = LN(c).tp[2]; DPolys& merged = LN(c).tp[3];

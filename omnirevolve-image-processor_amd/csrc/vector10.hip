@@ -94,8 +94,7 @@ __global__ __launch_bounds__(256) void k_run_desc(const unsigned* __restrict__ r
 
 // Shared by stage 08-A and stage 10: turn per-slot flags (bit0 accepted, bit1 sequence start) + points into a DPolys of runs with >= 2 points
 int orip_runs_to_polys(orip_ctx* c, const int2* spt, const uint8_t* sflag, unsigned n_slots, DPolys& dst) {
-    dst.n = 0; dst.total = 0; dst.set_explicit();
-    HIPC(c, dst.off.ensure(64)); HIPC(c, hipMemsetAsync(dst.off.p, 0, 8, LN(c).stream));
+    HIPC(c, dst.clear(LN(c).stream));
     if (n_slots == 0) return 0;
     unsigned *start, *start_scan; { Carve L; L.each(n_slots, start, start_scan); HIPC(c, L.commit(LN(c).vtmp[7], 64)); }
     hipLaunchKernelGGL(k_run_starts, dim3(cdiv(n_slots, 256)), dim3(256), 0, LN(c).stream, sflag, n_slots, start);
@@ -489,7 +488,7 @@ static int dedup_cross_layer_impl(orip_ctx* c, int src_layer, int layer, bool re
         // ---- 4) reorder (or hand the kept lines over as they are: orip_dedup_cross_layer_deferred)
         if (reorder_now) { ORIP_TRY(vreorder(c, keepl, Lout, 10)); c->cross_unordered[layer] = false; }
         else {
-            if (keepl.n == 0) { HIPC(c, keepl.off.ensure(64)); HIPC(c, hipMemsetAsync(keepl.off.p, 0, 8, LN(c).stream)); }
+            if (keepl.n == 0) HIPC(c, keepl.clear(LN(c).stream));
             // The buffers change hands (lane temporary <-> the layer's slot).  Whatever comes back is grown to the largest list seen so far NOW,
             // while nothing is running on it, so that no later layer finds a too small buffer in the middle of its serial tail: growing means
             // hipFree, and hipFree waits for every stream of the device (4 of them cost 4.5 ms per step before this).

@@ -9,7 +9,7 @@
 //   a plane holds, per pixel, the LARGEST coverage of any primitive, as round(255 a) -- the reference draws one line after the other, so where lines
 //   overlap its anti-aliased fringes get darker than here; the host composes colour = (background (255 - A) + colour A + 127) / 255.
 // All arithmetic in float64 in the same order on both sides (no fused multiply-add: -ffp-contract=off).
-#include "vec_common.h"
+#include "orip_ctx.h"
 
 namespace {
 __device__ __forceinline__ int cover_u8(double a) { a = a < 0.0 ? 0.0 : (a > 1.0 ? 1.0 : a); return (int)floor(__dadd_rn(__dmul_rn(a, 255.0), 0.5)); }

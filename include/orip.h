@@ -194,6 +194,34 @@ int orip_stream_preview(orip_ctx* ctx, const uint8_t* data, int64_t n, int W, in
                         int tap_radius, int64_t* stats /* [ORIP_STREAM_STATS] */);
 int orip_stream_preview_fetch(orip_ctx* ctx, uint8_t* rgb /* [rh, rw, 3] */);
 
+/* ---- the second front door: svg_to_stream/gcode2stream.py (G-code -> plotter stream; csrc/gcode.hip) ----
+ * Parsing (:113-142, :177-300) and the speed plan stay on the host; these are its three device steps. */
+typedef struct {
+    double scale_x, scale_y, offset_x_mm, offset_y_mm, steps_per_mm;
+    int32_t W, H;          /* target size in steps, each 1..2^30 */
+    int32_t invert_y;
+} orip_gcode_map;
+/* convert_polylines_to_steps (:305-341) with mm_to_steps (:79-110): n paths, path p = points off[p] .. off[p + 1] - 1 of pts_mm (x, y in mm, float64) ->
+ * step polylines, resident: (v * scale + offset) * steps_per_mm in IEEE double without fused multiply-add, (H - 1) - y under invert_y, round half to
+ * even, clamp to [0, W - 1] x [0, H - 1]; a point equal to its predecessor's step position is dropped, then every path left with fewer than two points.
+ * Fails (no polylines) when a path of two or more points holds a coordinate that is not finite after the conversion: the reference raises there.
+ * Two-call pattern: the fetch copies off[n_out + 1] and pts[total_out, 2] (pts may be NULL). */
+int orip_gcode_to_steps(orip_ctx* ctx, const int64_t* off /* [n+1] */, const double* pts_mm /* [off[n],2] */, int64_t n, const orip_gcode_map* map,
+                        int64_t* n_out, int64_t* total_out);
+int orip_gcode_steps_fetch(orip_ctx* ctx, int64_t* off_out /* [n_out+1] */, int32_t* pts_out /* [total_out,2] or NULL */);
+/* order_paths_nearest (:151-172) from (0, 0): order_out[k] = index of the k-th path to draw -- the remaining path whose FIRST point has the smallest
+ * L1 distance from the cursor, the lowest index on ties; the cursor moves to that path's LAST point; paths are never reversed.  Exact for every input.
+ * ends: (first x, first y, last x, last y) per path, coordinates 0..2^30, or NULL for the resident step polylines (n must then be their count). */
+int orip_gcode_order(orip_ctx* ctx, const int32_t* ends /* [n,4] or NULL */, int64_t n, int32_t* order_out /* [n] */);
+/* StreamWriter.add_steps / finalize (helper :55-68, :166-175) for a whole plot: the bytes of the stream from the direction codes orip_stream_codes left
+ * resident.  Piece i reads cnt[i] codes from code0[i] on and owns the bytes from pos[i]: its speed byte when speed[i] >= 0, then (cnt[i] + 1) / 2 step bytes
+ * (two codes per byte, paired inside the piece, the last byte of an odd piece holds one).  Pieces are listed in byte order, each at least one byte, none
+ * overlapping.  Service bytes (pen, colour, the end byte) are svc_val[k] at svc_pos[k]; every other byte up to nbytes (the padded length) is zero.
+ * A piece or service byte outside the codes or the stream is an error, not a fault.  Two-call pattern: the fetch copies the nbytes bytes. */
+int orip_stream_pack(orip_ctx* ctx, int64_t n_pieces, const int64_t* code0, const int32_t* cnt, const int64_t* pos, const int32_t* speed, int64_t n_service,
+                     const int64_t* svc_pos, const uint8_t* svc_val, int64_t nbytes);
+int orip_stream_pack_fetch(orip_ctx* ctx, uint8_t* out /* [nbytes] */);
+
 /* ---- multi-GPU exchange (no counterpart in the reference, which is a single process) ----
  * One process per GPU; rank r owns the cluster layers {l : l % world == r} for stages 03-08 and 12.  Stage 10 is replicated and needs
  * every layer's stage-08 lists (10:236-267): orip_bcast_layer sends LINES_INTRA / TAPS_INTRA of one layer from its owner to all ranks

@@ -273,6 +273,9 @@ struct orip_ctx {
     DBuf stream_segs, stream_off, stream_codes; int64_t stream_n = 0, stream_total = 0;
     // 14_preview_stream: stream bytes, tile products / prefixes / totals / counters, key plane, RGB image (stream_preview.hip), resident until the fetch
     DBuf sp_data, sp_agg, sp_keys, sp_rgb; int sp_rw = 0, sp_rh = 0; bool sp_ready = false;
+    // gcode2stream (gcode.hip): scratch of the conversion, the resident step polylines (off int64[gc_n + 1], pts int2[gc_total]) between orip_gcode_to_steps and
+    // the fetch / orip_gcode_order, ends + order and the grid of the order, the piece table and the packed bytes between orip_stream_pack and its fetch
+    DBuf gc_tmp, gc_off, gc_pts, gc_ends, gc_grid, pk_tab, pk_out; int64_t gc_n = 0, gc_total = 0, pk_bytes = -1; bool gc_ready = false;
     DBuf resize_src, resize_dst;                       // raster01.hip staging
     int memo_pre_K = 0, memo_pre_H = 0, memo_pre_W = 0; // orip_contours_reserve cleared this many memo planes of an H x W image
     // profiling

@@ -284,6 +284,55 @@ class Device:
         self._ck(self.L.orip_stream_preview_fetch(self.h, _p(rgb)))
         return rgb, {k: int(v) for k, v in zip(STAT_FIELDS, st)}
 
+    # ---- gcode2stream: paths to steps, nearest-neighbour order, stream bytes (include/orip.h; csrc/gcode.hip)
+    def gcode_to_steps(self, off: np.ndarray, pts_mm: np.ndarray, map: dict, fetch_points: bool = True) -> Tuple[np.ndarray, np.ndarray]:
+        """paths in mm (off int64 [n + 1], pts float64 [total, 2]) -> step polylines (off int64, pts int32 [total', 2]), also left resident;
+        map: the fields of orip_gcode_map"""
+        o = np.ascontiguousarray(off, np.int64).reshape(-1)
+        p = np.ascontiguousarray(pts_mm, np.float64).reshape(-1, 2)
+        n = max(len(o) - 1, 0)
+        if n and int(o[-1]) != len(p):
+            raise ValueError(f"offsets end at {int(o[-1])}, {len(p)} points given")
+        m = _l.GcodeMap(**{k: map[k] for k, _ in _l.GcodeMap._fields_})
+        n_out, tot = C.c_int64(0), C.c_int64(0)
+        self._ck(self.L.orip_gcode_to_steps(self.h, _p(o) if n else None, _p(p) if len(p) else None, n, C.byref(m), C.byref(n_out), C.byref(tot)))
+        off_s = np.zeros(n_out.value + 1, np.int64)
+        pts_s = np.zeros((max(tot.value, 1), 2), np.int32)
+        self._ck(self.L.orip_gcode_steps_fetch(self.h, _p(off_s), _p(pts_s) if fetch_points else None))
+        return off_s, pts_s[:tot.value]
+
+    def gcode_order(self, ends: np.ndarray | None, n: int | None = None) -> np.ndarray:
+        """order of the paths (first x, first y, last x, last y) int32 [n, 4]; ends None: the n resident step polylines of gcode_to_steps"""
+        if ends is not None:
+            e = np.ascontiguousarray(ends, np.int32).reshape(-1, 4)
+            n = len(e)
+        order = np.zeros(max(int(n), 1), np.int32)
+        self._ck(self.L.orip_gcode_order(self.h, _p(e) if ends is not None and n else None, int(n), _p(order)))
+        return order[:int(n)]
+
+    def stream_codes_resident(self, moves: np.ndarray) -> Tuple[np.ndarray, None]:
+        """stream_codes without the codes: they stay on the device for stream_pack; -> (off int64 [n + 1], None)"""
+        m = np.ascontiguousarray(moves, np.int32).reshape(-1, 4)
+        total = C.c_int64(0)
+        self._ck(self.L.orip_stream_codes(self.h, _p(m) if len(m) else None, len(m), C.byref(total)))
+        off = np.zeros(len(m) + 1, np.int64)
+        self._ck(self.L.orip_stream_codes_fetch(self.h, _p(off), None))
+        return off, None
+
+    def stream_pack(self, table, codes=None) -> bytes:
+        """bytes of a piece table (orip.stream.PieceTable) from the resident direction codes; `codes` is what stream_codes_resident returned (None)"""
+        if codes is not None:
+            raise ValueError("stream_pack reads the codes orip_stream_codes left on the device; pass None")
+        c0 = np.ascontiguousarray(table.code0, np.int64); cnt = np.ascontiguousarray(table.cnt, np.int32)
+        pos = np.ascontiguousarray(table.pos, np.int64); spd = np.ascontiguousarray(table.speed, np.int32)
+        sp = np.ascontiguousarray(table.svc_pos, np.int64); sv = np.ascontiguousarray(table.svc_val, np.uint8)
+        npc, ns = len(pos), len(sp)
+        self._ck(self.L.orip_stream_pack(self.h, npc, _p(c0) if npc else None, _p(cnt) if npc else None, _p(pos) if npc else None, _p(spd) if npc else None,
+                                         ns, _p(sp) if ns else None, _p(sv) if ns else None, int(table.nbytes)))
+        out = np.zeros(max(int(table.nbytes), 1), np.uint8)
+        self._ck(self.L.orip_stream_pack_fetch(self.h, _p(out)))
+        return out[:int(table.nbytes)].tobytes()
+
     # ---- multi-GPU exchange (RCCL inside liborip.so)
     def comm_unique_id(self) -> bytes:
         buf = (C.c_uint8 * _l.COMM_ID_BYTES)()

@@ -1,0 +1,372 @@
+"""G-code -> plotter stream: the second front door of the reference (svg_to_stream/gcode2stream.py), same wire format as stage 13 (orip/stream.py).
+
+Four steps.  The text is parsed on the host into pen-down paths in mm (cheap: a pass over the lines).  The paths become step polylines on the device
+(orip_gcode_to_steps), are put into nearest-neighbour order there (orip_gcode_order: the reference's O(n^2) Python scan is its dominant cost) and the
+host plans the stream: every move of the plot (a travel to each path, then its segments), the speed pieces of every move with the plans of
+orip/stream.py, and the byte position of every piece -- flat numpy over ALL paths, no Python call per segment.  The direction codes
+(orip_stream_codes) stay on the device; orip_stream_pack writes the bytes there and only the finished stream comes back.
+
+Everything that decides a byte follows the reference in meaning: comment and word rules of the parser, unit and mode switches inside a line, pen
+state before motion, float64 arithmetic of the conversion, round half to even, the (L1 distance, index) order, the command sequence of the emitter,
+the dividers after --speed-scale.  The device steps are injectable so that this host logic can be tested without a GPU; the product has no CPU path."""
+from __future__ import annotations
+
+import argparse
+import re
+import sys
+from dataclasses import dataclass, fields
+from pathlib import Path
+from typing import Callable, List, Optional, Sequence, Tuple, Union
+
+import numpy as np
+
+from . import stream as ST
+
+A4_MM = (210.0, 297.0)
+MM_PER_INCH = 25.4
+MAX_TARGET_STEPS = 1 << 30          # ours, not the reference's: step coordinates are int32 on the device
+
+
+@dataclass
+class GcodeOptions:
+    """The command line of gcode2stream.py (:436-543): same names, same defaults."""
+    output: str = "stream_from_gcode.bin"
+    target_width_steps: Optional[int] = None
+    target_height_steps: Optional[int] = None
+    steps_per_mm: float = 40.0
+    invert_y: int = 0
+    offset_x_mm: float = 0.0
+    offset_y_mm: float = 0.0
+    scale_x: float = 1.0
+    scale_y: float = 1.0
+    color_index: int = 3
+    div_start: int = 28
+    div_fast: int = 15
+    profile: str = "triangle"
+    corner_deg: float = 85.0
+    corner_div: int = 28
+    corner_window_steps: int = 300
+    travel_div_fast: int = 10
+    travel_start_div: int = 28
+    travel_window_steps: int = 240
+    travel_quant_step: int = 4
+    short_len_steps: int = 120
+    short_div: int = 16
+    speed_scale: float = 1.0
+    no_reorder: bool = False
+
+
+# ------------------------------------------------------------------ parse (:113-142, :177-300)
+_COMMENT = re.compile(r"\([^)]*\)?|\)")       # "(" up to the next ")" or the end of the line, no nesting; a stray ")" goes too
+
+
+def _code_lines(text: str) -> List[str]:
+    out = []
+    for raw in text.splitlines():
+        line = _COMMENT.sub("", raw.split(";", 1)[0]).strip()
+        if line:
+            out.append(line)
+    return out
+
+
+def parse_gcode(text: Union[str, bytes]) -> Tuple[np.ndarray, np.ndarray, int]:
+    """Pen-down paths of a G-code text: (off int64 [n + 1], pts_mm float64 [total, 2], pen-down moves).  Path p is pts_mm[off[p]:off[p + 1]], always two
+    points or more.  Words are whitespace-separated, letter + number; a word whose number does not parse is skipped whole.  G90 / G91 and G20 / G21 act
+    where they stand in the line; M3 / M4 lower the pen, M5 lifts it, a Z word lowers it iff z <= 0 unless an M word of the line decided; the pen moves
+    before the line's motion, and lifting it closes the path.  int(float("inf")) raises, as in the reference: such a file is refused."""
+    if isinstance(text, (bytes, bytearray)):
+        text = bytes(text).decode("utf-8", errors="ignore")
+    x = y = 0.0
+    absolute, metric, down = True, True, False
+    flat: List[Tuple[float, float]] = []
+    off = [0]
+    open_from = 0                                     # len(flat) where the open path starts (== len(flat): none open)
+    moves = 0
+
+    def close():
+        nonlocal open_from
+        if len(flat) - open_from >= 2:
+            off.append(len(flat))
+        else:
+            del flat[open_from:]
+        open_from = len(flat)
+
+    for line in _code_lines(text):
+        pen = None; nx = ny = nz = None
+        for word in line.split():
+            letter, num = word[0].upper(), word[1:]
+            if not num:
+                continue
+            try:
+                if letter == "G" or letter == "M":
+                    code = int(float(num))             # OverflowError (Ginf) is not caught: the reference fails there too
+                elif letter in "XYZ":
+                    v = float(num)
+                else:
+                    continue
+            except ValueError:
+                continue
+            if letter == "G":
+                if code == 90: absolute = True
+                elif code == 91: absolute = False
+                elif code == 21: metric = True
+                elif code == 20: metric = False
+            elif letter == "M":
+                if code == 3 or code == 4: pen = True
+                elif code == 5: pen = False
+            else:
+                if not metric:
+                    v *= MM_PER_INCH
+                if letter == "X": nx = v
+                elif letter == "Y": ny = v
+                else: nz = v
+        if nz is not None and pen is None:
+            pen = nz <= 0.0
+        if pen is not None and pen != down:
+            if down:
+                close()
+            down = pen
+        if nx is not None or ny is not None:
+            ox, oy = x, y
+            if absolute:
+                x = nx if nx is not None else x
+                y = ny if ny is not None else y
+            else:
+                x = x + nx if nx is not None else x
+                y = y + ny if ny is not None else y
+            if down:
+                if len(flat) == open_from:
+                    flat.append((ox, oy))
+                flat.append((x, y))
+                moves += 1
+    close()
+    return np.asarray(off, np.int64), np.asarray(flat, np.float64).reshape(-1, 2), moves
+
+
+# ------------------------------------------------------------------ options (:546-603)
+def apply_speed_scale(o: GcodeOptions) -> GcodeOptions:
+    """--speed-scale (:546-587): six dividers divided by the scale, rounded half to even, at least 1; then the five ordering constraints."""
+    scale = float(o.speed_scale)
+    if scale <= 0.0:
+        raise SystemExit("Error: --speed-scale must be > 0")
+    if abs(scale - 1.0) < 1e-6:
+        return o
+    for name in ("div_start", "div_fast", "corner_div", "short_div", "travel_div_fast", "travel_start_div"):
+        setattr(o, name, max(1, int(round(getattr(o, name) / scale))))
+    o.div_start = max(o.div_start, o.div_fast)
+    o.corner_div = max(o.corner_div, o.div_fast)
+    o.short_div = max(o.short_div, o.div_fast)
+    o.travel_start_div = max(o.travel_start_div, o.travel_div_fast)
+    o.div_start = max(o.div_start, o.travel_div_fast)
+    return o
+
+
+def target_size(o: GcodeOptions) -> Tuple[int, int]:
+    """A4 at steps_per_mm unless BOTH sizes are given (:598-603)."""
+    if o.target_width_steps is None or o.target_height_steps is None:
+        return int(round(A4_MM[0] * o.steps_per_mm)), int(round(A4_MM[1] * o.steps_per_mm))
+    return int(o.target_width_steps), int(o.target_height_steps)
+
+
+def stream_config(o: GcodeOptions) -> ST.StreamConfig:
+    return ST.StreamConfig(steps_per_mm=o.steps_per_mm, invert_y=bool(o.invert_y), div_start=o.div_start, div_fast=o.div_fast, profile=o.profile,
+                           corner_deg=o.corner_deg, corner_div=o.corner_div, corner_window_steps=o.corner_window_steps, short_len_steps=o.short_len_steps,
+                           short_div=o.short_div, travel_div_fast=o.travel_div_fast, travel_start_div=o.travel_start_div,
+                           travel_window_steps=o.travel_window_steps, travel_quant_step=o.travel_quant_step)
+
+
+# ------------------------------------------------------------------ emit (:399-426), flat over all paths
+@dataclass
+class Plan:
+    """The moves of a plot and what the byte layout needs once their step counts are known."""
+    moves: np.ndarray           # int32 [M, 4]
+    kind: np.ndarray            # per item: service byte, or -1 for the next move
+    is_travel: np.ndarray       # per move
+    slow_in: np.ndarray
+    slow_out: np.ndarray
+
+
+def plan_moves(off: np.ndarray, pts: np.ndarray, sc: ST.StreamConfig, color_index: int) -> Plan:
+    """pen up, speed div_start, colour; per path: a travel when the cursor is elsewhere, pen down, the segments, pen up."""
+    if not (0 <= color_index <= 7):
+        raise ValueError("color index 0..7")
+    off = np.asarray(off, np.int64); pts = np.asarray(pts, np.int64).reshape(-1, 2)
+    n = len(off) - 1
+    nseg = np.diff(off) - 1
+    first, last = pts[off[:-1]], pts[off[1:] - 1]
+    cur = np.concatenate([np.zeros((1, 2), np.int64), last[:-1]])
+    trav = (cur != first).any(1)
+    per_path = trav + nseg                                                # moves of a path
+    mbase = np.cumsum(per_path) - per_path
+    M = int(per_path.sum())
+    moves = np.zeros((M, 4), np.int32)
+    is_travel = np.zeros(M, bool); slow_in = np.zeros(M, bool); slow_out = np.zeros(M, bool)
+    t = mbase[trav]
+    moves[t, :2] = cur[trav]; moves[t, 2:] = first[trav]; is_travel[t] = True
+    is_last = np.zeros(len(pts), bool); is_last[off[1:] - 1] = True
+    a = np.nonzero(~is_last)[0]                                           # first vertex of every segment
+    sp = np.repeat(np.arange(n), nseg)
+    s = mbase[sp] + trav[sp] + (a - off[sp])
+    moves[s, :2] = pts[a]; moves[s, 2:] = pts[a + 1]
+    slow_in[s], slow_out[s] = ST.corner_flags_flat(pts, off, sc.corner_deg)
+    items = per_path + 2
+    ibase = 3 + np.cumsum(items) - items
+    kind = np.full(3 + int(items.sum()), -1, np.int64)
+    kind[0] = ST.PEN_UP
+    kind[1] = 0x40 | (min(max(int(sc.div_start), 0), 63) & 0x3F)          # set_speed(div_start): written here, and remembered (layout: initial_div)
+    kind[2] = 0x08 | (color_index & 7)
+    kind[ibase + trav] = ST.PEN_DOWN
+    kind[ibase + per_path + 1] = ST.PEN_UP
+    return Plan(moves, kind, is_travel, slow_in, slow_out)
+
+
+def plan_pieces(P: Plan, counts: np.ndarray, sc: ST.StreamConfig) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """(move, divider, count) of every piece in move order.  A segment without corners is one piece; every other move takes the plan of its
+    (kind, step count), computed once per distinct pair with orip.stream's plan_travel / plan_segment and expanded with numpy."""
+    counts = np.asarray(counts, np.int64)
+    simple = ~P.is_travel & ~P.slow_in & ~P.slow_out
+    i0 = np.nonzero(simple & (counts > 0))[0]
+    pm = [i0]; pc = [counts[i0]]; pd = [np.where(counts[i0] <= sc.short_len_steps, sc.short_div, sc.div_fast).astype(np.int64)]
+    i1 = np.nonzero(~simple & (counts > 0))[0]
+    if len(i1):
+        cls = np.where(P.is_travel[i1], 0, 1 + P.slow_in[i1] + 2 * P.slow_out[i1]).astype(np.int64)
+        uniq, inv = np.unique(cls * (int(counts.max()) + 1) + counts[i1], return_inverse=True)
+        plan_off = [0]; plan_div: List[int] = []; plan_cnt: List[int] = []
+        for key in uniq:
+            c, k = divmod(int(key), int(counts.max()) + 1)
+            pcs = ST.plan_travel(k, sc) if c == 0 else ST.plan_segment(k, sc, bool((c - 1) & 1), bool((c - 1) & 2))
+            plan_div += [d for d, _ in pcs]; plan_cnt += [q for _, q in pcs]; plan_off.append(len(plan_div))
+        plan_off = np.asarray(plan_off, np.int64); plan_div = np.asarray(plan_div, np.int64); plan_cnt = np.asarray(plan_cnt, np.int64)
+        lens = np.diff(plan_off)[inv]
+        src = np.repeat(plan_off[inv], lens) + np.arange(int(lens.sum())) - np.repeat(np.cumsum(lens) - lens, lens)
+        pm.append(np.repeat(i1, lens)); pd.append(plan_div[src]); pc.append(plan_cnt[src])
+    pm, pd, pc = np.concatenate(pm), np.concatenate(pd), np.concatenate(pc)
+    order = np.argsort(pm, kind="stable")
+    return pm[order], pd[order], pc[order]
+
+
+EMPTY_STREAM = bytes([ST.EOF_BYTE]) + b"\x00" * (ST.SPI_CHUNK_SIZE - 1)    # no paths: the end byte and padding, without the three leading bytes (:364-391)
+
+
+def build_stream_from_gcode(text_or_paths, opts: Optional[GcodeOptions] = None, device=None, *, steps_fn: Optional[Callable] = None,
+                            order_fn: Optional[Callable] = None, codes_fn: Optional[Callable] = None, pack_fn: Optional[Callable] = None,
+                            timings: Optional[dict] = None) -> Tuple[bytes, dict]:
+    """The stream of a G-code text (str / bytes) or of paths in mm given as (off, pts_mm); opts as parsed, --speed-scale not yet applied.
+    Device steps, each None = the GPU (orip.device.Device; there is no CPU path in the product):
+      steps_fn(off, pts_mm, map: dict) -> (off int64, pts int32 [total, 2])      orip_gcode_to_steps
+      order_fn(ends int32 [n, 4]) -> order int32 [n]                             orip_gcode_order
+      codes_fn(moves int32 [M, 4]) -> (off int64 [M + 1], codes or None)         orip_stream_codes (None: the codes stay on the device)
+      pack_fn(table: orip.stream.PieceTable, codes) -> bytes                     orip_stream_pack
+    Returns (bytes, counts)."""
+    import time
+    o = apply_speed_scale(GcodeOptions(**{f.name: getattr(opts, f.name) for f in fields(GcodeOptions)}) if opts is not None else GcodeOptions())
+    W, H = target_size(o)
+    sc = stream_config(o)
+    tm = timings if timings is not None else {}
+    t0 = time.perf_counter()
+
+    def lap(name):
+        nonlocal t0
+        t1 = time.perf_counter(); tm[name] = tm.get(name, 0.0) + (t1 - t0); t0 = t1
+
+    if isinstance(text_or_paths, (str, bytes, bytearray)):
+        off_mm, pts_mm, pen_moves = parse_gcode(text_or_paths)
+    else:
+        off_mm, pts_mm = text_or_paths
+        off_mm = np.asarray(off_mm, np.int64); pts_mm = np.asarray(pts_mm, np.float64).reshape(-1, 2)
+        pen_moves = int((np.diff(off_mm) - 1).clip(0).sum())
+    lap("parse")
+    info = {"paths_mm": len(off_mm) - 1, "pen_down_moves": pen_moves, "paths": 0, "steps": 0, "target": (W, H)}
+    if len(off_mm) <= 1:
+        return EMPTY_STREAM, dict(info, bytes=len(EMPTY_STREAM))
+    if not (1 <= W <= MAX_TARGET_STEPS and 1 <= H <= MAX_TARGET_STEPS):
+        raise ValueError(f"target size {W} x {H} steps: each side must be in 1..2^30 (step coordinates are int32 on the device)")
+    if steps_fn is None or order_fn is None or codes_fn is None or pack_fn is None:
+        if device is None:
+            from .stages import device as _default_device
+            device = _default_device()
+        steps_fn = steps_fn or device.gcode_to_steps
+        order_fn = order_fn or device.gcode_order
+        codes_fn = codes_fn or device.stream_codes_resident
+        pack_fn = pack_fn or device.stream_pack
+    off, pts = steps_fn(off_mm, pts_mm, dict(scale_x=o.scale_x, scale_y=o.scale_y, offset_x_mm=o.offset_x_mm, offset_y_mm=o.offset_y_mm, steps_per_mm=o.steps_per_mm,
+                                             W=W, H=H, invert_y=int(bool(o.invert_y))))
+    off = np.asarray(off, np.int64); pts = np.asarray(pts, np.int32).reshape(-1, 2)
+    lap("to_steps")
+    n = len(off) - 1
+    info["paths"] = n
+    if n == 0:
+        return EMPTY_STREAM, dict(info, bytes=len(EMPTY_STREAM))
+    if not o.no_reorder:
+        order = np.asarray(order_fn(np.ascontiguousarray(np.concatenate([pts[off[:-1]], pts[off[1:] - 1]], 1), np.int32)), np.int64)
+        if len(order) != n or not np.array_equal(np.sort(order), np.arange(n)):
+            raise RuntimeError("the path order is not a permutation")
+        lens = np.diff(off)[order]
+        noff = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+        pts = pts[np.repeat(off[:-1][order], lens) + np.arange(int(lens.sum())) - np.repeat(noff[:-1], lens)]
+        off = noff
+    lap("order")
+    P = plan_moves(off, pts, sc, int(o.color_index))
+    lap("plan")
+    coff, codes = codes_fn(P.moves)
+    coff = np.asarray(coff, np.int64)
+    lap("codes")
+    pm, pd, pc = plan_pieces(P, np.diff(coff), sc)
+    table = ST.layout(P.kind, pm, pd, pc, coff, initial_div=int(sc.div_start))
+    lap("plan")
+    data = pack_fn(table, codes)
+    lap("pack")
+    info.update(steps=int(coff[-1]), bytes=len(data), pieces=len(table.pos), moves=len(P.moves))
+    return data, info
+
+
+# ------------------------------------------------------------------ command line (:436-638)
+def build_argparser() -> argparse.ArgumentParser:
+    d = GcodeOptions()
+    ap = argparse.ArgumentParser(description="Convert G-code to an OmniRevolve plotter stream (A4 defaults); ordering and packing run on the GPU.")
+    ap.add_argument("input", help="input G-code file")
+    ap.add_argument("-o", "--output", default=d.output, help="output stream file")
+    ap.add_argument("--target-width-steps", type=int, default=None, help="canvas width in steps (default: A4 width x steps per mm; needs the height too)")
+    ap.add_argument("--target-height-steps", type=int, default=None, help="canvas height in steps (default: A4 height x steps per mm; needs the width too)")
+    ap.add_argument("--steps-per-mm", type=float, default=d.steps_per_mm)
+    ap.add_argument("--invert-y", type=int, default=d.invert_y, help="1: flip Y inside the canvas")
+    ap.add_argument("--offset-x-mm", type=float, default=d.offset_x_mm)
+    ap.add_argument("--offset-y-mm", type=float, default=d.offset_y_mm)
+    ap.add_argument("--scale-x", type=float, default=d.scale_x)
+    ap.add_argument("--scale-y", type=float, default=d.scale_y)
+    ap.add_argument("--color-index", type=int, default=d.color_index, help="pen 0..7")
+    ap.add_argument("--div-start", type=int, default=d.div_start)
+    ap.add_argument("--div-fast", type=int, default=d.div_fast)
+    ap.add_argument("--profile", choices=["triangle", "scurve"], default=d.profile)
+    ap.add_argument("--corner-deg", type=float, default=d.corner_deg)
+    ap.add_argument("--corner-div", type=int, default=d.corner_div)
+    ap.add_argument("--corner-window-steps", type=int, default=d.corner_window_steps)
+    ap.add_argument("--travel-div-fast", type=int, default=d.travel_div_fast)
+    ap.add_argument("--travel-start-div", type=int, default=d.travel_start_div)
+    ap.add_argument("--travel-window-steps", type=int, default=d.travel_window_steps)
+    ap.add_argument("--travel-quant-step", type=int, default=d.travel_quant_step)
+    ap.add_argument("--short-len-steps", type=int, default=d.short_len_steps)
+    ap.add_argument("--short-div", type=int, default=d.short_div)
+    ap.add_argument("--speed-scale", type=float, default=d.speed_scale, help="> 1 faster (smaller dividers), < 1 slower")
+    ap.add_argument("--no-reorder", action="store_true", help="keep the paths in file order")
+    return ap
+
+
+def options_from_args(a: argparse.Namespace) -> GcodeOptions:
+    return GcodeOptions(**{f.name: getattr(a, f.name) for f in fields(GcodeOptions)})
+
+
+def main(argv: Optional[Sequence[str]] = None, **device_steps) -> None:
+    a = build_argparser().parse_args(argv)
+    opts = options_from_args(a)
+    apply_speed_scale(GcodeOptions(speed_scale=opts.speed_scale))        # a bad scale ends the run before the file is read, as in the reference
+    text = Path(a.input).read_bytes()
+    data, info = build_stream_from_gcode(text, opts, **device_steps)
+    Path(a.output).write_bytes(data)
+    print(f"[gcode] {a.input}: {info['paths_mm']} pen-down paths, {info['pen_down_moves']} pen-down moves")
+    print(f"[gcode] {info['paths']} paths in step space, {info['steps']} steps, target {info['target'][0]} x {info['target'][1]} steps")
+    print(f"stream saved: {a.output} ({len(data)} bytes)")
+
+
+if __name__ == "__main__":
+    main()

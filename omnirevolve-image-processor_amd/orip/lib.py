@@ -36,6 +36,11 @@ class Params10(C.Structure):
                 ("W", C.c_int32), ("H", C.c_int32)]
 
 
+class GcodeMap(C.Structure):
+    _fields_ = [("scale_x", C.c_double), ("scale_y", C.c_double), ("offset_x_mm", C.c_double), ("offset_y_mm", C.c_double), ("steps_per_mm", C.c_double),
+                ("W", C.c_int32), ("H", C.c_int32), ("invert_y", C.c_int32)]
+
+
 _vp, _i64, _i32, _f64, _f32, _cp = C.c_void_p, C.c_int64, C.c_int, C.c_double, C.c_float, C.c_char_p
 _P = C.POINTER
 
@@ -64,6 +69,9 @@ SIGNATURES = {
     "orip_preview_cover": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "orip_stream_codes": (_i32, [_vp, _vp, _i64, _P(_i64)]), "orip_stream_codes_fetch": (_i32, [_vp, _vp, _vp]),
     "orip_stream_preview": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp]), "orip_stream_preview_fetch": (_i32, [_vp, _vp]),
+    "orip_gcode_to_steps": (_i32, [_vp, _vp, _vp, _i64, _P(GcodeMap), _P(_i64), _P(_i64)]), "orip_gcode_steps_fetch": (_i32, [_vp, _vp, _vp]),
+    "orip_gcode_order": (_i32, [_vp, _vp, _i64, _vp]),
+    "orip_stream_pack": (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64]), "orip_stream_pack_fetch": (_i32, [_vp, _vp]),
     "orip_comm_unique_id": (_i32, [_vp]), "orip_comm_init": (_i32, [_vp, _vp, _i32, _i32]), "orip_comm_destroy": (_i32, [_vp]),
     "orip_bcast_layer": (_i32, [_vp, _i32, _i32]),
 }

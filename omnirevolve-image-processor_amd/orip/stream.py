@@ -275,12 +275,100 @@ def _emit_layer(P: _Plot, ops: Sequence[dict], color_idx: int, W: int, H: int, s
     return cur
 
 
-def assemble(P: _Plot, off: np.ndarray, codes: np.ndarray, sc: StreamConfig) -> bytes:
-    """Bytes of the plot from its items, the step offsets of its moves and their direction codes (StreamWriter semantics, helper :130-175:
-    a speed byte only when the divider changes, the steps of every piece paired on their own, end byte, padding)."""
+def corner_flags_flat(pts: np.ndarray, off: np.ndarray, corner_deg: float) -> Tuple[np.ndarray, np.ndarray]:
+    """corner_flags for every polyline of a flat list at once: pts int [total, 2], off [n + 1] (every polyline >= 2 points) -> slow_in / slow_out per
+    SEGMENT in list order (polyline p owns segments off[p] - p .. off[p + 1] - p - 2).  Same arithmetic, same re-decision near the threshold."""
+    pts = np.asarray(pts).reshape(-1, 2); off = np.asarray(off, np.int64)
+    total = len(pts)
+    sharp = np.zeros(total, bool)
+    if total >= 3:
+        p = pts.astype(np.float64)
+        v1, v2 = p[:-2] - p[1:-1], p[2:] - p[1:-1]
+        n1, n2 = np.hypot(v1[:, 0], v1[:, 1]), np.hypot(v2[:, 0], v2[:, 1])
+        ok = (n1 > 0) & (n2 > 0)
+        cosv = np.clip((v1[:, 0] * v2[:, 0] + v1[:, 1] * v2[:, 1]) / np.where(ok, n1 * n2, 1.0), -1.0, 1.0)
+        ang = np.where(ok, np.degrees(np.arccos(cosv)), 180.0)
+        sharp[1:-1] = ang < corner_deg
+        for j in np.nonzero(np.abs(ang - corner_deg) < 1e-6)[0]:
+            sharp[j + 1] = _angle(pts[j], pts[j + 1], pts[j + 2]) < corner_deg
+    sharp[off[:-1]] = False; sharp[off[1:] - 1] = False                   # a polyline's end points are no corners (and their angles span two polylines)
+    is_last = np.zeros(total, bool); is_last[off[1:] - 1] = True
+    a = np.nonzero(~is_last)[0]                                           # first vertex of every segment
+    return sharp[a], sharp[a + 1]
+
+
+# ------------------------------------------------------------------ byte layout
+@dataclass
+class PieceTable:
+    """Where every byte of a plot comes from.  Piece i (a run of steps at one divider) reads cnt[i] direction codes from code0[i] on and owns the bytes
+    from pos[i]: its speed byte when speed[i] >= 0, then (cnt[i] + 1) // 2 step bytes, the steps paired inside the piece.  Pieces without bytes are not
+    listed.  Service bytes (the end byte among them) are svc_val at svc_pos; nbytes is the padded length, every other byte is zero."""
+    code0: np.ndarray
+    cnt: np.ndarray
+    pos: np.ndarray
+    speed: np.ndarray
+    svc_pos: np.ndarray
+    svc_val: np.ndarray
+    nbytes: int
+
+
+def layout(kind: np.ndarray, pm: np.ndarray, pd: np.ndarray, pc: np.ndarray, off: np.ndarray, initial_div: Optional[int] = None) -> PieceTable:
+    """Byte positions of a plot.  kind: per item a service byte (>= 0) or -1 for the next move; (pm, pd, pc): move index, divider and step count of every
+    piece, in move order and plan order inside a move; off: first code of every move.  initial_div: the divider already set when the first piece starts
+    (StreamWriter.set_speed writes nothing for the divider it holds, helper :139-143); None: nothing set yet, the first piece writes its speed byte."""
+    kind = np.asarray(kind, np.int64)
+    is_move = kind < 0
+    nmov = int(is_move.sum())
+    first_of_move = np.r_[True, pm[1:] != pm[:-1]] if len(pm) else np.zeros(0, bool)
+    csum = np.cumsum(pc) - pc
+    within = csum - np.maximum.accumulate(np.where(first_of_move, csum, 0)) if len(pm) else np.zeros(0, np.int64)
+    pstart = off[pm] + within if len(pm) else np.zeros(0, np.int64)
+    spd = np.ones(len(pm), bool)
+    if len(pm) > 1:
+        spd[1:] = pd[1:] != pd[:-1]
+    if len(pm) and initial_div is not None:
+        spd[0] = pd[0] != initial_div
+    pbytes = spd.astype(np.int64) + (pc + 1) // 2
+    move_bytes = np.zeros(nmov, np.int64)
+    np.add.at(move_bytes, pm, pbytes)
+    item_bytes = np.ones(len(kind), np.int64)
+    item_bytes[is_move] = move_bytes
+    item_pos = np.cumsum(item_bytes) - item_bytes
+    total = int(item_bytes.sum())
+    bsum = np.cumsum(pbytes) - pbytes
+    ppos = item_pos[is_move][pm] + bsum - np.maximum.accumulate(np.where(first_of_move, bsum, 0)) if len(pm) else np.zeros(0, np.int64)
+    sp = np.clip(pd, 0, 63)                                               # make_speed_byte (helper :46-51)
+    speed = np.where(spd, 0x40 | (sp & 0x3F), -1)
+    live = pbytes > 0
+    svc_pos = np.r_[item_pos[~is_move], total].astype(np.int64)
+    svc_val = np.r_[kind[~is_move], EOF_BYTE].astype(np.uint8)
+    nbytes = total + 1 + (-(total + 1)) % SPI_CHUNK_SIZE
+    return PieceTable(pstart[live].astype(np.int64), pc[live].astype(np.int32), ppos[live].astype(np.int64), speed[live].astype(np.int32), svc_pos, svc_val, nbytes)
+
+
+def fill_bytes(T: PieceTable, codes: np.ndarray) -> bytes:
+    """The bytes of a piece table with numpy: index arrays per output byte, one code fetched per step.  Fine for stage 13's plots; orip_stream_pack does
+    the same on the device for streams of any size."""
+    out = np.zeros(T.nbytes, np.uint8)
+    out[T.svc_pos] = T.svc_val
+    if len(T.pos):
+        has = T.speed >= 0
+        out[T.pos[has]] = T.speed[has].astype(np.uint8)
+        pc = T.cnt.astype(np.int64)
+        nb = (pc + 1) // 2                                                # step bytes per piece
+        bpiece = np.repeat(np.arange(len(pc)), nb)
+        j = np.arange(int(nb.sum())) - np.repeat(np.cumsum(nb) - nb, nb)  # index of the byte inside its piece
+        a = codes[T.code0[bpiece] + 2 * j].astype(np.int64) & 7
+        has_b = 2 * j + 1 < pc[bpiece]
+        b = np.where(has_b, codes[np.minimum(T.code0[bpiece] + 2 * j + 1, max(len(codes) - 1, 0))].astype(np.int64) & 7, 0)
+        out[(T.pos + has)[bpiece] + j] = np.where(has_b, 0x80 | 0x40 | (a << 3) | b, 0x80 | (a << 3)).astype(np.uint8)
+    return out.tobytes()
+
+
+def plot_pieces(P: _Plot, off: np.ndarray, sc: StreamConfig) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """(move index, divider, count) of every piece of a plot, in move order; simple draw segments get their single piece without a Python call."""
     nmov = len(P.moves)
     counts = np.diff(off).astype(np.int64) if nmov else np.zeros(0, np.int64)
-    # pieces of every move: (move index, divider, count); simple draw segments get their single piece without a Python call
     piece_mov: List[np.ndarray] = []; piece_div: List[np.ndarray] = []; piece_cnt: List[np.ndarray] = []
     simple = np.array([p is None for p in P.plans], bool) if nmov else np.zeros(0, bool)
     if nmov:
@@ -295,45 +383,14 @@ def assemble(P: _Plot, off: np.ndarray, codes: np.ndarray, sc: StreamConfig) -> 
     pd = np.concatenate(piece_div) if piece_div else np.zeros(0, np.int64)
     pc = np.concatenate(piece_cnt) if piece_cnt else np.zeros(0, np.int64)
     order = np.argsort(pm, kind="stable")                                 # pieces in move order, the pieces of one move in plan order
-    pm, pd, pc = pm[order], pd[order], pc[order]
-    # first step of every piece inside the code array
-    within = np.zeros(len(pm), np.int64)
-    if len(pm):
-        first_of_move = np.r_[True, pm[1:] != pm[:-1]]
-        csum = np.cumsum(pc) - pc
-        within = csum - np.maximum.accumulate(np.where(first_of_move, csum, 0))
-    pstart = off[pm] + within if len(pm) else np.zeros(0, np.int64)
-    # speed bytes: helper set_speed appends only when the divider differs from the last one set (:139-143)
-    spd = np.ones(len(pm), bool)
-    if len(pm) > 1:
-        spd[1:] = pd[1:] != pd[:-1]
-    pbytes = spd.astype(np.int64) + (pc + 1) // 2
-    # item order: every move contributes its pieces' bytes, a service item one byte
-    kind = np.asarray(P.kind, np.int64)
-    move_bytes = np.zeros(nmov, np.int64)
-    np.add.at(move_bytes, pm, pbytes)
-    item_bytes = np.ones(len(kind), np.int64)
-    is_move = kind < 0
-    item_bytes[is_move] = move_bytes
-    item_pos = np.cumsum(item_bytes) - item_bytes
-    total = int(item_bytes.sum())
-    out = np.zeros(total + 1, np.uint8)
-    out[item_pos[~is_move]] = kind[~is_move].astype(np.uint8)
-    if len(pm):
-        move_pos = item_pos[is_move]                                      # byte position of every move
-        ppos = move_pos[pm] + (np.cumsum(pbytes) - pbytes) - np.maximum.accumulate(np.where(first_of_move, np.cumsum(pbytes) - pbytes, 0))
-        sp = np.clip(pd, 0, 63)                                           # make_speed_byte (helper :46-51)
-        out[ppos[spd]] = (0x40 | (sp[spd] & 0x3F)).astype(np.uint8)
-        nb = (pc + 1) // 2                                                # step bytes per piece
-        bpiece = np.repeat(np.arange(len(pm)), nb)
-        j = np.arange(int(nb.sum())) - np.repeat(np.cumsum(nb) - nb, nb)  # index of the byte inside its piece
-        a = codes[pstart[bpiece] + 2 * j].astype(np.int64) & 7
-        has_b = 2 * j + 1 < pc[bpiece]
-        b = np.where(has_b, codes[np.minimum(pstart[bpiece] + 2 * j + 1, max(len(codes) - 1, 0))].astype(np.int64) & 7, 0)
-        out[(ppos + spd)[bpiece] + j] = np.where(has_b, 0x80 | 0x40 | (a << 3) | b, 0x80 | (a << 3)).astype(np.uint8)
-    out[total] = EOF_BYTE
-    pad = (-(total + 1)) % SPI_CHUNK_SIZE
-    return out.tobytes() + b"\x00" * pad
+    return pm[order], pd[order], pc[order]
+
+
+def assemble(P: _Plot, off: np.ndarray, codes: np.ndarray, sc: StreamConfig, *, initial_div: Optional[int] = None) -> bytes:
+    """Bytes of the plot from its items, the step offsets of its moves and their direction codes (StreamWriter semantics, helper :130-175:
+    a speed byte only when the divider changes, the steps of every piece paired on their own, end byte, padding).  initial_div: layout()."""
+    pm, pd, pc = plot_pieces(P, off, sc)
+    return fill_bytes(layout(np.asarray(P.kind, np.int64), pm, pd, pc, np.asarray(off, np.int64), initial_div), codes)
 
 
 def build_stream(layers: Sequence[Tuple[str, int, Sequence[dict]]], W: int, H: int, sc: StreamConfig, codes_fn: Optional[Callable] = None,

@@ -1,0 +1,179 @@
+"""gcode2stream on the CPU: the parser against the reference's extract_polylines_mm, the whole host path (options, plan, byte layout) against the files the
+reference's main() wrote, with numpy doubles standing in for the three device steps (tests/gcode_double.py; tests/stream_double.py for the codes), the
+doubles themselves against the recorded conversion and order, and the command line.  Fixture: tests/golden/golden_gcode.npz (make_golden_gcode.py).
+No comparison here has a tolerance and no recorded case is left out."""
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from util import load
+from stream_double import codes_numpy
+import gcode_double as D
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+G = load("golden_gcode.npz")
+MAIN_CASES = json.loads(bytes(G["main_cases"]).decode())
+ORDER_NAMES = json.loads(bytes(G["order_names"]).decode())
+CONV_SETS = json.loads(bytes(G["conv_sets"]).decode())
+DOUBLES = dict(steps_fn=D.to_steps_numpy, order_fn=D.order_numpy, codes_fn=codes_numpy, pack_fn=D.pack_numpy)
+
+
+def conv_map(s):
+    spm, inv, W, H, ox, oy, sx, sy = s
+    return dict(scale_x=sx, scale_y=sy, offset_x_mm=ox, offset_y_mm=oy, steps_per_mm=spm, W=W, H=H, invert_y=int(inv))
+
+
+def options_for(args):
+    from orip import gcode as GC
+    return GC.options_from_args(GC.build_argparser().parse_args(["in.gcode"] + list(args)))
+
+
+@pytest.mark.parametrize("i", range(int(G["parse_count"][0])))
+def test_parser_matches_reference(i):
+    from orip.gcode import parse_gcode
+    off, pts, moves = parse_gcode(bytes(G[f"parse_{i}_text"]))
+    assert np.array_equal(off, G[f"parse_{i}_off"]) and moves == int(G[f"parse_{i}_moves"][0])
+    assert pts.tobytes() == G[f"parse_{i}_pts"].astype(np.float64).tobytes()              # the same float64 bits, -0.0 and all
+    off2, pts2, moves2 = parse_gcode(bytes(G[f"parse_{i}_text"]).decode("utf-8", errors="ignore"))
+    assert np.array_equal(off, off2) and pts.tobytes() == pts2.tobytes() and moves == moves2
+
+
+def test_parser_fails_where_the_reference_raises():
+    from orip.gcode import parse_gcode
+    with pytest.raises(OverflowError):
+        parse_gcode("Ginf X1\n")
+    off, pts, _ = parse_gcode("Gnan X1 Y1\nM3\nG1 X2 Y2\n")                                # int(float('nan')) is a ValueError: the word is skipped
+    assert np.array_equal(off, [0, 2]) and pts.tolist() == [[1.0, 1.0], [2.0, 2.0]]
+
+
+@pytest.mark.parametrize("i", range(len(CONV_SETS)))
+def test_double_to_steps_matches_reference(i):
+    off, pts = D.to_steps_numpy(G["conv_off"], G["conv_pts"], conv_map(CONV_SETS[i]))
+    assert np.array_equal(off, G[f"conv_{i}_off"]) and np.array_equal(pts, G[f"conv_{i}_out"])
+
+
+@pytest.mark.parametrize("i", [0, 1])
+def test_double_to_steps_exact_halves(i):
+    off, pts = D.to_steps_numpy(G["conv_half_off"], G["conv_half_pts"], conv_map([2.0, bool(i), 400, 300, 0.0, 0.0, 1.0, 1.0]))
+    assert np.array_equal(off, G[f"conv_half_{i}_off"]) and np.array_equal(pts, G[f"conv_half_{i}_out"])
+
+
+def test_double_to_steps_refuses_non_finite():
+    off = np.array([0, 2, 3], np.int64)
+    with pytest.raises(OverflowError):
+        D.to_steps_numpy(off, np.array([[0, 0], [np.inf, 1], [np.nan, 0]]), conv_map(CONV_SETS[0]))
+    o, p = D.to_steps_numpy(off, np.array([[0, 0], [5, 1], [np.nan, 0]]), conv_map(CONV_SETS[0]))      # a lone point is never converted by the reference
+    assert np.array_equal(o, [0, 2]) and p.tolist() == [[0, 0], [50, 10]]
+
+
+@pytest.mark.parametrize("name", [n for n in ORDER_NAMES if n != "large"])
+def test_double_order_matches_reference(name):
+    assert np.array_equal(D.order_numpy(G[f"order_{name}_ends"]), G[f"order_{name}_perm"])
+
+
+@pytest.mark.parametrize("i", range(len(MAIN_CASES)))
+def test_host_path_reproduces_reference_stream(i):
+    from orip.gcode import build_stream_from_gcode
+    name, args = MAIN_CASES[i]
+    data, info = build_stream_from_gcode(bytes(G[f"text_{name}"]), options_for(args), **DOUBLES)
+    want = bytes(G[f"main_{i}_bin"])
+    assert len(data) == len(want) and data == want, (name, args, info)
+
+
+def test_paths_input_and_numpy_assembler_agree():
+    """the same stream from (off, pts_mm) instead of text, and from orip.stream.fill_bytes instead of the per-piece double"""
+    from orip import gcode as GC, stream as ST
+    text = bytes(G["text_drawing"])
+    off, pts, _ = GC.parse_gcode(text)
+    opts = options_for(MAIN_CASES[0][1])
+    a, _ = GC.build_stream_from_gcode((off, pts), opts, **DOUBLES)
+    b, _ = GC.build_stream_from_gcode(text, opts, **dict(DOUBLES, pack_fn=ST.fill_bytes))
+    assert a == bytes(G["main_0_bin"]) and b == a
+
+
+def test_assemble_initial_divider():
+    """assemble's default keeps today's bytes (test_stream_host.py shows that against golden_stream.npz); with the divider of the first piece given as
+    already set, exactly that one speed byte goes"""
+    from orip import stream as ST
+    sc = ST.StreamConfig()
+    P = ST._Plot(); P.svc(ST.PEN_UP); P.move(0, 0, 700, 300, lambda n: ST.plan_travel(n, sc)); P.svc(ST.PEN_DOWN); P.move(700, 300, 900, 300, None)
+    off, codes = codes_numpy(np.asarray(P.moves, np.int32))
+    base = ST.assemble(P, off, codes, sc)
+    assert ST.assemble(P, off, codes, sc, initial_div=None) == base and ST.assemble(P, off, codes, sc, initial_div=sc.travel_start_div + 1) == base
+    cut = ST.assemble(P, off, codes, sc, initial_div=sc.travel_start_div)
+    assert base[1] == 0x40 | sc.travel_start_div and cut[:1] == base[:1] and cut[1:cut.index(bytes([ST.EOF_BYTE]))] == base[2:base.index(bytes([ST.EOF_BYTE]))]
+
+
+def test_cli_options():
+    from orip import gcode as GC
+    d = options_for([])
+    assert (d.output, d.steps_per_mm, d.invert_y, d.color_index, d.div_start, d.div_fast, d.profile, d.corner_deg, d.corner_div, d.corner_window_steps) == \
+        ("stream_from_gcode.bin", 40.0, 0, 3, 28, 15, "triangle", 85.0, 28, 300)
+    assert (d.travel_div_fast, d.travel_start_div, d.travel_window_steps, d.travel_quant_step, d.short_len_steps, d.short_div, d.speed_scale, d.no_reorder) == \
+        (10, 28, 240, 4, 120, 16, 1.0, False)
+    assert GC.target_size(d) == (8400, 11880)
+    assert GC.target_size(options_for(["--steps-per-mm", "12.5", "--target-width-steps", "300"])) == (2625, 3712)           # one size alone: A4; round half to even
+    assert GC.target_size(options_for(["--target-width-steps", "300", "--target-height-steps", "200"])) == (300, 200)
+    s = GC.apply_speed_scale(options_for(["--speed-scale", "0.5"]))
+    assert (s.div_start, s.div_fast, s.corner_div, s.short_div, s.travel_div_fast, s.travel_start_div) == (56, 30, 56, 32, 20, 56)
+    s = GC.apply_speed_scale(options_for(["--speed-scale", "2", "--div-fast", "5", "--short-div", "3"]))                    # 2.5 -> 2, 1.5 -> 2: half to even
+    assert (s.div_fast, s.short_div, s.div_start) == (2, 2, 14)
+    s = GC.apply_speed_scale(options_for(["--speed-scale", "100"]))                                                         # floor 1
+    assert (s.div_start, s.div_fast, s.corner_div, s.short_div, s.travel_div_fast, s.travel_start_div) == (1, 1, 1, 1, 1, 1)
+    s = GC.apply_speed_scale(options_for(["--speed-scale", "1.5", "--div-start", "12", "--travel-div-fast", "30", "--travel-start-div", "15"]))
+    assert (s.travel_div_fast, s.travel_start_div, s.div_start) == (20, 20, 20)                                            # constraints four and five
+    s = GC.apply_speed_scale(options_for(["--speed-scale", "1.0000001", "--div-start", "7"]))
+    assert s.div_start == 7
+    for bad in ("0", "-1"):
+        with pytest.raises(SystemExit) as e:
+            GC.apply_speed_scale(options_for(["--speed-scale", bad]))
+        assert e.value.code not in (0, None)
+
+
+def test_failures_are_loud(tmp_path):
+    """what the reference refuses is refused: colour outside 0..7 (once there is something to draw), a non-finite coordinate under the pen, a bad scale;
+    and our own limit, a target above 2^30 steps"""
+    from orip import gcode as GC
+    text = bytes(G["text_origin"])
+    with pytest.raises(ValueError):
+        GC.build_stream_from_gcode(text, options_for(["--color-index", "8"]), **DOUBLES)
+    data, _ = GC.build_stream_from_gcode(b"", options_for(["--color-index", "8"]), **DOUBLES)                                # the reference never looks at it
+    assert data == GC.EMPTY_STREAM and data == bytes(G[f"main_{[c[0] for c in MAIN_CASES].index('empty')}_bin"])
+    with pytest.raises((OverflowError, ValueError)):
+        GC.build_stream_from_gcode("M3\nG1 X1e308 Y1\nG1 X2 Y2\n", options_for(["--scale-x", "1e10"]), **DOUBLES)
+    with pytest.raises(ValueError):
+        GC.build_stream_from_gcode(text, options_for(["--target-width-steps", str((1 << 30) + 1), "--target-height-steps", "100"]), **DOUBLES)
+    src = tmp_path / "a.gcode"; src.write_bytes(text)
+    script = os.path.join(ROOT, "omnirevolve-image-processor_amd", "svg_to_stream", "gcode2stream.py")
+    for args in (["--speed-scale", "0"], ["--profile", "sine"]):
+        r = subprocess.run([sys.executable, script, str(src), "-o", str(tmp_path / "o.bin")] + args, capture_output=True, text=True, timeout=120)
+        assert r.returncode != 0 and not (tmp_path / "o.bin").exists()
+
+
+def test_script_without_gpu_fails_loudly_or_matches(tmp_path):
+    """the script has no CPU path: without a usable GPU it exits non-zero and writes nothing; with one it writes the reference's bytes"""
+    src = tmp_path / "a.gcode"; src.write_bytes(bytes(G["text_origin"]))
+    i = [c[0] for c in MAIN_CASES].index("origin")
+    script = os.path.join(ROOT, "omnirevolve-image-processor_amd", "svg_to_stream", "gcode2stream.py")
+    r = subprocess.run([sys.executable, script, str(src), "-o", str(tmp_path / "o.bin")] + MAIN_CASES[i][1], capture_output=True, text=True, timeout=300)
+    if r.returncode == 0:
+        assert (tmp_path / "o.bin").read_bytes() == bytes(G[f"main_{i}_bin"])
+    else:
+        assert "no CPU fallback" in r.stderr and not (tmp_path / "o.bin").exists()
+
+
+def test_flat_corner_flags_equal_per_polyline_flags():
+    from orip import stream as ST
+    rng = np.random.default_rng(3)
+    polys = [np.cumsum(rng.integers(-30, 31, (int(rng.integers(2, 12)), 2)), axis=0) + 500 for _ in range(200)]
+    polys.append(np.array([[0, 0], [100, 0], [100, 100], [0, 100], [0, 0]]))                      # 90 degree corners against thresholds around 90
+    polys.append(np.array([[0, 0], [10, 0], [10, 0], [0, 0]]))                                    # a repeated point: angle 180 by definition
+    off = np.concatenate([[0], np.cumsum([len(p) for p in polys])]); pts = np.concatenate(polys)
+    for deg in (85.0, 90.0, 90.0000001, 120.0):
+        a, b = ST.corner_flags_flat(pts, off, deg)
+        want = [ST.corner_flags(p, deg) for p in polys]
+        assert np.array_equal(a, np.concatenate([w[0] for w in want])) and np.array_equal(b, np.concatenate([w[1] for w in want]))

@@ -205,8 +205,9 @@ typedef struct {
  * step polylines, resident: (v * scale + offset) * steps_per_mm in IEEE double without fused multiply-add, (H - 1) - y under invert_y, round half to
  * even, clamp to [0, W - 1] x [0, H - 1]; a point equal to its predecessor's step position is dropped, then every path left with fewer than two points.
  * Fails (no polylines) when a path of two or more points holds a coordinate that is not finite after the conversion: the reference raises there.
- * Two-call pattern: the fetch copies off[n_out + 1] and pts[total_out, 2] (pts may be NULL). */
-int orip_gcode_to_steps(orip_ctx* ctx, const int64_t* off /* [n+1] */, const double* pts_mm /* [off[n],2] */, int64_t n, const orip_gcode_map* map,
+ * off == NULL and pts_mm == NULL (n > 0): the n fitted paths orip_svg_flatten / orip_svg_fit left resident are converted, as orip_gcode_order takes the
+ * resident step polylines for ends == NULL.  Two-call pattern: the fetch copies off[n_out + 1] and pts[total_out, 2] (pts may be NULL). */
+int orip_gcode_to_steps(orip_ctx* ctx, const int64_t* off /* [n+1] or NULL */, const double* pts_mm /* [off[n],2] or NULL */, int64_t n, const orip_gcode_map* map,
                         int64_t* n_out, int64_t* total_out);
 int orip_gcode_steps_fetch(orip_ctx* ctx, int64_t* off_out /* [n_out+1] */, int32_t* pts_out /* [total_out,2] or NULL */);
 /* order_paths_nearest (:151-172) from (0, 0): order_out[k] = index of the k-th path to draw -- the remaining path whose FIRST point has the smallest
@@ -221,6 +222,28 @@ int orip_gcode_order(orip_ctx* ctx, const int32_t* ends /* [n,4] or NULL */, int
 int orip_stream_pack(orip_ctx* ctx, int64_t n_pieces, const int64_t* code0, const int32_t* cnt, const int64_t* pos, const int32_t* speed, int64_t n_service,
                      const int64_t* svc_pos, const uint8_t* svc_val, int64_t nbytes);
 int orip_stream_pack_fetch(orip_ctx* ctx, uint8_t* out /* [nbytes] */);
+
+/* ---- the third front door: svg_to_stream/svg2stream.py (SVG -> G-code -> plotter stream; csrc/svg.hip) ----
+ * The XML and the path data are parsed on the host (orip/svg.py) into segments; from the control points to the stream bytes the geometry stays here.
+ * orip_svg_flatten: n_seg segments -- kind[s] 1 line / 2 quadratic / 3 cubic Bezier, ctrl[s] its four control points (x, y) in user units (the unused
+ * ones are ignored), mat[s] the index of its matrix (a, b, c, d, e, f): x' = (a x + c y) + e, y' = (b x + d y) + f -- in n_sub subpaths, subpath p = the
+ * segments sub_off[p] .. sub_off[p + 1] - 1 (at least one), each starting where its predecessor ends.  Leaves one polyline per subpath resident, in raw
+ * units (float64): a curve is cut into n equal parameter steps, n the smallest integer >= 1 with n^2 >= |P0 - 2 P1 + P2| / (4 tol) (quadratic) resp.
+ * n^2 >= 3 max |Pi - 2 Pi+1 + Pi+2| / (4 tol) (cubic) over the TRANSFORMED control points, so that curve and chord differ by at most tol at every
+ * parameter; evaluation by de Casteljau in IEEE double without fused multiply-add, in the order csrc/svg.hip states; end points are the control end
+ * points exactly and joints inside a subpath appear once.  total_out receives the number of points.  Errors (no fault, no paths left): tol not positive
+ * and finite, an index out of range, a value that is not finite before or after its matrix, a curve of more than 2^16 pieces, 2^30 points or more.
+ * orip_svg_paths_fetch copies off[n_sub + 1] and pts[total, 2] (pts may be NULL) of the resident paths, flattened or fitted.
+ * orip_svg_bbox: (min x, min y, max x, max y) of the resident points (compute_gcode_bbox, svg2gcode.py:111-141); fails when there are none.
+ * orip_svg_fit: v' = v * s + o per axis in place, in IEEE double without fused multiply-add, then rounded as float(f"{v':.4f}") rounds it (the nearest
+ * multiple of 10^-4 to the exact v', ties to even, as one correctly rounded k / 1e4): scale_and_offset_gcode (:144-172) read back by a G-code parser.
+ * Fails before it changes anything when a fitted coordinate would not be finite or would reach 1e9 in magnitude.
+ * The fitted paths go on to orip_gcode_to_steps(ctx, NULL, NULL, n_sub, ...) without leaving the device. */
+int orip_svg_flatten(orip_ctx* ctx, const int32_t* kind /* [n_seg] */, const double* ctrl /* [n_seg,4,2] */, const int32_t* mat /* [n_seg] */, int64_t n_seg,
+                     const int64_t* sub_off /* [n_sub+1] */, int64_t n_sub, const double* mats /* [n_mat,6] */, int64_t n_mat, double tol, int64_t* total_out);
+int orip_svg_paths_fetch(orip_ctx* ctx, int64_t* off_out /* [n_sub+1] */, double* pts_out /* [total,2] or NULL */);
+int orip_svg_bbox(orip_ctx* ctx, double* box /* [4] */);
+int orip_svg_fit(orip_ctx* ctx, double sx, double sy, double ox, double oy);
 
 /* ---- multi-GPU exchange (no counterpart in the reference, which is a single process) ----
  * One process per GPU; rank r owns the cluster layers {l : l % world == r} for stages 03-08 and 12.  Stage 10 is replicated and needs

@@ -240,32 +240,39 @@ __global__ __launch_bounds__(256) void k_pk_service(const long long* __restrict_
 }
 }  // namespace
 
-// mm paths -> resident step polylines; *n_out paths with *total_out points remain
+// mm paths -> resident step polylines; *n_out paths with *total_out points remain.  off == NULL and pts_mm == NULL: the n resident fitted paths of svg.hip
 extern "C" int orip_gcode_to_steps(orip_ctx* c, const int64_t* off, const double* pts_mm, int64_t n, const orip_gcode_map* map, int64_t* n_out, int64_t* total_out) {
     orip_enter(c);
     ORIP_LANE(c, ORIP_LANE_CROSS);
     c->gc_n = 0; c->gc_total = 0; c->gc_ready = false;
-    if (!map || !n_out || !total_out || n < 0 || (n > 0 && !off)) ORIP_FAIL(c, "bad arguments");
+    const bool resident = !off && !pts_mm && n > 0;         // the fitted paths orip_svg_flatten / orip_svg_fit left on the device (svg.hip)
+    if (!map || !n_out || !total_out || n < 0 || (n > 0 && !off && !resident)) ORIP_FAIL(c, "bad arguments");
     *n_out = 0; *total_out = 0;
+    if (resident && (!c->sv_ready || n != c->sv_n)) ORIP_FAIL(c, "%lld paths asked for, %lld fitted paths resident", (long long)n, (long long)(c->sv_ready ? c->sv_n : -1));
     if (map->W < 1 || map->H < 1 || map->W > GC_COORD_MAX || map->H > GC_COORD_MAX)
         ORIP_FAIL(c, "target size %d x %d steps: each side must be in 1..2^30 (step coordinates are int32 on the device)", map->W, map->H);
-    const int64_t total = n > 0 ? off[n] : 0;
-    if (n > 0 && off[0] != 0) ORIP_FAIL(c, "offsets must start at 0");
-    for (int64_t p = 0; p < n; p++) if (off[p + 1] < off[p]) ORIP_FAIL(c, "offsets must not decrease (path %lld)", (long long)p);
+    const int64_t total = resident ? c->sv_total : n > 0 ? off[n] : 0;
+    if (!resident) {
+        if (n > 0 && off[0] != 0) ORIP_FAIL(c, "offsets must start at 0");
+        for (int64_t p = 0; p < n; p++) if (off[p + 1] < off[p]) ORIP_FAIL(c, "offsets must not decrease (path %lld)", (long long)p);
+    }
     if (n >= INT32_MAX / 2 || total >= INT32_MAX / 2) ORIP_FAIL(c, "%lld paths, %lld points: at most 2^30 of each", (long long)n, (long long)total);
-    if (total > 0 && !pts_mm) ORIP_FAIL(c, "bad arguments");
+    if (total > 0 && !pts_mm && !resident) ORIP_FAIL(c, "bad arguments");
     hipStream_t s = LN(c).stream;
     HIPC(c, c->gc_off.ensure(64)); HIPC(c, hipMemsetAsync(c->gc_off.p, 0, 8, s));
     if (total == 0) { HIPC(c, hipStreamSynchronize(s)); c->gc_ready = true; return 0; }
     long long* d_off; double2* d_mm; int2* xy; unsigned *keep, *kpos, *pid, *pc, *pk, *noff, *nidx; int* err;
     Carve L;
-    L.take(d_off, (size_t)n + 1); L.take(d_mm, (size_t)total); L.take(xy, (size_t)total); L.take(keep, (size_t)total + 1); L.take(kpos, (size_t)total + 1);
+    L.take(d_off, resident ? 0 : (size_t)n + 1); L.take(d_mm, resident ? 0 : (size_t)total); L.take(xy, (size_t)total); L.take(keep, (size_t)total + 1); L.take(kpos, (size_t)total + 1);
     L.take(pid, (size_t)total); L.take(pc, (size_t)n + 1); L.take(pk, (size_t)n + 1); L.take(noff, (size_t)n + 1); L.take(nidx, (size_t)n + 1); L.take(err, 1);
     HIPC(c, L.commit(c->gc_tmp, 64));
     HIPC(c, c->gc_off.ensure((size_t)(n + 1) * 8 + 64)); HIPC(c, c->gc_pts.ensure((size_t)total * 8 + 64));     // the output is never larger than the input
     HIPC(c, hipMemsetAsync(c->gc_off.p, 0, 8, s));
-    HIPC(c, hipMemcpyAsync(d_off, off, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, s));
-    HIPC(c, hipMemcpyAsync(d_mm, pts_mm, (size_t)total * 16, hipMemcpyHostToDevice, s));
+    if (resident) { d_off = c->sv_off.as<long long>(); d_mm = c->sv_pts.as<double2>(); }
+    else {
+        HIPC(c, hipMemcpyAsync(d_off, off, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, s));
+        HIPC(c, hipMemcpyAsync(d_mm, pts_mm, (size_t)total * 16, hipMemcpyHostToDevice, s));
+    }
     HIPC(c, hipMemsetAsync(err, 0, 4, s));
     { ProfScope ps(c, "k_gc_points");
       hipLaunchKernelGGL(k_gc_points, dim3(cdiv(total + 1, 256)), dim3(256), 0, s, d_off, n, d_mm, total, *map, xy, keep, pid, err); }

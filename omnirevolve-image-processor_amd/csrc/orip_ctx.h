@@ -276,6 +276,9 @@ struct orip_ctx {
     // gcode2stream (gcode.hip): scratch of the conversion, the resident step polylines (off int64[gc_n + 1], pts int2[gc_total]) between orip_gcode_to_steps and
     // the fetch / orip_gcode_order, ends + order and the grid of the order, the piece table and the packed bytes between orip_stream_pack and its fetch
     DBuf gc_tmp, gc_off, gc_pts, gc_ends, gc_grid, pk_tab, pk_out; int64_t gc_n = 0, gc_total = 0, pk_bytes = -1; bool gc_ready = false;
+    // svg2stream (svg.hip): scratch of the flattening and of the box, the resident paths (off int64[sv_n + 1], pts double2[sv_total]; raw units after
+    // orip_svg_flatten, page mm after orip_svg_fit) until the next flatten; orip_gcode_to_steps reads them when it is called without pointers
+    DBuf sv_tmp, sv_tmp2, sv_off, sv_pts; int64_t sv_n = 0, sv_total = 0; bool sv_ready = false, sv_box_ok = false; double sv_box[4] = {0, 0, 0, 0};
     DBuf resize_src, resize_dst;                       // raster01.hip staging
     int memo_pre_K = 0, memo_pre_H = 0, memo_pre_W = 0; // orip_contours_reserve cleared this many memo planes of an H x W image
     // profiling

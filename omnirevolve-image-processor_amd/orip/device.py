@@ -301,6 +301,53 @@ class Device:
         self._ck(self.L.orip_gcode_steps_fetch(self.h, _p(off_s), _p(pts_s) if fetch_points else None))
         return off_s, pts_s[:tot.value]
 
+    def gcode_to_steps_resident(self, n: int, map: dict, fetch_points: bool = True) -> Tuple[np.ndarray, np.ndarray]:
+        """gcode_to_steps of the n fitted paths svg_flatten / svg_fit left on the device (off == NULL, pts_mm == NULL)"""
+        m = _l.GcodeMap(**{k: map[k] for k, _ in _l.GcodeMap._fields_})
+        n_out, tot = C.c_int64(0), C.c_int64(0)
+        self._ck(self.L.orip_gcode_to_steps(self.h, None, None, int(n), C.byref(m), C.byref(n_out), C.byref(tot)))
+        off_s = np.zeros(n_out.value + 1, np.int64)
+        pts_s = np.zeros((max(tot.value, 1), 2), np.int32)
+        self._ck(self.L.orip_gcode_steps_fetch(self.h, _p(off_s), _p(pts_s) if fetch_points else None))
+        return off_s, pts_s[:tot.value]
+
+    # ---- svg2stream: flatten, bounding box, fit (include/orip.h; csrc/svg.hip)
+    def svg_flatten(self, table, tol: float) -> int:
+        """segments of an orip.svg.SegmentTable (mats: its raw matrices) -> resident polylines in raw units; returns the number of points"""
+        kind = np.ascontiguousarray(table.kind, np.int32).reshape(-1); ctrl = np.ascontiguousarray(table.ctrl, np.float64).reshape(-1, 4, 2)
+        mi = np.ascontiguousarray(table.mat, np.int32).reshape(-1); sub = np.ascontiguousarray(table.sub_off, np.int64).reshape(-1)
+        mats = np.ascontiguousarray(table.raw_mats(), np.float64).reshape(-1, 6)
+        if not (len(kind) == len(ctrl) == len(mi)) or len(sub) < 1:
+            raise ValueError("segment table: kind, ctrl and mat must have one entry per segment, sub_off at least one")
+        ns, nsub = len(kind), len(sub) - 1
+        self._svg_n = 0
+        total = C.c_int64(0)
+        self._ck(self.L.orip_svg_flatten(self.h, _p(kind) if ns else None, _p(ctrl) if ns else None, _p(mi) if ns else None, ns, _p(sub) if ns else None, nsub,
+                                         _p(mats) if len(mats) else None, len(mats), float(tol), C.byref(total)))
+        self._svg_n = nsub
+        return int(total.value)
+
+    def svg_paths(self, n: int | None = None, with_points: bool = True):
+        """the resident paths, flattened or fitted: (off int64 [n + 1], pts float64 [total, 2], or None without the points)"""
+        n = self._svg_n if n is None else int(n)
+        off = np.zeros(n + 1, np.int64)
+        self._ck(self.L.orip_svg_paths_fetch(self.h, _p(off), None))
+        if not with_points:
+            return off, None
+        pts = np.zeros((max(int(off[-1]), 1), 2), np.float64)
+        self._ck(self.L.orip_svg_paths_fetch(self.h, _p(off), _p(pts)))
+        return off, pts[:int(off[-1])]
+
+    def svg_bbox(self) -> Tuple[float, float, float, float]:
+        """(min x, min y, max x, max y) of the resident points"""
+        box = np.zeros(4, np.float64)
+        self._ck(self.L.orip_svg_bbox(self.h, _p(box)))
+        return tuple(float(v) for v in box)
+
+    def svg_fit(self, sx: float, sy: float, ox: float, oy: float) -> None:
+        """v * s + o per axis, rounded to four decimals as float(f"{v:.4f}") rounds, in place on the resident paths"""
+        self._ck(self.L.orip_svg_fit(self.h, float(sx), float(sy), float(ox), float(oy)))
+
     def gcode_order(self, ends: np.ndarray | None, n: int | None = None) -> np.ndarray:
         """order of the paths (first x, first y, last x, last y) int32 [n, 4]; ends None: the n resident step polylines of gcode_to_steps"""
         if ends is not None:

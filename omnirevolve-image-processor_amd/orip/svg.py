@@ -1,0 +1,677 @@
+"""SVG -> plotter stream: the third front door of the reference (svg_to_stream/svg2stream.py = svg2gcode.py, then gcode2stream.py, then the previewer), in one
+process and with the geometry on the device from the control points to the stream bytes.
+
+The XML and the path data are parsed on the host into a SegmentTable (lines, quadratic and cubic Beziers in user units, one 2 x 3 matrix per transformed
+element; arcs, circles, ellipses and rounded corners become cubics HERE, pieces of at most 90 degrees with handles 4/3 tan(theta / 4), so the device sees
+polynomials only).  The device flattens the curves (orip_svg_flatten), takes the bounding box (orip_svg_bbox) and fits the drawing onto the page with the
+reference's 4-decimal rounding (orip_svg_fit); orip_gcode_to_steps then reads the fitted paths where they lie and the rest is orip/gcode.py.
+
+What is the reference's and what is ours.  svg2gcode.py leaves the geometry to the third-party svg_to_gcode package, which is not available to compare
+against: the point set chosen for a curve is ours.  It is held to the curve within --tolerance-mm.  It is not the svg_to_gcode package's subdivision, and
+neither are the Y-up convention or the element coverage, because that package is not available to compare against.  From the fitted coordinates onward,
+every byte is the reference's: the box over all points (:111-141), the aspect-preserving fit (:320-351), v * s + o printed with :.4f (:144-172), and
+gcode2stream.py on that text.  viewBox is not applied to the geometry: the reference's docstring says it does not rely on it, and the fit makes a uniform
+viewBox scale irrelevant.  Raw Y is canvas height - y (Y-up G-code, [recalled]: DESIGN 5), the height by the rule of ensure_svg_has_size (:57-102).
+
+The tolerance.  The distance between the curve at parameter t and the emitted chord at the same t is at most tolerance_mm in page mm, with the scale that
+was finally applied.  The scale depends on the box and the box on the flattening; tolerance_bound() breaks the circle with a bound that holds before any
+curve is cut: every curve's end points are in the final point set, so the final box contains the box of the end points alone and the final automatic scale
+is at most the scale of that smaller box.  build_stream_from_svg checks the applied scale against the bound afterwards and flattens again only when the
+end points' box says nothing (all of them on one point).
+
+The device steps are injectable, as in orip/gcode.py, so that this host logic can be tested without a GPU; the product has no CPU path."""
+from __future__ import annotations
+
+import argparse
+import math
+import re
+import xml.etree.ElementTree as ET
+from dataclasses import dataclass, fields
+from pathlib import Path
+from typing import Callable, List, Optional, Sequence, Tuple, Union
+
+import numpy as np
+
+from . import gcode as GC
+
+LINE, QUAD, CUBIC = 1, 2, 3
+KAPPA = 4.0 / 3.0 * math.tan(math.pi / 8.0)            # handle length of a 90 degree piece, per unit radius
+IDENTITY = (1.0, 0.0, 0.0, 1.0, 0.0, 0.0)
+SKIPPED = {"defs", "clipPath", "mask", "symbol", "pattern", "marker"}
+GROUPS = {"svg", "g", "a", "switch"}
+
+
+# ------------------------------------------------------------------ the table
+@dataclass
+class SegmentTable:
+    """Flat arrays.  Segment s: kind[s] (LINE / QUAD / CUBIC), ctrl[s] its control points in user units (the unused ones repeat the last), mat[s] the index of
+    its matrix in mats (a, b, c, d, e, f: x' = a x + c y + e, y' = b x + d y + f).  Subpath p = segments sub_off[p] .. sub_off[p + 1] - 1, one pen-down path;
+    closed[p]: it ended with Z (the closing line is one of its segments)."""
+    kind: np.ndarray
+    ctrl: np.ndarray
+    mat: np.ndarray
+    sub_off: np.ndarray
+    closed: np.ndarray
+    mats: np.ndarray
+    canvas_height: float = 100.0
+
+    @property
+    def n_seg(self) -> int: return len(self.kind)
+    @property
+    def n_sub(self) -> int: return len(self.sub_off) - 1
+
+    def raw_mats(self) -> np.ndarray:
+        """the matrices with raw Y = canvas_height - y folded in: what the device applies"""
+        m = np.array(self.mats, np.float64).reshape(-1, 6)
+        m[:, 1] = -m[:, 1]; m[:, 3] = -m[:, 3]; m[:, 5] = float(self.canvas_height) - m[:, 5]
+        return m
+
+
+def _mul(A, B):
+    """A after B"""
+    return (A[0] * B[0] + A[2] * B[1], A[1] * B[0] + A[3] * B[1], A[0] * B[2] + A[2] * B[3], A[1] * B[2] + A[3] * B[3],
+            A[0] * B[4] + A[2] * B[5] + A[4], A[1] * B[4] + A[3] * B[5] + A[5])
+
+
+class _Builder:
+    def __init__(self):
+        self.kind: List[int] = []; self.ctrl: List[Tuple[float, ...]] = []; self.mat: List[int] = []
+        self.sub_off = [0]; self.closed: List[int] = []
+        self.mats: List[Tuple[float, ...]] = [IDENTITY]
+        self.m = 0
+        self.cur = self.start = (0.0, 0.0)
+
+    def _seg(self, kind, *p):
+        q = list(p) + [p[-1]] * (4 - len(p))
+        self.kind.append(kind); self.ctrl.append(tuple(v for xy in q for v in xy)); self.mat.append(self.m)
+        self.cur = p[-1]
+
+    def end(self, closed=False):
+        if len(self.kind) > self.sub_off[-1]:
+            self.sub_off.append(len(self.kind)); self.closed.append(int(closed))
+
+    def move(self, x, y):
+        self.end(); self.cur = self.start = (x, y)
+
+    def line(self, x, y): self._seg(LINE, self.cur, (x, y))
+    def quad(self, x1, y1, x, y): self._seg(QUAD, self.cur, (x1, y1), (x, y))
+    def cubic(self, x1, y1, x2, y2, x, y): self._seg(CUBIC, self.cur, (x1, y1), (x2, y2), (x, y))
+
+    def close(self):
+        if self.cur != self.start:
+            self.line(*self.start)
+        self.end(closed=True); self.cur = self.start
+
+    def corner(self, cx, cy, x, y):
+        """a quarter of an ellipse from the current point to (x, y); (cx, cy) is where the two tangents meet"""
+        x0, y0 = self.cur
+        self.cubic(x0 + KAPPA * (cx - x0), y0 + KAPPA * (cy - y0), x + KAPPA * (cx - x), y + KAPPA * (cy - y), x, y)
+
+    def arc(self, rx, ry, rot, large, sweep, x2, y2):
+        """SVG implementation notes F.6: end point to centre form, radii corrected, cut into pieces of at most 90 degrees"""
+        x1, y1 = self.cur
+        if x1 == x2 and y1 == y2:
+            return
+        rx, ry = abs(rx), abs(ry)
+        if rx == 0.0 or ry == 0.0:
+            return self.line(x2, y2)
+        phi = math.radians(rot % 360.0)
+        cp, sp = math.cos(phi), math.sin(phi)
+        dx, dy = (x1 - x2) / 2.0, (y1 - y2) / 2.0
+        xp, yp = cp * dx + sp * dy, -sp * dx + cp * dy
+        lam = xp * xp / (rx * rx) + yp * yp / (ry * ry)
+        if lam > 1.0:
+            rx *= math.sqrt(lam); ry *= math.sqrt(lam)
+        num = rx * rx * ry * ry - rx * rx * yp * yp - ry * ry * xp * xp
+        den = rx * rx * yp * yp + ry * ry * xp * xp
+        co = math.sqrt(max(0.0, num / den)) * (-1.0 if bool(large) == bool(sweep) else 1.0)
+        cxp, cyp = co * rx * yp / ry, -co * ry * xp / rx
+        cx, cy = cp * cxp - sp * cyp + (x1 + x2) / 2.0, sp * cxp + cp * cyp + (y1 + y2) / 2.0
+        th1 = math.atan2((yp - cyp) / ry, (xp - cxp) / rx)
+        dth = math.atan2((-yp - cyp) / ry, (-xp - cxp) / rx) - th1
+        if sweep and dth < 0.0: dth += 2.0 * math.pi
+        elif not sweep and dth > 0.0: dth -= 2.0 * math.pi
+        n = max(1, int(math.ceil(abs(dth) / (math.pi / 2.0) - 1e-9)))
+        d = dth / n
+        k = 4.0 / 3.0 * math.tan(d / 4.0)
+
+        def at(t):
+            c, s = math.cos(t), math.sin(t)
+            return (cx + cp * rx * c - sp * ry * s, cy + sp * rx * c + cp * ry * s), (-cp * rx * s - sp * ry * c, -sp * rx * s + cp * ry * c)
+        for i in range(n):
+            (_, _), (ax, ay) = at(th1 + i * d)
+            (ex, ey), (bx, by) = at(th1 + (i + 1) * d)
+            if i == n - 1:
+                ex, ey = x2, y2
+            x0, y0 = self.cur
+            self.cubic(x0 + k * ax, y0 + k * ay, ex - k * bx, ey - k * by, ex, ey)
+
+    def table(self, canvas_height) -> SegmentTable:
+        self.end()
+        return SegmentTable(np.asarray(self.kind, np.int32), np.asarray(self.ctrl, np.float64).reshape(-1, 4, 2), np.asarray(self.mat, np.int32),
+                            np.asarray(self.sub_off, np.int64), np.asarray(self.closed, np.uint8), np.asarray(self.mats, np.float64).reshape(-1, 6), float(canvas_height))
+
+
+# ------------------------------------------------------------------ path data
+_NUM = re.compile(r"[+-]?(?:\d+\.?\d*|\.\d+)(?:[eE][+-]?\d+)?")
+_SEP = re.compile(r"[\s,]*")
+_ARGS = {"M": 2, "L": 2, "H": 1, "V": 1, "C": 6, "S": 4, "Q": 4, "T": 2, "A": 7, "Z": 0}
+
+
+class _Stop(Exception):
+    pass
+
+
+def tokenize_path(d: str) -> List[Tuple[str, Tuple[float, ...]]]:
+    """(command letter, arguments) of every complete command of a path data string, implicit repetitions spelled out (M's as L, m's as l); numbers
+    need no separators (1.5.5, -1-2, 1e-3) and an arc's flags may be glued to what follows (a1 1 0 011 1).  Stops in front of the first thing that
+    is not a complete command: what came before it stands."""
+    out: List[Tuple[str, Tuple[float, ...]]] = []
+    pos, cmd = 0, None
+
+    def skip():
+        nonlocal pos
+        pos = _SEP.match(d, pos).end()
+
+    def num():
+        nonlocal pos
+        skip()
+        m = _NUM.match(d, pos)
+        if not m:
+            raise _Stop
+        pos = m.end()
+        return float(m.group())
+
+    def flag():
+        nonlocal pos
+        skip()
+        if pos < len(d) and d[pos] in "01":
+            pos += 1
+            return float(d[pos - 1])
+        raise _Stop
+    try:
+        while True:
+            skip()
+            if pos >= len(d):
+                break
+            ch = d[pos]
+            if ch.isalpha():
+                if ch.upper() not in _ARGS or (not out and ch.upper() != "M"):
+                    break
+                cmd = ch; pos += 1
+                if ch.upper() == "Z":
+                    out.append((ch, ()))
+                    continue
+            elif cmd is None or cmd.upper() == "Z":
+                break
+            elif cmd == "M": cmd = "L"
+            elif cmd == "m": cmd = "l"
+            if cmd.upper() == "A":
+                a = (num(), num(), num(), flag(), flag(), num(), num())
+            else:
+                a = tuple(num() for _ in range(_ARGS[cmd.upper()]))
+            out.append((cmd, a))
+            if cmd == "M": cmd = "L"
+            elif cmd == "m": cmd = "l"
+    except _Stop:
+        pass
+    return out
+
+
+def _draw_path(b: _Builder, d: str):
+    prev = ""
+    c2 = q1 = None                                   # the last cubic's second handle, the last quadratic's handle
+    first = True
+    b.cur = b.start = (0.0, 0.0)
+    for cmd, a in tokenize_path(d):
+        up = cmd.upper()
+        rel = cmd.islower()
+        x0, y0 = b.cur
+        ox, oy = (x0, y0) if rel else (0.0, 0.0)
+        if up == "M" or (first and up == "L"):
+            b.move(a[0] + ox, a[1] + oy)
+        elif up == "Z": b.close()
+        elif up == "L": b.line(a[0] + ox, a[1] + oy)
+        elif up == "H": b.line(a[0] + ox, y0)
+        elif up == "V": b.line(x0, a[0] + oy)
+        elif up == "C":
+            b.cubic(a[0] + ox, a[1] + oy, a[2] + ox, a[3] + oy, a[4] + ox, a[5] + oy); c2 = (a[2] + ox, a[3] + oy)
+        elif up == "S":
+            h = (2.0 * x0 - c2[0], 2.0 * y0 - c2[1]) if prev in "CS" and prev else (x0, y0)
+            b.cubic(h[0], h[1], a[0] + ox, a[1] + oy, a[2] + ox, a[3] + oy); c2 = (a[0] + ox, a[1] + oy)
+        elif up == "Q":
+            b.quad(a[0] + ox, a[1] + oy, a[2] + ox, a[3] + oy); q1 = (a[0] + ox, a[1] + oy)
+        elif up == "T":
+            q1 = (2.0 * x0 - q1[0], 2.0 * y0 - q1[1]) if prev in "QT" and prev else (x0, y0)
+            b.quad(q1[0], q1[1], a[0] + ox, a[1] + oy)
+        elif up == "A": b.arc(a[0], a[1], a[2], a[3] != 0.0, a[4] != 0.0, a[5] + ox, a[6] + oy)
+        prev = up; first = False
+    b.end()
+
+
+# ------------------------------------------------------------------ elements
+_LEN = re.compile(r"^([+-]?\d*\.?\d+(?:[eE][+-]?\d+)?)([a-zA-Z%]*)$")
+_TF = re.compile(r"(matrix|translate|scale|rotate|skewX|skewY)\s*\(([^)]*)\)")
+
+
+def parse_length(s: Optional[str]) -> Optional[float]:
+    """'123', '123px', '210mm' -> the number, the unit dropped; anything else -> None"""
+    if s is None:
+        return None
+    m = _LEN.match(s.strip())
+    return float(m.group(1)) if m else None
+
+
+def parse_transform(s: Optional[str]):
+    """the product of a transform list, in document order (the first entry is applied last to a point)"""
+    M = IDENTITY
+    for name, args in _TF.findall(s or ""):
+        v = [float(t) for t in _NUM.findall(args)]
+        if name == "matrix" and len(v) == 6: T = tuple(v)
+        elif name == "translate" and len(v) in (1, 2): T = (1.0, 0.0, 0.0, 1.0, v[0], v[1] if len(v) == 2 else 0.0)
+        elif name == "scale" and len(v) in (1, 2): T = (v[0], 0.0, 0.0, v[1] if len(v) == 2 else v[0], 0.0, 0.0)
+        elif name == "rotate" and len(v) in (1, 3):
+            c, sn = math.cos(math.radians(v[0])), math.sin(math.radians(v[0]))
+            T = (c, sn, -sn, c, 0.0, 0.0)
+            if len(v) == 3:
+                T = _mul(_mul((1.0, 0.0, 0.0, 1.0, v[1], v[2]), T), (1.0, 0.0, 0.0, 1.0, -v[1], -v[2]))
+        elif name == "skewX" and len(v) == 1: T = (1.0, 0.0, math.tan(math.radians(v[0])), 1.0, 0.0, 0.0)
+        elif name == "skewY" and len(v) == 1: T = (1.0, math.tan(math.radians(v[0])), 0.0, 1.0, 0.0, 0.0)
+        else:
+            continue
+        M = _mul(M, T)
+    return M
+
+
+def canvas_height(root) -> float:
+    """the height svg2gcode.py's ensure_svg_has_size leaves on the root (:57-102): its own when width and height are there, else the rounded viewBox
+    height, else the rounded height, else 100.  A height that does not read as a number counts as 100."""
+    h = root.get("height")
+    if h:                                               # a height that is there is never rewritten, whatever the width
+        v = parse_length(h)
+        return v if v is not None else 100.0
+    vb = root.get("viewBox") or root.get("viewbox")
+    vb_h = 100.0
+    if vb:
+        parts = vb.replace(",", " ").split()
+        if len(parts) == 4:
+            try:
+                float(parts[2]); vb_h = float(parts[3])
+            except ValueError:
+                vb_h = 100.0
+    return float(int(round(vb_h)))
+
+
+def _f(el, name, default=0.0) -> float:
+    v = parse_length(el.get(name))
+    return default if v is None else v
+
+
+def _draw_element(b: _Builder, el, tag: str):
+    if tag == "path":
+        _draw_path(b, el.get("d") or "")
+    elif tag == "line":
+        b.move(_f(el, "x1"), _f(el, "y1")); b.line(_f(el, "x2"), _f(el, "y2")); b.end()
+    elif tag in ("polyline", "polygon"):
+        v = [float(t) for t in _NUM.findall(el.get("points") or "")]
+        pts = list(zip(v[0::2], v[1::2]))
+        if len(pts) >= 2:
+            b.move(*pts[0])
+            for p in pts[1:]:
+                b.line(*p)
+            b.close() if tag == "polygon" else b.end()
+    elif tag == "rect":
+        x, y, w, h = _f(el, "x"), _f(el, "y"), _f(el, "width"), _f(el, "height")
+        rx, ry = parse_length(el.get("rx")), parse_length(el.get("ry"))
+        if w <= 0.0 or h <= 0.0:
+            return
+        rx, ry = (ry if rx is None else rx), (rx if ry is None else ry)
+        rx, ry = min(max(rx or 0.0, 0.0), w / 2.0), min(max(ry or 0.0, 0.0), h / 2.0)
+        if rx == 0.0 or ry == 0.0:
+            b.move(x, y); b.line(x + w, y); b.line(x + w, y + h); b.line(x, y + h); b.close()
+            return
+        b.move(x + rx, y)
+        for (lx, ly), (cx, cy), (ex, ey) in (((x + w - rx, y), (x + w, y), (x + w, y + ry)), ((x + w, y + h - ry), (x + w, y + h), (x + w - rx, y + h)),
+                                             ((x + rx, y + h), (x, y + h), (x, y + h - ry)), ((x, y + ry), (x, y), (x + rx, y))):
+            if (lx, ly) != b.cur:
+                b.line(lx, ly)
+            b.corner(cx, cy, ex, ey)
+        b.close()
+    elif tag in ("circle", "ellipse"):
+        cx, cy = _f(el, "cx"), _f(el, "cy")
+        rx, ry = (_f(el, "r"), _f(el, "r")) if tag == "circle" else (_f(el, "rx"), _f(el, "ry"))
+        if rx <= 0.0 or ry <= 0.0:
+            return
+        b.move(cx + rx, cy)
+        b.corner(cx + rx, cy + ry, cx, cy + ry); b.corner(cx - rx, cy + ry, cx - rx, cy)
+        b.corner(cx - rx, cy - ry, cx, cy - ry); b.corner(cx + rx, cy - ry, cx + rx, cy)
+        b.close()
+
+
+def _walk(b: _Builder, el, m: int):
+    tag = el.tag.rsplit("}", 1)[-1] if isinstance(el.tag, str) else ""
+    if not tag or tag in SKIPPED or (el.get("display") or "").strip() == "none":
+        return
+    if el.get("transform"):
+        b.mats.append(_mul(b.mats[m], parse_transform(el.get("transform"))))
+        m = len(b.mats) - 1
+    if tag in GROUPS:
+        for ch in el:
+            _walk(b, ch, m)
+    else:
+        b.m = m
+        _draw_element(b, el, tag)
+        b.end()
+
+
+def parse_svg(text: Union[str, bytes]) -> SegmentTable:
+    root = ET.fromstring(text)
+    b = _Builder()
+    _walk(b, root, 0)
+    return b.table(canvas_height(root))
+
+
+# ------------------------------------------------------------------ options, fit, tolerance
+@dataclass
+class SvgOptions:
+    """The command lines of svg2gcode.py (:178-259) and svg2stream.py (:34-156): same names, same defaults; tolerance_mm is ours (None: half a step)."""
+    output: str = "from_svg.gcode"
+    movement_speed: float = 8000.0
+    cutting_speed: float = 2000.0
+    passes: int = 1
+    pass_depth: float = 0.0
+    page_width_mm: float = 210.0
+    page_height_mm: float = 297.0
+    margin_mm: float = 10.0
+    scale: Optional[float] = None
+    scale_x: Optional[float] = None
+    scale_y: Optional[float] = None
+    output_stream: Optional[str] = None
+    gcode_output: Optional[str] = None
+    steps_per_mm: float = 40.0
+    target_width_steps: Optional[int] = None
+    target_height_steps: Optional[int] = None
+    invert_y: int = 0
+    color_index: int = 3
+    speed_scale: float = 1.0
+    no_reorder: bool = False
+    no_preview: bool = False
+    preview_render_width: int = 1200
+    preview_render_height: int = 900
+    tolerance_mm: Optional[float] = None
+
+
+def tolerance_mm(o: SvgOptions) -> float:
+    t = 0.5 / float(o.steps_per_mm) if o.tolerance_mm is None else float(o.tolerance_mm)
+    if not (t > 0.0 and math.isfinite(t)):
+        raise ValueError("--tolerance-mm must be a positive number")
+    return t
+
+
+def _avail(o: SvgOptions) -> Tuple[float, float]:
+    return max(1e-6, o.page_width_mm - 2.0 * o.margin_mm), max(1e-6, o.page_height_mm - 2.0 * o.margin_mm)
+
+
+def _user_scales(o: SvgOptions) -> Tuple[Optional[float], Optional[float]]:
+    sx = sy = o.scale
+    if o.scale_x is not None: sx = o.scale_x
+    if o.scale_y is not None: sy = o.scale_y
+    return sx, sy
+
+
+def fit_transform(bbox, o: SvgOptions) -> Tuple[float, float, float, float]:
+    """(sx, sy, offset_x, offset_y) of svg2gcode.py:320-351 in Python floats.  A box of zero width or height: the reference copies its text unfitted;
+    ours is not text, so the paths go through the same rounding with s = 1, o = 0 (stated deviation)."""
+    min_x, min_y, max_x, max_y = (float(v) for v in bbox)
+    width, height = max_x - min_x, max_y - min_y
+    if width <= 0 or height <= 0:
+        return 1.0, 1.0, 0.0, 0.0
+    aw, ah = _avail(o)
+    auto = min(aw / width, ah / height)
+    ux, uy = _user_scales(o)
+    sx = auto if ux is None else ux
+    sy = auto if uy is None else uy
+    return sx, sy, o.margin_mm - min_x * sx, o.margin_mm - min_y * sy
+
+
+def tolerance_bound(table: SegmentTable, o: SvgOptions) -> float:
+    """An upper bound of the largest scale fit_transform can return for this table, from its end points alone (module docstring).  Along an axis on
+    which all end points agree that axis says nothing; if both do, the control hull stands in (a guess, checked after the fact by the caller).  Such
+    a drawing may also come out with a box of zero width or height, which is fitted with scale 1."""
+    ux, uy = _user_scales(o)
+    m = table.raw_mats()[table.mat]
+    last = np.take_along_axis(table.ctrl, np.clip(table.kind, 1, 3).reshape(-1, 1, 1).repeat(2, 2).astype(np.int64), 1)[:, 0]
+
+    def raw(p):
+        return np.stack([m[:, 0] * p[:, 0] + m[:, 2] * p[:, 1] + m[:, 4], m[:, 1] * p[:, 0] + m[:, 3] * p[:, 1] + m[:, 5]], 1)
+    ends = np.concatenate([raw(table.ctrl[:, 0]), raw(last)])
+    aw, ah = _avail(o)
+
+    def scales(p):
+        w, h = np.ptp(p[:, 0]), np.ptp(p[:, 1])
+        return [a / e for a, e in ((aw, w), (ah, h)) if e > 0], w > 0 and h > 0
+    cand, full = scales(ends)
+    if not cand:
+        cand, _ = scales(np.concatenate([raw(table.ctrl[:, j]) for j in range(4)]))
+    bound = [abs(u) for u in (ux, uy) if u is not None]
+    if len(bound) < 2:
+        bound.append(min(cand) if cand else 1.0)
+    if not full:
+        bound.append(1.0)
+    return max(bound) or 1.0
+
+
+def gcode_options(o: SvgOptions) -> GC.GcodeOptions:
+    """what svg2stream.py forwards to gcode2stream.py (:264-290): scale 1, offsets 0, the canvas from the page unless both sizes are given"""
+    if o.target_width_steps is not None and o.target_height_steps is not None:
+        W, H = int(o.target_width_steps), int(o.target_height_steps)
+    else:
+        W, H = int(round(o.page_width_mm * o.steps_per_mm)), int(round(o.page_height_mm * o.steps_per_mm))
+    return GC.GcodeOptions(steps_per_mm=o.steps_per_mm, invert_y=o.invert_y, color_index=o.color_index, speed_scale=o.speed_scale, scale_x=1.0, scale_y=1.0,
+                           offset_x_mm=0.0, offset_y_mm=0.0, target_width_steps=W, target_height_steps=H, no_reorder=bool(o.no_reorder))
+
+
+def gcode_text(off, pts, passes: int = 1) -> str:
+    """the fitted paths in a dialect the reference's parser reads: G21, G90, M5; per path G0 to its first point, M3, one G1 per further point, M5"""
+    off = np.asarray(off, np.int64); pts = np.asarray(pts, np.float64).reshape(-1, 2)
+    xy = ["X%.4f Y%.4f" % (x, y) for x, y in pts.tolist()]
+    out = ["G21", "G90", "M5"]
+    for _ in range(max(1, int(passes))):
+        for a, b in zip(off[:-1].tolist(), off[1:].tolist()):
+            if b - a < 1:
+                continue
+            out.append("G0 " + xy[a]); out.append("M3")
+            out.extend("G1 " + s for s in xy[a + 1:b])
+            out.append("M5")
+    return "\n".join(out) + "\n"
+
+
+class _Resident:
+    """the device steps; `paths` is only a count, the points stay where orip_svg_flatten left them"""
+    def __init__(self, dev): self.dev = dev
+    def flatten(self, table, tol): return {"n": table.n_sub, "total": self.dev.svg_flatten(table, tol)}
+    def bbox(self, paths): return self.dev.svg_bbox()
+    def fit(self, paths, sx, sy, ox, oy): self.dev.svg_fit(sx, sy, ox, oy); return paths
+    def fetch(self, paths, with_points=True): return self.dev.svg_paths(paths["n"], with_points)
+    def steps(self, paths, m): return self.dev.gcode_to_steps_resident(paths["n"], m)
+
+
+MAX_REFLATTEN = 8
+
+
+def fit_paths(table: SegmentTable, o: SvgOptions, flatten_fn, bbox_fn, fit_fn, tm: Optional[dict] = None):
+    """flatten -> bbox -> fit with the tolerance kept: (paths, {"tol_raw", "scale": (sx, sy, ox, oy), "bbox", "flattens"})"""
+    import time
+    tm = tm if tm is not None else {}
+
+    def lap(name, t0):
+        tm[name] = tm.get(name, 0.0) + (time.perf_counter() - t0)
+    tol = tolerance_mm(o)
+    tol_raw = tol / tolerance_bound(table, o)
+    for k in range(MAX_REFLATTEN):
+        t0 = time.perf_counter(); paths = flatten_fn(table, tol_raw); lap("flatten", t0)
+        t0 = time.perf_counter(); box = tuple(float(v) for v in bbox_fn(paths)); lap("bbox", t0)
+        sx, sy, ox, oy = fit_transform(box, o)
+        if max(abs(sx), abs(sy)) * tol_raw <= tol * (1.0 + 1e-12):
+            break
+        tol_raw = tol / max(abs(sx), abs(sy)) / 2.0           # only where the end points' box said nothing: take the measured scale, with room for the box to shrink
+    else:
+        raise RuntimeError("the tolerance could not be met: the scale keeps growing as the curves are cut finer")
+    t0 = time.perf_counter(); paths = fit_fn(paths, sx, sy, ox, oy); lap("fit", t0)
+    return paths, {"tol_raw": tol_raw, "scale": (sx, sy, ox, oy), "bbox": box, "flattens": k + 1}
+
+
+def build_stream_from_svg(text: Union[str, bytes, SegmentTable], opts: Optional[SvgOptions] = None, device=None, *, flatten_fn: Optional[Callable] = None,
+                          bbox_fn: Optional[Callable] = None, fit_fn: Optional[Callable] = None, fetch_fn: Optional[Callable] = None, steps_fn: Optional[Callable] = None,
+                          order_fn: Optional[Callable] = None, codes_fn: Optional[Callable] = None, pack_fn: Optional[Callable] = None, timings: Optional[dict] = None,
+                          want_paths: bool = False) -> Tuple[bytes, dict]:
+    """The stream of an SVG text (or of a parsed SegmentTable).  Device steps, each None = the GPU (there is no CPU path in the product):
+      flatten_fn(table, tol_raw) -> paths          orip_svg_flatten      (`paths` is whatever the other steps take: on the GPU a count, the points stay there)
+      bbox_fn(paths) -> (min x, min y, max x, max y)   orip_svg_bbox
+      fit_fn(paths, sx, sy, ox, oy) -> paths       orip_svg_fit
+      fetch_fn(paths, with_points) -> (off int64, pts float64 or None)   orip_svg_paths_fetch  (the points only with want_paths: info["fitted_paths"])
+      steps_fn(paths, map) -> (off, pts int32)     orip_gcode_to_steps without pointers
+      order_fn, codes_fn, pack_fn                  as in orip.gcode.build_stream_from_gcode
+    Returns (bytes, info)."""
+    import time
+    o = opts if opts is not None else SvgOptions()
+    tm = timings if timings is not None else {}
+    t0 = time.perf_counter()
+    table = text if isinstance(text, SegmentTable) else parse_svg(text)
+    tm["parse_svg"] = tm.get("parse_svg", 0.0) + (time.perf_counter() - t0)
+    go = gcode_options(o)
+    GC.apply_speed_scale(GC.GcodeOptions(speed_scale=go.speed_scale))
+    tolerance_mm(o)
+    info = {"segments": table.n_seg, "subpaths": table.n_sub, "canvas_height": table.canvas_height}
+    if table.n_seg == 0:
+        data, ginfo = GC.build_stream_from_gcode((np.zeros(1, np.int64), np.zeros((0, 2))), go)
+        if want_paths:
+            info["fitted_paths"] = (np.zeros(1, np.int64), np.zeros((0, 2)))
+        return data, dict(ginfo, **info)
+    if any(f is None for f in (flatten_fn, bbox_fn, fit_fn, fetch_fn, steps_fn, order_fn, codes_fn, pack_fn)):
+        if device is None:
+            from .stages import device as _default_device
+            device = _default_device()
+        R = _Resident(device)
+        flatten_fn = flatten_fn or R.flatten; bbox_fn = bbox_fn or R.bbox; fit_fn = fit_fn or R.fit; fetch_fn = fetch_fn or R.fetch; steps_fn = steps_fn or R.steps
+        order_fn = order_fn or device.gcode_order; codes_fn = codes_fn or device.stream_codes_resident; pack_fn = pack_fn or device.stream_pack
+    paths, fi = fit_paths(table, o, flatten_fn, bbox_fn, fit_fn, tm)
+    info.update(fi)
+    t0 = time.perf_counter()
+    off_mm, pts_mm = fetch_fn(paths, want_paths)
+    off_mm = np.asarray(off_mm, np.int64)
+    if want_paths:
+        info["fitted_paths"] = (off_mm, np.asarray(pts_mm, np.float64).reshape(-1, 2))
+    tm["fetch_paths"] = tm.get("fetch_paths", 0.0) + (time.perf_counter() - t0)
+    data, ginfo = GC.build_stream_from_gcode((off_mm, np.zeros((int(off_mm[-1]), 2))), go, steps_fn=lambda _off, _pts, m: steps_fn(paths, m), order_fn=order_fn,
+                                             codes_fn=codes_fn, pack_fn=pack_fn, timings=tm)
+    return data, dict(ginfo, **info)
+
+
+# ------------------------------------------------------------------ command lines
+def _add_fit_args(ap: argparse.ArgumentParser, d: SvgOptions):
+    ap.add_argument("--page-width-mm", type=float, default=d.page_width_mm, help="target page width in mm (default: 210, A4)")
+    ap.add_argument("--page-height-mm", type=float, default=d.page_height_mm, help="target page height in mm (default: 297, A4)")
+    ap.add_argument("--margin-mm", type=float, default=d.margin_mm, help="margin from the page border in mm (default: 10)")
+    ap.add_argument("--scale", type=float, default=None, help="uniform scale, SVG units -> mm; overrides the automatic fit")
+    ap.add_argument("--scale-x", type=float, default=None, help="X scale; overrides --scale for X")
+    ap.add_argument("--scale-y", type=float, default=None, help="Y scale; overrides --scale for Y")
+    ap.add_argument("--tolerance-mm", type=float, default=None, help="largest distance between a curve and its polyline on the page (default: half a step, 0.5 / steps per mm)")
+
+
+def build_gcode_argparser() -> argparse.ArgumentParser:
+    d = SvgOptions()
+    ap = argparse.ArgumentParser(description="Convert SVG to G-code fitted onto a page; curves are flattened and fitted on the GPU.")
+    ap.add_argument("input", help="input SVG file")
+    ap.add_argument("-o", "--output", default=d.output, help="output G-code file (default: from_svg.gcode)")
+    ap.add_argument("--movement-speed", type=float, default=d.movement_speed, help="accepted for the reference's command line; only matters to a laser, a pen plot has no feed words")
+    ap.add_argument("--cutting-speed", type=float, default=d.cutting_speed, help="accepted for the reference's command line; only matters to a laser")
+    ap.add_argument("--passes", type=int, default=d.passes, help="number of passes over the same paths (the paths are repeated)")
+    ap.add_argument("--pass-depth", type=float, default=d.pass_depth, help="accepted for the reference's command line; only matters to a laser")
+    ap.add_argument("--steps-per-mm", type=float, default=d.steps_per_mm, help="only sets the default tolerance here")
+    _add_fit_args(ap, d)
+    return ap
+
+
+def build_stream_argparser() -> argparse.ArgumentParser:
+    d = SvgOptions()
+    ap = argparse.ArgumentParser(description="Convert SVG directly to an OmniRevolve plotter stream and render its preview; one process, geometry on the GPU.")
+    ap.add_argument("input", help="input SVG file")
+    ap.add_argument("-o", "--output-stream", default=None, help="output stream file (default: <svg stem>_stream.bin)")
+    ap.add_argument("--gcode-output", default=None, help="G-code output file (default: <svg stem>.gcode)")
+    _add_fit_args(ap, d)
+    ap.add_argument("--steps-per-mm", type=float, default=d.steps_per_mm)
+    ap.add_argument("--target-width-steps", type=int, default=None, help="canvas width in steps (default: page width x steps per mm; needs the height too)")
+    ap.add_argument("--target-height-steps", type=int, default=None, help="canvas height in steps (default: page height x steps per mm; needs the width too)")
+    ap.add_argument("--invert-y", type=int, default=d.invert_y, help="1: flip Y inside the canvas")
+    ap.add_argument("--color-index", type=int, default=d.color_index, help="pen 0..7")
+    ap.add_argument("--speed-scale", type=float, default=d.speed_scale, help="> 1 faster (smaller dividers), < 1 slower")
+    ap.add_argument("--no-reorder", action="store_true", help="keep the paths in file order")
+    ap.add_argument("--no-preview", action="store_true", help="do not render <svg stem>_stream_preview.png")
+    ap.add_argument("--preview-render-width", type=int, default=d.preview_render_width)
+    ap.add_argument("--preview-render-height", type=int, default=d.preview_render_height)
+    return ap
+
+
+def options_from_args(a: argparse.Namespace) -> SvgOptions:
+    return SvgOptions(**{f.name: getattr(a, f.name) for f in fields(SvgOptions) if hasattr(a, f.name)})
+
+
+def _read(path: str) -> bytes:
+    p = Path(path)
+    if not p.is_file():
+        raise SystemExit(f"Input SVG not found: {p}")
+    return p.read_bytes()
+
+
+def main_gcode(argv: Optional[Sequence[str]] = None, **device_steps) -> None:
+    """svg2gcode.py: the fitted paths as G-code"""
+    a = build_gcode_argparser().parse_args(argv)
+    o = options_from_args(a)
+    table = parse_svg(_read(a.input))
+    info = {}
+    off, pts = np.zeros(1, np.int64), np.zeros((0, 2))
+    if table.n_seg:
+        R = device_steps
+        if not R:
+            from .stages import device as _default_device
+            r = _Resident(_default_device())
+            R = dict(flatten_fn=r.flatten, bbox_fn=r.bbox, fit_fn=r.fit, fetch_fn=r.fetch)
+        paths, info = fit_paths(table, o, R["flatten_fn"], R["bbox_fn"], R["fit_fn"])
+        off, pts = R["fetch_fn"](paths, True)
+    Path(a.output).write_text(gcode_text(off, pts, o.passes), encoding="utf-8")
+    print(f"G-code saved to {a.output}: {len(off) - 1} paths, {len(pts)} points")
+    if "scale" in info:
+        sx, sy, ox, oy = info["scale"]
+        print(f"  Raw bbox: x=[{info['bbox'][0]:.3f}, {info['bbox'][2]:.3f}], y=[{info['bbox'][1]:.3f}, {info['bbox'][3]:.3f}]")
+        print(f"  Final scale: sx={sx:.5f}, sy={sy:.5f}; offsets: {ox:.3f}, {oy:.3f} mm; tolerance {tolerance_mm(o)} mm = {info['tol_raw']:.6g} raw units")
+
+
+def main_stream(argv: Optional[Sequence[str]] = None, **device_steps) -> None:
+    """svg2stream.py: G-code file, stream file and (unless --no-preview) the preview PNG"""
+    a = build_stream_argparser().parse_args(argv)
+    o = options_from_args(a)
+    src = Path(a.input)
+    text = _read(a.input)
+    gcode_path = Path(a.gcode_output) if a.gcode_output else src.with_suffix(".gcode")
+    stream_path = Path(a.output_stream) if a.output_stream else src.with_name(src.stem + "_stream.bin")
+    device = device_steps.pop("device", None)
+    if device is None and not device_steps:
+        from .stages import device as _default_device
+        device = _default_device()
+    data, info = build_stream_from_svg(text, o, device, want_paths=True, **device_steps)
+    off, pts = info["fitted_paths"]
+    gcode_path.write_text(gcode_text(off, pts), encoding="utf-8")
+    stream_path.write_bytes(data)
+    print(f"[svg] {a.input}: {info['segments']} segments in {info['subpaths']} subpaths -> {len(pts)} points")
+    print(f"[svg] G-code saved: {gcode_path}")
+    print(f"stream saved: {stream_path} ({len(data)} bytes)")
+    if o.no_preview:
+        print("Preview disabled (--no-preview).")
+        return
+    from . import stream_preview as SP
+    W, H = info["target"]
+    rgb, _ = SP.preview(device, data, W, H, o.preview_render_width, o.preview_render_height, invert_y=True)
+    png = src.with_name(src.stem + "_stream_preview.png")
+    SP.save_png(rgb, str(png))
+    print(f"Image saved: {png}")

@@ -97,6 +97,33 @@ int orip_kmeans_fit_rgb(orip_ctx* ctx, const int64_t* sample_idx, int64_t n_idx,
  * counts_out ([K] pixels per label) may be NULL. */
 int orip_assign_palette(orip_ctx* ctx, const uint8_t* palette_rgb, int K, uint8_t* labels_out, int64_t* counts_out);
 
+/* ---- analyze_colors.py (marker recommendation; csrc/analyze.hip) ----
+ * The statistics of ColorAnalyzer.analyze (:58-105) from every pixel of the image set with orip_set_image; the reference takes them from an unseeded random
+ * 50 000-pixel sample (:70-72).  A uint8 image has at most 2^24 colours: one pass gives the exact colour table, every later step runs on it with the pixel
+ * counts as weights.  Palette matching and the recommendation stay on the host (orip/analyze.py).
+ * orip_colors_table: a pixel is kept when any of R, G, B is < white_threshold (:60); when ignore_white == 0 or fewer than min_kept pixels are kept, every
+ * pixel is kept (:63-67; *used_all = 1 when the count decided it, the caller prints the warning).  Leaves resident the distinct kept colours in ascending
+ * order of R<<16|G<<8|B with their pixel counts; returns their number and the kept pixels.  Valid until the next image or table.
+ * orip_colors_fetch: keys u32 [n_colors], counts int64 [n_colors] (either may be NULL), the kept pixels. */
+int orip_colors_table(orip_ctx* ctx, int ignore_white, int white_threshold, int64_t min_kept, int64_t* n_colors, int64_t* kept_pixels, int* used_all);
+int orip_colors_fetch(orip_ctx* ctx, uint32_t* keys_out, int64_t* counts_out, int64_t* kept_pixels);
+/* _build_hue_histogram (:128-167): kept pixels per bucket, in the reference's key order red, orange, yellow, green, cyan, blue, purple, pink, brown, gray,
+ * black.  HSV is OpenCV's 8-bit COLOR_RGB2HSV in integers (h 0..179), recalled and not pinned. */
+int orip_colors_hue(orip_ctx* ctx, int64_t* counts_out /* [11] */);
+/* Weighted k-means over the resident table, 2 <= K <= 32, 1 <= n_init <= 64; stands in for KMeans(n_clusters, random_state=42, n_init=10) (:76), whose random
+ * stream is not reproduced.  Fails when the table holds fewer than K colours.  Init i:
+ *   seeding  k-means++ with one candidate per step, exact integers: the weight of colour j is count_j for the first centre, count_j * mind2_j afterwards
+ *            (mind2: squared distance to the nearest chosen centre); t = splitmix64(seed ^ (i * 2^32 + step)) mod (sum of the weights); the first colour in
+ *            key order whose inclusive prefix sum exceeds t.
+ *   Lloyd    an iteration labels every colour with its nearest centre -- ((r-cr)^2 + (g-cg)^2) + (b-cb)^2 in IEEE double without fused multiply-add, ties
+ *            to the lowest index --, sums n, R, G, B of count * channel per cluster in int64 and sets each centre to sum / n (an empty cluster keeps its
+ *            centre).  It stops after the iteration in which no colour changed its label (the first one changes all), or after max_iter iterations.
+ * Results per init: centers [n_init,K,3] float64, n [n_init,K] and sums [n_init,K,3] int64 of the last iteration's labels, iterations run (may be NULL).
+ * The caller picks the best init from n and sums, exactly (orip/analyze.py: best_init). */
+int orip_colors_kmeans(orip_ctx* ctx, int K, int n_init, int max_iter, uint64_t seed, double* centers_out, int64_t* n_out, int64_t* sums_out, int32_t* iters_out);
+/* cv2.cvtColor(BGR2LAB) of stage 02 (02:35) for n R, G, B triples -> u8 [n,3] */
+int orip_lab_of_rgb(orip_ctx* ctx, const uint8_t* rgb /* [n,3] */, int64_t n, uint8_t* lab_out /* [n,3] */);
+
 /* assignment (02:53-55) + dark->light relabel (02:120-127) + per-cluster mask + 3x3 RECT open/close (02:144-154).
  * Leaves labels u8 [H,W] (dark->light index) and K masks resident; layer l of the context = cluster l. */
 int orip_extract_layers(orip_ctx* ctx, const float* centers /* [K,3] */, int K, int open_iters, int close_iters,

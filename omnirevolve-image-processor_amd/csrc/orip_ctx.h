@@ -279,6 +279,10 @@ struct orip_ctx {
     // svg2stream (svg.hip): scratch of the flattening and of the box, the resident paths (off int64[sv_n + 1], pts double2[sv_total]; raw units after
     // orip_svg_flatten, page mm after orip_svg_fit) until the next flatten; orip_gcode_to_steps reads them when it is called without pointers
     DBuf sv_tmp, sv_tmp2, sv_off, sv_pts; int64_t sv_n = 0, sv_total = 0; bool sv_ready = false, sv_box_ok = false; double sv_box[4] = {0, 0, 0, 0};
+    // analyze_colors (analyze.hip): the 2^24-bin table of the image's colours, the kept colours in key order (keys u32[an_D], counts int64[an_D]) resident from
+    // orip_colors_table until the next image or table; an_tmp = AnState + the compaction's block counts / offsets, an_km = the k-means inits, their segment
+    // sums, mind2 int32[n_init, an_D] and labels u8[n_init, an_D] (free between calls)
+    DBuf an_table, an_keys, an_counts, an_tmp, an_km; int64_t an_D = 0, an_kept = 0; bool an_ready = false;
     DBuf resize_src, resize_dst;                       // raster01.hip staging
     int memo_pre_K = 0, memo_pre_H = 0, memo_pre_W = 0; // orip_contours_reserve cleared this many memo planes of an H x W image
     // profiling

@@ -711,7 +711,7 @@ int orip_morph_open_close(orip_ctx* c, const u8* src, u8* dst, int K, int shape,
 extern "C" int orip_set_image(orip_ctx* c, const uint8_t* bgr, int H, int W) {
     orip_enter(c);
     ORIP_TRY(orip_contours_invalidate(c));
-    c->mask_bits = nullptr;
+    c->mask_bits = nullptr; c->an_ready = false;
     if (!bgr || H <= 0 || W <= 0) ORIP_FAIL(c, "bad image %dx%d", W, H);
     ORIP_TRY(orip_raster02_lab_tables(c));
     c->H = H; c->W = W;
@@ -732,6 +732,24 @@ extern "C" int orip_lab_of(orip_ctx* c, const int64_t* idx, int64_t n, uint8_t* 
     HIPC(c, hipGetLastError());
     HIPC(c, hipMemcpyAsync(lab_out, c->tmpB.p, (size_t)n * 3, hipMemcpyDeviceToHost, LN(c).stream));
     HIPC(c, hipStreamSynchronize(LN(c).stream));
+    return 0;
+}
+
+// analyze_colors.py: the same BGR2LAB for a short list of R, G, B triples (palette colours, cluster centres), so the palette logic measures in stage 02's Lab
+extern "C" int orip_lab_of_rgb(orip_ctx* c, const uint8_t* rgb, int64_t n, uint8_t* lab_out) {
+    orip_enter(c);
+    if (n < 0 || n > (1 << 24) || (n && (!rgb || !lab_out))) ORIP_FAIL(c, "bad colour list (n = %lld)", (long long)n);
+    if (n == 0) return 0;
+    ORIP_TRY(orip_raster02_lab_tables(c));
+    std::vector<u8> bgr((size_t)n * 3);
+    for (int64_t i = 0; i < n; i++) { bgr[3 * i] = rgb[3 * i + 2]; bgr[3 * i + 1] = rgb[3 * i + 1]; bgr[3 * i + 2] = rgb[3 * i]; }
+    HIPC(c, LN(c).tmpE.ensure((size_t)n * 6 + 32));
+    u8* d_in = LN(c).tmpE.as<u8>(); u8* d_out = d_in + (size_t)n * 3 + 16;
+    HIPC(c, hipMemcpyAsync(d_in, bgr.data(), (size_t)n * 3, hipMemcpyHostToDevice, LN(c).stream));
+    hipLaunchKernelGGL(k_lab_gather, dim3(std::min<int64_t>(2048, cdiv(n, 256))), dim3(256), 0, LN(c).stream, d_in, (const int64_t*)nullptr, n, d_out, c->lab_tabs.as<LabTabs>());
+    HIPC(c, hipGetLastError());
+    HIPC(c, hipMemcpyAsync(lab_out, d_out, (size_t)n * 3, hipMemcpyDeviceToHost, LN(c).stream));
+    HIPC(c, hipStreamSynchronize(LN(c).stream));       // (also keeps `bgr` alive until the upload is done)
     return 0;
 }
 

@@ -120,6 +120,41 @@ class Device:
         self._ck(self.L.orip_assign_palette(self.h, _p(pal), len(pal), _p(labels) if fetch else None, _p(counts)))
         return labels, counts
 
+    # ---- analyze_colors.py (include/orip.h; csrc/analyze.hip)
+    def colors_table(self, ignore_white: bool = True, white_threshold: int = 240, min_kept: int = 100, fetch: bool = True):
+        """the exact colour table of the kept pixels (:58-67), left resident: (keys u32 [D] = R<<16|G<<8|B ascending, counts int64 [D], kept pixels,
+        used_all: fewer than min_kept pixels passed the filter and every pixel was kept); keys and counts are None without fetch"""
+        d, kept, ua = C.c_int64(0), C.c_int64(0), C.c_int32(0)
+        self._ck(self.L.orip_colors_table(self.h, int(bool(ignore_white)), int(white_threshold), int(min_kept), C.byref(d), C.byref(kept), C.byref(ua)))
+        self._colors_D = int(d.value)
+        if not fetch:
+            return None, None, int(kept.value), bool(ua.value)
+        keys = np.zeros(max(d.value, 1), np.uint32); counts = np.zeros(max(d.value, 1), np.int64)
+        self._ck(self.L.orip_colors_fetch(self.h, _p(keys), _p(counts), C.byref(kept)))
+        return keys[:d.value], counts[:d.value], int(kept.value), bool(ua.value)
+
+    def colors_hue(self) -> np.ndarray:
+        """kept pixels per bucket of _build_hue_histogram (:128-167), int64 [11] in orip.analyze.HUE_KEYS order"""
+        out = np.zeros(11, np.int64)
+        self._ck(self.L.orip_colors_hue(self.h, _p(out)))
+        return out
+
+    def colors_kmeans(self, K: int, n_init: int = 10, max_iter: int = 300, seed: int = 42):
+        """weighted k-means over the resident table: (centers float64 [n_init,K,3], n int64 [n_init,K], sums int64 [n_init,K,3], iterations int32 [n_init])"""
+        K, n_init = int(K), int(n_init)
+        if K < 1 or n_init < 1:
+            raise ValueError(f"K={K}, n_init={n_init}")
+        cen = np.zeros((n_init, K, 3), np.float64); n = np.zeros((n_init, K), np.int64); sums = np.zeros((n_init, K, 3), np.int64); it = np.zeros(n_init, np.int32)
+        self._ck(self.L.orip_colors_kmeans(self.h, K, n_init, int(max_iter), int(seed) & 0xFFFFFFFFFFFFFFFF, _p(cen), _p(n), _p(sums), _p(it)))
+        return cen, n, sums, it
+
+    def lab_of_rgb(self, rgb) -> np.ndarray:
+        """stage 02's BGR2LAB of R, G, B triples [n,3] -> uint8 [n,3]"""
+        a = np.ascontiguousarray(np.asarray(rgb).reshape(-1, 3), np.uint8)
+        out = np.zeros((max(len(a), 1), 3), np.uint8)
+        self._ck(self.L.orip_lab_of_rgb(self.h, _p(a) if len(a) else None, len(a), _p(out) if len(a) else None))
+        return out[:len(a)]
+
     def extract_layers(self, centers: np.ndarray, open_iters=1, close_iters=1, want_counts=True):
         c = np.ascontiguousarray(centers, np.float32)
         K = len(c)

@@ -1,0 +1,202 @@
+"""analyze_colors on the GPU (csrc/analyze.hip) against the numpy double (tests/analyze_double.py): colour table, hue buckets, every k-means init and the
+chosen one, bit for bit and without tolerance; determinism of repeated calls; orip_lab_of_rgb against orip_lab_of; the tool on disk feeding
+process_colors.py --mode palette."""
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+import analyze_double as D
+from oracle import oracle as O
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+G = np.load(os.path.join(ROOT, "tests", "golden", "golden_analyze.npz"))
+CASES = [str(c) for c in G["cases"]]
+
+
+@pytest.fixture(scope="module")
+def dev():
+    from orip.device import Device
+    d = Device(0)
+    yield d
+    d.close()
+
+
+def _set_rgb(dev, rgb):
+    dev.set_image(np.ascontiguousarray(np.asarray(rgb, np.uint8)[:, :, ::-1]))
+
+
+def _k_colors(k, shape=(37, 53), seed=5):
+    """an image with exactly k distinct, non-white colours"""
+    rng = np.random.default_rng(seed)
+    pal = np.stack([np.arange(k) * 7 + 3, rng.integers(0, 200, k), rng.integers(0, 200, k)], 1).astype(np.uint8)
+    idx = rng.integers(0, k, shape); idx.flat[:k] = np.arange(k)
+    return pal[idx]
+
+
+def _one_color():
+    img = np.empty((1000, 1003, 3), np.uint8); img[:] = (12, 200, 77)      # a million pixels in one bin; 1003 * 1000 is not a multiple of 4
+    return img
+
+
+def _noise():
+    return np.random.default_rng(9).integers(0, 256, (301, 403, 3), dtype=np.uint8)
+
+
+def _synth4096():
+    from orip.synth import synth_image
+    return np.ascontiguousarray(synth_image(4096, 4096, 8)[:, :, ::-1])
+
+
+IMAGES = {
+    "fixture_a": lambda: G["img_a"], "fixture_b": lambda: G["img_b"], "fixture_c": lambda: G["img_c"],
+    "one_colour": _one_color, "all_white": lambda: np.full((64, 80, 3), 255, np.uint8), "one_pixel": lambda: np.array([[[1, 2, 3]]], np.uint8),
+    "one_white_pixel": lambda: np.array([[[250, 250, 250]]], np.uint8), "exactly_5_colours": lambda: _k_colors(5), "noise": _noise, "synth_4096": _synth4096,
+}
+
+
+# ---- 1. table, total, hue buckets
+@pytest.mark.parametrize("name", list(IMAGES))
+def test_table_and_hue_match_the_double(dev, name):
+    rgb = IMAGES[name]()
+    _set_rgb(dev, rgb)
+    for kw in ({}, {"ignore_white": False}, {"white_threshold": 128, "min_kept": 1000}):
+        keys, counts, kept, used_all = dev.colors_table(**kw)
+        wk, wc, wkept, wall = D.color_table(rgb, **kw)
+        assert keys.dtype == np.uint32 and counts.dtype == np.int64
+        assert (kept, used_all) == (wkept, wall), kw
+        assert np.array_equal(keys, wk) and np.array_equal(counts, wc), kw
+        assert int(counts.sum()) == kept
+        assert dev.colors_hue().tolist() == D.hue_counts(wk, wc).tolist(), kw
+
+
+def test_hand_checked_hue_list_on_the_device(dev):
+    from analyze_double import HUE_LIST
+    from orip.analyze import HUE_KEYS
+    rgb = np.array([c[0] for c in HUE_LIST], np.uint8)[None]
+    _set_rgb(dev, rgb)
+    dev.colors_table(ignore_white=False)
+    want = {k: 0 for k in HUE_KEYS}
+    for _, _, bucket in HUE_LIST:
+        want[bucket] += 1
+    assert dev.colors_hue().tolist() == [want[k] for k in HUE_KEYS]
+
+
+def test_fewer_colours_than_clusters_is_an_error_not_a_hang(dev):
+    from orip.device import OripError
+    _set_rgb(dev, _k_colors(4))
+    assert len(dev.colors_table()[0]) == 4
+    with pytest.raises(OripError, match="fewer than K=5"):
+        dev.colors_kmeans(5)
+    cen, n, sums, it = dev.colors_kmeans(4, n_init=3)                       # exactly K colours: every colour its own cluster
+    keys, counts, _, _ = dev.colors_table()
+    for i in range(3):
+        assert sorted(n[i].tolist()) == sorted(counts.tolist()) and set(map(tuple, cen[i].tolist())) == {(float(k >> 16), float((k >> 8) & 255), float(k & 255)) for k in keys.tolist()}
+    with pytest.raises(OripError, match="K=1 out of range"):
+        dev.colors_kmeans(1)
+    with pytest.raises(OripError, match="K=33 out of range"):
+        dev.colors_kmeans(33)
+
+
+def test_a_new_image_invalidates_the_table(dev):
+    from orip.device import OripError
+    _set_rgb(dev, _k_colors(6)); dev.colors_table()
+    _set_rgb(dev, _k_colors(7))
+    for call in (dev.colors_hue, lambda: dev.colors_kmeans(2)):
+        with pytest.raises(OripError, match="no colour table"):
+            call()
+
+
+# ---- 2. every init and the chosen one
+def _check_kmeans(dev, rgb, K, **kw):
+    from orip.analyze import best_init
+    _set_rgb(dev, rgb)
+    keys, counts, _, _ = dev.colors_table()
+    cen, n, sums, it = dev.colors_kmeans(K, **kw)
+    wcen, wn, wsums, wit = D.kmeans(keys, counts, K, **kw)
+    assert np.array_equal(n, wn) and np.array_equal(sums, wsums)
+    assert cen.dtype == np.float64 and cen.tobytes() == wcen.tobytes()
+    assert it.tolist() == wit.tolist()
+    assert best_init(n, sums) == D.best_init(keys, counts, wn, wsums)
+    return cen, n, sums, it
+
+
+@pytest.mark.parametrize("case", CASES)
+def test_kmeans_every_init_matches_the_double(dev, case):
+    nm, K = case.split(":")
+    _check_kmeans(dev, G[f"img_{nm}"], int(K))
+
+
+@pytest.mark.parametrize("K,seed", [(2, 0), (7, 1), (32, 2 ** 63 + 5)])
+def test_kmeans_other_seeds_and_cluster_counts(dev, K, seed):
+    _check_kmeans(dev, _noise(), K, n_init=3, max_iter=12, seed=seed)
+
+
+def test_kmeans_exactly_K_colours(dev):
+    _check_kmeans(dev, _k_colors(5), 5)
+
+
+def test_kmeans_4096(dev):
+    _check_kmeans(dev, _synth4096(), 8, n_init=2, max_iter=20)
+
+
+# ---- 3. determinism: the reference clusters an unseeded random sample; two calls here give identical bytes
+def test_two_calls_give_identical_bytes(dev):
+    _set_rgb(dev, G["img_a"])
+    runs = []
+    for _ in range(2):
+        keys, counts, kept, _ = dev.colors_table()
+        cen, n, sums, it = dev.colors_kmeans(6)
+        runs.append(b"".join(a.tobytes() for a in (keys, counts, dev.colors_hue(), cen, n, sums, it)) + str(kept).encode())
+    assert runs[0] == runs[1]
+
+
+# ---- 4. Lab of a colour list = Lab of an image of the same colours
+def test_lab_of_rgb_equals_lab_of(dev):
+    rgb = np.random.default_rng(3).integers(0, 256, (17, 29, 3), dtype=np.uint8)
+    rgb[0, 0] = 0; rgb[0, 1] = 255
+    _set_rgb(dev, rgb)
+    want = dev.lab_of().reshape(-1, 3)
+    assert np.array_equal(dev.lab_of_rgb(rgb.reshape(-1, 3)), want)
+    assert np.array_equal(want, O.bgr2lab(np.ascontiguousarray(rgb.reshape(-1, 3)[:, ::-1])))
+    assert dev.lab_of_rgb(np.zeros((0, 3), np.uint8)).shape == (0, 3)
+
+
+# ---- 5. the tool on disk, then process_colors.py --mode palette on its file
+def test_tool_feeds_process_colors(tmp_path):
+    from PIL import Image
+    from orip import analyze as AN
+    from analyze_double import DoubleDevice, lab_cpu
+    rgb = G["img_b"]
+    src = tmp_path / "blobs.png"; Image.fromarray(rgb).save(src)
+    stages = os.path.join(ROOT, "omnirevolve-image-processor_amd", "stages")
+    env = dict(os.environ, PYTHONPATH=os.path.join(ROOT, "omnirevolve-image-processor_amd") + os.pathsep + os.environ.get("PYTHONPATH", ""), MPLCONFIGDIR=str(tmp_path))
+    r = subprocess.run([sys.executable, os.path.join(stages, "analyze_colors.py"), str(src), "-n", "3", "-c", "4", "-o", str(tmp_path / "panels.png")],
+                       capture_output=True, text=True, timeout=600, env=env, cwd=tmp_path)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    for section in ("Using default marker palette", "Clustering 19200 pixels into 4 groups...", "Analyzed pixels: 19,200", "Dominant colors:", "RECOMMENDED MARKERS (3):",
+                    "Recommendations saved to blobs_colors.json", "Visualization saved to"):
+        assert section in r.stdout, section
+    assert (tmp_path / "panels.png").stat().st_size > 1000
+    data = json.loads((tmp_path / "blobs_colors.json").read_text())
+    # the same recommendation as the host logic over the numpy double
+    a = AN.ColorAnalyzer(AN.Palette(None, lab_cpu)); a.analyze(DoubleDevice(rgb), n_clusters=4)
+    want = a.recommend_colors(3)
+    assert [(it["name"], it["coverage"], it["position"]) for it in data["recommended_colors"]] == [(nm, sc, i) for i, (nm, sc) in enumerate(want, 1)]
+    names = [it["name"] for it in data["recommended_colors"]]
+    assert len(names) == 3
+    out = tmp_path / "layers"
+    r = subprocess.run([sys.executable, os.path.join(stages, "process_colors.py"), str(src), "-o", str(out), "--mode", "palette", "--palette", str(tmp_path / "blobs_colors.json"), "-n", "3"],
+                       capture_output=True, text=True, timeout=600, env=env, cwd=tmp_path)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    dump = json.loads((out / "palette.json").read_text())
+    assert [c["name"] for c in dump["colors"]] == names and [c["rgb"] for c in dump["colors"]] == [list(AN.DEFAULT_MARKERS[n]) for n in names]
+    labels = np.load(out / "labels.npy")
+    pal = np.array([AN.DEFAULT_MARKERS[n] for n in names], np.uint8)
+    assert np.array_equal(labels, O.assign_labels_rgb(rgb, pal)) and np.unique(labels).tolist() == [0, 1, 2]
+    assert sorted(p.name for p in out.glob("layer_*.png")) == sorted(f"layer_{i + 1}_{n}.png" for i, n in enumerate(names))

@@ -251,3 +251,18 @@ if __name__ == "__main__":
         make_e2e("a", 96, 96, 4, {"pixels_per_mm": 4}, seed=11)             # canvas 840x1188, scale ~7.9
     if "b" in which:
         make_e2e("b", 120, 88, 4, {"pixels_per_mm": 6, "edge_kernel_size": 5}, seed=12)   # canvas 1260x1782
+    # c / d: the vector parameters away from their defaults (a and b change none of them).  Not in the default list:
+    # `make_golden.py c d` records them.
+    if "c" in which:      # thin pen, hash stride below the collision radius, small landscape sheet, asymmetric margins; canvas 600x400
+        make_e2e("c", 96, 96, 4, {"pixels_per_mm": 4, "pen_width_px": 24, "pen_radius_px": 12,
+                                  "collision_radius_intra_px": 9.0, "hash_stride_px": 6.0,
+                                  "dedup_sample_step": 3, "ignore_tail_points_intra": 40, "max_join_jump_px": 30.0,
+                                  "tap_max_dim": 12, "tap_max_perimeter": 70.0,
+                                  "margin_left_mm": 5.0, "margin_right_mm": 20.0, "margin_top_mm": 0.0, "margin_bottom_mm": 33.0,
+                                  "target_width_mm": 150, "target_height_mm": 100}, seed=119)
+    if "d" in which:      # widest pen stage 10 accepts, odd brush (51 -> stamp radius 25), stride above the radius; canvas 1050x1485
+        make_e2e("d", 110, 80, 4, {"pixels_per_mm": 5, "pen_width_px": 62, "pen_radius_px": 20,
+                                   "collision_radius_intra_px": 25.5, "hash_stride_px": 40.0,
+                                   "dedup_sample_step": 11, "ignore_tail_points_intra": 300, "max_join_jump_px": 120.0,
+                                   "tap_max_dim": 40, "tap_max_perimeter": 300.0,
+                                   "margin_left_mm": 0.0, "margin_right_mm": 0.0}, seed=120)

@@ -135,7 +135,7 @@ def test_stage04_golden_pure(dev, t):
     assert same_polys(dev.get_polys(SLOT_CONTOURS, 0), want)                        # reference's own trace output
 
 
-@pytest.mark.parametrize("tag", ["a", "b"])
+@pytest.mark.parametrize("tag", ["a", "b", "c", "d"])
 def test_stage04_golden_e2e(dev, tag):
     import json
     from orip.lib import SLOT_CONTOURS

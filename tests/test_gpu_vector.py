@@ -43,7 +43,7 @@ def _rand_polys(rng, n, lo=2, hi=40, span=8000, step=15, closed_p=0.3):
     return out
 
 
-@pytest.fixture(scope="module", params=["a", "b"])
+@pytest.fixture(scope="module", params=["a", "b", "c", "d"])
 def G(request):
     return load(f"golden_e2e_{request.param}.npz")
 
@@ -256,7 +256,7 @@ def test_stage08_cumulative_lengths_long_polylines(dev):
     assert same_polys(got_l, want_l), (len(got_l), len(want_l))
 
 
-@pytest.mark.parametrize("tag", ["a", "b"])
+@pytest.mark.parametrize("tag", ["a", "b", "c", "d"])
 def test_full_chain_image_to_ops_matches_reference(dev, tag):
     """Resident path 02 -> 12 from the image: final ops identical to the reference chain's ops.pkl."""
     from orip import stages as S

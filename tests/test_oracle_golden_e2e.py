@@ -19,7 +19,7 @@ def _taps(a):
     return [(int(x), int(y)) for x, y in a]
 
 
-@pytest.fixture(scope="module", params=["a", "b"])
+@pytest.fixture(scope="module", params=["a", "b", "c", "d"])
 def G(request):
     return load(f"golden_e2e_{request.param}.npz")
 

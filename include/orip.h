@@ -271,6 +271,27 @@ int orip_svg_flatten(orip_ctx* ctx, const int32_t* kind /* [n_seg] */, const dou
 int orip_svg_paths_fetch(orip_ctx* ctx, int64_t* off_out /* [n_sub+1] */, double* pts_out /* [total,2] or NULL */);
 int orip_svg_bbox(orip_ctx* ctx, double* box /* [4] */);
 int orip_svg_fit(orip_ctx* ctx, double sx, double sy, double ox, double oy);
+/* Hatch fill of the fitted paths (csrc/hatch.hip): hatch_fill of stream_generators/plotter_demo/omnirevolve_plotter_demo.py (:220-260), every fill group
+ * at once.  fill_group[p] is -1 or the group of subpath p, 0 <= group < n_sub (n_sub must be the resident count); the groups are hatched in ascending
+ * order of their number, each over all its subpaths, every subpath closed by the edge from its last point to its first (poly[(i + 1) % n], :242).
+ *   Quantise: q = rint(v * steps_per_mm) per coordinate, one rounded multiply, ties to even (mm_to_steps of gcode2stream.py without offset, inversion, clamp).
+ *   Lines (:230-236): y0 = floor_div(min_y + spacing / 2, spacing) * spacing over the group's points, then y0, y0 + spacing, ... <= max_y; line k counts from 0.
+ *   Crossings (:243-247): an edge with y1 == y2 is skipped, otherwise ordered to y1 < y2; it crosses y iff y1 < y <= y2, at x = x1 + t * (x2 - x1) with
+ *   t = (y - y1) / (y2 - y1), each operation in IEEE double rounded on its own.
+ *   Segments (:248-258): the crossings of a line ascending, paired (0, 1), (2, 3), ..., an odd last one dropped; sx = trunc(x_a + inset),
+ *   ex = trunc(x_b - inset) toward zero; dropped when ex <= sx.  Pairs leave in ascending x on every line; with ORIP_HATCH_SERPENTINE a segment of an odd
+ *   line k runs from ex to sx (:255-260; empty lines count).
+ *   ORIP_HATCH_VERTICAL is the same with x and y exchanged.  With both directions all horizontal segments come first.
+ * Each segment is appended to the resident paths as a 2-point path, a coordinate k as k / steps_per_mm rounded to 4 decimals as orip_svg_fit rounds; with
+ * steps_per_mm <= 5000 (required) rint of that times steps_per_mm is k again.  stats: fill groups, lines, crossings, segments (the last three summed over
+ * the directions).  Valid once after orip_svg_fit per flatten.  Errors (no fault, the resident paths as they were): the wrong state, n_sub not the resident
+ * count, a group out of range, spacing < 1, inset < 0, no direction, steps_per_mm not in (0, 5000], a quantised value of 2^30 or beyond, more than 2^26
+ * lines or 2^30 crossings in one direction, paths or points beyond what orip_gcode_to_steps takes. */
+#define ORIP_HATCH_SERPENTINE 1
+#define ORIP_HATCH_HORIZONTAL 2
+#define ORIP_HATCH_VERTICAL 4
+int orip_svg_hatch(orip_ctx* ctx, const int32_t* fill_group /* [n_sub] */, int64_t n_sub, double steps_per_mm, int32_t spacing, int32_t inset, int32_t flags,
+                   int64_t* stats /* [4]: groups, lines, crossings, segments */);
 
 /* ---- multi-GPU exchange (no counterpart in the reference, which is a single process) ----
  * One process per GPU; rank r owns the cluster layers {l : l % world == r} for stages 03-08 and 12.  Stage 10 is replicated and needs

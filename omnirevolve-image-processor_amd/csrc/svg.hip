@@ -19,6 +19,7 @@
 //    10^4 in one correctly rounded division.  p = v' * 1e4 rounded, e = fma(v', 1e4, -p) is the exact rest; k = rint(p), and only when p - k is exactly
 //    +-0.5 does the sign of e decide (v' = 5e-05: p is exactly 0.5, e > 0, so k = 1).  When p is no tie, e is too small to cross one.
 #include "vec_common.h"
+#include "sv_round.h"
 
 namespace {
 constexpr int SV_MAX_PIECES = 1 << 16;
@@ -26,9 +27,6 @@ constexpr int64_t SV_MAX_POINTS = (1ll << 30) - 1;        // what orip_gcode_to_
 constexpr double SV_FIT_LIMIT = 1e9;
 constexpr int SV_BOX_BLOCKS = 256;
 
-__device__ __forceinline__ double sv_mul(double a, double b) { return __dmul_rn(a, b); }
-__device__ __forceinline__ double sv_add(double a, double b) { return __dadd_rn(a, b); }
-__device__ __forceinline__ double sv_sub(double a, double b) { return __dsub_rn(a, b); }
 __device__ __forceinline__ double sv_lerp(double a, double b, double t) { return sv_add(a, sv_mul(sv_sub(b, a), t)); }
 // |a - 2 b + c|^2 as (a - b) + (c - b), squared and summed
 __device__ __forceinline__ double sv_dd2(double2 a, double2 b, double2 c) {
@@ -157,14 +155,6 @@ __host__ __device__ __forceinline__ double sv_fit_value(double v, double s, doub
     volatile double m = v * s; return m + o;
 #endif
 }
-__device__ __forceinline__ double sv_round4(double v) {
-    const double p = sv_mul(v, 1e4), e = __fma_rn(v, 1e4, -p);
-    double k = rint(p);
-    const double r = sv_sub(p, k);                                           // exact
-    if (r == 0.5 && e > 0.0) k = sv_add(k, 1.0);
-    else if (r == -0.5 && e < 0.0) k = sv_sub(k, 1.0);
-    return __ddiv_rn(k, 1e4);
-}
 __global__ __launch_bounds__(256) void k_svg_fit(double2* __restrict__ pts, int64_t n, double sx, double sy, double ox, double oy) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
@@ -193,7 +183,7 @@ extern "C" int orip_svg_flatten(orip_ctx* c, const int32_t* kind, const double* 
                                 const double* mats, int64_t n_mat, double tol, int64_t* total_out) {
     orip_enter(c);
     ORIP_LANE(c, ORIP_LANE_CROSS);
-    c->sv_ready = false; c->sv_box_ok = false; c->sv_n = 0; c->sv_total = 0;
+    c->sv_ready = false; c->sv_box_ok = false; c->sv_n = 0; c->sv_total = 0; c->sv_fitted = false; c->sv_hatched = false;
     if (!total_out || n_seg < 0 || n_sub < 0 || n_mat < 0 || (n_seg > 0 && (!kind || !ctrl || !mat || !mats || !sub_off))) ORIP_FAIL(c, "bad arguments");
     *total_out = 0;
     if (!(tol > 0.0) || !std::isfinite(tol)) ORIP_FAIL(c, "the tolerance must be a positive finite number");
@@ -265,7 +255,7 @@ extern "C" int orip_svg_fit(orip_ctx* c, double sx, double sy, double ox, double
     orip_enter(c);
     ORIP_LANE(c, ORIP_LANE_CROSS);
     if (!c->sv_ready) ORIP_FAIL(c, "no paths: orip_svg_flatten has not succeeded since the last failure");
-    if (c->sv_total == 0) return 0;
+    if (c->sv_total == 0) { c->sv_fitted = true; return 0; }
     // v * s + o is monotonic in v, so the box's corners bound every fitted value: a drawing outside the limit is refused before a kernel touches it
     double box[4];
     ORIP_TRY(sv_box(c, box));
@@ -276,6 +266,6 @@ extern "C" int orip_svg_fit(orip_ctx* c, double sx, double sy, double ox, double
       hipLaunchKernelGGL(k_svg_fit, dim3(cdiv(c->sv_total, 256)), dim3(256), 0, s, c->sv_pts.as<double2>(), c->sv_total, sx, sy, ox, oy); }
     HIPC(c, hipGetLastError());
     HIPC(c, hipStreamSynchronize(s));
-    c->sv_box_ok = false;
+    c->sv_box_ok = false; c->sv_fitted = true;
     return 0;
 }

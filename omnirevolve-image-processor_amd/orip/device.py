@@ -383,6 +383,15 @@ class Device:
         """v * s + o per axis, rounded to four decimals as float(f"{v:.4f}") rounds, in place on the resident paths"""
         self._ck(self.L.orip_svg_fit(self.h, float(sx), float(sy), float(ox), float(oy)))
 
+    def svg_hatch(self, fill_group, steps_per_mm: float, spacing: int, inset: int, flags: int) -> dict:
+        """hatch lines of the fitted resident paths, appended to them as 2-point paths (include/orip.h: orip_svg_hatch; flags: orip.lib.HATCH_*);
+        fill_group int32 per resident subpath, -1 or its group -> {"groups", "lines", "crossings", "segments"}"""
+        g = np.ascontiguousarray(fill_group, np.int32).reshape(-1)
+        st = np.zeros(4, np.int64)
+        self._ck(self.L.orip_svg_hatch(self.h, _p(g) if len(g) else None, len(g), float(steps_per_mm), int(spacing), int(inset), int(flags), _p(st)))
+        self._svg_n = len(g) + int(st[3])
+        return {k: int(v) for k, v in zip(("groups", "lines", "crossings", "segments"), st)}
+
     def gcode_order(self, ends: np.ndarray | None, n: int | None = None) -> np.ndarray:
         """order of the paths (first x, first y, last x, last y) int32 [n, 4]; ends None: the n resident step polylines of gcode_to_steps"""
         if ends is not None:

@@ -19,6 +19,13 @@ curve is cut: every curve's end points are in the final point set, so the final 
 is at most the scale of that smaller box.  build_stream_from_svg checks the applied scale against the bound afterwards and flattens again only when the
 end points' box says nothing (all of them on one point).
 
+Hatch fill (off unless --hatch-spacing-mm is given).  The reference fills shapes in its demo sheet generator (stream_generators/plotter_demo/
+omnirevolve_plotter_demo.py, hatch_fill :220-260): scanlines over a group of polygons in integer steps, crossings paired even-odd, both ends inset, every
+other line reversed.  Here a fill group is one SVG element (all subpaths of a path, so holes work), chosen by its fill (parse_svg), and orip_svg_hatch
+runs that function's rules on the fitted paths after they are quantised to steps; the hatch lines join the fitted paths as 2-point paths in mm, so the
+G-code text, the order and the stream treat them like any other path.  Every fill is even-odd, whatever fill-rule says, because the reference's pairing is
+(stated deviation), and the SVG default of a black fill is not taken as a request to hatch: only a fill that is written down is.
+
 The device steps are injectable, as in orip/gcode.py, so that this host logic can be tested without a GPU; the product has no CPU path."""
 from __future__ import annotations
 
@@ -33,6 +40,7 @@ from typing import Callable, List, Optional, Sequence, Tuple, Union
 import numpy as np
 
 from . import gcode as GC
+from .lib import HATCH_SERPENTINE, HATCH_HORIZONTAL, HATCH_VERTICAL
 
 LINE, QUAD, CUBIC = 1, 2, 3
 KAPPA = 4.0 / 3.0 * math.tan(math.pi / 8.0)            # handle length of a 90 degree piece, per unit radius
@@ -46,7 +54,8 @@ GROUPS = {"svg", "g", "a", "switch"}
 class SegmentTable:
     """Flat arrays.  Segment s: kind[s] (LINE / QUAD / CUBIC), ctrl[s] its control points in user units (the unused ones repeat the last), mat[s] the index of
     its matrix in mats (a, b, c, d, e, f: x' = a x + c y + e, y' = b x + d y + f).  Subpath p = segments sub_off[p] .. sub_off[p + 1] - 1, one pen-down path;
-    closed[p]: it ended with Z (the closing line is one of its segments)."""
+    closed[p]: it ended with Z (the closing line is one of its segments).  fill_group[p]: -1, or the ordinal of the element subpath p belongs to when that
+    element is to be hatched (parse_svg; None counts as all -1)."""
     kind: np.ndarray
     ctrl: np.ndarray
     mat: np.ndarray
@@ -54,6 +63,7 @@ class SegmentTable:
     closed: np.ndarray
     mats: np.ndarray
     canvas_height: float = 100.0
+    fill_group: Optional[np.ndarray] = None
 
     @property
     def n_seg(self) -> int: return len(self.kind)
@@ -77,6 +87,7 @@ class _Builder:
     def __init__(self):
         self.kind: List[int] = []; self.ctrl: List[Tuple[float, ...]] = []; self.mat: List[int] = []
         self.sub_off = [0]; self.closed: List[int] = []
+        self.fill_group: List[int] = []; self.elements = 0
         self.mats: List[Tuple[float, ...]] = [IDENTITY]
         self.m = 0
         self.cur = self.start = (0.0, 0.0)
@@ -149,7 +160,8 @@ class _Builder:
     def table(self, canvas_height) -> SegmentTable:
         self.end()
         return SegmentTable(np.asarray(self.kind, np.int32), np.asarray(self.ctrl, np.float64).reshape(-1, 4, 2), np.asarray(self.mat, np.int32),
-                            np.asarray(self.sub_off, np.int64), np.asarray(self.closed, np.uint8), np.asarray(self.mats, np.float64).reshape(-1, 6), float(canvas_height))
+                            np.asarray(self.sub_off, np.int64), np.asarray(self.closed, np.uint8), np.asarray(self.mats, np.float64).reshape(-1, 6), float(canvas_height),
+                            np.asarray(self.fill_group, np.int32))
 
 
 # ------------------------------------------------------------------ path data
@@ -348,26 +360,47 @@ def _draw_element(b: _Builder, el, tag: str):
         b.close()
 
 
-def _walk(b: _Builder, el, m: int):
+_FILL = re.compile(r"(?:^|;)\s*fill\s*:\s*([^;]+)")
+HATCH_FILLS = ("stated", "all")
+
+
+def _fill_of(el, inherited: Optional[str]) -> Optional[str]:
+    """the element's fill as written: the style property, else the presentation attribute, else what the enclosing groups say; None: nobody says"""
+    m = _FILL.search(el.get("style") or "")
+    own = m.group(1) if m else el.get("fill")
+    return inherited if own is None else own.strip().lower()
+
+
+def _walk(b: _Builder, el, m: int, fill: Optional[str] = None, fill_all: bool = False):
     tag = el.tag.rsplit("}", 1)[-1] if isinstance(el.tag, str) else ""
     if not tag or tag in SKIPPED or (el.get("display") or "").strip() == "none":
         return
+    fill = _fill_of(el, fill)
     if el.get("transform"):
         b.mats.append(_mul(b.mats[m], parse_transform(el.get("transform"))))
         m = len(b.mats) - 1
     if tag in GROUPS:
         for ch in el:
-            _walk(b, ch, m)
+            _walk(b, ch, m, fill, fill_all)
     else:
         b.m = m
         _draw_element(b, el, tag)
         b.end()
+        new = len(b.closed) - len(b.fill_group)
+        if new:                                             # an element that drew something: the next ordinal, whether it is filled or not
+            wanted = tag != "line" and (fill_all or (fill is not None and fill not in ("none", "transparent")))
+            b.fill_group.extend([b.elements if wanted else -1] * new)
+            b.elements += 1
 
 
-def parse_svg(text: Union[str, bytes]) -> SegmentTable:
+def parse_svg(text: Union[str, bytes], hatch_fill: str = "stated") -> SegmentTable:
+    """hatch_fill decides table.fill_group: "stated" marks an element whose fill (style property or presentation attribute, its own or inherited from a
+    group) is written down and is not none / transparent; "all" marks every element that draws.  A line is never marked."""
+    if hatch_fill not in HATCH_FILLS:
+        raise ValueError("--hatch-fill must be one of " + ", ".join(HATCH_FILLS))
     root = ET.fromstring(text)
     b = _Builder()
-    _walk(b, root, 0)
+    _walk(b, root, 0, None, hatch_fill == "all")
     return b.table(canvas_height(root))
 
 
@@ -399,6 +432,38 @@ class SvgOptions:
     preview_render_width: int = 1200
     preview_render_height: int = 900
     tolerance_mm: Optional[float] = None
+    hatch_spacing_mm: Optional[float] = None            # None: no hatching
+    hatch_inset_mm: float = 27.0 / 40.0                 # the reference's 27 steps at 40 steps per mm
+    hatch_direction: str = "horizontal"
+    no_serpentine: bool = False
+    hatch_fill: str = "stated"
+
+
+HATCH_DIRECTIONS = {"horizontal": HATCH_HORIZONTAL, "vertical": HATCH_VERTICAL, "cross": HATCH_HORIZONTAL | HATCH_VERTICAL}
+HATCH_MAX_STEPS_PER_MM = 5000.0
+
+
+def hatch_params(o: SvgOptions) -> Optional[dict]:
+    """None without --hatch-spacing-mm, else what orip_svg_hatch takes: spacing and inset in steps, the flags, steps per mm.  Above 5000 steps per mm the
+    four decimals of the G-code no longer name every step, so the written file and the stream could disagree: refused."""
+    if o.hatch_spacing_mm is None:
+        return None
+    spm = float(o.steps_per_mm)
+    if not (0.0 < spm <= HATCH_MAX_STEPS_PER_MM):
+        raise ValueError(f"hatching needs --steps-per-mm in (0, {HATCH_MAX_STEPS_PER_MM:g}]: beyond it four decimals of a mm do not name every step")
+    if o.hatch_direction not in HATCH_DIRECTIONS:
+        raise ValueError("--hatch-direction must be one of " + ", ".join(HATCH_DIRECTIONS))
+    if o.hatch_fill not in HATCH_FILLS:
+        raise ValueError("--hatch-fill must be one of " + ", ".join(HATCH_FILLS))
+    s, i = float(o.hatch_spacing_mm) * spm, float(o.hatch_inset_mm) * spm
+    if not (math.isfinite(s) and math.isfinite(i)) or abs(s) >= 2 ** 31 - 1 or abs(i) >= 2 ** 31 - 1:
+        raise ValueError("--hatch-spacing-mm and --hatch-inset-mm must be finite and below 2^31 steps")
+    spacing, inset = int(round(s)), int(round(i))
+    if spacing < 1:
+        raise ValueError(f"--hatch-spacing-mm {o.hatch_spacing_mm} is {spacing} steps at {spm:g} steps per mm: at least 1")
+    if inset < 0:
+        raise ValueError("--hatch-inset-mm must not be negative")
+    return {"spacing": spacing, "inset": inset, "flags": HATCH_DIRECTIONS[o.hatch_direction] | (0 if o.no_serpentine else HATCH_SERPENTINE), "steps_per_mm": spm}
 
 
 def tolerance_mm(o: SvgOptions) -> float:
@@ -495,6 +560,10 @@ class _Resident:
     def fetch(self, paths, with_points=True): return self.dev.svg_paths(paths["n"], with_points)
     def steps(self, paths, m): return self.dev.gcode_to_steps_resident(paths["n"], m)
 
+    def hatch(self, paths, fill_group, prm):
+        st = self.dev.svg_hatch(fill_group, prm["steps_per_mm"], prm["spacing"], prm["inset"], prm["flags"])
+        return {"n": paths["n"] + st["segments"], "total": paths["total"] + 2 * st["segments"]}, st
+
 
 MAX_REFLATTEN = 8
 
@@ -521,14 +590,29 @@ def fit_paths(table: SegmentTable, o: SvgOptions, flatten_fn, bbox_fn, fit_fn, t
     return paths, {"tol_raw": tol_raw, "scale": (sx, sy, ox, oy), "bbox": box, "flattens": k + 1}
 
 
+def hatch_paths(table: SegmentTable, prm: dict, paths, hatch_fn, info: dict, tm: Optional[dict] = None):
+    """the fitted paths with the hatch lines of the table's fill groups behind them; info["hatch"] = the counts"""
+    import time
+    t0 = time.perf_counter()
+    fg = np.full(table.n_sub, -1, np.int32) if table.fill_group is None else np.asarray(table.fill_group, np.int32).reshape(-1)
+    if len(fg) != table.n_sub:
+        raise ValueError(f"fill_group has {len(fg)} entries for {table.n_sub} subpaths")
+    paths, st = hatch_fn(paths, fg, prm)
+    info["hatch"] = {k: int(st[k]) for k in ("groups", "lines", "crossings", "segments")}
+    if tm is not None:
+        tm["hatch"] = tm.get("hatch", 0.0) + (time.perf_counter() - t0)
+    return paths
+
+
 def build_stream_from_svg(text: Union[str, bytes, SegmentTable], opts: Optional[SvgOptions] = None, device=None, *, flatten_fn: Optional[Callable] = None,
-                          bbox_fn: Optional[Callable] = None, fit_fn: Optional[Callable] = None, fetch_fn: Optional[Callable] = None, steps_fn: Optional[Callable] = None,
-                          order_fn: Optional[Callable] = None, codes_fn: Optional[Callable] = None, pack_fn: Optional[Callable] = None, timings: Optional[dict] = None,
+                          bbox_fn: Optional[Callable] = None, fit_fn: Optional[Callable] = None, hatch_fn: Optional[Callable] = None, fetch_fn: Optional[Callable] = None,
+                          steps_fn: Optional[Callable] = None, order_fn: Optional[Callable] = None, codes_fn: Optional[Callable] = None, pack_fn: Optional[Callable] = None, timings: Optional[dict] = None,
                           want_paths: bool = False) -> Tuple[bytes, dict]:
     """The stream of an SVG text (or of a parsed SegmentTable).  Device steps, each None = the GPU (there is no CPU path in the product):
       flatten_fn(table, tol_raw) -> paths          orip_svg_flatten      (`paths` is whatever the other steps take: on the GPU a count, the points stay there)
       bbox_fn(paths) -> (min x, min y, max x, max y)   orip_svg_bbox
       fit_fn(paths, sx, sy, ox, oy) -> paths       orip_svg_fit
+      hatch_fn(paths, fill_group, params) -> (paths, counts)   orip_svg_hatch  (only with --hatch-spacing-mm; params: hatch_params(); info["hatch"] = counts)
       fetch_fn(paths, with_points) -> (off int64, pts float64 or None)   orip_svg_paths_fetch  (the points only with want_paths: info["fitted_paths"])
       steps_fn(paths, map) -> (off, pts int32)     orip_gcode_to_steps without pointers
       order_fn, codes_fn, pack_fn                  as in orip.gcode.build_stream_from_gcode
@@ -537,7 +621,8 @@ def build_stream_from_svg(text: Union[str, bytes, SegmentTable], opts: Optional[
     o = opts if opts is not None else SvgOptions()
     tm = timings if timings is not None else {}
     t0 = time.perf_counter()
-    table = text if isinstance(text, SegmentTable) else parse_svg(text)
+    hp = hatch_params(o)
+    table = text if isinstance(text, SegmentTable) else parse_svg(text, o.hatch_fill)
     tm["parse_svg"] = tm.get("parse_svg", 0.0) + (time.perf_counter() - t0)
     go = gcode_options(o)
     GC.apply_speed_scale(GC.GcodeOptions(speed_scale=go.speed_scale))
@@ -548,15 +633,18 @@ def build_stream_from_svg(text: Union[str, bytes, SegmentTable], opts: Optional[
         if want_paths:
             info["fitted_paths"] = (np.zeros(1, np.int64), np.zeros((0, 2)))
         return data, dict(ginfo, **info)
-    if any(f is None for f in (flatten_fn, bbox_fn, fit_fn, fetch_fn, steps_fn, order_fn, codes_fn, pack_fn)):
+    if any(f is None for f in (flatten_fn, bbox_fn, fit_fn, fetch_fn, steps_fn, order_fn, codes_fn, pack_fn)) or (hp and hatch_fn is None):
         if device is None:
             from .stages import device as _default_device
             device = _default_device()
         R = _Resident(device)
         flatten_fn = flatten_fn or R.flatten; bbox_fn = bbox_fn or R.bbox; fit_fn = fit_fn or R.fit; fetch_fn = fetch_fn or R.fetch; steps_fn = steps_fn or R.steps
+        hatch_fn = hatch_fn or R.hatch
         order_fn = order_fn or device.gcode_order; codes_fn = codes_fn or device.stream_codes_resident; pack_fn = pack_fn or device.stream_pack
     paths, fi = fit_paths(table, o, flatten_fn, bbox_fn, fit_fn, tm)
     info.update(fi)
+    if hp:
+        paths = hatch_paths(table, hp, paths, hatch_fn, info, tm)
     t0 = time.perf_counter()
     off_mm, pts_mm = fetch_fn(paths, want_paths)
     off_mm = np.asarray(off_mm, np.int64)
@@ -577,6 +665,11 @@ def _add_fit_args(ap: argparse.ArgumentParser, d: SvgOptions):
     ap.add_argument("--scale-x", type=float, default=None, help="X scale; overrides --scale for X")
     ap.add_argument("--scale-y", type=float, default=None, help="Y scale; overrides --scale for Y")
     ap.add_argument("--tolerance-mm", type=float, default=None, help="largest distance between a curve and its polyline on the page (default: half a step, 0.5 / steps per mm)")
+    ap.add_argument("--hatch-spacing-mm", type=float, default=None, help="hatch-fill closed shapes with lines this far apart (default: no hatching); rounded to whole steps")
+    ap.add_argument("--hatch-inset-mm", type=float, default=d.hatch_inset_mm, help="how far each hatch line stays inside the outline (default: 0.675, 27 steps at 40 steps per mm)")
+    ap.add_argument("--hatch-direction", choices=sorted(HATCH_DIRECTIONS), default=d.hatch_direction, help="hatch lines along X, along Y, or both (default: horizontal)")
+    ap.add_argument("--no-serpentine", action="store_true", help="draw every hatch line in the same direction; by default every other line is reversed")
+    ap.add_argument("--hatch-fill", choices=HATCH_FILLS, default=d.hatch_fill, help="stated: elements whose fill is written down and is not none (default); all: every element that draws")
 
 
 def build_gcode_argparser() -> argparse.ArgumentParser:
@@ -588,7 +681,7 @@ def build_gcode_argparser() -> argparse.ArgumentParser:
     ap.add_argument("--cutting-speed", type=float, default=d.cutting_speed, help="accepted for the reference's command line; only matters to a laser")
     ap.add_argument("--passes", type=int, default=d.passes, help="number of passes over the same paths (the paths are repeated)")
     ap.add_argument("--pass-depth", type=float, default=d.pass_depth, help="accepted for the reference's command line; only matters to a laser")
-    ap.add_argument("--steps-per-mm", type=float, default=d.steps_per_mm, help="only sets the default tolerance here")
+    ap.add_argument("--steps-per-mm", type=float, default=d.steps_per_mm, help="sets the default tolerance and the grid of the hatch lines here")
     _add_fit_args(ap, d)
     return ap
 
@@ -628,7 +721,8 @@ def main_gcode(argv: Optional[Sequence[str]] = None, **device_steps) -> None:
     """svg2gcode.py: the fitted paths as G-code"""
     a = build_gcode_argparser().parse_args(argv)
     o = options_from_args(a)
-    table = parse_svg(_read(a.input))
+    hp = hatch_params(o)
+    table = parse_svg(_read(a.input), o.hatch_fill)
     info = {}
     off, pts = np.zeros(1, np.int64), np.zeros((0, 2))
     if table.n_seg:
@@ -636,8 +730,10 @@ def main_gcode(argv: Optional[Sequence[str]] = None, **device_steps) -> None:
         if not R:
             from .stages import device as _default_device
             r = _Resident(_default_device())
-            R = dict(flatten_fn=r.flatten, bbox_fn=r.bbox, fit_fn=r.fit, fetch_fn=r.fetch)
+            R = dict(flatten_fn=r.flatten, bbox_fn=r.bbox, fit_fn=r.fit, fetch_fn=r.fetch, hatch_fn=r.hatch)
         paths, info = fit_paths(table, o, R["flatten_fn"], R["bbox_fn"], R["fit_fn"])
+        if hp:
+            paths = hatch_paths(table, hp, paths, R["hatch_fn"], info)
         off, pts = R["fetch_fn"](paths, True)
     Path(a.output).write_text(gcode_text(off, pts, o.passes), encoding="utf-8")
     print(f"G-code saved to {a.output}: {len(off) - 1} paths, {len(pts)} points")
@@ -645,6 +741,8 @@ def main_gcode(argv: Optional[Sequence[str]] = None, **device_steps) -> None:
         sx, sy, ox, oy = info["scale"]
         print(f"  Raw bbox: x=[{info['bbox'][0]:.3f}, {info['bbox'][2]:.3f}], y=[{info['bbox'][1]:.3f}, {info['bbox'][3]:.3f}]")
         print(f"  Final scale: sx={sx:.5f}, sy={sy:.5f}; offsets: {ox:.3f}, {oy:.3f} mm; tolerance {tolerance_mm(o)} mm = {info['tol_raw']:.6g} raw units")
+    if "hatch" in info:
+        print("  Hatch: {groups} fill groups, {lines} lines, {crossings} crossings -> {segments} segments".format(**info["hatch"]))
 
 
 def main_stream(argv: Optional[Sequence[str]] = None, **device_steps) -> None:
@@ -664,6 +762,8 @@ def main_stream(argv: Optional[Sequence[str]] = None, **device_steps) -> None:
     gcode_path.write_text(gcode_text(off, pts), encoding="utf-8")
     stream_path.write_bytes(data)
     print(f"[svg] {a.input}: {info['segments']} segments in {info['subpaths']} subpaths -> {len(pts)} points")
+    if "hatch" in info:
+        print("[svg] hatch: {groups} fill groups, {lines} lines, {crossings} crossings -> {segments} segments".format(**info["hatch"]))
     print(f"[svg] G-code saved: {gcode_path}")
     print(f"stream saved: {stream_path} ({len(data)} bytes)")
     if o.no_preview:

@@ -297,15 +297,16 @@ class Device:
             self._ck(self.L.orip_dedup_cross_layer_from(self.h, src, layer))
 
     # ---- 13_build_stream: direction codes of all moves of a plot
-    def stream_codes(self, moves: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
-        """moves int32 [n,4] (x0, y0, x1, y1) -> (off int64 [n+1], codes uint8 [total])"""
+    def stream_codes(self, moves: np.ndarray, fetch_codes: bool = True) -> Tuple[np.ndarray, np.ndarray | None]:
+        """moves int32 [n,4] (x0, y0, x1, y1) -> (off int64 [n+1], codes uint8 [total]); without the fetch the codes stay on the device for
+        stream_pack and (off, None) comes back"""
         m = np.ascontiguousarray(moves, np.int32).reshape(-1, 4)
         total = C.c_int64(0)
         self._ck(self.L.orip_stream_codes(self.h, _p(m) if len(m) else None, len(m), C.byref(total)))
         off = np.zeros(len(m) + 1, np.int64)
-        codes = np.zeros(max(total.value, 1), np.uint8)
-        self._ck(self.L.orip_stream_codes_fetch(self.h, _p(off), _p(codes)))
-        return off, codes[:total.value]
+        codes = np.zeros(max(total.value, 1), np.uint8) if fetch_codes else None
+        self._ck(self.L.orip_stream_codes_fetch(self.h, _p(off), _p(codes) if fetch_codes else None))
+        return off, codes[:total.value] if fetch_codes else None
 
     def stream_preview(self, data, W: int, H: int, rw: int, rh: int, flags: int, palette, tap_radius: int) -> Tuple[np.ndarray, dict]:
         """decode + replay + draw a plotter stream (include/orip.h: orip_stream_preview) -> (rgb uint8 [rh, rw, 3], statistics dict);
@@ -320,27 +321,19 @@ class Device:
         return rgb, {k: int(v) for k, v in zip(STAT_FIELDS, st)}
 
     # ---- gcode2stream: paths to steps, nearest-neighbour order, stream bytes (include/orip.h; csrc/gcode.hip)
-    def gcode_to_steps(self, off: np.ndarray, pts_mm: np.ndarray, map: dict, fetch_points: bool = True) -> Tuple[np.ndarray, np.ndarray]:
+    def gcode_to_steps(self, off: np.ndarray | None, pts_mm: np.ndarray | None, map: dict, fetch_points: bool = True, n: int | None = None) -> Tuple[np.ndarray, np.ndarray]:
         """paths in mm (off int64 [n + 1], pts float64 [total, 2]) -> step polylines (off int64, pts int32 [total', 2]), also left resident;
-        map: the fields of orip_gcode_map"""
-        o = np.ascontiguousarray(off, np.int64).reshape(-1)
-        p = np.ascontiguousarray(pts_mm, np.float64).reshape(-1, 2)
-        n = max(len(o) - 1, 0)
-        if n and int(o[-1]) != len(p):
-            raise ValueError(f"offsets end at {int(o[-1])}, {len(p)} points given")
+        off = pts_mm = None: the n fitted paths svg_flatten / svg_fit left on the device; map: the fields of orip_gcode_map"""
+        o = p = None
+        if off is not None or pts_mm is not None:
+            o = np.ascontiguousarray(off, np.int64).reshape(-1)
+            p = np.ascontiguousarray(pts_mm, np.float64).reshape(-1, 2)
+            n = max(len(o) - 1, 0)
+            if n and int(o[-1]) != len(p):
+                raise ValueError(f"offsets end at {int(o[-1])}, {len(p)} points given")
         m = _l.GcodeMap(**{k: map[k] for k, _ in _l.GcodeMap._fields_})
         n_out, tot = C.c_int64(0), C.c_int64(0)
-        self._ck(self.L.orip_gcode_to_steps(self.h, _p(o) if n else None, _p(p) if len(p) else None, n, C.byref(m), C.byref(n_out), C.byref(tot)))
-        off_s = np.zeros(n_out.value + 1, np.int64)
-        pts_s = np.zeros((max(tot.value, 1), 2), np.int32)
-        self._ck(self.L.orip_gcode_steps_fetch(self.h, _p(off_s), _p(pts_s) if fetch_points else None))
-        return off_s, pts_s[:tot.value]
-
-    def gcode_to_steps_resident(self, n: int, map: dict, fetch_points: bool = True) -> Tuple[np.ndarray, np.ndarray]:
-        """gcode_to_steps of the n fitted paths svg_flatten / svg_fit left on the device (off == NULL, pts_mm == NULL)"""
-        m = _l.GcodeMap(**{k: map[k] for k, _ in _l.GcodeMap._fields_})
-        n_out, tot = C.c_int64(0), C.c_int64(0)
-        self._ck(self.L.orip_gcode_to_steps(self.h, None, None, int(n), C.byref(m), C.byref(n_out), C.byref(tot)))
+        self._ck(self.L.orip_gcode_to_steps(self.h, _p(o) if o is not None and n else None, _p(p) if p is not None and len(p) else None, int(n), C.byref(m), C.byref(n_out), C.byref(tot)))
         off_s = np.zeros(n_out.value + 1, np.int64)
         pts_s = np.zeros((max(tot.value, 1), 2), np.int32)
         self._ck(self.L.orip_gcode_steps_fetch(self.h, _p(off_s), _p(pts_s) if fetch_points else None))
@@ -401,17 +394,8 @@ class Device:
         self._ck(self.L.orip_gcode_order(self.h, _p(e) if ends is not None and n else None, int(n), _p(order)))
         return order[:int(n)]
 
-    def stream_codes_resident(self, moves: np.ndarray) -> Tuple[np.ndarray, None]:
-        """stream_codes without the codes: they stay on the device for stream_pack; -> (off int64 [n + 1], None)"""
-        m = np.ascontiguousarray(moves, np.int32).reshape(-1, 4)
-        total = C.c_int64(0)
-        self._ck(self.L.orip_stream_codes(self.h, _p(m) if len(m) else None, len(m), C.byref(total)))
-        off = np.zeros(len(m) + 1, np.int64)
-        self._ck(self.L.orip_stream_codes_fetch(self.h, _p(off), None))
-        return off, None
-
     def stream_pack(self, table, codes=None) -> bytes:
-        """bytes of a piece table (orip.stream.PieceTable) from the resident direction codes; `codes` is what stream_codes_resident returned (None)"""
+        """bytes of a piece table (orip.stream.PieceTable) from the resident direction codes; `codes` is what stream_codes(..., fetch_codes=False) returned (None)"""
         if codes is not None:
             raise ValueError("stream_pack reads the codes orip_stream_codes left on the device; pass None")
         c0 = np.ascontiguousarray(table.code0, np.int64); cnt = np.ascontiguousarray(table.cnt, np.int32)

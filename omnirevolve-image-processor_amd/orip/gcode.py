@@ -175,76 +175,7 @@ def stream_config(o: GcodeOptions) -> ST.StreamConfig:
                            travel_window_steps=o.travel_window_steps, travel_quant_step=o.travel_quant_step)
 
 
-# ------------------------------------------------------------------ emit (:399-426), flat over all paths
-@dataclass
-class Plan:
-    """The moves of a plot and what the byte layout needs once their step counts are known."""
-    moves: np.ndarray           # int32 [M, 4]
-    kind: np.ndarray            # per item: service byte, or -1 for the next move
-    is_travel: np.ndarray       # per move
-    slow_in: np.ndarray
-    slow_out: np.ndarray
-
-
-def plan_moves(off: np.ndarray, pts: np.ndarray, sc: ST.StreamConfig, color_index: int) -> Plan:
-    """pen up, speed div_start, colour; per path: a travel when the cursor is elsewhere, pen down, the segments, pen up."""
-    if not (0 <= color_index <= 7):
-        raise ValueError("color index 0..7")
-    off = np.asarray(off, np.int64); pts = np.asarray(pts, np.int64).reshape(-1, 2)
-    n = len(off) - 1
-    nseg = np.diff(off) - 1
-    first, last = pts[off[:-1]], pts[off[1:] - 1]
-    cur = np.concatenate([np.zeros((1, 2), np.int64), last[:-1]])
-    trav = (cur != first).any(1)
-    per_path = trav + nseg                                                # moves of a path
-    mbase = np.cumsum(per_path) - per_path
-    M = int(per_path.sum())
-    moves = np.zeros((M, 4), np.int32)
-    is_travel = np.zeros(M, bool); slow_in = np.zeros(M, bool); slow_out = np.zeros(M, bool)
-    t = mbase[trav]
-    moves[t, :2] = cur[trav]; moves[t, 2:] = first[trav]; is_travel[t] = True
-    is_last = np.zeros(len(pts), bool); is_last[off[1:] - 1] = True
-    a = np.nonzero(~is_last)[0]                                           # first vertex of every segment
-    sp = np.repeat(np.arange(n), nseg)
-    s = mbase[sp] + trav[sp] + (a - off[sp])
-    moves[s, :2] = pts[a]; moves[s, 2:] = pts[a + 1]
-    slow_in[s], slow_out[s] = ST.corner_flags_flat(pts, off, sc.corner_deg)
-    items = per_path + 2
-    ibase = 3 + np.cumsum(items) - items
-    kind = np.full(3 + int(items.sum()), -1, np.int64)
-    kind[0] = ST.PEN_UP
-    kind[1] = 0x40 | (min(max(int(sc.div_start), 0), 63) & 0x3F)          # set_speed(div_start): written here, and remembered (layout: initial_div)
-    kind[2] = 0x08 | (color_index & 7)
-    kind[ibase + trav] = ST.PEN_DOWN
-    kind[ibase + per_path + 1] = ST.PEN_UP
-    return Plan(moves, kind, is_travel, slow_in, slow_out)
-
-
-def plan_pieces(P: Plan, counts: np.ndarray, sc: ST.StreamConfig) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
-    """(move, divider, count) of every piece in move order.  A segment without corners is one piece; every other move takes the plan of its
-    (kind, step count), computed once per distinct pair with orip.stream's plan_travel / plan_segment and expanded with numpy."""
-    counts = np.asarray(counts, np.int64)
-    simple = ~P.is_travel & ~P.slow_in & ~P.slow_out
-    i0 = np.nonzero(simple & (counts > 0))[0]
-    pm = [i0]; pc = [counts[i0]]; pd = [np.where(counts[i0] <= sc.short_len_steps, sc.short_div, sc.div_fast).astype(np.int64)]
-    i1 = np.nonzero(~simple & (counts > 0))[0]
-    if len(i1):
-        cls = np.where(P.is_travel[i1], 0, 1 + P.slow_in[i1] + 2 * P.slow_out[i1]).astype(np.int64)
-        uniq, inv = np.unique(cls * (int(counts.max()) + 1) + counts[i1], return_inverse=True)
-        plan_off = [0]; plan_div: List[int] = []; plan_cnt: List[int] = []
-        for key in uniq:
-            c, k = divmod(int(key), int(counts.max()) + 1)
-            pcs = ST.plan_travel(k, sc) if c == 0 else ST.plan_segment(k, sc, bool((c - 1) & 1), bool((c - 1) & 2))
-            plan_div += [d for d, _ in pcs]; plan_cnt += [q for _, q in pcs]; plan_off.append(len(plan_div))
-        plan_off = np.asarray(plan_off, np.int64); plan_div = np.asarray(plan_div, np.int64); plan_cnt = np.asarray(plan_cnt, np.int64)
-        lens = np.diff(plan_off)[inv]
-        src = np.repeat(plan_off[inv], lens) + np.arange(int(lens.sum())) - np.repeat(np.cumsum(lens) - lens, lens)
-        pm.append(np.repeat(i1, lens)); pd.append(plan_div[src]); pc.append(plan_cnt[src])
-    pm, pd, pc = np.concatenate(pm), np.concatenate(pd), np.concatenate(pc)
-    order = np.argsort(pm, kind="stable")
-    return pm[order], pd[order], pc[order]
-
-
+# ------------------------------------------------------------------ emit (:399-426): orip.stream's planner over all paths
 EMPTY_STREAM = bytes([ST.EOF_BYTE]) + b"\x00" * (ST.SPI_CHUNK_SIZE - 1)    # no paths: the end byte and padding, without the three leading bytes (:364-391)
 
 
@@ -255,8 +186,7 @@ def build_stream_from_gcode(text_or_paths, opts: Optional[GcodeOptions] = None, 
     Device steps, each None = the GPU (orip.device.Device; there is no CPU path in the product):
       steps_fn(off, pts_mm, map: dict) -> (off int64, pts int32 [total, 2])      orip_gcode_to_steps
       order_fn(ends int32 [n, 4]) -> order int32 [n]                             orip_gcode_order
-      codes_fn(moves int32 [M, 4]) -> (off int64 [M + 1], codes or None)         orip_stream_codes (None: the codes stay on the device)
-      pack_fn(table: orip.stream.PieceTable, codes) -> bytes                     orip_stream_pack
+      codes_fn, pack_fn                                                          orip.stream.compile_plan
     Returns (bytes, counts)."""
     import time
     o = apply_speed_scale(GcodeOptions(**{f.name: getattr(opts, f.name) for f in fields(GcodeOptions)}) if opts is not None else GcodeOptions())
@@ -281,14 +211,12 @@ def build_stream_from_gcode(text_or_paths, opts: Optional[GcodeOptions] = None, 
         return EMPTY_STREAM, dict(info, bytes=len(EMPTY_STREAM))
     if not (1 <= W <= MAX_TARGET_STEPS and 1 <= H <= MAX_TARGET_STEPS):
         raise ValueError(f"target size {W} x {H} steps: each side must be in 1..2^30 (step coordinates are int32 on the device)")
-    if steps_fn is None or order_fn is None or codes_fn is None or pack_fn is None:
+    if steps_fn is None or order_fn is None:
         if device is None:
             from .stages import device as _default_device
             device = _default_device()
         steps_fn = steps_fn or device.gcode_to_steps
         order_fn = order_fn or device.gcode_order
-        codes_fn = codes_fn or device.stream_codes_resident
-        pack_fn = pack_fn or device.stream_pack
     off, pts = steps_fn(off_mm, pts_mm, dict(scale_x=o.scale_x, scale_y=o.scale_y, offset_x_mm=o.offset_x_mm, offset_y_mm=o.offset_y_mm, steps_per_mm=o.steps_per_mm,
                                              W=W, H=H, invert_y=int(bool(o.invert_y))))
     off = np.asarray(off, np.int64); pts = np.asarray(pts, np.int32).reshape(-1, 2)
@@ -306,16 +234,12 @@ def build_stream_from_gcode(text_or_paths, opts: Optional[GcodeOptions] = None, 
         pts = pts[np.repeat(off[:-1][order], lens) + np.arange(int(lens.sum())) - np.repeat(noff[:-1], lens)]
         off = noff
     lap("order")
-    P = plan_moves(off, pts, sc, int(o.color_index))
+    if not (0 <= int(o.color_index) <= 7):
+        raise ValueError("color index 0..7")
+    div0 = min(max(int(sc.div_start), 0), 63)                             # set_speed(div_start): written here, and remembered (layout: initial_div)
+    P = ST.plan_ops(off, pts, np.zeros(n, bool), (0, 0), [ST.PEN_UP, 0x40 | div0, 0x08 | int(o.color_index)], False, sc)
     lap("plan")
-    coff, codes = codes_fn(P.moves)
-    coff = np.asarray(coff, np.int64)
-    lap("codes")
-    pm, pd, pc = plan_pieces(P, np.diff(coff), sc)
-    table = ST.layout(P.kind, pm, pd, pc, coff, initial_div=int(sc.div_start))
-    lap("plan")
-    data = pack_fn(table, codes)
-    lap("pack")
+    data, table, coff = ST.compile_plan(P, sc, device, codes_fn, pack_fn, initial_div=int(sc.div_start), lap=lap)
     info.update(steps=int(coff[-1]), bytes=len(data), pieces=len(table.pos), moves=len(P.moves))
     return data, info
 

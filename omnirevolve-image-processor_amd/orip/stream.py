@@ -4,12 +4,15 @@ shared/omnirevolve_plotter_stream_creator_helper.py).
 Wire format (helper :7-15): step bytes 11 FFF SSS (two steps) / 10 SSS 000 (one); service bytes 0x40|div (speed), 0x01 pen up,
 0x02 pen down, 0x03 tap, 0x08..0x0F colour, 0x3F end of stream; padded with zeros to a multiple of 1024 bytes (:170-175).
 
-The reference emits the stream one segment at a time through a byte-appending writer.  Here a plot is compiled in three passes:
-  1. every MOVE of the plot (pen-up travel, polyline segment) is collected in order, in plotter step space (numpy per polyline);
+The reference emits the stream one segment at a time through a byte-appending writer.  Here a plot is compiled in three passes, the same for
+stage 13 and for gcode2stream / svg2stream (orip/gcode.py, orip/svg.py):
+  1. every MOVE of the plot (pen-up travel, polyline segment) and every service byte is laid out in order, in plotter step space, as flat numpy
+     arrays over all ops (plan_ops: no Python call per segment);
   2. the direction codes of all moves come from ONE launch of the HIP kernel behind orip_stream_codes (closed-form Bresenham, one thread
-     per step) -- the only per-step work of the stage;
-  3. the speed plan cuts every move into pieces (divider, step range) exactly as the helper's ramps do, and the bytes of all pieces are
-     assembled with vectorised numpy (prefix sums of the byte counts; steps are paired per piece, as StreamWriter.add_steps pairs them).
+     per step) and stay on the device;
+  3. the speed plan cuts every move into pieces (divider, step range) exactly as the helper's ramps do (plan_pieces), layout() gives every piece
+     its byte position (prefix sums of the byte counts), and orip_stream_pack writes the bytes on the device (steps are paired per piece, as
+     StreamWriter.add_steps pairs them); only the finished stream comes back.
 Everything that decides a byte follows the reference line by line in meaning: rounding (Python round = half-to-even), clamping, the
 Y flip, the "approach before colour select" rule, corner thresholds, ramp tables, the per-piece step pairing, the pen / tap sequence."""
 from __future__ import annotations
@@ -166,27 +169,6 @@ def _angle(a, b, c) -> float:                                          # angle_d
     return math.degrees(math.acos(max(-1.0, min(1.0, (v1x * v2x + v1y * v2y) / (n1 * n2)))))
 
 
-def corner_flags(pl: np.ndarray, corner_deg: float) -> Tuple[np.ndarray, np.ndarray]:
-    """slow_in / slow_out of every segment of a polyline in step space (emit_polyline, helper :300-312).  The interior angle at vertex j is
-    computed vectorised; a vertex whose angle comes out within 1e-6 degrees of the threshold is decided again with the helper's scalar
-    formula (math.hypot / acos / degrees), so the comparison is the reference's own arithmetic wherever it could matter."""
-    n = len(pl)
-    sharp = np.zeros(n, bool)                                           # sharp[j]: angle at vertex j (between j-1, j, j+1) below the threshold
-    if n >= 3:
-        p = pl.astype(np.float64)
-        v1, v2 = p[:-2] - p[1:-1], p[2:] - p[1:-1]
-        n1, n2 = np.hypot(v1[:, 0], v1[:, 1]), np.hypot(v2[:, 0], v2[:, 1])
-        ok = (n1 > 0) & (n2 > 0)
-        cosv = np.clip((v1[:, 0] * v2[:, 0] + v1[:, 1] * v2[:, 1]) / np.where(ok, n1 * n2, 1.0), -1.0, 1.0)
-        ang = np.where(ok, np.degrees(np.arccos(cosv)), 180.0)
-        sharp[1:-1] = ang < corner_deg
-        for j in np.nonzero(np.abs(ang - corner_deg) < 1e-6)[0]:
-            sharp[j + 1] = _angle(pl[j], pl[j + 1], pl[j + 2]) < corner_deg
-    slow_in = sharp[:-1].copy(); slow_in[0] = False                     # segment i = (i, i+1): entry corner at vertex i (i > 0)
-    slow_out = sharp[1:].copy(); slow_out[-1] = False                   # exit corner at vertex i + 1 (when a vertex i + 2 exists)
-    return slow_in, slow_out
-
-
 # ------------------------------------------------------------------ colour remap (13:92-160)
 def _color_idx(x) -> int:
     try:
@@ -222,62 +204,12 @@ def resolve_color_index(name: str, orig: int, ordinal: int, force, by_name, by_o
     return _color_idx(orig)
 
 
-# ------------------------------------------------------------------ the compiler
-class _Plot:
-    """Ordered items of a plot: service bytes and moves.  A move is recorded with the plan function that will cut it into speed pieces
-    once its step count is known."""
-
-    def __init__(self):
-        self.kind: List[int] = []            # per item: >= 0 service byte, -1 a move
-        self.moves: List[Tuple[int, int, int, int]] = []
-        self.plans: List[Callable[[int], List[Tuple[int, int]]]] = []
-
-    def svc(self, b: int):
-        self.kind.append(b)
-
-    def move(self, x0, y0, x1, y1, plan):
-        self.kind.append(-1); self.moves.append((int(x0), int(y0), int(x1), int(y1))); self.plans.append(plan)
-
-
-def _emit_layer(P: _Plot, ops: Sequence[dict], color_idx: int, W: int, H: int, sc: StreamConfig, cur: Tuple[int, int]) -> Tuple[int, int]:
-    """13:179-227."""
-    travel = lambda n: plan_travel(n, sc)        # noqa: E731
-    if ops:
-        first = ops[0]
-        s = to_steps(np.array([[first["x"], first["y"]]]) if first["type"] == "tap" else np.asarray(first["points"]).reshape(-1, 2)[:1], W, H)[0]
-        if cur != (s[0], s[1]):
-            P.move(cur[0], cur[1], s[0], s[1], travel); cur = (int(s[0]), int(s[1]))
-    if not (0 <= color_idx <= 7):
-        raise ValueError("color index 0..7")
-    P.svc(0x08 | (color_idx & 7))
-    for op in ops:
-        if op["type"] == "tap":
-            t = to_steps(np.array([[op["x"], op["y"]]]), W, H)[0]
-            if cur != (t[0], t[1]):
-                P.svc(PEN_UP); P.move(cur[0], cur[1], t[0], t[1], travel); cur = (int(t[0]), int(t[1]))
-            P.svc(TAP)
-            continue
-        pts = np.asarray(op["points"]).reshape(-1, 2)
-        if len(pts) < 2:
-            continue
-        pl = to_steps(pts, W, H)
-        if cur != (pl[0, 0], pl[0, 1]):
-            P.svc(PEN_UP); P.move(cur[0], cur[1], pl[0, 0], pl[0, 1], travel)
-        P.svc(PEN_DOWN)
-        sin, sout = corner_flags(pl, sc.corner_deg)
-        for i in range(len(pl) - 1):
-            if sin[i] or sout[i]:
-                P.move(pl[i, 0], pl[i, 1], pl[i + 1, 0], pl[i + 1, 1], (lambda n, a=bool(sin[i]), b=bool(sout[i]): plan_segment(n, sc, a, b)))
-            else:
-                P.move(pl[i, 0], pl[i, 1], pl[i + 1, 0], pl[i + 1, 1], None)          # the common case, planned vectorised in assemble()
-        P.svc(PEN_UP)
-        cur = (int(pl[-1, 0]), int(pl[-1, 1]))
-    return cur
-
-
 def corner_flags_flat(pts: np.ndarray, off: np.ndarray, corner_deg: float) -> Tuple[np.ndarray, np.ndarray]:
-    """corner_flags for every polyline of a flat list at once: pts int [total, 2], off [n + 1] (every polyline >= 2 points) -> slow_in / slow_out per
-    SEGMENT in list order (polyline p owns segments off[p] - p .. off[p + 1] - p - 2).  Same arithmetic, same re-decision near the threshold."""
+    """slow_in / slow_out of every segment of the polylines of a flat list (emit_polyline, helper :300-312): pts int [total, 2], off [n + 1] (a polyline
+    of one point has no segment and is no corner of its neighbours) -> flags per SEGMENT in list order (polyline p owns segments off[p] - p ..
+    off[p + 1] - p - 2).  The interior angle at every vertex is computed vectorised; a vertex whose angle comes out within 1e-6 degrees of the
+    threshold is decided again with the helper's scalar formula (math.hypot / acos / degrees), so the comparison is the reference's own arithmetic
+    wherever it could matter."""
     pts = np.asarray(pts).reshape(-1, 2); off = np.asarray(off, np.int64)
     total = len(pts)
     sharp = np.zeros(total, bool)
@@ -295,6 +227,89 @@ def corner_flags_flat(pts: np.ndarray, off: np.ndarray, corner_deg: float) -> Tu
     is_last = np.zeros(total, bool); is_last[off[1:] - 1] = True
     a = np.nonzero(~is_last)[0]                                           # first vertex of every segment
     return sharp[a], sharp[a + 1]
+
+
+# ------------------------------------------------------------------ the plan of a plot, flat over all ops
+@dataclass
+class Plan:
+    """The moves of a plot and what the byte layout needs once their step counts are known."""
+    moves: np.ndarray           # int32 [M, 4]
+    kind: np.ndarray            # per item: service byte, or -1 for the next move
+    is_travel: np.ndarray       # per move
+    slow_in: np.ndarray
+    slow_out: np.ndarray
+
+
+def fixed_plan(kind, travels=()) -> Plan:
+    """service bytes and pen-up travels (x0, y0, x1, y1) in a given order: kind per item, -1 for the next travel"""
+    t = np.asarray(travels, np.int32).reshape(-1, 4)
+    return Plan(t, np.asarray(kind, np.int64), np.ones(len(t), bool), np.zeros(len(t), bool), np.zeros(len(t), bool))
+
+
+def concat_plans(plans: Sequence[Plan]) -> Plan:
+    return Plan(*(np.concatenate([getattr(p, f) for p in plans]) for f in ("moves", "kind", "is_travel", "slow_in", "slow_out")))
+
+
+def plan_ops(off: np.ndarray, pts: np.ndarray, is_tap: np.ndarray, cur, head: Sequence[int], lift: bool, sc: StreamConfig) -> Plan:
+    """The ops of a plot in step space (op i is pts[off[i]:off[i + 1]]; a tap is one point, a line two or more), drawn in order from the cursor `cur`
+    with the pen up: the service bytes `head`; then per op a travel when the cursor is elsewhere (after a pen-up byte of its own when `lift`), and
+    the tap byte, or pen down, the segments, pen up.  The cursor stays on a tap and goes to a line's last point."""
+    off = np.asarray(off, np.int64); pts = np.asarray(pts, np.int64).reshape(-1, 2); is_tap = np.asarray(is_tap, bool)
+    n = len(off) - 1
+    nseg = np.diff(off) - 1
+    first, last = pts[off[:-1]], pts[off[1:] - 1]
+    before = np.concatenate([np.asarray(cur, np.int64).reshape(1, 2), last[:-1]])[:n]      # the cursor in front of every op
+    trav = (before != first).any(1)
+    per_op = trav + nseg                                                  # moves of an op
+    mbase = np.cumsum(per_op) - per_op
+    M = int(per_op.sum())
+    moves = np.zeros((M, 4), np.int32)
+    is_travel = np.zeros(M, bool); slow_in = np.zeros(M, bool); slow_out = np.zeros(M, bool)
+    t = mbase[trav]
+    moves[t, :2] = before[trav]; moves[t, 2:] = first[trav]; is_travel[t] = True
+    is_last = np.zeros(len(pts), bool); is_last[off[1:] - 1] = True
+    a = np.nonzero(~is_last)[0]                                           # first vertex of every segment
+    sp = np.repeat(np.arange(n), nseg)
+    s = mbase[sp] + trav[sp] + (a - off[sp])
+    moves[s, :2] = pts[a]; moves[s, 2:] = pts[a + 1]
+    slow_in[s], slow_out[s] = corner_flags_flat(pts, off, sc.corner_deg)
+    lead = trav * (1 + bool(lift))                                        # items in front of the op's own: [pen up,] travel
+    items = lead + np.where(is_tap, 1, nseg + 2)
+    ibase = len(head) + np.cumsum(items) - items
+    kind = np.full(len(head) + int(items.sum()), -1, np.int64)
+    kind[:len(head)] = head
+    if lift:
+        kind[ibase[trav]] = PEN_UP
+    own = ibase + lead
+    kind[own[is_tap]] = TAP
+    kind[own[~is_tap]] = PEN_DOWN
+    kind[(own + nseg + 1)[~is_tap]] = PEN_UP
+    return Plan(moves, kind, is_travel, slow_in, slow_out)
+
+
+def plan_pieces(P: Plan, counts: np.ndarray, sc: StreamConfig) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """(move, divider, count) of every piece in move order.  A segment without corners is one piece; every other move takes the plan of its
+    (kind, step count), computed once per distinct pair with plan_travel / plan_segment and expanded with numpy."""
+    counts = np.asarray(counts, np.int64)
+    simple = ~P.is_travel & ~P.slow_in & ~P.slow_out
+    i0 = np.nonzero(simple & (counts > 0))[0]
+    pm = [i0]; pc = [counts[i0]]; pd = [np.where(counts[i0] <= sc.short_len_steps, sc.short_div, sc.div_fast).astype(np.int64)]
+    i1 = np.nonzero(~simple & (counts > 0))[0]
+    if len(i1):
+        cls = np.where(P.is_travel[i1], 0, 1 + P.slow_in[i1] + 2 * P.slow_out[i1]).astype(np.int64)
+        uniq, inv = np.unique(cls * (int(counts.max()) + 1) + counts[i1], return_inverse=True)
+        plan_off = [0]; plan_div: List[int] = []; plan_cnt: List[int] = []
+        for key in uniq:
+            c, k = divmod(int(key), int(counts.max()) + 1)
+            pcs = plan_travel(k, sc) if c == 0 else plan_segment(k, sc, bool((c - 1) & 1), bool((c - 1) & 2))
+            plan_div += [d for d, _ in pcs]; plan_cnt += [q for _, q in pcs]; plan_off.append(len(plan_div))
+        plan_off = np.asarray(plan_off, np.int64); plan_div = np.asarray(plan_div, np.int64); plan_cnt = np.asarray(plan_cnt, np.int64)
+        lens = np.diff(plan_off)[inv]
+        src = np.repeat(plan_off[inv], lens) + np.arange(int(lens.sum())) - np.repeat(np.cumsum(lens) - lens, lens)
+        pm.append(np.repeat(i1, lens)); pd.append(plan_div[src]); pc.append(plan_cnt[src])
+    pm, pd, pc = np.concatenate(pm), np.concatenate(pd), np.concatenate(pc)
+    order = np.argsort(pm, kind="stable")
+    return pm[order], pd[order], pc[order]
 
 
 # ------------------------------------------------------------------ byte layout
@@ -346,70 +361,71 @@ def layout(kind: np.ndarray, pm: np.ndarray, pd: np.ndarray, pc: np.ndarray, off
     return PieceTable(pstart[live].astype(np.int64), pc[live].astype(np.int32), ppos[live].astype(np.int64), speed[live].astype(np.int32), svc_pos, svc_val, nbytes)
 
 
-def fill_bytes(T: PieceTable, codes: np.ndarray) -> bytes:
-    """The bytes of a piece table with numpy: index arrays per output byte, one code fetched per step.  Fine for stage 13's plots; orip_stream_pack does
-    the same on the device for streams of any size."""
-    out = np.zeros(T.nbytes, np.uint8)
-    out[T.svc_pos] = T.svc_val
-    if len(T.pos):
-        has = T.speed >= 0
-        out[T.pos[has]] = T.speed[has].astype(np.uint8)
-        pc = T.cnt.astype(np.int64)
-        nb = (pc + 1) // 2                                                # step bytes per piece
-        bpiece = np.repeat(np.arange(len(pc)), nb)
-        j = np.arange(int(nb.sum())) - np.repeat(np.cumsum(nb) - nb, nb)  # index of the byte inside its piece
-        a = codes[T.code0[bpiece] + 2 * j].astype(np.int64) & 7
-        has_b = 2 * j + 1 < pc[bpiece]
-        b = np.where(has_b, codes[np.minimum(T.code0[bpiece] + 2 * j + 1, max(len(codes) - 1, 0))].astype(np.int64) & 7, 0)
-        out[(T.pos + has)[bpiece] + j] = np.where(has_b, 0x80 | 0x40 | (a << 3) | b, 0x80 | (a << 3)).astype(np.uint8)
-    return out.tobytes()
 
 
-def plot_pieces(P: _Plot, off: np.ndarray, sc: StreamConfig) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
-    """(move index, divider, count) of every piece of a plot, in move order; simple draw segments get their single piece without a Python call."""
-    nmov = len(P.moves)
-    counts = np.diff(off).astype(np.int64) if nmov else np.zeros(0, np.int64)
-    piece_mov: List[np.ndarray] = []; piece_div: List[np.ndarray] = []; piece_cnt: List[np.ndarray] = []
-    simple = np.array([p is None for p in P.plans], bool) if nmov else np.zeros(0, bool)
-    if nmov:
-        idx = np.nonzero(simple & (counts > 0))[0]
-        piece_mov.append(idx); piece_cnt.append(counts[idx])
-        piece_div.append(np.where(counts[idx] <= sc.short_len_steps, sc.short_div, sc.div_fast).astype(np.int64))
-        for m in np.nonzero(~simple)[0]:
-            pcs = P.plans[m](int(counts[m]))
-            if pcs:
-                piece_mov.append(np.full(len(pcs), m, np.int64)); piece_div.append(np.array([d for d, _ in pcs], np.int64)); piece_cnt.append(np.array([c for _, c in pcs], np.int64))
-    pm = np.concatenate(piece_mov) if piece_mov else np.zeros(0, np.int64)
-    pd = np.concatenate(piece_div) if piece_div else np.zeros(0, np.int64)
-    pc = np.concatenate(piece_cnt) if piece_cnt else np.zeros(0, np.int64)
-    order = np.argsort(pm, kind="stable")                                 # pieces in move order, the pieces of one move in plan order
-    return pm[order], pd[order], pc[order]
+# ------------------------------------------------------------------ the compiler
+def compile_plan(P: Plan, sc: StreamConfig, device=None, codes_fn: Optional[Callable] = None, pack_fn: Optional[Callable] = None, initial_div: Optional[int] = None,
+                 lap: Callable[[str], None] = lambda name: None) -> Tuple[bytes, PieceTable, np.ndarray]:
+    """The bytes of a plan: direction codes of all moves, speed pieces, byte positions, packing (StreamWriter semantics, helper :130-175: a speed
+    byte only when the divider changes, the steps of every piece paired on their own, end byte, padding).  The two device steps, each None = the
+    GPU (orip.device.Device: the codes stay resident, the bytes are written there) -- there is no CPU path in the product:
+      codes_fn(moves int32 [M, 4]) -> (off int64 [M + 1], codes or None)         orip_stream_codes
+      pack_fn(table: PieceTable, codes) -> bytes                                 orip_stream_pack
+    initial_div: layout().  lap(name) is called after each of "codes", "plan", "pack".  Returns (bytes, piece table, first code of every move)."""
+    if codes_fn is None or pack_fn is None:
+        if device is None:
+            from .stages import device as _default_device
+            device = _default_device()
+        codes_fn = codes_fn or (lambda moves: device.stream_codes(moves, fetch_codes=False))
+        pack_fn = pack_fn or device.stream_pack
+    off, codes = codes_fn(P.moves)
+    off = np.asarray(off, np.int64)
+    lap("codes")
+    pm, pd, pc = plan_pieces(P, np.diff(off), sc)
+    table = layout(P.kind, pm, pd, pc, off, initial_div)
+    lap("plan")
+    data = pack_fn(table, codes)
+    lap("pack")
+    return data, table, off
 
 
-def assemble(P: _Plot, off: np.ndarray, codes: np.ndarray, sc: StreamConfig, *, initial_div: Optional[int] = None) -> bytes:
-    """Bytes of the plot from its items, the step offsets of its moves and their direction codes (StreamWriter semantics, helper :130-175:
-    a speed byte only when the divider changes, the steps of every piece paired on their own, end byte, padding).  initial_div: layout()."""
-    pm, pd, pc = plot_pieces(P, off, sc)
-    return fill_bytes(layout(np.asarray(P.kind, np.int64), pm, pd, pc, np.asarray(off, np.int64), initial_div), codes)
+def _layer_ops(ops: Sequence[dict], W: int, H: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+    """ops of a layer as flat arrays in step space, lines of fewer than two points dropped: (off, pts, is_tap, first point of ops[0] as given)"""
+    raw = [np.array([[op["x"], op["y"]]], np.float64) if op["type"] == "tap" else np.asarray(op["points"], np.float64).reshape(-1, 2) for op in ops]
+    tap = np.array([op["type"] == "tap" for op in ops], bool)
+    npts = np.array([len(q) for q in raw], np.int64)
+    steps = to_steps(np.concatenate(raw), W, H)                           # one call for the whole layer
+    first = steps[:npts[0]][0]
+    keep = tap | (npts >= 2)
+    return np.concatenate([[0], np.cumsum(npts[keep])]).astype(np.int64), steps[np.repeat(keep, npts)], tap[keep], first
 
 
-def build_stream(layers: Sequence[Tuple[str, int, Sequence[dict]]], W: int, H: int, sc: StreamConfig, codes_fn: Optional[Callable] = None,
-                 color_maps=(None, None, None)) -> Tuple[bytes, Dict[str, int]]:
-    """13:231-281 for layers given as (colour name, manifest colour index, ops).  codes_fn(moves int32 [n,4]) -> (off, codes): the direction
-    codes of all moves; None = the GPU (orip.device.Device.stream_codes, liborip.so) -- there is no CPU path in the product."""
-    if codes_fn is None:
-        from .stages import device
-        codes_fn = device().stream_codes
+def plan_layers(layers: Sequence[Tuple[str, int, Sequence[dict]]], W: int, H: int, sc: StreamConfig, color_maps=(None, None, None)) -> Tuple[Plan, Dict[str, int]]:
+    """The plan of 13:231-281 for layers given as (colour name, manifest colour index, ops), and the ops counted by type; per layer 13:179-227: the
+    approach to the first op (a travel without a pen-up byte), the colour byte, the ops."""
     force, by_name, by_order = color_maps
-    P = _Plot()
-    P.svc(PEN_UP)
-    cur = (0, 0)
+    plans = [fixed_plan([PEN_UP])]
+    cur = np.zeros(2, np.int64)
     n_lines = n_taps = 0
     for ordinal, (name, orig_idx, ops) in enumerate(layers):
         cidx = resolve_color_index(name, orig_idx, ordinal, force, by_name, by_order)
         n_lines += sum(1 for o in ops if o["type"] == "line"); n_taps += sum(1 for o in ops if o["type"] == "tap")
-        cur = _emit_layer(P, ops, cidx, W, H, sc, cur)
-    moves = np.asarray(P.moves, np.int32).reshape(-1, 4)
-    off, codes = codes_fn(moves)
-    data = assemble(P, np.asarray(off, np.int64), np.asarray(codes, np.uint8), sc)
-    return data, {"lines": n_lines, "taps": n_taps, "bytes": len(data)}
+        off, pts, is_tap = np.zeros(1, np.int64), np.zeros((0, 2), np.int64), np.zeros(0, bool)
+        if ops:
+            off, pts, is_tap, first = _layer_ops(ops, W, H)
+            if (cur != first).any():
+                plans.append(fixed_plan([-1], [[*cur, *first]])); cur = first
+        if not (0 <= cidx <= 7):
+            raise ValueError("color index 0..7")
+        plans.append(plan_ops(off, pts, is_tap, cur, [0x08 | (cidx & 7)], True, sc))
+        if len(pts):
+            cur = pts[-1]
+    return concat_plans(plans), {"lines": n_lines, "taps": n_taps}
+
+
+def build_stream(layers: Sequence[Tuple[str, int, Sequence[dict]]], W: int, H: int, sc: StreamConfig, codes_fn: Optional[Callable] = None,
+                 color_maps=(None, None, None), device=None, pack_fn: Optional[Callable] = None) -> Tuple[bytes, Dict[str, int]]:
+    """plot_stream.bin of stage 13 and its counts: plan_layers() through compile_plan() (device / codes_fn / pack_fn: there)."""
+    P, meta = plan_layers(layers, W, H, sc, color_maps)
+    data, _, _ = compile_plan(P, sc, device, codes_fn, pack_fn)
+    return data, dict(meta, bytes=len(data))

@@ -558,7 +558,7 @@ class _Resident:
     def bbox(self, paths): return self.dev.svg_bbox()
     def fit(self, paths, sx, sy, ox, oy): self.dev.svg_fit(sx, sy, ox, oy); return paths
     def fetch(self, paths, with_points=True): return self.dev.svg_paths(paths["n"], with_points)
-    def steps(self, paths, m): return self.dev.gcode_to_steps_resident(paths["n"], m)
+    def steps(self, paths, m): return self.dev.gcode_to_steps(None, None, m, n=paths["n"])
 
     def hatch(self, paths, fill_group, prm):
         st = self.dev.svg_hatch(fill_group, prm["steps_per_mm"], prm["spacing"], prm["inset"], prm["flags"])
@@ -640,7 +640,7 @@ def build_stream_from_svg(text: Union[str, bytes, SegmentTable], opts: Optional[
         R = _Resident(device)
         flatten_fn = flatten_fn or R.flatten; bbox_fn = bbox_fn or R.bbox; fit_fn = fit_fn or R.fit; fetch_fn = fetch_fn or R.fetch; steps_fn = steps_fn or R.steps
         hatch_fn = hatch_fn or R.hatch
-        order_fn = order_fn or device.gcode_order; codes_fn = codes_fn or device.stream_codes_resident; pack_fn = pack_fn or device.stream_pack
+        order_fn = order_fn or device.gcode_order
     paths, fi = fit_paths(table, o, flatten_fn, bbox_fn, fit_fn, tm)
     info.update(fi)
     if hp:
@@ -651,7 +651,7 @@ def build_stream_from_svg(text: Union[str, bytes, SegmentTable], opts: Optional[
     if want_paths:
         info["fitted_paths"] = (off_mm, np.asarray(pts_mm, np.float64).reshape(-1, 2))
     tm["fetch_paths"] = tm.get("fetch_paths", 0.0) + (time.perf_counter() - t0)
-    data, ginfo = GC.build_stream_from_gcode((off_mm, np.zeros((int(off_mm[-1]), 2))), go, steps_fn=lambda _off, _pts, m: steps_fn(paths, m), order_fn=order_fn,
+    data, ginfo = GC.build_stream_from_gcode((off_mm, np.zeros((int(off_mm[-1]), 2))), go, device, steps_fn=lambda _off, _pts, m: steps_fn(paths, m), order_fn=order_fn,
                                              codes_fn=codes_fn, pack_fn=pack_fn, timings=tm)
     return data, dict(ginfo, **info)
 

@@ -1,5 +1,6 @@
 # 13_build_stream.py -- drop-in for the reference stage of the same name: vector_manifest.json + <layer>/ops.pkl -> plot_stream.bin
-# + plot_stream.json.  The per-step work (direction codes of every move) runs on the GPU through liborip.so; see orip/stream.py.
+# + plot_stream.json.  The per-step work (direction codes of every move, the bytes of the stream) runs on the GPU through liborip.so; the host
+# plans the moves and their speed pieces with flat numpy; see orip/stream.py.
 import json
 import os
 from pathlib import Path

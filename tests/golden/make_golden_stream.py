@@ -7,6 +7,7 @@ does not take: the stand-in of this directory is registered as `cv2`), so every 
   * travel*    : bytes of travel_ramped for single moves (short / long / odd lengths), default helper Config
   * poly*      : bytes of emit_polyline for random polylines with sharp corners, short and long edges, repeated points, both ramp profiles
   * e2e_{a,b}* : plot_stream.bin / plot_stream.json of 13_build_stream.main() on the ops of golden_e2e_{a,b}.npz, plus a colour-remap variant
+  * golden_stream_edges.npz (write_edges): the same two files for a hand-written plot of edge cases, with its ops
 Nothing from the reference is copied: the fixture holds arrays only.   Usage: python tests/golden/make_golden_stream.py
 """
 from __future__ import annotations
@@ -85,38 +86,75 @@ def main():
         G = np.load(os.path.join(HERE, f"golden_e2e_{tag}.npz"))
         cfg = json.loads(bytes(G["cfg_json"]).decode())
         man = json.loads(bytes(G["manifest_json"]).decode())
+        layers = {}
+        for n in cfg["color_names"]:
+            kinds = G[f"ops_kinds_{n}"]; off = G[f"ops_{n}_off"]; pts = G[f"ops_{n}_pts"]
+            layers[n] = [{"type": "line", "points": pts[off[i]:off[i + 1]].astype(np.float32)} if k == 0 else {"type": "tap", "x": int(pts[off[i], 0]), "y": int(pts[off[i], 1])}
+                         for i, k in enumerate(kinds)]
         for variant, extra, env in (("", {}, {}), ("_remap", {"stream_color_by_order": [3, 0, 1, 2], "stream_color_by_name": {"layer_mid": 5}}, {}),
                                     ("_env", {}, {"STREAM_FORCE_COLOR_INDEX": "6"})):
-            with tempfile.TemporaryDirectory() as td:
-                full = dict(cfg); full.update(extra); full["output_dir"] = td
-                with open(os.path.join(td, "config.json"), "w") as f:
-                    json.dump(full, f)
-                for n in cfg["color_names"]:
-                    os.makedirs(os.path.join(td, n), exist_ok=True)
-                    kinds = G[f"ops_kinds_{n}"]; off = G[f"ops_{n}_off"]; pts = G[f"ops_{n}_pts"]
-                    ops = []
-                    for i, k in enumerate(kinds):
-                        q = pts[off[i]:off[i + 1]]
-                        ops.append({"type": "line", "points": q.astype(np.float32)} if k == 0 else {"type": "tap", "x": int(q[0, 0]), "y": int(q[0, 1])})
-                    with open(os.path.join(td, n, "ops.pkl"), "wb") as f:
-                        pickle.dump(ops, f)
-                with open(os.path.join(td, "vector_manifest.json"), "w") as f:
-                    json.dump(man, f)
-                os.environ["CONFIG_PATH"] = os.path.join(td, "config.json")
-                old = {k: os.environ.get(k) for k in env}
-                os.environ.update(env)
-                try:
-                    with contextlib.redirect_stdout(io.StringIO()):
-                        m13.main()
-                finally:
-                    for k, v in old.items():
-                        if v is None: os.environ.pop(k, None)
-                        else: os.environ[k] = v
-                g[f"e2e_{tag}{variant}_bin"] = np.frombuffer(open(os.path.join(td, "plot_stream.bin"), "rb").read(), np.uint8)
-                g[f"e2e_{tag}{variant}_json"] = np.frombuffer(open(os.path.join(td, "plot_stream.json"), "rb").read(), np.uint8)
-                g[f"e2e_{tag}{variant}_cfg"] = np.frombuffer(json.dumps(extra).encode(), np.uint8)
+            g[f"e2e_{tag}{variant}_bin"], g[f"e2e_{tag}{variant}_json"] = run_main(m13, dict(cfg, **extra), man, layers, env)
+            g[f"e2e_{tag}{variant}_cfg"] = np.frombuffer(json.dumps(extra).encode(), np.uint8)
     np.savez_compressed(os.path.join(HERE, "golden_stream.npz"), **g)
     print("golden_stream.npz:", len(g), "arrays;", {k: int(v.size) for k, v in g.items() if k.endswith("_bin")})
+    write_edges(m13)
+
+
+def run_main(m13, cfg, man, layers, env):
+    """plot_stream.bin / plot_stream.json of the reference's main() on layers {name: ops}, as uint8 arrays"""
+    with tempfile.TemporaryDirectory() as td:
+        full = dict(cfg); full["output_dir"] = td
+        with open(os.path.join(td, "config.json"), "w") as f:
+            json.dump(full, f)
+        for n, ops in layers.items():
+            os.makedirs(os.path.join(td, n), exist_ok=True)
+            with open(os.path.join(td, n, "ops.pkl"), "wb") as f:
+                pickle.dump(ops, f)
+        with open(os.path.join(td, "vector_manifest.json"), "w") as f:
+            json.dump(man, f)
+        os.environ["CONFIG_PATH"] = os.path.join(td, "config.json")
+        old = {k: os.environ.get(k) for k in env}
+        os.environ.update(env)
+        try:
+            with contextlib.redirect_stdout(io.StringIO()):
+                m13.main()
+        finally:
+            for k, v in old.items():
+                if v is None: os.environ.pop(k, None)
+                else: os.environ[k] = v
+        return tuple(np.frombuffer(open(os.path.join(td, f), "rb").read(), np.uint8) for f in ("plot_stream.bin", "plot_stream.json"))
+
+
+def edge_layers(W=840, H=1188):
+    """a hand-written plot at the places where stage 13's rules are easy to get wrong: an empty layer, an approach to a one-point line that is then
+    skipped, taps with and without a travel, a line that starts on the cursor, a repeated point, half-integer rounding, clamping that merges points,
+    a one-step travel, a colour byte with no approach"""
+    line = lambda *p: {"type": "line", "points": np.array(p, np.float32).reshape(-1, 2)}      # noqa: E731
+    tap = lambda x, y: {"type": "tap", "x": x, "y": y}                                        # noqa: E731
+    return {"e0": [],
+            "e1": [line((50, 60)), tap(50, 60), tap(50, 60), tap(300, 20), line((300, 20), (340, 20), (340, 90)), line((340, 90), (10, 95)),
+                   line((10, 95), (10, 95), (12, 95), (12.5, 96.5), (13.5, 97.5))],
+            "e2": [tap(14, 98), line((7, 7), (7, 7)), line((-30, -5), (W + 40, 3), (W + 90, H + 7), (5, H + 50)), tap(5, H - 1)],
+            "e3": [line((6, H - 1), (6, H - 2)), line((100, 100), (101, 100), (101, 101), (100, 100)), line((400, 400))],
+            "e4": []}
+
+
+def write_edges(m13=None):
+    """golden_stream_edges.npz: the reference's main() on edge_layers(); bin, json, cfg, manifest and the ops as arrays (scheme of golden_e2e_*.npz)"""
+    m13 = m13 or load_ref("13_build_stream.py")
+    layers = edge_layers()
+    cfg = {"color_names": list(layers), "pixels_per_mm": json.loads(bytes(np.load(os.path.join(HERE, "golden_e2e_a.npz"))["cfg_json"]).decode())["pixels_per_mm"]}
+    man = {"image_size": [840, 1188], "coords": "pixel_top_left",
+           "layers": [{"name": n, "color_name": n, "color_index": i + 1, "file": f"{n}/ops.pkl", "count_ops": len(ops)} for i, (n, ops) in enumerate(layers.items())]}
+    g = {"cfg_json": np.frombuffer(json.dumps(cfg).encode(), np.uint8), "manifest_json": np.frombuffer(json.dumps(man).encode(), np.uint8)}
+    g["bin"], g["json"] = run_main(m13, cfg, man, layers, {})
+    for n, ops in layers.items():
+        q = [np.asarray(o["points"], np.float32).reshape(-1, 2) if o["type"] == "line" else np.array([[o["x"], o["y"]]], np.float32) for o in ops]
+        g[f"ops_kinds_{n}"] = np.array([0 if o["type"] == "line" else 1 for o in ops], np.uint8)
+        g[f"ops_{n}_off"] = np.concatenate([[0], np.cumsum([len(v) for v in q])]).astype(np.int64)
+        g[f"ops_{n}_pts"] = np.concatenate(q) if q else np.zeros((0, 2), np.float32)
+    np.savez_compressed(os.path.join(HERE, "golden_stream_edges.npz"), **g)
+    print("golden_stream_edges.npz:", len(g), "arrays;", int(g["bin"].size), "bytes,", bytes(g["json"]).decode())
 
 
 if __name__ == "__main__":

@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 from util import load
-from stream_double import codes_numpy
+from stream_double import codes_numpy, corner_flags, fill_bytes
 import gcode_double as D
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -85,26 +85,30 @@ def test_host_path_reproduces_reference_stream(i):
 
 
 def test_paths_input_and_numpy_assembler_agree():
-    """the same stream from (off, pts_mm) instead of text, and from orip.stream.fill_bytes instead of the per-piece double"""
-    from orip import gcode as GC, stream as ST
+    """the same stream from (off, pts_mm) instead of text, and from stream_double.fill_bytes instead of the per-piece double"""
+    from orip import gcode as GC
     text = bytes(G["text_drawing"])
     off, pts, _ = GC.parse_gcode(text)
     opts = options_for(MAIN_CASES[0][1])
     a, _ = GC.build_stream_from_gcode((off, pts), opts, **DOUBLES)
-    b, _ = GC.build_stream_from_gcode(text, opts, **dict(DOUBLES, pack_fn=ST.fill_bytes))
+    b, _ = GC.build_stream_from_gcode(text, opts, **dict(DOUBLES, pack_fn=fill_bytes))
     assert a == bytes(G["main_0_bin"]) and b == a
 
 
 def test_assemble_initial_divider():
-    """assemble's default keeps today's bytes (test_stream_host.py shows that against golden_stream.npz); with the divider of the first piece given as
+    """layout's default keeps today's bytes (test_stream_host.py shows that against golden_stream.npz); with the divider of the first piece given as
     already set, exactly that one speed byte goes"""
     from orip import stream as ST
     sc = ST.StreamConfig()
-    P = ST._Plot(); P.svc(ST.PEN_UP); P.move(0, 0, 700, 300, lambda n: ST.plan_travel(n, sc)); P.svc(ST.PEN_DOWN); P.move(700, 300, 900, 300, None)
-    off, codes = codes_numpy(np.asarray(P.moves, np.int32))
-    base = ST.assemble(P, off, codes, sc)
-    assert ST.assemble(P, off, codes, sc, initial_div=None) == base and ST.assemble(P, off, codes, sc, initial_div=sc.travel_start_div + 1) == base
-    cut = ST.assemble(P, off, codes, sc, initial_div=sc.travel_start_div)
+    P = ST.concat_plans([ST.fixed_plan([ST.PEN_UP, -1], [[0, 0, 700, 300]]), ST.plan_ops([0, 2], [[700, 300], [900, 300]], [False], (700, 300), [], False, sc)])
+    assert P.kind.tolist() == [ST.PEN_UP, -1, ST.PEN_DOWN, -1, ST.PEN_UP] and P.is_travel.tolist() == [True, False]
+
+    def packed(initial_div=None, pack_fn=fill_bytes):
+        return ST.compile_plan(P, sc, codes_fn=codes_numpy, pack_fn=pack_fn, initial_div=initial_div)[0]
+    base = packed()
+    assert packed(pack_fn=D.pack_numpy) == base
+    assert packed(initial_div=None) == base and packed(initial_div=sc.travel_start_div + 1) == base
+    cut = packed(initial_div=sc.travel_start_div)
     assert base[1] == 0x40 | sc.travel_start_div and cut[:1] == base[:1] and cut[1:cut.index(bytes([ST.EOF_BYTE]))] == base[2:base.index(bytes([ST.EOF_BYTE]))]
 
 
@@ -175,5 +179,5 @@ def test_flat_corner_flags_equal_per_polyline_flags():
     off = np.concatenate([[0], np.cumsum([len(p) for p in polys])]); pts = np.concatenate(polys)
     for deg in (85.0, 90.0, 90.0000001, 120.0):
         a, b = ST.corner_flags_flat(pts, off, deg)
-        want = [ST.corner_flags(p, deg) for p in polys]
+        want = [corner_flags(p, deg) for p in polys]
         assert np.array_equal(a, np.concatenate([w[0] for w in want])) and np.array_equal(b, np.concatenate([w[1] for w in want]))

@@ -1,5 +1,5 @@
 """gcode2stream on the GPU: each kernel of csrc/gcode.hip against the reference's recorded output (tests/golden/golden_gcode.npz), bit for bit; the packed
-bytes against the numpy assembler on stage 13's plots; the whole tool, in process and as the script on disk, against the files the reference's main()
+bytes against the doubles' two numpy packers on stage 13's plots; the whole tool, in process and as the script on disk, against the files the reference's main()
 wrote; every degenerate input of the order; one order beyond what the reference can run, checked pair by pair against the definition; and a round trip
 through the stream preview.  No comparison has a tolerance and no recorded case is left out."""
 import json
@@ -15,7 +15,8 @@ pytestmark = pytest.mark.gpu
 from util import load
 import gcode_double as D
 from test_gcode_host import G, MAIN_CASES, ORDER_NAMES, CONV_SETS, conv_map, options_for
-from test_stream_host import _layers_from_e2e
+from stream_double import fill_bytes
+from test_stream_host import _layers_from_e2e, _pipeline_config
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SCRIPT = os.path.join(ROOT, "omnirevolve-image-processor_amd", "svg_to_stream", "gcode2stream.py")
@@ -134,28 +135,24 @@ def test_order_large_pair_by_pair(dev):
 # ------------------------------------------------------------------ pack
 @pytest.mark.parametrize("tag", ["a", "b"])
 def test_pack_equals_numpy_assembler_on_stage13_plots(dev, tag):
-    """same pieces, two assemblers: orip_stream_pack on the resident codes against orip.stream.fill_bytes on the fetched ones, and both the reference's file"""
+    """same pieces, three packers: orip_stream_pack on the resident codes against the doubles' two on the fetched ones, and all three the reference's file"""
     from orip import stream as ST
-    from orip.config import Config, canvas_size_px
+    from orip.config import canvas_size_px
     cfgd, layers = _layers_from_e2e(tag)
-    cfg = Config()
-    for k, v in cfgd.items():
-        if k in Config.__dataclass_fields__:
-            setattr(cfg, k, v)
+    cfg = _pipeline_config(cfgd)
     W, H = canvas_size_px(cfg)
     sc = ST.stream_config_from_pipeline(cfg)
-    maps = ST.load_color_maps(cfg)
-    P = ST._Plot(); P.svc(ST.PEN_UP)
-    cur = (0, 0)
-    for ordinal, (name, orig, ops) in enumerate(layers):
-        cur = ST._emit_layer(P, ops, ST.resolve_color_index(name, orig, ordinal, *maps), W, H, sc, cur)
-    off, codes = dev.stream_codes(np.asarray(P.moves, np.int32).reshape(-1, 4))
-    pm, pd, pc = ST.plot_pieces(P, off, sc)
-    table = ST.layout(np.asarray(P.kind, np.int64), pm, pd, pc, off)
+    P, _ = ST.plan_layers(layers, W, H, sc, ST.load_color_maps(cfg))
+    fetched = {}
+
+    def codes_fn(moves):                                                    # fetched for the doubles; the device packs from its own resident copy
+        off, fetched["codes"] = dev.stream_codes(moves)
+        return off, None
+    data, table, _ = ST.compile_plan(P, sc, dev, codes_fn=codes_fn)
     want = bytes(GS[f"e2e_{tag}_bin"])
-    assert ST.fill_bytes(table, codes) == want
-    assert dev.stream_pack(table) == want
-    assert D.pack_numpy(table, codes) == want
+    assert fill_bytes(table, fetched["codes"]) == want
+    assert data == want
+    assert D.pack_numpy(table, fetched["codes"]) == want
 
 
 def test_pack_edges(dev):
@@ -166,7 +163,7 @@ def test_pack_edges(dev):
     # pieces of one and two steps, a piece that only sets the speed, a speed byte above 0x7f is refused, service bytes between pieces
     T = ST.PieceTable(np.array([0, 1, 3, 5], np.int64), np.array([1, 2, 0, 7], np.int32), np.array([1, 3, 6, 8], np.int64), np.array([0x5c, -1, 0x4a, 0x7f], np.int32),
                       np.array([0, 5, 7, 13], np.int64), np.array([1, 2, 1, 0x3f], np.uint8), 1024)
-    assert dev.stream_pack(T) == D.pack_numpy(T, codes) == ST.fill_bytes(T, codes)
+    assert dev.stream_pack(T) == D.pack_numpy(T, codes) == fill_bytes(T, codes)
     E = ST.PieceTable(np.zeros(0, np.int64), np.zeros(0, np.int32), np.zeros(0, np.int64), np.zeros(0, np.int32), np.array([0], np.int64), np.array([0x3f], np.uint8), 1024)
     assert dev.stream_pack(E) == bytes([0x3f]) + bytes(1023)
     for bad in (dict(code0=np.array([0, 1, 3, 6], np.int64)),            # reads past the resident codes

@@ -193,14 +193,14 @@ def test_resident_hand_off(dev):
         o2, p2 = dev.svg_paths()
         assert len(o2) - 1 == len(polys) + len(want) and int(o2[-1]) == len(pts) + 2 * len(want)
         with pytest.raises(OripError):
-            dev.gcode_to_steps_resident(len(polys), STEP_MAP)                                   # the count is the hatched one now
-        soff, spts = dev.gcode_to_steps_resident(len(o2) - 1, STEP_MAP)
+            dev.gcode_to_steps(None, None, STEP_MAP, n=len(polys))                                   # the count is the hatched one now
+        soff, spts = dev.gcode_to_steps(None, None, STEP_MAP, n=len(o2) - 1)
         n = len(soff) - 1 - len(want)
         assert np.array_equal(spts[soff[n]:].reshape(-1, 4), want)                              # the reference's integers
         b = dev.gcode_to_steps(o2, p2, STEP_MAP)
         assert np.array_equal(b[0], soff) and np.array_equal(b[1], spts)
         m = dict(STEP_MAP, invert_y=1, H=2000)
-        soff, spts = dev.gcode_to_steps_resident(len(o2) - 1, m)
+        soff, spts = dev.gcode_to_steps(None, None, m, n=len(o2) - 1)
         mirrored = want.copy(); mirrored[:, [1, 3]] = 1999 - mirrored[:, [1, 3]]
         assert np.array_equal(spts[soff[len(soff) - 1 - len(want)]:].reshape(-1, 4), mirrored)
 

@@ -13,7 +13,7 @@ pytestmark = pytest.mark.gpu
 
 from util import load
 from stream_double import codes_numpy
-from test_stream_host import _layers_from_e2e
+from test_stream_host import _layers_from_e2e, _pipeline_config, edge_plot
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 G = load("golden_stream.npz")
@@ -52,16 +52,22 @@ def test_direction_codes_large_random_vs_closed_form(dev):
 
 @pytest.mark.parametrize("tag", ["a", "b"])
 def test_whole_stream_on_device_matches_reference(dev, tag):
+    """direction codes and packing both on the device"""
     from orip import stream as ST
-    from orip.config import Config, canvas_size_px
+    from orip.config import canvas_size_px
     cfgd, layers = _layers_from_e2e(tag)
-    cfg = Config()
-    for k, v in cfgd.items():
-        if k in Config.__dataclass_fields__:
-            setattr(cfg, k, v)
+    cfg = _pipeline_config(cfgd)
     W, H = canvas_size_px(cfg)
-    data, _ = ST.build_stream(layers, W, H, ST.stream_config_from_pipeline(cfg), codes_fn=dev.stream_codes, color_maps=ST.load_color_maps(cfg))
+    data, _ = ST.build_stream(layers, W, H, ST.stream_config_from_pipeline(cfg), color_maps=ST.load_color_maps(cfg), device=dev)
     assert data == bytes(G[f"e2e_{tag}_bin"])
+
+
+def test_edge_plot_on_device_matches_reference(dev):
+    """the 21 moves of golden_stream_edges.npz (test_stream_host.py: edge_plot): every branch of the planner, codes and packing on the device"""
+    from orip import stream as ST
+    layers, W, H, sc, maps, want, wj = edge_plot()
+    data, meta = ST.build_stream(layers, W, H, sc, color_maps=maps, device=dev)
+    assert data == want and meta == {"lines": wj["lines"], "taps": wj["taps"], "bytes": wj["bytes"]}
 
 
 def test_stage_script_13_on_disk(tmp_path):

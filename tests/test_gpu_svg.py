@@ -149,7 +149,7 @@ def test_error_returns(dev):
         with pytest.raises(OripError):                                                      # and nothing is left behind
             dev.svg_bbox()
         with pytest.raises(OripError):
-            dev.gcode_to_steps_resident(1, dict(scale_x=1.0, scale_y=1.0, offset_x_mm=0.0, offset_y_mm=0.0, steps_per_mm=10.0, W=100, H=100, invert_y=0))
+            dev.gcode_to_steps(None, None, dict(scale_x=1.0, scale_y=1.0, offset_x_mm=0.0, offset_y_mm=0.0, steps_per_mm=10.0, W=100, H=100, invert_y=0), n=1)
     assert dev.svg_flatten(T([0, 0, 0, 0, 65536.0 ** 2, 0, 65536.0 ** 2, 0]), 0.25) == 65537   # exactly 2^16 pieces pass
     with pytest.raises(OripError):
         dev.svg_flatten(T([0, 0, 0, 0, np.nextafter(65536.0 ** 2, np.inf), 0, 0, 0]), 0.25)
@@ -180,13 +180,13 @@ def test_resident_hand_off(dev):
         dev.svg_flatten(t, 0.02)
         dev.svg_fit(1.4, 1.4, 12.0, -3.0)
         off, pts = dev.svg_paths()
-        a = dev.gcode_to_steps_resident(t.n_sub, mm)
+        a = dev.gcode_to_steps(None, None, mm, n=t.n_sub)
         order = dev.gcode_order(None, len(a[0]) - 1)
         b = dev.gcode_to_steps(off, pts, mm)
         assert len(a[0]) > 5 and same(a, b) and np.array_equal(order, dev.gcode_order(np.concatenate([b[1][b[0][:-1]], b[1][b[0][1:] - 1]], 1)))
         assert same(dev.svg_paths(), (off, pts))                                            # the fitted paths are still there
     with pytest.raises(OripError):
-        dev.gcode_to_steps_resident(t.n_sub + 1, m)
+        dev.gcode_to_steps(None, None, m, n=t.n_sub + 1)
     with pytest.raises(OripError):                                                          # one pointer alone is neither form
         dev._ck(dev.L.orip_gcode_to_steps(dev.h, None, pts.ctypes.data_as(C.c_void_p), t.n_sub, C.byref(GcodeMap(**m)), C.byref(C.c_int64(0)), C.byref(C.c_int64(0))))
 

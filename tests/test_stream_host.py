@@ -1,13 +1,15 @@
-"""Host logic of the plotter stream (orip/stream.py: speed plans, corner flags, byte assembly, colour remap) against bytes produced by the
-REFERENCE's own 13_build_stream.py / stream helper (tests/golden/golden_stream.npz, make_golden_stream.py).  CPU only: the direction codes come
-from the numpy test double (tests/stream_double.py), which the first test pins to the reference's bresenham_dir_codes."""
+"""Host logic of the plotter stream (orip/stream.py: the flat planner, speed plans, corner flags, byte layout, colour remap) against bytes produced by
+the REFERENCE's own 13_build_stream.py / stream helper (tests/golden/golden_stream.npz, golden_stream_edges.npz, make_golden_stream.py).  CPU only: the
+direction codes come from the numpy test double (tests/stream_double.py), which the first test pins to the reference's bresenham_dir_codes, the bytes from
+the doubles' two packers (gcode_double.pack_numpy, stream_double.fill_bytes)."""
 import json
 
 import numpy as np
 import pytest
 
 from util import load
-from stream_double import codes_numpy
+from stream_double import codes_numpy, fill_bytes
+from gcode_double import pack_numpy
 
 G = load("golden_stream.npz")
 
@@ -22,38 +24,35 @@ def test_double_matches_reference_bresenham():
     assert np.array_equal(off, G["bres_off"]) and np.array_equal(codes, G["bres_codes"])
 
 
-def _one_move(ST, move, plan, sc):
-    P = ST._Plot(); P.move(*move, plan)
-    off, codes = codes_numpy(np.array([move]))
-    return np.frombuffer(ST.assemble(P, off, codes, sc), np.uint8)
+def _bytes(ST, P, sc, pack_fn=pack_numpy, initial_div=None):
+    data, _, _ = ST.compile_plan(P, sc, codes_fn=codes_numpy, pack_fn=pack_fn, initial_div=initial_div)
+    return np.frombuffer(data, np.uint8)
 
 
 def test_travel_ramps_match_reference():
     ST = _st(); sc = ST.StreamConfig()
     for i, m in enumerate(G["travel_moves"]):
         want = G["travel_bytes"][G["travel_off"][i]:G["travel_off"][i + 1]]
-        got = _one_move(ST, tuple(int(v) for v in m), lambda n: ST.plan_travel(n, sc), sc)
+        got = _bytes(ST, ST.fixed_plan([-1], [m]), sc)
         assert np.array_equal(got[:len(want)], want) and got[len(want)] == 0x3F, (i, m)
 
 
 @pytest.mark.parametrize("profile", ["triangle", "scurve"])
 def test_polylines_with_corners_match_reference(profile):
+    """every recorded polyline as one line op through the planner, from a cursor on its first point: pen down, exactly the bytes emit_polyline
+    wrote (the first of them the speed byte, as in a fresh writer), pen up, the end byte"""
     ST = _st(); sc = ST.StreamConfig(profile=profile, div_start=25, corner_div=30, corner_window_steps=800)
     off, pts = G["poly_off"], G["poly_pts"]
     for i in range(len(off) - 1):
         pl = pts[off[i]:off[i + 1]].astype(np.int64)
         want = G[f"poly_{profile}_bytes"][G[f"poly_{profile}_off"][i]:G[f"poly_{profile}_off"][i + 1]]
-        P = ST._Plot()
-        sin, sout = ST.corner_flags(pl, sc.corner_deg)
-        for j in range(len(pl) - 1):
-            P.move(pl[j, 0], pl[j, 1], pl[j + 1, 0], pl[j + 1, 1], None if not (sin[j] or sout[j]) else (lambda n, a=bool(sin[j]), b=bool(sout[j]): ST.plan_segment(n, sc, a, b)))
-        o, c = codes_numpy(np.asarray(P.moves, np.int64).reshape(-1, 4))
-        got = np.frombuffer(ST.assemble(P, o, c, sc), np.uint8)
-        assert np.array_equal(got[:len(want)], want) and got[len(want)] == 0x3F, (profile, i)
+        P = ST.plan_ops([0, len(pl)], pl, [False], pl[0], [], False, sc)
+        assert len(P.moves) == len(pl) - 1 and not P.is_travel.any()
+        got = _bytes(ST, P, sc)
+        assert got[0] == ST.PEN_DOWN and np.array_equal(got[1:1 + len(want)], want) and got[1 + len(want)] == ST.PEN_UP and got[2 + len(want)] == 0x3F, (profile, i)
 
 
-def _layers_from_e2e(tag):
-    E = load(f"golden_e2e_{tag}.npz")
+def _layers_from(E):
     cfg = json.loads(bytes(E["cfg_json"]).decode()); man = json.loads(bytes(E["manifest_json"]).decode())
     layers = []
     for L in man["layers"]:
@@ -65,23 +64,57 @@ def _layers_from_e2e(tag):
     return cfg, layers
 
 
-@pytest.mark.parametrize("tag", ["a", "b"])
-@pytest.mark.parametrize("variant", ["", "_remap", "_env"])
-def test_whole_stream_matches_reference(tag, variant, monkeypatch):
-    ST = _st()
-    from orip.config import Config, canvas_size_px
-    cfgd, layers = _layers_from_e2e(tag)
-    extra = json.loads(bytes(G[f"e2e_{tag}{variant}_cfg"]).decode())
+def _layers_from_e2e(tag):
+    return _layers_from(load(f"golden_e2e_{tag}.npz"))
+
+
+def _pipeline_config(cfgd):
+    from orip.config import Config
     cfg = Config()
-    for k, v in {**cfgd, **extra}.items():
+    for k, v in cfgd.items():
         if k in Config.__dataclass_fields__:
             setattr(cfg, k, v)
+    return cfg
+
+
+@pytest.mark.parametrize("pack_fn", [pack_numpy, fill_bytes])
+@pytest.mark.parametrize("tag", ["a", "b"])
+@pytest.mark.parametrize("variant", ["", "_remap", "_env"])
+def test_whole_stream_matches_reference(tag, variant, pack_fn, monkeypatch):
+    ST = _st()
+    from orip.config import canvas_size_px
+    cfgd, layers = _layers_from_e2e(tag)
+    extra = json.loads(bytes(G[f"e2e_{tag}{variant}_cfg"]).decode())
+    cfg = _pipeline_config({**cfgd, **extra})
     if variant == "_env":
         monkeypatch.setenv("STREAM_FORCE_COLOR_INDEX", "6")
     W, H = canvas_size_px(cfg)
-    data, meta = ST.build_stream(layers, W, H, ST.stream_config_from_pipeline(cfg), codes_fn=codes_numpy, color_maps=ST.load_color_maps(cfg))
+    data, meta = ST.build_stream(layers, W, H, ST.stream_config_from_pipeline(cfg), codes_fn=codes_numpy, pack_fn=pack_fn, color_maps=ST.load_color_maps(cfg))
     want = bytes(G[f"e2e_{tag}{variant}_bin"])
     assert data == want
     wj = json.loads(bytes(G[f"e2e_{tag}{variant}_json"]).decode())
     assert meta["lines"] == wj["lines"] and meta["taps"] == wj["taps"] and meta["bytes"] == wj["bytes"] and wj["target_steps"] == {"width": W, "height": H}
     assert len(data) % 1024 == 0
+
+
+def edge_plot():
+    """the hand-written plot of golden_stream_edges.npz (make_golden_stream.py: edge_layers): (layers, W, H, stream config, colour maps, bytes, counts)"""
+    ST = _st()
+    from orip.config import canvas_size_px
+    E = load("golden_stream_edges.npz")
+    cfgd, layers = _layers_from(E)
+    cfg = _pipeline_config(cfgd)
+    W, H = canvas_size_px(cfg)
+    return layers, W, H, ST.stream_config_from_pipeline(cfg), ST.load_color_maps(cfg), bytes(E["bin"]), json.loads(bytes(E["json"]).decode())
+
+
+@pytest.mark.parametrize("pack_fn", [pack_numpy, fill_bytes])
+def test_edge_plot_matches_reference(pack_fn):
+    """an empty layer, an approach to a one-point line that is then skipped, taps with and without a travel, a line that starts on the cursor, a
+    repeated point, half-integer rounding, clamping that merges points, a one-step travel, a colour byte with no approach: 21 moves"""
+    ST = _st()
+    layers, W, H, sc, maps, want, wj = edge_plot()
+    data, meta = ST.build_stream(layers, W, H, sc, codes_fn=codes_numpy, pack_fn=pack_fn, color_maps=maps)
+    assert data == want
+    assert meta == {"lines": wj["lines"], "taps": wj["taps"], "bytes": wj["bytes"]} and wj["target_steps"] == {"width": W, "height": H}
+    assert (meta["lines"], meta["taps"], len(data)) == (9, 5, 4096)

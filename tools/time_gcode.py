@@ -3,8 +3,8 @@
             build_stream_from_gcode, and the whole script on the same file as a child process
   order   : the order kernel alone at several sizes of uniformly spread paths (call time, k_gc_chain time, time per step) and for a star
             (every path starts on one point); at --check-size the result is compared with the numpy definition (tests/gcode_double.py)
-  pack    : orip_stream_pack + the fetch of the bytes against orip_stream_codes_fetch + orip.stream.fill_bytes (what assemble does) on one
-            piece table of about --pack-steps steps
+  pack    : orip_stream_pack + the fetch of the bytes on one piece table of about --pack-steps steps, next to orip_stream_codes with and without
+            the fetch of the codes
 usage: python tools/time_gcode.py [--paths N] [--order-sizes 25000,50000,...] [--star N] [--pack-steps N] [--skip whole,order,pack] [--out FILE.json]"""
 import argparse
 import json
@@ -90,22 +90,20 @@ def main():
             nm = max(1, a.pack_steps // 5000)
             p = np.stack([rng.integers(0, 8400, nm + 1), rng.integers(0, 11880, nm + 1)], 1)
             moves = np.concatenate([p[:-1], p[1:]], 1).astype(np.int32)
-            P = GC.Plan(moves, np.r_[[ST.PEN_UP], np.full(nm, -1)].astype(np.int64), np.ones(nm, bool), np.zeros(nm, bool), np.zeros(nm, bool))
-            t0 = time.perf_counter(); off, _ = dev.stream_codes_resident(moves); t_codes = time.perf_counter() - t0
-            t0 = time.perf_counter(); pm, pd, pc = GC.plan_pieces(P, np.diff(off), sc); table = ST.layout(P.kind, pm, pd, pc, off); t_plan = time.perf_counter() - t0
-            dev.stream_pack(table)                                   # buffers, code objects
+            P = ST.fixed_plan(np.r_[[ST.PEN_UP], np.full(nm, -1)], moves)
+            tm = {}; clk = [time.perf_counter()]
+
+            def lap(name):
+                t1 = time.perf_counter(); tm[name] = t1 - clk[0]; clk[0] = t1
+            _, table, off = ST.compile_plan(P, sc, dev, lap=lap)       # its pack is the warm-up: buffers, code objects
+            t_codes, t_plan = tm["codes"], tm["plan"]
             t = []
             for _ in range(a.reps):
                 t0 = time.perf_counter(); data = dev.stream_pack(table); t.append(time.perf_counter() - t0)
             dev.prof_reset(); dev.prof_enable(True); dev.stream_pack(table); dev.prof_enable(False)
             r = {"steps": int(off[-1]), "pieces": len(table.pos), "bytes": len(data), "codes_s": t_codes, "plan_s": t_plan, "pack_and_fetch_s_median": float(np.median(t)),
                  "k_pk_bytes_ms": dev.prof_get("k_pk_bytes")[0]}
-            t0 = time.perf_counter(); off2, codes = dev.stream_codes(moves); r["codes_with_fetch_s"] = time.perf_counter() - t0
-            try:
-                t0 = time.perf_counter(); data2 = ST.fill_bytes(table, codes); r["numpy_fill_bytes_s"] = time.perf_counter() - t0
-                r["equal"] = bool(data2 == data)
-            except MemoryError:
-                r["numpy_fill_bytes_s"] = None; r["equal"] = None
+            t0 = time.perf_counter(); dev.stream_codes(moves); r["codes_with_fetch_s"] = time.perf_counter() - t0
             res["pack"] = r; print("pack", json.dumps(r), flush=True)
         if "whole" not in skip:
             t0 = time.perf_counter(); text = synth_gcode(a.paths); t_gen = time.perf_counter() - t0

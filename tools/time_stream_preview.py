@@ -27,7 +27,7 @@ def bench_stream(size=4096, K=8):
         ops = S.run_path(img, cfg, dev)
         W, H = canvas_size_px(cfg)
         layers = [(n, i, ops[n]) for i, n in enumerate(cfg.color_names)]
-        data, _ = ST.build_stream(layers, W, H, ST.stream_config_from_pipeline(cfg), codes_fn=dev.stream_codes, color_maps=ST.load_color_maps(cfg))
+        data, _ = ST.build_stream(layers, W, H, ST.stream_config_from_pipeline(cfg), color_maps=ST.load_color_maps(cfg), device=dev)
     finally:
         dev.close()
     return data, cfg

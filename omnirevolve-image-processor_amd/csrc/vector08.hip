@@ -322,9 +322,11 @@ __device__ __forceinline__ int64_t ub_u32v(const unsigned* a, int64_t n, unsigne
     while (lo < hi) { int64_t mid = (lo + hi) >> 1; if (a[mid] <= v) lo = mid + 1; else hi = mid; }
     return lo;
 }
-struct SampleArrs { double* sx; double* sy; double* dprev; int* xi; int* yi; unsigned* rank; uint8_t* inc; };
-// 32-bit cell key (column, row) of the point hash (A5); computed while the samples are produced
-__device__ __forceinline__ unsigned cell_key32(long long cx, long long cy) { return ((unsigned)((cx + 32768) & 0xffff) << 16) | (unsigned)((cy + 32768) & 0xffff); }
+// One record per sample.  sx, sy: the float64 position; dprev: distance to the predecessor on the same polyline; spt: the position truncated to integers (what a
+// surviving sample contributes to the cleaned line); pxy: the rounded pixel as x | y << 16 inside the canvas (W, H <= 16383), ORIP_PXY_OUT off it -- an
+// off-canvas sample's pixel is never read, every consumer tests the sentinel first; rank: the polyline, in processing order.
+#define ORIP_PXY_OUT 0xffffffffu
+struct SampleArrs { double* sx; double* sy; double* dprev; int2* spt; unsigned* pxy; unsigned* rank; };
 // rank (polyline) and segment of sample g, as k_samples needs them.  Both are monotone in g, so the values of the first sample of a
 // 256-sample block and of the next block bound the searches of every sample in between: k_sample_hints does the two full binary
 // searches once per block, k_samples only searches between the hints (mostly zero to a few steps instead of ~28 dependent loads).
@@ -356,21 +358,29 @@ __global__ __launch_bounds__(256) void k_sample_hints(const int64_t* __restrict_
     if (!ri.pass) k = sample_seg(cum + off[i], ri.n_eff, (double)sample_t(g - sbase[r], step), -1, ri.n_eff - 2);
     hints[b] = make_int2((int)r, (int)k);
 }
+// LDS slot of a block's s-th staged sample.  A producer thread t writes samples 4t .. 4t + 3, so a wave's write of 8-byte values would fall on 8 banks' worth of
+// addresses (threads t, t + 8, ... on the same bank), of 4-byte values on 16.  Exchanging the four slots of a thread by bits of t spreads them over all banks at
+// no cost in space; the consumers' consecutive reads stay consecutive within every group of four.
+__device__ __forceinline__ unsigned smp_slot8(unsigned s) { return s ^ ((s >> 5) & 3u); }      // t >> 3
+__device__ __forceinline__ unsigned smp_slot4(unsigned s) { return s ^ ((s >> 6) & 3u); }      // t >> 4
 template <class Src>
 __global__ __launch_bounds__(256) void k_samples(Src src, const int64_t* __restrict__ cumoff, const float* __restrict__ cum,
                                                   const RsInfo* __restrict__ info, const unsigned* __restrict__ ord, const unsigned* __restrict__ sbase, int64_t n_rank,
-                                                  unsigned MS, double step, int W, int H, SampleArrs A, double inv_cell, unsigned* __restrict__ ckeys, unsigned* __restrict__ cvals,
+                                                  unsigned MS, double step, int W, int H, SampleArrs A,
                                                   const int2* __restrict__ hints, unsigned nhb, unsigned long long* __restrict__ pixbits, int Wq, unsigned* __restrict__ firstseq) {
     // FOUR consecutive samples per thread.  A sample costs a chain of ~18 dependent loads (rank, polyline, a bisection of its cumulative lengths, the
     // segment's end points), and with one sample per thread the kernel sat at 1.5 TB/s with every wave slot taken.  Consecutive samples of a polyline
     // lie a few segments apart (8 px of arc length against segments of 2 .. 3 px), so the second to fourth find their segment with ONE round of eight
-    // independent loads from where the previous one stood, and their predecessor (the tail bookkeeping's distance, 08:141,147) is in registers.
+    // independent loads from where the previous one stood.
+    // The threads leave position and polyline of their samples in LDS; after the barrier thread t takes the block's samples t, t + 256, t + 512, t + 768, derives
+    // the rest of the record (distance to the predecessor, truncated point, pixel) from the staged positions and stores it: every store instruction of a wave
+    // writes 64 consecutive elements (stored straight from the producers it wrote 64 elements at a stride of four).
     constexpr int S = 4;
-    __shared__ double shx[256], shy[256];                  // the thread's last sample: the predecessor of the next thread's first one
+    constexpr unsigned NS = 256 * S;
+    __shared__ double shx[NS], shy[NS], shp[2];            // [smp_slot8(s)]: sample s of the block; shp: the predecessor of sample 0
+    __shared__ unsigned shr[NS];                           // [smp_slot4(s)]: its rank, bit 31: first sample of its polyline
     const unsigned g0 = (blockIdx.x * 256 + threadIdx.x) * S;
-    const bool act = g0 < MS;
-    double x0 = 0.0, y0 = 0.0, xl = 0.0, yl = 0.0; unsigned j0 = 0;
-    if (act) {
+    if (g0 < MS) {
         const unsigned hb = g0 >> 8;                       // hints: rank and segment of every 256th sample (k_sample_hints)
         const int2 h0 = hints[hb];
         const bool last = hb + 1 == nhb;
@@ -380,8 +390,7 @@ __global__ __launch_bounds__(256) void k_samples(Src src, const int64_t* __restr
         auto cu = src.cur(i); const float* s = cum + cumoff[i];
         RsInfo ri = info[i];
         int64_t kprev = -2;                                // segment of the previous sample of this polyline taken by this thread (-2: none)
-        double px = 0.0, py = 0.0;
-        j0 = j;
+        const unsigned j0 = j;
         // position of sample jj of the current polyline, its segment known to lie in [klo, khi]
         auto pos_at = [&](int64_t k, double t, double& ox, double& oy) {
             double sk = (double)s[k], sk1 = (double)s[k + 1];
@@ -426,43 +435,44 @@ __global__ __launch_bounds__(256) void k_samples(Src src, const int64_t* __restr
                 kprev = k;
                 pos_at(k, t, x, y);
             }
-            long long xi = vs::round_half_even(x), yi = vs::round_half_even(y);
-            A.sx[g] = x; A.sy[g] = y; A.rank[g] = (unsigned)r;
-            bool in = xi >= 0 && yi >= 0 && xi < W && yi < H;
-            A.xi[g] = (int)xi; A.yi[g] = (int)yi; A.inc[g] = in ? 1 : 0;
-            if (pixbits && in) {       // the canvas is read at sample pixels only (k_caps_stamp_bits): mark the pixel, give it its "never stamped" value
-                unsigned long long* wp = &pixbits[(size_t)yi * Wq + (xi >> 6)]; const unsigned long long bit = 1ULL << (xi & 63);
-                if (!(*wp & bit) && !(atomicOr(wp, bit) & bit)) firstseq[(size_t)yi * W + xi] = 0xffffffffu;      // whoever sets the bit initialises the pixel: one write per distinct pixel, not per sample
-            }
-            if (ckeys) { ckeys[g] = cell_key32((long long)floor(__dmul_rn(x, inv_cell)), (long long)floor(__dmul_rn(y, inv_cell))); cvals[g] = g; }
-            // distance to the predecessor on the same polyline, exactly as the tail bookkeeping evaluates it (08:141,147)
-            if (j == 0) A.dprev[g] = 0.0;
-            else if (u > 0) A.dprev[g] = vs::norm2_f64(x - px, y - py);
-            else { x0 = x; y0 = y; }                       // the predecessor is the previous thread's last sample: after the barrier
-            px = x; py = y; xl = x; yl = y;
+            const unsigned ls = threadIdx.x * S + (unsigned)u;
+            shx[smp_slot8(ls)] = x; shy[smp_slot8(ls)] = y;
+            shr[smp_slot4(ls)] = (unsigned)r | (j == 0 ? 0x80000000u : 0u);
             j++;
         }
-        if (j0 > 0 && threadIdx.x == 0) {                  // the first thread of a block computes its predecessor again
+        if (j0 > 0 && threadIdx.x == 0) {                  // the block's first sample continues a polyline: its predecessor, computed again
             // (the loop above has moved on: look the polyline of sample g0 up again)
             int64_t r2 = sample_rank(sbase, info, ord, h0.x + 1, (int64_t)h1.x + 1, g0);
             const unsigned i2 = ord[r2]; cu = src.cur(i2); s = cum + cumoff[i2]; ri = info[i2];
             double qx, qy;
             if (ri.pass) { const int2 q = cu.at(j0 - 1); qx = (double)(float)q.x; qy = (double)(float)q.y; }
             else { const double t = (double)sample_t(j0 - 1, step); pos_at(sample_seg(s, ri.n_eff, t, -1, ri.n_eff - 2), t, qx, qy); }
-            A.dprev[g0] = vs::norm2_f64(x0 - qx, y0 - qy);
+            shp[0] = qx; shp[1] = qy;
         }
     }
-    shx[threadIdx.x] = xl; shy[threadIdx.x] = yl;
     __syncthreads();
-    if (act && j0 > 0 && threadIdx.x > 0) A.dprev[g0] = vs::norm2_f64(x0 - shx[threadIdx.x - 1], y0 - shy[threadIdx.x - 1]);
-}
-
-// distance of every sample to its predecessor on the same polyline, exactly as the tail bookkeeping evaluates it (08:141,147)
-__global__ __launch_bounds__(256) void k_sample_dist(const unsigned* __restrict__ sbase, unsigned MS, SampleArrs A) {
-    unsigned g = blockIdx.x * 256 + threadIdx.x;
-    if (g >= MS) return;
-    unsigned b = sbase[A.rank[g]];
-    A.dprev[g] = (g > b) ? vs::norm2_f64(A.sx[g] - A.sx[g - 1], A.sy[g] - A.sy[g - 1]) : 0.0;
+    const unsigned b0 = blockIdx.x * NS;
+#pragma unroll
+    for (int u = 0; u < S; u++) {
+        const unsigned ls = threadIdx.x + 256u * (unsigned)u, g = b0 + ls;
+        if (g >= MS) break;
+        const unsigned at = smp_slot8(ls);
+        const double x = shx[at], y = shy[at];
+        const unsigned rw = shr[smp_slot4(ls)];
+        // distance to the predecessor on the same polyline, exactly as the tail bookkeeping evaluates it (08:141,147)
+        double d = 0.0;
+        if (!(rw >> 31)) { const unsigned before = smp_slot8(ls ? ls - 1u : 0u); d = vs::norm2_f64(x - (ls ? shx[before] : shp[0]), y - (ls ? shy[before] : shp[1])); }
+        A.dprev[g] = d;
+        A.sx[g] = x; A.sy[g] = y; A.rank[g] = rw & 0x7fffffffu;
+        A.spt[g] = make_int2((int)x, (int)y);
+        const long long xi = vs::round_half_even(x), yi = vs::round_half_even(y);
+        const bool in = xi >= 0 && yi >= 0 && xi < W && yi < H;
+        A.pxy[g] = in ? ((unsigned)xi | ((unsigned)yi << 16)) : ORIP_PXY_OUT;
+        if (pixbits && in) {       // the canvas is read at sample pixels only (k_caps_stamp_bits): mark the pixel, give it its "never stamped" value
+            unsigned long long* wp = &pixbits[(size_t)yi * Wq + (xi >> 6)]; const unsigned long long bit = 1ULL << (xi & 63);
+            if (!(*wp & bit) && !(atomicOr(wp, bit) & bit)) firstseq[(size_t)yi * W + xi] = 0xffffffffu;      // whoever sets the bit initialises the pixel: one write per distinct pixel, not per sample
+        }
+    }
 }
 
 // ================================================================= A3: tail simulation (08:139-155)
@@ -607,13 +617,13 @@ __global__ __launch_bounds__(256) void k_tail_par(const unsigned* __restrict__ s
 // previous in-canvas sample of the same polyline (the far end of the capsule stamped when sample j is popped, 08:151-155); -1: none, -2: j is off-canvas
 // lastin[g] = 1 + index of the last in-canvas sample at or before g inside its polyline (0: none): a max-scan by polyline
 struct IncIndex {
-    const uint8_t* inc;
-    __device__ unsigned operator()(unsigned g) const { return inc[g] ? g + 1u : 0u; }
+    const unsigned* pxy;
+    __device__ unsigned operator()(unsigned g) const { return pxy[g] != ORIP_PXY_OUT ? g + 1u : 0u; }
 };
 __global__ __launch_bounds__(256) void k_capprev(const unsigned* __restrict__ sbase, unsigned MS, SampleArrs A, const unsigned* __restrict__ lastin, int* __restrict__ capprev) {
     unsigned g = blockIdx.x * 256 + threadIdx.x;
     if (g >= MS) return;
-    if (!A.inc[g]) { capprev[g] = -2; return; }
+    if (A.pxy[g] == ORIP_PXY_OUT) { capprev[g] = -2; return; }
     const unsigned b = sbase[A.rank[g]];
     const unsigned l = g > b ? lastin[g - 1] : 0u;
     capprev[g] = l ? (int)(l - 1u - b) : -1;
@@ -650,11 +660,15 @@ __global__ __launch_bounds__(256) void k_caps_insert(SampleArrs A, const unsigne
         cp[u] = !on[u] ? -1 : (capprev ? capprev[g[u]] : (g[u] > bb[u] ? (int)(g[u] - bb[u]) - 1 : -1));      // capprev == nullptr: every sample is on the canvas, so the capsule runs from the previous sample
         on[u] = cp[u] >= 0;
     }
-    unsigned long long key[S], h[S];
+    unsigned long long key[S], h[S]; unsigned pa[S], pb[S];
 #pragma unroll
     for (int u = 0; u < S; u++) {
-        key[u] = 0; h[u] = 0;
-        if (on[u]) { key[u] = cap_key(A.xi[bb[u] + cp[u]], A.yi[bb[u] + cp[u]], A.xi[g[u]], A.yi[g[u]]); h[u] = hash64(key[u]) & tmask; }
+        key[u] = 0; h[u] = 0; pa[u] = 0; pb[u] = 0;
+        if (on[u]) pa[u] = A.pxy[bb[u] + cp[u]], pb[u] = A.pxy[g[u]];      // both on the canvas (cp >= 0): packed pixels
+    }
+#pragma unroll
+    for (int u = 0; u < S; u++) {
+        if (on[u]) { key[u] = cap_key((int)(pa[u] & 0xffffu), (int)(pa[u] >> 16), (int)(pb[u] & 0xffffu), (int)(pb[u] >> 16)); h[u] = hash64(key[u]) & tmask; }
     }
     uint4 sl[S];
 #pragma unroll
@@ -730,7 +744,7 @@ __global__ __launch_bounds__(256) void k_cell_keys(SampleArrs A, unsigned MS, do
 // and collects the survivors; the hash-bucket searches (dozens of dependent loads) then run over the dense survivor list, so a wave
 // is not held up by one lane that has to search.
 __global__ __launch_bounds__(256) void k_accept_pre(SampleArrs A, const unsigned* __restrict__ sbase, const unsigned* __restrict__ npop, unsigned MS,
-                                                     const unsigned* __restrict__ firstseq, int W, int2* __restrict__ spt, uint8_t* __restrict__ sflag,
+                                                     const unsigned* __restrict__ firstseq, int W, uint8_t* __restrict__ sflag,
                                                      unsigned* __restrict__ surv, unsigned* __restrict__ n_surv, unsigned long long* __restrict__ work) {
     // four samples per thread, 256 apart (as k_caps_insert: the chains rank -> base and pixel -> canvas word are waited for, not the bandwidth)
     constexpr int S = 4;
@@ -741,7 +755,7 @@ __global__ __launch_bounds__(256) void k_accept_pre(SampleArrs A, const unsigned
 #pragma unroll
     for (int u = 0; u < S; u++) {
         np[u] = 0; xi[u] = 0; yi[u] = 0; ok[u] = false;
-        if (on[u]) { bb[u] = sbase[bb[u]]; ok[u] = A.inc[g[u]] != 0; np[u] = npop[g[u]]; xi[u] = A.xi[g[u]]; yi[u] = A.yi[g[u]]; }
+        if (on[u]) { bb[u] = sbase[bb[u]]; const unsigned p = A.pxy[g[u]]; ok[u] = p != ORIP_PXY_OUT; np[u] = npop[g[u]]; xi[u] = (int)(p & 0xffffu); yi[u] = (int)(p >> 16); }
     }
     unsigned fs[S];
 #pragma unroll
@@ -755,7 +769,6 @@ __global__ __launch_bounds__(256) void k_accept_pre(SampleArrs A, const unsigned
             const unsigned limit = bb[u] + np[u];         // own samples with global index < limit have been popped (hashed + stamped)
             bool k = ok[u];
             if (k && fs[u] < limit) k = false;
-            spt[g[u]] = make_int2((int)A.sx[g[u]], (int)A.sy[g[u]]);
             sflag[g[u]] = (k ? 1 : 0) | (j == 0 ? 2 : 0);
             need = k && np[u] > 0; mynp = need ? np[u] : 0u;
         }
@@ -1561,8 +1574,8 @@ static int dedup08_a(orip_ctx* c, int layer, const orip_params08& P, DPolys& S, 
         if (MS > 0) {
             if (MS > 0x7ffffff0u) ORIP_FAIL(c, "too many samples");
             if (T.on) { char b[48]; snprintf(b, sizeof b, " [MS %u]", MS); T.log += b; }
-            SampleArrs A; unsigned* npop; int* capprev; int2* spt; uint8_t* sflag;
-            { Carve L; L.each(MS, A.sx, A.sy, A.dprev, A.xi, A.yi, A.rank, npop, capprev, spt, A.inc, sflag); HIPC(c, L.commit(LN(c).vtmp[3], 1024)); }
+            SampleArrs A; unsigned* npop; int* capprev; uint8_t* sflag;
+            { Carve L; L.each(MS, A.sx, A.sy, A.dprev, A.spt, A.pxy, A.rank, npop, capprev, sflag); HIPC(c, L.commit(LN(c).vtmp[3], 1024)); }
             const unsigned nb = (unsigned)cdiv(MS, 256);
             unsigned *ckin, *ckout, *cvin, *cvout; int2* hints;
             { Carve L; L.each(MS, ckin, ckout, cvin, cvout); L.take(hints, nb + 1, 64);
@@ -1576,7 +1589,7 @@ static int dedup08_a(orip_ctx* c, int layer, const orip_params08& P, DPolys& S, 
             unsigned long long* pixbits = LN(c).pixbits.as<unsigned long long>();
             HIPC(c, hipMemsetAsync(pixbits, 0, (size_t)Wq * H * 8, LN(c).stream));
             hipLaunchKernelGGL(k_sample_hints, dim3(cdiv(nb, 256)), dim3(256), 0, LN(c).stream, cumoff, cum, info, ord, sbase, nk, MS, step, nb, hints);
-            { ProfScope ps(c, "k_samples"); ORIP_WITH_SRC(c, kept0, sv, { hipLaunchKernelGGL(k_samples<decltype(sv)>, dim3(cdiv(nb, 4)), dim3(256), 0, LN(c).stream, sv, cumoff, cum, info, ord, sbase, nk, MS, step, W, H, A, inv, (unsigned*)nullptr, (unsigned*)nullptr, hints, (unsigned)nb, pixbits, Wq, firstseq); }); }
+            { ProfScope ps(c, "k_samples"); ORIP_WITH_SRC(c, kept0, sv, { hipLaunchKernelGGL(k_samples<decltype(sv)>, dim3(cdiv(nb, 4)), dim3(256), 0, LN(c).stream, sv, cumoff, cum, info, ord, sbase, nk, MS, step, W, H, A, hints, (unsigned)nb, pixbits, Wq, firstseq); }); }
             T.tick("samples");
             // ---- A3
             {
@@ -1596,7 +1609,7 @@ static int dedup08_a(orip_ctx* c, int layer, const orip_params08& P, DPolys& S, 
             if (any_out)
             {
                 unsigned* lastin = LN(c).vtmp[8].as<unsigned>();            // MS words over S: the prefix sums of the tail simulation are no longer needed
-                auto vin = rocprim::make_transform_iterator(rocprim::counting_iterator<unsigned>(0u), IncIndex{A.inc});
+                auto vin = rocprim::make_transform_iterator(rocprim::counting_iterator<unsigned>(0u), IncIndex{A.pxy});
                 HIPC(c, orip_with_tmp(c, [&](void* tmp, size_t& bytes) { return rocprim::inclusive_scan_by_key(tmp, bytes, A.rank, vin, lastin, (size_t)MS, rocprim::maximum<unsigned>(), rocprim::equal_to<unsigned>(), LN(c).stream); }));
                 hipLaunchKernelGGL(k_capprev, dim3(cdiv(MS, 256)), dim3(256), 0, LN(c).stream, sbase, MS, A, lastin, capprev);
             }
@@ -1638,7 +1651,7 @@ static int dedup08_a(orip_ctx* c, int layer, const orip_params08& P, DPolys& S, 
                 unsigned* d_ns = &fl->accept_survivors; unsigned long long* d_work = &fl->accept_work;
                 HIPC(c, hipMemsetAsync(d_ns, 0, 4, LN(c).stream));
                 HIPC(c, hipMemsetAsync(d_work, 0, 8, LN(c).stream));
-                { ProfScope ps(c, "k_accept"); hipLaunchKernelGGL(k_accept_pre, dim3(cdiv(MS, 1024)), dim3(256), 0, LN(c).stream, A, sbase, npop, MS, firstseq, W, spt, sflag, surv, d_ns, d_work); }
+                { ProfScope ps(c, "k_accept"); hipLaunchKernelGGL(k_accept_pre, dim3(cdiv(MS, 1024)), dim3(256), 0, LN(c).stream, A, sbase, npop, MS, firstseq, W, sflag, surv, d_ns, d_work); }
                 unsigned long long h_work = 0; ORIP_TRY(vread(c, &h_work, d_work));
                 const double R2 = P.col_rad * P.col_rad;
                 // without the hash when it gives the hash's answer (cell >= radius) and costs less than sorting every sample into buckets
@@ -1657,7 +1670,7 @@ static int dedup08_a(orip_ctx* c, int layer, const orip_params08& P, DPolys& S, 
             }
             HIPC(c, hipGetLastError());
             T.tick("accept");
-            ORIP_TRY(orip_runs_to_polys(c, spt, sflag, MS, cleaned));
+            ORIP_TRY(orip_runs_to_polys(c, A.spt, sflag, MS, cleaned));
             T.tick("runs");
         }
         // ---- A7

@@ -66,3 +66,15 @@ def compare_ops(ops, want_ops, names):
                 assert (a["x"], a["y"]) == (b["x"], b["y"]), n
     dg, tg = O.path_length(ops); dw, tw = O.path_length(want_ops)
     assert abs(dg + tg - dw - tw) <= 1e-3 * (dw + tw)      # north_star: plotted path length within 1e-3 relative
+
+
+def expected_stage02(img, centres, open_iters, close_iters):
+    """stage 02 from explicit centres with any iteration counts, composed from the oracle's parts (O.stage02 fixes the iterations at 1 / 1):
+    (centres sorted dark -> light, labels int64 [H,W], pixels per layer, masks uint8 [K,H,W])"""
+    from oracle import oracle as O
+    cen = np.asarray(centres, np.float32)
+    order = np.argsort(cen[:, 0], kind="stable")
+    lut = np.zeros(len(cen), np.int64); lut[order] = np.arange(len(cen))
+    labels = lut[O.assign(O.bgr2lab(img), cen)]
+    masks = np.stack([O.morph_open_close((labels == k).astype(np.uint8) * 255, 0, 3, open_iters, close_iters) for k in range(len(cen))])
+    return cen[order], labels, np.bincount(labels.ravel(), minlength=len(cen)), masks

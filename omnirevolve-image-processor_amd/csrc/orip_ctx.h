@@ -182,18 +182,63 @@ static_assert(sizeof(LaneFlags) <= 4096, "LaneRes::flags is 4096 bytes, allocate
 //   lane l+1 pf08.*              own buffers of Prefetch08; src_off points into the SCALED list's offsets (c->polys), valid while pf08.tag matches the list's pf_tag
 //   ORIP_LANE_CROSS canvas       forbidden raster of stage 10  orip_dedup_cross_begin (cleared there) -> the last orip_dedup_cross_layer* call of that pass
 //   Everything else -- tp[], pixbits, tmpE, canvas on the other lanes, the other vtmp slots, the rest of flags -- is free between entry points.
-enum { VT0_KEYS = 0, VT0_COMP_START = 2, VT0_ORDER = 3, VT0_MEMO = 6, VT0_LOG_USED = 7, VT0_WINFO = 8, VT0_EDGE_BITS = 10,     // lane 0
-       VTL_STEPLOG = 9, VT_LEAVES = 11 };       // layer lanes (VT_LEAVES: wherever vfeatures runs -- its perimeter leaves, and those of the stage-08 prefetch)
+//
+// WITHIN ONE CALL on a layer lane or on ORIP_LANE_CROSS all twelve slots are in use, so they alias on purpose: a slot is free for its next role once the
+// kernels that read its previous one have been enqueued on the lane's stream (one stream: order is enough; where the side stream reads, the table says so).
+// A helper overwrites what it takes, so a caller must not hold those live across the call:
+//   vscan_excl, vsort_pairs, orip_with_tmp   tmpF (vscan_excl only above 32768 items)
+//   vgather, vgather_views, vgather_list     tmpE, tmpF (their scan), dst
+//   vfeatures                                VT_LEAVES, tmpF (only when the list has more than ORIP_LONG_POLY points: the long polylines' leaves and length order)
+//   vreorder                                 VTL_FEAT, flags.nn_seed / nn_dbg2; all of vfeatures and vgather_list; with prefetch08: all of orip_prefetch08
+//   split_small (vector08a.hip)              VTL_SPLIT, VTL_SPLIT_FEAT; all of vfeatures, vscan_excl and vgather_list; waits for ev4 or drains the prefetch
+//   orip_runs_to_polys                       VTL_RUN_STARTS, VTL_TAIL_RUNS; all of vscan_excl and vgather
+//   orip_prefetch08 (side stream)            pf08.*, VT_LEAVES, tmpF (until ev4); READS the caller's features (stage 07's VTL_FEAT) until ev3
+// and every stage holds live, across such calls:
+//   04  (raster04.hip)    on the layer's lane: VTL_STEPLOG trace_launch -> trace_finish (between entry points, see above); inside trace_finish VTL_CAPS (walk sums per
+//                         slot, to k_vwalk_fill) and then VTL_CELLS (kept walk slots); with ORIP_WALK_DBG (debug) also VT_LEAVES: per-component counters,
+//                         trace_launch -> trace_finish.  Calls orip_with_tmp (tmpF) for its scans
+//   07  (vector.hip)      nothing of its own: vreorder's VTL_FEAT is the feat07 the prefetch reads on the side stream until ev3.  Stage 08's A0 fills the same
+//                         slot behind ev4 only; the two meet in practice behind several host round trips of split_small, but no event orders them
+//   08-A (vector08a.hip)  VTL_FEAT A0 -> k_rank_counts (across split_small, vsort_pairs, vscan_excl); VTL_RANKS A1 -> A6; VTL_CUM A2 (k_samples reads it last);
+//                         VTL_SAMPLES, VTL_CELLS, canvas, pixbits A2 -> A6, VTL_SAMPLES on through orip_runs_to_polys (its spt and sflag are the input);
+//                         VTL_TAIL_RUNS A3 -> A6: tail sums (8 MS bytes) and, behind them, redo, which the side stream reads until ev3 (awaited by A5); the
+//                         last-in scan and then the survivors take the first 4 MS bytes only, and orip_runs_to_polys takes the slot once A6 is enqueued;
+//                         VTL_CAPS A4; A7's split_small finds everything but tp[] free
+//   08-B (vector08b.hip)  VTL_FEAT (features, parents, groups) groups -> paths; canvas (group ids) raster -> paths; VTL_STEPLOG (bit planes, skeleton bytes)
+//                         raster -> paths; VTL_SPLIT_FEAT (labels) and VTL_RANKS (block counts) within components; VTL_CUM (sorted pixels), VTL_CAPS (component
+//                         tables) components -> paths; VTL_SAMPLES (heads) within components; VTL_CELLS within paths.  Calls vfeatures (first, into
+//                         VTL_FEAT), vscan_excl, vsort_pairs and, last, vgather
+//   08 C  (vector08.hip)  vreorder of tp[2] or tp[3]: nothing else is live
+//   10  (vector10.hip)    canvas (forbidden raster, across calls) and VTL_STEPLOG (seed / distance planes) for the whole call; VTL_RANKS, VTL_CUM cut ->
+//                         orip_runs_to_polys (VTL_CUM is its input); VTL_SPLIT, VTL_SPLIT_FEAT tiny lines -> the compaction of the taps; VTL_SAMPLES (tap
+//                         sequence) from there to the end, across vreorder
+//   12  (vector.hip)      VTL_FEAT, taken after the deferred vreorder of the layer has finished with it; calls vfeatures
+enum { VT0_KEYS = 0, VT0_HEADS = 1, VT0_COMP_START = 2, VT0_ORDER = 3, VT0_ORDER_SORT = 5, VT0_MEMO = 6, VT0_LOG_USED = 7, VT0_WINFO = 8, VT0_EDGE_BITS = 10,     // lane 0
+       VT0_NMS_BITS = 11 };     // (VT0_HEADS, VT0_ORDER_SORT: component heads / sort buffers inside orip_contours_prepare; VT0_NMS_BITS: candidate and strong planes inside orip_detect_edges)
+// Layer lanes and ORIP_LANE_CROSS.  A name is the slot's role in stage 08-A, or in the helper that owns it; the other roles of the same index, in call order:
+enum { VTL_RANKS = 0,           // 08-A: perimeter sort, order, samples per rank, sample bases, RsInfo | 08-B: skeleton pixels per block | 10: steps per point, their bases
+       VTL_CUM = 1,             // 08-A: cumulative lengths and their offsets | 08-B: skeleton pixels sorted by label | 10: cut steps (points, flags)
+       VTL_SPLIT = 2,           // split_small: tap / keep flags, their scans, tap centres, descriptors | 10: the same for _tiny_and_taps
+       VTL_SAMPLES = 3,         // 08-A: the per-sample arrays (SampleArrs, npop, capprev, sflag) | 08-B: component heads and their scan | 10: tap sequence, accepted taps
+       VTL_CAPS = 4,            // 08-A: capsule table | 08-B: component tables | 04 trace_finish: walk sums per slot
+       VTL_CELLS = 5,           // 08-A: cell keys / values (bucket sort), sample hints | 08-B: per-component path scratch | 04 trace_finish: kept walk slots
+       VTL_FEAT = 6,            // features: 08-A kept polylines | 08-B lines, parents, groups | vreorder (07, 08 C, 10, 12): features, ends, order | 12: features, alive flags
+       VTL_RUN_STARTS = 7,      // orip_runs_to_polys: run starts and their scan
+       VTL_TAIL_RUNS = 8,       // 08-A: tail sums + redo flags -> last-in scan -> survivors, THEN orip_runs_to_polys: run lengths, begins, keep flags, descriptors
+       VTL_STEPLOG = 9,         // 04: step log of the layer's trace (between entry points, see above) | 08-B: skeleton bytes, thinning bit planes | 10: seed, distance, occupancy planes
+       VTL_SPLIT_FEAT = 10,     // split_small: features of its source list | 08-B: union-find labels of the padded raster | 10: features of the cut lines
+       VT_LEAVES = 11,          // wherever vfeatures runs: its perimeter leaves and length order, and those of the stage-08 prefetch (between entry points, see above) | 04 with ORIP_WALK_DBG: per-component debug counters of the trace
+       VT_SLOTS = 12 };
 struct LaneRes {
     hipStream_t stream = 0;
     hipStream_t stream2 = 0;              // side stream of the lane (work that may overlap the main chain), fenced with ev2 / ev3
     hipEvent_t ev2 = nullptr, ev3 = nullptr, ev4 = nullptr;   // (ev4 / ev3: features / everything of stage 08's prefetch)
-    DBuf vtmp[12], tmpE, tmpF, flags, canvas;             // flags: one LaneFlags
+    DBuf vtmp[VT_SLOTS], tmpE, tmpF, flags, canvas;             // flags: one LaneFlags
     DBuf pixbits;                         // stage 08-A: one bit per canvas pixel that is the rounded position of a sample
     unsigned caps_hint = 0;               // distinct capsules of the lane's last stage-08-A run (sizes the next run's table)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     DPolys tp[6];   // persistent temporaries of the vector stages (no hipFree in steady state: hipFree synchronises the device)
-    // stage 08's order-independent front, computed on the side stream while stage 07's greedy chain runs (vector08.hip: orip_prefetch08)
+    // stage 08's order-independent front, computed on the side stream while stage 07's greedy chain runs (vector08a.hip: orip_prefetch08)
     struct Prefetch08 {
         bool pending = false;          // side-stream work the lane's main stream has not waited for yet (orip_pf08_drain)
         bool valid = false; uint64_t tag = 0; int64_t n = 0; int64_t tot_f = 0; double step = 0;
@@ -230,7 +275,7 @@ struct LaneGuard {
 #define ORIP_LANE_NODRAIN(ctx, lane_id)                                                                                      \
     LaneGuard _lane_guard((ctx), (lane_id));                                                                                 \
     if (!_lane_guard.ok) ORIP_FAIL(ctx, "lane %d is busy: another call is using this layer's stream and scratch", (int)(lane_id))
-// Stage 08's prefetch (vector08.hip: orip_prefetch08) may still be running on the lane's side stream when stage 07 returns: stage 08 waits for its parts where it
+// Stage 08's prefetch (vector08a.hip: orip_prefetch08) may still be running on the lane's side stream when stage 07 returns: stage 08 waits for its parts where it
 // consumes them; every other call that claims the lane puts its main stream behind the whole of it first (it reads the scaled list and the lane's scratch).
 #define ORIP_LANE(ctx, lane_id)                                                                                              \
     ORIP_LANE_NODRAIN(ctx, lane_id);                                                                                         \
@@ -346,7 +391,7 @@ int orip_raster02_lab_tables(orip_ctx* c);
 int orip_contours_layer_impl(orip_ctx* c, int layer, bool sync);
 int orip_scale_vectors_impl(orip_ctx* c, int layer, float sx, float sy, float dx, float dy, bool sync);
 int orip_sort_contours_impl(orip_ctx* c, int layer, bool sync, const orip_params08* prm_for_prefetch = nullptr);
-// stage 08's order-independent front on the lane's side stream, called by stage 07 under its greedy chain with the features it has computed (vector08.hip)
+// stage 08's order-independent front on the lane's side stream, called by stage 07 under its greedy chain with the features it has computed (vector08a.hip)
 struct PolyFeat;
 int orip_prefetch08(orip_ctx* c, const orip_params08& prm, DPolys& scaled, const PolyFeat* feat07);
 // explicit points of a walk-coded list (no-op for explicit lists); on the calling lane's stream, not synchronised (vector_common.hip)

@@ -332,7 +332,7 @@ extern "C" int orip_detect_edges(orip_ctx* c, int morph_k, int open_iters, int c
     // computed from words; the edge bit planes stay for stage 04's thinning
     const int Ww = (W + 63) >> 6; const size_t nw = (size_t)H * Ww;
     unsigned long long *cand, *strong, *ebits, *thin2;
-    { Carve L; L.each(nw * K, cand, strong); HIPC(c, L.commit(LN(c).vtmp[11], 64)); }
+    { Carve L; L.each(nw * K, cand, strong); HIPC(c, L.commit(LN(c).vtmp[VT0_NMS_BITS], 64)); }
     HIPC(c, orip_edge_planes(c, nw * K, ebits, thin2));      // (thin2: stage 04's second thinning plane, sized here so that the buffer stays where it is)
     if (nms_from_bits && c->morphed_bits) {
         ProfScope ps(c, "k_blur_sobel_nms");

@@ -160,7 +160,7 @@ __global__ __launch_bounds__(64) void k_vown(WalkArgs A, const unsigned* __restr
 // ---- thinning_zhangsuen (04:35-99) and the state bytes on bit planes: one bit per pixel, 64 pixels per word, blockIdx.z = layer.
 // The reference numbers the neighbours from the south (P2 = (y+1, x), then clockwise as seen with y down: SW, W, NW, N, NE, E, SE);
 // A(p) counts transitions around the same cycle wherever it starts, B(p) is symmetric, only the two product conditions differ from
-// the usual orientation.  Bit-sliced evaluation as in stage 08-B (vector08.hip: zs_word_del).
+// the usual orientation.  Bit-sliced evaluation as in stage 08-B (vector08b.hip: zs_word_del).
 __global__ __launch_bounds__(256) void k_bytes_to_bits04(const u8* __restrict__ src, unsigned long long* __restrict__ bits, int H, int W, int Ww) {
     const size_t nw = (size_t)H * Ww, w0 = ((size_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 64;
     if (w0 >= nw) return;
@@ -499,7 +499,7 @@ extern "C" int orip_contours_prepare(orip_ctx* c) {
     { ProfScope ps(c, "k_compact_write"); hipLaunchKernelGGL(k_compact_write_bits, dim3(nblk), block, 0, LN(c).stream, bA, c->tmpD.as<int>(), nwords, nw, H, W, Ww, d_boff, keys_in, lin_in); }
     { ProfScope ps(c, "radix_sort_pairs"); HIPC(c, orip_with_tmp(c, [&](void* tmp, size_t& bytes) { return rocprim::radix_sort_pairs(tmp, bytes, keys_in, keys, lin_in, lin, (size_t)M, 0, 30, LN(c).stream); })); }
     // ---- component segmentation
-    unsigned *head, *head_scan; { Carve L; L.each(M, head, head_scan); HIPC(c, L.commit(LN(c).vtmp[1], 64)); }
+    unsigned *head, *head_scan; { Carve L; L.each(M, head, head_scan); HIPC(c, L.commit(LN(c).vtmp[VT0_HEADS], 64)); }
     hipLaunchKernelGGL(k_heads, dim3(cdiv(M, 256)), block, 0, LN(c).stream, keys, (int64_t)M, head);
     HIPC(c, orip_with_tmp(c, [&](void* tmp, size_t& bytes) { return rocprim::exclusive_scan(tmp, bytes, (const unsigned*)head, head_scan, 0u, (size_t)M, rocprim::plus<unsigned>(), LN(c).stream); }));
     unsigned last2[2];
@@ -529,7 +529,7 @@ extern "C" int orip_contours_prepare(orip_ctx* c) {
     // per-layer largest-first schedule: components sorted by (layer, size descending); layer l owns order[layer_first[l] .. layer_first[l+1])
     {
         unsigned long long *kin, *kout; unsigned *idin, *idout;
-        { Carve L; L.each(NC, kin, kout, idin, idout); HIPC(c, L.commit(LN(c).vtmp[5], 64)); }
+        { Carve L; L.each(NC, kin, kout, idin, idout); HIPC(c, L.commit(LN(c).vtmp[VT0_ORDER_SORT], 64)); }
         hipLaunchKernelGGL(k_comp_order_keys, dim3(cdiv(NC, 256)), block, 0, LN(c).stream, keys, comp_start, NC, kin, idin);
         HIPC(c, orip_with_tmp(c, [&](void* tmp, size_t& bytes) { return rocprim::radix_sort_pairs(tmp, bytes, kin, kout, idin, idout, (size_t)NC, 0, 40, LN(c).stream); }));
         R.order = LN(c).vtmp[VT0_ORDER].as<unsigned>();
@@ -604,7 +604,7 @@ static int trace_finish(orip_ctx* c, Prep04& R, int layer) {
     // with the totals (an overflowed trace -- rare: the logs hold 64 entries per skeleton pixel -- is redone with larger logs).
     const unsigned nslots = 2u * Ml, sl0 = 2u * b0;
     const size_t ns1 = (size_t)nslots + 1;
-    WSum *ws, *wo; { Carve L; L.each(ns1, ws, wo); HIPC(c, L.commit(LN(c).vtmp[4], 256)); }
+    WSum *ws, *wo; { Carve L; L.each(ns1, ws, wo); HIPC(c, L.commit(LN(c).vtmp[VTL_CAPS], 256)); }
     WalkStore& WS = c->wstore[layer];
     WSum h_tot; unsigned log_shift = 0; WalkArgs A;
     for (;;) {
@@ -655,8 +655,8 @@ static int trace_finish(orip_ctx* c, Prep04& R, int layer) {
     HIPC(c, WS.walk.ensure((size_t)std::max(h_paths, 1u) * sizeof(VWalk) + 64));
     HIPC(c, WS.piece.ensure((size_t)std::max(h_pieces, 1u) * sizeof(VPiece) + 64));
     HIPC(c, WS.own.ensure((size_t)std::max(h_own, 1u) * 8 + 64));
-    HIPC(c, LN(c).vtmp[5].ensure((size_t)std::max(h_paths, 1u) * 4 + 64));
-    unsigned* kept_slots = LN(c).vtmp[5].as<unsigned>();
+    HIPC(c, LN(c).vtmp[VTL_CELLS].ensure((size_t)std::max(h_paths, 1u) * 4 + 64));
+    unsigned* kept_slots = LN(c).vtmp[VTL_CELLS].as<unsigned>();
     WS.n = P.n; WS.W = R.A.W; WS.n_own = h_own;
     hipLaunchKernelGGL(k_vwalk_fill, dim3(cdiv(nslots + 1, 256)), block, 0, LN(c).stream, A, sl0, nslots, wo, log_shift,
                        WS.walk.as<VWalk>(), WS.piece.as<VPiece>(), kept_slots, P.off.as<int64_t>());

@@ -40,9 +40,12 @@ struct PolyFeat {
     uint8_t closed;             // first == last on the ORIGINAL polyline (n >= 2)
 };
 
-// (stage 08's prefetch keeps the segment lengths of polylines above ORIP_LONG_CUM = 128 points (k_seglen) and takes the perimeters of open views above
-// this threshold from them: it must not be below ORIP_LONG_CUM)
+// polylines above ORIP_LONG_POLY points get a block for their features (vfeatures); above ORIP_LONG_CUM points a wavefront for their cumulative lengths
+// (stage 08-A: k_cumlen_long2).  Stage 08's prefetch keeps the segment lengths of the polylines above ORIP_LONG_CUM (k_seglen) and takes the
+// perimeters of open views above ORIP_LONG_POLY from them.
 #define ORIP_LONG_POLY 192
+#define ORIP_LONG_CUM 128
+static_assert(ORIP_LONG_POLY >= ORIP_LONG_CUM, "every polyline whose perimeter is summed from stored segment lengths must have had them stored");
 // ---- where a list's points come from (vsrc.h): explicit array or the layer's walk records ----
 static inline ESrc esrc_of(const DPolys& P) { return ESrc{P.off.as<int64_t>(), reinterpret_cast<const int2*>(P.pts.p)}; }
 int vsrc_of(orip_ctx* c, const DPolys& P, VSrc& out);
@@ -52,6 +55,12 @@ int vsrc_of(orip_ctx* c, const DPolys& P, VSrc& out);
         if (is_coded(P)) { VSrc SRC; ORIP_TRY(vsrc_of(c, P, SRC)); BODY }                      \
         else { const ESrc SRC = esrc_of(P); BODY }                                             \
     } while (0)
+// first index in the ascending a[0 .. n) whose element is > v
+__device__ __forceinline__ int64_t ub_u32(const unsigned* a, int64_t n, unsigned v) {
+    int64_t lo = 0, hi = n;
+    while (lo < hi) { int64_t mid = (lo + hi) >> 1; if (a[mid] <= v) lo = mid + 1; else hi = mid; }
+    return lo;
+}
 // a cursor as the point getter vec_serial.h's sums take
 template <class Cur> struct CurPt {
     Cur& c;
@@ -60,7 +69,7 @@ template <class Cur> struct CurPt {
 // features of every polyline of a list: short ones one lane each, long ones one block each.
 // what: bit0 perimeter KIND0, bit1 perimeter KIND1 (hypot), bit2 arcLength closed, bit3 arcLength open, bit4 open view (_ensure_open)
 int vfeatures(orip_ctx* c, const DPolys& P, int what, PolyFeat* feat);
-// The same for stage 08's prefetch (vector08.hip: orip_prefetch08), which runs them in three parts around its own kernels and events, each on LN(c).stream:
+// The same for stage 08's prefetch (vector08a.hip: orip_prefetch08), which runs them in three parts around its own kernels and events, each on LN(c).stream:
 // the short polylines' features and every polyline's end points (what: as vfeatures, and bit5 (with bit0): per_rev[i] = the same perimeter over the
 // REVERSED open polyline); order = the polylines longest first (kin, kout, vin: scratch of n words each); then the long polylines' perimeters in both
 // directions from STORED segment lengths (seg[k] = float32 length of segment k, the bounding boxes already in feat; leaves in the lane's vtmp[VT_LEAVES]).
@@ -78,6 +87,10 @@ int vgather(orip_ctx* c, const GatherDesc* d, int64_t n, const int32_t* src, DPo
 int vgather_views(orip_ctx* c, const GatherDesc* d, int64_t n, const DPolys& src, DPolys& dst, int64_t known_total = -1);
 // selection out of a list of either kind
 int vgather_list(orip_ctx* c, const GatherDesc* d, int64_t n, const DPolys& src, DPolys& dst, int64_t known_total = -1);
+
+// Runs of accepted slots -> polylines: per-slot flags (bit0 accepted, bit1 sequence start) and points -> dst, one polyline per run of >= 2 accepted slots.
+// Shared by stage 08-A (slots = samples) and stage 10 (slots = cut steps).
+int orip_runs_to_polys(orip_ctx* c, const int2* spt, const uint8_t* sflag, unsigned n_slots, DPolys& dst);
 
 // Greedy reorder of a whole DPolys list into dst.  kind: 7 -> 07 rules (arcLength closed seed), 8 -> 08 (_poly_perimeter seed), 10 -> 10 (arcLength open seed)
 // prefetch08 (optional, stage 07 only): stage 08's parameters; orip_prefetch08 is then called right after the greedy kernel has been enqueued, with the

@@ -334,7 +334,7 @@ extern "C" int orip_plot_order(orip_ctx* c, int layer, double R_insert, int64_t*
     if (nl + nt == 0) return 0;
     if (nl + nt > 0x3fffffff) ORIP_FAIL(c, "too many ops");
     PolyFeat* feat; uint8_t *alive_l, *alive_t;
-    { Carve S; S.take(feat, std::max<int64_t>(nl, 1)); S.take(alive_l, nl); S.take(alive_t, nt); HIPC(c, S.commit(LN(c).vtmp[6], 256)); }
+    { Carve S; S.take(feat, std::max<int64_t>(nl, 1)); S.take(alive_l, nl); S.take(alive_t, nt); HIPC(c, S.commit(LN(c).vtmp[VTL_FEAT], 256)); }
     HIPC(c, c->ops[layer].ensure((size_t)(nl + nt) * 20 + 64));
     HIPC(c, T.xy.ensure(64));
     if (nl) ORIP_TRY(vfeatures(c, L, 2, feat));

@@ -36,12 +36,7 @@ __global__ __launch_bounds__(256) void k_cut_counts(const int64_t* __restrict__ 
     }
 }
 
-// slot s -> (point index i, step k): i = upper_bound(base, s) - 1
-__device__ __forceinline__ int64_t ub_u32(const unsigned* a, int64_t n, unsigned v) {   // first index with a[idx] > v
-    int64_t lo = 0, hi = n;
-    while (lo < hi) { int64_t mid = (lo + hi) >> 1; if (a[mid] <= v) lo = mid + 1; else hi = mid; }
-    return lo;
-}
+// slot s -> (point index i, step k): i = ub_u32(base, s) - 1
 __global__ __launch_bounds__(256) void k_cut_slots(const int32_t* __restrict__ pts, const unsigned* __restrict__ cnt, const unsigned* __restrict__ base, int64_t n_pts,
                                                     const uint8_t* __restrict__ first_of_poly, unsigned n_slots, const u8* __restrict__ forb, int H, int W,
                                                     int2* __restrict__ spt, uint8_t* __restrict__ sflag /* bit0 free, bit1 poly start */) {
@@ -64,60 +59,6 @@ __global__ __launch_bounds__(256) void k_cut_slots(const int32_t* __restrict__ p
     spt[s] = make_int2((int)qx, (int)qy);
     sflag[s] = fl;
 }
-__global__ __launch_bounds__(256) void k_run_starts(const uint8_t* __restrict__ sflag, unsigned n, unsigned* __restrict__ start) {
-    unsigned s = blockIdx.x * 256 + threadIdx.x;
-    if (s >= n) return;
-    uint8_t f = sflag[s];
-    start[s] = ((f & 1) && ((f & 2) || s == 0 || !(sflag[s - 1] & 1))) ? 1u : 0u;
-}
-__global__ __launch_bounds__(256) void k_run_accum(const uint8_t* __restrict__ sflag, const unsigned* __restrict__ start, const unsigned* __restrict__ start_scan,
-                                                    unsigned n, unsigned* __restrict__ rlen, unsigned* __restrict__ rbegin) {
-    unsigned s = blockIdx.x * 256 + threadIdx.x;
-    if (s >= n) return;
-    if (!(sflag[s] & 1)) return;
-    unsigned rid = start_scan[s] + start[s] - 1;      // inclusive scan - 1
-    atomicAdd(&rlen[rid], 1u);
-    if (start[s]) rbegin[rid] = s;
-}
-__global__ __launch_bounds__(256) void k_run_keep(const unsigned* __restrict__ rlen, unsigned n_runs, unsigned min_len, unsigned* __restrict__ keep) {
-    unsigned r = blockIdx.x * 256 + threadIdx.x;
-    if (r < n_runs) keep[r] = rlen[r] >= min_len ? 1u : 0u;
-    if (r == n_runs) keep[r] = 0;
-}
-__global__ __launch_bounds__(256) void k_run_desc(const unsigned* __restrict__ rlen, const unsigned* __restrict__ rbegin, const unsigned* __restrict__ keep,
-                                                   const unsigned* __restrict__ keep_scan, unsigned n_runs, GatherDesc* __restrict__ d) {
-    unsigned r = blockIdx.x * 256 + threadIdx.x;
-    if (r >= n_runs || !keep[r]) return;
-    GatherDesc g; g.begin = rbegin[r]; g.len = rlen[r]; g.rev = 0; g.src = 0;
-    d[keep_scan[r]] = g;
-}
-
-// Shared by stage 08-A and stage 10: turn per-slot flags (bit0 accepted, bit1 sequence start) + points into a DPolys of runs with >= 2 points
-int orip_runs_to_polys(orip_ctx* c, const int2* spt, const uint8_t* sflag, unsigned n_slots, DPolys& dst) {
-    HIPC(c, dst.clear(LN(c).stream));
-    if (n_slots == 0) return 0;
-    unsigned *start, *start_scan; { Carve L; L.each(n_slots, start, start_scan); HIPC(c, L.commit(LN(c).vtmp[7], 64)); }
-    hipLaunchKernelGGL(k_run_starts, dim3(cdiv(n_slots, 256)), dim3(256), 0, LN(c).stream, sflag, n_slots, start);
-    ORIP_TRY(vscan_excl<unsigned>(c, start, start_scan, n_slots));
-    unsigned a[2];
-    HIPC(c, hipMemcpyAsync(&a[0], start_scan + (n_slots - 1), 4, hipMemcpyDeviceToHost, LN(c).stream));      // both words, one wait
-    ORIP_TRY(vread(c, &a[1], start + (n_slots - 1)));
-    unsigned n_runs = a[0] + a[1];
-    if (n_runs == 0) return 0;
-    unsigned *rlen, *rbegin, *keep, *keep_scan; GatherDesc* desc;
-    { Carve L; L.each((size_t)n_runs + 1, rlen, rbegin, keep, keep_scan); L.take(desc, n_runs); HIPC(c, L.commit(LN(c).vtmp[8], 256)); }
-    HIPC(c, hipMemsetAsync(rlen, 0, (size_t)(n_runs + 1) * 4, LN(c).stream));
-    hipLaunchKernelGGL(k_run_accum, dim3(cdiv(n_slots, 256)), dim3(256), 0, LN(c).stream, sflag, start, start_scan, n_slots, rlen, rbegin);
-    hipLaunchKernelGGL(k_run_keep, dim3(cdiv(n_runs + 1, 256)), dim3(256), 0, LN(c).stream, rlen, n_runs, 2u, keep);
-    ORIP_TRY(vscan_excl<unsigned>(c, keep, keep_scan, (size_t)n_runs + 1));
-    unsigned n_keep = 0;
-    ORIP_TRY(vread(c, &n_keep, keep_scan + n_runs));
-    if (n_keep == 0) return 0;
-    hipLaunchKernelGGL(k_run_desc, dim3(cdiv(n_runs, 256)), dim3(256), 0, LN(c).stream, rlen, rbegin, keep, keep_scan, n_runs, desc);
-    HIPC(c, hipGetLastError());
-    return vgather(c, desc, n_keep, reinterpret_cast<const int32_t*>(spt), dst);
-}
-
 // ---- _tiny_and_taps (10:99-118) ----
 // cv::minEnclosingCircle (recalled OpenCV 4.x algorithm, see vec_serial.h) with one wavefront per polyline: the three nested
 // loops of the incremental algorithm are "skip points that are inside, update on the first one that is not", so each of them is
@@ -431,7 +372,7 @@ static int dedup_cross_layer_impl(orip_ctx* c, int src_layer, int layer, bool re
     const int rad_taps = (int)std::max<long long>(1, vs::round_half_even(P.D_taps / 2.0));
     u8* forb = LN(c).canvas.as<u8>();
     const int occ_w = (Wp + 63) >> 6, occ_h = (Hp + 31) >> 5;
-    u8 *seeds, *hd, *occ; { Carve L; L.each((size_t)Wp * Hp, seeds, hd); L.take(occ, (size_t)occ_w * occ_h); HIPC(c, L.commit(LN(c).vtmp[9], 64)); }
+    u8 *seeds, *hd, *occ; { Carve L; L.each((size_t)Wp * Hp, seeds, hd); L.take(occ, (size_t)occ_w * occ_h); HIPC(c, L.commit(LN(c).vtmp[VTL_STEPLOG], 64)); }
     PhaseTimer T(c, "ORIP_TIME10");
     { T.lap();
         if (layer < 0 || layer >= ORIP_MAX_LAYERS) ORIP_FAIL(c, "bad layer %d", layer);
@@ -444,14 +385,14 @@ static int dedup_cross_layer_impl(orip_ctx* c, int src_layer, int layer, bool re
         if (Lin.n > 0 && Lin.total > 0) {
             if (Lin.total > 0x7fffffff) ORIP_FAIL(c, "layer too large");
             unsigned *cnt, *base; uint8_t* fop;
-            { Carve L; L.each(Lin.total + 1, cnt, base, fop); HIPC(c, L.commit(LN(c).vtmp[0], 64)); }
+            { Carve L; L.each(Lin.total + 1, cnt, base, fop); HIPC(c, L.commit(LN(c).vtmp[VTL_RANKS], 64)); }
             HIPC(c, hipMemsetAsync(cnt + Lin.total, 0, 4, LN(c).stream));
             hipLaunchKernelGGL(k_cut_counts, dim3((unsigned)std::min<int64_t>(Lin.n, 65535)), dim3(256), 0, LN(c).stream, Lin.off.as<int64_t>(), Lin.pts.as<int32_t>(), Lin.n, P.step_px, cnt, fop);
             ORIP_TRY(vscan_excl<unsigned>(c, cnt, base, (size_t)Lin.total + 1));
             unsigned n_slots = 0;
             ORIP_TRY(vread(c, &n_slots, base + Lin.total));
             if (n_slots) {
-                int2* spt; uint8_t* sflag; { Carve L; L.each(n_slots, spt, sflag); HIPC(c, L.commit(LN(c).vtmp[1], 64)); }
+                int2* spt; uint8_t* sflag; { Carve L; L.each(n_slots, spt, sflag); HIPC(c, L.commit(LN(c).vtmp[VTL_CUM], 64)); }
                 { ProfScope ps(c, "k_cut_slots"); hipLaunchKernelGGL(k_cut_slots, dim3(cdiv(n_slots, 256)), dim3(256), 0, LN(c).stream, Lin.pts.as<int32_t>(), cnt, base, Lin.total, fop, n_slots, forb, H, W, spt, sflag); }
                 ORIP_TRY(orip_runs_to_polys(c, spt, sflag, n_slots, cut));
             }
@@ -461,11 +402,11 @@ static int dedup_cross_layer_impl(orip_ctx* c, int src_layer, int layer, bool re
         int64_t n_tap_lines = 0;
         keepl.n = 0; keepl.total = 0; keepl.set_explicit();
         unsigned *is_tap, *is_keep, *tap_scan, *keep_scan; int2* tap_xy; GatherDesc* kd;
-        { Carve L; L.each(cut.n + 1, is_tap, is_keep, tap_scan, keep_scan, tap_xy, kd); HIPC(c, L.commit(LN(c).vtmp[2], 256)); }
+        { Carve L; L.each(cut.n + 1, is_tap, is_keep, tap_scan, keep_scan, tap_xy, kd); HIPC(c, L.commit(LN(c).vtmp[VTL_SPLIT], 256)); }
         int64_t n_seq = Tin.n;
         if (cut.n > 0) {
-            HIPC(c, LN(c).vtmp[10].ensure((size_t)cut.n * sizeof(PolyFeat) + 64));
-            PolyFeat* cfeat = LN(c).vtmp[10].as<PolyFeat>();
+            HIPC(c, LN(c).vtmp[VTL_SPLIT_FEAT].ensure((size_t)cut.n * sizeof(PolyFeat) + 64));
+            PolyFeat* cfeat = LN(c).vtmp[VTL_SPLIT_FEAT].as<PolyFeat>();
             ORIP_TRY(vfeatures(c, cut, 0, cfeat));
             hipLaunchKernelGGL(k_tiny_taps10, dim3((unsigned)std::min<int64_t>(cut.n + 1, 65535)), dim3(64), 0, LN(c).stream, cut.off.as<int64_t>(), cut.pts.as<int32_t>(), cut.n, P, cfeat, is_tap, is_keep, tap_xy);
             ORIP_TRY(vscan_excl<unsigned>(c, is_tap, tap_scan, (size_t)cut.n + 1));
@@ -481,7 +422,7 @@ static int dedup_cross_layer_impl(orip_ctx* c, int src_layer, int layer, bool re
         }
         // taps_seq = taps_in + taps_from_lines
         n_seq = Tin.n + n_tap_lines;
-        int2 *seq, *acc; { Carve L; L.each(n_seq + 1, seq, acc); HIPC(c, L.commit(LN(c).vtmp[3], 64)); }
+        int2 *seq, *acc; { Carve L; L.each(n_seq + 1, seq, acc); HIPC(c, L.commit(LN(c).vtmp[VTL_SAMPLES], 64)); }
         if (Tin.n) HIPC(c, hipMemcpyAsync(seq, Tin.xy.p, (size_t)Tin.n * 8, hipMemcpyDeviceToDevice, LN(c).stream));
         if (n_tap_lines) hipLaunchKernelGGL(k_compact_sel, dim3(cdiv(cut.n, 256)), dim3(256), 0, LN(c).stream, is_tap, tap_scan, cut.n, cut.off.as<int64_t>(), (GatherDesc*)nullptr, tap_xy, seq + Tin.n);
         const double ms_tiny = T.lap();

@@ -1241,6 +1241,61 @@ int vgather_list(orip_ctx* c, const GatherDesc* d, int64_t n, const DPolys& src,
     if (is_coded(src)) return vgather_views(c, d, n, src, dst, known_total);
     return vgather(c, d, n, src.pts.as<int32_t>(), dst, known_total);
 }
+// ---- runs of accepted slots -> polylines (stage 08-A: samples; stage 10: cut steps)
+__global__ __launch_bounds__(256) void k_run_starts(const uint8_t* __restrict__ sflag, unsigned n, unsigned* __restrict__ start) {
+    unsigned s = blockIdx.x * 256 + threadIdx.x;
+    if (s >= n) return;
+    uint8_t f = sflag[s];
+    start[s] = ((f & 1) && ((f & 2) || s == 0 || !(sflag[s - 1] & 1))) ? 1u : 0u;
+}
+__global__ __launch_bounds__(256) void k_run_accum(const uint8_t* __restrict__ sflag, const unsigned* __restrict__ start, const unsigned* __restrict__ start_scan,
+                                                    unsigned n, unsigned* __restrict__ rlen, unsigned* __restrict__ rbegin) {
+    unsigned s = blockIdx.x * 256 + threadIdx.x;
+    if (s >= n) return;
+    if (!(sflag[s] & 1)) return;
+    unsigned rid = start_scan[s] + start[s] - 1;      // inclusive scan - 1
+    atomicAdd(&rlen[rid], 1u);
+    if (start[s]) rbegin[rid] = s;
+}
+__global__ __launch_bounds__(256) void k_run_keep(const unsigned* __restrict__ rlen, unsigned n_runs, unsigned min_len, unsigned* __restrict__ keep) {
+    unsigned r = blockIdx.x * 256 + threadIdx.x;
+    if (r < n_runs) keep[r] = rlen[r] >= min_len ? 1u : 0u;
+    if (r == n_runs) keep[r] = 0;
+}
+__global__ __launch_bounds__(256) void k_run_desc(const unsigned* __restrict__ rlen, const unsigned* __restrict__ rbegin, const unsigned* __restrict__ keep,
+                                                   const unsigned* __restrict__ keep_scan, unsigned n_runs, GatherDesc* __restrict__ d) {
+    unsigned r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= n_runs || !keep[r]) return;
+    GatherDesc g; g.begin = rbegin[r]; g.len = rlen[r]; g.rev = 0; g.src = 0;
+    d[keep_scan[r]] = g;
+}
+
+// Shared by stage 08-A and stage 10 (vec_common.h): turn per-slot flags (bit0 accepted, bit1 sequence start) + points into a DPolys of runs with >= 2 points
+int orip_runs_to_polys(orip_ctx* c, const int2* spt, const uint8_t* sflag, unsigned n_slots, DPolys& dst) {
+    HIPC(c, dst.clear(LN(c).stream));
+    if (n_slots == 0) return 0;
+    unsigned *start, *start_scan; { Carve L; L.each(n_slots, start, start_scan); HIPC(c, L.commit(LN(c).vtmp[VTL_RUN_STARTS], 64)); }
+    hipLaunchKernelGGL(k_run_starts, dim3(cdiv(n_slots, 256)), dim3(256), 0, LN(c).stream, sflag, n_slots, start);
+    ORIP_TRY(vscan_excl<unsigned>(c, start, start_scan, n_slots));
+    unsigned a[2];
+    HIPC(c, hipMemcpyAsync(&a[0], start_scan + (n_slots - 1), 4, hipMemcpyDeviceToHost, LN(c).stream));      // both words, one wait
+    ORIP_TRY(vread(c, &a[1], start + (n_slots - 1)));
+    unsigned n_runs = a[0] + a[1];
+    if (n_runs == 0) return 0;
+    unsigned *rlen, *rbegin, *keep, *keep_scan; GatherDesc* desc;
+    { Carve L; L.each((size_t)n_runs + 1, rlen, rbegin, keep, keep_scan); L.take(desc, n_runs); HIPC(c, L.commit(LN(c).vtmp[VTL_TAIL_RUNS], 256)); }
+    HIPC(c, hipMemsetAsync(rlen, 0, (size_t)(n_runs + 1) * 4, LN(c).stream));
+    hipLaunchKernelGGL(k_run_accum, dim3(cdiv(n_slots, 256)), dim3(256), 0, LN(c).stream, sflag, start, start_scan, n_slots, rlen, rbegin);
+    hipLaunchKernelGGL(k_run_keep, dim3(cdiv(n_runs + 1, 256)), dim3(256), 0, LN(c).stream, rlen, n_runs, 2u, keep);
+    ORIP_TRY(vscan_excl<unsigned>(c, keep, keep_scan, (size_t)n_runs + 1));
+    unsigned n_keep = 0;
+    ORIP_TRY(vread(c, &n_keep, keep_scan + n_runs));
+    if (n_keep == 0) return 0;
+    hipLaunchKernelGGL(k_run_desc, dim3(cdiv(n_runs, 256)), dim3(256), 0, LN(c).stream, rlen, rbegin, keep, keep_scan, n_runs, desc);
+    HIPC(c, hipGetLastError());
+    return vgather(c, desc, n_keep, reinterpret_cast<const int32_t*>(spt), dst);
+}
+
 // explicit points of a walk-coded list, on request (orip_get_polys, consumers that read int32 pairs); enqueued on the calling lane's stream
 int orip_polys_materialize(orip_ctx* c, DPolys& P) {
     if (!is_coded(P)) return 0;
@@ -1260,7 +1315,7 @@ int vreorder(orip_ctx* c, DPolys& src, DPolys& dst, int kind, const orip_params0
     if (n == 0) { HIPC(c, dst.clear(LN(c).stream)); return 0; }
     if (n > 0x7fffffff) ORIP_FAIL(c, "too many polylines");
     PolyFeat* feat; NNEnds* ends; GatherDesc* desc; int32_t* order; uint8_t *flips, *used;
-    { Carve L; L.each(n, feat, ends, desc, order, flips, used); HIPC(c, L.commit(LN(c).vtmp[6], 256)); }
+    { Carve L; L.each(n, feat, ends, desc, order, flips, used); HIPC(c, L.commit(LN(c).vtmp[VTL_FEAT], 256)); }
     int what = kind == 7 ? 4 : (kind == 8 ? 1 : 8);
     if (kind == 7 && is_coded(src) && src.vident && !getenv("ORIP_ARC_POINTS")) {      // whole walks: the long contours' arc lengths from the walk records
         VSrc vs_; ORIP_TRY(vsrc_of(c, src, vs_));

@@ -32,7 +32,7 @@ PAT(p_salu_valu_alt, "s_add_i32 %0, %0, 1\n\tv_add_u32 %9, %0, %8\n\t")
 PAT(p_ff1_readlane, "s_ff1_i32_b32 %3, %4\n\tv_readlane_b32 %5, %8, %3\n\ts_add_i32 %4, %4, %5\n\t")
 PAT(p_cselect, "s_and_b32 %3, %0, %1\n\ts_cselect_b32 %5, %1, %2\n\ts_cselect_b32 %6, -1, 0\n\t")
 
-// cross-lane and wide LDS patterns (the chains of csrc/vector08.hip k_cumlen_*)
+// cross-lane and wide LDS patterns (the chains of csrc/vector08a.hip k_cumlen_*)
 #define PATX(name, body) \
 __global__ __launch_bounds__(64) void name(unsigned long long* out, int n) { \
     __shared__ __align__(16) int lds[1024]; for (int i = threadIdx.x; i < 1024; i += 64) lds[i] = i; __syncthreads(); \

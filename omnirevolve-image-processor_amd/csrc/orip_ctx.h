@@ -154,10 +154,14 @@ struct LaneFlags {
     int trace_overflow;                                     // 04 trace: a log ran full (set by k_trace, read by trace_finish -- possibly in a later call)
     int nn_seed[2];                                         // vreorder (07 / 08 / 10 on its lane): seed polyline, coordinate-range flags
     alignas(8) unsigned long long nn_dbg2[10];              // vreorder: ORIP_NN_DBG2 counters of the grid greedy
-    int caps_overflow;                                      // 08-A4: the capsule table ran full
-    unsigned caps_distinct;                                 // 08-A4: distinct capsules (read back at the end of orip_dedup_layer -> caps_hint)
-    unsigned accept_survivors;                              // 08-A5: samples the cheap test leaves for the near test
-    alignas(8) unsigned long long accept_work;              // 08-A5: candidate pairs of the direct near test
+    // The next four are cleared by k_caps_init, the first kernel of every growth round of 08-A4, on the lane's main stream; every writer and reader below is on
+    // that stream, behind it, in the same call (the side stream's k_tail_replay takes no flag), and the read-back of the call before lies in front of it.
+    int caps_overflow;                                      // 08-A4: the capsule table ran full.  Set by k_caps_insert right behind the clear, read back by the host, cleared
+                                                            //        again by the next round's k_caps_init: exactly when a larger table starts from empty
+    unsigned caps_distinct;                                 // 08-A4: distinct capsules.  Added to by k_caps_stamp_bits, which runs once, behind the last round; read back at the
+                                                            //        end of orip_dedup_layer -> caps_hint (nothing of 08-A5, 08-B or the reorder in between writes it)
+    unsigned accept_survivors;                              // 08-A5: samples the cheap test leaves for the near test.  Added to by k_accept_pre, read by k_accept_brute / k_accept
+    alignas(8) unsigned long long accept_work;              // 08-A5: candidate pairs of the direct near test.  Added to by k_accept_pre, read back by the host behind it
     int zs_changed[12];                                     // 08-B: per thinning iteration of a batch, something was deleted
     unsigned comp_counts[3];                                // 08-B: work-list cursors of the three component classes
     int taps_kept;                                          // 10 (ORIP_LANE_CROSS): sequential taps accepted
@@ -201,8 +205,9 @@ static_assert(sizeof(LaneFlags) <= 4096, "LaneRes::flags is 4096 bytes, allocate
 //                         slot behind ev4 only; the two meet in practice behind several host round trips of split_small, but no event orders them
 //   08-A (vector08a.hip)  VTL_FEAT A0 -> k_rank_counts (across split_small, vsort_pairs, vscan_excl); VTL_RANKS A1 -> A6; VTL_CUM A2 (k_samples reads it last);
 //                         VTL_SAMPLES, VTL_CELLS, canvas, pixbits A2 -> A6, VTL_SAMPLES on through orip_runs_to_polys (its spt and sflag are the input);
-//                         VTL_TAIL_RUNS A3 -> A6: tail sums (8 MS bytes) and, behind them, redo, which the side stream reads until ev3 (awaited by A5); the
-//                         last-in scan and then the survivors take the first 4 MS bytes only, and orip_runs_to_polys takes the slot once A6 is enqueued;
+//                         VTL_RANKS also holds the redo flags of A3 (nk + 1 words behind RsInfo), which the side stream reads until ev3 (awaited by A5);
+//                         VTL_TAIL_RUNS A2 -> A6: the block-local tail sums (8 MS bytes; k_samples -> k_tail_par), then the last-in scan and then the
+//                         survivors in its first 4 MS bytes, and orip_runs_to_polys takes the slot once A6 is enqueued;
 //                         VTL_CAPS A4; A7's split_small finds everything but tp[] free
 //   08-B (vector08b.hip)  VTL_FEAT (features, parents, groups) groups -> paths; canvas (group ids) raster -> paths; VTL_STEPLOG (bit planes, skeleton bytes)
 //                         raster -> paths; VTL_SPLIT_FEAT (labels) and VTL_RANKS (block counts) within components; VTL_CUM (sorted pixels), VTL_CAPS (component
@@ -216,7 +221,7 @@ static_assert(sizeof(LaneFlags) <= 4096, "LaneRes::flags is 4096 bytes, allocate
 enum { VT0_KEYS = 0, VT0_HEADS = 1, VT0_COMP_START = 2, VT0_ORDER = 3, VT0_ORDER_SORT = 5, VT0_MEMO = 6, VT0_LOG_USED = 7, VT0_WINFO = 8, VT0_EDGE_BITS = 10,     // lane 0
        VT0_NMS_BITS = 11 };     // (VT0_HEADS, VT0_ORDER_SORT: component heads / sort buffers inside orip_contours_prepare; VT0_NMS_BITS: candidate and strong planes inside orip_detect_edges)
 // Layer lanes and ORIP_LANE_CROSS.  A name is the slot's role in stage 08-A, or in the helper that owns it; the other roles of the same index, in call order:
-enum { VTL_RANKS = 0,           // 08-A: perimeter sort, order, samples per rank, sample bases, RsInfo | 08-B: skeleton pixels per block | 10: steps per point, their bases
+enum { VTL_RANKS = 0,           // 08-A: perimeter sort, order, samples per rank, sample bases + any-out word, RsInfo, redo flags | 08-B: skeleton pixels per block | 10: steps per point, their bases
        VTL_CUM = 1,             // 08-A: cumulative lengths and their offsets | 08-B: skeleton pixels sorted by label | 10: cut steps (points, flags)
        VTL_SPLIT = 2,           // split_small: tap / keep flags, their scans, tap centres, descriptors | 10: the same for _tiny_and_taps
        VTL_SAMPLES = 3,         // 08-A: the per-sample arrays (SampleArrs, npop, capprev, sflag) | 08-B: component heads and their scan | 10: tap sequence, accepted taps
@@ -224,7 +229,7 @@ enum { VTL_RANKS = 0,           // 08-A: perimeter sort, order, samples per rank
        VTL_CELLS = 5,           // 08-A: cell keys / values (bucket sort), sample hints | 08-B: per-component path scratch | 04 trace_finish: kept walk slots
        VTL_FEAT = 6,            // features: 08-A kept polylines | 08-B lines, parents, groups | vreorder (07, 08 C, 10, 12): features, ends, order | 12: features, alive flags
        VTL_RUN_STARTS = 7,      // orip_runs_to_polys: run starts and their scan
-       VTL_TAIL_RUNS = 8,       // 08-A: tail sums + redo flags -> last-in scan -> survivors, THEN orip_runs_to_polys: run lengths, begins, keep flags, descriptors
+       VTL_TAIL_RUNS = 8,       // 08-A: block-local tail sums -> last-in scan -> survivors, THEN orip_runs_to_polys: run lengths, begins, keep flags, descriptors
        VTL_STEPLOG = 9,         // 04: step log of the layer's trace (between entry points, see above) | 08-B: skeleton bytes, thinning bit planes | 10: seed, distance, occupancy planes
        VTL_SPLIT_FEAT = 10,     // split_small: features of its source list | 08-B: union-find labels of the padded raster | 10: features of the cut lines
        VT_LEAVES = 11,          // wherever vfeatures runs: its perimeter leaves and length order, and those of the stage-08 prefetch (between entry points, see above) | 04 with ORIP_WALK_DBG: per-component debug counters of the trace

@@ -9,7 +9,7 @@
 // samples of all polylines of the layer are tested in parallel.  Self-collision (_PointHash, 08:68-99) is a sorted
 // (polyline, cell) bucket list scanned in pop order.
 // Layout: the kernels phase by phase (A0 / A7, A2, A3, A4, A5), the prefetch, then the host side: split_small (A0 / A7), one function per phase
-// (a1_order .. a56_accept) and dedup08_a, which calls them in order.  This is the one unit of stage 08 that calls rocPRIM directly (the scans by key of
+// (a1_order .. a56_accept) and dedup08_a, which calls them in order.  This is the one unit of stage 08 that calls rocPRIM directly (the last-in scan by key of
 // A3, the segmented sort of A5).
 #include "vec08.h"
 #include <rocprim/rocprim.hpp>
@@ -304,8 +304,9 @@ __global__ __launch_bounds__(256) void k_seglen(Src src, int64_t n_polys, int64_
 // any_out: set when a sampled polyline reaches beyond the canvas (its samples lie inside the box of its points): only then can a sample be
 // off-canvas, and only then does "the previous in-canvas sample" (k_capprev) differ from "the previous sample"
 __global__ __launch_bounds__(256) void k_rank_counts(const RsInfo* __restrict__ info, const unsigned* __restrict__ ord, int64_t n, unsigned* __restrict__ mr,
-                                                      const PolyFeat* __restrict__ feat, int W, int H, unsigned* __restrict__ any_out) {
+                                                      const PolyFeat* __restrict__ feat, int W, int H, unsigned* __restrict__ any_out, unsigned* __restrict__ redo) {
     int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (r <= n) redo[r] = 0u;                                 // the n + 1 redo flags of A3 (A08::redo)
     if (r < n) {
         const unsigned i = ord[r]; const unsigned m = info[i].m;
         mr[r] = m;
@@ -314,10 +315,17 @@ __global__ __launch_bounds__(256) void k_rank_counts(const RsInfo* __restrict__ 
     if (r == n) mr[r] = 0;
 }
 // One record per sample.  sx, sy: the float64 position; dprev: distance to the predecessor on the same polyline; spt: the position truncated to integers (what a
-// surviving sample contributes to the cleaned line); pxy: the rounded pixel as x | y << 16 inside the canvas (W, H <= 16383), ORIP_PXY_OUT off it -- an
-// off-canvas sample's pixel is never read, every consumer tests the sentinel first; rank: the polyline, in processing order.
+// surviving sample contributes to the cleaned line); rank: the polyline, in processing order.
+// pxy: the rounded pixel and one flag.  Inside the canvas (W, H <= 16383) x sits in bits 0-13, y in bits 16-29, and ORIP_PXY_FIRST (bit 15) is set on the first
+// sample of its polyline; bits 14, 30 and 31 are zero.  Off the canvas the word is ORIP_PXY_OUT (all ones) and carries neither a pixel nor the flag: every
+// consumer tests the sentinel first, then takes the coordinates with pxy_x / pxy_y.
+// Sloc: the sum of dprev from the first sample of g's polyline -- or of g's 1024-sample block of k_samples (ORIP_SMP_BLOCK), whichever comes later -- up to g.
 #define ORIP_PXY_OUT 0xffffffffu
-struct SampleArrs { double* sx; double* sy; double* dprev; int2* spt; unsigned* pxy; unsigned* rank; };
+#define ORIP_PXY_FIRST 0x8000u
+#define ORIP_SMP_BLOCK 1024u
+__device__ __forceinline__ int pxy_x(unsigned p) { return (int)(p & 0x3fffu); }
+__device__ __forceinline__ int pxy_y(unsigned p) { return (int)((p >> 16) & 0x3fffu); }
+struct SampleArrs { double* sx; double* sy; double* dprev; int2* spt; unsigned* pxy; unsigned* rank; double* Sloc; };
 // rank (polyline) and segment of sample g, as k_samples needs them.  Both are monotone in g, so the values of the first sample of a
 // 256-sample block and of the next block bound the searches of every sample in between: k_sample_hints does the two full binary
 // searches once per block, k_samples only searches between the hints (mostly zero to a few steps instead of ~28 dependent loads).
@@ -354,6 +362,16 @@ __global__ __launch_bounds__(256) void k_sample_hints(const int64_t* __restrict_
 // no cost in space; the consumers' consecutive reads stay consecutive within every group of four.
 __device__ __forceinline__ unsigned smp_slot8(unsigned s) { return s ^ ((s >> 5) & 3u); }      // t >> 3
 __device__ __forceinline__ unsigned smp_slot4(unsigned s) { return s ^ ((s >> 6) & 3u); }      // t >> 4
+// one step of a segmented inclusive wave scan of (f, a): f = a segment starts at or before this lane within the lanes combined so far, a = the sum since then.
+// Lanes the DPP pattern leaves out receive (0, +0.0), the identity.
+template <int CTRL, int ROWMASK>
+__device__ __forceinline__ void wave_seg_step(double& a, unsigned& f) {
+    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(a), CTRL, ROWMASK, 0xf, false);
+    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(a), CTRL, ROWMASK, 0xf, false);
+    const unsigned pf = (unsigned)__builtin_amdgcn_update_dpp(0, (int)f, CTRL, ROWMASK, 0xf, false);
+    if (!f) a = __dadd_rn(__hiloint2double(hi, lo), a);
+    f |= pf;
+}
 template <class Src>
 __global__ __launch_bounds__(256) void k_samples(Src src, const int64_t* __restrict__ cumoff, const float* __restrict__ cum,
                                                   const RsInfo* __restrict__ info, const unsigned* __restrict__ ord, const unsigned* __restrict__ sbase, int64_t n_rank,
@@ -366,9 +384,12 @@ __global__ __launch_bounds__(256) void k_samples(Src src, const int64_t* __restr
     // The threads leave position and polyline of their samples in LDS; after the barrier thread t takes the block's samples t, t + 256, t + 512, t + 768, derives
     // the rest of the record (distance to the predecessor, truncated point, pixel) from the staged positions and stores it: every store instruction of a wave
     // writes 64 consecutive elements (stored straight from the producers it wrote 64 elements at a stride of four).
+    // Last, the block scans its 1024 distances by polyline (Sloc, see SampleArrs): k_tail_par forms its tail sums from them, no pass over the samples in between.
     constexpr int S = 4;
     constexpr unsigned NS = 256 * S;
-    __shared__ double shx[NS], shy[NS], shp[2];            // [smp_slot8(s)]: sample s of the block; shp: the predecessor of sample 0
+    static_assert(NS == ORIP_SMP_BLOCK, "k_tail_par takes a block of k_samples for 1024 samples");
+    __shared__ double shx[NS], shy[NS], shp[2], swa[4];    // swa, swf: sum and flag of each wave's 256 samples (the scan)
+    __shared__ unsigned swf[4];            // [smp_slot8(s)]: sample s of the block; shp: the predecessor of sample 0
     __shared__ unsigned shr[NS];                           // [smp_slot4(s)]: its rank, bit 31: first sample of its polyline
     const unsigned g0 = (blockIdx.x * 256 + threadIdx.x) * S;
     if (g0 < MS) {
@@ -443,6 +464,7 @@ __global__ __launch_bounds__(256) void k_samples(Src src, const int64_t* __restr
     }
     __syncthreads();
     const unsigned b0 = blockIdx.x * NS;
+    double dd[S] = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
     for (int u = 0; u < S; u++) {
         const unsigned ls = threadIdx.x + 256u * (unsigned)u, g = b0 + ls;
@@ -453,17 +475,50 @@ __global__ __launch_bounds__(256) void k_samples(Src src, const int64_t* __restr
         // distance to the predecessor on the same polyline, exactly as the tail bookkeeping evaluates it (08:141,147)
         double d = 0.0;
         if (!(rw >> 31)) { const unsigned before = smp_slot8(ls ? ls - 1u : 0u); d = vs::norm2_f64(x - (ls ? shx[before] : shp[0]), y - (ls ? shy[before] : shp[1])); }
-        A.dprev[g] = d;
+        A.dprev[g] = d; dd[u] = d;
         A.sx[g] = x; A.sy[g] = y; A.rank[g] = rw & 0x7fffffffu;
         A.spt[g] = make_int2((int)x, (int)y);
         const long long xi = vs::round_half_even(x), yi = vs::round_half_even(y);
         const bool in = xi >= 0 && yi >= 0 && xi < W && yi < H;
-        A.pxy[g] = in ? ((unsigned)xi | ((unsigned)yi << 16)) : ORIP_PXY_OUT;
+        A.pxy[g] = in ? ((unsigned)xi | ((unsigned)yi << 16) | ((rw >> 31) ? ORIP_PXY_FIRST : 0u)) : ORIP_PXY_OUT;
         if (pixbits && in) {       // the canvas is read at sample pixels only (k_caps_stamp_bits): mark the pixel, give it its "never stamped" value
             unsigned long long* wp = &pixbits[(size_t)yi * Wq + (xi >> 6)]; const unsigned long long bit = 1ULL << (xi & 63);
             if (!(*wp & bit) && !(atomicOr(wp, bit) & bit)) firstseq[(size_t)yi * W + xi] = 0xffffffffu;      // whoever sets the bit initialises the pixel: one write per distinct pixel, not per sample
         }
     }
+    // ---- Sloc: segmented inclusive scan of the block's distances; a segment starts at the first sample of a polyline (whose distance is 0).  The distances take
+    // the place of the staged x once every thread has read its positions; thread t then owns samples 4t .. 4t + 3 again (the producers' layout): four serial
+    // steps, a wave scan of the threads' sums, the four waves' sums in order.  Any summation order serves (k_tail_par has the argument); this one is fixed.
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < S; u++) shx[smp_slot8(threadIdx.x + 256u * (unsigned)u)] = dd[u];      // (beyond MS: 0)
+    __syncthreads();
+    const unsigned l0 = threadIdx.x * S;
+    double v[S]; unsigned f[S];
+#pragma unroll
+    for (int q = 0; q < S; q++) { v[q] = shx[smp_slot8(l0 + q)]; f[q] = (b0 + l0 + q < MS) ? shr[smp_slot4(l0 + q)] >> 31 : 0u; }
+    double wa = v[0]; unsigned wf = f[0];
+#pragma unroll
+    for (int q = 1; q < S; q++) { wa = f[q] ? v[q] : __dadd_rn(wa, v[q]); wf |= f[q]; }
+    wave_seg_step<0x111, 0xf>(wa, wf); wave_seg_step<0x112, 0xf>(wa, wf); wave_seg_step<0x114, 0xf>(wa, wf); wave_seg_step<0x118, 0xf>(wa, wf);      // row_shr 1, 2, 4, 8
+    wave_seg_step<0x142, 0xa>(wa, wf); wave_seg_step<0x143, 0xc>(wa, wf);                                                                              // row_bcast 15, 31
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    if (lane == 63) { swa[wv] = wa; swf[wv] = wf; }
+    // (wa, wf) of the lane before: what precedes this thread's samples inside the wave
+    double ea = __hiloint2double(__builtin_amdgcn_update_dpp(0, __double2hiint(wa), 0x138 /* wave_shr:1 */, 0xf, 0xf, false),
+                                 __builtin_amdgcn_update_dpp(0, __double2loint(wa), 0x138, 0xf, 0xf, false));
+    const unsigned ef = (unsigned)__builtin_amdgcn_update_dpp(0, (int)wf, 0x138, 0xf, 0xf, false);
+    __syncthreads();
+    if (!ef) {                                             // no polyline starts in the wave before this thread: the waves before it count too
+        double ca = 0.0;
+        for (int k = 0; k < wv; k++) ca = swf[k] ? swa[k] : __dadd_rn(ca, swa[k]);
+        ea = __dadd_rn(ca, ea);
+    }
+#pragma unroll
+    for (int q = 0; q < S; q++) { ea = f[q] ? v[q] : __dadd_rn(ea, v[q]); v[q] = ea; }
+    const unsigned gs = b0 + l0;
+    if (gs + S <= MS) { double2* o = reinterpret_cast<double2*>(A.Sloc + gs); o[0] = make_double2(v[0], v[1]); o[1] = make_double2(v[2], v[3]); }
+    else { for (int q = 0; q < S; q++) if (gs + q < MS) A.Sloc[gs + q] = v[q]; }
 }
 
 // ================================================================= A3: tail simulation (08:139-155)
@@ -565,49 +620,77 @@ __global__ __launch_bounds__(64) void k_tail_replay(const unsigned* __restrict__
 
 // Parallel form of the same simulation.  After sample j is pushed the queue holds samples head..j and tail_len is the sum of the
 // distances D[head+1..j]; the pops leave the smallest head with that sum <= tail_len_px (the sums shrink as head grows and a head
-// never moves back because D >= 0).  With S = per-polyline inclusive prefix sums of D (rocPRIM scan-by-key) the sum is S[j] - S[head],
-// found by binary search.  The reference compares a float64 running sum with its own rounding history; both that sum and S[j]-S[h]
-// are within ~1e-8 px of the real sum for polylines shorter than 2^22 px (ulp(2^22) * <64 additions per scan path; 2 ulp(256) per
-// push/pop over < 2^20 samples), so a comparison that clears the threshold by more than ORIP_TAIL_EPS is the reference's decision.
-// Any sample that is closer marks its polyline, and marked polylines are redone by the sequential simulation (k_tail_replay).
+// never moves back because D >= 0), found by binary search.
+// The sum comes from the block-local prefix sums k_samples leaves (Sloc: from the polyline's first sample or from the first sample of the 1024-sample block,
+// whichever is later).  With j in block K and h on the same polyline:
+//   h in block K too:   Sloc[j] - Sloc[h]                                      (both count from the same sample)
+//   h in block K' < K:  Sloc[j] + (L[K-1] + L[K-2] + ... + L[K']) - Sloc[h]     L[k] = Sloc of block k's last sample: blocks K' .. K-1 lie inside the
+//                                                                               polyline from h on, so L[k] is block k's whole sum (block K' counts from where h's
+//                                                                               Sloc does).  The L are added in this order, from K-1 down.
+// The window in LDS (the 256 sums before the tail block + its own) is brought into block K's frame once: an entry of block K-1 has L[K-1] taken off.
+// The reference compares a float64 running sum with its own rounding history.  Here a distance reaches the compared value through fewer than 64 additions:
+// at most 16 inside a Sloc (4 serial per thread, 6 levels of the wave scan, 2 wave sums, 1 to join them, and the 3 serial ones of the wave sums' own threads), 1 per
+// block sum L, of which at most ORIP_TAIL_BLOCKS = 32 are taken, 2 for the difference -- and every partial sum is checked to stay below 2^22 px.  An addition
+// errs by at most ulp(2^22) / 2 = 4.7e-10 px, so the value is within 3e-8 px of the real sum, as is the reference's (2 ulp(256) per push / pop over < 2^20 samples):
+// a comparison that clears the threshold by more than ORIP_TAIL_EPS is the reference's decision, whatever the order of summation.
+// Any sample that is closer marks its polyline, so does one whose search would go back over more than ORIP_TAIL_BLOCKS block sums, and marked polylines are
+// redone by the sequential simulation (k_tail_replay) from the exact distances: the rounding of these sums decides which polylines are redone, never a result.
 #define ORIP_TAIL_EPS 1e-6
-__global__ __launch_bounds__(256) void k_tail_par(const unsigned* __restrict__ sbase, const unsigned* __restrict__ rank, const double* __restrict__ S, unsigned MS, double T,
+#define ORIP_TAIL_BLOCKS 32u
+__global__ __launch_bounds__(256) void k_tail_par(const unsigned* __restrict__ sbase, const unsigned* __restrict__ rank, const double* __restrict__ Sloc, unsigned MS, double T,
                                                    unsigned* __restrict__ npop, unsigned* __restrict__ redo) {
     __shared__ double win[512];
-    const unsigned g0 = blockIdx.x * 256, w0 = g0 >= 256 ? g0 - 256 : 0;      // window = S[w0 .. g0 + 255]
-    for (unsigned t = threadIdx.x; t < 512; t += 256) { const unsigned idx = w0 + t; win[t] = (idx < MS && idx < g0 + 256) ? S[idx] : 0.0; }
+    const unsigned g0 = blockIdx.x * 256, w0 = g0 >= 256 ? g0 - 256 : 0;      // window = samples w0 .. g0 + 255
+    const unsigned KB = g0 / ORIP_SMP_BLOCK, B0 = KB * ORIP_SMP_BLOCK;         // the tail block lies inside block KB of k_samples, which starts at sample B0
+    const double lastprev = w0 < B0 ? Sloc[B0 - 1] : 0.0;                     // (w0 < B0: the tail block is the first of block KB and the 256 before it the end of block KB - 1)
+    for (unsigned t = threadIdx.x; t < 512; t += 256) {
+        const unsigned idx = w0 + t;
+        win[t] = (idx < MS && idx < g0 + 256) ? (idx < B0 ? Sloc[idx] - lastprev : Sloc[idx]) : 0.0;
+    }
     __syncthreads();
     unsigned g = g0 + threadIdx.x;
     if (g >= MS) return;
     const unsigned r = rank[g], b = sbase[r];
-    const double Sj = S[g];
-    bool unsure = !(Sj < 4194304.0) || (g - b) >= (1u << 20);
-    // smallest h in [b, g] with Sj - S[h] <= T.  The tail covers a few dozen samples, so the answer almost always lies in the block's LDS
-    // window (the 256 sums before the block + its own); otherwise gallop back through global memory, then bisect.
-    unsigned lo = b, hi = g;                 // answer in [lo, hi]; S[hi] satisfies (Sj - S[g] = 0 <= T)
+    const double Sj = Sloc[g];
+    bool unsure = !(Sj + (b < B0 ? lastprev : 0.0) < 4194304.0) || (g - b) >= (1u << 20);
+    // tail(p) = sum of the distances of samples p + 1 .. g, for b <= p <= g.  Below the window: the block sums between p's block and KB, kept while the
+    // search moves back (kc: the block reached, acc: L[KB-1] + ... + L[kc]).
+    unsigned kc = KB; double acc = 0.0;
+    auto tail = [&](unsigned p) -> double {
+        if (p >= w0) return Sj - win[p - w0];
+        const unsigned kb = p / ORIP_SMP_BLOCK;
+        if (KB - kb > ORIP_TAIL_BLOCKS) { unsure = true; return __longlong_as_double(0x7ff0000000000000LL); }      // too far back for the error bound: "does not fit", the replay decides
+        if (kb > kc) { kc = KB; acc = 0.0; }
+        while (kc > kb) { kc--; acc += Sloc[kc * ORIP_SMP_BLOCK + (ORIP_SMP_BLOCK - 1u)]; }
+        const double up = Sj + acc;
+        if (!(up < 4194304.0)) unsure = true;
+        return up - Sloc[p];
+    };
+    // smallest h in [b, g] with tail(h) <= T.  The tail covers a few dozen samples, so the answer almost always lies in the block's LDS
+    // window; otherwise gallop back through global memory, then bisect.
+    unsigned lo = b, hi = g;                 // answer in [lo, hi]; hi satisfies (tail(g) = 0 <= T)
     const unsigned wlo = max(b, w0);         // first index of my polyline inside the window
-    if (wlo == b || !(Sj - win[wlo - w0] <= T)) {
-        if (wlo > b) lo = wlo + 1; else lo = b;
-        if (wlo > b) { /* S[wlo] fails: answer in (wlo, g] */ }
-        else if (Sj - win[b - w0] <= T) hi = b;                           // the whole prefix fits
-        while (lo < hi) { const unsigned mid = (lo + hi) >> 1; if (Sj - win[mid - w0] <= T) hi = mid; else lo = mid + 1; }
+    if (wlo == b || !(tail(wlo) <= T)) {
+        if (wlo > b) lo = wlo + 1;           // wlo fails: answer in (wlo, g]
+        else if (tail(b) <= T) hi = b;       // the whole prefix fits
+        while (lo < hi) { const unsigned mid = (lo + hi) >> 1; if (tail(mid) <= T) hi = mid; else lo = mid + 1; }
     } else {
-        hi = wlo;                            // S[wlo] still satisfies: continue below the window in global memory
+        hi = wlo;                            // wlo still satisfies: continue below the window
         for (unsigned stepb = 1; hi > b; stepb <<= 1) {
             const unsigned p = (hi - b > stepb) ? hi - stepb : b;
-            if (Sj - S[p] <= T) { hi = p; if (p == b) break; } else { lo = p + 1; break; }
+            if (tail(p) <= T) { hi = p; if (p == b) break; } else { lo = p + 1; break; }
         }
-        while (lo < hi) { const unsigned mid = (lo + hi) >> 1; if (Sj - S[mid] <= T) hi = mid; else lo = mid + 1; }
+        while (lo < hi) { const unsigned mid = (lo + hi) >> 1; if (tail(mid) <= T) hi = mid; else lo = mid + 1; }
     }
     const unsigned h = lo;
-    if (!(Sj - S[h] <= T - ORIP_TAIL_EPS)) unsure = true;
-    if (h > b && !(Sj - S[h - 1] > T + ORIP_TAIL_EPS)) unsure = true;
+    if (!(tail(h) <= T - ORIP_TAIL_EPS)) unsure = true;
+    if (h > b && !(tail(h - 1) > T + ORIP_TAIL_EPS)) unsure = true;
     npop[g] = h - b;
     if (unsure) redo[r] = 1u;
 }
 // previous in-canvas sample of the same polyline (the far end of the capsule stamped when sample j is popped, 08:151-155); -1: none, -2: j is off-canvas
 // lastin[g] = 1 + index of the last in-canvas sample at or before g inside its polyline (0: none): a max-scan by polyline
-struct IncIndex {
+struct IncIndex {       // (the sentinel has every bit set, the first-sample flag included: an on-canvas word never equals it)
     const unsigned* pxy;
     __device__ unsigned operator()(unsigned g) const { return pxy[g] != ORIP_PXY_OUT ? g + 1u : 0u; }
 };
@@ -630,36 +713,45 @@ __device__ __forceinline__ unsigned long long hash64(unsigned long long x) { x ^
 // one 16-byte slot per capsule: key and first sequence number arrive in one memory sector (the table is far larger than the caches and
 // every probe is a random access: two arrays meant two sectors per probe)
 struct __attribute__((aligned(16))) CapSlot { unsigned long long key; unsigned val; unsigned pad; };
-__global__ __launch_bounds__(256) void k_caps_init(CapSlot* __restrict__ tab, unsigned long long tsize) {
+// Also clears the four counters of A4 / A5 (LaneFlags has the argument for each).
+__global__ __launch_bounds__(256) void k_caps_init(CapSlot* __restrict__ tab, unsigned long long tsize, LaneFlags* __restrict__ fl) {
     unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x;
+    if (i == 0) { fl->caps_overflow = 0; fl->caps_distinct = 0u; fl->accept_survivors = 0u; fl->accept_work = 0ull; }
     if (i < tsize) reinterpret_cast<uint4*>(tab)[i] = make_uint4(0u, 0u, 0xffffffffu, 0u);
 }
+// CP: capprev is given (some sample is off the canvas).  Without it every sample is on the canvas, the capsule of sample g runs from sample g - 1, and it has
+// one unless g is the first sample of its polyline -- which its own pxy word says (ORIP_PXY_FIRST): two independent loads and the table, no rank or base.
+template <bool CP>
 __global__ __launch_bounds__(256) void k_caps_insert(SampleArrs A, const unsigned* __restrict__ sbase, const int* __restrict__ capprev, unsigned MS,
                                                       CapSlot* tab, unsigned long long tmask, int max_probe, int* __restrict__ overflow) {
-    // Four samples per thread, a block's 1024 samples apart by 256: the chain rank -> base -> pixels -> slot is four dependent loads deep, and with one
-    // sample per thread the kernel waits for them one after the other (1 TB/s of the card's 8 with every wave slot full); four independent chains per
-    // thread keep four times as many loads in flight.
+    // Four samples per thread, a block's 1024 samples apart by 256: with one sample per thread the kernel waits for its chain of dependent loads one after the
+    // other (1 TB/s of the card's 8 with every wave slot full); four independent chains per thread keep four times as many loads in flight.  With capprev the
+    // chain is rank -> base -> pixels -> slot, without it pixels -> slot.
     constexpr int S = 4;
     const unsigned g0 = blockIdx.x * (256 * S) + threadIdx.x;
-    unsigned g[S], bb[S]; int cp[S]; bool on[S];
-#pragma unroll
-    for (int u = 0; u < S; u++) { g[u] = g0 + 256u * u; on[u] = g[u] < MS; bb[u] = on[u] ? A.rank[g[u]] : 0u; }
-#pragma unroll
-    for (int u = 0; u < S; u++) if (on[u]) bb[u] = sbase[bb[u]];
-#pragma unroll
-    for (int u = 0; u < S; u++) {
-        cp[u] = !on[u] ? -1 : (capprev ? capprev[g[u]] : (g[u] > bb[u] ? (int)(g[u] - bb[u]) - 1 : -1));      // capprev == nullptr: every sample is on the canvas, so the capsule runs from the previous sample
-        on[u] = cp[u] >= 0;
-    }
+    unsigned g[S]; bool on[S];
     unsigned long long key[S], h[S]; unsigned pa[S], pb[S];
 #pragma unroll
-    for (int u = 0; u < S; u++) {
-        key[u] = 0; h[u] = 0; pa[u] = 0; pb[u] = 0;
-        if (on[u]) pa[u] = A.pxy[bb[u] + cp[u]], pb[u] = A.pxy[g[u]];      // both on the canvas (cp >= 0): packed pixels
+    for (int u = 0; u < S; u++) { g[u] = g0 + 256u * u; on[u] = g[u] < MS; key[u] = 0; h[u] = 0; pa[u] = 0; pb[u] = 0; }
+    if constexpr (CP) {
+        unsigned bb[S]; int cp[S];
+#pragma unroll
+        for (int u = 0; u < S; u++) bb[u] = on[u] ? A.rank[g[u]] : 0u;
+#pragma unroll
+        for (int u = 0; u < S; u++) if (on[u]) bb[u] = sbase[bb[u]];
+#pragma unroll
+        for (int u = 0; u < S; u++) { cp[u] = on[u] ? capprev[g[u]] : -1; on[u] = cp[u] >= 0; }
+#pragma unroll
+        for (int u = 0; u < S; u++) if (on[u]) pa[u] = A.pxy[bb[u] + cp[u]], pb[u] = A.pxy[g[u]];      // both on the canvas (cp >= 0): packed pixels
+    } else {
+#pragma unroll
+        for (int u = 0; u < S; u++) if (on[u]) { pb[u] = A.pxy[g[u]]; pa[u] = g[u] ? A.pxy[g[u] - 1u] : 0u; }
+#pragma unroll
+        for (int u = 0; u < S; u++) on[u] = on[u] && !(pb[u] & ORIP_PXY_FIRST);
     }
 #pragma unroll
     for (int u = 0; u < S; u++) {
-        if (on[u]) { key[u] = cap_key((int)(pa[u] & 0xffffu), (int)(pa[u] >> 16), (int)(pb[u] & 0xffffu), (int)(pb[u] >> 16)); h[u] = hash64(key[u]) & tmask; }
+        if (on[u]) { key[u] = cap_key(pxy_x(pa[u]), pxy_y(pa[u]), pxy_x(pb[u]), pxy_y(pb[u])); h[u] = hash64(key[u]) & tmask; }
     }
     uint4 sl[S];
 #pragma unroll
@@ -746,7 +838,7 @@ __global__ __launch_bounds__(256) void k_accept_pre(SampleArrs A, const unsigned
 #pragma unroll
     for (int u = 0; u < S; u++) {
         np[u] = 0; xi[u] = 0; yi[u] = 0; ok[u] = false;
-        if (on[u]) { bb[u] = sbase[bb[u]]; const unsigned p = A.pxy[g[u]]; ok[u] = p != ORIP_PXY_OUT; np[u] = npop[g[u]]; xi[u] = (int)(p & 0xffffu); yi[u] = (int)(p >> 16); }
+        if (on[u]) { bb[u] = sbase[bb[u]]; const unsigned p = A.pxy[g[u]]; ok[u] = p != ORIP_PXY_OUT; np[u] = npop[g[u]]; xi[u] = pxy_x(p); yi[u] = pxy_y(p); }
     }
     unsigned fs[S];
 #pragma unroll
@@ -972,8 +1064,10 @@ int split_small(orip_ctx* c, DPolys& src, const orip_params08& P, DPolys& kept, 
     return 0;
 }
 
-__global__ __launch_bounds__(256) void k_fill_per(const PolyFeat* __restrict__ f, int64_t n, float* __restrict__ k, unsigned* __restrict__ v) {
+// Also clears the any-out word that k_rank_counts sets (A08::sbase has the argument).
+__global__ __launch_bounds__(256) void k_fill_per(const PolyFeat* __restrict__ f, int64_t n, float* __restrict__ k, unsigned* __restrict__ v, unsigned* __restrict__ any_out) {
     int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i == 0) *any_out = 0u;
     if (i < n) { k[i] = f[i].per; v[i] = (unsigned)i; }
 }
 
@@ -984,21 +1078,26 @@ struct A08 {
     int64_t nk;                                                     // kept polylines
     PolyFeat* feat;                                                 // VTL_FEAT: their open-view features (A0 -> k_rank_counts)
     unsigned *ord, *mr, *sbase; RsInfo* info;                       // VTL_RANKS: order by perimeter, samples per rank, sample bases (nk + 1, then the any-out word), lengths
+    // The any-out word, sbase[nk + 1], is cleared by k_fill_per (first kernel of A1, right behind the carve) and set by k_rank_counts (A2); in between run the
+    // perimeter sort (its own four arrays and tmpF) and the cumulative lengths (VTL_CUM, info, or the prefetch's buffers): nothing touches the word, and the side
+    // stream has no work of this call yet.  The read-back behind the scan of mr is its only reader.
+    unsigned* redo;                                                 // VTL_RANKS too: nk + 1 flags, polylines the sequential simulation redoes.  Cleared by k_rank_counts (A2); set
+    // by k_tail_par (A3), read by k_tail_replay on the side stream until ev3, which A5 awaits; between clearing and setting run the scan of mr, k_sample_hints and
+    // k_samples, which take mr, sbase, info, ord of this slot and never redo, and nothing of this call on the side stream.  VTL_RANKS stays until A6.
     double step; int64_t* cumoff; float* cum;                       // VTL_CUM, or the prefetch's cum: cumulative lengths and where each polyline's start
     unsigned MS; bool any_out;                                      // samples of the layer; some polyline leaves the canvas
-    SampleArrs A; unsigned* npop; int* capprev; uint8_t* sflag;     // VTL_SAMPLES: one entry per sample (capprev == nullptr: every sample is on the canvas)
+    SampleArrs A; unsigned* npop; int* capprev; uint8_t* sflag;     // VTL_SAMPLES: one entry per sample (capprev == nullptr: every sample is on the canvas); A.Sloc: VTL_TAIL_RUNS
     unsigned *ckin, *ckout, *cvin, *cvout; int2* hints;             // VTL_CELLS: cell keys / values of the bucket sort, hints of k_samples
     double cell, inv;                                               // side of a _PointHash cell and its inverse
     int Wq; unsigned* firstseq; unsigned long long* pixbits;        // canvas: first stamp per sample pixel; pixbits: the sample pixels, Wq words per row
-    unsigned* redo;                                                 // VTL_TAIL_RUNS, behind the MS tail sums: polylines the sequential simulation redoes
 };
 
 // ---- A1: order by perimeter, descending, stable
 static int a1_order(orip_ctx* c, A08& a) {
     const int64_t nk = a.nk; float *kin, *kout; unsigned* vin;
     { Carve L; L.each(nk, kin, kout, vin, a.ord); L.take(a.mr, nk + 1);
-      L.take(a.sbase, nk + 2); L.take(a.info, nk); HIPC(c, L.commit(LN(c).vtmp[VTL_RANKS], 256)); }      // sbase: nk + 1 sample bases, then the any-out word (one read-back fetches both)
-    hipLaunchKernelGGL(k_fill_per, dim3(cdiv(nk, 256)), dim3(256), 0, LN(c).stream, a.feat, nk, kin, vin);
+      L.take(a.sbase, nk + 2); L.take(a.info, nk); L.take(a.redo, nk + 1); HIPC(c, L.commit(LN(c).vtmp[VTL_RANKS], 256)); }      // sbase: nk + 1 sample bases, then the any-out word (one read-back fetches both)
+    hipLaunchKernelGGL(k_fill_per, dim3(cdiv(nk, 256)), dim3(256), 0, LN(c).stream, a.feat, nk, kin, vin, a.sbase + nk + 1);
     ORIP_TRY((vsort_pairs<float, unsigned>(c, kin, kout, vin, a.ord, (size_t)nk, 0, 32, true)));
     return 0;
 }
@@ -1020,8 +1119,7 @@ static int a2_resample(orip_ctx* c, const orip_params08& P, DPolys& kept0, A08& 
                 hipLaunchKernelGGL(k_cumlen_long2<decltype(sv)>, dim3((unsigned)std::min<int64_t>(nk, 8192), 1), dim3(64), 0, LN(c).stream, sv, nk, a.step, a.cum, (int64_t)0, a.info, a.ord, 0, (const float*)nullptr); }); }
     }
     T.tick("cumlen");
-    HIPC(c, hipMemsetAsync(a.sbase + nk + 1, 0, 4, LN(c).stream));
-    hipLaunchKernelGGL(k_rank_counts, dim3(cdiv(nk + 1, 256)), dim3(256), 0, LN(c).stream, a.info, a.ord, nk, a.mr, a.feat, W, H, a.sbase + nk + 1);
+    hipLaunchKernelGGL(k_rank_counts, dim3(cdiv(nk + 1, 256)), dim3(256), 0, LN(c).stream, a.info, a.ord, nk, a.mr, a.feat, W, H, a.sbase + nk + 1, a.redo);
     ORIP_TRY(vscan_excl<unsigned>(c, a.mr, a.sbase, (size_t)nk + 1));
     unsigned ms_out[2] = {0, 0};
     ORIP_TRY(vread(c, ms_out, a.sbase + nk, 2));                // the sample count and, with it, whether any polyline leaves the canvas
@@ -1030,6 +1128,7 @@ static int a2_resample(orip_ctx* c, const orip_params08& P, DPolys& kept0, A08& 
     if (MS > 0x7ffffff0u) ORIP_FAIL(c, "too many samples");
     if (T.on) { char b[48]; snprintf(b, sizeof b, " [MS %u]", MS); T.log += b; }
     { Carve L; L.each(MS, a.A.sx, a.A.sy, a.A.dprev, a.A.spt, a.A.pxy, a.A.rank, a.npop, a.capprev, a.sflag); HIPC(c, L.commit(LN(c).vtmp[VTL_SAMPLES], 1024)); }
+    { Carve L; L.take(a.A.Sloc, MS); HIPC(c, L.commit(LN(c).vtmp[VTL_TAIL_RUNS], 64)); }      // block-local tail sums: k_samples -> k_tail_par
     const unsigned nb = (unsigned)cdiv(MS, 256);
     { Carve L; L.each(MS, a.ckin, a.ckout, a.cvin, a.cvout); L.take(a.hints, nb + 1, 64);
       HIPC(c, L.commit(LN(c).vtmp[VTL_CELLS], 64 + (size_t)MS * 8)); }      // (8 MS: what two retired arrays took; no request shrinks with the layouts' restatement)
@@ -1061,11 +1160,8 @@ static void tail_dbg_dump(orip_ctx* c, int layer, const A08& a) {
 static int a3_tails(orip_ctx* c, int layer, const orip_params08& P, A08& a) {
     const int64_t nk = a.nk; const unsigned MS = a.MS;
     {
-        double* S; { Carve L; L.take(S, MS); L.take(a.redo, nk + 1); HIPC(c, L.commit(LN(c).vtmp[VTL_TAIL_RUNS], 64)); }
-        HIPC(c, hipMemsetAsync(a.redo, 0, (size_t)(nk + 1) * 4, LN(c).stream));
-        HIPC(c, orip_with_tmp(c, [&](void* tmp, size_t& bytes) { return rocprim::inclusive_scan_by_key(tmp, bytes, a.A.rank, a.A.dprev, S, (size_t)MS, rocprim::plus<double>(), rocprim::equal_to<unsigned>(), LN(c).stream); }));
         ProfScope ps(c, "k_tail_sim");
-        hipLaunchKernelGGL(k_tail_par, dim3(cdiv(MS, 256)), dim3(256), 0, LN(c).stream, a.sbase, a.A.rank, S, MS, P.tail_len_px, a.npop, a.redo);
+        hipLaunchKernelGGL(k_tail_par, dim3(cdiv(MS, 256)), dim3(256), 0, LN(c).stream, a.sbase, a.A.rank, a.A.Sloc, MS, P.tail_len_px, a.npop, a.redo);
         if (getenv("ORIP_TAIL_DBG")) tail_dbg_dump(c, layer, a);
         const unsigned* only = getenv("ORIP_TAIL_SEQ") ? nullptr : a.redo;          // test hook: force the sequential simulation everywhere
         // the sequential redo only feeds the acceptance test (A6): it runs on the lane's side stream under the capsule / hash work
@@ -1075,7 +1171,7 @@ static int a3_tails(orip_ctx* c, int layer, const orip_params08& P, A08& a) {
         HIPC(c, hipEventRecord(LN(c).ev3, LN(c).stream2));
     }
     if (a.any_out) {
-        unsigned* lastin = LN(c).vtmp[VTL_TAIL_RUNS].as<unsigned>();            // MS words over S: the prefix sums of the tail simulation are no longer needed (redo, behind S, stays)
+        unsigned* lastin = LN(c).vtmp[VTL_TAIL_RUNS].as<unsigned>();            // MS words over Sloc: k_tail_par has consumed the tail sums
         auto vin = rocprim::make_transform_iterator(rocprim::counting_iterator<unsigned>(0u), IncIndex{a.A.pxy});
         HIPC(c, orip_with_tmp(c, [&](void* tmp, size_t& bytes) { return rocprim::inclusive_scan_by_key(tmp, bytes, a.A.rank, vin, lastin, (size_t)MS, rocprim::maximum<unsigned>(), rocprim::equal_to<unsigned>(), LN(c).stream); }));
         hipLaunchKernelGGL(k_capprev, dim3(cdiv(MS, 256)), dim3(256), 0, LN(c).stream, a.sbase, MS, a.A, lastin, a.capprev);
@@ -1099,14 +1195,14 @@ static int a4_capsules(orip_ctx* c, const orip_params08& P, A08& a) {
     for (;; tsize = std::min(tfull, tsize * 4)) {
         HIPC(c, LN(c).vtmp[VTL_CAPS].ensure((size_t)tsize * 16 + 64));
         tab = LN(c).vtmp[VTL_CAPS].as<CapSlot>();
-        hipLaunchKernelGGL(k_caps_init, dim3((unsigned)cdiv(tsize, 256)), dim3(256), 0, LN(c).stream, tab, tsize);
-        HIPC(c, hipMemsetAsync(d_ovf, 0, 4, LN(c).stream));
+        hipLaunchKernelGGL(k_caps_init, dim3((unsigned)cdiv(tsize, 256)), dim3(256), 0, LN(c).stream, tab, tsize, fl);      // (and the counters of A4 / A5)
         const int max_probe = tsize >= tfull ? 0x7fffffff : 96;
-        { ProfScope ps(c, "k_caps_insert"); hipLaunchKernelGGL(k_caps_insert, dim3(cdiv(MS, 1024)), dim3(256), 0, LN(c).stream, a.A, a.sbase, a.capprev, MS, tab, tsize - 1, max_probe, d_ovf); }
+        { ProfScope ps(c, "k_caps_insert");
+          if (a.capprev) hipLaunchKernelGGL(k_caps_insert<true>, dim3(cdiv(MS, 1024)), dim3(256), 0, LN(c).stream, a.A, a.sbase, a.capprev, MS, tab, tsize - 1, max_probe, d_ovf);
+          else hipLaunchKernelGGL(k_caps_insert<false>, dim3(cdiv(MS, 1024)), dim3(256), 0, LN(c).stream, a.A, a.sbase, a.capprev, MS, tab, tsize - 1, max_probe, d_ovf); }
         int ovf = 0; ORIP_TRY(vread(c, &ovf, d_ovf));
         if (!ovf) break;
     }
-    HIPC(c, hipMemsetAsync(d_dist, 0, 4, LN(c).stream));
     {
         ProfScope ps(c, "k_caps_stamp");
         const dim3 sg((unsigned)std::min<unsigned long long>(tsize / 64 / 4 + 1, 16384));
@@ -1120,8 +1216,6 @@ static int a56_accept(orip_ctx* c, const orip_params08& P, A08& a, PhaseTimer& T
     HIPC(c, hipStreamWaitEvent(LN(c).stream, LN(c).ev3, 0));       // pop counts of the redone polylines
     unsigned* surv = LN(c).vtmp[VTL_TAIL_RUNS].as<unsigned>();      // MS words again (the scan results kept there have been consumed by k_capprev)
     unsigned* d_ns = &fl->accept_survivors; unsigned long long* d_work = &fl->accept_work;
-    HIPC(c, hipMemsetAsync(d_ns, 0, 4, LN(c).stream));
-    HIPC(c, hipMemsetAsync(d_work, 0, 8, LN(c).stream));
     { ProfScope ps(c, "k_accept"); hipLaunchKernelGGL(k_accept_pre, dim3(cdiv(MS, 1024)), dim3(256), 0, LN(c).stream, a.A, a.sbase, a.npop, MS, a.firstseq, P.W, a.sflag, surv, d_ns, d_work); }
     unsigned long long h_work = 0; ORIP_TRY(vread(c, &h_work, d_work));
     const double R2 = P.col_rad * P.col_rad;

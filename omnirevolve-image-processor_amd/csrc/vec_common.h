@@ -1,5 +1,8 @@
 // csrc/vec_common.h -- interface of the building blocks the vector stages (05, 07, 08, 10, 12) share: the types and the device-inline helpers here,
-// the functions and every kernel behind them in vector_common.hip.
+// the functions and every kernel behind them in three units:
+//   vector_common.hip    the rocPRIM wrappers (vscan_excl, vsort_pairs), vsrc_of, the gather family (vgather*, orip_polys_materialize), orip_runs_to_polys
+//   vector_features.hip  the per-polyline features with numpy's pairwise tree (vfeatures*, vlen_order, vwalk_arcs)
+//   vector_greedy.hip    the greedy nearest-neighbour order (vreorder: the brute-force kernel, the grid kernel with its asm step)
 #pragma once
 #include "orip_ctx.h"
 #include "vec_serial.h"
@@ -35,7 +38,7 @@ struct PolyFeat {
     int32_t x0, y0, x1, y1;     // bbox
     int32_t sx, sy, ex, ey;     // first / last point (of the OPEN view when open_view)
     int64_t n;                  // points (of the open view when open_view)
-    float per;                  // numpy pairwise float32 perimeter (KIND 0) or 12:_poly_len (KIND 1)
+    float per;                  // numpy pairwise float32 perimeter (VF_PER) or 12:_poly_len (VF_PER_HYPOT)
     double arc;                 // cv::arcLength (closed flag given by caller), exact double sum
     uint8_t closed;             // first == last on the ORIGINAL polyline (n >= 2)
 };
@@ -55,6 +58,12 @@ int vsrc_of(orip_ctx* c, const DPolys& P, VSrc& out);
         if (is_coded(P)) { VSrc SRC; ORIP_TRY(vsrc_of(c, P, SRC)); BODY }                      \
         else { const ESrc SRC = esrc_of(P); BODY }                                             \
     } while (0)
+// last index in [0, n) whose offset is <= v (off ascending, off[0] <= v): the polyline that holds point v of a list
+__device__ __forceinline__ int64_t last_le(const int64_t* off, int64_t n, int64_t v) {
+    int64_t lo = 0, hi = n - 1;
+    while (lo < hi) { const int64_t mid = (lo + hi + 1) >> 1; if (off[mid] <= v) lo = mid; else hi = mid - 1; }
+    return lo;
+}
 // first index in the ascending a[0 .. n) whose element is > v
 __device__ __forceinline__ int64_t ub_u32(const unsigned* a, int64_t n, unsigned v) {
     int64_t lo = 0, hi = n;
@@ -66,16 +75,26 @@ template <class Cur> struct CurPt {
     Cur& c;
     __device__ __forceinline__ vs::IPt operator()(int64_t i) const { const int2 p = c.at(i); return vs::IPt{p.x, p.y}; }
 };
-// features of every polyline of a list: short ones one lane each, long ones one block each.
-// what: bit0 perimeter KIND0, bit1 perimeter KIND1 (hypot), bit2 arcLength closed, bit3 arcLength open, bit4 open view (_ensure_open)
+// features of every polyline of a list: short ones one lane each, long ones one block each.  `what` is a mask of
+enum : int {
+    VF_PER = 1,             // PolyFeat::per = numpy's pairwise float32 perimeter (vec_serial.h KIND 0)
+    VF_PER_HYPOT = 2,       // PolyFeat::per = 12:_poly_len, the same tree over np.hypot lengths (KIND 1; stage 12's seed)
+    VF_ARC_CLOSED = 4,      // PolyFeat::arc = cv::arcLength(closed = true)
+    VF_ARC_OPEN = 8,        // PolyFeat::arc = cv::arcLength(closed = false)
+    VF_OPEN_VIEW = 16,      // features of the open view (_ensure_open): a closed polyline without its last point
+    VF_PER_REV = 32,        // with VF_PER: per_rev[i] = the same perimeter over the REVERSED open polyline (numpy's pairwise sum depends on the order)
+    VF_LEAVES_DONE = 64,    // long polylines: the leaf sums are in place (k_perim_leaves_seg), only combine them; set by vfeatures_long_seg alone
+};
 int vfeatures(orip_ctx* c, const DPolys& P, int what, PolyFeat* feat);
 // The same for stage 08's prefetch (vector08a.hip: orip_prefetch08), which runs them in three parts around its own kernels and events, each on LN(c).stream:
-// the short polylines' features and every polyline's end points (what: as vfeatures, and bit5 (with bit0): per_rev[i] = the same perimeter over the
-// REVERSED open polyline); order = the polylines longest first (kin, kout, vin: scratch of n words each); then the long polylines' perimeters in both
+// the short polylines' features and every polyline's end points (what: as vfeatures, per_rev for VF_PER_REV);
+// order = the polylines longest first (kin, kout, vin: scratch of n words each); then the long polylines' perimeters in both
 // directions from STORED segment lengths (seg[k] = float32 length of segment k, the bounding boxes already in feat; leaves in the lane's vtmp[VT_LEAVES]).
 void vfeatures_short(orip_ctx* c, const VSrc& src, int64_t n, int what, PolyFeat* feat, float* per_rev);
 int vlen_order(orip_ctx* c, const int64_t* off, int64_t n, unsigned* kin, unsigned* kout, unsigned* vin, unsigned* order);
 int vfeatures_long_seg(orip_ctx* c, const VSrc& src, int64_t n, int64_t total, PolyFeat* feat, const unsigned* order, float* per_rev, const float* seg);
+// cv::arcLength(closed = true) of the long contours of a list of whole walks, from the walk records (k_walk_arcs); vfeatures_short has done the short ones
+void vwalk_arcs(orip_ctx* c, const VSrc& src, int64_t n, PolyFeat* feat);
 
 // ---- descriptor-driven gather: output polyline k = src points [begin[k], begin[k]+len[k]) (reversed if rev[k]) ----
 struct GatherDesc { int64_t begin; int64_t len; int32_t rev; int32_t src; };     // src: index of the source polyline (walk-coded sources are addressed by polyline, not by point)

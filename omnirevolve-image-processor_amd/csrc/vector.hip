@@ -337,7 +337,7 @@ extern "C" int orip_plot_order(orip_ctx* c, int layer, double R_insert, int64_t*
     { Carve S; S.take(feat, std::max<int64_t>(nl, 1)); S.take(alive_l, nl); S.take(alive_t, nt); HIPC(c, S.commit(LN(c).vtmp[VTL_FEAT], 256)); }
     HIPC(c, c->ops[layer].ensure((size_t)(nl + nt) * 20 + 64));
     HIPC(c, T.xy.ensure(64));
-    if (nl) ORIP_TRY(vfeatures(c, L, 2, feat));
+    if (nl) ORIP_TRY(vfeatures(c, L, VF_PER_HYPOT, feat));
     int* d_n = &LN(c).flags.as<LaneFlags>()->plot_ops;
     const size_t lds = (size_t)nl * 17 + (size_t)nt * 9 + 64;
     if (lds <= 150 * 1024 && !getenv("ORIP_PLOT_1WG")) {

@@ -997,7 +997,7 @@ int orip_prefetch08(orip_ctx* c, const orip_params08& P, DPolys& S, const PolyFe
         PolyFeat* ff = F.feat.as<PolyFeat>(); float* per_rev = reinterpret_cast<float*>(ff + n); RsInfo* inf = F.info.as<RsInfo>(); float* cum = F.cum.as<float>();
         VSrc sS; ORIP_TRY(vsrc_of(c, S, sS));
         // per-polyline fields first (open view, end points; bounding box and perimeters of the short ones): one thread per polyline
-        vfeatures_short(c, sS, n, 1 | 16 | 32, ff, per_rev);
+        vfeatures_short(c, sS, n, VF_PER | VF_OPEN_VIEW | VF_PER_REV, ff, per_rev);
         // A2 (the long polylines): cumulative lengths of both readings, longest first.  k_seglen fetches the points (once each) and leaves every segment's
         // float32 length in F.seg and the open view's bounding box in ff; both readings and the perimeter sums (A0 / A1, forwards and backwards) then
         // read 4 bytes per segment instead of turning (polyline, index) into a point again.
@@ -1043,7 +1043,7 @@ int split_small(orip_ctx* c, DPolys& src, const orip_params08& P, DPolys& kept, 
     if (kept_feat && is_coded(src) && src.pf_tag && F.valid && F.tag == src.pf_tag && !src.vident) {      // computed under stage 07's greedy, per walk and direction
         if (F.pending) HIPC(c, hipStreamWaitEvent(LN(c).stream, LN(c).ev4, 0));
         hipLaunchKernelGGL(k_pf_pick_feat, dim3(cdiv(n, 256)), dim3(256), 0, LN(c).stream, src.vview.as<VView>(), n, F.feat.as<PolyFeat>(), reinterpret_cast<const float*>(F.feat.as<PolyFeat>() + F.n), sfeat);
-    } else { HIPC(c, orip_pf08_drain(c)); ORIP_TRY(vfeatures(c, src, kept_feat ? (1 | 16) : 0, sfeat)); }      // (the prefetch shares vfeatures' scratch)
+    } else { HIPC(c, orip_pf08_drain(c)); ORIP_TRY(vfeatures(c, src, kept_feat ? (VF_PER | VF_OPEN_VIEW) : 0, sfeat)); }      // (the prefetch shares vfeatures' scratch)
     { ProfScope ps(c, "k_split_small08"); ORIP_WITH_SRC(c, src, sv, { hipLaunchKernelGGL(k_split_small08<decltype(sv)>, dim3(cdiv(n + 1, 128)), dim3(128), 0, LN(c).stream, sv, n, P, sfeat, is_tap, is_keep, tap_xy, kd); }); }
     ORIP_TRY(vscan_excl<unsigned>(c, is_tap, tap_scan, (size_t)n + 1));
     ORIP_TRY(vscan_excl<unsigned>(c, is_keep, keep_scan, (size_t)n + 1));

@@ -561,7 +561,7 @@ struct B08 {
 static int b_groups(orip_ctx* c, const orip_params08& P, DPolys& lines2, B08& b) {
     const int64_t n2 = b.n2; const int exp = P.post_brush * 2 + 6;
     { Carve L; L.take(b.f2, n2); L.each(n2 + 1, b.par, b.is_root, b.root_scan); L.take(b.grp, n2); HIPC(c, L.commit(LN(c).vtmp[VTL_FEAT], 256)); }
-    ORIP_TRY(vfeatures(c, lines2, 1, b.f2));
+    ORIP_TRY(vfeatures(c, lines2, VF_PER, b.f2));
     hipLaunchKernelGGL(k_iota, dim3(cdiv(n2, 256)), dim3(256), 0, LN(c).stream, b.par, (int)n2);
     { ProfScope ps(c, "k_bbox_pairs"); hipLaunchKernelGGL(k_bbox_pairs, dim3((unsigned)std::min<int64_t>(n2, 8192)), dim3(256), 0, LN(c).stream, b.f2, (int)n2, exp, b.par); }
     hipLaunchKernelGGL(k_group_init, dim3(cdiv(n2, 256)), dim3(256), 0, LN(c).stream, b.grp, (int)n2);

@@ -9,7 +9,7 @@
 //   a plane holds, per pixel, the LARGEST coverage of any primitive, as round(255 a) -- the reference draws one line after the other, so where lines
 //   overlap its anti-aliased fringes get darker than here; the host composes colour = (background (255 - A) + colour A + 127) / 255.
 // All arithmetic in float64 in the same order on both sides (no fused multiply-add: -ffp-contract=off).
-#include "orip_ctx.h"
+#include "vec_common.h"
 
 namespace {
 __device__ __forceinline__ int cover_u8(double a) { a = a < 0.0 ? 0.0 : (a > 1.0 ? 1.0 : a); return (int)floor(__dadd_rn(__dmul_rn(a, 255.0), 0.5)); }
@@ -19,8 +19,7 @@ __global__ __launch_bounds__(256) void k_prev_lines(const int64_t* __restrict__ 
                                                     double half, int aa, int* __restrict__ plane) {
     const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (k + 1 >= total) return;
-    int64_t lo = 0, hi = n_polys - 1;                      // polyline of point k: the last i with off[i] <= k
-    while (lo < hi) { const int64_t mid = (lo + hi + 1) >> 1; if (off[mid] <= k) lo = mid; else hi = mid - 1; }
+    const int64_t lo = last_le(off, n_polys, k);           // polyline of point k
     if (k + 1 >= off[lo + 1]) return;                      // k is the last point of its polyline
     const int2 p0 = pts[k], p1 = pts[k + 1];
     const int r = (int)ceil(half + 0.5);

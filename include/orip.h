@@ -237,10 +237,24 @@ typedef struct {
 int orip_gcode_to_steps(orip_ctx* ctx, const int64_t* off /* [n+1] or NULL */, const double* pts_mm /* [off[n],2] or NULL */, int64_t n, const orip_gcode_map* map,
                         int64_t* n_out, int64_t* total_out);
 int orip_gcode_steps_fetch(orip_ctx* ctx, int64_t* off_out /* [n_out+1] */, int32_t* pts_out /* [total_out,2] or NULL */);
+/* src_out[k] = the index of the input path that step polyline k came from (ascending: the conversion drops paths, it never reorders them). */
+int orip_gcode_steps_source_fetch(orip_ctx* ctx, int32_t* src_out /* [n_out] */);
 /* order_paths_nearest (:151-172) from (0, 0): order_out[k] = index of the k-th path to draw -- the remaining path whose FIRST point has the smallest
  * L1 distance from the cursor, the lowest index on ties; the cursor moves to that path's LAST point; paths are never reversed.  Exact for every input.
  * ends: (first x, first y, last x, last y) per path, coordinates 0..2^30, or NULL for the resident step polylines (n must then be their count). */
 int orip_gcode_order(orip_ctx* ctx, const int32_t* ends /* [n,4] or NULL */, int64_t n, int32_t* order_out /* [n] */);
+/* The order of the reference's demo sheet (stream_generators/plotter_demo/omnirevolve_plotter_demo.py: order_paths_nearest :197-216 inside
+ * draw_color_group :317-333 called for one pen after the other): the cursor starts at start_xy; for g = 0 .. n_groups - 1 in turn, while paths of group g
+ * remain, the minimum of the key (L1 distance << 32) | (2 i + r) over the remaining paths i of that group is taken, r = 0 for the path's first point and
+ * r = 1 for its last one, the latter only with ORIP_ORDER_REVERSE; order_out[k] = i, rev_out[k] = r, and the cursor moves to the OTHER end of path i.  The
+ * cursor carries over from one group to the next; empty groups are legal.  That key is the reference's scan (in index order d_fwd < best, then
+ * d_rev < best, both strict).  Exact for every input.  With one group, no flag and start_xy == NULL the result is orip_gcode_order's.
+ * ends as for orip_gcode_order; n <= 2^26; group[i] in 0 .. n_groups - 1, n_groups in 1..64; start_xy in 0..2^30.  Anything else is an error before any
+ * launch; n == 0 returns before any launch. */
+#define ORIP_ORDER_REVERSE 1
+#define ORIP_ORDER_MAX_GROUPS 64
+int orip_gcode_order_pens(orip_ctx* ctx, const int32_t* ends /* [n,4] or NULL = resident step polylines */, const int32_t* group /* [n], 0..n_groups-1 */, int64_t n,
+                          int32_t n_groups /* 1..64 */, int32_t flags, const int32_t* start_xy /* [2], NULL = (0,0) */, int32_t* order_out /* [n] */, uint8_t* rev_out /* [n] */);
 /* StreamWriter.add_steps / finalize (helper :55-68, :166-175) for a whole plot: the bytes of the stream from the direction codes orip_stream_codes left
  * resident.  Piece i reads cnt[i] codes from code0[i] on and owns the bytes from pos[i]: its speed byte when speed[i] >= 0, then (cnt[i] + 1) / 2 step bytes
  * (two codes per byte, paired inside the piece, the last byte of an odd piece holds one).  Pieces are listed in byte order, each at least one byte, none
@@ -292,6 +306,8 @@ int orip_svg_fit(orip_ctx* ctx, double sx, double sy, double ox, double oy);
 #define ORIP_HATCH_VERTICAL 4
 int orip_svg_hatch(orip_ctx* ctx, const int32_t* fill_group /* [n_sub] */, int64_t n_sub, double steps_per_mm, int32_t spacing, int32_t inset, int32_t flags,
                    int64_t* stats /* [4]: groups, lines, crossings, segments */);
+/* group_out[k] = the fill group, as the caller numbered it, of the k-th hatch line orip_svg_hatch appended (k counts from the first appended path). */
+int orip_svg_hatch_groups_fetch(orip_ctx* ctx, int32_t* group_out /* [segments] */);
 
 /* ---- multi-GPU exchange (no counterpart in the reference, which is a single process) ----
  * One process per GPU; rank r owns the cluster layers {l : l % world == r} for stages 03-08 and 12.  Stage 10 is replicated and needs

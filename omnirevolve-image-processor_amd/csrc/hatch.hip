@@ -211,7 +211,8 @@ __global__ __launch_bounds__(256) void k_ht_pairs(const double* __restrict__ xs,
 
 __global__ __launch_bounds__(256) void k_ht_emit(const double* __restrict__ xs, const unsigned* __restrict__ crow, const unsigned* __restrict__ keep, const unsigned* __restrict__ kpos, int64_t X,
                                                  const long long* __restrict__ rowbase, int64_t G, const long long* __restrict__ y0, int spacing, int inset, int serpentine, int vert,
-                                                 double spm, int64_t n0, int64_t t0, int64_t S, long long* __restrict__ off_out, double2* __restrict__ pts_out) {
+                                                 double spm, int64_t n0, int64_t t0, int64_t S, long long* __restrict__ off_out, double2* __restrict__ pts_out, const int* __restrict__ gnum,
+                                                 int* __restrict__ grp_out) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= X || !keep[i]) return;
     const int64_t s = kpos[i];
@@ -227,11 +228,12 @@ __global__ __launch_bounds__(256) void k_ht_emit(const double* __restrict__ xs, 
     pts_out[t0 + 2 * s] = vert ? make_double2(l, a) : make_double2(a, l);
     pts_out[t0 + 2 * s + 1] = vert ? make_double2(l, b) : make_double2(b, l);
     off_out[n0 + s + 1] = t0 + 2 * (s + 1);
+    grp_out[s] = gnum[lo];                                                   // the caller's number of the owning group
 }
 
 struct HtPlan {                       // what the directions share: the quantised points (ht_pts) and where the next segments go
-    int2* q; int *pgrp, *nxt, *box; HtCounters* cn; long long *y0, *nl, *rowbase, *chunkn, *chunkoff;
-    int64_t G, total, n, tot; int spacing, inset, serpentine; double spm;
+    int2* q; int *pgrp, *nxt, *box, *gnum; HtCounters* cn; long long *y0, *nl, *rowbase, *chunkn, *chunkoff;
+    int64_t G, total, n, tot, n_sub; int spacing, inset, serpentine; double spm;
 };
 
 // one direction: appends its segments behind path P.n / point P.tot (not committed) and moves both on
@@ -291,9 +293,10 @@ int ht_direction(orip_ctx* c, HtPlan& P, int vert, int64_t* stats) {
     const int64_t n1 = P.n + S, t1 = P.tot + 2 * (int64_t)S;
     if (n1 >= HT_MAX_POINTS || t1 > HT_MAX_POINTS) ORIP_FAIL(c, "%lld paths with %lld points after hatching: at most 2^30 - 2 paths and 2^30 - 1 points", (long long)n1, (long long)t1);
     HIPC(c, c->sv_off.ensure((size_t)(n1 + 1) * 8 + 64, s, true)); HIPC(c, c->sv_pts.ensure((size_t)t1 * 16 + 64, s, true));
+    HIPC(c, c->ht_grp.ensure((size_t)(n1 - P.n_sub) * 4 + 64, s, true));
     { ProfScope ps(c, "k_ht_emit");
       hipLaunchKernelGGL(k_ht_emit, dim3(cdiv(X, 256)), dim3(256), 0, s, xs2, crow, keep, kpos, (int64_t)X, P.rowbase, G, P.y0, P.spacing, P.inset, P.serpentine, vert, P.spm, P.n, P.tot, (int64_t)S,
-                         c->sv_off.as<long long>(), c->sv_pts.as<double2>()); }
+                         c->sv_off.as<long long>(), c->sv_pts.as<double2>(), P.gnum, c->ht_grp.as<int>() + (P.n - P.n_sub)); }
     HIPC(c, hipGetLastError());
     HIPC(c, hipStreamSynchronize(s));
     P.n = n1; P.tot = t1;
@@ -325,15 +328,19 @@ extern "C" int orip_svg_hatch(orip_ctx* c, const int32_t* fill_group, int64_t n_
     for (int64_t p = 0; p < n_sub; p++) if (fill_group[p] >= 0) gid[p] = rank[fill_group[p]];
     stats[0] = G;
     const int64_t total = c->sv_total;
+    c->ht_nseg = 0;
     if (G == 0 || total == 0) { c->sv_hatched = true; return 0; }
+    std::vector<int32_t> gnum((size_t)G, 0);                                  // rank -> the caller's number
+    for (int64_t p = 0; p < n_sub; p++) if (gid[p] >= 0) gnum[gid[p]] = fill_group[p];
     hipStream_t s = LN(c).stream;
     HtPlan P{};
     int* d_gid;
     { Carve L; L.take(d_gid, (size_t)n_sub); L.take(P.q, (size_t)total); L.take(P.pgrp, (size_t)total); L.take(P.nxt, (size_t)total); L.take(P.box, (size_t)4 * G); L.take(P.cn, 1);
       L.take(P.y0, (size_t)G); L.take(P.nl, (size_t)G + 1); L.take(P.rowbase, (size_t)G + 1); L.take(P.chunkn, (size_t)total + 1); L.take(P.chunkoff, (size_t)total + 1);
-      HIPC(c, L.commit(c->ht_pts, 64)); }
-    P.G = G; P.total = total; P.n = c->sv_n; P.tot = total; P.spacing = spacing; P.inset = inset; P.serpentine = flags & ORIP_HATCH_SERPENTINE ? 1 : 0; P.spm = steps_per_mm;
+      L.take(P.gnum, (size_t)G); HIPC(c, L.commit(c->ht_pts, 64)); }
+    P.G = G; P.total = total; P.n = c->sv_n; P.n_sub = c->sv_n; P.tot = total; P.spacing = spacing; P.inset = inset; P.serpentine = flags & ORIP_HATCH_SERPENTINE ? 1 : 0; P.spm = steps_per_mm;
     HIPC(c, hipMemcpyAsync(d_gid, gid.data(), (size_t)n_sub * 4, hipMemcpyHostToDevice, s));
+    HIPC(c, hipMemcpyAsync(P.gnum, gnum.data(), (size_t)G * 4, hipMemcpyHostToDevice, s));
     HIPC(c, hipMemsetAsync(P.cn, 0, sizeof(HtCounters), s));
     hipLaunchKernelGGL(k_ht_box_init, dim3(cdiv(G, 256)), dim3(256), 0, s, P.box, G);
     { ProfScope ps(c, "k_ht_quant");
@@ -344,6 +351,19 @@ extern "C" int orip_svg_hatch(orip_ctx* c, const int32_t* fill_group, int64_t n_
     if (h.err) ORIP_FAIL(c, "a coordinate reaches 2^30 hatch units at %g steps per mm", steps_per_mm);
     if (flags & ORIP_HATCH_HORIZONTAL) ORIP_TRY(ht_direction(c, P, 0, stats));
     if (flags & ORIP_HATCH_VERTICAL) ORIP_TRY(ht_direction(c, P, 1, stats));
+    c->ht_nseg = P.n - c->sv_n;
     c->sv_n = P.n; c->sv_total = P.tot; c->sv_hatched = true; c->sv_box_ok = false;
+    return 0;
+}
+
+extern "C" int orip_svg_hatch_groups_fetch(orip_ctx* c, int32_t* group_out) {
+    orip_enter(c);
+    ORIP_LANE(c, ORIP_LANE_CROSS);
+    if (!c->sv_ready || !c->sv_hatched) ORIP_FAIL(c, "no hatch lines: orip_svg_hatch has not succeeded on the resident paths");
+    if (c->ht_nseg == 0) return 0;
+    if (!group_out) ORIP_FAIL(c, "bad arguments");
+    hipStream_t s = LN(c).stream;
+    HIPC(c, hipMemcpyAsync(group_out, c->ht_grp.p, (size_t)c->ht_nseg * 4, hipMemcpyDeviceToHost, s));
+    HIPC(c, hipStreamSynchronize(s));
     return 0;
 }

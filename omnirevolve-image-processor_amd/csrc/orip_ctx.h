@@ -326,6 +326,9 @@ struct orip_ctx {
     // gcode2stream (gcode.hip): scratch of the conversion, the resident step polylines (off int64[gc_n + 1], pts int2[gc_total]) between orip_gcode_to_steps and
     // the fetch / orip_gcode_order, ends + order and the grid of the order, the piece table and the packed bytes between orip_stream_pack and its fetch
     DBuf gc_tmp, gc_off, gc_pts, gc_ends, gc_grid, pk_tab, pk_out; int64_t gc_n = 0, gc_total = 0, pk_bytes = -1; bool gc_ready = false;
+    // resident next to the step polylines: gc_src int32[gc_n] = the input path every step polyline came from (orip_gcode_steps_source_fetch); scratch of
+    // orip_gcode_order_pens: op_ends = ends, groups, results, boxes and group descriptors, op_grid = the cell grids of all groups and the slot table
+    DBuf gc_src, op_ends, op_grid;
     // svg2stream (svg.hip): scratch of the flattening and of the box, the resident paths (off int64[sv_n + 1], pts double2[sv_total]; raw units after
     // orip_svg_flatten, page mm after orip_svg_fit) until the next flatten; orip_gcode_to_steps reads them when it is called without pointers
     DBuf sv_tmp, sv_tmp2, sv_off, sv_pts; int64_t sv_n = 0, sv_total = 0; bool sv_ready = false, sv_box_ok = false; double sv_box[4] = {0, 0, 0, 0};
@@ -333,6 +336,8 @@ struct orip_ctx {
     // next flatten).  Scratch, free between calls: ht_pts = the quantised points with their group and successor, the groups' boxes and the call's counters;
     // ht_rows = one direction's line ranges per group, chunk counts per edge and crossing counts per row; ht_x = its crossings, unsorted and sorted
     DBuf ht_pts, ht_rows, ht_x; bool sv_fitted = false, sv_hatched = false;
+    // resident after orip_svg_hatch: ht_grp int32[ht_nseg] = the caller's fill group of every appended hatch line (orip_svg_hatch_groups_fetch)
+    DBuf ht_grp; int64_t ht_nseg = 0;
     // analyze_colors (analyze.hip): the 2^24-bin table of the image's colours, the kept colours in key order (keys u32[an_D], counts int64[an_D]) resident from
     // orip_colors_table until the next image or table; an_tmp = AnState + the compaction's block counts / offsets, an_km = the k-means inits, their segment
     // sums, mind2 int32[n_init, an_D] and labels u8[n_init, an_D] (free between calls)

@@ -394,6 +394,37 @@ class Device:
         self._ck(self.L.orip_gcode_order(self.h, _p(e) if ends is not None and n else None, int(n), _p(order)))
         return order[:int(n)]
 
+    def gcode_order_pens(self, ends: np.ndarray | None, group, n_groups: int, reverse: bool = False, start=(0, 0), n: int | None = None) -> Tuple[np.ndarray, np.ndarray]:
+        """group after group from `start`, inside a group the nearest remaining end (include/orip.h: orip_gcode_order_pens) -> (order int32 [n], rev bool [n]);
+        ends int32 [n, 4] or None for the n resident step polylines, group int32 [n] in 0 .. n_groups - 1, reverse: strokes may be drawn backwards"""
+        g = np.ascontiguousarray(group, np.int32).reshape(-1)
+        if ends is not None:
+            e = np.ascontiguousarray(ends, np.int32).reshape(-1, 4)
+            n = len(e)
+        n = len(g) if n is None else int(n)
+        if len(g) != n:
+            raise ValueError(f"{len(g)} groups given for {n} paths")
+        st = np.asarray(start, np.int64).reshape(-1)
+        if len(st) != 2 or (st < 0).any() or (st > 1 << 30).any():
+            raise OripError(f"start {tuple(st.tolist())} outside 0..2^30")
+        st = np.ascontiguousarray(st, np.int32)
+        order = np.zeros(max(n, 1), np.int32); rev = np.zeros(max(n, 1), np.uint8)
+        self._ck(self.L.orip_gcode_order_pens(self.h, _p(e) if ends is not None and n else None, _p(g) if n else None, n, int(n_groups), _l.ORDER_REVERSE if reverse else 0,
+                                              _p(st), _p(order), _p(rev)))
+        return order[:n], rev[:n].astype(bool)
+
+    def gcode_steps_source(self, n: int) -> np.ndarray:
+        """for each of the n resident step polylines of gcode_to_steps the index of the input path it came from (int32 [n])"""
+        src = np.zeros(max(int(n), 1), np.int32)
+        self._ck(self.L.orip_gcode_steps_source_fetch(self.h, _p(src)))
+        return src[:int(n)]
+
+    def svg_hatch_groups(self, segments: int) -> np.ndarray:
+        """the caller's fill group of every hatch line svg_hatch appended (int32 [segments], the count svg_hatch returned)"""
+        out = np.zeros(max(int(segments), 1), np.int32)
+        self._ck(self.L.orip_svg_hatch_groups_fetch(self.h, _p(out)))
+        return out[:int(segments)]
+
     def stream_pack(self, table, codes=None) -> bytes:
         """bytes of a piece table (orip.stream.PieceTable) from the resident direction codes; `codes` is what stream_codes(..., fetch_codes=False) returned (None)"""
         if codes is not None:

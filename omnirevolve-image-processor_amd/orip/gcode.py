@@ -8,7 +8,13 @@ orip/stream.py, and the byte position of every piece -- flat numpy over ALL path
 
 Everything that decides a byte follows the reference in meaning: comment and word rules of the parser, unit and mode switches inside a line, pen
 state before motion, float64 arithmetic of the conversion, round half to even, the (L1 distance, index) order, the command sequence of the emitter,
-the dividers after --speed-scale.  The device steps are injectable so that this host logic can be tested without a GPU; the product has no CPU path."""
+the dividers after --speed-scale.  The device steps are injectable so that this host logic can be tested without a GPU; the product has no CPU path.
+
+Pens (ours on this front door; the reference's gcode2stream.py draws everything with --color-index).  With a pen per path (--tool-pens: the T words of
+the text; svg2stream --pen-colors: the stroke colours) the paths are drawn pen after pen, in --pen-order, each pen's paths in nearest-neighbour order from
+where the pen before it stopped, with one colour byte per pen: draw_color_group of the reference's demo sheet (stream_generators/plotter_demo/
+omnirevolve_plotter_demo.py :317-333) called for one pen after the other.  --allow-reverse lets that order draw a stroke backwards when its far end is
+nearer (the demo's order_paths_nearest :197-216); both run on the device (orip_gcode_order_pens).  Without these options nothing changes."""
 from __future__ import annotations
 
 import argparse
@@ -54,6 +60,9 @@ class GcodeOptions:
     short_div: int = 16
     speed_scale: float = 1.0
     no_reorder: bool = False
+    allow_reverse: bool = False         # ours from here on: strokes may be drawn backwards
+    tool_pens: bool = False             # T words of the text choose the pen of a path
+    pen_order: Optional[str] = None     # pens in drawing order, comma-separated (default: ascending)
 
 
 # ------------------------------------------------------------------ parse (:113-142, :177-300)
@@ -69,11 +78,16 @@ def _code_lines(text: str) -> List[str]:
     return out
 
 
-def parse_gcode(text: Union[str, bytes]) -> Tuple[np.ndarray, np.ndarray, int]:
+MAX_PENS = 8
+
+
+def parse_gcode(text: Union[str, bytes], pens_out: Optional[List[int]] = None) -> Tuple[np.ndarray, np.ndarray, int]:
     """Pen-down paths of a G-code text: (off int64 [n + 1], pts_mm float64 [total, 2], pen-down moves).  Path p is pts_mm[off[p]:off[p + 1]], always two
     points or more.  Words are whitespace-separated, letter + number; a word whose number does not parse is skipped whole.  G90 / G91 and G20 / G21 act
     where they stand in the line; M3 / M4 lower the pen, M5 lifts it, a Z word lowers it iff z <= 0 unless an M word of the line decided; the pen moves
-    before the line's motion, and lifting it closes the path.  int(float("inf")) raises, as in the reference: such a file is refused."""
+    before the line's motion, and lifting it closes the path.  int(float("inf")) raises, as in the reference: such a file is refused.
+    T words are skipped, as in the reference, unless a list is given as pens_out: then it receives, per path, the tool in force at the path's first
+    pen-down move (-1: no T word seen so far), and a tool outside 0..7 is an error."""
     if isinstance(text, (bytes, bytearray)):
         text = bytes(text).decode("utf-8", errors="ignore")
     x = y = 0.0
@@ -82,11 +96,14 @@ def parse_gcode(text: Union[str, bytes]) -> Tuple[np.ndarray, np.ndarray, int]:
     off = [0]
     open_from = 0                                     # len(flat) where the open path starts (== len(flat): none open)
     moves = 0
+    tool = open_tool = -1
 
     def close():
         nonlocal open_from
         if len(flat) - open_from >= 2:
             off.append(len(flat))
+            if pens_out is not None:
+                pens_out.append(open_tool)
         else:
             del flat[open_from:]
         open_from = len(flat)
@@ -102,11 +119,17 @@ def parse_gcode(text: Union[str, bytes]) -> Tuple[np.ndarray, np.ndarray, int]:
                     code = int(float(num))             # OverflowError (Ginf) is not caught: the reference fails there too
                 elif letter in "XYZ":
                     v = float(num)
+                elif letter == "T" and pens_out is not None:
+                    code = int(float(num))
                 else:
                     continue
             except ValueError:
                 continue
-            if letter == "G":
+            if letter == "T":
+                if not (0 <= code < MAX_PENS):
+                    raise ValueError(f"tool T{code}: the plotter has pens 0..{MAX_PENS - 1}")
+                tool = code
+            elif letter == "G":
                 if code == 90: absolute = True
                 elif code == 91: absolute = False
                 elif code == 21: metric = True
@@ -136,7 +159,7 @@ def parse_gcode(text: Union[str, bytes]) -> Tuple[np.ndarray, np.ndarray, int]:
                 y = y + ny if ny is not None else y
             if down:
                 if len(flat) == open_from:
-                    flat.append((ox, oy))
+                    flat.append((ox, oy)); open_tool = tool
                 flat.append((x, y))
                 moves += 1
     close()
@@ -179,14 +202,67 @@ def stream_config(o: GcodeOptions) -> ST.StreamConfig:
 EMPTY_STREAM = bytes([ST.EOF_BYTE]) + b"\x00" * (ST.SPI_CHUNK_SIZE - 1)    # no paths: the end byte and padding, without the three leading bytes (:364-391)
 
 
+def pen_sequence(pen_order: Optional[str]) -> List[int]:
+    """--pen-order as the drawing sequence of all eight pens: the listed ones first, in the order given, the others behind them ascending"""
+    seq: List[int] = []
+    for tok in (pen_order or "").split(","):
+        if not tok.strip():
+            continue
+        try:
+            p = int(tok)
+        except ValueError:
+            raise ValueError(f"--pen-order: {tok.strip()!r} is not a pen number")
+        if not (0 <= p < MAX_PENS) or p in seq:
+            raise ValueError(f"--pen-order: pen {p} is outside 0..{MAX_PENS - 1} or listed twice")
+        seq.append(p)
+    return seq + [p for p in range(MAX_PENS) if p not in seq]
+
+
+def gather_paths(off: np.ndarray, pts: np.ndarray, order: np.ndarray, rev: Optional[np.ndarray] = None) -> Tuple[np.ndarray, np.ndarray]:
+    """the paths in the given order, those with rev[k] set back to front: (off, pts), flat numpy over all paths"""
+    order = np.asarray(order, np.int64)
+    lens = np.diff(off)[order]
+    noff = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    t = np.arange(int(lens.sum())) - np.repeat(noff[:-1], lens)
+    if rev is not None:
+        t = np.where(np.repeat(np.asarray(rev, bool), lens), np.repeat(lens, lens) - 1 - t, t)
+    return noff, pts[np.repeat(off[:-1][order], lens) + t]
+
+
+def plan_pens(off: np.ndarray, pts: np.ndarray, path_pen: np.ndarray, head: Sequence[int], sc: ST.StreamConfig) -> ST.Plan:
+    """The plan of paths in drawing order whose pens come in runs (path_pen[k]: the pen of path k), from (0, 0): the service bytes `head`, then per run
+    what draw_color_group does (:317-333) -- the approach to the run's first point when the cursor is elsewhere, the colour byte, and per path a travel
+    when the cursor is elsewhere, pen down, the segments, pen up.  The pattern of orip.stream.plan_layers, every move by the same engine."""
+    off = np.asarray(off, np.int64); pts = np.asarray(pts, np.int64).reshape(-1, 2); path_pen = np.asarray(path_pen, np.int64)
+    plans = [ST.fixed_plan(list(head))]
+    cur = np.zeros(2, np.int64)
+    cuts = np.concatenate([[0], np.nonzero(np.diff(path_pen))[0] + 1, [len(path_pen)]]) if len(path_pen) else np.zeros(1, np.int64)
+    for a, b in zip(cuts[:-1].tolist(), cuts[1:].tolist()):
+        pen = int(path_pen[a])
+        if not (0 <= pen < MAX_PENS):
+            raise ValueError("color index 0..7")
+        goff, gpts = off[a:b + 1] - off[a], pts[off[a]:off[b]]
+        if (cur != gpts[0]).any():
+            plans.append(ST.fixed_plan([-1], [[*cur, *gpts[0]]])); cur = gpts[0]
+        plans.append(ST.plan_ops(goff, gpts, np.zeros(b - a, bool), cur, [0x08 | pen], False, sc))
+        cur = gpts[-1]
+    return ST.concat_plans(plans)
+
+
 def build_stream_from_gcode(text_or_paths, opts: Optional[GcodeOptions] = None, device=None, *, steps_fn: Optional[Callable] = None,
                             order_fn: Optional[Callable] = None, codes_fn: Optional[Callable] = None, pack_fn: Optional[Callable] = None,
-                            timings: Optional[dict] = None) -> Tuple[bytes, dict]:
+                            timings: Optional[dict] = None, pens: Optional[np.ndarray] = None, order_pens_fn: Optional[Callable] = None,
+                            source_fn: Optional[Callable] = None) -> Tuple[bytes, dict]:
     """The stream of a G-code text (str / bytes) or of paths in mm given as (off, pts_mm); opts as parsed, --speed-scale not yet applied.
     Device steps, each None = the GPU (orip.device.Device; there is no CPU path in the product):
       steps_fn(off, pts_mm, map: dict) -> (off int64, pts int32 [total, 2])      orip_gcode_to_steps
       order_fn(ends int32 [n, 4]) -> order int32 [n]                             orip_gcode_order
       codes_fn, pack_fn                                                          orip.stream.compile_plan
+    and, only with pens or --allow-reverse:
+      source_fn(n) -> src int32 [n]: the input path of every step polyline       orip_gcode_steps_source_fetch
+      order_pens_fn(ends, group int32 [n], n_groups, reverse) -> (order, rev)    orip_gcode_order_pens
+    pens: one pen per input path, 0..7, or -1 for --color-index (a text's T words under --tool-pens when None).  info["pens"] then counts the paths per
+    pen, those that took --color-index ("unmatched") and the strokes drawn backwards ("reversed").
     Returns (bytes, counts)."""
     import time
     o = apply_speed_scale(GcodeOptions(**{f.name: getattr(opts, f.name) for f in fields(GcodeOptions)}) if opts is not None else GcodeOptions())
@@ -200,23 +276,34 @@ def build_stream_from_gcode(text_or_paths, opts: Optional[GcodeOptions] = None, 
         t1 = time.perf_counter(); tm[name] = tm.get(name, 0.0) + (t1 - t0); t0 = t1
 
     if isinstance(text_or_paths, (str, bytes, bytearray)):
-        off_mm, pts_mm, pen_moves = parse_gcode(text_or_paths)
+        tools: Optional[List[int]] = [] if o.tool_pens and pens is None else None
+        off_mm, pts_mm, pen_moves = parse_gcode(text_or_paths, tools)
+        if tools is not None:
+            pens = np.asarray(tools, np.int64)
     else:
         off_mm, pts_mm = text_or_paths
         off_mm = np.asarray(off_mm, np.int64); pts_mm = np.asarray(pts_mm, np.float64).reshape(-1, 2)
         pen_moves = int((np.diff(off_mm) - 1).clip(0).sum())
     lap("parse")
     info = {"paths_mm": len(off_mm) - 1, "pen_down_moves": pen_moves, "paths": 0, "steps": 0, "target": (W, H)}
+    seq = pen_sequence(o.pen_order)
+    grouped = pens is not None or bool(o.allow_reverse)                   # the new order; without either, everything below is as it was
+    if pens is not None:
+        pens = np.asarray(pens, np.int64).reshape(-1)
+        if len(pens) != len(off_mm) - 1 or (pens < -1).any() or (pens >= MAX_PENS).any():
+            raise ValueError(f"pens: one per path ({len(off_mm) - 1}), each -1 or 0..{MAX_PENS - 1}")
     if len(off_mm) <= 1:
         return EMPTY_STREAM, dict(info, bytes=len(EMPTY_STREAM))
     if not (1 <= W <= MAX_TARGET_STEPS and 1 <= H <= MAX_TARGET_STEPS):
         raise ValueError(f"target size {W} x {H} steps: each side must be in 1..2^30 (step coordinates are int32 on the device)")
-    if steps_fn is None or order_fn is None:
+    if steps_fn is None or order_fn is None or (grouped and (order_pens_fn is None or source_fn is None)):
         if device is None:
             from .stages import device as _default_device
             device = _default_device()
         steps_fn = steps_fn or device.gcode_to_steps
         order_fn = order_fn or device.gcode_order
+        order_pens_fn = order_pens_fn or (lambda ends, group, n_groups, reverse: device.gcode_order_pens(ends, group, n_groups, reverse))
+        source_fn = source_fn or device.gcode_steps_source
     off, pts = steps_fn(off_mm, pts_mm, dict(scale_x=o.scale_x, scale_y=o.scale_y, offset_x_mm=o.offset_x_mm, offset_y_mm=o.offset_y_mm, steps_per_mm=o.steps_per_mm,
                                              W=W, H=H, invert_y=int(bool(o.invert_y))))
     off = np.asarray(off, np.int64); pts = np.asarray(pts, np.int32).reshape(-1, 2)
@@ -225,7 +312,35 @@ def build_stream_from_gcode(text_or_paths, opts: Optional[GcodeOptions] = None, 
     info["paths"] = n
     if n == 0:
         return EMPTY_STREAM, dict(info, bytes=len(EMPTY_STREAM))
-    if not o.no_reorder:
+    path_pen = None
+    if grouped:
+        if not (0 <= int(o.color_index) <= 7):
+            raise ValueError("color index 0..7")
+        # the pen of every step polyline, through the paths the conversion dropped; its group is the pen's place in the drawing sequence
+        if pens is not None:
+            src = np.asarray(source_fn(n), np.int64).reshape(-1)
+            if len(src) != n or (src < 0).any() or (src >= len(pens)).any():
+                raise RuntimeError("the source indices of the step polylines do not name input paths")
+            pen = np.where(pens[src] < 0, int(o.color_index), pens[src])
+            info["pens"] = {"paths": np.bincount(pen, minlength=MAX_PENS).tolist(), "unmatched": int((pens[src] < 0).sum()), "reversed": 0}
+            group = np.argsort(np.asarray(seq))[pen].astype(np.int32)
+        else:
+            pen = np.full(n, int(o.color_index), np.int64); group = np.zeros(n, np.int32)
+        n_groups = MAX_PENS if pens is not None else 1
+        if o.no_reorder:
+            order, rev = np.argsort(group, kind="stable"), np.zeros(n, bool)      # pen after pen all the same, file order inside a pen
+        else:
+            order, rev = order_pens_fn(np.ascontiguousarray(np.concatenate([pts[off[:-1]], pts[off[1:] - 1]], 1), np.int32), group, n_groups, bool(o.allow_reverse))
+            order = np.asarray(order, np.int64); rev = np.asarray(rev, bool)
+            if len(order) != n or len(rev) != n or not np.array_equal(np.sort(order), np.arange(n)) or (np.diff(group[order]) < 0).any():
+                raise RuntimeError("the path order is not a permutation that keeps the pens together")
+        off, pts = gather_paths(off, pts, order, rev)
+        path_pen = pen[order]
+        if pens is not None:
+            info["pens"]["reversed"] = int(rev.sum())
+        else:
+            info["reversed"] = int(rev.sum())
+    elif not o.no_reorder:
         order = np.asarray(order_fn(np.ascontiguousarray(np.concatenate([pts[off[:-1]], pts[off[1:] - 1]], 1), np.int32)), np.int64)
         if len(order) != n or not np.array_equal(np.sort(order), np.arange(n)):
             raise RuntimeError("the path order is not a permutation")
@@ -237,7 +352,10 @@ def build_stream_from_gcode(text_or_paths, opts: Optional[GcodeOptions] = None, 
     if not (0 <= int(o.color_index) <= 7):
         raise ValueError("color index 0..7")
     div0 = min(max(int(sc.div_start), 0), 63)                             # set_speed(div_start): written here, and remembered (layout: initial_div)
-    P = ST.plan_ops(off, pts, np.zeros(n, bool), (0, 0), [ST.PEN_UP, 0x40 | div0, 0x08 | int(o.color_index)], False, sc)
+    if pens is not None:
+        P = plan_pens(off, pts, path_pen, [ST.PEN_UP, 0x40 | div0], sc)
+    else:
+        P = ST.plan_ops(off, pts, np.zeros(n, bool), (0, 0), [ST.PEN_UP, 0x40 | div0, 0x08 | int(o.color_index)], False, sc)
     lap("plan")
     data, table, coff = ST.compile_plan(P, sc, device, codes_fn, pack_fn, initial_div=int(sc.div_start), lap=lap)
     info.update(steps=int(coff[-1]), bytes=len(data), pieces=len(table.pos), moves=len(P.moves))
@@ -273,6 +391,9 @@ def build_argparser() -> argparse.ArgumentParser:
     ap.add_argument("--short-div", type=int, default=d.short_div)
     ap.add_argument("--speed-scale", type=float, default=d.speed_scale, help="> 1 faster (smaller dividers), < 1 slower")
     ap.add_argument("--no-reorder", action="store_true", help="keep the paths in file order")
+    ap.add_argument("--allow-reverse", action="store_true", help="let the order draw a stroke backwards when its far end is nearer")
+    ap.add_argument("--tool-pens", action="store_true", help="a path is drawn with the pen its T word names (T0..T7; before any T: --color-index), pen after pen")
+    ap.add_argument("--pen-order", default=None, help="pens in drawing order, comma-separated (default: ascending); pens without paths are skipped")
     return ap
 
 
@@ -289,6 +410,8 @@ def main(argv: Optional[Sequence[str]] = None, **device_steps) -> None:
     Path(a.output).write_bytes(data)
     print(f"[gcode] {a.input}: {info['paths_mm']} pen-down paths, {info['pen_down_moves']} pen-down moves")
     print(f"[gcode] {info['paths']} paths in step space, {info['steps']} steps, target {info['target'][0]} x {info['target'][1]} steps")
+    if "pens" in info:
+        print("[gcode] pens: " + ", ".join(f"{p}: {k} paths" for p, k in enumerate(info["pens"]["paths"]) if k) + f"; {info['pens']['reversed']} strokes reversed")
     print(f"stream saved: {a.output} ({len(data)} bytes)")
 
 

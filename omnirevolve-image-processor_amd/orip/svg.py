@@ -26,6 +26,14 @@ runs that function's rules on the fitted paths after they are quantised to steps
 G-code text, the order and the stream treat them like any other path.  Every fill is even-odd, whatever fill-rule says, because the reference's pairing is
 (stated deviation), and the SVG default of a black fill is not taken as a request to hatch: only a fill that is written down is.
 
+Pens (off unless --pen-colors is given; ours, the reference's svg2stream.py draws with one pen).  parse_svg records the stroke and the fill of every
+subpath's element as written (style property, presentation attribute, enclosing groups).  --pen-colors names the colour of each pen; a subpath is drawn
+with the pen whose colour is nearest to its stroke -- squared Euclidean distance over the 8-bit sRGB values, in integers, the lowest pen on ties.  That
+metric is this module's choice: the reference defines none, and it is NOT the Lab metric of analyze_colors, which lives on the device.  A subpath
+without a stated stroke takes --color-index; a hatch line takes the pen of its element's fill colour, or of its stroke where the fill is no colour.
+What is drawn does not change (an element with stroke="none" is still drawn, as before: stated deviation).  The pens travel through the hatch
+(orip_svg_hatch_groups_fetch) and the conversion to steps (orip_gcode_steps_source_fetch) into orip/gcode.py, which draws pen after pen.
+
 The device steps are injectable, as in orip/gcode.py, so that this host logic can be tested without a GPU; the product has no CPU path."""
 from __future__ import annotations
 
@@ -55,7 +63,8 @@ class SegmentTable:
     """Flat arrays.  Segment s: kind[s] (LINE / QUAD / CUBIC), ctrl[s] its control points in user units (the unused ones repeat the last), mat[s] the index of
     its matrix in mats (a, b, c, d, e, f: x' = a x + c y + e, y' = b x + d y + f).  Subpath p = segments sub_off[p] .. sub_off[p + 1] - 1, one pen-down path;
     closed[p]: it ended with Z (the closing line is one of its segments).  fill_group[p]: -1, or the ordinal of the element subpath p belongs to when that
-    element is to be hatched (parse_svg; None counts as all -1)."""
+    element is to be hatched (parse_svg; None counts as all -1).  stroke_rgb[p], fill_rgb[p]: the colour of the subpath's element as written, 8-bit sRGB, or
+    (-1, -1, -1) where none is stated or what is stated is no colour (None counts as all -1)."""
     kind: np.ndarray
     ctrl: np.ndarray
     mat: np.ndarray
@@ -64,6 +73,8 @@ class SegmentTable:
     mats: np.ndarray
     canvas_height: float = 100.0
     fill_group: Optional[np.ndarray] = None
+    stroke_rgb: Optional[np.ndarray] = None
+    fill_rgb: Optional[np.ndarray] = None
 
     @property
     def n_seg(self) -> int: return len(self.kind)
@@ -88,6 +99,7 @@ class _Builder:
         self.kind: List[int] = []; self.ctrl: List[Tuple[float, ...]] = []; self.mat: List[int] = []
         self.sub_off = [0]; self.closed: List[int] = []
         self.fill_group: List[int] = []; self.elements = 0
+        self.stroke_rgb: List[Tuple[int, int, int]] = []; self.fill_rgb: List[Tuple[int, int, int]] = []
         self.mats: List[Tuple[float, ...]] = [IDENTITY]
         self.m = 0
         self.cur = self.start = (0.0, 0.0)
@@ -161,7 +173,7 @@ class _Builder:
         self.end()
         return SegmentTable(np.asarray(self.kind, np.int32), np.asarray(self.ctrl, np.float64).reshape(-1, 4, 2), np.asarray(self.mat, np.int32),
                             np.asarray(self.sub_off, np.int64), np.asarray(self.closed, np.uint8), np.asarray(self.mats, np.float64).reshape(-1, 6), float(canvas_height),
-                            np.asarray(self.fill_group, np.int32))
+                            np.asarray(self.fill_group, np.int32), np.asarray(self.stroke_rgb, np.int16).reshape(-1, 3), np.asarray(self.fill_rgb, np.int16).reshape(-1, 3))
 
 
 # ------------------------------------------------------------------ path data
@@ -371,17 +383,105 @@ def _fill_of(el, inherited: Optional[str]) -> Optional[str]:
     return inherited if own is None else own.strip().lower()
 
 
-def _walk(b: _Builder, el, m: int, fill: Optional[str] = None, fill_all: bool = False):
+_STROKE = re.compile(r"(?:^|;)\s*stroke\s*:\s*([^;]+)")
+
+
+def _stroke_of(el, inherited: Optional[str]) -> Optional[str]:
+    """the element's stroke as written, resolved as _fill_of resolves the fill"""
+    m = _STROKE.search(el.get("style") or "")
+    own = m.group(1) if m else el.get("stroke")
+    return inherited if own is None else own.strip().lower()
+
+
+# the 16 basic CSS colour keywords, and orange
+COLOR_KEYWORDS = {"black": (0, 0, 0), "silver": (192, 192, 192), "gray": (128, 128, 128), "white": (255, 255, 255), "maroon": (128, 0, 0), "red": (255, 0, 0),
+                  "purple": (128, 0, 128), "fuchsia": (255, 0, 255), "green": (0, 128, 0), "lime": (0, 255, 0), "olive": (128, 128, 0), "yellow": (255, 255, 0),
+                  "navy": (0, 0, 128), "blue": (0, 0, 255), "teal": (0, 128, 128), "aqua": (0, 255, 255), "orange": (255, 165, 0)}
+NO_COLOR = (-1, -1, -1)
+_HEX = re.compile(r"^#([0-9a-f]{3}|[0-9a-f]{6})$")
+_RGB = re.compile(r"^rgb\(\s*([+-]?\d*\.?\d+)(%?)\s*,\s*([+-]?\d*\.?\d+)(%?)\s*,\s*([+-]?\d*\.?\d+)(%?)\s*\)$")
+
+
+def parse_color(s: Optional[str]) -> Tuple[int, int, int]:
+    """#rgb, #rrggbb, rgb(r, g, b) with integers or percentages (clamped to 0..255), a keyword of COLOR_KEYWORDS, in any letter case -> 8-bit sRGB;
+    none, transparent, currentColor, url(...), unknown words and None -> NO_COLOR"""
+    if s is None:
+        return NO_COLOR
+    t = s.strip().lower()
+    m = _HEX.match(t)
+    if m:
+        h = m.group(1)
+        if len(h) == 3:
+            h = "".join(ch * 2 for ch in h)
+        return int(h[0:2], 16), int(h[2:4], 16), int(h[4:6], 16)
+    m = _RGB.match(t)
+    if m:
+        v = [(m.group(i), m.group(i + 1)) for i in (1, 3, 5)]
+        if len({pc for _, pc in v}) != 1 or (v[0][1] == "" and any("." in num for num, _ in v)):
+            return NO_COLOR                                  # integers and percentages do not mix, and a plain value is an integer
+        return tuple(min(255, max(0, int(round(float(num) * 255.0 / 100.0)) if pc else int(num))) for num, pc in v)
+    return COLOR_KEYWORDS.get(t, NO_COLOR)
+
+
+def parse_pen_colors(spec: str) -> List[Tuple[int, int, int]]:
+    """--pen-colors: 1..8 comma-separated colours (#rgb, #rrggbb or a keyword), position = pen; the word rgbk: the previewer's default palette"""
+    from .stream_preview import DEFAULT_PALETTE
+    if spec.strip().lower() == "rgbk":
+        return [tuple(int(v) for v in c) for c in DEFAULT_PALETTE]
+    out = [parse_color(tok) for tok in spec.split(",")]
+    if not (1 <= len(out) <= GC.MAX_PENS) or any(c == NO_COLOR or "(" in tok for c, tok in zip(out, spec.split(","))):
+        raise ValueError(f"--pen-colors: 1..{GC.MAX_PENS} comma-separated colours (#rgb, #rrggbb or a keyword), or rgbk")
+    return out
+
+
+def nearest_pen(rgb, palette) -> np.ndarray:
+    """per row of rgb int [n, 3] the palette entry at the smallest squared Euclidean distance over 8-bit sRGB, integers, the lowest index on ties; -1 for
+    a row that is NO_COLOR.  Ours: the reference defines no such mapping, and this is not the Lab metric of analyze_colors."""
+    c = np.asarray(rgb, np.int64).reshape(-1, 3)
+    pal = np.asarray(palette, np.int64).reshape(-1, 3)
+    d = ((c[:, None, :] - pal[None, :, :]) ** 2).sum(2)
+    return np.where((c < 0).any(1), -1, np.argmin(d, 1)).astype(np.int64)      # argmin: the first minimum
+
+
+def subpath_pens(table: SegmentTable, palette) -> np.ndarray:
+    """the pen of every subpath by its stroke; -1: no stroke stated (the caller's --color-index)"""
+    if table.stroke_rgb is None:
+        return np.full(table.n_sub, -1, np.int64)
+    return nearest_pen(table.stroke_rgb, palette)
+
+
+def hatch_pens(table: SegmentTable, groups, palette) -> np.ndarray:
+    """the pen of every hatch line from its fill group (an element's ordinal): the pen of the element's fill colour, or of its stroke where the fill is
+    not a colour (--hatch-fill all); -1 where neither is"""
+    groups = np.asarray(groups, np.int64).reshape(-1)
+    fg = np.asarray(table.fill_group, np.int64).reshape(-1) if table.fill_group is not None else np.zeros(0, np.int64)
+    if len(groups) == 0:
+        return np.zeros(0, np.int64)
+    if len(fg) == 0 or groups.min() < 0 or groups.max() > fg.max():
+        raise RuntimeError("the hatch lines name fill groups the table does not have")
+    first = np.full(int(fg.max()) + 1, -1, np.int64)                       # a subpath of every group: all of an element's subpaths share its colours
+    sub = np.nonzero(fg >= 0)[0][::-1]
+    first[fg[sub]] = sub
+    if (first[groups] < 0).any():
+        raise RuntimeError("the hatch lines name fill groups the table does not have")
+    none = np.full((table.n_sub, 3), -1, np.int64)
+    fill = nearest_pen(none if table.fill_rgb is None else table.fill_rgb, palette)
+    pen = np.where(fill >= 0, fill, subpath_pens(table, palette))
+    return pen[first[groups]]
+
+
+def _walk(b: _Builder, el, m: int, fill: Optional[str] = None, fill_all: bool = False, stroke: Optional[str] = None):
     tag = el.tag.rsplit("}", 1)[-1] if isinstance(el.tag, str) else ""
     if not tag or tag in SKIPPED or (el.get("display") or "").strip() == "none":
         return
     fill = _fill_of(el, fill)
+    stroke = _stroke_of(el, stroke)
     if el.get("transform"):
         b.mats.append(_mul(b.mats[m], parse_transform(el.get("transform"))))
         m = len(b.mats) - 1
     if tag in GROUPS:
         for ch in el:
-            _walk(b, ch, m, fill, fill_all)
+            _walk(b, ch, m, fill, fill_all, stroke)
     else:
         b.m = m
         _draw_element(b, el, tag)
@@ -390,6 +490,7 @@ def _walk(b: _Builder, el, m: int, fill: Optional[str] = None, fill_all: bool = 
         if new:                                             # an element that drew something: the next ordinal, whether it is filled or not
             wanted = tag != "line" and (fill_all or (fill is not None and fill not in ("none", "transparent")))
             b.fill_group.extend([b.elements if wanted else -1] * new)
+            b.stroke_rgb.extend([parse_color(stroke)] * new); b.fill_rgb.extend([parse_color(fill)] * new)
             b.elements += 1
 
 
@@ -437,6 +538,9 @@ class SvgOptions:
     hatch_direction: str = "horizontal"
     no_serpentine: bool = False
     hatch_fill: str = "stated"
+    pen_colors: Optional[str] = None                    # None: one pen, --color-index
+    pen_order: Optional[str] = None
+    allow_reverse: bool = False
 
 
 HATCH_DIRECTIONS = {"horizontal": HATCH_HORIZONTAL, "vertical": HATCH_VERTICAL, "cross": HATCH_HORIZONTAL | HATCH_VERTICAL}
@@ -533,18 +637,27 @@ def gcode_options(o: SvgOptions) -> GC.GcodeOptions:
     else:
         W, H = int(round(o.page_width_mm * o.steps_per_mm)), int(round(o.page_height_mm * o.steps_per_mm))
     return GC.GcodeOptions(steps_per_mm=o.steps_per_mm, invert_y=o.invert_y, color_index=o.color_index, speed_scale=o.speed_scale, scale_x=1.0, scale_y=1.0,
-                           offset_x_mm=0.0, offset_y_mm=0.0, target_width_steps=W, target_height_steps=H, no_reorder=bool(o.no_reorder))
+                           offset_x_mm=0.0, offset_y_mm=0.0, target_width_steps=W, target_height_steps=H, no_reorder=bool(o.no_reorder),
+                           allow_reverse=bool(o.allow_reverse), pen_order=o.pen_order)
 
 
-def gcode_text(off, pts, passes: int = 1) -> str:
-    """the fitted paths in a dialect the reference's parser reads: G21, G90, M5; per path G0 to its first point, M3, one G1 per further point, M5"""
+def gcode_text(off, pts, passes: int = 1, pens=None) -> str:
+    """the fitted paths in a dialect the reference's parser reads: G21, G90, M5; per path G0 to its first point, M3, one G1 per further point, M5.  With
+    pens (one per path, 0..7) a line T<pen> stands in front of every path whose pen differs from the one before it; both parsers skip T words, and
+    gcode2stream.py --tool-pens honours them."""
     off = np.asarray(off, np.int64); pts = np.asarray(pts, np.float64).reshape(-1, 2)
     xy = ["X%.4f Y%.4f" % (x, y) for x, y in pts.tolist()]
     out = ["G21", "G90", "M5"]
+    tools = None if pens is None else np.asarray(pens, np.int64).reshape(-1).tolist()
+    if tools is not None and len(tools) != len(off) - 1:
+        raise ValueError(f"{len(tools)} pens for {len(off) - 1} paths")
+    tool = None
     for _ in range(max(1, int(passes))):
-        for a, b in zip(off[:-1].tolist(), off[1:].tolist()):
+        for p, (a, b) in enumerate(zip(off[:-1].tolist(), off[1:].tolist())):
             if b - a < 1:
                 continue
+            if tools is not None and tools[p] != tool:
+                tool = tools[p]; out.append("T%d" % tool)
             out.append("G0 " + xy[a]); out.append("M3")
             out.extend("G1 " + s for s in xy[a + 1:b])
             out.append("M5")
@@ -563,6 +676,10 @@ class _Resident:
     def hatch(self, paths, fill_group, prm):
         st = self.dev.svg_hatch(fill_group, prm["steps_per_mm"], prm["spacing"], prm["inset"], prm["flags"])
         return {"n": paths["n"] + st["segments"], "total": paths["total"] + 2 * st["segments"]}, st
+
+    def hatch_groups(self, paths, segments): return self.dev.svg_hatch_groups(segments)
+    def source(self, n): return self.dev.gcode_steps_source(n)
+    def order_pens(self, ends, group, n_groups, reverse): return self.dev.gcode_order_pens(ends, group, n_groups, reverse)
 
 
 MAX_REFLATTEN = 8
@@ -590,6 +707,29 @@ def fit_paths(table: SegmentTable, o: SvgOptions, flatten_fn, bbox_fn, fit_fn, t
     return paths, {"tol_raw": tol_raw, "scale": (sx, sy, ox, oy), "bbox": box, "flattens": k + 1}
 
 
+def path_pens(table: SegmentTable, o: SvgOptions, paths, info: dict, hatch_groups_fn: Optional[Callable]) -> Optional[np.ndarray]:
+    """None without --pen-colors, else the pen of every fitted path, hatch lines included (-1: --color-index); info["pen_colors"] = the palette"""
+    if o.pen_colors is None:
+        return None
+    palette = parse_pen_colors(o.pen_colors)
+    info["pen_colors"] = palette
+    pens = subpath_pens(table, palette)
+    seg = int(info["hatch"]["segments"]) if "hatch" in info else 0
+    if seg:
+        groups = np.asarray(hatch_groups_fn(paths, seg), np.int64).reshape(-1)
+        if len(groups) != seg:
+            raise RuntimeError(f"{len(groups)} fill groups for {seg} hatch lines")
+        pens = np.concatenate([pens, hatch_pens(table, groups, palette)])
+    return pens
+
+
+def resolved_pens(pens: np.ndarray, o: SvgOptions) -> np.ndarray:
+    """the pens as the G-code names them: --color-index where none was matched"""
+    if not (0 <= int(o.color_index) < GC.MAX_PENS):
+        raise ValueError("color index 0..7")
+    return np.where(pens < 0, int(o.color_index), pens)
+
+
 def hatch_paths(table: SegmentTable, prm: dict, paths, hatch_fn, info: dict, tm: Optional[dict] = None):
     """the fitted paths with the hatch lines of the table's fill groups behind them; info["hatch"] = the counts"""
     import time
@@ -607,7 +747,8 @@ def hatch_paths(table: SegmentTable, prm: dict, paths, hatch_fn, info: dict, tm:
 def build_stream_from_svg(text: Union[str, bytes, SegmentTable], opts: Optional[SvgOptions] = None, device=None, *, flatten_fn: Optional[Callable] = None,
                           bbox_fn: Optional[Callable] = None, fit_fn: Optional[Callable] = None, hatch_fn: Optional[Callable] = None, fetch_fn: Optional[Callable] = None,
                           steps_fn: Optional[Callable] = None, order_fn: Optional[Callable] = None, codes_fn: Optional[Callable] = None, pack_fn: Optional[Callable] = None, timings: Optional[dict] = None,
-                          want_paths: bool = False) -> Tuple[bytes, dict]:
+                          want_paths: bool = False, hatch_groups_fn: Optional[Callable] = None, source_fn: Optional[Callable] = None,
+                          order_pens_fn: Optional[Callable] = None) -> Tuple[bytes, dict]:
     """The stream of an SVG text (or of a parsed SegmentTable).  Device steps, each None = the GPU (there is no CPU path in the product):
       flatten_fn(table, tol_raw) -> paths          orip_svg_flatten      (`paths` is whatever the other steps take: on the GPU a count, the points stay there)
       bbox_fn(paths) -> (min x, min y, max x, max y)   orip_svg_bbox
@@ -616,12 +757,18 @@ def build_stream_from_svg(text: Union[str, bytes, SegmentTable], opts: Optional[
       fetch_fn(paths, with_points) -> (off int64, pts float64 or None)   orip_svg_paths_fetch  (the points only with want_paths: info["fitted_paths"])
       steps_fn(paths, map) -> (off, pts int32)     orip_gcode_to_steps without pointers
       order_fn, codes_fn, pack_fn                  as in orip.gcode.build_stream_from_gcode
+    and, only with --pen-colors or --allow-reverse:
+      hatch_groups_fn(paths, segments) -> int32 [segments]   orip_svg_hatch_groups_fetch  (the fill group of every hatch line)
+      source_fn, order_pens_fn                     as in orip.gcode.build_stream_from_gcode
+    With --pen-colors, info["path_pens"] is the pen of every fitted path (hatch lines included, --color-index where no stroke is stated).
     Returns (bytes, info)."""
     import time
     o = opts if opts is not None else SvgOptions()
     tm = timings if timings is not None else {}
     t0 = time.perf_counter()
     hp = hatch_params(o)
+    if o.pen_colors is not None:
+        parse_pen_colors(o.pen_colors)                      # a bad list ends the run before anything is parsed
     table = text if isinstance(text, SegmentTable) else parse_svg(text, o.hatch_fill)
     tm["parse_svg"] = tm.get("parse_svg", 0.0) + (time.perf_counter() - t0)
     go = gcode_options(o)
@@ -633,7 +780,9 @@ def build_stream_from_svg(text: Union[str, bytes, SegmentTable], opts: Optional[
         if want_paths:
             info["fitted_paths"] = (np.zeros(1, np.int64), np.zeros((0, 2)))
         return data, dict(ginfo, **info)
-    if any(f is None for f in (flatten_fn, bbox_fn, fit_fn, fetch_fn, steps_fn, order_fn, codes_fn, pack_fn)) or (hp and hatch_fn is None):
+    pens_on = o.pen_colors is not None
+    if any(f is None for f in (flatten_fn, bbox_fn, fit_fn, fetch_fn, steps_fn, order_fn, codes_fn, pack_fn)) or (hp and hatch_fn is None) or \
+            ((pens_on or o.allow_reverse) and (source_fn is None or order_pens_fn is None)) or (pens_on and hp and hatch_groups_fn is None):
         if device is None:
             from .stages import device as _default_device
             device = _default_device()
@@ -641,10 +790,14 @@ def build_stream_from_svg(text: Union[str, bytes, SegmentTable], opts: Optional[
         flatten_fn = flatten_fn or R.flatten; bbox_fn = bbox_fn or R.bbox; fit_fn = fit_fn or R.fit; fetch_fn = fetch_fn or R.fetch; steps_fn = steps_fn or R.steps
         hatch_fn = hatch_fn or R.hatch
         order_fn = order_fn or device.gcode_order
+        hatch_groups_fn = hatch_groups_fn or R.hatch_groups; source_fn = source_fn or R.source; order_pens_fn = order_pens_fn or R.order_pens
     paths, fi = fit_paths(table, o, flatten_fn, bbox_fn, fit_fn, tm)
     info.update(fi)
     if hp:
         paths = hatch_paths(table, hp, paths, hatch_fn, info, tm)
+    pens = path_pens(table, o, paths, info, hatch_groups_fn)
+    if pens is not None:
+        info["path_pens"] = resolved_pens(pens, o)
     t0 = time.perf_counter()
     off_mm, pts_mm = fetch_fn(paths, want_paths)
     off_mm = np.asarray(off_mm, np.int64)
@@ -652,7 +805,7 @@ def build_stream_from_svg(text: Union[str, bytes, SegmentTable], opts: Optional[
         info["fitted_paths"] = (off_mm, np.asarray(pts_mm, np.float64).reshape(-1, 2))
     tm["fetch_paths"] = tm.get("fetch_paths", 0.0) + (time.perf_counter() - t0)
     data, ginfo = GC.build_stream_from_gcode((off_mm, np.zeros((int(off_mm[-1]), 2))), go, device, steps_fn=lambda _off, _pts, m: steps_fn(paths, m), order_fn=order_fn,
-                                             codes_fn=codes_fn, pack_fn=pack_fn, timings=tm)
+                                             codes_fn=codes_fn, pack_fn=pack_fn, timings=tm, pens=pens, order_pens_fn=order_pens_fn, source_fn=source_fn)
     return data, dict(ginfo, **info)
 
 
@@ -670,6 +823,8 @@ def _add_fit_args(ap: argparse.ArgumentParser, d: SvgOptions):
     ap.add_argument("--hatch-direction", choices=sorted(HATCH_DIRECTIONS), default=d.hatch_direction, help="hatch lines along X, along Y, or both (default: horizontal)")
     ap.add_argument("--no-serpentine", action="store_true", help="draw every hatch line in the same direction; by default every other line is reversed")
     ap.add_argument("--hatch-fill", choices=HATCH_FILLS, default=d.hatch_fill, help="stated: elements whose fill is written down and is not none (default); all: every element that draws")
+    ap.add_argument("--pen-colors", default=None, help="the colour of each pen, comma-separated (#rgb, #rrggbb or a keyword; position = pen), or rgbk; a path is drawn with the pen "
+                                                        "nearest to its stroke colour (default: one pen, --color-index)")
 
 
 def build_gcode_argparser() -> argparse.ArgumentParser:
@@ -700,6 +855,8 @@ def build_stream_argparser() -> argparse.ArgumentParser:
     ap.add_argument("--color-index", type=int, default=d.color_index, help="pen 0..7")
     ap.add_argument("--speed-scale", type=float, default=d.speed_scale, help="> 1 faster (smaller dividers), < 1 slower")
     ap.add_argument("--no-reorder", action="store_true", help="keep the paths in file order")
+    ap.add_argument("--pen-order", default=None, help="pens in drawing order, comma-separated (default: ascending); pens without paths are skipped")
+    ap.add_argument("--allow-reverse", action="store_true", help="let the order draw a stroke backwards when its far end is nearer")
     ap.add_argument("--no-preview", action="store_true", help="do not render <svg stem>_stream_preview.png")
     ap.add_argument("--preview-render-width", type=int, default=d.preview_render_width)
     ap.add_argument("--preview-render-height", type=int, default=d.preview_render_height)
@@ -722,20 +879,23 @@ def main_gcode(argv: Optional[Sequence[str]] = None, **device_steps) -> None:
     a = build_gcode_argparser().parse_args(argv)
     o = options_from_args(a)
     hp = hatch_params(o)
+    if o.pen_colors is not None:
+        parse_pen_colors(o.pen_colors)
     table = parse_svg(_read(a.input), o.hatch_fill)
     info = {}
-    off, pts = np.zeros(1, np.int64), np.zeros((0, 2))
+    off, pts, pens = np.zeros(1, np.int64), np.zeros((0, 2)), None
     if table.n_seg:
         R = device_steps
         if not R:
             from .stages import device as _default_device
             r = _Resident(_default_device())
-            R = dict(flatten_fn=r.flatten, bbox_fn=r.bbox, fit_fn=r.fit, fetch_fn=r.fetch, hatch_fn=r.hatch)
+            R = dict(flatten_fn=r.flatten, bbox_fn=r.bbox, fit_fn=r.fit, fetch_fn=r.fetch, hatch_fn=r.hatch, hatch_groups_fn=r.hatch_groups)
         paths, info = fit_paths(table, o, R["flatten_fn"], R["bbox_fn"], R["fit_fn"])
         if hp:
             paths = hatch_paths(table, hp, paths, R["hatch_fn"], info)
+        pens = path_pens(table, o, paths, info, R.get("hatch_groups_fn"))
         off, pts = R["fetch_fn"](paths, True)
-    Path(a.output).write_text(gcode_text(off, pts, o.passes), encoding="utf-8")
+    Path(a.output).write_text(gcode_text(off, pts, o.passes, None if pens is None else resolved_pens(pens, o)), encoding="utf-8")
     print(f"G-code saved to {a.output}: {len(off) - 1} paths, {len(pts)} points")
     if "scale" in info:
         sx, sy, ox, oy = info["scale"]
@@ -759,11 +919,14 @@ def main_stream(argv: Optional[Sequence[str]] = None, **device_steps) -> None:
         device = _default_device()
     data, info = build_stream_from_svg(text, o, device, want_paths=True, **device_steps)
     off, pts = info["fitted_paths"]
-    gcode_path.write_text(gcode_text(off, pts), encoding="utf-8")
+    gcode_path.write_text(gcode_text(off, pts, pens=info.get("path_pens")), encoding="utf-8")
     stream_path.write_bytes(data)
     print(f"[svg] {a.input}: {info['segments']} segments in {info['subpaths']} subpaths -> {len(pts)} points")
     if "hatch" in info:
         print("[svg] hatch: {groups} fill groups, {lines} lines, {crossings} crossings -> {segments} segments".format(**info["hatch"]))
+    if "pens" in info:
+        print("[svg] pens: " + ", ".join(f"{p}: {k} paths" for p, k in enumerate(info["pens"]["paths"]) if k) +
+              f"; {info['pens']['unmatched']} without a stroke colour, {info['pens']['reversed']} strokes reversed")
     print(f"[svg] G-code saved: {gcode_path}")
     print(f"stream saved: {stream_path} ({len(data)} bytes)")
     if o.no_preview:
@@ -771,7 +934,10 @@ def main_stream(argv: Optional[Sequence[str]] = None, **device_steps) -> None:
         return
     from . import stream_preview as SP
     W, H = info["target"]
-    rgb, _ = SP.preview(device, data, W, H, o.preview_render_width, o.preview_render_height, invert_y=True)
+    palette = {}
+    if "pen_colors" in info:                              # the pens' own colours; the previewer has four (pens 4..7 render as pen 3, as they always did)
+        palette = {"palette": tuple((list(info["pen_colors"]) + list(SP.DEFAULT_PALETTE[len(info["pen_colors"]):]))[:4])}
+    rgb, _ = SP.preview(device, data, W, H, o.preview_render_width, o.preview_render_height, invert_y=True, **palette)
     png = src.with_name(src.stem + "_stream_preview.png")
     SP.save_png(rgb, str(png))
     print(f"Image saved: {png}")

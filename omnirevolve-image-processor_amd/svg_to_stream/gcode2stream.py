@@ -3,6 +3,7 @@
 The conversion to steps, the nearest-neighbour order of the paths and the packing of the stream run on the GPU (orip.gcode, liborip.so); there is no CPU path.
 
     python gcode2stream.py drawing.gcode -o stream.bin [--steps-per-mm 40] [--invert-y 1] [--speed-scale 1.5] [--no-reorder] ...
+                           [--tool-pens [--pen-order 3,0,...]] [--allow-reverse]      (ours: pens from the T words, strokes drawn backwards where that is nearer)
 """
 import os
 import sys

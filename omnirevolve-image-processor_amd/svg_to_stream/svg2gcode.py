@@ -5,6 +5,7 @@ CPU path.  The points chosen for a curve are this project's, held to the curve w
 
     python svg2gcode.py drawing.svg -o drawing.gcode [--page-width-mm 210 --page-height-mm 297 --margin-mm 10] [--scale S | --scale-x SX --scale-y SY] [--tolerance-mm T]
                          [--hatch-spacing-mm S [--hatch-inset-mm I] [--hatch-direction horizontal|vertical|cross] [--no-serpentine] [--hatch-fill stated|all]]
+                         [--pen-colors rgbk|LIST]      (ours: a T<pen> line wherever the pen changes)
 """
 import os
 import sys

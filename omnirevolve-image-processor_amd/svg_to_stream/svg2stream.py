@@ -5,6 +5,7 @@ stream bytes (orip.svg, orip.gcode, liborip.so); the G-code file is written from
 decoded and drawn on the GPU into <stem>_stream_preview.png (orip.stream_preview: what the reference shows in a window).  There is no CPU path.
 
     python svg2stream.py drawing.svg [-o stream.bin] [--gcode-output drawing.gcode] [--steps-per-mm 40] [--scale S] [--no-reorder] [--no-preview] [--hatch-spacing-mm S ...] ...
+                          [--pen-colors rgbk|LIST [--pen-order 3,0,...]] [--allow-reverse]      (ours: a pen per stroke colour, drawn pen after pen)
 """
 import os
 import sys

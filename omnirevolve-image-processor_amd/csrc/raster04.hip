@@ -640,8 +640,8 @@ static int trace_finish(orip_ctx* c, Prep04& R, int layer) {
         for (size_t i = 0; i < h.size(); i++) tot[i % 32] += h[i];
         for (size_t i = 0; i < NCl; i++) if (h[i * 32 + 7] > h[big * 32 + 7]) big = i;
         const unsigned long long* d = &h[big * 32];
-        fprintf(stderr, "[walk dbg] layer %d NC=%u M=%u F=%u: w1=%llu s1=%llu w2=%llu s2=%llu hit=%llu det=%llu tiles=%llu | largest fg=%llu: w1=%llu s1=%llu w2=%llu s2=%llu hit=%llu det=%llu tiles=%llu jumped=%llu\n",
-                layer, NCl, Ml, R.F[layer], tot[0], tot[1], tot[2], tot[3], tot[4], tot[5], tot[6], d[7], d[0], d[1], d[2], d[3], d[4], d[5], d[6], d[15]);
+        fprintf(stderr, "[walk dbg] layer %d NC=%u M=%u F=%u: w1=%llu s1=%llu w2=%llu s2=%llu hit=%llu det=%llu tiles=%llu | largest fg=%llu: w1=%llu s1=%llu w2=%llu s2=%llu hit=%llu det=%llu tiles=%llu jumped=%llu calls=%llu rounds=%llu\n",
+                layer, NCl, Ml, R.F[layer], tot[0], tot[1], tot[2], tot[3], tot[4], tot[5], tot[6], d[7], d[0], d[1], d[2], d[3], d[4], d[5], d[6], d[15], d[22], d[23]);
         if (d[8]) fprintf(stderr, "[walk prof] layer %d largest component: cycles total=%llu window loads=%llu scans=%llu look-ups=%llu | look-ups=%llu loop exits=%llu\n",
                           layer, d[8], d[9], d[10], d[11], d[12], d[13]);
         if (d[8]) fprintf(stderr, "[walk prof]   inside the look-ups: duplicate check %llu cycles (exact check in %llu look-ups); forced stretches %llu cycles in %llu calls, %llu rounds; stepping loop %llu cycles; walk start + end %llu cycles\n", d[14], d[20], d[16], d[17], d[18], d[19], d[21]);

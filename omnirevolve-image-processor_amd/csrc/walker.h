@@ -798,7 +798,10 @@ ORIP_HD inline void trace_component(const WalkArgs& A, unsigned c) {
                 if (r < (moved ? 1 : 8)) break;                                   // not worth leaving the stepping loop for
                 // direction code of step j: from the pixel before (lane j - 1's, or the cursor) to q
                 unsigned qp = (unsigned)__shfl_up((int)q, 1, 64); if (lane == 0) qp = wv.pl;
-                const int dd = (int)q - (int)qp; const int dy = dd > 1 ? 1 : (dd < -1 ? -1 : 0); const int dx = dd - dy * W;
+                // (a difference of linear indices names the row step only while W - 1 > 1: in two columns +1 is a step right or one down-left, in
+                // one column it is a step down -- there the rows themselves are compared, y = index >> (W - 1).  Two-column skeletons do get here:
+                // a zigzag between two junction clusters is a listed chain that only leftover walks visit, tests/contour_cases.py narrow())
+                const int dd = (int)q - (int)qp; const int dy = W > 2 ? (dd > 1 ? 1 : (dd < -1 ? -1 : 0)) : (int)(q >> (W - 1)) - (int)(qp >> (W - 1)); const int dx = dd - dy * W;
                 const int kk = (dy + 1) * 3 + (dx + 1); const int k = kk > 4 ? kk - 1 : kk;
                 const unsigned myst = (q << 3) | (unsigned)k;
                 const unsigned nbp = h.nb;
@@ -894,6 +897,7 @@ ORIP_HD inline void trace_component(const WalkArgs& A, unsigned c) {
     if (A.dbg && wv.leader()) {
         unsigned long long* d = A.dbg + 32ull * c; d[0] = d_w1; d[1] = d_s1; d[2] = d_w2; d[3] = d_s2; d[4] = d_hit; d[5] = d_det; d[6] = wv.nload; d[7] = (unsigned long long)fg;
         d[8] = WPROF_NOW() - t_begin; d[9] = wv.t_tile; d[10] = t_scan; d[11] = t_flush; d[12] = n_flush; d[13] = n_ev; d[14] = t_f3; d[15] = d_jump; d[16] = t_chain; d[17] = n_chain; d[18] = n_round; d[19] = t_run; d[20] = wv.n_exact; d[21] = t_walk;     // cycle counts: ORIP_WALK_PROF builds only
+        d[22] = n_chain; d[23] = n_round;                                  // chain_jump calls and the rounds that moved the cursor: counted in every build (the [walk dbg] line)
     }
 }
 

@@ -255,6 +255,32 @@ int orip_gcode_order(orip_ctx* ctx, const int32_t* ends /* [n,4] or NULL */, int
 #define ORIP_ORDER_MAX_GROUPS 64
 int orip_gcode_order_pens(orip_ctx* ctx, const int32_t* ends /* [n,4] or NULL = resident step polylines */, const int32_t* group /* [n], 0..n_groups-1 */, int64_t n,
                           int32_t n_groups /* 1..64 */, int32_t flags, const int32_t* start_xy /* [2], NULL = (0,0) */, int32_t* order_out /* [n] */, uint8_t* rev_out /* [n] */);
+/* --merge-paths (csrc/gcode_merge.hip; ours, the reference's generators draw paths that are already whole): step polylines that meet end to end become
+ * one stroke.  Input: n step polylines of two points or more (coordinates 0 .. 2^30), one group per polyline (the pen's place in the drawing sequence;
+ * NULL = all 0), and ORIP_MERGE_REVERSE, set exactly when strokes may be drawn backwards.
+ *   Every path has two ENDS, head (first point) and tail (last point); the NODE of an end is the triple (group, x, y), compared in full.  The DEGREE of a
+ *   node is the number of ends on it; a closed path puts two ends on one node.  Two ends are JOINED iff they are on the same node, its degree is exactly 2,
+ *   they belong to different paths, and one is a tail and the other a head or ORIP_MERGE_REVERSE is set.  A node of degree 3 or more joins nothing: the
+ *   rule then depends on no processing order, and which two of three strokes belong together is not ours to guess.  A path has at most one join per end,
+ *   so the joined paths form CHAINS, open ones or cycles.
+ *   Each chain becomes one output path.  An open chain is traversed from one free end to the other, in the direction in which its lowest-index member
+ *   runs head -> tail.  A cycle starts at the head of its lowest-index member, runs through that member forwards and goes once round; the result is closed
+ *   (first point == last point).  Members traversed tail -> head are reversed (never without ORIP_MERGE_REVERSE).  The first point of every member but
+ *   the first is dropped: it equals the point before it.  Output paths are listed by ascending lowest member index, so a drawing in which nothing joins
+ *   comes back unchanged.  Coincidence is on the step grid; there is no tolerance.
+ * member_off[paths_out + 1], member[n] (the input indices in traversal order, chain after chain) and rev[n] (one per entry of member: 1 = traversed
+ * tail -> head) say what went where.  stats: paths_out, points_out, joins = n - paths_out (the pen lifts that are gone: the join that closes a cycle
+ * saves none and is not counted), cycles.
+ * off == NULL and pts == NULL: the resident step polylines, n must be their count (as for orip_gcode_order).  In both forms the merged polylines BECOME
+ * the resident step polylines: orip_gcode_steps_fetch copies them out, orip_gcode_order(ctx, NULL, paths_out, ...) and orip_gcode_order_pens(ctx, NULL,
+ * ...) order them.  orip_gcode_steps_source_fetch is an error after a merge until the next orip_gcode_to_steps: ask for the sources first.
+ * Errors before any launch, without a fault and with the resident paths left as they were: n < 0 or n > 2^26, 2^30 points or more, off not starting at 0
+ * or decreasing, a path under two points, a coordinate outside 0 .. 2^30, a group outside 0 .. n_groups - 1, n_groups outside 1 .. 64, unknown flags,
+ * exactly one of off / pts NULL, n that is not the resident count, NULL stats.  n == 0 returns zeros before any launch. */
+#define ORIP_MERGE_REVERSE 1
+int orip_gcode_merge(orip_ctx* ctx, const int64_t* off /* [n+1] or NULL */, const int32_t* pts /* [off[n],2] or NULL */, const int32_t* group /* [n] or NULL = all 0 */,
+                     int64_t n, int32_t n_groups /* 1..64 */, int32_t flags, int64_t* stats /* [4]: paths_out, points_out, joins, cycles */);
+int orip_gcode_merge_fetch(orip_ctx* ctx, int64_t* member_off /* [paths_out+1] */, int32_t* member /* [n] */, uint8_t* rev /* [n] */);
 /* StreamWriter.add_steps / finalize (helper :55-68, :166-175) for a whole plot: the bytes of the stream from the direction codes orip_stream_codes left
  * resident.  Piece i reads cnt[i] codes from code0[i] on and owns the bytes from pos[i]: its speed byte when speed[i] >= 0, then (cnt[i] + 1) / 2 step bytes
  * (two codes per byte, paired inside the piece, the last byte of an odd piece holds one).  Pieces are listed in byte order, each at least one byte, none

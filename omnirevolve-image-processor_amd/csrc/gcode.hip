@@ -379,7 +379,7 @@ __global__ __launch_bounds__(256) void k_pk_service(const long long* __restrict_
 extern "C" int orip_gcode_to_steps(orip_ctx* c, const int64_t* off, const double* pts_mm, int64_t n, const orip_gcode_map* map, int64_t* n_out, int64_t* total_out) {
     orip_enter(c);
     ORIP_LANE(c, ORIP_LANE_CROSS);
-    c->gc_n = 0; c->gc_total = 0; c->gc_ready = false;
+    c->gc_n = 0; c->gc_total = 0; c->gc_ready = false; c->gc_merged = false;
     const bool resident = !off && !pts_mm && n > 0;         // the fitted paths orip_svg_flatten / orip_svg_fit left on the device (svg.hip)
     if (!map || !n_out || !total_out || n < 0 || (n > 0 && !off && !resident)) ORIP_FAIL(c, "bad arguments");
     *n_out = 0; *total_out = 0;
@@ -448,6 +448,7 @@ extern "C" int orip_gcode_steps_source_fetch(orip_ctx* c, int32_t* src_out) {
     orip_enter(c);
     ORIP_LANE(c, ORIP_LANE_CROSS);
     if (!c->gc_ready) ORIP_FAIL(c, "no step polylines: orip_gcode_to_steps has not succeeded since the last failure");
+    if (c->gc_merged) ORIP_FAIL(c, "the step polylines have been merged: ask for the sources before orip_gcode_merge");
     if (c->gc_n == 0) return 0;
     if (!src_out) ORIP_FAIL(c, "bad arguments");
     hipStream_t s = LN(c).stream;

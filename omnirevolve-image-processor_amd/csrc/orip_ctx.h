@@ -329,6 +329,11 @@ struct orip_ctx {
     // resident next to the step polylines: gc_src int32[gc_n] = the input path every step polyline came from (orip_gcode_steps_source_fetch); scratch of
     // orip_gcode_order_pens: op_ends = ends, groups, results, boxes and group descriptors, op_grid = the cell grids of all groups and the slot table
     DBuf gc_src, op_ends, op_grid;
+    // --merge-paths (gcode_merge.hip): mg_tab / mg_tmp = scratch of the node table and of the chains, free between calls (the unit states their layout);
+    // mg_off / mg_pts = the output, swapped with gc_off / gc_pts when a merge succeeds; mg_res = member_off int64[mg_paths + 1], member int32[mg_n],
+    // rev u8[mg_n] of the last merge of mg_n paths (-1: none) until the next one.  gc_merged: the resident step polylines are merged ones, gc_src no
+    // longer names them (cleared by orip_gcode_to_steps)
+    DBuf mg_tab, mg_tmp, mg_off, mg_pts, mg_res; int64_t mg_n = -1, mg_paths = 0; bool gc_merged = false;
     // svg2stream (svg.hip): scratch of the flattening and of the box, the resident paths (off int64[sv_n + 1], pts double2[sv_total]; raw units after
     // orip_svg_flatten, page mm after orip_svg_fit) until the next flatten; orip_gcode_to_steps reads them when it is called without pointers
     DBuf sv_tmp, sv_tmp2, sv_off, sv_pts; int64_t sv_n = 0, sv_total = 0; bool sv_ready = false, sv_box_ok = false; double sv_box[4] = {0, 0, 0, 0};

@@ -413,6 +413,45 @@ class Device:
                                               _p(st), _p(order), _p(rev)))
         return order[:n], rev[:n].astype(bool)
 
+    def gcode_merge(self, off, pts, group, n_groups: int, reverse: bool = False, n: int | None = None):
+        """--merge-paths (include/orip.h: orip_gcode_merge): step polylines (off int64 [n + 1], pts int32 [total, 2]; both None = the n resident ones) that
+        meet end to end inside a group become one stroke, and the merged polylines become the resident ones.  group int32 [n] or None (all 0).
+        -> (off int64, pts int32 [total', 2], member_off int64 [paths_out + 1], member int32 [n], rev bool [n], {"paths_out", "points_out", "joins", "cycles"})"""
+        o = p = None
+        if off is not None or pts is not None:
+            if off is None or pts is None:
+                raise OripError("off and pts: both or neither")
+            o = np.ascontiguousarray(off, np.int64).reshape(-1)
+            p = np.ascontiguousarray(pts, np.int32).reshape(-1, 2)
+            n = max(len(o) - 1, 0)
+            if len(o) < 1 or int(o[-1]) != len(p):
+                raise OripError(f"offsets end at {int(o[-1]) if len(o) else None}, {len(p)} points given")
+            if len(p) == 0:
+                p = np.zeros((1, 2), np.int32)                   # n == 0: a pointer all the same, so that the form stays the explicit one
+        g = None
+        if group is not None:
+            g = np.ascontiguousarray(group, np.int32).reshape(-1)
+            n = len(g) if n is None else n
+            if len(g) != n:
+                raise ValueError(f"{len(g)} groups given for {n} paths")
+        if n is None:
+            raise ValueError("n: the number of resident step polylines")
+        n = int(n)
+        st = np.zeros(4, np.int64)
+        self._ck(self.L.orip_gcode_merge(self.h, _p(o) if o is not None else None, _p(p) if p is not None else None, _p(g) if g is not None and n else None, n, int(n_groups),
+                                         _l.MERGE_REVERSE if reverse else 0, _p(st)))
+        paths, total = int(st[0]), int(st[1])
+        moff = np.zeros(paths + 1, np.int64); member = np.zeros(max(n, 1), np.int32); rev = np.zeros(max(n, 1), np.uint8)
+        self._ck(self.L.orip_gcode_merge_fetch(self.h, _p(moff), _p(member), _p(rev)))
+        off_s, pts_s = self.gcode_steps_fetch(paths, total)
+        return off_s, pts_s, moff, member[:n], rev[:n].astype(bool), {k: int(v) for k, v in zip(("paths_out", "points_out", "joins", "cycles"), st)}
+
+    def gcode_steps_fetch(self, n: int, total: int) -> Tuple[np.ndarray, np.ndarray]:
+        """the n resident step polylines of `total` points, as gcode_to_steps or gcode_merge left them: (off int64 [n + 1], pts int32 [total, 2])"""
+        off = np.zeros(int(n) + 1, np.int64); pts = np.zeros((max(int(total), 1), 2), np.int32)
+        self._ck(self.L.orip_gcode_steps_fetch(self.h, _p(off), _p(pts)))
+        return off, pts[:int(total)]
+
     def gcode_steps_source(self, n: int) -> np.ndarray:
         """for each of the n resident step polylines of gcode_to_steps the index of the input path it came from (int32 [n])"""
         src = np.zeros(max(int(n), 1), np.int32)

@@ -14,7 +14,12 @@ Pens (ours on this front door; the reference's gcode2stream.py draws everything 
 the text; svg2stream --pen-colors: the stroke colours) the paths are drawn pen after pen, in --pen-order, each pen's paths in nearest-neighbour order from
 where the pen before it stopped, with one colour byte per pen: draw_color_group of the reference's demo sheet (stream_generators/plotter_demo/
 omnirevolve_plotter_demo.py :317-333) called for one pen after the other.  --allow-reverse lets that order draw a stroke backwards when its far end is
-nearer (the demo's order_paths_nearest :197-216); both run on the device (orip_gcode_order_pens).  Without these options nothing changes."""
+nearer (the demo's order_paths_nearest :197-216); both run on the device (orip_gcode_order_pens).  Without these options nothing changes.
+
+--merge-paths (ours as well): step polylines of one pen that meet end to end -- every <line> of a CAD export, a path cut at every M, G-code that lifts the
+pen at every vertex -- become one stroke before any order (orip_gcode_merge; include/orip.h states the rule), so the pen stays down across the joint and the
+joint gets the corner slow-down of a vertex instead of a stop and a start.  Coincidence is on the step grid, without a tolerance; where three or more ends
+meet nothing is joined.  Without the option no device call is added and every byte is what it was."""
 from __future__ import annotations
 
 import argparse
@@ -63,6 +68,7 @@ class GcodeOptions:
     allow_reverse: bool = False         # ours from here on: strokes may be drawn backwards
     tool_pens: bool = False             # T words of the text choose the pen of a path
     pen_order: Optional[str] = None     # pens in drawing order, comma-separated (default: ascending)
+    merge_paths: bool = False           # strokes of one pen that meet end to end are drawn as one
 
 
 # ------------------------------------------------------------------ parse (:113-142, :177-300)
@@ -252,7 +258,7 @@ def plan_pens(off: np.ndarray, pts: np.ndarray, path_pen: np.ndarray, head: Sequ
 def build_stream_from_gcode(text_or_paths, opts: Optional[GcodeOptions] = None, device=None, *, steps_fn: Optional[Callable] = None,
                             order_fn: Optional[Callable] = None, codes_fn: Optional[Callable] = None, pack_fn: Optional[Callable] = None,
                             timings: Optional[dict] = None, pens: Optional[np.ndarray] = None, order_pens_fn: Optional[Callable] = None,
-                            source_fn: Optional[Callable] = None) -> Tuple[bytes, dict]:
+                            source_fn: Optional[Callable] = None, merge_fn: Optional[Callable] = None) -> Tuple[bytes, dict]:
     """The stream of a G-code text (str / bytes) or of paths in mm given as (off, pts_mm); opts as parsed, --speed-scale not yet applied.
     Device steps, each None = the GPU (orip.device.Device; there is no CPU path in the product):
       steps_fn(off, pts_mm, map: dict) -> (off int64, pts int32 [total, 2])      orip_gcode_to_steps
@@ -261,6 +267,9 @@ def build_stream_from_gcode(text_or_paths, opts: Optional[GcodeOptions] = None, 
     and, only with pens or --allow-reverse:
       source_fn(n) -> src int32 [n]: the input path of every step polyline       orip_gcode_steps_source_fetch
       order_pens_fn(ends, group int32 [n], n_groups, reverse) -> (order, rev)    orip_gcode_order_pens
+    and, only with --merge-paths (after the pens have been worked out, before any order):
+      merge_fn(off, pts, group int32 [n], n_groups, reverse) -> (off, pts, member_off, member, rev, counts)      orip_gcode_merge
+    info["merge"] then holds paths_in, paths_out, joins and cycles; the pen of a merged path is its members' pen.
     pens: one pen per input path, 0..7, or -1 for --color-index (a text's T words under --tool-pens when None).  info["pens"] then counts the paths per
     pen, those that took --color-index ("unmatched") and the strokes drawn backwards ("reversed").
     Returns (bytes, counts)."""
@@ -296,10 +305,14 @@ def build_stream_from_gcode(text_or_paths, opts: Optional[GcodeOptions] = None, 
         return EMPTY_STREAM, dict(info, bytes=len(EMPTY_STREAM))
     if not (1 <= W <= MAX_TARGET_STEPS and 1 <= H <= MAX_TARGET_STEPS):
         raise ValueError(f"target size {W} x {H} steps: each side must be in 1..2^30 (step coordinates are int32 on the device)")
-    if steps_fn is None or order_fn is None or (grouped and (order_pens_fn is None or source_fn is None)):
+    if steps_fn is None or order_fn is None or (grouped and (order_pens_fn is None or source_fn is None)) or (o.merge_paths and merge_fn is None):
         if device is None:
             from .stages import device as _default_device
             device = _default_device()
+        if merge_fn is None:                                              # the polylines this device's own conversion left resident are merged where they are
+            resident = steps_fn is None
+            merge_fn = lambda off, pts, group, n_groups, reverse: (device.gcode_merge(None, None, group, n_groups, reverse, n=len(off) - 1) if resident else
+                                                                   device.gcode_merge(off, pts, group, n_groups, reverse))
         steps_fn = steps_fn or device.gcode_to_steps
         order_fn = order_fn or device.gcode_order
         order_pens_fn = order_pens_fn or (lambda ends, group, n_groups, reverse: device.gcode_order_pens(ends, group, n_groups, reverse))
@@ -313,6 +326,8 @@ def build_stream_from_gcode(text_or_paths, opts: Optional[GcodeOptions] = None, 
     if n == 0:
         return EMPTY_STREAM, dict(info, bytes=len(EMPTY_STREAM))
     path_pen = None
+    pen = group = None
+    n_groups = MAX_PENS if pens is not None else 1
     if grouped:
         if not (0 <= int(o.color_index) <= 7):
             raise ValueError("color index 0..7")
@@ -326,7 +341,24 @@ def build_stream_from_gcode(text_or_paths, opts: Optional[GcodeOptions] = None, 
             group = np.argsort(np.asarray(seq))[pen].astype(np.int32)
         else:
             pen = np.full(n, int(o.color_index), np.int64); group = np.zeros(n, np.int32)
-        n_groups = MAX_PENS if pens is not None else 1
+    if o.merge_paths:
+        lap("order")                                                      # the sources and the pens belong to the order's lap, as before
+        n_in = n
+        off, pts, member_off, member, _, mst = merge_fn(off, pts, group if group is not None else np.zeros(n, np.int32), n_groups, bool(o.allow_reverse))
+        off = np.asarray(off, np.int64); pts = np.asarray(pts, np.int32).reshape(-1, 2)
+        member_off = np.asarray(member_off, np.int64).reshape(-1); member = np.asarray(member, np.int64).reshape(-1)
+        n = len(off) - 1
+        if not (1 <= n <= n_in) or len(member_off) != n + 1 or len(member) != n_in or int(member_off[-1]) != n_in or not np.array_equal(np.sort(member), np.arange(n_in)):
+            raise RuntimeError("the merge did not return every path once")
+        if grouped:
+            first = member[member_off[:-1]]
+            if (group[member] != np.repeat(group[first], np.diff(member_off))).any():
+                raise RuntimeError("the merge joined paths of different pens")
+            pen, group = pen[first], group[first]
+        info["paths"] = n
+        info["merge"] = {"paths_in": n_in, "paths_out": n, "joins": int(mst["joins"]), "cycles": int(mst["cycles"])}
+        lap("merge")
+    if grouped:
         if o.no_reorder:
             order, rev = np.argsort(group, kind="stable"), np.zeros(n, bool)      # pen after pen all the same, file order inside a pen
         else:
@@ -394,6 +426,7 @@ def build_argparser() -> argparse.ArgumentParser:
     ap.add_argument("--allow-reverse", action="store_true", help="let the order draw a stroke backwards when its far end is nearer")
     ap.add_argument("--tool-pens", action="store_true", help="a path is drawn with the pen its T word names (T0..T7; before any T: --color-index), pen after pen")
     ap.add_argument("--pen-order", default=None, help="pens in drawing order, comma-separated (default: ascending); pens without paths are skipped")
+    ap.add_argument("--merge-paths", action="store_true", help="draw strokes of one pen that meet end to end on the step grid as one stroke (no tolerance; where three or more ends meet, none are joined)")
     return ap
 
 
@@ -412,6 +445,8 @@ def main(argv: Optional[Sequence[str]] = None, **device_steps) -> None:
     print(f"[gcode] {info['paths']} paths in step space, {info['steps']} steps, target {info['target'][0]} x {info['target'][1]} steps")
     if "pens" in info:
         print("[gcode] pens: " + ", ".join(f"{p}: {k} paths" for p, k in enumerate(info["pens"]["paths"]) if k) + f"; {info['pens']['reversed']} strokes reversed")
+    if "merge" in info:
+        print("[gcode] merge: {paths_in} paths -> {paths_out}, {joins} pen lifts saved, {cycles} closed".format(**info["merge"]))
     print(f"stream saved: {a.output} ({len(data)} bytes)")
 
 

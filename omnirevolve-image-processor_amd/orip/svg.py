@@ -541,6 +541,7 @@ class SvgOptions:
     pen_colors: Optional[str] = None                    # None: one pen, --color-index
     pen_order: Optional[str] = None
     allow_reverse: bool = False
+    merge_paths: bool = False                           # strokes of one pen that meet end to end on the step grid are drawn as one (orip.gcode)
 
 
 HATCH_DIRECTIONS = {"horizontal": HATCH_HORIZONTAL, "vertical": HATCH_VERTICAL, "cross": HATCH_HORIZONTAL | HATCH_VERTICAL}
@@ -638,7 +639,7 @@ def gcode_options(o: SvgOptions) -> GC.GcodeOptions:
         W, H = int(round(o.page_width_mm * o.steps_per_mm)), int(round(o.page_height_mm * o.steps_per_mm))
     return GC.GcodeOptions(steps_per_mm=o.steps_per_mm, invert_y=o.invert_y, color_index=o.color_index, speed_scale=o.speed_scale, scale_x=1.0, scale_y=1.0,
                            offset_x_mm=0.0, offset_y_mm=0.0, target_width_steps=W, target_height_steps=H, no_reorder=bool(o.no_reorder),
-                           allow_reverse=bool(o.allow_reverse), pen_order=o.pen_order)
+                           allow_reverse=bool(o.allow_reverse), pen_order=o.pen_order, merge_paths=bool(o.merge_paths))
 
 
 def gcode_text(off, pts, passes: int = 1, pens=None) -> str:
@@ -680,6 +681,7 @@ class _Resident:
     def hatch_groups(self, paths, segments): return self.dev.svg_hatch_groups(segments)
     def source(self, n): return self.dev.gcode_steps_source(n)
     def order_pens(self, ends, group, n_groups, reverse): return self.dev.gcode_order_pens(ends, group, n_groups, reverse)
+    def merge(self, off, pts, group, n_groups, reverse): return self.dev.gcode_merge(None, None, group, n_groups, reverse, n=len(off) - 1)
 
 
 MAX_REFLATTEN = 8
@@ -748,7 +750,7 @@ def build_stream_from_svg(text: Union[str, bytes, SegmentTable], opts: Optional[
                           bbox_fn: Optional[Callable] = None, fit_fn: Optional[Callable] = None, hatch_fn: Optional[Callable] = None, fetch_fn: Optional[Callable] = None,
                           steps_fn: Optional[Callable] = None, order_fn: Optional[Callable] = None, codes_fn: Optional[Callable] = None, pack_fn: Optional[Callable] = None, timings: Optional[dict] = None,
                           want_paths: bool = False, hatch_groups_fn: Optional[Callable] = None, source_fn: Optional[Callable] = None,
-                          order_pens_fn: Optional[Callable] = None) -> Tuple[bytes, dict]:
+                          order_pens_fn: Optional[Callable] = None, merge_fn: Optional[Callable] = None) -> Tuple[bytes, dict]:
     """The stream of an SVG text (or of a parsed SegmentTable).  Device steps, each None = the GPU (there is no CPU path in the product):
       flatten_fn(table, tol_raw) -> paths          orip_svg_flatten      (`paths` is whatever the other steps take: on the GPU a count, the points stay there)
       bbox_fn(paths) -> (min x, min y, max x, max y)   orip_svg_bbox
@@ -760,6 +762,8 @@ def build_stream_from_svg(text: Union[str, bytes, SegmentTable], opts: Optional[
     and, only with --pen-colors or --allow-reverse:
       hatch_groups_fn(paths, segments) -> int32 [segments]   orip_svg_hatch_groups_fetch  (the fill group of every hatch line)
       source_fn, order_pens_fn                     as in orip.gcode.build_stream_from_gcode
+    and, only with --merge-paths:
+      merge_fn                                     as in orip.gcode.build_stream_from_gcode (hatch lines go through it like any path; serpentine lines do not touch)
     With --pen-colors, info["path_pens"] is the pen of every fitted path (hatch lines included, --color-index where no stroke is stated).
     Returns (bytes, info)."""
     import time
@@ -782,11 +786,14 @@ def build_stream_from_svg(text: Union[str, bytes, SegmentTable], opts: Optional[
         return data, dict(ginfo, **info)
     pens_on = o.pen_colors is not None
     if any(f is None for f in (flatten_fn, bbox_fn, fit_fn, fetch_fn, steps_fn, order_fn, codes_fn, pack_fn)) or (hp and hatch_fn is None) or \
-            ((pens_on or o.allow_reverse) and (source_fn is None or order_pens_fn is None)) or (pens_on and hp and hatch_groups_fn is None):
+            ((pens_on or o.allow_reverse) and (source_fn is None or order_pens_fn is None)) or (pens_on and hp and hatch_groups_fn is None) or \
+            (o.merge_paths and merge_fn is None):
         if device is None:
             from .stages import device as _default_device
             device = _default_device()
         R = _Resident(device)
+        if merge_fn is None:                                # where the conversion ran on this device its polylines are merged in place, else they are sent
+            merge_fn = R.merge if steps_fn is None else device.gcode_merge
         flatten_fn = flatten_fn or R.flatten; bbox_fn = bbox_fn or R.bbox; fit_fn = fit_fn or R.fit; fetch_fn = fetch_fn or R.fetch; steps_fn = steps_fn or R.steps
         hatch_fn = hatch_fn or R.hatch
         order_fn = order_fn or device.gcode_order
@@ -805,7 +812,7 @@ def build_stream_from_svg(text: Union[str, bytes, SegmentTable], opts: Optional[
         info["fitted_paths"] = (off_mm, np.asarray(pts_mm, np.float64).reshape(-1, 2))
     tm["fetch_paths"] = tm.get("fetch_paths", 0.0) + (time.perf_counter() - t0)
     data, ginfo = GC.build_stream_from_gcode((off_mm, np.zeros((int(off_mm[-1]), 2))), go, device, steps_fn=lambda _off, _pts, m: steps_fn(paths, m), order_fn=order_fn,
-                                             codes_fn=codes_fn, pack_fn=pack_fn, timings=tm, pens=pens, order_pens_fn=order_pens_fn, source_fn=source_fn)
+                                             codes_fn=codes_fn, pack_fn=pack_fn, timings=tm, pens=pens, order_pens_fn=order_pens_fn, source_fn=source_fn, merge_fn=merge_fn)
     return data, dict(ginfo, **info)
 
 
@@ -857,6 +864,8 @@ def build_stream_argparser() -> argparse.ArgumentParser:
     ap.add_argument("--no-reorder", action="store_true", help="keep the paths in file order")
     ap.add_argument("--pen-order", default=None, help="pens in drawing order, comma-separated (default: ascending); pens without paths are skipped")
     ap.add_argument("--allow-reverse", action="store_true", help="let the order draw a stroke backwards when its far end is nearer")
+    ap.add_argument("--merge-paths", action="store_true", help="draw strokes of one pen that meet end to end on the step grid as one stroke (no tolerance; where three or more ends meet, "
+                                                               "none are joined); the G-code file is not changed")
     ap.add_argument("--no-preview", action="store_true", help="do not render <svg stem>_stream_preview.png")
     ap.add_argument("--preview-render-width", type=int, default=d.preview_render_width)
     ap.add_argument("--preview-render-height", type=int, default=d.preview_render_height)
@@ -927,6 +936,8 @@ def main_stream(argv: Optional[Sequence[str]] = None, **device_steps) -> None:
     if "pens" in info:
         print("[svg] pens: " + ", ".join(f"{p}: {k} paths" for p, k in enumerate(info["pens"]["paths"]) if k) +
               f"; {info['pens']['unmatched']} without a stroke colour, {info['pens']['reversed']} strokes reversed")
+    if "merge" in info:
+        print("[svg] merge: {paths_in} paths -> {paths_out}, {joins} pen lifts saved, {cycles} closed".format(**info["merge"]))
     print(f"[svg] G-code saved: {gcode_path}")
     print(f"stream saved: {stream_path} ({len(data)} bytes)")
     if o.no_preview:

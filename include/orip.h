@@ -281,6 +281,38 @@ int orip_gcode_order_pens(orip_ctx* ctx, const int32_t* ends /* [n,4] or NULL = 
 int orip_gcode_merge(orip_ctx* ctx, const int64_t* off /* [n+1] or NULL */, const int32_t* pts /* [off[n],2] or NULL */, const int32_t* group /* [n] or NULL = all 0 */,
                      int64_t n, int32_t n_groups /* 1..64 */, int32_t flags, int64_t* stats /* [4]: paths_out, points_out, joins, cycles */);
 int orip_gcode_merge_fetch(orip_ctx* ctx, int64_t* member_off /* [paths_out+1] */, int32_t* member /* [n] */, uint8_t* rev /* [n] */);
+/* --improve-order (csrc/gcode_improve.hip; ours, the reference stops at the greedy order): 2-opt and or-opt on a drawing sequence, by steepest descent.
+ * Input: n step polylines given by their ends as for orip_gcode_order_pens (ends NULL = the resident ones, n must be their count), one group per polyline,
+ * a start cursor, and a valid drawing sequence order[n], rev[n]: order is a permutation, the groups of its entries do not decrease, rev[k] is 0 or 1 and
+ * all 0 unless ORIP_ORDER_REVERSE is set.  order / rev are rewritten in place.
+ *   Distance: d(p, q) = max(|px - qx|, |py - qy|), the steps of a travel (csrc/stream.hip: k_seg_counts).  Inside one group the positions are 0 .. m - 1;
+ *   a_k is the point where the stroke at position k is entered, b_k the point where it is left (rev swaps them); b_{-1} is the cursor at the group's
+ *   start; a_m does not exist and a term that mentions it is 0.  link(k) = d(b_{k-1}, a_k), link(m) = 0.  The travel of a group is the sum of link(k).
+ *   Moves.  R(i, j), 0 <= i <= j <= m - 1, only with ORIP_ORDER_REVERSE: the positions i .. j are put in reverse order and every stroke in them is drawn
+ *   the other way (i = j flips one stroke); gain = link(i) + link(j+1) - d(b_{i-1}, b_j) - d(a_i, a_{j+1}).  M(i, L, p), L in {1, 2, 3}, j = i + L - 1
+ *   <= m - 1, p in {-1, .., m - 1} without {i - 1, .., j}: the block i .. j is taken out and put back behind position p (p = -1: in front of everything),
+ *   its order and directions kept; gain = link(i) + link(j+1) - d(b_{i-1}, a_{j+1}) + link(p+1) - d(b_p, a_i) - d(b_j, a_{p+1}).
+ *   One round: of all moves the one with the largest gain; among equal gains the lowest (code, i, j) for R and (code, i, p) for M, code = 0 for R and L
+ *   for M.  If its gain is <= 0 the group is done (converged); otherwise it is applied, one move per round, and the next round follows, up to max_rounds
+ *   rounds per group.  max_rounds == ORIP_IMPROVE_ROUNDS_AUTO: 2 m + 64 rounds for a group of m strokes, worked out per group inside the call.  A group
+ *   counts as converged only when a round has found no gain: with max_rounds == 0 nothing is looked at and nothing converges.
+ *   Groups are handled in ascending order; the cursor of group g is the exit of the last stroke of the last non-empty group before it AS IMPROVED
+ *   (start_xy for the first).  A group's end is open: the approach to the next group is not in its objective.  Every applied move lowers a non-negative
+ *   integer, so the descent ends.  Gains are sums of three distances of up to 2^30 each and do not fit int32.
+ *   A group of more than ORIP_IMPROVE_MAX_PATHS strokes is left exactly as given and counted in skipped_groups: not an error, a hatch-heavy sheet must
+ *   still plot.  Declined: a time-based stop (not deterministic), several moves per round, re-insertion of a block reversed.
+ * stats: travel_before and travel_after cover the whole sequence from start_xy, every link of every group and the approaches between groups -- the
+ * pen-up steps the stream will hold; rounds = moves applied, over all groups; converged_groups; skipped_groups.  Empty groups are counted nowhere.
+ * Errors before any launch, with the context still good and order / rev untouched: the argument errors of orip_gcode_order_pens (n < 0 or > 2^26,
+ * n_groups outside 1 .. 64, unknown flags, a group or coordinate or start out of range, n that is not the resident count), an order that is not a
+ * permutation or whose groups decrease, a rev bit without the flag, max_rounds < 0, NULL stats.  n == 0 returns zeros before any launch.
+ * A call on 65 536 strokes with ORIP_IMPROVE_ROUNDS_AUTO can run for tens of seconds. */
+#define ORIP_IMPROVE_MAX_PATHS 65536
+#define ORIP_IMPROVE_ROUNDS_AUTO INT64_MAX
+int orip_gcode_improve(orip_ctx* ctx, const int32_t* ends /* [n,4] or NULL = resident */, const int32_t* group /* [n] */, int64_t n, int32_t n_groups,
+                       int32_t flags /* ORIP_ORDER_REVERSE */, const int32_t* start_xy /* NULL = (0,0) */, int64_t max_rounds,
+                       int32_t* order /* [n] in/out */, uint8_t* rev /* [n] in/out */,
+                       int64_t* stats /* [5]: travel_before, travel_after, rounds, converged_groups, skipped_groups */);
 /* StreamWriter.add_steps / finalize (helper :55-68, :166-175) for a whole plot: the bytes of the stream from the direction codes orip_stream_codes left
  * resident.  Piece i reads cnt[i] codes from code0[i] on and owns the bytes from pos[i]: its speed byte when speed[i] >= 0, then (cnt[i] + 1) / 2 step bytes
  * (two codes per byte, paired inside the piece, the last byte of an odd piece holds one).  Pieces are listed in byte order, each at least one byte, none

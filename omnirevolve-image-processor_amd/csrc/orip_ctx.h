@@ -334,6 +334,10 @@ struct orip_ctx {
     // rev u8[mg_n] of the last merge of mg_n paths (-1: none) until the next one.  gc_merged: the resident step polylines are merged ones, gc_src no
     // longer names them (cleared by orip_gcode_to_steps)
     DBuf mg_tab, mg_tmp, mg_off, mg_pts, mg_res; int64_t mg_n = -1, mg_paths = 0; bool gc_merged = false;
+    // --improve-order (gcode_improve.hip), free between calls: im_state = the ends, the given sequence and the two position-ordered copies of the state
+    // (ab int4[2][n], id int[2][n]) a move is written between; im_rec = one record per block of the evaluation, the two status slots and the two travels
+    // (the unit states the layout)
+    DBuf im_state, im_rec;
     // svg2stream (svg.hip): scratch of the flattening and of the box, the resident paths (off int64[sv_n + 1], pts double2[sv_total]; raw units after
     // orip_svg_flatten, page mm after orip_svg_fit) until the next flatten; orip_gcode_to_steps reads them when it is called without pointers
     DBuf sv_tmp, sv_tmp2, sv_off, sv_pts; int64_t sv_n = 0, sv_total = 0; bool sv_ready = false, sv_box_ok = false; double sv_box[4] = {0, 0, 0, 0};

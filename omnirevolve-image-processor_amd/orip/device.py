@@ -413,6 +413,33 @@ class Device:
                                               _p(st), _p(order), _p(rev)))
         return order[:n], rev[:n].astype(bool)
 
+    def gcode_improve(self, ends: np.ndarray | None, group, n_groups: int, order, rev, reverse: bool = False, start=(0, 0), max_rounds: int | None = None,
+                      n: int | None = None):
+        """--improve-order (include/orip.h: orip_gcode_improve): 2-opt and or-opt on the drawing sequence (order int [n], rev bool [n]) of the paths
+        ends int32 [n, 4] (None: the n resident step polylines), group after group from `start`; max_rounds None = 2 m + 64 rounds for a group of m strokes.
+        -> (order int32 [n], rev bool [n], {"travel_before", "travel_after", "rounds", "converged_groups", "skipped_groups"})"""
+        g = np.ascontiguousarray(group, np.int32).reshape(-1)
+        if ends is not None:
+            e = np.ascontiguousarray(ends, np.int32).reshape(-1, 4)
+            n = len(e)
+        n = len(g) if n is None else int(n)
+        o = np.array(order, np.int32).reshape(-1)                # copies: the call rewrites them in place
+        r = np.array(rev, np.uint8).reshape(-1)
+        if len(g) != n or len(o) != n or len(r) != n:
+            raise ValueError(f"{len(g)} groups, {len(o)} positions and {len(r)} directions given for {n} paths")
+        st = np.asarray(start, np.int64).reshape(-1)
+        if len(st) != 2 or (st < 0).any() or (st > 1 << 30).any():
+            raise OripError(f"start {tuple(st.tolist())} outside 0..2^30")
+        st = np.ascontiguousarray(st, np.int32)
+        if max_rounds is not None and not (-(1 << 63) <= int(max_rounds) < (1 << 63)):
+            raise OripError(f"{max_rounds} rounds")
+        if n == 0:
+            o = np.zeros(1, np.int32); r = np.zeros(1, np.uint8)
+        stats = np.zeros(5, np.int64)
+        self._ck(self.L.orip_gcode_improve(self.h, _p(e) if ends is not None and n else None, _p(g) if n else None, n, int(n_groups), _l.ORDER_REVERSE if reverse else 0,
+                                           _p(st), _l.IMPROVE_ROUNDS_AUTO if max_rounds is None else int(max_rounds), _p(o), _p(r), _p(stats)))
+        return o[:n], r[:n].astype(bool), {k: int(v) for k, v in zip(("travel_before", "travel_after", "rounds", "converged_groups", "skipped_groups"), stats)}
+
     def gcode_merge(self, off, pts, group, n_groups: int, reverse: bool = False, n: int | None = None):
         """--merge-paths (include/orip.h: orip_gcode_merge): step polylines (off int64 [n + 1], pts int32 [total, 2]; both None = the n resident ones) that
         meet end to end inside a group become one stroke, and the merged polylines become the resident ones.  group int32 [n] or None (all 0).

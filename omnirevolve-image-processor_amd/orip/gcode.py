@@ -19,7 +19,13 @@ nearer (the demo's order_paths_nearest :197-216); both run on the device (orip_g
 --merge-paths (ours as well): step polylines of one pen that meet end to end -- every <line> of a CAD export, a path cut at every M, G-code that lifts the
 pen at every vertex -- become one stroke before any order (orip_gcode_merge; include/orip.h states the rule), so the pen stays down across the joint and the
 joint gets the corner slow-down of a vertex instead of a stop and a start.  Coincidence is on the step grid, without a tolerance; where three or more ends
-meet nothing is joined.  Without the option no device call is added and every byte is what it was."""
+meet nothing is joined.  Without the option no device call is added and every byte is what it was.
+
+--improve-order (ours as well): the greedy order looks one step ahead; this option then lowers the pen-up steps of the plot, max(|dx|, |dy|) per travel as the
+stream compiler counts them, by steepest descent over two kinds of move inside a pen's group: a run of strokes drawn in reverse order and direction (2-opt,
+only with --allow-reverse) and a block of one to three strokes put elsewhere (or-opt).  One move per round, the best of all, ties by a fixed order; at most
+--improve-rounds rounds per group (default 2 m + 64 for m strokes); groups of more than 65 536 strokes are left as they are (orip_gcode_improve;
+include/orip.h states the rule).  It runs after the order and, with --merge-paths, on the merged strokes.  Without the option no device call is added."""
 from __future__ import annotations
 
 import argparse
@@ -69,6 +75,8 @@ class GcodeOptions:
     tool_pens: bool = False             # T words of the text choose the pen of a path
     pen_order: Optional[str] = None     # pens in drawing order, comma-separated (default: ascending)
     merge_paths: bool = False           # strokes of one pen that meet end to end are drawn as one
+    improve_order: bool = False         # 2-opt / or-opt on the order, per pen group
+    improve_rounds: Optional[int] = None    # rounds per group at most (None: 2 m + 64 for a group of m strokes); only with improve_order
 
 
 # ------------------------------------------------------------------ parse (:113-142, :177-300)
@@ -258,7 +266,7 @@ def plan_pens(off: np.ndarray, pts: np.ndarray, path_pen: np.ndarray, head: Sequ
 def build_stream_from_gcode(text_or_paths, opts: Optional[GcodeOptions] = None, device=None, *, steps_fn: Optional[Callable] = None,
                             order_fn: Optional[Callable] = None, codes_fn: Optional[Callable] = None, pack_fn: Optional[Callable] = None,
                             timings: Optional[dict] = None, pens: Optional[np.ndarray] = None, order_pens_fn: Optional[Callable] = None,
-                            source_fn: Optional[Callable] = None, merge_fn: Optional[Callable] = None) -> Tuple[bytes, dict]:
+                            source_fn: Optional[Callable] = None, merge_fn: Optional[Callable] = None, improve_fn: Optional[Callable] = None) -> Tuple[bytes, dict]:
     """The stream of a G-code text (str / bytes) or of paths in mm given as (off, pts_mm); opts as parsed, --speed-scale not yet applied.
     Device steps, each None = the GPU (orip.device.Device; there is no CPU path in the product):
       steps_fn(off, pts_mm, map: dict) -> (off int64, pts int32 [total, 2])      orip_gcode_to_steps
@@ -270,6 +278,9 @@ def build_stream_from_gcode(text_or_paths, opts: Optional[GcodeOptions] = None, 
     and, only with --merge-paths (after the pens have been worked out, before any order):
       merge_fn(off, pts, group int32 [n], n_groups, reverse) -> (off, pts, member_off, member, rev, counts)      orip_gcode_merge
     info["merge"] then holds paths_in, paths_out, joins and cycles; the pen of a merged path is its members' pen.
+    and, only with --improve-order (after the order, before the paths are gathered; without pens: one group, no stroke reversed):
+      improve_fn(ends, group int32 [n], n_groups, order, rev, reverse, max_rounds) -> (order, rev, stats)       orip_gcode_improve
+    info["improve"] then holds travel_before, travel_after (pen-up steps of the whole plot), rounds, converged_groups and skipped_groups.
     pens: one pen per input path, 0..7, or -1 for --color-index (a text's T words under --tool-pens when None).  info["pens"] then counts the paths per
     pen, those that took --color-index ("unmatched") and the strokes drawn backwards ("reversed").
     Returns (bytes, counts)."""
@@ -277,6 +288,7 @@ def build_stream_from_gcode(text_or_paths, opts: Optional[GcodeOptions] = None, 
     o = apply_speed_scale(GcodeOptions(**{f.name: getattr(opts, f.name) for f in fields(GcodeOptions)}) if opts is not None else GcodeOptions())
     W, H = target_size(o)
     sc = stream_config(o)
+    check_improve_options(o)
     tm = timings if timings is not None else {}
     t0 = time.perf_counter()
 
@@ -305,7 +317,8 @@ def build_stream_from_gcode(text_or_paths, opts: Optional[GcodeOptions] = None, 
         return EMPTY_STREAM, dict(info, bytes=len(EMPTY_STREAM))
     if not (1 <= W <= MAX_TARGET_STEPS and 1 <= H <= MAX_TARGET_STEPS):
         raise ValueError(f"target size {W} x {H} steps: each side must be in 1..2^30 (step coordinates are int32 on the device)")
-    if steps_fn is None or order_fn is None or (grouped and (order_pens_fn is None or source_fn is None)) or (o.merge_paths and merge_fn is None):
+    if steps_fn is None or order_fn is None or (grouped and (order_pens_fn is None or source_fn is None)) or (o.merge_paths and merge_fn is None) or \
+            (o.improve_order and improve_fn is None):
         if device is None:
             from .stages import device as _default_device
             device = _default_device()
@@ -317,6 +330,8 @@ def build_stream_from_gcode(text_or_paths, opts: Optional[GcodeOptions] = None, 
         order_fn = order_fn or device.gcode_order
         order_pens_fn = order_pens_fn or (lambda ends, group, n_groups, reverse: device.gcode_order_pens(ends, group, n_groups, reverse))
         source_fn = source_fn or device.gcode_steps_source
+        improve_fn = improve_fn or (lambda ends, group, n_groups, order, rev, reverse, max_rounds: device.gcode_improve(ends, group, n_groups, order, rev, reverse,
+                                                                                                                   max_rounds=max_rounds))
     off, pts = steps_fn(off_mm, pts_mm, dict(scale_x=o.scale_x, scale_y=o.scale_y, offset_x_mm=o.offset_x_mm, offset_y_mm=o.offset_y_mm, steps_per_mm=o.steps_per_mm,
                                              W=W, H=H, invert_y=int(bool(o.invert_y))))
     off = np.asarray(off, np.int64); pts = np.asarray(pts, np.int32).reshape(-1, 2)
@@ -358,6 +373,14 @@ def build_stream_from_gcode(text_or_paths, opts: Optional[GcodeOptions] = None, 
         info["paths"] = n
         info["merge"] = {"paths_in": n_in, "paths_out": n, "joins": int(mst["joins"]), "cycles": int(mst["cycles"])}
         lap("merge")
+    def improve(ends, group, n_groups, order, rev, reverse):
+        order, rev, ist = improve_fn(ends, group, n_groups, np.asarray(order, np.int32), np.asarray(rev, bool), reverse, o.improve_rounds)
+        order = np.asarray(order, np.int64).reshape(-1); rev = np.asarray(rev, bool).reshape(-1)
+        if len(order) != n or len(rev) != n or not np.array_equal(np.sort(order), np.arange(n)) or (np.diff(np.asarray(group)[order]) < 0).any() or (rev.any() and not reverse):
+            raise RuntimeError("the improved order is not a permutation that keeps the pens together and the directions allowed")
+        info["improve"] = {k: int(ist[k]) for k in IMPROVE_STATS}
+        return order, rev
+
     if grouped:
         if o.no_reorder:
             order, rev = np.argsort(group, kind="stable"), np.zeros(n, bool)      # pen after pen all the same, file order inside a pen
@@ -366,6 +389,10 @@ def build_stream_from_gcode(text_or_paths, opts: Optional[GcodeOptions] = None, 
             order = np.asarray(order, np.int64); rev = np.asarray(rev, bool)
             if len(order) != n or len(rev) != n or not np.array_equal(np.sort(order), np.arange(n)) or (np.diff(group[order]) < 0).any():
                 raise RuntimeError("the path order is not a permutation that keeps the pens together")
+            if o.improve_order:
+                lap("order")
+                order, rev = improve(np.ascontiguousarray(np.concatenate([pts[off[:-1]], pts[off[1:] - 1]], 1), np.int32), group, n_groups, order, rev, bool(o.allow_reverse))
+                lap("improve")
         off, pts = gather_paths(off, pts, order, rev)
         path_pen = pen[order]
         if pens is not None:
@@ -376,6 +403,10 @@ def build_stream_from_gcode(text_or_paths, opts: Optional[GcodeOptions] = None, 
         order = np.asarray(order_fn(np.ascontiguousarray(np.concatenate([pts[off[:-1]], pts[off[1:] - 1]], 1), np.int32)), np.int64)
         if len(order) != n or not np.array_equal(np.sort(order), np.arange(n)):
             raise RuntimeError("the path order is not a permutation")
+        if o.improve_order:
+            lap("order")
+            order, _ = improve(np.ascontiguousarray(np.concatenate([pts[off[:-1]], pts[off[1:] - 1]], 1), np.int32), np.zeros(n, np.int32), 1, order, np.zeros(n, bool), False)
+            lap("improve")
         lens = np.diff(off)[order]
         noff = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
         pts = pts[np.repeat(off[:-1][order], lens) + np.arange(int(lens.sum())) - np.repeat(noff[:-1], lens)]
@@ -392,6 +423,25 @@ def build_stream_from_gcode(text_or_paths, opts: Optional[GcodeOptions] = None, 
     data, table, coff = ST.compile_plan(P, sc, device, codes_fn, pack_fn, initial_div=int(sc.div_start), lap=lap)
     info.update(steps=int(coff[-1]), bytes=len(data), pieces=len(table.pos), moves=len(P.moves))
     return data, info
+
+
+IMPROVE_STATS = ("travel_before", "travel_after", "rounds", "converged_groups", "skipped_groups")
+
+
+def check_improve_options(o) -> None:
+    """--improve-order starts from the greedy order, and --improve-rounds belongs to it"""
+    if o.improve_order and o.no_reorder:
+        raise ValueError("--improve-order with --no-reorder: file order was asked for")
+    if o.improve_rounds is not None and not o.improve_order:
+        raise ValueError("--improve-rounds needs --improve-order")
+    if o.improve_rounds is not None and int(o.improve_rounds) < 0:
+        raise ValueError("--improve-rounds must not be negative")
+
+
+def improve_line(tag: str, st: dict) -> str:
+    saved = st["travel_before"] - st["travel_after"]
+    return (f"[{tag}] improve: pen-up steps {st['travel_before']} -> {st['travel_after']} ({saved} saved), {st['rounds']} rounds, "
+            f"{st['converged_groups']} groups converged, {st['skipped_groups']} skipped")
 
 
 # ------------------------------------------------------------------ command line (:436-638)
@@ -427,6 +477,8 @@ def build_argparser() -> argparse.ArgumentParser:
     ap.add_argument("--tool-pens", action="store_true", help="a path is drawn with the pen its T word names (T0..T7; before any T: --color-index), pen after pen")
     ap.add_argument("--pen-order", default=None, help="pens in drawing order, comma-separated (default: ascending); pens without paths are skipped")
     ap.add_argument("--merge-paths", action="store_true", help="draw strokes of one pen that meet end to end on the step grid as one stroke (no tolerance; where three or more ends meet, none are joined)")
+    ap.add_argument("--improve-order", action="store_true", help="after the greedy order, lower the pen-up travel by 2-opt (with --allow-reverse) and or-opt moves, one per round, pen by pen")
+    ap.add_argument("--improve-rounds", type=int, default=None, help="rounds per pen at most (default: 2 m + 64 for m strokes); needs --improve-order")
     return ap
 
 
@@ -438,6 +490,7 @@ def main(argv: Optional[Sequence[str]] = None, **device_steps) -> None:
     a = build_argparser().parse_args(argv)
     opts = options_from_args(a)
     apply_speed_scale(GcodeOptions(speed_scale=opts.speed_scale))        # a bad scale ends the run before the file is read, as in the reference
+    check_improve_options(opts)
     text = Path(a.input).read_bytes()
     data, info = build_stream_from_gcode(text, opts, **device_steps)
     Path(a.output).write_bytes(data)
@@ -447,6 +500,8 @@ def main(argv: Optional[Sequence[str]] = None, **device_steps) -> None:
         print("[gcode] pens: " + ", ".join(f"{p}: {k} paths" for p, k in enumerate(info["pens"]["paths"]) if k) + f"; {info['pens']['reversed']} strokes reversed")
     if "merge" in info:
         print("[gcode] merge: {paths_in} paths -> {paths_out}, {joins} pen lifts saved, {cycles} closed".format(**info["merge"]))
+    if "improve" in info:
+        print(improve_line("gcode", info["improve"]))
     print(f"stream saved: {a.output} ({len(data)} bytes)")
 
 

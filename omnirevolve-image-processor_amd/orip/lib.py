@@ -76,6 +76,7 @@ SIGNATURES = {
     "orip_gcode_order": (_i32, [_vp, _vp, _i64, _vp]), "orip_gcode_steps_source_fetch": (_i32, [_vp, _vp]),
     "orip_gcode_order_pens": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp]),
     "orip_gcode_merge": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp]), "orip_gcode_merge_fetch": (_i32, [_vp, _vp, _vp, _vp]),
+    "orip_gcode_improve": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _i64, _vp, _vp, _vp]),
     "orip_svg_flatten": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _f64, _P(_i64)]), "orip_svg_paths_fetch": (_i32, [_vp, _vp, _vp]),
     "orip_svg_bbox": (_i32, [_vp, _vp]), "orip_svg_fit": (_i32, [_vp, _f64, _f64, _f64, _f64]),
     "orip_svg_hatch": (_i32, [_vp, _vp, _i64, _f64, _i32, _i32, _i32, _vp]), "orip_svg_hatch_groups_fetch": (_i32, [_vp, _vp]),
@@ -87,6 +88,7 @@ COMM_ID_BYTES = 128
 HATCH_SERPENTINE, HATCH_HORIZONTAL, HATCH_VERTICAL = 1, 2, 4
 ORDER_REVERSE, ORDER_MAX_GROUPS = 1, 64
 MERGE_REVERSE = 1
+IMPROVE_MAX_PATHS, IMPROVE_ROUNDS_AUTO = 65536, (1 << 63) - 1
 
 _lib = None
 

@@ -542,6 +542,8 @@ class SvgOptions:
     pen_order: Optional[str] = None
     allow_reverse: bool = False
     merge_paths: bool = False                           # strokes of one pen that meet end to end on the step grid are drawn as one (orip.gcode)
+    improve_order: bool = False                         # 2-opt / or-opt on the order, per pen group (orip.gcode)
+    improve_rounds: Optional[int] = None                # rounds per group at most; None: 2 m + 64
 
 
 HATCH_DIRECTIONS = {"horizontal": HATCH_HORIZONTAL, "vertical": HATCH_VERTICAL, "cross": HATCH_HORIZONTAL | HATCH_VERTICAL}
@@ -639,7 +641,8 @@ def gcode_options(o: SvgOptions) -> GC.GcodeOptions:
         W, H = int(round(o.page_width_mm * o.steps_per_mm)), int(round(o.page_height_mm * o.steps_per_mm))
     return GC.GcodeOptions(steps_per_mm=o.steps_per_mm, invert_y=o.invert_y, color_index=o.color_index, speed_scale=o.speed_scale, scale_x=1.0, scale_y=1.0,
                            offset_x_mm=0.0, offset_y_mm=0.0, target_width_steps=W, target_height_steps=H, no_reorder=bool(o.no_reorder),
-                           allow_reverse=bool(o.allow_reverse), pen_order=o.pen_order, merge_paths=bool(o.merge_paths))
+                           allow_reverse=bool(o.allow_reverse), pen_order=o.pen_order, merge_paths=bool(o.merge_paths),
+                           improve_order=bool(o.improve_order), improve_rounds=o.improve_rounds)
 
 
 def gcode_text(off, pts, passes: int = 1, pens=None) -> str:
@@ -750,7 +753,7 @@ def build_stream_from_svg(text: Union[str, bytes, SegmentTable], opts: Optional[
                           bbox_fn: Optional[Callable] = None, fit_fn: Optional[Callable] = None, hatch_fn: Optional[Callable] = None, fetch_fn: Optional[Callable] = None,
                           steps_fn: Optional[Callable] = None, order_fn: Optional[Callable] = None, codes_fn: Optional[Callable] = None, pack_fn: Optional[Callable] = None, timings: Optional[dict] = None,
                           want_paths: bool = False, hatch_groups_fn: Optional[Callable] = None, source_fn: Optional[Callable] = None,
-                          order_pens_fn: Optional[Callable] = None, merge_fn: Optional[Callable] = None) -> Tuple[bytes, dict]:
+                          order_pens_fn: Optional[Callable] = None, merge_fn: Optional[Callable] = None, improve_fn: Optional[Callable] = None) -> Tuple[bytes, dict]:
     """The stream of an SVG text (or of a parsed SegmentTable).  Device steps, each None = the GPU (there is no CPU path in the product):
       flatten_fn(table, tol_raw) -> paths          orip_svg_flatten      (`paths` is whatever the other steps take: on the GPU a count, the points stay there)
       bbox_fn(paths) -> (min x, min y, max x, max y)   orip_svg_bbox
@@ -764,6 +767,8 @@ def build_stream_from_svg(text: Union[str, bytes, SegmentTable], opts: Optional[
       source_fn, order_pens_fn                     as in orip.gcode.build_stream_from_gcode
     and, only with --merge-paths:
       merge_fn                                     as in orip.gcode.build_stream_from_gcode (hatch lines go through it like any path; serpentine lines do not touch)
+    and, only with --improve-order:
+      improve_fn                                   as in orip.gcode.build_stream_from_gcode
     With --pen-colors, info["path_pens"] is the pen of every fitted path (hatch lines included, --color-index where no stroke is stated).
     Returns (bytes, info)."""
     import time
@@ -773,6 +778,7 @@ def build_stream_from_svg(text: Union[str, bytes, SegmentTable], opts: Optional[
     hp = hatch_params(o)
     if o.pen_colors is not None:
         parse_pen_colors(o.pen_colors)                      # a bad list ends the run before anything is parsed
+    GC.check_improve_options(o)
     table = text if isinstance(text, SegmentTable) else parse_svg(text, o.hatch_fill)
     tm["parse_svg"] = tm.get("parse_svg", 0.0) + (time.perf_counter() - t0)
     go = gcode_options(o)
@@ -787,7 +793,7 @@ def build_stream_from_svg(text: Union[str, bytes, SegmentTable], opts: Optional[
     pens_on = o.pen_colors is not None
     if any(f is None for f in (flatten_fn, bbox_fn, fit_fn, fetch_fn, steps_fn, order_fn, codes_fn, pack_fn)) or (hp and hatch_fn is None) or \
             ((pens_on or o.allow_reverse) and (source_fn is None or order_pens_fn is None)) or (pens_on and hp and hatch_groups_fn is None) or \
-            (o.merge_paths and merge_fn is None):
+            (o.merge_paths and merge_fn is None) or (o.improve_order and improve_fn is None):
         if device is None:
             from .stages import device as _default_device
             device = _default_device()
@@ -812,7 +818,8 @@ def build_stream_from_svg(text: Union[str, bytes, SegmentTable], opts: Optional[
         info["fitted_paths"] = (off_mm, np.asarray(pts_mm, np.float64).reshape(-1, 2))
     tm["fetch_paths"] = tm.get("fetch_paths", 0.0) + (time.perf_counter() - t0)
     data, ginfo = GC.build_stream_from_gcode((off_mm, np.zeros((int(off_mm[-1]), 2))), go, device, steps_fn=lambda _off, _pts, m: steps_fn(paths, m), order_fn=order_fn,
-                                             codes_fn=codes_fn, pack_fn=pack_fn, timings=tm, pens=pens, order_pens_fn=order_pens_fn, source_fn=source_fn, merge_fn=merge_fn)
+                                             codes_fn=codes_fn, pack_fn=pack_fn, timings=tm, pens=pens, order_pens_fn=order_pens_fn, source_fn=source_fn, merge_fn=merge_fn,
+                                             improve_fn=improve_fn)
     return data, dict(ginfo, **info)
 
 
@@ -866,6 +873,9 @@ def build_stream_argparser() -> argparse.ArgumentParser:
     ap.add_argument("--allow-reverse", action="store_true", help="let the order draw a stroke backwards when its far end is nearer")
     ap.add_argument("--merge-paths", action="store_true", help="draw strokes of one pen that meet end to end on the step grid as one stroke (no tolerance; where three or more ends meet, "
                                                                "none are joined); the G-code file is not changed")
+    ap.add_argument("--improve-order", action="store_true", help="after the greedy order, lower the pen-up travel by 2-opt (with --allow-reverse) and or-opt moves, one per round, pen by pen; "
+                                                                 "the G-code file is not changed")
+    ap.add_argument("--improve-rounds", type=int, default=None, help="rounds per pen at most (default: 2 m + 64 for m strokes); needs --improve-order")
     ap.add_argument("--no-preview", action="store_true", help="do not render <svg stem>_stream_preview.png")
     ap.add_argument("--preview-render-width", type=int, default=d.preview_render_width)
     ap.add_argument("--preview-render-height", type=int, default=d.preview_render_height)
@@ -938,6 +948,8 @@ def main_stream(argv: Optional[Sequence[str]] = None, **device_steps) -> None:
               f"; {info['pens']['unmatched']} without a stroke colour, {info['pens']['reversed']} strokes reversed")
     if "merge" in info:
         print("[svg] merge: {paths_in} paths -> {paths_out}, {joins} pen lifts saved, {cycles} closed".format(**info["merge"]))
+    if "improve" in info:
+        print(GC.improve_line("svg", info["improve"]))
     print(f"[svg] G-code saved: {gcode_path}")
     print(f"stream saved: {stream_path} ({len(data)} bytes)")
     if o.no_preview:

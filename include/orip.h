@@ -239,6 +239,34 @@ int orip_gcode_to_steps(orip_ctx* ctx, const int64_t* off /* [n+1] or NULL */, c
 int orip_gcode_steps_fetch(orip_ctx* ctx, int64_t* off_out /* [n_out+1] */, int32_t* pts_out /* [total_out,2] or NULL */);
 /* src_out[k] = the index of the input path that step polyline k came from (ascending: the conversion drops paths, it never reorders them). */
 int orip_gcode_steps_source_fetch(orip_ctx* ctx, int32_t* src_out /* [n_out] */);
+/* --clip (csrc/gcode_clip.hip; ours, the reference clamps): orip_gcode_to_steps with the strokes CUT at a rectangle of the sheet instead of every point
+ * clamped to it.  What lies outside is not drawn and the pen is lifted there; the clamp draws it along the edge of the paper, and gives a segment with
+ * one end outside another slope.  rect = (x0, y0, x1, y1) in steps, the closed rectangle R = [x0, x1] x [y0, y1], 0 <= x0 <= x1 <= W - 1 and the same in y.
+ *   1. Conversion.  Every point is converted as orip_gcode_to_steps converts it -- the same three double operations without fused multiply-add, (H - 1) - y
+ *      under invert_y, round half to even (one piece of code, csrc/gc_convert.h) -- and NOT clamped.  In a path of two points or more a coordinate that is
+ *      not finite afterwards is the error it is there, and a rounded coordinate outside [-2^30, 2^30] is an error too: the drawing is that far off the
+ *      sheet.  Both are found on the device; no step polylines are resident after them.
+ *   2. Segments.  A path of k >= 2 points v_0 .. v_{k-1} has k - 1 segments P(t) = v_i + t (v_{i+1} - v_i), t in [0, 1]; degenerate ones are included.
+ *      The part of a segment inside R is empty or an interval [t0, t1] of exact rationals; a single point, t0 = t1, is not empty.  The clipped ends are
+ *      A = P(t0) and B = P(t1).  The coordinate fixed by the side that was hit is exact.  The other one is v + num / den with den > 0 and is rounded as
+ *      v + floor(num / den) + (2 rem >= den): to the nearest step, halves toward +infinity.  That is a function of the exact point, so a segment and its
+ *      reverse are cut at the same grid points, and a cut point never leaves R.  A cut point may sit up to half a step off the true line: that is the grid.
+ *   3. Strokes.  The segments of a path are taken in order.  Two consecutive non-empty segments belong to one stroke iff the first has t1 = 1 and the second
+ *      t0 = 0, which is to say iff their shared vertex lies in R; anything else starts a new stroke.  A stroke's points are A of its first segment, then B
+ *      of each of its segments; a point equal to its predecessor is dropped, then every stroke left with fewer than two points (a path that touches a
+ *      corner of R from outside draws nothing).  Strokes keep the order of their paths and, inside a path, of their segments.
+ *   4. For an input whose unclamped points all lie in R the result is orip_gcode_to_steps' result exactly.
+ * The argument forms are orip_gcode_to_steps' (off == NULL and pts_mm == NULL: the resident fitted paths), and so is what is resident afterwards: the
+ * strokes are the step polylines that orip_gcode_steps_fetch copies out and that orip_gcode_order, orip_gcode_order_pens, orip_gcode_merge and
+ * orip_gcode_improve take for NULL, and orip_gcode_steps_source_fetch gives src[k] = the input path of stroke k, ascending, now with repeats.
+ * stats: segments, inside (whole: t0 = 0 and t1 = 1), cut (not empty, not whole), outside (empty), paths_out, points_out; inside + cut + outside ==
+ * segments.  Coordinates are in +-2^30, so a difference is up to 2^31 and every product the rule compares is up to 2^62: int64 throughout.
+ * Errors before any launch, with the resident step polylines left as they were: the argument errors of orip_gcode_to_steps; rect NULL, inverted or not
+ * inside the sheet; stats NULL; 2^29 points or more (a cut can double the points, and the input no longer bounds the output).
+ * Declined: clipping in mm before the rounding (the result would depend on the double rounding of a crossing), a free clip polygon. */
+int orip_gcode_to_steps_clip(orip_ctx* ctx, const int64_t* off /* [n+1] or NULL */, const double* pts_mm /* [off[n],2] or NULL */, int64_t n, const orip_gcode_map* map,
+                             const int32_t* rect /* [4]: x0, y0, x1, y1 */, int64_t* n_out, int64_t* total_out,
+                             int64_t* stats /* [6]: segments, inside, cut, outside, paths_out, points_out */);
 /* order_paths_nearest (:151-172) from (0, 0): order_out[k] = index of the k-th path to draw -- the remaining path whose FIRST point has the smallest
  * L1 distance from the cursor, the lowest index on ties; the cursor moves to that path's LAST point; paths are never reversed.  Exact for every input.
  * ends: (first x, first y, last x, last y) per path, coordinates 0..2^30, or NULL for the resident step polylines (n must then be their count). */

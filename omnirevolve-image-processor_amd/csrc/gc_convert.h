@@ -1,0 +1,21 @@
+// csrc/gc_convert.h -- the arithmetic of mm_to_steps (gcode2stream.py :79-110) up to the rounding, stated once for the two conversions that must agree in
+// every bit: orip_gcode_to_steps (gcode.hip), which then clamps to the sheet, and orip_gcode_to_steps_clip (gcode_clip.hip), which cuts there instead.
+#pragma once
+#include "orip_ctx.h"
+
+// (v * scale + offset) * steps_per_mm in IEEE double, the three operations kept apart, (H - 1) - y under invert_y, round half to even (Python's round());
+// false when a coordinate is not finite afterwards.  Nothing is clamped and nothing is cast here.
+__device__ __forceinline__ bool gc_round_mm(const orip_gcode_map& g, double xm, double ym, double& xf, double& yf) {
+    xf = __dmul_rn(__dadd_rn(__dmul_rn(xm, g.scale_x), g.offset_x_mm), g.steps_per_mm);
+    yf = __dmul_rn(__dadd_rn(__dmul_rn(ym, g.scale_y), g.offset_y_mm), g.steps_per_mm);
+    if (g.invert_y) yf = __dsub_rn((double)(g.H - 1), yf);
+    xf = rint(xf); yf = rint(yf);
+    return isfinite(xf) && isfinite(yf);
+}
+
+// last p with off[p] <= i (paths without points are skipped by the search)
+__device__ __forceinline__ int64_t gc_path_of(const long long* __restrict__ off, int64_t n, int64_t i) {
+    int64_t lo = 0, hi = n;
+    while (hi - lo > 1) { const int64_t mid = (lo + hi) >> 1; if (off[mid] <= i) lo = mid; else hi = mid; }
+    return lo;
+}

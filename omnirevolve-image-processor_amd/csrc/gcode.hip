@@ -36,6 +36,7 @@
 //    byte of an odd piece holds one), or zero; a second kernel drops the service bytes (the end byte among them) in.  The direction codes are the resident
 //    result of orip_stream_codes and never leave the device.
 #include "orip_ctx.h"
+#include "gc_convert.h"
 #include <rocprim/rocprim.hpp>
 #include <climits>
 
@@ -45,24 +46,14 @@ constexpr int GC_BIG = 64;                       // a cell with more entries tha
 
 // ------------------------------------------------------------------------------------------------ 1. paths to steps
 __device__ __forceinline__ bool gc_step(const orip_gcode_map& g, double xm, double ym, int2& o) {
-    double xf = __dmul_rn(__dadd_rn(__dmul_rn(xm, g.scale_x), g.offset_x_mm), g.steps_per_mm);
-    double yf = __dmul_rn(__dadd_rn(__dmul_rn(ym, g.scale_y), g.offset_y_mm), g.steps_per_mm);
-    if (g.invert_y) yf = __dsub_rn((double)(g.H - 1), yf);
-    xf = rint(xf); yf = rint(yf);                                     // Python round(): half to even
+    double xf, yf;
     o = make_int2(0, 0);
-    if (!(isfinite(xf) && isfinite(yf))) return false;
+    if (!gc_round_mm(g, xm, ym, xf, yf)) return false;                // gc_convert.h: the arithmetic and Python's round(), shared with gcode_clip.hip
     const double xmax = (double)(g.W - 1), ymax = (double)(g.H - 1);
     xf = xf < 0.0 ? 0.0 : (xf > xmax ? xmax : xf);
     yf = yf < 0.0 ? 0.0 : (yf > ymax ? ymax : yf);
     o = make_int2((int)xf, (int)yf);
     return true;
-}
-
-// last p with off[p] <= i (paths without points are skipped by the search)
-__device__ __forceinline__ int64_t gc_path_of(const long long* __restrict__ off, int64_t n, int64_t i) {
-    int64_t lo = 0, hi = n;
-    while (hi - lo > 1) { const int64_t mid = (lo + hi) >> 1; if (off[mid] <= i) lo = mid; else hi = mid; }
-    return lo;
 }
 
 __global__ __launch_bounds__(256) void k_gc_points(const long long* __restrict__ off, int64_t n, const double2* __restrict__ mm, int64_t total, orip_gcode_map g,

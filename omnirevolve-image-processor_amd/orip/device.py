@@ -339,6 +339,29 @@ class Device:
         self._ck(self.L.orip_gcode_steps_fetch(self.h, _p(off_s), _p(pts_s) if fetch_points else None))
         return off_s, pts_s[:tot.value]
 
+    def gcode_to_steps_clip(self, off: np.ndarray | None, pts_mm: np.ndarray | None, map: dict, rect, n: int | None = None) -> Tuple[np.ndarray, np.ndarray, dict]:
+        """--clip (include/orip.h: orip_gcode_to_steps_clip): gcode_to_steps with the strokes cut at rect = (x0, y0, x1, y1) in steps instead of clamped to
+        the sheet; the strokes are left resident as gcode_to_steps leaves its polylines.  off = pts_mm = None: the n fitted paths on the device.
+        -> (off int64, pts int32 [total', 2], {"segments", "inside", "cut", "outside", "paths_out", "points_out"})"""
+        o = p = None
+        if off is not None or pts_mm is not None:
+            o = np.ascontiguousarray(off, np.int64).reshape(-1)
+            p = np.ascontiguousarray(pts_mm, np.float64).reshape(-1, 2)
+            n = max(len(o) - 1, 0)
+            if n and int(o[-1]) != len(p):
+                raise ValueError(f"offsets end at {int(o[-1])}, {len(p)} points given")
+        r = np.asarray(rect, np.int64).reshape(-1)
+        if len(r) != 4 or (np.abs(r) > 1 << 30).any():
+            raise OripError(f"clip rectangle {tuple(r.tolist())}: four step coordinates")
+        r = np.ascontiguousarray(r, np.int32)
+        m = _l.GcodeMap(**{k: map[k] for k, _ in _l.GcodeMap._fields_})
+        n_out, tot = C.c_int64(0), C.c_int64(0)
+        st = np.zeros(len(_l.CLIP_STATS), np.int64)
+        self._ck(self.L.orip_gcode_to_steps_clip(self.h, _p(o) if o is not None and n else None, _p(p) if p is not None and len(p) else None, int(n), C.byref(m), _p(r),
+                                                 C.byref(n_out), C.byref(tot), _p(st)))
+        off_s, pts_s = self.gcode_steps_fetch(n_out.value, tot.value)
+        return off_s, pts_s, {k: int(v) for k, v in zip(_l.CLIP_STATS, st)}
+
     # ---- svg2stream: flatten, bounding box, fit (include/orip.h; csrc/svg.hip)
     def svg_flatten(self, table, tol: float) -> int:
         """segments of an orip.svg.SegmentTable (mats: its raw matrices) -> resident polylines in raw units; returns the number of points"""

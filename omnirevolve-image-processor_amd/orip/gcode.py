@@ -25,7 +25,14 @@ meet nothing is joined.  Without the option no device call is added and every by
 stream compiler counts them, by steepest descent over two kinds of move inside a pen's group: a run of strokes drawn in reverse order and direction (2-opt,
 only with --allow-reverse) and a block of one to three strokes put elsewhere (or-opt).  One move per round, the best of all, ties by a fixed order; at most
 --improve-rounds rounds per group (default 2 m + 64 for m strokes); groups of more than 65 536 strokes are left as they are (orip_gcode_improve;
-include/orip.h states the rule).  It runs after the order and, with --merge-paths, on the merged strokes.  Without the option no device call is added."""
+include/orip.h states the rule).  It runs after the order and, with --merge-paths, on the merged strokes.  Without the option no device call is added.
+
+--clip (ours as well): the reference clamps every point to the sheet (mm_to_steps / clamp_xy), so whatever leaves the sheet is drawn along the edge of the
+paper, and a segment with one end outside changes its slope.  With --clip the strokes are cut where they cross the rectangle [m, W - 1 - m] x [m, H - 1 - m]
+in steps, m = --clip-margin-mm in steps (default 0: the sheet); what lies outside is not drawn and the pen is lifted there (orip_gcode_to_steps_clip, which
+takes the place of orip_gcode_to_steps; include/orip.h states the rule, exact in integers on the step grid).  A path that leaves and comes back becomes
+several strokes of the same input path, so pens, merge, order and improve work on the cut strokes unchanged.  Without the option no device call is added
+and every byte is what it was."""
 from __future__ import annotations
 
 import argparse
@@ -77,6 +84,8 @@ class GcodeOptions:
     merge_paths: bool = False           # strokes of one pen that meet end to end are drawn as one
     improve_order: bool = False         # 2-opt / or-opt on the order, per pen group
     improve_rounds: Optional[int] = None    # rounds per group at most (None: 2 m + 64 for a group of m strokes); only with improve_order
+    clip: bool = False                  # strokes are cut at the sheet's edge (less the margin) instead of clamped to it
+    clip_margin_mm: Optional[float] = None  # the clip rectangle lies this far inside the sheet (None: 0); only with clip
 
 
 # ------------------------------------------------------------------ parse (:113-142, :177-300)
@@ -266,7 +275,8 @@ def plan_pens(off: np.ndarray, pts: np.ndarray, path_pen: np.ndarray, head: Sequ
 def build_stream_from_gcode(text_or_paths, opts: Optional[GcodeOptions] = None, device=None, *, steps_fn: Optional[Callable] = None,
                             order_fn: Optional[Callable] = None, codes_fn: Optional[Callable] = None, pack_fn: Optional[Callable] = None,
                             timings: Optional[dict] = None, pens: Optional[np.ndarray] = None, order_pens_fn: Optional[Callable] = None,
-                            source_fn: Optional[Callable] = None, merge_fn: Optional[Callable] = None, improve_fn: Optional[Callable] = None) -> Tuple[bytes, dict]:
+                            source_fn: Optional[Callable] = None, merge_fn: Optional[Callable] = None, improve_fn: Optional[Callable] = None,
+                            clip_fn: Optional[Callable] = None) -> Tuple[bytes, dict]:
     """The stream of a G-code text (str / bytes) or of paths in mm given as (off, pts_mm); opts as parsed, --speed-scale not yet applied.
     Device steps, each None = the GPU (orip.device.Device; there is no CPU path in the product):
       steps_fn(off, pts_mm, map: dict) -> (off int64, pts int32 [total, 2])      orip_gcode_to_steps
@@ -281,6 +291,9 @@ def build_stream_from_gcode(text_or_paths, opts: Optional[GcodeOptions] = None, 
     and, only with --improve-order (after the order, before the paths are gathered; without pens: one group, no stroke reversed):
       improve_fn(ends, group int32 [n], n_groups, order, rev, reverse, max_rounds) -> (order, rev, stats)       orip_gcode_improve
     info["improve"] then holds travel_before, travel_after (pen-up steps of the whole plot), rounds, converged_groups and skipped_groups.
+    and, only with --clip, in the place of steps_fn (source_fn keeps its meaning: the input path of every stroke, now with repeats):
+      clip_fn(off, pts_mm, map: dict, rect: (x0, y0, x1, y1)) -> (off, pts, stats)                              orip_gcode_to_steps_clip
+    info["clip"] then holds rect and segments, inside, cut, outside, paths_out and points_out.
     pens: one pen per input path, 0..7, or -1 for --color-index (a text's T words under --tool-pens when None).  info["pens"] then counts the paths per
     pen, those that took --color-index ("unmatched") and the strokes drawn backwards ("reversed").
     Returns (bytes, counts)."""
@@ -289,6 +302,7 @@ def build_stream_from_gcode(text_or_paths, opts: Optional[GcodeOptions] = None, 
     W, H = target_size(o)
     sc = stream_config(o)
     check_improve_options(o)
+    rect = clip_rect(o)
     tm = timings if timings is not None else {}
     t0 = time.perf_counter()
 
@@ -317,23 +331,31 @@ def build_stream_from_gcode(text_or_paths, opts: Optional[GcodeOptions] = None, 
         return EMPTY_STREAM, dict(info, bytes=len(EMPTY_STREAM))
     if not (1 <= W <= MAX_TARGET_STEPS and 1 <= H <= MAX_TARGET_STEPS):
         raise ValueError(f"target size {W} x {H} steps: each side must be in 1..2^30 (step coordinates are int32 on the device)")
-    if steps_fn is None or order_fn is None or (grouped and (order_pens_fn is None or source_fn is None)) or (o.merge_paths and merge_fn is None) or \
+    convert_fn = steps_fn if rect is None else clip_fn
+    if convert_fn is None or order_fn is None or (grouped and (order_pens_fn is None or source_fn is None)) or (o.merge_paths and merge_fn is None) or \
             (o.improve_order and improve_fn is None):
         if device is None:
             from .stages import device as _default_device
             device = _default_device()
         if merge_fn is None:                                              # the polylines this device's own conversion left resident are merged where they are
-            resident = steps_fn is None
+            resident = convert_fn is None
             merge_fn = lambda off, pts, group, n_groups, reverse: (device.gcode_merge(None, None, group, n_groups, reverse, n=len(off) - 1) if resident else
                                                                    device.gcode_merge(off, pts, group, n_groups, reverse))
         steps_fn = steps_fn or device.gcode_to_steps
+        clip_fn = clip_fn or device.gcode_to_steps_clip
         order_fn = order_fn or device.gcode_order
         order_pens_fn = order_pens_fn or (lambda ends, group, n_groups, reverse: device.gcode_order_pens(ends, group, n_groups, reverse))
         source_fn = source_fn or device.gcode_steps_source
         improve_fn = improve_fn or (lambda ends, group, n_groups, order, rev, reverse, max_rounds: device.gcode_improve(ends, group, n_groups, order, rev, reverse,
                                                                                                                    max_rounds=max_rounds))
-    off, pts = steps_fn(off_mm, pts_mm, dict(scale_x=o.scale_x, scale_y=o.scale_y, offset_x_mm=o.offset_x_mm, offset_y_mm=o.offset_y_mm, steps_per_mm=o.steps_per_mm,
-                                             W=W, H=H, invert_y=int(bool(o.invert_y))))
+    m = dict(scale_x=o.scale_x, scale_y=o.scale_y, offset_x_mm=o.offset_x_mm, offset_y_mm=o.offset_y_mm, steps_per_mm=o.steps_per_mm, W=W, H=H, invert_y=int(bool(o.invert_y)))
+    if rect is None:
+        off, pts = steps_fn(off_mm, pts_mm, m)
+    else:
+        off, pts, cst = clip_fn(off_mm, pts_mm, m, rect)
+        info["clip"] = dict({"rect": tuple(int(v) for v in rect)}, **{k: int(cst[k]) for k in CLIP_STATS})
+        if info["clip"]["inside"] + info["clip"]["cut"] + info["clip"]["outside"] != info["clip"]["segments"] or info["clip"]["paths_out"] != len(off) - 1:
+            raise RuntimeError("the clip's counts do not add up")
     off = np.asarray(off, np.int64); pts = np.asarray(pts, np.int32).reshape(-1, 2)
     lap("to_steps")
     n = len(off) - 1
@@ -426,6 +448,31 @@ def build_stream_from_gcode(text_or_paths, opts: Optional[GcodeOptions] = None, 
 
 
 IMPROVE_STATS = ("travel_before", "travel_after", "rounds", "converged_groups", "skipped_groups")
+CLIP_STATS = ("segments", "inside", "cut", "outside", "paths_out", "points_out")
+
+
+def clip_rect(o) -> Optional[Tuple[int, int, int, int]]:
+    """None without --clip, else the clip rectangle (x0, y0, x1, y1) in steps: the sheet of target_size(o) less --clip-margin-mm on every side.  The margin
+    belongs to --clip, is not negative and leaves a point at least."""
+    if not o.clip:
+        if o.clip_margin_mm is not None:
+            raise ValueError("--clip-margin-mm needs --clip")
+        return None
+    W, H = target_size(o)
+    margin = 0.0 if o.clip_margin_mm is None else float(o.clip_margin_mm)
+    if not (margin >= 0.0) or margin == float("inf"):
+        raise ValueError("--clip-margin-mm must be a number and not negative")
+    m = margin * float(o.steps_per_mm)
+    m = int(round(m)) if m < float(1 << 31) else 1 << 31
+    if 2 * m > min(W, H) - 1:
+        raise ValueError(f"--clip-margin-mm {margin:g} is {m} steps: nothing is left of a sheet of {W} x {H} steps")
+    return m, m, W - 1 - m, H - 1 - m
+
+
+def clip_line(tag: str, c: dict) -> str:
+    x0, y0, x1, y1 = c["rect"]
+    return (f"[{tag}] clip: {c['segments']} segments: {c['inside']} inside, {c['cut']} cut, {c['outside']} outside [{x0}, {x1}] x [{y0}, {y1}] steps -> "
+            f"{c['paths_out']} strokes, {c['points_out']} points")
 
 
 def check_improve_options(o) -> None:
@@ -479,6 +526,8 @@ def build_argparser() -> argparse.ArgumentParser:
     ap.add_argument("--merge-paths", action="store_true", help="draw strokes of one pen that meet end to end on the step grid as one stroke (no tolerance; where three or more ends meet, none are joined)")
     ap.add_argument("--improve-order", action="store_true", help="after the greedy order, lower the pen-up travel by 2-opt (with --allow-reverse) and or-opt moves, one per round, pen by pen")
     ap.add_argument("--improve-rounds", type=int, default=None, help="rounds per pen at most (default: 2 m + 64 for m strokes); needs --improve-order")
+    ap.add_argument("--clip", action="store_true", help="cut the strokes at the edge of the sheet and lift the pen outside it, instead of clamping every point onto the edge")
+    ap.add_argument("--clip-margin-mm", type=float, default=None, help="cut this far inside the edge of the sheet (default: 0); needs --clip")
     return ap
 
 
@@ -491,11 +540,14 @@ def main(argv: Optional[Sequence[str]] = None, **device_steps) -> None:
     opts = options_from_args(a)
     apply_speed_scale(GcodeOptions(speed_scale=opts.speed_scale))        # a bad scale ends the run before the file is read, as in the reference
     check_improve_options(opts)
+    clip_rect(opts)
     text = Path(a.input).read_bytes()
     data, info = build_stream_from_gcode(text, opts, **device_steps)
     Path(a.output).write_bytes(data)
     print(f"[gcode] {a.input}: {info['paths_mm']} pen-down paths, {info['pen_down_moves']} pen-down moves")
     print(f"[gcode] {info['paths']} paths in step space, {info['steps']} steps, target {info['target'][0]} x {info['target'][1]} steps")
+    if "clip" in info:
+        print(clip_line("gcode", info["clip"]))
     if "pens" in info:
         print("[gcode] pens: " + ", ".join(f"{p}: {k} paths" for p, k in enumerate(info["pens"]["paths"]) if k) + f"; {info['pens']['reversed']} strokes reversed")
     if "merge" in info:

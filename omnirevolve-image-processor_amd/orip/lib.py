@@ -74,6 +74,7 @@ SIGNATURES = {
     "orip_stream_preview": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp]), "orip_stream_preview_fetch": (_i32, [_vp, _vp]),
     "orip_gcode_to_steps": (_i32, [_vp, _vp, _vp, _i64, _P(GcodeMap), _P(_i64), _P(_i64)]), "orip_gcode_steps_fetch": (_i32, [_vp, _vp, _vp]),
     "orip_gcode_order": (_i32, [_vp, _vp, _i64, _vp]), "orip_gcode_steps_source_fetch": (_i32, [_vp, _vp]),
+    "orip_gcode_to_steps_clip": (_i32, [_vp, _vp, _vp, _i64, _P(GcodeMap), _vp, _P(_i64), _P(_i64), _vp]),
     "orip_gcode_order_pens": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp]),
     "orip_gcode_merge": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp]), "orip_gcode_merge_fetch": (_i32, [_vp, _vp, _vp, _vp]),
     "orip_gcode_improve": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _i64, _vp, _vp, _vp]),
@@ -88,6 +89,7 @@ COMM_ID_BYTES = 128
 HATCH_SERPENTINE, HATCH_HORIZONTAL, HATCH_VERTICAL = 1, 2, 4
 ORDER_REVERSE, ORDER_MAX_GROUPS = 1, 64
 MERGE_REVERSE = 1
+CLIP_STATS = ("segments", "inside", "cut", "outside", "paths_out", "points_out")
 IMPROVE_MAX_PATHS, IMPROVE_ROUNDS_AUTO = 65536, (1 << 63) - 1
 
 _lib = None

@@ -34,6 +34,10 @@ without a stated stroke takes --color-index; a hatch line takes the pen of its e
 What is drawn does not change (an element with stroke="none" is still drawn, as before: stated deviation).  The pens travel through the hatch
 (orip_svg_hatch_groups_fetch) and the conversion to steps (orip_gcode_steps_source_fetch) into orip/gcode.py, which draws pen after pen.
 
+--clip (off unless given; ours, orip/gcode.py states it): a drawing that --scale or a small page pushes over the edge of the sheet is cut there instead
+of being clamped onto the edge.  The fitted paths, hatch lines included, are cut where they lie on the device (orip_gcode_to_steps_clip without pointers);
+the pens of the cut strokes still come through the sources, and the G-code file is not changed.
+
 The device steps are injectable, as in orip/gcode.py, so that this host logic can be tested without a GPU; the product has no CPU path."""
 from __future__ import annotations
 
@@ -544,6 +548,8 @@ class SvgOptions:
     merge_paths: bool = False                           # strokes of one pen that meet end to end on the step grid are drawn as one (orip.gcode)
     improve_order: bool = False                         # 2-opt / or-opt on the order, per pen group (orip.gcode)
     improve_rounds: Optional[int] = None                # rounds per group at most; None: 2 m + 64
+    clip: bool = False                                  # strokes are cut at the sheet's edge instead of clamped to it (orip.gcode)
+    clip_margin_mm: Optional[float] = None              # the clip rectangle lies this far inside the sheet; None: 0
 
 
 HATCH_DIRECTIONS = {"horizontal": HATCH_HORIZONTAL, "vertical": HATCH_VERTICAL, "cross": HATCH_HORIZONTAL | HATCH_VERTICAL}
@@ -642,7 +648,7 @@ def gcode_options(o: SvgOptions) -> GC.GcodeOptions:
     return GC.GcodeOptions(steps_per_mm=o.steps_per_mm, invert_y=o.invert_y, color_index=o.color_index, speed_scale=o.speed_scale, scale_x=1.0, scale_y=1.0,
                            offset_x_mm=0.0, offset_y_mm=0.0, target_width_steps=W, target_height_steps=H, no_reorder=bool(o.no_reorder),
                            allow_reverse=bool(o.allow_reverse), pen_order=o.pen_order, merge_paths=bool(o.merge_paths),
-                           improve_order=bool(o.improve_order), improve_rounds=o.improve_rounds)
+                           improve_order=bool(o.improve_order), improve_rounds=o.improve_rounds, clip=bool(o.clip), clip_margin_mm=o.clip_margin_mm)
 
 
 def gcode_text(off, pts, passes: int = 1, pens=None) -> str:
@@ -676,6 +682,7 @@ class _Resident:
     def fit(self, paths, sx, sy, ox, oy): self.dev.svg_fit(sx, sy, ox, oy); return paths
     def fetch(self, paths, with_points=True): return self.dev.svg_paths(paths["n"], with_points)
     def steps(self, paths, m): return self.dev.gcode_to_steps(None, None, m, n=paths["n"])
+    def clip(self, paths, m, rect): return self.dev.gcode_to_steps_clip(None, None, m, rect, n=paths["n"])
 
     def hatch(self, paths, fill_group, prm):
         st = self.dev.svg_hatch(fill_group, prm["steps_per_mm"], prm["spacing"], prm["inset"], prm["flags"])
@@ -753,7 +760,8 @@ def build_stream_from_svg(text: Union[str, bytes, SegmentTable], opts: Optional[
                           bbox_fn: Optional[Callable] = None, fit_fn: Optional[Callable] = None, hatch_fn: Optional[Callable] = None, fetch_fn: Optional[Callable] = None,
                           steps_fn: Optional[Callable] = None, order_fn: Optional[Callable] = None, codes_fn: Optional[Callable] = None, pack_fn: Optional[Callable] = None, timings: Optional[dict] = None,
                           want_paths: bool = False, hatch_groups_fn: Optional[Callable] = None, source_fn: Optional[Callable] = None,
-                          order_pens_fn: Optional[Callable] = None, merge_fn: Optional[Callable] = None, improve_fn: Optional[Callable] = None) -> Tuple[bytes, dict]:
+                          order_pens_fn: Optional[Callable] = None, merge_fn: Optional[Callable] = None, improve_fn: Optional[Callable] = None,
+                          clip_fn: Optional[Callable] = None) -> Tuple[bytes, dict]:
     """The stream of an SVG text (or of a parsed SegmentTable).  Device steps, each None = the GPU (there is no CPU path in the product):
       flatten_fn(table, tol_raw) -> paths          orip_svg_flatten      (`paths` is whatever the other steps take: on the GPU a count, the points stay there)
       bbox_fn(paths) -> (min x, min y, max x, max y)   orip_svg_bbox
@@ -769,6 +777,8 @@ def build_stream_from_svg(text: Union[str, bytes, SegmentTable], opts: Optional[
       merge_fn                                     as in orip.gcode.build_stream_from_gcode (hatch lines go through it like any path; serpentine lines do not touch)
     and, only with --improve-order:
       improve_fn                                   as in orip.gcode.build_stream_from_gcode
+    and, only with --clip, in the place of steps_fn (hatch lines are cut like any path, and their pens still come through the sources):
+      clip_fn(paths, map, rect) -> (off, pts int32, stats)   orip_gcode_to_steps_clip without pointers
     With --pen-colors, info["path_pens"] is the pen of every fitted path (hatch lines included, --color-index where no stroke is stated).
     Returns (bytes, info)."""
     import time
@@ -782,6 +792,7 @@ def build_stream_from_svg(text: Union[str, bytes, SegmentTable], opts: Optional[
     table = text if isinstance(text, SegmentTable) else parse_svg(text, o.hatch_fill)
     tm["parse_svg"] = tm.get("parse_svg", 0.0) + (time.perf_counter() - t0)
     go = gcode_options(o)
+    GC.clip_rect(go)
     GC.apply_speed_scale(GC.GcodeOptions(speed_scale=go.speed_scale))
     tolerance_mm(o)
     info = {"segments": table.n_seg, "subpaths": table.n_sub, "canvas_height": table.canvas_height}
@@ -791,7 +802,8 @@ def build_stream_from_svg(text: Union[str, bytes, SegmentTable], opts: Optional[
             info["fitted_paths"] = (np.zeros(1, np.int64), np.zeros((0, 2)))
         return data, dict(ginfo, **info)
     pens_on = o.pen_colors is not None
-    if any(f is None for f in (flatten_fn, bbox_fn, fit_fn, fetch_fn, steps_fn, order_fn, codes_fn, pack_fn)) or (hp and hatch_fn is None) or \
+    convert_fn = clip_fn if o.clip else steps_fn
+    if any(f is None for f in (flatten_fn, bbox_fn, fit_fn, fetch_fn, convert_fn, order_fn, codes_fn, pack_fn)) or (hp and hatch_fn is None) or \
             ((pens_on or o.allow_reverse) and (source_fn is None or order_pens_fn is None)) or (pens_on and hp and hatch_groups_fn is None) or \
             (o.merge_paths and merge_fn is None) or (o.improve_order and improve_fn is None):
         if device is None:
@@ -799,8 +811,9 @@ def build_stream_from_svg(text: Union[str, bytes, SegmentTable], opts: Optional[
             device = _default_device()
         R = _Resident(device)
         if merge_fn is None:                                # where the conversion ran on this device its polylines are merged in place, else they are sent
-            merge_fn = R.merge if steps_fn is None else device.gcode_merge
+            merge_fn = R.merge if convert_fn is None else device.gcode_merge
         flatten_fn = flatten_fn or R.flatten; bbox_fn = bbox_fn or R.bbox; fit_fn = fit_fn or R.fit; fetch_fn = fetch_fn or R.fetch; steps_fn = steps_fn or R.steps
+        clip_fn = clip_fn or R.clip
         hatch_fn = hatch_fn or R.hatch
         order_fn = order_fn or device.gcode_order
         hatch_groups_fn = hatch_groups_fn or R.hatch_groups; source_fn = source_fn or R.source; order_pens_fn = order_pens_fn or R.order_pens
@@ -819,7 +832,7 @@ def build_stream_from_svg(text: Union[str, bytes, SegmentTable], opts: Optional[
     tm["fetch_paths"] = tm.get("fetch_paths", 0.0) + (time.perf_counter() - t0)
     data, ginfo = GC.build_stream_from_gcode((off_mm, np.zeros((int(off_mm[-1]), 2))), go, device, steps_fn=lambda _off, _pts, m: steps_fn(paths, m), order_fn=order_fn,
                                              codes_fn=codes_fn, pack_fn=pack_fn, timings=tm, pens=pens, order_pens_fn=order_pens_fn, source_fn=source_fn, merge_fn=merge_fn,
-                                             improve_fn=improve_fn)
+                                             improve_fn=improve_fn, clip_fn=lambda _off, _pts, m, rect: clip_fn(paths, m, rect))
     return data, dict(ginfo, **info)
 
 
@@ -876,6 +889,9 @@ def build_stream_argparser() -> argparse.ArgumentParser:
     ap.add_argument("--improve-order", action="store_true", help="after the greedy order, lower the pen-up travel by 2-opt (with --allow-reverse) and or-opt moves, one per round, pen by pen; "
                                                                  "the G-code file is not changed")
     ap.add_argument("--improve-rounds", type=int, default=None, help="rounds per pen at most (default: 2 m + 64 for m strokes); needs --improve-order")
+    ap.add_argument("--clip", action="store_true", help="cut the strokes at the edge of the sheet and lift the pen outside it, instead of clamping every point onto the edge; "
+                                                        "the G-code file is not changed")
+    ap.add_argument("--clip-margin-mm", type=float, default=None, help="cut this far inside the edge of the sheet (default: 0); needs --clip")
     ap.add_argument("--no-preview", action="store_true", help="do not render <svg stem>_stream_preview.png")
     ap.add_argument("--preview-render-width", type=int, default=d.preview_render_width)
     ap.add_argument("--preview-render-height", type=int, default=d.preview_render_height)
@@ -943,6 +959,8 @@ def main_stream(argv: Optional[Sequence[str]] = None, **device_steps) -> None:
     print(f"[svg] {a.input}: {info['segments']} segments in {info['subpaths']} subpaths -> {len(pts)} points")
     if "hatch" in info:
         print("[svg] hatch: {groups} fill groups, {lines} lines, {crossings} crossings -> {segments} segments".format(**info["hatch"]))
+    if "clip" in info:
+        print(GC.clip_line("svg", info["clip"]))
     if "pens" in info:
         print("[svg] pens: " + ", ".join(f"{p}: {k} paths" for p, k in enumerate(info["pens"]["paths"]) if k) +
               f"; {info['pens']['unmatched']} without a stroke colour, {info['pens']['reversed']} strokes reversed")

@@ -1,7 +1,10 @@
-// csrc/gc_convert.h -- the arithmetic of mm_to_steps (gcode2stream.py :79-110) up to the rounding, stated once for the two conversions that must agree in
-// every bit: orip_gcode_to_steps (gcode.hip), which then clamps to the sheet, and orip_gcode_to_steps_clip (gcode_clip.hip), which cuts there instead.
+// csrc/gc_convert.h -- what the gcode units share.  The arithmetic of mm_to_steps (gcode2stream.py :79-110) up to the rounding, stated once for the two
+// conversions that must agree in every bit: orip_gcode_to_steps (gcode.hip), which then clamps to the sheet, and orip_gcode_to_steps_clip (gcode_clip.hip),
+// which cuts there instead; the path of a point; the check of an offsets array.
 #pragma once
 #include "orip_ctx.h"
+
+constexpr int GC_COORD_MAX = 1 << 30;            // step coordinates are int32 in [0, 2^30]
 
 // (v * scale + offset) * steps_per_mm in IEEE double, the three operations kept apart, (H - 1) - y under invert_y, round half to even (Python's round());
 // false when a coordinate is not finite afterwards.  Nothing is clamped and nothing is cast here.
@@ -18,4 +21,11 @@ __device__ __forceinline__ int64_t gc_path_of(const long long* __restrict__ off,
     int64_t lo = 0, hi = n;
     while (hi - lo > 1) { const int64_t mid = (lo + hi) >> 1; if (off[mid] <= i) lo = mid; else hi = mid; }
     return lo;
+}
+
+// the offsets of n explicit paths: off[0] == 0, nowhere decreasing; the message names the entry point `who`
+static inline int gc_check_offsets(orip_ctx* c, const char* who, const int64_t* off, int64_t n) {
+    if (off[0] != 0) ORIP_FAIL_AS(c, who, "offsets must start at 0");
+    for (int64_t p = 0; p < n; p++) if (off[p + 1] < off[p]) ORIP_FAIL_AS(c, who, "offsets must not decrease (path %lld)", (long long)p);
+    return 0;
 }

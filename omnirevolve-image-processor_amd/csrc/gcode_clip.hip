@@ -181,10 +181,7 @@ extern "C" int orip_gcode_to_steps_clip(orip_ctx* c, const int64_t* off, const d
         ORIP_FAIL(c, "clip rectangle [%d, %d] x [%d, %d]: must be 0 <= x0 <= x1 <= %d, 0 <= y0 <= y1 <= %d", rect[0], rect[2], rect[1], rect[3], map->W - 1, map->H - 1);
     if (n >= INT32_MAX / 2) ORIP_FAIL(c, "%lld paths: at most 2^30", (long long)n);                  // before off[n] is looked at
     const int64_t total = resident ? c->sv_total : n > 0 ? off[n] : 0;
-    if (!resident) {
-        if (n > 0 && off[0] != 0) ORIP_FAIL(c, "offsets must start at 0");
-        for (int64_t p = 0; p < n; p++) if (off[p + 1] < off[p]) ORIP_FAIL(c, "offsets must not decrease (path %lld)", (long long)p);
-    }
+    if (!resident && n > 0) ORIP_TRY(gc_check_offsets(c, __func__, off, n));
     if (total >= (int64_t)1 << 29) ORIP_FAIL(c, "%lld points: fewer than 2^29 (a cut can double the points)", (long long)total);
     if (total > 0 && !pts_mm && !resident) ORIP_FAIL(c, "bad arguments");
     // checked: from here on the resident step polylines are this call's

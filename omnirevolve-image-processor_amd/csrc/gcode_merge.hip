@@ -34,6 +34,7 @@
 // = their exclusive scans; place int2[n] = (first output point, 1 reversed | 2 first point dropped); MgCounters.
 // Resident: the merged polylines in c->gc_off / c->gc_pts (swapped with c->mg_off / c->mg_pts), member_off / member / rev in c->mg_res until the next merge.
 #include "orip_ctx.h"
+#include "gc_convert.h"
 #include <rocprim/rocprim.hpp>
 
 namespace {
@@ -45,12 +46,6 @@ __device__ __forceinline__ unsigned mg_hash(const int4 e) {
     unsigned long long k = (((unsigned long long)(unsigned)e.x << 32) | (unsigned)e.y) * 0x9E3779B97F4A7C15ull + (unsigned long long)(unsigned)e.z * 0xC2B2AE3D27D4EB4Full;
     k ^= k >> 32; k *= 0xD6E8FEB86659FD93ull; k ^= k >> 32;
     return (unsigned)k;
-}
-// last p with off[p] <= i (every path has points, so this is the path of point i)
-__device__ __forceinline__ int mg_path_of(const long long* __restrict__ off, int n, long long i) {
-    int lo = 0, hi = n;
-    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (off[mid] <= i) lo = mid; else hi = mid; }
-    return lo;
 }
 
 // ------------------------------------------------------------------------------------------------ 1. ends -> nodes
@@ -173,7 +168,7 @@ __global__ __launch_bounds__(256) void k_mg_emit(const long long* __restrict__ o
                                                  int2* __restrict__ out) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= total) return;
-    const int p = mg_path_of(off, n, i);
+    const int p = (int)gc_path_of(off, n, i);                                    // every path has points, so this is the path of point i
     const int2 pl = place[p];
     if (pl.x < 0) return;
     long long q = i - off[p];
@@ -196,11 +191,8 @@ extern "C" int orip_gcode_merge(orip_ctx* c, const int64_t* off, const int32_t* 
     if (resident && (!c->gc_ready || n != c->gc_n)) ORIP_FAIL(c, "%lld paths asked for, %lld step polylines resident", (long long)n, (long long)(c->gc_ready ? c->gc_n : -1));
     int64_t total = resident ? c->gc_total : 0;
     if (!resident) {
-        if (off[0] != 0) ORIP_FAIL(c, "offsets must start at 0");
-        for (int64_t p = 0; p < n; p++) {
-            if (off[p + 1] < off[p]) ORIP_FAIL(c, "offsets must not decrease (path %lld)", (long long)p);
-            if (off[p + 1] - off[p] < 2) ORIP_FAIL(c, "path %lld has fewer than two points", (long long)p);
-        }
+        ORIP_TRY(gc_check_offsets(c, __func__, off, n));
+        for (int64_t p = 0; p < n; p++) if (off[p + 1] - off[p] < 2) ORIP_FAIL(c, "path %lld has fewer than two points", (long long)p);
         total = off[n];
         if (total >= (int64_t)1 << 30) ORIP_FAIL(c, "%lld points: fewer than 2^30", (long long)total);
         for (int64_t i = 0; i < 2 * total; i++) if (pts[i] < 0 || pts[i] > MG_COORD_MAX) ORIP_FAIL(c, "point %lld: coordinate %d outside 0..2^30", (long long)(i / 2), pts[i]);

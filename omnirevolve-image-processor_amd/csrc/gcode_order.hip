@@ -1,0 +1,338 @@
+// csrc/gcode_order.hip -- the nearest-neighbour order of the step polylines of svg_to_stream/gcode2stream.py (order_paths_nearest :151-172), as one list
+// (orip_gcode_order) and group by group with reversible strokes (orip_gcode_order_pens).  ONE search serves both: gc_search below.
+//
+// 2. Order.  The reference starts at (0, 0) and takes, again and again, the remaining path whose FIRST point has the smallest L1 distance from the cursor,
+//    the lowest index on ties; the cursor moves to that path's LAST point.  That is a chain of n dependent searches over n points: n^2 / 2 distances.  Here
+//    the first points are bucketed into a grid of square cells (a power of two wide, about two points per cell, 16 bytes per point: x, y, id), in global
+//    memory, where the grid of a 10^6-path plot (16 MB + 8 bytes per cell) stays in L2.  ONE wave walks the chain; its lanes do the search of a step:
+//      * the window starts as the 3 x 3 cells around the cursor's cell and grows by one ring of cells at a time; four lanes share a cell (entries j, j + 4,
+//        ...), so a pass looks at 16 cells; a cell of more than GC_BIG entries is scanned by all 64 lanes instead (thousands of paths that start on
+//        one point are one such cell);
+//      * the key of an entry is (L1 distance << 32) | id, id = 2 * index (+ 1 for a path's last point, 2b), the search takes the minimum: exactly the
+//        reference's `d < best_d` over a list in index order;
+//      * the search stops once the best distance is SMALLER than the distance from the cursor to the nearest window border that still has cells behind
+//        it: every point outside the window is at least that far in one coordinate alone, hence in L1, so it can neither win nor tie.  A border on the
+//        edge of the grid has nothing behind it; with all four there the whole grid has been seen.  A cursor outside the bounding box of the first
+//        points adds its distance from the box in the OTHER coordinate to each border's bound (all first points on one row, the cursor far above it:
+//        without that term every step would scan the whole row);
+//      * the winner leaves its cell (the cell's last live entry takes its place), so a cell only ever holds paths that remain.
+//    Integer arithmetic throughout; coordinates are int32 in [0, 2^30], so an L1 distance fits 32 bits.  The per-step cost is three dependent L2 round trips
+//    (cell headers, entries, the winner's end point and the entry that takes its place) while the window stays at 3 x 3.
+//    Degenerate inputs: all first points equal, or on one row or column, give a grid of one cell, one row or one column -- same code, the big-cell path does
+//    the work; a cursor outside the grid's bounding box is clamped to the nearest cell and the borders behind it count as edges of the grid; n = 0 returns
+//    before any launch.
+//    2b. The same walk group by group, both ends of a path as candidates (orip_gcode_order_pens; the reference's demo sheet: order_paths_nearest :197-216 of
+//    stream_generators/plotter_demo/omnirevolve_plotter_demo.py inside draw_color_group :317-333): one grid per group side by side in the same arrays, the
+//    cursor carried from group to group inside one launch, and a slot table through which a winner's other end leaves its cell without a search.
+//
+// Two kernels around the one search, because the plain order must not pay for the groups (DESIGN 6 "pens": the group descriptor, the cell offset and the
+// removal's range checks cost 6 % of the chain): k_gc_chain has its grid by value and a cell offset of constant 0, k_op_chain reads both per group.  The grid
+// itself is built by the same kernels for both (gc_grids); a null group array there means "everything is group 0".
+#include "orip_ctx.h"
+#include "gc_convert.h"
+#include <rocprim/rocprim.hpp>
+#include <climits>
+
+namespace {
+constexpr int GC_BIG = 64;                       // a cell with more entries than this is scanned by the whole wave
+
+struct GcGrid { int x0, y0, x1, y1, sh, gx, gy; };      // bounding box of the candidate points, log2 of the cell width, cells per side
+__device__ __forceinline__ int gc_cell(const GcGrid& g, int x, int y) { return ((y - g.y0) >> g.sh) * g.gx + ((x - g.x0) >> g.sh); }
+// One grid per group, side by side in the same arrays: group g owns the cells cell0 .. cell0 + gx * gy - 1, and because the entries are laid out by one
+// scan over all cells, its entries are one range too -- a search that stays inside its group's cells cannot see another group's candidate.
+struct OpGroup { GcGrid g; int cell0, paths; };          // box and cells over the group's candidate points; how many paths it holds
+
+// ------------------------------------------------------------------------------------------------ the grid
+__global__ __launch_bounds__(256) void k_gc_ends(const long long* __restrict__ off, const int2* __restrict__ pts, int64_t n, int4* __restrict__ se) {
+    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= n) return;
+    const int2 a = pts[off[p]], b = pts[off[p + 1] - 1];
+    se[p] = make_int4(a.x, a.y, b.x, b.y);
+}
+// candidate t: its id 2i + r (path and end), its point and its group (grp == nullptr: group 0).  Without reversal the first points only (ids 2i), with it both ends
+__device__ __forceinline__ int op_cand(const int4* __restrict__ se, const int* __restrict__ grp, int t, int rev, int2& p, int& g) {
+    const int i = rev ? t >> 1 : t, r = rev ? t & 1 : 0;
+    const int4 e = se[i];
+    p = r ? make_int2(e.z, e.w) : make_int2(e.x, e.y);
+    g = grp ? grp[i] : 0;
+    return 2 * i + r;
+}
+__global__ __launch_bounds__(256) void k_op_bbox(const int4* __restrict__ se, const int* __restrict__ grp, int m, int rev, int* __restrict__ box) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= m) return;
+    int2 p; int g; op_cand(se, grp, t, rev, p, g);
+    int* b = box + 4 * g;
+    atomicMin(&b[0], p.x); atomicMin(&b[1], p.y); atomicMax(&b[2], p.x); atomicMax(&b[3], p.y);
+}
+__global__ __launch_bounds__(256) void k_op_count(const int4* __restrict__ se, const int* __restrict__ grp, int m, int rev, const OpGroup* __restrict__ G, unsigned* __restrict__ cnt) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= m) return;
+    int2 p; int g; op_cand(se, grp, t, rev, p, g);
+    const OpGroup o = G[g];
+    atomicAdd(&cnt[o.cell0 + gc_cell(o.g, p.x, p.y)], 1u);
+}
+__global__ __launch_bounds__(256) void k_op_fill(const int4* __restrict__ se, const int* __restrict__ grp, int m, int rev, const OpGroup* __restrict__ G, const unsigned* __restrict__ start,
+                                                 unsigned* __restrict__ fill, int4* __restrict__ ent, int* __restrict__ slot) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= m) return;
+    int2 p; int g; const int id = op_cand(se, grp, t, rev, p, g);
+    const OpGroup o = G[g];
+    const int c = o.cell0 + gc_cell(o.g, p.x, p.y);
+    const int at = (int)(start[c] + atomicAdd(&fill[c], 1u));
+    ent[at] = make_int4(p.x, p.y, id, 0);
+    if (rev) slot[id] = at;                              // where candidate id sits: how a winner's other end is found without a search
+}
+__global__ __launch_bounds__(256) void k_gc_hdr(const unsigned* __restrict__ start, const unsigned* __restrict__ cnt, int ncell, int2* __restrict__ hdr) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c < ncell) hdr[c] = make_int2((int)start[c], (int)cnt[c]);
+}
+
+// ------------------------------------------------------------------------------------------------ the search of one step
+// what a lane remembers about the best entry it has seen in the current step: its key, slot and cell, and the cell's header when it was read
+struct GcBest { unsigned long long key; int slot, cell, first, count; };
+__device__ __forceinline__ void gc_look(GcBest& b, const int4 e, int slot, int cell, const int2 h, int cx, int cy) {
+    const unsigned d = (unsigned)abs(e.x - cx) + (unsigned)abs(e.y - cy);
+    const unsigned long long key = ((unsigned long long)d << 32) | (unsigned)e.z;
+    if (key < b.key) { b.key = key; b.slot = slot; b.cell = cell; b.first = h.x; b.count = h.y; }
+}
+#define GCU(x) __builtin_amdgcn_readfirstlane((int)(x))
+
+// The nearest live entry to (cx, cy) among the cells cell0 .. cell0 + gx * gy - 1 of grid g, for a block of one wave: the winner's GcBest, the same in every
+// lane (key = ~0ull: nothing found, which cannot happen while the grid holds an entry).  hdr and ent are read only; they change between two searches.
+__device__ __forceinline__ GcBest gc_search(const GcGrid& g, const int cell0, const int cx, const int cy, const int2* hdr, const int4* ent) {
+    __shared__ unsigned long long s_best;
+    const int lane = threadIdx.x, sub = lane & 3, slot16 = lane >> 2;
+    const long long INF = 1ll << 62;
+    const int ccx = min(max(cx - g.x0, 0) >> g.sh, g.gx - 1), ccy = min(max(cy - g.y0, 0) >> g.sh, g.gy - 1);
+    const long long ox = max(max(g.x0 - cx, cx - g.x1), 0), oy = max(max(g.y0 - cy, cy - g.y1), 0);
+    GcBest b; b.key = ~0ull; b.slot = b.cell = b.first = b.count = 0;
+    unsigned long long best = ~0ull;
+    for (int r = 1;; r++) {
+        const int xl = ccx - r, xh = ccx + r, yl = ccy - r, yh = ccy + r;
+        const int cxl = max(xl, 0), cxh = min(xh, g.gx - 1), cyl = max(yl, 0), cyh = min(yh, g.gy - 1);
+        // the cells of this pass: the whole clamped block for r == 1, afterwards the ring's four sides where they lie inside the grid
+        const int w = cxh - cxl + 1;
+        const int iyl = max(yl + 1, 0), iyh = min(yh - 1, g.gy - 1), hcol = max(iyh - iyl + 1, 0);
+        const int n0 = r == 1 ? w * (cyh - cyl + 1) : (yl >= 0 ? w : 0);
+        const int n1 = r == 1 ? 0 : (yh <= g.gy - 1 ? w : 0), n2 = r == 1 ? 0 : (xl >= 0 ? hcol : 0), n3 = r == 1 ? 0 : (xh <= g.gx - 1 ? hcol : 0);
+        const int T = n0 + n1 + n2 + n3;
+        for (int t0 = 0; t0 < T; t0 += 16) {
+            int t = t0 + slot16, cell = -1;
+            int2 h = make_int2(0, 0);
+            if (t < T) {
+                int x, y;
+                if (r == 1) { x = cxl + t % w; y = cyl + t / w; }
+                else if (t < n0) { x = cxl + t; y = yl; }
+                else if ((t -= n0) < n1) { x = cxl + t; y = yh; }
+                else if ((t -= n1) < n2) { x = xl; y = iyl + t; }
+                else { x = xh; y = iyl + (t - n2); }
+                cell = cell0 + y * g.gx + x;
+                h = hdr[cell];
+                if (h.y <= GC_BIG)
+                    for (int j = sub; j < h.y; j += 4) gc_look(b, ent[h.x + j], h.x + j, cell, h, cx, cy);
+            }
+            unsigned long long big = __ballot(cell >= 0 && h.y > GC_BIG && sub == 0);
+            while (big) {                                                  // wave-uniform loop: a crowded cell, all lanes on it
+                const int l = __ffsll((long long)big) - 1;
+                big &= big - 1;
+                const int bc = __shfl(cell, l), bx = __shfl(h.x, l), by = __shfl(h.y, l);
+                for (int j = lane; j < by; j += 64) gc_look(b, ent[bx + j], bx + j, bc, make_int2(bx, by), cx, cy);
+            }
+        }
+        // the wave's minimum through LDS (one wave: the three accesses below happen in program order)
+        if (lane == 0) s_best = ~0ull;
+        __syncthreads();
+        if (b.key != ~0ull) atomicMin(&s_best, b.key);
+        __syncthreads();
+        best = s_best;
+        __syncthreads();
+        // the least distance of a point behind each border that still has cells behind it: the way to the border in that coordinate, plus
+        // the cursor's distance from the bounding box in the other one (every candidate lies inside the box; a group whose points all lie far
+        // from where the previous group ended is this term's case too)
+        long long bd = INF;
+        if (xl > 0) bd = min(bd, (long long)cx - ((long long)g.x0 + ((long long)xl << g.sh)) + 1 + oy);
+        if (yl > 0) bd = min(bd, (long long)cy - ((long long)g.y0 + ((long long)yl << g.sh)) + 1 + ox);
+        if (xh < g.gx - 1) bd = min(bd, (long long)g.x0 + ((long long)(xh + 1) << g.sh) - (long long)cx + oy);
+        if (yh < g.gy - 1) bd = min(bd, (long long)g.y0 + ((long long)(yh + 1) << g.sh) - (long long)cy + ox);
+        if (bd == INF || (long long)(best >> 32) < bd) break;
+    }
+    // the winner's lane hands over where the entry sits
+    const unsigned long long mine = __ballot(b.key == best);
+    const int wl = __ffsll((long long)mine) - 1;
+    GcBest w;
+    w.key = mine ? best : ~0ull;
+    w.slot = GCU(__shfl(b.slot, wl)); w.cell = GCU(__shfl(b.cell, wl)); w.first = GCU(__shfl(b.first, wl)); w.count = GCU(__shfl(b.count, wl));
+    return w;
+}
+
+// ------------------------------------------------------------------------------------------------ 2. one list, first points only
+// hdr and ent change under the chain (lane 0 removes the winner of every step); `se` does not
+__global__ __launch_bounds__(64) void k_gc_chain(const int4* __restrict__ se, int n, int2* hdr, int4* ent, GcGrid g, int* __restrict__ order) {
+    const int lane = threadIdx.x;
+    int cx = 0, cy = 0;
+    for (int step = 0; step < n; step++) {
+        const GcBest w = gc_search(g, 0, cx, cy, hdr, ent);
+        const int id = GCU((unsigned)w.key), win = id >> 1;
+        if (id < 0 || win >= n) { if (lane == 0) order[0] = -1; return; }                    // cannot happen: n - step paths remain somewhere in the grid
+        // the cell's last live entry takes the winner's place
+        const int4 last = ent[w.first + w.count - 1];
+        const int4 e = se[win];
+        if (lane == 0) { ent[w.slot] = last; hdr[w.cell] = make_int2(w.first, w.count - 1); order[step] = win; }
+        __threadfence_block();
+        cx = GCU(e.z); cy = GCU(e.w);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ 2b. order by pen group, strokes reversible
+// The same walk, group after group with the cursor carried over: gc_search on the cells of the current group.  hdr, ent and slot change under the chain;
+// `se` and the groups do not.  With `rev` the winner's other end leaves too: lane 0 does both removals one after the other in program order, so the second
+// one reads the slot table and the cell header as the first one left them (both ends in one cell; the other end being the entry that has just been moved
+// into the winner's place; a closed path, whose forward end wins).
+__global__ __launch_bounds__(64) void k_op_chain(const int4* __restrict__ se, int n, const OpGroup* __restrict__ groups, int n_groups, int rev, int sx, int sy, int ncell, int m,
+                                                 int2* hdr, int4* ent, int* slot, int* __restrict__ order, uint8_t* __restrict__ rev_out) {
+    const int lane = threadIdx.x;
+    int cx = sx, cy = sy, k = 0;
+    for (int gi = 0; gi < n_groups; gi++) {
+        const GcGrid g = groups[gi].g;
+        const int cell0 = groups[gi].cell0, paths = groups[gi].paths;
+        for (int step = 0; step < paths; step++, k++) {
+            const GcBest w = gc_search(g, cell0, cx, cy, hdr, ent);
+            const int id = GCU((unsigned)w.key), win = id >> 1, wr = id & 1;
+            // cannot happen: paths - step paths of the group remain somewhere in its cells.  Every index below is checked before it is used all the same
+            if (id < 0 || win >= n || (wr && !rev)) { if (lane == 0) order[0] = -1; return; }
+            const int4 last = ent[w.first + w.count - 1];
+            const int4 e = se[win];
+            int lost = 0;
+            if (lane == 0) {
+                ent[w.slot] = last; hdr[w.cell] = make_int2(w.first, w.count - 1); order[k] = win; rev_out[k] = (uint8_t)wr;
+                if (rev) {
+                    if ((unsigned)last.z < 2u * (unsigned)n) slot[last.z] = w.slot; else lost = 1;
+                    const int pc = cell0 + gc_cell(g, wr ? e.x : e.z, wr ? e.y : e.w);       // the other end's cell, from its coordinates
+                    if (!lost && pc >= 0 && pc < ncell) {
+                        const int ps = slot[id ^ 1];                                         // read behind the first removal, in this lane's program order
+                        const int2 ph = hdr[pc];
+                        if (ph.y > 0 && ps >= ph.x && ps < ph.x + ph.y && ph.x + ph.y <= m) {
+                            const int4 l2 = ent[ph.x + ph.y - 1];
+                            if ((unsigned)l2.z < 2u * (unsigned)n) { ent[ps] = l2; slot[l2.z] = ps; hdr[pc] = make_int2(ph.x, ph.y - 1); } else lost = 1;
+                        } else lost = 1;
+                    } else lost = 1;
+                }
+            }
+            __threadfence_block();
+            if (__shfl(lost, 0)) { if (lane == 0) order[0] = -1; return; }
+            cx = GCU(wr ? e.x : e.z); cy = GCU(wr ? e.y : e.w);
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ host: ends and grids, the same for both orders
+// square cells, a power of two wide: the smallest for which the grid over box b has at most cand / 2 cells (one cell at least), each side at most 2^15
+GcGrid gc_grid_for(const int* b, int64_t cand) {
+    GcGrid g{b[0], b[1], b[2], b[3], 0, 1, 1};
+    const int64_t wx = (int64_t)b[2] - b[0], wy = (int64_t)b[3] - b[1], want = std::max<int64_t>(1, cand / 2);
+    for (g.sh = 0;; g.sh++) {
+        g.gx = (int)(wx >> g.sh) + 1; g.gy = (int)(wy >> g.sh) + 1;
+        if (g.gx <= (1 << 15) && g.gy <= (1 << 15) && (int64_t)g.gx * g.gy <= want) break;
+    }
+    return g;
+}
+
+struct GcOrder { int4* se; int* order; uint8_t* rv; OpGroup* dG; int2* hdr; int4* ent; int* slot; int ncell; OpGroup hG[ORIP_ORDER_MAX_GROUPS]; };
+// Checks and uploads the ends (NULL: the resident step polylines), boxes every group's candidates, chooses the grids and fills them: everything in front of
+// the chain, enqueued on the lane's stream.  group == NULL: one group of all n paths, no group array on the device.  paths[g] = paths of group g.  Nothing
+// is launched before the ends are known to be good.  The layout of c->gc_ends and c->gc_grid is stated in orip_ctx.h.
+int gc_grids(orip_ctx* c, const char* who, const int32_t* ends, const int32_t* group, int64_t n, int G, int rev, const int64_t* paths, GcOrder& o) {
+    if (ends)
+        for (int64_t i = 0; i < 4 * n; i++) if (ends[i] < 0 || ends[i] > GC_COORD_MAX) ORIP_FAIL_AS(c, who, "path %lld: coordinate %d outside 0..2^30", (long long)(i / 4), ends[i]);
+    const int64_t m = n << rev;                                             // candidates
+    hipStream_t s = LN(c).stream;
+    int *grp, *box;
+    { Carve L; L.take(o.se, (size_t)n); L.take(grp, group ? (size_t)n : 0); L.take(o.order, (size_t)n); L.take(o.rv, group ? (size_t)n : 0); L.take(box, (size_t)4 * G);
+      L.take(o.dG, (size_t)G); HIPC(c, L.commit(c->gc_ends, 64)); }
+    if (ends) HIPC(c, hipMemcpyAsync(o.se, ends, (size_t)n * 16, hipMemcpyHostToDevice, s));
+    else hipLaunchKernelGGL(k_gc_ends, dim3(cdiv(n, 256)), dim3(256), 0, s, c->gc_off.as<long long>(), c->gc_pts.as<int2>(), n, o.se);
+    if (group) HIPC(c, hipMemcpyAsync(grp, group, (size_t)n * 4, hipMemcpyHostToDevice, s)); else grp = nullptr;
+    int hbox[4 * ORIP_ORDER_MAX_GROUPS];
+    for (int g = 0; g < G; g++) { hbox[4 * g] = hbox[4 * g + 1] = INT_MAX; hbox[4 * g + 2] = hbox[4 * g + 3] = INT_MIN; }
+    HIPC(c, hipMemcpyAsync(box, hbox, (size_t)16 * G, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_op_bbox, dim3(cdiv(m, 256)), dim3(256), 0, s, o.se, grp, (int)m, rev, box);
+    HIPC(c, hipMemcpyAsync(hbox, box, (size_t)16 * G, hipMemcpyDeviceToHost, s));
+    HIPC(c, hipStreamSynchronize(s));
+    int64_t ncell = 0;
+    for (int g = 0; g < G; g++) {
+        OpGroup& q = o.hG[g];
+        q.g = GcGrid{0, 0, 0, 0, 0, 1, 1}; q.cell0 = (int)ncell; q.paths = (int)paths[g];
+        if (!paths[g]) continue;                                              // an empty group: no cells, no steps
+        const int* b = hbox + 4 * g;
+        if (b[0] < 0 || b[1] < 0 || b[2] > GC_COORD_MAX || b[3] > GC_COORD_MAX || b[0] > b[2] || b[1] > b[3]) {
+            if (group) ORIP_FAIL_AS(c, who, "bounding box of group %d is off", g);
+            ORIP_FAIL_AS(c, who, "bounding box of the first points is off");
+        }
+        q.g = gc_grid_for(b, paths[g] << rev);
+        ncell += (int64_t)q.g.gx * q.g.gy;                                    // at most m / 2 + G over all groups
+    }
+    o.ncell = (int)ncell;
+    unsigned *cnt, *start, *fill;
+    { Carve L; L.take(cnt, (size_t)ncell + 1); L.take(start, (size_t)ncell + 1); L.take(fill, (size_t)ncell); L.take(o.hdr, (size_t)ncell); L.take(o.ent, (size_t)m);
+      L.take(o.slot, rev ? (size_t)m : 0); HIPC(c, L.commit(c->gc_grid, 64)); }
+    HIPC(c, hipMemcpyAsync(o.dG, o.hG, sizeof(OpGroup) * G, hipMemcpyHostToDevice, s));
+    HIPC(c, hipMemsetAsync(cnt, 0, ((size_t)ncell + 1) * 4, s));
+    HIPC(c, hipMemsetAsync(fill, 0, (size_t)ncell * 4, s));
+    hipLaunchKernelGGL(k_op_count, dim3(cdiv(m, 256)), dim3(256), 0, s, o.se, grp, (int)m, rev, o.dG, cnt);
+    HIPC(c, orip_with_tmp(c, [&](void* tmp, size_t& bytes) { return rocprim::exclusive_scan(tmp, bytes, cnt, start, 0u, (size_t)ncell + 1, rocprim::plus<unsigned>(), s); }));
+    hipLaunchKernelGGL(k_op_fill, dim3(cdiv(m, 256)), dim3(256), 0, s, o.se, grp, (int)m, rev, o.dG, start, fill, o.ent, o.slot);
+    hipLaunchKernelGGL(k_gc_hdr, dim3(cdiv(ncell, 256)), dim3(256), 0, s, start, cnt, (int)ncell, o.hdr);
+    return 0;
+}
+}  // namespace
+
+// order[k] = index of the k-th path to draw.  ends: (first x, first y, last x, last y) per path, or NULL for the resident step polylines.
+extern "C" int orip_gcode_order(orip_ctx* c, const int32_t* ends, int64_t n, int32_t* order_out) {
+    orip_enter(c);
+    ORIP_LANE(c, ORIP_LANE_CROSS);
+    if (n < 0 || (n > 0 && !order_out)) ORIP_FAIL(c, "bad arguments");
+    if (n == 0) return 0;
+    if (!ends && (!c->gc_ready || n != c->gc_n)) ORIP_FAIL(c, "%lld paths asked for, %lld step polylines resident", (long long)n, (long long)(c->gc_ready ? c->gc_n : -1));
+    if (n > (1 << 27)) ORIP_FAIL(c, "%lld paths: at most 2^27", (long long)n);
+    GcOrder o;
+    ORIP_TRY(gc_grids(c, __func__, ends, nullptr, n, 1, 0, &n, o));
+    hipStream_t s = LN(c).stream;
+    { ProfScope ps(c, "k_gc_chain");
+      hipLaunchKernelGGL(k_gc_chain, dim3(1), dim3(64), 0, s, o.se, (int)n, o.hdr, o.ent, o.hG[0].g, o.order); }
+    HIPC(c, hipGetLastError());
+    HIPC(c, hipMemcpyAsync(order_out, o.order, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    HIPC(c, hipStreamSynchronize(s));
+    if (order_out[0] < 0) ORIP_FAIL(c, "the chain lost a path (internal error)");
+    return 0;
+}
+
+// group after group from start_xy, inside a group the nearest remaining end (first points only without ORIP_ORDER_REVERSE); include/orip.h states the rule
+extern "C" int orip_gcode_order_pens(orip_ctx* c, const int32_t* ends, const int32_t* group, int64_t n, int32_t n_groups, int32_t flags, const int32_t* start_xy,
+                                     int32_t* order_out, uint8_t* rev_out) {
+    orip_enter(c);
+    ORIP_LANE(c, ORIP_LANE_CROSS);
+    if (n < 0 || (n > 0 && (!group || !order_out || !rev_out)) || (flags & ~ORIP_ORDER_REVERSE)) ORIP_FAIL(c, "bad arguments");
+    if (n_groups < 1 || n_groups > ORIP_ORDER_MAX_GROUPS) ORIP_FAIL(c, "%d groups: 1..%d", n_groups, ORIP_ORDER_MAX_GROUPS);
+    const int sx = start_xy ? start_xy[0] : 0, sy = start_xy ? start_xy[1] : 0;
+    if (sx < 0 || sy < 0 || sx > GC_COORD_MAX || sy > GC_COORD_MAX) ORIP_FAIL(c, "start (%d, %d) outside 0..2^30", sx, sy);
+    if (n == 0) return 0;
+    if (!ends && (!c->gc_ready || n != c->gc_n)) ORIP_FAIL(c, "%lld paths asked for, %lld step polylines resident", (long long)n, (long long)(c->gc_ready ? c->gc_n : -1));
+    if (n > (1 << 26)) ORIP_FAIL(c, "%lld paths: at most 2^26", (long long)n);
+    int64_t paths[ORIP_ORDER_MAX_GROUPS] = {0};
+    for (int64_t i = 0; i < n; i++) {
+        if (group[i] < 0 || group[i] >= n_groups) ORIP_FAIL(c, "path %lld: group %d of %d", (long long)i, group[i], n_groups);
+        paths[group[i]]++;
+    }
+    const int rev = flags & ORIP_ORDER_REVERSE ? 1 : 0;
+    GcOrder o;
+    ORIP_TRY(gc_grids(c, __func__, ends, group, n, n_groups, rev, paths, o));
+    hipStream_t s = LN(c).stream;
+    { ProfScope ps(c, "k_op_chain");
+      hipLaunchKernelGGL(k_op_chain, dim3(1), dim3(64), 0, s, o.se, (int)n, o.dG, (int)n_groups, rev, sx, sy, o.ncell, (int)(n << rev), o.hdr, o.ent, o.slot, o.order, o.rv); }
+    HIPC(c, hipGetLastError());
+    HIPC(c, hipMemcpyAsync(order_out, o.order, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    HIPC(c, hipMemcpyAsync(rev_out, o.rv, (size_t)n, hipMemcpyDeviceToHost, s));
+    HIPC(c, hipStreamSynchronize(s));
+    if (order_out[0] < 0) ORIP_FAIL(c, "the chain lost a path (internal error)");
+    return 0;
+}

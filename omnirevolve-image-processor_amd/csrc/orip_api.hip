@@ -93,7 +93,7 @@ extern "C" void orip_destroy(orip_ctx* c) {
     c->comm_sizes.release();
     c->stream_segs.release(); c->stream_off.release(); c->stream_codes.release();
     c->sp_data.release(); c->sp_agg.release(); c->sp_keys.release(); c->sp_rgb.release();
-    c->gc_tmp.release(); c->gc_off.release(); c->gc_pts.release(); c->gc_ends.release(); c->gc_grid.release(); c->pk_tab.release(); c->pk_out.release(); c->gc_src.release(); c->op_ends.release(); c->op_grid.release(); c->ht_grp.release();
+    c->gc_tmp.release(); c->gc_off.release(); c->gc_pts.release(); c->gc_ends.release(); c->gc_grid.release(); c->pk_tab.release(); c->pk_out.release(); c->gc_src.release(); c->ht_grp.release();
     c->mg_tab.release(); c->mg_tmp.release(); c->mg_off.release(); c->mg_pts.release(); c->mg_res.release();
     c->im_state.release(); c->im_rec.release();
     c->sv_tmp.release(); c->sv_tmp2.release(); c->sv_off.release(); c->sv_pts.release(); c->ht_pts.release(); c->ht_rows.release(); c->ht_x.release();

@@ -33,13 +33,15 @@
 
 typedef uint8_t u8;
 
-#define ORIP_FAIL(ctx, ...)                                              \
+// `who` names the entry point in the message: a helper that checks arguments for several entry points passes its caller's __func__ on
+#define ORIP_FAIL_AS(ctx, who, ...)                                      \
     do {                                                                 \
         char _b[512];                                                    \
         snprintf(_b, sizeof(_b), __VA_ARGS__);                           \
-        { std::lock_guard<std::mutex> _g((ctx)->mu); (ctx)->err = std::string(__func__) + ": " + _b; } \
+        { std::lock_guard<std::mutex> _g((ctx)->mu); (ctx)->err = std::string(who) + ": " + _b; } \
         return -1;                                                       \
     } while (0)
+#define ORIP_FAIL(ctx, ...) ORIP_FAIL_AS(ctx, __func__, __VA_ARGS__)
 
 #define HIPC(ctx, call)                                                                        \
     do {                                                                                       \
@@ -324,11 +326,15 @@ struct orip_ctx {
     // 14_preview_stream: stream bytes, tile products / prefixes / totals / counters, key plane, RGB image (stream_preview.hip), resident until the fetch
     DBuf sp_data, sp_agg, sp_keys, sp_rgb; int sp_rw = 0, sp_rh = 0; bool sp_ready = false;
     // gcode2stream (gcode.hip): scratch of the conversion, the resident step polylines (off int64[gc_n + 1], pts int2[gc_total]) between orip_gcode_to_steps and
-    // the fetch / orip_gcode_order, ends + order and the grid of the order, the piece table and the packed bytes between orip_stream_pack and its fetch
-    DBuf gc_tmp, gc_off, gc_pts, gc_ends, gc_grid, pk_tab, pk_out; int64_t gc_n = 0, gc_total = 0, pk_bytes = -1; bool gc_ready = false;
-    // resident next to the step polylines: gc_src int32[gc_n] = the input path every step polyline came from (orip_gcode_steps_source_fetch); scratch of
-    // orip_gcode_order_pens: op_ends = ends, groups, results, boxes and group descriptors, op_grid = the cell grids of all groups and the slot table
-    DBuf gc_src, op_ends, op_grid;
+    // the fetch / the orders, gc_src int32[gc_n] = the input path every step polyline came from (orip_gcode_steps_source_fetch) next to them; the piece
+    // table and the packed bytes between orip_stream_pack and its fetch (stream.hip)
+    DBuf gc_tmp, gc_off, gc_pts, gc_src, pk_tab, pk_out; int64_t gc_n = 0, gc_total = 0, pk_bytes = -1; bool gc_ready = false;
+    // orip_gcode_order and orip_gcode_order_pens (gcode_order.hip: gc_grids), free between calls.  With n paths in G groups, m = n or 2n candidates (both ends
+    // under ORIP_ORDER_REVERSE) and ncell cells over all groups' grids:
+    //   gc_ends = se int4[n] (first x, y, last x, y), grp int[n], order int[n], rev u8[n], box int[4G], OpGroup[G]; grp and rev only for the grouped order
+    //   gc_grid = cnt unsigned[ncell + 1], start unsigned[ncell + 1], fill unsigned[ncell], hdr int2[ncell] = (first entry, live entries) per cell,
+    //             ent int4[m] = (x, y, id, 0), slot int[m] = where candidate id sits (under ORIP_ORDER_REVERSE only)
+    DBuf gc_ends, gc_grid;
     // --merge-paths (gcode_merge.hip): mg_tab / mg_tmp = scratch of the node table and of the chains, free between calls (the unit states their layout);
     // mg_off / mg_pts = the output, swapped with gc_off / gc_pts when a merge succeeds; mg_res = member_off int64[mg_paths + 1], member int32[mg_n],
     // rev u8[mg_n] of the last merge of mg_n paths (-1: none) until the next one.  gc_merged: the resident step polylines are merged ones, gc_src no

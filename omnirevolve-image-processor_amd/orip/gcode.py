@@ -241,6 +241,11 @@ def pen_sequence(pen_order: Optional[str]) -> List[int]:
     return seq + [p for p in range(MAX_PENS) if p not in seq]
 
 
+def path_ends(off: np.ndarray, pts: np.ndarray) -> np.ndarray:
+    """(first x, first y, last x, last y) of every path: int32 [n, 4], what the orders and the improvement take"""
+    return np.ascontiguousarray(np.concatenate([pts[off[:-1]], pts[off[1:] - 1]], 1), np.int32)
+
+
 def gather_paths(off: np.ndarray, pts: np.ndarray, order: np.ndarray, rev: Optional[np.ndarray] = None) -> Tuple[np.ndarray, np.ndarray]:
     """the paths in the given order, those with rev[k] set back to front: (off, pts), flat numpy over all paths"""
     order = np.asarray(order, np.int64)
@@ -407,13 +412,13 @@ def build_stream_from_gcode(text_or_paths, opts: Optional[GcodeOptions] = None, 
         if o.no_reorder:
             order, rev = np.argsort(group, kind="stable"), np.zeros(n, bool)      # pen after pen all the same, file order inside a pen
         else:
-            order, rev = order_pens_fn(np.ascontiguousarray(np.concatenate([pts[off[:-1]], pts[off[1:] - 1]], 1), np.int32), group, n_groups, bool(o.allow_reverse))
+            order, rev = order_pens_fn(path_ends(off, pts), group, n_groups, bool(o.allow_reverse))
             order = np.asarray(order, np.int64); rev = np.asarray(rev, bool)
             if len(order) != n or len(rev) != n or not np.array_equal(np.sort(order), np.arange(n)) or (np.diff(group[order]) < 0).any():
                 raise RuntimeError("the path order is not a permutation that keeps the pens together")
             if o.improve_order:
                 lap("order")
-                order, rev = improve(np.ascontiguousarray(np.concatenate([pts[off[:-1]], pts[off[1:] - 1]], 1), np.int32), group, n_groups, order, rev, bool(o.allow_reverse))
+                order, rev = improve(path_ends(off, pts), group, n_groups, order, rev, bool(o.allow_reverse))
                 lap("improve")
         off, pts = gather_paths(off, pts, order, rev)
         path_pen = pen[order]
@@ -422,17 +427,14 @@ def build_stream_from_gcode(text_or_paths, opts: Optional[GcodeOptions] = None, 
         else:
             info["reversed"] = int(rev.sum())
     elif not o.no_reorder:
-        order = np.asarray(order_fn(np.ascontiguousarray(np.concatenate([pts[off[:-1]], pts[off[1:] - 1]], 1), np.int32)), np.int64)
+        order = np.asarray(order_fn(path_ends(off, pts)), np.int64)
         if len(order) != n or not np.array_equal(np.sort(order), np.arange(n)):
             raise RuntimeError("the path order is not a permutation")
         if o.improve_order:
             lap("order")
-            order, _ = improve(np.ascontiguousarray(np.concatenate([pts[off[:-1]], pts[off[1:] - 1]], 1), np.int32), np.zeros(n, np.int32), 1, order, np.zeros(n, bool), False)
+            order, _ = improve(path_ends(off, pts), np.zeros(n, np.int32), 1, order, np.zeros(n, bool), False)
             lap("improve")
-        lens = np.diff(off)[order]
-        noff = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
-        pts = pts[np.repeat(off[:-1][order], lens) + np.arange(int(lens.sum())) - np.repeat(noff[:-1], lens)]
-        off = noff
+        off, pts = gather_paths(off, pts, order)
     lap("order")
     if not (0 <= int(o.color_index) <= 7):
         raise ValueError("color index 0..7")

@@ -1,4 +1,4 @@
-"""gcode2stream on the GPU: each kernel of csrc/gcode.hip against the reference's recorded output (tests/golden/golden_gcode.npz), bit for bit; the packed
+"""gcode2stream on the GPU: each kernel of csrc/gcode.hip, csrc/gcode_order.hip and the pack of csrc/stream.hip against the reference's recorded output (tests/golden/golden_gcode.npz), bit for bit; the packed
 bytes against the doubles' two numpy packers on stage 13's plots; the whole tool, in process and as the script on disk, against the files the reference's main()
 wrote; every degenerate input of the order; one order beyond what the reference can run, checked pair by pair against the definition; and a round trip
 through the stream preview.  No comparison has a tolerance and no recorded case is left out."""
@@ -106,6 +106,27 @@ def test_order_degenerate_inputs(dev):
         dev.gcode_order(np.array([[0, 0, -1, 0]]))
     with pytest.raises(OripError):
         dev.gcode_order(np.array([[0, 0, (1 << 30) + 1, 0]]))
+
+
+def _shared_walk_cases():
+    rng = np.random.default_rng(22)
+    far = lambda k: rng.integers(0, 1 << 20, (k, 2))
+    same = lambda k: np.concatenate([np.full((k, 2), 77), far(k)], 1)
+    cluster = np.concatenate([1000 + rng.integers(0, 40, (300, 2)), rng.integers(0, 1 << 29, (300, 2))], 1)      # the cursor lands anywhere in the box
+    return {"same_64": same(64), "same_65": same(65), "same_3000": same(3000),                                     # the two sides of GC_BIG, and far beyond
+            "row_500": np.concatenate([np.stack([rng.integers(0, 1 << 20, 500), np.full(500, 9)], 1), far(500)], 1),
+            "column_500_at_top": np.concatenate([np.stack([np.full(500, 1 << 30), rng.integers(0, 1 << 20, 500)], 1), far(500)], 1),
+            "cluster_and_one_far": np.concatenate([cluster, [[1000 + (1 << 29), 1000 + (1 << 29), 5, 5]]]),
+            "one_far": np.array([[1 << 30, 0, 3, 3]]), "two_apart": np.array([[900, 5, 0, 1 << 30], [3, 800, 7, 7]])}
+
+
+@pytest.mark.parametrize("name", list(_shared_walk_cases()))
+def test_order_shared_walk_shapes(dev, name):
+    """orip_gcode_order through the grouped setup kernels and the shared search: a cell of exactly GC_BIG entries and of one more (four lanes against the
+    whole wave), thousands on one point, one row with the cursor starting off it, one column on the last coordinate, a tight cluster with one path 2^29
+    steps away (the window grows ring by ring until it meets the grid's edge on all four sides), one path and two"""
+    e = _shared_walk_cases()[name]
+    assert np.array_equal(dev.gcode_order(e), D.order_numpy(e))
 
 
 def test_order_of_resident_polylines(dev):

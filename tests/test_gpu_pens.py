@@ -75,6 +75,14 @@ def test_order_one_crowded_cell(dev):
     same(dev, np.full((3000, 4), 77), np.arange(3000) % 2, 2)
 
 
+@pytest.mark.parametrize("k", [64, 65])
+def test_order_cell_at_the_whole_wave_threshold(dev, k):
+    """k paths per group on one point, two groups: without reversal a cell of 64 entries (four lanes each) or 65 (the whole wave), with it 128 / 130"""
+    same(dev, np.full((2 * k, 4), 77), np.repeat([0, 1], k), 2)
+    rng = np.random.default_rng(k)
+    same(dev, np.concatenate([np.full((2 * k, 2), 77), rng.integers(0, 1 << 20, (2 * k, 2))], 1), np.arange(2 * k) % 2, 2)      # far ends apart: more cells than one
+
+
 def test_order_both_ends_in_one_cell(dev):
     """short strokes on a wide sheet: a path's two ends share a cell (the grid's cells are far wider than a stroke)"""
     rng = np.random.default_rng(6)

@@ -1,4 +1,4 @@
-"""Where the time of gcode2stream goes (orip/gcode.py, csrc/gcode.hip), on seeded synthetic plots.
+"""Where the time of gcode2stream goes (orip/gcode.py, csrc/gcode.hip, csrc/gcode_order.hip, csrc/stream.hip), on seeded synthetic plots.
   whole   : parse / to-steps / order / plan / codes / pack + fetch of a hatch-like plot of --paths paths on A4 at 40 steps per mm, through
             build_stream_from_gcode, and the whole script on the same file as a child process
   order   : the order kernel alone at several sizes of uniformly spread paths (call time, k_gc_chain time, time per step) and for a star
@@ -51,7 +51,7 @@ def time_order(dev, ends, reps):
         kern.append(dev.prof_get("k_gc_chain")[0] * 1e-3)
     n = len(ends)
     return {"paths": n, "call_s_median": float(np.median(call)), "chain_s_median": float(np.median(kern)), "chain_us_per_step": 1e6 * float(np.median(kern)) / n,
-            "reps": reps}, order
+            "reps": reps, "call_s": call, "chain_s": kern}, order
 
 
 def main():

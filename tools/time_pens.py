@@ -1,4 +1,4 @@
-"""What the grouped, reversible order costs next to the order it grew from (csrc/gcode.hip: k_gc_chain, k_op_chain), on --paths uniformly spread paths on an
+"""What the grouped, reversible order costs next to the order it grew from (csrc/gcode_order.hip: k_gc_chain, k_op_chain), on --paths uniformly spread paths on an
 A4 step canvas (8400 x 11880), the input of tools/time_gcode.py's order section:
   parent          : orip_gcode_order
   one_group       : orip_gcode_order_pens, one group, no flag (the same work: the result must be equal)
@@ -28,7 +28,7 @@ def timed(dev, call, kernel, reps):
         t0 = time.perf_counter(); out = call(); t.append(time.perf_counter() - t0)
         dev.prof_enable(False)
         k.append(dev.prof_get(kernel)[0] * 1e-3)
-    return {"call_s_median": float(np.median(t)), "chain_s_median": float(np.median(k)), "reps": reps}, out
+    return {"call_s_median": float(np.median(t)), "chain_s_median": float(np.median(k)), "reps": reps, "call_s": t, "chain_s": k}, out
 
 
 def main():

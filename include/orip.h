@@ -309,6 +309,45 @@ int orip_gcode_order_pens(orip_ctx* ctx, const int32_t* ends /* [n,4] or NULL = 
 int orip_gcode_merge(orip_ctx* ctx, const int64_t* off /* [n+1] or NULL */, const int32_t* pts /* [off[n],2] or NULL */, const int32_t* group /* [n] or NULL = all 0 */,
                      int64_t n, int32_t n_groups /* 1..64 */, int32_t flags, int64_t* stats /* [4]: paths_out, points_out, joins, cycles */);
 int orip_gcode_merge_fetch(orip_ctx* ctx, int64_t* member_off /* [paths_out+1] */, int32_t* member /* [n] */, uint8_t* rev /* [n] */);
+/* --simplify-mm (csrc/gcode_simplify.hip; ours, the reference's simplify_enabled / epsilon_factor in image_processor/config.py are dead settings): vertices
+ * within a tolerance of the stroke are dropped.  Ramer-Douglas-Peucker on the step grid, per stroke, exact in integers.
+ * Input: n step polylines of two points or more, coordinates 0 .. 2^30, no two consecutive points equal (the conversions and the merge guarantee it;
+ * in the uploaded form a consecutive duplicate is an argument error), and the tolerance in QUARTER STEPS, tol4 in 0 .. ORIP_SIMPLIFY_TOL4_MAX; the tools
+ * take tol4 = round(4 * mm * steps_per_mm), so nothing depends on a rounding of coordinates.
+ *   A SPAN (a, b), a < b the indices of two kept points of one stroke, has an interior when b - a >= 2.  With d = P_b - P_a, L = |d|^2 and, for an
+ *   interior point P, t = (P - P_a) . d, the KEY of P is
+ *       K = |P - P_a|^2 L            if t <= 0
+ *       K = |P - P_b|^2 L            if t >= L
+ *       K = cross(P - P_a, d)^2      otherwise
+ *   the squared distance to the SEGMENT times L (L is common to the span).  The segment, not the line: a point beyond an end of the chord is not on it.
+ *   A DEGENERATE span, P_a = P_b (a closed stroke, or deeper down a figure-eight), has K = |P - P_a|^2.
+ *   The span's point is the interior point with the largest K, the lowest index among equals.  It is kept iff 16 K > tol4^2 L, strictly; in a degenerate
+ *   span iff K > 0, so a loop is never collapsed to a stroke of no length and the output never has two equal consecutive points.  If it is kept, the
+ *   spans (a, m) and (m, b) are treated the same way; if not, the whole interior is dropped.  The first and the last point of a stroke are always kept,
+ *   and the stroke's first span is (first, last).
+ *   K reaches 2^122 and 16 K and tol4^2 L are compared in full, on 128-bit integers: no floating point, no 64-bit shortcut.
+ * Consequences.  The number and the order of the strokes, their ends, their pens and their sources do not change: orders, improvement and
+ * orip_gcode_steps_source_fetch are not affected.  Every dropped point lies within tol4 / 4 steps of the kept segment that spans it.  The pass is
+ * idempotent.  A stroke of two points (every hatch line) passes through untouched.  tol4 == 0 removes exactly the vertices that lie on the segment
+ * between their kept neighbours.  The result is a function of the input alone; the worst case is quadratic in a stroke's length (n log n on drawings) and
+ * nothing bounds it, because the result must not depend on a budget.
+ * kept[points_out] (orip_gcode_simplify_fetch): the index of every output point in the input point list, ascending.  stats: paths (= n), points_in,
+ * points_out, rounds = the levels of re-queued spans the device went through (0: every stroke was finished where it was first looked at; strokes of at
+ * most ORIP_SIMPLIFY_LOCAL points always are); rounds says nothing about the result.
+ * off == NULL and pts == NULL: the resident step polylines, n must be their count (as for orip_gcode_merge).  In both forms the simplified polylines
+ * BECOME the resident step polylines: orip_gcode_steps_fetch copies them out and the orders, the merge and the improvement take them for NULL.  The source
+ * indices stay what they were: the resident form keeps its strokes, and an uploaded list of as many polylines as are resident is taken for them; any
+ * other uploaded list has no sources (as after a merge) until the next conversion.
+ * Errors before any launch, without a fault and with the resident polylines left as they were: tol4 outside its range, n < 0 or n > 2^26, 2^30 points or
+ * more, off not starting at 0 or decreasing, a path under two points, a coordinate outside 0 .. 2^30, a point equal to the one before it, exactly one of
+ * off / pts NULL, n that is not the resident count, NULL stats.  n == 0 returns zeros before any launch.
+ * Declined: a tolerance in mm applied before the rounding to steps (double rounding), Visvalingam or any area criterion (one rule only), dropping short
+ * strokes or small loops (this pass never removes a stroke), a bound on the worst case. */
+#define ORIP_SIMPLIFY_TOL4_MAX ((1 << 17) - 1)
+#define ORIP_SIMPLIFY_LOCAL 1024      /* a span of at most this many points is finished by one wave in LDS and is never re-queued */
+int orip_gcode_simplify(orip_ctx* ctx, const int64_t* off /* [n+1] or NULL */, const int32_t* pts /* [off[n],2] or NULL */, int64_t n, int32_t tol4,
+                        int64_t* stats /* [4]: paths, points_in, points_out, rounds */);
+int orip_gcode_simplify_fetch(orip_ctx* ctx, int64_t* kept /* [points_out]: index of every output point in the input point list */);
 /* --improve-order (csrc/gcode_improve.hip; ours, the reference stops at the greedy order): 2-opt and or-opt on a drawing sequence, by steepest descent.
  * Input: n step polylines given by their ends as for orip_gcode_order_pens (ends NULL = the resident ones, n must be their count), one group per polyline,
  * a start cursor, and a valid drawing sequence order[n], rev[n]: order is a permutation, the groups of its entries do not decrease, rev[k] is 0 or 1 and

@@ -344,6 +344,10 @@ struct orip_ctx {
     // (ab int4[2][n], id int[2][n]) a move is written between; im_rec = one record per block of the evaluation, the two status slots and the two travels
     // (the unit states the layout)
     DBuf im_state, im_rec;
+    // --simplify-mm (gcode_simplify.hip): sp_tmp = the keep flags, their scan, the two span lists and the counts, free between calls (the unit states the
+    // layout); sp_off / sp_pts = the output, swapped with gc_off / gc_pts when a call succeeds; sp_res = kept int64[sp_points], the input index of every
+    // output point of the last call (-1: none) until the next one.  gc_src still names the simplified polylines: their number and order do not change
+    DBuf sp_tmp, sp_off, sp_pts, sp_res; int64_t sp_points = -1;
     // svg2stream (svg.hip): scratch of the flattening and of the box, the resident paths (off int64[sv_n + 1], pts double2[sv_total]; raw units after
     // orip_svg_flatten, page mm after orip_svg_fit) until the next flatten; orip_gcode_to_steps reads them when it is called without pointers
     DBuf sv_tmp, sv_tmp2, sv_off, sv_pts; int64_t sv_n = 0, sv_total = 0; bool sv_ready = false, sv_box_ok = false; double sv_box[4] = {0, 0, 0, 0};

@@ -496,6 +496,34 @@ class Device:
         off_s, pts_s = self.gcode_steps_fetch(paths, total)
         return off_s, pts_s, moff, member[:n], rev[:n].astype(bool), {k: int(v) for k, v in zip(("paths_out", "points_out", "joins", "cycles"), st)}
 
+    def gcode_simplify(self, off, pts, tol4: int, n: int | None = None):
+        """--simplify-mm (include/orip.h: orip_gcode_simplify): Ramer-Douglas-Peucker on the step polylines (off int64 [n + 1], pts int32 [total, 2]; both
+        None = the n resident ones) with the tolerance tol4 in quarter steps, and the simplified polylines become the resident ones.
+        -> (off int64, pts int32 [total', 2], kept int64 [total']: the input index of every output point, {"paths", "points_in", "points_out", "rounds"})"""
+        o = p = None
+        if off is not None or pts is not None:
+            if off is None or pts is None:
+                raise OripError("off and pts: both or neither")
+            o = np.ascontiguousarray(off, np.int64).reshape(-1)
+            p = np.ascontiguousarray(pts, np.int32).reshape(-1, 2)
+            n = max(len(o) - 1, 0)
+            if len(o) < 1 or int(o[-1]) != len(p):
+                raise OripError(f"offsets end at {int(o[-1]) if len(o) else None}, {len(p)} points given")
+            if len(p) == 0:
+                p = np.zeros((1, 2), np.int32)                   # n == 0: a pointer all the same, so that the form stays the explicit one
+        if n is None:
+            raise ValueError("n: the number of resident step polylines")
+        if not (-(1 << 31) <= int(tol4) < (1 << 31)):
+            raise OripError(f"tolerance {tol4} quarter steps")
+        n = int(n)
+        st = np.zeros(4, np.int64)
+        self._ck(self.L.orip_gcode_simplify(self.h, _p(o) if o is not None else None, _p(p) if p is not None else None, n, int(tol4), _p(st)))
+        total = int(st[2])
+        kept = np.zeros(max(total, 1), np.int64)
+        self._ck(self.L.orip_gcode_simplify_fetch(self.h, _p(kept)))
+        off_s, pts_s = self.gcode_steps_fetch(n, total)
+        return off_s, pts_s, kept[:total], {k: int(v) for k, v in zip(("paths", "points_in", "points_out", "rounds"), st)}
+
     def gcode_steps_fetch(self, n: int, total: int) -> Tuple[np.ndarray, np.ndarray]:
         """the n resident step polylines of `total` points, as gcode_to_steps or gcode_merge left them: (off int64 [n + 1], pts int32 [total, 2])"""
         off = np.zeros(int(n) + 1, np.int64); pts = np.zeros((max(int(total), 1), 2), np.int32)

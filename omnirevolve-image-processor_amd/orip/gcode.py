@@ -32,7 +32,14 @@ paper, and a segment with one end outside changes its slope.  With --clip the st
 in steps, m = --clip-margin-mm in steps (default 0: the sheet); what lies outside is not drawn and the pen is lifted there (orip_gcode_to_steps_clip, which
 takes the place of orip_gcode_to_steps; include/orip.h states the rule, exact in integers on the step grid).  A path that leaves and comes back becomes
 several strokes of the same input path, so pens, merge, order and improve work on the cut strokes unchanged.  Without the option no device call is added
-and every byte is what it was."""
+and every byte is what it was.
+
+--simplify-mm (ours as well): every vertex of the input goes into the stream, as a move of its own, a speed byte and a candidate corner, and a segment of at
+most --short-len-steps is drawn at --short-div; a curve flattened into chords the pen cannot resolve is drawn slower and in more bytes than it need be.  With
+--simplify-mm T the vertices that lie within T of the stroke are dropped: Ramer-Douglas-Peucker per stroke on the step grid, exact in integers, the tolerance
+in quarter steps, tol4 = round(4 T steps_per_mm) (orip_gcode_simplify; include/orip.h states the rule).  0 is allowed: it removes exactly the vertices on
+the segment between their kept neighbours.  It runs after the merge, so that the joints inside a merged chain can go, and before the order; strokes, their
+ends, pens and sources do not change.  Without the option no device call is added and every byte is what it was."""
 from __future__ import annotations
 
 import argparse
@@ -86,6 +93,7 @@ class GcodeOptions:
     improve_rounds: Optional[int] = None    # rounds per group at most (None: 2 m + 64 for a group of m strokes); only with improve_order
     clip: bool = False                  # strokes are cut at the sheet's edge (less the margin) instead of clamped to it
     clip_margin_mm: Optional[float] = None  # the clip rectangle lies this far inside the sheet (None: 0); only with clip
+    simplify_mm: Optional[float] = None     # vertices within this distance of the stroke are dropped (None: every vertex is drawn; 0: only those on the stroke)
 
 
 # ------------------------------------------------------------------ parse (:113-142, :177-300)
@@ -281,7 +289,7 @@ def build_stream_from_gcode(text_or_paths, opts: Optional[GcodeOptions] = None, 
                             order_fn: Optional[Callable] = None, codes_fn: Optional[Callable] = None, pack_fn: Optional[Callable] = None,
                             timings: Optional[dict] = None, pens: Optional[np.ndarray] = None, order_pens_fn: Optional[Callable] = None,
                             source_fn: Optional[Callable] = None, merge_fn: Optional[Callable] = None, improve_fn: Optional[Callable] = None,
-                            clip_fn: Optional[Callable] = None) -> Tuple[bytes, dict]:
+                            clip_fn: Optional[Callable] = None, simplify_fn: Optional[Callable] = None) -> Tuple[bytes, dict]:
     """The stream of a G-code text (str / bytes) or of paths in mm given as (off, pts_mm); opts as parsed, --speed-scale not yet applied.
     Device steps, each None = the GPU (orip.device.Device; there is no CPU path in the product):
       steps_fn(off, pts_mm, map: dict) -> (off int64, pts int32 [total, 2])      orip_gcode_to_steps
@@ -299,6 +307,9 @@ def build_stream_from_gcode(text_or_paths, opts: Optional[GcodeOptions] = None, 
     and, only with --clip, in the place of steps_fn (source_fn keeps its meaning: the input path of every stroke, now with repeats):
       clip_fn(off, pts_mm, map: dict, rect: (x0, y0, x1, y1)) -> (off, pts, stats)                              orip_gcode_to_steps_clip
     info["clip"] then holds rect and segments, inside, cut, outside, paths_out and points_out.
+    and, only with --simplify-mm (after the merge, before any order):
+      simplify_fn(off, pts, tol4) -> (off, pts, kept int64: the input index of every output point, stats)       orip_gcode_simplify
+    info["simplify"] then holds tol4, points_in, points_out and paths_changed.
     pens: one pen per input path, 0..7, or -1 for --color-index (a text's T words under --tool-pens when None).  info["pens"] then counts the paths per
     pen, those that took --color-index ("unmatched") and the strokes drawn backwards ("reversed").
     Returns (bytes, counts)."""
@@ -308,6 +319,7 @@ def build_stream_from_gcode(text_or_paths, opts: Optional[GcodeOptions] = None, 
     sc = stream_config(o)
     check_improve_options(o)
     rect = clip_rect(o)
+    tol4 = simplify_tol4(o)
     tm = timings if timings is not None else {}
     t0 = time.perf_counter()
 
@@ -338,10 +350,13 @@ def build_stream_from_gcode(text_or_paths, opts: Optional[GcodeOptions] = None, 
         raise ValueError(f"target size {W} x {H} steps: each side must be in 1..2^30 (step coordinates are int32 on the device)")
     convert_fn = steps_fn if rect is None else clip_fn
     if convert_fn is None or order_fn is None or (grouped and (order_pens_fn is None or source_fn is None)) or (o.merge_paths and merge_fn is None) or \
-            (o.improve_order and improve_fn is None):
+            (o.improve_order and improve_fn is None) or (tol4 is not None and simplify_fn is None):
         if device is None:
             from .stages import device as _default_device
             device = _default_device()
+        if simplify_fn is None:                                           # likewise simplified where they are, when this device's conversion or merge left them
+            sp_resident = merge_fn is None if o.merge_paths else convert_fn is None
+            simplify_fn = lambda off, pts, t4: device.gcode_simplify(None, None, t4, n=len(off) - 1) if sp_resident else device.gcode_simplify(off, pts, t4)
         if merge_fn is None:                                              # the polylines this device's own conversion left resident are merged where they are
             resident = convert_fn is None
             merge_fn = lambda off, pts, group, n_groups, reverse: (device.gcode_merge(None, None, group, n_groups, reverse, n=len(off) - 1) if resident else
@@ -400,6 +415,19 @@ def build_stream_from_gcode(text_or_paths, opts: Optional[GcodeOptions] = None, 
         info["paths"] = n
         info["merge"] = {"paths_in": n_in, "paths_out": n, "joins": int(mst["joins"]), "cycles": int(mst["cycles"])}
         lap("merge")
+    if tol4 is not None:
+        if not o.merge_paths:
+            lap("order")
+        off_in, pts_in = off, pts
+        off, pts, kept, _ = simplify_fn(off, pts, tol4)
+        off = np.asarray(off, np.int64).reshape(-1); pts = np.asarray(pts, np.int32).reshape(-1, 2); kept = np.asarray(kept, np.int64).reshape(-1)
+        # the same strokes with the same ends, every stroke an ascending selection of its own points
+        if len(off) != n + 1 or off[0] != 0 or int(off[-1]) != len(pts) or len(kept) != len(pts) or (np.diff(off) < 2).any() or \
+                not np.array_equal(kept[off[:-1]], off_in[:-1]) or not np.array_equal(kept[off[1:] - 1], off_in[1:] - 1) or \
+                (np.diff(kept) <= 0).any() or not np.array_equal(pts, pts_in[kept]):
+            raise RuntimeError("the simplification did not return every stroke with its ends and its points in order")
+        info["simplify"] = {"tol4": tol4, "points_in": len(pts_in), "points_out": len(pts), "paths_changed": int((np.diff(off) != np.diff(off_in)).sum())}
+        lap("simplify")
     def improve(ends, group, n_groups, order, rev, reverse):
         order, rev, ist = improve_fn(ends, group, n_groups, np.asarray(order, np.int32), np.asarray(rev, bool), reverse, o.improve_rounds)
         order = np.asarray(order, np.int64).reshape(-1); rev = np.asarray(rev, bool).reshape(-1)
@@ -451,6 +479,7 @@ def build_stream_from_gcode(text_or_paths, opts: Optional[GcodeOptions] = None, 
 
 IMPROVE_STATS = ("travel_before", "travel_after", "rounds", "converged_groups", "skipped_groups")
 CLIP_STATS = ("segments", "inside", "cut", "outside", "paths_out", "points_out")
+SIMPLIFY_TOL4_MAX = (1 << 17) - 1             # include/orip.h: ORIP_SIMPLIFY_TOL4_MAX
 
 
 def clip_rect(o) -> Optional[Tuple[int, int, int, int]]:
@@ -475,6 +504,26 @@ def clip_line(tag: str, c: dict) -> str:
     x0, y0, x1, y1 = c["rect"]
     return (f"[{tag}] clip: {c['segments']} segments: {c['inside']} inside, {c['cut']} cut, {c['outside']} outside [{x0}, {x1}] x [{y0}, {y1}] steps -> "
             f"{c['paths_out']} strokes, {c['points_out']} points")
+
+
+def simplify_tol4(o) -> Optional[int]:
+    """None without --simplify-mm, else the tolerance in quarter steps, round(4 mm steps_per_mm): 0 .. 2^17 - 1"""
+    if o.simplify_mm is None:
+        return None
+    mm = float(o.simplify_mm)
+    if not (mm >= 0.0) or mm == float("inf"):
+        raise ValueError("--simplify-mm must be a number and not negative")
+    q = 4.0 * mm * float(o.steps_per_mm)
+    if not (q < float(1 << 31)):
+        raise ValueError(f"--simplify-mm {mm:g} at {o.steps_per_mm:g} steps per mm is too wide")
+    t = int(round(q))
+    if t > SIMPLIFY_TOL4_MAX:
+        raise ValueError(f"--simplify-mm {mm:g} is {t / 4:g} steps: at most {SIMPLIFY_TOL4_MAX / 4:g}")
+    return t
+
+
+def simplify_line(tag: str, st: dict) -> str:
+    return f"[{tag}] simplify: {st['points_in']} points -> {st['points_out']} within {st['tol4'] / 4:g} steps, {st['paths_changed']} strokes changed"
 
 
 def check_improve_options(o) -> None:
@@ -530,6 +579,8 @@ def build_argparser() -> argparse.ArgumentParser:
     ap.add_argument("--improve-rounds", type=int, default=None, help="rounds per pen at most (default: 2 m + 64 for m strokes); needs --improve-order")
     ap.add_argument("--clip", action="store_true", help="cut the strokes at the edge of the sheet and lift the pen outside it, instead of clamping every point onto the edge")
     ap.add_argument("--clip-margin-mm", type=float, default=None, help="cut this far inside the edge of the sheet (default: 0); needs --clip")
+    ap.add_argument("--simplify-mm", type=float, default=None, help="drop the vertices that lie within this distance of the stroke (Ramer-Douglas-Peucker on the step grid; "
+                    "0: only vertices on the straight line between their neighbours)")
     return ap
 
 
@@ -543,6 +594,7 @@ def main(argv: Optional[Sequence[str]] = None, **device_steps) -> None:
     apply_speed_scale(GcodeOptions(speed_scale=opts.speed_scale))        # a bad scale ends the run before the file is read, as in the reference
     check_improve_options(opts)
     clip_rect(opts)
+    simplify_tol4(opts)
     text = Path(a.input).read_bytes()
     data, info = build_stream_from_gcode(text, opts, **device_steps)
     Path(a.output).write_bytes(data)
@@ -554,6 +606,8 @@ def main(argv: Optional[Sequence[str]] = None, **device_steps) -> None:
         print("[gcode] pens: " + ", ".join(f"{p}: {k} paths" for p, k in enumerate(info["pens"]["paths"]) if k) + f"; {info['pens']['reversed']} strokes reversed")
     if "merge" in info:
         print("[gcode] merge: {paths_in} paths -> {paths_out}, {joins} pen lifts saved, {cycles} closed".format(**info["merge"]))
+    if "simplify" in info:
+        print(simplify_line("gcode", info["simplify"]))
     if "improve" in info:
         print(improve_line("gcode", info["improve"]))
     print(f"stream saved: {a.output} ({len(data)} bytes)")

@@ -77,6 +77,7 @@ SIGNATURES = {
     "orip_gcode_to_steps_clip": (_i32, [_vp, _vp, _vp, _i64, _P(GcodeMap), _vp, _P(_i64), _P(_i64), _vp]),
     "orip_gcode_order_pens": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp]),
     "orip_gcode_merge": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp]), "orip_gcode_merge_fetch": (_i32, [_vp, _vp, _vp, _vp]),
+    "orip_gcode_simplify": (_i32, [_vp, _vp, _vp, _i64, _i32, _vp]), "orip_gcode_simplify_fetch": (_i32, [_vp, _vp]),
     "orip_gcode_improve": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _i64, _vp, _vp, _vp]),
     "orip_svg_flatten": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _f64, _P(_i64)]), "orip_svg_paths_fetch": (_i32, [_vp, _vp, _vp]),
     "orip_svg_bbox": (_i32, [_vp, _vp]), "orip_svg_fit": (_i32, [_vp, _f64, _f64, _f64, _f64]),
@@ -89,6 +90,7 @@ COMM_ID_BYTES = 128
 HATCH_SERPENTINE, HATCH_HORIZONTAL, HATCH_VERTICAL = 1, 2, 4
 ORDER_REVERSE, ORDER_MAX_GROUPS = 1, 64
 MERGE_REVERSE = 1
+SIMPLIFY_TOL4_MAX, SIMPLIFY_LOCAL = (1 << 17) - 1, 1024      # include/orip.h: the largest tolerance in quarter steps; the points one wave finishes alone
 CLIP_STATS = ("segments", "inside", "cut", "outside", "paths_out", "points_out")
 IMPROVE_MAX_PATHS, IMPROVE_ROUNDS_AUTO = 65536, (1 << 63) - 1
 

@@ -38,6 +38,10 @@ What is drawn does not change (an element with stroke="none" is still drawn, as 
 of being clamped onto the edge.  The fitted paths, hatch lines included, are cut where they lie on the device (orip_gcode_to_steps_clip without pointers);
 the pens of the cut strokes still come through the sources, and the G-code file is not changed.
 
+--simplify-mm (off unless given; ours, orip/gcode.py states it): the vertices that lie within the given distance of their stroke are dropped, on the step
+grid and on the device (orip_gcode_simplify), after the merge and before the order.  It is forwarded as it is; the G-code file is not changed, and
+--tolerance-mm keeps its meaning (how far a chord may lie from its curve; this option then thins the chords that the pen cannot tell apart).
+
 The device steps are injectable, as in orip/gcode.py, so that this host logic can be tested without a GPU; the product has no CPU path."""
 from __future__ import annotations
 
@@ -550,6 +554,7 @@ class SvgOptions:
     improve_rounds: Optional[int] = None                # rounds per group at most; None: 2 m + 64
     clip: bool = False                                  # strokes are cut at the sheet's edge instead of clamped to it (orip.gcode)
     clip_margin_mm: Optional[float] = None              # the clip rectangle lies this far inside the sheet; None: 0
+    simplify_mm: Optional[float] = None                 # vertices within this distance of the stroke are dropped (orip.gcode); None: none are
 
 
 HATCH_DIRECTIONS = {"horizontal": HATCH_HORIZONTAL, "vertical": HATCH_VERTICAL, "cross": HATCH_HORIZONTAL | HATCH_VERTICAL}
@@ -648,7 +653,8 @@ def gcode_options(o: SvgOptions) -> GC.GcodeOptions:
     return GC.GcodeOptions(steps_per_mm=o.steps_per_mm, invert_y=o.invert_y, color_index=o.color_index, speed_scale=o.speed_scale, scale_x=1.0, scale_y=1.0,
                            offset_x_mm=0.0, offset_y_mm=0.0, target_width_steps=W, target_height_steps=H, no_reorder=bool(o.no_reorder),
                            allow_reverse=bool(o.allow_reverse), pen_order=o.pen_order, merge_paths=bool(o.merge_paths),
-                           improve_order=bool(o.improve_order), improve_rounds=o.improve_rounds, clip=bool(o.clip), clip_margin_mm=o.clip_margin_mm)
+                           improve_order=bool(o.improve_order), improve_rounds=o.improve_rounds, clip=bool(o.clip), clip_margin_mm=o.clip_margin_mm,
+                           simplify_mm=o.simplify_mm)
 
 
 def gcode_text(off, pts, passes: int = 1, pens=None) -> str:
@@ -692,6 +698,7 @@ class _Resident:
     def source(self, n): return self.dev.gcode_steps_source(n)
     def order_pens(self, ends, group, n_groups, reverse): return self.dev.gcode_order_pens(ends, group, n_groups, reverse)
     def merge(self, off, pts, group, n_groups, reverse): return self.dev.gcode_merge(None, None, group, n_groups, reverse, n=len(off) - 1)
+    def simplify(self, off, pts, tol4): return self.dev.gcode_simplify(None, None, tol4, n=len(off) - 1)
 
 
 MAX_REFLATTEN = 8
@@ -761,7 +768,7 @@ def build_stream_from_svg(text: Union[str, bytes, SegmentTable], opts: Optional[
                           steps_fn: Optional[Callable] = None, order_fn: Optional[Callable] = None, codes_fn: Optional[Callable] = None, pack_fn: Optional[Callable] = None, timings: Optional[dict] = None,
                           want_paths: bool = False, hatch_groups_fn: Optional[Callable] = None, source_fn: Optional[Callable] = None,
                           order_pens_fn: Optional[Callable] = None, merge_fn: Optional[Callable] = None, improve_fn: Optional[Callable] = None,
-                          clip_fn: Optional[Callable] = None) -> Tuple[bytes, dict]:
+                          clip_fn: Optional[Callable] = None, simplify_fn: Optional[Callable] = None) -> Tuple[bytes, dict]:
     """The stream of an SVG text (or of a parsed SegmentTable).  Device steps, each None = the GPU (there is no CPU path in the product):
       flatten_fn(table, tol_raw) -> paths          orip_svg_flatten      (`paths` is whatever the other steps take: on the GPU a count, the points stay there)
       bbox_fn(paths) -> (min x, min y, max x, max y)   orip_svg_bbox
@@ -779,6 +786,8 @@ def build_stream_from_svg(text: Union[str, bytes, SegmentTable], opts: Optional[
       improve_fn                                   as in orip.gcode.build_stream_from_gcode
     and, only with --clip, in the place of steps_fn (hatch lines are cut like any path, and their pens still come through the sources):
       clip_fn(paths, map, rect) -> (off, pts int32, stats)   orip_gcode_to_steps_clip without pointers
+    and, only with --simplify-mm:
+      simplify_fn                                  as in orip.gcode.build_stream_from_gcode (a hatch line has two points and passes through untouched)
     With --pen-colors, info["path_pens"] is the pen of every fitted path (hatch lines included, --color-index where no stroke is stated).
     Returns (bytes, info)."""
     import time
@@ -793,6 +802,7 @@ def build_stream_from_svg(text: Union[str, bytes, SegmentTable], opts: Optional[
     tm["parse_svg"] = tm.get("parse_svg", 0.0) + (time.perf_counter() - t0)
     go = gcode_options(o)
     GC.clip_rect(go)
+    GC.simplify_tol4(go)
     GC.apply_speed_scale(GC.GcodeOptions(speed_scale=go.speed_scale))
     tolerance_mm(o)
     info = {"segments": table.n_seg, "subpaths": table.n_sub, "canvas_height": table.canvas_height}
@@ -805,11 +815,13 @@ def build_stream_from_svg(text: Union[str, bytes, SegmentTable], opts: Optional[
     convert_fn = clip_fn if o.clip else steps_fn
     if any(f is None for f in (flatten_fn, bbox_fn, fit_fn, fetch_fn, convert_fn, order_fn, codes_fn, pack_fn)) or (hp and hatch_fn is None) or \
             ((pens_on or o.allow_reverse) and (source_fn is None or order_pens_fn is None)) or (pens_on and hp and hatch_groups_fn is None) or \
-            (o.merge_paths and merge_fn is None) or (o.improve_order and improve_fn is None):
+            (o.merge_paths and merge_fn is None) or (o.improve_order and improve_fn is None) or (o.simplify_mm is not None and simplify_fn is None):
         if device is None:
             from .stages import device as _default_device
             device = _default_device()
         R = _Resident(device)
+        if simplify_fn is None:                             # likewise, where this device's merge or (without one) its conversion left them
+            simplify_fn = R.simplify if (merge_fn is None if o.merge_paths else convert_fn is None) else device.gcode_simplify
         if merge_fn is None:                                # where the conversion ran on this device its polylines are merged in place, else they are sent
             merge_fn = R.merge if convert_fn is None else device.gcode_merge
         flatten_fn = flatten_fn or R.flatten; bbox_fn = bbox_fn or R.bbox; fit_fn = fit_fn or R.fit; fetch_fn = fetch_fn or R.fetch; steps_fn = steps_fn or R.steps
@@ -832,7 +844,7 @@ def build_stream_from_svg(text: Union[str, bytes, SegmentTable], opts: Optional[
     tm["fetch_paths"] = tm.get("fetch_paths", 0.0) + (time.perf_counter() - t0)
     data, ginfo = GC.build_stream_from_gcode((off_mm, np.zeros((int(off_mm[-1]), 2))), go, device, steps_fn=lambda _off, _pts, m: steps_fn(paths, m), order_fn=order_fn,
                                              codes_fn=codes_fn, pack_fn=pack_fn, timings=tm, pens=pens, order_pens_fn=order_pens_fn, source_fn=source_fn, merge_fn=merge_fn,
-                                             improve_fn=improve_fn, clip_fn=lambda _off, _pts, m, rect: clip_fn(paths, m, rect))
+                                             improve_fn=improve_fn, clip_fn=lambda _off, _pts, m, rect: clip_fn(paths, m, rect), simplify_fn=simplify_fn)
     return data, dict(ginfo, **info)
 
 
@@ -892,6 +904,8 @@ def build_stream_argparser() -> argparse.ArgumentParser:
     ap.add_argument("--clip", action="store_true", help="cut the strokes at the edge of the sheet and lift the pen outside it, instead of clamping every point onto the edge; "
                                                         "the G-code file is not changed")
     ap.add_argument("--clip-margin-mm", type=float, default=None, help="cut this far inside the edge of the sheet (default: 0); needs --clip")
+    ap.add_argument("--simplify-mm", type=float, default=None, help="drop the vertices that lie within this distance of the stroke (Ramer-Douglas-Peucker on the step grid; "
+                    "0: only vertices on the straight line between their neighbours)")
     ap.add_argument("--no-preview", action="store_true", help="do not render <svg stem>_stream_preview.png")
     ap.add_argument("--preview-render-width", type=int, default=d.preview_render_width)
     ap.add_argument("--preview-render-height", type=int, default=d.preview_render_height)
@@ -966,6 +980,8 @@ def main_stream(argv: Optional[Sequence[str]] = None, **device_steps) -> None:
               f"; {info['pens']['unmatched']} without a stroke colour, {info['pens']['reversed']} strokes reversed")
     if "merge" in info:
         print("[svg] merge: {paths_in} paths -> {paths_out}, {joins} pen lifts saved, {cycles} closed".format(**info["merge"]))
+    if "simplify" in info:
+        print(GC.simplify_line("svg", info["simplify"]))
     if "improve" in info:
         print(GC.improve_line("svg", info["improve"]))
     print(f"[svg] G-code saved: {gcode_path}")

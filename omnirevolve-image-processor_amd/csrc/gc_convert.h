@@ -1,6 +1,6 @@
 // csrc/gc_convert.h -- what the gcode units share.  The arithmetic of mm_to_steps (gcode2stream.py :79-110) up to the rounding, stated once for the two
 // conversions that must agree in every bit: orip_gcode_to_steps (gcode.hip), which then clamps to the sheet, and orip_gcode_to_steps_clip (gcode_clip.hip),
-// which cuts there instead; the path of a point; the check of an offsets array.
+// which cuts there instead; the path of a point; the host side of the resident step polylines: the intake of both input forms, the hand-over, the orders' checks.
 #pragma once
 #include "orip_ctx.h"
 
@@ -23,9 +23,19 @@ __device__ __forceinline__ int64_t gc_path_of(const long long* __restrict__ off,
     return lo;
 }
 
-// the offsets of n explicit paths: off[0] == 0, nowhere decreasing; the message names the entry point `who`
-static inline int gc_check_offsets(orip_ctx* c, const char* who, const int64_t* off, int64_t n) {
-    if (off[0] != 0) ORIP_FAIL_AS(c, who, "offsets must start at 0");
-    for (int64_t p = 0; p < n; p++) if (off[p + 1] < off[p]) ORIP_FAIL_AS(c, who, "offsets must not decrease (path %lld)", (long long)p);
-    return 0;
-}
+// ---- host helpers, defined in gcode.hip; `who` is the entry point's __func__, which every message names.  orip_ctx.h states the contract they keep
+// mm paths, explicit or (off == pts_mm == NULL, n > 0) the n fitted paths of svg.hip: the form (others_ok: the entry point's own pointers), the resident
+// count, the map, fewer than 2^30 paths, the offsets; then, behind the caller's Carve of d_off[n + 1] and d_mm[total] (0 of each when resident), the upload
+int gc_mm_check(orip_ctx* c, const char* who, const int64_t* off, const double* pts_mm, int64_t n, const orip_gcode_map* map, bool others_ok, bool& resident, int64_t& total);
+int gc_mm_upload(orip_ctx* c, const char* who, const int64_t* off, const double* pts_mm, int64_t n, int64_t total, bool resident, long long*& d_off, double2*& d_mm);
+// step polylines, explicit or (off == pts == NULL) the n resident ones, at most 2^26: every check of the form, no state touched (no_repeats: no point equals
+// the one before it); then the upload that makes a checked explicit input the resident list.  gc_merged is the caller's, here and below
+int gc_steps_check(orip_ctx* c, const char* who, const int64_t* off, const int32_t* pts, int64_t n, bool no_repeats, int64_t& total);
+int gc_steps_upload(orip_ctx* c, const char* who, const int64_t* off, const int32_t* pts, int64_t n, int64_t total);
+void gc_drop(orip_ctx* c);                                                              // no list: every reader fails until a writer succeeds
+int gc_publish_empty(orip_ctx* c, const char* who);                                     // the list of no polylines
+void gc_publish(orip_ctx* c, DBuf& off, DBuf& pts, int64_t n, int64_t total);           // a result in (off, pts) becomes the list: the buffers are swapped
+// the orders' checks: n polylines resident; n_groups in 1..64 and every path's group in range, counted into paths[] when given; the start point
+int gc_check_resident(orip_ctx* c, const char* who, int64_t n);
+int gc_check_groups(orip_ctx* c, const char* who, const int32_t* group, int64_t n, int32_t n_groups, int64_t* paths);
+int gc_check_start(orip_ctx* c, const char* who, const int32_t* start_xy, int& sx, int& sy);

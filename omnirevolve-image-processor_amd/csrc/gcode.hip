@@ -62,24 +62,84 @@ __global__ __launch_bounds__(256) void k_gc_emit(const long long* __restrict__ o
 }
 }  // namespace
 
+// ------------------------------------------------------------------------------------------------ the resident list's host side (gc_convert.h)
+static int gc_check_offsets(orip_ctx* c, const char* who, const int64_t* off, int64_t n) {
+    if (off[0] != 0) ORIP_FAIL_AS(c, who, "offsets must start at 0");
+    for (int64_t p = 0; p < n; p++) if (off[p + 1] < off[p]) ORIP_FAIL_AS(c, who, "offsets must not decrease (path %lld)", (long long)p);
+    return 0;
+}
+int gc_mm_check(orip_ctx* c, const char* who, const int64_t* off, const double* pts_mm, int64_t n, const orip_gcode_map* map, bool others_ok, bool& resident, int64_t& total) {
+    resident = !off && !pts_mm && n > 0;                    // the fitted paths orip_svg_flatten / orip_svg_fit left on the device (svg.hip)
+    if (!map || !others_ok || n < 0 || (n > 0 && !off && !resident)) ORIP_FAIL_AS(c, who, "bad arguments");
+    if (resident && (!c->sv_ready || n != c->sv_n)) ORIP_FAIL_AS(c, who, "%lld paths asked for, %lld fitted paths resident", (long long)n, (long long)(c->sv_ready ? c->sv_n : -1));
+    if (map->W < 1 || map->H < 1 || map->W > GC_COORD_MAX || map->H > GC_COORD_MAX)
+        ORIP_FAIL_AS(c, who, "target size %d x %d steps: each side must be in 1..2^30 (step coordinates are int32 on the device)", map->W, map->H);
+    if (n >= INT32_MAX / 2) ORIP_FAIL_AS(c, who, "%lld paths: at most 2^30", (long long)n);         // before off[n] is looked at
+    total = resident ? c->sv_total : n > 0 ? off[n] : 0;
+    if (!resident && n > 0) ORIP_TRY(gc_check_offsets(c, who, off, n));
+    if (total > 0 && !pts_mm && !resident) ORIP_FAIL_AS(c, who, "bad arguments");
+    return 0;
+}
+int gc_mm_upload(orip_ctx* c, const char* who, const int64_t* off, const double* pts_mm, int64_t n, int64_t total, bool resident, long long*& d_off, double2*& d_mm) {
+    if (resident) { d_off = c->sv_off.as<long long>(); d_mm = c->sv_pts.as<double2>(); return 0; }
+    HIPC_AS(c, who, hipMemcpyAsync(d_off, off, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, LN(c).stream));
+    HIPC_AS(c, who, hipMemcpyAsync(d_mm, pts_mm, (size_t)total * 16, hipMemcpyHostToDevice, LN(c).stream));
+    return 0;
+}
+int gc_steps_check(orip_ctx* c, const char* who, const int64_t* off, const int32_t* pts, int64_t n, bool no_repeats, int64_t& total) {
+    if (n < 0 || n > (1 << 26)) ORIP_FAIL_AS(c, who, "%lld paths: 0..2^26", (long long)n);
+    if (!off != !pts) ORIP_FAIL_AS(c, who, "off and pts: both or neither");
+    if (!off) { total = c->gc_total; return gc_check_resident(c, who, n); }
+    ORIP_TRY(gc_check_offsets(c, who, off, n));
+    for (int64_t p = 0; p < n; p++) if (off[p + 1] - off[p] < 2) ORIP_FAIL_AS(c, who, "path %lld has fewer than two points", (long long)p);
+    total = off[n];
+    if (total >= (int64_t)1 << 30) ORIP_FAIL_AS(c, who, "%lld points: fewer than 2^30", (long long)total);
+    for (int64_t i = 0; i < 2 * total; i++) if (pts[i] < 0 || pts[i] > GC_COORD_MAX) ORIP_FAIL_AS(c, who, "point %lld: coordinate %d outside 0..2^30", (long long)(i / 2), pts[i]);
+    for (int64_t p = 0; no_repeats && p < n; p++)
+        for (int64_t i = off[p] + 1; i < off[p + 1]; i++)
+            if (pts[2 * i] == pts[2 * i - 2] && pts[2 * i + 1] == pts[2 * i - 1]) ORIP_FAIL_AS(c, who, "path %lld: point %lld equals the point before it", (long long)p, (long long)i);
+    return 0;
+}
+int gc_steps_upload(orip_ctx* c, const char* who, const int64_t* off, const int32_t* pts, int64_t n, int64_t total) {
+    c->gc_ready = false;
+    HIPC_AS(c, who, c->gc_off.ensure((size_t)(n + 1) * 8 + 64)); HIPC_AS(c, who, c->gc_pts.ensure((size_t)total * 8 + 64));
+    HIPC_AS(c, who, hipMemcpyAsync(c->gc_off.p, off, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, LN(c).stream));
+    if (total) HIPC_AS(c, who, hipMemcpyAsync(c->gc_pts.p, pts, (size_t)total * 8, hipMemcpyHostToDevice, LN(c).stream));
+    c->gc_n = n; c->gc_total = total; c->gc_ready = true;
+    return 0;
+}
+void gc_drop(orip_ctx* c) { c->gc_n = 0; c->gc_total = 0; c->gc_ready = false; c->gc_merged = false; }
+int gc_publish_empty(orip_ctx* c, const char* who) { static const int64_t zero = 0; return gc_steps_upload(c, who, &zero, nullptr, 0, 0); }
+void gc_publish(orip_ctx* c, DBuf& off, DBuf& pts, int64_t n, int64_t total) { std::swap(c->gc_off, off); std::swap(c->gc_pts, pts); c->gc_n = n; c->gc_total = total; }
+int gc_check_resident(orip_ctx* c, const char* who, int64_t n) {
+    if (!c->gc_ready || n != c->gc_n) ORIP_FAIL_AS(c, who, "%lld paths asked for, %lld step polylines resident", (long long)n, (long long)(c->gc_ready ? c->gc_n : -1));
+    return 0;
+}
+int gc_check_groups(orip_ctx* c, const char* who, const int32_t* group, int64_t n, int32_t n_groups, int64_t* paths) {
+    if (n_groups < 1 || n_groups > ORIP_ORDER_MAX_GROUPS) ORIP_FAIL_AS(c, who, "%d groups: 1..%d", n_groups, ORIP_ORDER_MAX_GROUPS);
+    for (int64_t p = 0; group && p < n; p++) {
+        if (group[p] < 0 || group[p] >= n_groups) ORIP_FAIL_AS(c, who, "path %lld: group %d of %d", (long long)p, group[p], n_groups);
+        if (paths) paths[group[p]]++;
+    }
+    return 0;
+}
+int gc_check_start(orip_ctx* c, const char* who, const int32_t* start_xy, int& sx, int& sy) {
+    sx = start_xy ? start_xy[0] : 0; sy = start_xy ? start_xy[1] : 0;
+    if (sx < 0 || sy < 0 || sx > GC_COORD_MAX || sy > GC_COORD_MAX) ORIP_FAIL_AS(c, who, "start (%d, %d) outside 0..2^30", sx, sy);
+    return 0;
+}
+
 // mm paths -> resident step polylines; *n_out paths with *total_out points remain.  off == NULL and pts_mm == NULL: the n resident fitted paths of svg.hip
 extern "C" int orip_gcode_to_steps(orip_ctx* c, const int64_t* off, const double* pts_mm, int64_t n, const orip_gcode_map* map, int64_t* n_out, int64_t* total_out) {
     orip_enter(c);
     ORIP_LANE(c, ORIP_LANE_CROSS);
-    c->gc_n = 0; c->gc_total = 0; c->gc_ready = false; c->gc_merged = false;
-    const bool resident = !off && !pts_mm && n > 0;         // the fitted paths orip_svg_flatten / orip_svg_fit left on the device (svg.hip)
-    if (!map || !n_out || !total_out || n < 0 || (n > 0 && !off && !resident)) ORIP_FAIL(c, "bad arguments");
+    gc_drop(c);                                             // the one writer that drops the list before it looks at its arguments
+    bool resident; int64_t total;
+    ORIP_TRY(gc_mm_check(c, __func__, off, pts_mm, n, map, n_out && total_out, resident, total));
     *n_out = 0; *total_out = 0;
-    if (resident && (!c->sv_ready || n != c->sv_n)) ORIP_FAIL(c, "%lld paths asked for, %lld fitted paths resident", (long long)n, (long long)(c->sv_ready ? c->sv_n : -1));
-    if (map->W < 1 || map->H < 1 || map->W > GC_COORD_MAX || map->H > GC_COORD_MAX)
-        ORIP_FAIL(c, "target size %d x %d steps: each side must be in 1..2^30 (step coordinates are int32 on the device)", map->W, map->H);
-    const int64_t total = resident ? c->sv_total : n > 0 ? off[n] : 0;
-    if (!resident && n > 0) ORIP_TRY(gc_check_offsets(c, __func__, off, n));
-    if (n >= INT32_MAX / 2 || total >= INT32_MAX / 2) ORIP_FAIL(c, "%lld paths, %lld points: at most 2^30 of each", (long long)n, (long long)total);
-    if (total > 0 && !pts_mm && !resident) ORIP_FAIL(c, "bad arguments");
+    if (total >= INT32_MAX / 2) ORIP_FAIL(c, "%lld paths, %lld points: at most 2^30 of each", (long long)n, (long long)total);
+    if (total == 0) return gc_publish_empty(c, __func__);
     hipStream_t s = LN(c).stream;
-    HIPC(c, c->gc_off.ensure(64)); HIPC(c, hipMemsetAsync(c->gc_off.p, 0, 8, s));
-    if (total == 0) { HIPC(c, hipStreamSynchronize(s)); c->gc_ready = true; return 0; }
     long long* d_off; double2* d_mm; int2* xy; unsigned *keep, *kpos, *pid, *pc, *pk, *noff, *nidx; int* err;
     Carve L;
     L.take(d_off, resident ? 0 : (size_t)n + 1); L.take(d_mm, resident ? 0 : (size_t)total); L.take(xy, (size_t)total); L.take(keep, (size_t)total + 1); L.take(kpos, (size_t)total + 1);
@@ -88,11 +148,7 @@ extern "C" int orip_gcode_to_steps(orip_ctx* c, const int64_t* off, const double
     HIPC(c, c->gc_off.ensure((size_t)(n + 1) * 8 + 64)); HIPC(c, c->gc_pts.ensure((size_t)total * 8 + 64));     // the output is never larger than the input
     HIPC(c, c->gc_src.ensure((size_t)n * 4 + 64));
     HIPC(c, hipMemsetAsync(c->gc_off.p, 0, 8, s));
-    if (resident) { d_off = c->sv_off.as<long long>(); d_mm = c->sv_pts.as<double2>(); }
-    else {
-        HIPC(c, hipMemcpyAsync(d_off, off, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, s));
-        HIPC(c, hipMemcpyAsync(d_mm, pts_mm, (size_t)total * 16, hipMemcpyHostToDevice, s));
-    }
+    ORIP_TRY(gc_mm_upload(c, __func__, off, pts_mm, n, total, resident, d_off, d_mm));
     HIPC(c, hipMemsetAsync(err, 0, 4, s));
     { ProfScope ps(c, "k_gc_points");
       hipLaunchKernelGGL(k_gc_points, dim3(cdiv(total + 1, 256)), dim3(256), 0, s, d_off, n, d_mm, total, *map, xy, keep, pid, err); }

@@ -26,13 +26,12 @@
 //
 // Scratch in c->gc_tmp, free between calls: off long long[n + 1] and mm double2[total] (explicit form only), ab int4[total] = (A, B), cs and scan
 // unsigned long long[total + 1], sstart unsigned[total + 1], ps and pscan unsigned long long[total + 1] = (points << 32 | kept) per stroke, ClCounters.
-// Resident afterwards, as after orip_gcode_to_steps: c->gc_off, c->gc_pts, c->gc_src; gc_merged cleared.
+// Resident afterwards, as after orip_gcode_to_steps: c->gc_off, c->gc_pts, c->gc_src (orip_ctx.h states the contract; this writer checks before it drops).
 #include "orip_ctx.h"
 #include "gc_convert.h"
 #include <rocprim/rocprim.hpp>
 
 namespace {
-constexpr int CL_COORD_MAX = 1 << 30;
 constexpr int CL_ERR_NOT_FINITE = 1, CL_ERR_RANGE = 2;
 struct ClCounters { unsigned long long inside, cut, outside; int err; };
 struct ClRect { int x0, y0, x1, y1; };
@@ -67,7 +66,7 @@ __device__ __forceinline__ int cl_convert(const orip_gcode_map& g, double2 mm, i
     double xf, yf;
     o = make_int2(0, 0);
     if (!gc_round_mm(g, mm.x, mm.y, xf, yf)) return CL_ERR_NOT_FINITE;
-    const double top = (double)CL_COORD_MAX;
+    const double top = (double)GC_COORD_MAX;
     if (xf < -top || xf > top || yf < -top || yf > top) return CL_ERR_RANGE;
     o = make_int2((int)xf, (int)yf);
     return 0;
@@ -172,25 +171,16 @@ extern "C" int orip_gcode_to_steps_clip(orip_ctx* c, const int64_t* off, const d
                                         int64_t* total_out, int64_t* stats) {
     orip_enter(c);
     ORIP_LANE(c, ORIP_LANE_CROSS);
-    const bool resident = !off && !pts_mm && n > 0;         // the fitted paths orip_svg_flatten / orip_svg_fit left on the device (svg.hip)
-    if (!map || !n_out || !total_out || !stats || !rect || n < 0 || (n > 0 && !off && !resident)) ORIP_FAIL(c, "bad arguments");
-    if (resident && (!c->sv_ready || n != c->sv_n)) ORIP_FAIL(c, "%lld paths asked for, %lld fitted paths resident", (long long)n, (long long)(c->sv_ready ? c->sv_n : -1));
-    if (map->W < 1 || map->H < 1 || map->W > CL_COORD_MAX || map->H > CL_COORD_MAX)
-        ORIP_FAIL(c, "target size %d x %d steps: each side must be in 1..2^30 (step coordinates are int32 on the device)", map->W, map->H);
+    bool resident; int64_t total;
+    ORIP_TRY(gc_mm_check(c, __func__, off, pts_mm, n, map, n_out && total_out && stats && rect, resident, total));
     if (rect[0] < 0 || rect[1] < 0 || rect[0] > rect[2] || rect[1] > rect[3] || rect[2] > map->W - 1 || rect[3] > map->H - 1)
         ORIP_FAIL(c, "clip rectangle [%d, %d] x [%d, %d]: must be 0 <= x0 <= x1 <= %d, 0 <= y0 <= y1 <= %d", rect[0], rect[2], rect[1], rect[3], map->W - 1, map->H - 1);
-    if (n >= INT32_MAX / 2) ORIP_FAIL(c, "%lld paths: at most 2^30", (long long)n);                  // before off[n] is looked at
-    const int64_t total = resident ? c->sv_total : n > 0 ? off[n] : 0;
-    if (!resident && n > 0) ORIP_TRY(gc_check_offsets(c, __func__, off, n));
     if (total >= (int64_t)1 << 29) ORIP_FAIL(c, "%lld points: fewer than 2^29 (a cut can double the points)", (long long)total);
-    if (total > 0 && !pts_mm && !resident) ORIP_FAIL(c, "bad arguments");
-    // checked: from here on the resident step polylines are this call's
-    c->gc_n = 0; c->gc_total = 0; c->gc_ready = false; c->gc_merged = false;
+    gc_drop(c);                                                               // checked: from here on the resident step polylines are this call's
     *n_out = 0; *total_out = 0;
     for (int k = 0; k < 6; k++) stats[k] = 0;
+    if (total == 0) return gc_publish_empty(c, __func__);
     hipStream_t s = LN(c).stream;
-    HIPC(c, c->gc_off.ensure(64)); HIPC(c, hipMemsetAsync(c->gc_off.p, 0, 8, s));
-    if (total == 0) { HIPC(c, hipStreamSynchronize(s)); c->gc_ready = true; return 0; }
     long long* d_off; double2* d_mm; int4* ab; u64 *cs, *scan, *ps, *pscan; unsigned* sstart; ClCounters* cn;
     Carve L;
     L.take(d_off, resident ? 0 : (size_t)n + 1); L.take(d_mm, resident ? 0 : (size_t)total); L.take(ab, (size_t)total); L.take(cs, (size_t)total + 1); L.take(scan, (size_t)total + 1);
@@ -200,11 +190,7 @@ extern "C" int orip_gcode_to_steps_clip(orip_ctx* c, const int64_t* off, const d
     const int64_t cap_pts = 2 * total;
     HIPC(c, c->gc_off.ensure((size_t)(total + 1) * 8 + 64)); HIPC(c, c->gc_pts.ensure((size_t)cap_pts * 8 + 64)); HIPC(c, c->gc_src.ensure((size_t)total * 4 + 64));
     HIPC(c, hipMemsetAsync(c->gc_off.p, 0, 8, s));
-    if (resident) { d_off = c->sv_off.as<long long>(); d_mm = c->sv_pts.as<double2>(); }
-    else {
-        HIPC(c, hipMemcpyAsync(d_off, off, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, s));
-        HIPC(c, hipMemcpyAsync(d_mm, pts_mm, (size_t)total * 16, hipMemcpyHostToDevice, s));
-    }
+    ORIP_TRY(gc_mm_upload(c, __func__, off, pts_mm, n, total, resident, d_off, d_mm));
     HIPC(c, hipMemsetAsync(cn, 0, sizeof(ClCounters), s));
     HIPC(c, hipMemsetAsync(sstart, 0xFF, ((size_t)total + 1) * 4, s));          // an entry nobody writes fails every bound check
     const ClRect R = {rect[0], rect[1], rect[2], rect[3]};

@@ -28,9 +28,9 @@
 // Scratch, free between calls: c->im_state = se int4[n] (the ends, uploaded or taken from the resident polylines), ord int[n], rv u8[n] (the given sequence),
 // ab int4[2][n], id int[2][n]; c->im_rec = ImRec[IM_MAX_REC], ImStatus[2], travel u64[2].
 #include "orip_ctx.h"
+#include "gc_convert.h"
 
 namespace {
-constexpr int IM_COORD_MAX = 1 << 30;
 constexpr int IM_BATCH = 32;                       // rounds between two looks at the status word
 constexpr int IM_TILE = 256;                       // gaps staged at a time = threads of a block
 constexpr int IM_BLOCKS = 2048;                    // blocks k_im_eval aims for: 8 per CU
@@ -213,21 +213,18 @@ extern "C" int orip_gcode_improve(orip_ctx* c, const int32_t* ends, const int32_
     ORIP_LANE(c, ORIP_LANE_CROSS);
     if (!stats) ORIP_FAIL(c, "bad arguments");
     if (n < 0 || (n > 0 && (!group || !order || !rev)) || (flags & ~ORIP_ORDER_REVERSE)) ORIP_FAIL(c, "bad arguments");
-    if (n_groups < 1 || n_groups > ORIP_ORDER_MAX_GROUPS) ORIP_FAIL(c, "%d groups: 1..%d", n_groups, ORIP_ORDER_MAX_GROUPS);
-    const int sx = start_xy ? start_xy[0] : 0, sy = start_xy ? start_xy[1] : 0;
-    if (sx < 0 || sy < 0 || sx > IM_COORD_MAX || sy > IM_COORD_MAX) ORIP_FAIL(c, "start (%d, %d) outside 0..2^30", sx, sy);
+    int sx, sy;
+    ORIP_TRY(gc_check_groups(c, __func__, nullptr, 0, n_groups, nullptr));
+    ORIP_TRY(gc_check_start(c, __func__, start_xy, sx, sy));
     if (max_rounds < 0) ORIP_FAIL(c, "%lld rounds: 0 or more, or ORIP_IMPROVE_ROUNDS_AUTO", (long long)max_rounds);
     for (int k = 0; k < 5; k++) stats[k] = 0;
     if (n == 0) return 0;
-    if (!ends && (!c->gc_ready || n != c->gc_n)) ORIP_FAIL(c, "%lld paths asked for, %lld step polylines resident", (long long)n, (long long)(c->gc_ready ? c->gc_n : -1));
+    if (!ends) ORIP_TRY(gc_check_resident(c, __func__, n));
     if (n > (1 << 26)) ORIP_FAIL(c, "%lld paths: at most 2^26", (long long)n);
     int64_t paths[ORIP_ORDER_MAX_GROUPS] = {0};
-    for (int64_t i = 0; i < n; i++) {
-        if (group[i] < 0 || group[i] >= n_groups) ORIP_FAIL(c, "path %lld: group %d of %d", (long long)i, group[i], n_groups);
-        paths[group[i]]++;
-    }
+    ORIP_TRY(gc_check_groups(c, __func__, group, n, n_groups, paths));
     if (ends)
-        for (int64_t i = 0; i < 4 * n; i++) if (ends[i] < 0 || ends[i] > IM_COORD_MAX) ORIP_FAIL(c, "path %lld: coordinate %d outside 0..2^30", (long long)(i / 4), ends[i]);
+        for (int64_t i = 0; i < 4 * n; i++) if (ends[i] < 0 || ends[i] > GC_COORD_MAX) ORIP_FAIL(c, "path %lld: coordinate %d outside 0..2^30", (long long)(i / 4), ends[i]);
     const int reverse = flags & ORIP_ORDER_REVERSE ? 1 : 0;
     {   // the sequence: a permutation whose groups do not decrease, directions only with the flag
         std::vector<uint8_t> seen((size_t)n, 0);

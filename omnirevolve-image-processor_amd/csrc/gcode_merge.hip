@@ -32,14 +32,12 @@
 // Scratch, free between calls.  c->mg_tab (nodes): E int4[2n] = (x, y, group, 0) per end; slot int[T]; own int[2n]; cnt unsigned[2n]; arr int[4n]; grp int[n].
 // c->mg_tmp (chains): succ0 int[2n]; JA, JB int4[2n]; cyc u8[2n]; head unsigned[3][n + 1] = (is lowest, chain points, chain members) and scan unsigned[3][n + 1]
 // = their exclusive scans; place int2[n] = (first output point, 1 reversed | 2 first point dropped); MgCounters.
-// Resident: the merged polylines in c->gc_off / c->gc_pts (swapped with c->mg_off / c->mg_pts), member_off / member / rev in c->mg_res until the next merge.
+// Resident: the merged polylines (gc_publish; orip_ctx.h states the list's contract and this writer's gc_merged rule), member_off / member / rev in c->mg_res until the next merge.
 #include "orip_ctx.h"
 #include "gc_convert.h"
 #include <rocprim/rocprim.hpp>
 
 namespace {
-constexpr int MG_COORD_MAX = 1 << 30;
-constexpr int64_t MG_MAX_PATHS = 1 << 26;
 struct MgCounters { unsigned cycles, bad; };
 
 __device__ __forceinline__ unsigned mg_hash(const int4 e) {
@@ -184,27 +182,13 @@ extern "C" int orip_gcode_merge(orip_ctx* c, const int64_t* off, const int32_t* 
     ORIP_LANE(c, ORIP_LANE_CROSS);
     if (!stats) ORIP_FAIL(c, "bad arguments");
     if (flags & ~ORIP_MERGE_REVERSE) ORIP_FAIL(c, "unknown flags %d", flags);
-    if (n_groups < 1 || n_groups > ORIP_ORDER_MAX_GROUPS) ORIP_FAIL(c, "%d groups: 1..%d", n_groups, ORIP_ORDER_MAX_GROUPS);
-    if (n < 0 || n > MG_MAX_PATHS) ORIP_FAIL(c, "%lld paths: 0..2^26", (long long)n);
-    if (!off != !pts) ORIP_FAIL(c, "off and pts: both or neither");
-    const bool resident = !off;
-    if (resident && (!c->gc_ready || n != c->gc_n)) ORIP_FAIL(c, "%lld paths asked for, %lld step polylines resident", (long long)n, (long long)(c->gc_ready ? c->gc_n : -1));
-    int64_t total = resident ? c->gc_total : 0;
-    if (!resident) {
-        ORIP_TRY(gc_check_offsets(c, __func__, off, n));
-        for (int64_t p = 0; p < n; p++) if (off[p + 1] - off[p] < 2) ORIP_FAIL(c, "path %lld has fewer than two points", (long long)p);
-        total = off[n];
-        if (total >= (int64_t)1 << 30) ORIP_FAIL(c, "%lld points: fewer than 2^30", (long long)total);
-        for (int64_t i = 0; i < 2 * total; i++) if (pts[i] < 0 || pts[i] > MG_COORD_MAX) ORIP_FAIL(c, "point %lld: coordinate %d outside 0..2^30", (long long)(i / 2), pts[i]);
-    }
-    if (group) for (int64_t p = 0; p < n; p++) if (group[p] < 0 || group[p] >= n_groups) ORIP_FAIL(c, "path %lld: group %d of %d", (long long)p, group[p], n_groups);
+    int64_t total;
+    ORIP_TRY(gc_steps_check(c, __func__, off, pts, n, false, total));
+    ORIP_TRY(gc_check_groups(c, __func__, group, n, n_groups, nullptr));
     hipStream_t s = LN(c).stream;
     stats[0] = stats[1] = stats[2] = stats[3] = 0;
     if (n == 0) {                                                             // nothing to launch; the explicit form leaves the empty list resident
-        if (!resident) {
-            HIPC(c, c->gc_off.ensure(64)); HIPC(c, hipMemsetAsync(c->gc_off.p, 0, 8, s)); HIPC(c, hipStreamSynchronize(s));
-            c->gc_n = 0; c->gc_total = 0; c->gc_ready = true;
-        }
+        if (off) ORIP_TRY(gc_publish_empty(c, __func__));
         c->gc_merged = true; c->mg_n = 0; c->mg_paths = 0;
         return 0;
     }
@@ -220,13 +204,7 @@ extern "C" int orip_gcode_merge(orip_ctx* c, const int64_t* off, const int32_t* 
     long long* r_moff; int* r_member; uint8_t* r_rev;
     { Carve L; L.take(r_moff, (size_t)N + 1); L.take(r_member, (size_t)N); L.take(r_rev, (size_t)N); HIPC(c, L.commit(c->mg_res, 64)); }
     c->mg_n = -1;
-    if (!resident) {                                                          // checked above: from here on the input is the resident list
-        c->gc_ready = false;
-        HIPC(c, c->gc_off.ensure(((size_t)N + 1) * 8 + 64)); HIPC(c, c->gc_pts.ensure((size_t)total * 8 + 64));
-        HIPC(c, hipMemcpyAsync(c->gc_off.p, off, ((size_t)N + 1) * 8, hipMemcpyHostToDevice, s));
-        HIPC(c, hipMemcpyAsync(c->gc_pts.p, pts, (size_t)total * 8, hipMemcpyHostToDevice, s));
-        c->gc_n = n; c->gc_total = total; c->gc_ready = true;
-    }
+    if (off) ORIP_TRY(gc_steps_upload(c, __func__, off, pts, n, total));      // checked above: from here on the input is the resident list
     c->gc_merged = true;                                                      // the sources no longer name these polylines
     if (group) HIPC(c, hipMemcpyAsync(grp, group, (size_t)N * 4, hipMemcpyHostToDevice, s));
     else HIPC(c, hipMemsetAsync(grp, 0, (size_t)N * 4, s));
@@ -259,9 +237,8 @@ extern "C" int orip_gcode_merge(orip_ctx* c, const int64_t* off, const int32_t* 
     HIPC(c, hipMemcpyAsync(&h.points, scan + ((size_t)N + 1) + N, 4, hipMemcpyDeviceToHost, s));
     HIPC(c, hipMemcpyAsync(&h.cn, cn, sizeof(MgCounters), hipMemcpyDeviceToHost, s));
     HIPC(c, hipStreamSynchronize(s));                                         // the one sync
-    if (h.cn.bad || h.paths < 1 || h.paths > (unsigned)N || (int64_t)h.points > total) { c->gc_ready = false; ORIP_FAIL(c, "the chains do not add up (internal error)"); }
-    std::swap(c->gc_off, c->mg_off); std::swap(c->gc_pts, c->mg_pts);
-    c->gc_n = h.paths; c->gc_total = h.points;
+    if (h.cn.bad || h.paths < 1 || h.paths > (unsigned)N || (int64_t)h.points > total) { gc_drop(c); ORIP_FAIL(c, "the chains do not add up (internal error)"); }
+    gc_publish(c, c->mg_off, c->mg_pts, h.paths, h.points);
     c->mg_n = n; c->mg_paths = h.paths;
     stats[0] = h.paths; stats[1] = h.points; stats[2] = n - (int64_t)h.paths; stats[3] = h.cn.cycles;
     return 0;

@@ -292,7 +292,7 @@ extern "C" int orip_gcode_order(orip_ctx* c, const int32_t* ends, int64_t n, int
     ORIP_LANE(c, ORIP_LANE_CROSS);
     if (n < 0 || (n > 0 && !order_out)) ORIP_FAIL(c, "bad arguments");
     if (n == 0) return 0;
-    if (!ends && (!c->gc_ready || n != c->gc_n)) ORIP_FAIL(c, "%lld paths asked for, %lld step polylines resident", (long long)n, (long long)(c->gc_ready ? c->gc_n : -1));
+    if (!ends) ORIP_TRY(gc_check_resident(c, __func__, n));
     if (n > (1 << 27)) ORIP_FAIL(c, "%lld paths: at most 2^27", (long long)n);
     GcOrder o;
     ORIP_TRY(gc_grids(c, __func__, ends, nullptr, n, 1, 0, &n, o));
@@ -312,17 +312,14 @@ extern "C" int orip_gcode_order_pens(orip_ctx* c, const int32_t* ends, const int
     orip_enter(c);
     ORIP_LANE(c, ORIP_LANE_CROSS);
     if (n < 0 || (n > 0 && (!group || !order_out || !rev_out)) || (flags & ~ORIP_ORDER_REVERSE)) ORIP_FAIL(c, "bad arguments");
-    if (n_groups < 1 || n_groups > ORIP_ORDER_MAX_GROUPS) ORIP_FAIL(c, "%d groups: 1..%d", n_groups, ORIP_ORDER_MAX_GROUPS);
-    const int sx = start_xy ? start_xy[0] : 0, sy = start_xy ? start_xy[1] : 0;
-    if (sx < 0 || sy < 0 || sx > GC_COORD_MAX || sy > GC_COORD_MAX) ORIP_FAIL(c, "start (%d, %d) outside 0..2^30", sx, sy);
+    int sx, sy;
+    ORIP_TRY(gc_check_groups(c, __func__, nullptr, 0, n_groups, nullptr));
+    ORIP_TRY(gc_check_start(c, __func__, start_xy, sx, sy));
     if (n == 0) return 0;
-    if (!ends && (!c->gc_ready || n != c->gc_n)) ORIP_FAIL(c, "%lld paths asked for, %lld step polylines resident", (long long)n, (long long)(c->gc_ready ? c->gc_n : -1));
+    if (!ends) ORIP_TRY(gc_check_resident(c, __func__, n));
     if (n > (1 << 26)) ORIP_FAIL(c, "%lld paths: at most 2^26", (long long)n);
     int64_t paths[ORIP_ORDER_MAX_GROUPS] = {0};
-    for (int64_t i = 0; i < n; i++) {
-        if (group[i] < 0 || group[i] >= n_groups) ORIP_FAIL(c, "path %lld: group %d of %d", (long long)i, group[i], n_groups);
-        paths[group[i]]++;
-    }
+    ORIP_TRY(gc_check_groups(c, __func__, group, n, n_groups, paths));
     const int rev = flags & ORIP_ORDER_REVERSE ? 1 : 0;
     GcOrder o;
     ORIP_TRY(gc_grids(c, __func__, ends, group, n, n_groups, rev, paths, o));

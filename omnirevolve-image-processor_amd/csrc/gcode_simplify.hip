@@ -25,7 +25,7 @@
 //    per stroke reads the new offset at its first point.
 //
 // Scratch, free between calls.  c->sp_tmp: keep u8[total + 1] (the last one stays 0, so the scan's last word is the output count); pos unsigned[total + 1];
-// list int2[2][cap]; SpState.  Output: c->sp_off / c->sp_pts, swapped with c->gc_off / c->gc_pts when the call succeeds.
+// list int2[2][cap]; SpState.  Output: c->sp_off / c->sp_pts, made the resident list when the call succeeds (gc_publish; orip_ctx.h states the contract).
 // Resident: kept int64[sp_points] in c->sp_res until the next call.
 #include "orip_ctx.h"
 #include "gc_convert.h"
@@ -34,7 +34,6 @@
 #include <climits>
 
 namespace {
-constexpr int64_t SP_MAX_PATHS = 1 << 26;
 constexpr int SP_S = ORIP_SIMPLIFY_LOCAL;           // points a wave finishes alone: SP_WAVES * SP_S * 8 bytes of LDS per block
 constexpr int SP_WAVES = 4;
 constexpr int SP_BLOCKS = 2048;                     // 8 per CU
@@ -204,29 +203,13 @@ extern "C" int orip_gcode_simplify(orip_ctx* c, const int64_t* off, const int32_
     ORIP_LANE(c, ORIP_LANE_CROSS);
     if (!stats) ORIP_FAIL(c, "bad arguments");
     if (tol4 < 0 || tol4 > ORIP_SIMPLIFY_TOL4_MAX) ORIP_FAIL(c, "tolerance %d quarter steps: 0..2^17 - 1", tol4);
-    if (n < 0 || n > SP_MAX_PATHS) ORIP_FAIL(c, "%lld paths: 0..2^26", (long long)n);
-    if (!off != !pts) ORIP_FAIL(c, "off and pts: both or neither");
-    const bool resident = !off;
-    if (resident && (!c->gc_ready || n != c->gc_n)) ORIP_FAIL(c, "%lld paths asked for, %lld step polylines resident", (long long)n, (long long)(c->gc_ready ? c->gc_n : -1));
-    int64_t total = resident ? c->gc_total : 0;
-    if (!resident) {
-        ORIP_TRY(gc_check_offsets(c, __func__, off, n));
-        for (int64_t p = 0; p < n; p++) if (off[p + 1] - off[p] < 2) ORIP_FAIL(c, "path %lld has fewer than two points", (long long)p);
-        total = off[n];
-        if (total >= (int64_t)1 << 30) ORIP_FAIL(c, "%lld points: fewer than 2^30", (long long)total);
-        for (int64_t i = 0; i < 2 * total; i++) if (pts[i] < 0 || pts[i] > GC_COORD_MAX) ORIP_FAIL(c, "point %lld: coordinate %d outside 0..2^30", (long long)(i / 2), pts[i]);
-        for (int64_t p = 0; p < n; p++)
-            for (int64_t i = off[p] + 1; i < off[p + 1]; i++)
-                if (pts[2 * i] == pts[2 * i - 2] && pts[2 * i + 1] == pts[2 * i - 1]) ORIP_FAIL(c, "path %lld: point %lld equals the point before it", (long long)p, (long long)i);
-    }
+    int64_t total;
+    ORIP_TRY(gc_steps_check(c, __func__, off, pts, n, true, total));
     hipStream_t s = LN(c).stream;
     stats[0] = stats[1] = stats[2] = stats[3] = 0;
+    const bool same_count = c->gc_ready && c->gc_n == n;                      // as many as the sources name: taken for the polylines a fetch gave out
     if (n == 0) {                                                             // nothing to launch; the explicit form leaves the empty list resident
-        if (!resident) {
-            HIPC(c, c->gc_off.ensure(64)); HIPC(c, hipMemsetAsync(c->gc_off.p, 0, 8, s)); HIPC(c, hipStreamSynchronize(s));
-            if (!c->gc_ready || c->gc_n != 0) c->gc_merged = true;
-            c->gc_n = 0; c->gc_total = 0; c->gc_ready = true;
-        }
+        if (off) { ORIP_TRY(gc_publish_empty(c, __func__)); if (!same_count) c->gc_merged = true; }
         c->sp_points = 0;
         return 0;
     }
@@ -238,15 +221,8 @@ extern "C" int orip_gcode_simplify(orip_ctx* c, const int64_t* off, const int32_
     HIPC(c, c->sp_off.ensure(((size_t)N + 1) * 8 + 64)); HIPC(c, c->sp_pts.ensure(T * 8 + 64));                   // the output is never larger than the input
     HIPC(c, c->sp_res.ensure(T * 8 + 64));
     c->sp_points = -1;
-    if (!resident) {                                                          // checked above: from here on the input is the resident list
-        const bool same_count = c->gc_ready && c->gc_n == n;                  // as many as the sources name: taken for the polylines a fetch gave out
-        c->gc_ready = false;
-        HIPC(c, c->gc_off.ensure(((size_t)N + 1) * 8 + 64)); HIPC(c, c->gc_pts.ensure(T * 8 + 64));
-        HIPC(c, hipMemcpyAsync(c->gc_off.p, off, ((size_t)N + 1) * 8, hipMemcpyHostToDevice, s));
-        HIPC(c, hipMemcpyAsync(c->gc_pts.p, pts, T * 8, hipMemcpyHostToDevice, s));
-        c->gc_n = n; c->gc_total = total; c->gc_ready = true;
-        if (!same_count) c->gc_merged = true;                                 // the sources do not name these polylines
-    }
+    if (off) ORIP_TRY(gc_steps_upload(c, __func__, off, pts, n, total));      // checked above: from here on the input is the resident list
+    if (off && !same_count) c->gc_merged = true;                              // the sources do not name these polylines
     HIPC(c, hipMemsetAsync(keep, 0, T + 1, s));
     HIPC(c, hipMemsetAsync(st, 0, sizeof(SpState), s));
     const long long* d_off = c->gc_off.as<long long>(); const int2* d_pts = c->gc_pts.as<int2>();
@@ -266,7 +242,7 @@ extern "C" int orip_gcode_simplify(orip_ctx* c, const int64_t* off, const int32_
         HIPC(c, hipMemcpyAsync(&h, st, sizeof(SpState), hipMemcpyDeviceToHost, s));
         HIPC(c, hipStreamSynchronize(s));                                     // one look per batch
     } while (h.cnt[r % 3] != 0 && !h.bad);
-    if (h.bad) { c->gc_ready = false; ORIP_FAIL(c, "the spans do not add up (internal error %u)", h.bad); }
+    if (h.bad) { gc_drop(c); ORIP_FAIL(c, "the spans do not add up (internal error %u)", h.bad); }
     HIPC(c, orip_with_tmp(c, [&](void* tmp, size_t& bytes) {
         return rocprim::exclusive_scan(tmp, bytes, rocprim::make_transform_iterator(keep, SpFlag()), pos, 0u, T + 1, rocprim::plus<unsigned>(), s); }));
     hipLaunchKernelGGL(k_sp_offs, dim3(cdiv((int64_t)N + 1, 256)), b, 0, s, d_off, N, (long long)total, pos, c->sp_off.as<long long>(), st);
@@ -277,9 +253,9 @@ extern "C" int orip_gcode_simplify(orip_ctx* c, const int64_t* off, const int32_
     HIPC(c, hipMemcpyAsync(&points, pos + T, 4, hipMemcpyDeviceToHost, s));
     HIPC(c, hipMemcpyAsync(&h, st, sizeof(SpState), hipMemcpyDeviceToHost, s));
     HIPC(c, hipStreamSynchronize(s));
-    if (h.bad || (int64_t)points > total || (int64_t)points < 2 * n) { c->gc_ready = false; ORIP_FAIL(c, "the kept points do not add up (internal error %u)", h.bad); }
-    std::swap(c->gc_off, c->sp_off); std::swap(c->gc_pts, c->sp_pts);
-    c->gc_total = points; c->sp_points = points;
+    if (h.bad || (int64_t)points > total || (int64_t)points < 2 * n) { gc_drop(c); ORIP_FAIL(c, "the kept points do not add up (internal error %u)", h.bad); }
+    gc_publish(c, c->sp_off, c->sp_pts, n, points);
+    c->sp_points = points;
     stats[0] = n; stats[1] = total; stats[2] = points; stats[3] = h.rounds;
     return 0;
 }

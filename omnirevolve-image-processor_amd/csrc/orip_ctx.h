@@ -43,11 +43,12 @@ typedef uint8_t u8;
     } while (0)
 #define ORIP_FAIL(ctx, ...) ORIP_FAIL_AS(ctx, __func__, __VA_ARGS__)
 
-#define HIPC(ctx, call)                                                                        \
+#define HIPC_AS(ctx, who, call)                                                                \
     do {                                                                                       \
         hipError_t _e = (call);                                                                \
-        if (_e != hipSuccess) ORIP_FAIL(ctx, "%s -> %s", #call, hipGetErrorString(_e));        \
+        if (_e != hipSuccess) ORIP_FAIL_AS(ctx, who, "%s -> %s", #call, hipGetErrorString(_e)); \
     } while (0)
+#define HIPC(ctx, call) HIPC_AS(ctx, __func__, call)
 
 #define ORIP_TRY(expr) do { int _r = (expr); if (_r != 0) return _r; } while (0)
 
@@ -325,9 +326,25 @@ struct orip_ctx {
     DBuf stream_segs, stream_off, stream_codes; int64_t stream_n = 0, stream_total = 0;
     // 14_preview_stream: stream bytes, tile products / prefixes / totals / counters, key plane, RGB image (stream_preview.hip), resident until the fetch
     DBuf sp_data, sp_agg, sp_keys, sp_rgb; int sp_rw = 0, sp_rh = 0; bool sp_ready = false;
-    // gcode2stream (gcode.hip): scratch of the conversion, the resident step polylines (off int64[gc_n + 1], pts int2[gc_total]) between orip_gcode_to_steps and
-    // the fetch / the orders, gc_src int32[gc_n] = the input path every step polyline came from (orip_gcode_steps_source_fetch) next to them; the piece
-    // table and the packed bytes between orip_stream_pack and its fetch (stream.hip)
+    // gcode2stream (gcode.hip): gc_tmp = scratch of the conversions; the piece table and the packed bytes between orip_stream_pack and its fetch (stream.hip).
+    // THE RESIDENT STEP POLYLINES: gc_off int64[gc_n + 1], gc_pts int2[gc_total], valid while gc_ready; gc_src int32[gc_n] = the input path every polyline
+    // came from, which names them while !gc_merged (a field of the merge's line below).  This block is the one statement of their contract; the helpers that
+    // keep it are declared in gc_convert.h and defined in gcode.hip, and no other code writes these fields.
+    //   Readers (fail while !gc_ready, or when the n they are given is not gc_n): orip_gcode_steps_fetch, orip_gcode_steps_source_fetch (also fails while
+    //   gc_merged), and for NULL input orip_gcode_order, orip_gcode_order_pens, orip_gcode_improve, orip_gcode_merge, orip_gcode_simplify.
+    //   Writers, and what each leaves:
+    //     orip_gcode_to_steps       drops the list on entry (gc_drop), before it looks at its arguments: after ANY failure there is no list.  Success: its
+    //                               polylines and their sources, gc_merged cleared; no points to convert (n == 0 included): the empty list (gc_publish_empty).
+    //     orip_gcode_to_steps_clip  checks first: an argument error leaves the list as it was.  Then as orip_gcode_to_steps: dropped, and a device-found
+    //                               error (a coordinate not finite or out of range, counts that do not add up) leaves no list.
+    //     orip_gcode_merge          checks first: an argument error leaves the list as it was.  The explicit form then uploads its input as the list
+    //                               (gc_steps_upload; n == 0: the empty list); the resident form works on the list.  gc_merged is SET in every case that passes
+    //                               the checks, n == 0 in either form included.  Success: the merged polylines (gc_publish swaps mg_off / mg_pts in).
+    //                               A device-found error (chains that do not add up) leaves no list.
+    //     orip_gcode_simplify       as the merge, with sp_off / sp_pts, but strokes keep their number and order, so gc_merged is left as it is -- except that
+    //                               an explicit input of another count than the resident one (or with no list resident) cannot be the polylines the sources
+    //                               name: then, n == 0 included, gc_merged is set.  An explicit input of the resident count is taken for the polylines a fetch gave out.
+    //   A failed HIP call inside a writer leaves what had been written up to it; gc_ready is false across an upload, so a list is never half there.
     DBuf gc_tmp, gc_off, gc_pts, gc_src, pk_tab, pk_out; int64_t gc_n = 0, gc_total = 0, pk_bytes = -1; bool gc_ready = false;
     // orip_gcode_order and orip_gcode_order_pens (gcode_order.hip: gc_grids), free between calls.  With n paths in G groups, m = n or 2n candidates (both ends
     // under ORIP_ORDER_REVERSE) and ncell cells over all groups' grids:
@@ -337,8 +354,7 @@ struct orip_ctx {
     DBuf gc_ends, gc_grid;
     // --merge-paths (gcode_merge.hip): mg_tab / mg_tmp = scratch of the node table and of the chains, free between calls (the unit states their layout);
     // mg_off / mg_pts = the output, swapped with gc_off / gc_pts when a merge succeeds; mg_res = member_off int64[mg_paths + 1], member int32[mg_n],
-    // rev u8[mg_n] of the last merge of mg_n paths (-1: none) until the next one.  gc_merged: the resident step polylines are merged ones, gc_src no
-    // longer names them (cleared by orip_gcode_to_steps)
+    // rev u8[mg_n] of the last merge of mg_n paths (-1: none) until the next one.  gc_merged: gc_src no longer names the resident step polylines (above)
     DBuf mg_tab, mg_tmp, mg_off, mg_pts, mg_res; int64_t mg_n = -1, mg_paths = 0; bool gc_merged = false;
     // --improve-order (gcode_improve.hip), free between calls: im_state = the ends, the given sequence and the two position-ordered copies of the state
     // (ab int4[2][n], id int[2][n]) a move is written between; im_rec = one record per block of the evaluation, the two status slots and the two travels
@@ -346,7 +362,7 @@ struct orip_ctx {
     DBuf im_state, im_rec;
     // --simplify-mm (gcode_simplify.hip): sp_tmp = the keep flags, their scan, the two span lists and the counts, free between calls (the unit states the
     // layout); sp_off / sp_pts = the output, swapped with gc_off / gc_pts when a call succeeds; sp_res = kept int64[sp_points], the input index of every
-    // output point of the last call (-1: none) until the next one.  gc_src still names the simplified polylines: their number and order do not change
+    // output point of the last call (-1: none) until the next one
     DBuf sp_tmp, sp_off, sp_pts, sp_res; int64_t sp_points = -1;
     // svg2stream (svg.hip): scratch of the flattening and of the box, the resident paths (off int64[sv_n + 1], pts double2[sv_total]; raw units after
     // orip_svg_flatten, page mm after orip_svg_fit) until the next flatten; orip_gcode_to_steps reads them when it is called without pointers

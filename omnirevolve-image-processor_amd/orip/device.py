@@ -17,6 +17,40 @@ def _p(a: np.ndarray):
     return a.ctypes.data_as(C.c_void_p)
 
 
+def _mm_paths(off, pts_mm, n):
+    """mm paths for the C side: (off pointer, pts pointer, n, the arrays that own the memory); both None = the n fitted paths resident on the device"""
+    if off is None and pts_mm is None:
+        return None, None, int(n), ()
+    o = np.ascontiguousarray(off, np.int64).reshape(-1)
+    p = np.ascontiguousarray(pts_mm, np.float64).reshape(-1, 2)
+    n = max(len(o) - 1, 0)
+    if n and int(o[-1]) != len(p):
+        raise ValueError(f"offsets end at {int(o[-1])}, {len(p)} points given")
+    return _p(o) if n else None, _p(p) if len(p) else None, n, (o, p)
+
+
+def _step_paths(off, pts, n):
+    """step polylines for the C side, as _mm_paths; both None = the n resident ones (n may still be None: the caller may know it from elsewhere)"""
+    if off is None and pts is None:
+        return None, None, n, ()
+    if off is None or pts is None:
+        raise OripError("off and pts: both or neither")
+    o = np.ascontiguousarray(off, np.int64).reshape(-1)
+    p = np.ascontiguousarray(pts, np.int32).reshape(-1, 2)
+    if len(o) < 1 or int(o[-1]) != len(p):
+        raise OripError(f"offsets end at {int(o[-1]) if len(o) else None}, {len(p)} points given")
+    if len(p) == 0:
+        p = np.zeros((1, 2), np.int32)                           # n == 0: a pointer all the same, so that the form stays the explicit one
+    return _p(o), _p(p), len(o) - 1, (o, p)
+
+
+def _start_xy(start) -> np.ndarray:
+    st = np.asarray(start, np.int64).reshape(-1)
+    if len(st) != 2 or (st < 0).any() or (st > 1 << 30).any():
+        raise OripError(f"start {tuple(st.tolist())} outside 0..2^30")
+    return np.ascontiguousarray(st, np.int32)
+
+
 class Device:
     def __init__(self, device_id: int = 0):
         self.L = _l.load()
@@ -324,32 +358,17 @@ class Device:
     def gcode_to_steps(self, off: np.ndarray | None, pts_mm: np.ndarray | None, map: dict, fetch_points: bool = True, n: int | None = None) -> Tuple[np.ndarray, np.ndarray]:
         """paths in mm (off int64 [n + 1], pts float64 [total, 2]) -> step polylines (off int64, pts int32 [total', 2]), also left resident;
         off = pts_mm = None: the n fitted paths svg_flatten / svg_fit left on the device; map: the fields of orip_gcode_map"""
-        o = p = None
-        if off is not None or pts_mm is not None:
-            o = np.ascontiguousarray(off, np.int64).reshape(-1)
-            p = np.ascontiguousarray(pts_mm, np.float64).reshape(-1, 2)
-            n = max(len(o) - 1, 0)
-            if n and int(o[-1]) != len(p):
-                raise ValueError(f"offsets end at {int(o[-1])}, {len(p)} points given")
+        po, pp, n, _keep = _mm_paths(off, pts_mm, n)
         m = _l.GcodeMap(**{k: map[k] for k, _ in _l.GcodeMap._fields_})
         n_out, tot = C.c_int64(0), C.c_int64(0)
-        self._ck(self.L.orip_gcode_to_steps(self.h, _p(o) if o is not None and n else None, _p(p) if p is not None and len(p) else None, int(n), C.byref(m), C.byref(n_out), C.byref(tot)))
-        off_s = np.zeros(n_out.value + 1, np.int64)
-        pts_s = np.zeros((max(tot.value, 1), 2), np.int32)
-        self._ck(self.L.orip_gcode_steps_fetch(self.h, _p(off_s), _p(pts_s) if fetch_points else None))
-        return off_s, pts_s[:tot.value]
+        self._ck(self.L.orip_gcode_to_steps(self.h, po, pp, n, C.byref(m), C.byref(n_out), C.byref(tot)))
+        return self.gcode_steps_fetch(n_out.value, tot.value, fetch_points)
 
     def gcode_to_steps_clip(self, off: np.ndarray | None, pts_mm: np.ndarray | None, map: dict, rect, n: int | None = None) -> Tuple[np.ndarray, np.ndarray, dict]:
         """--clip (include/orip.h: orip_gcode_to_steps_clip): gcode_to_steps with the strokes cut at rect = (x0, y0, x1, y1) in steps instead of clamped to
         the sheet; the strokes are left resident as gcode_to_steps leaves its polylines.  off = pts_mm = None: the n fitted paths on the device.
         -> (off int64, pts int32 [total', 2], {"segments", "inside", "cut", "outside", "paths_out", "points_out"})"""
-        o = p = None
-        if off is not None or pts_mm is not None:
-            o = np.ascontiguousarray(off, np.int64).reshape(-1)
-            p = np.ascontiguousarray(pts_mm, np.float64).reshape(-1, 2)
-            n = max(len(o) - 1, 0)
-            if n and int(o[-1]) != len(p):
-                raise ValueError(f"offsets end at {int(o[-1])}, {len(p)} points given")
+        po, pp, n, _keep = _mm_paths(off, pts_mm, n)
         r = np.asarray(rect, np.int64).reshape(-1)
         if len(r) != 4 or (np.abs(r) > 1 << 30).any():
             raise OripError(f"clip rectangle {tuple(r.tolist())}: four step coordinates")
@@ -357,8 +376,7 @@ class Device:
         m = _l.GcodeMap(**{k: map[k] for k, _ in _l.GcodeMap._fields_})
         n_out, tot = C.c_int64(0), C.c_int64(0)
         st = np.zeros(len(_l.CLIP_STATS), np.int64)
-        self._ck(self.L.orip_gcode_to_steps_clip(self.h, _p(o) if o is not None and n else None, _p(p) if p is not None and len(p) else None, int(n), C.byref(m), _p(r),
-                                                 C.byref(n_out), C.byref(tot), _p(st)))
+        self._ck(self.L.orip_gcode_to_steps_clip(self.h, po, pp, n, C.byref(m), _p(r), C.byref(n_out), C.byref(tot), _p(st)))
         off_s, pts_s = self.gcode_steps_fetch(n_out.value, tot.value)
         return off_s, pts_s, {k: int(v) for k, v in zip(_l.CLIP_STATS, st)}
 
@@ -427,10 +445,7 @@ class Device:
         n = len(g) if n is None else int(n)
         if len(g) != n:
             raise ValueError(f"{len(g)} groups given for {n} paths")
-        st = np.asarray(start, np.int64).reshape(-1)
-        if len(st) != 2 or (st < 0).any() or (st > 1 << 30).any():
-            raise OripError(f"start {tuple(st.tolist())} outside 0..2^30")
-        st = np.ascontiguousarray(st, np.int32)
+        st = _start_xy(start)
         order = np.zeros(max(n, 1), np.int32); rev = np.zeros(max(n, 1), np.uint8)
         self._ck(self.L.orip_gcode_order_pens(self.h, _p(e) if ends is not None and n else None, _p(g) if n else None, n, int(n_groups), _l.ORDER_REVERSE if reverse else 0,
                                               _p(st), _p(order), _p(rev)))
@@ -450,10 +465,7 @@ class Device:
         r = np.array(rev, np.uint8).reshape(-1)
         if len(g) != n or len(o) != n or len(r) != n:
             raise ValueError(f"{len(g)} groups, {len(o)} positions and {len(r)} directions given for {n} paths")
-        st = np.asarray(start, np.int64).reshape(-1)
-        if len(st) != 2 or (st < 0).any() or (st > 1 << 30).any():
-            raise OripError(f"start {tuple(st.tolist())} outside 0..2^30")
-        st = np.ascontiguousarray(st, np.int32)
+        st = _start_xy(start)
         if max_rounds is not None and not (-(1 << 63) <= int(max_rounds) < (1 << 63)):
             raise OripError(f"{max_rounds} rounds")
         if n == 0:
@@ -467,17 +479,7 @@ class Device:
         """--merge-paths (include/orip.h: orip_gcode_merge): step polylines (off int64 [n + 1], pts int32 [total, 2]; both None = the n resident ones) that
         meet end to end inside a group become one stroke, and the merged polylines become the resident ones.  group int32 [n] or None (all 0).
         -> (off int64, pts int32 [total', 2], member_off int64 [paths_out + 1], member int32 [n], rev bool [n], {"paths_out", "points_out", "joins", "cycles"})"""
-        o = p = None
-        if off is not None or pts is not None:
-            if off is None or pts is None:
-                raise OripError("off and pts: both or neither")
-            o = np.ascontiguousarray(off, np.int64).reshape(-1)
-            p = np.ascontiguousarray(pts, np.int32).reshape(-1, 2)
-            n = max(len(o) - 1, 0)
-            if len(o) < 1 or int(o[-1]) != len(p):
-                raise OripError(f"offsets end at {int(o[-1]) if len(o) else None}, {len(p)} points given")
-            if len(p) == 0:
-                p = np.zeros((1, 2), np.int32)                   # n == 0: a pointer all the same, so that the form stays the explicit one
+        po, pp, n, _keep = _step_paths(off, pts, n)
         g = None
         if group is not None:
             g = np.ascontiguousarray(group, np.int32).reshape(-1)
@@ -488,7 +490,7 @@ class Device:
             raise ValueError("n: the number of resident step polylines")
         n = int(n)
         st = np.zeros(4, np.int64)
-        self._ck(self.L.orip_gcode_merge(self.h, _p(o) if o is not None else None, _p(p) if p is not None else None, _p(g) if g is not None and n else None, n, int(n_groups),
+        self._ck(self.L.orip_gcode_merge(self.h, po, pp, _p(g) if g is not None and n else None, n, int(n_groups),
                                          _l.MERGE_REVERSE if reverse else 0, _p(st)))
         paths, total = int(st[0]), int(st[1])
         moff = np.zeros(paths + 1, np.int64); member = np.zeros(max(n, 1), np.int32); rev = np.zeros(max(n, 1), np.uint8)
@@ -500,34 +502,24 @@ class Device:
         """--simplify-mm (include/orip.h: orip_gcode_simplify): Ramer-Douglas-Peucker on the step polylines (off int64 [n + 1], pts int32 [total, 2]; both
         None = the n resident ones) with the tolerance tol4 in quarter steps, and the simplified polylines become the resident ones.
         -> (off int64, pts int32 [total', 2], kept int64 [total']: the input index of every output point, {"paths", "points_in", "points_out", "rounds"})"""
-        o = p = None
-        if off is not None or pts is not None:
-            if off is None or pts is None:
-                raise OripError("off and pts: both or neither")
-            o = np.ascontiguousarray(off, np.int64).reshape(-1)
-            p = np.ascontiguousarray(pts, np.int32).reshape(-1, 2)
-            n = max(len(o) - 1, 0)
-            if len(o) < 1 or int(o[-1]) != len(p):
-                raise OripError(f"offsets end at {int(o[-1]) if len(o) else None}, {len(p)} points given")
-            if len(p) == 0:
-                p = np.zeros((1, 2), np.int32)                   # n == 0: a pointer all the same, so that the form stays the explicit one
+        po, pp, n, _keep = _step_paths(off, pts, n)
         if n is None:
             raise ValueError("n: the number of resident step polylines")
         if not (-(1 << 31) <= int(tol4) < (1 << 31)):
             raise OripError(f"tolerance {tol4} quarter steps")
         n = int(n)
         st = np.zeros(4, np.int64)
-        self._ck(self.L.orip_gcode_simplify(self.h, _p(o) if o is not None else None, _p(p) if p is not None else None, n, int(tol4), _p(st)))
+        self._ck(self.L.orip_gcode_simplify(self.h, po, pp, n, int(tol4), _p(st)))
         total = int(st[2])
         kept = np.zeros(max(total, 1), np.int64)
         self._ck(self.L.orip_gcode_simplify_fetch(self.h, _p(kept)))
         off_s, pts_s = self.gcode_steps_fetch(n, total)
         return off_s, pts_s, kept[:total], {k: int(v) for k, v in zip(("paths", "points_in", "points_out", "rounds"), st)}
 
-    def gcode_steps_fetch(self, n: int, total: int) -> Tuple[np.ndarray, np.ndarray]:
-        """the n resident step polylines of `total` points, as gcode_to_steps or gcode_merge left them: (off int64 [n + 1], pts int32 [total, 2])"""
+    def gcode_steps_fetch(self, n: int, total: int, points: bool = True) -> Tuple[np.ndarray, np.ndarray]:
+        """the n resident step polylines of `total` points, as gcode_to_steps or gcode_merge left them: (off int64 [n + 1], pts int32 [total, 2]; zeros without `points`)"""
         off = np.zeros(int(n) + 1, np.int64); pts = np.zeros((max(int(total), 1), 2), np.int32)
-        self._ck(self.L.orip_gcode_steps_fetch(self.h, _p(off), _p(pts)))
+        self._ck(self.L.orip_gcode_steps_fetch(self.h, _p(off), _p(pts) if points else None))
         return off, pts[:int(total)]
 
     def gcode_steps_source(self, n: int) -> np.ndarray:

@@ -44,6 +44,7 @@ from __future__ import annotations
 
 import argparse
 import re
+from collections import namedtuple
 import sys
 from dataclasses import dataclass, fields
 from pathlib import Path
@@ -313,13 +314,140 @@ def build_stream_from_gcode(text_or_paths, opts: Optional[GcodeOptions] = None, 
     pens: one pen per input path, 0..7, or -1 for --color-index (a text's T words under --tool-pens when None).  info["pens"] then counts the paths per
     pen, those that took --color-index ("unmatched") and the strokes drawn backwards ("reversed").
     Returns (bytes, counts)."""
+    steps = StrokeSteps(clip_fn if opts is not None and opts.clip else steps_fn, source_fn, merge_fn, simplify_fn, order_fn, order_pens_fn, improve_fn, codes_fn, pack_fn)
+    return stroke_stream(text_or_paths, opts, device, steps, timings, pens)
+
+
+# The device steps of the stroke pipeline, each a callable or None = not given; build_stream_from_gcode states the signatures.  convert: steps_fn or, with --clip, clip_fn
+StrokeSteps = namedtuple("StrokeSteps", "convert source merge simplify order order_pens improve codes pack", defaults=(None,) * 9)
+
+
+def resolve_steps(st: StrokeSteps, o, grouped: bool, device=None, convert: Optional[Callable] = None, force: bool = False):
+    """The steps the options need, those not given taken from a device -> (steps, device); codes and pack stay as given (orip.stream.compile_plan fills them).
+    When none is missing, and the caller does not `force` a device for steps of its own, no device is made and orip.stages is not imported.  convert(device)
+    -> the conversion of a front door whose paths are on the device already (orip.svg).  Merge and simplify work on the polylines the pass before them left
+    resident when that pass ran on this device, and are sent their input when it was given."""
+    need = ["convert", "order"] + ["order_pens", "source"] * bool(grouped) + ["merge"] * bool(o.merge_paths) + ["improve"] * bool(o.improve_order) + ["simplify"] * (o.simplify_mm is not None)
+    if not force and all(getattr(st, k) is not None for k in need):
+        return st, device
+    if device is None:
+        from .stages import device as _default_device
+        device = _default_device()
+    after_convert = st.convert is None                                     # resident behind this device's own conversion,
+    after_merge = st.merge is None if o.merge_paths else after_convert     # and behind its merge or, without one, behind the conversion
+    own = StrokeSteps(
+        convert=convert(device) if convert is not None else device.gcode_to_steps_clip if o.clip else device.gcode_to_steps, source=device.gcode_steps_source,
+        merge=(lambda off, pts, group, n_groups, reverse: device.gcode_merge(None, None, group, n_groups, reverse, n=len(off) - 1)) if after_convert else device.gcode_merge,
+        simplify=(lambda off, pts, t4: device.gcode_simplify(None, None, t4, n=len(off) - 1)) if after_merge else device.gcode_simplify,
+        order=device.gcode_order, order_pens=device.gcode_order_pens,
+        improve=lambda ends, group, n_groups, order, rev, reverse, max_rounds: device.gcode_improve(ends, group, n_groups, order, rev, reverse, max_rounds=max_rounds))
+    return StrokeSteps(*(a or b for a, b in zip(st, own))), device
+
+
+def _convert(st: StrokeSteps, off_mm, pts_mm, m: dict, rect, info: dict):
+    """mm paths -> step polylines, clamped to the sheet or (rect) cut at it; info["clip"]"""
+    if rect is None:
+        off, pts = st.convert(off_mm, pts_mm, m)
+    else:
+        off, pts, cst = st.convert(off_mm, pts_mm, m, rect)
+        info["clip"] = dict({"rect": tuple(int(v) for v in rect)}, **{k: int(cst[k]) for k in CLIP_STATS})
+        if info["clip"]["inside"] + info["clip"]["cut"] + info["clip"]["outside"] != info["clip"]["segments"] or info["clip"]["paths_out"] != len(off) - 1:
+            raise RuntimeError("the clip's counts do not add up")
+    return np.asarray(off, np.int64), np.asarray(pts, np.int32).reshape(-1, 2)
+
+
+def _stroke_pens(st: StrokeSteps, o: GcodeOptions, pens, n: int, info: dict):
+    """(pen, group) of every step polyline: its input path's pen, through the paths the conversion dropped, and that pen's place in the drawing sequence"""
+    if not (0 <= int(o.color_index) <= 7):
+        raise ValueError("color index 0..7")
+    if pens is None:
+        return np.full(n, int(o.color_index), np.int64), np.zeros(n, np.int32)
+    src = np.asarray(st.source(n), np.int64).reshape(-1)
+    if len(src) != n or (src < 0).any() or (src >= len(pens)).any():
+        raise RuntimeError("the source indices of the step polylines do not name input paths")
+    pen = np.where(pens[src] < 0, int(o.color_index), pens[src])
+    info["pens"] = {"paths": np.bincount(pen, minlength=MAX_PENS).tolist(), "unmatched": int((pens[src] < 0).sum()), "reversed": 0}
+    return pen, np.argsort(np.asarray(pen_sequence(o.pen_order)))[pen].astype(np.int32)
+
+
+def _merge(st: StrokeSteps, o: GcodeOptions, off, pts, pen, group, n_groups: int, info: dict):
+    """strokes of one pen that meet end to end become one; the pen of a merged stroke is its members' pen; info["merge"]"""
+    n_in = len(off) - 1
+    off, pts, member_off, member, _, mst = st.merge(off, pts, group if group is not None else np.zeros(n_in, np.int32), n_groups, bool(o.allow_reverse))
+    off = np.asarray(off, np.int64); pts = np.asarray(pts, np.int32).reshape(-1, 2)
+    member_off = np.asarray(member_off, np.int64).reshape(-1); member = np.asarray(member, np.int64).reshape(-1)
+    n = len(off) - 1
+    if not (1 <= n <= n_in) or len(member_off) != n + 1 or len(member) != n_in or int(member_off[-1]) != n_in or not np.array_equal(np.sort(member), np.arange(n_in)):
+        raise RuntimeError("the merge did not return every path once")
+    if group is not None:
+        first = member[member_off[:-1]]
+        if (group[member] != np.repeat(group[first], np.diff(member_off))).any():
+            raise RuntimeError("the merge joined paths of different pens")
+        pen, group = pen[first], group[first]
+    info["paths"] = n
+    info["merge"] = {"paths_in": n_in, "paths_out": n, "joins": int(mst["joins"]), "cycles": int(mst["cycles"])}
+    return off, pts, pen, group
+
+
+def _simplify(st: StrokeSteps, off_in, pts_in, tol4: int, info: dict):
+    """the same strokes with the same ends, every stroke an ascending selection of its own points; info["simplify"]"""
+    n = len(off_in) - 1
+    off, pts, kept, _ = st.simplify(off_in, pts_in, tol4)
+    off = np.asarray(off, np.int64).reshape(-1); pts = np.asarray(pts, np.int32).reshape(-1, 2); kept = np.asarray(kept, np.int64).reshape(-1)
+    if len(off) != n + 1 or off[0] != 0 or int(off[-1]) != len(pts) or len(kept) != len(pts) or (np.diff(off) < 2).any() or \
+            not np.array_equal(kept[off[:-1]], off_in[:-1]) or not np.array_equal(kept[off[1:] - 1], off_in[1:] - 1) or \
+            (np.diff(kept) <= 0).any() or not np.array_equal(pts, pts_in[kept]):
+        raise RuntimeError("the simplification did not return every stroke with its ends and its points in order")
+    info["simplify"] = {"tol4": tol4, "points_in": len(pts_in), "points_out": len(pts), "paths_changed": int((np.diff(off) != np.diff(off_in)).sum())}
+    return off, pts
+
+
+def _checked_order(order, rev, n: int, group, reverse: bool, what: str):
+    """(order int64, rev bool) when order is a permutation of the n strokes whose groups do not decrease and nothing is reversed without `reverse`"""
+    order = np.asarray(order, np.int64).reshape(-1)
+    rev = np.zeros(n, bool) if rev is None else np.asarray(rev, bool).reshape(-1)
+    if len(order) != n or len(rev) != n or not np.array_equal(np.sort(order), np.arange(n)) or (np.diff(np.asarray(group)[order]) < 0).any() or (rev.any() and not reverse):
+        raise RuntimeError(what)
+    return order, rev
+
+
+def _order(st: StrokeSteps, o: GcodeOptions, off, pts, group, n_groups: int, info: dict, lap):
+    """the drawing sequence (order, rev), or (None, None) for the strokes as they stand: pen after pen (group given) or as one list, greedy and then improved"""
+    n = len(off) - 1
+    if o.no_reorder:                                                      # pen after pen all the same, file order inside a pen
+        return (np.argsort(group, kind="stable"), np.zeros(n, bool)) if group is not None else (None, None)
+    ends, reverse = path_ends(off, pts), bool(o.allow_reverse)
+    if group is not None:
+        order, rev = _checked_order(*st.order_pens(ends, group, n_groups, reverse), n, group, True, "the path order is not a permutation that keeps the pens together")
+    else:                                                                 # one group, no stroke reversed
+        group, n_groups = np.zeros(n, np.int32), 1
+        order, rev = _checked_order(st.order(ends), None, n, group, True, "the path order is not a permutation")
+    if o.improve_order:
+        lap("order")
+        order, rev, ist = st.improve(ends, group, n_groups, np.asarray(order, np.int32), rev, reverse, o.improve_rounds)
+        order, rev = _checked_order(order, rev, n, group, reverse, "the improved order is not a permutation that keeps the pens together and the directions allowed")
+        info["improve"] = {k: int(ist[k]) for k in IMPROVE_STATS}
+        lap("improve")
+    return order, rev
+
+
+def _plan(o: GcodeOptions, sc: ST.StreamConfig, off, pts, path_pen) -> ST.Plan:
+    """every move of the plot; path_pen: the pen of every stroke in drawing order, or None for --color-index throughout"""
+    if not (0 <= int(o.color_index) <= 7):
+        raise ValueError("color index 0..7")
+    div0 = min(max(int(sc.div_start), 0), 63)                             # set_speed(div_start): written here, and remembered (layout: initial_div)
+    if path_pen is not None:
+        return plan_pens(off, pts, path_pen, [ST.PEN_UP, 0x40 | div0], sc)
+    return ST.plan_ops(off, pts, np.zeros(len(off) - 1, bool), (0, 0), [ST.PEN_UP, 0x40 | div0, 0x08 | int(o.color_index)], False, sc)
+
+
+def stroke_stream(text_or_paths, opts: Optional[GcodeOptions], device, steps: StrokeSteps, timings: Optional[dict] = None, pens: Optional[np.ndarray] = None) -> Tuple[bytes, dict]:
+    """build_stream_from_gcode with the device steps as one record: parse, convert, pens of the strokes, merge, simplify, order, plan, compile"""
     import time
     o = apply_speed_scale(GcodeOptions(**{f.name: getattr(opts, f.name) for f in fields(GcodeOptions)}) if opts is not None else GcodeOptions())
     W, H = target_size(o)
     sc = stream_config(o)
-    check_improve_options(o)
-    rect = clip_rect(o)
-    tol4 = simplify_tol4(o)
+    rect, tol4 = stroke_options(o)
     tm = timings if timings is not None else {}
     t0 = time.perf_counter()
 
@@ -338,7 +466,7 @@ def build_stream_from_gcode(text_or_paths, opts: Optional[GcodeOptions] = None, 
         pen_moves = int((np.diff(off_mm) - 1).clip(0).sum())
     lap("parse")
     info = {"paths_mm": len(off_mm) - 1, "pen_down_moves": pen_moves, "paths": 0, "steps": 0, "target": (W, H)}
-    seq = pen_sequence(o.pen_order)
+    pen_sequence(o.pen_order)
     grouped = pens is not None or bool(o.allow_reverse)                   # the new order; without either, everything below is as it was
     if pens is not None:
         pens = np.asarray(pens, np.int64).reshape(-1)
@@ -348,131 +476,32 @@ def build_stream_from_gcode(text_or_paths, opts: Optional[GcodeOptions] = None, 
         return EMPTY_STREAM, dict(info, bytes=len(EMPTY_STREAM))
     if not (1 <= W <= MAX_TARGET_STEPS and 1 <= H <= MAX_TARGET_STEPS):
         raise ValueError(f"target size {W} x {H} steps: each side must be in 1..2^30 (step coordinates are int32 on the device)")
-    convert_fn = steps_fn if rect is None else clip_fn
-    if convert_fn is None or order_fn is None or (grouped and (order_pens_fn is None or source_fn is None)) or (o.merge_paths and merge_fn is None) or \
-            (o.improve_order and improve_fn is None) or (tol4 is not None and simplify_fn is None):
-        if device is None:
-            from .stages import device as _default_device
-            device = _default_device()
-        if simplify_fn is None:                                           # likewise simplified where they are, when this device's conversion or merge left them
-            sp_resident = merge_fn is None if o.merge_paths else convert_fn is None
-            simplify_fn = lambda off, pts, t4: device.gcode_simplify(None, None, t4, n=len(off) - 1) if sp_resident else device.gcode_simplify(off, pts, t4)
-        if merge_fn is None:                                              # the polylines this device's own conversion left resident are merged where they are
-            resident = convert_fn is None
-            merge_fn = lambda off, pts, group, n_groups, reverse: (device.gcode_merge(None, None, group, n_groups, reverse, n=len(off) - 1) if resident else
-                                                                   device.gcode_merge(off, pts, group, n_groups, reverse))
-        steps_fn = steps_fn or device.gcode_to_steps
-        clip_fn = clip_fn or device.gcode_to_steps_clip
-        order_fn = order_fn or device.gcode_order
-        order_pens_fn = order_pens_fn or (lambda ends, group, n_groups, reverse: device.gcode_order_pens(ends, group, n_groups, reverse))
-        source_fn = source_fn or device.gcode_steps_source
-        improve_fn = improve_fn or (lambda ends, group, n_groups, order, rev, reverse, max_rounds: device.gcode_improve(ends, group, n_groups, order, rev, reverse,
-                                                                                                                   max_rounds=max_rounds))
+    st, device = resolve_steps(steps, o, grouped, device)
     m = dict(scale_x=o.scale_x, scale_y=o.scale_y, offset_x_mm=o.offset_x_mm, offset_y_mm=o.offset_y_mm, steps_per_mm=o.steps_per_mm, W=W, H=H, invert_y=int(bool(o.invert_y)))
-    if rect is None:
-        off, pts = steps_fn(off_mm, pts_mm, m)
-    else:
-        off, pts, cst = clip_fn(off_mm, pts_mm, m, rect)
-        info["clip"] = dict({"rect": tuple(int(v) for v in rect)}, **{k: int(cst[k]) for k in CLIP_STATS})
-        if info["clip"]["inside"] + info["clip"]["cut"] + info["clip"]["outside"] != info["clip"]["segments"] or info["clip"]["paths_out"] != len(off) - 1:
-            raise RuntimeError("the clip's counts do not add up")
-    off = np.asarray(off, np.int64); pts = np.asarray(pts, np.int32).reshape(-1, 2)
+    off, pts = _convert(st, off_mm, pts_mm, m, rect, info)
     lap("to_steps")
-    n = len(off) - 1
-    info["paths"] = n
+    info["paths"] = n = len(off) - 1
     if n == 0:
         return EMPTY_STREAM, dict(info, bytes=len(EMPTY_STREAM))
-    path_pen = None
-    pen = group = None
-    n_groups = MAX_PENS if pens is not None else 1
-    if grouped:
-        if not (0 <= int(o.color_index) <= 7):
-            raise ValueError("color index 0..7")
-        # the pen of every step polyline, through the paths the conversion dropped; its group is the pen's place in the drawing sequence
-        if pens is not None:
-            src = np.asarray(source_fn(n), np.int64).reshape(-1)
-            if len(src) != n or (src < 0).any() or (src >= len(pens)).any():
-                raise RuntimeError("the source indices of the step polylines do not name input paths")
-            pen = np.where(pens[src] < 0, int(o.color_index), pens[src])
-            info["pens"] = {"paths": np.bincount(pen, minlength=MAX_PENS).tolist(), "unmatched": int((pens[src] < 0).sum()), "reversed": 0}
-            group = np.argsort(np.asarray(seq))[pen].astype(np.int32)
-        else:
-            pen = np.full(n, int(o.color_index), np.int64); group = np.zeros(n, np.int32)
+    pen, group = _stroke_pens(st, o, pens, n, info) if grouped else (None, None)
     if o.merge_paths:
         lap("order")                                                      # the sources and the pens belong to the order's lap, as before
-        n_in = n
-        off, pts, member_off, member, _, mst = merge_fn(off, pts, group if group is not None else np.zeros(n, np.int32), n_groups, bool(o.allow_reverse))
-        off = np.asarray(off, np.int64); pts = np.asarray(pts, np.int32).reshape(-1, 2)
-        member_off = np.asarray(member_off, np.int64).reshape(-1); member = np.asarray(member, np.int64).reshape(-1)
-        n = len(off) - 1
-        if not (1 <= n <= n_in) or len(member_off) != n + 1 or len(member) != n_in or int(member_off[-1]) != n_in or not np.array_equal(np.sort(member), np.arange(n_in)):
-            raise RuntimeError("the merge did not return every path once")
-        if grouped:
-            first = member[member_off[:-1]]
-            if (group[member] != np.repeat(group[first], np.diff(member_off))).any():
-                raise RuntimeError("the merge joined paths of different pens")
-            pen, group = pen[first], group[first]
-        info["paths"] = n
-        info["merge"] = {"paths_in": n_in, "paths_out": n, "joins": int(mst["joins"]), "cycles": int(mst["cycles"])}
+        off, pts, pen, group = _merge(st, o, off, pts, pen, group, MAX_PENS if pens is not None else 1, info)
         lap("merge")
     if tol4 is not None:
         if not o.merge_paths:
             lap("order")
-        off_in, pts_in = off, pts
-        off, pts, kept, _ = simplify_fn(off, pts, tol4)
-        off = np.asarray(off, np.int64).reshape(-1); pts = np.asarray(pts, np.int32).reshape(-1, 2); kept = np.asarray(kept, np.int64).reshape(-1)
-        # the same strokes with the same ends, every stroke an ascending selection of its own points
-        if len(off) != n + 1 or off[0] != 0 or int(off[-1]) != len(pts) or len(kept) != len(pts) or (np.diff(off) < 2).any() or \
-                not np.array_equal(kept[off[:-1]], off_in[:-1]) or not np.array_equal(kept[off[1:] - 1], off_in[1:] - 1) or \
-                (np.diff(kept) <= 0).any() or not np.array_equal(pts, pts_in[kept]):
-            raise RuntimeError("the simplification did not return every stroke with its ends and its points in order")
-        info["simplify"] = {"tol4": tol4, "points_in": len(pts_in), "points_out": len(pts), "paths_changed": int((np.diff(off) != np.diff(off_in)).sum())}
+        off, pts = _simplify(st, off, pts, tol4, info)
         lap("simplify")
-    def improve(ends, group, n_groups, order, rev, reverse):
-        order, rev, ist = improve_fn(ends, group, n_groups, np.asarray(order, np.int32), np.asarray(rev, bool), reverse, o.improve_rounds)
-        order = np.asarray(order, np.int64).reshape(-1); rev = np.asarray(rev, bool).reshape(-1)
-        if len(order) != n or len(rev) != n or not np.array_equal(np.sort(order), np.arange(n)) or (np.diff(np.asarray(group)[order]) < 0).any() or (rev.any() and not reverse):
-            raise RuntimeError("the improved order is not a permutation that keeps the pens together and the directions allowed")
-        info["improve"] = {k: int(ist[k]) for k in IMPROVE_STATS}
-        return order, rev
-
-    if grouped:
-        if o.no_reorder:
-            order, rev = np.argsort(group, kind="stable"), np.zeros(n, bool)      # pen after pen all the same, file order inside a pen
-        else:
-            order, rev = order_pens_fn(path_ends(off, pts), group, n_groups, bool(o.allow_reverse))
-            order = np.asarray(order, np.int64); rev = np.asarray(rev, bool)
-            if len(order) != n or len(rev) != n or not np.array_equal(np.sort(order), np.arange(n)) or (np.diff(group[order]) < 0).any():
-                raise RuntimeError("the path order is not a permutation that keeps the pens together")
-            if o.improve_order:
-                lap("order")
-                order, rev = improve(path_ends(off, pts), group, n_groups, order, rev, bool(o.allow_reverse))
-                lap("improve")
+    order, rev = _order(st, o, off, pts, group, MAX_PENS if pens is not None else 1, info, lap)
+    if order is not None:
         off, pts = gather_paths(off, pts, order, rev)
-        path_pen = pen[order]
-        if pens is not None:
-            info["pens"]["reversed"] = int(rev.sum())
-        else:
-            info["reversed"] = int(rev.sum())
-    elif not o.no_reorder:
-        order = np.asarray(order_fn(path_ends(off, pts)), np.int64)
-        if len(order) != n or not np.array_equal(np.sort(order), np.arange(n)):
-            raise RuntimeError("the path order is not a permutation")
-        if o.improve_order:
-            lap("order")
-            order, _ = improve(path_ends(off, pts), np.zeros(n, np.int32), 1, order, np.zeros(n, bool), False)
-            lap("improve")
-        off, pts = gather_paths(off, pts, order)
+    if grouped:
+        (info["pens"] if pens is not None else info)["reversed"] = int(rev.sum())
     lap("order")
-    if not (0 <= int(o.color_index) <= 7):
-        raise ValueError("color index 0..7")
-    div0 = min(max(int(sc.div_start), 0), 63)                             # set_speed(div_start): written here, and remembered (layout: initial_div)
-    if pens is not None:
-        P = plan_pens(off, pts, path_pen, [ST.PEN_UP, 0x40 | div0], sc)
-    else:
-        P = ST.plan_ops(off, pts, np.zeros(n, bool), (0, 0), [ST.PEN_UP, 0x40 | div0, 0x08 | int(o.color_index)], False, sc)
+    P = _plan(o, sc, off, pts, pen[order] if pens is not None else None)
     lap("plan")
-    data, table, coff = ST.compile_plan(P, sc, device, codes_fn, pack_fn, initial_div=int(sc.div_start), lap=lap)
+    data, table, coff = ST.compile_plan(P, sc, device, st.codes, st.pack, initial_div=int(sc.div_start), lap=lap)
     info.update(steps=int(coff[-1]), bytes=len(data), pieces=len(table.pos), moves=len(P.moves))
     return data, info
 
@@ -500,12 +529,6 @@ def clip_rect(o) -> Optional[Tuple[int, int, int, int]]:
     return m, m, W - 1 - m, H - 1 - m
 
 
-def clip_line(tag: str, c: dict) -> str:
-    x0, y0, x1, y1 = c["rect"]
-    return (f"[{tag}] clip: {c['segments']} segments: {c['inside']} inside, {c['cut']} cut, {c['outside']} outside [{x0}, {x1}] x [{y0}, {y1}] steps -> "
-            f"{c['paths_out']} strokes, {c['points_out']} points")
-
-
 def simplify_tol4(o) -> Optional[int]:
     """None without --simplify-mm, else the tolerance in quarter steps, round(4 mm steps_per_mm): 0 .. 2^17 - 1"""
     if o.simplify_mm is None:
@@ -522,18 +545,15 @@ def simplify_tol4(o) -> Optional[int]:
     return t
 
 
-def simplify_line(tag: str, st: dict) -> str:
-    return f"[{tag}] simplify: {st['points_in']} points -> {st['points_out']} within {st['tol4'] / 4:g} steps, {st['paths_changed']} strokes changed"
-
-
-def check_improve_options(o) -> None:
-    """--improve-order starts from the greedy order, and --improve-rounds belongs to it"""
+def stroke_options(o) -> Tuple[Optional[Tuple[int, int, int, int]], Optional[int]]:
+    """the options of the stroke passes, checked together -> (clip rectangle or None, tol4 or None); --improve-order starts from the greedy order, --improve-rounds belongs to it"""
     if o.improve_order and o.no_reorder:
         raise ValueError("--improve-order with --no-reorder: file order was asked for")
     if o.improve_rounds is not None and not o.improve_order:
         raise ValueError("--improve-rounds needs --improve-order")
     if o.improve_rounds is not None and int(o.improve_rounds) < 0:
         raise ValueError("--improve-rounds must not be negative")
+    return clip_rect(o), simplify_tol4(o)
 
 
 def improve_line(tag: str, st: dict) -> str:
@@ -570,18 +590,50 @@ def build_argparser() -> argparse.ArgumentParser:
     ap.add_argument("--short-len-steps", type=int, default=d.short_len_steps)
     ap.add_argument("--short-div", type=int, default=d.short_div)
     ap.add_argument("--speed-scale", type=float, default=d.speed_scale, help="> 1 faster (smaller dividers), < 1 slower")
-    ap.add_argument("--no-reorder", action="store_true", help="keep the paths in file order")
-    ap.add_argument("--allow-reverse", action="store_true", help="let the order draw a stroke backwards when its far end is nearer")
+    add_stroke_args(ap, STROKE_ARGS[:2])
     ap.add_argument("--tool-pens", action="store_true", help="a path is drawn with the pen its T word names (T0..T7; before any T: --color-index), pen after pen")
-    ap.add_argument("--pen-order", default=None, help="pens in drawing order, comma-separated (default: ascending); pens without paths are skipped")
-    ap.add_argument("--merge-paths", action="store_true", help="draw strokes of one pen that meet end to end on the step grid as one stroke (no tolerance; where three or more ends meet, none are joined)")
-    ap.add_argument("--improve-order", action="store_true", help="after the greedy order, lower the pen-up travel by 2-opt (with --allow-reverse) and or-opt moves, one per round, pen by pen")
-    ap.add_argument("--improve-rounds", type=int, default=None, help="rounds per pen at most (default: 2 m + 64 for m strokes); needs --improve-order")
-    ap.add_argument("--clip", action="store_true", help="cut the strokes at the edge of the sheet and lift the pen outside it, instead of clamping every point onto the edge")
-    ap.add_argument("--clip-margin-mm", type=float, default=None, help="cut this far inside the edge of the sheet (default: 0); needs --clip")
-    ap.add_argument("--simplify-mm", type=float, default=None, help="drop the vertices that lie within this distance of the stroke (Ramer-Douglas-Peucker on the step grid; "
-                    "0: only vertices on the straight line between their neighbours)")
+    add_stroke_args(ap, STROKE_ARGS[2:])
     return ap
+
+
+STROKE_ARGS = ("--no-reorder", "--allow-reverse", "--pen-order", "--merge-paths", "--improve-order", "--improve-rounds", "--clip", "--clip-margin-mm", "--simplify-mm")
+
+
+def add_stroke_args(ap: argparse.ArgumentParser, names: Sequence[str] = STROKE_ARGS, suffix: str = "") -> None:
+    """the options of the stroke passes, those of `names` in that order; `suffix` ends the help of the three that change what is drawn but not the G-code file"""
+    flag, number = dict(action="store_true"), dict(default=None)
+    table = {
+        "--no-reorder": (flag, "keep the paths in file order"),
+        "--allow-reverse": (flag, "let the order draw a stroke backwards when its far end is nearer"),
+        "--pen-order": (number, "pens in drawing order, comma-separated (default: ascending); pens without paths are skipped"),
+        "--merge-paths": (flag, "draw strokes of one pen that meet end to end on the step grid as one stroke (no tolerance; where three or more ends meet, none are joined)" + suffix),
+        "--improve-order": (flag, "after the greedy order, lower the pen-up travel by 2-opt (with --allow-reverse) and or-opt moves, one per round, pen by pen" + suffix),
+        "--improve-rounds": (dict(number, type=int), "rounds per pen at most (default: 2 m + 64 for m strokes); needs --improve-order"),
+        "--clip": (flag, "cut the strokes at the edge of the sheet and lift the pen outside it, instead of clamping every point onto the edge" + suffix),
+        "--clip-margin-mm": (dict(number, type=float), "cut this far inside the edge of the sheet (default: 0); needs --clip"),
+        "--simplify-mm": (dict(number, type=float), "drop the vertices that lie within this distance of the stroke (Ramer-Douglas-Peucker on the step grid; "
+                                                    "0: only vertices on the straight line between their neighbours)"),
+    }
+    for name in names:
+        ap.add_argument(name, help=table[name][1], **table[name][0])
+
+
+def report_lines(tag: str, info: dict, unmatched: bool = False):
+    """the lines the tools print about the stroke passes that ran; `unmatched`: the pens line also counts the paths without a stroke colour"""
+    if "clip" in info:
+        c = info["clip"]; x0, y0, x1, y1 = c["rect"]
+        yield (f"[{tag}] clip: {c['segments']} segments: {c['inside']} inside, {c['cut']} cut, {c['outside']} outside [{x0}, {x1}] x [{y0}, {y1}] steps -> "
+               f"{c['paths_out']} strokes, {c['points_out']} points")
+    if "pens" in info:
+        yield (f"[{tag}] pens: " + ", ".join(f"{p}: {k} paths" for p, k in enumerate(info["pens"]["paths"]) if k) + "; " +
+               (f"{info['pens']['unmatched']} without a stroke colour, " if unmatched else "") + f"{info['pens']['reversed']} strokes reversed")
+    if "merge" in info:
+        yield f"[{tag}] " + "merge: {paths_in} paths -> {paths_out}, {joins} pen lifts saved, {cycles} closed".format(**info["merge"])
+    if "simplify" in info:
+        st = info["simplify"]
+        yield f"[{tag}] simplify: {st['points_in']} points -> {st['points_out']} within {st['tol4'] / 4:g} steps, {st['paths_changed']} strokes changed"
+    if "improve" in info:
+        yield improve_line(tag, info["improve"])
 
 
 def options_from_args(a: argparse.Namespace) -> GcodeOptions:
@@ -592,24 +644,14 @@ def main(argv: Optional[Sequence[str]] = None, **device_steps) -> None:
     a = build_argparser().parse_args(argv)
     opts = options_from_args(a)
     apply_speed_scale(GcodeOptions(speed_scale=opts.speed_scale))        # a bad scale ends the run before the file is read, as in the reference
-    check_improve_options(opts)
-    clip_rect(opts)
-    simplify_tol4(opts)
+    stroke_options(opts)
     text = Path(a.input).read_bytes()
     data, info = build_stream_from_gcode(text, opts, **device_steps)
     Path(a.output).write_bytes(data)
     print(f"[gcode] {a.input}: {info['paths_mm']} pen-down paths, {info['pen_down_moves']} pen-down moves")
     print(f"[gcode] {info['paths']} paths in step space, {info['steps']} steps, target {info['target'][0]} x {info['target'][1]} steps")
-    if "clip" in info:
-        print(clip_line("gcode", info["clip"]))
-    if "pens" in info:
-        print("[gcode] pens: " + ", ".join(f"{p}: {k} paths" for p, k in enumerate(info["pens"]["paths"]) if k) + f"; {info['pens']['reversed']} strokes reversed")
-    if "merge" in info:
-        print("[gcode] merge: {paths_in} paths -> {paths_out}, {joins} pen lifts saved, {cycles} closed".format(**info["merge"]))
-    if "simplify" in info:
-        print(simplify_line("gcode", info["simplify"]))
-    if "improve" in info:
-        print(improve_line("gcode", info["improve"]))
+    for line in report_lines("gcode", info):
+        print(line)
     print(f"stream saved: {a.output} ({len(data)} bytes)")
 
 

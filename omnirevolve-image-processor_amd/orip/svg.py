@@ -696,9 +696,6 @@ class _Resident:
 
     def hatch_groups(self, paths, segments): return self.dev.svg_hatch_groups(segments)
     def source(self, n): return self.dev.gcode_steps_source(n)
-    def order_pens(self, ends, group, n_groups, reverse): return self.dev.gcode_order_pens(ends, group, n_groups, reverse)
-    def merge(self, off, pts, group, n_groups, reverse): return self.dev.gcode_merge(None, None, group, n_groups, reverse, n=len(off) - 1)
-    def simplify(self, off, pts, tol4): return self.dev.gcode_simplify(None, None, tol4, n=len(off) - 1)
 
 
 MAX_REFLATTEN = 8
@@ -797,12 +794,10 @@ def build_stream_from_svg(text: Union[str, bytes, SegmentTable], opts: Optional[
     hp = hatch_params(o)
     if o.pen_colors is not None:
         parse_pen_colors(o.pen_colors)                      # a bad list ends the run before anything is parsed
-    GC.check_improve_options(o)
+    go = gcode_options(o)
+    GC.stroke_options(go)
     table = text if isinstance(text, SegmentTable) else parse_svg(text, o.hatch_fill)
     tm["parse_svg"] = tm.get("parse_svg", 0.0) + (time.perf_counter() - t0)
-    go = gcode_options(o)
-    GC.clip_rect(go)
-    GC.simplify_tol4(go)
     GC.apply_speed_scale(GC.GcodeOptions(speed_scale=go.speed_scale))
     tolerance_mm(o)
     info = {"segments": table.n_seg, "subpaths": table.n_sub, "canvas_height": table.canvas_height}
@@ -812,23 +807,16 @@ def build_stream_from_svg(text: Union[str, bytes, SegmentTable], opts: Optional[
             info["fitted_paths"] = (np.zeros(1, np.int64), np.zeros((0, 2)))
         return data, dict(ginfo, **info)
     pens_on = o.pen_colors is not None
-    convert_fn = clip_fn if o.clip else steps_fn
-    if any(f is None for f in (flatten_fn, bbox_fn, fit_fn, fetch_fn, convert_fn, order_fn, codes_fn, pack_fn)) or (hp and hatch_fn is None) or \
-            ((pens_on or o.allow_reverse) and (source_fn is None or order_pens_fn is None)) or (pens_on and hp and hatch_groups_fn is None) or \
-            (o.merge_paths and merge_fn is None) or (o.improve_order and improve_fn is None) or (o.simplify_mm is not None and simplify_fn is None):
-        if device is None:
-            from .stages import device as _default_device
-            device = _default_device()
+    given = clip_fn if o.clip else steps_fn                 # the stroke steps take (off, pts_mm, ...); here the conversion takes the fitted paths where they are
+    steps = GC.StrokeSteps(None if given is None else (lambda _off, _pts, m, *rect: given(paths, m, *rect)), source_fn, merge_fn, simplify_fn, order_fn, order_pens_fn,
+                           improve_fn, codes_fn, pack_fn)
+    own = any(f is None for f in (flatten_fn, bbox_fn, fit_fn, fetch_fn)) or (hp and hatch_fn is None) or (pens_on and hp and hatch_groups_fn is None)
+    steps, device = GC.resolve_steps(steps, go, pens_on or o.allow_reverse, device, force=bool(own),
+                                     convert=lambda dev: lambda _off, _pts, m, *rect: (_Resident(dev).clip if rect else _Resident(dev).steps)(paths, m, *rect))
+    if own:
         R = _Resident(device)
-        if simplify_fn is None:                             # likewise, where this device's merge or (without one) its conversion left them
-            simplify_fn = R.simplify if (merge_fn is None if o.merge_paths else convert_fn is None) else device.gcode_simplify
-        if merge_fn is None:                                # where the conversion ran on this device its polylines are merged in place, else they are sent
-            merge_fn = R.merge if convert_fn is None else device.gcode_merge
-        flatten_fn = flatten_fn or R.flatten; bbox_fn = bbox_fn or R.bbox; fit_fn = fit_fn or R.fit; fetch_fn = fetch_fn or R.fetch; steps_fn = steps_fn or R.steps
-        clip_fn = clip_fn or R.clip
-        hatch_fn = hatch_fn or R.hatch
-        order_fn = order_fn or device.gcode_order
-        hatch_groups_fn = hatch_groups_fn or R.hatch_groups; source_fn = source_fn or R.source; order_pens_fn = order_pens_fn or R.order_pens
+        flatten_fn = flatten_fn or R.flatten; bbox_fn = bbox_fn or R.bbox; fit_fn = fit_fn or R.fit; fetch_fn = fetch_fn or R.fetch
+        hatch_fn = hatch_fn or R.hatch; hatch_groups_fn = hatch_groups_fn or R.hatch_groups
     paths, fi = fit_paths(table, o, flatten_fn, bbox_fn, fit_fn, tm)
     info.update(fi)
     if hp:
@@ -842,9 +830,7 @@ def build_stream_from_svg(text: Union[str, bytes, SegmentTable], opts: Optional[
     if want_paths:
         info["fitted_paths"] = (off_mm, np.asarray(pts_mm, np.float64).reshape(-1, 2))
     tm["fetch_paths"] = tm.get("fetch_paths", 0.0) + (time.perf_counter() - t0)
-    data, ginfo = GC.build_stream_from_gcode((off_mm, np.zeros((int(off_mm[-1]), 2))), go, device, steps_fn=lambda _off, _pts, m: steps_fn(paths, m), order_fn=order_fn,
-                                             codes_fn=codes_fn, pack_fn=pack_fn, timings=tm, pens=pens, order_pens_fn=order_pens_fn, source_fn=source_fn, merge_fn=merge_fn,
-                                             improve_fn=improve_fn, clip_fn=lambda _off, _pts, m, rect: clip_fn(paths, m, rect), simplify_fn=simplify_fn)
+    data, ginfo = GC.stroke_stream((off_mm, np.zeros((int(off_mm[-1]), 2))), go, device, steps, tm, pens)
     return data, dict(ginfo, **info)
 
 
@@ -893,19 +879,7 @@ def build_stream_argparser() -> argparse.ArgumentParser:
     ap.add_argument("--invert-y", type=int, default=d.invert_y, help="1: flip Y inside the canvas")
     ap.add_argument("--color-index", type=int, default=d.color_index, help="pen 0..7")
     ap.add_argument("--speed-scale", type=float, default=d.speed_scale, help="> 1 faster (smaller dividers), < 1 slower")
-    ap.add_argument("--no-reorder", action="store_true", help="keep the paths in file order")
-    ap.add_argument("--pen-order", default=None, help="pens in drawing order, comma-separated (default: ascending); pens without paths are skipped")
-    ap.add_argument("--allow-reverse", action="store_true", help="let the order draw a stroke backwards when its far end is nearer")
-    ap.add_argument("--merge-paths", action="store_true", help="draw strokes of one pen that meet end to end on the step grid as one stroke (no tolerance; where three or more ends meet, "
-                                                               "none are joined); the G-code file is not changed")
-    ap.add_argument("--improve-order", action="store_true", help="after the greedy order, lower the pen-up travel by 2-opt (with --allow-reverse) and or-opt moves, one per round, pen by pen; "
-                                                                 "the G-code file is not changed")
-    ap.add_argument("--improve-rounds", type=int, default=None, help="rounds per pen at most (default: 2 m + 64 for m strokes); needs --improve-order")
-    ap.add_argument("--clip", action="store_true", help="cut the strokes at the edge of the sheet and lift the pen outside it, instead of clamping every point onto the edge; "
-                                                        "the G-code file is not changed")
-    ap.add_argument("--clip-margin-mm", type=float, default=None, help="cut this far inside the edge of the sheet (default: 0); needs --clip")
-    ap.add_argument("--simplify-mm", type=float, default=None, help="drop the vertices that lie within this distance of the stroke (Ramer-Douglas-Peucker on the step grid; "
-                    "0: only vertices on the straight line between their neighbours)")
+    GC.add_stroke_args(ap, ("--no-reorder", "--pen-order", "--allow-reverse") + GC.STROKE_ARGS[3:], "; the G-code file is not changed")
     ap.add_argument("--no-preview", action="store_true", help="do not render <svg stem>_stream_preview.png")
     ap.add_argument("--preview-render-width", type=int, default=d.preview_render_width)
     ap.add_argument("--preview-render-height", type=int, default=d.preview_render_height)
@@ -973,17 +947,8 @@ def main_stream(argv: Optional[Sequence[str]] = None, **device_steps) -> None:
     print(f"[svg] {a.input}: {info['segments']} segments in {info['subpaths']} subpaths -> {len(pts)} points")
     if "hatch" in info:
         print("[svg] hatch: {groups} fill groups, {lines} lines, {crossings} crossings -> {segments} segments".format(**info["hatch"]))
-    if "clip" in info:
-        print(GC.clip_line("svg", info["clip"]))
-    if "pens" in info:
-        print("[svg] pens: " + ", ".join(f"{p}: {k} paths" for p, k in enumerate(info["pens"]["paths"]) if k) +
-              f"; {info['pens']['unmatched']} without a stroke colour, {info['pens']['reversed']} strokes reversed")
-    if "merge" in info:
-        print("[svg] merge: {paths_in} paths -> {paths_out}, {joins} pen lifts saved, {cycles} closed".format(**info["merge"]))
-    if "simplify" in info:
-        print(GC.simplify_line("svg", info["simplify"]))
-    if "improve" in info:
-        print(GC.improve_line("svg", info["improve"]))
+    for line in GC.report_lines("svg", info, unmatched=True):
+        print(line)
     print(f"[svg] G-code saved: {gcode_path}")
     print(f"stream saved: {stream_path} ({len(data)} bytes)")
     if o.no_preview:

@@ -348,6 +348,46 @@ int orip_gcode_merge_fetch(orip_ctx* ctx, int64_t* member_off /* [paths_out+1] *
 int orip_gcode_simplify(orip_ctx* ctx, const int64_t* off /* [n+1] or NULL */, const int32_t* pts /* [off[n],2] or NULL */, int64_t n, int32_t tol4,
                         int64_t* stats /* [4]: paths, points_in, points_out, rounds */);
 int orip_gcode_simplify_fetch(orip_ctx* ctx, int64_t* kept /* [points_out]: index of every output point in the input point list */);
+/* --dedup (csrc/gcode_dedup.hip; ours, the reference has no such pass on its vector front doors): collinear segments of one pen that lie over each other
+ * are drawn once.  Exact on the step grid: no tolerance, no rounding, no new coordinate.
+ * Input: n step polylines of two points or more, coordinates 0 .. 2^30, no two consecutive points equal (the conversions and the merge guarantee it; in
+ * the uploaded form a consecutive duplicate is an argument error), and one group per polyline (the pen's place in the drawing sequence; NULL = all 0).
+ *   Segments.  Stroke s with points v_0 .. v_{k-1} has the segments j = 0 .. k - 2, v_j -> v_{j+1}; segments are numbered by stroke, then by position: g.
+ *   Line.  d = v_{j+1} - v_j, q = gcd(|dx|, |dy|), u = d / q, negated when ux < 0 or ux == 0 and uy < 0; c = ux y - uy x, constant along the line, |c| <=
+ *   2^61: int64 throughout.  LINE = (group, ux, uy, c), compared in full.  Two segments can overlap in more than a point iff their LINEs are equal; strokes
+ *   of different pens never touch each other's ink.
+ *   Parameter.  tau(P) = x when ux > 0, else y: strictly monotone along the line.  A segment is the closed interval [lo, hi], lo < hi, of its ends' tau.
+ *   Survival.  The first drawn copy stays: of segment g there remains the closure of [lo, hi] minus the union of the intervals of all segments g' < g on
+ *   the same LINE, and of that the components of positive length, its PIECES; touching in a point covers nothing.  Every piece end is an end of the segment
+ *   itself or an end point of an earlier segment on the line: a grid point of the input.  Pieces are listed and oriented in the segment's drawing direction.
+ *   Strokes.  The pieces of a stroke's segments are taken in order.  Two consecutive pieces belong to one output stroke iff they meet at a vertex of the
+ *   stroke that both segments still reach: the first is the last piece of segment j - 1 and ends at v_j, the second is the first piece of segment j and
+ *   starts there.  A cut point only ever begins or ends a stroke.  An output stroke's points are the start of its first piece, then the end of every piece.
+ *   Output strokes keep the order of their input strokes and, inside one, the order along it.  origin[k] (orip_gcode_dedup_fetch) = the input stroke of
+ *   output stroke k: ascending, with repeats and gaps.
+ * Consequences.  Per group, the primitive lattice steps of the output (unordered pairs of neighbouring grid points on a segment) are a set, each once, equal
+ * to the support of the input's multiset: nothing drawn is lost, nothing is drawn twice.  A drawing in which no two segments share a primitive step comes
+ * back unchanged.  The pass is idempotent.  Every output stroke has two points or more and no equal consecutive points, and its interior vertices are input
+ * vertices.  pieces <= 2 segments (an end point cuts at most one later segment), so points_out <= 4 segments.  The drawn set does not depend on the strokes'
+ * directions; only which copy survives depends on the order: the lowest g.
+ * stats: segments, whole (survive untouched), cut (survive in part), covered (gone), pieces, paths_out, points_out, draw_steps_in, draw_steps_out; whole +
+ * cut + covered == segments; the two draw-step counts are the sums of max(|dx|, |dy|) over the segments in and over the pieces out, the stream compiler's
+ * cost of a pen-down move, additive along a line: the ink saved is an exact integer.
+ * off == NULL and pts == NULL: the resident step polylines, n must be their count (as for orip_gcode_merge).  In both forms the result BECOMES the resident
+ * step polylines.  The source indices follow: while they name the input (the resident form before a merge; an uploaded list of as many polylines as are
+ * resident is taken for them) they are gathered through origin, so orip_gcode_steps_source_fetch keeps giving the input path of every stroke, with repeats as
+ * after orip_gcode_to_steps_clip; any other uploaded list has no sources (as after a merge) until the next conversion.
+ * Errors before any launch, without a fault and with the resident polylines left as they were: n < 0 or n > 2^26, 2^28 points or more (the bound above then
+ * keeps the output under 2^30; scratch and output buffers are sized by the bound, some 195 bytes per segment, 52 GB at 2^28), off not starting at 0 or decreasing, a path under two points, a coordinate outside 0 .. 2^30, a point equal to the one
+ * before it, a group outside 0 .. n_groups - 1, n_groups outside 1 .. 64, exactly one of off / pts NULL, n that is not the resident count, NULL stats.
+ * n == 0 returns zeros before any launch.  An inconsistency found on the device (counts that do not add up) leaves no list.
+ * Declined: a tolerance for near-parallel or near-coincident lines (the answer would depend on a processing order; the raster path is the place for
+ * "close enough"), removing ink of one pen under another, keeping the longest copy instead of the first (one rule only), a bound on the worst case (many
+ * nested segments on one line are quadratic, and the result must not depend on a budget). */
+int orip_gcode_dedup(orip_ctx* ctx, const int64_t* off /* [n+1] or NULL */, const int32_t* pts /* [off[n],2] or NULL */, const int32_t* group /* [n] or NULL = all 0 */,
+                     int64_t n, int32_t n_groups /* 1..64 */,
+                     int64_t* stats /* [9]: segments, whole, cut, covered, pieces, paths_out, points_out, draw_steps_in, draw_steps_out */);
+int orip_gcode_dedup_fetch(orip_ctx* ctx, int32_t* origin /* [paths_out] */);
 /* --improve-order (csrc/gcode_improve.hip; ours, the reference stops at the greedy order): 2-opt and or-opt on a drawing sequence, by steepest descent.
  * Input: n step polylines given by their ends as for orip_gcode_order_pens (ends NULL = the resident ones, n must be their count), one group per polyline,
  * a start cursor, and a valid drawing sequence order[n], rev[n]: order is a permutation, the groups of its entries do not decrease, rev[k] is 0 or 1 and

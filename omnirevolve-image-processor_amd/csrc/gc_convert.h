@@ -28,13 +28,14 @@ __device__ __forceinline__ int64_t gc_path_of(const long long* __restrict__ off,
 // count, the map, fewer than 2^30 paths, the offsets; then, behind the caller's Carve of d_off[n + 1] and d_mm[total] (0 of each when resident), the upload
 int gc_mm_check(orip_ctx* c, const char* who, const int64_t* off, const double* pts_mm, int64_t n, const orip_gcode_map* map, bool others_ok, bool& resident, int64_t& total);
 int gc_mm_upload(orip_ctx* c, const char* who, const int64_t* off, const double* pts_mm, int64_t n, int64_t total, bool resident, long long*& d_off, double2*& d_mm);
-// step polylines, explicit or (off == pts == NULL) the n resident ones, at most 2^26: every check of the form, no state touched (no_repeats: no point equals
-// the one before it); then the upload that makes a checked explicit input the resident list.  gc_merged is the caller's, here and below
-int gc_steps_check(orip_ctx* c, const char* who, const int64_t* off, const int32_t* pts, int64_t n, bool no_repeats, int64_t& total);
+// step polylines, explicit or (off == pts == NULL) the n resident ones, at most 2^26, of fewer than 2^max_log2 points (looked at before any point is): every
+// check of the form, no state touched (no_repeats: no point equals the one before it); then the upload that makes a checked explicit input the resident list.  gc_merged is the caller's, here and below
+int gc_steps_check(orip_ctx* c, const char* who, const int64_t* off, const int32_t* pts, int64_t n, bool no_repeats, int64_t& total, int max_log2 = 30);
 int gc_steps_upload(orip_ctx* c, const char* who, const int64_t* off, const int32_t* pts, int64_t n, int64_t total);
 void gc_drop(orip_ctx* c);                                                              // no list: every reader fails until a writer succeeds
 int gc_publish_empty(orip_ctx* c, const char* who);                                     // the list of no polylines
 void gc_publish(orip_ctx* c, DBuf& off, DBuf& pts, int64_t n, int64_t total);           // a result in (off, pts) becomes the list: the buffers are swapped
+void gc_publish_src(orip_ctx* c, DBuf& src);                                            // the sources of the list just published, gathered by its writer: swapped in
 // the orders' checks: n polylines resident; n_groups in 1..64 and every path's group in range, counted into paths[] when given; the start point
 int gc_check_resident(orip_ctx* c, const char* who, int64_t n);
 int gc_check_groups(orip_ctx* c, const char* who, const int32_t* group, int64_t n, int32_t n_groups, int64_t* paths);

@@ -86,14 +86,19 @@ int gc_mm_upload(orip_ctx* c, const char* who, const int64_t* off, const double*
     HIPC_AS(c, who, hipMemcpyAsync(d_mm, pts_mm, (size_t)total * 16, hipMemcpyHostToDevice, LN(c).stream));
     return 0;
 }
-int gc_steps_check(orip_ctx* c, const char* who, const int64_t* off, const int32_t* pts, int64_t n, bool no_repeats, int64_t& total) {
+int gc_steps_check(orip_ctx* c, const char* who, const int64_t* off, const int32_t* pts, int64_t n, bool no_repeats, int64_t& total, int max_log2) {
     if (n < 0 || n > (1 << 26)) ORIP_FAIL_AS(c, who, "%lld paths: 0..2^26", (long long)n);
     if (!off != !pts) ORIP_FAIL_AS(c, who, "off and pts: both or neither");
-    if (!off) { total = c->gc_total; return gc_check_resident(c, who, n); }
+    if (!off) {
+        ORIP_TRY(gc_check_resident(c, who, n));
+        total = c->gc_total;
+        if (total >= (int64_t)1 << max_log2) ORIP_FAIL_AS(c, who, "%lld points: fewer than 2^%d", (long long)total, max_log2);
+        return 0;
+    }
     ORIP_TRY(gc_check_offsets(c, who, off, n));
     for (int64_t p = 0; p < n; p++) if (off[p + 1] - off[p] < 2) ORIP_FAIL_AS(c, who, "path %lld has fewer than two points", (long long)p);
     total = off[n];
-    if (total >= (int64_t)1 << 30) ORIP_FAIL_AS(c, who, "%lld points: fewer than 2^30", (long long)total);
+    if (total >= (int64_t)1 << max_log2) ORIP_FAIL_AS(c, who, "%lld points: fewer than 2^%d", (long long)total, max_log2);
     for (int64_t i = 0; i < 2 * total; i++) if (pts[i] < 0 || pts[i] > GC_COORD_MAX) ORIP_FAIL_AS(c, who, "point %lld: coordinate %d outside 0..2^30", (long long)(i / 2), pts[i]);
     for (int64_t p = 0; no_repeats && p < n; p++)
         for (int64_t i = off[p] + 1; i < off[p + 1]; i++)
@@ -111,6 +116,7 @@ int gc_steps_upload(orip_ctx* c, const char* who, const int64_t* off, const int3
 void gc_drop(orip_ctx* c) { c->gc_n = 0; c->gc_total = 0; c->gc_ready = false; c->gc_merged = false; }
 int gc_publish_empty(orip_ctx* c, const char* who) { static const int64_t zero = 0; return gc_steps_upload(c, who, &zero, nullptr, 0, 0); }
 void gc_publish(orip_ctx* c, DBuf& off, DBuf& pts, int64_t n, int64_t total) { std::swap(c->gc_off, off); std::swap(c->gc_pts, pts); c->gc_n = n; c->gc_total = total; }
+void gc_publish_src(orip_ctx* c, DBuf& src) { std::swap(c->gc_src, src); }
 int gc_check_resident(orip_ctx* c, const char* who, int64_t n) {
     if (!c->gc_ready || n != c->gc_n) ORIP_FAIL_AS(c, who, "%lld paths asked for, %lld step polylines resident", (long long)n, (long long)(c->gc_ready ? c->gc_n : -1));
     return 0;

@@ -331,7 +331,7 @@ struct orip_ctx {
     // came from, which names them while !gc_merged (a field of the merge's line below).  This block is the one statement of their contract; the helpers that
     // keep it are declared in gc_convert.h and defined in gcode.hip, and no other code writes these fields.
     //   Readers (fail while !gc_ready, or when the n they are given is not gc_n): orip_gcode_steps_fetch, orip_gcode_steps_source_fetch (also fails while
-    //   gc_merged), and for NULL input orip_gcode_order, orip_gcode_order_pens, orip_gcode_improve, orip_gcode_merge, orip_gcode_simplify.
+    //   gc_merged), and for NULL input orip_gcode_order, orip_gcode_order_pens, orip_gcode_improve, orip_gcode_merge, orip_gcode_simplify, orip_gcode_dedup.
     //   Writers, and what each leaves:
     //     orip_gcode_to_steps       drops the list on entry (gc_drop), before it looks at its arguments: after ANY failure there is no list.  Success: its
     //                               polylines and their sources, gc_merged cleared; no points to convert (n == 0 included): the empty list (gc_publish_empty).
@@ -344,6 +344,10 @@ struct orip_ctx {
     //     orip_gcode_simplify       as the merge, with sp_off / sp_pts, but strokes keep their number and order, so gc_merged is left as it is -- except that
     //                               an explicit input of another count than the resident one (or with no list resident) cannot be the polylines the sources
     //                               name: then, n == 0 included, gc_merged is set.  An explicit input of the resident count is taken for the polylines a fetch gave out.
+    //     orip_gcode_dedup          as the simplify, with dd_off / dd_pts and the same rule for an explicit input and gc_merged; but strokes are cut and vanish, so
+    //                               while !gc_merged the sources are gathered through origin and swapped in with the list (gc_publish_src, dd_src): gc_src keeps
+    //                               naming the input path of every stroke, with repeats as after the clip.  A device-found error (a repeated point in the
+    //                               resident list, pieces that do not add up) leaves no list.
     //   A failed HIP call inside a writer leaves what had been written up to it; gc_ready is false across an upload, so a list is never half there.
     DBuf gc_tmp, gc_off, gc_pts, gc_src, pk_tab, pk_out; int64_t gc_n = 0, gc_total = 0, pk_bytes = -1; bool gc_ready = false;
     // orip_gcode_order and orip_gcode_order_pens (gcode_order.hip: gc_grids), free between calls.  With n paths in G groups, m = n or 2n candidates (both ends
@@ -364,6 +368,10 @@ struct orip_ctx {
     // layout); sp_off / sp_pts = the output, swapped with gc_off / gc_pts when a call succeeds; sp_res = kept int64[sp_points], the input index of every
     // output point of the last call (-1: none) until the next one
     DBuf sp_tmp, sp_off, sp_pts, sp_res; int64_t sp_points = -1;
+    // --dedup (gcode_dedup.hip): dd_tmp = the sort words, the sorted intervals, the per-segment records and the scans, free between calls (the unit states the
+    // layout); dd_off / dd_pts = the output, swapped with gc_off / gc_pts when a call succeeds, dd_src = the gathered sources, swapped with gc_src then;
+    // dd_res = origin int32[dd_paths], the input stroke of every output stroke of the last call (-1: none) until the next one
+    DBuf dd_tmp, dd_off, dd_pts, dd_src, dd_res; int64_t dd_paths = -1;
     // svg2stream (svg.hip): scratch of the flattening and of the box, the resident paths (off int64[sv_n + 1], pts double2[sv_total]; raw units after
     // orip_svg_flatten, page mm after orip_svg_fit) until the next flatten; orip_gcode_to_steps reads them when it is called without pointers
     DBuf sv_tmp, sv_tmp2, sv_off, sv_pts; int64_t sv_n = 0, sv_total = 0; bool sv_ready = false, sv_box_ok = false; double sv_box[4] = {0, 0, 0, 0};

@@ -516,6 +516,29 @@ class Device:
         off_s, pts_s = self.gcode_steps_fetch(n, total)
         return off_s, pts_s, kept[:total], {k: int(v) for k, v in zip(("paths", "points_in", "points_out", "rounds"), st)}
 
+    def gcode_dedup(self, off, pts, group, n_groups: int, n: int | None = None):
+        """--dedup (include/orip.h: orip_gcode_dedup): of the collinear segments of one group that lie over each other on the step polylines (off int64 [n + 1],
+        pts int32 [total, 2]; both None = the n resident ones) only the first drawn copy stays, and what is left becomes the resident polylines.  group
+        int32 [n] or None (all 0).
+        -> (off int64, pts int32 [total', 2], origin int32 [paths_out]: the input stroke of every output stroke, {lib.DEDUP_STATS})"""
+        po, pp, n, _keep = _step_paths(off, pts, n)
+        g = None
+        if group is not None:
+            g = np.ascontiguousarray(group, np.int32).reshape(-1)
+            n = len(g) if n is None else n
+            if len(g) != n:
+                raise ValueError(f"{len(g)} groups given for {n} paths")
+        if n is None:
+            raise ValueError("n: the number of resident step polylines")
+        n = int(n)
+        st = np.zeros(9, np.int64)
+        self._ck(self.L.orip_gcode_dedup(self.h, po, pp, _p(g) if g is not None and n else None, n, int(n_groups), _p(st)))
+        paths, total = int(st[5]), int(st[6])
+        origin = np.zeros(max(paths, 1), np.int32)
+        self._ck(self.L.orip_gcode_dedup_fetch(self.h, _p(origin)))
+        off_s, pts_s = self.gcode_steps_fetch(paths, total)
+        return off_s, pts_s, origin[:paths], {k: int(v) for k, v in zip(_l.DEDUP_STATS, st)}
+
     def gcode_steps_fetch(self, n: int, total: int, points: bool = True) -> Tuple[np.ndarray, np.ndarray]:
         """the n resident step polylines of `total` points, as gcode_to_steps or gcode_merge left them: (off int64 [n + 1], pts int32 [total, 2]; zeros without `points`)"""
         off = np.zeros(int(n) + 1, np.int64); pts = np.zeros((max(int(total), 1), 2), np.int32)

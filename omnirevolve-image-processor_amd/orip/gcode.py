@@ -39,7 +39,15 @@ most --short-len-steps is drawn at --short-div; a curve flattened into chords th
 --simplify-mm T the vertices that lie within T of the stroke are dropped: Ramer-Douglas-Peucker per stroke on the step grid, exact in integers, the tolerance
 in quarter steps, tol4 = round(4 T steps_per_mm) (orip_gcode_simplify; include/orip.h states the rule).  0 is allowed: it removes exactly the vertices on
 the segment between their kept neighbours.  It runs after the merge, so that the joints inside a merged chain can go, and before the order; strokes, their
-ends, pens and sources do not change.  Without the option no device call is added and every byte is what it was."""
+ends, pens and sources do not change.  Without the option no device call is added and every byte is what it was.
+
+--dedup (ours as well): a map exported as one closed polygon per region, a table made of rectangles, a wall drawn over the walls it joins, a tracer that
+walks a thin feature out and back -- all hold the same line twice, and the second pass is a darker, wider line, a tear with a wet pen, and pen-down time.
+With --dedup collinear segments of one pen that lie over each other on the step grid are drawn once: the first drawn copy stays, of a later one only the
+stretches nothing earlier covers, cut at end points of the input (orip_gcode_dedup; include/orip.h states the rule, exact in integers, no tolerance).  It
+runs after the pens have been worked out and before the merge, which joins the pieces it leaves, and before the simplification, which would move two copies
+of a shared border apart.  A stroke can be cut into several and can vanish; pens and sources follow.  Allowed with --no-reorder: strokes keep file order.
+Without the option no device call is added and every byte is what it was."""
 from __future__ import annotations
 
 import argparse
@@ -95,6 +103,7 @@ class GcodeOptions:
     clip: bool = False                  # strokes are cut at the sheet's edge (less the margin) instead of clamped to it
     clip_margin_mm: Optional[float] = None  # the clip rectangle lies this far inside the sheet (None: 0); only with clip
     simplify_mm: Optional[float] = None     # vertices within this distance of the stroke are dropped (None: every vertex is drawn; 0: only those on the stroke)
+    dedup: bool = False                 # collinear segments of one pen that lie over each other are drawn once, the first drawn copy stays
 
 
 # ------------------------------------------------------------------ parse (:113-142, :177-300)
@@ -290,7 +299,7 @@ def build_stream_from_gcode(text_or_paths, opts: Optional[GcodeOptions] = None, 
                             order_fn: Optional[Callable] = None, codes_fn: Optional[Callable] = None, pack_fn: Optional[Callable] = None,
                             timings: Optional[dict] = None, pens: Optional[np.ndarray] = None, order_pens_fn: Optional[Callable] = None,
                             source_fn: Optional[Callable] = None, merge_fn: Optional[Callable] = None, improve_fn: Optional[Callable] = None,
-                            clip_fn: Optional[Callable] = None, simplify_fn: Optional[Callable] = None) -> Tuple[bytes, dict]:
+                            clip_fn: Optional[Callable] = None, simplify_fn: Optional[Callable] = None, dedup_fn: Optional[Callable] = None) -> Tuple[bytes, dict]:
     """The stream of a G-code text (str / bytes) or of paths in mm given as (off, pts_mm); opts as parsed, --speed-scale not yet applied.
     Device steps, each None = the GPU (orip.device.Device; there is no CPU path in the product):
       steps_fn(off, pts_mm, map: dict) -> (off int64, pts int32 [total, 2])      orip_gcode_to_steps
@@ -311,33 +320,40 @@ def build_stream_from_gcode(text_or_paths, opts: Optional[GcodeOptions] = None, 
     and, only with --simplify-mm (after the merge, before any order):
       simplify_fn(off, pts, tol4) -> (off, pts, kept int64: the input index of every output point, stats)       orip_gcode_simplify
     info["simplify"] then holds tol4, points_in, points_out and paths_changed.
+    and, only with --dedup (after the pens have been worked out, before the merge):
+      dedup_fn(off, pts, group int32 [n], n_groups) -> (off, pts, origin int32: the input stroke of every output stroke, stats)       orip_gcode_dedup
+    info["dedup"] then holds segments, whole, cut, covered, pieces, paths_out, points_out, draw_steps_in and draw_steps_out; a stroke keeps its origin's pen.
     pens: one pen per input path, 0..7, or -1 for --color-index (a text's T words under --tool-pens when None).  info["pens"] then counts the paths per
     pen, those that took --color-index ("unmatched") and the strokes drawn backwards ("reversed").
     Returns (bytes, counts)."""
-    steps = StrokeSteps(clip_fn if opts is not None and opts.clip else steps_fn, source_fn, merge_fn, simplify_fn, order_fn, order_pens_fn, improve_fn, codes_fn, pack_fn)
+    steps = StrokeSteps(clip_fn if opts is not None and opts.clip else steps_fn, source_fn, merge_fn, simplify_fn, order_fn, order_pens_fn, improve_fn, codes_fn, pack_fn,
+                        dedup_fn)
     return stroke_stream(text_or_paths, opts, device, steps, timings, pens)
 
 
 # The device steps of the stroke pipeline, each a callable or None = not given; build_stream_from_gcode states the signatures.  convert: steps_fn or, with --clip, clip_fn
-StrokeSteps = namedtuple("StrokeSteps", "convert source merge simplify order order_pens improve codes pack", defaults=(None,) * 9)
+StrokeSteps = namedtuple("StrokeSteps", "convert source merge simplify order order_pens improve codes pack dedup", defaults=(None,) * 10)
 
 
 def resolve_steps(st: StrokeSteps, o, grouped: bool, device=None, convert: Optional[Callable] = None, force: bool = False):
     """The steps the options need, those not given taken from a device -> (steps, device); codes and pack stay as given (orip.stream.compile_plan fills them).
     When none is missing, and the caller does not `force` a device for steps of its own, no device is made and orip.stages is not imported.  convert(device)
-    -> the conversion of a front door whose paths are on the device already (orip.svg).  Merge and simplify work on the polylines the pass before them left
-    resident when that pass ran on this device, and are sent their input when it was given."""
-    need = ["convert", "order"] + ["order_pens", "source"] * bool(grouped) + ["merge"] * bool(o.merge_paths) + ["improve"] * bool(o.improve_order) + ["simplify"] * (o.simplify_mm is not None)
+    -> the conversion of a front door whose paths are on the device already (orip.svg).  Dedup, merge and simplify work on the polylines the pass before them
+    left resident when that pass ran on this device, and are sent their input when it was given."""
+    need = ["convert", "order"] + ["order_pens", "source"] * bool(grouped) + ["merge"] * bool(o.merge_paths) + ["improve"] * bool(o.improve_order) + \
+        ["simplify"] * (o.simplify_mm is not None) + ["dedup"] * bool(o.dedup)
     if not force and all(getattr(st, k) is not None for k in need):
         return st, device
     if device is None:
         from .stages import device as _default_device
         device = _default_device()
     after_convert = st.convert is None                                     # resident behind this device's own conversion,
-    after_merge = st.merge is None if o.merge_paths else after_convert     # and behind its merge or, without one, behind the conversion
+    after_dedup = st.dedup is None if o.dedup else after_convert           # behind its dedup or, without one, behind the conversion,
+    after_merge = st.merge is None if o.merge_paths else after_dedup       # and behind its merge or, without one, behind what stands before the merge
     own = StrokeSteps(
         convert=convert(device) if convert is not None else device.gcode_to_steps_clip if o.clip else device.gcode_to_steps, source=device.gcode_steps_source,
-        merge=(lambda off, pts, group, n_groups, reverse: device.gcode_merge(None, None, group, n_groups, reverse, n=len(off) - 1)) if after_convert else device.gcode_merge,
+        merge=(lambda off, pts, group, n_groups, reverse: device.gcode_merge(None, None, group, n_groups, reverse, n=len(off) - 1)) if after_dedup else device.gcode_merge,
+        dedup=(lambda off, pts, group, n_groups: device.gcode_dedup(None, None, group, n_groups, n=len(off) - 1)) if after_convert else device.gcode_dedup,
         simplify=(lambda off, pts, t4: device.gcode_simplify(None, None, t4, n=len(off) - 1)) if after_merge else device.gcode_simplify,
         order=device.gcode_order, order_pens=device.gcode_order_pens,
         improve=lambda ends, group, n_groups, order, rev, reverse, max_rounds: device.gcode_improve(ends, group, n_groups, order, rev, reverse, max_rounds=max_rounds))
@@ -386,6 +402,37 @@ def _merge(st: StrokeSteps, o: GcodeOptions, off, pts, pen, group, n_groups: int
         pen, group = pen[first], group[first]
     info["paths"] = n
     info["merge"] = {"paths_in": n_in, "paths_out": n, "joins": int(mst["joins"]), "cycles": int(mst["cycles"])}
+    return off, pts, pen, group
+
+
+def draw_steps(off, pts) -> int:
+    """the pen-down steps of the strokes as the stream compiler counts them: max(|dx|, |dy|) per segment"""
+    d = np.abs(np.diff(np.asarray(pts, np.int64).reshape(-1, 2), axis=0)).max(1) if len(pts) > 1 else np.zeros(0, np.int64)
+    inner = np.ones(len(d), bool); inner[np.asarray(off[1:-1], np.int64) - 1] = False          # the gap between two strokes is not a segment
+    return int(d[inner].sum())
+
+
+def _dedup(st: StrokeSteps, off_in, pts_in, pen, group, n_groups: int, info: dict):
+    """the strokes less every stretch an earlier segment of the same pen has drawn; a stroke left in parts keeps its pen; info["dedup"]"""
+    n_in = len(off_in) - 1
+    off, pts, origin, dst = st.dedup(off_in, pts_in, group if group is not None else np.zeros(n_in, np.int32), n_groups)
+    off = np.asarray(off, np.int64).reshape(-1); pts = np.asarray(pts, np.int32).reshape(-1, 2); origin = np.asarray(origin, np.int64).reshape(-1)
+    d = {k: int(dst[k]) for k in DEDUP_STATS}
+    n = len(off) - 1
+    if n < 1 or len(origin) != n or (np.diff(origin) < 0).any() or origin[0] < 0 or origin[-1] >= n_in:
+        raise RuntimeError("the dedup's origins are not the input strokes in ascending order")
+    same = (np.diff(pts, axis=0) == 0).all(1) if len(pts) > 1 else np.zeros(0, bool)
+    if off[0] != 0 or int(off[-1]) != len(pts) or (np.diff(off) < 2).any() or np.delete(same, off[1:-1] - 1).any():
+        raise RuntimeError("the dedup returned a stroke of fewer than two points or with a repeated point")
+    if d["whole"] + d["cut"] + d["covered"] != d["segments"] or d["segments"] != len(pts_in) - n_in or d["paths_out"] != n or d["points_out"] != len(pts) or \
+            d["pieces"] != len(pts) - n or d["pieces"] > 2 * d["segments"] or d["draw_steps_in"] != draw_steps(off_in, pts_in) or d["draw_steps_out"] != draw_steps(off, pts):
+        raise RuntimeError("the dedup's counts do not add up")
+    if d["draw_steps_out"] > d["draw_steps_in"]:
+        raise RuntimeError("the dedup added ink")
+    if group is not None:
+        pen, group = pen[origin], group[origin]
+    info["paths"] = n
+    info["dedup"] = d
     return off, pts, pen, group
 
 
@@ -442,7 +489,7 @@ def _plan(o: GcodeOptions, sc: ST.StreamConfig, off, pts, path_pen) -> ST.Plan:
 
 
 def stroke_stream(text_or_paths, opts: Optional[GcodeOptions], device, steps: StrokeSteps, timings: Optional[dict] = None, pens: Optional[np.ndarray] = None) -> Tuple[bytes, dict]:
-    """build_stream_from_gcode with the device steps as one record: parse, convert, pens of the strokes, merge, simplify, order, plan, compile"""
+    """build_stream_from_gcode with the device steps as one record: parse, convert, pens of the strokes, dedup, merge, simplify, order, plan, compile"""
     import time
     o = apply_speed_scale(GcodeOptions(**{f.name: getattr(opts, f.name) for f in fields(GcodeOptions)}) if opts is not None else GcodeOptions())
     W, H = target_size(o)
@@ -484,16 +531,22 @@ def stroke_stream(text_or_paths, opts: Optional[GcodeOptions], device, steps: St
     if n == 0:
         return EMPTY_STREAM, dict(info, bytes=len(EMPTY_STREAM))
     pen, group = _stroke_pens(st, o, pens, n, info) if grouped else (None, None)
+    n_groups = MAX_PENS if pens is not None else 1
+    if o.dedup:
+        lap("order")                                                      # the sources and the pens belong to the order's lap
+        off, pts, pen, group = _dedup(st, off, pts, pen, group, n_groups, info)
+        lap("dedup")
     if o.merge_paths:
-        lap("order")                                                      # the sources and the pens belong to the order's lap, as before
-        off, pts, pen, group = _merge(st, o, off, pts, pen, group, MAX_PENS if pens is not None else 1, info)
+        if not o.dedup:
+            lap("order")                                                  # the sources and the pens belong to the order's lap, as before
+        off, pts, pen, group = _merge(st, o, off, pts, pen, group, n_groups, info)
         lap("merge")
     if tol4 is not None:
-        if not o.merge_paths:
+        if not (o.merge_paths or o.dedup):
             lap("order")
         off, pts = _simplify(st, off, pts, tol4, info)
         lap("simplify")
-    order, rev = _order(st, o, off, pts, group, MAX_PENS if pens is not None else 1, info, lap)
+    order, rev = _order(st, o, off, pts, group, n_groups, info, lap)
     if order is not None:
         off, pts = gather_paths(off, pts, order, rev)
     if grouped:
@@ -508,6 +561,7 @@ def stroke_stream(text_or_paths, opts: Optional[GcodeOptions], device, steps: St
 
 IMPROVE_STATS = ("travel_before", "travel_after", "rounds", "converged_groups", "skipped_groups")
 CLIP_STATS = ("segments", "inside", "cut", "outside", "paths_out", "points_out")
+DEDUP_STATS = ("segments", "whole", "cut", "covered", "pieces", "paths_out", "points_out", "draw_steps_in", "draw_steps_out")      # include/orip.h: orip_gcode_dedup
 SIMPLIFY_TOL4_MAX = (1 << 17) - 1             # include/orip.h: ORIP_SIMPLIFY_TOL4_MAX
 
 
@@ -596,11 +650,11 @@ def build_argparser() -> argparse.ArgumentParser:
     return ap
 
 
-STROKE_ARGS = ("--no-reorder", "--allow-reverse", "--pen-order", "--merge-paths", "--improve-order", "--improve-rounds", "--clip", "--clip-margin-mm", "--simplify-mm")
+STROKE_ARGS = ("--no-reorder", "--allow-reverse", "--pen-order", "--merge-paths", "--improve-order", "--improve-rounds", "--clip", "--clip-margin-mm", "--simplify-mm", "--dedup")
 
 
 def add_stroke_args(ap: argparse.ArgumentParser, names: Sequence[str] = STROKE_ARGS, suffix: str = "") -> None:
-    """the options of the stroke passes, those of `names` in that order; `suffix` ends the help of the three that change what is drawn but not the G-code file"""
+    """the options of the stroke passes, those of `names` in that order; `suffix` ends the help of the four that change what is drawn but not the G-code file"""
     flag, number = dict(action="store_true"), dict(default=None)
     table = {
         "--no-reorder": (flag, "keep the paths in file order"),
@@ -613,6 +667,7 @@ def add_stroke_args(ap: argparse.ArgumentParser, names: Sequence[str] = STROKE_A
         "--clip-margin-mm": (dict(number, type=float), "cut this far inside the edge of the sheet (default: 0); needs --clip"),
         "--simplify-mm": (dict(number, type=float), "drop the vertices that lie within this distance of the stroke (Ramer-Douglas-Peucker on the step grid; "
                                                     "0: only vertices on the straight line between their neighbours)"),
+        "--dedup": (flag, "draw collinear segments of one pen that lie over each other on the step grid once: the first drawn copy stays (no tolerance)" + suffix),
     }
     for name in names:
         ap.add_argument(name, help=table[name][1], **table[name][0])
@@ -627,6 +682,9 @@ def report_lines(tag: str, info: dict, unmatched: bool = False):
     if "pens" in info:
         yield (f"[{tag}] pens: " + ", ".join(f"{p}: {k} paths" for p, k in enumerate(info["pens"]["paths"]) if k) + "; " +
                (f"{info['pens']['unmatched']} without a stroke colour, " if unmatched else "") + f"{info['pens']['reversed']} strokes reversed")
+    if "dedup" in info:
+        yield (f"[{tag}] " + "dedup: {segments} segments: {whole} whole, {cut} cut, {covered} covered -> {paths_out} strokes, "
+                              "pen-down steps {draw_steps_in} -> {draw_steps_out}".format(**info["dedup"]))
     if "merge" in info:
         yield f"[{tag}] " + "merge: {paths_in} paths -> {paths_out}, {joins} pen lifts saved, {cycles} closed".format(**info["merge"])
     if "simplify" in info:

@@ -42,6 +42,10 @@ the pens of the cut strokes still come through the sources, and the G-code file 
 grid and on the device (orip_gcode_simplify), after the merge and before the order.  It is forwarded as it is; the G-code file is not changed, and
 --tolerance-mm keeps its meaning (how far a chord may lie from its curve; this option then thins the chords that the pen cannot tell apart).
 
+--dedup (off unless given; ours, orip/gcode.py states it): collinear segments of one pen that lie over each other on the step grid -- the shared border of
+two regions, the inner edges of a table of <rect>s -- are drawn once, on the device (orip_gcode_dedup), after the pens and before the merge.  Hatch lines
+go through it like any path.  It is forwarded as it is; the G-code file is not changed.
+
 The device steps are injectable, as in orip/gcode.py, so that this host logic can be tested without a GPU; the product has no CPU path."""
 from __future__ import annotations
 
@@ -555,6 +559,7 @@ class SvgOptions:
     clip: bool = False                                  # strokes are cut at the sheet's edge instead of clamped to it (orip.gcode)
     clip_margin_mm: Optional[float] = None              # the clip rectangle lies this far inside the sheet; None: 0
     simplify_mm: Optional[float] = None                 # vertices within this distance of the stroke are dropped (orip.gcode); None: none are
+    dedup: bool = False                                 # collinear segments of one pen that lie over each other are drawn once (orip.gcode)
 
 
 HATCH_DIRECTIONS = {"horizontal": HATCH_HORIZONTAL, "vertical": HATCH_VERTICAL, "cross": HATCH_HORIZONTAL | HATCH_VERTICAL}
@@ -654,7 +659,7 @@ def gcode_options(o: SvgOptions) -> GC.GcodeOptions:
                            offset_x_mm=0.0, offset_y_mm=0.0, target_width_steps=W, target_height_steps=H, no_reorder=bool(o.no_reorder),
                            allow_reverse=bool(o.allow_reverse), pen_order=o.pen_order, merge_paths=bool(o.merge_paths),
                            improve_order=bool(o.improve_order), improve_rounds=o.improve_rounds, clip=bool(o.clip), clip_margin_mm=o.clip_margin_mm,
-                           simplify_mm=o.simplify_mm)
+                           simplify_mm=o.simplify_mm, dedup=bool(o.dedup))
 
 
 def gcode_text(off, pts, passes: int = 1, pens=None) -> str:
@@ -765,7 +770,7 @@ def build_stream_from_svg(text: Union[str, bytes, SegmentTable], opts: Optional[
                           steps_fn: Optional[Callable] = None, order_fn: Optional[Callable] = None, codes_fn: Optional[Callable] = None, pack_fn: Optional[Callable] = None, timings: Optional[dict] = None,
                           want_paths: bool = False, hatch_groups_fn: Optional[Callable] = None, source_fn: Optional[Callable] = None,
                           order_pens_fn: Optional[Callable] = None, merge_fn: Optional[Callable] = None, improve_fn: Optional[Callable] = None,
-                          clip_fn: Optional[Callable] = None, simplify_fn: Optional[Callable] = None) -> Tuple[bytes, dict]:
+                          clip_fn: Optional[Callable] = None, simplify_fn: Optional[Callable] = None, dedup_fn: Optional[Callable] = None) -> Tuple[bytes, dict]:
     """The stream of an SVG text (or of a parsed SegmentTable).  Device steps, each None = the GPU (there is no CPU path in the product):
       flatten_fn(table, tol_raw) -> paths          orip_svg_flatten      (`paths` is whatever the other steps take: on the GPU a count, the points stay there)
       bbox_fn(paths) -> (min x, min y, max x, max y)   orip_svg_bbox
@@ -785,6 +790,8 @@ def build_stream_from_svg(text: Union[str, bytes, SegmentTable], opts: Optional[
       clip_fn(paths, map, rect) -> (off, pts int32, stats)   orip_gcode_to_steps_clip without pointers
     and, only with --simplify-mm:
       simplify_fn                                  as in orip.gcode.build_stream_from_gcode (a hatch line has two points and passes through untouched)
+    and, only with --dedup:
+      dedup_fn                                     as in orip.gcode.build_stream_from_gcode (hatch lines go through it like any path)
     With --pen-colors, info["path_pens"] is the pen of every fitted path (hatch lines included, --color-index where no stroke is stated).
     Returns (bytes, info)."""
     import time
@@ -809,7 +816,7 @@ def build_stream_from_svg(text: Union[str, bytes, SegmentTable], opts: Optional[
     pens_on = o.pen_colors is not None
     given = clip_fn if o.clip else steps_fn                 # the stroke steps take (off, pts_mm, ...); here the conversion takes the fitted paths where they are
     steps = GC.StrokeSteps(None if given is None else (lambda _off, _pts, m, *rect: given(paths, m, *rect)), source_fn, merge_fn, simplify_fn, order_fn, order_pens_fn,
-                           improve_fn, codes_fn, pack_fn)
+                           improve_fn, codes_fn, pack_fn, dedup_fn)
     own = any(f is None for f in (flatten_fn, bbox_fn, fit_fn, fetch_fn)) or (hp and hatch_fn is None) or (pens_on and hp and hatch_groups_fn is None)
     steps, device = GC.resolve_steps(steps, go, pens_on or o.allow_reverse, device, force=bool(own),
                                      convert=lambda dev: lambda _off, _pts, m, *rect: (_Resident(dev).clip if rect else _Resident(dev).steps)(paths, m, *rect))

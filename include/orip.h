@@ -388,6 +388,65 @@ int orip_gcode_dedup(orip_ctx* ctx, const int64_t* off /* [n+1] or NULL */, cons
                      int64_t n, int32_t n_groups /* 1..64 */,
                      int64_t* stats /* [9]: segments, whole, cut, covered, pieces, paths_out, points_out, draw_steps_in, draw_steps_out */);
 int orip_gcode_dedup_fetch(orip_ctx* ctx, int32_t* origin /* [paths_out] */);
+/* --occlude (csrc/gcode_occlude.hip; ours, the reference has no such pass): filled shapes hide what lies under them.  Hidden-line removal on the step
+ * grid, after the conversion, in exact integer and rational arithmetic: no floating point behind gc_round_mm, no tolerance.
+ * Input.  STROKES: n step polylines of two points or more, coordinates 0 .. 2^30, no two consecutive points equal, and level[k] in 0 .. 2^30 - 1 per
+ *   stroke.  RINGS: m rings of one point or more, coordinates -2^30 .. 2^30 (a ring may leave the sheet under --clip), ring_level[r] in 0 .. 2^30 - 1,
+ *   NON-DECREASING.  A ring is closed by the edge from its last point to its first; edges of zero length are ignored.  All rings of one level form one
+ *   SHAPE (an element's holes work); a shape's level is its place in paint order, higher is painted later.
+ *   Inside.  A rational point P is INSIDE a shape iff P lies on none of its edges and a ray from P that meets no vertex crosses an odd number of them:
+ *   even-odd, whatever fill-rule says (the deviation the hatch states).  The boundary is not inside: a shape hides its open interior only, so the border
+ *   two neighbouring regions share is never removed here (both copies stay and --dedup, which runs next, takes the second), and a stroke that runs along
+ *   an edge of the shape above it stays.
+ *   Hidden.  A point of stroke k is HIDDEN iff it is inside some shape with level > level[k], strictly: neither a shape's own outline nor its hatch is
+ *   hidden by that shape.  Shapes hide across pens.
+ *   Pieces.  Segment j of a stroke is P(t) = v_j + t (v_{j+1} - v_j), t in [0, 1].  Its visible set, the t whose point is not hidden, is closed and a
+ *   finite union of intervals and single points; its PIECES are the components of positive length [t0, t1], in order (isolated visible points are not
+ *   pieces).  A piece end with t = 0 or t = 1 is the vertex itself.  Any other end is an exact rational point of the segment, where it meets an edge or
+ *   where a collinear overlap with one ends; each coordinate v + num / den of it is rounded as v + floor(num / den) + (2 rem >= den): to the nearest
+ *   step, halves toward +infinity, the rounding of step 2 of orip_gcode_to_steps_clip.  It is a function of the exact point, so a stroke and its reverse
+ *   are cut at the same grid points; a cut point may sit up to half a step off the true line: that is the grid.  A piece whose two rounded ends coincide
+ *   is dropped and counted in `collapsed`.
+ *   Strokes.  The pieces of a stroke are taken in order.  Two consecutive pieces belong to one output stroke iff the first is the last piece of segment
+ *   j - 1 and has t1 = 1, the second is the first piece of segment j and has t0 = 0, and neither was dropped.  A cut point only ever begins or ends a
+ *   stroke.  An output stroke's points are the start of its first piece, then the end of every piece.  Output strokes keep the order of their input
+ *   strokes and, inside one, the order along it; origin[k] (orip_gcode_occlude_fetch) = the input stroke of output stroke k, ascending, with repeats and gaps.
+ * Bit widths.  Differences are up to 2^31 in magnitude; a cross product of two differences reaches 2^63 and does not fit int64; a crossing parameter is
+ * num / den with both up to 2^63; two parameters are compared through products of up to 2^126; num * d in the rounding is up to 2^94.  The rule runs on
+ * 128-bit integers throughout, as the simplify does: no 64-bit shortcut, no floating point.
+ * Consequences.  A drawing with no ring above any stroke comes back unchanged, origin = 0 .. n - 1.  Every output stroke has two points or more and no
+ * repeated point, and its interior vertices are input vertices.  whole + cut + hidden == segments and pieces - collapsed == points_out - paths_out.  For a
+ * rectilinear drawing every cut is a grid point, nothing collapses, the output's primitive lattice steps are exactly the input's whose midpoint is not
+ * hidden, each once and in order, and the pass is idempotent.  The set of drawn segments and the segment counts do not change when a stroke is reversed.
+ * Nothing depends on the pens.
+ * stats: segments, whole (one piece, [0, 1]), cut (any other segment with a piece, dropped ones included), hidden (no piece), pieces (dropped ones
+ * included), collapsed, paths_out, points_out, draw_steps_in, draw_steps_out (sums of max(|dx|, |dy|) over the segments in and the kept pieces out).
+ * orip_gcode_occlude: strokes explicit, or off == pts == NULL for the n resident step polylines (as for orip_gcode_dedup); rings explicit, in steps.
+ * orip_svg_occlude: strokes are the resident step polylines; ring r is the resident fitted path ring_sub[r] (they stay resident behind the conversion),
+ * converted on the device by the conversion's own code (csrc/gc_convert.h) and not otherwise touched: no point is dropped.  With ORIP_OCCLUDE_CLAMP it is
+ * clamped to the sheet as orip_gcode_to_steps clamps, without the flag it is left as orip_gcode_to_steps_clip's conversion leaves it.  A ring coordinate
+ * that is not finite or lies outside +-2^30 is found on the device: an error that leaves no list, as in the clip.
+ * In every form the result BECOMES the resident step polylines, and the sources follow as in the dedup: while they name the input they are gathered through
+ * origin; an uploaded list of another count than the resident one has no sources until the next conversion.
+ * Errors before any launch, without a fault and with the resident polylines left as they were: the stroke errors of orip_gcode_dedup (2^28 points or
+ * more among them), a level out of range, m < 0 or m > 2^26, 2^28 ring points or more, ring_off not starting at 0 or decreasing, a ring of no points, a
+ * ring coordinate outside +-2^30 (explicit form), ring_level decreasing or out of range, ring_sub outside the resident fitted paths, a wrong resident
+ * count, unknown flags, a bad map, NULL stats or NULL arrays.  n == 0 returns zeros and (explicit form) the empty list before any launch; m == 0, or no
+ * ring above the lowest stroke, is legal and returns the input.  The output is not bounded by the input (a comb of E edges cuts one segment into E / 2 + 1
+ * pieces), so the pass counts first and emits second; 2^30 output points or more is an error found after the count that leaves no list, and so does an
+ * inconsistency found on the device.
+ * Declined: fill-opacity, opacity and fills of white or none treated specially (a stated fill occludes, nothing else); fill-rule="nonzero"; clip-path and
+ * mask; a shape hiding its own outline or hatch; a tolerance or an inset around the shape (the boundary is exact, "a little more" is a drawing decision);
+ * occlusion in mm before the rounding to steps (double rounding); a bound on the worst case (every segment against every edge of every shape above whose
+ * box it meets, and the result must not depend on a budget). */
+#define ORIP_OCCLUDE_CLAMP 1
+#define ORIP_OCCLUDE_STATS 10
+int orip_gcode_occlude(orip_ctx* ctx, const int64_t* off /* [n+1] or NULL */, const int32_t* pts /* [off[n],2] or NULL */, const int32_t* level /* [n] */, int64_t n,
+                       const int64_t* ring_off /* [m+1] */, const int32_t* ring_pts /* [ring_off[m],2] */, const int32_t* ring_level /* [m] */, int64_t m,
+                       int64_t* stats /* [10]: segments, whole, cut, hidden, pieces, collapsed, paths_out, points_out, draw_steps_in, draw_steps_out */);
+int orip_svg_occlude(orip_ctx* ctx, const int32_t* level /* [n] */, int64_t n, const int32_t* ring_sub /* [m] */, const int32_t* ring_level /* [m] */, int64_t m,
+                     const orip_gcode_map* map, int32_t flags /* ORIP_OCCLUDE_CLAMP */, int64_t* stats /* [10] */);
+int orip_gcode_occlude_fetch(orip_ctx* ctx, int32_t* origin /* [paths_out] */);
 /* --improve-order (csrc/gcode_improve.hip; ours, the reference stops at the greedy order): 2-opt and or-opt on a drawing sequence, by steepest descent.
  * Input: n step polylines given by their ends as for orip_gcode_order_pens (ends NULL = the resident ones, n must be their count), one group per polyline,
  * a start cursor, and a valid drawing sequence order[n], rev[n]: order is a permutation, the groups of its entries do not decrease, rev[k] is 0 or 1 and

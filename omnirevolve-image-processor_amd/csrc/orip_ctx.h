@@ -331,7 +331,7 @@ struct orip_ctx {
     // came from, which names them while !gc_merged (a field of the merge's line below).  This block is the one statement of their contract; the helpers that
     // keep it are declared in gc_convert.h and defined in gcode.hip, and no other code writes these fields.
     //   Readers (fail while !gc_ready, or when the n they are given is not gc_n): orip_gcode_steps_fetch, orip_gcode_steps_source_fetch (also fails while
-    //   gc_merged), and for NULL input orip_gcode_order, orip_gcode_order_pens, orip_gcode_improve, orip_gcode_merge, orip_gcode_simplify, orip_gcode_dedup.
+    //   gc_merged), and for NULL input orip_gcode_order, orip_gcode_order_pens, orip_gcode_improve, orip_gcode_merge, orip_gcode_simplify, orip_gcode_dedup, orip_gcode_occlude; orip_svg_occlude always.
     //   Writers, and what each leaves:
     //     orip_gcode_to_steps       drops the list on entry (gc_drop), before it looks at its arguments: after ANY failure there is no list.  Success: its
     //                               polylines and their sources, gc_merged cleared; no points to convert (n == 0 included): the empty list (gc_publish_empty).
@@ -348,6 +348,11 @@ struct orip_ctx {
     //                               while !gc_merged the sources are gathered through origin and swapped in with the list (gc_publish_src, dd_src): gc_src keeps
     //                               naming the input path of every stroke, with repeats as after the clip.  A device-found error (a repeated point in the
     //                               resident list, pieces that do not add up) leaves no list.
+    //     orip_gcode_occlude, orip_svg_occlude   as the dedup, with oc_off / oc_pts / oc_src and the same rule for an explicit input and gc_merged: checks
+    //                               first (strokes, levels, rings: an argument error leaves the list as it was); n == 0 leaves the empty list (explicit form) or
+    //                               the resident one, which is empty; success swaps the pieces in and, while !gc_merged, the sources gathered through origin.
+    //                               A device-found error (a ring coordinate not finite or out of range, a repeated point in the resident list, 2^30
+    //                               output points or more, pieces that do not add up) leaves no list.
     //   A failed HIP call inside a writer leaves what had been written up to it; gc_ready is false across an upload, so a list is never half there.
     DBuf gc_tmp, gc_off, gc_pts, gc_src, pk_tab, pk_out; int64_t gc_n = 0, gc_total = 0, pk_bytes = -1; bool gc_ready = false;
     // orip_gcode_order and orip_gcode_order_pens (gcode_order.hip: gc_grids), free between calls.  With n paths in G groups, m = n or 2n candidates (both ends
@@ -372,6 +377,11 @@ struct orip_ctx {
     // layout); dd_off / dd_pts = the output, swapped with gc_off / gc_pts when a call succeeds, dd_src = the gathered sources, swapped with gc_src then;
     // dd_res = origin int32[dd_paths], the input stroke of every output stroke of the last call (-1: none) until the next one
     DBuf dd_tmp, dd_off, dd_pts, dd_src, dd_res; int64_t dd_paths = -1;
+    // --occlude (gcode_occlude.hip): oc_tmp = the levels, the rings and their edges, the shapes' tables, the per-segment records and the scans; oc_ev = the
+    // events, the hidden intervals and the pieces of the segments that meet a shape (the unit states both layouts), free between calls; oc_off / oc_pts =
+    // the output, swapped with gc_off / gc_pts when a call succeeds, oc_src = the gathered sources, swapped with gc_src then; oc_res = origin
+    // int32[oc_paths], the input stroke of every output stroke of the last call (-1: none) until the next one
+    DBuf oc_tmp, oc_ev, oc_off, oc_pts, oc_src, oc_res; int64_t oc_paths = -1;
     // svg2stream (svg.hip): scratch of the flattening and of the box, the resident paths (off int64[sv_n + 1], pts double2[sv_total]; raw units after
     // orip_svg_flatten, page mm after orip_svg_fit) until the next flatten; orip_gcode_to_steps reads them when it is called without pointers
     DBuf sv_tmp, sv_tmp2, sv_off, sv_pts; int64_t sv_n = 0, sv_total = 0; bool sv_ready = false, sv_box_ok = false; double sv_box[4] = {0, 0, 0, 0};

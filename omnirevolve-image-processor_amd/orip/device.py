@@ -539,6 +539,51 @@ class Device:
         off_s, pts_s = self.gcode_steps_fetch(paths, total)
         return off_s, pts_s, origin[:paths], {k: int(v) for k, v in zip(_l.DEDUP_STATS, st)}
 
+    def _occlude_result(self, st):
+        paths, total = int(st[6]), int(st[7])
+        origin = np.zeros(max(paths, 1), np.int32)
+        self._ck(self.L.orip_gcode_occlude_fetch(self.h, _p(origin)))
+        off_s, pts_s = self.gcode_steps_fetch(paths, total)
+        return off_s, pts_s, origin[:paths], {k: int(v) for k, v in zip(_l.OCCLUDE_STATS, st)}
+
+    def gcode_occlude(self, off, pts, level, ring_off, ring_pts, ring_level, n: int | None = None):
+        """--occlude (include/orip.h: orip_gcode_occlude): of the step polylines (off int64 [n + 1], pts int32 [total, 2]; both None = the n resident ones)
+        with level int32 [n] only what no shape of a higher level hides stays, and that becomes the resident polylines.  The shapes are the rings ring_off
+        int64 [m + 1], ring_pts int32 [R, 2] (steps, -2^30 .. 2^30) with ring_level int32 [m], non-decreasing; the rings of one level are one shape.
+        -> (off int64, pts int32 [total', 2], origin int32 [paths_out]: the input stroke of every output stroke, {lib.OCCLUDE_STATS})"""
+        po, pp, n, _keep = _step_paths(off, pts, n)
+        lv = np.ascontiguousarray(level, np.int32).reshape(-1)
+        n = len(lv) if n is None else int(n)
+        if len(lv) != n:
+            raise ValueError(f"{len(lv)} levels given for {n} paths")
+        ro = np.ascontiguousarray(ring_off, np.int64).reshape(-1)
+        rp = np.ascontiguousarray(ring_pts, np.int32).reshape(-1, 2)
+        rl = np.ascontiguousarray(ring_level, np.int32).reshape(-1)
+        m = len(rl)
+        if len(ro) != m + 1 or (m and len(rp) < int(ro[-1])):
+            raise ValueError(f"{len(ro)} ring offsets and {len(rp)} ring points given for {m} rings")
+        st = np.zeros(10, np.int64)
+        self._ck(self.L.orip_gcode_occlude(self.h, po, pp, _p(lv) if n else None, n, _p(ro) if m else None, _p(rp) if m and len(rp) else None, _p(rl) if m else None, m, _p(st)))
+        return self._occlude_result(st)
+
+    def svg_occlude(self, level, ring_sub, ring_level, map: dict, clamp: bool, n: int | None = None):
+        """--occlude on the resident step polylines (include/orip.h: orip_svg_occlude): ring r is the resident fitted path ring_sub[r], converted on the
+        device as the conversion converts (map: the conversion's; clamp: to the sheet, as gcode_to_steps, or not, as gcode_to_steps_clip).
+        -> (off, pts, origin, stats) as gcode_occlude"""
+        lv = np.ascontiguousarray(level, np.int32).reshape(-1)
+        n = len(lv) if n is None else int(n)
+        if len(lv) != n:
+            raise ValueError(f"{len(lv)} levels given for {n} paths")
+        rs = np.ascontiguousarray(ring_sub, np.int32).reshape(-1)
+        rl = np.ascontiguousarray(ring_level, np.int32).reshape(-1)
+        if len(rs) != len(rl):
+            raise ValueError(f"{len(rs)} rings and {len(rl)} ring levels")
+        m = len(rl)
+        gm = _l.GcodeMap(**{k: map[k] for k, _ in _l.GcodeMap._fields_})
+        st = np.zeros(10, np.int64)
+        self._ck(self.L.orip_svg_occlude(self.h, _p(lv) if n else None, n, _p(rs) if m else None, _p(rl) if m else None, m, C.byref(gm), _l.OCCLUDE_CLAMP if clamp else 0, _p(st)))
+        return self._occlude_result(st)
+
     def gcode_steps_fetch(self, n: int, total: int, points: bool = True) -> Tuple[np.ndarray, np.ndarray]:
         """the n resident step polylines of `total` points, as gcode_to_steps or gcode_merge left them: (off int64 [n + 1], pts int32 [total, 2]; zeros without `points`)"""
         off = np.zeros(int(n) + 1, np.int64); pts = np.zeros((max(int(total), 1), 2), np.int32)

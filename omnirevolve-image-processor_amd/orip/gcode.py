@@ -335,28 +335,46 @@ def build_stream_from_gcode(text_or_paths, opts: Optional[GcodeOptions] = None, 
 StrokeSteps = namedtuple("StrokeSteps", "convert source merge simplify order order_pens improve codes pack dedup", defaults=(None,) * 10)
 
 
-def resolve_steps(st: StrokeSteps, o, grouped: bool, device=None, convert: Optional[Callable] = None, force: bool = False):
+class Occlude:
+    """--occlude of the SVG door (orip.svg states it), which StrokeSteps does not carry: fn(off, pts, level int32 [n], ring_sub, ring_level, map, clamp) ->
+    (off, pts, origin int32: the input stroke of every output stroke, stats) or None = the device (orip_svg_occlude); path_level = the level of every
+    input path, which a stroke takes through its source; the rings as fitted paths and their levels; clamp = the rings are clamped as the strokes were"""
+    def __init__(self, fn, path_level, ring_sub, ring_level, clamp: bool):
+        self.fn = fn; self.path_level = np.asarray(path_level, np.int64).reshape(-1)
+        self.ring_sub = np.asarray(ring_sub, np.int32).reshape(-1); self.ring_level = np.asarray(ring_level, np.int32).reshape(-1); self.clamp = bool(clamp)
+
+
+def resolve_steps(st: StrokeSteps, o, grouped: bool, device=None, convert: Optional[Callable] = None, force: bool = False, occlude: Optional[Occlude] = None):
     """The steps the options need, those not given taken from a device -> (steps, device); codes and pack stay as given (orip.stream.compile_plan fills them).
     When none is missing, and the caller does not `force` a device for steps of its own, no device is made and orip.stages is not imported.  convert(device)
     -> the conversion of a front door whose paths are on the device already (orip.svg).  Dedup, merge and simplify work on the polylines the pass before them
-    left resident when that pass ran on this device, and are sent their input when it was given."""
+    left resident when that pass ran on this device, and are sent their input when it was given.  `occlude`: its fn is filled in the same way; it needs the
+    sources whether or not pens are in use, and the rings are fitted paths that only the device's own conversion leaves next to the strokes, so behind a
+    given conversion the strokes are uploaded first (an occlusion without rings makes them the resident list) and the pass then runs as it does otherwise."""
     need = ["convert", "order"] + ["order_pens", "source"] * bool(grouped) + ["merge"] * bool(o.merge_paths) + ["improve"] * bool(o.improve_order) + \
-        ["simplify"] * (o.simplify_mm is not None) + ["dedup"] * bool(o.dedup)
-    if not force and all(getattr(st, k) is not None for k in need):
+        ["simplify"] * (o.simplify_mm is not None) + ["dedup"] * bool(o.dedup) + ["source"] * (occlude is not None)
+    if not force and all(getattr(st, k) is not None for k in need) and (occlude is None or occlude.fn is not None):
         return st, device
     if device is None:
         from .stages import device as _default_device
         device = _default_device()
     after_convert = st.convert is None                                     # resident behind this device's own conversion,
-    after_dedup = st.dedup is None if o.dedup else after_convert           # behind its dedup or, without one, behind the conversion,
+    after_occlude = occlude.fn is None if occlude is not None else after_convert      # behind its occlusion or, without one, behind the conversion,
+    after_dedup = st.dedup is None if o.dedup else after_occlude           # behind its dedup or, without one, behind what stands before the dedup,
     after_merge = st.merge is None if o.merge_paths else after_dedup       # and behind its merge or, without one, behind what stands before the merge
     own = StrokeSteps(
         convert=convert(device) if convert is not None else device.gcode_to_steps_clip if o.clip else device.gcode_to_steps, source=device.gcode_steps_source,
         merge=(lambda off, pts, group, n_groups, reverse: device.gcode_merge(None, None, group, n_groups, reverse, n=len(off) - 1)) if after_dedup else device.gcode_merge,
-        dedup=(lambda off, pts, group, n_groups: device.gcode_dedup(None, None, group, n_groups, n=len(off) - 1)) if after_convert else device.gcode_dedup,
+        dedup=(lambda off, pts, group, n_groups: device.gcode_dedup(None, None, group, n_groups, n=len(off) - 1)) if after_occlude else device.gcode_dedup,
         simplify=(lambda off, pts, t4: device.gcode_simplify(None, None, t4, n=len(off) - 1)) if after_merge else device.gcode_simplify,
         order=device.gcode_order, order_pens=device.gcode_order_pens,
         improve=lambda ends, group, n_groups, order, rev, reverse, max_rounds: device.gcode_improve(ends, group, n_groups, order, rev, reverse, max_rounds=max_rounds))
+    if occlude is not None and occlude.fn is None:
+        def own_occlude(off, pts, level, ring_sub, ring_level, m, clamp):
+            if not after_convert:
+                device.gcode_occlude(off, pts, level, np.zeros(1, np.int64), np.zeros((0, 2), np.int32), np.zeros(0, np.int32))
+            return device.svg_occlude(level, ring_sub, ring_level, m, clamp, n=len(off) - 1)
+        occlude.fn = own_occlude
     return StrokeSteps(*(a or b for a, b in zip(st, own))), device
 
 
@@ -436,6 +454,31 @@ def _dedup(st: StrokeSteps, off_in, pts_in, pen, group, n_groups: int, info: dic
     return off, pts, pen, group
 
 
+def _occlude(st: StrokeSteps, oc: Occlude, off_in, pts_in, pen, group, m: dict, info: dict):
+    """the strokes less what a shape of a higher level hides; a stroke takes its level through its source, and what is left of it keeps its pen; info["occlude"]"""
+    n_in = len(off_in) - 1
+    src = np.asarray(st.source(n_in), np.int64).reshape(-1)
+    if len(src) != n_in or (src < 0).any() or (src >= len(oc.path_level)).any():
+        raise RuntimeError("the source indices of the step polylines do not name input paths")
+    off, pts, origin, ost = oc.fn(off_in, pts_in, oc.path_level[src].astype(np.int32), oc.ring_sub, oc.ring_level, m, oc.clamp)
+    off = np.asarray(off, np.int64).reshape(-1); pts = np.asarray(pts, np.int32).reshape(-1, 2); origin = np.asarray(origin, np.int64).reshape(-1)
+    d = {k: int(ost[k]) for k in OCCLUDE_STATS}
+    n = len(off) - 1
+    if n < 0 or len(origin) != n or (np.diff(origin) < 0).any() or (n and (origin[0] < 0 or origin[-1] >= n_in)):
+        raise RuntimeError("the occlusion's origins are not the input strokes in ascending order")
+    same = (np.diff(pts, axis=0) == 0).all(1) if len(pts) > 1 else np.zeros(0, bool)
+    if off[0] != 0 or int(off[-1]) != len(pts) or (np.diff(off) < 2).any() or np.delete(same, off[1:-1] - 1).any():
+        raise RuntimeError("the occlusion returned a stroke of fewer than two points or with a repeated point")
+    if d["whole"] + d["cut"] + d["hidden"] != d["segments"] or d["segments"] != len(pts_in) - n_in or d["paths_out"] != n or d["points_out"] != len(pts) or \
+            d["pieces"] - d["collapsed"] != len(pts) - n or d["draw_steps_in"] != draw_steps(off_in, pts_in) or d["draw_steps_out"] != draw_steps(off, pts):
+        raise RuntimeError("the occlusion's counts do not add up")
+    if group is not None:
+        pen, group = pen[origin], group[origin]
+    info["paths"] = n
+    info["occlude"] = d
+    return off, pts, pen, group
+
+
 def _simplify(st: StrokeSteps, off_in, pts_in, tol4: int, info: dict):
     """the same strokes with the same ends, every stroke an ascending selection of its own points; info["simplify"]"""
     n = len(off_in) - 1
@@ -488,8 +531,10 @@ def _plan(o: GcodeOptions, sc: ST.StreamConfig, off, pts, path_pen) -> ST.Plan:
     return ST.plan_ops(off, pts, np.zeros(len(off) - 1, bool), (0, 0), [ST.PEN_UP, 0x40 | div0, 0x08 | int(o.color_index)], False, sc)
 
 
-def stroke_stream(text_or_paths, opts: Optional[GcodeOptions], device, steps: StrokeSteps, timings: Optional[dict] = None, pens: Optional[np.ndarray] = None) -> Tuple[bytes, dict]:
-    """build_stream_from_gcode with the device steps as one record: parse, convert, pens of the strokes, dedup, merge, simplify, order, plan, compile"""
+def stroke_stream(text_or_paths, opts: Optional[GcodeOptions], device, steps: StrokeSteps, timings: Optional[dict] = None, pens: Optional[np.ndarray] = None,
+                  occlude: Optional[Occlude] = None) -> Tuple[bytes, dict]:
+    """build_stream_from_gcode with the device steps as one record: parse, convert, pens of the strokes, [occlude, the SVG door's], dedup, merge, simplify,
+    order, plan, compile"""
     import time
     o = apply_speed_scale(GcodeOptions(**{f.name: getattr(opts, f.name) for f in fields(GcodeOptions)}) if opts is not None else GcodeOptions())
     W, H = target_size(o)
@@ -523,7 +568,7 @@ def stroke_stream(text_or_paths, opts: Optional[GcodeOptions], device, steps: St
         return EMPTY_STREAM, dict(info, bytes=len(EMPTY_STREAM))
     if not (1 <= W <= MAX_TARGET_STEPS and 1 <= H <= MAX_TARGET_STEPS):
         raise ValueError(f"target size {W} x {H} steps: each side must be in 1..2^30 (step coordinates are int32 on the device)")
-    st, device = resolve_steps(steps, o, grouped, device)
+    st, device = resolve_steps(steps, o, grouped, device, occlude=occlude)
     m = dict(scale_x=o.scale_x, scale_y=o.scale_y, offset_x_mm=o.offset_x_mm, offset_y_mm=o.offset_y_mm, steps_per_mm=o.steps_per_mm, W=W, H=H, invert_y=int(bool(o.invert_y)))
     off, pts = _convert(st, off_mm, pts_mm, m, rect, info)
     lap("to_steps")
@@ -532,17 +577,23 @@ def stroke_stream(text_or_paths, opts: Optional[GcodeOptions], device, steps: St
         return EMPTY_STREAM, dict(info, bytes=len(EMPTY_STREAM))
     pen, group = _stroke_pens(st, o, pens, n, info) if grouped else (None, None)
     n_groups = MAX_PENS if pens is not None else 1
+    if occlude is not None:
+        lap("order")                                                      # the sources and the pens belong to the order's lap
+        off, pts, pen, group = _occlude(st, occlude, off, pts, pen, group, m, info)
+        lap("occlude")
+        if len(off) <= 1:                                                 # everything lies under a shape
+            return EMPTY_STREAM, dict(info, bytes=len(EMPTY_STREAM))
     if o.dedup:
         lap("order")                                                      # the sources and the pens belong to the order's lap
         off, pts, pen, group = _dedup(st, off, pts, pen, group, n_groups, info)
         lap("dedup")
     if o.merge_paths:
-        if not o.dedup:
+        if not (o.dedup or occlude is not None):
             lap("order")                                                  # the sources and the pens belong to the order's lap, as before
         off, pts, pen, group = _merge(st, o, off, pts, pen, group, n_groups, info)
         lap("merge")
     if tol4 is not None:
-        if not (o.merge_paths or o.dedup):
+        if not (o.merge_paths or o.dedup or occlude is not None):
             lap("order")
         off, pts = _simplify(st, off, pts, tol4, info)
         lap("simplify")
@@ -562,6 +613,7 @@ def stroke_stream(text_or_paths, opts: Optional[GcodeOptions], device, steps: St
 IMPROVE_STATS = ("travel_before", "travel_after", "rounds", "converged_groups", "skipped_groups")
 CLIP_STATS = ("segments", "inside", "cut", "outside", "paths_out", "points_out")
 DEDUP_STATS = ("segments", "whole", "cut", "covered", "pieces", "paths_out", "points_out", "draw_steps_in", "draw_steps_out")      # include/orip.h: orip_gcode_dedup
+OCCLUDE_STATS = ("segments", "whole", "cut", "hidden", "pieces", "collapsed", "paths_out", "points_out", "draw_steps_in", "draw_steps_out")      # include/orip.h: orip_gcode_occlude
 SIMPLIFY_TOL4_MAX = (1 << 17) - 1             # include/orip.h: ORIP_SIMPLIFY_TOL4_MAX
 
 
@@ -682,6 +734,9 @@ def report_lines(tag: str, info: dict, unmatched: bool = False):
     if "pens" in info:
         yield (f"[{tag}] pens: " + ", ".join(f"{p}: {k} paths" for p, k in enumerate(info["pens"]["paths"]) if k) + "; " +
                (f"{info['pens']['unmatched']} without a stroke colour, " if unmatched else "") + f"{info['pens']['reversed']} strokes reversed")
+    if "occlude" in info:
+        yield (f"[{tag}] " + "occlude: {segments} segments: {whole} whole, {cut} cut, {hidden} hidden -> {paths_out} strokes, "
+                              "pen-down steps {draw_steps_in} -> {draw_steps_out}".format(**info["occlude"]))
     if "dedup" in info:
         yield (f"[{tag}] " + "dedup: {segments} segments: {whole} whole, {cut} cut, {covered} covered -> {paths_out} strokes, "
                               "pen-down steps {draw_steps_in} -> {draw_steps_out}".format(**info["dedup"]))

@@ -79,6 +79,8 @@ SIGNATURES = {
     "orip_gcode_merge": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp]), "orip_gcode_merge_fetch": (_i32, [_vp, _vp, _vp, _vp]),
     "orip_gcode_simplify": (_i32, [_vp, _vp, _vp, _i64, _i32, _vp]), "orip_gcode_simplify_fetch": (_i32, [_vp, _vp]),
     "orip_gcode_dedup": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _vp]), "orip_gcode_dedup_fetch": (_i32, [_vp, _vp]),
+    "orip_gcode_occlude": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp]), "orip_gcode_occlude_fetch": (_i32, [_vp, _vp]),
+    "orip_svg_occlude": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _P(GcodeMap), _i32, _vp]),
     "orip_gcode_improve": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _i64, _vp, _vp, _vp]),
     "orip_svg_flatten": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _f64, _P(_i64)]), "orip_svg_paths_fetch": (_i32, [_vp, _vp, _vp]),
     "orip_svg_bbox": (_i32, [_vp, _vp]), "orip_svg_fit": (_i32, [_vp, _f64, _f64, _f64, _f64]),
@@ -94,6 +96,8 @@ MERGE_REVERSE = 1
 SIMPLIFY_TOL4_MAX, SIMPLIFY_LOCAL = (1 << 17) - 1, 1024      # include/orip.h: the largest tolerance in quarter steps; the points one wave finishes alone
 CLIP_STATS = ("segments", "inside", "cut", "outside", "paths_out", "points_out")
 DEDUP_STATS = ("segments", "whole", "cut", "covered", "pieces", "paths_out", "points_out", "draw_steps_in", "draw_steps_out")
+OCCLUDE_STATS = ("segments", "whole", "cut", "hidden", "pieces", "collapsed", "paths_out", "points_out", "draw_steps_in", "draw_steps_out")
+OCCLUDE_CLAMP = 1
 IMPROVE_MAX_PATHS, IMPROVE_ROUNDS_AUTO = 65536, (1 << 63) - 1
 
 _lib = None

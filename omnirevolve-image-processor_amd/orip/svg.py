@@ -46,6 +46,14 @@ grid and on the device (orip_gcode_simplify), after the merge and before the ord
 two regions, the inner edges of a table of <rect>s -- are drawn once, on the device (orip_gcode_dedup), after the pens and before the merge.  Hatch lines
 go through it like any path.  It is forwarded as it is; the G-code file is not changed.
 
+--occlude (off unless given; ours, svg2stream.py only; include/orip.h states the rule): filled shapes hide what lies under them.  Which elements occlude is
+what --hatch-fill decides (fill_group >= 0: one notion of "filled" in the tool).  The parser records the ordinal of every subpath's element, its place in paint
+order: that is a path's LEVEL, a hatch line's level is its fill group, and the rings are the filled subpaths with that number -- so a shape hides neither
+its own outline nor its own hatch, and everything painted before it where it lies inside, across pens.  The pass runs on the step polylines, on the device
+(orip_svg_occlude: the rings are the resident fitted paths, converted there as the strokes were, clamped unless --clip cuts), after the pens have been worked
+out and before the dedup, which then removes what is doubled among what is left; the merge rejoins a closed outline that was cut at its start vertex.
+Pens and levels follow through origin.  The G-code file is not changed; the preview is rendered from the stream and shows the result.
+
 The device steps are injectable, as in orip/gcode.py, so that this host logic can be tested without a GPU; the product has no CPU path."""
 from __future__ import annotations
 
@@ -76,7 +84,8 @@ class SegmentTable:
     its matrix in mats (a, b, c, d, e, f: x' = a x + c y + e, y' = b x + d y + f).  Subpath p = segments sub_off[p] .. sub_off[p + 1] - 1, one pen-down path;
     closed[p]: it ended with Z (the closing line is one of its segments).  fill_group[p]: -1, or the ordinal of the element subpath p belongs to when that
     element is to be hatched (parse_svg; None counts as all -1).  stroke_rgb[p], fill_rgb[p]: the colour of the subpath's element as written, 8-bit sRGB, or
-    (-1, -1, -1) where none is stated or what is stated is no colour (None counts as all -1)."""
+    (-1, -1, -1) where none is stated or what is stated is no colour (None counts as all -1).  element[p]: the ordinal of subpath p's element among the
+    elements that drew something, its place in paint order (None: not recorded; --occlude needs it)."""
     kind: np.ndarray
     ctrl: np.ndarray
     mat: np.ndarray
@@ -87,6 +96,7 @@ class SegmentTable:
     fill_group: Optional[np.ndarray] = None
     stroke_rgb: Optional[np.ndarray] = None
     fill_rgb: Optional[np.ndarray] = None
+    element: Optional[np.ndarray] = None
 
     @property
     def n_seg(self) -> int: return len(self.kind)
@@ -110,7 +120,7 @@ class _Builder:
     def __init__(self):
         self.kind: List[int] = []; self.ctrl: List[Tuple[float, ...]] = []; self.mat: List[int] = []
         self.sub_off = [0]; self.closed: List[int] = []
-        self.fill_group: List[int] = []; self.elements = 0
+        self.fill_group: List[int] = []; self.elements = 0; self.element: List[int] = []
         self.stroke_rgb: List[Tuple[int, int, int]] = []; self.fill_rgb: List[Tuple[int, int, int]] = []
         self.mats: List[Tuple[float, ...]] = [IDENTITY]
         self.m = 0
@@ -185,7 +195,8 @@ class _Builder:
         self.end()
         return SegmentTable(np.asarray(self.kind, np.int32), np.asarray(self.ctrl, np.float64).reshape(-1, 4, 2), np.asarray(self.mat, np.int32),
                             np.asarray(self.sub_off, np.int64), np.asarray(self.closed, np.uint8), np.asarray(self.mats, np.float64).reshape(-1, 6), float(canvas_height),
-                            np.asarray(self.fill_group, np.int32), np.asarray(self.stroke_rgb, np.int16).reshape(-1, 3), np.asarray(self.fill_rgb, np.int16).reshape(-1, 3))
+                            np.asarray(self.fill_group, np.int32), np.asarray(self.stroke_rgb, np.int16).reshape(-1, 3), np.asarray(self.fill_rgb, np.int16).reshape(-1, 3),
+                            np.asarray(self.element, np.int32))
 
 
 # ------------------------------------------------------------------ path data
@@ -501,7 +512,7 @@ def _walk(b: _Builder, el, m: int, fill: Optional[str] = None, fill_all: bool = 
         new = len(b.closed) - len(b.fill_group)
         if new:                                             # an element that drew something: the next ordinal, whether it is filled or not
             wanted = tag != "line" and (fill_all or (fill is not None and fill not in ("none", "transparent")))
-            b.fill_group.extend([b.elements if wanted else -1] * new)
+            b.fill_group.extend([b.elements if wanted else -1] * new); b.element.extend([b.elements] * new)
             b.stroke_rgb.extend([parse_color(stroke)] * new); b.fill_rgb.extend([parse_color(fill)] * new)
             b.elements += 1
 
@@ -560,6 +571,7 @@ class SvgOptions:
     clip_margin_mm: Optional[float] = None              # the clip rectangle lies this far inside the sheet; None: 0
     simplify_mm: Optional[float] = None                 # vertices within this distance of the stroke are dropped (orip.gcode); None: none are
     dedup: bool = False                                 # collinear segments of one pen that lie over each other are drawn once (orip.gcode)
+    occlude: bool = False                               # filled shapes hide what lies under them (svg2stream.py only)
 
 
 HATCH_DIRECTIONS = {"horizontal": HATCH_HORIZONTAL, "vertical": HATCH_VERTICAL, "cross": HATCH_HORIZONTAL | HATCH_VERTICAL}
@@ -744,6 +756,31 @@ def path_pens(table: SegmentTable, o: SvgOptions, paths, info: dict, hatch_group
     return pens
 
 
+def occlusion_rings(table: SegmentTable):
+    """--occlude: the subpaths that hide, (ring_sub, ring_level) -- those of the elements --hatch-fill marks, the one notion of "filled" in the tool, each
+    with its element's ordinal, its place in paint order; ascending as the parser leaves them"""
+    if table.element is None or table.fill_group is None:
+        raise ValueError("--occlude needs the element ordinals and the fill groups of a parsed SVG")
+    fg = np.asarray(table.fill_group, np.int64).reshape(-1); el = np.asarray(table.element, np.int64).reshape(-1)
+    if len(fg) != table.n_sub or len(el) != table.n_sub or (el < 0).any() or (np.diff(el) < 0).any() or ((fg >= 0) & (fg != el)).any():
+        raise ValueError("the element ordinals must ascend, one per subpath, and a fill group is its element's ordinal")
+    sub = np.nonzero(fg >= 0)[0]
+    return sub.astype(np.int32), fg[sub].astype(np.int32)
+
+
+def path_levels(table: SegmentTable, paths, info: dict, hatch_groups_fn: Optional[Callable]) -> np.ndarray:
+    """--occlude: the level of every fitted path: a subpath's is its element's ordinal, a hatch line's is its fill group, so a shape hides neither its own
+    outline nor its own hatch"""
+    level = np.asarray(table.element, np.int64).reshape(-1)
+    seg = int(info["hatch"]["segments"]) if "hatch" in info else 0
+    if seg:
+        groups = np.asarray(hatch_groups_fn(paths, seg), np.int64).reshape(-1)
+        if len(groups) != seg or (groups < 0).any():
+            raise RuntimeError(f"{len(groups)} fill groups for {seg} hatch lines")
+        level = np.concatenate([level, groups])
+    return level
+
+
 def resolved_pens(pens: np.ndarray, o: SvgOptions) -> np.ndarray:
     """the pens as the G-code names them: --color-index where none was matched"""
     if not (0 <= int(o.color_index) < GC.MAX_PENS):
@@ -770,7 +807,8 @@ def build_stream_from_svg(text: Union[str, bytes, SegmentTable], opts: Optional[
                           steps_fn: Optional[Callable] = None, order_fn: Optional[Callable] = None, codes_fn: Optional[Callable] = None, pack_fn: Optional[Callable] = None, timings: Optional[dict] = None,
                           want_paths: bool = False, hatch_groups_fn: Optional[Callable] = None, source_fn: Optional[Callable] = None,
                           order_pens_fn: Optional[Callable] = None, merge_fn: Optional[Callable] = None, improve_fn: Optional[Callable] = None,
-                          clip_fn: Optional[Callable] = None, simplify_fn: Optional[Callable] = None, dedup_fn: Optional[Callable] = None) -> Tuple[bytes, dict]:
+                          clip_fn: Optional[Callable] = None, simplify_fn: Optional[Callable] = None, dedup_fn: Optional[Callable] = None,
+                          occlude_fn: Optional[Callable] = None) -> Tuple[bytes, dict]:
     """The stream of an SVG text (or of a parsed SegmentTable).  Device steps, each None = the GPU (there is no CPU path in the product):
       flatten_fn(table, tol_raw) -> paths          orip_svg_flatten      (`paths` is whatever the other steps take: on the GPU a count, the points stay there)
       bbox_fn(paths) -> (min x, min y, max x, max y)   orip_svg_bbox
@@ -792,6 +830,9 @@ def build_stream_from_svg(text: Union[str, bytes, SegmentTable], opts: Optional[
       simplify_fn                                  as in orip.gcode.build_stream_from_gcode (a hatch line has two points and passes through untouched)
     and, only with --dedup:
       dedup_fn                                     as in orip.gcode.build_stream_from_gcode (hatch lines go through it like any path)
+    and, only with --occlude (after the pens have been worked out, before the dedup; it needs source_fn and, with hatching, hatch_groups_fn):
+      occlude_fn(paths, off, pts, level int32 [n], ring_sub, ring_level, map, clamp) -> (off, pts, origin int32, stats)   orip_svg_occlude
+    the rings are the fitted paths ring_sub with their levels, clamp = not --clip; info["occlude"] = the ten counts of include/orip.h.
     With --pen-colors, info["path_pens"] is the pen of every fitted path (hatch lines included, --color-index where no stroke is stated).
     Returns (bytes, info)."""
     import time
@@ -817,8 +858,13 @@ def build_stream_from_svg(text: Union[str, bytes, SegmentTable], opts: Optional[
     given = clip_fn if o.clip else steps_fn                 # the stroke steps take (off, pts_mm, ...); here the conversion takes the fitted paths where they are
     steps = GC.StrokeSteps(None if given is None else (lambda _off, _pts, m, *rect: given(paths, m, *rect)), source_fn, merge_fn, simplify_fn, order_fn, order_pens_fn,
                            improve_fn, codes_fn, pack_fn, dedup_fn)
-    own = any(f is None for f in (flatten_fn, bbox_fn, fit_fn, fetch_fn)) or (hp and hatch_fn is None) or (pens_on and hp and hatch_groups_fn is None)
-    steps, device = GC.resolve_steps(steps, go, pens_on or o.allow_reverse, device, force=bool(own),
+    own = any(f is None for f in (flatten_fn, bbox_fn, fit_fn, fetch_fn)) or (hp and hatch_fn is None) or ((pens_on or o.occlude) and hp and hatch_groups_fn is None)
+    occ = None
+    if o.occlude:                                           # the rings and their levels are known now; the strokes' levels once the hatch lines are there
+        ring_sub, ring_level = occlusion_rings(table)
+        occ = GC.Occlude(None if occlude_fn is None else (lambda off, pts, level, rs, rl, m, clamp: occlude_fn(paths, off, pts, level, rs, rl, m, clamp)),
+                         np.zeros(0, np.int64), ring_sub, ring_level, not o.clip)
+    steps, device = GC.resolve_steps(steps, go, pens_on or o.allow_reverse, device, force=bool(own), occlude=occ,
                                      convert=lambda dev: lambda _off, _pts, m, *rect: (_Resident(dev).clip if rect else _Resident(dev).steps)(paths, m, *rect))
     if own:
         R = _Resident(device)
@@ -837,7 +883,9 @@ def build_stream_from_svg(text: Union[str, bytes, SegmentTable], opts: Optional[
     if want_paths:
         info["fitted_paths"] = (off_mm, np.asarray(pts_mm, np.float64).reshape(-1, 2))
     tm["fetch_paths"] = tm.get("fetch_paths", 0.0) + (time.perf_counter() - t0)
-    data, ginfo = GC.stroke_stream((off_mm, np.zeros((int(off_mm[-1]), 2))), go, device, steps, tm, pens)
+    if occ is not None:
+        occ.path_level = path_levels(table, paths, info, hatch_groups_fn)
+    data, ginfo = GC.stroke_stream((off_mm, np.zeros((int(off_mm[-1]), 2))), go, device, steps, tm, pens, occ)
     return data, dict(ginfo, **info)
 
 
@@ -887,6 +935,8 @@ def build_stream_argparser() -> argparse.ArgumentParser:
     ap.add_argument("--color-index", type=int, default=d.color_index, help="pen 0..7")
     ap.add_argument("--speed-scale", type=float, default=d.speed_scale, help="> 1 faster (smaller dividers), < 1 slower")
     GC.add_stroke_args(ap, ("--no-reorder", "--pen-order", "--allow-reverse") + GC.STROKE_ARGS[3:], "; the G-code file is not changed")
+    ap.add_argument("--occlude", action="store_true", help="filled shapes (what --hatch-fill marks) hide the strokes and hatch lines of the elements painted before them; "
+                                                           "exact on the step grid; the G-code file is not changed")
     ap.add_argument("--no-preview", action="store_true", help="do not render <svg stem>_stream_preview.png")
     ap.add_argument("--preview-render-width", type=int, default=d.preview_render_width)
     ap.add_argument("--preview-render-height", type=int, default=d.preview_render_height)

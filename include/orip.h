@@ -447,6 +447,54 @@ int orip_gcode_occlude(orip_ctx* ctx, const int64_t* off /* [n+1] or NULL */, co
 int orip_svg_occlude(orip_ctx* ctx, const int32_t* level /* [n] */, int64_t n, const int32_t* ring_sub /* [m] */, const int32_t* ring_level /* [m] */, int64_t m,
                      const orip_gcode_map* map, int32_t flags /* ORIP_OCCLUDE_CLAMP */, int64_t* stats /* [10] */);
 int orip_gcode_occlude_fetch(orip_ctx* ctx, int32_t* origin /* [paths_out] */);
+/* --dashes / --dash-mm (csrc/gcode_dash.hip; ours, the reference has no such pass): a stroke with a dash pattern is drawn as its dashes.  All arithmetic is
+ * integer on the step grid: nothing behind the conversion to steps is floating point.
+ * Unit.  u = 1 / ORIP_DASH_UNIT = 1/256 step: every length below is in u.
+ * Input.  n step polylines as every stroke pass takes them: two points or more, coordinates 0 .. 2^30, no two consecutive points equal.  Per stroke
+ *   pattern[k], -1 = solid, else an index into the pattern table, and phase[k] in u, 0 <= phase < P.  The table: pat_off int32[np + 1], pat_val int64[..];
+ *   every pattern has an even number of entries, 2 .. 64, alternately dash and gap, each in 256 .. 2^40 (a dash or a gap shorter than a step is nothing the
+ *   grid can show).  P = the sum of a pattern's entries, A_t = the sum of those before entry t.
+ *   Length.  Segment j of a stroke runs v_j -> v_{j+1}, D = dx^2 + dy^2 <= 2^61.  l_j = floor(256 sqrt(D)), the integer square root of the 78-bit number
+ *   65536 D, exact; l_j >= 256.  S_0 = 0, S_{j+1} = S_j + l_j.  The floor makes a stroke's measured length up to 1/256 step per segment shorter than its
+ *   true length: the one place where the rule departs from Euclid.  A dashed stroke with S_end >= 2^62 is an error found on the device that leaves no list
+ *   (every l < 2^39, so that takes more than 2^23 points); it is found from sums of the lengths' high parts, which cannot wrap.  Solid strokes are not measured.
+ *   On-intervals.  The pattern position of arc position s is (s + phase) mod P.  The on-intervals of a stroke are [r P + A_2i - phase, r P + A_2i+1 - phase]
+ *   for all integers r and all i; each is intersected with [0, S_end], and those of positive length are the stroke's DASHES, in ascending order.
+ *   Points of a dash [s0, s1]: the cut point at s0, every vertex v_j with s0 < S_j < s1 strictly, the cut point at s1.  Where s = S_j the cut point is the
+ *   vertex v_j.  Otherwise it lies in the one segment with S_j < s < S_{j+1}, at the exact rational point v_j + (s - S_j) / l_j (dx, dy), each coordinate
+ *   rounded to the nearest step, halves toward +infinity: v + floor((2 d (s - S_j) + l_j) / (2 l_j)), a true floor for negative d -- the rounding of
+ *   orip_gcode_to_steps_clip and of the occlusion.  The products reach 2^71: 128-bit integers.  Within a dash a point equal to the point before it is left
+ *   out.  A dash left with one point is dropped and counted in `collapsed` (a one-step dash on a diagonal can round onto one grid point).
+ *   Strokes.  A solid stroke passes through bit for bit.  Every kept dash is an output stroke.  Output strokes keep the order of their input strokes and,
+ *   inside one, ascending s; origin[k] (orip_gcode_dash_fetch) = the input stroke of output stroke k: ascending, with repeats and gaps.  A dashed stroke
+ *   can vanish, when it lies wholly in a gap.
+ * stats: paths_in, dashed (strokes with pattern >= 0), dashes, collapsed, paths_out, points_out, length_in (the sum of S_end over the dashed strokes),
+ *   length_on (the sum of s1 - s0 over all dashes, collapsed ones included).
+ * Consequences.  paths_out == paths_in - dashed + dashes - collapsed.  length_on <= length_in.  For a stroke with phase 0 and S_end a multiple of P,
+ * length_on = S_end (sum of the dash entries) / P exactly.  Every output stroke has two points or more and no repeated point; its interior vertices are
+ * input vertices in order and its two ends lie within half a step (Chebyshev) of the exact point.  A pattern whose first dash is at least S_end, with
+ * phase 0, returns the stroke unchanged.  A drawing without a dashed stroke comes back unchanged, origin = 0 .. n - 1.  For an axis-parallel stroke and a
+ * pattern and phase of whole steps every cut is a grid point, nothing collapses, and the output's primitive lattice steps are exactly those of the input
+ * whose midpoint is on, each once and in order.  Nothing depends on pens or groups.
+ * off == NULL and pts == NULL: the resident step polylines, n must be their count.  In both forms the result BECOMES the resident step polylines, and the
+ * sources follow through origin while they still name the input, as in orip_gcode_dedup.
+ * Errors before any launch, without a fault and with the resident polylines left as they were: the stroke errors of orip_gcode_dedup (2^28 points or more
+ * among them), a pattern index outside -1 .. np - 1, a phase outside [0, P), np outside 0 .. 2^20, a pattern of odd, zero or more than 64 entries, an
+ * entry outside 256 .. 2^40, pat_off not ascending from 0, NULL stats or arrays, a wrong resident count.  n == 0 returns zeros and (explicit form) the empty
+ * list before any launch.  The output is not bounded by the input (one 2-point line becomes hundreds of strokes), so the pass counts first and emits
+ * second: 2^30 output points or more, counted before the repeated points and the collapsed dashes are taken out, is an error found after the count that
+ * leaves no list, and so does any inconsistency found on the device.
+ * Declined: dots for zero-length dashes; stroke-linecap (the nib is round); pathLength; vector-effect; dashing in mm before the rounding to steps (double
+ * rounding, and a float prefix sum whose result depends on the order of addition); carrying the phase across the pieces --clip makes of one path (each
+ * stroke the conversion leaves starts its own pattern, so under --clip the phase restarts at the sheet's edge) or across strokes that --merge-paths would
+ * join (the merge runs later); a bound on the worst case. */
+#define ORIP_DASH_UNIT 256
+#define ORIP_DASH_MAX_ENTRIES 64
+#define ORIP_DASH_STATS 8
+int orip_gcode_dash(orip_ctx* ctx, const int64_t* off /* [n+1] or NULL */, const int32_t* pts /* [off[n],2] or NULL */, const int32_t* pattern /* [n]: -1 or 0..np-1 */,
+                    const int64_t* phase /* [n] */, int64_t n, const int32_t* pat_off /* [np+1] */, const int64_t* pat_val /* [pat_off[np]] */, int32_t n_patterns,
+                    int64_t* stats /* [8]: paths_in, dashed, dashes, collapsed, paths_out, points_out, length_in, length_on */);
+int orip_gcode_dash_fetch(orip_ctx* ctx, int32_t* origin /* [paths_out] */);
 /* --improve-order (csrc/gcode_improve.hip; ours, the reference stops at the greedy order): 2-opt and or-opt on a drawing sequence, by steepest descent.
  * Input: n step polylines given by their ends as for orip_gcode_order_pens (ends NULL = the resident ones, n must be their count), one group per polyline,
  * a start cursor, and a valid drawing sequence order[n], rev[n]: order is a permutation, the groups of its entries do not decrease, rev[k] is 0 or 1 and

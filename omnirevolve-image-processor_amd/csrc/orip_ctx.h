@@ -331,7 +331,7 @@ struct orip_ctx {
     // came from, which names them while !gc_merged (a field of the merge's line below).  This block is the one statement of their contract; the helpers that
     // keep it are declared in gc_convert.h and defined in gcode.hip, and no other code writes these fields.
     //   Readers (fail while !gc_ready, or when the n they are given is not gc_n): orip_gcode_steps_fetch, orip_gcode_steps_source_fetch (also fails while
-    //   gc_merged), and for NULL input orip_gcode_order, orip_gcode_order_pens, orip_gcode_improve, orip_gcode_merge, orip_gcode_simplify, orip_gcode_dedup, orip_gcode_occlude; orip_svg_occlude always.
+    //   gc_merged), and for NULL input orip_gcode_order, orip_gcode_order_pens, orip_gcode_improve, orip_gcode_merge, orip_gcode_simplify, orip_gcode_dedup, orip_gcode_occlude, orip_gcode_dash; orip_svg_occlude always.
     //   Writers, and what each leaves:
     //     orip_gcode_to_steps       drops the list on entry (gc_drop), before it looks at its arguments: after ANY failure there is no list.  Success: its
     //                               polylines and their sources, gc_merged cleared; no points to convert (n == 0 included): the empty list (gc_publish_empty).
@@ -353,6 +353,11 @@ struct orip_ctx {
     //                               the resident one, which is empty; success swaps the pieces in and, while !gc_merged, the sources gathered through origin.
     //                               A device-found error (a ring coordinate not finite or out of range, a repeated point in the resident list, 2^30
     //                               output points or more, pieces that do not add up) leaves no list.
+    //     orip_gcode_dash           as the dedup, with ds_off / ds_pts / ds_src and the same rule for an explicit input and gc_merged: checks first (strokes,
+    //                               patterns, phases: an argument error leaves the list as it was); success swaps the dashes in, the list of no polylines
+    //                               when every stroke lies in a gap, and, while !gc_merged, the sources gathered through origin.  A device-found error (a
+    //                               repeated point in the resident list, a dashed stroke of 2^62 units or more, 2^30 output points or more, counts that do
+    //                               not add up) leaves no list.
     //   A failed HIP call inside a writer leaves what had been written up to it; gc_ready is false across an upload, so a list is never half there.
     DBuf gc_tmp, gc_off, gc_pts, gc_src, pk_tab, pk_out; int64_t gc_n = 0, gc_total = 0, pk_bytes = -1; bool gc_ready = false;
     // orip_gcode_order and orip_gcode_order_pens (gcode_order.hip: gc_grids), free between calls.  With n paths in G groups, m = n or 2n candidates (both ends
@@ -382,6 +387,11 @@ struct orip_ctx {
     // the output, swapped with gc_off / gc_pts when a call succeeds, oc_src = the gathered sources, swapped with gc_src then; oc_res = origin
     // int32[oc_paths], the input stroke of every output stroke of the last call (-1: none) until the next one
     DBuf oc_tmp, oc_ev, oc_off, oc_pts, oc_src, oc_res; int64_t oc_paths = -1;
+    // --dashes / --dash-mm (gcode_dash.hip): ds_tmp = the lengths and their scan, the patterns' tables, the per-segment counts and their scan, the list of
+    // the segments a wave takes; ds_raw = the points and dashes before the repeated points and the collapsed dashes are taken out (the unit states both
+    // layouts), free between calls; ds_off / ds_pts = the output, swapped with gc_off / gc_pts when a call succeeds, ds_src = the gathered sources, swapped
+    // with gc_src then; ds_res = origin int32[ds_paths], the input stroke of every output stroke of the last call (-1: none) until the next one
+    DBuf ds_tmp, ds_raw, ds_off, ds_pts, ds_src, ds_res; int64_t ds_paths = -1;
     // svg2stream (svg.hip): scratch of the flattening and of the box, the resident paths (off int64[sv_n + 1], pts double2[sv_total]; raw units after
     // orip_svg_flatten, page mm after orip_svg_fit) until the next flatten; orip_gcode_to_steps reads them when it is called without pointers
     DBuf sv_tmp, sv_tmp2, sv_off, sv_pts; int64_t sv_n = 0, sv_total = 0; bool sv_ready = false, sv_box_ok = false; double sv_box[4] = {0, 0, 0, 0};

@@ -584,6 +584,29 @@ class Device:
         self._ck(self.L.orip_svg_occlude(self.h, _p(lv) if n else None, n, _p(rs) if m else None, _p(rl) if m else None, m, C.byref(gm), _l.OCCLUDE_CLAMP if clamp else 0, _p(st)))
         return self._occlude_result(st)
 
+    def gcode_dash(self, off, pts, pattern, phase, pat_off, pat_val, n: int | None = None):
+        """--dashes / --dash-mm (include/orip.h: orip_gcode_dash): of the step polylines (off int64 [n + 1], pts int32 [total, 2]; both None = the n resident
+        ones) every stroke with pattern[k] >= 0 is cut into the dashes of that pattern of the table (pat_off int32 [np + 1], pat_val int64, in 1/256 step),
+        entered at phase[k]; -1 = solid.  What is left becomes the resident polylines.
+        -> (off int64, pts int32 [total', 2], origin int32 [paths_out]: the input stroke of every output stroke, {lib.DASH_STATS})"""
+        po, pp, n, _keep = _step_paths(off, pts, n)
+        pa = np.ascontiguousarray(pattern, np.int32).reshape(-1)
+        ph = np.ascontiguousarray(phase, np.int64).reshape(-1)
+        n = len(pa) if n is None else int(n)
+        if len(pa) != n or len(ph) != n:
+            raise ValueError(f"{len(pa)} patterns and {len(ph)} phases given for {n} paths")
+        qo = np.ascontiguousarray(pat_off, np.int32).reshape(-1)
+        qv = np.ascontiguousarray(pat_val, np.int64).reshape(-1)
+        if len(qo) < 1 or len(qv) < int(qo[-1]):
+            raise ValueError(f"{len(qo)} pattern offsets and {len(qv)} entries given")
+        st = np.zeros(len(_l.DASH_STATS), np.int64)
+        self._ck(self.L.orip_gcode_dash(self.h, po, pp, _p(pa) if n else None, _p(ph) if n else None, n, _p(qo), _p(qv) if len(qv) else None, len(qo) - 1, _p(st)))
+        paths, total = int(st[4]), int(st[5])
+        origin = np.zeros(max(paths, 1), np.int32)
+        self._ck(self.L.orip_gcode_dash_fetch(self.h, _p(origin)))
+        off_s, pts_s = self.gcode_steps_fetch(paths, total)
+        return off_s, pts_s, origin[:paths], {k: int(v) for k, v in zip(_l.DASH_STATS, st)}
+
     def gcode_steps_fetch(self, n: int, total: int, points: bool = True) -> Tuple[np.ndarray, np.ndarray]:
         """the n resident step polylines of `total` points, as gcode_to_steps or gcode_merge left them: (off int64 [n + 1], pts int32 [total, 2]; zeros without `points`)"""
         off = np.zeros(int(n) + 1, np.int64); pts = np.zeros((max(int(total), 1), 2), np.int32)

@@ -47,7 +47,14 @@ With --dedup collinear segments of one pen that lie over each other on the step 
 stretches nothing earlier covers, cut at end points of the input (orip_gcode_dedup; include/orip.h states the rule, exact in integers, no tolerance).  It
 runs after the pens have been worked out and before the merge, which joins the pieces it leaves, and before the simplification, which would move two copies
 of a shared border apart.  A stroke can be cut into several and can vanish; pens and sources follow.  Allowed with --no-reorder: strokes keep file order.
-Without the option no device call is added and every byte is what it was."""
+Without the option no device call is added and every byte is what it was.
+
+--dash-mm (ours as well; svg2stream --dashes honours the drawing's own stroke-dasharray through the same pass): G-code has no notion of a dash, so a
+perforation, a fold line or a stitch line is asked for here.  Every stroke is cut into the dashes of the pattern, measured along the stroke in 1/256 step
+from its first point (--dash-offset-mm: from that far into the pattern): orip_gcode_dash; include/orip.h states the rule, exact in integers on the step
+grid.  It runs after the pens have been worked out and before the occlusion and the dedup; every stroke the conversion leaves starts the pattern anew, so
+under --clip the phase restarts at the sheet's edge, and the merge, which runs later, does not carry it on.  A dash keeps its stroke's pen and source; a
+dash that rounds onto one grid point is dropped.  Without the option no device call is added and every byte is what it was."""
 from __future__ import annotations
 
 import argparse
@@ -104,6 +111,8 @@ class GcodeOptions:
     clip_margin_mm: Optional[float] = None  # the clip rectangle lies this far inside the sheet (None: 0); only with clip
     simplify_mm: Optional[float] = None     # vertices within this distance of the stroke are dropped (None: every vertex is drawn; 0: only those on the stroke)
     dedup: bool = False                 # collinear segments of one pen that lie over each other are drawn once, the first drawn copy stays
+    dash_mm: Optional[str] = None       # every path is drawn dashed: dash and gap lengths in mm, comma-separated (None: solid)
+    dash_offset_mm: Optional[float] = None  # where in the pattern a path starts (None: 0); only with dash_mm
 
 
 # ------------------------------------------------------------------ parse (:113-142, :177-300)
@@ -299,7 +308,8 @@ def build_stream_from_gcode(text_or_paths, opts: Optional[GcodeOptions] = None, 
                             order_fn: Optional[Callable] = None, codes_fn: Optional[Callable] = None, pack_fn: Optional[Callable] = None,
                             timings: Optional[dict] = None, pens: Optional[np.ndarray] = None, order_pens_fn: Optional[Callable] = None,
                             source_fn: Optional[Callable] = None, merge_fn: Optional[Callable] = None, improve_fn: Optional[Callable] = None,
-                            clip_fn: Optional[Callable] = None, simplify_fn: Optional[Callable] = None, dedup_fn: Optional[Callable] = None) -> Tuple[bytes, dict]:
+                            clip_fn: Optional[Callable] = None, simplify_fn: Optional[Callable] = None, dedup_fn: Optional[Callable] = None,
+                            dash_fn: Optional[Callable] = None) -> Tuple[bytes, dict]:
     """The stream of a G-code text (str / bytes) or of paths in mm given as (off, pts_mm); opts as parsed, --speed-scale not yet applied.
     Device steps, each None = the GPU (orip.device.Device; there is no CPU path in the product):
       steps_fn(off, pts_mm, map: dict) -> (off int64, pts int32 [total, 2])      orip_gcode_to_steps
@@ -323,12 +333,15 @@ def build_stream_from_gcode(text_or_paths, opts: Optional[GcodeOptions] = None, 
     and, only with --dedup (after the pens have been worked out, before the merge):
       dedup_fn(off, pts, group int32 [n], n_groups) -> (off, pts, origin int32: the input stroke of every output stroke, stats)       orip_gcode_dedup
     info["dedup"] then holds segments, whole, cut, covered, pieces, paths_out, points_out, draw_steps_in and draw_steps_out; a stroke keeps its origin's pen.
+    and, only with --dash-mm (after the pens have been worked out, before the dedup; it needs source_fn):
+      dash_fn(off, pts, pattern int32 [n], phase int64 [n], pat_off, pat_val) -> (off, pts, origin int32, stats)                      orip_gcode_dash
+    info["dash"] then holds the eight counts of include/orip.h; a dash keeps its stroke's pen.
     pens: one pen per input path, 0..7, or -1 for --color-index (a text's T words under --tool-pens when None).  info["pens"] then counts the paths per
     pen, those that took --color-index ("unmatched") and the strokes drawn backwards ("reversed").
     Returns (bytes, counts)."""
     steps = StrokeSteps(clip_fn if opts is not None and opts.clip else steps_fn, source_fn, merge_fn, simplify_fn, order_fn, order_pens_fn, improve_fn, codes_fn, pack_fn,
                         dedup_fn)
-    return stroke_stream(text_or_paths, opts, device, steps, timings, pens)
+    return stroke_stream(text_or_paths, opts, device, steps, timings, pens, dash_fn=dash_fn)
 
 
 # The device steps of the stroke pipeline, each a callable or None = not given; build_stream_from_gcode states the signatures.  convert: steps_fn or, with --clip, clip_fn
@@ -344,22 +357,35 @@ class Occlude:
         self.ring_sub = np.asarray(ring_sub, np.int32).reshape(-1); self.ring_level = np.asarray(ring_level, np.int32).reshape(-1); self.clamp = bool(clamp)
 
 
-def resolve_steps(st: StrokeSteps, o, grouped: bool, device=None, convert: Optional[Callable] = None, force: bool = False, occlude: Optional[Occlude] = None):
+class Dash:
+    """The dash pass (--dash-mm here, --dashes of the SVG door), which StrokeSteps does not carry: fn(off, pts, pattern int32 [n], phase int64 [n], pat_off,
+    pat_val) -> (off, pts, origin int32: the input stroke of every output stroke, stats) or None = the device (orip_gcode_dash); path_pattern (-1: solid) and
+    path_phase of every input path, which a stroke takes through its source; the pattern table in 1/256 step (include/orip.h states the rule)"""
+    def __init__(self, fn, path_pattern, path_phase, pat_off, pat_val):
+        self.fn = fn; self.path_pattern = np.asarray(path_pattern, np.int32).reshape(-1); self.path_phase = np.asarray(path_phase, np.int64).reshape(-1)
+        self.pat_off = np.asarray(pat_off, np.int32).reshape(-1); self.pat_val = np.asarray(pat_val, np.int64).reshape(-1)
+        self.device_follows = False                 # resolve_steps: pass and sources are both this device's, whose sources follow the dashes through origin
+
+
+def resolve_steps(st: StrokeSteps, o, grouped: bool, device=None, convert: Optional[Callable] = None, force: bool = False, occlude: Optional[Occlude] = None,
+                  dash: Optional[Dash] = None):
     """The steps the options need, those not given taken from a device -> (steps, device); codes and pack stay as given (orip.stream.compile_plan fills them).
     When none is missing, and the caller does not `force` a device for steps of its own, no device is made and orip.stages is not imported.  convert(device)
     -> the conversion of a front door whose paths are on the device already (orip.svg).  Dedup, merge and simplify work on the polylines the pass before them
-    left resident when that pass ran on this device, and are sent their input when it was given.  `occlude`: its fn is filled in the same way; it needs the
+    left resident when that pass ran on this device, and are sent their input when it was given.  `dash`: its fn is filled in the same way, and it needs
+    the sources as the occlusion does; it stands between the conversion and the occlusion.  `occlude`: its fn is filled in the same way; it needs the
     sources whether or not pens are in use, and the rings are fitted paths that only the device's own conversion leaves next to the strokes, so behind a
     given conversion the strokes are uploaded first (an occlusion without rings makes them the resident list) and the pass then runs as it does otherwise."""
     need = ["convert", "order"] + ["order_pens", "source"] * bool(grouped) + ["merge"] * bool(o.merge_paths) + ["improve"] * bool(o.improve_order) + \
-        ["simplify"] * (o.simplify_mm is not None) + ["dedup"] * bool(o.dedup) + ["source"] * (occlude is not None)
-    if not force and all(getattr(st, k) is not None for k in need) and (occlude is None or occlude.fn is not None):
+        ["simplify"] * (o.simplify_mm is not None) + ["dedup"] * bool(o.dedup) + ["source"] * (occlude is not None or dash is not None)
+    if not force and all(getattr(st, k) is not None for k in need) and (occlude is None or occlude.fn is not None) and (dash is None or dash.fn is not None):
         return st, device
     if device is None:
         from .stages import device as _default_device
         device = _default_device()
     after_convert = st.convert is None                                     # resident behind this device's own conversion,
-    after_occlude = occlude.fn is None if occlude is not None else after_convert      # behind its occlusion or, without one, behind the conversion,
+    after_dash = dash.fn is None if dash is not None else after_convert    # behind its dash pass or, without one, behind the conversion,
+    after_occlude = occlude.fn is None if occlude is not None else after_dash         # behind its occlusion or, without one, behind what stands before it,
     after_dedup = st.dedup is None if o.dedup else after_occlude           # behind its dedup or, without one, behind what stands before the dedup,
     after_merge = st.merge is None if o.merge_paths else after_dedup       # and behind its merge or, without one, behind what stands before the merge
     own = StrokeSteps(
@@ -371,10 +397,13 @@ def resolve_steps(st: StrokeSteps, o, grouped: bool, device=None, convert: Optio
         improve=lambda ends, group, n_groups, order, rev, reverse, max_rounds: device.gcode_improve(ends, group, n_groups, order, rev, reverse, max_rounds=max_rounds))
     if occlude is not None and occlude.fn is None:
         def own_occlude(off, pts, level, ring_sub, ring_level, m, clamp):
-            if not after_convert:
+            if not after_dash:
                 device.gcode_occlude(off, pts, level, np.zeros(1, np.int64), np.zeros((0, 2), np.int32), np.zeros(0, np.int32))
             return device.svg_occlude(level, ring_sub, ring_level, m, clamp, n=len(off) - 1)
         occlude.fn = own_occlude
+    if dash is not None and dash.fn is None:
+        dash.device_follows = st.source is None
+        dash.fn = (lambda off, pts, pattern, phase, po, pv: device.gcode_dash(None, None, pattern, phase, po, pv, n=len(off) - 1)) if after_convert else device.gcode_dash
     return StrokeSteps(*(a or b for a, b in zip(st, own))), device
 
 
@@ -479,6 +508,40 @@ def _occlude(st: StrokeSteps, oc: Occlude, off_in, pts_in, pen, group, m: dict, 
     return off, pts, pen, group
 
 
+def _dash(st: StrokeSteps, dh: Dash, off_in, pts_in, pen, group, info: dict):
+    """the strokes, those with a pattern as their dashes; a stroke takes pattern and phase through its source, and a dash keeps its stroke's pen and, the
+    fifth value returned, its source; info["dash"]"""
+    n_in = len(off_in) - 1
+    src = np.asarray(st.source(n_in), np.int64).reshape(-1)
+    if len(src) != n_in or (src < 0).any() or (src >= len(dh.path_pattern)).any() or len(dh.path_phase) != len(dh.path_pattern):
+        raise RuntimeError("the source indices of the step polylines do not name input paths")
+    pattern = dh.path_pattern[src]
+    off, pts, origin, dst = dh.fn(off_in, pts_in, pattern, dh.path_phase[src], dh.pat_off, dh.pat_val)
+    off = np.asarray(off, np.int64).reshape(-1); pts = np.asarray(pts, np.int32).reshape(-1, 2); origin = np.asarray(origin, np.int64).reshape(-1)
+    d = {k: int(dst[k]) for k in DASH_STATS}
+    n = len(off) - 1
+    if n < 0 or len(origin) != n or (np.diff(origin) < 0).any() or (n and (origin[0] < 0 or origin[-1] >= n_in)):
+        raise RuntimeError("the dash pass's origins are not the input strokes in ascending order")
+    same = (np.diff(pts, axis=0) == 0).all(1) if len(pts) > 1 else np.zeros(0, bool)
+    if off[0] != 0 or int(off[-1]) != len(pts) or (np.diff(off) < 2).any() or np.delete(same, off[1:-1] - 1).any():
+        raise RuntimeError("the dash pass returned a stroke of fewer than two points or with a repeated point")
+    if d["paths_in"] != n_in or d["dashed"] != int((pattern >= 0).sum()) or d["paths_out"] != n or d["points_out"] != len(pts) or \
+            d["paths_out"] != d["paths_in"] - d["dashed"] + d["dashes"] - d["collapsed"] or not (0 <= d["length_on"] <= d["length_in"]):
+        raise RuntimeError("the dash pass's counts do not add up")
+    if group is not None:
+        pen, group = pen[origin], group[origin]
+    info["paths"] = n
+    info["dash"] = d
+    return off, pts, pen, group, src[origin]
+
+
+def _sources_behind_dash(src, n: int):
+    """what the source step gives behind a dash pass that did not run on the device whose sources are asked: the sources _dash gathered through origin"""
+    if n != len(src):
+        raise RuntimeError(f"{n} sources asked for, the dash pass left {len(src)} strokes")
+    return src
+
+
 def _simplify(st: StrokeSteps, off_in, pts_in, tol4: int, info: dict):
     """the same strokes with the same ends, every stroke an ascending selection of its own points; info["simplify"]"""
     n = len(off_in) - 1
@@ -532,14 +595,15 @@ def _plan(o: GcodeOptions, sc: ST.StreamConfig, off, pts, path_pen) -> ST.Plan:
 
 
 def stroke_stream(text_or_paths, opts: Optional[GcodeOptions], device, steps: StrokeSteps, timings: Optional[dict] = None, pens: Optional[np.ndarray] = None,
-                  occlude: Optional[Occlude] = None) -> Tuple[bytes, dict]:
-    """build_stream_from_gcode with the device steps as one record: parse, convert, pens of the strokes, [occlude, the SVG door's], dedup, merge, simplify,
-    order, plan, compile"""
+                  occlude: Optional[Occlude] = None, dash: Optional[Dash] = None, dash_fn: Optional[Callable] = None) -> Tuple[bytes, dict]:
+    """build_stream_from_gcode with the device steps as one record: parse, convert, pens of the strokes, [dash: --dash-mm gives every path the one pattern,
+    with dash_fn; the SVG door brings a record of its own], [occlude, the SVG door's], dedup, merge, simplify, order, plan, compile"""
     import time
     o = apply_speed_scale(GcodeOptions(**{f.name: getattr(opts, f.name) for f in fields(GcodeOptions)}) if opts is not None else GcodeOptions())
     W, H = target_size(o)
     sc = stream_config(o)
     rect, tol4 = stroke_options(o)
+    own_dash = dash_option(o)
     tm = timings if timings is not None else {}
     t0 = time.perf_counter()
 
@@ -568,7 +632,9 @@ def stroke_stream(text_or_paths, opts: Optional[GcodeOptions], device, steps: St
         return EMPTY_STREAM, dict(info, bytes=len(EMPTY_STREAM))
     if not (1 <= W <= MAX_TARGET_STEPS and 1 <= H <= MAX_TARGET_STEPS):
         raise ValueError(f"target size {W} x {H} steps: each side must be in 1..2^30 (step coordinates are int32 on the device)")
-    st, device = resolve_steps(steps, o, grouped, device, occlude=occlude)
+    if own_dash is not None and dash is None:                             # --dash-mm: every path gets the pattern
+        dash = Dash(dash_fn, np.zeros(len(off_mm) - 1, np.int32), np.full(len(off_mm) - 1, own_dash[1], np.int64), [0, len(own_dash[0])], own_dash[0])
+    st, device = resolve_steps(steps, o, grouped, device, occlude=occlude, dash=dash)
     m = dict(scale_x=o.scale_x, scale_y=o.scale_y, offset_x_mm=o.offset_x_mm, offset_y_mm=o.offset_y_mm, steps_per_mm=o.steps_per_mm, W=W, H=H, invert_y=int(bool(o.invert_y)))
     off, pts = _convert(st, off_mm, pts_mm, m, rect, info)
     lap("to_steps")
@@ -577,6 +643,14 @@ def stroke_stream(text_or_paths, opts: Optional[GcodeOptions], device, steps: St
         return EMPTY_STREAM, dict(info, bytes=len(EMPTY_STREAM))
     pen, group = _stroke_pens(st, o, pens, n, info) if grouped else (None, None)
     n_groups = MAX_PENS if pens is not None else 1
+    if dash is not None:                                                  # before the occlusion: a shape on top cuts dashes as it does on a screen
+        lap("order")                                                      # the sources and the pens belong to the order's lap
+        off, pts, pen, group, dash_src = _dash(st, dash, off, pts, pen, group, info)
+        if not dash.device_follows:                                       # a given pass or given sources: nobody gathered them through origin but _dash
+            st = st._replace(source=lambda k: _sources_behind_dash(dash_src, k))
+        lap("dash")
+        if len(off) <= 1:                                                 # every stroke lies in a gap
+            return EMPTY_STREAM, dict(info, bytes=len(EMPTY_STREAM))
     if occlude is not None:
         lap("order")                                                      # the sources and the pens belong to the order's lap
         off, pts, pen, group = _occlude(st, occlude, off, pts, pen, group, m, info)
@@ -588,12 +662,12 @@ def stroke_stream(text_or_paths, opts: Optional[GcodeOptions], device, steps: St
         off, pts, pen, group = _dedup(st, off, pts, pen, group, n_groups, info)
         lap("dedup")
     if o.merge_paths:
-        if not (o.dedup or occlude is not None):
+        if not (o.dedup or occlude is not None or dash is not None):
             lap("order")                                                  # the sources and the pens belong to the order's lap, as before
         off, pts, pen, group = _merge(st, o, off, pts, pen, group, n_groups, info)
         lap("merge")
     if tol4 is not None:
-        if not (o.merge_paths or o.dedup or occlude is not None):
+        if not (o.merge_paths or o.dedup or occlude is not None or dash is not None):
             lap("order")
         off, pts = _simplify(st, off, pts, tol4, info)
         lap("simplify")
@@ -614,6 +688,8 @@ IMPROVE_STATS = ("travel_before", "travel_after", "rounds", "converged_groups", 
 CLIP_STATS = ("segments", "inside", "cut", "outside", "paths_out", "points_out")
 DEDUP_STATS = ("segments", "whole", "cut", "covered", "pieces", "paths_out", "points_out", "draw_steps_in", "draw_steps_out")      # include/orip.h: orip_gcode_dedup
 OCCLUDE_STATS = ("segments", "whole", "cut", "hidden", "pieces", "collapsed", "paths_out", "points_out", "draw_steps_in", "draw_steps_out")      # include/orip.h: orip_gcode_occlude
+DASH_STATS = ("paths_in", "dashed", "dashes", "collapsed", "paths_out", "points_out", "length_in", "length_on")      # include/orip.h: orip_gcode_dash
+DASH_UNIT, DASH_MAX_ENTRIES = 256, 64         # include/orip.h: ORIP_DASH_UNIT (dash lengths are in 1/256 step), ORIP_DASH_MAX_ENTRIES
 SIMPLIFY_TOL4_MAX = (1 << 17) - 1             # include/orip.h: ORIP_SIMPLIFY_TOL4_MAX
 
 
@@ -649,6 +725,44 @@ def simplify_tol4(o) -> Optional[int]:
     if t > SIMPLIFY_TOL4_MAX:
         raise ValueError(f"--simplify-mm {mm:g} is {t / 4:g} steps: at most {SIMPLIFY_TOL4_MAX / 4:g}")
     return t
+
+
+def dash_entries(lengths: Sequence[float], scale: float) -> Optional[List[int]]:
+    """a dash array as the entries of a pattern in 1/256 step, int(round(length scale)) each, an odd count doubled as SVG does; None when an entry would be
+    under one step or over 2^40, or when there are none or more than 64: nothing the pass can take"""
+    ent = [int(round(float(v) * scale)) for v in lengths]
+    ent = ent * 2 if len(ent) % 2 else ent
+    if not ent or len(ent) > DASH_MAX_ENTRIES or any(not (DASH_UNIT <= e <= (1 << 40)) for e in ent):
+        return None
+    return ent
+
+
+def dash_option(o) -> Optional[Tuple[List[int], int]]:
+    """None without --dash-mm, else (the pattern's entries in 1/256 step, the phase): 1 .. 64 lengths in mm, each at least a step; --dash-offset-mm, of any
+    sign, reduced mod the pattern's length in Python integers"""
+    if o.dash_mm is None:
+        if o.dash_offset_mm is not None:
+            raise ValueError("--dash-offset-mm needs --dash-mm")
+        return None
+    scale = float(o.steps_per_mm) * DASH_UNIT
+    try:
+        mm = [float(tok) for tok in str(o.dash_mm).split(",")]
+    except ValueError:
+        raise ValueError(f"--dash-mm {o.dash_mm!r}: comma-separated lengths in mm")
+    if not (1 <= len(mm) <= DASH_MAX_ENTRIES):
+        raise ValueError(f"--dash-mm: {len(mm)} lengths, 1..{DASH_MAX_ENTRIES} are taken")
+    for v in mm:
+        if not (v >= 0.0) or v == float("inf"):
+            raise ValueError(f"--dash-mm {v:g}: a length must be a number and not negative")
+        if not (DASH_UNIT <= int(round(v * scale)) <= (1 << 40)):
+            raise ValueError(f"--dash-mm {v:g} at {float(o.steps_per_mm):g} steps per mm is {int(round(v * scale)) / DASH_UNIT:g} steps: at least 1, at most 2^32")
+    ent = dash_entries(mm, scale)
+    if ent is None:
+        raise ValueError(f"--dash-mm: {2 * len(mm)} entries once the odd count is doubled, at most {DASH_MAX_ENTRIES}")
+    x = 0.0 if o.dash_offset_mm is None else float(o.dash_offset_mm)
+    if x != x or x in (float("inf"), float("-inf")):
+        raise ValueError("--dash-offset-mm must be a number")
+    return ent, int(round(x * scale)) % sum(ent)
 
 
 def stroke_options(o) -> Tuple[Optional[Tuple[int, int, int, int]], Optional[int]]:
@@ -699,6 +813,9 @@ def build_argparser() -> argparse.ArgumentParser:
     add_stroke_args(ap, STROKE_ARGS[:2])
     ap.add_argument("--tool-pens", action="store_true", help="a path is drawn with the pen its T word names (T0..T7; before any T: --color-index), pen after pen")
     add_stroke_args(ap, STROKE_ARGS[2:])
+    ap.add_argument("--dash-mm", default=None, help="draw every path dashed: 1..64 comma-separated lengths in mm, dash and gap in turn (an odd count is repeated, as "
+                                                    "in SVG); each at least one step; the pattern starts anew with every path")
+    ap.add_argument("--dash-offset-mm", type=float, default=None, help="where in the pattern a path starts (any sign; default 0); needs --dash-mm")
     return ap
 
 
@@ -734,6 +851,12 @@ def report_lines(tag: str, info: dict, unmatched: bool = False):
     if "pens" in info:
         yield (f"[{tag}] pens: " + ", ".join(f"{p}: {k} paths" for p, k in enumerate(info["pens"]["paths"]) if k) + "; " +
                (f"{info['pens']['unmatched']} without a stroke colour, " if unmatched else "") + f"{info['pens']['reversed']} strokes reversed")
+    if "dash" in info and "dashed" not in info["dash"]:
+        yield f"[{tag}] dash: no stroke dashed, {info['dash']['ignored']} dash arrays ignored (under a step, over the limits or all zero): their strokes are solid"
+    elif "dash" in info:
+        d = info["dash"]
+        yield (f"[{tag}] dash: {d['dashed']} strokes dashed, {d['length_on'] / DASH_UNIT:.0f} of {d['length_in'] / DASH_UNIT:.0f} steps drawn in {d['dashes']} dashes, "
+               f"{d['collapsed']} under a step dropped" + (f", {d['ignored']} dash arrays ignored" if d.get("ignored") else "") + f" -> {d['paths_out']} strokes")
     if "occlude" in info:
         yield (f"[{tag}] " + "occlude: {segments} segments: {whole} whole, {cut} cut, {hidden} hidden -> {paths_out} strokes, "
                               "pen-down steps {draw_steps_in} -> {draw_steps_out}".format(**info["occlude"]))
@@ -758,6 +881,7 @@ def main(argv: Optional[Sequence[str]] = None, **device_steps) -> None:
     opts = options_from_args(a)
     apply_speed_scale(GcodeOptions(speed_scale=opts.speed_scale))        # a bad scale ends the run before the file is read, as in the reference
     stroke_options(opts)
+    dash_option(opts)
     text = Path(a.input).read_bytes()
     data, info = build_stream_from_gcode(text, opts, **device_steps)
     Path(a.output).write_bytes(data)

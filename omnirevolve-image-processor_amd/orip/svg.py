@@ -54,6 +54,13 @@ its own outline nor its own hatch, and everything painted before it where it lie
 out and before the dedup, which then removes what is doubled among what is left; the merge rejoins a closed outline that was cut at its start vertex.
 Pens and levels follow through origin.  The G-code file is not changed; the preview is rendered from the stream and shows the result.
 
+--dashes (off unless given; ours, svg2stream.py only; include/orip.h states the rule): a stroke that states a stroke-dasharray is drawn as its dashes.  The
+parser records stroke-dasharray and stroke-dashoffset per subpath, resolved as the stroke colour is (style property, else presentation attribute, else the
+enclosing groups; a unit is dropped); dash_patterns() scales them to 1/256 steps and says which values leave the stroke solid.  The pass runs on the step
+polylines, on the device (orip_gcode_dash), after the pens have been worked out and before the occlusion, so a shape on top cuts dashes as it does on a
+screen, and the phase counts from the start of every stroke the conversion leaves.  Hatch lines are never dashed.  A drawing that states no dash array gets
+no device call.  Declined: dots for zero-length dashes, stroke-linecap, pathLength, vector-effect.  The G-code file is not changed.
+
 The device steps are injectable, as in orip/gcode.py, so that this host logic can be tested without a GPU; the product has no CPU path."""
 from __future__ import annotations
 
@@ -85,7 +92,8 @@ class SegmentTable:
     closed[p]: it ended with Z (the closing line is one of its segments).  fill_group[p]: -1, or the ordinal of the element subpath p belongs to when that
     element is to be hatched (parse_svg; None counts as all -1).  stroke_rgb[p], fill_rgb[p]: the colour of the subpath's element as written, 8-bit sRGB, or
     (-1, -1, -1) where none is stated or what is stated is no colour (None counts as all -1).  element[p]: the ordinal of subpath p's element among the
-    elements that drew something, its place in paint order (None: not recorded; --occlude needs it)."""
+    elements that drew something, its place in paint order (None: not recorded; --occlude needs it).  dash_array[p], dash_offset[p]: stroke-dasharray and
+    stroke-dashoffset of the subpath's element as written, or None where nobody states one (lists of strings; None: not recorded; --dashes reads them)."""
     kind: np.ndarray
     ctrl: np.ndarray
     mat: np.ndarray
@@ -97,6 +105,8 @@ class SegmentTable:
     stroke_rgb: Optional[np.ndarray] = None
     fill_rgb: Optional[np.ndarray] = None
     element: Optional[np.ndarray] = None
+    dash_array: Optional[list] = None
+    dash_offset: Optional[list] = None
 
     @property
     def n_seg(self) -> int: return len(self.kind)
@@ -122,6 +132,7 @@ class _Builder:
         self.sub_off = [0]; self.closed: List[int] = []
         self.fill_group: List[int] = []; self.elements = 0; self.element: List[int] = []
         self.stroke_rgb: List[Tuple[int, int, int]] = []; self.fill_rgb: List[Tuple[int, int, int]] = []
+        self.dash_array: List[Optional[str]] = []; self.dash_offset: List[Optional[str]] = []
         self.mats: List[Tuple[float, ...]] = [IDENTITY]
         self.m = 0
         self.cur = self.start = (0.0, 0.0)
@@ -196,7 +207,7 @@ class _Builder:
         return SegmentTable(np.asarray(self.kind, np.int32), np.asarray(self.ctrl, np.float64).reshape(-1, 4, 2), np.asarray(self.mat, np.int32),
                             np.asarray(self.sub_off, np.int64), np.asarray(self.closed, np.uint8), np.asarray(self.mats, np.float64).reshape(-1, 6), float(canvas_height),
                             np.asarray(self.fill_group, np.int32), np.asarray(self.stroke_rgb, np.int16).reshape(-1, 3), np.asarray(self.fill_rgb, np.int16).reshape(-1, 3),
-                            np.asarray(self.element, np.int32))
+                            np.asarray(self.element, np.int32), list(self.dash_array), list(self.dash_offset))
 
 
 # ------------------------------------------------------------------ path data
@@ -416,6 +427,65 @@ def _stroke_of(el, inherited: Optional[str]) -> Optional[str]:
     return inherited if own is None else own.strip().lower()
 
 
+_DASHARRAY = re.compile(r"(?:^|;)\s*stroke-dasharray\s*:\s*([^;]+)")
+_DASHOFFSET = re.compile(r"(?:^|;)\s*stroke-dashoffset\s*:\s*([^;]+)")
+
+
+def _dash_of(el, inherited: Optional[str], prop, attr: str) -> Optional[str]:
+    """stroke-dasharray or stroke-dashoffset of the element as written, resolved as _stroke_of resolves the stroke"""
+    m = prop.search(el.get("style") or "")
+    own = m.group(1) if m else el.get(attr)
+    return inherited if own is None else own.strip().lower()
+
+
+def parse_dasharray(s: Optional[str]) -> Optional[List[float]]:
+    """the lengths of a stroke-dasharray, separated by commas or white space, a unit dropped as parse_length drops it; None where SVG draws the stroke solid:
+    nothing stated, none, or a list that holds a negative, a percentage or something that is no number (an invalid value)"""
+    if s is None or s.strip().lower() in ("", "none"):
+        return None
+    out = []
+    for tok in re.split(r"[\s,]+", s.strip().strip(",")):
+        v = None if tok.endswith("%") else parse_length(tok)
+        if v is None or not (v >= 0.0) or not math.isfinite(v):
+            return None
+        out.append(v)
+    return out
+
+
+def dash_patterns(table: SegmentTable, fit_scale, steps_per_mm: float, n_paths: int):
+    """--dashes: the drawing's own dash arrays as what orip_gcode_dash takes -> (pattern int32 [n_paths], phase int64 [n_paths], pat_off int32, pat_val int64,
+    ignored).  Fitted path p < n_sub is subpath p; the paths behind them are hatch lines and are never dashed.  A length in user units becomes 1/256 steps
+    by the scale sqrt(|det|) of the subpath's accumulated matrix x sqrt(|sx sy|) of the applied fit x steps per mm x 256, and every entry is rounded by
+    itself (int(round())); an odd list is doubled.  Deviation, stated: under a non-uniform transform SVG dashes in the element's own space, so that a dash
+    along the stretched axis is longer than one across it; ours measures along the drawn stroke with the mean scale.  The offset is scaled alike and
+    reduced mod the pattern's length.  Identical scaled patterns share a table entry.  A list that sums to zero, that has an entry which rounds to under
+    one step (SVG draws a dot or nothing for a zero entry; ours draws the stroke solid: stated) or over 2^40, or more than 64 entries after doubling,
+    leaves the stroke solid and is counted in `ignored`."""
+    pattern = np.full(int(n_paths), -1, np.int32); phase = np.zeros(int(n_paths), np.int64)
+    arrays = table.dash_array if table.dash_array is not None else []
+    offsets = table.dash_offset if table.dash_offset is not None else []
+    if len(arrays) not in (0, table.n_sub) or len(offsets) not in (0, table.n_sub) or n_paths < table.n_sub * bool(arrays):
+        raise ValueError(f"{len(arrays)} dash arrays and {len(offsets)} dash offsets for {table.n_sub} subpaths in {n_paths} paths")
+    g = math.sqrt(abs(float(fit_scale[0]) * float(fit_scale[1]))) * float(steps_per_mm) * GC.DASH_UNIT
+    known, vals, off, ignored = {}, [], [0], 0
+    for p, text in enumerate(arrays):
+        lengths = parse_dasharray(text)
+        if lengths is None:
+            continue
+        M = table.mats[int(table.mat[int(table.sub_off[p])])]
+        k = math.sqrt(abs(float(M[0]) * float(M[3]) - float(M[1]) * float(M[2]))) * g
+        ent = GC.dash_entries(lengths, k) if math.isfinite(k) and sum(lengths) > 0.0 else None
+        if ent is None:
+            ignored += 1
+            continue
+        if tuple(ent) not in known:
+            known[tuple(ent)] = len(off) - 1; vals += ent; off.append(len(vals))
+        pattern[p] = known[tuple(ent)]
+        x = parse_length(offsets[p]) if offsets else None
+        phase[p] = int(round((x or 0.0) * k)) % sum(ent)
+    return pattern, phase, np.asarray(off, np.int32), np.asarray(vals, np.int64), ignored
+
+
 # the 16 basic CSS colour keywords, and orange
 COLOR_KEYWORDS = {"black": (0, 0, 0), "silver": (192, 192, 192), "gray": (128, 128, 128), "white": (255, 255, 255), "maroon": (128, 0, 0), "red": (255, 0, 0),
                   "purple": (128, 0, 128), "fuchsia": (255, 0, 255), "green": (0, 128, 0), "lime": (0, 255, 0), "olive": (128, 128, 0), "yellow": (255, 255, 0),
@@ -493,18 +563,20 @@ def hatch_pens(table: SegmentTable, groups, palette) -> np.ndarray:
     return pen[first[groups]]
 
 
-def _walk(b: _Builder, el, m: int, fill: Optional[str] = None, fill_all: bool = False, stroke: Optional[str] = None):
+def _walk(b: _Builder, el, m: int, fill: Optional[str] = None, fill_all: bool = False, stroke: Optional[str] = None, dash: Optional[str] = None,
+          dash_at: Optional[str] = None):
     tag = el.tag.rsplit("}", 1)[-1] if isinstance(el.tag, str) else ""
     if not tag or tag in SKIPPED or (el.get("display") or "").strip() == "none":
         return
     fill = _fill_of(el, fill)
     stroke = _stroke_of(el, stroke)
+    dash = _dash_of(el, dash, _DASHARRAY, "stroke-dasharray"); dash_at = _dash_of(el, dash_at, _DASHOFFSET, "stroke-dashoffset")
     if el.get("transform"):
         b.mats.append(_mul(b.mats[m], parse_transform(el.get("transform"))))
         m = len(b.mats) - 1
     if tag in GROUPS:
         for ch in el:
-            _walk(b, ch, m, fill, fill_all, stroke)
+            _walk(b, ch, m, fill, fill_all, stroke, dash, dash_at)
     else:
         b.m = m
         _draw_element(b, el, tag)
@@ -514,6 +586,7 @@ def _walk(b: _Builder, el, m: int, fill: Optional[str] = None, fill_all: bool = 
             wanted = tag != "line" and (fill_all or (fill is not None and fill not in ("none", "transparent")))
             b.fill_group.extend([b.elements if wanted else -1] * new); b.element.extend([b.elements] * new)
             b.stroke_rgb.extend([parse_color(stroke)] * new); b.fill_rgb.extend([parse_color(fill)] * new)
+            b.dash_array.extend([dash] * new); b.dash_offset.extend([dash_at] * new)
             b.elements += 1
 
 
@@ -572,6 +645,7 @@ class SvgOptions:
     simplify_mm: Optional[float] = None                 # vertices within this distance of the stroke are dropped (orip.gcode); None: none are
     dedup: bool = False                                 # collinear segments of one pen that lie over each other are drawn once (orip.gcode)
     occlude: bool = False                               # filled shapes hide what lies under them (svg2stream.py only)
+    dashes: bool = False                                # stroke-dasharray is drawn as dashes (svg2stream.py only)
 
 
 HATCH_DIRECTIONS = {"horizontal": HATCH_HORIZONTAL, "vertical": HATCH_VERTICAL, "cross": HATCH_HORIZONTAL | HATCH_VERTICAL}
@@ -808,7 +882,7 @@ def build_stream_from_svg(text: Union[str, bytes, SegmentTable], opts: Optional[
                           want_paths: bool = False, hatch_groups_fn: Optional[Callable] = None, source_fn: Optional[Callable] = None,
                           order_pens_fn: Optional[Callable] = None, merge_fn: Optional[Callable] = None, improve_fn: Optional[Callable] = None,
                           clip_fn: Optional[Callable] = None, simplify_fn: Optional[Callable] = None, dedup_fn: Optional[Callable] = None,
-                          occlude_fn: Optional[Callable] = None) -> Tuple[bytes, dict]:
+                          occlude_fn: Optional[Callable] = None, dash_fn: Optional[Callable] = None) -> Tuple[bytes, dict]:
     """The stream of an SVG text (or of a parsed SegmentTable).  Device steps, each None = the GPU (there is no CPU path in the product):
       flatten_fn(table, tol_raw) -> paths          orip_svg_flatten      (`paths` is whatever the other steps take: on the GPU a count, the points stay there)
       bbox_fn(paths) -> (min x, min y, max x, max y)   orip_svg_bbox
@@ -833,6 +907,9 @@ def build_stream_from_svg(text: Union[str, bytes, SegmentTable], opts: Optional[
     and, only with --occlude (after the pens have been worked out, before the dedup; it needs source_fn and, with hatching, hatch_groups_fn):
       occlude_fn(paths, off, pts, level int32 [n], ring_sub, ring_level, map, clamp) -> (off, pts, origin int32, stats)   orip_svg_occlude
     the rings are the fitted paths ring_sub with their levels, clamp = not --clip; info["occlude"] = the ten counts of include/orip.h.
+    and, only with --dashes on a drawing that states a dash array (after the pens have been worked out, before the occlusion; it needs source_fn):
+      dash_fn                                      as in orip.gcode.build_stream_from_gcode; the patterns are dash_patterns()'s
+    info["dash"] = the eight counts of include/orip.h and "ignored", the dash arrays that left their stroke solid (where no stroke is dashed, "ignored" alone, if any).
     With --pen-colors, info["path_pens"] is the pen of every fitted path (hatch lines included, --color-index where no stroke is stated).
     Returns (bytes, info)."""
     import time
@@ -864,9 +941,10 @@ def build_stream_from_svg(text: Union[str, bytes, SegmentTable], opts: Optional[
         ring_sub, ring_level = occlusion_rings(table)
         occ = GC.Occlude(None if occlude_fn is None else (lambda off, pts, level, rs, rl, m, clamp: occlude_fn(paths, off, pts, level, rs, rl, m, clamp)),
                          np.zeros(0, np.int64), ring_sub, ring_level, not o.clip)
-    steps, device = GC.resolve_steps(steps, go, pens_on or o.allow_reverse, device, force=bool(own), occlude=occ,
-                                     convert=lambda dev: lambda _off, _pts, m, *rect: (_Resident(dev).clip if rect else _Resident(dev).steps)(paths, m, *rect))
-    if own:
+    if own:                                                 # steps of this door's own; the stroke steps are resolved below, once the fit says whether a dash pass runs
+        if device is None:
+            from .stages import device as _default_device
+            device = _default_device()
         R = _Resident(device)
         flatten_fn = flatten_fn or R.flatten; bbox_fn = bbox_fn or R.bbox; fit_fn = fit_fn or R.fit; fetch_fn = fetch_fn or R.fetch
         hatch_fn = hatch_fn or R.hatch; hatch_groups_fn = hatch_groups_fn or R.hatch_groups
@@ -885,7 +963,16 @@ def build_stream_from_svg(text: Union[str, bytes, SegmentTable], opts: Optional[
     tm["fetch_paths"] = tm.get("fetch_paths", 0.0) + (time.perf_counter() - t0)
     if occ is not None:
         occ.path_level = path_levels(table, paths, info, hatch_groups_fn)
-    data, ginfo = GC.stroke_stream((off_mm, np.zeros((int(off_mm[-1]), 2))), go, device, steps, tm, pens, occ)
+    dsh, ignored = None, 0
+    if o.dashes and table.dash_array is not None:           # the fit is known now, and with it whether any stroke is dashed: the residency chain needs to know
+        pattern, phase, pat_off, pat_val, ignored = dash_patterns(table, info["scale"], o.steps_per_mm, len(off_mm) - 1)
+        if (pattern >= 0).any():                            # no usable dash array: no pass, no device call
+            dsh = GC.Dash(dash_fn, pattern, phase, pat_off, pat_val)
+    steps, device = GC.resolve_steps(steps, go, pens_on or o.allow_reverse, device, force=bool(own), occlude=occ, dash=dsh,
+                                     convert=lambda dev: lambda _off, _pts, m, *rect: (_Resident(dev).clip if rect else _Resident(dev).steps)(paths, m, *rect))
+    data, ginfo = GC.stroke_stream((off_mm, np.zeros((int(off_mm[-1]), 2))), go, device, steps, tm, pens, occ, dsh)
+    if "dash" in ginfo or ignored:                          # an ignored dash array is reported whether or not a pass ran: the stroke is solid, and the line says so
+        ginfo["dash"] = dict(ginfo.get("dash", {}), ignored=ignored)
     return data, dict(ginfo, **info)
 
 
@@ -937,6 +1024,8 @@ def build_stream_argparser() -> argparse.ArgumentParser:
     GC.add_stroke_args(ap, ("--no-reorder", "--pen-order", "--allow-reverse") + GC.STROKE_ARGS[3:], "; the G-code file is not changed")
     ap.add_argument("--occlude", action="store_true", help="filled shapes (what --hatch-fill marks) hide the strokes and hatch lines of the elements painted before them; "
                                                            "exact on the step grid; the G-code file is not changed")
+    ap.add_argument("--dashes", action="store_true", help="draw a stroke that states a stroke-dasharray as its dashes, measured on the step grid from the start of "
+                                                          "every stroke (hatch lines stay solid); the G-code file is not changed")
     ap.add_argument("--no-preview", action="store_true", help="do not render <svg stem>_stream_preview.png")
     ap.add_argument("--preview-render-width", type=int, default=d.preview_render_width)
     ap.add_argument("--preview-render-height", type=int, default=d.preview_render_height)

@@ -84,12 +84,22 @@ int orip_resize_area(orip_ctx* ctx, const uint8_t* src, int H, int W, int cn, in
 int orip_set_image(orip_ctx* ctx, const uint8_t* bgr, int H, int W);
 /* cv2.cvtColor(BGR2LAB) (02:35) of the whole image or of the pixels idx[0..n) -> host u8 [n,3] (test hook) */
 int orip_lab_of(orip_ctx* ctx, const int64_t* idx, int64_t n, uint8_t* lab_out);
-/* _kmeans_lab fit part (02:39-49): Lab of the sampled pixels + cv2.kmeans(PP centres, attempts, (EPS|ITER)) */
+/* _kmeans_lab fit part (02:39-49): Lab of the sampled pixels + cv2.kmeans(PP centres, attempts, (EPS|ITER)).  The samples: sample_idx == NULL with
+ * n_idx == 0: every pixel; a host pointer: these n_idx pixels, uploaded by this call; NULL with n_idx == -1: the resident set (orip_kmeans_samples) --
+ * the call fails, naming both sizes, when there is none or it was made for another pixel count than the image's. */
 int orip_kmeans_fit(orip_ctx* ctx, const int64_t* sample_idx, int64_t n_idx, int K, int attempts, int max_iter,
                     double eps, float* centers_out /* [K,3] in cv2.kmeans order */, double* compactness_out);
+/* The subsample of 02:39-44 is a function of the pixel count and a fixed seed, the same array for every image of one size: orip_kmeans_samples uploads it
+ * into a buffer the context keeps for nothing else and records the pixel count H * W of the image set at that moment (indices outside 0 .. H * W - 1 are
+ * refused); sample_idx == NULL drops the set.  It stays until the next orip_kmeans_samples, the first image of another pixel count (orip_set_image,
+ * orip_resize_area with as_image) or orip_destroy; an image of the same pixel count keeps it.  orip_kmeans_samples_info: what is resident -- both 0 when
+ * nothing is; either pointer may be NULL. */
+int orip_kmeans_samples(orip_ctx* ctx, const int64_t* sample_idx, int64_t n_idx);
+int orip_kmeans_samples_info(orip_ctx* ctx, int64_t* n_idx, int64_t* n_pixels);
 /* ---- process_colors.py (standalone label-map tool) ---- */
 /* kmeans_palette (:31-46): cv2.kmeans (PP centres) over the R, G, B bytes of the sampled pixels of the image set with orip_set_image; same
- * arguments as orip_kmeans_fit, centres in R, G, B order.  The subsample (:35-39, numpy RandomState) stays on the host. */
+ * arguments as orip_kmeans_fit (the resident set of orip_kmeans_samples included), centres in R, G, B order.  The subsample (:35-39, numpy
+ * RandomState) stays on the host. */
 int orip_kmeans_fit_rgb(orip_ctx* ctx, const int64_t* sample_idx, int64_t n_idx, int K, int attempts, int max_iter,
                         double eps, float* centers_out /* [K,3] */, double* compactness_out);
 /* assign_labels (:69-77): index of the nearest palette colour per pixel, with the reference's int16 arithmetic (squares of differences above

@@ -179,6 +179,8 @@ static_assert(sizeof(LaneFlags) <= 4096, "LaneRes::flags is 4096 bytes, allocate
 // ever indexed by its constant on that lane.
 //   lane 0  vtmp[VT0_MEMO]       memo planes of the walker     orip_contours_reserve (cleared there) or orip_contours_prepare -> last trace of the prepare
 //   lane 0  vtmp[VT0_EDGE_BITS]  bit planes of `edges`         orip_detect_edges (c->edge_bits) -> the next orip_contours_prepare, which thins in them
+//           its second set (orip_edge_planes: b) then holds the degree-2 planes: k_bits_to_skel_state of that prepare -> lane 0's ev3, while the chain kernels
+//           step on them on the side stream; only a prepare's thinning writes it again, behind ev3 (orip_detect_edges sizes it and writes the first set only)
 //   lane 0  vtmp[VT0_KEYS, VT0_COMP_START, VT0_ORDER, VT0_LOG_USED, VT0_WINFO]  the stage-04 schedule (Prep04::A, Prep04::order: keys / lin of the skeleton, first
 //           pixel of each component, largest-first component order, log entries used per component, two WalkInfo per pixel): orip_contours_prepare -> the last
 //           orip_contours_layer of that prepare (every layer's k_trace / trace_finish reads them from its own lane); orip_contours_invalidate ends the lifetime
@@ -310,6 +312,11 @@ struct orip_ctx {
     DBuf cref, cpix;               // forced stretches of the skeletons (walker.h: ST_CHAIN): position plane and chain pixel lists
     DBuf lab_tabs;  // u16 gamma[256] + u16 cbrt[3072] + i32 coeffs[9]
     bool tabs_ready = false;
+    // The resident k-means sample set (orip_kmeans_samples): km_idx int64[km_n], pixel indices into an image of km_npx pixels; km_n == 0: none.  The buffer
+    // serves nothing else, so no stage overwrites it.  Lifetime: orip_kmeans_samples -> the next orip_kmeans_samples, or the first image of another pixel
+    // count (orip_set_image, orip_resize_area as_image), or orip_destroy; an image of the same pixel count keeps it (the set depends on the count alone).
+    DBuf km_idx; int64_t km_n = 0, km_npx = 0;
+    void km_drop_unless(int64_t npx) { if (km_npx != npx) { km_n = 0; km_npx = 0; } }
     const void* edge_bits = nullptr;   // bit planes of `edges` left in lane 0's scratch by stage 03 (nullptr: not available); consumed by stage 04
     const void* morphed_bits = nullptr; // bit planes of the opened / closed masks left in tmpA for stage 03's NMS kernel (nullptr: byte planes in tmpB)
     const void* mask_bits = nullptr;   // bit planes of `masks` left in tmpA by stage 02 (nullptr: not available); consumed by stage 03

@@ -151,6 +151,6 @@ extern "C" int orip_resize_area(orip_ctx* c, const uint8_t* src, int H, int W, i
     HIPC(c, hipGetLastError());
     if (dst) HIPC(c, hipMemcpyAsync(dst, out, ndst, hipMemcpyDeviceToHost, s));
     HIPC(c, hipStreamSynchronize(s));
-    if (as_image) { c->H = newH; c->W = newW; c->an_ready = false; }
+    if (as_image) { c->H = newH; c->W = newW; c->an_ready = false; c->km_drop_unless((int64_t)newH * newW); }
     return 0;
 }

@@ -715,6 +715,7 @@ extern "C" int orip_set_image(orip_ctx* c, const uint8_t* bgr, int H, int W) {
     if (!bgr || H <= 0 || W <= 0) ORIP_FAIL(c, "bad image %dx%d", W, H);
     ORIP_TRY(orip_raster02_lab_tables(c));
     c->H = H; c->W = W;
+    c->km_drop_unless((int64_t)H * W);          // (a sample set made for another pixel count)
     HIPC(c, c->image.ensure((size_t)H * W * 3 + 16));
     HIPC(c, hipMemcpyAsync(c->image.p, bgr, (size_t)H * W * 3, hipMemcpyHostToDevice, LN(c).stream));
     return 0;
@@ -759,18 +760,23 @@ static int kmeans_fit_impl(orip_ctx* c, bool rgb, const int64_t* sample_idx, int
     c->mask_bits = nullptr;
     if (!c->image.p) ORIP_FAIL(c, "no image set");
     if (K < 1 || K > ORIP_MAX_LAYERS) ORIP_FAIL(c, "K=%d out of range 1..%d", K, ORIP_MAX_LAYERS);
-    ORIP_TRY(orip_contours_invalidate(c));       // (the sample indices go to tmpC)
-    int64_t N = sample_idx ? n_idx : (int64_t)c->H * c->W;
+    ORIP_TRY(orip_contours_invalidate(c));       // (the sample indices of the upload path go to tmpC)
+    const int64_t npx = (int64_t)c->H * c->W;
+    const bool resident = !sample_idx && n_idx == -1;      // the set orip_kmeans_samples left in the context
+    if (resident && (c->km_n == 0 || c->km_npx != npx))
+        ORIP_FAIL(c, "no resident sample set for this image: the set holds %lld indices made for %lld pixels, the image has %lld pixels (orip_kmeans_samples)",
+                  (long long)c->km_n, (long long)c->km_npx, (long long)npx);
+    int64_t N = resident ? c->km_n : (sample_idx ? n_idx : npx);
     if (N < K || N > 0x7fffffff) ORIP_FAIL(c, "bad sample count %lld", (long long)N);
     HIPC(c, c->tmpB.ensure((size_t)N * 3 + 16));
     if (sample_idx) { HIPC(c, c->tmpC.ensure((size_t)N * 8)); HIPC(c, hipMemcpyAsync(c->tmpC.p, sample_idx, (size_t)N * 8, hipMemcpyHostToDevice, LN(c).stream)); }
+    const int64_t* d_idx = resident ? c->km_idx.as<int64_t>() : (sample_idx ? c->tmpC.as<int64_t>() : nullptr);
     if (rgb) {
-        hipLaunchKernelGGL(k_rgb_gather, dim3(std::min<int64_t>(2048, cdiv(N, 256))), dim3(256), 0, LN(c).stream, c->image.as<u8>(),
-                           sample_idx ? c->tmpC.as<int64_t>() : nullptr, N, c->tmpB.as<u8>());
+        hipLaunchKernelGGL(k_rgb_gather, dim3(std::min<int64_t>(2048, cdiv(N, 256))), dim3(256), 0, LN(c).stream, c->image.as<u8>(), d_idx, N, c->tmpB.as<u8>());
     } else {
         ProfScope ps(c, "k_lab_gather");
-        hipLaunchKernelGGL(k_lab_gather, dim3(std::min<int64_t>(2048, cdiv(N, 256))), dim3(256), 0, LN(c).stream, c->image.as<u8>(),
-                           sample_idx ? c->tmpC.as<int64_t>() : nullptr, N, c->tmpB.as<u8>(), c->lab_tabs.as<LabTabs>());
+        hipLaunchKernelGGL(k_lab_gather, dim3(std::min<int64_t>(2048, cdiv(N, 256))), dim3(256), 0, LN(c).stream, c->image.as<u8>(), d_idx, N, c->tmpB.as<u8>(),
+                           c->lab_tabs.as<LabTabs>());
     }
     HIPC(c, c->tmpD.ensure((size_t)N * 4 * 4 + 256));     // (later stages find tmpD at least this large)
     attempts = std::max(attempts, 1);
@@ -802,6 +808,30 @@ static int kmeans_fit_impl(orip_ctx* c, bool rgb, const int64_t* sample_idx, int
     }
     memcpy(centers_out, hr[bg].cen, sizeof(float) * K * 3);
     if (compactness_out) *compactness_out = hr[bg].compact;
+    return 0;
+}
+
+// The subsample of 02:39-44 depends on the pixel count and a fixed seed alone: a resident chain uploads it once and every later fit of an image of that
+// size gathers through the context's copy (the set's lifetime: orip_ctx.h).  Synchronised, so the caller's array is free on return.
+extern "C" int orip_kmeans_samples(orip_ctx* c, const int64_t* sample_idx, int64_t n_idx) {
+    orip_enter(c);
+    c->km_n = 0; c->km_npx = 0;
+    if (!sample_idx) return 0;
+    if (!c->image.p) ORIP_FAIL(c, "no image set");
+    const int64_t npx = (int64_t)c->H * c->W;
+    if (n_idx < 1 || n_idx > 0x7fffffff) ORIP_FAIL(c, "bad sample count %lld", (long long)n_idx);
+    for (int64_t i = 0; i < n_idx; i++)
+        if (sample_idx[i] < 0 || sample_idx[i] >= npx) ORIP_FAIL(c, "sample %lld is pixel %lld of %lld", (long long)i, (long long)sample_idx[i], (long long)npx);
+    HIPC(c, c->km_idx.ensure((size_t)n_idx * 8));
+    HIPC(c, hipMemcpyAsync(c->km_idx.p, sample_idx, (size_t)n_idx * 8, hipMemcpyHostToDevice, LN(c).stream));
+    HIPC(c, hipStreamSynchronize(LN(c).stream));
+    c->km_n = n_idx; c->km_npx = npx;
+    return 0;
+}
+extern "C" int orip_kmeans_samples_info(orip_ctx* c, int64_t* n_idx, int64_t* n_pixels) {
+    orip_enter(c);
+    if (n_idx) *n_idx = c->km_n;
+    if (n_pixels) *n_pixels = c->km_npx;
     return 0;
 }
 

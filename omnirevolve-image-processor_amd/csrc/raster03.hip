@@ -236,7 +236,12 @@ __device__ __forceinline__ void uf_unite(int* L, int a, int b) {
 }
 
 // components of bit planes (one bit per pixel, 64 per word, blockIdx.z = layer): a thread owns a word, returns at once when it is
-// empty and walks its set bits otherwise.  Same ids (block raster) and the same union-find as above.  mode 0 init, 1 merge, 2 flatten.
+// empty and works on its RUNS (maximal stretches of set bits inside the word) otherwise.  Same ids (block raster) and the same union-find as above; an id
+// grows with x along a row, so the first pixel of a run has the run's smallest id.  mode 0 init: every pixel of a run points at the run's first pixel (the
+// forest in between is free: everything downstream reads only the flattened label, the component's minimum id).  mode 1 merge, one union per adjacency
+// between runs instead of up to four per pixel: the run that starts at bit 0 with the word on its left when that one ends set, and every run with one pixel
+// of each stretch of the row above inside its own extent widened by a pixel on either side (8-connectivity) -- a stretch there is part of one run of the
+// row above, and the runs of that row are joined among themselves by their own threads.  mode 2 flatten.
 __global__ __launch_bounds__(256) void k_ccl_bits(const unsigned long long* __restrict__ bits, int* __restrict__ par, int H, int W, int Ww, int mode) {
     const size_t nw = (size_t)H * Ww, wi = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (wi >= nw) return;
@@ -246,21 +251,29 @@ __global__ __launch_bounds__(256) void k_ccl_bits(const unsigned long long* __re
     const int Wb = (W + 1) >> 1, Hb = (H + 1) >> 1;
     int* L = par + (size_t)Wb * Hb * 4 * blockIdx.z;
     const int y = (int)(wi / Ww), xw = (int)(wi % Ww), x0 = xw * 64;
-    if (mode != 1) {
-        while (m) { const int j = __ffsll((long long)m) - 1; m &= m - 1; const int id = px_id(y, x0 + j, Wb); L[id] = mode == 0 ? id : uf_find(L, id); }
+    if (mode == 2) {
+        while (m) { const int j = __ffsll((long long)m) - 1; m &= m - 1; const int id = px_id(y, x0 + j, Wb); L[id] = uf_find(L, id); }
         return;
     }
-    const unsigned long long left = xw > 0 ? b[wi - 1] : 0ULL;
-    unsigned long long U = 0, UL = 0, UR = 0;
-    if (y > 0) { U = b[wi - Ww]; if (xw > 0) UL = b[wi - Ww - 1]; if (xw + 1 < Ww) UR = b[wi - Ww + 1]; }
-    const unsigned long long hasW = (m << 1) | (left >> 63), hasNW = (U << 1) | (UL >> 63), hasNE = (U >> 1) | (UR << 63);
-    while (m) {
-        const int j = __ffsll((long long)m) - 1; m &= m - 1;
-        const int x = x0 + j, id = px_id(y, x, Wb);
-        if ((hasW >> j) & 1ULL) uf_unite(L, id, px_id(y, x - 1, Wb));
-        if ((hasNW >> j) & 1ULL) uf_unite(L, id, px_id(y - 1, x - 1, Wb));
-        if ((U >> j) & 1ULL) uf_unite(L, id, px_id(y - 1, x, Wb));
-        if ((hasNE >> j) & 1ULL) uf_unite(L, id, px_id(y - 1, x + 1, Wb));
+    unsigned long long U = 0; bool left = false, nw_px = false, ne_px = false;
+    if (mode == 1) {
+        left = xw > 0 && (b[wi - 1] >> 63);
+        if (y > 0) { U = b[wi - Ww]; nw_px = xw > 0 && (b[wi - Ww - 1] >> 63); ne_px = xw + 1 < Ww && (b[wi - Ww + 1] & 1ULL); }
+    }
+    unsigned long long starts = m & ~(m << 1);
+    while (starts) {
+        const int s = __ffsll((long long)starts) - 1; starts &= starts - 1;
+        const unsigned long long inv = ~(m >> s);                          // (zero only for the full word)
+        const int e = s + (inv ? __ffsll((long long)inv) - 1 : 64) - 1;     // last pixel of the run
+        const int id = px_id(y, x0 + s, Wb);
+        if (mode == 0) { for (int j = s; j <= e; j++) L[px_id(y, x0 + j, Wb)] = id; continue; }
+        if (s == 0 && left) uf_unite(L, id, px_id(y, x0 - 1, Wb));
+        const int lo = s > 0 ? s - 1 : 0, hi = e < 63 ? e + 1 : 63;
+        const unsigned long long up = U & ((2ULL << hi) - 1ULL) & ~((1ULL << lo) - 1ULL);
+        if (s == 0 && nw_px && !(U & 1ULL)) uf_unite(L, id, px_id(y - 1, x0 - 1, Wb));      // (with U's bit 0 set, the stretch that starts there is the same run)
+        unsigned long long g = up & ~(up << 1);
+        while (g) { const int j = __ffsll((long long)g) - 1; g &= g - 1; uf_unite(L, id, px_id(y - 1, x0 + j, Wb)); }
+        if (e == 63 && ne_px && !(U >> 63)) uf_unite(L, id, px_id(y - 1, x0 + 64, Wb));
     }
 }
 int orip_ccl_bits(orip_ctx* c, const unsigned long long* bits, int* par, int K) {

@@ -271,8 +271,8 @@ __global__ __launch_bounds__(256) void k_bits_to_skel_state(const unsigned long 
 // ------------------------------------------------------------------------------------------------
 // Forced stretches (walker.h: ST_CHAIN): maximal chains of degree-2 skeleton pixels, listed when at least ORIP_CHAIN_MIN long.
 //   k_chain_ends_bits: a degree-2 pixel with a skeleton neighbour that is not degree-2 ends a chain (from the bit planes, 64 pixels at a time)
-//   k_chain_build: one thread per end pixel walks its chain (each pixel has exactly one way on); the end with the smaller pixel index
-//                  owns the chain, takes room in cpix with one atomic, walks it again and writes cpix / cref / the state flags
+//   k_chain_build: one thread per end pixel walks its chain (each pixel has exactly one way on), stepping on the degree-2 bit planes; the end with the
+//                  smaller pixel index owns the chain, takes room in cpix with one atomic, walks it again and writes cpix / cref / the state flags
 // Runs on lane 0's side stream underneath the component labelling; the traces wait for it.
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_chain_ends_bits(const unsigned long long* __restrict__ bits, const unsigned long long* __restrict__ d2bits, int H, int W, int Ww,
@@ -297,7 +297,8 @@ __global__ __launch_bounds__(256) void k_chain_ends_bits(const unsigned long lon
         if (k < cap) ends[k] = ((unsigned)blockIdx.z << 26) | ((unsigned)y * (unsigned)W + (unsigned)x);
     }
 }
-__global__ __launch_bounds__(64) void k_chain_build(u8* __restrict__ st, int H, int W, const unsigned* __restrict__ ends, const unsigned* __restrict__ n_ends, unsigned cap_ends,
+__global__ __launch_bounds__(64) void k_chain_build(u8* __restrict__ st, const unsigned long long* __restrict__ d2bits, int H, int W, int Ww, const unsigned* __restrict__ ends,
+                                                     const unsigned* __restrict__ n_ends, unsigned cap_ends,
                                                      unsigned* __restrict__ cpix, unsigned* __restrict__ cref, unsigned* __restrict__ n_cpix, unsigned cap_cpix) {
     const unsigned ne = min(*n_ends, cap_ends);
     const unsigned e = blockIdx.x * 64 + threadIdx.x;
@@ -305,31 +306,43 @@ __global__ __launch_bounds__(64) void k_chain_build(u8* __restrict__ st, int H, 
     const int layer = (int)(ends[e] >> 26); const unsigned p0 = ends[e] & 0x3ffffffu;
     const int64_t plane = (int64_t)H * W;
     u8* s = st + plane * layer; unsigned* cr = cref + plane * layer;
-    // the way on from `cur` (a degree-2 pixel): its degree-2 neighbour that is not `prev`; ~0u: the chain ends here
-    auto next_of = [&](unsigned cur, unsigned prev) -> unsigned {
-        const int y = (int)(cur / (unsigned)W), x = (int)(cur % (unsigned)W);
-        for (int dy = -1; dy <= 1; dy++) for (int dx = -1; dx <= 1; dx++) {
-            if (!dy && !dx) continue;
-            const int yy = y + dy, xx = x + dx;
-            if (yy < 0 || yy >= H || xx < 0 || xx >= W) continue;
-            const unsigned q = (unsigned)yy * (unsigned)W + (unsigned)xx;
-            if (q == prev) continue;
-            const u8 v = s[q];
-            if ((v & ST_FG) && (v & ST_DEG2)) return q;
-        }
-        return ~0u;
+    const unsigned long long* d2 = d2bits + (size_t)H * Ww * layer;
+    // The way on from (y, x), a degree-2 pixel: its degree-2 neighbour that is not the one it came from.  Everything the step tests is in the degree-2 bit
+    // plane (ST_DEG2 implies ST_FG: k_bits_to_skel_state; the plane holds no bit outside the image): the word of each of the three rows around the pixel,
+    // the word next to it only at bit 0 / 63, give the neighbourhood as nine bits in the scan order dy, dx = -1 .. 1 (bit 3 (dy + 1) + dx + 1); `from` is
+    // the bit of the previous pixel (-1: none).  Returns the bit of the first neighbour left in that order, -1: the chain ends here.  No division, and
+    // three independent 8-byte loads from 2 MB per layer where the state plane took up to eight dependent byte loads from 16 MB.
+    auto next_of = [&](int y, int x, int from) -> int {
+        const int xw = x >> 6, j = x & 63;
+        auto row3 = [&](int yy) -> unsigned {
+            if (yy < 0 || yy >= H) return 0u;
+            const unsigned long long* r = d2 + (size_t)yy * Ww;
+            const unsigned long long w = r[xw];
+            unsigned f = j ? (unsigned)(w >> (j - 1)) & 7u : (unsigned)(w << 1) & 6u;
+            if (j == 0 && xw > 0) f |= (unsigned)(r[xw - 1] >> 63);
+            if (j == 63 && xw + 1 < Ww) f |= (unsigned)(r[xw + 1] & 1ULL) << 2;
+            return f;
+        };
+        unsigned nb = (row3(y - 1) | (row3(y) << 3) | (row3(y + 1) << 6)) & ~(1u << 4);
+        if (from >= 0) nb &= ~(1u << from);
+        return nb ? __ffs((int)nb) - 1 : -1;
     };
-    unsigned m = 1, cur = p0, prev = ~0u;
-    for (;;) { const unsigned nx = next_of(cur, prev); if (nx == ~0u || m > (1u << 24)) break; prev = cur; cur = nx; m++; }
-    if (m < ORIP_CHAIN_MIN || !(p0 < cur)) return;                   // short, or the other end owns it
+    const int y0 = (int)(p0 / (unsigned)W), x0 = (int)(p0 % (unsigned)W);
+    unsigned m = 1; int y = y0, x = x0, from = -1;
+    for (;;) { const int k = next_of(y, x, from); if (k < 0 || m > (1u << 24)) break; y += k / 3 - 1; x += k % 3 - 1; from = 8 - k; m++; }      // (8 - k: the way back)
+    const unsigned last = (unsigned)y * (unsigned)W + (unsigned)x;
+    if (m < ORIP_CHAIN_MIN || !(p0 < last)) return;                  // short, or the other end owns it
     const unsigned base = atomicAdd(n_cpix, m + 2u);
     if (base + m + 2u > cap_cpix) return;
     cpix[base] = ORIP_CHAIN_SENTINEL; cpix[base + m + 1u] = ORIP_CHAIN_SENTINEL;
-    cur = p0; prev = ~0u;
+    y = y0; x = x0; from = -1;
     for (unsigned j = 0; j < m; j++) {
+        const unsigned cur = (unsigned)y * (unsigned)W + (unsigned)x;
         cpix[base + 1u + j] = cur; cr[cur] = base + 1u + j;
         s[cur] = (u8)(s[cur] | ST_CHAIN | ((j == 0 || j == m - 1u) ? ST_CHAIN_END : 0));
-        const unsigned nx = next_of(cur, prev); prev = cur; cur = nx;
+        if (j + 1u == m) break;
+        const int k = next_of(y, x, from); if (k < 0) break;         // (never: the first traversal took the same steps from the same plane)
+        y += k / 3 - 1; x += k % 3 - 1; from = 8 - k;
     }
 }
 
@@ -436,6 +449,10 @@ extern "C" int orip_contours_prepare(orip_ctx* c) {
     unsigned long long *bA, *bB;
     HIPC(c, orip_edge_planes(c, nwords, bA, bB));
     dim3 gw((unsigned)cdiv((int64_t)nw, 256), 1, K);
+    // bB's lifetime as the degree-2 planes: k_bits_to_skel_state below -> ev3, while k_chain_ends_bits and k_chain_build step on them on the side stream.
+    // Its only writers are this call's thinning and k_bits_to_skel_state (orip_detect_edges, the other user of orip_edge_planes, sizes the second set and
+    // writes the first only), so the thinning goes behind the chain work of the prepare before -- long finished in a resident chain, whose traces wait for ev3
+    if (R.chains) HIPC(c, hipStreamWaitEvent(LN(c).stream, LN(c).ev3, 0));
     if (c->edge_bits != (const void*)bA) hipLaunchKernelGGL(k_bytes_to_bits04, gw, block, 0, LN(c).stream, c->edges.as<u8>(), bA, H, W, Ww);   // stage 03 may have left them
     c->edge_bits = nullptr;
     // two iterations per round trip to the host, each with its own flag (an iteration after an unchanged one changes nothing either)
@@ -471,7 +488,7 @@ extern "C" int orip_contours_prepare(orip_ctx* c) {
         const unsigned init[2] = {0u, 64u};
         HIPC(c, hipMemcpyAsync(d_cn, init, 8, hipMemcpyHostToDevice, s2));
         hipLaunchKernelGGL(k_chain_ends_bits, dim3((unsigned)cdiv((int64_t)H * Ww, 256), 1, K), block, 0, s2, bA, bB, H, W, Ww, ends, d_cn, cap_ends);
-        hipLaunchKernelGGL(k_chain_build, dim3(cdiv(cap_ends, 64)), dim3(64), 0, s2, c->tmpC.as<u8>(), H, W, ends, d_cn, cap_ends, cpix, c->cref.as<unsigned>(), d_cn + 1, cap_cpix - 64u);
+        hipLaunchKernelGGL(k_chain_build, dim3(cdiv(cap_ends, 64)), dim3(64), 0, s2, c->tmpC.as<u8>(), bB, H, W, Ww, ends, d_cn, cap_ends, cpix, c->cref.as<unsigned>(), d_cn + 1, cap_cpix - 64u);
         HIPC(c, hipEventRecord(LN(c).ev3, s2));
     }
     // ---- components of the thinned bit planes

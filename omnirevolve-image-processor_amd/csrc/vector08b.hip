@@ -179,29 +179,37 @@ __global__ __launch_bounds__(256) void k_zs_tile(const unsigned long long* __res
     }
 }
 // plain (linear id) union-find CCL on the padded raster, driven from the thinned bit plane: a thread owns a 64-pixel word, returns at once when it is empty (the
-// skeleton fills ~1 % of the canvas) and walks its set bits otherwise.  mode 0: init, 1: merge, 2: flatten.
+// skeleton fills ~1 % of the canvas) and works on its runs otherwise, as k_ccl_bits of raster03.hip does (the id grows with x here too): mode 0 init, every pixel of
+// a run points at the run's first pixel; 1 merge, one union per adjacency between runs; 2 flatten.
 __global__ __launch_bounds__(256) void k_ccl2_bits(const unsigned long long* __restrict__ bits, int* __restrict__ L, int H, int W, int Ww, int mode) {
     const size_t wi = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (wi >= (size_t)H * Ww) return;
     unsigned long long m = bits[wi];
     if (!m) return;
     const int y = (int)(wi / Ww), xw = (int)(wi % Ww), x0 = xw * 64;
-    if (mode != 1) {
-        while (m) { const int j = __ffsll((long long)m) - 1; m &= m - 1; const int id = y * W + x0 + j; L[id] = mode == 0 ? id : ufind(L, id); }
+    if (mode == 2) {
+        while (m) { const int j = __ffsll((long long)m) - 1; m &= m - 1; const int id = y * W + x0 + j; L[id] = ufind(L, id); }
         return;
     }
-    const unsigned long long cur = m;
-    const unsigned long long left = xw > 0 ? bits[wi - 1] : 0ULL;
-    unsigned long long U = 0, UL = 0, UR = 0;
-    if (y > 0) { U = bits[wi - Ww]; if (xw > 0) UL = bits[wi - Ww - 1]; if (xw + 1 < Ww) UR = bits[wi - Ww + 1]; }
-    const unsigned long long hasW = (cur << 1) | (left >> 63), hasNW = (U << 1) | (UL >> 63), hasNE = (U >> 1) | (UR << 63);
-    while (m) {
-        const int j = __ffsll((long long)m) - 1; m &= m - 1;
-        const int id = y * W + x0 + j;
-        if ((hasW >> j) & 1ULL) uunite(L, id, id - 1);
-        if ((hasNW >> j) & 1ULL) uunite(L, id, id - W - 1);
-        if ((U >> j) & 1ULL) uunite(L, id, id - W);
-        if ((hasNE >> j) & 1ULL) uunite(L, id, id - W + 1);
+    unsigned long long U = 0; bool left = false, nw_px = false, ne_px = false;
+    if (mode == 1) {
+        left = xw > 0 && (bits[wi - 1] >> 63);
+        if (y > 0) { U = bits[wi - Ww]; nw_px = xw > 0 && (bits[wi - Ww - 1] >> 63); ne_px = xw + 1 < Ww && (bits[wi - Ww + 1] & 1ULL); }
+    }
+    unsigned long long starts = m & ~(m << 1);
+    while (starts) {
+        const int s = __ffsll((long long)starts) - 1; starts &= starts - 1;
+        const unsigned long long inv = ~(m >> s);                          // (zero only for the full word)
+        const int e = s + (inv ? __ffsll((long long)inv) - 1 : 64) - 1;     // last pixel of the run
+        const int id = y * W + x0 + s;
+        if (mode == 0) { for (int j = s; j <= e; j++) L[id + j - s] = id; continue; }
+        if (s == 0 && left) uunite(L, id, id - 1);
+        const int lo = s > 0 ? s - 1 : 0, hi = e < 63 ? e + 1 : 63;
+        const unsigned long long up = U & ((2ULL << hi) - 1ULL) & ~((1ULL << lo) - 1ULL);
+        if (s == 0 && nw_px && !(U & 1ULL)) uunite(L, id, id - W - 1);      // (with U's bit 0 set, the stretch that starts there is the same run)
+        unsigned long long g = up & ~(up << 1);
+        while (g) { const int j = __ffsll((long long)g) - 1; g &= g - 1; uunite(L, id, (y - 1) * W + x0 + j); }
+        if (e == 63 && ne_px && !(U >> 63)) uunite(L, id, (y - 1) * W + x0 + 64);
     }
 }
 // ordered compaction of the skeleton pixels (count / write) from the thinned BIT plane (a word per thread, [Hp][Wwp] words; pixel index on the

@@ -13,6 +13,14 @@ class OripError(RuntimeError):
     pass
 
 
+class _Resident:
+    def __repr__(self):
+        return "RESIDENT"
+
+
+RESIDENT = _Resident()      # kmeans_fit / kmeans_fit_rgb: fit from the sample set kmeans_samples left in the context
+
+
 def _p(a: np.ndarray):
     return a.ctypes.data_as(C.c_void_p)
 
@@ -127,24 +135,55 @@ class Device:
         self._ck(self.L.orip_lab_of(self.h, _p(idx), len(idx), _p(out)))
         return out
 
-    def kmeans_fit(self, sample_idx: np.ndarray | None, K: int, attempts=3, max_iter=40, eps=0.5) -> Tuple[np.ndarray, float]:
+    def _kmeans(self, fit, sample_idx, K: int, attempts, max_iter, eps) -> Tuple[np.ndarray, float]:
+        """sample_idx: None = every pixel, RESIDENT = the set of kmeans_samples, else the indices (uploaded by this call)"""
         centers = np.zeros((K, 3), np.float32)
         comp = C.c_double(0)
         if sample_idx is None:
-            self._ck(self.L.orip_kmeans_fit(self.h, None, 0, K, attempts, max_iter, eps, _p(centers), C.byref(comp)))
+            self._ck(fit(self.h, None, 0, K, attempts, max_iter, eps, _p(centers), C.byref(comp)))
+        elif sample_idx is RESIDENT:
+            self._ck(fit(self.h, None, -1, K, attempts, max_iter, eps, _p(centers), C.byref(comp)))
         else:
             idx = np.ascontiguousarray(sample_idx, np.int64)
-            self._ck(self.L.orip_kmeans_fit(self.h, _p(idx), len(idx), K, attempts, max_iter, eps, _p(centers), C.byref(comp)))
+            self._ck(fit(self.h, _p(idx), len(idx), K, attempts, max_iter, eps, _p(centers), C.byref(comp)))
         return centers, comp.value
 
+    def kmeans_fit(self, sample_idx, K: int, attempts=3, max_iter=40, eps=0.5) -> Tuple[np.ndarray, float]:
+        return self._kmeans(self.L.orip_kmeans_fit, sample_idx, K, attempts, max_iter, eps)
+
+    def kmeans_samples(self, sample_idx: np.ndarray | None):
+        """leave the sample set resident for fits with RESIDENT (None: drop it); it lives until an image of another pixel count is set"""
+        self._km_key = None              # whatever kmeans_fit_subsampled left is gone
+        if sample_idx is None:
+            self._ck(self.L.orip_kmeans_samples(self.h, None, 0))
+            return
+        idx = np.ascontiguousarray(sample_idx, np.int64)
+        self._ck(self.L.orip_kmeans_samples(self.h, _p(idx), len(idx)))
+
+    def kmeans_samples_info(self) -> Tuple[int, int]:
+        """(indices, pixel count of the image they were made for) of the resident sample set; (0, 0): none"""
+        n, npx = C.c_int64(0), C.c_int64(0)
+        self._ck(self.L.orip_kmeans_samples_info(self.h, C.byref(n), C.byref(npx)))
+        return n.value, npx.value
+
+    def kmeans_fit_subsampled(self, limit: int, K: int, attempts=3, max_iter=40, eps=0.5, rgb: bool = False) -> Tuple[np.ndarray, float]:
+        """The fit of stage 02 on its fixed-seed subsample (orip.stages.subsample_indices: a function of the pixel count and `limit` alone).  The set is built
+        and uploaded only when the context does not hold the one of (H * W, limit) already -- decided from what the library reports and from which
+        (pixel count, limit) this object uploaded last, never from array contents."""
+        from . import stages as S
+        fit = self.kmeans_fit_rgb if rgb else self.kmeans_fit
+        npx, limit = self.H * self.W, int(limit)
+        if npx <= limit:
+            return fit(None, K, attempts, max_iter, eps)
+        if getattr(self, "_km_key", None) != (npx, limit) or self.kmeans_samples_info() != (limit, npx):
+            self.kmeans_samples(S.subsample_indices(npx, limit))
+            self._km_key = (npx, limit)
+        return fit(RESIDENT, K, attempts, max_iter, eps)
+
     # ---- process_colors.py
-    def kmeans_fit_rgb(self, sample_idx: np.ndarray | None, K: int, attempts=3, max_iter=30, eps=1.0) -> Tuple[np.ndarray, float]:
+    def kmeans_fit_rgb(self, sample_idx, K: int, attempts=3, max_iter=30, eps=1.0) -> Tuple[np.ndarray, float]:
         """kmeans_palette's cv2.kmeans (process_colors.py:41-45) over the R, G, B bytes of the sampled pixels; float centres in R, G, B order"""
-        centers = np.zeros((K, 3), np.float32)
-        comp = C.c_double(0)
-        idx = None if sample_idx is None else np.ascontiguousarray(sample_idx, np.int64)
-        self._ck(self.L.orip_kmeans_fit_rgb(self.h, _p(idx) if idx is not None else None, 0 if idx is None else len(idx), K, attempts, max_iter, eps, _p(centers), C.byref(comp)))
-        return centers, comp.value
+        return self._kmeans(self.L.orip_kmeans_fit_rgb, sample_idx, K, attempts, max_iter, eps)
 
     def assign_palette(self, palette_rgb: np.ndarray, fetch: bool = True):
         """assign_labels (process_colors.py:69-77): (labels u8 [H,W] or None, pixels per label)"""

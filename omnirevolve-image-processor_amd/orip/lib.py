@@ -51,6 +51,7 @@ SIGNATURES = {
     "orip_resize_area": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32]),
     "orip_set_image": (_i32, [_vp, _vp, _i32, _i32]), "orip_lab_of": (_i32, [_vp, _vp, _i64, _vp]),
     "orip_kmeans_fit": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _f64, _vp, _P(_f64)]),
+    "orip_kmeans_samples": (_i32, [_vp, _vp, _i64]), "orip_kmeans_samples_info": (_i32, [_vp, _P(_i64), _P(_i64)]),
     "orip_kmeans_fit_rgb": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _f64, _vp, _P(_f64)]), "orip_assign_palette": (_i32, [_vp, _vp, _i32, _vp, _vp]),
     "orip_colors_table": (_i32, [_vp, _i32, _i32, _i64, _P(_i64), _P(_i64), _P(_i32)]), "orip_colors_fetch": (_i32, [_vp, _vp, _vp, _P(_i64)]),
     "orip_colors_hue": (_i32, [_vp, _vp]), "orip_colors_kmeans": (_i32, [_vp, _i32, _i32, _i32, C.c_uint64, _vp, _vp, _vp, _vp]),

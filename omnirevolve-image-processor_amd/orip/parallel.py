@@ -199,7 +199,7 @@ def run_path_sharded(dev, cfg, H: int, W: int, rank: int, world: int, coll_devic
     K = max(2, len(names))
     lnames = S.cluster_names(cfg)[:K]
     dev.contours_reserve(K if world == 1 else len(owned_layers(K, rank, world)))      # memo planes cleared under the k-means fit
-    centers, _ = dev.kmeans_fit(S.subsample_indices(H * W), K)
+    centers, _ = dev.kmeans_fit_subsampled(S.SUBSAMPLE_LIMIT, K)       # the sample set stays in the context from step to step
     dev.extract_layers(centers, want_counts=False)
     order = sorted(range(K), key=lambda l: (S.darkness_rank10(lnames[l]), names.index(lnames[l])))
     R = S.r_insert12(cfg)

@@ -200,7 +200,9 @@ static_assert(sizeof(LaneFlags) <= 4096, "LaneRes::flags is 4096 bytes, allocate
 //   vfeatures                                VT_LEAVES, tmpF (only when the list has more than ORIP_LONG_POLY points: the long polylines' leaves and length order)
 //   vreorder                                 VTL_FEAT, flags.nn_seed / nn_dbg2; all of vfeatures and vgather_list; with prefetch08: all of orip_prefetch08
 //   split_small (vector08a.hip)              VTL_SPLIT, VTL_SPLIT_FEAT; all of vfeatures, vscan_excl and vgather_list; waits for ev4 or drains the prefetch
-//   orip_runs_to_polys                       VTL_RUN_STARTS, VTL_TAIL_RUNS; all of vscan_excl and vgather
+//   orip_runs_to_polys                       VTL_RUN_STARTS (one word pair per tile of ORIP_RUN_TILE slots), VTL_TAIL_RUNS (20 bytes per run; at most one run
+//                                            per slot, and stage 10 comes close: every second one); all of vscan_excl; dst.  READS the caller's flags and
+//                                            point source (08-A: sflag, sx, sy of VTL_SAMPLES; 10: VTL_CUM) until its last kernel
 //   orip_prefetch08 (side stream)            pf08.*, VT_LEAVES, tmpF (until ev4); READS the caller's features (stage 07's VTL_FEAT) until ev3
 // and every stage holds live, across such calls:
 //   04  (raster04.hip)    on the layer's lane: VTL_STEPLOG trace_launch -> trace_finish (between entry points, see above); inside trace_finish VTL_CAPS (walk sums per
@@ -209,7 +211,7 @@ static_assert(sizeof(LaneFlags) <= 4096, "LaneRes::flags is 4096 bytes, allocate
 //   07  (vector.hip)      nothing of its own: vreorder's VTL_FEAT is the feat07 the prefetch reads on the side stream until ev3.  Stage 08's A0 fills the same
 //                         slot behind ev4 only; the two meet in practice behind several host round trips of split_small, but no event orders them
 //   08-A (vector08a.hip)  VTL_FEAT A0 -> k_rank_counts (across split_small, vsort_pairs, vscan_excl); VTL_RANKS A1 -> A6; VTL_CUM A2 (k_samples reads it last);
-//                         VTL_SAMPLES, VTL_CELLS, canvas, pixbits A2 -> A6, VTL_SAMPLES on through orip_runs_to_polys (its spt and sflag are the input);
+//                         VTL_SAMPLES, VTL_CELLS, canvas, pixbits A2 -> A6, VTL_SAMPLES on through orip_runs_to_polys (its sx, sy and sflag are the input);
 //                         VTL_RANKS also holds the redo flags of A3 (nk + 1 words behind RsInfo), which the side stream reads until ev3 (awaited by A5);
 //                         VTL_TAIL_RUNS A2 -> A6: the block-local tail sums (8 MS bytes; k_samples -> k_tail_par), then the last-in scan and then the
 //                         survivors in its first 4 MS bytes, and orip_runs_to_polys takes the slot once A6 is enqueued;
@@ -233,8 +235,8 @@ enum { VTL_RANKS = 0,           // 08-A: perimeter sort, order, samples per rank
        VTL_CAPS = 4,            // 08-A: capsule table | 08-B: component tables | 04 trace_finish: walk sums per slot
        VTL_CELLS = 5,           // 08-A: cell keys / values (bucket sort), sample hints | 08-B: per-component path scratch | 04 trace_finish: kept walk slots
        VTL_FEAT = 6,            // features: 08-A kept polylines | 08-B lines, parents, groups | vreorder (07, 08 C, 10, 12): features, ends, order | 12: features, alive flags
-       VTL_RUN_STARTS = 7,      // orip_runs_to_polys: run starts and their scan
-       VTL_TAIL_RUNS = 8,       // 08-A: block-local tail sums -> last-in scan -> survivors, THEN orip_runs_to_polys: run lengths, begins, keep flags, descriptors
+       VTL_RUN_STARTS = 7,      // orip_runs_to_polys: accepted slots and run starts per tile, scanned in place
+       VTL_TAIL_RUNS = 8,       // 08-A: block-local tail sums -> last-in scan -> survivors, THEN orip_runs_to_polys: per run its first slot, rank and keep / length key, per kept run its first slot
        VTL_STEPLOG = 9,         // 04: step log of the layer's trace (between entry points, see above) | 08-B: skeleton bytes, thinning bit planes | 10: seed, distance, occupancy planes
        VTL_SPLIT_FEAT = 10,     // split_small: features of its source list | 08-B: union-find labels of the padded raster | 10: features of the cut lines
        VT_LEAVES = 11,          // wherever vfeatures runs: its perimeter leaves and length order, and those of the stage-08 prefetch (between entry points, see above) | 04 with ORIP_WALK_DBG: per-component debug counters of the trace

@@ -107,9 +107,17 @@ int vgather_views(orip_ctx* c, const GatherDesc* d, int64_t n, const DPolys& src
 // selection out of a list of either kind
 int vgather_list(orip_ctx* c, const GatherDesc* d, int64_t n, const DPolys& src, DPolys& dst, int64_t known_total = -1);
 
-// Runs of accepted slots -> polylines: per-slot flags (bit0 accepted, bit1 sequence start) and points -> dst, one polyline per run of >= 2 accepted slots.
-// Shared by stage 08-A (slots = samples) and stage 10 (slots = cut steps).
-int orip_runs_to_polys(orip_ctx* c, const int2* spt, const uint8_t* sflag, unsigned n_slots, DPolys& dst);
+// Runs of accepted slots -> polylines: per-slot flags (bit0 accepted, bit1 sequence start) -> dst, one polyline per run of >= 2 accepted slots, in slot
+// order.  A run starts at an accepted slot s when bit 1 is set, s == 0, or slot s - 1 is not accepted.  The flags are read twice, ORIP_RUN_TILE slots per
+// block (16 per lane and load); everything behind that is per run, and only the points of the kept runs are fetched from the caller's point source.
+// Shared by stage 08-A (slots = samples) and stage 10 (slots = cut steps); instantiated in vector_common.hip for the two sources below.
+#define ORIP_RUN_TILE 4096u
+struct SlotPtsI2 { const int2* p; __device__ __forceinline__ int2 at(unsigned s) const { return p[s]; } };        // stage 10: the cut steps' points, stored densely
+struct SlotPtsF64 {                                                                                                // stage 08-A: the samples' float64 positions, truncated toward zero
+    const double* x; const double* y;
+    __device__ __forceinline__ int2 at(unsigned s) const { return make_int2((int)x[s], (int)y[s]); }
+};
+template <class Pts> int orip_runs_to_polys(orip_ctx* c, Pts pts, const uint8_t* sflag, unsigned n_slots, DPolys& dst);
 
 // Greedy reorder of a whole DPolys list into dst.  kind: 7 -> 07 rules (arcLength closed seed), 8 -> 08 (_poly_perimeter seed), 10 -> 10 (arcLength open seed)
 // prefetch08 (optional, stage 07 only): stage 08's parameters; orip_prefetch08 is then called right after the greedy kernel has been enqueued, with the

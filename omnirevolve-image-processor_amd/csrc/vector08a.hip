@@ -314,8 +314,8 @@ __global__ __launch_bounds__(256) void k_rank_counts(const RsInfo* __restrict__ 
     }
     if (r == n) mr[r] = 0;
 }
-// One record per sample.  sx, sy: the float64 position; dprev: distance to the predecessor on the same polyline; spt: the position truncated to integers (what a
-// surviving sample contributes to the cleaned line); rank: the polyline, in processing order.
+// One record per sample.  sx, sy: the float64 position; dprev: distance to the predecessor on the same polyline; rank: the polyline, in processing order.  (What a surviving
+// sample contributes to the cleaned line is its position truncated to integers: orip_runs_to_polys takes it from sx, sy, for the survivors only.)
 // pxy: the rounded pixel and one flag.  Inside the canvas (W, H <= 16383) x sits in bits 0-13, y in bits 16-29, and ORIP_PXY_FIRST (bit 15) is set on the first
 // sample of its polyline; bits 14, 30 and 31 are zero.  Off the canvas the word is ORIP_PXY_OUT (all ones) and carries neither a pixel nor the flag: every
 // consumer tests the sentinel first, then takes the coordinates with pxy_x / pxy_y.
@@ -325,7 +325,7 @@ __global__ __launch_bounds__(256) void k_rank_counts(const RsInfo* __restrict__ 
 #define ORIP_SMP_BLOCK 1024u
 __device__ __forceinline__ int pxy_x(unsigned p) { return (int)(p & 0x3fffu); }
 __device__ __forceinline__ int pxy_y(unsigned p) { return (int)((p >> 16) & 0x3fffu); }
-struct SampleArrs { double* sx; double* sy; double* dprev; int2* spt; unsigned* pxy; unsigned* rank; double* Sloc; };
+struct SampleArrs { double* sx; double* sy; double* dprev; unsigned* pxy; unsigned* rank; double* Sloc; };
 // rank (polyline) and segment of sample g, as k_samples needs them.  Both are monotone in g, so the values of the first sample of a
 // 256-sample block and of the next block bound the searches of every sample in between: k_sample_hints does the two full binary
 // searches once per block, k_samples only searches between the hints (mostly zero to a few steps instead of ~28 dependent loads).
@@ -382,7 +382,7 @@ __global__ __launch_bounds__(256) void k_samples(Src src, const int64_t* __restr
     // lie a few segments apart (8 px of arc length against segments of 2 .. 3 px), so the second to fourth find their segment with ONE round of eight
     // independent loads from where the previous one stood.
     // The threads leave position and polyline of their samples in LDS; after the barrier thread t takes the block's samples t, t + 256, t + 512, t + 768, derives
-    // the rest of the record (distance to the predecessor, truncated point, pixel) from the staged positions and stores it: every store instruction of a wave
+    // the rest of the record (distance to the predecessor, pixel) from the staged positions and stores it: every store instruction of a wave
     // writes 64 consecutive elements (stored straight from the producers it wrote 64 elements at a stride of four).
     // Last, the block scans its 1024 distances by polyline (Sloc, see SampleArrs): k_tail_par forms its tail sums from them, no pass over the samples in between.
     constexpr int S = 4;
@@ -477,7 +477,6 @@ __global__ __launch_bounds__(256) void k_samples(Src src, const int64_t* __restr
         if (!(rw >> 31)) { const unsigned before = smp_slot8(ls ? ls - 1u : 0u); d = vs::norm2_f64(x - (ls ? shx[before] : shp[0]), y - (ls ? shy[before] : shp[1])); }
         A.dprev[g] = d; dd[u] = d;
         A.sx[g] = x; A.sy[g] = y; A.rank[g] = rw & 0x7fffffffu;
-        A.spt[g] = make_int2((int)x, (int)y);
         const long long xi = vs::round_half_even(x), yi = vs::round_half_even(y);
         const bool in = xi >= 0 && yi >= 0 && xi < W && yi < H;
         A.pxy[g] = in ? ((unsigned)xi | ((unsigned)yi << 16) | ((rw >> 31) ? ORIP_PXY_FIRST : 0u)) : ORIP_PXY_OUT;
@@ -1127,7 +1126,7 @@ static int a2_resample(orip_ctx* c, const orip_params08& P, DPolys& kept0, A08& 
     if (MS == 0) return 0;
     if (MS > 0x7ffffff0u) ORIP_FAIL(c, "too many samples");
     if (T.on) { char b[48]; snprintf(b, sizeof b, " [MS %u]", MS); T.log += b; }
-    { Carve L; L.each(MS, a.A.sx, a.A.sy, a.A.dprev, a.A.spt, a.A.pxy, a.A.rank, a.npop, a.capprev, a.sflag); HIPC(c, L.commit(LN(c).vtmp[VTL_SAMPLES], 1024)); }
+    { Carve L; L.each(MS, a.A.sx, a.A.sy, a.A.dprev, a.A.pxy, a.A.rank, a.npop, a.capprev, a.sflag); HIPC(c, L.commit(LN(c).vtmp[VTL_SAMPLES], 1024)); }
     { Carve L; L.take(a.A.Sloc, MS); HIPC(c, L.commit(LN(c).vtmp[VTL_TAIL_RUNS], 64)); }      // block-local tail sums: k_samples -> k_tail_par
     const unsigned nb = (unsigned)cdiv(MS, 256);
     { Carve L; L.each(MS, a.ckin, a.ckout, a.cvin, a.cvout); L.take(a.hints, nb + 1, 64);
@@ -1256,7 +1255,7 @@ int dedup08_a(orip_ctx* c, int layer, const orip_params08& P, DPolys& S, DTaps& 
             ORIP_TRY(a3_tails(c, layer, P, a));            T.tick("tail");
             ORIP_TRY(a4_capsules(c, P, a));                caps_counted = true; T.tick("caps");
             ORIP_TRY(a56_accept(c, P, a, T));              T.tick("accept");
-            ORIP_TRY(orip_runs_to_polys(c, a.A.spt, a.sflag, a.MS, cleaned));
+            ORIP_TRY(orip_runs_to_polys(c, SlotPtsF64{a.A.sx, a.A.sy}, a.sflag, a.MS, cleaned));
             T.tick("runs");
         }
         // ---- A7: the same split on the cleaned lines

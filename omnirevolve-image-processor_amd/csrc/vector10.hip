@@ -394,7 +394,7 @@ static int dedup_cross_layer_impl(orip_ctx* c, int src_layer, int layer, bool re
             if (n_slots) {
                 int2* spt; uint8_t* sflag; { Carve L; L.each(n_slots, spt, sflag); HIPC(c, L.commit(LN(c).vtmp[VTL_CUM], 64)); }
                 { ProfScope ps(c, "k_cut_slots"); hipLaunchKernelGGL(k_cut_slots, dim3(cdiv(n_slots, 256)), dim3(256), 0, LN(c).stream, Lin.pts.as<int32_t>(), cnt, base, Lin.total, fop, n_slots, forb, H, W, spt, sflag); }
-                ORIP_TRY(orip_runs_to_polys(c, spt, sflag, n_slots, cut));
+                ORIP_TRY(orip_runs_to_polys(c, SlotPtsI2{spt}, sflag, n_slots, cut));
             }
         }
         const double ms_cut = T.lap();

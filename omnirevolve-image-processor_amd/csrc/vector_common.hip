@@ -149,59 +149,121 @@ int vgather_list(orip_ctx* c, const GatherDesc* d, int64_t n, const DPolys& src,
     return vgather(c, d, n, src.pts.as<int32_t>(), dst, known_total);
 }
 // ---- runs of accepted slots -> polylines (stage 08-A: samples; stage 10: cut steps)
-__global__ __launch_bounds__(256) void k_run_starts(const uint8_t* __restrict__ sflag, unsigned n, unsigned* __restrict__ start) {
-    unsigned s = blockIdx.x * 256 + threadIdx.x;
-    if (s >= n) return;
-    uint8_t f = sflag[s];
-    start[s] = ((f & 1) && ((f & 2) || s == 0 || !(sflag[s - 1] & 1))) ? 1u : 0u;
+// A run is a stretch of consecutive accepted slots, so its first slot and the number of accepted slots in front of it say everything: its length is the
+// distance to the next run's count.  Nothing is written per slot; both passes over the flags write per tile or per run.
+namespace {
+// bit `bit` of each of the four flag bytes of w, as bits 0 .. 3
+__device__ __forceinline__ unsigned flag_bits4(unsigned w, int bit) { return ((((w >> bit) & 0x01010101u) * 0x01020408u) >> 24) & 0xfu; }
+// The 16 slots of one lane, from s0 on: acc = accepted (bit i: slot s0 + i), st = accepted and first of a run.  One 16-byte load where the flags allow it
+// (wide: sflag is 16-byte aligned, which Carve gives both callers; s0 is a multiple of 16), byte loads for the last, partial group or an unaligned array.
+// Every lane of the wave must call it (the slot in front of s0 comes from the lane before).
+__device__ __forceinline__ void run_lane_flags(const uint8_t* __restrict__ sflag, unsigned n, unsigned s0, bool wide, unsigned& acc, unsigned& st) {
+    unsigned seq = 0; acc = 0;
+    if (wide && s0 < n && n - s0 >= 16u) {
+        const uint4 q = *reinterpret_cast<const uint4*>(sflag + s0);
+        acc = flag_bits4(q.x, 0) | flag_bits4(q.y, 0) << 4 | flag_bits4(q.z, 0) << 8 | flag_bits4(q.w, 0) << 12;
+        seq = flag_bits4(q.x, 1) | flag_bits4(q.y, 1) << 4 | flag_bits4(q.z, 1) << 8 | flag_bits4(q.w, 1) << 12;
+    } else {
+        for (unsigned i = 0; i < 16u && s0 < n && i < n - s0; i++) { const unsigned f = sflag[s0 + i]; acc |= (f & 1u) << i; seq |= ((f >> 1) & 1u) << i; }
+    }
+    unsigned before = __shfl_up(acc >> 15, 1, 64);          // slot s0 - 1: the last slot of the lane before, or (first lane of the wave) one byte
+    if ((threadIdx.x & 63u) == 0) before = (s0 > 0 && s0 <= n) ? (sflag[s0 - 1] & 1u) : 0u;
+    st = acc & (seq | ~((acc << 1) | before)) & 0xffffu;
 }
-__global__ __launch_bounds__(256) void k_run_accum(const uint8_t* __restrict__ sflag, const unsigned* __restrict__ start, const unsigned* __restrict__ start_scan,
-                                                    unsigned n, unsigned* __restrict__ rlen, unsigned* __restrict__ rbegin) {
-    unsigned s = blockIdx.x * 256 + threadIdx.x;
-    if (s >= n) return;
-    if (!(sflag[s] & 1)) return;
-    unsigned rid = start_scan[s] + start[s] - 1;      // inclusive scan - 1
-    atomicAdd(&rlen[rid], 1u);
-    if (start[s]) rbegin[rid] = s;
+// One block per tile of ORIP_RUN_TILE slots.  Counting pass (LIST = false): tiles[b] = runs that start in the tile << 32 | accepted slots of the tile, and a
+// zero behind the last tile; their exclusive scan, in place, is the listing pass's input (LIST = true): rbegin[r] = first slot of run r, rpos[r] = accepted
+// slots in front of it, rpos[n_runs] = n_acc.
+template <bool LIST>
+__global__ __launch_bounds__(256) void k_run_tiles(const uint8_t* __restrict__ sflag, unsigned n, unsigned nb, int64_t* __restrict__ tiles,
+                                                    unsigned n_acc, unsigned n_runs, unsigned* __restrict__ rbegin, unsigned* __restrict__ rpos) {
+    static_assert(ORIP_RUN_TILE == 256u * 16u, "a lane takes 16 slots of its block's tile");
+    __shared__ unsigned wsum[4];
+    const unsigned tid = threadIdx.x, s0 = blockIdx.x * ORIP_RUN_TILE + tid * 16u;
+    unsigned acc, st;
+    run_lane_flags(sflag, n, s0, (reinterpret_cast<uintptr_t>(sflag) & 15u) == 0, acc, st);
+    const unsigned mine = (unsigned)__popc(acc) | (unsigned)__popc(st) << 16;      // both sums of a tile are <= 4096: 16 bits each
+    unsigned inc = mine;
+    for (int o = 1; o < 64; o <<= 1) { const unsigned t = __shfl_up(inc, o, 64); if ((int)(tid & 63u) >= o) inc += t; }
+    if ((tid & 63u) == 63u) wsum[tid >> 6] = inc;
+    __syncthreads();
+    if (!LIST) {
+        if (tid == 0) { const unsigned t = wsum[0] + wsum[1] + wsum[2] + wsum[3]; tiles[blockIdx.x] = (int64_t)(t >> 16) << 32 | (int64_t)(t & 0xffffu); if (blockIdx.x == 0) tiles[nb] = 0; }
+        return;
+    }
+    unsigned ex = inc - mine;
+    for (unsigned w = 0; w < (tid >> 6); w++) ex += wsum[w];
+    const int64_t base = tiles[blockIdx.x];
+    const unsigned pos0 = (unsigned)(base & 0xffffffffll) + (ex & 0xffffu), run0 = (unsigned)(base >> 32) + (ex >> 16);
+    for (unsigned m = st; m; m &= m - 1u) {
+        const unsigned i = (unsigned)__ffs((int)m) - 1u, below = (1u << i) - 1u;
+        const unsigned r = run0 + (unsigned)__popc(st & below);
+        if (r < n_runs) { rbegin[r] = s0 + i; rpos[r] = pos0 + (unsigned)__popc(acc & below); }
+    }
+    if (blockIdx.x == 0 && tid == 0) rpos[n_runs] = n_acc;
 }
-__global__ __launch_bounds__(256) void k_run_keep(const unsigned* __restrict__ rlen, unsigned n_runs, unsigned min_len, unsigned* __restrict__ keep) {
-    unsigned r = blockIdx.x * 256 + threadIdx.x;
-    if (r < n_runs) keep[r] = rlen[r] >= min_len ? 1u : 0u;
-    if (r == n_runs) keep[r] = 0;
+// key[r] = 1 << 32 | length for a run of at least min_len slots, else 0, and 0 behind the last run: the exclusive scan, in place, gives a kept run its
+// index among the kept runs (high word) and the offset of its points (low word), and behind the last run both totals
+__global__ __launch_bounds__(256) void k_run_keys(const unsigned* __restrict__ rpos, unsigned n_runs, unsigned min_len, int64_t* __restrict__ key) {
+    const unsigned r = blockIdx.x * 256 + threadIdx.x;
+    if (r > n_runs) return;
+    const unsigned len = r < n_runs ? rpos[r + 1] - rpos[r] : 0u;
+    key[r] = len >= min_len ? ((int64_t)1 << 32 | (int64_t)len) : 0;
 }
-__global__ __launch_bounds__(256) void k_run_desc(const unsigned* __restrict__ rlen, const unsigned* __restrict__ rbegin, const unsigned* __restrict__ keep,
-                                                   const unsigned* __restrict__ keep_scan, unsigned n_runs, GatherDesc* __restrict__ d) {
-    unsigned r = blockIdx.x * 256 + threadIdx.x;
-    if (r >= n_runs || !keep[r]) return;
-    GatherDesc g; g.begin = rbegin[r]; g.len = rlen[r]; g.rev = 0; g.src = 0;
-    d[keep_scan[r]] = g;
+__global__ __launch_bounds__(256) void k_run_offsets(const unsigned* __restrict__ rbegin, const unsigned* __restrict__ rpos, const int64_t* __restrict__ key, unsigned n_runs, unsigned min_len,
+                                                      unsigned n_keep, int64_t* __restrict__ off, unsigned* __restrict__ kbegin) {
+    const unsigned r = blockIdx.x * 256 + threadIdx.x;
+    if (r > n_runs) return;
+    const int64_t v = key[r]; const unsigned k = (unsigned)(v >> 32);
+    if (r == n_runs) { if (k == n_keep) off[k] = v & 0xffffffffll; return; }
+    if (rpos[r + 1] - rpos[r] < min_len || k >= n_keep) return;
+    off[k] = v & 0xffffffffll; kbegin[k] = rbegin[r];
 }
+// 4096 consecutive output points per block (as k_gather_pts): point j of kept run k is slot kbegin[k] + j of the caller's source
+template <class Pts>
+__global__ __launch_bounds__(256) void k_run_gather(Pts pts, const unsigned* __restrict__ kbegin, int64_t n, const int64_t* __restrict__ off, int2* __restrict__ dst, int64_t total) {
+    const int64_t start = (int64_t)blockIdx.x * 4096;
+    if (start >= total) return;
+    int64_t k = last_le(off, n, start);
+    for (int64_t idx = start + threadIdx.x; idx < min(total, start + 4096); idx += 256) {
+        while (off[k + 1] <= idx) k++;           // (kept runs have at least two points: none is empty)
+        dst[idx] = pts.at(kbegin[k] + (unsigned)(idx - off[k]));
+    }
+}
+}  // namespace
 
-// Shared by stage 08-A and stage 10 (vec_common.h): turn per-slot flags (bit0 accepted, bit1 sequence start) + points into a DPolys of runs with >= 2 points
-int orip_runs_to_polys(orip_ctx* c, const int2* spt, const uint8_t* sflag, unsigned n_slots, DPolys& dst) {
+// Shared by stage 08-A and stage 10 (vec_common.h).  Two host reads: (accepted slots, runs) and (kept runs, their points).
+template <class Pts>
+int orip_runs_to_polys(orip_ctx* c, Pts pts, const uint8_t* sflag, unsigned n_slots, DPolys& dst) {
     HIPC(c, dst.clear(LN(c).stream));
     if (n_slots == 0) return 0;
-    unsigned *start, *start_scan; { Carve L; L.each(n_slots, start, start_scan); HIPC(c, L.commit(LN(c).vtmp[VTL_RUN_STARTS], 64)); }
-    hipLaunchKernelGGL(k_run_starts, dim3(cdiv(n_slots, 256)), dim3(256), 0, LN(c).stream, sflag, n_slots, start);
-    ORIP_TRY(vscan_excl<unsigned>(c, start, start_scan, n_slots));
-    unsigned a[2];
-    HIPC(c, hipMemcpyAsync(&a[0], start_scan + (n_slots - 1), 4, hipMemcpyDeviceToHost, LN(c).stream));      // both words, one wait
-    ORIP_TRY(vread(c, &a[1], start + (n_slots - 1)));
-    unsigned n_runs = a[0] + a[1];
+    const hipStream_t st = LN(c).stream;
+    const unsigned nb = (unsigned)cdiv(n_slots, ORIP_RUN_TILE);
+    int64_t* tiles; { Carve L; L.take(tiles, (size_t)nb + 1); HIPC(c, L.commit(LN(c).vtmp[VTL_RUN_STARTS], 64)); }
+    hipLaunchKernelGGL(k_run_tiles<false>, dim3(nb), dim3(256), 0, st, sflag, n_slots, nb, tiles, 0u, 0u, (unsigned*)nullptr, (unsigned*)nullptr);
+    ORIP_TRY(vscan_excl<int64_t>(c, tiles, tiles, (size_t)nb + 1));
+    int64_t sums = 0;
+    ORIP_TRY(vread(c, &sums, tiles + nb));
+    const unsigned n_acc = (unsigned)(sums & 0xffffffffll), n_runs = (unsigned)(sums >> 32);
     if (n_runs == 0) return 0;
-    unsigned *rlen, *rbegin, *keep, *keep_scan; GatherDesc* desc;
-    { Carve L; L.each((size_t)n_runs + 1, rlen, rbegin, keep, keep_scan); L.take(desc, n_runs); HIPC(c, L.commit(LN(c).vtmp[VTL_TAIL_RUNS], 256)); }
-    HIPC(c, hipMemsetAsync(rlen, 0, (size_t)(n_runs + 1) * 4, LN(c).stream));
-    hipLaunchKernelGGL(k_run_accum, dim3(cdiv(n_slots, 256)), dim3(256), 0, LN(c).stream, sflag, start, start_scan, n_slots, rlen, rbegin);
-    hipLaunchKernelGGL(k_run_keep, dim3(cdiv(n_runs + 1, 256)), dim3(256), 0, LN(c).stream, rlen, n_runs, 2u, keep);
-    ORIP_TRY(vscan_excl<unsigned>(c, keep, keep_scan, (size_t)n_runs + 1));
-    unsigned n_keep = 0;
-    ORIP_TRY(vread(c, &n_keep, keep_scan + n_runs));
+    unsigned *rbegin, *rpos, *kbegin; int64_t* key;
+    { Carve L; L.take(key, (size_t)n_runs + 1); L.take(rpos, (size_t)n_runs + 1); L.each(n_runs, rbegin, kbegin); HIPC(c, L.commit(LN(c).vtmp[VTL_TAIL_RUNS], 64)); }
+    hipLaunchKernelGGL(k_run_tiles<true>, dim3(nb), dim3(256), 0, st, sflag, n_slots, nb, tiles, n_acc, n_runs, rbegin, rpos);
+    hipLaunchKernelGGL(k_run_keys, dim3(cdiv((int64_t)n_runs + 1, 256)), dim3(256), 0, st, rpos, n_runs, 2u, key);
+    ORIP_TRY(vscan_excl<int64_t>(c, key, key, (size_t)n_runs + 1));
+    int64_t kept = 0;
+    ORIP_TRY(vread(c, &kept, key + n_runs));
+    const unsigned n_keep = (unsigned)(kept >> 32); const int64_t total = kept & 0xffffffffll;
     if (n_keep == 0) return 0;
-    hipLaunchKernelGGL(k_run_desc, dim3(cdiv(n_runs, 256)), dim3(256), 0, LN(c).stream, rlen, rbegin, keep, keep_scan, n_runs, desc);
+    HIPC(c, dst.off.ensure((size_t)(n_keep + 1) * 8 + 64));
+    HIPC(c, dst.pts.ensure((size_t)total * 8 + 64));
+    dst.n = n_keep; dst.total = total; dst.set_explicit();
+    hipLaunchKernelGGL(k_run_offsets, dim3(cdiv((int64_t)n_runs + 1, 256)), dim3(256), 0, st, rbegin, rpos, key, n_runs, 2u, n_keep, dst.off.as<int64_t>(), kbegin);
+    hipLaunchKernelGGL(k_run_gather<Pts>, dim3((unsigned)cdiv(total, 4096)), dim3(256), 0, st, pts, kbegin, (int64_t)n_keep, dst.off.as<int64_t>(), reinterpret_cast<int2*>(dst.pts.p), total);
     HIPC(c, hipGetLastError());
-    return vgather(c, desc, n_keep, reinterpret_cast<const int32_t*>(spt), dst);
+    return 0;
 }
+template int orip_runs_to_polys<SlotPtsI2>(orip_ctx*, SlotPtsI2, const uint8_t*, unsigned, DPolys&);
+template int orip_runs_to_polys<SlotPtsF64>(orip_ctx*, SlotPtsF64, const uint8_t*, unsigned, DPolys&);
 
 // explicit points of a walk-coded list, on request (orip_get_polys, consumers that read int32 pairs); enqueued on the calling lane's stream
 int orip_polys_materialize(orip_ctx* c, DPolys& P) {

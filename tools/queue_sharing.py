@@ -12,7 +12,7 @@ CLASSES = [      # (lane class, kernels only that class of stream launches on th
     ("raster side", ("k_chain_ends_bits", "k_chain_build")),
     ("layer main", ("k_trace", "k_greedy_nn_fast", "k_plot_order_wave")),
     ("layer side", ("k_comp_paths_lds", "k_comp_paths_glb", "k_tail_replay", "k_seglen", "k_perim_leaves_seg")),
-    ("stage 10", ("k_taps_wave", "k_taps_sequential", "k_stamp_chain", "k_stamp_discs", "k_cut_counts", "k_run_keep")),
+    ("stage 10", ("k_taps_wave", "k_taps_sequential", "k_stamp_chain", "k_stamp_discs", "k_cut_counts", "k_cut_slots")),
 ]
 def short(n):
     n = re.sub(r"\(anonymous namespace\)::", "", n); n = re.sub(r"^void ", "", n); n = re.sub(r"[<(].*", "", n)

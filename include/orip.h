@@ -537,6 +537,38 @@ int orip_gcode_improve(orip_ctx* ctx, const int32_t* ends /* [n,4] or NULL = res
                        int32_t flags /* ORIP_ORDER_REVERSE */, const int32_t* start_xy /* NULL = (0,0) */, int64_t max_rounds,
                        int32_t* order /* [n] in/out */, uint8_t* rev /* [n] in/out */,
                        int64_t* stats /* [5]: travel_before, travel_after, rounds, converged_groups, skipped_groups */);
+/* --loop-start (csrc/gcode_seam.hip; ours, the reference has no such pass): where every closed stroke of a drawing sequence is entered and left.  The orders
+ * and orip_gcode_improve see a closed stroke as the one point its file happened to list first; this pass chooses that point, for all of them at once.
+ * Input: n step polylines (off, pts), or off == pts == NULL for the n resident ones, which are read and never written (an explicit input does not become
+ * the resident list either); a drawing sequence order[n], rev[n], NULL for either meaning identity and no reversal; a start cursor.
+ *   Distance: d(p, q) = max(|px - qx|, |py - qy|), the steps of a travel (csrc/stream.hip: k_seg_counts), as in orip_gcode_improve.
+ *   Closed: a stroke is CLOSED iff it has at least 4 points and its first point equals its last.  Everything else is open: A, B, A and every 2-point stroke.
+ *   Ring and seam: a closed stroke of L points has the ring vertices 0 .. L - 2, indexed in the STORED point list whatever rev says.  Seam s: the stored list
+ *   becomes s, s + 1, .., L - 2, 0, 1, .., s and is then drawn backwards if rev is set; either way the stroke is entered and left at stored vertex s.  Seam
+ *   0 is the stroke as it stands.  Two ring vertices on one grid point (a figure eight) are two candidates.
+ *   Objective: a_k and b_k are the entry and the exit of the stroke at position k (an open stroke: its first and last point, swapped by rev; a closed one:
+ *   its seam vertex, twice), b_{-1} is the start cursor; the objective is the sum of d(b_{k-1}, a_k) over the WHOLE sequence.  The approaches between pen
+ *   groups are in it, groups play no other part, and the end is open: it is the quantity travel_after of orip_gcode_improve reports.
+ *   Answer: the assignment of seams with the LEAST objective and, among those, the one whose seam list, read in drawing order, is LEXICOGRAPHICALLY
+ *   SMALLEST.  Exact, without rounds and without a budget: cost-to-go values are taken backwards, f_k[v] = min_u d(v, u) + f_{k+1}[u] where the next stroke
+ *   is closed, f_k[v] = d(v, a_{k+1}) where it is open, 0 behind the last stroke; a forward pass then takes, stroke by stroke, the lowest vertex that
+ *   attains min_v d(b_{k-1}, v) + f_k[v].  The values are sums of up to n distances of up to 2^30 and are 64-bit.
+ *   Consequences: open strokes, the order, rev, pens and sources are untouched; per stroke the drawn segments are the same multiset, so the pen-down steps
+ *   do not change, and no stroke gains a repeated point; travel_after <= travel_before, and both are the travel of the polylines as gathered; the pass run
+ *   on its own output returns all zeros; a sequence without a closed stroke comes back as it was; changing one seam alone never lowers the travel; maximal
+ *   stretches of consecutive closed strokes (runs) do not depend on each other, an open stroke between them fixes the cursor.
+ * seam_out[k] = the seam of the stroke at POSITION k of the sequence, 0 for an open stroke.  stats: closed strokes, those whose seam is not 0 (moved),
+ * travel_before (every seam 0), travel_after.
+ * Errors before any launch, with the context still good and the outputs untouched: n < 0 or > 2^26; off without pts or the reverse; off not starting at 0
+ * or not increasing by at least 2; 2^30 points or more; a coordinate or the start outside 0 .. 2^30; an order that is not a permutation; a rev byte above
+ * 1; NULL stats, or NULL seam_out with n > 0; n that is not the resident count.  n == 0 returns zeros before any launch.
+ * Declined: letting the greedy order enter a ring at its nearest vertex (the order stays the reference's rule; a pass of its own); alternating with
+ * orip_gcode_improve until nothing moves; choosing a ring's direction (it does not change the travel); entering a ring on an edge between two vertices
+ * (that would invent a vertex); any bound on the worst case: two rings of 10^5 vertices in a row are 10^10 pairs, and the result must not depend on a
+ * budget. */
+int orip_gcode_seam(orip_ctx* ctx, const int64_t* off /* [n+1] or NULL */, const int32_t* pts /* [off[n],2] or NULL = resident */, int64_t n,
+                    const int32_t* order /* [n] or NULL */, const uint8_t* rev /* [n] or NULL */, const int32_t* start_xy /* NULL = (0,0) */,
+                    int32_t* seam_out /* [n], by sequence position; 0 for open strokes */, int64_t* stats /* [4]: closed, moved, travel_before, travel_after */);
 /* StreamWriter.add_steps / finalize (helper :55-68, :166-175) for a whole plot: the bytes of the stream from the direction codes orip_stream_codes left
  * resident.  Piece i reads cnt[i] codes from code0[i] on and owns the bytes from pos[i]: its speed byte when speed[i] >= 0, then (cnt[i] + 1) / 2 step bytes
  * (two codes per byte, paired inside the piece, the last byte of an odd piece holds one).  Pieces are listed in byte order, each at least one byte, none

@@ -95,7 +95,7 @@ extern "C" void orip_destroy(orip_ctx* c) {
     c->sp_data.release(); c->sp_agg.release(); c->sp_keys.release(); c->sp_rgb.release();
     c->gc_tmp.release(); c->gc_off.release(); c->gc_pts.release(); c->gc_ends.release(); c->gc_grid.release(); c->pk_tab.release(); c->pk_out.release(); c->gc_src.release(); c->ht_grp.release();
     c->mg_tab.release(); c->mg_tmp.release(); c->mg_off.release(); c->mg_pts.release(); c->mg_res.release();
-    c->im_state.release(); c->im_rec.release();
+    c->im_state.release(); c->im_rec.release(); c->sm_state.release(); c->sm_in.release(); c->sm_f.release();
     c->sp_tmp.release(); c->sp_off.release(); c->sp_pts.release(); c->sp_res.release();
     c->dd_tmp.release(); c->dd_off.release(); c->dd_pts.release(); c->dd_src.release(); c->dd_res.release();
     c->oc_tmp.release(); c->oc_ev.release(); c->oc_off.release(); c->oc_pts.release(); c->oc_src.release(); c->oc_res.release();

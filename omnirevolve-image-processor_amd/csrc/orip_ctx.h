@@ -341,6 +341,7 @@ struct orip_ctx {
     // keep it are declared in gc_convert.h and defined in gcode.hip, and no other code writes these fields.
     //   Readers (fail while !gc_ready, or when the n they are given is not gc_n): orip_gcode_steps_fetch, orip_gcode_steps_source_fetch (also fails while
     //   gc_merged), and for NULL input orip_gcode_order, orip_gcode_order_pens, orip_gcode_improve, orip_gcode_merge, orip_gcode_simplify, orip_gcode_dedup, orip_gcode_occlude, orip_gcode_dash; orip_svg_occlude always.
+    //   orip_gcode_seam is a reader in both forms: NULL input reads the list, an explicit input goes to sm_in and does not become the list; it never writes these fields.
     //   Writers, and what each leaves:
     //     orip_gcode_to_steps       drops the list on entry (gc_drop), before it looks at its arguments: after ANY failure there is no list.  Success: its
     //                               polylines and their sources, gc_merged cleared; no points to convert (n == 0 included): the empty list (gc_publish_empty).
@@ -383,6 +384,10 @@ struct orip_ctx {
     // (ab int4[2][n], id int[2][n]) a move is written between; im_rec = one record per block of the evaluation, the two status slots and the two travels
     // (the unit states the layout)
     DBuf im_state, im_rec;
+    // --loop-start (gcode_seam.hip), free between calls: sm_state = per position of the sequence the ring size, where the stroke's points start, entry and
+    // exit, the scanned flags, the runs, the levels, the large layers and the seams, and the counters; sm_in = off / pts of an explicit input; sm_f = the
+    // cost-to-go of every ring vertex, int64 (the unit states the layout)
+    DBuf sm_state, sm_in, sm_f;
     // --simplify-mm (gcode_simplify.hip): sp_tmp = the keep flags, their scan, the two span lists and the counts, free between calls (the unit states the
     // layout); sp_off / sp_pts = the output, swapped with gc_off / gc_pts when a call succeeds; sp_res = kept int64[sp_points], the input index of every
     // output point of the last call (-1: none) until the next one

@@ -514,6 +514,28 @@ class Device:
                                            _p(st), _l.IMPROVE_ROUNDS_AUTO if max_rounds is None else int(max_rounds), _p(o), _p(r), _p(stats)))
         return o[:n], r[:n].astype(bool), {k: int(v) for k, v in zip(("travel_before", "travel_after", "rounds", "converged_groups", "skipped_groups"), stats)}
 
+    def gcode_seam(self, off, pts, order, rev, start=(0, 0), n: int | None = None):
+        """--loop-start (include/orip.h: orip_gcode_seam): where every closed stroke of the drawing sequence (order int [n], rev bool [n], either None =
+        identity / no reversal) is entered and left, for the least pen-up travel from `start`; the step polylines (off int64 [n + 1], pts int32 [total, 2])
+        or, both None, the n resident ones, which are read and not changed.
+        -> (seam int32 [n]: by sequence position, the stored ring vertex a closed stroke starts and ends at, 0 for an open one,
+            {"closed", "moved", "travel_before", "travel_after"})"""
+        po, pp, n, _keep = _step_paths(off, pts, n)
+        o = None if order is None else np.ascontiguousarray(order, np.int32).reshape(-1)
+        r = None if rev is None else np.ascontiguousarray(rev, np.uint8).reshape(-1)
+        if n is None:
+            n = len(o) if o is not None else len(r) if r is not None else None
+        if n is None:
+            raise ValueError("n: the number of resident step polylines")
+        n = int(n)
+        if (o is not None and len(o) != n) or (r is not None and len(r) != n):
+            raise ValueError(f"{None if o is None else len(o)} positions and {None if r is None else len(r)} directions given for {n} paths")
+        st = _start_xy(start)
+        seam = np.zeros(max(n, 1), np.int32)
+        stats = np.zeros(4, np.int64)
+        self._ck(self.L.orip_gcode_seam(self.h, po, pp, n, _p(o) if o is not None and n else None, _p(r) if r is not None and n else None, _p(st), _p(seam), _p(stats)))
+        return seam[:n], {k: int(v) for k, v in zip(_l.SEAM_STATS, stats)}
+
     def gcode_merge(self, off, pts, group, n_groups: int, reverse: bool = False, n: int | None = None):
         """--merge-paths (include/orip.h: orip_gcode_merge): step polylines (off int64 [n + 1], pts int32 [total, 2]; both None = the n resident ones) that
         meet end to end inside a group become one stroke, and the merged polylines become the resident ones.  group int32 [n] or None (all 0).

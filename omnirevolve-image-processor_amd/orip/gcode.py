@@ -54,7 +54,14 @@ perforation, a fold line or a stitch line is asked for here.  Every stroke is cu
 from its first point (--dash-offset-mm: from that far into the pattern): orip_gcode_dash; include/orip.h states the rule, exact in integers on the step
 grid.  It runs after the pens have been worked out and before the occlusion and the dedup; every stroke the conversion leaves starts the pattern anew, so
 under --clip the phase restarts at the sheet's edge, and the merge, which runs later, does not carry it on.  A dash keeps its stroke's pen and source; a
-dash that rounds onto one grid point is dropped.  Without the option no device call is added and every byte is what it was."""
+dash that rounds onto one grid point is dropped.  Without the option no device call is added and every byte is what it was.
+
+--loop-start (ours as well): a circle, a rectangle, a closed path and a ring --merge-paths has rebuilt are entered and left at the vertex their file happened
+to list first, and the orders and --improve-order see such a stroke as that one point.  With --loop-start every closed stroke (four points or more, the
+first equal to the last) starts and ends at the ring vertex that makes the pen-up steps of the whole plot least, all closed strokes chosen together and
+exactly, ties to the lowest vertex in drawing order (orip_gcode_seam; include/orip.h states the rule).  It runs after the order and after --improve-order,
+immediately before the paths are gathered; the order, the directions, pens, sources, open strokes and every drawn segment stay as they are.  Allowed with
+--no-reorder: file order, better seams.  Without the option no device call is added and every byte is what it was."""
 from __future__ import annotations
 
 import argparse
@@ -111,6 +118,7 @@ class GcodeOptions:
     clip_margin_mm: Optional[float] = None  # the clip rectangle lies this far inside the sheet (None: 0); only with clip
     simplify_mm: Optional[float] = None     # vertices within this distance of the stroke are dropped (None: every vertex is drawn; 0: only those on the stroke)
     dedup: bool = False                 # collinear segments of one pen that lie over each other are drawn once, the first drawn copy stays
+    loop_start: bool = False            # every closed stroke starts and ends at the ring vertex that makes the pen-up travel of the plot least
     dash_mm: Optional[str] = None       # every path is drawn dashed: dash and gap lengths in mm, comma-separated (None: solid)
     dash_offset_mm: Optional[float] = None  # where in the pattern a path starts (None: 0); only with dash_mm
 
@@ -273,14 +281,19 @@ def path_ends(off: np.ndarray, pts: np.ndarray) -> np.ndarray:
     return np.ascontiguousarray(np.concatenate([pts[off[:-1]], pts[off[1:] - 1]], 1), np.int32)
 
 
-def gather_paths(off: np.ndarray, pts: np.ndarray, order: np.ndarray, rev: Optional[np.ndarray] = None) -> Tuple[np.ndarray, np.ndarray]:
-    """the paths in the given order, those with rev[k] set back to front: (off, pts), flat numpy over all paths"""
+def gather_paths(off: np.ndarray, pts: np.ndarray, order: np.ndarray, rev: Optional[np.ndarray] = None, seam: Optional[np.ndarray] = None) -> Tuple[np.ndarray, np.ndarray]:
+    """the paths in the given order, those with rev[k] set back to front: (off, pts), flat numpy over all paths.  seam[k] > 0 (by position, closed strokes
+    only: include/orip.h, orip_gcode_seam): the stroke of L points is rotated to start and end at its stored vertex seam[k], s, s + 1, .., L - 2, 0, .., s,
+    before rev turns it round"""
     order = np.asarray(order, np.int64)
     lens = np.diff(off)[order]
     noff = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
     t = np.arange(int(lens.sum())) - np.repeat(noff[:-1], lens)
     if rev is not None:
         t = np.where(np.repeat(np.asarray(rev, bool), lens), np.repeat(lens, lens) - 1 - t, t)
+    if seam is not None:
+        s = np.repeat(np.asarray(seam, np.int64), lens)
+        t = np.where(s > 0, (t + s) % np.repeat(lens - 1, lens), t)
     return noff, pts[np.repeat(off[:-1][order], lens) + t]
 
 
@@ -309,7 +322,7 @@ def build_stream_from_gcode(text_or_paths, opts: Optional[GcodeOptions] = None, 
                             timings: Optional[dict] = None, pens: Optional[np.ndarray] = None, order_pens_fn: Optional[Callable] = None,
                             source_fn: Optional[Callable] = None, merge_fn: Optional[Callable] = None, improve_fn: Optional[Callable] = None,
                             clip_fn: Optional[Callable] = None, simplify_fn: Optional[Callable] = None, dedup_fn: Optional[Callable] = None,
-                            dash_fn: Optional[Callable] = None) -> Tuple[bytes, dict]:
+                            dash_fn: Optional[Callable] = None, seam_fn: Optional[Callable] = None) -> Tuple[bytes, dict]:
     """The stream of a G-code text (str / bytes) or of paths in mm given as (off, pts_mm); opts as parsed, --speed-scale not yet applied.
     Device steps, each None = the GPU (orip.device.Device; there is no CPU path in the product):
       steps_fn(off, pts_mm, map: dict) -> (off int64, pts int32 [total, 2])      orip_gcode_to_steps
@@ -336,12 +349,15 @@ def build_stream_from_gcode(text_or_paths, opts: Optional[GcodeOptions] = None, 
     and, only with --dash-mm (after the pens have been worked out, before the dedup; it needs source_fn):
       dash_fn(off, pts, pattern int32 [n], phase int64 [n], pat_off, pat_val) -> (off, pts, origin int32, stats)                      orip_gcode_dash
     info["dash"] then holds the eight counts of include/orip.h; a dash keeps its stroke's pen.
+    and, only with --loop-start (after the order and the improvement, immediately before the paths are gathered):
+      seam_fn(off, pts, order or None, rev or None) -> (seam int32 [n] by sequence position, stats)                                    orip_gcode_seam
+    info["seam"] then holds closed, moved, travel_before and travel_after (pen-up steps of the whole plot).
     pens: one pen per input path, 0..7, or -1 for --color-index (a text's T words under --tool-pens when None).  info["pens"] then counts the paths per
     pen, those that took --color-index ("unmatched") and the strokes drawn backwards ("reversed").
     Returns (bytes, counts)."""
     steps = StrokeSteps(clip_fn if opts is not None and opts.clip else steps_fn, source_fn, merge_fn, simplify_fn, order_fn, order_pens_fn, improve_fn, codes_fn, pack_fn,
                         dedup_fn)
-    return stroke_stream(text_or_paths, opts, device, steps, timings, pens, dash_fn=dash_fn)
+    return stroke_stream(text_or_paths, opts, device, steps, timings, pens, dash_fn=dash_fn, seam_fn=seam_fn)
 
 
 # The device steps of the stroke pipeline, each a callable or None = not given; build_stream_from_gcode states the signatures.  convert: steps_fn or, with --clip, clip_fn
@@ -367,18 +383,27 @@ class Dash:
         self.device_follows = False                 # resolve_steps: pass and sources are both this device's, whose sources follow the dashes through origin
 
 
+class Seam:
+    """--loop-start, which StrokeSteps does not carry: fn(off, pts, order int32 [n] or None, rev bool [n] or None) -> (seam int32 [n]: by sequence position,
+    the stored ring vertex a closed stroke starts and ends at, 0 for an open one; stats) or None = the device (orip_gcode_seam)"""
+    def __init__(self, fn=None):
+        self.fn = fn
+
+
 def resolve_steps(st: StrokeSteps, o, grouped: bool, device=None, convert: Optional[Callable] = None, force: bool = False, occlude: Optional[Occlude] = None,
-                  dash: Optional[Dash] = None):
+                  dash: Optional[Dash] = None, seam: Optional[Seam] = None):
     """The steps the options need, those not given taken from a device -> (steps, device); codes and pack stay as given (orip.stream.compile_plan fills them).
     When none is missing, and the caller does not `force` a device for steps of its own, no device is made and orip.stages is not imported.  convert(device)
     -> the conversion of a front door whose paths are on the device already (orip.svg).  Dedup, merge and simplify work on the polylines the pass before them
     left resident when that pass ran on this device, and are sent their input when it was given.  `dash`: its fn is filled in the same way, and it needs
     the sources as the occlusion does; it stands between the conversion and the occlusion.  `occlude`: its fn is filled in the same way; it needs the
     sources whether or not pens are in use, and the rings are fitted paths that only the device's own conversion leaves next to the strokes, so behind a
-    given conversion the strokes are uploaded first (an occlusion without rings makes them the resident list) and the pass then runs as it does otherwise."""
+    given conversion the strokes are uploaded first (an occlusion without rings makes them the resident list) and the pass then runs as it does otherwise.
+    `seam`: its fn is filled in the same way; it reads the strokes the last pass in front of the order left resident, or is sent them."""
     need = ["convert", "order"] + ["order_pens", "source"] * bool(grouped) + ["merge"] * bool(o.merge_paths) + ["improve"] * bool(o.improve_order) + \
         ["simplify"] * (o.simplify_mm is not None) + ["dedup"] * bool(o.dedup) + ["source"] * (occlude is not None or dash is not None)
-    if not force and all(getattr(st, k) is not None for k in need) and (occlude is None or occlude.fn is not None) and (dash is None or dash.fn is not None):
+    if not force and all(getattr(st, k) is not None for k in need) and (occlude is None or occlude.fn is not None) and (dash is None or dash.fn is not None) and \
+            (seam is None or seam.fn is not None):
         return st, device
     if device is None:
         from .stages import device as _default_device
@@ -387,7 +412,8 @@ def resolve_steps(st: StrokeSteps, o, grouped: bool, device=None, convert: Optio
     after_dash = dash.fn is None if dash is not None else after_convert    # behind its dash pass or, without one, behind the conversion,
     after_occlude = occlude.fn is None if occlude is not None else after_dash         # behind its occlusion or, without one, behind what stands before it,
     after_dedup = st.dedup is None if o.dedup else after_occlude           # behind its dedup or, without one, behind what stands before the dedup,
-    after_merge = st.merge is None if o.merge_paths else after_dedup       # and behind its merge or, without one, behind what stands before the merge
+    after_merge = st.merge is None if o.merge_paths else after_dedup       # behind its merge or, without one, behind what stands before the merge,
+    after_simplify = st.simplify is None if o.simplify_mm is not None else after_merge    # and behind its simplification or, without one, behind what stands before it
     own = StrokeSteps(
         convert=convert(device) if convert is not None else device.gcode_to_steps_clip if o.clip else device.gcode_to_steps, source=device.gcode_steps_source,
         merge=(lambda off, pts, group, n_groups, reverse: device.gcode_merge(None, None, group, n_groups, reverse, n=len(off) - 1)) if after_dedup else device.gcode_merge,
@@ -401,6 +427,8 @@ def resolve_steps(st: StrokeSteps, o, grouped: bool, device=None, convert: Optio
                 device.gcode_occlude(off, pts, level, np.zeros(1, np.int64), np.zeros((0, 2), np.int32), np.zeros(0, np.int32))
             return device.svg_occlude(level, ring_sub, ring_level, m, clamp, n=len(off) - 1)
         occlude.fn = own_occlude
+    if seam is not None and seam.fn is None:
+        seam.fn = (lambda off, pts, order, rev: device.gcode_seam(None, None, order, rev, n=len(off) - 1)) if after_simplify else device.gcode_seam
     if dash is not None and dash.fn is None:
         dash.device_follows = st.source is None
         dash.fn = (lambda off, pts, pattern, phase, po, pv: device.gcode_dash(None, None, pattern, phase, po, pv, n=len(off) - 1)) if after_convert else device.gcode_dash
@@ -584,6 +612,37 @@ def _order(st: StrokeSteps, o: GcodeOptions, off, pts, group, n_groups: int, inf
     return order, rev
 
 
+def travel_steps(off, pts, start=(0, 0)) -> int:
+    """the pen-up steps of strokes drawn as they stand, from `start`: max(|dx|, |dy|) per travel, as the stream compiler counts them"""
+    off = np.asarray(off, np.int64); pts = np.asarray(pts, np.int64).reshape(-1, 2)
+    if len(off) <= 1:
+        return 0
+    a, b = pts[off[:-1]], pts[off[1:] - 1]
+    return int(np.abs(a - np.concatenate([np.asarray(start, np.int64).reshape(1, 2), b[:-1]])).max(1).sum())
+
+
+def _seam(sm: Seam, off, pts, order, rev, info: dict):
+    """the strokes gathered in drawing order, every closed one started at the vertex the pass chose; info["seam"]"""
+    n = len(off) - 1
+    seam, sst = sm.fn(off, pts, None if order is None else np.asarray(order, np.int32), None if rev is None else np.asarray(rev, bool))
+    seam = np.asarray(seam, np.int64).reshape(-1)
+    d = {k: int(sst[k]) for k in SEAM_STATS}
+    seq = np.arange(n) if order is None else np.asarray(order, np.int64)
+    lens = np.diff(off)[seq]
+    closed = (lens >= 4) & (pts[off[:-1][seq]] == pts[off[1:][seq] - 1]).all(1)
+    if len(seam) != n or (seam < 0).any() or (seam[~closed] != 0).any() or (seam[closed] >= lens[closed] - 1).any():
+        raise RuntimeError("the seams do not name a ring vertex of every closed stroke and 0 for every open one")
+    before = gather_paths(off, pts, seq, rev)
+    goff, gpts = gather_paths(off, pts, seq, rev, seam)
+    if d["closed"] != int(closed.sum()) or d["moved"] != int((seam != 0).sum()) or d["travel_before"] != travel_steps(*before) or d["travel_after"] != travel_steps(goff, gpts) or \
+            d["travel_after"] > d["travel_before"] or draw_steps(goff, gpts) != draw_steps(*before):
+        raise RuntimeError("the seam pass's counts do not add up")
+    if "improve" in info and d["travel_before"] != info["improve"]["travel_after"]:
+        raise RuntimeError("the seam pass and the improvement count different pen-up steps for the same sequence")
+    info["seam"] = d
+    return goff, gpts
+
+
 def _plan(o: GcodeOptions, sc: ST.StreamConfig, off, pts, path_pen) -> ST.Plan:
     """every move of the plot; path_pen: the pen of every stroke in drawing order, or None for --color-index throughout"""
     if not (0 <= int(o.color_index) <= 7):
@@ -595,9 +654,11 @@ def _plan(o: GcodeOptions, sc: ST.StreamConfig, off, pts, path_pen) -> ST.Plan:
 
 
 def stroke_stream(text_or_paths, opts: Optional[GcodeOptions], device, steps: StrokeSteps, timings: Optional[dict] = None, pens: Optional[np.ndarray] = None,
-                  occlude: Optional[Occlude] = None, dash: Optional[Dash] = None, dash_fn: Optional[Callable] = None) -> Tuple[bytes, dict]:
+                  occlude: Optional[Occlude] = None, dash: Optional[Dash] = None, dash_fn: Optional[Callable] = None, seam_fn: Optional[Callable] = None,
+                  seam: Optional["Seam"] = None) -> Tuple[bytes, dict]:
     """build_stream_from_gcode with the device steps as one record: parse, convert, pens of the strokes, [dash: --dash-mm gives every path the one pattern,
-    with dash_fn; the SVG door brings a record of its own], [occlude, the SVG door's], dedup, merge, simplify, order, plan, compile"""
+    with dash_fn; the SVG door brings a record of its own], [occlude, the SVG door's], dedup, merge, simplify, order, [seam: --loop-start, with seam_fn, or the record a door has
+    resolved already], plan, compile"""
     import time
     o = apply_speed_scale(GcodeOptions(**{f.name: getattr(opts, f.name) for f in fields(GcodeOptions)}) if opts is not None else GcodeOptions())
     W, H = target_size(o)
@@ -634,7 +695,8 @@ def stroke_stream(text_or_paths, opts: Optional[GcodeOptions], device, steps: St
         raise ValueError(f"target size {W} x {H} steps: each side must be in 1..2^30 (step coordinates are int32 on the device)")
     if own_dash is not None and dash is None:                             # --dash-mm: every path gets the pattern
         dash = Dash(dash_fn, np.zeros(len(off_mm) - 1, np.int32), np.full(len(off_mm) - 1, own_dash[1], np.int64), [0, len(own_dash[0])], own_dash[0])
-    st, device = resolve_steps(steps, o, grouped, device, occlude=occlude, dash=dash)
+    sm = (seam if seam is not None else Seam(seam_fn)) if o.loop_start else None
+    st, device = resolve_steps(steps, o, grouped, device, occlude=occlude, dash=dash, seam=sm)
     m = dict(scale_x=o.scale_x, scale_y=o.scale_y, offset_x_mm=o.offset_x_mm, offset_y_mm=o.offset_y_mm, steps_per_mm=o.steps_per_mm, W=W, H=H, invert_y=int(bool(o.invert_y)))
     off, pts = _convert(st, off_mm, pts_mm, m, rect, info)
     lap("to_steps")
@@ -672,7 +734,11 @@ def stroke_stream(text_or_paths, opts: Optional[GcodeOptions], device, steps: St
         off, pts = _simplify(st, off, pts, tol4, info)
         lap("simplify")
     order, rev = _order(st, o, off, pts, group, n_groups, info, lap)
-    if order is not None:
+    if sm is not None:
+        lap("order")
+        off, pts = _seam(sm, off, pts, order, rev, info)
+        lap("seam")
+    elif order is not None:
         off, pts = gather_paths(off, pts, order, rev)
     if grouped:
         (info["pens"] if pens is not None else info)["reversed"] = int(rev.sum())
@@ -689,6 +755,7 @@ CLIP_STATS = ("segments", "inside", "cut", "outside", "paths_out", "points_out")
 DEDUP_STATS = ("segments", "whole", "cut", "covered", "pieces", "paths_out", "points_out", "draw_steps_in", "draw_steps_out")      # include/orip.h: orip_gcode_dedup
 OCCLUDE_STATS = ("segments", "whole", "cut", "hidden", "pieces", "collapsed", "paths_out", "points_out", "draw_steps_in", "draw_steps_out")      # include/orip.h: orip_gcode_occlude
 DASH_STATS = ("paths_in", "dashed", "dashes", "collapsed", "paths_out", "points_out", "length_in", "length_on")      # include/orip.h: orip_gcode_dash
+SEAM_STATS = ("closed", "moved", "travel_before", "travel_after")      # include/orip.h: orip_gcode_seam
 DASH_UNIT, DASH_MAX_ENTRIES = 256, 64         # include/orip.h: ORIP_DASH_UNIT (dash lengths are in 1/256 step), ORIP_DASH_MAX_ENTRIES
 SIMPLIFY_TOL4_MAX = (1 << 17) - 1             # include/orip.h: ORIP_SIMPLIFY_TOL4_MAX
 
@@ -782,6 +849,11 @@ def improve_line(tag: str, st: dict) -> str:
             f"{st['converged_groups']} groups converged, {st['skipped_groups']} skipped")
 
 
+def seam_line(tag: str, st: dict) -> str:
+    saved = st["travel_before"] - st["travel_after"]
+    return f"[{tag}] loop start: {st['closed']} closed strokes, {st['moved']} start elsewhere, pen-up steps {st['travel_before']} -> {st['travel_after']} ({saved} saved)"
+
+
 # ------------------------------------------------------------------ command line (:436-638)
 def build_argparser() -> argparse.ArgumentParser:
     d = GcodeOptions()
@@ -813,6 +885,8 @@ def build_argparser() -> argparse.ArgumentParser:
     add_stroke_args(ap, STROKE_ARGS[:2])
     ap.add_argument("--tool-pens", action="store_true", help="a path is drawn with the pen its T word names (T0..T7; before any T: --color-index), pen after pen")
     add_stroke_args(ap, STROKE_ARGS[2:])
+    ap.add_argument("--loop-start", action="store_true", help="start and end every closed stroke at the vertex that makes the pen-up travel of the whole plot least, "
+                                                              "all of them chosen together, after the order (and --improve-order); allowed with --no-reorder")
     ap.add_argument("--dash-mm", default=None, help="draw every path dashed: 1..64 comma-separated lengths in mm, dash and gap in turn (an odd count is repeated, as "
                                                     "in SVG); each at least one step; the pattern starts anew with every path")
     ap.add_argument("--dash-offset-mm", type=float, default=None, help="where in the pattern a path starts (any sign; default 0); needs --dash-mm")
@@ -870,6 +944,8 @@ def report_lines(tag: str, info: dict, unmatched: bool = False):
         yield f"[{tag}] simplify: {st['points_in']} points -> {st['points_out']} within {st['tol4'] / 4:g} steps, {st['paths_changed']} strokes changed"
     if "improve" in info:
         yield improve_line(tag, info["improve"])
+    if "seam" in info:
+        yield seam_line(tag, info["seam"])
 
 
 def options_from_args(a: argparse.Namespace) -> GcodeOptions:

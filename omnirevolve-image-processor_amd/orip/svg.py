@@ -644,6 +644,7 @@ class SvgOptions:
     clip_margin_mm: Optional[float] = None              # the clip rectangle lies this far inside the sheet; None: 0
     simplify_mm: Optional[float] = None                 # vertices within this distance of the stroke are dropped (orip.gcode); None: none are
     dedup: bool = False                                 # collinear segments of one pen that lie over each other are drawn once (orip.gcode)
+    loop_start: bool = False                            # closed strokes start at the vertex that makes the pen-up travel least (orip.gcode)
     occlude: bool = False                               # filled shapes hide what lies under them (svg2stream.py only)
     dashes: bool = False                                # stroke-dasharray is drawn as dashes (svg2stream.py only)
 
@@ -745,7 +746,7 @@ def gcode_options(o: SvgOptions) -> GC.GcodeOptions:
                            offset_x_mm=0.0, offset_y_mm=0.0, target_width_steps=W, target_height_steps=H, no_reorder=bool(o.no_reorder),
                            allow_reverse=bool(o.allow_reverse), pen_order=o.pen_order, merge_paths=bool(o.merge_paths),
                            improve_order=bool(o.improve_order), improve_rounds=o.improve_rounds, clip=bool(o.clip), clip_margin_mm=o.clip_margin_mm,
-                           simplify_mm=o.simplify_mm, dedup=bool(o.dedup))
+                           simplify_mm=o.simplify_mm, dedup=bool(o.dedup), loop_start=bool(o.loop_start))
 
 
 def gcode_text(off, pts, passes: int = 1, pens=None) -> str:
@@ -882,7 +883,7 @@ def build_stream_from_svg(text: Union[str, bytes, SegmentTable], opts: Optional[
                           want_paths: bool = False, hatch_groups_fn: Optional[Callable] = None, source_fn: Optional[Callable] = None,
                           order_pens_fn: Optional[Callable] = None, merge_fn: Optional[Callable] = None, improve_fn: Optional[Callable] = None,
                           clip_fn: Optional[Callable] = None, simplify_fn: Optional[Callable] = None, dedup_fn: Optional[Callable] = None,
-                          occlude_fn: Optional[Callable] = None, dash_fn: Optional[Callable] = None) -> Tuple[bytes, dict]:
+                          occlude_fn: Optional[Callable] = None, dash_fn: Optional[Callable] = None, seam_fn: Optional[Callable] = None) -> Tuple[bytes, dict]:
     """The stream of an SVG text (or of a parsed SegmentTable).  Device steps, each None = the GPU (there is no CPU path in the product):
       flatten_fn(table, tol_raw) -> paths          orip_svg_flatten      (`paths` is whatever the other steps take: on the GPU a count, the points stay there)
       bbox_fn(paths) -> (min x, min y, max x, max y)   orip_svg_bbox
@@ -910,6 +911,8 @@ def build_stream_from_svg(text: Union[str, bytes, SegmentTable], opts: Optional[
     and, only with --dashes on a drawing that states a dash array (after the pens have been worked out, before the occlusion; it needs source_fn):
       dash_fn                                      as in orip.gcode.build_stream_from_gcode; the patterns are dash_patterns()'s
     info["dash"] = the eight counts of include/orip.h and "ignored", the dash arrays that left their stroke solid (where no stroke is dashed, "ignored" alone, if any).
+    and, only with --loop-start:
+      seam_fn                                      as in orip.gcode.build_stream_from_gcode (a circle, a <rect> and a closed <path> are closed strokes; hatch lines are open)
     With --pen-colors, info["path_pens"] is the pen of every fitted path (hatch lines included, --color-index where no stroke is stated).
     Returns (bytes, info)."""
     import time
@@ -968,9 +971,10 @@ def build_stream_from_svg(text: Union[str, bytes, SegmentTable], opts: Optional[
         pattern, phase, pat_off, pat_val, ignored = dash_patterns(table, info["scale"], o.steps_per_mm, len(off_mm) - 1)
         if (pattern >= 0).any():                            # no usable dash array: no pass, no device call
             dsh = GC.Dash(dash_fn, pattern, phase, pat_off, pat_val)
-    steps, device = GC.resolve_steps(steps, go, pens_on or o.allow_reverse, device, force=bool(own), occlude=occ, dash=dsh,
+    sm = GC.Seam(seam_fn) if o.loop_start else None
+    steps, device = GC.resolve_steps(steps, go, pens_on or o.allow_reverse, device, force=bool(own), occlude=occ, dash=dsh, seam=sm,
                                      convert=lambda dev: lambda _off, _pts, m, *rect: (_Resident(dev).clip if rect else _Resident(dev).steps)(paths, m, *rect))
-    data, ginfo = GC.stroke_stream((off_mm, np.zeros((int(off_mm[-1]), 2))), go, device, steps, tm, pens, occ, dsh)
+    data, ginfo = GC.stroke_stream((off_mm, np.zeros((int(off_mm[-1]), 2))), go, device, steps, tm, pens, occ, dsh, seam=sm)
     if "dash" in ginfo or ignored:                          # an ignored dash array is reported whether or not a pass ran: the stroke is solid, and the line says so
         ginfo["dash"] = dict(ginfo.get("dash", {}), ignored=ignored)
     return data, dict(ginfo, **info)
@@ -1024,6 +1028,8 @@ def build_stream_argparser() -> argparse.ArgumentParser:
     GC.add_stroke_args(ap, ("--no-reorder", "--pen-order", "--allow-reverse") + GC.STROKE_ARGS[3:], "; the G-code file is not changed")
     ap.add_argument("--occlude", action="store_true", help="filled shapes (what --hatch-fill marks) hide the strokes and hatch lines of the elements painted before them; "
                                                            "exact on the step grid; the G-code file is not changed")
+    ap.add_argument("--loop-start", action="store_true", help="start and end every closed stroke (a circle, a rectangle, a closed path) at the vertex that makes the pen-up "
+                                                              "travel of the whole plot least, all of them chosen together, after the order; the G-code file is not changed")
     ap.add_argument("--dashes", action="store_true", help="draw a stroke that states a stroke-dasharray as its dashes, measured on the step grid from the start of "
                                                           "every stroke (hatch lines stay solid); the G-code file is not changed")
     ap.add_argument("--no-preview", action="store_true", help="do not render <svg stem>_stream_preview.png")

@@ -62,6 +62,23 @@ __global__ __launch_bounds__(256) void k_gc_emit(const long long* __restrict__ o
 }
 }  // namespace
 
+// ------------------------------------------------------------------------------------------------ the cutting passes' compaction (gc_cut.h)
+__global__ __launch_bounds__(256) void k_gc_cut_compact(int64_t S, const unsigned* __restrict__ rec, const int2* __restrict__ sinfo, unsigned long long* __restrict__ cs) {
+    const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (g > S) return;
+    unsigned long long out = 0;
+    if (g < S) {
+        const unsigned r = rec[g], np = r & GC_CUT_NP;
+        if (np) {
+            bool cont = false;
+            if ((r & GC_CUT_FA) && g > 0 && sinfo[g - 1].y == sinfo[g].y) { const unsigned rp = rec[g - 1]; cont = (rp & GC_CUT_NP) && (rp & GC_CUT_FB); }
+            const unsigned starts = np - (cont ? 1u : 0u);
+            out = ((unsigned long long)(np + starts) << 32) | starts;
+        }
+    }
+    cs[g] = out;
+}
+
 // ------------------------------------------------------------------------------------------------ the resident list's host side (gc_convert.h)
 static int gc_check_offsets(orip_ctx* c, const char* who, const int64_t* off, int64_t n) {
     if (off[0] != 0) ORIP_FAIL_AS(c, who, "offsets must start at 0");
@@ -117,6 +134,49 @@ void gc_drop(orip_ctx* c) { c->gc_n = 0; c->gc_total = 0; c->gc_ready = false; c
 int gc_publish_empty(orip_ctx* c, const char* who) { static const int64_t zero = 0; return gc_steps_upload(c, who, &zero, nullptr, 0, 0); }
 void gc_publish(orip_ctx* c, DBuf& off, DBuf& pts, int64_t n, int64_t total) { std::swap(c->gc_off, off); std::swap(c->gc_pts, pts); c->gc_n = n; c->gc_total = total; }
 void gc_publish_src(orip_ctx* c, DBuf& src) { std::swap(c->gc_src, src); }
+// the cutting passes' frame (gc_cut.h)
+hipError_t gc_scan_u64(orip_ctx* c, unsigned long long* in, unsigned long long* out, size_t count) {
+    return orip_with_tmp(c, [&](void* tmp, size_t& bytes) { return rocprim::exclusive_scan(tmp, bytes, in, out, 0ull, count, rocprim::plus<unsigned long long>(), LN(c).stream); });
+}
+static bool gc_same_count(const orip_ctx* c, int64_t n) { return c->gc_ready && c->gc_n == n; }      // as many as the sources name: taken for the polylines a fetch gave out
+int gc_cut_empty(orip_ctx* c, const char* who, GcCut& r, bool explicit_in) {
+    const bool same_count = gc_same_count(c, 0);
+    if (explicit_in) { ORIP_TRY(gc_publish_empty(c, who)); if (!same_count) c->gc_merged = true; }
+    r.paths = 0;
+    return 0;
+}
+int gc_cut_intake(orip_ctx* c, const char* who, GcCut& r, const int64_t* off, const int32_t* pts, int64_t n, int64_t total, bool& sources) {
+    const bool same_count = gc_same_count(c, n);                              // of the list in front of the upload
+    r.paths = -1;
+    if (off) ORIP_TRY(gc_steps_upload(c, who, off, pts, n, total));           // checked by the caller: from here on the input is the resident list
+    if (off && !same_count) c->gc_merged = true;                              // the sources do not name these polylines
+    sources = !c->gc_merged;                                                  // gc_src names the input strokes: gathered through origin by the pass
+    return 0;
+}
+int gc_cut_ensure(orip_ctx* c, const char* who, GcCut& r, long long cap_paths, long long cap_pts) {
+    HIPC_AS(c, who, r.off.ensure(((size_t)cap_paths + 1) * 8 + 64)); HIPC_AS(c, who, r.pts.ensure((size_t)cap_pts * 8 + 64));
+    HIPC_AS(c, who, r.res.ensure((size_t)cap_paths * 4 + 64)); HIPC_AS(c, who, r.src.ensure((size_t)cap_paths * 4 + 64));
+    return 0;
+}
+GcCutOut gc_cut_out(orip_ctx* c, const GcCut& r, bool sources, long long cap_pts, long long cap_paths) {
+    return {r.pts.as<int2>(), r.off.as<long long>(), r.res.as<int>(), r.src.as<int>(), sources ? c->gc_src.as<int>() : nullptr, cap_pts, cap_paths};
+}
+void gc_cut_publish(orip_ctx* c, GcCut& r, bool sources, int64_t paths, int64_t points) {
+    gc_publish(c, r.off, r.pts, paths, points);
+    if (sources) gc_publish_src(c, r.src);
+    r.paths = paths;
+}
+int gc_cut_fetch(orip_ctx* c, const char* who, const GcCut& r, const char* pass, int32_t* origin) {
+    orip_enter(c);
+    ORIP_LANE_AS(c, who, ORIP_LANE_CROSS);
+    if (r.paths < 0) ORIP_FAIL_AS(c, who, "no result: %s has not succeeded since the last failure", pass);
+    if (r.paths == 0) return 0;
+    if (!origin) ORIP_FAIL_AS(c, who, "bad arguments");
+    hipStream_t s = LN(c).stream;
+    HIPC_AS(c, who, hipMemcpyAsync(origin, r.res.p, (size_t)r.paths * 4, hipMemcpyDeviceToHost, s));
+    HIPC_AS(c, who, hipStreamSynchronize(s));
+    return 0;
+}
 int gc_check_resident(orip_ctx* c, const char* who, int64_t n) {
     if (!c->gc_ready || n != c->gc_n) ORIP_FAIL_AS(c, who, "%lld paths asked for, %lld step polylines resident", (long long)n, (long long)(c->gc_ready ? c->gc_n : -1));
     return 0;

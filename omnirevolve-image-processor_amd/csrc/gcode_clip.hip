@@ -29,7 +29,6 @@
 // Resident afterwards, as after orip_gcode_to_steps: c->gc_off, c->gc_pts, c->gc_src (orip_ctx.h states the contract; this writer checks before it drops).
 #include "orip_ctx.h"
 #include "gc_convert.h"
-#include <rocprim/rocprim.hpp>
 
 namespace {
 constexpr int CL_ERR_NOT_FINITE = 1, CL_ERR_RANGE = 2;
@@ -197,10 +196,10 @@ extern "C" int orip_gcode_to_steps_clip(orip_ctx* c, const int64_t* off, const d
     const dim3 g1(cdiv(total + 1, 256)), b(256);
     { ProfScope ps_(c, "k_cl_segments");
       hipLaunchKernelGGL(k_cl_segments, g1, b, 0, s, d_off, n, d_mm, total, *map, R, ab, cs, cn); }
-    HIPC(c, orip_with_tmp(c, [&](void* tmp, size_t& bytes) { return rocprim::exclusive_scan(tmp, bytes, cs, scan, (u64)0, (size_t)total + 1, rocprim::plus<u64>(), s); }));
+    HIPC(c, gc_scan_u64(c, cs, scan, (size_t)total + 1));
     hipLaunchKernelGGL(k_cl_starts, g1, b, 0, s, cs, scan, total, sstart);
     hipLaunchKernelGGL(k_cl_strokes, g1, b, 0, s, scan, total, sstart, ps);
-    HIPC(c, orip_with_tmp(c, [&](void* tmp, size_t& bytes) { return rocprim::exclusive_scan(tmp, bytes, ps, pscan, (u64)0, (size_t)total + 1, rocprim::plus<u64>(), s); }));
+    HIPC(c, gc_scan_u64(c, ps, pscan, (size_t)total + 1));
     { ProfScope ps_(c, "k_cl_emit");
       hipLaunchKernelGGL(k_cl_emit, g1, b, 0, s, d_off, n, total, ab, cs, scan, sstart, ps, pscan, cap_pts, c->gc_pts.as<int2>(), c->gc_off.as<long long>(), c->gc_src.as<int>()); }
     HIPC(c, hipGetLastError());

@@ -25,15 +25,15 @@
 //    corrects it against the exact 128-bit remainder, so no result of floating point is trusted.
 // 4. Compaction.  k_ds_alive: a raw point that does not begin its dash and differs from the raw point before it marks its dash alive (a dash of one
 //    distinct point has none: collapsed).  k_ds_flag: a point stays when it begins its dash or differs from the point before it, and its dash is alive;
-//    cs2 = (1 << 32) | begins.  One more scan, and k_ds_out writes points, offsets, origin and the gathered sources.
+//    cs2 = (1 << 32) | begins.  One more scan (gc_cut.h: gc_scan_u64, as the one of step 2), and k_ds_out writes points, offsets, origin and the
+//    gathered sources (gc_cut_start, gc_cut_close).
 // Everything on the calling lane's stream; two read-backs and two host synchronisations: behind the count (the raw arrays are sized by it) and behind the
 // last launch.
 //
 // Scratch in c->ds_tmp, free between calls, ONE Carve (orip_gcode_dash): X DsLen[total + 1] twice (lengths, scanned); pat int[n], ph u64[n]; poff int[np + 1],
 // A u64[E + np], On u64[E + np] (pattern q's tables start at poff[q] + q and hold its m + 1 prefixes); scans u64[2 total + 2] (cs, scan); longlist
 // unsigned[total]; DsCounters.  c->ds_raw, ONE Carve behind the first read-back: rpts int2[R], rdid unsigned[R], dpath int[Q], alive unsigned[Q], scans
-// u64[2 R + 2] (cs2, scan2).  Output: c->ds_off / c->ds_pts, sized by R and Q, made the resident list when the call succeeds (gc_publish; orip_ctx.h states
-// the contract); c->ds_src, the sources gathered through origin (gc_publish_src).  Resident until the next call: origin int32[ds_paths] in c->ds_res.
+// u64[2 R + 2] (cs2, scan2).  Output: the record c->ds, sized by R and Q (gc_cut.h states the frame, orip_ctx.h the contract).
 #include "orip_ctx.h"
 #include "gc_convert.h"
 #include <rocprim/rocprim.hpp>
@@ -59,7 +59,6 @@ struct DsPat { const u64* A; const u64* On; unsigned m; u64 P, ph; };           
 struct DsPos { u64 r, rem; unsigned t; bool at; };                                    // of an arc position: period, place in it, boundaries of the period at or before it, on one
 struct DsSeg { bool head, head_start, closing; u64 c, r0, x0, len; unsigned t0, ns; };
 struct DsRaw { int2* pts; unsigned* did; int* dpath; long long R, Q; };
-struct DsOut { int2* pts; long long* off; int* origin; int* src; const int* src_in; long long cap_pts, cap_paths; };
 
 // floor(256 sqrt(D)), D <= 2^61: the double's estimate is within one of it, the two loops make it exact on the radicand D 2^16
 __device__ __forceinline__ u64 ds_isqrt(u64 D) {
@@ -262,24 +261,20 @@ __global__ __launch_bounds__(256) void k_ds_flag(DsRaw o, const unsigned* __rest
     bool start = false;
     cs2[i] = i < o.R && ds_kept(o, alive, i, start) ? (1ull << 32) | (start ? 1u : 0u) : 0;
 }
-__global__ __launch_bounds__(256) void k_ds_out(DsRaw o, const unsigned* __restrict__ alive, const u64* __restrict__ scan2, DsOut out, DsCounters* cn) {
+__global__ __launch_bounds__(256) void k_ds_out(DsRaw o, const unsigned* __restrict__ alive, const u64* __restrict__ scan2, GcCutOut out, DsCounters* cn) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= o.R) return;
     if (i == 0) {                                                                 // the closing offset, and the totals for the read-back
         const u64 tot = scan2[o.R];
         cn->tot = tot;
-        if ((long long)(unsigned)tot <= out.cap_paths) out.off[(unsigned)tot] = (long long)(tot >> 32);
+        gc_cut_close(out, tot);
     }
     bool start = false;
     if (!ds_kept(o, alive, i, start)) return;
     const long long at = (long long)(scan2[i] >> 32), sid = (long long)(unsigned)scan2[i] - (start ? 0 : 1);
     if (at >= out.cap_pts || sid < 0 || sid >= out.cap_paths) { atomicOr(&cn->bad, DS_BAD_PLACE); return; }
     out.pts[at] = o.pts[i];
-    if (start) {
-        const int path = o.dpath[o.did[i] & ~DS_START];
-        out.off[sid] = at; out.origin[sid] = path;
-        if (out.src_in) out.src[sid] = out.src_in[path];
-    }
+    if (start) gc_cut_start(out, sid, at, o.dpath[o.did[i] & ~DS_START]);
 }
 
 // the pattern table, checked, as prefix sums: hA / hOn, pattern q at pat_off[q] + q
@@ -325,21 +320,14 @@ extern "C" int orip_gcode_dash(orip_ctx* c, const int64_t* off, const int32_t* p
     }
     hipStream_t s = LN(c).stream;
     for (int k = 0; k < ORIP_DASH_STATS; k++) stats[k] = 0;
-    const bool same_count = c->gc_ready && c->gc_n == n;                      // as many as the sources name: taken for the polylines a fetch gave out
-    if (n == 0) {                                                             // nothing to launch; the explicit form leaves the empty list resident
-        if (off) { ORIP_TRY(gc_publish_empty(c, __func__)); if (!same_count) c->gc_merged = true; }
-        c->ds_paths = 0;
-        return 0;
-    }
+    if (n == 0) return gc_cut_empty(c, __func__, c->ds, off != nullptr);
     const size_t Z = (size_t)total, E = hA.size();
     DsLen *len, *X; int *d_pat, *d_poff; u64 *d_ph, *d_A, *d_On, *scans; unsigned* longlist; DsCounters* cn;
     { Carve L; L.each(Z + 1, len, X); L.take(d_pat, (size_t)n); L.take(d_ph, (size_t)n); L.take(d_poff, (size_t)np + 1); L.each(E + 1, d_A, d_On); L.take(scans, 2 * Z + 2);
       L.take(longlist, Z); L.take(cn, 1); HIPC(c, L.commit(c->ds_tmp, 64)); }
     u64 *cs = scans, *scan = scans + Z + 1;
-    c->ds_paths = -1;
-    if (off) ORIP_TRY(gc_steps_upload(c, __func__, off, pts, n, total));      // checked above: from here on the input is the resident list
-    if (off && !same_count) c->gc_merged = true;                              // the sources do not name these polylines
-    const bool sources = !c->gc_merged;                                       // gc_src names the input strokes: gathered through origin below
+    bool sources;
+    ORIP_TRY(gc_cut_intake(c, __func__, c->ds, off, pts, n, total, sources));
     HIPC(c, hipMemcpyAsync(d_pat, pattern, (size_t)n * 4, hipMemcpyHostToDevice, s));
     HIPC(c, hipMemcpyAsync(d_ph, phase, (size_t)n * 8, hipMemcpyHostToDevice, s));
     HIPC(c, hipMemcpyAsync(d_poff, pat_off, ((size_t)np + 1) * 4, hipMemcpyHostToDevice, s));
@@ -353,7 +341,7 @@ extern "C" int orip_gcode_dash(orip_ctx* c, const int64_t* off, const int32_t* p
       HIPC(c, orip_with_tmp(c, [&](void* tmp, size_t& bytes) { return rocprim::exclusive_scan(tmp, bytes, len, X, DsLen{0, 0}, Z + 1, DsAdd(), s); })); }
     { ProfScope ps(c, "ds_count");
       hipLaunchKernelGGL(k_ds_count, gp1, b, 0, s, d_off, n, total, X, T, cs, longlist, cn);
-      HIPC(c, orip_with_tmp(c, [&](void* tmp, size_t& bytes) { return rocprim::exclusive_scan(tmp, bytes, cs, scan, (u64)0, Z + 1, rocprim::plus<u64>(), s); })); }
+      HIPC(c, gc_scan_u64(c, cs, scan, Z + 1)); }
     HIPC(c, hipGetLastError());
     struct { u64 tot; DsCounters cn; } h1;                                    // first read-back: the size of the raw arrays, and what the count found
     HIPC(c, hipMemcpyAsync(&h1.tot, scan + Z, 8, hipMemcpyDeviceToHost, s));
@@ -366,10 +354,9 @@ extern "C" int orip_gcode_dash(orip_ctx* c, const int64_t* off, const int32_t* p
     if (h1.cn.bad || (u64)R != h1.cn.raw_points || Q > R || h1.cn.dashed > (u64)n || h1.cn.length_on > h1.cn.length_in || Q - (n - (int64_t)h1.cn.dashed) != (int64_t)h1.cn.dashes) {
         gc_drop(c); ORIP_FAIL(c, "the count does not add up (internal error %u)", h1.cn.bad);
     }
-    HIPC(c, c->ds_off.ensure(((size_t)Q + 1) * 8 + 64)); HIPC(c, c->ds_pts.ensure((size_t)R * 8 + 64));
-    HIPC(c, c->ds_res.ensure((size_t)Q * 4 + 64)); HIPC(c, c->ds_src.ensure((size_t)Q * 4 + 64));
+    ORIP_TRY(gc_cut_ensure(c, __func__, c->ds, Q, R));
     int64_t paths = 0, points = 0;
-    if (R == 0) HIPC(c, hipMemsetAsync(c->ds_off.p, 0, 8, s));                // every stroke lies in a gap: the list of no polylines
+    if (R == 0) HIPC(c, hipMemsetAsync(c->ds.off.p, 0, 8, s));                // every stroke lies in a gap: the list of no polylines
     else {
         DsRaw o = {nullptr, nullptr, nullptr, R, Q}; unsigned* alive; u64* scans2;
         { Carve L; L.take(o.pts, (size_t)R); L.take(o.did, (size_t)R); L.take(o.dpath, (size_t)Q); L.take(alive, (size_t)Q); L.take(scans2, 2 * (size_t)R + 2);
@@ -384,32 +371,20 @@ extern "C" int orip_gcode_dash(orip_ctx* c, const int64_t* off, const int32_t* p
         { ProfScope ps(c, "ds_compact");
           hipLaunchKernelGGL(k_ds_alive, gr, b, 0, s, o, alive, cn);
           hipLaunchKernelGGL(k_ds_flag, gr1, b, 0, s, o, alive, cs2);
-          HIPC(c, orip_with_tmp(c, [&](void* tmp, size_t& bytes) { return rocprim::exclusive_scan(tmp, bytes, cs2, scan2, (u64)0, (size_t)R + 1, rocprim::plus<u64>(), s); }));
-          const DsOut out = {c->ds_pts.as<int2>(), c->ds_off.as<long long>(), c->ds_res.as<int>(), c->ds_src.as<int>(), sources ? c->gc_src.as<int>() : nullptr, R, Q};
+          HIPC(c, gc_scan_u64(c, cs2, scan2, (size_t)R + 1));
+          const GcCutOut out = gc_cut_out(c, c->ds, sources, R, Q);
           hipLaunchKernelGGL(k_ds_out, gr, b, 0, s, o, alive, scan2, out, cn); }
         HIPC(c, hipGetLastError());
         DsCounters h;                                                         // second read-back: the output's size, and what the emit found
         HIPC(c, hipMemcpyAsync(&h, cn, sizeof(DsCounters), hipMemcpyDeviceToHost, s));
         HIPC(c, hipStreamSynchronize(s));
-        paths = (int64_t)(h.tot & 0xFFFFFFFFu); points = (int64_t)(h.tot >> 32);
+        gc_cut_totals(h.tot, paths, points);
         if (h.bad || paths > Q || points > R || 2 * paths > points) { gc_drop(c); ORIP_FAIL(c, "the dashes do not add up (internal error %u)", h.bad); }
     }
-    gc_publish(c, c->ds_off, c->ds_pts, paths, points);
-    if (sources) gc_publish_src(c, c->ds_src);
-    c->ds_paths = paths;
+    gc_cut_publish(c, c->ds, sources, paths, points);
     stats[0] = n; stats[1] = (int64_t)h1.cn.dashed; stats[2] = (int64_t)h1.cn.dashes; stats[3] = Q - paths; stats[4] = paths; stats[5] = points;
     stats[6] = (int64_t)h1.cn.length_in; stats[7] = (int64_t)h1.cn.length_on;
     return 0;
 }
 
-extern "C" int orip_gcode_dash_fetch(orip_ctx* c, int32_t* origin) {
-    orip_enter(c);
-    ORIP_LANE(c, ORIP_LANE_CROSS);
-    if (c->ds_paths < 0) ORIP_FAIL(c, "no result: orip_gcode_dash has not succeeded since the last failure");
-    if (c->ds_paths == 0) return 0;
-    if (!origin) ORIP_FAIL(c, "bad arguments");
-    hipStream_t s = LN(c).stream;
-    HIPC(c, hipMemcpyAsync(origin, c->ds_res.p, (size_t)c->ds_paths * 4, hipMemcpyDeviceToHost, s));
-    HIPC(c, hipStreamSynchronize(s));
-    return 0;
-}
+extern "C" int orip_gcode_dash_fetch(orip_ctx* c, int32_t* origin) { return gc_cut_fetch(c, __func__, c->ds, "orip_gcode_dash", origin); }

@@ -29,9 +29,8 @@
 //      ballot of the gaps, the pieces numbered by the ballot's prefix count.
 //    32 was chosen by measurement, on a long stroke over 10^5 earlier dashes and on 2 x 10^4 nested segments against a grid of squares; DESIGN 6 "dedup"
 //    has the timings.
-// 6. k_dd_compact, per segment: cs = (points << 32) | strokes started.  A piece starts a stroke unless it is its segment's first, starts at the segment's
-//    first vertex, and the segment before it in the stroke still reaches that vertex.  One 64-bit exclusive scan places the points and numbers the strokes
-//    (the clip's compaction, gcode_clip.hip).  The emit sweep writes every piece where the scan says: points, offsets, origin and the gathered sources.
+// 6. The cutting passes' compaction (gc_cut.h: k_gc_cut_compact, gc_scan_u64) places the points and numbers the strokes; the emit sweep writes every
+//    piece where the scan says (gc_cut_piece): points, offsets, origin and the gathered sources.
 // Everything on the calling lane's stream; one read-back (the counters, the scan's last word among them) and one host synchronisation, behind the last launch.
 //
 // Scratch in c->dd_tmp, free between calls, ONE Carve (orip_gcode_dedup): w0, w1, w2 u64[S]; ka u64[S] and kb u64[max(S, 2 (nb + nsb))], the sort's two key
@@ -39,8 +38,7 @@
 // ulonglong2[S] (lo, hi words by g); sinfo int2[S] (forward, stroke); se ulonglong2[S] (the end words in sorted order); pmax u64[S]; lineid unsigned[S];
 // lists unsigned[2 S + 1] (lstart[S + 1], then the long list); rec unsigned[S] (pieces | long << 29 | first piece starts at the first vertex << 30 | last
 // piece ends at the second << 31; the head flags before that); grp int[n]; scans u64[2 S + 2] (cs, scan); DdCounters.  About 130 bytes per segment.
-// Output: c->dd_off / c->dd_pts, made the resident list when the call succeeds (gc_publish; orip_ctx.h states the contract); c->dd_src, the sources gathered
-// through origin (gc_publish_src).  Resident until the next call: origin int32[dd_paths] in c->dd_res.
+// Output: the record c->dd (gc_cut.h states the frame, orip_ctx.h the contract).
 #include "orip_ctx.h"
 #include "gc_convert.h"
 #include <rocprim/rocprim.hpp>
@@ -53,11 +51,10 @@
 namespace {
 typedef unsigned long long u64;
 constexpr int DD_LONG_BLOCKS = 1024, DD_WAVES = 4;
-constexpr unsigned DD_NP = (1u << 29) - 1, DD_LONG = 1u << 29, DD_FA = 1u << 30, DD_FB = 1u << 31;
+constexpr unsigned DD_NP = GC_CUT_NP, DD_LONG = GC_CUT_OWN, DD_FA = GC_CUT_FA, DD_FB = GC_CUT_FB;        // the pass's own bit: a wave took the segment
 constexpr unsigned DD_BAD_REPEAT = 1, DD_BAD_LINE = 2, DD_BAD_PLACE = 4, DD_BAD_LIST = 8;
 struct DdCounters { u64 whole, cut, covered, pieces, steps_in, steps_out, tot; unsigned n_long, bad; };
 struct DdSum { u64 maxhi; unsigned ming, pad; };                                      // of 64 sorted positions, or of 64 such blocks
-struct DdOut { int2* pts; long long* off; int* origin; int* src; const int* src_in; long long cap_pts, cap_paths; };
 
 __device__ __forceinline__ u64 dd_max(u64 a, u64 b) { return a > b ? a : b; }
 // pen-down steps between two points of one line: max(|dx|, |dy|)
@@ -204,20 +201,10 @@ __device__ __forceinline__ void dd_place(DdSeg& s, const unsigned* __restrict__ 
     s.pbase = scan[s.g] >> 32; s.sbase = (unsigned)scan[s.g];
 }
 // piece u of the segment in tau order, from word a to word b
-__device__ __forceinline__ void dd_emit(const DdSeg& s, unsigned u, u64 a, u64 b, const DdOut& o, DdCounters* cn) {
-    if (u >= s.np_all) { atomicOr(&cn->bad, DD_BAD_PLACE); return; }
-    const unsigned t = s.fwd ? u : s.np_all - 1 - u;                              // its place in drawing order
-    long long at = (long long)s.pbase + (s.cont ? (t ? 2ll * t - 1 : 0) : 2ll * t);
-    const bool starts = !(s.cont && t == 0);
-    const long long sid = (long long)s.sbase + t - (s.cont ? 1 : 0);
-    if (at < 0 || at + (starts ? 2 : 1) > o.cap_pts || (starts && (sid < 0 || sid >= o.cap_paths))) { atomicOr(&cn->bad, DD_BAD_PLACE); return; }
-    if (starts) {
-        o.pts[at] = dd_point(s.fwd ? a : b, s.tx);
-        o.off[sid] = at; o.origin[sid] = s.path;
-        if (o.src_in) o.src[sid] = o.src_in[s.path];
-        at++;
-    }
-    o.pts[at] = dd_point(s.fwd ? b : a, s.tx);
+__device__ __forceinline__ void dd_emit(const DdSeg& s, unsigned u, u64 a, u64 b, const GcCutOut& o, DdCounters* cn) {
+    const unsigned t = s.fwd ? u : s.np_all - 1 - u;                              // its place in drawing order; beyond np_all when u is
+    if (!gc_cut_piece(o, (long long)s.pbase, (long long)s.sbase, s.cont, t, s.np_all, s.path, dd_point(s.fwd ? a : b, s.tx), dd_point(s.fwd ? b : a, s.tx)))
+        atomicOr(&cn->bad, DD_BAD_PLACE);
 }
 __device__ __forceinline__ unsigned dd_record(const DdSeg& s, unsigned np, bool flo, bool fhi) {
     const bool fa = s.fwd ? flo : fhi, fb = s.fwd ? fhi : flo;
@@ -227,7 +214,7 @@ __device__ __forceinline__ unsigned dd_record(const DdSeg& s, unsigned np, bool 
 template <bool EMIT>
 __global__ __launch_bounds__(256) void k_dd_survive(int64_t S, const unsigned* __restrict__ ord, const ulonglong2* __restrict__ se, const u64* __restrict__ reach,
                                                     const unsigned* __restrict__ lineid, const unsigned* __restrict__ lstart, const int2* __restrict__ sinfo, const u64* __restrict__ w1,
-                                                    unsigned* __restrict__ rec, unsigned* __restrict__ longlist, const u64* __restrict__ cs, const u64* __restrict__ scan, DdOut o,
+                                                    unsigned* __restrict__ rec, unsigned* __restrict__ longlist, const u64* __restrict__ cs, const u64* __restrict__ scan, GcCutOut o,
                                                     DdCounters* cn) {
     __shared__ u64 s_cnt[5];                                                      // whole, cut, covered, pieces, steps_out
     if (threadIdx.x < 5) s_cnt[threadIdx.x] = 0;
@@ -236,7 +223,7 @@ __global__ __launch_bounds__(256) void k_dd_survive(int64_t S, const unsigned* _
     if (k < S) {
         if (EMIT && k == 0) {                                                     // the closing offset, and the totals for the one read-back
             cn->tot = scan[S];
-            if ((long long)(unsigned)scan[S] <= o.cap_paths) o.off[(unsigned)scan[S]] = (long long)(scan[S] >> 32);
+            gc_cut_close(o, scan[S]);
         }
         DdSeg s;
         if (!dd_segment(k, S, ord, se, reach, lineid, lstart, sinfo, w1, s)) atomicOr(&cn->bad, DD_BAD_LINE);
@@ -292,7 +279,7 @@ __device__ __forceinline__ u64 dd_wave_prefix_max(u64 v, int lane) {
 template <bool EMIT>
 __global__ __launch_bounds__(256) void k_dd_long(int64_t S, const unsigned* __restrict__ ord, const ulonglong2* __restrict__ se, const u64* __restrict__ reach,
                                                  const unsigned* __restrict__ lineid, const unsigned* __restrict__ lstart, const int2* __restrict__ sinfo, const u64* __restrict__ w1,
-                                                 unsigned* __restrict__ rec, const unsigned* __restrict__ longlist, const u64* __restrict__ cs, const u64* __restrict__ scan, DdOut o,
+                                                 unsigned* __restrict__ rec, const unsigned* __restrict__ longlist, const u64* __restrict__ cs, const u64* __restrict__ scan, GcCutOut o,
                                                  DdCounters* cn) {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const unsigned count = cn->n_long < (unsigned)S ? cn->n_long : (unsigned)S;
@@ -343,22 +330,6 @@ __global__ __launch_bounds__(256) void k_dd_long(int64_t S, const unsigned* __re
     }
 }
 
-// cs[g] = (points << 32) | strokes started; cs[S] = 0
-__global__ __launch_bounds__(256) void k_dd_compact(int64_t S, const unsigned* __restrict__ rec, const int2* __restrict__ sinfo, u64* __restrict__ cs) {
-    const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (g > S) return;
-    u64 out = 0;
-    if (g < S) {
-        const unsigned r = rec[g], np = r & DD_NP;
-        if (np) {
-            bool cont = false;
-            if ((r & DD_FA) && g > 0 && sinfo[g - 1].y == sinfo[g].y) { const unsigned rp = rec[g - 1]; cont = (rp & DD_NP) && (rp & DD_FB); }
-            const unsigned starts = np - (cont ? 1u : 0u);
-            out = ((u64)(np + starts) << 32) | starts;
-        }
-    }
-    cs[g] = out;
-}
 }  // namespace
 
 // include/orip.h states the rule; the surviving strokes become the resident step polylines
@@ -371,12 +342,7 @@ extern "C" int orip_gcode_dedup(orip_ctx* c, const int64_t* off, const int32_t* 
     ORIP_TRY(gc_check_groups(c, __func__, group, n, n_groups, nullptr));
     hipStream_t s = LN(c).stream;
     for (int k = 0; k < 9; k++) stats[k] = 0;
-    const bool same_count = c->gc_ready && c->gc_n == n;                      // as many as the sources name: taken for the polylines a fetch gave out
-    if (n == 0) {                                                             // nothing to launch; the explicit form leaves the empty list resident
-        if (off) { ORIP_TRY(gc_publish_empty(c, __func__)); if (!same_count) c->gc_merged = true; }
-        c->dd_paths = 0;
-        return 0;
-    }
+    if (n == 0) return gc_cut_empty(c, __func__, c->dd, off != nullptr);
     const int64_t S = total - n;                                              // segments: every path has two points or more, so n <= S
     const size_t Z = (size_t)S;
     const int64_t nb = (S + 63) / 64, nsb = (nb + 63) / 64;                   // blocks of 64 sorted positions, and of 64 blocks
@@ -385,12 +351,9 @@ extern "C" int orip_gcode_dedup(orip_ctx* c, const int64_t* off, const int32_t* 
       L.take(rec, Z); L.take(grp, (size_t)n); L.take(scans, 2 * Z + 2); L.take(cn, 1); HIPC(c, L.commit(c->dd_tmp, 64)); }
     unsigned *ia = idx, *ib = idx + Z, *lstart = lists, *longlist = lists + Z + 1; u64 *cs = scans, *scan = scans + Z + 1;
     const long long cap_paths = 2 * S, cap_pts = 4 * S;                       // pieces <= 2 segments: an end point cuts one later segment at most
-    HIPC(c, c->dd_off.ensure(((size_t)cap_paths + 1) * 8 + 64)); HIPC(c, c->dd_pts.ensure((size_t)cap_pts * 8 + 64));
-    HIPC(c, c->dd_res.ensure((size_t)cap_paths * 4 + 64)); HIPC(c, c->dd_src.ensure((size_t)cap_paths * 4 + 64));
-    c->dd_paths = -1;
-    if (off) ORIP_TRY(gc_steps_upload(c, __func__, off, pts, n, total));      // checked above: from here on the input is the resident list
-    if (off && !same_count) c->gc_merged = true;                              // the sources do not name these polylines
-    const bool sources = !c->gc_merged;                                       // gc_src names the input strokes: gathered through origin below
+    ORIP_TRY(gc_cut_ensure(c, __func__, c->dd, cap_paths, cap_pts));
+    bool sources;
+    ORIP_TRY(gc_cut_intake(c, __func__, c->dd, off, pts, n, total, sources));
     if (group) HIPC(c, hipMemcpyAsync(grp, group, (size_t)n * 4, hipMemcpyHostToDevice, s));
     else HIPC(c, hipMemsetAsync(grp, 0, (size_t)n * 4, s));
     HIPC(c, hipMemsetAsync(cn, 0, sizeof(DdCounters), s));
@@ -417,13 +380,13 @@ extern "C" int orip_gcode_dedup(orip_ctx* c, const int64_t* off, const int32_t* 
       hipLaunchKernelGGL(k_dd_blocks, dim3(cdiv(nb, 256)), b, 0, s, S, ord, se, sum, nb);
       hipLaunchKernelGGL(k_dd_superblocks, dim3(cdiv(nsb, 256)), b, 0, s, sum, nb, nsb);
       hipLaunchKernelGGL(k_dd_reach, gs, b, 0, s, S, ord, se, pmax, lineid, lstart, sum, nb, reach, cn); }
-    DdOut o = {c->dd_pts.as<int2>(), c->dd_off.as<long long>(), c->dd_res.as<int>(), c->dd_src.as<int>(), sources ? c->gc_src.as<int>() : nullptr, cap_pts, cap_paths};
+    const GcCutOut o = gc_cut_out(c, c->dd, sources, cap_pts, cap_paths);
     { ProfScope ps(c, "dd_survive");
       hipLaunchKernelGGL(k_dd_survive<false>, gs, b, 0, s, S, ord, se, reach, lineid, lstart, sinfo, w1, rec, longlist, cs, scan, o, cn);
       hipLaunchKernelGGL(k_dd_long<false>, dim3(DD_LONG_BLOCKS), b, 0, s, S, ord, se, reach, lineid, lstart, sinfo, w1, rec, longlist, cs, scan, o, cn); }
     { ProfScope ps(c, "dd_compact");
-      hipLaunchKernelGGL(k_dd_compact, gs1, b, 0, s, S, rec, sinfo, cs);
-      HIPC(c, orip_with_tmp(c, [&](void* tmp, size_t& bytes) { return rocprim::exclusive_scan(tmp, bytes, cs, scan, (u64)0, Z + 1, rocprim::plus<u64>(), s); })); }
+      hipLaunchKernelGGL(k_gc_cut_compact, gs1, b, 0, s, S, rec, sinfo, cs);
+      HIPC(c, gc_scan_u64(c, cs, scan, Z + 1)); }
     { ProfScope ps(c, "dd_emit");
       hipLaunchKernelGGL(k_dd_survive<true>, gs, b, 0, s, S, ord, se, reach, lineid, lstart, sinfo, w1, rec, longlist, cs, scan, o, cn);
       hipLaunchKernelGGL(k_dd_long<true>, dim3(DD_LONG_BLOCKS), b, 0, s, S, ord, se, reach, lineid, lstart, sinfo, w1, rec, longlist, cs, scan, o, cn); }
@@ -431,28 +394,17 @@ extern "C" int orip_gcode_dedup(orip_ctx* c, const int64_t* off, const int32_t* 
     DdCounters h;                                                             // the emit pass adds to nothing but `bad` and `tot`
     HIPC(c, hipMemcpyAsync(&h, cn, sizeof(DdCounters), hipMemcpyDeviceToHost, s));
     HIPC(c, hipStreamSynchronize(s));                                         // the one read-back and the one sync, behind the last launch
-    const int64_t paths = (int64_t)(h.tot & 0xFFFFFFFFu), points = (int64_t)(h.tot >> 32);
+    int64_t paths, points;
+    gc_cut_totals(h.tot, paths, points);
     if (h.bad & DD_BAD_REPEAT) { gc_drop(c); ORIP_FAIL(c, "a resident polyline holds a point equal to the one before it"); }
     if (h.bad || h.whole + h.cut + h.covered != (u64)S || h.pieces > 2 * (u64)S || paths < 1 || paths > (int64_t)h.pieces || points != (int64_t)h.pieces + paths ||
         h.steps_out > h.steps_in) {
         gc_drop(c); ORIP_FAIL(c, "the pieces do not add up (internal error %u)", h.bad);
     }
-    gc_publish(c, c->dd_off, c->dd_pts, paths, points);
-    if (sources) gc_publish_src(c, c->dd_src);
-    c->dd_paths = paths;
+    gc_cut_publish(c, c->dd, sources, paths, points);
     stats[0] = S; stats[1] = (int64_t)h.whole; stats[2] = (int64_t)h.cut; stats[3] = (int64_t)h.covered; stats[4] = (int64_t)h.pieces; stats[5] = paths; stats[6] = points;
     stats[7] = (int64_t)h.steps_in; stats[8] = (int64_t)h.steps_out;
     return 0;
 }
 
-extern "C" int orip_gcode_dedup_fetch(orip_ctx* c, int32_t* origin) {
-    orip_enter(c);
-    ORIP_LANE(c, ORIP_LANE_CROSS);
-    if (c->dd_paths < 0) ORIP_FAIL(c, "no result: orip_gcode_dedup has not succeeded since the last failure");
-    if (c->dd_paths == 0) return 0;
-    if (!origin) ORIP_FAIL(c, "bad arguments");
-    hipStream_t s = LN(c).stream;
-    HIPC(c, hipMemcpyAsync(origin, c->dd_res.p, (size_t)c->dd_paths * 4, hipMemcpyDeviceToHost, s));
-    HIPC(c, hipStreamSynchronize(s));
-    return 0;
-}
+extern "C" int orip_gcode_dedup_fetch(orip_ctx* c, int32_t* origin) { return gc_cut_fetch(c, __func__, c->dd, "orip_gcode_dedup", origin); }

@@ -27,8 +27,8 @@
 //      merge: a visible point of no length is not a piece.  Piece ends are rounded (oc_point) and the kept pieces are written in order.
 //    Ranking by walking is quadratic in the events of one (segment, shape) and in the intervals of one segment, shared by 64 lanes; it needs no bound on
 //    either, so a comb of any number of teeth and a shape of any number of edges take the same path as a square.
-// 5. k_oc_compact and one 64-bit scan as in the dedup: cs = (points << 32) | strokes started.  The host reads the totals (second read-back), refuses
-//    2^30 points, sizes the output, and k_oc_emit, one thread per segment, copies the pieces to where the scan says, with origin and the gathered sources.
+// 5. The cutting passes' compaction (gc_cut.h: k_gc_cut_compact, gc_scan_u64).  The host reads the totals (second read-back), refuses 2^30 points, sizes
+//    the output, and k_oc_emit, one thread per segment, copies the pieces to where the scan says (gc_cut_piece), with origin and the gathered sources.
 // Everything on the calling lane's stream; a third read-back fetches the counters behind the last launch.
 //
 // Scratch, free between calls.  c->oc_tmp, ONE Carve (oc_core): lvl int[n]; roff long long[m + 1]; rsub int[m]; rpts int2[R]; edges int4[R]; spt long
@@ -37,10 +37,9 @@
 // per segment, their scan); scans u64[2 S + 2] (cs, scan); OcCounters.  c->oc_ev, one Carve behind the first read-back, E = all events: ev_t ulonglong2[E]
 // and ev_k int[E] (the events), so_t ulonglong2[E] and so_h int[E] (ranked, with the state behind), iv_s and iv_e ulonglong2[E] (the hidden stretches).
 // Ranked intervals reuse ev_t / so_t, the pieces (int4) reuse iv_s: a segment with K events has at most K - 1 stretches and K pieces.  72 bytes an event.
-// Output: c->oc_off / c->oc_pts, made the resident list when the call succeeds (gc_publish); c->oc_src (gc_publish_src); origin int32[oc_paths] in c->oc_res.
+// Output: the record c->oc (gc_cut.h states the frame, orip_ctx.h the contract).
 #include "orip_ctx.h"
 #include "gc_convert.h"
-#include <rocprim/rocprim.hpp>
 #include <algorithm>
 #include <climits>
 #include <vector>
@@ -50,11 +49,10 @@ typedef unsigned long long u64;
 typedef __int128 i128;
 typedef unsigned __int128 u128;
 constexpr int OC_BLOCKS = 4096;                                                       // one wave each; they stride over the work list
-constexpr unsigned OC_NP = (1u << 29) - 1, OC_WHOLE = 1u << 29, OC_FA = 1u << 30, OC_FB = 1u << 31;
+constexpr unsigned OC_NP = GC_CUT_NP, OC_WHOLE = GC_CUT_OWN, OC_FA = GC_CUT_FA, OC_FB = GC_CUT_FB;       // the pass's own bit: the segment is whole
 constexpr unsigned OC_BAD_REPEAT = 1, OC_BAD_PLACE = 2, OC_BAD_LIST = 4, OC_BAD_COUNT = 8, OC_BAD_NOT_FINITE = 16, OC_BAD_RANGE = 32;
 struct OcCounters { u64 whole, cut, hidden, pieces, collapsed, steps_in, steps_out; unsigned n_work, bad; };
 struct OcShapes { const long long* spt; const int* slevel; const int4* sbox; const int4* edges; int64_t ns; };
-struct OcOut { int2* pts; long long* off; int* origin; int* src; const int* src_in; long long cap_pts, cap_paths; };
 struct OcSeg { int2 A, B; long long dx, dy; bool xdom; };
 
 __device__ __forceinline__ bool oc_lt(const ulonglong2 a, const ulonglong2 b) { return (u128)a.x * b.y < (u128)b.x * a.y; }
@@ -330,30 +328,14 @@ __global__ __launch_bounds__(64) void k_oc_pieces(int64_t n, const int2* __restr
     }
 }
 
-// cs[g] = (points << 32) | strokes started; cs[S] = 0
-__global__ __launch_bounds__(256) void k_oc_compact(int64_t S, const unsigned* __restrict__ rec, const int2* __restrict__ sinfo, u64* __restrict__ cs) {
-    const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (g > S) return;
-    u64 out = 0;
-    if (g < S) {
-        const unsigned r = rec[g], nk = r & OC_NP;
-        if (nk) {
-            bool cont = false;
-            if ((r & OC_FA) && g > 0 && sinfo[g - 1].y == sinfo[g].y) { const unsigned rp = rec[g - 1]; cont = (rp & OC_NP) && (rp & OC_FB); }
-            const unsigned starts = nk - (cont ? 1u : 0u);
-            out = ((u64)(nk + starts) << 32) | starts;
-        }
-    }
-    cs[g] = out;
-}
 __global__ __launch_bounds__(256) void k_oc_emit(int64_t S, int64_t total, int64_t n, const int2* __restrict__ pts, const unsigned* __restrict__ rec, const int2* __restrict__ sinfo,
-                                                 const u64* __restrict__ cs, const u64* __restrict__ scan, const u64* __restrict__ evbase, const int4* __restrict__ pc, u64 E, OcOut o,
+                                                 const u64* __restrict__ cs, const u64* __restrict__ scan, const u64* __restrict__ evbase, const int4* __restrict__ pc, u64 E, GcCutOut o,
                                                  OcCounters* cn) {
     __shared__ u64 s_steps;
     if (threadIdx.x == 0) s_steps = 0;
     __syncthreads();
     const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (g == 0 && (long long)(unsigned)scan[S] <= o.cap_paths) o.off[(unsigned)scan[S]] = (long long)(scan[S] >> 32);
+    if (g == 0) gc_cut_close(o, scan[S]);
     if (g < S) {
         const unsigned r = rec[g], nk = r & OC_NP;
         const int2 si = sinfo[g];
@@ -364,17 +346,7 @@ __global__ __launch_bounds__(256) void k_oc_emit(int64_t S, int64_t total, int64
             u64 steps = 0;
             for (unsigned t = 0; t < nk; t++) {
                 const int4 pq = (r & OC_WHOLE) ? make_int4(pts[si.x - 1].x, pts[si.x - 1].y, pts[si.x].x, pts[si.x].y) : pc[evbase[g] + t];
-                long long at = pbase + (cont ? (t ? 2ll * t - 1 : 0) : 2ll * t);
-                const bool starts = !(cont && t == 0);
-                const long long sid = sbase + t - (cont ? 1 : 0);
-                if (at < 0 || at + (starts ? 2 : 1) > o.cap_pts || (starts && (sid < 0 || sid >= o.cap_paths))) { atomicOr(&cn->bad, OC_BAD_PLACE); break; }
-                if (starts) {
-                    o.pts[at] = make_int2(pq.x, pq.y);
-                    o.off[sid] = at; o.origin[sid] = si.y;
-                    if (o.src_in) o.src[sid] = o.src_in[si.y];
-                    at++;
-                }
-                o.pts[at] = make_int2(pq.z, pq.w);
+                if (!gc_cut_piece(o, pbase, sbase, cont, t, nk, si.y, make_int2(pq.x, pq.y), make_int2(pq.z, pq.w))) { atomicOr(&cn->bad, OC_BAD_PLACE); break; }
                 if (r & OC_WHOLE) steps += oc_steps(make_int2(pq.x, pq.y), make_int2(pq.z, pq.w));
             }
             if (steps) atomicAdd(&s_steps, steps);
@@ -432,12 +404,7 @@ int oc_core(orip_ctx* c, const char* who, const int64_t* up_off, const int32_t* 
     spt.push_back(R);
 
     for (int k = 0; k < ORIP_OCCLUDE_STATS; k++) stats[k] = 0;
-    const bool same_count = c->gc_ready && c->gc_n == n;                      // as many as the sources name: taken for the polylines a fetch gave out
-    if (n == 0) {                                                             // nothing to launch; the explicit form leaves the empty list resident
-        if (up_off) { ORIP_TRY(gc_publish_empty(c, who)); if (!same_count) c->gc_merged = true; }
-        c->oc_paths = 0;
-        return 0;
-    }
+    if (n == 0) return gc_cut_empty(c, who, c->oc, up_off != nullptr);
     const int64_t S = total - n;
     const size_t Z = (size_t)S;
     int *lvl, *rsub, *d_slevel; long long *d_roff, *d_spt; int2 *rpts, *sinfo; int4 *edges, *sbox; unsigned *rec, *work; u64 *evs, *scans; OcCounters* cn;
@@ -445,10 +412,8 @@ int oc_core(orip_ctx* c, const char* who, const int64_t* up_off, const int32_t* 
       L.take(d_slevel, (size_t)ns); L.take(sbox, (size_t)ns); L.take(sinfo, Z); L.take(rec, Z); L.take(work, Z); L.take(evs, 2 * Z + 2); L.take(scans, 2 * Z + 2); L.take(cn, 1);
       HIPC_AS(c, who, L.commit(c->oc_tmp, 64)); }
     u64 *evcnt = evs, *evbase = evs + Z + 1, *cs = scans, *scan = scans + Z + 1;
-    c->oc_paths = -1;
-    if (up_off) ORIP_TRY(gc_steps_upload(c, who, up_off, up_pts, n, total));  // checked: from here on the input is the resident list
-    if (up_off && !same_count) c->gc_merged = true;                           // the sources do not name these polylines
-    const bool sources = !c->gc_merged;
+    bool sources;
+    ORIP_TRY(gc_cut_intake(c, who, c->oc, up_off, up_pts, n, total, sources));
     HIPC_AS(c, who, hipMemcpyAsync(lvl, level, (size_t)n * 4, hipMemcpyHostToDevice, s));
     HIPC_AS(c, who, hipMemcpyAsync(d_roff, roff.data(), ((size_t)m + 1) * 8, hipMemcpyHostToDevice, s));
     HIPC_AS(c, who, hipMemcpyAsync(d_spt, spt.data(), ((size_t)ns + 1) * 8, hipMemcpyHostToDevice, s));
@@ -470,7 +435,7 @@ int oc_core(orip_ctx* c, const char* who, const int64_t* up_off, const int32_t* 
       hipLaunchKernelGGL(k_oc_cand, dim3(cdiv(total, 256)), b, 0, s, d_off, n, d_pts, total, lvl, sh, sinfo, rec, work, evcnt, cn); }
     { ProfScope ps(c, "oc_count");
       hipLaunchKernelGGL(k_oc_count, dim3(wblocks), dim3(64), 0, s, n, d_pts, total, lvl, sh, sinfo, work, evcnt, cn);
-      HIPC_AS(c, who, orip_with_tmp(c, [&](void* tmp, size_t& bytes) { return rocprim::exclusive_scan(tmp, bytes, evcnt, evbase, (u64)0, Z + 1, rocprim::plus<u64>(), s); })); }
+      HIPC_AS(c, who, gc_scan_u64(c, evcnt, evbase, Z + 1)); }
     HIPC_AS(c, who, hipGetLastError());
     struct { u64 E; OcCounters cn; } h1;                                      // first read-back: the events, and what the conversion of the rings found
     HIPC_AS(c, who, hipMemcpyAsync(&h1.E, evbase + Z, 8, hipMemcpyDeviceToHost, s));
@@ -487,17 +452,17 @@ int oc_core(orip_ctx* c, const char* who, const int64_t* up_off, const int32_t* 
     if (h1.cn.n_work) { ProfScope ps(c, "oc_pieces");                         // a listed segment without an event is whole: the same kernel says so
       hipLaunchKernelGGL(k_oc_pieces, dim3(wblocks), dim3(64), 0, s, n, d_pts, total, lvl, sh, sinfo, work, evcnt, evbase, ev, rec, cn); }
     { ProfScope ps(c, "oc_compact");
-      hipLaunchKernelGGL(k_oc_compact, gs1, b, 0, s, S, rec, sinfo, cs);
-      HIPC_AS(c, who, orip_with_tmp(c, [&](void* tmp, size_t& bytes) { return rocprim::exclusive_scan(tmp, bytes, cs, scan, (u64)0, Z + 1, rocprim::plus<u64>(), s); })); }
+      hipLaunchKernelGGL(k_gc_cut_compact, gs1, b, 0, s, S, rec, sinfo, cs);
+      HIPC_AS(c, who, gc_scan_u64(c, cs, scan, Z + 1)); }
     HIPC_AS(c, who, hipGetLastError());
     u64 tot = 0;                                                              // second read-back: the size of the output
     HIPC_AS(c, who, hipMemcpyAsync(&tot, scan + Z, 8, hipMemcpyDeviceToHost, s));
     HIPC_AS(c, who, hipStreamSynchronize(s));
-    const int64_t paths = (int64_t)(tot & 0xFFFFFFFFu), points = (int64_t)(tot >> 32);
+    int64_t paths, points;
+    gc_cut_totals(tot, paths, points);
     if (points >= (int64_t)1 << 30) { gc_drop(c); ORIP_FAIL_AS(c, who, "%lld output points: fewer than 2^30", (long long)points); }
-    HIPC_AS(c, who, c->oc_off.ensure(((size_t)paths + 1) * 8 + 64)); HIPC_AS(c, who, c->oc_pts.ensure((size_t)points * 8 + 64));
-    HIPC_AS(c, who, c->oc_res.ensure((size_t)paths * 4 + 64)); HIPC_AS(c, who, c->oc_src.ensure((size_t)paths * 4 + 64));
-    OcOut o = {c->oc_pts.as<int2>(), c->oc_off.as<long long>(), c->oc_res.as<int>(), c->oc_src.as<int>(), sources ? c->gc_src.as<int>() : nullptr, points, paths};
+    ORIP_TRY(gc_cut_ensure(c, who, c->oc, paths, points));
+    const GcCutOut o = gc_cut_out(c, c->oc, sources, points, paths);
     { ProfScope ps(c, "oc_emit");
       hipLaunchKernelGGL(k_oc_emit, gs1, b, 0, s, S, total, n, d_pts, rec, sinfo, cs, scan, evbase, (const int4*)ev.iv_s, E, o, cn); }
     HIPC_AS(c, who, hipGetLastError());
@@ -508,9 +473,7 @@ int oc_core(orip_ctx* c, const char* who, const int64_t* up_off, const int32_t* 
     if (h.bad || h.whole + h.cut + h.hidden != (u64)S || pieces < h.collapsed || (int64_t)(pieces - h.collapsed) != points - paths || 2 * paths > points) {
         gc_drop(c); ORIP_FAIL_AS(c, who, "the pieces do not add up (internal error %u)", h.bad);
     }
-    gc_publish(c, c->oc_off, c->oc_pts, paths, points);                       // everything hidden: the list of no polylines
-    if (sources) gc_publish_src(c, c->oc_src);
-    c->oc_paths = paths;
+    gc_cut_publish(c, c->oc, sources, paths, points);                         // everything hidden: the list of no polylines
     stats[0] = S; stats[1] = (int64_t)h.whole; stats[2] = (int64_t)h.cut; stats[3] = (int64_t)h.hidden; stats[4] = (int64_t)pieces; stats[5] = (int64_t)h.collapsed;
     stats[6] = paths; stats[7] = points; stats[8] = (int64_t)h.steps_in; stats[9] = (int64_t)h.steps_out;
     return 0;
@@ -543,14 +506,4 @@ extern "C" int orip_svg_occlude(orip_ctx* c, const int32_t* level, int64_t n, co
     return oc_core(c, __func__, nullptr, nullptr, level, n, total, rg, stats);
 }
 
-extern "C" int orip_gcode_occlude_fetch(orip_ctx* c, int32_t* origin) {
-    orip_enter(c);
-    ORIP_LANE(c, ORIP_LANE_CROSS);
-    if (c->oc_paths < 0) ORIP_FAIL(c, "no result: the occlusion has not succeeded since the last failure");
-    if (c->oc_paths == 0) return 0;
-    if (!origin) ORIP_FAIL(c, "bad arguments");
-    hipStream_t s = LN(c).stream;
-    HIPC(c, hipMemcpyAsync(origin, c->oc_res.p, (size_t)c->oc_paths * 4, hipMemcpyDeviceToHost, s));
-    HIPC(c, hipStreamSynchronize(s));
-    return 0;
-}
+extern "C" int orip_gcode_occlude_fetch(orip_ctx* c, int32_t* origin) { return gc_cut_fetch(c, __func__, c->oc, "the occlusion", origin); }

@@ -97,8 +97,8 @@ extern "C" void orip_destroy(orip_ctx* c) {
     c->mg_tab.release(); c->mg_tmp.release(); c->mg_off.release(); c->mg_pts.release(); c->mg_res.release();
     c->im_state.release(); c->im_rec.release(); c->sm_state.release(); c->sm_in.release(); c->sm_f.release();
     c->sp_tmp.release(); c->sp_off.release(); c->sp_pts.release(); c->sp_res.release();
-    c->dd_tmp.release(); c->dd_off.release(); c->dd_pts.release(); c->dd_src.release(); c->dd_res.release();
-    c->oc_tmp.release(); c->oc_ev.release(); c->oc_off.release(); c->oc_pts.release(); c->oc_src.release(); c->oc_res.release();
+    c->dd_tmp.release(); c->oc_tmp.release(); c->oc_ev.release(); c->ds_tmp.release(); c->ds_raw.release();
+    c->dd.release(); c->oc.release(); c->ds.release();
     c->sv_tmp.release(); c->sv_tmp2.release(); c->sv_off.release(); c->sv_pts.release(); c->ht_pts.release(); c->ht_rows.release(); c->ht_x.release();
     c->an_table.release(); c->an_keys.release(); c->an_counts.release(); c->an_tmp.release(); c->an_km.release();
     c->resize_src.release(); c->resize_dst.release();

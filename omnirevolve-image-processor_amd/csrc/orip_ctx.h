@@ -76,7 +76,7 @@ struct DBuf {
     void release() { if (p) hipFree(p); p = nullptr; cap = 0; }
     template <class T> T* as() const { return (T*)p; }
 };
-
+#include "gc_cut.h"             // GcCut, the result record of a cutting pass, made of DBufs; and what the three passes share
 // Device polyline list: off int64[n+1], pts int32[2*total].
 // A list can also be WALK-CODED (virt): its points are not stored but generated from the walk records stage 04 leaves for the layer
 // (WalkStore below: own points, bounce tails as (log range, cycle) pieces) through a view per polyline (walk, first point, length,
@@ -284,14 +284,16 @@ struct LaneGuard {
     LaneGuard(orip_ctx* ctx, int lane_id);
     ~LaneGuard();
 };
-#define ORIP_LANE_NODRAIN(ctx, lane_id)                                                                                      \
+#define ORIP_LANE_NODRAIN_AS(ctx, who, lane_id)                                                                              \
     LaneGuard _lane_guard((ctx), (lane_id));                                                                                 \
-    if (!_lane_guard.ok) ORIP_FAIL(ctx, "lane %d is busy: another call is using this layer's stream and scratch", (int)(lane_id))
+    if (!_lane_guard.ok) ORIP_FAIL_AS(ctx, who, "lane %d is busy: another call is using this layer's stream and scratch", (int)(lane_id))
+#define ORIP_LANE_NODRAIN(ctx, lane_id) ORIP_LANE_NODRAIN_AS(ctx, __func__, lane_id)
 // Stage 08's prefetch (vector08a.hip: orip_prefetch08) may still be running on the lane's side stream when stage 07 returns: stage 08 waits for its parts where it
 // consumes them; every other call that claims the lane puts its main stream behind the whole of it first (it reads the scaled list and the lane's scratch).
-#define ORIP_LANE(ctx, lane_id)                                                                                              \
-    ORIP_LANE_NODRAIN(ctx, lane_id);                                                                                         \
-    HIPC(ctx, orip_pf08_drain(ctx))
+#define ORIP_LANE_AS(ctx, who, lane_id)                                                                                      \
+    ORIP_LANE_NODRAIN_AS(ctx, who, lane_id);                                                                                 \
+    HIPC_AS(ctx, who, orip_pf08_drain(ctx))
+#define ORIP_LANE(ctx, lane_id) ORIP_LANE_AS(ctx, __func__, lane_id)
 
 struct orip_ctx {
     int device = 0;
@@ -354,20 +356,18 @@ struct orip_ctx {
     //     orip_gcode_simplify       as the merge, with sp_off / sp_pts, but strokes keep their number and order, so gc_merged is left as it is -- except that
     //                               an explicit input of another count than the resident one (or with no list resident) cannot be the polylines the sources
     //                               name: then, n == 0 included, gc_merged is set.  An explicit input of the resident count is taken for the polylines a fetch gave out.
-    //     orip_gcode_dedup          as the simplify, with dd_off / dd_pts and the same rule for an explicit input and gc_merged; but strokes are cut and vanish, so
-    //                               while !gc_merged the sources are gathered through origin and swapped in with the list (gc_publish_src, dd_src): gc_src keeps
-    //                               naming the input path of every stroke, with repeats as after the clip.  A device-found error (a repeated point in the
-    //                               resident list, pieces that do not add up) leaves no list.
-    //     orip_gcode_occlude, orip_svg_occlude   as the dedup, with oc_off / oc_pts / oc_src and the same rule for an explicit input and gc_merged: checks
-    //                               first (strokes, levels, rings: an argument error leaves the list as it was); n == 0 leaves the empty list (explicit form) or
-    //                               the resident one, which is empty; success swaps the pieces in and, while !gc_merged, the sources gathered through origin.
-    //                               A device-found error (a ring coordinate not finite or out of range, a repeated point in the resident list, 2^30
-    //                               output points or more, pieces that do not add up) leaves no list.
-    //     orip_gcode_dash           as the dedup, with ds_off / ds_pts / ds_src and the same rule for an explicit input and gc_merged: checks first (strokes,
-    //                               patterns, phases: an argument error leaves the list as it was); success swaps the dashes in, the list of no polylines
-    //                               when every stroke lies in a gap, and, while !gc_merged, the sources gathered through origin.  A device-found error (a
-    //                               repeated point in the resident list, a dashed stroke of 2^62 units or more, 2^30 output points or more, counts that do
-    //                               not add up) leaves no list.
+    //     THE CUTTING PASSES: orip_gcode_dedup (record dd), orip_gcode_occlude and orip_svg_occlude (oc), orip_gcode_dash (ds); gc_cut.h holds their
+    //                               frame.  As the simplify, with the record's off / pts and the same rule for an explicit input and gc_merged: every check
+    //                               of the arguments first (an argument error leaves the list as it was); n == 0 leaves the empty list (explicit form) or the
+    //                               resident one, which is empty.  But strokes are cut and vanish, so while !gc_merged the sources are gathered through
+    //                               origin and swapped in with the list (gc_cut_publish, the record's src): gc_src keeps naming the input path of every
+    //                               stroke, with repeats as after the clip.  A device-found error (a repeated point in the resident list, 2^30 output
+    //                               points or more, counts that do not add up; below, what a pass adds) leaves no list.  Particular to a pass:
+    //       the occlusion           two entry points, explicit rings in steps or the resident fitted paths, behind their own checks of the strokes and one
+    //                               body; it sizes its events and then its output by read-backs of their own, and a ring coordinate that is not finite or
+    //                               out of range is a device-found error of the first.
+    //       the dash                sizes its raw arrays by a read-back; when every stroke lies in a gap it launches nothing more and leaves the list of
+    //                               no polylines; a dashed stroke of 2^62 units or more is a device-found error.
     //   A failed HIP call inside a writer leaves what had been written up to it; gc_ready is false across an upload, so a list is never half there.
     DBuf gc_tmp, gc_off, gc_pts, gc_src, pk_tab, pk_out; int64_t gc_n = 0, gc_total = 0, pk_bytes = -1; bool gc_ready = false;
     // orip_gcode_order and orip_gcode_order_pens (gcode_order.hip: gc_grids), free between calls.  With n paths in G groups, m = n or 2n candidates (both ends
@@ -393,19 +393,15 @@ struct orip_ctx {
     // output point of the last call (-1: none) until the next one
     DBuf sp_tmp, sp_off, sp_pts, sp_res; int64_t sp_points = -1;
     // --dedup (gcode_dedup.hip): dd_tmp = the sort words, the sorted intervals, the per-segment records and the scans, free between calls (the unit states the
-    // layout); dd_off / dd_pts = the output, swapped with gc_off / gc_pts when a call succeeds, dd_src = the gathered sources, swapped with gc_src then;
-    // dd_res = origin int32[dd_paths], the input stroke of every output stroke of the last call (-1: none) until the next one
-    DBuf dd_tmp, dd_off, dd_pts, dd_src, dd_res; int64_t dd_paths = -1;
+    // layout); dd = the result record (gc_cut.h: GcCut states what it holds and for how long, for all three cutting passes)
+    DBuf dd_tmp; GcCut dd;
     // --occlude (gcode_occlude.hip): oc_tmp = the levels, the rings and their edges, the shapes' tables, the per-segment records and the scans; oc_ev = the
-    // events, the hidden intervals and the pieces of the segments that meet a shape (the unit states both layouts), free between calls; oc_off / oc_pts =
-    // the output, swapped with gc_off / gc_pts when a call succeeds, oc_src = the gathered sources, swapped with gc_src then; oc_res = origin
-    // int32[oc_paths], the input stroke of every output stroke of the last call (-1: none) until the next one
-    DBuf oc_tmp, oc_ev, oc_off, oc_pts, oc_src, oc_res; int64_t oc_paths = -1;
+    // events, the hidden intervals and the pieces of the segments that meet a shape (the unit states both layouts), free between calls; oc = the result record
+    DBuf oc_tmp, oc_ev; GcCut oc;
     // --dashes / --dash-mm (gcode_dash.hip): ds_tmp = the lengths and their scan, the patterns' tables, the per-segment counts and their scan, the list of
     // the segments a wave takes; ds_raw = the points and dashes before the repeated points and the collapsed dashes are taken out (the unit states both
-    // layouts), free between calls; ds_off / ds_pts = the output, swapped with gc_off / gc_pts when a call succeeds, ds_src = the gathered sources, swapped
-    // with gc_src then; ds_res = origin int32[ds_paths], the input stroke of every output stroke of the last call (-1: none) until the next one
-    DBuf ds_tmp, ds_raw, ds_off, ds_pts, ds_src, ds_res; int64_t ds_paths = -1;
+    // layouts), free between calls; ds = the result record
+    DBuf ds_tmp, ds_raw; GcCut ds;
     // svg2stream (svg.hip): scratch of the flattening and of the box, the resident paths (off int64[sv_n + 1], pts double2[sv_total]; raw units after
     // orip_svg_flatten, page mm after orip_svg_fit) until the next flatten; orip_gcode_to_steps reads them when it is called without pointers
     DBuf sv_tmp, sv_tmp2, sv_off, sv_pts; int64_t sv_n = 0, sv_total = 0; bool sv_ready = false, sv_box_ok = false; double sv_box[4] = {0, 0, 0, 0};

@@ -52,6 +52,19 @@ def _step_paths(off, pts, n):
     return _p(o), _p(p), len(o) - 1, (o, p)
 
 
+def _groups(group, n):
+    """(group int32 [n] or None = all 0, n) of a call that takes one group per path; n: the count _step_paths found, or None when only the groups tell it"""
+    g = None
+    if group is not None:
+        g = np.ascontiguousarray(group, np.int32).reshape(-1)
+        n = len(g) if n is None else n
+        if len(g) != n:
+            raise ValueError(f"{len(g)} groups given for {n} paths")
+    if n is None:
+        raise ValueError("n: the number of resident step polylines")
+    return g, int(n)
+
+
 def _start_xy(start) -> np.ndarray:
     st = np.asarray(start, np.int64).reshape(-1)
     if len(st) != 2 or (st < 0).any() or (st > 1 << 30).any():
@@ -541,15 +554,7 @@ class Device:
         meet end to end inside a group become one stroke, and the merged polylines become the resident ones.  group int32 [n] or None (all 0).
         -> (off int64, pts int32 [total', 2], member_off int64 [paths_out + 1], member int32 [n], rev bool [n], {"paths_out", "points_out", "joins", "cycles"})"""
         po, pp, n, _keep = _step_paths(off, pts, n)
-        g = None
-        if group is not None:
-            g = np.ascontiguousarray(group, np.int32).reshape(-1)
-            n = len(g) if n is None else n
-            if len(g) != n:
-                raise ValueError(f"{len(g)} groups given for {n} paths")
-        if n is None:
-            raise ValueError("n: the number of resident step polylines")
-        n = int(n)
+        g, n = _groups(group, n)
         st = np.zeros(4, np.int64)
         self._ck(self.L.orip_gcode_merge(self.h, po, pp, _p(g) if g is not None and n else None, n, int(n_groups),
                                          _l.MERGE_REVERSE if reverse else 0, _p(st)))
@@ -583,29 +588,19 @@ class Device:
         int32 [n] or None (all 0).
         -> (off int64, pts int32 [total', 2], origin int32 [paths_out]: the input stroke of every output stroke, {lib.DEDUP_STATS})"""
         po, pp, n, _keep = _step_paths(off, pts, n)
-        g = None
-        if group is not None:
-            g = np.ascontiguousarray(group, np.int32).reshape(-1)
-            n = len(g) if n is None else n
-            if len(g) != n:
-                raise ValueError(f"{len(g)} groups given for {n} paths")
-        if n is None:
-            raise ValueError("n: the number of resident step polylines")
-        n = int(n)
+        g, n = _groups(group, n)
         st = np.zeros(9, np.int64)
         self._ck(self.L.orip_gcode_dedup(self.h, po, pp, _p(g) if g is not None and n else None, n, int(n_groups), _p(st)))
-        paths, total = int(st[5]), int(st[6])
-        origin = np.zeros(max(paths, 1), np.int32)
-        self._ck(self.L.orip_gcode_dedup_fetch(self.h, _p(origin)))
-        off_s, pts_s = self.gcode_steps_fetch(paths, total)
-        return off_s, pts_s, origin[:paths], {k: int(v) for k, v in zip(_l.DEDUP_STATS, st)}
+        return self._cut_result(st, _l.DEDUP_STATS, self.L.orip_gcode_dedup_fetch)
 
-    def _occlude_result(self, st):
-        paths, total = int(st[6]), int(st[7])
+    def _cut_result(self, st, names, fetch):
+        """what a cutting pass (dedup, occlusion, dash) left: its stats st under `names`, its origin through `fetch`, the resident polylines
+        -> (off int64, pts int32 [total', 2], origin int32 [paths_out], {names})"""
+        paths, total = int(st[names.index("paths_out")]), int(st[names.index("points_out")])
         origin = np.zeros(max(paths, 1), np.int32)
-        self._ck(self.L.orip_gcode_occlude_fetch(self.h, _p(origin)))
+        self._ck(fetch(self.h, _p(origin)))
         off_s, pts_s = self.gcode_steps_fetch(paths, total)
-        return off_s, pts_s, origin[:paths], {k: int(v) for k, v in zip(_l.OCCLUDE_STATS, st)}
+        return off_s, pts_s, origin[:paths], {k: int(v) for k, v in zip(names, st)}
 
     def gcode_occlude(self, off, pts, level, ring_off, ring_pts, ring_level, n: int | None = None):
         """--occlude (include/orip.h: orip_gcode_occlude): of the step polylines (off int64 [n + 1], pts int32 [total, 2]; both None = the n resident ones)
@@ -625,7 +620,7 @@ class Device:
             raise ValueError(f"{len(ro)} ring offsets and {len(rp)} ring points given for {m} rings")
         st = np.zeros(10, np.int64)
         self._ck(self.L.orip_gcode_occlude(self.h, po, pp, _p(lv) if n else None, n, _p(ro) if m else None, _p(rp) if m and len(rp) else None, _p(rl) if m else None, m, _p(st)))
-        return self._occlude_result(st)
+        return self._cut_result(st, _l.OCCLUDE_STATS, self.L.orip_gcode_occlude_fetch)
 
     def svg_occlude(self, level, ring_sub, ring_level, map: dict, clamp: bool, n: int | None = None):
         """--occlude on the resident step polylines (include/orip.h: orip_svg_occlude): ring r is the resident fitted path ring_sub[r], converted on the
@@ -643,7 +638,7 @@ class Device:
         gm = _l.GcodeMap(**{k: map[k] for k, _ in _l.GcodeMap._fields_})
         st = np.zeros(10, np.int64)
         self._ck(self.L.orip_svg_occlude(self.h, _p(lv) if n else None, n, _p(rs) if m else None, _p(rl) if m else None, m, C.byref(gm), _l.OCCLUDE_CLAMP if clamp else 0, _p(st)))
-        return self._occlude_result(st)
+        return self._cut_result(st, _l.OCCLUDE_STATS, self.L.orip_gcode_occlude_fetch)
 
     def gcode_dash(self, off, pts, pattern, phase, pat_off, pat_val, n: int | None = None):
         """--dashes / --dash-mm (include/orip.h: orip_gcode_dash): of the step polylines (off int64 [n + 1], pts int32 [total, 2]; both None = the n resident
@@ -662,11 +657,7 @@ class Device:
             raise ValueError(f"{len(qo)} pattern offsets and {len(qv)} entries given")
         st = np.zeros(len(_l.DASH_STATS), np.int64)
         self._ck(self.L.orip_gcode_dash(self.h, po, pp, _p(pa) if n else None, _p(ph) if n else None, n, _p(qo), _p(qv) if len(qv) else None, len(qo) - 1, _p(st)))
-        paths, total = int(st[4]), int(st[5])
-        origin = np.zeros(max(paths, 1), np.int32)
-        self._ck(self.L.orip_gcode_dash_fetch(self.h, _p(origin)))
-        off_s, pts_s = self.gcode_steps_fetch(paths, total)
-        return off_s, pts_s, origin[:paths], {k: int(v) for k, v in zip(_l.DASH_STATS, st)}
+        return self._cut_result(st, _l.DASH_STATS, self.L.orip_gcode_dash_fetch)
 
     def gcode_steps_fetch(self, n: int, total: int, points: bool = True) -> Tuple[np.ndarray, np.ndarray]:
         """the n resident step polylines of `total` points, as gcode_to_steps or gcode_merge left them: (off int64 [n + 1], pts int32 [total, 2]; zeros without `points`)"""

@@ -447,15 +447,39 @@ def _convert(st: StrokeSteps, off_mm, pts_mm, m: dict, rect, info: dict):
     return np.asarray(off, np.int64), np.asarray(pts, np.int32).reshape(-1, 2)
 
 
+def _sources(st: StrokeSteps, n: int, n_paths: int, tables_ok: bool = True):
+    """the input path of each of the n step polylines, checked against the n_paths input paths (tables_ok: the caller's per-path tables are of one length)"""
+    src = np.asarray(st.source(n), np.int64).reshape(-1)
+    if len(src) != n or (src < 0).any() or (src >= n_paths).any() or not tables_ok:
+        raise RuntimeError("the source indices of the step polylines do not name input paths")
+    return src
+
+
+def _cut_result(what: str, out, n_in: int, pen, group, info: dict, may_be_empty: bool = True):
+    """What a cutting pass (`what`: "the dedup", "the occlusion", "the dash pass") returned, (off, pts, origin), normalised and checked: the origins are the
+    input strokes in ascending order, every stroke has two points or more and no repeated point, and at least one is left unless the pass may leave none.
+    Pen and group follow origin; info["paths"].  -> (off, pts, origin, pen, group)"""
+    off, pts, origin = out
+    off = np.asarray(off, np.int64).reshape(-1); pts = np.asarray(pts, np.int32).reshape(-1, 2); origin = np.asarray(origin, np.int64).reshape(-1)
+    n = len(off) - 1
+    if n < (0 if may_be_empty else 1) or len(origin) != n or (np.diff(origin) < 0).any() or (n and (origin[0] < 0 or origin[-1] >= n_in)):
+        raise RuntimeError(f"{what}'s origins are not the input strokes in ascending order")
+    same = (np.diff(pts, axis=0) == 0).all(1) if len(pts) > 1 else np.zeros(0, bool)
+    if off[0] != 0 or int(off[-1]) != len(pts) or (np.diff(off) < 2).any() or np.delete(same, off[1:-1] - 1).any():
+        raise RuntimeError(f"{what} returned a stroke of fewer than two points or with a repeated point")
+    if group is not None:
+        pen, group = pen[origin], group[origin]
+    info["paths"] = n
+    return off, pts, origin, pen, group
+
+
 def _stroke_pens(st: StrokeSteps, o: GcodeOptions, pens, n: int, info: dict):
     """(pen, group) of every step polyline: its input path's pen, through the paths the conversion dropped, and that pen's place in the drawing sequence"""
     if not (0 <= int(o.color_index) <= 7):
         raise ValueError("color index 0..7")
     if pens is None:
         return np.full(n, int(o.color_index), np.int64), np.zeros(n, np.int32)
-    src = np.asarray(st.source(n), np.int64).reshape(-1)
-    if len(src) != n or (src < 0).any() or (src >= len(pens)).any():
-        raise RuntimeError("the source indices of the step polylines do not name input paths")
+    src = _sources(st, n, len(pens))
     pen = np.where(pens[src] < 0, int(o.color_index), pens[src])
     info["pens"] = {"paths": np.bincount(pen, minlength=MAX_PENS).tolist(), "unmatched": int((pens[src] < 0).sum()), "reversed": 0}
     return pen, np.argsort(np.asarray(pen_sequence(o.pen_order)))[pen].astype(np.int32)
@@ -490,23 +514,15 @@ def draw_steps(off, pts) -> int:
 def _dedup(st: StrokeSteps, off_in, pts_in, pen, group, n_groups: int, info: dict):
     """the strokes less every stretch an earlier segment of the same pen has drawn; a stroke left in parts keeps its pen; info["dedup"]"""
     n_in = len(off_in) - 1
-    off, pts, origin, dst = st.dedup(off_in, pts_in, group if group is not None else np.zeros(n_in, np.int32), n_groups)
-    off = np.asarray(off, np.int64).reshape(-1); pts = np.asarray(pts, np.int32).reshape(-1, 2); origin = np.asarray(origin, np.int64).reshape(-1)
+    *out, dst = st.dedup(off_in, pts_in, group if group is not None else np.zeros(n_in, np.int32), n_groups)
     d = {k: int(dst[k]) for k in DEDUP_STATS}
+    off, pts, origin, pen, group = _cut_result("the dedup", out, n_in, pen, group, info, may_be_empty=False)
     n = len(off) - 1
-    if n < 1 or len(origin) != n or (np.diff(origin) < 0).any() or origin[0] < 0 or origin[-1] >= n_in:
-        raise RuntimeError("the dedup's origins are not the input strokes in ascending order")
-    same = (np.diff(pts, axis=0) == 0).all(1) if len(pts) > 1 else np.zeros(0, bool)
-    if off[0] != 0 or int(off[-1]) != len(pts) or (np.diff(off) < 2).any() or np.delete(same, off[1:-1] - 1).any():
-        raise RuntimeError("the dedup returned a stroke of fewer than two points or with a repeated point")
     if d["whole"] + d["cut"] + d["covered"] != d["segments"] or d["segments"] != len(pts_in) - n_in or d["paths_out"] != n or d["points_out"] != len(pts) or \
             d["pieces"] != len(pts) - n or d["pieces"] > 2 * d["segments"] or d["draw_steps_in"] != draw_steps(off_in, pts_in) or d["draw_steps_out"] != draw_steps(off, pts):
         raise RuntimeError("the dedup's counts do not add up")
     if d["draw_steps_out"] > d["draw_steps_in"]:
         raise RuntimeError("the dedup added ink")
-    if group is not None:
-        pen, group = pen[origin], group[origin]
-    info["paths"] = n
     info["dedup"] = d
     return off, pts, pen, group
 
@@ -514,24 +530,14 @@ def _dedup(st: StrokeSteps, off_in, pts_in, pen, group, n_groups: int, info: dic
 def _occlude(st: StrokeSteps, oc: Occlude, off_in, pts_in, pen, group, m: dict, info: dict):
     """the strokes less what a shape of a higher level hides; a stroke takes its level through its source, and what is left of it keeps its pen; info["occlude"]"""
     n_in = len(off_in) - 1
-    src = np.asarray(st.source(n_in), np.int64).reshape(-1)
-    if len(src) != n_in or (src < 0).any() or (src >= len(oc.path_level)).any():
-        raise RuntimeError("the source indices of the step polylines do not name input paths")
-    off, pts, origin, ost = oc.fn(off_in, pts_in, oc.path_level[src].astype(np.int32), oc.ring_sub, oc.ring_level, m, oc.clamp)
-    off = np.asarray(off, np.int64).reshape(-1); pts = np.asarray(pts, np.int32).reshape(-1, 2); origin = np.asarray(origin, np.int64).reshape(-1)
+    src = _sources(st, n_in, len(oc.path_level))
+    *out, ost = oc.fn(off_in, pts_in, oc.path_level[src].astype(np.int32), oc.ring_sub, oc.ring_level, m, oc.clamp)
     d = {k: int(ost[k]) for k in OCCLUDE_STATS}
+    off, pts, origin, pen, group = _cut_result("the occlusion", out, n_in, pen, group, info)
     n = len(off) - 1
-    if n < 0 or len(origin) != n or (np.diff(origin) < 0).any() or (n and (origin[0] < 0 or origin[-1] >= n_in)):
-        raise RuntimeError("the occlusion's origins are not the input strokes in ascending order")
-    same = (np.diff(pts, axis=0) == 0).all(1) if len(pts) > 1 else np.zeros(0, bool)
-    if off[0] != 0 or int(off[-1]) != len(pts) or (np.diff(off) < 2).any() or np.delete(same, off[1:-1] - 1).any():
-        raise RuntimeError("the occlusion returned a stroke of fewer than two points or with a repeated point")
     if d["whole"] + d["cut"] + d["hidden"] != d["segments"] or d["segments"] != len(pts_in) - n_in or d["paths_out"] != n or d["points_out"] != len(pts) or \
             d["pieces"] - d["collapsed"] != len(pts) - n or d["draw_steps_in"] != draw_steps(off_in, pts_in) or d["draw_steps_out"] != draw_steps(off, pts):
         raise RuntimeError("the occlusion's counts do not add up")
-    if group is not None:
-        pen, group = pen[origin], group[origin]
-    info["paths"] = n
     info["occlude"] = d
     return off, pts, pen, group
 
@@ -540,25 +546,15 @@ def _dash(st: StrokeSteps, dh: Dash, off_in, pts_in, pen, group, info: dict):
     """the strokes, those with a pattern as their dashes; a stroke takes pattern and phase through its source, and a dash keeps its stroke's pen and, the
     fifth value returned, its source; info["dash"]"""
     n_in = len(off_in) - 1
-    src = np.asarray(st.source(n_in), np.int64).reshape(-1)
-    if len(src) != n_in or (src < 0).any() or (src >= len(dh.path_pattern)).any() or len(dh.path_phase) != len(dh.path_pattern):
-        raise RuntimeError("the source indices of the step polylines do not name input paths")
+    src = _sources(st, n_in, len(dh.path_pattern), len(dh.path_phase) == len(dh.path_pattern))
     pattern = dh.path_pattern[src]
-    off, pts, origin, dst = dh.fn(off_in, pts_in, pattern, dh.path_phase[src], dh.pat_off, dh.pat_val)
-    off = np.asarray(off, np.int64).reshape(-1); pts = np.asarray(pts, np.int32).reshape(-1, 2); origin = np.asarray(origin, np.int64).reshape(-1)
+    *out, dst = dh.fn(off_in, pts_in, pattern, dh.path_phase[src], dh.pat_off, dh.pat_val)
     d = {k: int(dst[k]) for k in DASH_STATS}
+    off, pts, origin, pen, group = _cut_result("the dash pass", out, n_in, pen, group, info)
     n = len(off) - 1
-    if n < 0 or len(origin) != n or (np.diff(origin) < 0).any() or (n and (origin[0] < 0 or origin[-1] >= n_in)):
-        raise RuntimeError("the dash pass's origins are not the input strokes in ascending order")
-    same = (np.diff(pts, axis=0) == 0).all(1) if len(pts) > 1 else np.zeros(0, bool)
-    if off[0] != 0 or int(off[-1]) != len(pts) or (np.diff(off) < 2).any() or np.delete(same, off[1:-1] - 1).any():
-        raise RuntimeError("the dash pass returned a stroke of fewer than two points or with a repeated point")
     if d["paths_in"] != n_in or d["dashed"] != int((pattern >= 0).sum()) or d["paths_out"] != n or d["points_out"] != len(pts) or \
             d["paths_out"] != d["paths_in"] - d["dashed"] + d["dashes"] - d["collapsed"] or not (0 <= d["length_on"] <= d["length_in"]):
         raise RuntimeError("the dash pass's counts do not add up")
-    if group is not None:
-        pen, group = pen[origin], group[origin]
-    info["paths"] = n
     info["dash"] = d
     return off, pts, pen, group, src[origin]
 

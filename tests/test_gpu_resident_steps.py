@@ -1,6 +1,7 @@
 """The resident step polylines between the calls that write them (csrc/orip_ctx.h states the contract): what orip_gcode_to_steps, orip_gcode_to_steps_clip,
 orip_gcode_merge and orip_gcode_simplify leave behind after a bad argument, after an explicit upload and after n == 0, and when the sources still name
-the polylines.  The drawing is the one of test_gpu_simplify.py's resident form: six paths in mm that become five polylines of fourteen points.  Every comparison is exact."""
+the polylines.  The drawing is the one of test_gpu_simplify.py's resident form: six paths in mm that become five polylines of fourteen points.  The last
+test chains the three cutting passes (dash, occlusion, dedup; csrc/gc_cut.h) on a drawing of its own.  Every comparison is exact."""
 import numpy as np
 import pytest
 
@@ -106,3 +107,44 @@ def test_an_explicit_empty_list(dev, steps, which):
     assert len(dev.gcode_order(None, n=0)) == 0
     fails(lambda: dev.gcode_order(None, n=1), "orip_gcode_order:", "1 paths asked for, 0 step polylines resident")
     convert(dev, steps)
+
+
+CHAIN = [[(10, 10), (30, 10), (30, 30), (10, 30), (10, 10)], [(30, 10), (50, 10), (50, 30), (30, 30), (30, 10)], [(50, 50), (50, 50.2)], [(5, 60), (45, 60), (25, 60)],
+         [(0, 10), (60, 10)], [(0, 40), (60, 40)], [(12, 30), (28, 30)], [(20, 50), (20, 70)]]
+
+
+def test_the_cutting_passes_chained_keep_their_own_records(dev):
+    """dash, occlusion and dedup one after the other on the resident list: each result, its stats and its origin are the sequential definition's
+    (tests/dash_double.py, occlude_double.py, dedup_double.py applied in turn), the sources follow the composed origin, and after all three calls every
+    pass's own fetch still gives that pass's origin: the three result records are independent"""
+    import ctypes as C
+    import dash_double as DS
+    import dedup_double as DD
+    import occlude_double as OD
+    off_mm = np.concatenate([[0], np.cumsum([len(p) for p in CHAIN])]).astype(np.int64)
+    off, pts = dev.gcode_to_steps(off_mm, np.asarray([q for p in CHAIN for q in p], np.float64), MAP)
+    src = dev.gcode_steps_source(len(off) - 1)
+    assert len(off) - 1 == 7 and src.tolist() == [0, 1, 3, 4, 5, 6, 7]         # the third path rounds to one point: the sources are not the identity
+    pattern = np.where(pts[off[:-1], 1] == 40, 0, -1).astype(np.int32)         # the y = 40 line only
+    assert pattern.tolist() == [-1, -1, -1, -1, 0, -1, -1]
+    dash_args = (pattern, np.zeros(7, np.int64), np.array([0, 2], np.int32), np.array([20 * 256, 10 * 256], np.int64))
+    ring = (np.array([0, 5], np.int64), np.array([(40, 0), (70, 0), (70, 20), (40, 20), (40, 0)], np.int32), np.array([1], np.int32))
+
+    w_ds = DS.dash_numpy(off, pts, *dash_args)
+    w_oc = OD.occlude_numpy(w_ds[0], w_ds[1], np.zeros(8, np.int32), *ring)
+    w_dd = DD.dedup_numpy(w_oc[0], w_oc[1], None, 1)
+    assert [len(w[0]) - 1 for w in (w_ds, w_oc, w_dd)] == [8, 9, 8]
+    assert w_ds[2].tolist() == [0, 1, 2, 3, 4, 4, 5, 6] and w_oc[2].tolist() == [0, 1, 1, 2, 3, 4, 5, 6, 7] and w_dd[2].tolist() == [0, 1, 2, 3, 4, 5, 6, 8]
+    composed = w_ds[2][w_oc[2][w_dd[2]]]
+    assert composed.tolist() == [0, 1, 1, 2, 3, 4, 4, 6]
+
+    g_ds = dev.gcode_dash(None, None, *dash_args, n=7)
+    g_oc = dev.gcode_occlude(None, None, np.zeros(8, np.int32), *ring, n=8)
+    g_dd = dev.gcode_dedup(None, None, None, 1, n=9)
+    for got, want in ((g_ds, w_ds), (g_oc, w_oc), (g_dd, w_dd)):
+        assert all(np.array_equal(a, b) for a, b in zip(got[:3], want[:3])) and got[3] == want[3]
+    assert dev.gcode_steps_source(8).tolist() == src[composed].tolist() == [0, 1, 1, 3, 4, 5, 5, 7]
+    for fetch, want in ((dev.L.orip_gcode_dash_fetch, w_ds), (dev.L.orip_gcode_occlude_fetch, w_oc), (dev.L.orip_gcode_dedup_fetch, w_dd)):
+        origin = np.full(len(want[2]), -1, np.int32)
+        dev._ck(fetch(dev.h, origin.ctypes.data_as(C.c_void_p)))
+        assert origin.tolist() == want[2].tolist()

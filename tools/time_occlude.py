@@ -5,7 +5,8 @@ under a polygon of --edges edges: many events on a segment, many edges in a shap
 rings by the host clock (the call ends in a stream synchronisation; the uploads and its three read-backs are inside it, the fetches are not), median of
 --reps after one warm-up call; its phases (orip_prof_get, in runs of their own: every timed scope ends in an event wait); the stats; the same clock around
 orip_gcode_dedup on the same strokes; and, up to --check-segments segments, the comparison with the sequential definition (tests/occlude_double.py).
-usage: python tools/time_occlude.py [--tiles K] [--strokes N] [--shapes N] [--teeth N] [--edges N] [--segments N] [--reps K] [--out FILE.json]"""
+--lib FILE loads another build of the library, so that two builds can be timed from one tree.
+usage: python tools/time_occlude.py [--tiles K] [--strokes N] [--shapes N] [--teeth N] [--edges N] [--segments N] [--reps K] [--lib FILE] [--out FILE.json]"""
 import argparse
 import json
 import math
@@ -76,14 +77,17 @@ def main():
     ap.add_argument("--segments", type=int, default=200)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--check-segments", type=int, default=3000)
+    ap.add_argument("--lib", default=None)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "occlude_times.json"))
     a = ap.parse_args()
     from orip import lib
+    if a.lib:
+        lib.LIB_PATH = os.path.abspath(a.lib)
     from orip.device import Device
     import occlude_double as OD
     inputs = {"tiles": tiles(a.tiles), "free": free(a.strokes, a.shapes), "comb": comb(a.teeth, a.edges, a.segments)}
     res = {k: getattr(a, k) for k in ("tiles", "strokes", "shapes", "teeth", "edges", "segments", "reps")}
-    res.update(side_steps=SIDE, inputs={})
+    res.update(side_steps=SIDE, lib=a.lib, inputs={})
     dev = Device(0)
     try:
         for name, arr in inputs.items():

@@ -620,7 +620,39 @@ int orip_svg_fit(orip_ctx* ctx, double sx, double sy, double ox, double oy);
 #define ORIP_HATCH_VERTICAL 4
 int orip_svg_hatch(orip_ctx* ctx, const int32_t* fill_group /* [n_sub] */, int64_t n_sub, double steps_per_mm, int32_t spacing, int32_t inset, int32_t flags,
                    int64_t* stats /* [4]: groups, lines, crossings, segments */);
-/* group_out[k] = the fill group, as the caller numbered it, of the k-th hatch line orip_svg_hatch appended (k counts from the first appended path). */
+/* Hatch fill at an angle (csrc/hatch_angle.hip).  Ours: the reference's hatch_fill knows X and Y only, and orip_svg_hatch above stays pinned to it.  The
+ * rule is integer and rational arithmetic on the step grid, exact, with one answer for every input.  fill_group, the closing edge of every subpath, the
+ * state contract and what is appended are those of orip_svg_hatch.
+ *   Direction: an integer vector u = (ux, uy), not zero, max(|ux|, |uy|) <= 4096.  n = (-uy, ux), U2 = ux^2 + uy^2, and rs(v) = (isqrt(4 v) + 1) >> 1, the
+ *   exact nearest integer to sqrt(v).  (The tools take an angle A, reduce it into (-90, 90] and pass ux = round(4096 cos A), uy = round(4096 sin A).)
+ *   Quantise: q = rint(v * steps_per_mm) as orip_svg_hatch; |q| >= 2^24 is an error, so that every product below stays inside signed 128 bits.
+ *   Coordinates: for a point p, s(p) = n . p and w(p) = u . p, both below 2^37 in magnitude.
+ *   Lines: D = rs(spacing^2 U2), I = rs(inset^2 U2).  Line k is n . p = k D for every integer k: ONE family for the whole drawing, so the hatches of
+ *   neighbouring shapes line up.  A group's lines are k = floor(min s / D) + 1 .. floor(max s / D) over its points (floor division throughout); empty
+ *   lines count in `lines`.  D is off from spacing |u| by at most 1/2, so the distance of the lines is Euclid's spacing within a factor of
+ *   1 +- 1 / (2 spacing |u|): within 1 +- 2^-12 for the tools' |u| of about 4096, and likewise the inset.  A stated deviation.
+ *   Crossings: an edge runs from a point to its successor in its closed subpath.  s_a == s_b: skipped; otherwise ordered to s_a < s_b.  It crosses line k
+ *   iff s_a < k D <= s_b, at w = w_a + (k D - s_a)(w_b - w_a) / (s_b - s_a), kept as numerator (below 2^77) over denominator (below 2^38).
+ *   Segments: on a line the crossings ascend by exact comparison of w (128-bit cross products); equal values are interchangeable.  They are paired (0, 1),
+ *   (2, 3), ..., an odd last one dropped.  ws = w_0 + I, we = w_1 - I, kept iff we > ws strictly.  The exact point for w on line k is
+ *   ((w ux - k D uy) / U2, (w uy + k D ux) / U2); each coordinate is rounded to the nearest step, halves toward +infinity (the rounding of the clip, the
+ *   occlusion and the dashes).  A segment whose rounded ends coincide is dropped and counted in `collapsed`.  With ORIP_HATCH_SERPENTINE a segment on a
+ *   line with k & 1 (two's complement, so also for negative k) runs from we to ws.
+ *   Order: the families first -- ORIP_HATCH_HORIZONTAL here means "along u", ORIP_HATCH_VERTICAL "along (-uy, ux)" (the same rule with that vector as u);
+ *   with both, the family along u first -- then the groups ascending, then k ascending, then the pairs ascending in w.
+ * Each segment is appended as a 2-point path in mm, k / steps_per_mm rounded to 4 decimals, as orip_svg_hatch does.  stats: fill groups, lines, crossings,
+ * segments (appended), collapsed (the last four summed over the families).  Valid once after orip_svg_fit per flatten: either hatch call after the other
+ * is refused.  It fills what orip_svg_hatch_groups_fetch reads.  Errors (no fault, the resident paths as they were): those of orip_svg_hatch, u zero or a
+ * component beyond 4096, a quantised value of 2^24 or beyond.
+ * NOT promised: u = (4096, 0) is not ORIP_HATCH_HORIZONTAL of orip_svg_hatch.  The lines are the same ones -- that call's y0 is a multiple of the spacing
+ * too, so both hatch on y = k spacing and find the same crossings -- but that call truncates float crossings, numbers a group's lines from the group's own
+ * y0 for the serpentine parity and counts a line at or below the group's lowest point in `lines`; this one rounds exact crossings, takes the parity from
+ * the global k and counts no such line.  On rectangles with integer corners the two draw the same undirected segments; on slanted edges the ends can
+ * differ by a step. */
+int orip_svg_hatch_angle(orip_ctx* ctx, const int32_t* fill_group /* [n_sub] */, int64_t n_sub, double steps_per_mm, int32_t spacing, int32_t inset, int32_t ux, int32_t uy,
+                         int32_t flags, int64_t* stats /* [5]: groups, lines, crossings, segments, collapsed */);
+/* group_out[k] = the fill group, as the caller numbered it, of the k-th hatch line orip_svg_hatch or orip_svg_hatch_angle appended (k counts from the
+ * first appended path). */
 int orip_svg_hatch_groups_fetch(orip_ctx* ctx, int32_t* group_out /* [segments] */);
 
 /* ---- multi-GPU exchange (no counterpart in the reference, which is a single process) ----

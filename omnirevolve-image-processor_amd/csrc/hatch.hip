@@ -19,22 +19,16 @@
 //    k -> k / steps_per_mm rounded to 4 decimals as the fit rounds.
 // Nothing is committed (sv_n, sv_total) before the last kernel of the last direction has run, so an error leaves the resident paths as they were.  Every
 // index is bounded by a count computed on the device and checked on the host before the buffers are sized: rows by the scanned line counts, crossings by
-// the scanned row counts, outputs by the scanned kept flags.
-#include "vec_common.h"
+// the scanned row counts, outputs by the scanned kept flags.  The limits, the counters, k_ht_classify and the intake of a call are in hatch_common.h, which
+// hatch_angle.hip (the exact hatch along any direction) shares.
+#include "hatch_common.h"
 #include "sv_round.h"
 #include <rocprim/rocprim.hpp>
 #include <climits>
 #include <cmath>
 
 namespace {
-constexpr unsigned HT_WAVE_MAX = 64, HT_BLOCK_MAX = 2048;
-constexpr int HT_CHUNK = 64;
-constexpr int64_t HT_MAX_ROWS = 1ll << 26, HT_MAX_CROSSINGS = 1ll << 30, HT_MAX_POINTS = (1ll << 30) - 1;     // the last: what orip_gcode_to_steps accepts
-constexpr double HT_QLIM = 1073741824.0, HT_MAX_SPM = 5000.0;
-
-struct HtCounters { unsigned long long crossings; unsigned n_med, n_big; int err; int pad; };
-
-__device__ __forceinline__ long long ht_floordiv(long long a, long long b) { const long long q = a / b; return (a % b != 0 && a < 0) ? q - 1 : q; }     // b > 0
+constexpr double HT_QLIM = 1073741824.0;
 
 __global__ __launch_bounds__(256) void k_ht_box_init(int* __restrict__ box, int64_t G) {
     const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -129,16 +123,6 @@ __global__ __launch_bounds__(256) void k_ht_cross(const int2* __restrict__ q, co
         xs[p] = sv_add(x1, sv_mul(t, dx));
         crow[p] = (unsigned)row;
     }
-}
-
-// rows for the block sort go on a list (in any order); rows beyond it are counted: a non-zero count calls the segmented sort.  rowcnt[R] = 0 closes the scan
-__global__ __launch_bounds__(256) void k_ht_classify(unsigned* __restrict__ rowcnt, int64_t R, unsigned* __restrict__ medlist, HtCounters* __restrict__ cn) {
-    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (r > R) return;
-    if (r == R) { rowcnt[r] = 0; return; }
-    const unsigned n = rowcnt[r];
-    if (n > HT_BLOCK_MAX) atomicAdd(&cn->n_big, 1u);
-    else if (n > HT_WAVE_MAX) { const unsigned i = atomicAdd(&cn->n_med, 1u); if (i < R) medlist[i] = (unsigned)r; }
 }
 
 __global__ __launch_bounds__(256) void k_ht_sort_wave(const double* __restrict__ xs, double* __restrict__ out, const unsigned* __restrict__ rowoff, const unsigned* __restrict__ rowcnt, int64_t R) {
@@ -309,29 +293,14 @@ extern "C" int orip_svg_hatch(orip_ctx* c, const int32_t* fill_group, int64_t n_
     ORIP_LANE(c, ORIP_LANE_CROSS);
     if (!stats || n_sub < 0 || (n_sub > 0 && !fill_group)) ORIP_FAIL(c, "bad arguments");
     for (int k = 0; k < 4; k++) stats[k] = 0;
-    if (!c->sv_ready || !c->sv_fitted) ORIP_FAIL(c, "no fitted paths: orip_svg_flatten and orip_svg_fit come first");
-    if (c->sv_hatched) ORIP_FAIL(c, "the resident paths are hatched already: flatten again first");
-    if (n_sub != c->sv_n) ORIP_FAIL(c, "%lld fill groups given, %lld paths resident", (long long)n_sub, (long long)c->sv_n);
-    if (!(steps_per_mm > 0.0) || !(steps_per_mm <= HT_MAX_SPM)) ORIP_FAIL(c, "steps per mm %g: hatching needs a value in (0, 5000], so that four decimals of a mm name every step", steps_per_mm);
-    if (spacing < 1) ORIP_FAIL(c, "hatch spacing %d steps: at least 1", spacing);
-    if (inset < 0) ORIP_FAIL(c, "hatch inset %d steps: at least 0", inset);
-    if (!(flags & (ORIP_HATCH_HORIZONTAL | ORIP_HATCH_VERTICAL)) || (flags & ~(ORIP_HATCH_SERPENTINE | ORIP_HATCH_HORIZONTAL | ORIP_HATCH_VERTICAL)))
-        ORIP_FAIL(c, "flags %d: ORIP_HATCH_HORIZONTAL, ORIP_HATCH_VERTICAL or both, and ORIP_HATCH_SERPENTINE", flags);
-    // the groups in use, renumbered 0 .. G - 1 in ascending order of their number
-    std::vector<int32_t> gid((size_t)n_sub, -1), rank((size_t)n_sub, 0);
-    for (int64_t p = 0; p < n_sub; p++) {
-        if (fill_group[p] < -1 || fill_group[p] >= n_sub) ORIP_FAIL(c, "subpath %lld: fill group %d of %lld", (long long)p, fill_group[p], (long long)n_sub);
-        if (fill_group[p] >= 0) rank[fill_group[p]] = 1;
-    }
-    int64_t G = 0;
-    for (int64_t g = 0; g < n_sub; g++) { const int32_t used = rank[g]; rank[g] = (int32_t)G; G += used; }
-    for (int64_t p = 0; p < n_sub; p++) if (fill_group[p] >= 0) gid[p] = rank[fill_group[p]];
+    HtGroups grp;
+    ORIP_TRY(ht_intake(c, __func__, fill_group, n_sub, steps_per_mm, spacing, inset, flags, grp));
+    const std::vector<int32_t>&gid = grp.gid, &gnum = grp.gnum;
+    const int64_t G = grp.G;
     stats[0] = G;
     const int64_t total = c->sv_total;
     c->ht_nseg = 0;
     if (G == 0 || total == 0) { c->sv_hatched = true; return 0; }
-    std::vector<int32_t> gnum((size_t)G, 0);                                  // rank -> the caller's number
-    for (int64_t p = 0; p < n_sub; p++) if (gid[p] >= 0) gnum[gid[p]] = fill_group[p];
     hipStream_t s = LN(c).stream;
     HtPlan P{};
     int* d_gid;

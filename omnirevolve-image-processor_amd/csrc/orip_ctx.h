@@ -407,7 +407,8 @@ struct orip_ctx {
     DBuf sv_tmp, sv_tmp2, sv_off, sv_pts; int64_t sv_n = 0, sv_total = 0; bool sv_ready = false, sv_box_ok = false; double sv_box[4] = {0, 0, 0, 0};
     // hatch fill (hatch.hip): sv_fitted = orip_svg_fit has run on the resident paths, sv_hatched = orip_svg_hatch has appended to them (both cleared by the
     // next flatten).  Scratch, free between calls: ht_pts = the quantised points with their group and successor, the groups' boxes and the call's counters;
-    // ht_rows = one direction's line ranges per group, chunk counts per edge and crossing counts per row; ht_x = its crossings, unsorted and sorted
+    // ht_rows = one direction's line ranges per group, chunk counts per edge and crossing counts per row; ht_x = its crossings, unsorted and sorted.
+    // orip_svg_hatch_angle (hatch_angle.hip) keeps the same contract on the same buffers, with its own records in them; either call sets sv_hatched
     DBuf ht_pts, ht_rows, ht_x; bool sv_fitted = false, sv_hatched = false;
     // resident after orip_svg_hatch: ht_grp int32[ht_nseg] = the caller's fill group of every appended hatch line (orip_svg_hatch_groups_fetch)
     DBuf ht_grp; int64_t ht_nseg = 0;

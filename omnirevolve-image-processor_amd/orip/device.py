@@ -478,6 +478,18 @@ class Device:
         self._svg_n = len(g) + int(st[3])
         return {k: int(v) for k, v in zip(("groups", "lines", "crossings", "segments"), st)}
 
+    def svg_hatch_angle(self, fill_group, steps_per_mm: float, spacing: int, inset: int, u, flags: int) -> dict:
+        """hatch lines along the integer direction u = (ux, uy), exact on the step grid, appended as svg_hatch appends its own (include/orip.h:
+        orip_svg_hatch_angle) -> {"groups", "lines", "crossings", "segments", "collapsed"}"""
+        g = np.ascontiguousarray(fill_group, np.int32).reshape(-1)
+        st = np.zeros(5, np.int64)
+        ux, uy = (int(v) for v in u)
+        if max(abs(ux), abs(uy)) >= 2 ** 31:
+            raise ValueError("the hatch direction must fit 32 bits")
+        self._ck(self.L.orip_svg_hatch_angle(self.h, _p(g) if len(g) else None, len(g), float(steps_per_mm), int(spacing), int(inset), ux, uy, int(flags), _p(st)))
+        self._svg_n = len(g) + int(st[3])
+        return {k: int(v) for k, v in zip(("groups", "lines", "crossings", "segments", "collapsed"), st)}
+
     def gcode_order(self, ends: np.ndarray | None, n: int | None = None) -> np.ndarray:
         """order of the paths (first x, first y, last x, last y) int32 [n, 4]; ends None: the n resident step polylines of gcode_to_steps"""
         if ends is not None:

@@ -88,6 +88,7 @@ SIGNATURES = {
     "orip_svg_flatten": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _f64, _P(_i64)]), "orip_svg_paths_fetch": (_i32, [_vp, _vp, _vp]),
     "orip_svg_bbox": (_i32, [_vp, _vp]), "orip_svg_fit": (_i32, [_vp, _f64, _f64, _f64, _f64]),
     "orip_svg_hatch": (_i32, [_vp, _vp, _i64, _f64, _i32, _i32, _i32, _vp]), "orip_svg_hatch_groups_fetch": (_i32, [_vp, _vp]),
+    "orip_svg_hatch_angle": (_i32, [_vp, _vp, _i64, _f64, _i32, _i32, _i32, _i32, _i32, _vp]),
     "orip_stream_pack": (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64]), "orip_stream_pack_fetch": (_i32, [_vp, _vp]),
     "orip_comm_unique_id": (_i32, [_vp]), "orip_comm_init": (_i32, [_vp, _vp, _i32, _i32]), "orip_comm_destroy": (_i32, [_vp]),
     "orip_bcast_layer": (_i32, [_vp, _i32, _i32]),

@@ -26,6 +26,12 @@ runs that function's rules on the fitted paths after they are quantised to steps
 G-code text, the order and the stream treat them like any other path.  Every fill is even-odd, whatever fill-rule says, because the reference's pairing is
 (stated deviation), and the SVG default of a black fill is not taken as a request to hatch: only a fill that is written down is.
 
+Hatch angle (--hatch-angle-deg, only with --hatch-spacing-mm; ours, the reference's hatch_fill knows X and Y).  The angle, counter-clockwise in the frame
+of the written G-code, is reduced into (-90, 90] and becomes the integer direction u = (round(4096 cos A), round(4096 sin A)) (hatch_direction_vector);
+hatch_params adds it as "u", and _Resident.hatch then calls orip_svg_hatch_angle in the place of orip_svg_hatch: one global family of lines n . p = k D,
+exact rational crossings, ends rounded to the nearest step (include/orip.h states the rule).  --hatch-direction then means along the angle, across it, or
+both; info["hatch"] gains "collapsed"; everything behind the hatch sees ordinary 2-point paths.  0 degrees is NOT --hatch-direction horizontal.
+
 Pens (off unless --pen-colors is given; ours, the reference's svg2stream.py draws with one pen).  parse_svg records the stroke and the fill of every
 subpath's element as written (style property, presentation attribute, enclosing groups).  --pen-colors names the colour of each pen; a subpath is drawn
 with the pen whose colour is nearest to its stroke -- squared Euclidean distance over the 8-bit sRGB values, in integers, the lowest pen on ties.  That
@@ -634,6 +640,7 @@ class SvgOptions:
     hatch_direction: str = "horizontal"
     no_serpentine: bool = False
     hatch_fill: str = "stated"
+    hatch_angle_deg: Optional[float] = None             # None: the reference's hatch along X / Y; else the exact hatch along that angle (orip_svg_hatch_angle)
     pen_colors: Optional[str] = None                    # None: one pen, --color-index
     pen_order: Optional[str] = None
     allow_reverse: bool = False
@@ -651,13 +658,35 @@ class SvgOptions:
 
 HATCH_DIRECTIONS = {"horizontal": HATCH_HORIZONTAL, "vertical": HATCH_VERTICAL, "cross": HATCH_HORIZONTAL | HATCH_VERTICAL}
 HATCH_MAX_STEPS_PER_MM = 5000.0
+HATCH_U_SCALE = 4096
+
+
+def hatch_direction_vector(angle_deg: float) -> Tuple[int, int]:
+    """--hatch-angle-deg as the integer direction orip_svg_hatch_angle takes: the angle reduced into (-90, 90], then (round(4096 cos A), round(4096 sin A))"""
+    a = float(angle_deg)
+    if not math.isfinite(a):
+        raise ValueError("--hatch-angle-deg must be finite")
+    a = math.fmod(a, 180.0)
+    if a > 90.0:
+        a -= 180.0
+    elif a <= -90.0:
+        a += 180.0
+    r = math.radians(a)
+    return int(round(HATCH_U_SCALE * math.cos(r))), int(round(HATCH_U_SCALE * math.sin(r)))
+
+
+def hatch_effective_angle(u) -> float:
+    """the angle, in degrees, of the direction the hatch really takes"""
+    return math.degrees(math.atan2(int(u[1]), int(u[0])))
 
 
 def hatch_params(o: SvgOptions) -> Optional[dict]:
     """None without --hatch-spacing-mm, else what orip_svg_hatch takes: spacing and inset in steps, the flags, steps per mm.  Above 5000 steps per mm the
-    four decimals of the G-code no longer name every step, so the written file and the stream could disagree: refused."""
+    four decimals of the G-code no longer name every step, so the written file and the stream could disagree: refused.  Only with --hatch-angle-deg the
+    key "u": the direction orip_svg_hatch_angle takes, which is then the call that hatches."""
     if o.hatch_spacing_mm is None:
         return None
+    u = None if o.hatch_angle_deg is None else hatch_direction_vector(o.hatch_angle_deg)
     spm = float(o.steps_per_mm)
     if not (0.0 < spm <= HATCH_MAX_STEPS_PER_MM):
         raise ValueError(f"hatching needs --steps-per-mm in (0, {HATCH_MAX_STEPS_PER_MM:g}]: beyond it four decimals of a mm do not name every step")
@@ -673,7 +702,10 @@ def hatch_params(o: SvgOptions) -> Optional[dict]:
         raise ValueError(f"--hatch-spacing-mm {o.hatch_spacing_mm} is {spacing} steps at {spm:g} steps per mm: at least 1")
     if inset < 0:
         raise ValueError("--hatch-inset-mm must not be negative")
-    return {"spacing": spacing, "inset": inset, "flags": HATCH_DIRECTIONS[o.hatch_direction] | (0 if o.no_serpentine else HATCH_SERPENTINE), "steps_per_mm": spm}
+    prm = {"spacing": spacing, "inset": inset, "flags": HATCH_DIRECTIONS[o.hatch_direction] | (0 if o.no_serpentine else HATCH_SERPENTINE), "steps_per_mm": spm}
+    if u is not None:
+        prm["u"] = u
+    return prm
 
 
 def tolerance_mm(o: SvgOptions) -> float:
@@ -783,7 +815,10 @@ class _Resident:
     def clip(self, paths, m, rect): return self.dev.gcode_to_steps_clip(None, None, m, rect, n=paths["n"])
 
     def hatch(self, paths, fill_group, prm):
-        st = self.dev.svg_hatch(fill_group, prm["steps_per_mm"], prm["spacing"], prm["inset"], prm["flags"])
+        if "u" in prm:
+            st = self.dev.svg_hatch_angle(fill_group, prm["steps_per_mm"], prm["spacing"], prm["inset"], prm["u"], prm["flags"])
+        else:
+            st = self.dev.svg_hatch(fill_group, prm["steps_per_mm"], prm["spacing"], prm["inset"], prm["flags"])
         return {"n": paths["n"] + st["segments"], "total": paths["total"] + 2 * st["segments"]}, st
 
     def hatch_groups(self, paths, segments): return self.dev.svg_hatch_groups(segments)
@@ -863,6 +898,14 @@ def resolved_pens(pens: np.ndarray, o: SvgOptions) -> np.ndarray:
     return np.where(pens < 0, int(o.color_index), pens)
 
 
+def hatch_angle_report(info: dict) -> str:
+    """what the report lines add with --hatch-angle-deg: the angle the hatch really takes, its direction and the collapsed segments"""
+    if "hatch_u" not in info:
+        return ""
+    u = info["hatch_u"]
+    return ", {} collapsed, at {:.4f} deg (u = ({}, {}))".format(info["hatch"]["collapsed"], hatch_effective_angle(u), u[0], u[1])
+
+
 def hatch_paths(table: SegmentTable, prm: dict, paths, hatch_fn, info: dict, tm: Optional[dict] = None):
     """the fitted paths with the hatch lines of the table's fill groups behind them; info["hatch"] = the counts"""
     import time
@@ -871,7 +914,9 @@ def hatch_paths(table: SegmentTable, prm: dict, paths, hatch_fn, info: dict, tm:
     if len(fg) != table.n_sub:
         raise ValueError(f"fill_group has {len(fg)} entries for {table.n_sub} subpaths")
     paths, st = hatch_fn(paths, fg, prm)
-    info["hatch"] = {k: int(st[k]) for k in ("groups", "lines", "crossings", "segments")}
+    info["hatch"] = {k: int(st[k]) for k in ("groups", "lines", "crossings", "segments") + (("collapsed",) if "u" in prm else ())}
+    if "u" in prm:
+        info["hatch_u"] = tuple(int(v) for v in prm["u"])
     if tm is not None:
         tm["hatch"] = tm.get("hatch", 0.0) + (time.perf_counter() - t0)
     return paths
@@ -991,7 +1036,10 @@ def _add_fit_args(ap: argparse.ArgumentParser, d: SvgOptions):
     ap.add_argument("--tolerance-mm", type=float, default=None, help="largest distance between a curve and its polyline on the page (default: half a step, 0.5 / steps per mm)")
     ap.add_argument("--hatch-spacing-mm", type=float, default=None, help="hatch-fill closed shapes with lines this far apart (default: no hatching); rounded to whole steps")
     ap.add_argument("--hatch-inset-mm", type=float, default=d.hatch_inset_mm, help="how far each hatch line stays inside the outline (default: 0.675, 27 steps at 40 steps per mm)")
-    ap.add_argument("--hatch-direction", choices=sorted(HATCH_DIRECTIONS), default=d.hatch_direction, help="hatch lines along X, along Y, or both (default: horizontal)")
+    ap.add_argument("--hatch-direction", choices=sorted(HATCH_DIRECTIONS), default=d.hatch_direction, help="hatch lines along X, along Y, or both (default: horizontal); with "
+                                                                                                          "--hatch-angle-deg: along the angle, across it, or both")
+    ap.add_argument("--hatch-angle-deg", type=float, default=None, help="hatch along this angle, counter-clockwise in the frame of the written G-code (before --invert-y), exact on "
+                                                                         "the step grid, one family of lines for the whole drawing (default: the reference's hatch along X / Y)")
     ap.add_argument("--no-serpentine", action="store_true", help="draw every hatch line in the same direction; by default every other line is reversed")
     ap.add_argument("--hatch-fill", choices=HATCH_FILLS, default=d.hatch_fill, help="stated: elements whose fill is written down and is not none (default); all: every element that draws")
     ap.add_argument("--pen-colors", default=None, help="the colour of each pen, comma-separated (#rgb, #rrggbb or a keyword; position = pen), or rgbk; a path is drawn with the pen "
@@ -1077,7 +1125,7 @@ def main_gcode(argv: Optional[Sequence[str]] = None, **device_steps) -> None:
         print(f"  Raw bbox: x=[{info['bbox'][0]:.3f}, {info['bbox'][2]:.3f}], y=[{info['bbox'][1]:.3f}, {info['bbox'][3]:.3f}]")
         print(f"  Final scale: sx={sx:.5f}, sy={sy:.5f}; offsets: {ox:.3f}, {oy:.3f} mm; tolerance {tolerance_mm(o)} mm = {info['tol_raw']:.6g} raw units")
     if "hatch" in info:
-        print("  Hatch: {groups} fill groups, {lines} lines, {crossings} crossings -> {segments} segments".format(**info["hatch"]))
+        print("  Hatch: {groups} fill groups, {lines} lines, {crossings} crossings -> {segments} segments".format(**info["hatch"]) + hatch_angle_report(info))
 
 
 def main_stream(argv: Optional[Sequence[str]] = None, **device_steps) -> None:
@@ -1098,7 +1146,7 @@ def main_stream(argv: Optional[Sequence[str]] = None, **device_steps) -> None:
     stream_path.write_bytes(data)
     print(f"[svg] {a.input}: {info['segments']} segments in {info['subpaths']} subpaths -> {len(pts)} points")
     if "hatch" in info:
-        print("[svg] hatch: {groups} fill groups, {lines} lines, {crossings} crossings -> {segments} segments".format(**info["hatch"]))
+        print("[svg] hatch: {groups} fill groups, {lines} lines, {crossings} crossings -> {segments} segments".format(**info["hatch"]) + hatch_angle_report(info))
     for line in GC.report_lines("svg", info, unmatched=True):
         print(line)
     print(f"[svg] G-code saved: {gcode_path}")

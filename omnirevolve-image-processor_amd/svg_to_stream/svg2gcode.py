@@ -4,7 +4,8 @@
 CPU path.  The points chosen for a curve are this project's, held to the curve within --tolerance-mm; they are not the svg_to_gcode package's.
 
     python svg2gcode.py drawing.svg -o drawing.gcode [--page-width-mm 210 --page-height-mm 297 --margin-mm 10] [--scale S | --scale-x SX --scale-y SY] [--tolerance-mm T]
-                         [--hatch-spacing-mm S [--hatch-inset-mm I] [--hatch-direction horizontal|vertical|cross] [--no-serpentine] [--hatch-fill stated|all]]
+                         [--hatch-spacing-mm S [--hatch-inset-mm I] [--hatch-direction horizontal|vertical|cross] [--no-serpentine] [--hatch-fill stated|all]
+                          [--hatch-angle-deg A]]      (ours: the hatch along any angle, exact on the step grid)
                          [--pen-colors rgbk|LIST]      (ours: a T<pen> line wherever the pen changes)
 """
 import os

@@ -405,12 +405,13 @@ struct orip_ctx {
     // svg2stream (svg.hip): scratch of the flattening and of the box, the resident paths (off int64[sv_n + 1], pts double2[sv_total]; raw units after
     // orip_svg_flatten, page mm after orip_svg_fit) until the next flatten; orip_gcode_to_steps reads them when it is called without pointers
     DBuf sv_tmp, sv_tmp2, sv_off, sv_pts; int64_t sv_n = 0, sv_total = 0; bool sv_ready = false, sv_box_ok = false; double sv_box[4] = {0, 0, 0, 0};
-    // hatch fill (hatch.hip): sv_fitted = orip_svg_fit has run on the resident paths, sv_hatched = orip_svg_hatch has appended to them (both cleared by the
-    // next flatten).  Scratch, free between calls: ht_pts = the quantised points with their group and successor, the groups' boxes and the call's counters;
-    // ht_rows = one direction's line ranges per group, chunk counts per edge and crossing counts per row; ht_x = its crossings, unsorted and sorted.
-    // orip_svg_hatch_angle (hatch_angle.hip) keeps the same contract on the same buffers, with its own records in them; either call sets sv_hatched
+    // hatch fills (hatch_common.h: the frame; hatch.hip, hatch_angle.hip: the rules): sv_fitted = orip_svg_fit has run on the resident paths, sv_hatched =
+    // orip_svg_hatch or orip_svg_hatch_angle has appended to them (both cleared by the next flatten).  Scratch, free between calls, carved by the frame for
+    // either rule with that rule's records: ht_pts = the plan (HtPlan: the quantised points with their group and successor, the groups' boxes, the call's
+    // counters, per group the lines' origin, count and first row, per edge the chunk counts and their scan); ht_rows = one direction's crossing counts and
+    // offsets per row and the list of rows for the block sort; ht_x = its crossings, unsorted and sorted, with the pairs' flags and their scan
     DBuf ht_pts, ht_rows, ht_x; bool sv_fitted = false, sv_hatched = false;
-    // resident after orip_svg_hatch: ht_grp int32[ht_nseg] = the caller's fill group of every appended hatch line (orip_svg_hatch_groups_fetch)
+    // resident after either hatch call: ht_grp int32[ht_nseg] = the caller's fill group of every appended hatch line (orip_svg_hatch_groups_fetch)
     DBuf ht_grp; int64_t ht_nseg = 0;
     // analyze_colors (analyze.hip): the 2^24-bin table of the image's colours, the kept colours in key order (keys u32[an_D], counts int64[an_D]) resident from
     // orip_colors_table until the next image or table; an_tmp = AnState + the compaction's block counts / offsets, an_km = the k-means inits, their segment

@@ -1,4 +1,4 @@
-// csrc/sv_round.h -- the unfused double arithmetic and the 4-decimal rounding that svg.hip (the fit) and hatch.hip (the hatch lines' end points) share
+// csrc/sv_round.h -- the unfused double arithmetic and the 4-decimal rounding that svg.hip (the fit) and the hatch fills (hatch_common.h: the quantisation and the hatch lines' end points; hatch.hip: the crossings) share
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -469,26 +469,26 @@ class Device:
         """v * s + o per axis, rounded to four decimals as float(f"{v:.4f}") rounds, in place on the resident paths"""
         self._ck(self.L.orip_svg_fit(self.h, float(sx), float(sy), float(ox), float(oy)))
 
+    def _svg_hatch(self, call, names, fill_group, steps_per_mm, spacing, inset, *rest) -> dict:
+        """either hatch call: the group array, the stats array, the resident count moved on by the appended segments -> the counts by name"""
+        g = np.ascontiguousarray(fill_group, np.int32).reshape(-1)
+        st = np.zeros(len(names), np.int64)
+        self._ck(call(self.h, _p(g) if len(g) else None, len(g), float(steps_per_mm), int(spacing), int(inset), *rest, _p(st)))
+        self._svg_n = len(g) + int(st[names.index("segments")])
+        return {k: int(v) for k, v in zip(names, st)}
+
     def svg_hatch(self, fill_group, steps_per_mm: float, spacing: int, inset: int, flags: int) -> dict:
         """hatch lines of the fitted resident paths, appended to them as 2-point paths (include/orip.h: orip_svg_hatch; flags: orip.lib.HATCH_*);
         fill_group int32 per resident subpath, -1 or its group -> {"groups", "lines", "crossings", "segments"}"""
-        g = np.ascontiguousarray(fill_group, np.int32).reshape(-1)
-        st = np.zeros(4, np.int64)
-        self._ck(self.L.orip_svg_hatch(self.h, _p(g) if len(g) else None, len(g), float(steps_per_mm), int(spacing), int(inset), int(flags), _p(st)))
-        self._svg_n = len(g) + int(st[3])
-        return {k: int(v) for k, v in zip(("groups", "lines", "crossings", "segments"), st)}
+        return self._svg_hatch(self.L.orip_svg_hatch, _l.HATCH_STATS, fill_group, steps_per_mm, spacing, inset, int(flags))
 
     def svg_hatch_angle(self, fill_group, steps_per_mm: float, spacing: int, inset: int, u, flags: int) -> dict:
         """hatch lines along the integer direction u = (ux, uy), exact on the step grid, appended as svg_hatch appends its own (include/orip.h:
         orip_svg_hatch_angle) -> {"groups", "lines", "crossings", "segments", "collapsed"}"""
-        g = np.ascontiguousarray(fill_group, np.int32).reshape(-1)
-        st = np.zeros(5, np.int64)
         ux, uy = (int(v) for v in u)
         if max(abs(ux), abs(uy)) >= 2 ** 31:
             raise ValueError("the hatch direction must fit 32 bits")
-        self._ck(self.L.orip_svg_hatch_angle(self.h, _p(g) if len(g) else None, len(g), float(steps_per_mm), int(spacing), int(inset), ux, uy, int(flags), _p(st)))
-        self._svg_n = len(g) + int(st[3])
-        return {k: int(v) for k, v in zip(("groups", "lines", "crossings", "segments", "collapsed"), st)}
+        return self._svg_hatch(self.L.orip_svg_hatch_angle, _l.HATCH_ANGLE_STATS, fill_group, steps_per_mm, spacing, inset, ux, uy, int(flags))
 
     def gcode_order(self, ends: np.ndarray | None, n: int | None = None) -> np.ndarray:
         """order of the paths (first x, first y, last x, last y) int32 [n, 4]; ends None: the n resident step polylines of gcode_to_steps"""

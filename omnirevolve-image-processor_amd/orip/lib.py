@@ -95,6 +95,8 @@ SIGNATURES = {
 }
 COMM_ID_BYTES = 128
 HATCH_SERPENTINE, HATCH_HORIZONTAL, HATCH_VERTICAL = 1, 2, 4
+HATCH_STATS = ("groups", "lines", "crossings", "segments")
+HATCH_ANGLE_STATS = HATCH_STATS + ("collapsed",)
 ORDER_REVERSE, ORDER_MAX_GROUPS = 1, 64
 MERGE_REVERSE = 1
 SIMPLIFY_TOL4_MAX, SIMPLIFY_LOCAL = (1 << 17) - 1, 1024      # include/orip.h: the largest tolerance in quarter steps; the points one wave finishes alone

@@ -141,6 +141,53 @@ def test_mixed_classes_in_one_call(dev):
     against_double(dev, groups, 25, 1, (4096, 5), BOTH)
 
 
+SMALL = [A([0, 300], [50, 310], [20, 390])]                                                     # the second group of the drawings below: rows for the wave sort
+
+
+def against_plain_double(dev, groups, spacing, inset, flags):
+    """orip_svg_hatch on thin_triangles (y < 250) and SMALL (y >= 300) in one direction against the numpy double: the points, the counts, the fetched groups"""
+    off, pts, fg = put(dev, groups)
+    want, wst = HD.hatch_segments(off, HD.quantise(pts, 1.0), fg, spacing, inset, flags)
+    st = dev.svg_hatch(fg, 1.0, spacing, inset, flags)
+    assert st == wst, (st, wst)
+    o2, p2 = dev.svg_paths()
+    assert len(o2) == len(off) + len(want) and np.array_equal(o2[:len(off)], off) and np.array_equal(np.diff(o2[len(off) - 1:]), np.full(len(want), 2))
+    assert np.array_equal(p2[:len(pts)], pts) and np.array_equal(p2[len(pts):], want.reshape(-1, 2).astype(np.float64))
+    assert np.array_equal(dev.svg_hatch_groups(st["segments"]), np.where(want[:, 1] < 250, 0, 1))
+    return want, st
+
+
+@pytest.mark.parametrize("n", [32, 33, 1024, 1025])
+def test_rows_on_the_class_boundaries(dev, n):
+    """n thin triangles in one group at spacing 10: every non-empty row of the group holds exactly 2 n crossings = 64 (a full wave, no padding lane), 66 (the
+    first row of the block sort), 2048 (a block row with no padding slot), 2050 (the first row that calls the large sort), under both rules"""
+    groups = [thin_triangles(n), SMALL]
+    small = HD.hatch_segments([0, 3], SMALL[0], [0], 10, 0, HD.HORIZONTAL)[1]
+    want, st = against_plain_double(dev, groups, 10, 0, HD.HORIZONTAL)
+    # the apex row's pairs have ex == sx and are dropped: 19 rows of n segments, and the crossings say that the twentieth holds 2 n too
+    assert st["crossings"] - small["crossings"] == 2 * n * 20 and st["lines"] - small["lines"] == 21 and np.array_equal(np.bincount(want[want[:, 1] < 250, 1] // 10)[1:], np.full(19, n))
+    small = HA.hatch_segments_angle([0, 3], SMALL[0], [0], 10, 0, (4096, 0), HA.HORIZONTAL)[1]
+    want, st, ks = against_double(dev, groups, 10, 0, (4096, 0), HA.HORIZONTAL)
+    # 20 lines, none with more than 2 n crossings (a triangle meets a line twice at most), 2 n * 20 in all: 2 n on each.  The pairs of the two top rows collapse
+    assert st["crossings"] - small["crossings"] == 2 * n * 20 and st["lines"] - small["lines"] == 20 and st["collapsed"] - small["collapsed"] == 2 * n
+
+
+def test_both_rules_alternate_on_one_context():
+    """the two rules carve ht_rows and ht_x with records of different sizes and reuse what the last call left: each of four calls on one device equals its
+    double, the second pair on a drawing a fifth the size, in buffers the other rule left larger than it needs"""
+    from orip.device import Device
+    d = Device(0)
+    try:
+        for n in (200, 40):
+            groups = [thin_triangles(n), SMALL]
+            want, st = against_plain_double(d, groups, 10, 1, HD.HORIZONTAL | HD.SERPENTINE)
+            assert st["segments"] > 10 * n
+            want, st, _ = against_double(d, groups, 10, 1, ANGLES[30], BOTH)
+            assert st["segments"] > 10 * n
+    finally:
+        d.close()
+
+
 def test_edges_of_many_chunks(dev):
     tall = A([0, 0], [300, 1000], [-200, 700])
     want, st, _ = against_double(dev, [[tall]], 3, 1, ANGLES[17.5], BOTH)

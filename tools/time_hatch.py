@@ -4,7 +4,8 @@
 Per drawing: flatten, fit and hatch on the device after a warm-up run, --reps timed runs, median and spread; the kernels' own times; the result checked against
 the numpy double (tests/hatch_double.py) by equality.  Beside them, as context only: the wall time of that numpy double on the same input, and for `single`
 the wall time of the reference's hatch_fill recorded in tests/golden/golden_hatch.npz where the fixture was made (another machine's CPU).
-usage: python tools/time_hatch.py [--groups N] [--reps R] [--out FILE.json]"""
+usage: python tools/time_hatch.py [--groups N] [--reps R] [--lib FILE] [--out FILE.json]
+--lib FILE loads another build of the library, so that two builds can be timed from one tree."""
 import argparse
 import json
 import os
@@ -18,7 +19,7 @@ import numpy as np
 import hatch_double as HD
 
 SPM, SPACING, INSET = 40.0, 20, 27
-KERNELS = ("k_ht_quant", "k_ht_cross_count", "k_ht_cross_fill", "k_ht_sort_wave", "k_ht_sort_block", "ht_sort_segmented", "k_ht_emit")
+KERNELS = ("k_ht_quant", "k_ht_cross_count", "k_ht_cross_fill", "k_ht_sort_wave", "k_ht_sort_block", "ht_sort_segmented", "k_ht_pairs", "k_ht_emit")
 
 
 def many_polygons(n_groups, seed=1):
@@ -58,15 +59,19 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--groups", type=int, default=100000)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--lib", default=None)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    from orip import lib
+    if a.lib:
+        lib.LIB_PATH = os.path.abspath(a.lib)
     from orip.device import Device
     from util import load
     G = load("golden_hatch.npz")
     dev = Device(0)
     try:
         measure(dev, many_polygons(500, seed=2), 1)
-        res = {"steps_per_mm": SPM, "spacing_steps": SPACING, "inset_steps": INSET, "reps": a.reps,
+        res = {"steps_per_mm": SPM, "spacing_steps": SPACING, "inset_steps": INSET, "reps": a.reps, "lib": a.lib,
                "many": measure(dev, many_polygons(a.groups), a.reps), "single": measure(dev, [[HD.single_polygon(100000)]], a.reps)}
     finally:
         dev.close()

@@ -3,7 +3,8 @@ seeded drawing at the same spacing and inset: --groups filled star polygons of 1
 steps per mm, 0.5 mm spacing, the default inset, serpentine, one family of lines.
 Per call: flatten and fit (not timed), then the hatch, after a warm-up run, --reps timed runs, median and spread; the kernels' own times from the profiling
 scopes; the ratio of the medians.  The result of the new call is checked against the sequential double (tests/hatch_angle_double.py) by equality.
-usage: python tools/time_hatch_angle.py [--groups N] [--reps R] [--angles A,B,..] [--out FILE.json]"""
+usage: python tools/time_hatch_angle.py [--groups N] [--reps R] [--angles A,B,..] [--lib FILE] [--out FILE.json]
+--lib FILE loads another build of the library, so that two builds can be timed from one tree."""
 import argparse
 import json
 import os
@@ -19,7 +20,7 @@ import hatch_angle_double as HA
 
 SPM, SPACING, INSET = 40.0, 20, 27
 FLAGS = HD.HORIZONTAL | HD.SERPENTINE
-KERNELS_PLAIN = ("k_ht_quant", "k_ht_cross_count", "k_ht_cross_fill", "k_ht_sort_wave", "k_ht_sort_block", "ht_sort_segmented", "k_ht_emit")
+KERNELS_PLAIN = ("k_ht_quant", "k_ht_cross_count", "k_ht_cross_fill", "k_ht_sort_wave", "k_ht_sort_block", "ht_sort_segmented", "k_ht_pairs", "k_ht_emit")
 KERNELS_ANGLE = ("k_ha_quant", "k_ha_cross_count", "k_ha_cross_fill", "k_ha_sort_wave", "k_ha_sort_block", "ha_sort_merge", "k_ha_pairs", "k_ha_emit")
 
 
@@ -45,15 +46,19 @@ def main():
     ap.add_argument("--groups", type=int, default=5000)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--angles", default="0,30,45")
+    ap.add_argument("--lib", default=None)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    from orip import lib
+    if a.lib:
+        lib.LIB_PATH = os.path.abspath(a.lib)
     from orip.device import Device
     from orip.svg import hatch_direction_vector
     groups = many_polygons(a.groups)
     table = HD.polys_table([[p / SPM for p in g] for g in groups])
     n_pts = int(table.sub_off[-1]) + table.n_sub
     dev = Device(0)
-    res = {"steps_per_mm": SPM, "spacing_steps": SPACING, "inset_steps": INSET, "reps": a.reps, "groups": a.groups, "edges": n_pts, "angle": {}}
+    res = {"steps_per_mm": SPM, "spacing_steps": SPACING, "inset_steps": INSET, "reps": a.reps, "lib": a.lib, "groups": a.groups, "edges": n_pts, "angle": {}}
     try:
         res["plain"] = measure(dev, table, lambda: dev.svg_hatch(table.fill_group, SPM, SPACING, INSET, FLAGS), KERNELS_PLAIN, a.reps)
         for ang in (float(v) for v in a.angles.split(",")):

@@ -53,7 +53,8 @@ typedef struct {
 typedef struct {
     double tap_diam, min_keep, tap_max_per;
     int32_t tap_max_v;
-    double max_jump, D_lines, D_taps, step_px;
+    double max_jump, D_lines, D_taps;
+    double step_px;        /* cut step: supported range step_px <= 1 (any such value cuts every pixel, as 1 does); orip_dedup_cross_begin refuses larger values and NaN */
     int32_t W, H;
 } orip_params10;
 

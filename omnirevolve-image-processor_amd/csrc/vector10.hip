@@ -340,6 +340,8 @@ extern "C" int orip_dedup_cross_begin(orip_ctx* c, const orip_params10* prm) {
     const int W = P.W, H = P.H;
     if (W <= 0 || H <= 0 || W > 16383 || H > 16383) ORIP_FAIL(c, "canvas %dx%d out of range", W, H);
     if (P.max_jump < 4.0) ORIP_FAIL(c, "max_join_jump_px < 4 is not supported (cut output is assumed jump-free)");
+    // steps of more than 1 px leave cut points further than sqrt(2) apart: neither "jumps are the identity" nor "lines paint as discs at their vertices" holds then
+    if (!(P.step_px <= 1.0)) ORIP_FAIL(c, "step_px %g > 1 is not supported (the cut is resampled every pixel)", P.step_px);
     const int rad_lines = (int)std::max<long long>(1, vs::round_half_even(P.D_lines)) / 2;
     const int rad_taps = (int)std::max<long long>(1, vs::round_half_even(P.D_taps / 2.0));
     if (rad_lines > ORIP_PAD - 2 || rad_taps > 200) ORIP_FAIL(c, "brush radius %d/%d too large for the padded raster", rad_lines, rad_taps);

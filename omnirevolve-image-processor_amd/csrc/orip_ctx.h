@@ -3,7 +3,7 @@
 // Environment switches that force a path, and the input that takes the same path without them.  The rule: a switch may only force a path that
 // some input reaches anyway (the tests then check it against the default one); a path that no input reaches is deleted, not kept behind a switch.
 //   ORIP_MORPH_BYTES       byte-plane morphology                      non-binary explicit masks
-//   ORIP_PACK_BYTES        byte-wise bit-plane packing / unpacking    W % 64 != 0
+//   ORIP_PACK_BYTES        any-width bit-plane packing / unpacking    W % 64 != 0          (bitplane.h: k_pack_bits, k_bits_to_bytes)
 //   ORIP_NMS_BYTES         byte-plane blur + NMS                      gauss_k != 3, or H / W below 8
 //   ORIP_NN_NOGRID         greedy order without the grid kernel       list sizes beyond the LDS / grid limits
 //   ORIP_PLOT_1WG          plot order without the LDS kernel          list sizes beyond the LDS limit
@@ -448,6 +448,9 @@ template <class F> static inline hipError_t orip_with_tmp(orip_ctx* c, F&& run) 
 
 // K bit planes of nw words each -> 0 / 255 byte planes, for rows that are multiples of 64 wide; enqueued on the calling lane's stream (raster02.hip)
 void orip_bits_expand16(orip_ctx* c, const unsigned long long* bits, uint8_t* dst, size_t nw, int K);
+// open (erode^n, dilate^n) then close (dilate^n, erode^n) of K planes, src -> dst, on bit planes when the input is binary; unpack == false leaves the
+// result in c->morphed_bits only (raster02.hip; stage 03 opens and closes its masks with it)
+int orip_morph_open_close(orip_ctx* c, const uint8_t* src, uint8_t* dst, int K, int shape, int k, int open_iters, int close_iters, bool labels_mode, bool unpack = true);
 // Time one kernel launch with HIP events on ctx->stream when profiling is enabled (bench.py roofline leg).
 struct ProfScope {
     orip_ctx* c; const char* name;

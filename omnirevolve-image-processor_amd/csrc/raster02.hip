@@ -5,7 +5,7 @@
 //   morph_pass   : erode / dilate with an arbitrary <=7x7 structuring element (02:151-154, 03:25-30)
 // All float arithmetic mirrors numpy / OpenCV evaluation order: compiled with -ffp-contract=off and written
 // with explicit __fmul_rn/__fadd_rn where the order matters.
-#include "orip_ctx.h"
+#include "bitplane.h"
 #include <cmath>
 #include <algorithm>
 
@@ -542,22 +542,12 @@ static unsigned long long make_se_bits(int shape, int k) {
 // ------------------------------------------------------------------------------------------------
 // Binary fast path of the same chain: a 0/255 mask packs to one bit per pixel (64 pixels per word, 2 MB per 4096^2 layer, so the
 // whole chain of passes runs out of L2), dilation = OR and erosion = AND of shifted rows.  Out-of-image pixels are neutral
-// (erode: ones, dilate: zeros), exactly as in k_morph_pass.
+// (erode: ones, dilate: zeros), exactly as in k_morph_pass.  Rows that are no multiple of 64 wide pack and unpack through the shared kernels of
+// bitplane.h (k_pack_bits<PackLabels>, bp_pack_bytes, bp_bits_to_bytes); multiples of 64 through the one-pass kernels below.
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_bits_pack(const u8* __restrict__ src, unsigned long long* __restrict__ bits, int H, int W, int Ww, int labels_mode) {
-    const int layer = blockIdx.z;
-    const size_t wi = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (wi >= (size_t)H * Ww) return;
-    const int y = (int)(wi / Ww), xw = (int)(wi % Ww);
-    const u8* row = (labels_mode ? src : src + (size_t)H * W * layer) + (size_t)y * W;
-    unsigned long long b = 0;
-    const int x0 = xw * 64, n = min(64, W - x0);
-    for (int j = 0; j < n; j++) { const u8 v = row[x0 + j]; if (labels_mode ? (v == layer) : (v != 0)) b |= 1ULL << j; }
-    bits[(size_t)H * Ww * layer + wi] = b;
-}
 // labels -> K bit planes in ONE pass over the label plane (rows that are multiples of 64 wide): a thread takes the 64 labels of a word as four 16-byte
 // loads and emits the word of every layer -- per layer and 4 labels an exact "byte equals l" test on the 32-bit word (zero-byte detection of w ^ l l l l) and a
-// multiply that gathers the four flag bits.  k_bits_pack read the plane once per layer, a byte per load and lane (0.25 ms at 4096^2 x 8 in front of the walks).
+// multiply that gathers the four flag bits (nib_gather).  The per-layer pack reads the plane once per layer (0.25 ms at 4096^2 x 8 in front of the walks).
 __global__ __launch_bounds__(256) void k_bits_pack_labels(const u8* __restrict__ labels, unsigned long long* __restrict__ bits, int H, int W, int Ww, int K) {
     const size_t wi = (size_t)blockIdx.x * 256 + threadIdx.x, nw = (size_t)H * Ww;
     if (wi >= nw) return;
@@ -572,32 +562,20 @@ __global__ __launch_bounds__(256) void k_bits_pack_labels(const u8* __restrict__
         for (int q = 0; q < 16; q++) {
             const uint32_t x = w[q] ^ rep;
             const uint32_t z = ~(((x & 0x7f7f7f7fu) + 0x7f7f7f7fu) | x | 0x7f7f7f7fu);          // 0x80 in every byte of x that is zero, 0 elsewhere
-            const uint32_t nib = ((z >> 7) * 0x00204081u) >> 21 & 0xfu;                        // bits 0, 8, 16, 24 -> bits 0 .. 3
+            const uint32_t nib = nib_gather(z >> 7);                                            // bits 0, 8, 16, 24 -> bits 0 .. 3
             b |= (unsigned long long)nib << (4 * q);
         }
         bits[nw * l + wi] = b;
     }
 }
-__global__ __launch_bounds__(256) void k_bits_unpack(const unsigned long long* __restrict__ bits, u8* __restrict__ dst, int H, int W, int Ww) {
-    const int layer = blockIdx.z;
-    const size_t p = (size_t)blockIdx.x * 256 + threadIdx.x;                // four pixels per thread
-    const size_t plane = (size_t)H * W;
-    if (p * 4 >= plane) return;
-    u8* d = dst + plane * layer;
-    for (int j = 0; j < 4; j++) {
-        const size_t q = p * 4 + j; if (q >= plane) break;
-        const int y = (int)(q / W), x = (int)(q % W);
-        d[q] = ((bits[((size_t)layer * H + y) * Ww + (x >> 6)] >> (x & 63)) & 1ULL) ? 255 : 0;
-    }
-}
 // one bit per pixel -> 0 / 255 bytes, 16 pixels (ONE 16-byte store) per thread: rows that are multiples of 64 wide (nw words per plane = H * W / 64),
-// blockIdx.z = plane.  Four bits become four bytes by a multiply that drops bit i at position 8 i (n * (1 + 2^7 + 2^14 + 2^21), no carries) and a mask.
+// blockIdx.z = plane.  Four bits become four bytes through nib_spread (bitplane.h).
 __global__ __launch_bounds__(256) void k_bits_expand16(const unsigned long long* __restrict__ bits, uint8_t* __restrict__ dst, size_t nw) {
     const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (t >= nw * 4) return;
     const unsigned long long w = bits[nw * blockIdx.z + (t >> 2)];
     const unsigned n16 = (unsigned)(w >> ((t & 3) * 16)) & 0xffffu;
-    auto four = [](unsigned n4) { return (((n4 & 0xfu) * 0x00204081u) & 0x01010101u) * 0xffu; };
+    auto four = [](unsigned n4) { return nib_spread(n4) * 0xffu; };
     uint4 o; o.x = four(n16); o.y = four(n16 >> 4); o.z = four(n16 >> 8); o.w = four(n16 >> 12);
     reinterpret_cast<uint4*>(dst + nw * 64 * blockIdx.z)[t] = o;
 }
@@ -644,7 +622,7 @@ __global__ __launch_bounds__(256) void k_not_binary(const u8* __restrict__ src, 
 
 // open (erode^n, dilate^n) then close (dilate^n, erode^n); src plane(s) -> dst plane(s); uses tmpA as ping-pong
 // unpack == false: when the chain ran on bit planes, leave the result there (c->morphed_bits) and do not write the byte planes (stage 03)
-int orip_morph_open_close(orip_ctx* c, const u8* src, u8* dst, int K, int shape, int k, int open_iters, int close_iters, bool labels_mode, bool unpack = true) {
+int orip_morph_open_close(orip_ctx* c, const u8* src, u8* dst, int K, int shape, int k, int open_iters, int close_iters, bool labels_mode, bool unpack) {
     if (k < 1 || k > 7 || (k & 1) == 0) ORIP_FAIL(c, "structuring element size %d unsupported (odd, 1..7)", k);
     int H = c->H, W = c->W; size_t plane = (size_t)H * W;
     unsigned long long se = make_se_bits(shape, k);
@@ -671,7 +649,8 @@ int orip_morph_open_close(orip_ctx* c, const u8* src, u8* dst, int K, int shape,
         dim3 gw((unsigned)cdiv((int64_t)nw, 256), 1, K), block(256);
         if (have_bits) { if (c->mask_bits == (const void*)B) std::swap(A, B); }        // the planes are already there (first or second half)
         else if (labels_mode && (W & 63) == 0 && !getenv("ORIP_PACK_BYTES")) hipLaunchKernelGGL(k_bits_pack_labels, dim3(gw.x), block, 0, LN(c).stream, src, A, H, W, Ww, K);
-        else hipLaunchKernelGGL(k_bits_pack, gw, block, 0, LN(c).stream, src, A, H, W, Ww, labels_mode ? 1 : 0);
+        else if (labels_mode) hipLaunchKernelGGL(k_pack_bits<PackLabels>, gw, block, 0, LN(c).stream, src, A, H, W, Ww);
+        else bp_pack_bytes(LN(c).stream, gw, src, A, H, W, Ww);
         c->mask_bits = nullptr;
         for (size_t i = 0; i < passes.size(); i++) {
             ProfScope ps(c, "k_morph_bits");
@@ -679,7 +658,7 @@ int orip_morph_open_close(orip_ctx* c, const u8* src, u8* dst, int K, int shape,
             std::swap(A, B);
         }
         if (unpack && (W & 63) == 0 && !getenv("ORIP_PACK_BYTES")) orip_bits_expand16(c, A, dst, nw, K);
-        else if (unpack) hipLaunchKernelGGL(k_bits_unpack, dim3((unsigned)cdiv((int64_t)plane, 1024), 1, K), block, 0, LN(c).stream, A, dst, H, W, Ww);
+        else if (unpack) bp_bits_to_bytes(LN(c).stream, gw, A, dst, H, W, Ww);
         else c->morphed_bits = A;
         HIPC(c, hipGetLastError());
         if (labels_mode && dst == c->masks.as<u8>()) c->mask_bits = A;      // stage 03 can start from the bit planes

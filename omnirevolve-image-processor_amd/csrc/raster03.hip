@@ -3,11 +3,9 @@
 //   k_blur_sobel_nms : cv2.GaussianBlur((k,k),0) + Canny front half (Sobel 3x3, L1 magnitude, NMS) fused in LDS
 //   hysteresis       : Canny back half as 8-connected components of candidate pixels (union-find CCL),
 //                      a component is an edge iff it holds a strong pixel (order independent)
-// Also hosts the bit-plane union-find CCL (orip_ccl_bits) reused by stage 04.
-#include "orip_ctx.h"
+// The components (orip_ccl_bits, block-raster ids) and the bits -> bytes fallback are the shared bit-plane blocks of bitplane.h.
+#include "bitplane.h"
 #include <algorithm>
-
-int orip_morph_open_close(orip_ctx* c, const u8* src, u8* dst, int K, int shape, int k, int open_iters, int close_iters, bool labels_mode, bool unpack = true);
 
 // ------------------------------------------------------------------------------------------------
 // Gaussian (fixed tables) + Sobel + NMS.  Output: two bit planes, candidates (weak or
@@ -212,80 +210,6 @@ __global__ __launch_bounds__(256) void k_nms_bits3(const unsigned long long* __r
     }
 }
 
-// ------------------------------------------------------------------------------------------------
-// Generic 8-connected union-find CCL over "foreground" pixels.  Pixels are identified by their
-// BLOCK-RASTER id  ((y>>1)*Wb + (x>>1))*4 + (y&1)*2 + (x&1): the root (minimum id) of a component
-// then names the first 2x2 block, in block-raster order, that holds one of its pixels -- the label
-// order block-based CCL scanners produce.  par[] is indexed by id, per layer.
-// ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int px_id(int y, int x, int Wb) { return (((y >> 1) * Wb + (x >> 1)) << 2) | ((y & 1) << 1) | (x & 1); }
-
-__device__ __forceinline__ int uf_find(const int* L, int a) {
-    int p = L[a];
-    while (p != a) { a = p; p = L[a]; }
-    return a;
-}
-__device__ __forceinline__ void uf_unite(int* L, int a, int b) {
-    bool done;
-    do {
-        a = uf_find(L, a); b = uf_find(L, b);
-        if (a < b) { int old = atomicMin(&L[b], a); done = (old == b); b = old; }
-        else if (b < a) { int old = atomicMin(&L[a], b); done = (old == a); a = old; }
-        else done = true;
-    } while (!done);
-}
-
-// components of bit planes (one bit per pixel, 64 per word, blockIdx.z = layer): a thread owns a word, returns at once when it is
-// empty and works on its RUNS (maximal stretches of set bits inside the word) otherwise.  Same ids (block raster) and the same union-find as above; an id
-// grows with x along a row, so the first pixel of a run has the run's smallest id.  mode 0 init: every pixel of a run points at the run's first pixel (the
-// forest in between is free: everything downstream reads only the flattened label, the component's minimum id).  mode 1 merge, one union per adjacency
-// between runs instead of up to four per pixel: the run that starts at bit 0 with the word on its left when that one ends set, and every run with one pixel
-// of each stretch of the row above inside its own extent widened by a pixel on either side (8-connectivity) -- a stretch there is part of one run of the
-// row above, and the runs of that row are joined among themselves by their own threads.  mode 2 flatten.
-__global__ __launch_bounds__(256) void k_ccl_bits(const unsigned long long* __restrict__ bits, int* __restrict__ par, int H, int W, int Ww, int mode) {
-    const size_t nw = (size_t)H * Ww, wi = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (wi >= nw) return;
-    const unsigned long long* b = bits + nw * blockIdx.z;
-    unsigned long long m = b[wi];
-    if (!m) return;
-    const int Wb = (W + 1) >> 1, Hb = (H + 1) >> 1;
-    int* L = par + (size_t)Wb * Hb * 4 * blockIdx.z;
-    const int y = (int)(wi / Ww), xw = (int)(wi % Ww), x0 = xw * 64;
-    if (mode == 2) {
-        while (m) { const int j = __ffsll((long long)m) - 1; m &= m - 1; const int id = px_id(y, x0 + j, Wb); L[id] = uf_find(L, id); }
-        return;
-    }
-    unsigned long long U = 0; bool left = false, nw_px = false, ne_px = false;
-    if (mode == 1) {
-        left = xw > 0 && (b[wi - 1] >> 63);
-        if (y > 0) { U = b[wi - Ww]; nw_px = xw > 0 && (b[wi - Ww - 1] >> 63); ne_px = xw + 1 < Ww && (b[wi - Ww + 1] & 1ULL); }
-    }
-    unsigned long long starts = m & ~(m << 1);
-    while (starts) {
-        const int s = __ffsll((long long)starts) - 1; starts &= starts - 1;
-        const unsigned long long inv = ~(m >> s);                          // (zero only for the full word)
-        const int e = s + (inv ? __ffsll((long long)inv) - 1 : 64) - 1;     // last pixel of the run
-        const int id = px_id(y, x0 + s, Wb);
-        if (mode == 0) { for (int j = s; j <= e; j++) L[px_id(y, x0 + j, Wb)] = id; continue; }
-        if (s == 0 && left) uf_unite(L, id, px_id(y, x0 - 1, Wb));
-        const int lo = s > 0 ? s - 1 : 0, hi = e < 63 ? e + 1 : 63;
-        const unsigned long long up = U & ((2ULL << hi) - 1ULL) & ~((1ULL << lo) - 1ULL);
-        if (s == 0 && nw_px && !(U & 1ULL)) uf_unite(L, id, px_id(y - 1, x0 - 1, Wb));      // (with U's bit 0 set, the stretch that starts there is the same run)
-        unsigned long long g = up & ~(up << 1);
-        while (g) { const int j = __ffsll((long long)g) - 1; g &= g - 1; uf_unite(L, id, px_id(y - 1, x0 + j, Wb)); }
-        if (e == 63 && ne_px && !(U >> 63)) uf_unite(L, id, px_id(y - 1, x0 + 64, Wb));
-    }
-}
-int orip_ccl_bits(orip_ctx* c, const unsigned long long* bits, int* par, int K) {
-    const int H = c->H, W = c->W, Ww = (W + 63) >> 6;
-    dim3 g((unsigned)cdiv((int64_t)H * Ww, 256), 1, K), block(256);
-    { ProfScope ps(c, "k_ccl_init"); hipLaunchKernelGGL(k_ccl_bits, g, block, 0, LN(c).stream, bits, par, H, W, Ww, 0); }
-    { ProfScope ps(c, "k_ccl_bits"); hipLaunchKernelGGL(k_ccl_bits, g, block, 0, LN(c).stream, bits, par, H, W, Ww, 1); }
-    { ProfScope ps(c, "k_ccl_flatten"); hipLaunchKernelGGL(k_ccl_bits, g, block, 0, LN(c).stream, bits, par, H, W, Ww, 2); }
-    HIPC(c, hipGetLastError());
-    return 0;
-}
-
 // hysteresis on bit planes: roots of components that hold a strong pixel, then edge = candidate whose root is marked
 __global__ __launch_bounds__(256) void k_hyst_bits_mark(const unsigned long long* __restrict__ strong_bits, const int* __restrict__ par, u8* __restrict__ strong_root, int H, int W, int Ww) {
     const size_t nw = (size_t)H * Ww, wi = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -307,19 +231,6 @@ __global__ __launch_bounds__(256) void k_hyst_bits_out(const unsigned long long*
         while (m) { const int j = __ffsll((long long)m) - 1; m &= m - 1; if (strong_root[pplane * blockIdx.z + par[pplane * blockIdx.z + px_id(y, x0 + j, Wb)]]) e |= 1ULL << j; }
     }
     edge_bits[nw * blockIdx.z + wi] = e;
-}
-__global__ __launch_bounds__(256) void k_bits_to_bytes03(const unsigned long long* __restrict__ bits, u8* __restrict__ dst, int H, int W, int Ww) {
-    const size_t nw = (size_t)H * Ww, w0 = ((size_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 64;
-    if (w0 >= nw) return;
-    const unsigned long long* b = bits + nw * blockIdx.z; u8* d = dst + (size_t)H * W * blockIdx.z;
-    const int lane = threadIdx.x & 63;
-    const unsigned long long mine = (w0 + lane < nw) ? b[w0 + lane] : 0ULL;
-    for (int j = 0; j < 64; j++) {
-        const size_t wi = w0 + j; if (wi >= nw) break;
-        const unsigned long long v = ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(mine >> 32), j) << 32) | (unsigned)__builtin_amdgcn_readlane((int)(unsigned)mine, j);
-        const int y = (int)(wi / Ww), xx = (int)(wi % Ww) * 64 + lane;
-        if (xx < W) d[(size_t)y * W + xx] = ((v >> lane) & 1ULL) ? 255 : 0;
-    }
 }
 
 extern "C" int orip_detect_edges(orip_ctx* c, int morph_k, int open_iters, int close_iters, int gauss_k, int low, int high) {
@@ -358,7 +269,7 @@ extern "C" int orip_detect_edges(orip_ctx* c, int morph_k, int open_iters, int c
     { ProfScope ps(c, "k_hyst_mark"); hipLaunchKernelGGL(k_hyst_bits_mark, gw, block, 0, LN(c).stream, strong, c->tmpD.as<int>(), LN(c).tmpE.as<u8>(), H, W, Ww); }
     { ProfScope ps(c, "k_hyst_out"); hipLaunchKernelGGL(k_hyst_bits_out, gw, block, 0, LN(c).stream, cand, c->tmpD.as<int>(), LN(c).tmpE.as<u8>(), ebits, H, W, Ww); }
     if ((W & 63) == 0 && !getenv("ORIP_PACK_BYTES")) orip_bits_expand16(c, ebits, c->edges.as<u8>(), (size_t)H * Ww, K);
-    else hipLaunchKernelGGL(k_bits_to_bytes03, gw, block, 0, LN(c).stream, ebits, c->edges.as<u8>(), H, W, Ww);
+    else bp_bits_to_bytes(LN(c).stream, gw, ebits, c->edges.as<u8>(), H, W, Ww);
     HIPC(c, hipGetLastError());
     c->edge_bits = ebits;
     return 0;

@@ -1,75 +1,18 @@
 // csrc/raster04.hip -- stage 04 (04_find_contours.py vectorize_layer, 04:214-230) on gfx950:
-//   k_thin_bits04     : one Zhang-Suen sub-iteration on bit planes with the reference's rotated neighbour numbering (04:50-93)
-//   CCL               : union-find kernels of raster03.hip (component order = block-raster)
+//   k_thin_bits04     : one Zhang-Suen sub-iteration on bit planes with the reference's rotated neighbour numbering (04:50-93; bitplane.h: zs_delete)
+//   CCL               : orip_ccl_bits (bitplane.h; component order = block-raster)
 //   k_bits_to_skel_state : skeleton bytes and per-pixel state byte (fg, endpoint deg==1, junction deg>=3)  (04:128-130)
-//   k_compact_*_bits  : popcount / prefix-sum compaction of skeleton pixels in raster order (04:144,174)
+//   compaction        : popcount / prefix-sum compaction of skeleton pixels in raster order (04:144,174; bitplane.h: bp_compact_count, k_compact_write_bits<Emit04>)
 //   radix sort        : rocPRIM stable sort of (layer, component root) keys -> per-component pixel lists
 //   k_trace / k_write_walks : the centerline walker (walker.h), exact serial semantics (04:137-205): one wave per component
 //                       runs twice (count, then write); the guard-bounded "bounce" tails of phase-2 walks are
 //                       detected as cycles of the (prev,cur) state and written by k_expand_cycles in parallel.
-#include "orip_ctx.h"
+#include "bitplane.h"
 #include "walker.h"
 #include <rocprim/rocprim.hpp>
 #include <algorithm>
 #include <cstdlib>
 
-int orip_ccl_bits(orip_ctx* c, const unsigned long long* bits, int* par, int K);
-
-// ------------------------------------------------------------------------------------------------
-// Ordered compaction (raster order inside a layer, layers in order) of the thinned BIT planes ([K][H][Ww] words; a set bit = a skeleton
-// pixel = ST_FG in the state plane): a thread owns a word, a block 256 consecutive words of the flattened planes; popcounts, a shuffle scan
-// inside the wave, LDS across the 4 waves of a block, block offsets from an exclusive scan of per-block counts.  (Reading the state bytes
-// instead is 134 MB at 4096^2 x 8, 0.43 ms in front of the walks; the planes are 16 MB and almost empty.)
-// ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_compact_count_bits(const unsigned long long* __restrict__ bits, size_t nwords, unsigned* __restrict__ counts) {
-    __shared__ unsigned wsum[4];
-    const size_t wi = (size_t)blockIdx.x * 256 + threadIdx.x;
-    unsigned cnt = wi < nwords ? (unsigned)__popcll(bits[wi]) : 0u;
-    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_down(cnt, o, 64);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) counts[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-}
-__global__ __launch_bounds__(256) void k_compact_write_bits(const unsigned long long* __restrict__ bits, const int* __restrict__ par, size_t nwords, size_t nw, int H, int W, int Ww,
-                                                            const unsigned* __restrict__ block_off, unsigned* __restrict__ keys, unsigned* __restrict__ lin) {
-    __shared__ unsigned wsum[4];
-    const int Wb = (W + 1) >> 1, Hb = (H + 1) >> 1; const int64_t pplane = (int64_t)Wb * Hb * 4;
-    const size_t wi = (size_t)blockIdx.x * 256 + threadIdx.x;
-    unsigned long long m = wi < nwords ? bits[wi] : 0ULL;
-    const unsigned cnt = (unsigned)__popcll(m);
-    unsigned inc = cnt;
-    const int lane = threadIdx.x & 63;
-    for (int o = 1; o < 64; o <<= 1) { unsigned t = __shfl_up(inc, o, 64); if (lane >= o) inc += t; }
-    if (lane == 63) wsum[threadIdx.x >> 6] = inc;
-    __syncthreads();
-    if (!m) return;
-    unsigned pos = block_off[blockIdx.x] + inc - cnt;
-    for (int w = 0; w < (int)(threadIdx.x >> 6); w++) pos += wsum[w];
-    const int layer = (int)(wi / nw); const size_t wl = wi - (size_t)layer * nw;
-    const int y = (int)(wl / Ww), x0 = (int)(wl % Ww) * 64;
-    while (m) {
-        const int j = __ffsll((long long)m) - 1; m &= m - 1;
-        const int x = x0 + j;
-        const int id = (((y >> 1) * Wb + (x >> 1)) << 2) | ((y & 1) << 1) | (x & 1);
-        keys[pos] = ((unsigned)layer << 26) | (unsigned)par[pplane * layer + id];
-        lin[pos] = (unsigned)((int64_t)y * W + x);
-        pos++;
-    }
-}
-
-__global__ __launch_bounds__(256) void k_heads(const unsigned* __restrict__ keys, int64_t m, unsigned* __restrict__ head) {
-    int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= m) return;
-    head[i] = (i == 0 || keys[i] != keys[i - 1]) ? 1u : 0u;
-}
-// comp_start[c] = first element of component c; comp_start[nc] = m
-__global__ __launch_bounds__(256) void k_comp_starts(const unsigned* __restrict__ head, const unsigned* __restrict__ head_scan, int64_t m,
-                                                     unsigned* __restrict__ comp_start, unsigned nc) {
-    int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i == 0) comp_start[nc] = (unsigned)m;
-    if (i >= m) return;
-    if (head[i]) comp_start[head_scan[i]] = (unsigned)i;
-}
 __global__ __launch_bounds__(256) void k_gather_head_layers(const unsigned* __restrict__ keys, const unsigned* __restrict__ cs, unsigned nc, unsigned* __restrict__ out) {
     unsigned i = blockIdx.x * 256 + threadIdx.x;
     if (i < nc) out[i] = keys[cs[i]] >> 26;
@@ -78,8 +21,6 @@ __global__ __launch_bounds__(256) void k_gather_head_layers(const unsigned* __re
 // ------------------------------------------------------------------------------------------------
 // Walker.  NEIGH8 order (dx,dy) from 04:12.
 // ------------------------------------------------------------------------------------------------
-#include "walker.h"
-
 // one wavefront per component; wave i takes component comp_order[i] (largest components first, so the long serial
 // chains start immediately and the small ones fill in behind them)
 __global__ __launch_bounds__(64) void k_trace(WalkArgs A) {
@@ -160,55 +101,14 @@ __global__ __launch_bounds__(64) void k_vown(WalkArgs A, const unsigned* __restr
 // ---- thinning_zhangsuen (04:35-99) and the state bytes on bit planes: one bit per pixel, 64 pixels per word, blockIdx.z = layer.
 // The reference numbers the neighbours from the south (P2 = (y+1, x), then clockwise as seen with y down: SW, W, NW, N, NE, E, SE);
 // A(p) counts transitions around the same cycle wherever it starts, B(p) is symmetric, only the two product conditions differ from
-// the usual orientation.  Bit-sliced evaluation as in stage 08-B (vector08b.hip: zs_word_del).
-__global__ __launch_bounds__(256) void k_bytes_to_bits04(const u8* __restrict__ src, unsigned long long* __restrict__ bits, int H, int W, int Ww) {
-    const size_t nw = (size_t)H * Ww, w0 = ((size_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 64;
-    if (w0 >= nw) return;
-    const u8* s = src + (size_t)H * W * blockIdx.z; unsigned long long* b = bits + nw * blockIdx.z;
-    const int lane = threadIdx.x & 63;
-    unsigned long long mine = 0;
-    for (int j = 0; j < 64; j++) {
-        const size_t wi = w0 + j; bool fg = false;
-        if (wi < nw) { const int y = (int)(wi / Ww), x = (int)(wi % Ww) * 64 + lane; fg = x < W && s[(size_t)y * W + x] != 0; }
-        const unsigned long long m = __ballot(fg);
-        if (lane == j) mine = m;
-    }
-    if (w0 + lane < nw) b[w0 + lane] = mine;
-}
-struct Nb8 { unsigned long long N, NE, E, SE, S, SW, W, NW; };
-__device__ __forceinline__ Nb8 neighbour_planes(const unsigned long long* __restrict__ s, int H, int Ww, int y, int xw, unsigned long long M) {
-    auto W64 = [&](int yy, int xx) -> unsigned long long { return (yy < 0 || yy >= H || xx < 0 || xx >= Ww) ? 0ULL : s[(size_t)yy * Ww + xx]; };
-    const unsigned long long U = W64(y - 1, xw), UL = W64(y - 1, xw - 1), UR = W64(y - 1, xw + 1), ML = W64(y, xw - 1), MR = W64(y, xw + 1);
-    const unsigned long long D = W64(y + 1, xw), DL = W64(y + 1, xw - 1), DR = W64(y + 1, xw + 1);
-    Nb8 n; n.N = U; n.NE = (U >> 1) | (UR << 63); n.E = (M >> 1) | (MR << 63); n.SE = (D >> 1) | (DR << 63);
-    n.S = D; n.SW = (D << 1) | (DL >> 63); n.W = (M << 1) | (ML >> 63); n.NW = (U << 1) | (UL >> 63);
-    return n;
-}
-// bit-sliced neighbour count: b0 ones, b1 twos, b2 fours, b3 eights
-__device__ __forceinline__ void count8(const Nb8& n, unsigned long long& b0, unsigned long long& b1, unsigned long long& b2, unsigned long long& b3) {
-    auto FA = [](unsigned long long a, unsigned long long b, unsigned long long c, unsigned long long& sum, unsigned long long& carry) { const unsigned long long t = a ^ b; sum = t ^ c; carry = (a & b) | (t & c); };
-    unsigned long long s1, c1, s2, c2, s4, c4, s5, c5;
-    FA(n.N, n.NE, n.E, s1, c1); FA(n.SE, n.S, n.SW, s2, c2);
-    const unsigned long long s3 = n.W ^ n.NW, c3 = n.W & n.NW;
-    FA(s1, s2, s3, s4, c4); FA(c1, c2, c3, s5, c5);
-    const unsigned long long c6 = s5 & c4;
-    b0 = s4; b1 = s5 ^ c4; b2 = c5 ^ c6; b3 = c5 & c6;
-}
+// the usual orientation: zs_delete<ZS_ROTATED> of bitplane.h, where the bit-sliced evaluation is described.
 __global__ __launch_bounds__(256) void k_thin_bits04(const unsigned long long* __restrict__ src, unsigned long long* __restrict__ dst, int H, int Ww, int sub, int* __restrict__ changed) {
     const size_t nw = (size_t)H * Ww, wi = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (wi >= nw) return;
     const unsigned long long* s = src + nw * blockIdx.z; unsigned long long* d = dst + nw * blockIdx.z;
     const unsigned long long M = s[wi];
     if (!M) { d[wi] = 0; return; }
-    const Nb8 n = neighbour_planes(s, H, Ww, (int)(wi / Ww), (int)(wi % Ww), M);
-    unsigned long long b0, b1, b2, b3; count8(n, b0, b1, b2, b3);
-    const unsigned long long Bok = (b1 | b2) & ~b3 & ~(b2 & b1 & b0);          // 2 <= B <= 6
-    const unsigned long long P2 = n.S, P3 = n.SW, P4 = n.W, P5 = n.NW, P6 = n.N, P7 = n.NE, P8 = n.E, P9 = n.SE;
-    unsigned long long one = 0, two = 0;
-    auto TR = [&](unsigned long long a, unsigned long long b) { const unsigned long long t = ~a & b; two |= one & t; one |= t; };
-    TR(P2, P3); TR(P3, P4); TR(P4, P5); TR(P5, P6); TR(P6, P7); TR(P7, P8); TR(P8, P9); TR(P9, P2);
-    const unsigned long long cnd = sub == 0 ? (~(P2 & P4 & P6) & ~(P4 & P6 & P8)) : (~(P2 & P4 & P8) & ~(P2 & P6 & P8));
-    const unsigned long long del = M & (one & ~two) & Bok & cnd;
+    const unsigned long long del = zs_delete<ZS_ROTATED>(M, neighbour_planes(s, H, Ww, (int)(wi / Ww), (int)(wi % Ww), M), sub);
     if (del) *changed = 1;
     d[wi] = M & ~del;
 }
@@ -238,7 +138,7 @@ __global__ __launch_bounds__(256) void k_bits_to_skel_state(const unsigned long 
         if (w0 + lane >= nw) return;
         const size_t px = (w0 + lane) * 64;                 // == y * W + 64 xw
         uint4* ok = reinterpret_cast<uint4*>(sk + px); uint4* oo = reinterpret_cast<uint4*>(so + px);
-        auto spread = [](unsigned long long v, int g) { return ((((unsigned)(v >> (4 * g)) & 0xfu) * 0x00204081u) & 0x01010101u); };      // 4 bits -> 0 / 1 in 4 bytes
+        auto spread = [](unsigned long long v, int g) { return nib_spread((unsigned)(v >> (4 * g))); };      // 4 bits -> 0 / 1 in 4 bytes
 #pragma unroll
         for (int q = 0; q < 4; q++) {
             unsigned a[4], b[4];
@@ -253,12 +153,9 @@ __global__ __launch_bounds__(256) void k_bits_to_skel_state(const unsigned long 
         }
         return;
     }
-    auto bc = [&](unsigned long long v, int j) -> unsigned long long {
-        return ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(v >> 32), j) << 32) | (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, j);
-    };
     for (int j = 0; j < 64; j++) {
         const size_t wi = w0 + j; if (wi >= nw) break;
-        const unsigned long long f = bc(fg, j), e = bc(en, j), q = bc(ju, j), t2 = bc(d2, j);
+        const unsigned long long f = bcast64(fg, j), e = bcast64(en, j), q = bcast64(ju, j), t2 = bcast64(d2, j);
         const int y = (int)(wi / Ww), x = (int)(wi % Ww) * 64 + lane;
         if (x < W) {
             const bool on = (f >> lane) & 1ULL;
@@ -453,7 +350,7 @@ extern "C" int orip_contours_prepare(orip_ctx* c) {
     // Its only writers are this call's thinning and k_bits_to_skel_state (orip_detect_edges, the other user of orip_edge_planes, sizes the second set and
     // writes the first only), so the thinning goes behind the chain work of the prepare before -- long finished in a resident chain, whose traces wait for ev3
     if (R.chains) HIPC(c, hipStreamWaitEvent(LN(c).stream, LN(c).ev3, 0));
-    if (c->edge_bits != (const void*)bA) hipLaunchKernelGGL(k_bytes_to_bits04, gw, block, 0, LN(c).stream, c->edges.as<u8>(), bA, H, W, Ww);   // stage 03 may have left them
+    if (c->edge_bits != (const void*)bA) bp_pack_bytes(LN(c).stream, gw, c->edges.as<u8>(), bA, H, W, Ww);   // stage 03 may have left them
     c->edge_bits = nullptr;
     // two iterations per round trip to the host, each with its own flag (an iteration after an unchanged one changes nothing either)
     int* d_ch2 = fl->thin_changed;
@@ -498,7 +395,7 @@ extern "C" int orip_contours_prepare(orip_ctx* c) {
     const int nblk = (int)cdiv((int64_t)nwords, 256);
     unsigned *d_cnt, *d_boff; { Carve L; L.each(nblk + 1, d_cnt, d_boff); HIPC(c, L.commit(LN(c).tmpE, 64)); }
     HIPC(c, hipMemsetAsync(d_cnt + nblk, 0, sizeof(unsigned), LN(c).stream));
-    { ProfScope ps(c, "k_compact_count"); hipLaunchKernelGGL(k_compact_count_bits, dim3(nblk), block, 0, LN(c).stream, bA, nwords, d_cnt); }
+    { ProfScope ps(c, "k_compact_count"); bp_compact_count(LN(c).stream, (unsigned)nblk, bA, nwords, d_cnt); }
     HIPC(c, orip_with_tmp(c, [&](void* tmp, size_t& bytes) { return rocprim::exclusive_scan(tmp, bytes, (const unsigned*)d_cnt, d_boff, 0u, (size_t)nblk + 1, rocprim::plus<unsigned>(), LN(c).stream); }));
     unsigned M = 0;
     HIPC(c, hipMemcpyAsync(&M, d_boff + nblk, sizeof(unsigned), hipMemcpyDeviceToHost, LN(c).stream));
@@ -513,11 +410,11 @@ extern "C" int orip_contours_prepare(orip_ctx* c) {
     // keys / lin (double buffers for the sort)
     unsigned *keys_in, *lin_in, *keys, *lin;
     { Carve L; L.each(M, keys_in, lin_in, keys, lin); HIPC(c, L.commit(LN(c).vtmp[VT0_KEYS], 64)); }
-    { ProfScope ps(c, "k_compact_write"); hipLaunchKernelGGL(k_compact_write_bits, dim3(nblk), block, 0, LN(c).stream, bA, c->tmpD.as<int>(), nwords, nw, H, W, Ww, d_boff, keys_in, lin_in); }
+    { ProfScope ps(c, "k_compact_write"); hipLaunchKernelGGL(k_compact_write_bits<Emit04>, dim3(nblk), block, 0, LN(c).stream, bA, nwords, d_boff, Emit04{c->tmpD.as<int>(), nw, H, W, Ww}, keys_in, lin_in); }
     { ProfScope ps(c, "radix_sort_pairs"); HIPC(c, orip_with_tmp(c, [&](void* tmp, size_t& bytes) { return rocprim::radix_sort_pairs(tmp, bytes, keys_in, keys, lin_in, lin, (size_t)M, 0, 30, LN(c).stream); })); }
     // ---- component segmentation
     unsigned *head, *head_scan; { Carve L; L.each(M, head, head_scan); HIPC(c, L.commit(LN(c).vtmp[VT0_HEADS], 64)); }
-    hipLaunchKernelGGL(k_heads, dim3(cdiv(M, 256)), block, 0, LN(c).stream, keys, (int64_t)M, head);
+    bp_heads(LN(c).stream, keys, (int64_t)M, (int64_t)M, head);
     HIPC(c, orip_with_tmp(c, [&](void* tmp, size_t& bytes) { return rocprim::exclusive_scan(tmp, bytes, (const unsigned*)head, head_scan, 0u, (size_t)M, rocprim::plus<unsigned>(), LN(c).stream); }));
     unsigned last2[2];
     HIPC(c, hipMemcpyAsync(&last2[0], head_scan + (M - 1), 4, hipMemcpyDeviceToHost, LN(c).stream));
@@ -527,7 +424,7 @@ extern "C" int orip_contours_prepare(orip_ctx* c) {
     R.NC = NC;
     HIPC(c, LN(c).vtmp[VT0_COMP_START].ensure((size_t)(NC + 2) * 4 + 64));
     unsigned* comp_start = LN(c).vtmp[VT0_COMP_START].as<unsigned>();
-    hipLaunchKernelGGL(k_comp_starts, dim3(cdiv(M, 256)), block, 0, LN(c).stream, head, head_scan, (int64_t)M, comp_start, NC);
+    bp_comp_starts(LN(c).stream, head, head_scan, (int64_t)M, comp_start, NC);
     R.h_cs.assign(NC + 1, 0); std::vector<unsigned> h_keyfirst(NC);
     HIPC(c, hipMemcpyAsync(R.h_cs.data(), comp_start, (size_t)(NC + 1) * 4, hipMemcpyDeviceToHost, LN(c).stream));
     // layer of each component (key of its first element)

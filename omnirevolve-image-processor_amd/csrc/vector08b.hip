@@ -3,24 +3,16 @@
 // Stage B runs all clusters at once on one padded canvas: clusters are >= 76 px apart
 // in one axis, so per-ROI rasterise / thin / label equals whole-canvas rasterise / thin / label (DESIGN.md "stage 08-B").
 // Layout: the kernels (groups, raster, Zhang-Suen thinning, components, paths), then the host side: one function per phase (b_groups, b_raster_thin,
-// b_components, b_paths) and dedup08_b, which calls them in order.  Scans and sorts go through vscan_excl / vsort_pairs (vec_common.h).
+// b_components, b_paths) and dedup08_b, which calls them in order.  Scans and sorts go through vscan_excl / vsort_pairs (vec_common.h); the bit-plane
+// kernels (pack, thinning word, CCL, compaction, heads, bits -> bytes) are the shared blocks of bitplane.h, with the linear pixel id y * Wp + x.
 #include "vec08.h"
+#include "bitplane.h"
 #include <cstdio>
 #define PAD8 64
 
 namespace {
 
 // ================================================================= B: _post_skeleton_merge
-__device__ __forceinline__ int ufind(const int* L, int a) { int p = L[a]; while (p != a) { a = p; p = L[a]; } return a; }
-__device__ __forceinline__ void uunite(int* L, int a, int b) {
-    bool done;
-    do {
-        a = ufind(L, a); b = ufind(L, b);
-        if (a < b) { int old = atomicMin(&L[b], a); done = (old == b); b = old; }
-        else if (b < a) { int old = atomicMin(&L[a], b); done = (old == a); a = old; }
-        else done = true;
-    } while (!done);
-}
 __global__ __launch_bounds__(256) void k_iota(int* a, int n) { int i = blockIdx.x * 256 + threadIdx.x; if (i < n) a[i] = i; }
 __global__ __launch_bounds__(256) void k_bbox_pairs(const PolyFeat* __restrict__ f, int n, int exp, int* __restrict__ par) {
     // bboxes expanded by exp on each side overlap  <=>  not separated (08:41-42)
@@ -28,7 +20,7 @@ __global__ __launch_bounds__(256) void k_bbox_pairs(const PolyFeat* __restrict__
         int ax0 = f[i].x0 - exp, ay0 = f[i].y0 - exp, ax1 = f[i].x1 + exp, ay1 = f[i].y1 + exp;
         for (int j = i + 1 + threadIdx.x; j < n; j += 256) {
             int bx0 = f[j].x0 - exp, by0 = f[j].y0 - exp, bx1 = f[j].x1 + exp, by1 = f[j].y1 + exp;
-            if (!(ax1 < bx0 || bx1 < ax0 || ay1 < by0 || by1 < ay0)) uunite(par, i, j);
+            if (!(ax1 < bx0 || bx1 < ax0 || ay1 < by0 || by1 < ay0)) uf_unite(par, i, j);
         }
     }
 }
@@ -41,7 +33,7 @@ __global__ __launch_bounds__(256) void k_group_init(GroupInfo* g, int n) {
 __global__ __launch_bounds__(256) void k_group_accum(const PolyFeat* __restrict__ f, int n, int exp, int* __restrict__ par, GroupInfo* __restrict__ g, unsigned* __restrict__ is_root) {
     int i = blockIdx.x * 256 + threadIdx.x; if (i > n) return;
     if (i == n) { is_root[i] = 0; return; }
-    int r = ufind(par, i); par[i] = r;
+    int r = uf_find(par, i); par[i] = r;
     is_root[i] = (r == i) ? 1u : 0u;
     atomicMin(&g[r].x0, f[i].x0 - exp); atomicMin(&g[r].y0, f[i].y0 - exp); atomicMax(&g[r].x1, f[i].x1 + exp); atomicMax(&g[r].y1, f[i].y1 + exp);
     unsigned long long key = ((unsigned long long)(~__float_as_uint(f[i].per)) << 32) | (unsigned)i;     // longest, first index on ties (08:391)
@@ -74,60 +66,8 @@ __global__ __launch_bounds__(256) void k_stamp_groups(const int64_t* __restrict_
         }
     }
 }
-// ---- standard-orientation Zhang-Suen thinning (08:349-366) on bit planes (one bit per pixel, 64 pixels per word; the padded canvas is
-// 12.8 MB, i.e. cache-resident).  A sub-iteration evaluates the conditions for 64 pixels at once with bit-sliced logic: the eight neighbour
-// planes come from the three rows by word shifts, B = P2+...+P9 from a carry-save adder tree, A == 1 ("exactly one 0->1 transition") from
-// a one/two accumulator.  Out-of-image pixels are background.
-__global__ __launch_bounds__(256) void k_gid_to_bits(const unsigned* __restrict__ gid, unsigned long long* __restrict__ bits, int H, int W, int Ww) {
-    // a wave packs 64 consecutive words: one coalesced 256-byte read + one ballot per word, then one coalesced write of the 64 words
-    const size_t w0 = ((size_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 64, nw = (size_t)H * Ww;
-    if (w0 >= nw) return;
-    const int lane = threadIdx.x & 63;
-    unsigned long long mine = 0;
-    for (int j = 0; j < 64; j++) {
-        const size_t wi = w0 + j;
-        bool fg = false;
-        if (wi < nw) { const int y = (int)(wi / Ww), x = (int)(wi % Ww) * 64 + lane; fg = x < W && gid[(size_t)y * W + x] != 0; }
-        const unsigned long long b = __ballot(fg);
-        if (lane == j) mine = b;
-    }
-    if (w0 + lane < nw) bits[w0 + lane] = mine;
-}
-__global__ __launch_bounds__(256) void k_bits_to_mask(const unsigned long long* __restrict__ bits, u8* __restrict__ m, int H, int W, int Ww) {
-    const size_t w0 = ((size_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 64, nw = (size_t)H * Ww;
-    if (w0 >= nw) return;
-    const int lane = threadIdx.x & 63;
-    const unsigned long long mine = (w0 + lane < nw) ? bits[w0 + lane] : 0ULL;
-    for (int j = 0; j < 64; j++) {
-        const size_t wi = w0 + j; if (wi >= nw) break;
-        const unsigned long long b = ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(mine >> 32), j) << 32) | (unsigned)__builtin_amdgcn_readlane((int)(unsigned)mine, j);
-        const int y = (int)(wi / Ww), x = (int)(wi % Ww) * 64 + lane;
-        if (x < W) m[(size_t)y * W + x] = ((b >> lane) & 1ULL) ? 255 : 0;
-    }
-}
-// one Zhang-Suen sub-iteration on a 64-pixel word, bit-sliced: M = the word, the other eight = its neighbour words; returns the pixels it deletes
-__device__ __forceinline__ unsigned long long zs_word_del(unsigned long long M, unsigned long long U, unsigned long long UL, unsigned long long UR, unsigned long long ML,
-                                                          unsigned long long MR, unsigned long long D, unsigned long long DL, unsigned long long DR, int sub) {
-    // neighbour planes in the reference's numbering: P2 = north, then clockwise
-    const unsigned long long P2 = U, P3 = (U >> 1) | (UR << 63), P4 = (M >> 1) | (MR << 63), P5 = (D >> 1) | (DR << 63);
-    const unsigned long long P6 = D, P7 = (D << 1) | (DL >> 63), P8 = (M << 1) | (ML >> 63), P9 = (U << 1) | (UL >> 63);
-    // B = number of foreground neighbours, bit-sliced (b0 ones, b1 twos, b2 fours, b3 eights)
-    auto FA = [](unsigned long long a, unsigned long long b, unsigned long long c, unsigned long long& sum, unsigned long long& carry) { const unsigned long long t = a ^ b; sum = t ^ c; carry = (a & b) | (t & c); };
-    unsigned long long s1, c1, s2, c2, s4, c4, s5, c5;
-    FA(P2, P3, P4, s1, c1); FA(P5, P6, P7, s2, c2);
-    const unsigned long long s3 = P8 ^ P9, c3 = P8 & P9;
-    FA(s1, s2, s3, s4, c4);
-    FA(c1, c2, c3, s5, c5);
-    const unsigned long long b0 = s4, b1 = s5 ^ c4, c6 = s5 & c4, b2 = c5 ^ c6, b3 = c5 & c6;
-    const unsigned long long Bok = (b1 | b2) & ~b3 & ~(b2 & b1 & b0);          // 2 <= B <= 6
-    // A = number of 0 -> 1 transitions in P2, P3, ..., P9, P2: exactly one
-    unsigned long long one = 0, two = 0;
-    auto TR = [&](unsigned long long a, unsigned long long b) { const unsigned long long t = ~a & b; two |= one & t; one |= t; };
-    TR(P2, P3); TR(P3, P4); TR(P4, P5); TR(P5, P6); TR(P6, P7); TR(P7, P8); TR(P8, P9); TR(P9, P2);
-    const unsigned long long Aok = one & ~two;
-    const unsigned long long cnd = sub == 0 ? (~(P2 & P4 & P6) & ~(P4 & P6 & P8)) : (~(P2 & P4 & P8) & ~(P2 & P6 & P8));
-    return M & Aok & Bok & cnd;
-}
+// ---- standard-orientation Zhang-Suen thinning (08:349-366) on the bit plane of the padded canvas (12.8 MB, i.e. cache-resident): zs_delete<ZS_STANDARD>
+// of bitplane.h evaluates a sub-iteration for the 64 pixels of a word.  Out-of-image pixels are background.
 // `iters` whole iterations (two sub-iterations each) in ONE launch: a block keeps a tile of 64 rows x 2 words plus a halo of ZS_HALO rows / one word on
 // every side in LDS and runs the sub-iterations there.  A sub-iteration reads the 3x3 neighbourhood, so after t of them the tile is exact everywhere at
 // least t pixels inside the staged region: with iters <= ZS_HALO / 2 the core is exact after all of them, whatever the neighbouring tiles do meanwhile
@@ -162,7 +102,7 @@ __global__ __launch_bounds__(256) void k_zs_tile(const unsigned long long* __res
                 unsigned long long out = 0;
                 if (M) {
                     auto G = [&](int rr, int ww) -> unsigned long long { return (rr < 0 || rr >= ZS_ROWS || ww < 0 || ww > 3) ? 0ULL : T[cur][rr][ww]; };
-                    const unsigned long long del = zs_word_del(M, G(r - 1, wx), G(r - 1, wx - 1), G(r - 1, wx + 1), G(r, wx - 1), G(r, wx + 1), G(r + 1, wx), G(r + 1, wx - 1), G(r + 1, wx + 1), t & 1);
+                    const unsigned long long del = zs_delete<ZS_STANDARD>(M, nb8_of(M, G(r - 1, wx), G(r - 1, wx - 1), G(r - 1, wx + 1), G(r, wx - 1), G(r, wx + 1), G(r + 1, wx), G(r + 1, wx - 1), G(r + 1, wx + 1)), t & 1);
                     out = M & ~del;
                     if (del && r >= ZS_HALO && r < ZS_HALO + ZS_TR && (wx == 1 || wx == 2)) del_core = 1;
                 }
@@ -177,76 +117,6 @@ __global__ __launch_bounds__(256) void k_zs_tile(const unsigned long long* __res
         const int r = ZS_HALO + (i >> 1), wx = 1 + (i & 1), y = y0 + r, xw = x0 + wx;
         if (y < H && xw < Ww) d[(size_t)y * Ww + xw] = empty ? 0ULL : T[cur][r][wx];
     }
-}
-// plain (linear id) union-find CCL on the padded raster, driven from the thinned bit plane: a thread owns a 64-pixel word, returns at once when it is empty (the
-// skeleton fills ~1 % of the canvas) and works on its runs otherwise, as k_ccl_bits of raster03.hip does (the id grows with x here too): mode 0 init, every pixel of
-// a run points at the run's first pixel; 1 merge, one union per adjacency between runs; 2 flatten.
-__global__ __launch_bounds__(256) void k_ccl2_bits(const unsigned long long* __restrict__ bits, int* __restrict__ L, int H, int W, int Ww, int mode) {
-    const size_t wi = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (wi >= (size_t)H * Ww) return;
-    unsigned long long m = bits[wi];
-    if (!m) return;
-    const int y = (int)(wi / Ww), xw = (int)(wi % Ww), x0 = xw * 64;
-    if (mode == 2) {
-        while (m) { const int j = __ffsll((long long)m) - 1; m &= m - 1; const int id = y * W + x0 + j; L[id] = ufind(L, id); }
-        return;
-    }
-    unsigned long long U = 0; bool left = false, nw_px = false, ne_px = false;
-    if (mode == 1) {
-        left = xw > 0 && (bits[wi - 1] >> 63);
-        if (y > 0) { U = bits[wi - Ww]; nw_px = xw > 0 && (bits[wi - Ww - 1] >> 63); ne_px = xw + 1 < Ww && (bits[wi - Ww + 1] & 1ULL); }
-    }
-    unsigned long long starts = m & ~(m << 1);
-    while (starts) {
-        const int s = __ffsll((long long)starts) - 1; starts &= starts - 1;
-        const unsigned long long inv = ~(m >> s);                          // (zero only for the full word)
-        const int e = s + (inv ? __ffsll((long long)inv) - 1 : 64) - 1;     // last pixel of the run
-        const int id = y * W + x0 + s;
-        if (mode == 0) { for (int j = s; j <= e; j++) L[id + j - s] = id; continue; }
-        if (s == 0 && left) uunite(L, id, id - 1);
-        const int lo = s > 0 ? s - 1 : 0, hi = e < 63 ? e + 1 : 63;
-        const unsigned long long up = U & ((2ULL << hi) - 1ULL) & ~((1ULL << lo) - 1ULL);
-        if (s == 0 && nw_px && !(U & 1ULL)) uunite(L, id, id - W - 1);      // (with U's bit 0 set, the stretch that starts there is the same run)
-        unsigned long long g = up & ~(up << 1);
-        while (g) { const int j = __ffsll((long long)g) - 1; g &= g - 1; uunite(L, id, (y - 1) * W + x0 + j); }
-        if (e == 63 && ne_px && !(U >> 63)) uunite(L, id, (y - 1) * W + x0 + 64);
-    }
-}
-// ordered compaction of the skeleton pixels (count / write) from the thinned BIT plane (a word per thread, [Hp][Wwp] words; pixel index on the
-// padded raster = y * Wp + x): 1 bit per canvas pixel read, and almost every word is empty
-__global__ __launch_bounds__(256) void k_sk_count_bits(const unsigned long long* __restrict__ b, size_t nwords, unsigned* __restrict__ counts) {
-    __shared__ unsigned ws[4];
-    const size_t wi = (size_t)blockIdx.x * 256 + threadIdx.x;
-    unsigned c = wi < nwords ? (unsigned)__popcll(b[wi]) : 0u;
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o, 64);
-    if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) counts[blockIdx.x] = ws[0] + ws[1] + ws[2] + ws[3];
-}
-__global__ __launch_bounds__(256) void k_sk_write_bits(const unsigned long long* __restrict__ b, const int* __restrict__ L, size_t nwords, int Wp, int Wwp, const unsigned* __restrict__ boff,
-                                                       unsigned* __restrict__ keys, unsigned* __restrict__ lin) {
-    __shared__ unsigned ws[4];
-    const size_t wi = (size_t)blockIdx.x * 256 + threadIdx.x;
-    unsigned long long m = wi < nwords ? b[wi] : 0ULL;
-    const unsigned c = (unsigned)__popcll(m);
-    unsigned inc = c; const int lane = threadIdx.x & 63;
-    for (int o = 1; o < 64; o <<= 1) { unsigned t = __shfl_up(inc, o, 64); if (lane >= o) inc += t; }
-    if (lane == 63) ws[threadIdx.x >> 6] = inc;
-    __syncthreads();
-    if (!m) return;
-    unsigned pos = boff[blockIdx.x] + inc - c;
-    for (int w = 0; w < (int)(threadIdx.x >> 6); w++) pos += ws[w];
-    const size_t p0 = (wi / Wwp) * (size_t)Wp + (wi % Wwp) * 64;
-    while (m) { const int j = __ffsll((long long)m) - 1; m &= m - 1; const size_t p = p0 + j; keys[pos] = (unsigned)L[p]; lin[pos] = (unsigned)p; pos++; }
-}
-__global__ __launch_bounds__(256) void k_heads2(const unsigned* __restrict__ keys, int64_t m, unsigned* __restrict__ head) {
-    int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; if (i > m) return;
-    head[i] = (i < m && (i == 0 || keys[i] != keys[i - 1])) ? 1u : 0u;
-}
-__global__ __launch_bounds__(256) void k_comp_starts2(const unsigned* __restrict__ head, const unsigned* __restrict__ hs, int64_t m, unsigned* __restrict__ cs, unsigned nc) {
-    int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i == 0) cs[nc] = (unsigned)m;
-    if (i < m && head[i]) cs[hs[i]] = (unsigned)i;
 }
 // anchors: nearest skeleton pixel of the group to a0 / a1 (first in raster order on ties, 08:428-432)
 __device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v) {
@@ -591,7 +461,7 @@ static int b_raster_thin(orip_ctx* c, const orip_params08& P, DPolys& lines2, B0
     { Carve L; L.take(b.skA, Np); L.each(nwords, b.bA, b.bB);
       HIPC(c, L.commit(LN(c).vtmp[VTL_STEPLOG], 256 + Np + ntile_max * 4)); }      // (Np + 4 ntile_max: what a second byte plane and a tile list took; no request shrinks here)
     const dim3 gwd((unsigned)cdiv((int64_t)nwords, 256));
-    hipLaunchKernelGGL(k_gid_to_bits, gwd, blk, 0, LN(c).stream, b.gid, b.bA, Hp, Wp, Wwp);      // 4 waves x 64 words per block
+    hipLaunchKernelGGL(k_pack_bits<PackWords>, gwd, blk, 0, LN(c).stream, b.gid, b.bA, Hp, Wp, Wwp);      // 4 waves x 64 words per block
     T.tick("raster");
     // Twelve iterations before the first round trip to the host (16-px lines thin in 9 .. 12), four per round trip after that, each iteration with
     // its own flag: an iteration after the first unchanged one changes nothing either, so running to the end of a batch leaves the image the
@@ -607,7 +477,7 @@ static int b_raster_thin(orip_ctx* c, const orip_params08& P, DPolys& lines2, B0
         if (!all) break;
         it += nb;
     }
-    hipLaunchKernelGGL(k_bits_to_mask, gwd, blk, 0, LN(c).stream, b.bA, b.skA, Hp, Wp, Wwp);
+    bp_bits_to_bytes(LN(c).stream, gwd, b.bA, b.skA, Hp, Wp, Wwp);
     return 0;
 }
 // ---- components of the thinned bit plane: their pixels in raster order (b.M of them; nothing more is done when it is 0), each group's anchors, the
@@ -616,32 +486,32 @@ static int b_components(orip_ctx* c, B08& b, PhaseTimer& T) {
     const int Wp = b.Wp, Hp = b.Hp, Wwp = b.Wwp; const size_t nwords = b.nwords;
     dim3 blk(256); const dim3 gwd((unsigned)cdiv((int64_t)nwords, 256));
     HIPC(c, LN(c).vtmp[VTL_SPLIT_FEAT].ensure(b.Np * 4 + 64));
-    int* L2 = LN(c).vtmp[VTL_SPLIT_FEAT].as<int>();      // union-find label per pixel of the padded raster
-    hipLaunchKernelGGL(k_ccl2_bits, gwd, blk, 0, LN(c).stream, b.bA, L2, Hp, Wp, Wwp, 0);
-    { ProfScope ps(c, "k_ccl2_merge"); hipLaunchKernelGGL(k_ccl2_bits, gwd, blk, 0, LN(c).stream, b.bA, L2, Hp, Wp, Wwp, 1); }
-    hipLaunchKernelGGL(k_ccl2_bits, gwd, blk, 0, LN(c).stream, b.bA, L2, Hp, Wp, Wwp, 2);
+    int* L2 = LN(c).vtmp[VTL_SPLIT_FEAT].as<int>();      // union-find label per pixel of the padded raster (linear id: k_ccl_bits<IdsLinear>, init / merge / flatten)
+    hipLaunchKernelGGL(k_ccl_bits<IdsLinear>, gwd, blk, 0, LN(c).stream, b.bA, L2, Hp, Wp, Wwp, 0);
+    { ProfScope ps(c, "k_ccl2_merge"); hipLaunchKernelGGL(k_ccl_bits<IdsLinear>, gwd, blk, 0, LN(c).stream, b.bA, L2, Hp, Wp, Wwp, 1); }
+    hipLaunchKernelGGL(k_ccl_bits<IdsLinear>, gwd, blk, 0, LN(c).stream, b.bA, L2, Hp, Wp, Wwp, 2);
     T.tick("c:ccl");
     const int nblk = (int)cdiv((int64_t)nwords, 256);
     unsigned *bc, *bo; { Carve L; L.each(nblk + 1, bc, bo); HIPC(c, L.commit(LN(c).vtmp[VTL_RANKS], 64)); }
     HIPC(c, hipMemsetAsync(bc + nblk, 0, 4, LN(c).stream));
-    hipLaunchKernelGGL(k_sk_count_bits, dim3(nblk), blk, 0, LN(c).stream, b.bA, nwords, bc);
+    bp_compact_count(LN(c).stream, (unsigned)nblk, b.bA, nwords, bc);
     ORIP_TRY(vscan_excl<unsigned>(c, bc, bo, (size_t)nblk + 1));
     b.M = 0; ORIP_TRY(vread(c, &b.M, bo + nblk));
     const unsigned M = b.M;
     if (M == 0) return 0;
     unsigned *kin, *lin_in;
     { Carve L; L.each(M, kin, lin_in, b.keys, b.lin); HIPC(c, L.commit(LN(c).vtmp[VTL_CUM], 64)); }
-    hipLaunchKernelGGL(k_sk_write_bits, dim3(nblk), blk, 0, LN(c).stream, b.bA, L2, nwords, Wp, Wwp, bo, kin, lin_in);
+    hipLaunchKernelGGL(k_compact_write_bits<Emit08>, dim3(nblk), blk, 0, LN(c).stream, b.bA, nwords, bo, Emit08{L2, Wp, Wwp}, kin, lin_in);
     ORIP_TRY((vsort_pairs<unsigned, unsigned>(c, kin, b.keys, lin_in, b.lin, (size_t)M, 0, 27)));
     unsigned *head, *hs; { Carve L; L.each((size_t)M + 1, head, hs); HIPC(c, L.commit(LN(c).vtmp[VTL_SAMPLES], 64)); }
-    hipLaunchKernelGGL(k_heads2, dim3(cdiv(M + 1, 256)), blk, 0, LN(c).stream, b.keys, (int64_t)M, head);
+    bp_heads(LN(c).stream, b.keys, (int64_t)M, (int64_t)M + 1, head);
     ORIP_TRY(vscan_excl<unsigned>(c, head, hs, (size_t)M + 1));
     b.NC = 0; ORIP_TRY(vread(c, &b.NC, hs + M));
     const unsigned NC = b.NC; const size_t nc1 = (size_t)NC + 1;
     unsigned long long *ckin, *ckout; unsigned* cidx;
     { Carve L; L.each(nc1, ckin, ckout); L.take(b.cs, nc1 + 1);
       L.each(nc1, cidx, b.corder, b.outcnt, b.oflag, b.oscan); L.take(b.pd, NC); HIPC(c, L.commit(LN(c).vtmp[VTL_CAPS], 256)); }
-    hipLaunchKernelGGL(k_comp_starts2, dim3(cdiv(M, 256)), blk, 0, LN(c).stream, head, hs, (int64_t)M, b.cs, NC);
+    bp_comp_starts(LN(c).stream, head, hs, (int64_t)M, b.cs, NC);
     T.tick("c:sort");
     hipLaunchKernelGGL(k_nearest_anchor, dim3(cdiv(M, 256)), blk, 0, LN(c).stream, b.lin, (int64_t)M, b.gid, Wp, b.grp);
     T.tick("c:anchor");

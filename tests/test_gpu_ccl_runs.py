@@ -1,10 +1,12 @@
-"""k_ccl_bits unites runs, not pixels (raster03.hip): its two callers against the oracle on planes made of runs.  Stage 04 (set_edges -> find_contours):
+"""k_ccl_bits unites runs, not pixels (bitplane.h): its two callers against the oracle on planes made of runs.  Stage 04 (set_edges -> find_contours):
 the order of the contour list shows the component labels, so list equality checks them.  Stage 03 (set_masks -> detect_edges): the hysteresis
 components decide which candidates are edges.  W runs over one word, its last bit, two words, two words and a bit; the patterns put runs across word
 boundaries, runs of the row above that touch a run only at its widened ends, diagonal links only, late merges and long parent chains.  Stage 03 gets
 areas (its opening removes one-pixel lines) whose edge rings are such runs, and an all-ones mask in every stack (full words in front of the NMS; a uniform
 mask has no candidate, so a full candidate word cannot be made through set_masks -- the full word of the merge pass is stage 04's full row).  The no-GPU
-companion shows that the oracle finds several components and several contours in every plane, so that the equalities say something."""
+companion shows that the oracle finds several components and several contours in every plane, so that the equalities say something.  On the `stagger`
+planes the order of the components by their smallest BLOCK-RASTER pixel id differs from their order by smallest linear id y * W + x (on the other
+patterns the two orders agree): the contour list there is in the oracle's order only if the labels are block-raster ids."""
 import numpy as np
 import pytest
 
@@ -93,6 +95,15 @@ def widened(H, W):
     return e
 
 
+def stagger(H, W):
+    """vertical lines in every third column, every other one starting a row lower: of two neighbours the one that starts in row 1 lies in the earlier
+    2x2 block (smaller block-raster id), the one that starts in row 0 further right has the smaller linear id"""
+    e = np.zeros((H, W), np.uint8)
+    for i, x in enumerate(range(0, W, 3)):
+        e[(i + 1) & 1:, x] = 255
+    return e
+
+
 def ones(H, W):
     return np.full((H, W), 255, np.uint8)
 
@@ -171,6 +182,29 @@ def test_oracle_finds_several_edge_components(fn):
         assert n - 1 > (1 if W >= 63 else 0), (fn.__name__, H, W, n - 1)      # (eight columns hold one dot or bar and its ring of edges)
 
 
+def component_orders(sk):
+    """(labels ordered by their component's smallest block-raster id, by its smallest linear id, the label plane)"""
+    _, lab = O.ccl8(sk)
+    H, W = sk.shape; Wb = (W + 1) >> 1
+    yy, xx = np.nonzero(lab)
+    l = lab[yy, xx]
+    br = ((((yy >> 1) * Wb + (xx >> 1)) << 2) | ((yy & 1) << 1) | (xx & 1))
+    lin = yy * W + xx
+    ids = [int(i) for i in np.unique(l)]
+    return sorted(ids, key=lambda i: br[l == i].min()), sorted(ids, key=lambda i: lin[l == i].min()), lab
+
+
+@pytest.mark.parametrize("H,W", SHAPES)
+def test_stagger_tells_block_raster_ids_from_linear_ids(H, W):
+    """the two orders differ, every component has a contour, and the oracle lists the contours in block-raster order: a CCL that labelled by y * W + x
+    would hand stage 04 the same components in another order, and test_stage04_component_order_is_block_raster would see another list"""
+    e, sk, polys = want04(stagger, H, W)
+    by_block, by_linear, lab = component_orders(sk)
+    assert len(by_block) == len(range(0, W, 3)) and by_block != by_linear
+    first = [np.asarray(p).reshape(-1, 2)[0] for p in polys]
+    assert [int(lab[y, x]) for x, y in first] == by_block
+
+
 def test_all_ones_mask_has_no_edge():
     """a uniform mask has no gradient, so no candidate can be made of full words through set_masks; the plane still runs as a layer of every stack"""
     assert not O.stage03(ones(9, 65)).any()
@@ -190,6 +224,22 @@ def dev():
 def test_stage04_contours_equal_oracle(dev, H, W):
     from orip.lib import SLOT_CONTOURS
     for stack in STACKS:
+        w = [want04(fn, H, W) for fn in stack]
+        dev.set_edges(np.stack([x[0] for x in w]))
+        dev.find_contours()
+        for l, (e, sk, polys) in enumerate(w):
+            assert np.array_equal(dev.get_skeleton(l), sk), (stack[l].__name__, H, W, "skeleton")
+            got = dev.get_polys(SLOT_CONTOURS, l)
+            assert same_polys(got, polys), (stack[l].__name__, H, W, len(got), len(polys))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("H,W", SHAPES)
+def test_stage04_component_order_is_block_raster(dev, H, W):
+    """the stagger planes, alone and between two other layers: the contour list in the oracle's order (CPU companion:
+    test_stagger_tells_block_raster_ids_from_linear_ids)"""
+    from orip.lib import SLOT_CONTOURS
+    for stack in [(stagger,), (checker, stagger, rows)]:
         w = [want04(fn, H, W) for fn in stack]
         dev.set_edges(np.stack([x[0] for x in w]))
         dev.find_contours()

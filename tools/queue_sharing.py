@@ -8,15 +8,16 @@ from collections import defaultdict
 p = sys.argv[1]
 files = [p] if p.endswith(".csv") else sorted(glob.glob(os.path.join(p, "**", "*kernel_trace.csv"), recursive=True), key=os.path.getmtime)[-1:]      # the newest run, never a mix
 CLASSES = [      # (lane class, kernels only that class of stream launches on the bench path)
-    ("raster main", ("k_kmeans_fit", "k_lab_assign", "k_thin_bits04", "k_ccl_bits", "k_bits_to_skel_state")),
+    ("raster main", ("k_kmeans_fit", "k_lab_assign", "k_thin_bits04", "k_ccl_bits<IdsBlockRaster>", "k_bits_to_skel_state")),      # (k_ccl_bits<IdsLinear> is stage 08-B's, on the layer streams)
     ("raster side", ("k_chain_ends_bits", "k_chain_build")),
     ("layer main", ("k_trace", "k_greedy_nn_fast", "k_plot_order_wave")),
     ("layer side", ("k_comp_paths_lds", "k_comp_paths_glb", "k_tail_replay", "k_seglen", "k_perim_leaves_seg")),
     ("stage 10", ("k_taps_wave", "k_taps_sequential", "k_stamp_chain", "k_stamp_discs", "k_cut_counts", "k_cut_slots")),
 ]
-def short(n):
-    n = re.sub(r"\(anonymous namespace\)::", "", n); n = re.sub(r"^void ", "", n); n = re.sub(r"[<(].*", "", n)
-    return n
+LISTED = {k for _, names in CLASSES for k in names}
+def short(n):          # the kernel's name without its arguments; without its template arguments too, unless CLASSES lists it with them
+    n = re.sub(r"\(anonymous namespace\)::", "", n); n = re.sub(r"^void ", "", n); n = re.sub(r"\(.*", "", n)
+    return n if n in LISTED else re.sub(r"<.*", "", n)
 rows = []
 for f in files:
     with open(f) as fh:

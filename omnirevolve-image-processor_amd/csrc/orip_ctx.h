@@ -475,6 +475,9 @@ static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
 // stage entry points implemented across the .hip files
 int orip_raster02_lab_tables(orip_ctx* c);
+// the Lab (02:35) or, rgb, the R, G, B bytes of the n pixels d_idx names in the resident image (a device list; nullptr: pixels 0 .. n - 1) -> dst, n
+// triples in device memory; enqueued on the calling lane's stream (raster02.hip; the samples of kmeans02.hip)
+void orip_raster02_gather(orip_ctx* c, bool rgb, const int64_t* d_idx, int64_t n, uint8_t* dst);
 // the per-layer stages without the closing stream wait (orip_layer_front chains them on the layer's stream)
 int orip_contours_layer_impl(orip_ctx* c, int layer, bool sync);
 int orip_scale_vectors_impl(orip_ctx* c, int layer, float sx, float sy, float dx, float dy, bool sync);

@@ -1,8 +1,7 @@
 // csrc/raster02.hip -- stage 02 (02_color_extract.py) on gfx950:
 //   lab_assign   : BGR u8 -> Lab u8 (cv2.cvtColor, 02:35) -> nearest centre (02:53-55) -> dark->light label (02:120-127)
-//   lab_gather   : Lab of the k-means subsample (02:39-44)
-//   kmeans_fit   : cv2.kmeans with KMEANS_PP_CENTERS (02:46-49), one persistent workgroup
-//   morph_pass   : erode / dilate with an arbitrary <=7x7 structuring element (02:151-154, 03:25-30)
+//   lab_gather   : Lab of the k-means subsample (02:39-44); rgb_gather: its R, G, B bytes for process_colors.py.  The fit itself is kmeans02.hip
+//   morph_pass   : erode / dilate with an arbitrary <=7x7 structuring element (02:151-154, 03:25-30), on bit planes when the input is binary
 // All float arithmetic mirrors numpy / OpenCV evaluation order: compiled with -ffp-contract=off and written
 // with explicit __fmul_rn/__fadd_rn where the order matters.
 #include "bitplane.h"
@@ -124,6 +123,11 @@ __global__ __launch_bounds__(256) void k_rgb_gather(const u8* __restrict__ bgr, 
         rgb[3 * i] = bgr[3 * p + 2]; rgb[3 * i + 1] = bgr[3 * p + 1]; rgb[3 * i + 2] = bgr[3 * p];
     }
 }
+void orip_raster02_gather(orip_ctx* c, bool rgb, const int64_t* d_idx, int64_t n, uint8_t* dst) {      // (declared in orip_ctx.h; the k-means fit's samples)
+    const dim3 grid(std::min<int64_t>(2048, cdiv(n, 256))), block(256);
+    if (rgb) hipLaunchKernelGGL(k_rgb_gather, grid, block, 0, LN(c).stream, c->image.as<u8>(), d_idx, n, dst);
+    else hipLaunchKernelGGL(k_lab_gather, grid, block, 0, LN(c).stream, c->image.as<u8>(), d_idx, n, dst, c->lab_tabs.as<LabTabs>());
+}
 // process_colors.py assign_labels (:69-77): nearest palette colour in RGB with the reference's int16 arithmetic -- the squares of differences
 // above 181 wrap to negative values before they are summed (in int64), and np.argmin takes the first minimum.  Four pixels per thread (12 bytes in,
 // 4 bytes out), the palette in LDS.
@@ -159,331 +163,6 @@ __global__ void k_count_labels(const u8* __restrict__ labels, int64_t n, unsigne
         atomicAdd(&h[labels[i] & 15], 1u);
     __syncthreads();
     if (threadIdx.x < ORIP_MAX_LAYERS && h[threadIdx.x]) atomicAdd(&counts[threadIdx.x], (unsigned long long)h[threadIdx.x]);
-}
-
-// ------------------------------------------------------------------------------------------------
-// cv2.kmeans.  Samples are u8 Lab triples, so kmeans++ works on exact integers; the
-// sequential scans of the CPU algorithm are replaced by order-independent exact equivalents (see
-// DESIGN.md "kmeans_fit").
-// ------------------------------------------------------------------------------------------------
-struct KmState { unsigned long long rng; };
-
-__device__ __forceinline__ unsigned km_next(unsigned long long& st) {
-    st = (unsigned long long)(unsigned)st * 4164903690ULL + (unsigned)(st >> 32);
-    return (unsigned)st;
-}
-__device__ __forceinline__ double km_double(unsigned long long& st) {
-    unsigned t = km_next(st);
-    unsigned long long v = ((unsigned long long)t << 32) | km_next(st);
-    return (double)v * 5.4210108624275221700372640043497e-20;
-}
-
-__device__ __forceinline__ int isq3(const u8* a, const u8* b) {
-    int d0 = (int)a[0] - b[0], d1 = (int)a[1] - b[1], d2 = (int)a[2] - b[2];
-    return d0 * d0 + d1 * d1 + d2 * d2;
-}
-// hal::normL2Sqr_(sample, centre, 3) in float: s=0; s+=t*t per component
-__device__ __forceinline__ float fsq3(const u8* a, const float* c) {
-    float s = 0.f;
-    for (int j = 0; j < 3; j++) { float t = __fsub_rn((float)a[j], c[j]); s = __fadd_rn(s, __fmul_rn(t, t)); }
-    return s;
-}
-
-// ------------------------------------------------------------------------------------------------
-// The fit spread over KMB_B workgroups with a device-wide barrier between phases (a single workgroup spends 13 ms of pure ALU
-// time on one CU at the head of the whole path).  Every workgroup executes the same control flow: all decisions are taken from
-// values that every block reads from global memory after a barrier.  Integer sums are order-free; the only floating-point
-// reduction (compactness) is evaluated by workgroup 0 with the fixed tree of a 1024-thread workgroup.
-// ------------------------------------------------------------------------------------------------
-#define KMB_B 64
-#define KMB_T 256
-struct KmGlobal {
-    unsigned bar_count, bar_gen;
-    long long acc[8];                              // rotating accumulators of the integer passes
-    long long acc3[8][4];                          // the same for passes that sum three values at once (the three trials of a ++ centre)
-    int ci3[4];                                    // the three trial centres of a ++ step
-    long long tot[2][ORIP_MAX_LAYERS * 4];         // cluster sums (L, a, b, count), double-buffered by iteration parity
-    unsigned long long key;                        // farthest-point search of the empty-cluster repair
-    int ci;
-    double compact;
-    float slow_centers[ORIP_MAX_LAYERS * 3];
-    long long blockpart[KMB_B];
-};
-__device__ __forceinline__ void km_grid_sync(KmGlobal* G) {
-    __threadfence();
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const unsigned gen = atomicAdd(&G->bar_gen, 0u);
-        if (atomicAdd(&G->bar_count, 1u) == KMB_B - 1) { atomicExch(&G->bar_count, 0u); __threadfence(); atomicAdd(&G->bar_gen, 1u); }
-        else while (atomicAdd(&G->bar_gen, 0u) == gen) __builtin_amdgcn_s_sleep(1);
-    }
-    __syncthreads();
-    __threadfence();
-}
-__device__ __forceinline__ long long kmb_block_sum(long long v, long long* red) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    long long r = 0;
-    for (int w = 0; w < KMB_T / 64; w++) r += red[w];
-    return r;
-}
-// Attempts are independent but for the random draws, and every attempt makes the same number of them (one index, 3 (K - 1) doubles): `groups` groups of KMB_B
-// workgroups take the attempts a = group, group + groups, ... side by side (the fit is bound by its grid barriers, not by the card), each with its own
-// barrier, accumulators and work arrays; the host takes the first attempt with the smallest compactness, as the sequential loop does (02:46-49).
-struct KmResult { float cen[ORIP_MAX_LAYERS * 3]; double compact; int attempt; int status; int pad[2]; };
-__global__ __launch_bounds__(KMB_T) void k_kmeans_fit_mb(const u8* __restrict__ data, int N, int K, int attempts, int groups, int maxCount, double epsilon,
-                                                          int32_t* __restrict__ dist_all, int32_t* __restrict__ labels_all,
-                                                          double* __restrict__ dd_all, long long* __restrict__ parts_all, KmResult* __restrict__ res_all, KmGlobal* __restrict__ G_all) {
-    __shared__ long long red[KMB_T / 64];
-    __shared__ float centers[ORIP_MAX_LAYERS * 3], old_centers[ORIP_MAX_LAYERS * 3];
-    __shared__ int csum[KMB_T / 64][ORIP_MAX_LAYERS * 4];
-    __shared__ long long tot[ORIP_MAX_LAYERS * 4];
-    __shared__ int pp_idx[ORIP_MAX_LAYERS];
-    __shared__ double sh_shift;
-    __shared__ double ptree[1024];
-    const int tid = threadIdx.x, wave = tid >> 6, grp = blockIdx.x / KMB_B, bid = blockIdx.x % KMB_B;
-    const int gtid = bid * KMB_T + tid, gsz = KMB_B * KMB_T;
-    const int chunk = (N + gsz - 1) / gsz;
-    const int lo = min(N, gtid * chunk), hi = min(N, lo + chunk);
-    unsigned long long rng = 0xffffffffULL;   // identical in every thread
-    double best_compact = 1.79769313486231570815e+308; int best_attempt = -1;
-    int32_t* dist = dist_all + (size_t)grp * N; int32_t* labels = labels_all + (size_t)grp * N;      // (the trials of a ++ centre no longer write candidate distance arrays)
-    double* dd = dd_all + (size_t)grp * N; long long* parts = parts_all + (size_t)grp * KMB_B * KMB_T;
-    KmGlobal* G = G_all + grp; KmResult* res = res_all + grp;
-    unsigned pass = 0;                        // selects the accumulator; slot pass+4 is cleared for later use
-    // grid-wide integer sum of v (one value per thread); two barriers apart accumulators never collide
-    auto grid_sum = [&](long long v) -> long long {
-        long long bs = kmb_block_sum(v, red);
-        const unsigned slot = pass & 7u;
-        if (tid == 0) { atomicAdd((unsigned long long*)&G->acc[slot], (unsigned long long)bs); if (bid == 0) { const unsigned z = (pass + 4u) & 7u; G->acc[z] = 0; G->acc3[z][0] = G->acc3[z][1] = G->acc3[z][2] = 0; } }
-        km_grid_sync(G);
-        long long r = *(volatile long long*)&G->acc[slot];
-        pass++;
-        return r;
-    };
-    auto grid_sum3 = [&](long long v0, long long v1, long long v2, long long (&r)[3]) {
-        const long long b0 = kmb_block_sum(v0, red), b1 = kmb_block_sum(v1, red), b2 = kmb_block_sum(v2, red);
-        const unsigned slot = pass & 7u;
-        if (tid == 0) {
-            atomicAdd((unsigned long long*)&G->acc3[slot][0], (unsigned long long)b0); atomicAdd((unsigned long long*)&G->acc3[slot][1], (unsigned long long)b1);
-            atomicAdd((unsigned long long*)&G->acc3[slot][2], (unsigned long long)b2);
-            if (bid == 0) { const unsigned z = (pass + 4u) & 7u; G->acc[z] = 0; G->acc3[z][0] = G->acc3[z][1] = G->acc3[z][2] = 0; }
-        }
-        km_grid_sync(G);
-        for (int j = 0; j < 3; j++) r[j] = *(volatile long long*)&G->acc3[slot][j];
-        pass++;
-    };
-    for (int a = 0; a < attempts; a++) {
-        if (a % groups != grp) { for (int q = 0; q < 1 + 6 * (K - 1); q++) km_next(rng); continue; }      // another group's attempt: its draws
-        double compactness = 0;
-        for (int iter = 0;;) {
-            double max_shift = iter == 0 ? 1.79769313486231570815e+308 : 0.0;
-            __syncthreads();
-            if (tid < K * 3) { float t = centers[tid]; centers[tid] = old_centers[tid]; old_centers[tid] = t; }
-            __syncthreads();
-            if (iter == 0) {
-                // ---------------- generateCentersPP ----------------
-                if (bid == 0 && tid < 2 * ORIP_MAX_LAYERS * 4) (&G->tot[0][0])[tid] = 0;     // both sum buffers start an attempt empty (barriers follow)
-                int c0 = (int)(km_next(rng) % (unsigned)N);
-                if (tid == 0) pp_idx[0] = c0;
-                long long ls = 0;
-                for (int i = gtid; i < N; i += gsz) { int d = isq3(data + 3 * i, data + 3 * c0); dist[i] = d; ls += d; }
-                long long sum0 = grid_sum(ls);
-                // The three trials of a centre (02:47 -> cv::generateCentersPP, 3 trials per centre) share the distances they start from, so they run
-                // side by side: ONE pass of partial sums, the three descents in one phase, the three candidate sums in one reduction -- 3 grid
-                // barriers per centre instead of 9 (the fit is barrier-bound: 200 000 samples on 16 384 threads).  Every thread keeps its own
-                // contiguous chunk [lo, hi) from the update of the distances through the partial sums to the candidate sums, so no barrier is
-                // needed between a centre's update and the next centre's sums.  Same draws in the same order, same integer arithmetic.
-                for (int k = 1; k < K; k++) {
-                    double pj[3];
-                    for (int j = 0; j < 3; j++) pj[j] = km_double(rng) * (double)sum0;
-                    long long cs = 0;
-                    for (int i = lo; i < hi; i++) cs += dist[i];
-                    parts[gtid] = cs;
-                    long long bs = kmb_block_sum(cs, red);
-                    if (tid == 0) G->blockpart[bid] = bs;
-                    km_grid_sync(G);
-                    if (bid == 0 && tid < 64) {
-                        for (int j = 0; j < 3; j++) {
-                            const double p = pj[j];
-                            // ci = first index with inclusive prefix >= p, else N-1.  First wave of block 0 descends: block totals, the threads of the crossing
-                            // block, then the samples of the crossing chunk; every test is "(double)(inclusive integer prefix) >= p" on exact integers
-                            auto wave_incl = [&](long long v) { for (int o = 1; o < 64; o <<= 1) { long long t = __shfl_up(v, o, 64); if (tid >= o) v += t; } return v; };
-                            auto first_cross = [&](long long base, long long v, bool valid, long long& before) -> int {   // lane index of the first crossing, -1: none
-                                const long long inc = wave_incl(valid ? v : 0);
-                                const unsigned long long m = __ballot(valid && (double)(base + inc) >= p);
-                                const int f = m ? __ffsll((long long)m) - 1 : -1;
-                                const int src = f >= 0 ? f : 63;
-                                const long long incf = __shfl(inc, src, 64), vf = __shfl(valid ? v : 0, src, 64);
-                                before = base + (f >= 0 ? incf - vf : incf);        // prefix in front of the crossing lane / whole window when none
-                                return f;
-                            };
-                            long long run = 0; int ci = N - 1;
-                            int b = -1;
-                            for (int b0 = 0; b0 < KMB_B && b < 0; b0 += 64) {
-                                long long before; const bool valid = b0 + tid < KMB_B;
-                                const int f = first_cross(run, valid ? *(volatile long long*)&G->blockpart[b0 + tid] : 0, valid, before);
-                                run = before; if (f >= 0) b = b0 + f;
-                            }
-                            if (b >= 0) {
-                                int t = -1;
-                                for (int t0 = 0; t0 < KMB_T && t < 0; t0 += 64) {
-                                    long long before;
-                                    const int f = first_cross(run, *(volatile long long*)&parts[b * KMB_T + t0 + tid], true, before);
-                                    run = before; if (f >= 0) t = t0 + f;
-                                }
-                                if (t >= 0) {
-                                    const int l2 = min(N, (b * KMB_T + t) * chunk), h2 = min(N, l2 + chunk);
-                                    for (int i0 = l2; i0 < h2 && ci == N - 1; i0 += 64) {
-                                        long long before; const bool valid = i0 + tid < h2;
-                                        const int f = first_cross(run, valid ? (long long)dist[i0 + tid] : 0, valid, before);
-                                        run = before; if (f >= 0) { ci = i0 + f; break; }
-                                    }
-                                }
-                            }
-                            if (ci > N - 1) ci = N - 1;
-                            if (tid == 0) G->ci3[j] = ci;
-                        }
-                    }
-                    km_grid_sync(G);
-                    int cj[3]; for (int j = 0; j < 3; j++) cj[j] = *(volatile int*)&G->ci3[j];
-                    long long sj[3] = {0, 0, 0};
-                    for (int i = lo; i < hi; i++) {
-                        const int d0 = dist[i];
-                        for (int j = 0; j < 3; j++) sj[j] += min(isq3(data + 3 * i, data + 3 * cj[j]), d0);
-                    }
-                    long long Sj[3]; grid_sum3(sj[0], sj[1], sj[2], Sj);
-                    long long bestSum = 0x7fffffffffffffffLL; int bestCenter = -1;
-                    for (int j = 0; j < 3; j++) if (Sj[j] < bestSum) { bestSum = Sj[j]; bestCenter = cj[j]; }
-                    if (tid == 0) pp_idx[k] = bestCenter;
-                    sum0 = bestSum;
-                    if (k + 1 < K) for (int i = lo; i < hi; i++) dist[i] = min(isq3(data + 3 * i, data + 3 * bestCenter), dist[i]);      // own chunk: read next by this thread only, then (after a barrier) by the descent
-                    __syncthreads();
-                }
-                __syncthreads();
-                if (tid < K * 3) centers[tid] = (float)data[3 * pp_idx[tid / 3] + tid % 3];
-                __syncthreads();
-            } else {
-                // ---------------- recompute centres from labels ----------------
-                const int par = iter & 1;
-                for (int i = tid; i < (KMB_T / 64) * ORIP_MAX_LAYERS * 4; i += KMB_T) (&csum[0][0])[i] = 0;
-                __syncthreads();
-                for (int i = gtid; i < N; i += gsz) {
-                    int k = labels[i];
-                    atomicAdd(&csum[wave][k * 4 + 0], (int)data[3 * i]);
-                    atomicAdd(&csum[wave][k * 4 + 1], (int)data[3 * i + 1]);
-                    atomicAdd(&csum[wave][k * 4 + 2], (int)data[3 * i + 2]);
-                    atomicAdd(&csum[wave][k * 4 + 3], 1);
-                }
-                __syncthreads();
-                if (tid < K * 4) {
-                    long long t = 0; for (int w = 0; w < KMB_T / 64; w++) t += csum[w][tid];
-                    atomicAdd((unsigned long long*)&G->tot[par][tid], (unsigned long long)t);
-                    if (bid == 0) G->tot[par ^ 1][tid] = 0;        // the other buffer was last read two barriers ago
-                }
-                if (bid == 0 && tid == 0) G->key = 0;
-                km_grid_sync(G);
-                if (tid < K * 4) tot[tid] = *(volatile long long*)&G->tot[par][tid];
-                __syncthreads();
-                // float accumulation in sample order is exact (== integer sum) while every partial sum < 2^24
-                bool bad = false;
-                for (int k = 0; k < K; k++) for (int j = 0; j < 3; j++) if (tot[k * 4 + j] >= (1LL << 24)) bad = true;
-                if (bad) {
-                    // rare slow path: literal sequential float32 accumulation by one lane
-                    if (bid == 0 && tid == 0) {
-                        float acc[ORIP_MAX_LAYERS * 3];
-                        for (int q = 0; q < K * 3; q++) acc[q] = 0.f;
-                        for (int i = 0; i < N; i++) { int k = labels[i]; for (int j = 0; j < 3; j++) acc[k * 3 + j] = __fadd_rn(acc[k * 3 + j], (float)data[3 * i + j]); }
-                        for (int q = 0; q < K * 3; q++) G->slow_centers[q] = acc[q];
-                    }
-                    km_grid_sync(G);
-                    if (tid < K * 3) centers[tid] = *(volatile float*)&G->slow_centers[tid];
-                } else if (tid < K * 3) centers[tid] = (float)tot[(tid / 3) * 4 + tid % 3];
-                __syncthreads();
-                // empty-cluster repair (sequential over k, as the reference)
-                for (int k = 0; k < K; k++) {
-                    if (tot[k * 4 + 3] != 0) continue;      // uniform: every block holds the same totals
-                    int max_k = 0;
-                    for (int k1 = 1; k1 < K; k1++) if (tot[max_k * 4 + 3] < tot[k1 * 4 + 3]) max_k = k1;
-                    float nb[3]; float scale = 1.f / (float)tot[max_k * 4 + 3];
-                    for (int j = 0; j < 3; j++) nb[j] = __fmul_rn(centers[max_k * 3 + j], scale);
-                    // farthest point: max_dist <= dist  => last index among maxima
-                    unsigned long long key = 0;
-                    for (int i = gtid; i < N; i += gsz) {
-                        if (labels[i] != max_k) continue;
-                        float d = fsq3(data + 3 * i, nb);
-                        unsigned long long kk = ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)i;
-                        if (kk >= key) key = kk;
-                    }
-                    atomicMax(&G->key, key);
-                    km_grid_sync(G);
-                    const int far_i = (int)(*(volatile unsigned long long*)&G->key & 0xffffffffu);
-                    __syncthreads();
-                    if (tid == 0) {
-                        tot[max_k * 4 + 3]--; tot[k * 4 + 3]++;
-                        if (bid == 0) labels[far_i] = k;
-                        for (int j = 0; j < 3; j++) {
-                            float v = (float)data[3 * far_i + j];
-                            centers[max_k * 3 + j] = __fsub_rn(centers[max_k * 3 + j], v);
-                            centers[k * 3 + j] = __fadd_rn(centers[k * 3 + j], v);
-                        }
-                    }
-                    km_grid_sync(G);                           // everybody has read the key before it is cleared
-                    if (bid == 0 && tid == 0) G->key = 0;
-                    km_grid_sync(G);
-                }
-                if (tid == 0) {
-                    for (int k = 0; k < K; k++) {
-                        float scale = 1.f / (float)tot[k * 4 + 3];
-                        for (int j = 0; j < 3; j++) centers[k * 3 + j] = __fmul_rn(centers[k * 3 + j], scale);
-                        if (iter > 0) {
-                            double d = 0;
-                            for (int j = 0; j < 3; j++) { double t = (double)__fsub_rn(centers[k * 3 + j], old_centers[k * 3 + j]); d = __dadd_rn(d, __dmul_rn(t, t)); }
-                            max_shift = fmax(max_shift, d);
-                        }
-                    }
-                    sh_shift = max_shift;
-                }
-                __syncthreads();
-                max_shift = sh_shift;
-                __syncthreads();
-            }
-            ++iter;
-            bool last = (iter == max(maxCount, 2)) || (max_shift <= epsilon);
-            if (last) {
-                for (int i = gtid; i < N; i += gsz) dd[i] = (double)fsq3(data + 3 * i, &centers[3 * labels[i]]);
-                km_grid_sync(G);
-                if (bid == 0) {
-                    // the reduction tree of a 1024-thread workgroup: strided partials, shfl_down tree per 64, then 16 sequential adds
-                    for (int v = tid; v < 1024; v += KMB_T) { double s = 0; for (int i = v; i < N; i += 1024) s += dd[i]; ptree[v] = s; }
-                    __syncthreads();
-                    for (int o = 32; o > 0; o >>= 1) {
-                        for (int q = tid; q < 16 * o; q += KMB_T) { const int w = q / o, l = q % o; ptree[w * 64 + l] += ptree[w * 64 + l + o]; }
-                        __syncthreads();
-                    }
-                    if (tid == 0) { double r = 0; for (int w = 0; w < 16; w++) r += ptree[w * 64]; G->compact = r; }
-                }
-                km_grid_sync(G);
-                compactness = *(volatile double*)&G->compact;
-                break;
-            } else {
-                for (int i = gtid; i < N; i += gsz) {
-                    float md = 0.f; int kb = 0;
-                    for (int k = 0; k < K; k++) { float d = fsq3(data + 3 * i, &centers[3 * k]); if (k == 0 || md > d) { md = d; kb = k; } }
-                    labels[i] = kb;
-                }
-                km_grid_sync(G);
-            }
-        }
-        if (compactness < best_compact) {
-            best_compact = compactness; best_attempt = a;
-            if (bid == 0 && tid < K * 3) res->cen[tid] = centers[tid];
-        }
-        __syncthreads();
-    }
-    if (bid == 0 && tid == 0) { res->compact = best_compact; res->attempt = best_attempt; res->status = 0; }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -731,96 +410,6 @@ extern "C" int orip_lab_of_rgb(orip_ctx* c, const uint8_t* rgb, int64_t n, uint8
     HIPC(c, hipMemcpyAsync(lab_out, d_out, (size_t)n * 3, hipMemcpyDeviceToHost, LN(c).stream));
     HIPC(c, hipStreamSynchronize(LN(c).stream));       // (also keeps `bgr` alive until the upload is done)
     return 0;
-}
-
-static int kmeans_fit_impl(orip_ctx* c, bool rgb, const int64_t* sample_idx, int64_t n_idx, int K, int attempts, int max_iter, double eps,
-                           float* centers_out, double* compactness_out) {
-    orip_enter(c);
-    c->mask_bits = nullptr;
-    if (!c->image.p) ORIP_FAIL(c, "no image set");
-    if (K < 1 || K > ORIP_MAX_LAYERS) ORIP_FAIL(c, "K=%d out of range 1..%d", K, ORIP_MAX_LAYERS);
-    ORIP_TRY(orip_contours_invalidate(c));       // (the sample indices of the upload path go to tmpC)
-    const int64_t npx = (int64_t)c->H * c->W;
-    const bool resident = !sample_idx && n_idx == -1;      // the set orip_kmeans_samples left in the context
-    if (resident && (c->km_n == 0 || c->km_npx != npx))
-        ORIP_FAIL(c, "no resident sample set for this image: the set holds %lld indices made for %lld pixels, the image has %lld pixels (orip_kmeans_samples)",
-                  (long long)c->km_n, (long long)c->km_npx, (long long)npx);
-    int64_t N = resident ? c->km_n : (sample_idx ? n_idx : npx);
-    if (N < K || N > 0x7fffffff) ORIP_FAIL(c, "bad sample count %lld", (long long)N);
-    HIPC(c, c->tmpB.ensure((size_t)N * 3 + 16));
-    if (sample_idx) { HIPC(c, c->tmpC.ensure((size_t)N * 8)); HIPC(c, hipMemcpyAsync(c->tmpC.p, sample_idx, (size_t)N * 8, hipMemcpyHostToDevice, LN(c).stream)); }
-    const int64_t* d_idx = resident ? c->km_idx.as<int64_t>() : (sample_idx ? c->tmpC.as<int64_t>() : nullptr);
-    if (rgb) {
-        hipLaunchKernelGGL(k_rgb_gather, dim3(std::min<int64_t>(2048, cdiv(N, 256))), dim3(256), 0, LN(c).stream, c->image.as<u8>(), d_idx, N, c->tmpB.as<u8>());
-    } else {
-        ProfScope ps(c, "k_lab_gather");
-        hipLaunchKernelGGL(k_lab_gather, dim3(std::min<int64_t>(2048, cdiv(N, 256))), dim3(256), 0, LN(c).stream, c->image.as<u8>(), d_idx, N, c->tmpB.as<u8>(),
-                           c->lab_tabs.as<LabTabs>());
-    }
-    HIPC(c, c->tmpD.ensure((size_t)N * 4 * 4 + 256));     // (later stages find tmpD at least this large)
-    attempts = std::max(attempts, 1);
-    double epsilon = std::max(eps, 0.0); epsilon *= epsilon;
-    int maxCount = std::min(std::max(max_iter, 2), 100);
-    if (K == 1) { attempts = 1; maxCount = 2; }
-    const int groups = std::min(attempts, 4);
-    HIPC(c, c->tmpD.ensure((size_t)N * 4 * 2 * groups + 256));
-    int32_t* base = c->tmpD.as<int32_t>();
-    const size_t per = (size_t)N * 8 + (size_t)KMB_B * KMB_T * 8;
-    HIPC(c, c->tmpA.ensure(per * groups + (sizeof(KmGlobal) + sizeof(KmResult)) * groups + 256));
-    double* dd = c->tmpA.as<double>(); long long* parts = (long long*)(dd + (size_t)N * groups);
-    KmGlobal* G = (KmGlobal*)(parts + (size_t)KMB_B * KMB_T * groups); KmResult* res = (KmResult*)(G + groups);
-    HIPC(c, hipMemsetAsync(G, 0, sizeof(KmGlobal) * groups, LN(c).stream));
-    HIPC(c, hipMemsetAsync(res, 0xff, sizeof(KmResult) * groups, LN(c).stream));
-    {
-        ProfScope ps(c, "k_kmeans_fit");
-        hipLaunchKernelGGL(k_kmeans_fit_mb, dim3(KMB_B * groups), dim3(KMB_T), 0, LN(c).stream, c->tmpB.as<u8>(), (int)N, K, attempts, groups, maxCount, epsilon,
-                           base, base + (size_t)N * groups, dd, parts, res, G);
-    }
-    HIPC(c, hipGetLastError());
-    KmResult hr[4];
-    HIPC(c, hipMemcpyAsync(hr, res, sizeof(KmResult) * groups, hipMemcpyDeviceToHost, LN(c).stream));
-    HIPC(c, hipStreamSynchronize(LN(c).stream));
-    int bg = -1;
-    for (int g = 0; g < groups; g++) {
-        if (hr[g].status != 0) ORIP_FAIL(c, "kmeans kernel did not complete (group %d, status %d)", g, hr[g].status);
-        if (bg < 0 || hr[g].compact < hr[bg].compact || (hr[g].compact == hr[bg].compact && hr[g].attempt < hr[bg].attempt)) bg = g;
-    }
-    memcpy(centers_out, hr[bg].cen, sizeof(float) * K * 3);
-    if (compactness_out) *compactness_out = hr[bg].compact;
-    return 0;
-}
-
-// The subsample of 02:39-44 depends on the pixel count and a fixed seed alone: a resident chain uploads it once and every later fit of an image of that
-// size gathers through the context's copy (the set's lifetime: orip_ctx.h).  Synchronised, so the caller's array is free on return.
-extern "C" int orip_kmeans_samples(orip_ctx* c, const int64_t* sample_idx, int64_t n_idx) {
-    orip_enter(c);
-    c->km_n = 0; c->km_npx = 0;
-    if (!sample_idx) return 0;
-    if (!c->image.p) ORIP_FAIL(c, "no image set");
-    const int64_t npx = (int64_t)c->H * c->W;
-    if (n_idx < 1 || n_idx > 0x7fffffff) ORIP_FAIL(c, "bad sample count %lld", (long long)n_idx);
-    for (int64_t i = 0; i < n_idx; i++)
-        if (sample_idx[i] < 0 || sample_idx[i] >= npx) ORIP_FAIL(c, "sample %lld is pixel %lld of %lld", (long long)i, (long long)sample_idx[i], (long long)npx);
-    HIPC(c, c->km_idx.ensure((size_t)n_idx * 8));
-    HIPC(c, hipMemcpyAsync(c->km_idx.p, sample_idx, (size_t)n_idx * 8, hipMemcpyHostToDevice, LN(c).stream));
-    HIPC(c, hipStreamSynchronize(LN(c).stream));
-    c->km_n = n_idx; c->km_npx = npx;
-    return 0;
-}
-extern "C" int orip_kmeans_samples_info(orip_ctx* c, int64_t* n_idx, int64_t* n_pixels) {
-    orip_enter(c);
-    if (n_idx) *n_idx = c->km_n;
-    if (n_pixels) *n_pixels = c->km_npx;
-    return 0;
-}
-
-extern "C" int orip_kmeans_fit(orip_ctx* c, const int64_t* sample_idx, int64_t n_idx, int K, int attempts, int max_iter, double eps,
-                               float* centers_out, double* compactness_out) {
-    return kmeans_fit_impl(c, false, sample_idx, n_idx, K, attempts, max_iter, eps, centers_out, compactness_out);
-}
-extern "C" int orip_kmeans_fit_rgb(orip_ctx* c, const int64_t* sample_idx, int64_t n_idx, int K, int attempts, int max_iter, double eps,
-                                   float* centers_out, double* compactness_out) {
-    return kmeans_fit_impl(c, true, sample_idx, n_idx, K, attempts, max_iter, eps, centers_out, compactness_out);
 }
 
 // process_colors.py assign_labels: labels u8 [H,W] of the image against an RGB palette, resident (orip_get_labels) and optionally on the host

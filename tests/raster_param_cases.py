@@ -57,6 +57,14 @@ def tiny_indices(K, N, npx=ATTEMPT_SHAPE[0] * ATTEMPT_SHAPE[1]):
     return np.random.default_rng(1000 * K + N).choice(npx, N, replace=False).astype(np.int64)
 
 
+# The device gives thread g of a group's 16 384 the samples [g * chunk, (g + 1) * chunk) below N, chunk = ceil(N / 16 384).  Sample counts at which the
+# chunk length changes: lengths 1, 1, 2, 2, 3, 3, 4; at 16 385 the upper half of the workgroups owns nothing and the last thread that owns anything owns
+# one sample.  The samples are the first N pixels of the image, K and the other arguments below.
+CHUNK_IMAGE = dict(seed=21, shape=(193, 255), K=5)
+CHUNK_NS = [16383, 16384, 16385, 32768, 32769, 49152, 49153]
+CHUNK_N_RGB = 16385              # this one through the RGB fit as well
+
+
 def two_colour_bgr(shape=(40, 50)):
     """two colours in random positions: every attempt with K = 2 ends exactly as compact as every other, and which colour is centre 0 follows from the
     attempt's first draw -- only the choice among EQUAL attempts decides the centres' order"""

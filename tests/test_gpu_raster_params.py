@@ -101,6 +101,24 @@ def test_kmeans_tiny_samples(dev, K, N):
     _fit_matches(dev, img[:, :, ::-1].reshape(-1, 3).astype(np.float32), idx, K, rgb=True)
 
 
+@pytest.fixture(scope="module")
+def chunk_image():
+    im = C.CHUNK_IMAGE
+    img = C.noise_bgr(im["seed"], im["shape"])
+    return img, _lab(img), img[:, :, ::-1].reshape(-1, 3).astype(np.float32), im["K"]
+
+
+@pytest.mark.parametrize("N", C.CHUNK_NS)
+def test_kmeans_chunk_lengths(dev, chunk_image, N):
+    """sample counts at which a thread's chunk of samples grows by one (tests/test_oracle_raster_params.py: the last sample decides every one of them)"""
+    img, lab, rgb, K = chunk_image
+    dev.set_image(img)
+    idx = np.arange(N, dtype=np.int64)
+    _fit_matches(dev, lab, idx, K)
+    if N == C.CHUNK_N_RGB:
+        _fit_matches(dev, rgb, idx, K, rgb=True)
+
+
 def test_kmeans_uniform_image(dev):
     """every distance is 0: three equal centres, compactness 0, two clusters filled by the empty-cluster repair"""
     img = np.full((20, 30, 3), (40, 90, 200), np.uint8)

@@ -98,6 +98,18 @@ def test_combinations_are_distinct(sweep_sample):
     assert len(set(res)) >= 5
 
 
+@pytest.mark.parametrize("N", C.CHUNK_NS)
+def test_chunk_lengths_last_sample_decides(N):
+    """the fit of the first N samples is not the fit of the first N - 1: a device that drops the last sample of the last chunk fails the GPU case"""
+    im = C.CHUNK_IMAGE
+    s = _lab(C.noise_bgr(im["seed"], im["shape"]))
+    assert N <= len(s) and N in C.CHUNK_NS and C.CHUNK_N_RGB in C.CHUNK_NS
+    assert [-(-n // 16384) for n in C.CHUNK_NS] == [1, 1, 2, 2, 3, 3, 4]
+    cen, comp = O.kmeans(s[:N], im["K"], *C.KM_DEFAULT)
+    cen1, comp1 = O.kmeans(s[:N - 1], im["K"], *C.KM_DEFAULT)
+    assert comp != comp1 or not np.array_equal(cen, cen1)
+
+
 def test_uniform_image_three_equal_centres():
     s = _lab(np.full((20, 30, 3), (40, 90, 200), np.uint8))
     cen, comp = O.kmeans(s, 3)

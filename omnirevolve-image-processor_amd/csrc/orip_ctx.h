@@ -17,7 +17,7 @@
 //   ORIP_NO_CHAINS         per-pixel stepping of the walker           chains shorter than ORIP_CHAIN_MIN
 //   ORIP_TRACE_LATE        traces started by orip_contours_layer      a lane held by another thread
 //   ORIP_PAINT_SEPARABLE   separable line painting in stage 10        its radius and size conditions
-// Debug and test hooks, which change no result: ORIP_CAPS_TINY, ORIP_COMP_CAPS, ORIP_TIME08, ORIP_TIME10, ORIP_WALK_DBG, ORIP_NN_DBG2, ORIP_TAIL_DBG,
+// Debug and test hooks, which change no result: ORIP_CAPS_TINY, ORIP_CAPSSET_TINY, ORIP_CAPS_RANGE, ORIP_COMP_CAPS, ORIP_TIME08, ORIP_TIME10, ORIP_WALK_DBG, ORIP_NN_DBG2, ORIP_TAIL_DBG,
 // ORIP_ALLOC_DBG, ORIP_TRACE_LOG_F, ORIP_SERIAL_LAYERS.
 
 #include <hip/hip_runtime.h>

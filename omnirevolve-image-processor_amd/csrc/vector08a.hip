@@ -720,52 +720,98 @@ __global__ __launch_bounds__(256) void k_caps_init(CapSlot* __restrict__ tab, un
 }
 // CP: capprev is given (some sample is off the canvas).  Without it every sample is on the canvas, the capsule of sample g runs from sample g - 1, and it has
 // one unless g is the first sample of its polyline -- which its own pxy word says (ORIP_PXY_FIRST): two independent loads and the table, no rank or base.
+//
+// The set in LDS.  A probe whose key is in the table with a smaller sample index reads the slot and leaves, and on a retraced path that is nearly every
+// probe; the repeats are close together in sample order (consecutive laps of one walk are contiguous).  So a workgroup owns a RANGE of `chunks` * 1024
+// consecutive samples, goes through it in ascending chunks of 1024 and keeps in LDS the keys it has seen: `smask` + 1 slots of a 64-bit key (0: empty, as in
+// the table) and the smallest sample index of that key in the range, open addressing over at most ORIP_CAPSSET_PROBES slots, the slot index from the top bits of
+// hash64(key) (the table index takes the low ones).  Per chunk: (1) every live sample finds its key or claims an empty slot (atomicCAS) and takes the minimum
+// of the slot's index with its own g (atomicMin); one that meets neither within the bound is "not in the set"; one barrier; (2) a sample goes to the
+// table if it is not in the set or if the slot's index is its own -- the probe loop as it was.  Exact: the table has to end up with the minimum g per key.
+// Indices ascend with the chunks, so the first occurrence of a key in the range fixes the slot's index for good, it alone of the range's occurrences can be
+// the global minimum, and it reaches the table; so does every occurrence that did not fit.  Slots only ever fill up (nothing is evicted), so all occurrences
+// of a key walk the same slots to the same end: one slot per key, or none.  Within a chunk the atomicMin and the barrier decide, not the winner of the CAS,
+// who can be the later of two.  A later chunk's atomicMin cannot lower an index (its g are larger), so phase 2 of one chunk may run beside phase 1 of the
+// next: one barrier per chunk.  Barrier rule (kmeans02.hip): the loop's bounds come from blockIdx.x, `chunks` and MS alone, samples beyond MS are dead lanes.
+constexpr int ORIP_CAPSSET_PROBES = 4;
+constexpr int ORIP_CAPSSET_SHIFT = 52;      // the top 12 bits of the hash: up to 4096 slots
 template <bool CP>
 __global__ __launch_bounds__(256) void k_caps_insert(SampleArrs A, const unsigned* __restrict__ sbase, const int* __restrict__ capprev, unsigned MS,
+                                                      unsigned chunks, unsigned smask,
                                                       CapSlot* tab, unsigned long long tmask, int max_probe, int* __restrict__ overflow) {
-    // Four samples per thread, a block's 1024 samples apart by 256: with one sample per thread the kernel waits for its chain of dependent loads one after the
+    // Four samples per thread, a chunk's 1024 samples apart by 256: with one sample per thread the kernel waits for its chain of dependent loads one after the
     // other (1 TB/s of the card's 8 with every wave slot full); four independent chains per thread keep four times as many loads in flight.  With capprev the
     // chain is rank -> base -> pixels -> slot, without it pixels -> slot.
     constexpr int S = 4;
-    const unsigned g0 = blockIdx.x * (256 * S) + threadIdx.x;
-    unsigned g[S]; bool on[S];
-    unsigned long long key[S], h[S]; unsigned pa[S], pb[S];
+    extern __shared__ unsigned long long caps_set[];
+    unsigned long long* skey = caps_set; unsigned* sval = reinterpret_cast<unsigned*>(caps_set + (smask + 1u));
+    for (unsigned i = threadIdx.x; i <= smask; i += 256) { skey[i] = 0ULL; sval[i] = 0xffffffffu; }
+    __syncthreads();
+    const unsigned long long first = (unsigned long long)blockIdx.x * chunks * 1024ull;       // < MS: the grid is cdiv(MS, chunks * 1024)
+    const unsigned long long left = (unsigned long long)MS - first;
+    const unsigned nch = left < chunks * 1024ull ? (unsigned)((left + 1023ull) >> 10) : chunks;
+    // the pixel words of a chunk; without capprev they are two independent loads, issued one chunk ahead (in front of the barrier of the chunk before)
+    auto pixels = [&](unsigned ch, unsigned (&pa)[S], unsigned (&pb)[S], bool (&on)[S]) {
+        unsigned g[S];
 #pragma unroll
-    for (int u = 0; u < S; u++) { g[u] = g0 + 256u * u; on[u] = g[u] < MS; key[u] = 0; h[u] = 0; pa[u] = 0; pb[u] = 0; }
-    if constexpr (CP) {
-        unsigned bb[S]; int cp[S];
+        for (int u = 0; u < S; u++) { g[u] = (unsigned)first + ch * 1024u + threadIdx.x + 256u * u; on[u] = ch < nch && g[u] < MS; pa[u] = 0; pb[u] = 0; }
+        if constexpr (CP) {
+            unsigned bb[S]; int cp[S];
 #pragma unroll
-        for (int u = 0; u < S; u++) bb[u] = on[u] ? A.rank[g[u]] : 0u;
+            for (int u = 0; u < S; u++) bb[u] = on[u] ? A.rank[g[u]] : 0u;
 #pragma unroll
-        for (int u = 0; u < S; u++) if (on[u]) bb[u] = sbase[bb[u]];
+            for (int u = 0; u < S; u++) if (on[u]) bb[u] = sbase[bb[u]];
 #pragma unroll
-        for (int u = 0; u < S; u++) { cp[u] = on[u] ? capprev[g[u]] : -1; on[u] = cp[u] >= 0; }
+            for (int u = 0; u < S; u++) { cp[u] = on[u] ? capprev[g[u]] : -1; on[u] = cp[u] >= 0; }
 #pragma unroll
-        for (int u = 0; u < S; u++) if (on[u]) pa[u] = A.pxy[bb[u] + cp[u]], pb[u] = A.pxy[g[u]];      // both on the canvas (cp >= 0): packed pixels
-    } else {
+            for (int u = 0; u < S; u++) if (on[u]) pa[u] = A.pxy[bb[u] + cp[u]], pb[u] = A.pxy[g[u]];      // both on the canvas (cp >= 0): packed pixels
+        } else {
 #pragma unroll
-        for (int u = 0; u < S; u++) if (on[u]) { pb[u] = A.pxy[g[u]]; pa[u] = g[u] ? A.pxy[g[u] - 1u] : 0u; }
+            for (int u = 0; u < S; u++) if (on[u]) { pb[u] = A.pxy[g[u]]; pa[u] = g[u] ? A.pxy[g[u] - 1u] : 0u; }
+        }
+    };
+    unsigned npa[S], npb[S]; bool non[S];
+    pixels(0, npa, npb, non);
+    for (unsigned ch = 0; ch < nch; ch++) {
+        unsigned g[S]; bool on[S]; unsigned long long key[S], h[S]; int ss[S];
 #pragma unroll
-        for (int u = 0; u < S; u++) on[u] = on[u] && !(pb[u] & ORIP_PXY_FIRST);
-    }
+        for (int u = 0; u < S; u++) {
+            g[u] = (unsigned)first + ch * 1024u + threadIdx.x + 256u * u; key[u] = 0; h[u] = 0; ss[u] = -1;
+            on[u] = non[u]; if constexpr (!CP) on[u] = on[u] && !(npb[u] & ORIP_PXY_FIRST);
+            if (on[u]) key[u] = cap_key(pxy_x(npa[u]), pxy_y(npa[u]), pxy_x(npb[u]), pxy_y(npb[u]));
+        }
+        pixels(ch + 1, npa, npb, non);          // (past the range: no load)
+        // ---- 1: into the set
 #pragma unroll
-    for (int u = 0; u < S; u++) {
-        if (on[u]) { key[u] = cap_key(pxy_x(pa[u]), pxy_y(pa[u]), pxy_x(pb[u]), pxy_y(pb[u])); h[u] = hash64(key[u]) & tmask; }
-    }
-    uint4 sl[S];
+        for (int u = 0; u < S; u++) {
+            if (!on[u]) continue;
+            const unsigned long long hs = hash64(key[u]);
+            h[u] = hs & tmask;
+            unsigned i = (unsigned)(hs >> ORIP_CAPSSET_SHIFT) & smask;
+            for (int p = 0; p < ORIP_CAPSSET_PROBES; p++, i = (i + 1u) & smask) {
+                const unsigned long long old = atomicCAS(&skey[i], 0ULL, key[u]);
+                if (old == 0ULL || old == key[u]) { atomicMin(&sval[i], g[u]); ss[u] = (int)i; break; }
+            }
+        }
+        __syncthreads();
+        // ---- 2: the first occurrence in the range, and whatever the set had no room for, to the table
 #pragma unroll
-    for (int u = 0; u < S; u++) sl[u] = on[u] ? *reinterpret_cast<const uint4*>(&tab[h[u]]) : make_uint4(0, 0, 0, 0);      // first probes of all four in flight together
+        for (int u = 0; u < S; u++) on[u] = on[u] && (ss[u] < 0 || sval[ss[u]] == g[u]);
+        uint4 sl[S];
 #pragma unroll
-    for (int u = 0; u < S; u++) {
-        if (!on[u]) continue;
-        uint4 s = sl[u]; unsigned long long hh = h[u];
-        for (int probe = 0;; probe++) {
-            if (probe >= max_probe) { *overflow = 1; break; }      // table too small for the number of distinct capsules: the host retries larger
-            if (probe) s = *reinterpret_cast<const uint4*>(&tab[hh]);      // key and value in one 16-byte load (every probe reads another slot)
-            unsigned long long cur = ((unsigned long long)s.y << 32) | s.x;
-            if (cur == 0) { unsigned long long old = atomicCAS(&tab[hh].key, 0ULL, key[u]); if (old == 0 || old == key[u]) cur = key[u]; else cur = old; }
-            if (cur == key[u]) { if (s.z > g[u]) atomicMin(&tab[hh].val, g[u]); break; }    // the minimum only decreases: a stale read can only cost a useless atomic
-            hh = (hh + 1) & tmask;
+        for (int u = 0; u < S; u++) sl[u] = on[u] ? *reinterpret_cast<const uint4*>(&tab[h[u]]) : make_uint4(0, 0, 0, 0);      // first probes of all four in flight together
+#pragma unroll
+        for (int u = 0; u < S; u++) {
+            if (!on[u]) continue;
+            uint4 s = sl[u]; unsigned long long hh = h[u];
+            for (int probe = 0;; probe++) {
+                if (probe >= max_probe) { *overflow = 1; break; }      // table too small for the number of distinct capsules: the host retries larger
+                if (probe) s = *reinterpret_cast<const uint4*>(&tab[hh]);      // key and value in one 16-byte load (every probe reads another slot)
+                unsigned long long cur = ((unsigned long long)s.y << 32) | s.x;
+                if (cur == 0) { unsigned long long old = atomicCAS(&tab[hh].key, 0ULL, key[u]); if (old == 0 || old == key[u]) cur = key[u]; else cur = old; }
+                if (cur == key[u]) { if (s.z > g[u]) atomicMin(&tab[hh].val, g[u]); break; }    // the minimum only decreases: a stale read can only cost a useless atomic
+                hh = (hh + 1) & tmask;
+            }
         }
     }
 }
@@ -1189,6 +1235,21 @@ static int a4_capsules(orip_ctx* c, const orip_params08& P, A08& a) {
     if (LN(c).caps_hint) { while (tsize < 3ull * LN(c).caps_hint) tsize <<= 1; } else { while (tsize < MS / 4ull) tsize <<= 1; }
     tsize = std::min(tsize, tfull);
     if (getenv("ORIP_CAPS_TINY")) tsize = 1024;            // test hook: exercise the growth path
+    // The range of samples a workgroup owns and the slots of its set in LDS (k_caps_insert).  A longer range filters more and leaves fewer workgroups, each
+    // going through its chunks one after the other: the card holds 256 x 6 workgroups of 24 KB of LDS at a time, so the largest range that still leaves
+    // 2048 of them, down to one chunk, where the set only filters inside the chunk.  (Candidates and their times, longer ranges included: DESIGN 8.3.)
+    static const unsigned cand[] = {8192u, 4096u, 2048u, 1024u};
+    unsigned R = 1024u, TS = 2048u;
+    for (unsigned r : cand) if (cdiv(MS, r) >= 2048 || r == 1024u) { R = r; break; }
+    if (const char* e = getenv("ORIP_CAPS_RANGE")) {       // test hook: "R" or "R:T", a range of R samples (and a set of T slots) whatever the layer's size
+        char* end = nullptr; const unsigned long r = strtoul(e, &end, 10); unsigned long t = TS;
+        if (end && *end == ':') t = strtoul(end + 1, nullptr, 10);
+        if (r < 1024 || r > 65536 || (r & 1023)) ORIP_FAIL(c, "ORIP_CAPS_RANGE: a multiple of 1024 up to 65536");
+        if (t < 32 || t > 4096 || (t & (t - 1))) ORIP_FAIL(c, "ORIP_CAPS_RANGE: a power of two from 32 to 4096 slots");
+        R = (unsigned)r; TS = (unsigned)t;
+    }
+    if (getenv("ORIP_CAPSSET_TINY")) TS = 32u;             // test hook: most samples find no room in the set
+    const unsigned lds = TS * 12u;                         // 64-bit keys, then 32-bit sample indices: 24 KB
     CapSlot* tab = nullptr;
     int* d_ovf = &fl->caps_overflow; unsigned* d_dist = &fl->caps_distinct;
     for (;; tsize = std::min(tfull, tsize * 4)) {
@@ -1197,8 +1258,8 @@ static int a4_capsules(orip_ctx* c, const orip_params08& P, A08& a) {
         hipLaunchKernelGGL(k_caps_init, dim3((unsigned)cdiv(tsize, 256)), dim3(256), 0, LN(c).stream, tab, tsize, fl);      // (and the counters of A4 / A5)
         const int max_probe = tsize >= tfull ? 0x7fffffff : 96;
         { ProfScope ps(c, "k_caps_insert");
-          if (a.capprev) hipLaunchKernelGGL(k_caps_insert<true>, dim3(cdiv(MS, 1024)), dim3(256), 0, LN(c).stream, a.A, a.sbase, a.capprev, MS, tab, tsize - 1, max_probe, d_ovf);
-          else hipLaunchKernelGGL(k_caps_insert<false>, dim3(cdiv(MS, 1024)), dim3(256), 0, LN(c).stream, a.A, a.sbase, a.capprev, MS, tab, tsize - 1, max_probe, d_ovf); }
+          if (a.capprev) hipLaunchKernelGGL(k_caps_insert<true>, dim3(cdiv(MS, R)), dim3(256), lds, LN(c).stream, a.A, a.sbase, a.capprev, MS, R / 1024u, TS - 1u, tab, tsize - 1, max_probe, d_ovf);
+          else hipLaunchKernelGGL(k_caps_insert<false>, dim3(cdiv(MS, R)), dim3(256), lds, LN(c).stream, a.A, a.sbase, a.capprev, MS, R / 1024u, TS - 1u, tab, tsize - 1, max_probe, d_ovf); }
         int ovf = 0; ORIP_TRY(vread(c, &ovf, d_ovf));
         if (!ovf) break;
     }

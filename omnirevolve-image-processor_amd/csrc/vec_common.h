@@ -70,6 +70,21 @@ __device__ __forceinline__ int64_t ub_u32(const unsigned* a, int64_t n, unsigned
     while (lo < hi) { int64_t mid = (lo + hi) >> 1; if (a[mid] <= v) lo = mid + 1; else hi = mid; }
     return lo;
 }
+// inclusive scans over the 64 lanes of a wave in six DPP steps: sum and running maximum (stage 08-A's cumulative lengths and tail replay, the grid greedy's wide rounds)
+__device__ __forceinline__ unsigned wave_incl_scan_u32(unsigned v) {
+#define ORIP_DPP_ADD(ctrl, rowmask) v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, ctrl, rowmask, 0xf, false);
+    ORIP_DPP_ADD(0x111, 0xf) ORIP_DPP_ADD(0x112, 0xf) ORIP_DPP_ADD(0x114, 0xf) ORIP_DPP_ADD(0x118, 0xf)      // row_shr 1, 2, 4, 8
+    ORIP_DPP_ADD(0x142, 0xa) ORIP_DPP_ADD(0x143, 0xc)                                                          // row_bcast 15, 31
+#undef ORIP_DPP_ADD
+    return v;
+}
+__device__ __forceinline__ unsigned wave_incl_scan_max_u32(unsigned v) {                  // running maximum over the lanes, the same six DPP steps
+#define ORIP_DPP_MAX(ctrl, rowmask) { const unsigned t_ = (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, ctrl, rowmask, 0xf, false); v = t_ > v ? t_ : v; }
+    ORIP_DPP_MAX(0x111, 0xf) ORIP_DPP_MAX(0x112, 0xf) ORIP_DPP_MAX(0x114, 0xf) ORIP_DPP_MAX(0x118, 0xf)
+    ORIP_DPP_MAX(0x142, 0xa) ORIP_DPP_MAX(0x143, 0xc)
+#undef ORIP_DPP_MAX
+    return v;
+}
 // a cursor as the point getter vec_serial.h's sums take
 template <class Cur> struct CurPt {
     Cur& c;

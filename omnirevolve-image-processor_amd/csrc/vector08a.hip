@@ -97,24 +97,10 @@ __global__ __launch_bounds__(128) void k_cumlen(Src src, int64_t n_polys, double
 // ---- float32 np.cumsum without the serial chain (r03).  While the running sum p stays inside one binade [2^e, 2^(e+1)) its ulp u is fixed and
 // p is a multiple of u, so fl(p + d) = p + R(d) with R(d) = d rounded to a multiple of u: an INTEGER increment that does not depend on p -- except
 // (i) when d lies exactly half-way between two multiples of u (round-half-even looks at p's last bit) and (ii) when the sum reaches 2^(e+1) (the ulp
-// doubles).  A window of 64 lengths is therefore one integer wave scan; the first lane where (i) or (ii) happens does ONE real float add from its
+// doubles).  A window of 64 lengths is therefore one integer wave scan (vec_common.h: wave_incl_scan_u32); the first lane where (i) or (ii) happens does ONE real float add from its
 // neighbour's exact sum, and the lanes behind it are scanned again in the new binade.  A polyline crosses a binade ~18 times and meets a tie only
 // where the low bits of a length happen to be 10..0 at the current ulp; every other window costs one scan instead of 63 dependent adds.
 // State: E = biased exponent of p (0: p == 0), M = 24-bit significand; both wave-uniform.  Lengths are finite and >= 0.
-__device__ __forceinline__ unsigned wave_incl_scan_u32(unsigned v) {
-#define ORIP_DPP_ADD(ctrl, rowmask) v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, ctrl, rowmask, 0xf, false);
-    ORIP_DPP_ADD(0x111, 0xf) ORIP_DPP_ADD(0x112, 0xf) ORIP_DPP_ADD(0x114, 0xf) ORIP_DPP_ADD(0x118, 0xf)      // row_shr 1, 2, 4, 8
-    ORIP_DPP_ADD(0x142, 0xa) ORIP_DPP_ADD(0x143, 0xc)                                                          // row_bcast 15, 31
-#undef ORIP_DPP_ADD
-    return v;
-}
-__device__ __forceinline__ unsigned wave_incl_scan_max_u32(unsigned v) {                  // running maximum over the lanes, the same six DPP steps
-#define ORIP_DPP_MAX(ctrl, rowmask) { const unsigned t_ = (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, ctrl, rowmask, 0xf, false); v = t_ > v ? t_ : v; }
-    ORIP_DPP_MAX(0x111, 0xf) ORIP_DPP_MAX(0x112, 0xf) ORIP_DPP_MAX(0x114, 0xf) ORIP_DPP_MAX(0x118, 0xf)
-    ORIP_DPP_MAX(0x142, 0xa) ORIP_DPP_MAX(0x143, 0xc)
-#undef ORIP_DPP_MAX
-    return v;
-}
 __device__ __forceinline__ float cum_window(float dval, int lane, unsigned& E, unsigned& M) {
     const unsigned b = __float_as_uint(dval);
     const unsigned Ed = b >> 23, Md = Ed ? ((b & 0x7fffffu) | 0x800000u) : 0u;

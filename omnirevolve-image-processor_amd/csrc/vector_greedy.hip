@@ -521,7 +521,11 @@ __device__ __forceinline__ int nn_asm_steps(int& cx, int& cy, int& step, unsigne
 //     registers (v_readlane), not from another LDS round trip;
 //   * "no unscanned cell can be nearer" is an integer test: floor(d2) + 1 <= gap^2 - gap^2 / 2^18 - 1 (the three float roundings of a
 //     squared distance stay below 2^-22 relative): conservative, so at worst one more round is scanned, never a wrong winner;
-//   * results leave through a VGPR (one lane per step, 64 at a time).
+//   * results leave through a VGPR (one lane per step, 64 at a time);
+//   * a window taller than three rows (r >= 3: what the asm loop hands back) is one pass per 64 rows: the rows' bounds in the lanes, a wave scan
+//     over their counts, and the candidates 64 per trip across the rows -- not a scalar round trip per row.
+// Dynamic LDS: P (8 n bytes), cst (4 (G^2 + 2)), Eid (room for 2 n entries of 2 bytes), and behind it wtab, 129 words (NN_WTAB_BYTES) that map the
+// ordinals of a wide round's trip to their rows; the host's 158 KB check covers the first three, wtab lies between it and the CU's 160 KB.
 __global__ __launch_bounds__(64) void k_greedy_nn_fast(const NNEnds* __restrict__ ends, int n, const int* __restrict__ sel, int skip_if, int need_any, int rule07, int G,
                                                         int32_t* __restrict__ order, uint8_t* __restrict__ flips, int no_asm, unsigned long long* __restrict__ dbg) {
     ORIP_NN_GATE(sel, skip_if, need_any)
@@ -529,6 +533,8 @@ __global__ __launch_bounds__(64) void k_greedy_nn_fast(const NNEnds* __restrict_
     uint2* P = reinterpret_cast<uint2*>(smem);                                     // .x = sx | sy << 16, .y = ex | ey << 16; bit 15 of sx: used, bit 15 of sy: closed (rule07)
     unsigned* cst = reinterpret_cast<unsigned*>(P + n);                            // cst[0] = 0, cst[c + 1] = end of cell c
     uint16_t* Eid = reinterpret_cast<uint16_t*>(cst + (G * G + 2));                // entries sorted by cell: idx << 1 | end
+    unsigned* wtab = reinterpret_cast<unsigned*>(Eid + 2 * n);                     // behind room for 2 n entries: 128 slots + a spare one, the rows of a wide round's trip (NN_WTAB_BYTES)
+    const unsigned long long t_k0 = dbg ? __builtin_amdgcn_s_memtime() : 0ull;
     const int lane = threadIdx.x;
 #define NNU(x) __builtin_amdgcn_readfirstlane((int)(x))
     int mnx = 0x7fffffff, mny = 0x7fffffff, mxx = -0x7fffffff, mxy = -0x7fffffff;
@@ -580,6 +586,8 @@ __global__ __launch_bounds__(64) void k_greedy_nn_fast(const NNEnds* __restrict_
     const int rowoff = lane < 6 ? (lane >> 1) : 0, isend = lane < 6 ? (lane & 1) : 0;
     int step = 1, r_first = 1;
     unsigned long long d_fb = 0, d_calls = 0, t_asm = 0, t_gen = 0;      // ORIP_NN_DBG2: steps taken by the compiled code, asm entries, cycles in either
+    unsigned d_rounds = 0, d_cand = 0;                                   // ... its rounds and the candidates they hold (entries of the windows' cells)
+    if (dbg && lane == 0) dbg[9] = (__builtin_amdgcn_s_memtime() - t_k0) << 32;     // ... cycles of the prologue (bounding box, P, the grid), above the count of word 9
     while (step < n) {
         if (use_asm) {
             const unsigned long long t_0 = dbg ? __builtin_amdgcn_s_memtime() : 0ull;
@@ -599,18 +607,26 @@ __global__ __launch_bounds__(64) void k_greedy_nn_fast(const NNEnds* __restrict_
         for (int r = r_first;; r = 2 * r + 1) {
             const int x0 = max(0, gx - r), x1 = min(Gm1, gx + r), y0 = max(0, gy - r), y1 = min(Gm1, gy + r);
             unsigned myk = ~0u, myi = 0x7fffffffu, my0 = 0, my1 = 0;
+            d_rounds++;
             // entry `q` (clamped into the table) as a candidate; valid == false: counts as infinitely far
-            auto consider = [&](unsigned q, bool valid) {
-                const unsigned id = Eid[q < n_ent ? q : n_ent - 1u]; const unsigned i = id >> 1;
-                const uint2 e = P[i];
-                const unsigned xy = (id & 1u) ? e.y : (e.x & 0x7fff7fffu);
+            struct Cand { unsigned k, i; uint2 e; };
+            auto fetch = [&](unsigned q, bool valid) {
+                const unsigned id = Eid[q < n_ent ? q : n_ent - 1u]; Cand c; c.i = id >> 1;
+                c.e = P[c.i];
+                const unsigned xy = (id & 1u) ? c.e.y : (c.e.x & 0x7fff7fffu);
                 const float dx = __fsub_rn((float)(xy & 0xffffu), fx), dy = __fsub_rn((float)(xy >> 16), fy);
-                unsigned k = __float_as_uint(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)));
-                k = (valid && !(e.x & 0x8000u)) ? k : ~0u;                           // used polylines (the previous one among them) do not count
-                const unsigned long long key = ((unsigned long long)k << 32) | i, mine = ((unsigned long long)myk << 32) | myi;
-                const bool better = key < mine;
-                myk = better ? k : myk; myi = better ? i : myi; my0 = better ? e.x : my0; my1 = better ? e.y : my1;
+                const unsigned k = __float_as_uint(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)));
+                c.k = (valid && !(c.e.x & 0x8000u)) ? k : ~0u;                       // used polylines (the previous one among them) do not count
+                return c;
             };
+            auto merge = [&](const Cand& c) {
+                const unsigned long long key = ((unsigned long long)c.k << 32) | c.i, mine = ((unsigned long long)myk << 32) | myi;
+                const bool better = key < mine;
+                myk = better ? c.k : myk; myi = better ? c.i : myi; my0 = better ? c.e.x : my0; my1 = better ? c.e.y : my1;
+            };
+            auto consider = [&](unsigned q, bool valid) { merge(fetch(q, valid)); };
+            // two candidates per lane, both fetched before either is compared: their LDS reads are in flight together
+            auto consider2 = [&](unsigned qa, bool va, unsigned qb, bool vb) { const Cand a = fetch(qa, va), b = fetch(qb, vb); merge(a); merge(b); };
             if (y1 - y0 <= 2) {
                 // lanes 0..5: start / end of the entry range of the (up to) three rows
                 const int row = y0 + (lane >> 1);
@@ -620,6 +636,7 @@ __global__ __launch_bounds__(64) void k_greedy_nn_fast(const NNEnds* __restrict_
                 const unsigned lo1 = (unsigned)__builtin_amdgcn_readlane((int)bnd, 2), n1 = (unsigned)__builtin_amdgcn_readlane((int)bnd, 3) - lo1;
                 const unsigned lo2 = (unsigned)__builtin_amdgcn_readlane((int)bnd, 4), n2 = (unsigned)__builtin_amdgcn_readlane((int)bnd, 5) - lo2;
                 const unsigned n01 = n0 + n1, total = n01 + n2;
+                if (dbg) d_cand += total;
                 for (unsigned t0 = 0; t0 < total; t0 += 64) {                        // uniform trip count, no exec masking
                     const unsigned t = t0 + lane;
                     unsigned q = lo0 + t;
@@ -628,9 +645,31 @@ __global__ __launch_bounds__(64) void k_greedy_nn_fast(const NNEnds* __restrict_
                     consider(q, t < total);
                 }
             } else {
-                for (int row = y0; row <= y1; row++) {
-                    const unsigned lo = (unsigned)NNU(cst[row * G + x0]), hi = (unsigned)NNU(cst[row * G + x1 + 1]);
-                    for (unsigned q0 = lo; q0 < hi; q0 += 64) consider(q0 + lane, q0 + lane < hi);
+                // a taller window, 64 rows per pass: lane L reads both bounds of row yc + L, a wave scan gives every row the ordinal of its first
+                // candidate, and the candidates go 128 per trip (two per lane), whatever rows they lie in -- no scalar round trip per row.  A trip
+                // finds its rows through wtab: every non-empty row that starts inside the trip writes (first ordinal << 16 | first entry) at the slot
+                // of that ordinal, the row that holds the trip's first ordinal writes slot 0, every other lane the spare slot 128; a running maximum
+                // over the slots (the words grow with the row) hands each ordinal the word of its row.  Ordinals and entries stay below 2^15.
+                for (int yc = y0; yc <= y1; yc += 64) {
+                    const int row = min(yc + lane, y1);
+                    const unsigned lo = cst[row * G + x0], hi = cst[row * G + x1 + 1];
+                    const unsigned cn = yc + lane <= y1 ? hi - lo : 0u;
+                    const unsigned incl = wave_incl_scan_u32(cn), excl = incl - cn;
+                    const unsigned total = (unsigned)__builtin_amdgcn_readlane((int)incl, 63);
+                    const unsigned word = (excl << 16) | lo;
+                    if (dbg) d_cand += total;
+                    for (unsigned t0 = 0; t0 < total; t0 += 128) {                   // uniform trip count, no exec masking; two ordinals per lane, their LDS reads in flight together
+                        // (lanes write slots that other lanes read: relaxed atomics with a wave-scope fence between them -- plain LDS writes and reads, in order)
+                        __hip_atomic_store(&wtab[lane], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+                        __hip_atomic_store(&wtab[64 + lane], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+                        __hip_atomic_store(&wtab[(cn != 0u && excl < t0 + 128u && incl > t0) ? max(excl, t0) - t0 : 128u], word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+                        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                        const unsigned wa = wave_incl_scan_max_u32(__hip_atomic_load(&wtab[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT));
+                        unsigned wb = wave_incl_scan_max_u32(__hip_atomic_load(&wtab[64 + lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT));
+                        wb = max(wb, (unsigned)__builtin_amdgcn_readlane((int)wa, 63));      // the row that reaches over from the first half
+                        const unsigned ta = t0 + lane, tb = ta + 64u;
+                        consider2((wa & 0xffffu) + (ta - (wa >> 16)), ta < total, (wb & 0xffffu) + (tb - (wb >> 16)), tb < total);
+                    }
                 }
             }
             // minimum distance pattern over the wave
@@ -687,7 +726,7 @@ __global__ __launch_bounds__(64) void k_greedy_nn_fast(const NNEnds* __restrict_
         step++;
         if (dbg) t_gen += __builtin_amdgcn_s_memtime() - t_g0;
     }
-    if (dbg && lane == 0) { dbg[0] = d_fb; dbg[1] = d_calls; dbg[2] = t_asm; dbg[3] = t_gen; }
+    if (dbg && lane == 0) { dbg[0] = d_fb | ((unsigned long long)d_rounds << 32); dbg[1] = d_calls | ((unsigned long long)d_cand << 32); dbg[2] = t_asm; dbg[3] = t_gen; }
     { const int done = n & ~63; if (done + lane < n) { order[done + lane] = (int32_t)(ringv >> 1); flips[done + lane] = (uint8_t)(ringv & 1u); } }
 #undef NNU
 }
@@ -697,9 +736,11 @@ __global__ __launch_bounds__(64) void k_greedy_nn_fast(const NNEnds* __restrict_
 static int nn_dbg2_report(orip_ctx* c, unsigned long long* dbg, int kind, int64_t n, int G) {
     unsigned long long h[10];
     HIPC(c, hipStreamSynchronize(LN(c).stream)); HIPC(c, hipMemcpy(h, dbg, 80, hipMemcpyDeviceToHost));
+    const unsigned long long lo32 = 0xffffffffull;      // words 0, 1 and 9 carry a second counter in their upper half
     fprintf(stderr, "[nn dbg2] kind %d n %lld G %d: %llu steps by the compiled code (empty %llu, all used %llu, gap %llu; asm steps from cached candidates: "
-                    "one per lane %llu, two per lane %llu; with more than 128 candidates %llu), %llu asm entries, cycles asm %llu compiled %llu\n",
-            kind, (long long)n, G, h[0], h[5], h[7], h[8], h[4], h[6], h[9], h[1], h[2], h[3]);
+                    "one per lane %llu, two per lane %llu; with more than 128 candidates %llu), %llu asm entries, cycles asm %llu compiled %llu; "
+                    "compiled rounds %llu with %llu candidates, prologue cycles %llu\n",
+            kind, (long long)n, G, h[0] & lo32, h[5], h[7], h[8], h[4], h[6], h[9] & lo32, h[1] & lo32, h[2], h[3], h[0] >> 32, h[1] >> 32, h[9] >> 32);
     HIPC(c, hipMemsetAsync(dbg, 0, 80, LN(c).stream));
     return 0;
 }
@@ -724,11 +765,12 @@ int vreorder(orip_ctx* c, DPolys& src, DPolys& dst, int kind, const orip_params0
     // but not many more cells than polylines
     int G = 8; while (G < 128 && (size_t)(G + 8) * (G + 8) <= 4 * (size_t)n && (size_t)n * 12 + (size_t)((G + 8) * (G + 8) + 1) * 4 + 64 <= 158 * 1024) G += 8;
     const size_t lds_grid = (size_t)n * 12 + (size_t)(G * G + 1) * 4 + 64;        // (+4 for k_greedy_nn_fast: inside the 64 spare bytes of the 158 KB check)
+    constexpr size_t NN_WTAB_BYTES = 129 * 4;                                     // k_greedy_nn_fast's wtab, behind the 158 KB the check admits: the CU has 160 KB
     static std::once_flag attr_once;                // several layer threads may arrive here together
     static std::atomic<int> attr_err{0};
     std::call_once(attr_once, [] {
         orip_max_lds(k_greedy_nn<NNStoreLds>, 150 * 1024, attr_err);
-        orip_max_lds(k_greedy_nn_fast, 158 * 1024, attr_err);
+        orip_max_lds(k_greedy_nn_fast, 158 * 1024 + 4 + (int)NN_WTAB_BYTES, attr_err);
     });
     if (attr_err.load()) ORIP_FAIL(c, "hipFuncSetAttribute(greedy kernels) failed: %s", hipGetErrorString((hipError_t)attr_err.load()));
     // Seed and coordinate-range flags stay on the device: every kernel that may have to run is enqueued and picks itself from the flags
@@ -742,7 +784,7 @@ int vreorder(orip_ctx* c, DPolys& src, DPolys& dst, int kind, const orip_params0
         if (grid_ok) {
             unsigned long long* dbg2 = getenv("ORIP_NN_DBG2") ? fl->nn_dbg2 : nullptr;
             if (dbg2) HIPC(c, hipMemsetAsync(dbg2, 0, 80, LN(c).stream));
-            hipLaunchKernelGGL(k_greedy_nn_fast, dim3(1), dim3(64), lds_grid + 4, LN(c).stream, ends, (int)n, d_seed, NN_BEYOND_I16 | NN_BEYOND_15BIT, 0, r07, G, order, flips, getenv("ORIP_NN_NOASM") ? 1 : 0, dbg2);
+            hipLaunchKernelGGL(k_greedy_nn_fast, dim3(1), dim3(64), lds_grid + 4 + NN_WTAB_BYTES, LN(c).stream, ends, (int)n, d_seed, NN_BEYOND_I16 | NN_BEYOND_15BIT, 0, r07, G, order, flips, getenv("ORIP_NN_NOASM") ? 1 : 0, dbg2);
             if (dbg2) ORIP_TRY(nn_dbg2_report(c, dbg2, kind, n, G));
         }
         // Behind the grid kernel only ONE more launch, and a light one (256 threads, no dynamic LDS): a kernel that merely checks its flag and

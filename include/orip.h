@@ -458,6 +458,54 @@ int orip_gcode_occlude(orip_ctx* ctx, const int64_t* off /* [n+1] or NULL */, co
 int orip_svg_occlude(orip_ctx* ctx, const int32_t* level /* [n] */, int64_t n, const int32_t* ring_sub /* [m] */, const int32_t* ring_level /* [m] */, int64_t m,
                      const orip_gcode_map* map, int32_t flags /* ORIP_OCCLUDE_CLAMP */, int64_t* stats /* [10] */);
 int orip_gcode_occlude_fetch(orip_ctx* ctx, int32_t* origin /* [paths_out] */);
+/* --hatch-connect (csrc/gcode_link.hip; ours, the reference has no such pass): the lines of a hatch are drawn as zigzags.  Consecutive hatch lines of one
+ * shape are joined by a straight LINK where the link lies wholly inside the shape, so the pen stays down from one line to the next.  Integer arithmetic on
+ * the step grid throughout: no floating point, no tolerance.
+ * Input.  STROKES: n step polylines as every stroke pass takes them (two points or more, coordinates 0 .. 2^30) and cls[k] per stroke: -1 = the stroke
+ *   takes no part; otherwise cls[k] = 2 g + f >= 0, g < 2^30 the shape whose hatch the stroke belongs to, f the hatch family (0 along, 1 across).  Only
+ *   strokes of EXACTLY two points with cls >= 0 take part: the LINES.  Line k runs from its START (first point) to its END (second point).
+ *   RINGS: m rings of one point or more, coordinates -2^30 .. 2^30, ring_group[r] = g in 0 .. 2^30 - 1, NON-DECREASING; a ring is closed by the edge from
+ *   its last point to its first, edges of zero length are ignored, and all rings of one g form the SHAPE g (holes work): the conventions of
+ *   orip_gcode_occlude, with the shape's name in the place of its level.  A g without rings is a shape without interior.
+ *   In reach.  A link runs from the END E of line a to the START S of line b.  The pair (a, b) is IN REACH iff cls[a] == cls[b], a < b in the input list
+ *   (a hatch is only ever continued forwards, so the result depends on no processing order and no cycle can form), and dx^2 + dy^2 <= reach^2 for
+ *   (dx, dy) = S - E; |dx|, |dy| <= reach is looked at first, so the squares fit.  reach is in 1 .. 2^20.
+ *   Eligible.  A pair in reach is ELIGIBLE iff E is INSIDE shape g (even-odd, the boundary is not inside: orip_gcode_occlude's notion) and the closed
+ *   segment [E, S] shares no point with any edge of shape g: proper crossings, touching and collinear overlap all count, and E == S is a legal segment
+ *   of one point.  Together: the whole link lies in the open interior of the shape.  Orientation products reach 2^63: 128-bit integers.
+ *   Choice.  best(END a) = the eligible b with the least (d^2, b); best(START b) = the eligible a with the least (d^2, a); a -> b is a LINK iff each is
+ *   the other's best.  A line has at most one link out and one in and all links ascend: the links form open CHAINS.
+ *   Output.  A chain a0 -> a1 -> .. becomes one stroke a0.start, a0.end, a1.start, a1.end, ..; a point equal to its predecessor is dropped, and such a
+ *   link is counted in `coincident`.  Strokes leave in ascending order of their first (and lowest) member; a stroke that takes no part stays at its
+ *   place, bit for bit.  member_off[paths_out + 1] and member[n] (orip_gcode_hatch_link_fetch) name the input strokes of every output stroke in drawing
+ *   order, as orip_gcode_merge_fetch does; nothing is ever reversed.
+ * stats: lines, in_reach (pairs), eligible (pairs), links, coincident, paths_out, points_out, link_steps (the sum of max(|dx|, |dy|) over the links: the
+ *   pen-down steps the pass adds).
+ * Consequences.  paths_out == n - links and points_out == points_in - coincident.  Every output segment is an input segment or a link, in order.  Every
+ * link joins an END to a START of a later line of the same class within reach, meets no edge of its shape and starts inside it; a chain's members have one
+ * class.  A drawing in which nothing links comes back unchanged: m == 0, no line, or a hatch with inset 0, whose ends lie on the boundary.  The pass is NOT
+ * idempotent: a line left single because its best was taken can find a partner in a second run.
+ * orip_gcode_hatch_link: strokes explicit, or off == pts == NULL for the n resident step polylines; rings explicit, in steps.
+ * orip_svg_hatch_link: the strokes are the resident step polylines; ring r is the resident fitted path ring_sub[r], converted on the device by the
+ * conversion's own code (csrc/gc_convert.h), clamped to the sheet under ORIP_HATCH_LINK_CLAMP as orip_gcode_to_steps clamps: orip_svg_occlude's rings.
+ * In every form the result BECOMES the resident step polylines; while the sources name the input they are gathered through every stroke's first member
+ * (all members of a chain share shape and pen); an uploaded list of another count than the resident one has no sources until the next conversion.
+ * Errors before any launch, without a fault and with the resident polylines left as they were: the stroke and ring errors of orip_gcode_occlude (2^28
+ * points or more among them), cls < -1 (an int32 cls cannot name a g of 2^30 or more), ring_group decreasing or out of range, reach outside 1 .. 2^20, unknown flags, a
+ * bad map, NULL stats or arrays, a wrong resident count.  n == 0 returns zeros and (explicit form) the empty list.  Found on the device, leaving no list:
+ * a ring coordinate not finite or out of range after the conversion, 2^30 pairs in reach or more, counts that do not add up.
+ * Declined: reversing a line to link it (serpentine is the default and lines the ends up); links between the two families of a cross hatch, or between
+ * shapes; links that follow the outline instead of a straight segment; a link test against shapes painted above (the occlusion runs after this pass and
+ * cuts a link as it cuts any ink); a bound on the worst case (every pair in reach against every edge of its shape). */
+#define ORIP_HATCH_LINK_CLAMP 1
+#define ORIP_HATCH_LINK_STATS 8
+#define ORIP_HATCH_LINK_REACH_MAX (1 << 20)
+int orip_gcode_hatch_link(orip_ctx* ctx, const int64_t* off /* [n+1] or NULL */, const int32_t* pts /* [off[n],2] or NULL */, const int32_t* cls /* [n] */, int64_t n,
+                          const int64_t* ring_off /* [m+1] */, const int32_t* ring_pts /* [ring_off[m],2] */, const int32_t* ring_group /* [m] */, int64_t m,
+                          int32_t reach, int64_t* stats /* [8]: lines, in_reach, eligible, links, coincident, paths_out, points_out, link_steps */);
+int orip_svg_hatch_link(orip_ctx* ctx, const int32_t* cls /* [n] */, int64_t n, const int32_t* ring_sub /* [m] */, const int32_t* ring_group /* [m] */, int64_t m,
+                        const orip_gcode_map* map, int32_t flags /* ORIP_HATCH_LINK_CLAMP */, int32_t reach, int64_t* stats /* [8] */);
+int orip_gcode_hatch_link_fetch(orip_ctx* ctx, int64_t* member_off /* [paths_out+1] */, int32_t* member /* [n] */);
 /* --dashes / --dash-mm (csrc/gcode_dash.hip; ours, the reference has no such pass): a stroke with a dash pattern is drawn as its dashes.  All arithmetic is
  * integer on the step grid: nothing behind the conversion to steps is floating point.
  * Unit.  u = 1 / ORIP_DASH_UNIT = 1/256 step: every length below is in u.

@@ -16,6 +16,25 @@ __device__ __forceinline__ bool gc_round_mm(const orip_gcode_map& g, double xm, 
     return isfinite(xf) && isfinite(yf);
 }
 
+// A ring point of the passes whose shapes are resident fitted paths (the occlusion, the hatch link): the conversion above, clamped to the sheet as
+// orip_gcode_to_steps clamps when `clamp` is set, and nothing else: no point is dropped.  0, or why there is no point: the coordinate is not finite, or it
+// lies outside +-2^30 (o is then (0, 0))
+constexpr unsigned GC_RING_NOT_FINITE = 1, GC_RING_RANGE = 2;
+__device__ __forceinline__ unsigned gc_ring_step(const orip_gcode_map& g, const double2 mm, int clamp, int2& o) {
+    double xf, yf;
+    o = make_int2(0, 0);
+    if (!gc_round_mm(g, mm.x, mm.y, xf, yf)) return GC_RING_NOT_FINITE;
+    if (clamp) {
+        const double xmax = (double)(g.W - 1), ymax = (double)(g.H - 1);
+        xf = xf < 0.0 ? 0.0 : (xf > xmax ? xmax : xf);
+        yf = yf < 0.0 ? 0.0 : (yf > ymax ? ymax : yf);
+    }
+    const double top = (double)GC_COORD_MAX;
+    if (xf < -top || xf > top || yf < -top || yf > top) return GC_RING_RANGE;
+    o = make_int2((int)xf, (int)yf);
+    return 0;
+}
+
 // last p with off[p] <= i (paths without points are skipped by the search)
 __device__ __forceinline__ int64_t gc_path_of(const long long* __restrict__ off, int64_t n, int64_t i) {
     int64_t lo = 0, hi = n;

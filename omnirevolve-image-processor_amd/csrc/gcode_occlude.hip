@@ -128,20 +128,9 @@ __global__ __launch_bounds__(256) void k_oc_rings(const long long* __restrict__ 
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= R) return;
     const int64_t r = gc_path_of(roff, m, i);
-    const double2 mm = sv_pts[sv_off[rsub[r]] + (i - roff[r])];
-    double xf, yf;
-    int2 o = make_int2(0, 0);
-    if (!gc_round_mm(g, mm.x, mm.y, xf, yf)) atomicOr(&cn->bad, OC_BAD_NOT_FINITE);
-    else {
-        if (clamp) {
-            const double xmax = (double)(g.W - 1), ymax = (double)(g.H - 1);
-            xf = xf < 0.0 ? 0.0 : (xf > xmax ? xmax : xf);
-            yf = yf < 0.0 ? 0.0 : (yf > ymax ? ymax : yf);
-        }
-        const double top = (double)GC_COORD_MAX;
-        if (xf < -top || xf > top || yf < -top || yf > top) atomicOr(&cn->bad, OC_BAD_RANGE);
-        else o = make_int2((int)xf, (int)yf);
-    }
+    int2 o;
+    const unsigned why = gc_ring_step(g, sv_pts[sv_off[rsub[r]] + (i - roff[r])], clamp, o);                  // gc_convert.h: shared with the hatch link
+    if (why) atomicOr(&cn->bad, why == GC_RING_NOT_FINITE ? OC_BAD_NOT_FINITE : OC_BAD_RANGE);
     rpts[i] = o;
 }
 __global__ __launch_bounds__(256) void k_oc_boxinit(int4* __restrict__ sbox, int64_t ns) {

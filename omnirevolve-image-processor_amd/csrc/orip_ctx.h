@@ -342,7 +342,7 @@ struct orip_ctx {
     // came from, which names them while !gc_merged (a field of the merge's line below).  This block is the one statement of their contract; the helpers that
     // keep it are declared in gc_convert.h and defined in gcode.hip, and no other code writes these fields.
     //   Readers (fail while !gc_ready, or when the n they are given is not gc_n): orip_gcode_steps_fetch, orip_gcode_steps_source_fetch (also fails while
-    //   gc_merged), and for NULL input orip_gcode_order, orip_gcode_order_pens, orip_gcode_improve, orip_gcode_merge, orip_gcode_simplify, orip_gcode_dedup, orip_gcode_occlude, orip_gcode_dash; orip_svg_occlude always.
+    //   gc_merged), and for NULL input orip_gcode_order, orip_gcode_order_pens, orip_gcode_improve, orip_gcode_merge, orip_gcode_simplify, orip_gcode_dedup, orip_gcode_occlude, orip_gcode_dash, orip_gcode_hatch_link; orip_svg_occlude and orip_svg_hatch_link always.
     //   orip_gcode_seam is a reader in both forms: NULL input reads the list, an explicit input goes to sm_in and does not become the list; it never writes these fields.
     //   Writers, and what each leaves:
     //     orip_gcode_to_steps       drops the list on entry (gc_drop), before it looks at its arguments: after ANY failure there is no list.  Success: its
@@ -368,6 +368,12 @@ struct orip_ctx {
     //                               out of range is a device-found error of the first.
     //       the dash                sizes its raw arrays by a read-back; when every stroke lies in a gap it launches nothing more and leaves the list of
     //                               no polylines; a dashed stroke of 2^62 units or more is a device-found error.
+    //     orip_gcode_hatch_link, orip_svg_hatch_link (--hatch-connect, gcode_link.hip; record hl, the cutting passes' frame with origin = the first member
+    //                               of every output stroke): every check of the arguments first (an argument error leaves the list as it was); n == 0
+    //                               leaves the empty list (explicit form) or the resident one; the intake's rule for an explicit input and gc_merged.
+    //                               Strokes are joined, so while !gc_merged the sources are gathered through the first member and swapped in with the
+    //                               list (gc_cut_publish).  A device-found error (a ring coordinate not finite or out of range, 2^30 pairs in reach or
+    //                               more, counts that do not add up) leaves no list.
     //   A failed HIP call inside a writer leaves what had been written up to it; gc_ready is false across an upload, so a list is never half there.
     DBuf gc_tmp, gc_off, gc_pts, gc_src, pk_tab, pk_out; int64_t gc_n = 0, gc_total = 0, pk_bytes = -1; bool gc_ready = false;
     // orip_gcode_order and orip_gcode_order_pens (gcode_order.hip: gc_grids), free between calls.  With n paths in G groups, m = n or 2n candidates (both ends
@@ -402,6 +408,11 @@ struct orip_ctx {
     // the segments a wave takes; ds_raw = the points and dashes before the repeated points and the collapsed dashes are taken out (the unit states both
     // layouts), free between calls; ds = the result record
     DBuf ds_tmp, ds_raw; GcCut ds;
+    // --hatch-connect (gcode_link.hip): hl_tmp = the classes, the rings and their edges, the shapes' tables, the per-stroke flags and scans, the counters;
+    // hl_ln = the lines' points, classes and strokes, the bucket keys of their STARTs unsorted and sorted, the pair counts and their scan, the bests, the
+    // links and the two chain arrays; hl_pair = the pairs in reach and their eligibility (the unit states the three layouts), free between calls; hl = the
+    // result record; hl_res = member_off int64[hl_paths + 1], member int32[hl_n] of the last call of hl_n strokes (-1: none) until the next one
+    DBuf hl_tmp, hl_ln, hl_pair, hl_res; GcCut hl; int64_t hl_n = -1, hl_paths = 0;
     // svg2stream (svg.hip): scratch of the flattening and of the box, the resident paths (off int64[sv_n + 1], pts double2[sv_total]; raw units after
     // orip_svg_flatten, page mm after orip_svg_fit) until the next flatten; orip_gcode_to_steps reads them when it is called without pointers
     DBuf sv_tmp, sv_tmp2, sv_off, sv_pts; int64_t sv_n = 0, sv_total = 0; bool sv_ready = false, sv_box_ok = false; double sv_box[4] = {0, 0, 0, 0};

@@ -652,6 +652,55 @@ class Device:
         self._ck(self.L.orip_svg_occlude(self.h, _p(lv) if n else None, n, _p(rs) if m else None, _p(rl) if m else None, m, C.byref(gm), _l.OCCLUDE_CLAMP if clamp else 0, _p(st)))
         return self._cut_result(st, _l.OCCLUDE_STATS, self.L.orip_gcode_occlude_fetch)
 
+    def _link_result(self, st, n):
+        """what the hatch link left: its stats, member_off / member through the fetch, the resident polylines"""
+        d = {k: int(v) for k, v in zip(_l.HATCH_LINK_STATS, st)}
+        moff = np.zeros(d["paths_out"] + 1, np.int64); member = np.zeros(max(n, 1), np.int32)
+        self._ck(self.L.orip_gcode_hatch_link_fetch(self.h, _p(moff), _p(member)))
+        off_s, pts_s = self.gcode_steps_fetch(d["paths_out"], d["points_out"])
+        return off_s, pts_s, moff, member[:n], d
+
+    def gcode_hatch_link(self, off, pts, cls, ring_off, ring_pts, ring_group, reach: int, n: int | None = None):
+        """--hatch-connect (include/orip.h: orip_gcode_hatch_link): of the step polylines (off int64 [n + 1], pts int32 [total, 2]; both None = the n resident
+        ones) the 2-point strokes with cls[k] = 2 g + f >= 0 are joined into zigzags by links of at most `reach` steps that lie inside shape g, and the result
+        becomes the resident polylines.  The shapes are the rings ring_off int64 [m + 1], ring_pts int32 [R, 2] (steps, -2^30 .. 2^30) with ring_group int32
+        [m], non-decreasing; the rings of one group are one shape.
+        -> (off int64, pts int32 [total', 2], member_off int64 [paths_out + 1], member int32 [n], {lib.HATCH_LINK_STATS})"""
+        po, pp, n, _keep = _step_paths(off, pts, n)
+        cl = np.ascontiguousarray(cls, np.int32).reshape(-1)
+        n = len(cl) if n is None else int(n)
+        if len(cl) != n:
+            raise ValueError(f"{len(cl)} classes given for {n} paths")
+        ro = np.ascontiguousarray(ring_off, np.int64).reshape(-1)
+        rp = np.ascontiguousarray(ring_pts, np.int32).reshape(-1, 2)
+        rg = np.ascontiguousarray(ring_group, np.int32).reshape(-1)
+        m = len(rg)
+        if len(ro) != m + 1 or (m and len(rp) < int(ro[-1])):
+            raise ValueError(f"{len(ro)} ring offsets and {len(rp)} ring points given for {m} rings")
+        st = np.zeros(8, np.int64)
+        self._ck(self.L.orip_gcode_hatch_link(self.h, po, pp, _p(cl) if n else None, n, _p(ro) if m else None, _p(rp) if m and len(rp) else None, _p(rg) if m else None, m,
+                                              int(reach), _p(st)))
+        return self._link_result(st, n)
+
+    def svg_hatch_link(self, cls, ring_sub, ring_group, map: dict, clamp: bool, reach: int, n: int | None = None):
+        """--hatch-connect on the resident step polylines (include/orip.h: orip_svg_hatch_link): ring r is the resident fitted path ring_sub[r], converted on
+        the device as the conversion converts (map: the conversion's; clamp: to the sheet, as gcode_to_steps, or not, as gcode_to_steps_clip).
+        -> (off, pts, member_off, member, stats) as gcode_hatch_link"""
+        cl = np.ascontiguousarray(cls, np.int32).reshape(-1)
+        n = len(cl) if n is None else int(n)
+        if len(cl) != n:
+            raise ValueError(f"{len(cl)} classes given for {n} paths")
+        rs = np.ascontiguousarray(ring_sub, np.int32).reshape(-1)
+        rg = np.ascontiguousarray(ring_group, np.int32).reshape(-1)
+        if len(rs) != len(rg):
+            raise ValueError(f"{len(rs)} rings and {len(rg)} ring groups")
+        m = len(rg)
+        gm = _l.GcodeMap(**{k: map[k] for k, _ in _l.GcodeMap._fields_})
+        st = np.zeros(8, np.int64)
+        self._ck(self.L.orip_svg_hatch_link(self.h, _p(cl) if n else None, n, _p(rs) if m else None, _p(rg) if m else None, m, C.byref(gm),
+                                            _l.HATCH_LINK_CLAMP if clamp else 0, int(reach), _p(st)))
+        return self._link_result(st, n)
+
     def gcode_dash(self, off, pts, pattern, phase, pat_off, pat_val, n: int | None = None):
         """--dashes / --dash-mm (include/orip.h: orip_gcode_dash): of the step polylines (off int64 [n + 1], pts int32 [total, 2]; both None = the n resident
         ones) every stroke with pattern[k] >= 0 is cut into the dashes of that pattern of the table (pat_off int32 [np + 1], pat_val int64, in 1/256 step),

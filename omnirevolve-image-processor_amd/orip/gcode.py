@@ -56,6 +56,12 @@ grid.  It runs after the pens have been worked out and before the occlusion and 
 under --clip the phase restarts at the sheet's edge, and the merge, which runs later, does not carry it on.  A dash keeps its stroke's pen and source; a
 dash that rounds onto one grid point is dropped.  Without the option no device call is added and every byte is what it was.
 
+--hatch-connect (svg2stream.py's; ours as well): every hatch line is a stroke of its own, so a hatched sheet lifts the pen once per line.  The pass joins
+consecutive hatch lines of one shape and one hatch family into zigzags, by straight links of at most --hatch-connect-mm that lie wholly inside the shape
+(orip_svg_hatch_link; include/orip.h states the rule, exact in integers on the step grid).  It runs after the pens and the dashes and before the occlusion,
+the dedup, the merge and the simplification: it sees the hatch lines whole, and a shape on top cuts a zigzag as it cuts any ink.  Pen, level, dash pattern
+and source follow a zigzag through its first line.  Without the option no device call is added and every byte is what it was.
+
 --loop-start (ours as well): a circle, a rectangle, a closed path and a ring --merge-paths has rebuilt are entered and left at the vertex their file happened
 to list first, and the orders and --improve-order see such a stroke as that one point.  With --loop-start every closed stroke (four points or more, the
 first equal to the last) starts and ends at the ring vertex that makes the pen-up steps of the whole plot least, all closed strokes chosen together and
@@ -383,6 +389,18 @@ class Dash:
         self.device_follows = False                 # resolve_steps: pass and sources are both this device's, whose sources follow the dashes through origin
 
 
+class HatchLink:
+    """--hatch-connect of the SVG door (orip.svg states it), which StrokeSteps does not carry: fn(off, pts, cls int32 [n], ring_sub, ring_group, map, clamp,
+    reach) -> (off, pts, member_off int64, member int32: the input strokes of every output stroke, stats) or None = the device (orip_svg_hatch_link);
+    path_cls = the class 2 g + f of every input path (-1: no hatch line), which a stroke takes through its source; the rings as fitted paths and the shape g
+    of each; clamp = the rings are clamped as the strokes were; reach = the longest link in steps (include/orip.h states the rule)"""
+    def __init__(self, fn, path_cls, ring_sub, ring_group, clamp: bool, reach: int):
+        self.fn = fn; self.path_cls = np.asarray(path_cls, np.int64).reshape(-1)
+        self.ring_sub = np.asarray(ring_sub, np.int32).reshape(-1); self.ring_group = np.asarray(ring_group, np.int32).reshape(-1)
+        self.clamp = bool(clamp); self.reach = int(reach)
+        self.device_follows = False                 # resolve_steps: pass and sources are both this device's, whose sources follow the zigzags through their first line
+
+
 class Seam:
     """--loop-start, which StrokeSteps does not carry: fn(off, pts, order int32 [n] or None, rev bool [n] or None) -> (seam int32 [n]: by sequence position,
     the stored ring vertex a closed stroke starts and ends at, 0 for an open one; stats) or None = the device (orip_gcode_seam)"""
@@ -391,7 +409,7 @@ class Seam:
 
 
 def resolve_steps(st: StrokeSteps, o, grouped: bool, device=None, convert: Optional[Callable] = None, force: bool = False, occlude: Optional[Occlude] = None,
-                  dash: Optional[Dash] = None, seam: Optional[Seam] = None):
+                  dash: Optional[Dash] = None, seam: Optional[Seam] = None, hatch_link: Optional[HatchLink] = None):
     """The steps the options need, those not given taken from a device -> (steps, device); codes and pack stay as given (orip.stream.compile_plan fills them).
     When none is missing, and the caller does not `force` a device for steps of its own, no device is made and orip.stages is not imported.  convert(device)
     -> the conversion of a front door whose paths are on the device already (orip.svg).  Dedup, merge and simplify work on the polylines the pass before them
@@ -399,18 +417,21 @@ def resolve_steps(st: StrokeSteps, o, grouped: bool, device=None, convert: Optio
     the sources as the occlusion does; it stands between the conversion and the occlusion.  `occlude`: its fn is filled in the same way; it needs the
     sources whether or not pens are in use, and the rings are fitted paths that only the device's own conversion leaves next to the strokes, so behind a
     given conversion the strokes are uploaded first (an occlusion without rings makes them the resident list) and the pass then runs as it does otherwise.
-    `seam`: its fn is filled in the same way; it reads the strokes the last pass in front of the order left resident, or is sent them."""
+    `seam`: its fn is filled in the same way; it reads the strokes the last pass in front of the order left resident, or is sent them.  `hatch_link`: its
+    fn is filled in the same way, and it stands between the dash pass and the occlusion; it needs the sources, and its rings are fitted paths as the
+    occlusion's are, so behind a given pass the strokes are uploaded first in the same way (a link pass without rings makes them the resident list)."""
     need = ["convert", "order"] + ["order_pens", "source"] * bool(grouped) + ["merge"] * bool(o.merge_paths) + ["improve"] * bool(o.improve_order) + \
-        ["simplify"] * (o.simplify_mm is not None) + ["dedup"] * bool(o.dedup) + ["source"] * (occlude is not None or dash is not None)
+        ["simplify"] * (o.simplify_mm is not None) + ["dedup"] * bool(o.dedup) + ["source"] * (occlude is not None or dash is not None or hatch_link is not None)
     if not force and all(getattr(st, k) is not None for k in need) and (occlude is None or occlude.fn is not None) and (dash is None or dash.fn is not None) and \
-            (seam is None or seam.fn is not None):
+            (seam is None or seam.fn is not None) and (hatch_link is None or hatch_link.fn is not None):
         return st, device
     if device is None:
         from .stages import device as _default_device
         device = _default_device()
     after_convert = st.convert is None                                     # resident behind this device's own conversion,
     after_dash = dash.fn is None if dash is not None else after_convert    # behind its dash pass or, without one, behind the conversion,
-    after_occlude = occlude.fn is None if occlude is not None else after_dash         # behind its occlusion or, without one, behind what stands before it,
+    after_link = hatch_link.fn is None if hatch_link is not None else after_dash      # behind its hatch link or, without one, behind what stands before it,
+    after_occlude = occlude.fn is None if occlude is not None else after_link         # behind its occlusion or, without one, behind what stands before it,
     after_dedup = st.dedup is None if o.dedup else after_occlude           # behind its dedup or, without one, behind what stands before the dedup,
     after_merge = st.merge is None if o.merge_paths else after_dedup       # behind its merge or, without one, behind what stands before the merge,
     after_simplify = st.simplify is None if o.simplify_mm is not None else after_merge    # and behind its simplification or, without one, behind what stands before it
@@ -423,10 +444,18 @@ def resolve_steps(st: StrokeSteps, o, grouped: bool, device=None, convert: Optio
         improve=lambda ends, group, n_groups, order, rev, reverse, max_rounds: device.gcode_improve(ends, group, n_groups, order, rev, reverse, max_rounds=max_rounds))
     if occlude is not None and occlude.fn is None:
         def own_occlude(off, pts, level, ring_sub, ring_level, m, clamp):
-            if not after_dash:
+            if not after_link:
                 device.gcode_occlude(off, pts, level, np.zeros(1, np.int64), np.zeros((0, 2), np.int32), np.zeros(0, np.int32))
             return device.svg_occlude(level, ring_sub, ring_level, m, clamp, n=len(off) - 1)
         occlude.fn = own_occlude
+    if hatch_link is not None and hatch_link.fn is None:
+        hatch_link.device_follows = st.source is None and after_dash
+
+        def own_link(off, pts, cls, ring_sub, ring_group, m, clamp, reach):
+            if not after_dash:
+                device.gcode_hatch_link(off, pts, cls, np.zeros(1, np.int64), np.zeros((0, 2), np.int32), np.zeros(0, np.int32), reach)
+            return device.svg_hatch_link(cls, ring_sub, ring_group, m, clamp, reach, n=len(off) - 1)
+        hatch_link.fn = own_link
     if seam is not None and seam.fn is None:
         seam.fn = (lambda off, pts, order, rev: device.gcode_seam(None, None, order, rev, n=len(off) - 1)) if after_simplify else device.gcode_seam
     if dash is not None and dash.fn is None:
@@ -559,6 +588,43 @@ def _dash(st: StrokeSteps, dh: Dash, off_in, pts_in, pen, group, info: dict):
     return off, pts, pen, group, src[origin]
 
 
+def _hatch_link(st: StrokeSteps, hl: HatchLink, off_in, pts_in, pen, group, m: dict, info: dict):
+    """the strokes, the hatch lines joined into zigzags; a stroke takes its class through its source, and a zigzag keeps the pen and, the fifth value
+    returned, the source of its first line; info["hatch_link"]"""
+    n_in = len(off_in) - 1
+    src = _sources(st, n_in, len(hl.path_cls))
+    cls = hl.path_cls[src]
+    off, pts, member_off, member, lst = hl.fn(off_in, pts_in, cls.astype(np.int32), hl.ring_sub, hl.ring_group, m, hl.clamp, hl.reach)
+    off = np.asarray(off, np.int64).reshape(-1); pts = np.asarray(pts, np.int32).reshape(-1, 2)
+    member_off = np.asarray(member_off, np.int64).reshape(-1); member = np.asarray(member, np.int64).reshape(-1)
+    d = {k: int(lst[k]) for k in HATCH_LINK_STATS}
+    n = len(off) - 1
+    if not (1 <= n <= n_in) or len(member_off) != n + 1 or len(member) != n_in or member_off[0] != 0 or int(member_off[-1]) != n_in or (np.diff(member_off) < 1).any() or \
+            not np.array_equal(np.sort(member), np.arange(n_in)):
+        raise RuntimeError("the hatch link did not return every stroke once")
+    first = member[member_off[:-1]]
+    lens = np.diff(member_off)
+    if (np.diff(first) <= 0).any() or (cls[member] != np.repeat(cls[first], lens)).any() or (cls[first][lens > 1] < 0).any() or \
+            (group is not None and (group[member] != np.repeat(group[first], lens)).any()):
+        raise RuntimeError("the hatch link joined strokes of different shapes or pens, or left them out of order")
+    if off[0] != 0 or int(off[-1]) != len(pts) or (np.diff(off) < 2).any() or d["paths_out"] != n or n != n_in - d["links"] or d["points_out"] != len(pts) or \
+            len(pts) != len(pts_in) - d["coincident"] or d["lines"] != int(((cls >= 0) & (np.diff(off_in) == 2)).sum()) or not (d["links"] <= d["eligible"] <= d["in_reach"]) or \
+            draw_steps(off, pts) != draw_steps(off_in, pts_in) + d["link_steps"]:
+        raise RuntimeError("the hatch link's counts do not add up")
+    if group is not None:
+        pen, group = pen[first], group[first]
+    info["paths"] = n
+    info["hatch_link"] = dict(d, reach=hl.reach)
+    return off, pts, pen, group, src[first]
+
+
+def _sources_behind_link(src, n: int):
+    """what the source step gives behind a hatch link that did not run on the device whose sources are asked: the sources _hatch_link gathered through the first lines"""
+    if n != len(src):
+        raise RuntimeError(f"{n} sources asked for, the hatch link left {len(src)} strokes")
+    return src
+
+
 def _sources_behind_dash(src, n: int):
     """what the source step gives behind a dash pass that did not run on the device whose sources are asked: the sources _dash gathered through origin"""
     if n != len(src):
@@ -651,9 +717,9 @@ def _plan(o: GcodeOptions, sc: ST.StreamConfig, off, pts, path_pen) -> ST.Plan:
 
 def stroke_stream(text_or_paths, opts: Optional[GcodeOptions], device, steps: StrokeSteps, timings: Optional[dict] = None, pens: Optional[np.ndarray] = None,
                   occlude: Optional[Occlude] = None, dash: Optional[Dash] = None, dash_fn: Optional[Callable] = None, seam_fn: Optional[Callable] = None,
-                  seam: Optional["Seam"] = None) -> Tuple[bytes, dict]:
+                  seam: Optional["Seam"] = None, hatch_link: Optional[HatchLink] = None) -> Tuple[bytes, dict]:
     """build_stream_from_gcode with the device steps as one record: parse, convert, pens of the strokes, [dash: --dash-mm gives every path the one pattern,
-    with dash_fn; the SVG door brings a record of its own], [occlude, the SVG door's], dedup, merge, simplify, order, [seam: --loop-start, with seam_fn, or the record a door has
+    with dash_fn; the SVG door brings a record of its own], [hatch_link, the SVG door's], [occlude, the SVG door's], dedup, merge, simplify, order, [seam: --loop-start, with seam_fn, or the record a door has
     resolved already], plan, compile"""
     import time
     o = apply_speed_scale(GcodeOptions(**{f.name: getattr(opts, f.name) for f in fields(GcodeOptions)}) if opts is not None else GcodeOptions())
@@ -692,7 +758,7 @@ def stroke_stream(text_or_paths, opts: Optional[GcodeOptions], device, steps: St
     if own_dash is not None and dash is None:                             # --dash-mm: every path gets the pattern
         dash = Dash(dash_fn, np.zeros(len(off_mm) - 1, np.int32), np.full(len(off_mm) - 1, own_dash[1], np.int64), [0, len(own_dash[0])], own_dash[0])
     sm = (seam if seam is not None else Seam(seam_fn)) if o.loop_start else None
-    st, device = resolve_steps(steps, o, grouped, device, occlude=occlude, dash=dash, seam=sm)
+    st, device = resolve_steps(steps, o, grouped, device, occlude=occlude, dash=dash, seam=sm, hatch_link=hatch_link)
     m = dict(scale_x=o.scale_x, scale_y=o.scale_y, offset_x_mm=o.offset_x_mm, offset_y_mm=o.offset_y_mm, steps_per_mm=o.steps_per_mm, W=W, H=H, invert_y=int(bool(o.invert_y)))
     off, pts = _convert(st, off_mm, pts_mm, m, rect, info)
     lap("to_steps")
@@ -709,6 +775,12 @@ def stroke_stream(text_or_paths, opts: Optional[GcodeOptions], device, steps: St
         lap("dash")
         if len(off) <= 1:                                                 # every stroke lies in a gap
             return EMPTY_STREAM, dict(info, bytes=len(EMPTY_STREAM))
+    if hatch_link is not None:                                            # before the occlusion: it sees the hatch lines whole, and a shape on top cuts a zigzag
+        lap("order")                                                      # the sources and the pens belong to the order's lap
+        off, pts, pen, group, link_src = _hatch_link(st, hatch_link, off, pts, pen, group, m, info)
+        if not hatch_link.device_follows:                                 # a given pass or given sources: nobody gathered them through the first lines but _hatch_link
+            st = st._replace(source=lambda k: _sources_behind_link(link_src, k))
+        lap("hatch_link")
     if occlude is not None:
         lap("order")                                                      # the sources and the pens belong to the order's lap
         off, pts, pen, group = _occlude(st, occlude, off, pts, pen, group, m, info)
@@ -720,12 +792,12 @@ def stroke_stream(text_or_paths, opts: Optional[GcodeOptions], device, steps: St
         off, pts, pen, group = _dedup(st, off, pts, pen, group, n_groups, info)
         lap("dedup")
     if o.merge_paths:
-        if not (o.dedup or occlude is not None or dash is not None):
+        if not (o.dedup or occlude is not None or dash is not None or hatch_link is not None):
             lap("order")                                                  # the sources and the pens belong to the order's lap, as before
         off, pts, pen, group = _merge(st, o, off, pts, pen, group, n_groups, info)
         lap("merge")
     if tol4 is not None:
-        if not (o.merge_paths or o.dedup or occlude is not None or dash is not None):
+        if not (o.merge_paths or o.dedup or occlude is not None or dash is not None or hatch_link is not None):
             lap("order")
         off, pts = _simplify(st, off, pts, tol4, info)
         lap("simplify")
@@ -751,6 +823,8 @@ CLIP_STATS = ("segments", "inside", "cut", "outside", "paths_out", "points_out")
 DEDUP_STATS = ("segments", "whole", "cut", "covered", "pieces", "paths_out", "points_out", "draw_steps_in", "draw_steps_out")      # include/orip.h: orip_gcode_dedup
 OCCLUDE_STATS = ("segments", "whole", "cut", "hidden", "pieces", "collapsed", "paths_out", "points_out", "draw_steps_in", "draw_steps_out")      # include/orip.h: orip_gcode_occlude
 DASH_STATS = ("paths_in", "dashed", "dashes", "collapsed", "paths_out", "points_out", "length_in", "length_on")      # include/orip.h: orip_gcode_dash
+HATCH_LINK_STATS = ("lines", "in_reach", "eligible", "links", "coincident", "paths_out", "points_out", "link_steps")      # include/orip.h: orip_gcode_hatch_link
+HATCH_LINK_REACH_MAX = 1 << 20                # include/orip.h: ORIP_HATCH_LINK_REACH_MAX
 SEAM_STATS = ("closed", "moved", "travel_before", "travel_after")      # include/orip.h: orip_gcode_seam
 DASH_UNIT, DASH_MAX_ENTRIES = 256, 64         # include/orip.h: ORIP_DASH_UNIT (dash lengths are in 1/256 step), ORIP_DASH_MAX_ENTRIES
 SIMPLIFY_TOL4_MAX = (1 << 17) - 1             # include/orip.h: ORIP_SIMPLIFY_TOL4_MAX
@@ -927,6 +1001,9 @@ def report_lines(tag: str, info: dict, unmatched: bool = False):
         d = info["dash"]
         yield (f"[{tag}] dash: {d['dashed']} strokes dashed, {d['length_on'] / DASH_UNIT:.0f} of {d['length_in'] / DASH_UNIT:.0f} steps drawn in {d['dashes']} dashes, "
                f"{d['collapsed']} under a step dropped" + (f", {d['ignored']} dash arrays ignored" if d.get("ignored") else "") + f" -> {d['paths_out']} strokes")
+    if "hatch_link" in info:
+        yield (f"[{tag}] " + "hatch connect: {lines} hatch lines, {links} links of at most {reach} steps ({in_reach} pairs in reach, {eligible} inside their shape) -> "
+                              "{paths_out} strokes, {link_steps} pen-down steps added".format(**info["hatch_link"]))
     if "occlude" in info:
         yield (f"[{tag}] " + "occlude: {segments} segments: {whole} whole, {cut} cut, {hidden} hidden -> {paths_out} strokes, "
                               "pen-down steps {draw_steps_in} -> {draw_steps_out}".format(**info["occlude"]))

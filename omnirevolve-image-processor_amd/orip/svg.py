@@ -67,6 +67,17 @@ polylines, on the device (orip_gcode_dash), after the pens have been worked out 
 screen, and the phase counts from the start of every stroke the conversion leaves.  Hatch lines are never dashed.  A drawing that states no dash array gets
 no device call.  Declined: dots for zero-length dashes, stroke-linecap, pathLength, vector-effect.  The G-code file is not changed.
 
+--hatch-connect [--hatch-connect-mm M] (off unless given; ours, svg2stream.py only; include/orip.h states the rule): a hatch is drawn as zigzags.  Every
+hatch line is a stroke of its own, so a hatched sheet lifts the pen once per line; with the option consecutive lines of one fill group and one hatch family
+are joined by straight links of at most M mm (default: twice --hatch-spacing-mm; reach = int(round(M steps_per_mm)) steps, 1 .. 2^20) that lie wholly inside
+the shape, so a link never crosses the outline, a hole or a concave corner.  A line's CLASS is 2 g + f: g its fill group (orip_svg_hatch_groups_fetch), f its
+family, read off its direction in mm: 0 iff |d . u| >= |d . n|, u = (1, 0) for the hatch along X / Y and the tool's u under --hatch-angle-deg.  The rings
+are the subpaths --hatch-fill marks, numbered by their fill group.  The pass runs on the step polylines, on the device (orip_svg_hatch_link: the rings are
+the resident fitted paths, converted there as the strokes were, clamped unless --clip cuts), after the pens and the dashes and before the occlusion, so a
+shape on top cuts a zigzag as it does on a screen.  Pens, levels and sources follow a zigzag through its first line.  With --hatch-inset-mm 0 the ends lie on
+the outline and nothing links; with --no-serpentine a link is a long diagonal, mostly out of reach: the report line says how many lines linked.  The G-code
+file is not changed; the preview is rendered from the stream and shows the result.
+
 The device steps are injectable, as in orip/gcode.py, so that this host logic can be tested without a GPU; the product has no CPU path."""
 from __future__ import annotations
 
@@ -641,6 +652,8 @@ class SvgOptions:
     no_serpentine: bool = False
     hatch_fill: str = "stated"
     hatch_angle_deg: Optional[float] = None             # None: the reference's hatch along X / Y; else the exact hatch along that angle (orip_svg_hatch_angle)
+    hatch_connect: bool = False                         # hatch lines are joined into zigzags by links that stay inside the shape (svg2stream.py only)
+    hatch_connect_mm: Optional[float] = None            # the longest link; None: twice hatch_spacing_mm; only with hatch_connect
     pen_colors: Optional[str] = None                    # None: one pen, --color-index
     pen_order: Optional[str] = None
     allow_reverse: bool = False
@@ -706,6 +719,25 @@ def hatch_params(o: SvgOptions) -> Optional[dict]:
     if u is not None:
         prm["u"] = u
     return prm
+
+
+def hatch_connect_reach(o: SvgOptions) -> Optional[int]:
+    """None without --hatch-connect, else the longest link in steps, int(round(M steps_per_mm)) for M = --hatch-connect-mm (default: twice
+    --hatch-spacing-mm): 1 .. 2^20.  Both options belong to a hatch, and the length to --hatch-connect."""
+    if not o.hatch_connect:
+        if o.hatch_connect_mm is not None:
+            raise ValueError("--hatch-connect-mm needs --hatch-connect")
+        return None
+    if o.hatch_spacing_mm is None:
+        raise ValueError("--hatch-connect needs --hatch-spacing-mm: there is no hatch to connect")
+    mm = 2.0 * float(o.hatch_spacing_mm) if o.hatch_connect_mm is None else float(o.hatch_connect_mm)
+    if not (mm > 0.0 and math.isfinite(mm)):
+        raise ValueError("--hatch-connect-mm must be a positive number" if o.hatch_connect_mm is not None else "--hatch-connect needs a positive --hatch-spacing-mm")
+    r = mm * float(o.steps_per_mm)
+    reach = int(round(r)) if math.isfinite(r) and r < float(1 << 31) else 1 << 31
+    if not (1 <= reach <= GC.HATCH_LINK_REACH_MAX):
+        raise ValueError(f"--hatch-connect-mm {mm:g} is {reach} steps at {float(o.steps_per_mm):g} steps per mm: 1 .. 2^20")
+    return reach
 
 
 def tolerance_mm(o: SvgOptions) -> float:
@@ -891,6 +923,37 @@ def path_levels(table: SegmentTable, paths, info: dict, hatch_groups_fn: Optiona
     return level
 
 
+def hatch_link_rings(table: SegmentTable):
+    """--hatch-connect: the outlines of the hatched shapes, (ring_sub, ring_group) -- the subpaths --hatch-fill marks, as occlusion_rings collects them,
+    each with its fill group, the groups ascending (the order inside a group is kept)"""
+    if table.fill_group is None:
+        return np.zeros(0, np.int32), np.zeros(0, np.int32)
+    fg = np.asarray(table.fill_group, np.int64).reshape(-1)
+    if len(fg) != table.n_sub:
+        raise ValueError(f"fill_group has {len(fg)} entries for {table.n_sub} subpaths")
+    sub = np.nonzero(fg >= 0)[0]
+    sub = sub[np.argsort(fg[sub], kind="stable")]
+    return sub.astype(np.int32), fg[sub].astype(np.int32)
+
+
+def hatch_classes(table: SegmentTable, paths, info: dict, hatch_groups_fn: Optional[Callable], off_mm, pts_mm, u=None) -> np.ndarray:
+    """--hatch-connect: the class of every fitted path: -1 for a subpath, 2 g + f for a hatch line of fill group g whose direction d in mm has
+    f = 0 iff |d . u| >= |d . n|, n = (-u_y, u_x); u = (1, 0) unless the hatch runs at an angle"""
+    cls = np.full(table.n_sub, -1, np.int64)
+    seg = int(info["hatch"]["segments"]) if "hatch" in info else 0
+    if seg:
+        groups = np.asarray(hatch_groups_fn(paths, seg), np.int64).reshape(-1)
+        off_mm = np.asarray(off_mm, np.int64).reshape(-1); pts_mm = np.asarray(pts_mm, np.float64).reshape(-1, 2)
+        if len(groups) != seg or (groups < 0).any() or len(off_mm) != table.n_sub + seg + 1 or (np.diff(off_mm[table.n_sub:]) != 2).any() or int(off_mm[-1]) != len(pts_mm):
+            raise RuntimeError(f"{len(groups)} fill groups for {seg} hatch lines of two points each")
+        a = off_mm[table.n_sub:-1]
+        d = pts_mm[a + 1] - pts_mm[a]
+        ux, uy = (1.0, 0.0) if u is None else (float(u[0]), float(u[1]))
+        across = np.abs(d[:, 0] * ux + d[:, 1] * uy) < np.abs(d[:, 1] * ux - d[:, 0] * uy)
+        cls = np.concatenate([cls, 2 * groups + across])
+    return cls
+
+
 def resolved_pens(pens: np.ndarray, o: SvgOptions) -> np.ndarray:
     """the pens as the G-code names them: --color-index where none was matched"""
     if not (0 <= int(o.color_index) < GC.MAX_PENS):
@@ -928,7 +991,8 @@ def build_stream_from_svg(text: Union[str, bytes, SegmentTable], opts: Optional[
                           want_paths: bool = False, hatch_groups_fn: Optional[Callable] = None, source_fn: Optional[Callable] = None,
                           order_pens_fn: Optional[Callable] = None, merge_fn: Optional[Callable] = None, improve_fn: Optional[Callable] = None,
                           clip_fn: Optional[Callable] = None, simplify_fn: Optional[Callable] = None, dedup_fn: Optional[Callable] = None,
-                          occlude_fn: Optional[Callable] = None, dash_fn: Optional[Callable] = None, seam_fn: Optional[Callable] = None) -> Tuple[bytes, dict]:
+                          occlude_fn: Optional[Callable] = None, dash_fn: Optional[Callable] = None, seam_fn: Optional[Callable] = None,
+                          hatch_link_fn: Optional[Callable] = None) -> Tuple[bytes, dict]:
     """The stream of an SVG text (or of a parsed SegmentTable).  Device steps, each None = the GPU (there is no CPU path in the product):
       flatten_fn(table, tol_raw) -> paths          orip_svg_flatten      (`paths` is whatever the other steps take: on the GPU a count, the points stay there)
       bbox_fn(paths) -> (min x, min y, max x, max y)   orip_svg_bbox
@@ -956,6 +1020,9 @@ def build_stream_from_svg(text: Union[str, bytes, SegmentTable], opts: Optional[
     and, only with --dashes on a drawing that states a dash array (after the pens have been worked out, before the occlusion; it needs source_fn):
       dash_fn                                      as in orip.gcode.build_stream_from_gcode; the patterns are dash_patterns()'s
     info["dash"] = the eight counts of include/orip.h and "ignored", the dash arrays that left their stroke solid (where no stroke is dashed, "ignored" alone, if any).
+    and, only with --hatch-connect (after the pens and the dashes, before the occlusion; it needs source_fn, hatch_groups_fn and the points of fetch_fn):
+      hatch_link_fn(paths, off, pts, cls int32 [n], ring_sub, ring_group, map, clamp, reach) -> (off, pts, member_off, member, stats)   orip_svg_hatch_link
+    the rings are the fitted paths ring_sub with their fill groups, clamp = not --clip; info["hatch_link"] = the eight counts of include/orip.h and "reach".
     and, only with --loop-start:
       seam_fn                                      as in orip.gcode.build_stream_from_gcode (a circle, a <rect> and a closed <path> are closed strokes; hatch lines are open)
     With --pen-colors, info["path_pens"] is the pen of every fitted path (hatch lines included, --color-index where no stroke is stated).
@@ -965,6 +1032,7 @@ def build_stream_from_svg(text: Union[str, bytes, SegmentTable], opts: Optional[
     tm = timings if timings is not None else {}
     t0 = time.perf_counter()
     hp = hatch_params(o)
+    reach = hatch_connect_reach(o)
     if o.pen_colors is not None:
         parse_pen_colors(o.pen_colors)                      # a bad list ends the run before anything is parsed
     go = gcode_options(o)
@@ -983,7 +1051,7 @@ def build_stream_from_svg(text: Union[str, bytes, SegmentTable], opts: Optional[
     given = clip_fn if o.clip else steps_fn                 # the stroke steps take (off, pts_mm, ...); here the conversion takes the fitted paths where they are
     steps = GC.StrokeSteps(None if given is None else (lambda _off, _pts, m, *rect: given(paths, m, *rect)), source_fn, merge_fn, simplify_fn, order_fn, order_pens_fn,
                            improve_fn, codes_fn, pack_fn, dedup_fn)
-    own = any(f is None for f in (flatten_fn, bbox_fn, fit_fn, fetch_fn)) or (hp and hatch_fn is None) or ((pens_on or o.occlude) and hp and hatch_groups_fn is None)
+    own = any(f is None for f in (flatten_fn, bbox_fn, fit_fn, fetch_fn)) or (hp and hatch_fn is None) or ((pens_on or o.occlude or reach is not None) and hp and hatch_groups_fn is None)
     occ = None
     if o.occlude:                                           # the rings and their levels are known now; the strokes' levels once the hatch lines are there
         ring_sub, ring_level = occlusion_rings(table)
@@ -1004,7 +1072,7 @@ def build_stream_from_svg(text: Union[str, bytes, SegmentTable], opts: Optional[
     if pens is not None:
         info["path_pens"] = resolved_pens(pens, o)
     t0 = time.perf_counter()
-    off_mm, pts_mm = fetch_fn(paths, want_paths)
+    off_mm, pts_mm = fetch_fn(paths, want_paths or reach is not None)       # the hatch link reads a line's family off its direction
     off_mm = np.asarray(off_mm, np.int64)
     if want_paths:
         info["fitted_paths"] = (off_mm, np.asarray(pts_mm, np.float64).reshape(-1, 2))
@@ -1016,10 +1084,14 @@ def build_stream_from_svg(text: Union[str, bytes, SegmentTable], opts: Optional[
         pattern, phase, pat_off, pat_val, ignored = dash_patterns(table, info["scale"], o.steps_per_mm, len(off_mm) - 1)
         if (pattern >= 0).any():                            # no usable dash array: no pass, no device call
             dsh = GC.Dash(dash_fn, pattern, phase, pat_off, pat_val)
+    lnk = None
+    if reach is not None:
+        lnk = GC.HatchLink(None if hatch_link_fn is None else (lambda off, pts, cls, rs, rg, m, clamp, r: hatch_link_fn(paths, off, pts, cls, rs, rg, m, clamp, r)),
+                           hatch_classes(table, paths, info, hatch_groups_fn, off_mm, pts_mm, hp.get("u")), *hatch_link_rings(table), not o.clip, reach)
     sm = GC.Seam(seam_fn) if o.loop_start else None
-    steps, device = GC.resolve_steps(steps, go, pens_on or o.allow_reverse, device, force=bool(own), occlude=occ, dash=dsh, seam=sm,
+    steps, device = GC.resolve_steps(steps, go, pens_on or o.allow_reverse, device, force=bool(own), occlude=occ, dash=dsh, seam=sm, hatch_link=lnk,
                                      convert=lambda dev: lambda _off, _pts, m, *rect: (_Resident(dev).clip if rect else _Resident(dev).steps)(paths, m, *rect))
-    data, ginfo = GC.stroke_stream((off_mm, np.zeros((int(off_mm[-1]), 2))), go, device, steps, tm, pens, occ, dsh, seam=sm)
+    data, ginfo = GC.stroke_stream((off_mm, np.zeros((int(off_mm[-1]), 2))), go, device, steps, tm, pens, occ, dsh, seam=sm, hatch_link=lnk)
     if "dash" in ginfo or ignored:                          # an ignored dash array is reported whether or not a pass ran: the stroke is solid, and the line says so
         ginfo["dash"] = dict(ginfo.get("dash", {}), ignored=ignored)
     return data, dict(ginfo, **info)
@@ -1080,6 +1152,9 @@ def build_stream_argparser() -> argparse.ArgumentParser:
                                                               "travel of the whole plot least, all of them chosen together, after the order; the G-code file is not changed")
     ap.add_argument("--dashes", action="store_true", help="draw a stroke that states a stroke-dasharray as its dashes, measured on the step grid from the start of "
                                                           "every stroke (hatch lines stay solid); the G-code file is not changed")
+    ap.add_argument("--hatch-connect", action="store_true", help="draw a hatch as zigzags: join consecutive hatch lines of one shape by straight links that lie wholly "
+                                                                 "inside it, so the pen stays down; needs --hatch-spacing-mm; the G-code file is not changed")
+    ap.add_argument("--hatch-connect-mm", type=float, default=None, help="the longest link (default: twice --hatch-spacing-mm); needs --hatch-connect")
     ap.add_argument("--no-preview", action="store_true", help="do not render <svg stem>_stream_preview.png")
     ap.add_argument("--preview-render-width", type=int, default=d.preview_render_width)
     ap.add_argument("--preview-render-height", type=int, default=d.preview_render_height)

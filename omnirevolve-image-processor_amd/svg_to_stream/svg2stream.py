@@ -4,7 +4,7 @@ default output names (<stem>.gcode, <stem>_stream.bin), in one process instead o
 stream bytes (orip.svg, orip.gcode, liborip.so); the G-code file is written from the fitted paths on the way.  Unless --no-preview is given the stream is
 decoded and drawn on the GPU into <stem>_stream_preview.png (orip.stream_preview: what the reference shows in a window).  There is no CPU path.
 
-    python svg2stream.py drawing.svg [-o stream.bin] [--gcode-output drawing.gcode] [--steps-per-mm 40] [--scale S] [--no-reorder] [--no-preview] [--hatch-spacing-mm S [--hatch-angle-deg A] ...] ...
+    python svg2stream.py drawing.svg [-o stream.bin] [--gcode-output drawing.gcode] [--steps-per-mm 40] [--scale S] [--no-reorder] [--no-preview] [--hatch-spacing-mm S [--hatch-angle-deg A] [--hatch-connect [--hatch-connect-mm M]] ...] ...
                           [--pen-colors rgbk|LIST [--pen-order 3,0,...]] [--allow-reverse]      (ours: a pen per stroke colour, drawn pen after pen)
 """
 import os

@@ -42,9 +42,9 @@ typedef struct {
     double tap_diam, tap_max_dim, min_keep, tap_max_per;
     int32_t tap_max_v;
     double sample_step, tail_len_px, col_rad, grid_stride, max_jump;
-    int32_t post_on, post_brush;
-    double post_step, post_eps;
-    int32_t post_minlen;
+    int32_t post_on, post_brush;    /* skeleton merge (08:376-469) on / off; its brush: at most 129 (stamp radius max(1, brush) / 2 <= the 64-px pad of the raster), refused above; below 1 the radius is 0 */
+    double post_step, post_eps;     /* resample step: >= 1, +inf included (a path no longer than the step passes through), refused below 1 and NaN; RDP tolerance: any value */
+    int32_t post_minlen;            /* shortest path kept, in pixels: any value, values below 2 count as 2 */
     int32_t W, H;          /* canvas, 08:103-113 */
     int32_t brush_forbid;
 } orip_params08;

@@ -1,7 +1,8 @@
 // csrc/vector08b.hip -- stage 08-B (08_dedup_layer_basic.py _post_skeleton_merge, 08:376-469) on gfx950.
 //
-// Stage B runs all clusters at once on one padded canvas: clusters are >= 76 px apart
-// in one axis, so per-ROI rasterise / thin / label equals whole-canvas rasterise / thin / label (DESIGN.md "stage 08-B").
+// Stage B runs all clusters at once on one padded canvas: clusters are more than 4 post_brush + 12 px apart in one axis (76 at the default brush) and a
+// band reaches post_brush / 2 <= PAD8 beyond its lines, so per-ROI rasterise / thin / label equals whole-canvas rasterise / thin / label (DESIGN.md
+// "stage 08-B"; dedup08_b refuses a brush whose band the pad would clip).
 // Layout: the kernels (groups, raster, Zhang-Suen thinning, components, paths), then the host side: one function per phase (b_groups, b_raster_thin,
 // b_components, b_paths) and dedup08_b, which calls them in order.  Scans and sorts go through vscan_excl / vsort_pairs (vec_common.h); the bit-plane
 // kernels (pack, thinning word, CCL, compaction, heads, bits -> bytes) are the shared blocks of bitplane.h, with the linear pixel id y * Wp + x.
@@ -251,7 +252,7 @@ template <class WK> __device__ unsigned bfs_wave(WK& w, unsigned src, unsigned g
 
 template <bool LDSV>
 __device__ void comp_path_wave(CompWork<LDSV>& w, unsigned oi, unsigned b, unsigned S, unsigned a0c, unsigned a1c, const unsigned* __restrict__ lin, int Wp,
-                               int min_len, double step, float eps, unsigned pcap, int2* __restrict__ outpts, unsigned* __restrict__ outcnt, int lane) {
+                               int min_len, double step, float eps, unsigned pcap, unsigned omul, int2* __restrict__ outpts, unsigned* __restrict__ outcnt, int lane) {
     typedef CompWork<LDSV> WK;
     const unsigned NONE = WK::NONE;
     const unsigned e = b + S;
@@ -295,11 +296,11 @@ __device__ void comp_path_wave(CompWork<LDSV>& w, unsigned oi, unsigned b, unsig
     int m;
     if ((double)total <= step) {
         m = plen;
-        if ((unsigned)m > pcap) return;      // cannot happen: pcap >= step + 2
+        if ((unsigned)m > pcap) return;      // cannot happen: plen - 1 <= total <= step, and pcap >= min(step, cap) + 2 (LDS) or S (global)
         for (int k = lane; k < plen; k += 64) w.P[k] = make_float2(PX(k), PY(k));
     } else {
         m = (int)ceil((double)total / step);
-        if ((unsigned)m > pcap) return;      // cannot happen: pcap >= sqrt(2) S / step + 2
+        if ((unsigned)m > pcap) return;      // cannot happen: total <= sqrt(2) (plen - 1), and pcap >= sqrt(2) cap / step + 2 (LDS) or omul S (global), b_paths
         const float t0 = 0.0f, t1 = (float)(0.0 + step), delta = t1 - t0;
         for (int i = lane; i < m; i += 64) {
             float tf = i == 0 ? t0 : (i == 1 ? t1 : t0 + (float)i * delta);
@@ -351,7 +352,7 @@ __device__ void comp_path_wave(CompWork<LDSV>& w, unsigned oi, unsigned b, unsig
         }
         __syncthreads();
     }
-    int2* o = outpts + b; unsigned cnt = 0;
+    int2* o = outpts + (size_t)b * omul; unsigned cnt = 0;      // the component's region: omul S points >= m >= the kept ones
     const unsigned long long lt = (1ull << lane) - 1ull;
     for (int i0 = 0; i0 < m; i0 += 64) {
         int i = i0 + lane; bool kp = i < m && w.keep[i];
@@ -364,7 +365,7 @@ __device__ void comp_path_wave(CompWork<LDSV>& w, unsigned oi, unsigned b, unsig
 
 struct CompArgs {
     const unsigned* corder; const unsigned* cs; const unsigned* lin; const unsigned* gid; const GroupInfo* g; const unsigned* cid; const unsigned* nbr;
-    int Wp; int min_len; double step; float eps; int2* outpts; unsigned* outcnt;
+    int Wp; int min_len; double step; float eps; unsigned omul; int2* outpts; unsigned* outcnt;      // omul: resample / output points per component pixel (1 or 2)
 };
 __device__ __forceinline__ void comp_anchors(const CompArgs& A, unsigned b, unsigned& a0c, unsigned& a1c) {
     const GroupInfo* G = A.g + (A.gid[A.lin[b]] - 1);
@@ -389,7 +390,7 @@ __global__ __launch_bounds__(64) void k_comp_paths_lds(CompArgs A, const unsigne
         for (unsigned t = lane; t < S; t += 64) w.seen[t] = 0;
         __syncthreads();
         unsigned a0c, a1c; comp_anchors(A, b, a0c, a1c);
-        comp_path_wave<true>(w, oi, b, S, a0c, a1c, A.lin, A.Wp, A.min_len, A.step, A.eps, pcap, A.outpts, A.outcnt, lane);
+        comp_path_wave<true>(w, oi, b, S, a0c, a1c, A.lin, A.Wp, A.min_len, A.step, A.eps, pcap, A.omul, A.outpts, A.outcnt, lane);
         __syncthreads();
     }
 }
@@ -401,18 +402,19 @@ __global__ __launch_bounds__(64) void k_comp_paths_glb(CompArgs A, const unsigne
     for (unsigned li = blockIdx.x; li < n; li += gridDim.x) {
         unsigned oi = list[li]; unsigned c = A.corder[oi]; unsigned b = A.cs[c], S = A.cs[c + 1] - b;
         CompWork<false> w; w.nbr = A.nbr; w.b = b;
-        w.prev = X.prev + b; w.que = X.que + b; w.cum = X.cum + b; w.seen = X.seen + b; w.P = X.P + b; w.stk = X.stk + b; w.keep = X.keep + b;
+        const size_t bp = (size_t)b * A.omul;                  // P, stk and keep hold omul entries per pixel (resample points), the others one
+        w.prev = X.prev + b; w.que = X.que + b; w.cum = X.cum + b; w.seen = X.seen + b; w.P = X.P + bp; w.stk = X.stk + bp; w.keep = X.keep + bp;
         for (unsigned t = lane; t < S; t += 64) w.seen[t] = 0;
         __syncthreads();
         unsigned a0c, a1c; comp_anchors(A, b, a0c, a1c);
-        comp_path_wave<false>(w, oi, b, S, a0c, a1c, A.lin, A.Wp, A.min_len, A.step, A.eps, S, A.outpts, A.outcnt, lane);
+        comp_path_wave<false>(w, oi, b, S, a0c, a1c, A.lin, A.Wp, A.min_len, A.step, A.eps, S * A.omul, A.omul, A.outpts, A.outcnt, lane);
         __syncthreads();
     }
 }
 __global__ __launch_bounds__(256) void k_path_desc(const unsigned* __restrict__ corder, const unsigned* __restrict__ cs, const unsigned* __restrict__ outcnt, const unsigned* __restrict__ flag,
-                                                    const unsigned* __restrict__ scan, unsigned nc, GatherDesc* __restrict__ d) {
+                                                    const unsigned* __restrict__ scan, unsigned nc, unsigned omul, GatherDesc* __restrict__ d) {
     unsigned oi = blockIdx.x * 256 + threadIdx.x; if (oi >= nc || !flag[oi]) return;
-    GatherDesc g; g.begin = cs[corder[oi]]; g.len = outcnt[oi]; g.rev = 0; g.src = 0;
+    GatherDesc g; g.begin = (int64_t)cs[corder[oi]] * omul; g.len = outcnt[oi]; g.rev = 0; g.src = 0;
     d[scan[oi]] = g;
 }
 __global__ __launch_bounds__(256) void k_flag_nonzero(const unsigned* __restrict__ v, unsigned n, unsigned* __restrict__ f) {
@@ -524,13 +526,22 @@ static int b_components(orip_ctx* c, B08& b, PhaseTimer& T) {
 static int b_paths(orip_ctx* c, const orip_params08& P, B08& b, DPolys& merged, PhaseTimer& T) {
     const int Wp = b.Wp, Hp = b.Hp; const size_t Np = b.Np; const unsigned M = b.M, NC = b.NC; const size_t nc1 = (size_t)NC + 1;
     dim3 blk(256);
-    const double stp = P.post_step;
-    if (!(stp >= 1.0)) ORIP_FAIL(c, "postmerge_resample_step must be >= 1");
-    const double ratio = std::min(1.0, 1.41422 / stp);          // resample points per component pixel
-    auto pcap_of = [&](unsigned cap) { return (unsigned)(cap * ratio) + (unsigned)stp + 4u; };
-    auto cap_of = [&](size_t budget) {                             // bytes: 25/node + 13/resample point
-        unsigned cap = (unsigned)((budget - 13.0 * (stp + 4.0) - 64.0) / (25.0 + 13.0 * ratio));
-        return std::min(cap, 65000u) & ~7u;
+    const double stp = P.post_step;                             // >= 1 (dedup08_b), +inf included
+    // A path of plen <= S pixels is sqrt(2) (plen - 1) long at most, and its float32 running sum of 1 and fl(sqrt 2) stays within 1.41422 / 1.41421356 of
+    // that while the sum is below 2^17 (from there on the ulp is 1/64 and every fl(sqrt 2) term rounds up to 1.421875, 0.5 % high): for paths of up to
+    // ~93 000 diagonal pixels, i.e. every LDS component and global ones up to that length.  Longer than the step, a path resamples to
+    // m = ceil(total / step) <= ratio S + 1 points; otherwise it passes through with its m = plen <= min(S, step + 1) pixels.  RDP keeps at most m points
+    // and holds at most m spans, so m bounds P, stk, keep and the output.  For a step >= 1.41422 that is m <= S: one entry per pixel (omul = 1).  Below
+    // it (1 <= step < 1.41422) m <= 1.41422 (S - 1) + 1 <= 2 S, with 40 % to spare for the rounding of any sum: two.  Past the 2^17 limit, at a step in
+    // [1.41422, 1.422), m can exceed S in the global class; the m > pcap guard of comp_path_wave then drops that component's line and writes nothing.
+    const double ratio = 1.41422 / stp;                         // resample points per component pixel
+    const unsigned omul = ratio > 1.0 ? 2u : 1u;
+    const double pass = std::min(stp, 65536.0);                 // pixels of a passed-through path, as far as the step bounds them
+    auto pcap_of = [&](unsigned cap) { return (unsigned)(cap * ratio) + std::min((unsigned)pass, cap) + 4u; };
+    auto cap_of = [&](size_t budget) {                             // bytes: 25/node + 13/resample point; the pass-through room in full, or bounded by cap
+        const double a = ((double)budget - 13.0 * (pass + 4.0) - 64.0) / (25.0 + 13.0 * ratio), b2 = ((double)budget - 13.0 * 4.0 - 64.0) / (25.0 + 13.0 * (ratio + 1.0));
+        const double cap = std::max(a, b2);                     // (signed: a is negative for a step above budget / 13; b2 >= 576, so no class is ever empty by its sizing)
+        return (unsigned)std::min(cap, 65000.0) & ~7u;
     };
     const size_t lds0 = 32 * 1024, lds1 = 160 * 1024;
     unsigned cap0 = cap_of(lds0), cap1 = cap_of(lds1);
@@ -540,15 +551,15 @@ static int b_paths(orip_ctx* c, const orip_params08& P, B08& b, DPolys& merged, 
     auto lds_bytes = [&](unsigned cap) { return (size_t)cap * 25 + (size_t)pcap_of(cap) * 13 + 16; };
     // scratch: cid canvas (reuses the BFS canvas), nbr, class lists, global-class work arrays
     unsigned *cid, *nbr, *l0, *l1, *l2; int2* outpts; CompScratch X;
-    { Carve L; L.take(cid, Np); L.take(nbr, (size_t)M * 8); L.each(M, X.prev, X.que, X.cum, X.P, X.stk);
-      L.take(outpts, M); L.each(nc1, l0, l1, l2); L.each(M, X.seen, X.keep); HIPC(c, L.commit(LN(c).vtmp[VTL_CELLS], 1024)); }
+    { Carve L; L.take(cid, Np); L.take(nbr, (size_t)M * 8); L.each(M, X.prev, X.que, X.cum); L.each((size_t)M * omul, X.P, X.stk);
+      L.take(outpts, (size_t)M * omul); L.each(nc1, l0, l1, l2); L.take(X.seen, M); L.take(X.keep, (size_t)M * omul); HIPC(c, L.commit(LN(c).vtmp[VTL_CELLS], 1024)); }
     unsigned* counts = LN(c).flags.as<LaneFlags>()->comp_counts;
     HIPC(c, hipMemsetAsync(counts, 0, sizeof(LaneFlags::comp_counts), LN(c).stream));
     hipLaunchKernelGGL(k_cid_fill, dim3(cdiv(M, 256)), blk, 0, LN(c).stream, b.lin, M, cid);
     hipLaunchKernelGGL(k_nbr_build, dim3((unsigned)cdiv((int64_t)M * 8, 256)), blk, 0, LN(c).stream, b.lin, M, b.skA, cid, Wp, Hp, nbr);
     hipLaunchKernelGGL(k_comp_classes, dim3(cdiv(NC, 256)), blk, 0, LN(c).stream, b.corder, NC, b.cs, cap0, cap1, std::max(2, P.post_minlen), counts, l0, l1, l2, b.outcnt);
     CompArgs A; A.corder = b.corder; A.cs = b.cs; A.lin = b.lin; A.gid = b.gid; A.g = b.grp; A.cid = cid; A.nbr = nbr; A.Wp = Wp; A.min_len = P.post_minlen; A.step = stp;
-    A.eps = (float)P.post_eps; A.outpts = outpts; A.outcnt = b.outcnt;
+    A.eps = (float)P.post_eps; A.omul = omul; A.outpts = outpts; A.outcnt = b.outcnt;
     static std::once_flag attr_once;            // several layer threads may arrive here together
     static std::atomic<int> attr_err{0};
     std::call_once(attr_once, [&] { orip_max_lds(k_comp_paths_lds, (int)lds1, attr_err); });
@@ -568,7 +579,7 @@ static int b_paths(orip_ctx* c, const orip_params08& P, B08& b, DPolys& merged, 
     unsigned NP = 0; ORIP_TRY(vread(c, &NP, b.oscan + NC));
     HIPC(c, merged.clear(LN(c).stream));
     if (NP) {
-        hipLaunchKernelGGL(k_path_desc, dim3(cdiv(NC, 256)), blk, 0, LN(c).stream, b.corder, b.cs, b.outcnt, b.oflag, b.oscan, NC, b.pd);
+        hipLaunchKernelGGL(k_path_desc, dim3(cdiv(NC, 256)), blk, 0, LN(c).stream, b.corder, b.cs, b.outcnt, b.oflag, b.oscan, NC, omul, b.pd);
         ORIP_TRY(vgather(c, b.pd, NP, reinterpret_cast<const int32_t*>(outpts), merged));
     }
     return 0;
@@ -582,6 +593,9 @@ int dedup08_b(orip_ctx* c, const orip_params08& P, PhaseTimer& T) {
     if (b.n2 > 0x3fffffff) ORIP_FAIL(c, "too many lines");
     b.Wp = P.W + 2 * PAD8; b.Hp = P.H + 2 * PAD8; b.Np = (size_t)b.Wp * b.Hp;
     if (b.Np >= (1ull << 27)) ORIP_FAIL(c, "canvas too large for stage 08-B index packing");
+    // the stamp radius max(1, brush) / 2 must fit the pad, or a band along the canvas border is clipped by the raster (the reference's ROI never clips it)
+    if (P.post_brush > 2 * PAD8 + 1) ORIP_FAIL(c, "postmerge brush %d out of range: at most %d (stamp radius brush / 2 <= the %d-px pad)", P.post_brush, 2 * PAD8 + 1, PAD8);
+    if (!(P.post_step >= 1.0)) ORIP_FAIL(c, "postmerge_resample_step must be >= 1");
     ORIP_TRY(b_groups(c, P, lines2, b));                   T.tick("groups");
     ORIP_TRY(b_raster_thin(c, P, lines2, b, T));           T.tick("thin");      // (laps "raster" on its way)
     ORIP_TRY(b_components(c, b, T));                       // (laps "c:ccl", and with a skeleton "c:sort", "c:anchor", "comps")

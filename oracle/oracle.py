@@ -267,6 +267,13 @@ def zs_std(img, max_iter=48) -> np.ndarray:
     return out
 
 
+def zs_std_count(img, max_iter=48) -> Tuple[int, np.ndarray]:
+    """(iterations run, skeleton): zs_std with the loop count of 08:342-372 (the last one may have changed nothing; max_iter when the cap stopped it)"""
+    a = np.ascontiguousarray(img, np.uint8); out = np.empty_like(a)
+    it = lib().orc_zs_std(_p(a), _p(out), a.shape[0], a.shape[1], max_iter) if a.size else 0
+    return int(it), out
+
+
 def ccl8(fg) -> Tuple[int, np.ndarray]:
     a = np.ascontiguousarray((np.asarray(fg) > 0).astype(np.uint8)); lab = np.zeros(a.shape, np.int32)
     n = lib().orc_ccl8(_p(a), _p(lab), a.shape[0], a.shape[1])

@@ -506,6 +506,53 @@ int orip_gcode_hatch_link(orip_ctx* ctx, const int64_t* off /* [n+1] or NULL */,
 int orip_svg_hatch_link(orip_ctx* ctx, const int32_t* cls /* [n] */, int64_t n, const int32_t* ring_sub /* [m] */, const int32_t* ring_group /* [m] */, int64_t m,
                         const orip_gcode_map* map, int32_t flags /* ORIP_HATCH_LINK_CLAMP */, int32_t reach, int64_t* stats /* [8] */);
 int orip_gcode_hatch_link_fetch(orip_ctx* ctx, int64_t* member_off /* [paths_out+1] */, int32_t* member /* [n] */);
+/* --stipple-mm (csrc/gcode_stipple.hip; ours, the reference has no such pass): closed shapes are filled with DOTS, the plotter's taps (stream byte 0x03),
+ * on one lattice for the whole drawing.  Integer arithmetic on the step grid throughout: no floating point, no tolerance.
+ * Input.  RINGS: m rings of one point or more, coordinates -2^30 .. 2^30, ring_group[r] = g in 0 .. 2^30 - 1, NON-DECREASING; a ring is closed by the edge
+ *   from its last point to its first, edges of zero length are ignored, and all rings of one g form the SHAPE g (holes work): the conventions of
+ *   orip_gcode_hatch_link and orip_gcode_occlude.  g is the element's ordinal, so it is also the shape's paint level.  A shape without an edge of positive
+ *   length has no interior and takes no part.
+ *   Lattice.  One family for the whole drawing, as --hatch-angle-deg has one line family: pitch p in 2 .. 2^20, row q in 1 .. 2^20, shift s in 0 .. p - 1.
+ *   Lattice point (i, j) is x = i p + (s if j is odd else 0), y = j q, for every integer i and j; negative ones count, and odd means j & 1 in two's
+ *   complement.  Because the family is global the dots of neighbouring shapes line up, and a drawing moved by a lattice vector keeps its dots.
+ *   Inside.  orip_gcode_occlude's notion: even-odd, and a point on an edge is not inside.  The parity counts the edges A -> B with (ay <= y) != (by <= y)
+ *   that pass strictly to the right of the point (an orientation test), so a ray through a vertex or along a horizontal edge gives the right parity.
+ *   Clear of the outline.  P is CLEAR iff for every edge A -> B of positive length of ITS OWN shape the squared distance to the SEGMENT is at least
+ *   inset^2: with d = B - A, L = d.d, w = P - A, t = w.d: t <= 0: |w|^2 >= inset^2; t >= L: |P - B|^2 >= inset^2; otherwise cross(d, w)^2 >= inset^2 L.
+ *   Differences reach 2^31 and cross products 2^63, so the comparison runs on 128-bit products, as the simplify and the occlusion do: no 64-bit
+ *   shortcut.  inset is in 0 .. 2^20.
+ *   Dot.  A lattice point becomes a dot of shape g by these steps, in this order, and is counted once, at the first step that decides it:
+ *     1. it is INSIDE g; if not it is not counted at all;  2. it is CLEAR; if not: `near`;  3. it lies in the closed rectangle rect = (x0, y0, x1, y1)
+ *     (the front door passes the sheet [0, W - 1] x [0, H - 1], or the clip rectangle under --clip); if not: `outside`;  4. under ORIP_STIPPLE_OCCLUDE it
+ *     is not INSIDE any shape of a strictly higher group; if it is: `hidden`.  A shape does not hide its own dots; shapes hide across pens.
+ *   Order.  Dots leave by group ascending, then by row j ascending, then by x ascending inside a row; under ORIP_STIPPLE_SERPENTINE x descends in rows
+ *   with odd j (the row number is global, as in the angled hatch).  A lattice point inside two overlapping shapes is a dot of each.
+ * stats: groups (those with an edge of positive length), rows ((group, j) pairs of those groups whose row meets the group's bounding box), candidates
+ *   (lattice points INSIDE their shape), near, outside, hidden, dots.  candidates == near + outside + hidden + dots.
+ * orip_gcode_stipple: rings explicit, in steps.  orip_svg_stipple: ring r is the resident fitted path ring_sub[r], converted on the device by the
+ * conversion's own code (csrc/gc_convert.h), clamped to the sheet under ORIP_STIPPLE_CLAMP as orip_gcode_to_steps clamps: orip_svg_occlude's rings.
+ * Either call reads the fitted paths and writes neither the resident step polylines nor their sources; the dots wait in a list of their own for
+ * orip_gcode_stipple_fetch (xy int32 [dots, 2], group int32 [dots]) until the next call.
+ * Errors before any launch, with nothing resident touched (a dot list from an earlier call included): the ring errors of orip_gcode_occlude, pitch,
+ * row, shift or inset out of range, a rect with x1 < x0 or y1 < y0 or outside +-2^30, unknown flags, a bad map, NULL stats or arrays.  m == 0 returns
+ * zeros and the list of no dots.  Found on the device, after the count, leaving no dot list: 2^26 dots or more, 2^28 rows or more (or 2^28 blocks of 64
+ * lattice points over the shapes' boxes), a converted ring coordinate that is not finite or out of range.
+ * Declined: density from a fill's lightness or opacity, and a pitch per element; blue-noise or relaxed (Lloyd) stippling (the answer would depend on
+ * iteration counts, and one rule per input is worth more here); dots along strokes and dots for zero-length dashes; removing the second of two
+ * coincident dots of overlapping shapes (--occlude is the answer: the lower shape's dots are hidden); taps in the written G-code (G-code has no tap, and
+ * the reference's parser drops one-point paths); the option on gcode2stream.py and svg2gcode.py (G-code has no fills); a bound on the worst case (every
+ * lattice point of a shape's box against every edge of the shape, and of the shapes above whose boxes it meets). */
+#define ORIP_STIPPLE_SERPENTINE 1
+#define ORIP_STIPPLE_OCCLUDE 2
+#define ORIP_STIPPLE_CLAMP 4
+#define ORIP_STIPPLE_STATS 7
+#define ORIP_STIPPLE_MAX (1 << 20)
+int orip_gcode_stipple(orip_ctx* ctx, const int64_t* ring_off /* [m+1] */, const int32_t* ring_pts /* [ring_off[m],2] */, const int32_t* ring_group /* [m] */, int64_t m,
+                       int32_t pitch, int32_t row, int32_t shift, int32_t inset, const int32_t* rect /* [4] */, int32_t flags /* SERPENTINE | OCCLUDE */,
+                       int64_t* stats /* [7]: groups, rows, candidates, near, outside, hidden, dots */);
+int orip_svg_stipple(orip_ctx* ctx, const int32_t* ring_sub /* [m] */, const int32_t* ring_group /* [m] */, int64_t m, const orip_gcode_map* map, int32_t pitch, int32_t row,
+                     int32_t shift, int32_t inset, const int32_t* rect /* [4] */, int32_t flags /* SERPENTINE | OCCLUDE | CLAMP */, int64_t* stats /* [7] */);
+int orip_gcode_stipple_fetch(orip_ctx* ctx, int32_t* xy /* [dots,2] */, int32_t* group /* [dots] */);
 /* --dashes / --dash-mm (csrc/gcode_dash.hip; ours, the reference has no such pass): a stroke with a dash pattern is drawn as its dashes.  All arithmetic is
  * integer on the step grid: nothing behind the conversion to steps is floating point.
  * Unit.  u = 1 / ORIP_DASH_UNIT = 1/256 step: every length below is in u.

@@ -413,6 +413,11 @@ struct orip_ctx {
     // links and the two chain arrays; hl_pair = the pairs in reach and their eligibility (the unit states the three layouts), free between calls; hl = the
     // result record; hl_res = member_off int64[hl_paths + 1], member int32[hl_n] of the last call of hl_n strokes (-1: none) until the next one
     DBuf hl_tmp, hl_ln, hl_pair, hl_res; GcCut hl; int64_t hl_n = -1, hl_paths = 0;
+    // --stipple-mm (gcode_stipple.hip), which reads the fitted paths and writes nothing of the resident step polylines: st_tmp = the rings and their edges,
+    // the shapes' tables (first point, group, box, has an edge, the plan of its lattice slots), the chunks per shape and their scan, the counters; st_ch =
+    // per chunk of 64 slots the dot mask, the dot count and its scan (the unit states both layouts), free between calls; st_out = THE DOT LIST, xy int2
+    // [st_dots] and group int32[st_dots] of the last call (-1: none) until the next one that passes its argument checks
+    DBuf st_tmp, st_ch, st_out; int64_t st_dots = -1;
     // svg2stream (svg.hip): scratch of the flattening and of the box, the resident paths (off int64[sv_n + 1], pts double2[sv_total]; raw units after
     // orip_svg_flatten, page mm after orip_svg_fit) until the next flatten; orip_gcode_to_steps reads them when it is called without pointers
     DBuf sv_tmp, sv_tmp2, sv_off, sv_pts; int64_t sv_n = 0, sv_total = 0; bool sv_ready = false, sv_box_ok = false; double sv_box[4] = {0, 0, 0, 0};

@@ -701,6 +701,47 @@ class Device:
                                             _l.HATCH_LINK_CLAMP if clamp else 0, int(reach), _p(st)))
         return self._link_result(st, n)
 
+    def _stipple_result(self, st):
+        """what the stipple left: its stats, the dot list through the fetch"""
+        d = {k: int(v) for k, v in zip(_l.STIPPLE_STATS, st)}
+        xy = np.zeros((max(d["dots"], 1), 2), np.int32); grp = np.zeros(max(d["dots"], 1), np.int32)
+        self._ck(self.L.orip_gcode_stipple_fetch(self.h, _p(xy), _p(grp)))
+        return xy[:d["dots"]], grp[:d["dots"]], d
+
+    def gcode_stipple(self, ring_off, ring_pts, ring_group, lattice, inset: int, rect, flags: int):
+        """--stipple-mm (include/orip.h: orip_gcode_stipple): the dots of the shapes given as rings ring_off int64 [m + 1], ring_pts int32 [R, 2] (steps,
+        -2^30 .. 2^30) with ring_group int32 [m], non-decreasing (the rings of one group are one shape), on the lattice (pitch, row, shift), at least
+        `inset` from their shape's outline, inside rect (x0, y0, x1, y1); flags: lib.STIPPLE_SERPENTINE | lib.STIPPLE_OCCLUDE.  Nothing resident changes.
+        -> (xy int32 [dots, 2], group int32 [dots], {lib.STIPPLE_STATS})"""
+        ro = np.ascontiguousarray(ring_off, np.int64).reshape(-1)
+        rp = np.ascontiguousarray(ring_pts, np.int32).reshape(-1, 2)
+        rg = np.ascontiguousarray(ring_group, np.int32).reshape(-1)
+        m = len(rg)
+        if len(ro) != m + 1 or (m and len(rp) < int(ro[-1])):
+            raise ValueError(f"{len(ro)} ring offsets and {len(rp)} ring points given for {m} rings")
+        p, q, s = (int(v) for v in lattice)
+        rc = np.ascontiguousarray(rect, np.int32).reshape(4)
+        st = np.zeros(7, np.int64)
+        self._ck(self.L.orip_gcode_stipple(self.h, _p(ro) if m else None, _p(rp) if m and len(rp) else None, _p(rg) if m else None, m, p, q, s, int(inset), _p(rc), int(flags), _p(st)))
+        return self._stipple_result(st)
+
+    def svg_stipple(self, ring_sub, ring_group, map: dict, clamp: bool, lattice, inset: int, rect, flags: int):
+        """--stipple-mm on the resident fitted paths (include/orip.h: orip_svg_stipple): ring r is the resident fitted path ring_sub[r], converted on the
+        device as the conversion converts (map: the conversion's; clamp: to the sheet, as gcode_to_steps, or not, as gcode_to_steps_clip).
+        -> (xy, group, stats) as gcode_stipple"""
+        rs = np.ascontiguousarray(ring_sub, np.int32).reshape(-1)
+        rg = np.ascontiguousarray(ring_group, np.int32).reshape(-1)
+        if len(rs) != len(rg):
+            raise ValueError(f"{len(rs)} rings and {len(rg)} ring groups")
+        m = len(rg)
+        gm = _l.GcodeMap(**{k: map[k] for k, _ in _l.GcodeMap._fields_})
+        p, q, s = (int(v) for v in lattice)
+        rc = np.ascontiguousarray(rect, np.int32).reshape(4)
+        st = np.zeros(7, np.int64)
+        self._ck(self.L.orip_svg_stipple(self.h, _p(rs) if m else None, _p(rg) if m else None, m, C.byref(gm), p, q, s, int(inset), _p(rc),
+                                         int(flags) | (_l.STIPPLE_CLAMP if clamp else 0), _p(st)))
+        return self._stipple_result(st)
+
     def gcode_dash(self, off, pts, pattern, phase, pat_off, pat_val, n: int | None = None):
         """--dashes / --dash-mm (include/orip.h: orip_gcode_dash): of the step polylines (off int64 [n + 1], pts int32 [total, 2]; both None = the n resident
         ones) every stroke with pattern[k] >= 0 is cut into the dashes of that pattern of the table (pat_off int32 [np + 1], pat_val int64, in 1/256 step),

@@ -67,7 +67,14 @@ to list first, and the orders and --improve-order see such a stroke as that one 
 first equal to the last) starts and ends at the ring vertex that makes the pen-up steps of the whole plot least, all closed strokes chosen together and
 exactly, ties to the lowest vertex in drawing order (orip_gcode_seam; include/orip.h states the rule).  It runs after the order and after --improve-order,
 immediately before the paths are gathered; the order, the directions, pens, sources, open strokes and every drawn segment stay as they are.  Allowed with
---no-reorder: file order, better seams.  Without the option no device call is added and every byte is what it was."""
+--no-reorder: file order, better seams.  Without the option no device call is added and every byte is what it was.
+
+--stipple-mm (svg2stream.py's; ours as well): the plotter can lower and lift the pen on the spot (the tap, stream byte 0x03), and the stream compiler
+plans such ops (orip.stream.plan_ops), but no vector front door made any.  The pass fills the shapes --hatch-fill marks with dots on one lattice for the
+whole drawing, each at least --stipple-inset-mm from its shape's outline (orip_svg_stipple; include/orip.h states the rule, exact in integers on the step
+grid).  It runs after the simplification and immediately before the order: the dots pass through none of dash, link, occlude, dedup, merge or simplify
+(under --occlude the pass itself leaves out the dots a higher shape hides) and join the strokes as one-point ops, which the orders, --improve-order and
+the pens take like any stroke; --loop-start sees a dot as the open stroke P, P.  Without the option no device call is added and every byte is what it was."""
 from __future__ import annotations
 
 import argparse
@@ -290,7 +297,7 @@ def path_ends(off: np.ndarray, pts: np.ndarray) -> np.ndarray:
 def gather_paths(off: np.ndarray, pts: np.ndarray, order: np.ndarray, rev: Optional[np.ndarray] = None, seam: Optional[np.ndarray] = None) -> Tuple[np.ndarray, np.ndarray]:
     """the paths in the given order, those with rev[k] set back to front: (off, pts), flat numpy over all paths.  seam[k] > 0 (by position, closed strokes
     only: include/orip.h, orip_gcode_seam): the stroke of L points is rotated to start and end at its stored vertex seam[k], s, s + 1, .., L - 2, 0, .., s,
-    before rev turns it round"""
+    before rev turns it round.  A one-point op (a dot of --stipple-mm) has no seam and stays as it is"""
     order = np.asarray(order, np.int64)
     lens = np.diff(off)[order]
     noff = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
@@ -299,15 +306,17 @@ def gather_paths(off: np.ndarray, pts: np.ndarray, order: np.ndarray, rev: Optio
         t = np.where(np.repeat(np.asarray(rev, bool), lens), np.repeat(lens, lens) - 1 - t, t)
     if seam is not None:
         s = np.repeat(np.asarray(seam, np.int64), lens)
-        t = np.where(s > 0, (t + s) % np.repeat(lens - 1, lens), t)
+        t = np.where(s > 0, (t + s) % np.repeat(np.maximum(lens - 1, 1), lens), t)
     return noff, pts[np.repeat(off[:-1][order], lens) + t]
 
 
-def plan_pens(off: np.ndarray, pts: np.ndarray, path_pen: np.ndarray, head: Sequence[int], sc: ST.StreamConfig) -> ST.Plan:
+def plan_pens(off: np.ndarray, pts: np.ndarray, path_pen: np.ndarray, head: Sequence[int], sc: ST.StreamConfig, is_tap: Optional[np.ndarray] = None) -> ST.Plan:
     """The plan of paths in drawing order whose pens come in runs (path_pen[k]: the pen of path k), from (0, 0): the service bytes `head`, then per run
     what draw_color_group does (:317-333) -- the approach to the run's first point when the cursor is elsewhere, the colour byte, and per path a travel
-    when the cursor is elsewhere, pen down, the segments, pen up.  The pattern of orip.stream.plan_layers, every move by the same engine."""
+    when the cursor is elsewhere, pen down, the segments, pen up.  The pattern of orip.stream.plan_layers, every move by the same engine.  is_tap[k]: path
+    k is one point and is drawn as a tap (None: no path is)."""
     off = np.asarray(off, np.int64); pts = np.asarray(pts, np.int64).reshape(-1, 2); path_pen = np.asarray(path_pen, np.int64)
+    is_tap = np.zeros(len(path_pen), bool) if is_tap is None else np.asarray(is_tap, bool)
     plans = [ST.fixed_plan(list(head))]
     cur = np.zeros(2, np.int64)
     cuts = np.concatenate([[0], np.nonzero(np.diff(path_pen))[0] + 1, [len(path_pen)]]) if len(path_pen) else np.zeros(1, np.int64)
@@ -318,7 +327,7 @@ def plan_pens(off: np.ndarray, pts: np.ndarray, path_pen: np.ndarray, head: Sequ
         goff, gpts = off[a:b + 1] - off[a], pts[off[a]:off[b]]
         if (cur != gpts[0]).any():
             plans.append(ST.fixed_plan([-1], [[*cur, *gpts[0]]])); cur = gpts[0]
-        plans.append(ST.plan_ops(goff, gpts, np.zeros(b - a, bool), cur, [0x08 | pen], False, sc))
+        plans.append(ST.plan_ops(goff, gpts, is_tap[a:b], cur, [0x08 | pen], False, sc))
         cur = gpts[-1]
     return ST.concat_plans(plans)
 
@@ -401,6 +410,18 @@ class HatchLink:
         self.device_follows = False                 # resolve_steps: pass and sources are both this device's, whose sources follow the zigzags through their first line
 
 
+class Stipple:
+    """--stipple-mm of the SVG door (orip.svg states it), which StrokeSteps does not carry: fn(ring_sub, ring_group, map, clamp, lattice, inset, rect, flags)
+    -> (xy int32 [dots, 2], group int32 [dots], stats) or None = the device (orip_svg_stipple); the rings as fitted paths and the shape g of each; clamp =
+    the rings are clamped as the strokes were; lattice = (pitch, row, shift) and inset in steps; rect = (x0, y0, x1, y1), the sheet or the clip rectangle;
+    flags of STIPPLE_SERPENTINE and STIPPLE_OCCLUDE (include/orip.h states the rule); pen_of(group int64 [dots]) -> the pen of every dot, -1 for
+    --color-index (None: every dot takes --color-index)"""
+    def __init__(self, fn, ring_sub, ring_group, clamp: bool, lattice, inset: int, rect, flags: int, pen_of: Optional[Callable] = None):
+        self.fn = fn; self.ring_sub = np.asarray(ring_sub, np.int32).reshape(-1); self.ring_group = np.asarray(ring_group, np.int32).reshape(-1)
+        self.clamp = bool(clamp); self.lattice = tuple(int(v) for v in lattice); self.inset = int(inset); self.rect = tuple(int(v) for v in rect)
+        self.flags = int(flags); self.pen_of = pen_of
+
+
 class Seam:
     """--loop-start, which StrokeSteps does not carry: fn(off, pts, order int32 [n] or None, rev bool [n] or None) -> (seam int32 [n]: by sequence position,
     the stored ring vertex a closed stroke starts and ends at, 0 for an open one; stats) or None = the device (orip_gcode_seam)"""
@@ -409,7 +430,7 @@ class Seam:
 
 
 def resolve_steps(st: StrokeSteps, o, grouped: bool, device=None, convert: Optional[Callable] = None, force: bool = False, occlude: Optional[Occlude] = None,
-                  dash: Optional[Dash] = None, seam: Optional[Seam] = None, hatch_link: Optional[HatchLink] = None):
+                  dash: Optional[Dash] = None, seam: Optional[Seam] = None, hatch_link: Optional[HatchLink] = None, stipple: Optional[Stipple] = None):
     """The steps the options need, those not given taken from a device -> (steps, device); codes and pack stay as given (orip.stream.compile_plan fills them).
     When none is missing, and the caller does not `force` a device for steps of its own, no device is made and orip.stages is not imported.  convert(device)
     -> the conversion of a front door whose paths are on the device already (orip.svg).  Dedup, merge and simplify work on the polylines the pass before them
@@ -419,11 +440,13 @@ def resolve_steps(st: StrokeSteps, o, grouped: bool, device=None, convert: Optio
     given conversion the strokes are uploaded first (an occlusion without rings makes them the resident list) and the pass then runs as it does otherwise.
     `seam`: its fn is filled in the same way; it reads the strokes the last pass in front of the order left resident, or is sent them.  `hatch_link`: its
     fn is filled in the same way, and it stands between the dash pass and the occlusion; it needs the sources, and its rings are fitted paths as the
-    occlusion's are, so behind a given pass the strokes are uploaded first in the same way (a link pass without rings makes them the resident list)."""
+    occlusion's are, so behind a given pass the strokes are uploaded first in the same way (a link pass without rings makes them the resident list).
+    `stipple`: its fn is filled in the same way; it reads the fitted paths and touches no stroke, so it needs nothing resident behind the fit.  With it
+    the seam pass is always sent its strokes: the dots among them are in no resident list."""
     need = ["convert", "order"] + ["order_pens", "source"] * bool(grouped) + ["merge"] * bool(o.merge_paths) + ["improve"] * bool(o.improve_order) + \
         ["simplify"] * (o.simplify_mm is not None) + ["dedup"] * bool(o.dedup) + ["source"] * (occlude is not None or dash is not None or hatch_link is not None)
     if not force and all(getattr(st, k) is not None for k in need) and (occlude is None or occlude.fn is not None) and (dash is None or dash.fn is not None) and \
-            (seam is None or seam.fn is not None) and (hatch_link is None or hatch_link.fn is not None):
+            (seam is None or seam.fn is not None) and (hatch_link is None or hatch_link.fn is not None) and (stipple is None or stipple.fn is not None):
         return st, device
     if device is None:
         from .stages import device as _default_device
@@ -457,7 +480,9 @@ def resolve_steps(st: StrokeSteps, o, grouped: bool, device=None, convert: Optio
             return device.svg_hatch_link(cls, ring_sub, ring_group, m, clamp, reach, n=len(off) - 1)
         hatch_link.fn = own_link
     if seam is not None and seam.fn is None:
-        seam.fn = (lambda off, pts, order, rev: device.gcode_seam(None, None, order, rev, n=len(off) - 1)) if after_simplify else device.gcode_seam
+        seam.fn = (lambda off, pts, order, rev: device.gcode_seam(None, None, order, rev, n=len(off) - 1)) if after_simplify and stipple is None else device.gcode_seam
+    if stipple is not None and stipple.fn is None:
+        stipple.fn = device.svg_stipple
     if dash is not None and dash.fn is None:
         dash.device_follows = st.source is None
         dash.fn = (lambda off, pts, pattern, phase, po, pv: device.gcode_dash(None, None, pattern, phase, po, pv, n=len(off) - 1)) if after_convert else device.gcode_dash
@@ -683,10 +708,31 @@ def travel_steps(off, pts, start=(0, 0)) -> int:
     return int(np.abs(a - np.concatenate([np.asarray(start, np.int64).reshape(1, 2), b[:-1]])).max(1).sum())
 
 
-def _seam(sm: Seam, off, pts, order, rev, info: dict):
-    """the strokes gathered in drawing order, every closed one started at the vertex the pass chose; info["seam"]"""
+def _stipple(sp: Stipple, m: dict, info: dict):
+    """the dots of the stippled shapes, (xy, group), in the order the rule states; info["stipple"]"""
+    xy, grp, sst = sp.fn(sp.ring_sub, sp.ring_group, m, sp.clamp, sp.lattice, sp.inset, sp.rect, sp.flags)
+    xy = np.asarray(xy, np.int32).reshape(-1, 2); grp = np.asarray(grp, np.int64).reshape(-1)
+    d = {k: int(sst[k]) for k in STIPPLE_STATS}
+    (p, q, s), (x0, y0, x1, y1) = sp.lattice, sp.rect
+    x, y = xy[:, 0].astype(np.int64), xy[:, 1].astype(np.int64)
+    if len(grp) != len(xy) or d["dots"] != len(xy) or d["candidates"] != d["near"] + d["outside"] + d["hidden"] + d["dots"] or (np.diff(grp) < 0).any() or \
+            (d["hidden"] and not sp.flags & STIPPLE_OCCLUDE) or (len(grp) and not np.isin(grp, sp.ring_group).all()):
+        raise RuntimeError("the stipple's counts do not add up")
+    if (y % q).any() or ((x - np.where((y // q) & 1, s, 0)) % p).any() or ((x < x0) | (x > x1) | (y < y0) | (y > y1)).any():
+        raise RuntimeError("the stipple returned a dot off the lattice or outside the rectangle")
+    info["stipple"] = dict(d, pitch=p, row=q, shift=s)
+    return xy, grp
+
+
+def _seam(sm: Seam, off, pts, order, rev, info: dict, is_tap=None):
+    """the strokes gathered in drawing order, every closed one started at the vertex the pass chose; info["seam"].  is_tap[k]: stroke k is a dot, which the
+    pass is sent as the open two-point stroke P, P (its seam is 0)"""
     n = len(off) - 1
-    seam, sst = sm.fn(off, pts, None if order is None else np.asarray(order, np.int32), None if rev is None else np.asarray(rev, bool))
+    s_off, s_pts = off, pts
+    if is_tap is not None and is_tap.any():
+        twice = np.ones(len(pts), np.int64); twice[off[:-1][is_tap]] = 2
+        s_off = np.concatenate([[0], np.cumsum(np.diff(off) + is_tap)]).astype(np.int64); s_pts = np.repeat(pts, twice, axis=0)
+    seam, sst = sm.fn(s_off, s_pts, None if order is None else np.asarray(order, np.int32), None if rev is None else np.asarray(rev, bool))
     seam = np.asarray(seam, np.int64).reshape(-1)
     d = {k: int(sst[k]) for k in SEAM_STATS}
     seq = np.arange(n) if order is None else np.asarray(order, np.int64)
@@ -705,22 +751,23 @@ def _seam(sm: Seam, off, pts, order, rev, info: dict):
     return goff, gpts
 
 
-def _plan(o: GcodeOptions, sc: ST.StreamConfig, off, pts, path_pen) -> ST.Plan:
-    """every move of the plot; path_pen: the pen of every stroke in drawing order, or None for --color-index throughout"""
+def _plan(o: GcodeOptions, sc: ST.StreamConfig, off, pts, path_pen, is_tap=None) -> ST.Plan:
+    """every move of the plot; path_pen: the pen of every stroke in drawing order, or None for --color-index throughout; is_tap: the strokes that are dots
+    (None: none is)"""
     if not (0 <= int(o.color_index) <= 7):
         raise ValueError("color index 0..7")
     div0 = min(max(int(sc.div_start), 0), 63)                             # set_speed(div_start): written here, and remembered (layout: initial_div)
     if path_pen is not None:
-        return plan_pens(off, pts, path_pen, [ST.PEN_UP, 0x40 | div0], sc)
-    return ST.plan_ops(off, pts, np.zeros(len(off) - 1, bool), (0, 0), [ST.PEN_UP, 0x40 | div0, 0x08 | int(o.color_index)], False, sc)
+        return plan_pens(off, pts, path_pen, [ST.PEN_UP, 0x40 | div0], sc, is_tap)
+    return ST.plan_ops(off, pts, np.zeros(len(off) - 1, bool) if is_tap is None else is_tap, (0, 0), [ST.PEN_UP, 0x40 | div0, 0x08 | int(o.color_index)], False, sc)
 
 
 def stroke_stream(text_or_paths, opts: Optional[GcodeOptions], device, steps: StrokeSteps, timings: Optional[dict] = None, pens: Optional[np.ndarray] = None,
                   occlude: Optional[Occlude] = None, dash: Optional[Dash] = None, dash_fn: Optional[Callable] = None, seam_fn: Optional[Callable] = None,
-                  seam: Optional["Seam"] = None, hatch_link: Optional[HatchLink] = None) -> Tuple[bytes, dict]:
+                  seam: Optional["Seam"] = None, hatch_link: Optional[HatchLink] = None, stipple: Optional[Stipple] = None) -> Tuple[bytes, dict]:
     """build_stream_from_gcode with the device steps as one record: parse, convert, pens of the strokes, [dash: --dash-mm gives every path the one pattern,
-    with dash_fn; the SVG door brings a record of its own], [hatch_link, the SVG door's], [occlude, the SVG door's], dedup, merge, simplify, order, [seam: --loop-start, with seam_fn, or the record a door has
-    resolved already], plan, compile"""
+    with dash_fn; the SVG door brings a record of its own], [hatch_link, the SVG door's], [occlude, the SVG door's], dedup, merge, simplify, [stipple, the
+    SVG door's: its dots join the strokes as one-point ops], order, [seam: --loop-start, with seam_fn, or the record a door has resolved already], plan, compile"""
     import time
     o = apply_speed_scale(GcodeOptions(**{f.name: getattr(opts, f.name) for f in fields(GcodeOptions)}) if opts is not None else GcodeOptions())
     W, H = target_size(o)
@@ -758,15 +805,64 @@ def stroke_stream(text_or_paths, opts: Optional[GcodeOptions], device, steps: St
     if own_dash is not None and dash is None:                             # --dash-mm: every path gets the pattern
         dash = Dash(dash_fn, np.zeros(len(off_mm) - 1, np.int32), np.full(len(off_mm) - 1, own_dash[1], np.int64), [0, len(own_dash[0])], own_dash[0])
     sm = (seam if seam is not None else Seam(seam_fn)) if o.loop_start else None
-    st, device = resolve_steps(steps, o, grouped, device, occlude=occlude, dash=dash, seam=sm, hatch_link=hatch_link)
+    st, device = resolve_steps(steps, o, grouped, device, occlude=occlude, dash=dash, seam=sm, hatch_link=hatch_link, stipple=stipple)
     m = dict(scale_x=o.scale_x, scale_y=o.scale_y, offset_x_mm=o.offset_x_mm, offset_y_mm=o.offset_y_mm, steps_per_mm=o.steps_per_mm, W=W, H=H, invert_y=int(bool(o.invert_y)))
+
+    def finish(off, pts, pen, group):
+        """behind the stroke passes: [the dots], the order, [the seams], the plan, the bytes"""
+        is_tap = None
+        if stipple is not None:
+            lap("order")
+            xy, dot_group = _stipple(stipple, m, info)
+            info["taps"] = len(xy)
+            if len(xy):                                                   # one-point ops behind the strokes, in the order the rule states
+                is_tap = np.concatenate([np.zeros(len(off) - 1, bool), np.ones(len(xy), bool)])
+                off = np.concatenate([off, off[-1] + 1 + np.arange(len(xy), dtype=np.int64)]); pts = np.concatenate([pts, xy])
+                if grouped:
+                    dot_pen = np.full(len(xy), -1, np.int64) if pens is None or stipple.pen_of is None else np.asarray(stipple.pen_of(dot_group), np.int64).reshape(-1)
+                    if len(dot_pen) != len(xy) or (dot_pen < -1).any() or (dot_pen >= MAX_PENS).any():
+                        raise RuntimeError("the pens of the dots: one per dot, each -1 or a pen")
+                    dot_pen = np.where(dot_pen < 0, int(o.color_index), dot_pen)
+                    if pens is not None:
+                        info["pens"]["paths"] = (np.asarray(info["pens"]["paths"]) + np.bincount(dot_pen, minlength=MAX_PENS)).tolist()
+                    pen = np.concatenate([pen, dot_pen])
+                    group = np.concatenate([group, (np.argsort(np.asarray(pen_sequence(o.pen_order)))[dot_pen] if pens is not None else np.zeros(len(xy))).astype(np.int32)])
+            lap("stipple")
+        if len(off) <= 1:                                                 # neither a stroke nor a dot
+            return EMPTY_STREAM, dict(info, bytes=len(EMPTY_STREAM))
+        order, rev = _order(st, o, off, pts, group, n_groups, info, lap)
+        if sm is not None:
+            lap("order")
+            off, pts = _seam(sm, off, pts, order, rev, info, is_tap)
+            lap("seam")
+        elif order is not None:
+            off, pts = gather_paths(off, pts, order, rev)
+        if is_tap is not None and order is not None:
+            is_tap = is_tap[order]
+        if grouped:
+            (info["pens"] if pens is not None else info)["reversed"] = int(rev.sum())
+        lap("order")
+        P = _plan(o, sc, off, pts, pen[order] if pens is not None else None, is_tap)
+        lap("plan")
+        data, table, coff = ST.compile_plan(P, sc, device, st.codes, st.pack, initial_div=int(sc.div_start), lap=lap)
+        info.update(steps=int(coff[-1]), bytes=len(data), pieces=len(table.pos), moves=len(P.moves))
+        return data, info
+
+    def nothing_left():
+        """no stroke is left: the empty stream, unless the dots are still to come"""
+        if stipple is None:
+            return EMPTY_STREAM, dict(info, bytes=len(EMPTY_STREAM))
+        if pens is not None and "pens" not in info:
+            info["pens"] = {"paths": [0] * MAX_PENS, "unmatched": 0, "reversed": 0}
+        return finish(np.zeros(1, np.int64), np.zeros((0, 2), np.int32), *((np.zeros(0, np.int64), np.zeros(0, np.int32)) if grouped else (None, None)))
+
+    n_groups = MAX_PENS if pens is not None else 1
     off, pts = _convert(st, off_mm, pts_mm, m, rect, info)
     lap("to_steps")
     info["paths"] = n = len(off) - 1
     if n == 0:
-        return EMPTY_STREAM, dict(info, bytes=len(EMPTY_STREAM))
+        return nothing_left()
     pen, group = _stroke_pens(st, o, pens, n, info) if grouped else (None, None)
-    n_groups = MAX_PENS if pens is not None else 1
     if dash is not None:                                                  # before the occlusion: a shape on top cuts dashes as it does on a screen
         lap("order")                                                      # the sources and the pens belong to the order's lap
         off, pts, pen, group, dash_src = _dash(st, dash, off, pts, pen, group, info)
@@ -774,7 +870,7 @@ def stroke_stream(text_or_paths, opts: Optional[GcodeOptions], device, steps: St
             st = st._replace(source=lambda k: _sources_behind_dash(dash_src, k))
         lap("dash")
         if len(off) <= 1:                                                 # every stroke lies in a gap
-            return EMPTY_STREAM, dict(info, bytes=len(EMPTY_STREAM))
+            return nothing_left()
     if hatch_link is not None:                                            # before the occlusion: it sees the hatch lines whole, and a shape on top cuts a zigzag
         lap("order")                                                      # the sources and the pens belong to the order's lap
         off, pts, pen, group, link_src = _hatch_link(st, hatch_link, off, pts, pen, group, m, info)
@@ -786,7 +882,7 @@ def stroke_stream(text_or_paths, opts: Optional[GcodeOptions], device, steps: St
         off, pts, pen, group = _occlude(st, occlude, off, pts, pen, group, m, info)
         lap("occlude")
         if len(off) <= 1:                                                 # everything lies under a shape
-            return EMPTY_STREAM, dict(info, bytes=len(EMPTY_STREAM))
+            return nothing_left()
     if o.dedup:
         lap("order")                                                      # the sources and the pens belong to the order's lap
         off, pts, pen, group = _dedup(st, off, pts, pen, group, n_groups, info)
@@ -801,21 +897,7 @@ def stroke_stream(text_or_paths, opts: Optional[GcodeOptions], device, steps: St
             lap("order")
         off, pts = _simplify(st, off, pts, tol4, info)
         lap("simplify")
-    order, rev = _order(st, o, off, pts, group, n_groups, info, lap)
-    if sm is not None:
-        lap("order")
-        off, pts = _seam(sm, off, pts, order, rev, info)
-        lap("seam")
-    elif order is not None:
-        off, pts = gather_paths(off, pts, order, rev)
-    if grouped:
-        (info["pens"] if pens is not None else info)["reversed"] = int(rev.sum())
-    lap("order")
-    P = _plan(o, sc, off, pts, pen[order] if pens is not None else None)
-    lap("plan")
-    data, table, coff = ST.compile_plan(P, sc, device, st.codes, st.pack, initial_div=int(sc.div_start), lap=lap)
-    info.update(steps=int(coff[-1]), bytes=len(data), pieces=len(table.pos), moves=len(P.moves))
-    return data, info
+    return finish(off, pts, pen, group)
 
 
 IMPROVE_STATS = ("travel_before", "travel_after", "rounds", "converged_groups", "skipped_groups")
@@ -825,6 +907,8 @@ OCCLUDE_STATS = ("segments", "whole", "cut", "hidden", "pieces", "collapsed", "p
 DASH_STATS = ("paths_in", "dashed", "dashes", "collapsed", "paths_out", "points_out", "length_in", "length_on")      # include/orip.h: orip_gcode_dash
 HATCH_LINK_STATS = ("lines", "in_reach", "eligible", "links", "coincident", "paths_out", "points_out", "link_steps")      # include/orip.h: orip_gcode_hatch_link
 HATCH_LINK_REACH_MAX = 1 << 20                # include/orip.h: ORIP_HATCH_LINK_REACH_MAX
+STIPPLE_STATS = ("groups", "rows", "candidates", "near", "outside", "hidden", "dots")      # include/orip.h: orip_gcode_stipple
+STIPPLE_SERPENTINE, STIPPLE_OCCLUDE, STIPPLE_MAX = 1, 2, 1 << 20      # include/orip.h: ORIP_STIPPLE_SERPENTINE, ORIP_STIPPLE_OCCLUDE; pitch, row and inset at most
 SEAM_STATS = ("closed", "moved", "travel_before", "travel_after")      # include/orip.h: orip_gcode_seam
 DASH_UNIT, DASH_MAX_ENTRIES = 256, 64         # include/orip.h: ORIP_DASH_UNIT (dash lengths are in 1/256 step), ORIP_DASH_MAX_ENTRIES
 SIMPLIFY_TOL4_MAX = (1 << 17) - 1             # include/orip.h: ORIP_SIMPLIFY_TOL4_MAX
@@ -1015,6 +1099,10 @@ def report_lines(tag: str, info: dict, unmatched: bool = False):
     if "simplify" in info:
         st = info["simplify"]
         yield f"[{tag}] simplify: {st['points_in']} points -> {st['points_out']} within {st['tol4'] / 4:g} steps, {st['paths_changed']} strokes changed"
+    if "stipple" in info:
+        d = info["stipple"]
+        yield (f"[{tag}] stipple: {d['dots']} dots in {d['groups']} shapes (pitch {d['pitch']}, rows {d['row']}; {d['near']} near the outline, "
+               f"{d['outside']} off the sheet, {d['hidden']} hidden)")
     if "improve" in info:
         yield improve_line(tag, info["improve"])
     if "seam" in info:

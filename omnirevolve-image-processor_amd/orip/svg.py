@@ -78,6 +78,16 @@ shape on top cuts a zigzag as it does on a screen.  Pens, levels and sources fol
 the outline and nothing links; with --no-serpentine a link is a long diagonal, mostly out of reach: the report line says how many lines linked.  The G-code
 file is not changed; the preview is rendered from the stream and shows the result.
 
+--stipple-mm S [--stipple-inset-mm I] [--stipple-pattern square|stagger] (off unless given; ours, svg2stream.py only; include/orip.h states the rule): the
+shapes --hatch-fill marks are filled with dots, the plotter's taps, on ONE lattice for the whole drawing: pitch = int(round(S steps_per_mm)) steps, 2 .. 2^20;
+square = (pitch, pitch, 0), stagger (the default) = (pitch, max(1, (pitch 3547 + 2048) >> 12), pitch >> 1) as (pitch, row distance, shift of the odd rows);
+3547 / 4096 stands for sqrt(3) / 2, a stated deviation from a true hexagonal lattice.  A dot lies strictly inside its shape (even-odd, holes work) and at
+least I mm (default 0.675, --hatch-inset-mm's default; rounded as the pitch) from its outline, inside the sheet (the clip rectangle under --clip); under
+--occlude the dots a shape painted later covers are left out.  --no-serpentine draws every row left to right.  The dots are placed on the device
+(orip_svg_stipple: the rings are orip_svg_hatch_link's) after the simplification and join the strokes as one-point ops immediately before the order; with
+--pen-colors a dot takes the pen of its shape's fill colour, else of its stroke (hatch_pens).  Independent of --hatch-spacing-mm: both may be on.  The
+G-code file is not changed (G-code has no tap); the preview is rendered from the stream and shows the dots.
+
 The device steps are injectable, as in orip/gcode.py, so that this host logic can be tested without a GPU; the product has no CPU path."""
 from __future__ import annotations
 
@@ -654,6 +664,9 @@ class SvgOptions:
     hatch_angle_deg: Optional[float] = None             # None: the reference's hatch along X / Y; else the exact hatch along that angle (orip_svg_hatch_angle)
     hatch_connect: bool = False                         # hatch lines are joined into zigzags by links that stay inside the shape (svg2stream.py only)
     hatch_connect_mm: Optional[float] = None            # the longest link; None: twice hatch_spacing_mm; only with hatch_connect
+    stipple_mm: Optional[float] = None                  # filled shapes are filled with dots (taps) this far apart (svg2stream.py only); None: no dots
+    stipple_inset_mm: Optional[float] = None            # how far every dot stays inside its shape's outline; None: hatch_inset_mm's default; only with stipple_mm
+    stipple_pattern: Optional[str] = None               # square or stagger; None: stagger; only with stipple_mm
     pen_colors: Optional[str] = None                    # None: one pen, --color-index
     pen_order: Optional[str] = None
     allow_reverse: bool = False
@@ -738,6 +751,44 @@ def hatch_connect_reach(o: SvgOptions) -> Optional[int]:
     if not (1 <= reach <= GC.HATCH_LINK_REACH_MAX):
         raise ValueError(f"--hatch-connect-mm {mm:g} is {reach} steps at {float(o.steps_per_mm):g} steps per mm: 1 .. 2^20")
     return reach
+
+
+STIPPLE_PATTERNS = ("square", "stagger")
+
+
+def stipple_lattice(pitch: int, pattern: str) -> Tuple[int, int, int]:
+    """(pitch, row, shift) of orip_svg_stipple: square = (p, p, 0); stagger = (p, max(1, (p * 3547 + 2048) >> 12), p >> 1), every other row moved by half
+    a pitch and the rows 3547 / 4096 of a pitch apart.  That is sqrt(3) / 2 to four digits and then rounded to whole steps: a stated deviation from a true
+    hexagonal lattice, whose rows no step grid holds."""
+    if pattern not in STIPPLE_PATTERNS:
+        raise ValueError("--stipple-pattern must be one of " + ", ".join(STIPPLE_PATTERNS))
+    p = int(pitch)
+    return (p, p, 0) if pattern == "square" else (p, max(1, (p * 3547 + 2048) >> 12), p >> 1)
+
+
+def stipple_params(o: SvgOptions) -> Optional[dict]:
+    """None without --stipple-mm, else what orip_svg_stipple takes: "lattice" = (pitch, row, shift) with pitch = int(round(S steps_per_mm)) in 2 .. 2^20,
+    and "inset" = int(round(I steps_per_mm)) in 0 .. 2^20, I = --stipple-inset-mm (default: --hatch-inset-mm's default).  The inset and the pattern belong
+    to --stipple-mm."""
+    if o.stipple_mm is None:
+        if o.stipple_inset_mm is not None or o.stipple_pattern is not None:
+            raise ValueError("--stipple-inset-mm and --stipple-pattern need --stipple-mm")
+        return None
+    mm, spm = float(o.stipple_mm), float(o.steps_per_mm)
+    if not (mm > 0.0 and math.isfinite(mm)):
+        raise ValueError("--stipple-mm must be a positive number")
+    v = mm * spm
+    pitch = int(round(v)) if math.isfinite(v) and v < float(1 << 31) else 1 << 31
+    if not (2 <= pitch <= GC.STIPPLE_MAX):
+        raise ValueError(f"--stipple-mm {mm:g} is {pitch} steps at {spm:g} steps per mm: 2 .. 2^20")
+    im = SvgOptions.hatch_inset_mm if o.stipple_inset_mm is None else float(o.stipple_inset_mm)
+    if not (im >= 0.0 and math.isfinite(im)):
+        raise ValueError("--stipple-inset-mm must be a number and not negative")
+    v = im * spm
+    inset = int(round(v)) if math.isfinite(v) and v < float(1 << 31) else 1 << 31
+    if inset > GC.STIPPLE_MAX:
+        raise ValueError(f"--stipple-inset-mm {im:g} is {inset} steps at {spm:g} steps per mm: at most 2^20")
+    return {"lattice": stipple_lattice(pitch, "stagger" if o.stipple_pattern is None else o.stipple_pattern), "inset": inset}
 
 
 def tolerance_mm(o: SvgOptions) -> float:
@@ -992,7 +1043,7 @@ def build_stream_from_svg(text: Union[str, bytes, SegmentTable], opts: Optional[
                           order_pens_fn: Optional[Callable] = None, merge_fn: Optional[Callable] = None, improve_fn: Optional[Callable] = None,
                           clip_fn: Optional[Callable] = None, simplify_fn: Optional[Callable] = None, dedup_fn: Optional[Callable] = None,
                           occlude_fn: Optional[Callable] = None, dash_fn: Optional[Callable] = None, seam_fn: Optional[Callable] = None,
-                          hatch_link_fn: Optional[Callable] = None) -> Tuple[bytes, dict]:
+                          hatch_link_fn: Optional[Callable] = None, stipple_fn: Optional[Callable] = None) -> Tuple[bytes, dict]:
     """The stream of an SVG text (or of a parsed SegmentTable).  Device steps, each None = the GPU (there is no CPU path in the product):
       flatten_fn(table, tol_raw) -> paths          orip_svg_flatten      (`paths` is whatever the other steps take: on the GPU a count, the points stay there)
       bbox_fn(paths) -> (min x, min y, max x, max y)   orip_svg_bbox
@@ -1023,6 +1074,10 @@ def build_stream_from_svg(text: Union[str, bytes, SegmentTable], opts: Optional[
     and, only with --hatch-connect (after the pens and the dashes, before the occlusion; it needs source_fn, hatch_groups_fn and the points of fetch_fn):
       hatch_link_fn(paths, off, pts, cls int32 [n], ring_sub, ring_group, map, clamp, reach) -> (off, pts, member_off, member, stats)   orip_svg_hatch_link
     the rings are the fitted paths ring_sub with their fill groups, clamp = not --clip; info["hatch_link"] = the eight counts of include/orip.h and "reach".
+    and, only with --stipple-mm (after the simplification, immediately before the order; with --pen-colors the dots take hatch_pens' pen of their shape):
+      stipple_fn(paths, ring_sub, ring_group, map, clamp, lattice, inset, rect, flags) -> (xy int32 [dots, 2], group int32 [dots], stats)   orip_svg_stipple
+    the rings are the fitted paths ring_sub with their fill groups, clamp = not --clip, rect = the sheet or the clip rectangle; info["stipple"] = the seven
+    counts of include/orip.h with the lattice, info["taps"] = the dots drawn.
     and, only with --loop-start:
       seam_fn                                      as in orip.gcode.build_stream_from_gcode (a circle, a <rect> and a closed <path> are closed strokes; hatch lines are open)
     With --pen-colors, info["path_pens"] is the pen of every fitted path (hatch lines included, --color-index where no stroke is stated).
@@ -1033,6 +1088,7 @@ def build_stream_from_svg(text: Union[str, bytes, SegmentTable], opts: Optional[
     t0 = time.perf_counter()
     hp = hatch_params(o)
     reach = hatch_connect_reach(o)
+    sp = stipple_params(o)
     if o.pen_colors is not None:
         parse_pen_colors(o.pen_colors)                      # a bad list ends the run before anything is parsed
     go = gcode_options(o)
@@ -1089,9 +1145,16 @@ def build_stream_from_svg(text: Union[str, bytes, SegmentTable], opts: Optional[
         lnk = GC.HatchLink(None if hatch_link_fn is None else (lambda off, pts, cls, rs, rg, m, clamp, r: hatch_link_fn(paths, off, pts, cls, rs, rg, m, clamp, r)),
                            hatch_classes(table, paths, info, hatch_groups_fn, off_mm, pts_mm, hp.get("u")), *hatch_link_rings(table), not o.clip, reach)
     sm = GC.Seam(seam_fn) if o.loop_start else None
-    steps, device = GC.resolve_steps(steps, go, pens_on or o.allow_reverse, device, force=bool(own), occlude=occ, dash=dsh, seam=sm, hatch_link=lnk,
+    stp = None
+    if sp is not None:
+        W, H = GC.target_size(go)
+        stp = GC.Stipple(None if stipple_fn is None else (lambda rs, rg, m, clamp, lat, inset, rect, flags: stipple_fn(paths, rs, rg, m, clamp, lat, inset, rect, flags)),
+                         *hatch_link_rings(table), not o.clip, sp["lattice"], sp["inset"], GC.clip_rect(go) or (0, 0, W - 1, H - 1),
+                         (0 if o.no_serpentine else GC.STIPPLE_SERPENTINE) | (GC.STIPPLE_OCCLUDE if o.occlude else 0),
+                         (lambda groups: hatch_pens(table, groups, info["pen_colors"])) if pens_on else None)
+    steps, device = GC.resolve_steps(steps, go, pens_on or o.allow_reverse, device, force=bool(own), occlude=occ, dash=dsh, seam=sm, hatch_link=lnk, stipple=stp,
                                      convert=lambda dev: lambda _off, _pts, m, *rect: (_Resident(dev).clip if rect else _Resident(dev).steps)(paths, m, *rect))
-    data, ginfo = GC.stroke_stream((off_mm, np.zeros((int(off_mm[-1]), 2))), go, device, steps, tm, pens, occ, dsh, seam=sm, hatch_link=lnk)
+    data, ginfo = GC.stroke_stream((off_mm, np.zeros((int(off_mm[-1]), 2))), go, device, steps, tm, pens, occ, dsh, seam=sm, hatch_link=lnk, stipple=stp)
     if "dash" in ginfo or ignored:                          # an ignored dash array is reported whether or not a pass ran: the stroke is solid, and the line says so
         ginfo["dash"] = dict(ginfo.get("dash", {}), ignored=ignored)
     return data, dict(ginfo, **info)
@@ -1155,6 +1218,11 @@ def build_stream_argparser() -> argparse.ArgumentParser:
     ap.add_argument("--hatch-connect", action="store_true", help="draw a hatch as zigzags: join consecutive hatch lines of one shape by straight links that lie wholly "
                                                                  "inside it, so the pen stays down; needs --hatch-spacing-mm; the G-code file is not changed")
     ap.add_argument("--hatch-connect-mm", type=float, default=None, help="the longest link (default: twice --hatch-spacing-mm); needs --hatch-connect")
+    ap.add_argument("--stipple-mm", type=float, default=None, help="fill the shapes --hatch-fill marks with dots (pen taps) this far apart, on one lattice for the whole "
+                                                                   "drawing; rounded to whole steps; the G-code file is not changed")
+    ap.add_argument("--stipple-inset-mm", type=float, default=None, help="how far every dot stays inside its shape's outline (default: 0.675, as --hatch-inset-mm); needs --stipple-mm")
+    ap.add_argument("--stipple-pattern", choices=STIPPLE_PATTERNS, default=None, help="square: rows a pitch apart; stagger (default): every other row moved by half a pitch, "
+                                                                                      "the rows 3547/4096 of a pitch apart; needs --stipple-mm")
     ap.add_argument("--no-preview", action="store_true", help="do not render <svg stem>_stream_preview.png")
     ap.add_argument("--preview-render-width", type=int, default=d.preview_render_width)
     ap.add_argument("--preview-render-height", type=int, default=d.preview_render_height)

@@ -203,7 +203,11 @@ int orip_dedup_cross_layer_deferred(orip_ctx* ctx, int src_layer, int layer);
  * UNPINNED, visual QA only (csrc/vector_preview.hip states what is drawn; oracle/oracle.py: preview_cover is the same, bit for bit). */
 int orip_preview_cover(orip_ctx* ctx, int slot, int layer, int taps_which, int W, int H, int thickness, int radius, int antialias, uint8_t* line_cov, uint8_t* tap_cov);
 /* ---- stage 12: _build_ops_for_layer (12:85-187): LINES/TAPS_CROSS -> ops ----
- * ops are returned as 5 int32 each: (type 0 line / 1 tap, line index into LINES_CROSS, flip, x, y). */
+ * ops are returned as 5 int32 each: (type 0 line / 1 tap, line index into LINES_CROSS, flip, x, y).
+ * Contract: every line's first and last point and every tap lies within +-16777216 (2^24) px on both axes, the range in which the reference's float32
+ * coordinates are exact; inside it every choice (nearest end or tap, ties by list order, taps within R_insert) is the reference's, at any distance.  A
+ * coordinate outside it is refused with an error and leaves no ops for the layer.  A line of fewer than two points is no op (12:95-96), so *n_ops is the
+ * number of lines with two points or more plus the number of taps. */
 int orip_plot_order(orip_ctx* ctx, int layer, double R_insert, int64_t* n_ops);
 int orip_get_ops(orip_ctx* ctx, int layer, int32_t* ops5);
 

@@ -93,18 +93,80 @@ extern "C" int orip_sort_contours(orip_ctx* c, int layer) {
 // Stage 12.  All positions are integers (line ends, tap centres), so every hypot comparison of the
 // reference is evaluated on exact squared distances; ties resolve in the reference's scan order
 // (line k start, line k end, ..., then taps).  One 1024-thread block per layer.
+//
+// Contract (include/orip.h): every line end and tap lies in +-ORIP_PLOT_COORD_MAX = 2^24, where the reference's float32 coordinates are
+// still exact; d^2 <= 2^51 there, so (double)d^2 and its sqrt in the drain are exact too.  Both kernels take the bounding box of the
+// line ends, the taps and (0, 0) while they load the lists (PlotBox): a box outside the contract ends the kernel with n_ops = -1, which
+// orip_plot_order reports as an error.  While 2 span^2 < 2^32 (span <= 46340, any canvas up to that side) d^2 and the candidate's index
+// share one 64-bit key and a choice is one minimum; beyond, the minimum of d^2 is taken first and the minimum index among the lanes
+// that hold it second (Best12 / nearest12).  Lines of fewer than two points are no ops (12:95-96): they are never alive.
 // ------------------------------------------------------------------------------------------------
+#define ORIP_PLOT_COORD_MAX (1 << 24)
 __device__ __forceinline__ long long d2i(long long ax, long long ay, long long bx, long long by) { return (ax - bx) * (ax - bx) + (ay - by) * (ay - by); }
+
+// box[]: min x, min y, max x, max y over the line ends, the taps and (0, 0), then the number of lines with two points or more; in LDS, zeroed before use
+enum { PB_X0, PB_Y0, PB_X1, PB_Y1, PB_LINES, PB_WORDS };
+struct PlotBox {
+    int x0 = 0, y0 = 0, x1 = 0, y1 = 0, lines = 0;          // one lane's share
+    __device__ __forceinline__ void add(int x, int y) { x0 = min(x0, x); y0 = min(y0, y); x1 = max(x1, x); y1 = max(y1, y); }
+    __device__ __forceinline__ void merge_into(int* box) const {
+        atomicMin(box + PB_X0, x0); atomicMin(box + PB_Y0, y0); atomicMax(box + PB_X1, x1); atomicMax(box + PB_Y1, y1); atomicAdd(box + PB_LINES, lines);
+    }
+};
+__device__ __forceinline__ bool plot_box_refused(const int* box) {
+    return box[PB_X0] < -ORIP_PLOT_COORD_MAX || box[PB_Y0] < -ORIP_PLOT_COORD_MAX || box[PB_X1] > ORIP_PLOT_COORD_MAX || box[PB_Y1] > ORIP_PLOT_COORD_MAX;
+}
+__device__ __forceinline__ bool plot_box_wide(const int* box) {         // d^2 can reach 2^32: the packed key would wrap
+    const long long span = max((long long)box[PB_X1] - box[PB_X0], (long long)box[PB_Y1] - box[PB_Y0]);
+    return 2 * span * span >= (1LL << 32);
+}
+// a lane's nearest candidate so far; candidates arrive in ascending index, so on equal d^2 the earlier one stays
+template <bool WIDE> struct Best12 {
+    unsigned long long d = ~0ULL; unsigned i = ~0u;
+    __device__ __forceinline__ void take(long long d2, unsigned idx) {
+        if (WIDE) { if ((unsigned long long)d2 < d) { d = (unsigned long long)d2; i = idx; } }
+        else { const unsigned long long key = ((unsigned long long)d2 << 32) | idx; if (key < d) d = key; }
+    }
+};
+// The nearest alive candidate to (px, py) over all lanes: index 2 k / 2 k + 1 for the start / end of line k, 2 nl + t for tap t, ~0u if none is alive.
+// min_all(v) is the minimum of v over every lane that takes part (all of them call it, in the same order).
+template <bool WIDE, class LineAt, class TapAt, class MinAll>
+__device__ __forceinline__ unsigned nearest12(int first, int stride, int nl, int nt, const uint8_t* aliveL, const uint8_t* aliveT, long long px, long long py,
+                                              LineAt line_at, TapAt tap_at, MinAll min_all) {
+    Best12<WIDE> b;
+    for (int k = first; k < nl; k += stride) {
+        if (!aliveL[k]) continue;
+        const int4 e = line_at(k);
+        b.take(d2i(px, py, e.x, e.y), (unsigned)(2 * k));
+        b.take(d2i(px, py, e.z, e.w), (unsigned)(2 * k + 1));
+    }
+    for (int t = first; t < nt; t += stride) {
+        if (!aliveT[t]) continue;
+        const int2 p = tap_at(t);
+        b.take(d2i(px, py, p.x, p.y), (unsigned)(2 * nl + t));
+    }
+    if (!WIDE) return (unsigned)min_all(b.d);                // an index never reaches ~0u (nl + nt < 2^30)
+    const unsigned long long m = min_all(b.d);
+    if (m == ~0ULL) return ~0u;
+    return (unsigned)min_all(b.d == m ? (unsigned long long)b.i : ~0ULL);
+}
 
 __global__ __launch_bounds__(1024) void k_plot_order(const PolyFeat* __restrict__ lf, int nl, const int32_t* __restrict__ taps, int nt, double R,
                                                       uint8_t* __restrict__ alive_l, uint8_t* __restrict__ alive_t, int32_t* __restrict__ ops, int* __restrict__ n_ops_out) {
     __shared__ unsigned long long wb[16];
-    __shared__ long long px, py; __shared__ int nops, cursor, found;
+    __shared__ long long px, py; __shared__ int nops, cursor, box[PB_WORDS];
     const int tid = threadIdx.x;
-    for (int i = tid; i < nl; i += 1024) alive_l[i] = 1;
-    for (int i = tid; i < nt; i += 1024) alive_t[i] = 1;
-    if (tid == 0) { px = 0; py = 0; nops = 0; }
+    if (tid == 0) { px = 0; py = 0; nops = 0; for (int q = 0; q < PB_WORDS; q++) box[q] = 0; }
     __syncthreads();
+    {
+        PlotBox pb;
+        for (int i = tid; i < nl; i += 1024) { const PolyFeat f = lf[i]; const int ok = f.n >= 2; alive_l[i] = (uint8_t)ok; pb.lines += ok; pb.add(f.sx, f.sy); pb.add(f.ex, f.ey); }
+        for (int i = tid; i < nt; i += 1024) { alive_t[i] = 1; pb.add(taps[2 * i], taps[2 * i + 1]); }
+        pb.merge_into(box);
+    }
+    __syncthreads();
+    if (plot_box_refused(box)) { if (tid == 0) *n_ops_out = -1; return; }
+    const bool wide = plot_box_wide(box);
     auto emit_line = [&](int k, int flip) { int o = nops++; ops[5 * o] = 0; ops[5 * o + 1] = k; ops[5 * o + 2] = flip; ops[5 * o + 3] = 0; ops[5 * o + 4] = 0; };
     auto emit_tap = [&](int t) { int o = nops++; ops[5 * o] = 1; ops[5 * o + 1] = -1; ops[5 * o + 2] = 0; ops[5 * o + 3] = taps[2 * t]; ops[5 * o + 4] = taps[2 * t + 1]; };
     auto block_min = [&](unsigned long long v) -> unsigned long long {
@@ -135,10 +197,11 @@ __global__ __launch_bounds__(1024) void k_plot_order(const PolyFeat* __restrict_
         }
         __syncthreads();
     };
-    if (nl > 0) {
+    if (box[PB_LINES] > 0) {
         // first = longest line (first maximum), entered from the end nearer to (0,0) (strict <)
         unsigned long long best = ~0ULL;
         for (int k = tid; k < nl; k += 1024) {
+            if (!alive_l[k]) continue;
             unsigned long long key = ((unsigned long long)(~__float_as_uint(lf[k].per)) << 32) | (unsigned)k;   // per >= 0: larger per -> smaller key
             if (key < best) best = key;
         }
@@ -152,37 +215,17 @@ __global__ __launch_bounds__(1024) void k_plot_order(const PolyFeat* __restrict_
         }
         __syncthreads();
         drain();
-    } else if (nt > 0) {
-        unsigned long long best = ~0ULL;
-        for (int t = tid; t < nt; t += 1024) {
-            unsigned long long key = ((unsigned long long)d2i(0, 0, taps[2 * t], taps[2 * t + 1]) << 32) | (unsigned)t;
-            if (key < best) best = key;
-        }
-        unsigned long long b = block_min(best);
-        if (tid == 0) { int t = (int)(b & 0xffffffffu); emit_tap(t); alive_t[t] = 0; px = taps[2 * t]; py = taps[2 * t + 1]; }
-        __syncthreads();
-    }
-    const int total = nl + nt;
+    }           // no line of two points: the first op is the tap nearest to (0, 0), lowest index first, which is the loop's own rule from the start position
+    const int total = box[PB_LINES] + nt;
+    auto line_at = [&](int k) { return make_int4(lf[k].sx, lf[k].sy, lf[k].ex, lf[k].ey); };
+    auto tap_at = [&](int t) { return make_int2(taps[2 * t], taps[2 * t + 1]); };
     while (true) {
         __syncthreads();
         if (nops >= total) break;
-        long long x = px, y = py;
-        unsigned long long best = ~0ULL;
-        for (int k = tid; k < nl; k += 1024) {
-            if (!alive_l[k]) continue;
-            unsigned long long k1 = ((unsigned long long)d2i(x, y, lf[k].sx, lf[k].sy) << 32) | (unsigned)(2 * k);
-            unsigned long long k2 = ((unsigned long long)d2i(x, y, lf[k].ex, lf[k].ey) << 32) | (unsigned)(2 * k + 1);
-            if (k1 < best) best = k1;
-            if (k2 < best) best = k2;
-        }
-        for (int t = tid; t < nt; t += 1024) {
-            if (!alive_t[t]) continue;
-            unsigned long long kt = ((unsigned long long)d2i(x, y, taps[2 * t], taps[2 * t + 1]) << 32) | (unsigned)(2 * nl + t);
-            if (kt < best) best = kt;
-        }
-        unsigned long long b = block_min(best);
-        if (b == ~0ULL) break;
-        unsigned idx = (unsigned)(b & 0xffffffffu);
+        const long long x = px, y = py;
+        const unsigned idx = wide ? nearest12<true>(tid, 1024, nl, nt, alive_l, alive_t, x, y, line_at, tap_at, block_min)
+                                  : nearest12<false>(tid, 1024, nl, nt, alive_l, alive_t, x, y, line_at, tap_at, block_min);
+        if (idx == ~0u) break;
         bool is_line = idx < (unsigned)(2 * nl);
         if (tid == 0) {
             if (is_line) {
@@ -198,7 +241,6 @@ __global__ __launch_bounds__(1024) void k_plot_order(const PolyFeat* __restrict_
         if (is_line) drain();
     }
     if (tid == 0) *n_ops_out = nops;
-    (void)found;
 }
 
 // minimum of a 64-bit key over the wavefront with DPP row shifts / broadcasts (no LDS round trips); every lane gets the result
@@ -222,11 +264,20 @@ __global__ __launch_bounds__(64) void k_plot_order_wave(const PolyFeat* __restri
     int4* E = reinterpret_cast<int4*>(smem);                       // (sx, sy, ex, ey)
     int2* T = reinterpret_cast<int2*>(E + nl);
     uint8_t* aliveL = reinterpret_cast<uint8_t*>(T + nt); uint8_t* aliveT = aliveL + nl;
-    __shared__ int ring[64 * 5];
+    __shared__ int ring[64 * 5], box[PB_WORDS];
     const int lane = threadIdx.x;
-    for (int i = lane; i < nl; i += 64) { PolyFeat f = lf[i]; E[i] = make_int4(f.sx, f.sy, f.ex, f.ey); aliveL[i] = 1; }
-    for (int i = lane; i < nt; i += 64) { T[i] = make_int2(taps[2 * i], taps[2 * i + 1]); aliveT[i] = 1; }
+    if (lane < PB_WORDS) box[lane] = 0;
     __syncthreads();
+    {
+        PlotBox pb;
+        for (int i = lane; i < nl; i += 64) { PolyFeat f = lf[i]; const int ok = f.n >= 2; E[i] = make_int4(f.sx, f.sy, f.ex, f.ey); aliveL[i] = (uint8_t)ok; pb.lines += ok; pb.add(f.sx, f.sy); pb.add(f.ex, f.ey); }
+        for (int i = lane; i < nt; i += 64) { const int2 p = make_int2(taps[2 * i], taps[2 * i + 1]); T[i] = p; aliveT[i] = 1; pb.add(p.x, p.y); }
+        pb.merge_into(box);
+    }
+    __syncthreads();
+    if (plot_box_refused(box)) { if (lane == 0) *n_ops_out = -1; return; }
+    const bool wide = plot_box_wide(box);
+    const int n_lines = box[PB_LINES];
     long long px = 0, py = 0; int nops = 0;
     auto emit = [&](int type, int k, int flip, int x, int y) {
         if (lane == 0) { int* r = ring + 5 * (nops & 63); r[0] = type; r[1] = k; r[2] = flip; r[3] = x; r[4] = y; }
@@ -250,10 +301,11 @@ __global__ __launch_bounds__(64) void k_plot_order_wave(const PolyFeat* __restri
             px = p.x; py = p.y; cursor = found + 1;
         }
     };
-    if (nl > 0) {
+    if (n_lines > 0) {
         // first = longest line (first maximum), entered from the end nearer to (0,0) (strict <)
         unsigned long long best = ~0ULL;
         for (int k = lane; k < nl; k += 64) {
+            if (!aliveL[k]) continue;
             unsigned long long key = ((unsigned long long)(~__float_as_uint(lf[k].per)) << 32) | (unsigned)k;   // per >= 0: larger per -> smaller key
             if (key < best) best = key;
         }
@@ -265,40 +317,15 @@ __global__ __launch_bounds__(64) void k_plot_order_wave(const PolyFeat* __restri
         emit(0, k, flip, 0, 0);
         if (flip) { px = e.x; py = e.y; } else { px = e.z; py = e.w; }
         drain();
-    } else if (nt > 0) {
-        unsigned long long best = ~0ULL;
-        for (int t = lane; t < nt; t += 64) {
-            const int2 p = T[t];
-            unsigned long long key = ((unsigned long long)d2i(0, 0, p.x, p.y) << 32) | (unsigned)t;
-            if (key < best) best = key;
-        }
-        best = wave_min_key(best);
-        const int t = (int)(best & 0xffffffffu);
-        const int2 p = T[t];
-        if (lane == 0) aliveT[t] = 0;
-        emit(1, -1, 0, p.x, p.y);
-        px = p.x; py = p.y;
-    }
-    const int total = nl + nt;
+    }           // no line of two points: the first op is the tap nearest to (0, 0), lowest index first, which is the loop's own rule from the start position
+    const int total = n_lines + nt;
+    auto line_at = [&](int k) { return E[k]; };
+    auto tap_at = [&](int t) { return T[t]; };
+    auto wave_min = [](unsigned long long v) { return wave_min_key(v); };
     while (nops < total) {
-        unsigned long long best = ~0ULL;
-        for (int k = lane; k < nl; k += 64) {
-            if (!aliveL[k]) continue;
-            const int4 e = E[k];
-            unsigned long long k1 = ((unsigned long long)d2i(px, py, e.x, e.y) << 32) | (unsigned)(2 * k);
-            unsigned long long k2 = ((unsigned long long)d2i(px, py, e.z, e.w) << 32) | (unsigned)(2 * k + 1);
-            if (k1 < best) best = k1;
-            if (k2 < best) best = k2;
-        }
-        for (int t = lane; t < nt; t += 64) {
-            if (!aliveT[t]) continue;
-            const int2 p = T[t];
-            unsigned long long kt = ((unsigned long long)d2i(px, py, p.x, p.y) << 32) | (unsigned)(2 * nl + t);
-            if (kt < best) best = kt;
-        }
-        best = wave_min_key(best);
-        if (best == ~0ULL) break;
-        const unsigned idx = (unsigned)(best & 0xffffffffu);
+        const unsigned idx = wide ? nearest12<true>(lane, 64, nl, nt, aliveL, aliveT, px, py, line_at, tap_at, wave_min)
+                                  : nearest12<false>(lane, 64, nl, nt, aliveL, aliveT, px, py, line_at, tap_at, wave_min);
+        if (idx == ~0u) break;
         if (idx < (unsigned)(2 * nl)) {
             const int k = (int)(idx >> 1), flip = (int)(idx & 1u);
             const int4 e = E[k];
@@ -351,6 +378,7 @@ extern "C" int orip_plot_order(orip_ctx* c, int layer, double R_insert, int64_t*
     HIPC(c, hipGetLastError());
     int h = 0;
     ORIP_TRY(vread(c, &h, d_n));
+    if (h < 0) ORIP_FAIL(c, "orip_plot_order: a line end or a tap of layer %d lies outside the stage's range of +-%d (2^24) px", layer, ORIP_PLOT_COORD_MAX);
     c->n_ops[layer] = h; *n_ops = h;
     return 0;
 }

@@ -421,13 +421,18 @@ def stage10_layer(lines_in, taps_in, forbidden, prm=None):
     return lo.get(), to.get()
 
 
-def build_ops12(lines, taps, R_insert=80.0) -> List[dict]:
+def ops12_raw(lines, taps, R_insert=80.0) -> np.ndarray:
+    """the op rows of stage 12 as the device returns them: int32 [n, 5] of (type 0 line / 1 tap, line index or -1, flip, tap x, tap y)"""
     li, ti = PL(lines), TL(taps)
     cap = len(lines) + len(taps) + 1
     out = np.zeros((cap, 5), np.int32)
     m = lib().orc_build_ops12(li.h, ti.h, float(R_insert), _p(out), cap)
+    return out[:m]
+
+
+def build_ops12(lines, taps, R_insert=80.0) -> List[dict]:
     ops = []
-    for t, idx, flip, x, y in out[:m]:
+    for t, idx, flip, x, y in ops12_raw(lines, taps, R_insert):
         if t == 0:
             p = np.asarray(lines[idx]).reshape(-1, 2).astype(np.float32)
             ops.append({"type": "line", "points": p[::-1].copy() if flip else p})

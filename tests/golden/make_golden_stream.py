@@ -8,6 +8,7 @@ does not take: the stand-in of this directory is registered as `cv2`), so every 
   * poly*      : bytes of emit_polyline for random polylines with sharp corners, short and long edges, repeated points, both ramp profiles
   * e2e_{a,b}* : plot_stream.bin / plot_stream.json of 13_build_stream.main() on the ops of golden_e2e_{a,b}.npz, plus a colour-remap variant
   * golden_stream_edges.npz (write_edges): the same two files for a hand-written plot of edge cases, with its ops
+  * golden_stream_long.npz (write_long): 52 segments of 46 341 to 200 000 steps and the sha256 of bresenham_dir_codes on each
 Nothing from the reference is copied: the fixture holds arrays only.   Usage: python tests/golden/make_golden_stream.py
 """
 from __future__ import annotations
@@ -98,6 +99,31 @@ def main():
     np.savez_compressed(os.path.join(HERE, "golden_stream.npz"), **g)
     print("golden_stream.npz:", len(g), "arrays;", {k: int(v.size) for k, v in g.items() if k.endswith("_bin")})
     write_edges(m13)
+    write_long()
+
+
+LONG_PAIRS = [(70000, 69999), (70000, 35000), (70001, 35000), (99999, 1), (1, 99999), (131072, 65536), (131071, 3), (100000, 50000), (100000, 49999), (65537, 65536),
+              (200000, 100000), (46341, 46340), (92682, 46341)]
+
+
+def long_segments():
+    """every (dx, dy) of LONG_PAIRS in the four sign combinations; an axis that rises starts at 0, one that falls at 2^30, so every coordinate lies in 0 .. 2^30.
+    Exact ties of the error term (dy = dx / 2), near-diagonals, and 2 (k + 1) minor at or beyond 2^31 on more than half of the steps"""
+    A = 1 << 30
+    return np.array([(0 if sx > 0 else A, 0 if sy > 0 else A, dx if sx > 0 else A - dx, dy if sy > 0 else A - dy)
+                     for dx, dy in LONG_PAIRS for sx in (1, -1) for sy in (1, -1)], np.int32)
+
+
+def write_long():
+    """golden_stream_long.npz: the long segments and the sha256 of each one's bresenham_dir_codes (as uint8 bytes, one code a byte); the codes themselves are 5 MB"""
+    import hashlib
+    segs = long_segments()
+    dig = np.zeros((len(segs), 32), np.uint8); cnt = np.zeros(len(segs), np.int64)
+    for i, s in enumerate(segs):
+        c = np.array(RH.bresenham_dir_codes(*(int(v) for v in s)), np.uint8)
+        cnt[i] = len(c); dig[i] = np.frombuffer(hashlib.sha256(c.tobytes()).digest(), np.uint8)
+    np.savez_compressed(os.path.join(HERE, "golden_stream_long.npz"), long_segs=segs, long_steps=cnt, long_sha256=dig)
+    print("golden_stream_long.npz:", len(segs), "segments,", int(cnt.sum()), "steps")
 
 
 def run_main(m13, cfg, man, layers, env):

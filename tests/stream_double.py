@@ -1,5 +1,6 @@
 """TEST INFRASTRUCTURE: numpy stand-in for orip_stream_codes (the HIP kernel) so that the host logic of orip/stream.py can be checked on the CPU
-against the reference's golden bytes.  Same closed form as csrc/stream.hip; itself pinned by the `bres*` golden vectors.  Also two independent checks
+against the reference's golden bytes.  Same closed form as csrc/stream.hip; itself pinned by the `bres*` golden vectors and, on segments of up to 200 000 steps, by the
+digests of golden_stream_long.npz.  Also two independent checks
 that once were the product's own code: a vectorised packer of a piece table (fill_bytes) and the corner flags of ONE polyline (corner_flags)."""
 import math
 

@@ -50,6 +50,53 @@ def test_direction_codes_large_random_vs_closed_form(dev):
     assert np.array_equal(ex, (moves[:, 2] - moves[:, 0])[nz]) and np.array_equal(ey, (moves[:, 3] - moves[:, 1])[nz])
 
 
+def _replayed_ends(moves, off, codes):
+    """(dx, dy) reached by replaying each move's codes, for the moves that have steps"""
+    DX = np.array([0, 1, 1, 1, 0, -1, -1, -1]); DY = np.array([1, 1, 0, -1, -1, -1, 0, 1])
+    nz = np.diff(off) > 0
+    return nz, np.add.reduceat(DX[codes], off[:-1][nz]), np.add.reduceat(DY[codes], off[:-1][nz])
+
+
+def test_direction_codes_long_segments(dev):
+    """golden_stream_long.npz: 52 segments of 46 341 to 200 000 steps in 0 .. 2^30, 2 (k + 1) minor at or past 2^31 on more than half of the 5.1 M steps, exact ties
+    of the error term.  The double is pinned to the reference on these by test_stream_host.py; the kernel equals the double, and the codes lead to the end points"""
+    from test_stream_host import long_codes
+    segs, o2, c2 = long_codes()
+    off, codes = dev.stream_codes(segs)
+    assert np.array_equal(off, o2) and np.array_equal(codes, c2)
+    nz, ex, ey = _replayed_ends(segs, off, codes)
+    m = segs.astype(np.int64)
+    assert nz.all() and np.array_equal(ex, m[:, 2] - m[:, 0]) and np.array_equal(ey, m[:, 3] - m[:, 1])
+
+
+def _edge_batches():
+    Z = [7, 7, 7, 7]                                                                          # a move without steps
+    b = {}
+    for total in (255, 256, 257, 512):                                                        # the last block's `t >= total` guard, one move and three
+        b["one_%d" % total] = [[0, 0, total, 3]]
+        b["three_%d" % total] = [[4, 9, 104, 2], [104, 2, 104, 2 + total - 150], [104, 2, 54, 40]]
+    b["one_step"] = [[3, 3, 3, 4]]
+    long_a, long_b, long_c = [0, 0, 900, 301], [900, 301, 13, 1200], [13, 1200, 640, 0]
+    b["zero_runs"] = [Z] + [long_a] + [Z] + [long_b] + [Z, Z] + [long_c] + [Z] * 300 + [long_a] + [Z]      # first and last without steps; runs of 1, 2 and 300 in between
+    return {k: np.array(v, np.int64) for k, v in b.items()}
+
+
+@pytest.mark.parametrize("anchor", [0, -(1 << 31), (1 << 31) - 1 - 100000], ids=["origin", "int32_min", "int32_max_less_100000"])
+def test_direction_codes_search_and_launch_edges(dev, anchor):
+    """totals of 255, 256, 257 and 512 steps, n = 1, moves without steps in front, at the end and in runs of 1, 2 and 300 between long ones (the search must land on
+    the last off[i] <= t), and all of it again at the two ends of int32: only the position is extreme there, so the codes are those at the origin"""
+    for name, base in _edge_batches().items():
+        moves = (base + anchor).astype(np.int32)
+        assert np.array_equal(moves.astype(np.int64) - anchor, base)                          # inside int32
+        o2, c2 = codes_numpy(base)
+        if name[-3:].isdigit():
+            assert int(o2[-1]) == int(name[-3:])                                              # the total the batch is named after
+        off, codes = dev.stream_codes(moves)
+        assert np.array_equal(off, o2) and np.array_equal(codes, c2), name
+        nz, ex, ey = _replayed_ends(base, off, codes)
+        assert np.array_equal(ex, (base[:, 2] - base[:, 0])[nz]) and np.array_equal(ey, (base[:, 3] - base[:, 1])[nz]), name
+
+
 @pytest.mark.parametrize("tag", ["a", "b"])
 def test_whole_stream_on_device_matches_reference(dev, tag):
     """direction codes and packing both on the device"""

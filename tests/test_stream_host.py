@@ -24,6 +24,39 @@ def test_double_matches_reference_bresenham():
     assert np.array_equal(off, G["bres_off"]) and np.array_equal(codes, G["bres_codes"])
 
 
+LONG_PAIRS = [(70000, 69999), (70000, 35000), (70001, 35000), (99999, 1), (1, 99999), (131072, 65536), (131071, 3), (100000, 50000), (100000, 49999), (65537, 65536),
+              (200000, 100000), (46341, 46340), (92682, 46341)]
+_LONG = {}
+
+
+def long_codes():
+    """(segments int32 [52, 4], off, codes) of golden_stream_long.npz by the double, computed once and left unchanged"""
+    if not _LONG:
+        segs = load("golden_stream_long.npz")["long_segs"]
+        off, codes = codes_numpy(segs)
+        codes.setflags(write=False); off.setflags(write=False)
+        _LONG["v"] = (segs, off, codes)
+    return _LONG["v"]
+
+
+def test_double_matches_reference_bresenham_on_long_segments():
+    """segments of 46 341 to 200 000 steps, where 2 (k + 1) minor passes 2^31: the closed form against the sha256 of the reference's serial bresenham_dir_codes
+    (tests/golden/make_golden_stream.py: write_long; the codes themselves are 5 MB)"""
+    import hashlib
+    L = load("golden_stream_long.npz")
+    segs, off, codes = long_codes()
+    # the fixture is the set it is meant to be: every pair in the four sign combinations, inside 0 .. 2^30
+    d = segs[:, 2:].astype(np.int64) - segs[:, :2]
+    assert [tuple(int(v) for v in r) for r in np.abs(d)[::4]] == LONG_PAIRS and len(segs) == 4 * len(LONG_PAIRS) == 52
+    assert all(sorted((int(np.sign(x)), int(np.sign(y))) for x, y in d[i:i + 4]) == [(-1, -1), (-1, 1), (1, -1), (1, 1)] for i in range(0, 52, 4))
+    assert (np.abs(d)[np.arange(52) // 4 * 4] == np.abs(d)).all() and segs.min() == 0 and segs.max() == 1 << 30
+    assert np.array_equal(np.diff(off), L["long_steps"]) and off[-1] == 5106808
+    k = np.arange(int(off[-1])) - np.repeat(off[:-1], np.diff(off))
+    assert (2 * (k + 1) * np.repeat(np.abs(d).min(1), np.diff(off)) >= 1 << 31).sum() > 2_500_000          # products a 32-bit int does not hold
+    for i in range(52):
+        assert hashlib.sha256(codes[off[i]:off[i + 1]].tobytes()).digest() == L["long_sha256"][i].tobytes(), segs[i]
+
+
 def _bytes(ST, P, sc, pack_fn=pack_numpy, initial_div=None):
     data, _, _ = ST.compile_plan(P, sc, codes_fn=codes_numpy, pack_fn=pack_fn, initial_div=initial_div)
     return np.frombuffer(data, np.uint8)

@@ -17,7 +17,7 @@
 //   ORIP_NO_CHAINS         per-pixel stepping of the walker           chains shorter than ORIP_CHAIN_MIN
 //   ORIP_TRACE_LATE        traces started by orip_contours_layer      a lane held by another thread
 //   ORIP_PAINT_SEPARABLE   separable line painting in stage 10        its radius and size conditions
-// Debug and test hooks, which change no result: ORIP_CAPS_TINY, ORIP_CAPSSET_TINY, ORIP_CAPS_RANGE, ORIP_COMP_CAPS, ORIP_TIME08, ORIP_TIME10, ORIP_WALK_DBG, ORIP_NN_DBG2, ORIP_TAIL_DBG,
+// Debug and test hooks, which change no result: ORIP_CAPS_TINY, ORIP_CAPSSET_TINY, ORIP_CAPS_RANGE, ORIP_COMP_CAPS, ORIP_COMP_DBG, ORIP_TIME08, ORIP_TIME10, ORIP_WALK_DBG, ORIP_NN_DBG2, ORIP_TAIL_DBG,
 // ORIP_ALLOC_DBG, ORIP_TRACE_LOG_F, ORIP_SERIAL_LAYERS.
 
 #include <hip/hip_runtime.h>
@@ -169,6 +169,8 @@ struct LaneFlags {
     unsigned comp_counts[3];                                // 08-B: work-list cursors of the three component classes
     int taps_kept;                                          // 10 (ORIP_LANE_CROSS): sequential taps accepted
     int plot_ops;                                           // 12: ops written
+    // (last, so that the words above keep their offsets: a fill of a word range costs one dispatch more when the range leaves its 16-byte alignment)
+    alignas(8) unsigned long long tail_dbg[4];              // 08-A3: ORIP_TAIL_DBG counters of k_tail_replay (side stream; cleared in front of it, written only with the variable set)
 };
 static_assert(sizeof(LaneFlags) <= 4096, "LaneRes::flags is 4096 bytes, allocated and zeroed by orip_create");
 
@@ -212,7 +214,7 @@ static_assert(sizeof(LaneFlags) <= 4096, "LaneRes::flags is 4096 bytes, allocate
 //                         slot behind ev4 only; the two meet in practice behind several host round trips of split_small, but no event orders them
 //   08-A (vector08a.hip)  VTL_FEAT A0 -> k_rank_counts (across split_small, vsort_pairs, vscan_excl); VTL_RANKS A1 -> A6; VTL_CUM A2 (k_samples reads it last);
 //                         VTL_SAMPLES, VTL_CELLS, canvas, pixbits A2 -> A6, VTL_SAMPLES on through orip_runs_to_polys (its sx, sy and sflag are the input);
-//                         VTL_RANKS also holds the redo flags of A3 (nk + 1 words behind RsInfo), which the side stream reads until ev3 (awaited by A5);
+//                         VTL_RANKS also holds the redo marks of A3 (nk + 1 words behind RsInfo: 1 + the last unsure sample), which the side stream reads until ev3 (awaited by A5);
 //                         VTL_TAIL_RUNS A2 -> A6: the block-local tail sums (8 MS bytes; k_samples -> k_tail_par), then the last-in scan and then the
 //                         survivors in its first 4 MS bytes, and orip_runs_to_polys takes the slot once A6 is enqueued;
 //                         VTL_CAPS A4; A7's split_small finds everything but tp[] free

@@ -12,6 +12,7 @@
 // (a1_order .. a56_accept) and dedup08_a, which calls them in order.  This is the one unit of stage 08 that calls rocPRIM directly (the last-in scan by key of
 // A3, the segmented sort of A5).
 #include "vec08.h"
+#include "tail_window.h"
 #include <rocprim/rocprim.hpp>
 #include <type_traits>
 #include <vector>
@@ -522,20 +523,42 @@ __device__ __forceinline__ double dpp_shr1_f64(double v) {
     const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), 0x138, 0xf, 0xf, true);
     return __hiloint2double(hi, lo);
 }
-__global__ __launch_bounds__(64) void k_tail_replay(const unsigned* __restrict__ sbase, int64_t n_rank, double T, SampleArrs A, unsigned* __restrict__ npop, const unsigned* __restrict__ only) {
+// inclusive scan of increment pairs over the wave (tw_compose is associative, the earlier lanes' pair goes first); lanes a DPP pattern leaves out receive (0, 0),
+// the identity.  The same six steps as wave_incl_scan_u32.
+template <int CTRL, int ROWMASK>
+__device__ __forceinline__ void wave_tw_step(TwInc& f) {
+    auto sh = [](long long x) -> long long {
+        const int lo = __builtin_amdgcn_update_dpp(0, (int)(unsigned)((unsigned long long)x & 0xffffffffull), CTRL, ROWMASK, 0xf, false);
+        const int hi = __builtin_amdgcn_update_dpp(0, (int)(unsigned)((unsigned long long)x >> 32), CTRL, ROWMASK, 0xf, false);
+        return (long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo);
+    };
+    TwInc p; p.ev = sh(f.ev); p.od = sh(f.od);
+    f = tw_compose(p, f);
+}
+__device__ __forceinline__ void wave_incl_scan_tw(TwInc& f) {
+    wave_tw_step<0x111, 0xf>(f); wave_tw_step<0x112, 0xf>(f); wave_tw_step<0x114, 0xf>(f); wave_tw_step<0x118, 0xf>(f);      // row_shr 1, 2, 4, 8
+    wave_tw_step<0x142, 0xa>(f); wave_tw_step<0x143, 0xc>(f);                                                                    // row_bcast 15, 31
+}
+// `only` (k_tail_par's marks): a polyline is replayed from its first sample to its last unsure one and no further -- the samples behind it keep k_tail_par's
+// heads, which are the reference's (the argument stands at k_tail_par).  Without it (ORIP_TAIL_SEQ) every polyline is replayed to its end.
+// dbg (ORIP_TAIL_DBG only): {rounds, samples committed by rounds, samples decided by the plain loop, rounds in the integer form}, added to once per polyline.
+__global__ __launch_bounds__(64) void k_tail_replay(const unsigned* __restrict__ sbase, int64_t n_rank, double T, SampleArrs A, unsigned* __restrict__ npop, const unsigned* __restrict__ only,
+                                                    unsigned long long* __restrict__ dbg) {
     constexpr unsigned C = 1024u, RM = 2u * C - 1u;          // distances of the current chunk of C samples and of the one before it stay in LDS
     __shared__ double ops[64], rr[64];
     __shared__ double Dl[2 * C];
     __shared__ unsigned NPl[C];
     const int lane = threadIdx.x;
     for (int64_t r = blockIdx.x; r < n_rank; r += gridDim.x) {
-        if (only && !only[r]) continue;
+        const unsigned stop = only ? only[r] : 0xffffffffu;      // 1 + the last unsure sample
+        if (!stop) continue;
         const unsigned b = sbase[r], e = sbase[r + 1];
         if (e <= b) continue;
         const double* D = A.dprev + b; unsigned* NP = npop + b;
-        const unsigned m = e - b;
+        const unsigned m = e - b, me = min(m, stop);          // samples me .. m - 1 are read (distances, predictions) and never written
         unsigned head = 0; double racc = 0.0;
         unsigned j0 = 0, cb = 0;
+        unsigned n_rounds = 0, n_round_smp = 0, n_plain = 0, n_exact = 0;
         // one memory round trip per chunk: 32 independent loads per lane in flight, then the LDS writes (a load inside the rounds below
         // would cost the lone wave a round trip per 64 operations: most of the kernel's time)
         auto fill = [&](unsigned c0) {
@@ -551,12 +574,13 @@ __global__ __launch_bounds__(64) void k_tail_replay(const unsigned* __restrict__
             if (s > head) racc = __dadd_rn(racc, dist(s));
             while (head <= s && racc > T) { head++; if (head <= s) racc = __dsub_rn(racc, dist(head)); else racc = 0.0; }
             if (lane == 0) NP[s] = head;
+            n_plain++;
         };
         fill(0);
         __syncthreads();
-        while (j0 < m) {
+        while (j0 < me) {
             if (j0 >= cb + C) { __syncthreads(); cb += C; fill(cb); __syncthreads(); }
-            const unsigned s = j0 + (unsigned)lane; const bool valid = s < m && s < cb + C;
+            const unsigned s = j0 + (unsigned)lane; const bool valid = s < me && s < cb + C;
             unsigned hp = valid ? NPl[s & (C - 1u)] : 0u;
             hp = hp > head ? hp : head;
             hp = wave_incl_scan_max_u32(hp);                                               // heads never move back: running maximum (DPP steps: a ds_bpermute
@@ -576,10 +600,25 @@ __global__ __launch_bounds__(64) void k_tail_replay(const unsigned* __restrict__
             }
             __syncthreads();
             const double v = (unsigned)lane < total ? ops[lane] : 0.0;
-            double d = lane == 0 ? __dadd_rn(racc, v) : v;
-            double pre = d;
+            // The running values after every operation.  First the integer form (tail_window.h): inside the binade of racc an operation is an increment of
+            // racc / ulp that depends on nothing but the parity of the value it meets, so the window is one scan of increment pairs; it holds when every
+            // partial sum stays strictly inside the binade.  Otherwise (the first windows of a polyline, a tail length at a power of two) the real additions:
+            // 63 wave-shifted adds, lane i final after step i.
+            double pre; bool exact = false;
+            { int fe; long long fP;
+              if (tw_frame(racc, fe, fP)) {
+                  TwInc f; const bool fine = tw_inc(v, fe, f);
+                  wave_incl_scan_tw(f);
+                  const long long S = tw_apply(fP, f);
+                  exact = !__ballot((unsigned)lane < total && !(fine && tw_inside(S)));
+                  pre = tw_value(S, fe);                                                   // (lanes at and beyond `total` are never read)
+              } }
+            if (!exact) {
+                const double d = lane == 0 ? __dadd_rn(racc, v) : v;
+                pre = d;
 #pragma unroll
-            for (int q = 1; q < 64; q++) pre = __dadd_rn(dpp_shr1_f64(pre), d);
+                for (int q = 1; q < 64; q++) pre = __dadd_rn(dpp_shr1_f64(pre), d);
+            } else n_exact++;
             rr[lane] = pre;
             __syncthreads();
             bool bad = false;
@@ -596,9 +635,10 @@ __global__ __launch_bounds__(64) void k_tail_replay(const unsigned* __restrict__
                 racc = rr[last_op];
             }
             __syncthreads();
-            j0 += (unsigned)ncommit;
+            j0 += (unsigned)ncommit; n_rounds++; n_round_smp += (unsigned)ncommit;
             if (badm) { plain(j0); j0++; }
         }
+        if (dbg && lane == 0) { atomicAdd(&dbg[0], (unsigned long long)n_rounds); atomicAdd(&dbg[1], (unsigned long long)n_round_smp); atomicAdd(&dbg[2], (unsigned long long)n_plain); atomicAdd(&dbg[3], (unsigned long long)n_exact); }
         __syncthreads();
     }
 }
@@ -620,10 +660,17 @@ __global__ __launch_bounds__(64) void k_tail_replay(const unsigned* __restrict__
 // a comparison that clears the threshold by more than ORIP_TAIL_EPS is the reference's decision, whatever the order of summation.
 // Any sample that is closer marks its polyline, so does one whose search would go back over more than ORIP_TAIL_BLOCKS block sums, and marked polylines are
 // redone by the sequential simulation (k_tail_replay) from the exact distances: the rounding of these sums decides which polylines are redone, never a result.
+// The mark is redo[r] = 1 + the local index of the polyline's LAST unsure sample (0: none), and the replay stops behind that sample.  A sure sample j with
+// head h here has sum(h+1..j) <= T - EPS and, for h > b, sum(h..j) > T + EPS in real numbers, up to 3e-8.  The reference enters j with the head h' it left at
+// j - 1, and h' <= h: to have passed h it would have needed its running value over h+1..j-1 above T, but that sum is no larger than sum(h+1..j) <= T - EPS and
+// the reference's value lies within 3e-8 of it WHATEVER pops and pushes came before (that bound is over the history's length, not its content).  At j it then
+// pops while its value over head+1..j exceeds T: every head below h gives a sum >= sum(h..j) > T + EPS, so it pops; at h the sum is <= T - EPS, so it stops.
+// The reference's head at a sure sample is h, also where an unsure sample before it left the reference's head one ahead of the parallel one (h' = h, no pop
+// at j, against one pop here: the same head, and only heads are kept).  So behind the last unsure sample the npop written here are the reference's.
 #define ORIP_TAIL_EPS 1e-6
 #define ORIP_TAIL_BLOCKS 32u
 __global__ __launch_bounds__(256) void k_tail_par(const unsigned* __restrict__ sbase, const unsigned* __restrict__ rank, const double* __restrict__ Sloc, unsigned MS, double T,
-                                                   unsigned* __restrict__ npop, unsigned* __restrict__ redo) {
+                                                   unsigned* __restrict__ npop, unsigned* __restrict__ redo, unsigned* __restrict__ dbg_first) {
     __shared__ double win[512];
     const unsigned g0 = blockIdx.x * 256, w0 = g0 >= 256 ? g0 - 256 : 0;      // window = samples w0 .. g0 + 255
     const unsigned KB = g0 / ORIP_SMP_BLOCK, B0 = KB * ORIP_SMP_BLOCK;         // the tail block lies inside block KB of k_samples, which starts at sample B0
@@ -671,7 +718,10 @@ __global__ __launch_bounds__(256) void k_tail_par(const unsigned* __restrict__ s
     if (!(tail(h) <= T - ORIP_TAIL_EPS)) unsure = true;
     if (h > b && !(tail(h - 1) > T + ORIP_TAIL_EPS)) unsure = true;
     npop[g] = h - b;
-    if (unsure) redo[r] = 1u;
+    if (unsure) {
+        atomicMax(&redo[r], 1u + (g - b));                    // (k_rank_counts left 0)
+        if (dbg_first) atomicMin(&dbg_first[r], g - b);       // ORIP_TAIL_DBG only
+    }
 }
 // previous in-canvas sample of the same polyline (the far end of the capsule stamped when sample j is popped, 08:151-155); -1: none, -2: j is off-canvas
 // lastin[g] = 1 + index of the last in-canvas sample at or before g inside its polyline (0: none): a max-scan by polyline
@@ -1112,7 +1162,7 @@ struct A08 {
     // The any-out word, sbase[nk + 1], is cleared by k_fill_per (first kernel of A1, right behind the carve) and set by k_rank_counts (A2); in between run the
     // perimeter sort (its own four arrays and tmpF) and the cumulative lengths (VTL_CUM, info, or the prefetch's buffers): nothing touches the word, and the side
     // stream has no work of this call yet.  The read-back behind the scan of mr is its only reader.
-    unsigned* redo;                                                 // VTL_RANKS too: nk + 1 flags, polylines the sequential simulation redoes.  Cleared by k_rank_counts (A2); set
+    unsigned* redo;                                                 // VTL_RANKS too: nk + 1 words, 1 + the last sample the sequential simulation redoes (0: none).  Cleared by k_rank_counts (A2); set
     // by k_tail_par (A3), read by k_tail_replay on the side stream until ev3, which A5 awaits; between clearing and setting run the scan of mr, k_sample_hints and
     // k_samples, which take mr, sbase, info, ord of this slot and never redo, and nothing of this call on the side stream.  VTL_RANKS stays until A6.
     double step; int64_t* cumoff; float* cum;                       // VTL_CUM, or the prefetch's cum: cumulative lengths and where each polyline's start
@@ -1177,29 +1227,51 @@ static int a2_resample(orip_ctx* c, const orip_params08& P, DPolys& kept0, A08& 
     return 0;
 }
 // ORIP_TAIL_DBG (debug): how much of the layer the sequential tail simulation redoes.  Waits for the lane's stream.
-static void tail_dbg_dump(orip_ctx* c, int layer, const A08& a) {
+// redo[q] is 1 + the last unsure sample of polyline q (0: not redone); first[q] the first unsure one (k_tail_par's dbg_first).
+static void tail_dbg_dump(orip_ctx* c, int layer, const A08& a, const unsigned* first) {
     const int64_t nk = a.nk;
-    std::vector<unsigned> h(nk), sb(nk + 1);
+    std::vector<unsigned> h(nk), sb(nk + 1), f(nk);
     hipStreamSynchronize(LN(c).stream);
     hipMemcpy(h.data(), a.redo, nk * 4, hipMemcpyDeviceToHost);
     hipMemcpy(sb.data(), a.sbase, (nk + 1) * 4, hipMemcpyDeviceToHost);
-    unsigned long long nf = 0, sf = 0, mx = 0;
-    for (int64_t q = 0; q < nk; q++) if (h[q]) { nf++; sf += sb[q + 1] - sb[q]; mx = std::max<unsigned long long>(mx, sb[q + 1] - sb[q]); }
-    fprintf(stderr, "[tail dbg] layer %d: %llu of %lld polylines redone, %llu of %u samples, longest redone %llu\n", layer, nf, (long long)nk, sf, a.MS, mx);
+    hipMemcpy(f.data(), first, nk * 4, hipMemcpyDeviceToHost);
+    unsigned long long nf = 0, sf = 0, mx = 0, upto = 0;
+    std::vector<int64_t> red;
+    for (int64_t q = 0; q < nk; q++) if (h[q]) { nf++; sf += sb[q + 1] - sb[q]; upto += h[q]; mx = std::max<unsigned long long>(mx, sb[q + 1] - sb[q]); red.push_back(q); }
+    fprintf(stderr, "[tail dbg] layer %d: %llu of %lld polylines redone, %llu of %u samples (%llu up to the last unsure one), longest redone %llu\n", layer, nf, (long long)nk, sf, a.MS, upto, mx);
+    std::stable_sort(red.begin(), red.end(), [&](int64_t x, int64_t y) { return sb[x + 1] - sb[x] > sb[y + 1] - sb[y]; });
+    for (size_t i = 0; i < red.size() && i < 5; i++) { const int64_t q = red[i];
+        fprintf(stderr, "[tail dbg]   rank %lld: %u samples, first unsure %u, last unsure %u\n", (long long)q, sb[q + 1] - sb[q], f[q], h[q] - 1u); }
+}
+// the replay's counters (LaneFlags::tail_dbg).  Waits for the lane's side stream.
+static void tail_dbg_replay(orip_ctx* c, int layer, const unsigned long long* dbg) {
+    unsigned long long v[4] = {0, 0, 0, 0};
+    hipStreamSynchronize(LN(c).stream2);
+    hipMemcpy(v, dbg, sizeof v, hipMemcpyDeviceToHost);
+    fprintf(stderr, "[tail dbg] layer %d: replay %llu rounds, %llu samples committed by rounds, %llu by the plain loop, %llu rounds in the integer form\n", layer, v[0], v[1], v[2], v[3]);
 }
 // ---- A3: pops per sample (tail simulation), then the previous in-canvas sample of every sample
 static int a3_tails(orip_ctx* c, int layer, const orip_params08& P, A08& a) {
     const int64_t nk = a.nk; const unsigned MS = a.MS;
     {
         ProfScope ps(c, "k_tail_sim");
-        hipLaunchKernelGGL(k_tail_par, dim3(cdiv(MS, 256)), dim3(256), 0, LN(c).stream, a.sbase, a.A.rank, a.A.Sloc, MS, P.tail_len_px, a.npop, a.redo);
-        if (getenv("ORIP_TAIL_DBG")) tail_dbg_dump(c, layer, a);
+        const bool dbg = getenv("ORIP_TAIL_DBG") != nullptr;
+        unsigned* dbg_first = nullptr; unsigned long long* dbg_cnt = nullptr;      // (debug: a buffer of its own, released below)
+        if (dbg) {
+            HIPC(c, hipMalloc(&dbg_first, (size_t)(nk + 1) * 4));
+            const hipError_t me = hipMemsetAsync(dbg_first, 0xff, (size_t)(nk + 1) * 4, LN(c).stream);
+            if (me != hipSuccess) { hipFree(dbg_first); HIPC(c, me); }      // (nothing between here and the hipFree below returns)
+            dbg_cnt = LN(c).flags.as<LaneFlags>()->tail_dbg;
+        }
+        hipLaunchKernelGGL(k_tail_par, dim3(cdiv(MS, 256)), dim3(256), 0, LN(c).stream, a.sbase, a.A.rank, a.A.Sloc, MS, P.tail_len_px, a.npop, a.redo, dbg_first);
+        if (dbg) { tail_dbg_dump(c, layer, a, dbg_first); hipFree(dbg_first); HIPC(c, hipMemsetAsync(dbg_cnt, 0, sizeof(LaneFlags::tail_dbg), LN(c).stream)); }
         const unsigned* only = getenv("ORIP_TAIL_SEQ") ? nullptr : a.redo;          // test hook: force the sequential simulation everywhere
         // the sequential redo only feeds the acceptance test (A6): it runs on the lane's side stream under the capsule / hash work
         HIPC(c, hipEventRecord(LN(c).ev2, LN(c).stream));
         HIPC(c, hipStreamWaitEvent(LN(c).stream2, LN(c).ev2, 0));
-        hipLaunchKernelGGL(k_tail_replay, dim3((unsigned)std::min<int64_t>(nk, 65535)), dim3(64), 0, LN(c).stream2, a.sbase, nk, P.tail_len_px, a.A, a.npop, only);
+        hipLaunchKernelGGL(k_tail_replay, dim3((unsigned)std::min<int64_t>(nk, 65535)), dim3(64), 0, LN(c).stream2, a.sbase, nk, P.tail_len_px, a.A, a.npop, only, dbg_cnt);
         HIPC(c, hipEventRecord(LN(c).ev3, LN(c).stream2));
+        if (dbg) tail_dbg_replay(c, layer, dbg_cnt);
     }
     if (a.any_out) {
         unsigned* lastin = LN(c).vtmp[VTL_TAIL_RUNS].as<unsigned>();            // MS words over Sloc: k_tail_par has consumed the tail sums

@@ -124,9 +124,11 @@ __device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v)
     for (int o = 32; o > 0; o >>= 1) { unsigned long long t = __shfl_xor(v, o, 64); if (t < v) v = t; }
     return v;
 }
-__global__ __launch_bounds__(256) void k_nearest_anchor(const unsigned* __restrict__ lin, int64_t m, const unsigned* __restrict__ gid, int Wp, GroupInfo* __restrict__ g) {
+__global__ __launch_bounds__(256) void k_nearest_anchor(const unsigned* __restrict__ lin, int64_t m, const unsigned* __restrict__ gid, int Wp, GroupInfo* __restrict__ g,
+                                                        unsigned long long* __restrict__ ckey, unsigned nc) {
     int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const bool valid = i < m;
+    if (i < nc) ckey[i] = ~0ULL;                               // (nc <= m) the components' keys, for the minima of k_comp_keys behind this kernel
     unsigned grp = 0; unsigned long long k0 = ~0ULL, k1 = ~0ULL;
     if (valid) {
         unsigned p = lin[i]; int x = (int)(p % Wp) - PAD8, y = (int)(p / Wp) - PAD8;
@@ -153,19 +155,36 @@ __global__ __launch_bounds__(256) void k_nearest_anchor(const unsigned* __restri
     }
 }
 // per component: sort key (group rank, ROI-relative block-raster key of its first block)
-__global__ __launch_bounds__(128) void k_comp_keys(const unsigned* __restrict__ cs, unsigned nc, const unsigned* __restrict__ lin, const unsigned* __restrict__ gid, int Wp,
+// One thread per pixel of the component-sorted list (a component of 20 000 pixels was one thread's loop, and the launch as long as that loop): pixel q belongs
+// to component head_scan[q] + head[q] - 1 (the heads and their exclusive scan, still in place behind k_comp_starts).  Every pixel forms the whole key with the
+// group of its component's FIRST pixel, as the loop did, so the keys of one component differ in the block index alone and their minimum is the old key.  A
+// component's pixels are neighbours in the list: a segmented running minimum over the wave, then one atomicMin per (wave, component) on the word that
+// k_nearest_anchor has set to all ones.
+__global__ __launch_bounds__(256) void k_comp_keys(const unsigned* __restrict__ cs, const unsigned* __restrict__ head, const unsigned* __restrict__ head_scan, unsigned m,
+                                                    const unsigned* __restrict__ lin, const unsigned* __restrict__ gid, int Wp,
                                                     const GroupInfo* __restrict__ g, unsigned long long* __restrict__ ckey, unsigned* __restrict__ cidx) {
-    unsigned c = blockIdx.x * blockDim.x + threadIdx.x; if (c >= nc) return;
-    unsigned b = cs[c], e = cs[c + 1];
-    const GroupInfo* G = g + (gid[lin[b]] - 1);
-    int w = max(1, G->x1 - G->x0); int wb = (w + 1) >> 1;
-    unsigned best = 0xffffffffu;
-    for (unsigned q = b; q < e; q++) {
+    const unsigned q = blockIdx.x * 256 + threadIdx.x;
+    const bool valid = q < m;
+    unsigned c = 0xffffffffu; unsigned long long key = ~0ULL;
+    if (valid) {
+        const unsigned hd = head[q];
+        c = head_scan[q] + hd - 1u;
+        const GroupInfo* G = g + (gid[lin[cs[c]]] - 1);
+        int w = max(1, G->x1 - G->x0); int wb = (w + 1) >> 1;
         unsigned p = lin[q]; int x = (int)(p % Wp) - PAD8 - G->x0, y = (int)(p / Wp) - PAD8 - G->y0;
         unsigned k = (unsigned)((y >> 1) * wb + (x >> 1));
-        best = min(best, k);
+        key = ((unsigned long long)(unsigned)G->rank << 32) | k;
+        if (hd) cidx[c] = c;
     }
-    ckey[c] = ((unsigned long long)(unsigned)G->rank << 32) | best; cidx[c] = c;
+    const int lane = threadIdx.x & 63;
+    for (int o = 1; o < 64; o <<= 1) {                         // the lanes of a component are contiguous: equal c at distance o means equal c in between
+        const unsigned long long t = __shfl_up(key, o, 64); const unsigned ct = (unsigned)__shfl_up((int)c, o, 64);
+        if (lane >= o && ct == c && t < key) key = t;
+    }
+    const unsigned cn = (unsigned)__shfl_down((int)c, 1, 64);
+    if (valid && (lane == 63 || cn != c)) {                    // the last lane of the component in this wave (an invalid lane has no component)
+        if (key < *(volatile unsigned long long*)&ckey[c]) atomicMin(&ckey[c], key);      // (a stale read only lets a useless atomic through: k_nearest_anchor)
+    }
 }
 
 __device__ const int OFY[8] = {-1, -1, -1, 0, 1, 1, 1, 0};     // _OFFS (dy,dx), 08:252
@@ -515,9 +534,15 @@ static int b_components(orip_ctx* c, B08& b, PhaseTimer& T) {
       L.each(nc1, cidx, b.corder, b.outcnt, b.oflag, b.oscan); L.take(b.pd, NC); HIPC(c, L.commit(LN(c).vtmp[VTL_CAPS], 256)); }
     bp_comp_starts(LN(c).stream, head, hs, (int64_t)M, b.cs, NC);
     T.tick("c:sort");
-    hipLaunchKernelGGL(k_nearest_anchor, dim3(cdiv(M, 256)), blk, 0, LN(c).stream, b.lin, (int64_t)M, b.gid, Wp, b.grp);
+    hipLaunchKernelGGL(k_nearest_anchor, dim3(cdiv(M, 256)), blk, 0, LN(c).stream, b.lin, (int64_t)M, b.gid, Wp, b.grp, ckin, NC);      // (also sets the NC <= M keys to "none yet")
     T.tick("c:anchor");
-    hipLaunchKernelGGL(k_comp_keys, dim3(cdiv(NC, 128)), dim3(128), 0, LN(c).stream, b.cs, NC, b.lin, b.gid, Wp, b.grp, ckin, cidx);
+    hipLaunchKernelGGL(k_comp_keys, dim3(cdiv(M, 256)), blk, 0, LN(c).stream, b.cs, head, hs, M, b.lin, b.gid, Wp, b.grp, ckin, cidx);      // head, hs: VTL_SAMPLES, untouched since the carve above
+    if (getenv("ORIP_COMP_DBG")) {      // debug / test hook: the keys as k_comp_keys left them, one line per component in list order.  Waits for the lane's stream.
+        std::vector<unsigned long long> hk(NC);
+        hipStreamSynchronize(LN(c).stream);
+        hipMemcpy(hk.data(), ckin, (size_t)NC * 8, hipMemcpyDeviceToHost);
+        for (unsigned q = 0; q < NC; q++) fprintf(stderr, "[comp dbg] rank %u block %u\n", (unsigned)(hk[q] >> 32), (unsigned)hk[q]);
+    }
     ORIP_TRY((vsort_pairs<unsigned long long, unsigned>(c, ckin, ckout, cidx, b.corder, (size_t)NC, 0, 64)));
     T.tick("comps");
     return 0;

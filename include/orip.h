@@ -662,13 +662,42 @@ int orip_gcode_improve(orip_ctx* ctx, const int32_t* ends /* [n,4] or NULL = res
  * Errors before any launch, with the context still good and the outputs untouched: n < 0 or > 2^26; off without pts or the reverse; off not starting at 0
  * or not increasing by at least 2; 2^30 points or more; a coordinate or the start outside 0 .. 2^30; an order that is not a permutation; a rev byte above
  * 1; NULL stats, or NULL seam_out with n > 0; n that is not the resident count.  n == 0 returns zeros before any launch.
- * Declined: letting the greedy order enter a ring at its nearest vertex (the order stays the reference's rule; a pass of its own); alternating with
- * orip_gcode_improve until nothing moves; choosing a ring's direction (it does not change the travel); entering a ring on an edge between two vertices
+ * Letting the greedy order enter a ring at its nearest vertex is a pass of its own, orip_gcode_order_rings below (the plain orders stay the reference's
+ * rule).  Declined: alternating with orip_gcode_improve until nothing moves; choosing a ring's direction (it does not change the travel); entering a ring on an edge between two vertices
  * (that would invent a vertex); any bound on the worst case: two rings of 10^5 vertices in a row are 10^10 pairs, and the result must not depend on a
  * budget. */
 int orip_gcode_seam(orip_ctx* ctx, const int64_t* off /* [n+1] or NULL */, const int32_t* pts /* [off[n],2] or NULL = resident */, int64_t n,
                     const int32_t* order /* [n] or NULL */, const uint8_t* rev /* [n] or NULL */, const int32_t* start_xy /* NULL = (0,0) */,
                     int32_t* seam_out /* [n], by sequence position; 0 for open strokes */, int64_t* stats /* [4]: closed, moved, travel_before, travel_after */);
+/* --ring-entry (csrc/gcode_order.hip, 2c; ours, the reference has no such order): the greedy walk of orip_gcode_order_pens in which a closed stroke can be
+ * entered at ANY of its ring vertices.  The plain orders see a closed stroke as the one point its file lists first and cross a shape to reach it; this one
+ * takes a ring whose outline passes under the pen.  Input: n step polylines (off, pts), or off == pts == NULL for the n resident ones, which are read and
+ * never written (an explicit input does not become the resident list either); a group per stroke (NULL: all 0); a start cursor.
+ *   Closed: a stroke is CLOSED iff it has at least 4 points and its first point equals its last (orip_gcode_seam's definition).  Everything else is open:
+ *   A, B, A, every 2-point stroke and every 1-point stroke -- which is legal here: the dots of orip_svg_stipple arrive as such.
+ *   Candidates of stroke i.  Open: c = 0 is its first point and, under ORIP_ORDER_REVERSE, c = 1 its last.  Closed, of L points: c = v for every ring
+ *   vertex v = 0 .. L - 2, indexed in the stored list.  A closed stroke has no reverse candidate: its direction does not change the travel, and it is always
+ *   drawn forwards.
+ *   Walk: the cursor starts at start_xy.  For g = 0 .. n_groups - 1 in turn, while strokes of group g remain, take the minimum of the key (L1 distance from
+ *   the cursor, i, c), compared lexicographically, over all candidates of the remaining strokes of g; order_out[k] = i.  An open stroke: rev_out[k] = c,
+ *   seam_out[k] = 0, and the cursor moves to the stroke's other end.  A closed stroke: rev_out[k] = 0, seam_out[k] = c, and the cursor moves to that vertex:
+ *   the ring is drawn c, c + 1, .., L - 2, 0, .., c, the seam convention of orip_gcode_seam.  The cursor carries over between groups; empty groups are legal.
+ *   Distance: L1, as in both plain orders, not the steps of a travel.  Hence on an input without a closed stroke order_out and rev_out equal
+ *   orip_gcode_order_pens' for every flag, group and start, and orip_gcode_order's with one group and no flag.  Two ring vertices on one grid point are two
+ *   candidates and the lower v wins; of two identical rings the lower i wins.
+ * stats: closed strokes; moved = the seams that are not 0; candidates = how many were bucketed; travel = the pen-up steps of the sequence as returned,
+ * max(|dx|, |dy|) per travel from start_xy, the approaches between groups included: the quantity orip_gcode_improve and orip_gcode_seam count.
+ * NO GUARANTEE that travel is below the plain order's: greedy is not monotone, and a ring entered early can leave a worse tour behind.
+ * Errors before any launch, with the context still good and the outputs untouched: n < 0 or > 2^26; 2^28 points or more; a coordinate or the start outside
+ * 0 .. 2^30; off not starting at 0 or not increasing by at least 1, off without pts or the reverse; a group out of range, n_groups outside 1 .. 64, unknown
+ * flags; n that is not the resident count; a NULL output with n > 0, NULL stats.  n == 0 returns zeros before any launch.
+ * Declined: entering a ring on an edge between two vertices (that would invent a vertex); choosing a ring's direction; a Chebyshev key (the plain orders'
+ * results would no longer be the special case); falling back to the plain order when it is shorter (the caller can run both); any bound on the worst
+ * case. */
+int orip_gcode_order_rings(orip_ctx* ctx, const int64_t* off /* [n+1] or NULL */, const int32_t* pts /* [off[n],2] or NULL = resident */,
+                           const int32_t* group /* [n] or NULL = all 0 */, int64_t n, int32_t n_groups, int32_t flags /* ORIP_ORDER_REVERSE */,
+                           const int32_t* start_xy /* NULL = (0,0) */, int32_t* order_out /* [n] */, uint8_t* rev_out /* [n] */,
+                           int32_t* seam_out /* [n], by sequence position */, int64_t* stats /* [4]: closed, moved, candidates, travel */);
 /* StreamWriter.add_steps / finalize (helper :55-68, :166-175) for a whole plot: the bytes of the stream from the direction codes orip_stream_codes left
  * resident.  Piece i reads cnt[i] codes from code0[i] on and owns the bytes from pos[i]: its speed byte when speed[i] >= 0, then (cnt[i] + 1) / 2 step bytes
  * (two codes per byte, paired inside the piece, the last byte of an odd piece holds one).  Pieces are listed in byte order, each at least one byte, none

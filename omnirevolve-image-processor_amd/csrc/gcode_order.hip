@@ -1,5 +1,6 @@
 // csrc/gcode_order.hip -- the nearest-neighbour order of the step polylines of svg_to_stream/gcode2stream.py (order_paths_nearest :151-172), as one list
-// (orip_gcode_order) and group by group with reversible strokes (orip_gcode_order_pens).  ONE search serves both: gc_search below.
+// (orip_gcode_order) and group by group with reversible strokes (orip_gcode_order_pens); and, ours, the same walk with a closed stroke entered at its
+// nearest ring vertex (orip_gcode_order_rings, 2c).  ONE search serves all three: gc_search below.
 //
 // 2. Order.  The reference starts at (0, 0) and takes, again and again, the remaining path whose FIRST point has the smallest L1 distance from the cursor,
 //    the lowest index on ties; the cursor moves to that path's LAST point.  That is a chain of n dependent searches over n points: n^2 / 2 distances.  Here
@@ -32,6 +33,8 @@
 #include "gc_convert.h"
 #include <rocprim/rocprim.hpp>
 #include <climits>
+#include <cstring>
+#include <vector>
 
 namespace {
 constexpr int GC_BIG = 64;                       // a cell with more entries than this is scanned by the whole wave
@@ -90,16 +93,21 @@ __global__ __launch_bounds__(256) void k_gc_hdr(const unsigned* __restrict__ sta
 // ------------------------------------------------------------------------------------------------ the search of one step
 // what a lane remembers about the best entry it has seen in the current step: its key, slot and cell, and the cell's header when it was read
 struct GcBest { unsigned long long key; int slot, cell, first, count; };
-__device__ __forceinline__ void gc_look(GcBest& b, const int4 e, int slot, int cell, const int2 h, int cx, int cy) {
+// DEAD (the ring order, 2c): entries never move; one that has left has id -1 and is passed over.  Nothing is removed through cell and header there, and
+// the three words carry the entry itself instead: cell = x, count = y, first = the stroke (the entry's fourth word)
+template <bool DEAD> __device__ __forceinline__ void gc_look(GcBest& b, const int4 e, int slot, int cell, const int2 h, int cx, int cy) {
+    if (DEAD && e.z < 0) return;
     const unsigned d = (unsigned)abs(e.x - cx) + (unsigned)abs(e.y - cy);
     const unsigned long long key = ((unsigned long long)d << 32) | (unsigned)e.z;
-    if (key < b.key) { b.key = key; b.slot = slot; b.cell = cell; b.first = h.x; b.count = h.y; }
+    if (key < b.key) { b.key = key; b.slot = slot; b.cell = DEAD ? e.x : cell; b.count = DEAD ? e.y : h.y; b.first = DEAD ? e.w : h.x; }
 }
 #define GCU(x) __builtin_amdgcn_readfirstlane((int)(x))
 
 // The nearest live entry to (cx, cy) among the cells cell0 .. cell0 + gx * gy - 1 of grid g, for a block of one wave: the winner's GcBest, the same in every
 // lane (key = ~0ull: nothing found, which cannot happen while the grid holds an entry).  hdr and ent are read only; they change between two searches.
-__device__ __forceinline__ GcBest gc_search(const GcGrid& g, const int cell0, const int cx, const int cy, const int2* hdr, const int4* ent) {
+// DEAD: hdr does not change, a cell's entries stay where the fill put them and live[cell] counts those that remain; a cell with none is passed over
+// from that count alone, which is read past the L1 because atomics, which the L1 does not see, decrement it.  Without DEAD `live` is not looked at.
+template <bool DEAD> __device__ __forceinline__ GcBest gc_search(const GcGrid& g, const int cell0, const int cx, const int cy, const int2* hdr, const int4* ent, int* live) {
     __shared__ unsigned long long s_best;
     const int lane = threadIdx.x, sub = lane & 3, slot16 = lane >> 2;
     const long long INF = 1ll << 62;
@@ -128,15 +136,16 @@ __device__ __forceinline__ GcBest gc_search(const GcGrid& g, const int cell0, co
                 else { x = xh; y = iyl + (t - n2); }
                 cell = cell0 + y * g.gx + x;
                 h = hdr[cell];
+                if (DEAD && __hip_atomic_load(&live[cell], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) <= 0) h.y = 0;
                 if (h.y <= GC_BIG)
-                    for (int j = sub; j < h.y; j += 4) gc_look(b, ent[h.x + j], h.x + j, cell, h, cx, cy);
+                    for (int j = sub; j < h.y; j += 4) gc_look<DEAD>(b, ent[h.x + j], h.x + j, cell, h, cx, cy);
             }
             unsigned long long big = __ballot(cell >= 0 && h.y > GC_BIG && sub == 0);
             while (big) {                                                  // wave-uniform loop: a crowded cell, all lanes on it
                 const int l = __ffsll((long long)big) - 1;
                 big &= big - 1;
                 const int bc = __shfl(cell, l), bx = __shfl(h.x, l), by = __shfl(h.y, l);
-                for (int j = lane; j < by; j += 64) gc_look(b, ent[bx + j], bx + j, bc, make_int2(bx, by), cx, cy);
+                for (int j = lane; j < by; j += 64) gc_look<DEAD>(b, ent[bx + j], bx + j, bc, make_int2(bx, by), cx, cy);
             }
         }
         // the wave's minimum through LDS (one wave: the three accesses below happen in program order)
@@ -171,7 +180,7 @@ __global__ __launch_bounds__(64) void k_gc_chain(const int4* __restrict__ se, in
     const int lane = threadIdx.x;
     int cx = 0, cy = 0;
     for (int step = 0; step < n; step++) {
-        const GcBest w = gc_search(g, 0, cx, cy, hdr, ent);
+        const GcBest w = gc_search<false>(g, 0, cx, cy, hdr, ent, nullptr);
         const int id = GCU((unsigned)w.key), win = id >> 1;
         if (id < 0 || win >= n) { if (lane == 0) order[0] = -1; return; }                    // cannot happen: n - step paths remain somewhere in the grid
         // the cell's last live entry takes the winner's place
@@ -196,7 +205,7 @@ __global__ __launch_bounds__(64) void k_op_chain(const int4* __restrict__ se, in
         const GcGrid g = groups[gi].g;
         const int cell0 = groups[gi].cell0, paths = groups[gi].paths;
         for (int step = 0; step < paths; step++, k++) {
-            const GcBest w = gc_search(g, cell0, cx, cy, hdr, ent);
+            const GcBest w = gc_search<false>(g, cell0, cx, cy, hdr, ent, nullptr);
             const int id = GCU((unsigned)w.key), win = id >> 1, wr = id & 1;
             // cannot happen: paths - step paths of the group remain somewhere in its cells.  Every index below is checked before it is used all the same
             if (id < 0 || win >= n || (wr && !rev)) { if (lane == 0) order[0] = -1; return; }
@@ -223,6 +232,118 @@ __global__ __launch_bounds__(64) void k_op_chain(const int4* __restrict__ se, in
             cx = GCU(wr ? e.x : e.z); cy = GCU(wr ? e.y : e.w);
         }
     }
+}
+
+// ------------------------------------------------------------------------------------------------ 2c. the ring order: a closed stroke is entered at any ring vertex
+// orip_gcode_order_rings (ours; include/orip.h states the rule).  The walk of 2b over CANDIDATES: every ring vertex of a closed stroke, the first point of an
+// open one and, under ORIP_ORDER_REVERSE, its last.  Candidate c of stroke i has the id cbase[i] + c (a scan of the per-stroke counts), so ids ascend with
+// (i, c) and the key (L1 distance << 32) | id is the rule's (d, i, c).  The grid is built over the candidates, per group as in gc_grids.
+// When a stroke wins, ALL its candidates leave -- the 63 other vertices of a circle as well as the one entered.  Swap-removal, which 2 and 2b use, would be a
+// chain of dependent read-modify-writes by one lane per vertex (a moved entry may be the next one to leave).  Here entries never move: slot[id] = (entry,
+// cell) is fixed at fill time, the lanes mark the winner's entries dead 64 at a time (id = -1: one independent store each) and decrement the cell's live count
+// by an atomic; the search passes over a dead entry and over a cell without a live one.  The cost is that a cell keeps its dead entries to the end: with
+// about two candidates per cell that is a few wasted words per window.  A stroke is closed iff it has three candidates or more (L - 1 >= 3; an open one has
+// one or two).
+struct RoCounters { unsigned long long closed, moved, travel; };
+#ifndef RO_CELL_CANDS
+#define RO_CELL_CANDS 2                          // candidates per cell the grid aims at; make EXTRA=-DRO_CELL_CANDS=... builds another one for tools/time_ring_entry.py
+#endif
+
+// thread per stroke: its ends and how many candidates it has, which its group counts too
+__global__ __launch_bounds__(256) void k_ro_strokes(const long long* __restrict__ off, const int2* __restrict__ pts, const int* __restrict__ grp, int n, int rev,
+                                                    int4* __restrict__ se, int* __restrict__ cnt, unsigned long long* __restrict__ gcand) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const long long a = off[i], b = off[i + 1];
+    const int2 A = pts[a], B = pts[b - 1];
+    const int k = (b - a >= 4 && A.x == B.x && A.y == B.y) ? (int)(b - a - 1) : 1 + rev;
+    se[i] = make_int4(A.x, A.y, B.x, B.y);
+    cnt[i] = k;
+    if (i == 0) cnt[n] = 0;
+    atomicAdd(&gcand[grp ? grp[i] : 0], (unsigned long long)k);
+}
+// thread per candidate id: its stroke (the last i with cbase[i] <= id; every stroke has a candidate), its point, cd[id] = (x, y, stroke, group), the group's box
+__global__ __launch_bounds__(256) void k_ro_cands(const long long* __restrict__ off, const int2* __restrict__ pts, const int* __restrict__ grp, const int* __restrict__ cbase, int n,
+                                                  int4* __restrict__ cd, int* __restrict__ box) {
+    const int id = blockIdx.x * 256 + threadIdx.x;
+    const bool ok = id < cbase[n];
+    int g = 0, x0 = INT_MAX, y0 = INT_MAX, x1 = INT_MIN, y1 = INT_MIN;
+    if (ok) {
+        int lo = 0, hi = n;
+        while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (cbase[mid] <= id) lo = mid; else hi = mid; }
+        const int i = lo, c = id - cbase[i], k = cbase[i + 1] - cbase[i];
+        const int2 p = k >= 3 ? pts[off[i] + c] : pts[c ? off[i + 1] - 1 : off[i]];
+        g = grp ? grp[i] : 0;
+        cd[id] = make_int4(p.x, p.y, i, g);
+        x0 = x1 = p.x; y0 = y1 = p.y;
+    }
+    // a ring's vertices are 64 neighbours of one group: one box update per wave then, not one per candidate
+    const unsigned long long act = __ballot(ok);
+    if (!act) return;
+    const int g0 = __shfl(g, __ffsll((long long)act) - 1);
+    if (__all(!ok || g == g0)) {
+        for (int o = 32; o; o >>= 1) { x0 = min(x0, __shfl_xor(x0, o)); y0 = min(y0, __shfl_xor(y0, o)); x1 = max(x1, __shfl_xor(x1, o)); y1 = max(y1, __shfl_xor(y1, o)); }
+        if ((threadIdx.x & 63) != 0) return;
+        g = g0;
+    } else if (!ok) return;
+    int* b = box + 4 * g;
+    atomicMin(&b[0], x0); atomicMin(&b[1], y0); atomicMax(&b[2], x1); atomicMax(&b[3], y1);
+}
+__global__ __launch_bounds__(256) void k_ro_cells(const int4* __restrict__ cd, int m, const OpGroup* __restrict__ G, unsigned* __restrict__ cnt) {
+    const int id = blockIdx.x * 256 + threadIdx.x;
+    if (id >= m) return;
+    const int4 q = cd[id];
+    const OpGroup o = G[q.w];
+    atomicAdd(&cnt[o.cell0 + gc_cell(o.g, q.x, q.y)], 1u);
+}
+__global__ __launch_bounds__(256) void k_ro_fill(const int4* __restrict__ cd, int m, const OpGroup* __restrict__ G, const unsigned* __restrict__ start, unsigned* __restrict__ fill,
+                                                 int4* __restrict__ ent, int2* __restrict__ slot) {
+    const int id = blockIdx.x * 256 + threadIdx.x;
+    if (id >= m) return;
+    const int4 q = cd[id];
+    const OpGroup o = G[q.w];
+    const int c = o.cell0 + gc_cell(o.g, q.x, q.y);
+    const int at = (int)(start[c] + atomicAdd(&fill[c], 1u));
+    ent[at] = make_int4(q.x, q.y, id, q.z);
+    slot[id] = make_int2(at, c);
+}
+
+// One wave, group after group with the cursor carried over.  ent and live change under the chain: every lane's stores and atomics of a step are behind
+// the fence when the next search reads (the pattern of k_op_chain, whose lane 0 writes what all lanes read next; those pointers stay unqualified).  hdr,
+// slot, se and cbase do not change.  Every index read from memory is checked before it is used.
+__global__ __launch_bounds__(64) void k_ro_chain(const int4* __restrict__ se, const int* __restrict__ cbase, int n, const OpGroup* __restrict__ groups, int n_groups, int sx, int sy,
+                                                 int ncell, int m, const int2* hdr, int4* ent, const int2* slot, int* live, int* __restrict__ order, uint8_t* __restrict__ rev_out,
+                                                 int* __restrict__ seam, RoCounters* __restrict__ out) {
+    const int lane = threadIdx.x;
+    int cx = sx, cy = sy, k = 0;
+    unsigned long long travel = 0, closed = 0, moved = 0;
+    for (int gi = 0; gi < n_groups; gi++) {
+        const GcGrid g = groups[gi].g;
+        const int cell0 = groups[gi].cell0, paths = groups[gi].paths;
+        for (int step = 0; step < paths; step++, k++) {
+            const GcBest w = gc_search<true>(g, cell0, cx, cy, hdr, ent, live);
+            const int id = GCU((unsigned)w.key), i = w.first, ex = w.cell, ey = w.count;     // DEAD: the entry's own words (gc_look)
+            // cannot happen: paths - step strokes of the group have live candidates in its cells
+            if (w.key == ~0ull || id < 0 || id >= m || i < 0 || i >= n || k >= n) { if (lane == 0) order[0] = -1; return; }
+            const int cb = GCU(cbase[i]), kc = GCU(cbase[i + 1]) - cb, c = id - cb;
+            const int4 e = se[i];
+            if (c < 0 || c >= kc) { if (lane == 0) order[0] = -1; return; }
+            const bool ring = kc >= 3;
+            int lost = 0;
+            for (int j = lane; j < kc; j += 64) {                                            // all candidates of the stroke leave
+                const int2 s = slot[cb + j];
+                if ((unsigned)s.x < (unsigned)m && (unsigned)s.y < (unsigned)ncell) { ent[s.x].z = -1; atomicSub(&live[s.y], 1); }
+                else lost = 1;
+            }
+            travel += (unsigned long long)max(abs(ex - cx), abs(ey - cy));
+            closed += ring; moved += ring && c != 0;
+            if (lane == 0) { order[k] = i; rev_out[k] = (uint8_t)(ring ? 0 : c); seam[k] = ring ? c : 0; }
+            __threadfence_block();
+            if (__any(lost)) { if (lane == 0) order[0] = -1; return; }
+            cx = GCU(ring ? ex : (c ? e.x : e.z)); cy = GCU(ring ? ey : (c ? e.y : e.w));    // a ring: the vertex entered; an open stroke: its other end
+        }
+    }
+    if (lane == 0) { out->closed = closed; out->moved = moved; out->travel = travel; }
 }
 
 // ------------------------------------------------------------------------------------------------ host: ends and grids, the same for both orders
@@ -331,5 +452,100 @@ extern "C" int orip_gcode_order_pens(orip_ctx* c, const int32_t* ends, const int
     HIPC(c, hipMemcpyAsync(rev_out, o.rv, (size_t)n, hipMemcpyDeviceToHost, s));
     HIPC(c, hipStreamSynchronize(s));
     if (order_out[0] < 0) ORIP_FAIL(c, "the chain lost a path (internal error)");
+    return 0;
+}
+
+// the walk over candidates, a closed stroke entered at its nearest ring vertex; include/orip.h states the rule, 2c above the kernels
+extern "C" int orip_gcode_order_rings(orip_ctx* c, const int64_t* off, const int32_t* pts, const int32_t* group, int64_t n, int32_t n_groups, int32_t flags,
+                                      const int32_t* start_xy, int32_t* order_out, uint8_t* rev_out, int32_t* seam_out, int64_t* stats) {
+    orip_enter(c);
+    ORIP_LANE(c, ORIP_LANE_CROSS);
+    if (!stats || (n > 0 && (!order_out || !rev_out || !seam_out)) || (flags & ~ORIP_ORDER_REVERSE)) ORIP_FAIL(c, "bad arguments");
+    if (n < 0 || n > (1 << 26)) ORIP_FAIL(c, "%lld paths: 0..2^26", (long long)n);
+    int sx, sy;
+    ORIP_TRY(gc_check_groups(c, __func__, nullptr, 0, n_groups, nullptr));
+    ORIP_TRY(gc_check_start(c, __func__, start_xy, sx, sy));
+    if (n == 0) { for (int k = 0; k < 4; k++) stats[k] = 0; return 0; }
+    if (!off != !pts) ORIP_FAIL(c, "off and pts: both or neither");
+    int64_t total;
+    if (off) {                                                                // one-point strokes are legal here (the dots of a stipple), so not gc_steps_check
+        if (off[0] != 0) ORIP_FAIL(c, "offsets must start at 0");
+        for (int64_t p = 0; p < n; p++) if (off[p + 1] - off[p] < 1) ORIP_FAIL(c, "path %lld has no point", (long long)p);
+        total = off[n];
+    } else {
+        ORIP_TRY(gc_check_resident(c, __func__, n));
+        total = c->gc_total;
+    }
+    if (total >= (int64_t)1 << 28) ORIP_FAIL(c, "%lld points: fewer than 2^28", (long long)total);
+    for (int64_t i = 0; off && i < 2 * total; i++) if (pts[i] < 0 || pts[i] > GC_COORD_MAX) ORIP_FAIL(c, "point %lld: coordinate %d outside 0..2^30", (long long)(i / 2), pts[i]);
+    int64_t paths[ORIP_ORDER_MAX_GROUPS] = {0};
+    ORIP_TRY(gc_check_groups(c, __func__, group, n, n_groups, paths));
+    if (!group) paths[0] = n;
+    const int rev = flags & ORIP_ORDER_REVERSE ? 1 : 0, G = n_groups, N = (int)n;
+    const int64_t ub = total + n;                                             // candidates at most: known before the scan is read back
+    hipStream_t s = LN(c).stream;
+    const long long* d_off = c->gc_off.as<long long>(); const int2* d_pts = c->gc_pts.as<int2>();
+    if (off) {
+        long long* o2; int2* p2;
+        { Carve L; L.take(o2, (size_t)n + 1); L.take(p2, (size_t)total); HIPC(c, L.commit(c->ro_in, 64)); }
+        HIPC(c, hipMemcpyAsync(o2, off, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, s));
+        HIPC(c, hipMemcpyAsync(p2, pts, (size_t)total * 8, hipMemcpyHostToDevice, s));
+        d_off = o2; d_pts = p2;
+    }
+    int4 *se, *cd; int *grp, *cnt, *cbase, *order, *seam, *box; uint8_t* rv; unsigned long long* gcand; OpGroup* dG; RoCounters* rc;
+    { Carve L; L.take(se, (size_t)n); L.take(grp, group ? (size_t)n : 0); L.take(cnt, (size_t)n + 1); L.take(cbase, (size_t)n + 1); L.take(order, (size_t)n); L.take(seam, (size_t)n);
+      L.take(rv, (size_t)n); L.take(box, (size_t)4 * G); L.take(gcand, (size_t)G); L.take(dG, (size_t)G); L.take(rc, 1); L.take(cd, (size_t)ub); HIPC(c, L.commit(c->ro_state, 64)); }
+    if (group) HIPC(c, hipMemcpyAsync(grp, group, (size_t)n * 4, hipMemcpyHostToDevice, s)); else grp = nullptr;
+    int hbox[4 * ORIP_ORDER_MAX_GROUPS]; unsigned long long hcand[ORIP_ORDER_MAX_GROUPS]; int m32 = 0;
+    for (int g = 0; g < G; g++) { hbox[4 * g] = hbox[4 * g + 1] = INT_MAX; hbox[4 * g + 2] = hbox[4 * g + 3] = INT_MIN; }
+    HIPC(c, hipMemcpyAsync(box, hbox, (size_t)16 * G, hipMemcpyHostToDevice, s));
+    HIPC(c, hipMemsetAsync(gcand, 0, (size_t)8 * G, s));
+    HIPC(c, hipMemsetAsync(rc, 0, sizeof(RoCounters), s));
+    hipLaunchKernelGGL(k_ro_strokes, dim3(cdiv(n, 256)), dim3(256), 0, s, d_off, d_pts, grp, N, rev, se, cnt, gcand);
+    HIPC(c, orip_with_tmp(c, [&](void* tmp, size_t& bytes) { return rocprim::exclusive_scan(tmp, bytes, cnt, cbase, 0, (size_t)n + 1, rocprim::plus<int>(), s); }));
+    hipLaunchKernelGGL(k_ro_cands, dim3(cdiv(ub, 256)), dim3(256), 0, s, d_off, d_pts, grp, cbase, N, cd, box);
+    HIPC(c, hipGetLastError());
+    HIPC(c, hipMemcpyAsync(hbox, box, (size_t)16 * G, hipMemcpyDeviceToHost, s));
+    HIPC(c, hipMemcpyAsync(hcand, gcand, (size_t)8 * G, hipMemcpyDeviceToHost, s));
+    HIPC(c, hipMemcpyAsync(&m32, cbase + n, 4, hipMemcpyDeviceToHost, s));
+    HIPC(c, hipStreamSynchronize(s));
+    const int64_t m = m32;
+    int64_t ncell = 0, msum = 0;
+    OpGroup hG[ORIP_ORDER_MAX_GROUPS];
+    for (int g = 0; g < G; g++) {
+        OpGroup& q = hG[g];
+        q.g = GcGrid{0, 0, 0, 0, 0, 1, 1}; q.cell0 = (int)ncell; q.paths = (int)paths[g];
+        msum += (int64_t)hcand[g];
+        if (!paths[g]) { if (hcand[g]) ORIP_FAIL(c, "the candidates do not add up (internal error)"); continue; }
+        const int* b = hbox + 4 * g;
+        if (b[0] < 0 || b[1] < 0 || b[2] > GC_COORD_MAX || b[3] > GC_COORD_MAX || b[0] > b[2] || b[1] > b[3] || (int64_t)hcand[g] < paths[g])
+            ORIP_FAIL(c, "bounding box or candidates of group %d are off (internal error)", g);
+        q.g = gc_grid_for(b, (int64_t)hcand[g] * 2 / RO_CELL_CANDS);      // gc_grid_for aims at two per cell
+        ncell += (int64_t)q.g.gx * q.g.gy;                                    // at most m / 2 + G over all groups
+    }
+    if (m < n || m > ub || msum != m) ORIP_FAIL(c, "the candidates do not add up (internal error)");
+    unsigned *ccnt, *start, *fill; int2 *hdr, *slot; int4* ent;
+    { Carve L; L.take(ccnt, (size_t)ncell + 1); L.take(start, (size_t)ncell + 1); L.take(fill, (size_t)ncell); L.take(hdr, (size_t)ncell); L.take(ent, (size_t)m);
+      L.take(slot, (size_t)m); HIPC(c, L.commit(c->ro_grid, 64)); }
+    HIPC(c, hipMemcpyAsync(dG, hG, sizeof(OpGroup) * G, hipMemcpyHostToDevice, s));
+    HIPC(c, hipMemsetAsync(ccnt, 0, ((size_t)ncell + 1) * 4, s));
+    HIPC(c, hipMemsetAsync(fill, 0, (size_t)ncell * 4, s));
+    hipLaunchKernelGGL(k_ro_cells, dim3(cdiv(m, 256)), dim3(256), 0, s, cd, (int)m, dG, ccnt);
+    HIPC(c, orip_with_tmp(c, [&](void* tmp, size_t& bytes) { return rocprim::exclusive_scan(tmp, bytes, ccnt, start, 0u, (size_t)ncell + 1, rocprim::plus<unsigned>(), s); }));
+    hipLaunchKernelGGL(k_ro_fill, dim3(cdiv(m, 256)), dim3(256), 0, s, cd, (int)m, dG, start, fill, ent, slot);
+    hipLaunchKernelGGL(k_gc_hdr, dim3(cdiv(ncell, 256)), dim3(256), 0, s, start, ccnt, (int)ncell, hdr);
+    { ProfScope ps(c, "k_ro_chain");
+      hipLaunchKernelGGL(k_ro_chain, dim3(1), dim3(64), 0, s, se, cbase, N, dG, G, sx, sy, (int)ncell, (int)m, hdr, ent, slot, (int*)ccnt, order, rv, seam, rc); }
+    HIPC(c, hipGetLastError());
+    std::vector<int32_t> ho((size_t)n), hs((size_t)n); std::vector<uint8_t> hr((size_t)n); RoCounters hc;
+    HIPC(c, hipMemcpyAsync(ho.data(), order, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    HIPC(c, hipMemcpyAsync(hs.data(), seam, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    HIPC(c, hipMemcpyAsync(hr.data(), rv, (size_t)n, hipMemcpyDeviceToHost, s));
+    HIPC(c, hipMemcpyAsync(&hc, rc, sizeof hc, hipMemcpyDeviceToHost, s));
+    HIPC(c, hipStreamSynchronize(s));
+    if (ho[0] < 0) ORIP_FAIL(c, "the chain lost a path (internal error)");
+    if (hc.moved > hc.closed || hc.closed > (unsigned long long)n) ORIP_FAIL(c, "the counts do not add up (internal error)");
+    memcpy(order_out, ho.data(), (size_t)n * 4); memcpy(seam_out, hs.data(), (size_t)n * 4); memcpy(rev_out, hr.data(), (size_t)n);
+    stats[0] = (int64_t)hc.closed; stats[1] = (int64_t)hc.moved; stats[2] = m; stats[3] = (int64_t)hc.travel;
     return 0;
 }

@@ -96,6 +96,7 @@ extern "C" void orip_destroy(orip_ctx* c) {
     c->gc_tmp.release(); c->gc_off.release(); c->gc_pts.release(); c->gc_ends.release(); c->gc_grid.release(); c->pk_tab.release(); c->pk_out.release(); c->gc_src.release(); c->ht_grp.release();
     c->mg_tab.release(); c->mg_tmp.release(); c->mg_off.release(); c->mg_pts.release(); c->mg_res.release();
     c->im_state.release(); c->im_rec.release(); c->sm_state.release(); c->sm_in.release(); c->sm_f.release();
+    c->ro_in.release(); c->ro_state.release(); c->ro_grid.release();
     c->sp_tmp.release(); c->sp_off.release(); c->sp_pts.release(); c->sp_res.release();
     c->dd_tmp.release(); c->oc_tmp.release(); c->oc_ev.release(); c->ds_tmp.release(); c->ds_raw.release();
     c->dd.release(); c->oc.release(); c->ds.release();

@@ -346,6 +346,7 @@ struct orip_ctx {
     //   Readers (fail while !gc_ready, or when the n they are given is not gc_n): orip_gcode_steps_fetch, orip_gcode_steps_source_fetch (also fails while
     //   gc_merged), and for NULL input orip_gcode_order, orip_gcode_order_pens, orip_gcode_improve, orip_gcode_merge, orip_gcode_simplify, orip_gcode_dedup, orip_gcode_occlude, orip_gcode_dash, orip_gcode_hatch_link; orip_svg_occlude and orip_svg_hatch_link always.
     //   orip_gcode_seam is a reader in both forms: NULL input reads the list, an explicit input goes to sm_in and does not become the list; it never writes these fields.
+    //   orip_gcode_order_rings likewise: NULL input reads the list, an explicit input goes to ro_in.
     //   Writers, and what each leaves:
     //     orip_gcode_to_steps       drops the list on entry (gc_drop), before it looks at its arguments: after ANY failure there is no list.  Success: its
     //                               polylines and their sources, gc_merged cleared; no points to convert (n == 0 included): the empty list (gc_publish_empty).
@@ -396,6 +397,16 @@ struct orip_ctx {
     // exit, the scanned flags, the runs, the levels, the large layers and the seams, and the counters; sm_in = off / pts of an explicit input; sm_f = the
     // cost-to-go of every ring vertex, int64 (the unit states the layout)
     DBuf sm_state, sm_in, sm_f;
+    // --ring-entry (orip_gcode_order_rings, gcode_order.hip: 2c), free between calls.  With n strokes of `total` points in G groups, m candidates (every ring
+    // vertex of a closed stroke; an open stroke's first point, and its last under ORIP_ORDER_REVERSE; m <= total + n) and ncell cells over all groups' grids:
+    //   ro_in    = off int64[n + 1], pts int2[total] of an explicit input (the resident list is only read, and an explicit input does not become the list)
+    //   ro_state = se int4[n] (first x, y, last x, y), grp int[n] (only when given), cnt int[n + 1] = candidates per stroke, cbase int[n + 1] = their
+    //              exclusive scan (candidate c of stroke i has the id cbase[i] + c), order int[n], seam int[n], rev u8[n], box int[4G], gcand u64[G] =
+    //              candidates per group, OpGroup[G], RoCounters, cd int4[total + n] = (x, y, stroke, group) by id
+    //   ro_grid  = cnt unsigned[ncell + 1] = entries per cell and, under the chain, the LIVE entries of the cell, start unsigned[ncell + 1],
+    //              fill unsigned[ncell], hdr int2[ncell] = (first entry, entries), which the chain never writes, ent int4[m] = (x, y, id, stroke) with
+    //              id = -1 once the candidate has left, slot int2[m] = (entry, cell) of candidate id.  Entries never move.
+    DBuf ro_in, ro_state, ro_grid;
     // --simplify-mm (gcode_simplify.hip): sp_tmp = the keep flags, their scan, the two span lists and the counts, free between calls (the unit states the
     // layout); sp_off / sp_pts = the output, swapped with gc_off / gc_pts when a call succeeds; sp_res = kept int64[sp_points], the input index of every
     // output point of the last call (-1: none) until the next one

@@ -561,6 +561,21 @@ class Device:
         self._ck(self.L.orip_gcode_seam(self.h, po, pp, n, _p(o) if o is not None and n else None, _p(r) if r is not None and n else None, _p(st), _p(seam), _p(stats)))
         return seam[:n], {k: int(v) for k, v in zip(_l.SEAM_STATS, stats)}
 
+    def gcode_order_rings(self, off, pts, group, n_groups: int, reverse: bool = False, start=(0, 0), n: int | None = None):
+        """--ring-entry (include/orip.h: orip_gcode_order_rings): the greedy walk of gcode_order_pens in which a closed stroke is entered at its nearest ring
+        vertex; the step polylines (off int64 [n + 1], pts int32 [total, 2]; strokes of one point are legal) or, both None, the n resident ones, which are
+        read and not changed; group int32 [n] or None (all 0).
+        -> (order int32 [n], rev bool [n], seam int32 [n]: by sequence position, the stored ring vertex a closed stroke is entered at, 0 for an open one,
+            {"closed", "moved", "candidates", "travel"})"""
+        po, pp, n, _keep = _step_paths(off, pts, n)
+        g, n = _groups(group, n)
+        st = _start_xy(start)
+        order = np.zeros(max(n, 1), np.int32); rev = np.zeros(max(n, 1), np.uint8); seam = np.zeros(max(n, 1), np.int32)
+        stats = np.zeros(4, np.int64)
+        self._ck(self.L.orip_gcode_order_rings(self.h, po, pp, _p(g) if g is not None and n else None, n, int(n_groups), _l.ORDER_REVERSE if reverse else 0,
+                                               _p(st), _p(order), _p(rev), _p(seam), _p(stats)))
+        return order[:n], rev[:n].astype(bool), seam[:n], {k: int(v) for k, v in zip(_l.RING_ENTRY_STATS, stats)}
+
     def gcode_merge(self, off, pts, group, n_groups: int, reverse: bool = False, n: int | None = None):
         """--merge-paths (include/orip.h: orip_gcode_merge): step polylines (off int64 [n + 1], pts int32 [total, 2]; both None = the n resident ones) that
         meet end to end inside a group become one stroke, and the merged polylines become the resident ones.  group int32 [n] or None (all 0).

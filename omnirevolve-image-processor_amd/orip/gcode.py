@@ -74,7 +74,15 @@ plans such ops (orip.stream.plan_ops), but no vector front door made any.  The p
 whole drawing, each at least --stipple-inset-mm from its shape's outline (orip_svg_stipple; include/orip.h states the rule, exact in integers on the step
 grid).  It runs after the simplification and immediately before the order: the dots pass through none of dash, link, occlude, dedup, merge or simplify
 (under --occlude the pass itself leaves out the dots a higher shape hides) and join the strokes as one-point ops, which the orders, --improve-order and
-the pens take like any stroke; --loop-start sees a dot as the open stroke P, P.  Without the option no device call is added and every byte is what it was."""
+the pens take like any stroke; --loop-start sees a dot as the open stroke P, P.  Without the option no device call is added and every byte is what it was.
+
+--ring-entry (ours as well): the greedy order and --allow-reverse see a closed stroke as the point its file lists first, and cross a shape to reach that
+point while its outline passes under the pen.  With --ring-entry the greedy walk has every ring vertex of every closed stroke as a candidate and enters a
+ring at the nearest one (orip_gcode_order_rings; include/orip.h states the rule: the same L1 key, ties to the lowest stroke and vertex; on a drawing
+without a closed stroke it is the plain order).  The call stands in the place of the order; the rings are then rotated to where they were entered, so
+--improve-order, --loop-start (which may still lower the travel), the plan and the preview see them there.  Greedy is not monotone: the pen-up travel is
+usually lower, and nothing promises it; the tools report it.  Not with --no-reorder: file order was asked for, and --loop-start is the option for that.
+Without the option no device call is added and every byte is what it was."""
 from __future__ import annotations
 
 import argparse
@@ -131,6 +139,7 @@ class GcodeOptions:
     clip_margin_mm: Optional[float] = None  # the clip rectangle lies this far inside the sheet (None: 0); only with clip
     simplify_mm: Optional[float] = None     # vertices within this distance of the stroke are dropped (None: every vertex is drawn; 0: only those on the stroke)
     dedup: bool = False                 # collinear segments of one pen that lie over each other are drawn once, the first drawn copy stays
+    ring_entry: bool = False            # the greedy order enters a closed stroke at its nearest ring vertex
     loop_start: bool = False            # every closed stroke starts and ends at the ring vertex that makes the pen-up travel of the plot least
     dash_mm: Optional[str] = None       # every path is drawn dashed: dash and gap lengths in mm, comma-separated (None: solid)
     dash_offset_mm: Optional[float] = None  # where in the pattern a path starts (None: 0); only with dash_mm
@@ -337,7 +346,7 @@ def build_stream_from_gcode(text_or_paths, opts: Optional[GcodeOptions] = None, 
                             timings: Optional[dict] = None, pens: Optional[np.ndarray] = None, order_pens_fn: Optional[Callable] = None,
                             source_fn: Optional[Callable] = None, merge_fn: Optional[Callable] = None, improve_fn: Optional[Callable] = None,
                             clip_fn: Optional[Callable] = None, simplify_fn: Optional[Callable] = None, dedup_fn: Optional[Callable] = None,
-                            dash_fn: Optional[Callable] = None, seam_fn: Optional[Callable] = None) -> Tuple[bytes, dict]:
+                            dash_fn: Optional[Callable] = None, seam_fn: Optional[Callable] = None, ring_entry_fn: Optional[Callable] = None) -> Tuple[bytes, dict]:
     """The stream of a G-code text (str / bytes) or of paths in mm given as (off, pts_mm); opts as parsed, --speed-scale not yet applied.
     Device steps, each None = the GPU (orip.device.Device; there is no CPU path in the product):
       steps_fn(off, pts_mm, map: dict) -> (off int64, pts int32 [total, 2])      orip_gcode_to_steps
@@ -367,12 +376,15 @@ def build_stream_from_gcode(text_or_paths, opts: Optional[GcodeOptions] = None, 
     and, only with --loop-start (after the order and the improvement, immediately before the paths are gathered):
       seam_fn(off, pts, order or None, rev or None) -> (seam int32 [n] by sequence position, stats)                                    orip_gcode_seam
     info["seam"] then holds closed, moved, travel_before and travel_after (pen-up steps of the whole plot).
+    and, only with --ring-entry (in the place of order_fn / order_pens_fn; without pens: one group):
+      ring_entry_fn(off, pts, group int32 [n], n_groups, reverse) -> (order, rev, seam int32 [n] by sequence position, stats)          orip_gcode_order_rings
+    info["ring_entry"] then holds closed, moved, candidates and travel (pen-up steps of the sequence as the call returned it).
     pens: one pen per input path, 0..7, or -1 for --color-index (a text's T words under --tool-pens when None).  info["pens"] then counts the paths per
     pen, those that took --color-index ("unmatched") and the strokes drawn backwards ("reversed").
     Returns (bytes, counts)."""
     steps = StrokeSteps(clip_fn if opts is not None and opts.clip else steps_fn, source_fn, merge_fn, simplify_fn, order_fn, order_pens_fn, improve_fn, codes_fn, pack_fn,
                         dedup_fn)
-    return stroke_stream(text_or_paths, opts, device, steps, timings, pens, dash_fn=dash_fn, seam_fn=seam_fn)
+    return stroke_stream(text_or_paths, opts, device, steps, timings, pens, dash_fn=dash_fn, seam_fn=seam_fn, ring_entry_fn=ring_entry_fn)
 
 
 # The device steps of the stroke pipeline, each a callable or None = not given; build_stream_from_gcode states the signatures.  convert: steps_fn or, with --clip, clip_fn
@@ -429,8 +441,16 @@ class Seam:
         self.fn = fn
 
 
+class RingEntry:
+    """--ring-entry, which StrokeSteps does not carry: fn(off, pts, group int32 [n], n_groups, reverse) -> (order int32 [n], rev bool [n], seam int32 [n]:
+    by sequence position, the stored ring vertex a closed stroke is entered at, 0 for an open one; stats) or None = the device (orip_gcode_order_rings)"""
+    def __init__(self, fn=None):
+        self.fn = fn
+
+
 def resolve_steps(st: StrokeSteps, o, grouped: bool, device=None, convert: Optional[Callable] = None, force: bool = False, occlude: Optional[Occlude] = None,
-                  dash: Optional[Dash] = None, seam: Optional[Seam] = None, hatch_link: Optional[HatchLink] = None, stipple: Optional[Stipple] = None):
+                  dash: Optional[Dash] = None, seam: Optional[Seam] = None, hatch_link: Optional[HatchLink] = None, stipple: Optional[Stipple] = None,
+                  ring_entry: Optional[RingEntry] = None):
     """The steps the options need, those not given taken from a device -> (steps, device); codes and pack stay as given (orip.stream.compile_plan fills them).
     When none is missing, and the caller does not `force` a device for steps of its own, no device is made and orip.stages is not imported.  convert(device)
     -> the conversion of a front door whose paths are on the device already (orip.svg).  Dedup, merge and simplify work on the polylines the pass before them
@@ -442,11 +462,15 @@ def resolve_steps(st: StrokeSteps, o, grouped: bool, device=None, convert: Optio
     fn is filled in the same way, and it stands between the dash pass and the occlusion; it needs the sources, and its rings are fitted paths as the
     occlusion's are, so behind a given pass the strokes are uploaded first in the same way (a link pass without rings makes them the resident list).
     `stipple`: its fn is filled in the same way; it reads the fitted paths and touches no stroke, so it needs nothing resident behind the fit.  With it
-    the seam pass is always sent its strokes: the dots among them are in no resident list."""
-    need = ["convert", "order"] + ["order_pens", "source"] * bool(grouped) + ["merge"] * bool(o.merge_paths) + ["improve"] * bool(o.improve_order) + \
+    the seam pass is always sent its strokes: the dots among them are in no resident list.  `ring_entry`: its fn is filled in the same way and reads or is
+    sent the strokes exactly as the seam pass is; it stands in the place of both orders, which are then not needed, and it rotates the rings on the host, so
+    behind it the seam pass is always sent its strokes."""
+    plain = ring_entry is None
+    need = ["convert"] + ["order"] * plain + (["order_pens"] * plain + ["source"]) * bool(grouped) + ["merge"] * bool(o.merge_paths) + ["improve"] * bool(o.improve_order) + \
         ["simplify"] * (o.simplify_mm is not None) + ["dedup"] * bool(o.dedup) + ["source"] * (occlude is not None or dash is not None or hatch_link is not None)
     if not force and all(getattr(st, k) is not None for k in need) and (occlude is None or occlude.fn is not None) and (dash is None or dash.fn is not None) and \
-            (seam is None or seam.fn is not None) and (hatch_link is None or hatch_link.fn is not None) and (stipple is None or stipple.fn is not None):
+            (seam is None or seam.fn is not None) and (hatch_link is None or hatch_link.fn is not None) and (stipple is None or stipple.fn is not None) and \
+            (plain or ring_entry.fn is not None):
         return st, device
     if device is None:
         from .stages import device as _default_device
@@ -480,7 +504,10 @@ def resolve_steps(st: StrokeSteps, o, grouped: bool, device=None, convert: Optio
             return device.svg_hatch_link(cls, ring_sub, ring_group, m, clamp, reach, n=len(off) - 1)
         hatch_link.fn = own_link
     if seam is not None and seam.fn is None:
-        seam.fn = (lambda off, pts, order, rev: device.gcode_seam(None, None, order, rev, n=len(off) - 1)) if after_simplify and stipple is None else device.gcode_seam
+        seam.fn = (lambda off, pts, order, rev: device.gcode_seam(None, None, order, rev, n=len(off) - 1)) if after_simplify and stipple is None and plain else device.gcode_seam
+    if not plain and ring_entry.fn is None:
+        ring_entry.fn = (lambda off, pts, group, n_groups, reverse: device.gcode_order_rings(None, None, group, n_groups, reverse, n=len(off) - 1)) \
+            if after_simplify and stipple is None else device.gcode_order_rings
     if stipple is not None and stipple.fn is None:
         stipple.fn = device.svg_stipple
     if dash is not None and dash.fn is None:
@@ -679,13 +706,41 @@ def _checked_order(order, rev, n: int, group, reverse: bool, what: str):
     return order, rev
 
 
-def _order(st: StrokeSteps, o: GcodeOptions, off, pts, group, n_groups: int, info: dict, lap):
-    """the drawing sequence (order, rev), or (None, None) for the strokes as they stand: pen after pen (group given) or as one list, greedy and then improved"""
+def _ring_entry(rge: RingEntry, o: GcodeOptions, off, pts, group, n_groups: int, info: dict):
+    """--ring-entry: the greedy sequence with every closed stroke entered at its nearest ring vertex -> (pts with every ring rotated in place to the vertex
+    it was entered at, (order, rev)); info["ring_entry"].  Checked as _checked_order checks, and: the seams name a ring vertex of every closed stroke and are
+    0 elsewhere, no closed stroke is reversed, the counts add up and the travel is that of the strokes as gathered"""
+    n = len(off) - 1
+    grp = np.zeros(n, np.int32) if group is None else np.asarray(group, np.int32)
+    order, rev, seam, rst = rge.fn(off, pts, grp, n_groups if group is not None else 1, bool(o.allow_reverse))
+    order, rev = _checked_order(order, rev, n, grp, bool(o.allow_reverse), "the ring order is not a permutation that keeps the pens together and the directions allowed")
+    seam = np.asarray(seam, np.int64).reshape(-1)
+    d = {k: int(rst[k]) for k in RING_ENTRY_STATS}
+    lens = np.diff(off)[order]
+    closed = (lens >= 4) & (pts[off[:-1][order]] == pts[off[1:][order] - 1]).all(1)
+    if len(seam) != n or (seam < 0).any() or (seam[~closed] != 0).any() or (seam[closed] >= lens[closed] - 1).any() or rev[closed].any():
+        raise RuntimeError("the ring order's seams do not name a ring vertex of every closed stroke, forwards, and 0 for every open one")
+    candidates = int(np.where(closed, lens - 1, 1 + bool(o.allow_reverse)).sum())
+    if d["closed"] != int(closed.sum()) or d["moved"] != int((seam != 0).sum()) or d["candidates"] != candidates or \
+            d["travel"] != travel_steps(*gather_paths(off, pts, order, rev, seam)):
+        raise RuntimeError("the ring order's counts do not add up")
+    info["ring_entry"] = d
+    by_stroke = np.zeros(n, np.int64); by_stroke[order] = seam
+    return gather_paths(off, pts, np.arange(n), None, by_stroke)[1], (order, rev)
+
+
+def _order(st: StrokeSteps, o: GcodeOptions, off, pts, group, n_groups: int, info: dict, lap, greedy=None):
+    """the drawing sequence (order, rev), or (None, None) for the strokes as they stand: pen after pen (group given) or as one list, greedy and then improved.
+    greedy: the checked sequence --ring-entry has found already, in the place of either greedy order"""
     n = len(off) - 1
     if o.no_reorder:                                                      # pen after pen all the same, file order inside a pen
         return (np.argsort(group, kind="stable"), np.zeros(n, bool)) if group is not None else (None, None)
     ends, reverse = path_ends(off, pts), bool(o.allow_reverse)
-    if group is not None:
+    if greedy is not None:
+        order, rev = greedy
+        if group is None:
+            group, n_groups = np.zeros(n, np.int32), 1
+    elif group is not None:
         order, rev = _checked_order(*st.order_pens(ends, group, n_groups, reverse), n, group, True, "the path order is not a permutation that keeps the pens together")
     else:                                                                 # one group, no stroke reversed
         group, n_groups = np.zeros(n, np.int32), 1
@@ -695,6 +750,8 @@ def _order(st: StrokeSteps, o: GcodeOptions, off, pts, group, n_groups: int, inf
         order, rev, ist = st.improve(ends, group, n_groups, np.asarray(order, np.int32), rev, reverse, o.improve_rounds)
         order, rev = _checked_order(order, rev, n, group, reverse, "the improved order is not a permutation that keeps the pens together and the directions allowed")
         info["improve"] = {k: int(ist[k]) for k in IMPROVE_STATS}
+        if greedy is not None and info["improve"]["travel_before"] != info["ring_entry"]["travel"]:
+            raise RuntimeError("the ring order and the improvement count different pen-up steps for the same sequence")
         lap("improve")
     return order, rev
 
@@ -747,6 +804,8 @@ def _seam(sm: Seam, off, pts, order, rev, info: dict, is_tap=None):
         raise RuntimeError("the seam pass's counts do not add up")
     if "improve" in info and d["travel_before"] != info["improve"]["travel_after"]:
         raise RuntimeError("the seam pass and the improvement count different pen-up steps for the same sequence")
+    if "ring_entry" in info and "improve" not in info and d["travel_before"] != info["ring_entry"]["travel"]:
+        raise RuntimeError("the seam pass and the ring order count different pen-up steps for the same sequence")
     info["seam"] = d
     return goff, gpts
 
@@ -764,10 +823,12 @@ def _plan(o: GcodeOptions, sc: ST.StreamConfig, off, pts, path_pen, is_tap=None)
 
 def stroke_stream(text_or_paths, opts: Optional[GcodeOptions], device, steps: StrokeSteps, timings: Optional[dict] = None, pens: Optional[np.ndarray] = None,
                   occlude: Optional[Occlude] = None, dash: Optional[Dash] = None, dash_fn: Optional[Callable] = None, seam_fn: Optional[Callable] = None,
-                  seam: Optional["Seam"] = None, hatch_link: Optional[HatchLink] = None, stipple: Optional[Stipple] = None) -> Tuple[bytes, dict]:
+                  seam: Optional["Seam"] = None, hatch_link: Optional[HatchLink] = None, stipple: Optional[Stipple] = None,
+                  ring_entry_fn: Optional[Callable] = None, ring_entry: Optional[RingEntry] = None) -> Tuple[bytes, dict]:
     """build_stream_from_gcode with the device steps as one record: parse, convert, pens of the strokes, [dash: --dash-mm gives every path the one pattern,
     with dash_fn; the SVG door brings a record of its own], [hatch_link, the SVG door's], [occlude, the SVG door's], dedup, merge, simplify, [stipple, the
-    SVG door's: its dots join the strokes as one-point ops], order, [seam: --loop-start, with seam_fn, or the record a door has resolved already], plan, compile"""
+    SVG door's: its dots join the strokes as one-point ops], order [ring_entry: --ring-entry in the greedy order's place, with ring_entry_fn, or the record a
+    door has resolved already], [seam: --loop-start, with seam_fn, or the record a door has resolved already], plan, compile"""
     import time
     o = apply_speed_scale(GcodeOptions(**{f.name: getattr(opts, f.name) for f in fields(GcodeOptions)}) if opts is not None else GcodeOptions())
     W, H = target_size(o)
@@ -805,7 +866,8 @@ def stroke_stream(text_or_paths, opts: Optional[GcodeOptions], device, steps: St
     if own_dash is not None and dash is None:                             # --dash-mm: every path gets the pattern
         dash = Dash(dash_fn, np.zeros(len(off_mm) - 1, np.int32), np.full(len(off_mm) - 1, own_dash[1], np.int64), [0, len(own_dash[0])], own_dash[0])
     sm = (seam if seam is not None else Seam(seam_fn)) if o.loop_start else None
-    st, device = resolve_steps(steps, o, grouped, device, occlude=occlude, dash=dash, seam=sm, hatch_link=hatch_link, stipple=stipple)
+    rge = (ring_entry if ring_entry is not None else RingEntry(ring_entry_fn)) if o.ring_entry else None
+    st, device = resolve_steps(steps, o, grouped, device, occlude=occlude, dash=dash, seam=sm, hatch_link=hatch_link, stipple=stipple, ring_entry=rge)
     m = dict(scale_x=o.scale_x, scale_y=o.scale_y, offset_x_mm=o.offset_x_mm, offset_y_mm=o.offset_y_mm, steps_per_mm=o.steps_per_mm, W=W, H=H, invert_y=int(bool(o.invert_y)))
 
     def finish(off, pts, pen, group):
@@ -830,7 +892,10 @@ def stroke_stream(text_or_paths, opts: Optional[GcodeOptions], device, steps: St
             lap("stipple")
         if len(off) <= 1:                                                 # neither a stroke nor a dot
             return EMPTY_STREAM, dict(info, bytes=len(EMPTY_STREAM))
-        order, rev = _order(st, o, off, pts, group, n_groups, info, lap)
+        greedy = None
+        if rge is not None:                                               # in the greedy order's place; everything behind sees a ring where it is entered
+            pts, greedy = _ring_entry(rge, o, off, pts, group, n_groups, info)
+        order, rev = _order(st, o, off, pts, group, n_groups, info, lap, greedy)
         if sm is not None:
             lap("order")
             off, pts = _seam(sm, off, pts, order, rev, info, is_tap)
@@ -910,6 +975,7 @@ HATCH_LINK_REACH_MAX = 1 << 20                # include/orip.h: ORIP_HATCH_LINK_
 STIPPLE_STATS = ("groups", "rows", "candidates", "near", "outside", "hidden", "dots")      # include/orip.h: orip_gcode_stipple
 STIPPLE_SERPENTINE, STIPPLE_OCCLUDE, STIPPLE_MAX = 1, 2, 1 << 20      # include/orip.h: ORIP_STIPPLE_SERPENTINE, ORIP_STIPPLE_OCCLUDE; pitch, row and inset at most
 SEAM_STATS = ("closed", "moved", "travel_before", "travel_after")      # include/orip.h: orip_gcode_seam
+RING_ENTRY_STATS = ("closed", "moved", "candidates", "travel")         # include/orip.h: orip_gcode_order_rings
 DASH_UNIT, DASH_MAX_ENTRIES = 256, 64         # include/orip.h: ORIP_DASH_UNIT (dash lengths are in 1/256 step), ORIP_DASH_MAX_ENTRIES
 SIMPLIFY_TOL4_MAX = (1 << 17) - 1             # include/orip.h: ORIP_SIMPLIFY_TOL4_MAX
 
@@ -994,6 +1060,8 @@ def stroke_options(o) -> Tuple[Optional[Tuple[int, int, int, int]], Optional[int
         raise ValueError("--improve-rounds needs --improve-order")
     if o.improve_rounds is not None and int(o.improve_rounds) < 0:
         raise ValueError("--improve-rounds must not be negative")
+    if o.ring_entry and o.no_reorder:
+        raise ValueError("--ring-entry with --no-reorder: file order was asked for (--loop-start chooses the seams of a given order)")
     return clip_rect(o), simplify_tol4(o)
 
 
@@ -1001,6 +1069,11 @@ def improve_line(tag: str, st: dict) -> str:
     saved = st["travel_before"] - st["travel_after"]
     return (f"[{tag}] improve: pen-up steps {st['travel_before']} -> {st['travel_after']} ({saved} saved), {st['rounds']} rounds, "
             f"{st['converged_groups']} groups converged, {st['skipped_groups']} skipped")
+
+
+def ring_entry_line(tag: str, st: dict) -> str:
+    return (f"[{tag}] ring entry: {st['closed']} closed strokes, {st['moved']} entered away from their first vertex, {st['candidates']} candidates, "
+            f"pen-up steps {st['travel']} behind the greedy order")
 
 
 def seam_line(tag: str, st: dict) -> str:
@@ -1044,6 +1117,8 @@ def build_argparser() -> argparse.ArgumentParser:
     ap.add_argument("--dash-mm", default=None, help="draw every path dashed: 1..64 comma-separated lengths in mm, dash and gap in turn (an odd count is repeated, as "
                                                     "in SVG); each at least one step; the pattern starts anew with every path")
     ap.add_argument("--dash-offset-mm", type=float, default=None, help="where in the pattern a path starts (any sign; default 0); needs --dash-mm")
+    ap.add_argument("--ring-entry", action="store_true", help="let the greedy order enter a closed stroke at its nearest vertex instead of the one the file lists first "
+                                                              "(every ring vertex is a candidate; usually less pen-up travel, nothing promises it); not with --no-reorder")
     return ap
 
 
@@ -1103,6 +1178,8 @@ def report_lines(tag: str, info: dict, unmatched: bool = False):
         d = info["stipple"]
         yield (f"[{tag}] stipple: {d['dots']} dots in {d['groups']} shapes (pitch {d['pitch']}, rows {d['row']}; {d['near']} near the outline, "
                f"{d['outside']} off the sheet, {d['hidden']} hidden)")
+    if "ring_entry" in info:
+        yield ring_entry_line(tag, info["ring_entry"])
     if "improve" in info:
         yield improve_line(tag, info["improve"])
     if "seam" in info:

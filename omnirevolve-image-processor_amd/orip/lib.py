@@ -89,6 +89,7 @@ SIGNATURES = {
     "orip_gcode_dash": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp]), "orip_gcode_dash_fetch": (_i32, [_vp, _vp]),
     "orip_gcode_improve": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _i64, _vp, _vp, _vp]),
     "orip_gcode_seam": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "orip_gcode_order_rings": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "orip_svg_flatten": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _f64, _P(_i64)]), "orip_svg_paths_fetch": (_i32, [_vp, _vp, _vp]),
     "orip_svg_bbox": (_i32, [_vp, _vp]), "orip_svg_fit": (_i32, [_vp, _f64, _f64, _f64, _f64]),
     "orip_svg_hatch": (_i32, [_vp, _vp, _i64, _f64, _i32, _i32, _i32, _vp]), "orip_svg_hatch_groups_fetch": (_i32, [_vp, _vp]),
@@ -116,6 +117,7 @@ DASH_STATS = ("paths_in", "dashed", "dashes", "collapsed", "paths_out", "points_
 DASH_UNIT, DASH_MAX_ENTRIES = 256, 64                        # include/orip.h: dash lengths are in 1/256 step; entries of one pattern at most
 IMPROVE_MAX_PATHS, IMPROVE_ROUNDS_AUTO = 65536, (1 << 63) - 1
 SEAM_STATS = ("closed", "moved", "travel_before", "travel_after")
+RING_ENTRY_STATS = ("closed", "moved", "candidates", "travel")
 
 _lib = None
 

@@ -678,6 +678,7 @@ class SvgOptions:
     simplify_mm: Optional[float] = None                 # vertices within this distance of the stroke are dropped (orip.gcode); None: none are
     dedup: bool = False                                 # collinear segments of one pen that lie over each other are drawn once (orip.gcode)
     loop_start: bool = False                            # closed strokes start at the vertex that makes the pen-up travel least (orip.gcode)
+    ring_entry: bool = False                            # the greedy order enters a closed stroke at its nearest ring vertex (orip.gcode)
     occlude: bool = False                               # filled shapes hide what lies under them (svg2stream.py only)
     dashes: bool = False                                # stroke-dasharray is drawn as dashes (svg2stream.py only)
 
@@ -861,7 +862,7 @@ def gcode_options(o: SvgOptions) -> GC.GcodeOptions:
                            offset_x_mm=0.0, offset_y_mm=0.0, target_width_steps=W, target_height_steps=H, no_reorder=bool(o.no_reorder),
                            allow_reverse=bool(o.allow_reverse), pen_order=o.pen_order, merge_paths=bool(o.merge_paths),
                            improve_order=bool(o.improve_order), improve_rounds=o.improve_rounds, clip=bool(o.clip), clip_margin_mm=o.clip_margin_mm,
-                           simplify_mm=o.simplify_mm, dedup=bool(o.dedup), loop_start=bool(o.loop_start))
+                           simplify_mm=o.simplify_mm, dedup=bool(o.dedup), loop_start=bool(o.loop_start), ring_entry=bool(o.ring_entry))
 
 
 def gcode_text(off, pts, passes: int = 1, pens=None) -> str:
@@ -1043,7 +1044,7 @@ def build_stream_from_svg(text: Union[str, bytes, SegmentTable], opts: Optional[
                           order_pens_fn: Optional[Callable] = None, merge_fn: Optional[Callable] = None, improve_fn: Optional[Callable] = None,
                           clip_fn: Optional[Callable] = None, simplify_fn: Optional[Callable] = None, dedup_fn: Optional[Callable] = None,
                           occlude_fn: Optional[Callable] = None, dash_fn: Optional[Callable] = None, seam_fn: Optional[Callable] = None,
-                          hatch_link_fn: Optional[Callable] = None, stipple_fn: Optional[Callable] = None) -> Tuple[bytes, dict]:
+                          hatch_link_fn: Optional[Callable] = None, stipple_fn: Optional[Callable] = None, ring_entry_fn: Optional[Callable] = None) -> Tuple[bytes, dict]:
     """The stream of an SVG text (or of a parsed SegmentTable).  Device steps, each None = the GPU (there is no CPU path in the product):
       flatten_fn(table, tol_raw) -> paths          orip_svg_flatten      (`paths` is whatever the other steps take: on the GPU a count, the points stay there)
       bbox_fn(paths) -> (min x, min y, max x, max y)   orip_svg_bbox
@@ -1080,6 +1081,8 @@ def build_stream_from_svg(text: Union[str, bytes, SegmentTable], opts: Optional[
     counts of include/orip.h with the lattice, info["taps"] = the dots drawn.
     and, only with --loop-start:
       seam_fn                                      as in orip.gcode.build_stream_from_gcode (a circle, a <rect> and a closed <path> are closed strokes; hatch lines are open)
+    and, only with --ring-entry (in the place of order_fn / order_pens_fn):
+      ring_entry_fn                                as in orip.gcode.build_stream_from_gcode (the dots of --stipple-mm are open strokes of one point)
     With --pen-colors, info["path_pens"] is the pen of every fitted path (hatch lines included, --color-index where no stroke is stated).
     Returns (bytes, info)."""
     import time
@@ -1145,6 +1148,7 @@ def build_stream_from_svg(text: Union[str, bytes, SegmentTable], opts: Optional[
         lnk = GC.HatchLink(None if hatch_link_fn is None else (lambda off, pts, cls, rs, rg, m, clamp, r: hatch_link_fn(paths, off, pts, cls, rs, rg, m, clamp, r)),
                            hatch_classes(table, paths, info, hatch_groups_fn, off_mm, pts_mm, hp.get("u")), *hatch_link_rings(table), not o.clip, reach)
     sm = GC.Seam(seam_fn) if o.loop_start else None
+    rge = GC.RingEntry(ring_entry_fn) if o.ring_entry else None
     stp = None
     if sp is not None:
         W, H = GC.target_size(go)
@@ -1152,9 +1156,9 @@ def build_stream_from_svg(text: Union[str, bytes, SegmentTable], opts: Optional[
                          *hatch_link_rings(table), not o.clip, sp["lattice"], sp["inset"], GC.clip_rect(go) or (0, 0, W - 1, H - 1),
                          (0 if o.no_serpentine else GC.STIPPLE_SERPENTINE) | (GC.STIPPLE_OCCLUDE if o.occlude else 0),
                          (lambda groups: hatch_pens(table, groups, info["pen_colors"])) if pens_on else None)
-    steps, device = GC.resolve_steps(steps, go, pens_on or o.allow_reverse, device, force=bool(own), occlude=occ, dash=dsh, seam=sm, hatch_link=lnk, stipple=stp,
+    steps, device = GC.resolve_steps(steps, go, pens_on or o.allow_reverse, device, force=bool(own), occlude=occ, dash=dsh, seam=sm, hatch_link=lnk, stipple=stp, ring_entry=rge,
                                      convert=lambda dev: lambda _off, _pts, m, *rect: (_Resident(dev).clip if rect else _Resident(dev).steps)(paths, m, *rect))
-    data, ginfo = GC.stroke_stream((off_mm, np.zeros((int(off_mm[-1]), 2))), go, device, steps, tm, pens, occ, dsh, seam=sm, hatch_link=lnk, stipple=stp)
+    data, ginfo = GC.stroke_stream((off_mm, np.zeros((int(off_mm[-1]), 2))), go, device, steps, tm, pens, occ, dsh, seam=sm, hatch_link=lnk, stipple=stp, ring_entry=rge)
     if "dash" in ginfo or ignored:                          # an ignored dash array is reported whether or not a pass ran: the stroke is solid, and the line says so
         ginfo["dash"] = dict(ginfo.get("dash", {}), ignored=ignored)
     return data, dict(ginfo, **info)
@@ -1213,6 +1217,8 @@ def build_stream_argparser() -> argparse.ArgumentParser:
                                                            "exact on the step grid; the G-code file is not changed")
     ap.add_argument("--loop-start", action="store_true", help="start and end every closed stroke (a circle, a rectangle, a closed path) at the vertex that makes the pen-up "
                                                               "travel of the whole plot least, all of them chosen together, after the order; the G-code file is not changed")
+    ap.add_argument("--ring-entry", action="store_true", help="let the greedy order enter a closed stroke (a circle, a rectangle, a closed path) at its nearest vertex instead "
+                                                              "of the one it lists first; not with --no-reorder; the G-code file is not changed")
     ap.add_argument("--dashes", action="store_true", help="draw a stroke that states a stroke-dasharray as its dashes, measured on the step grid from the start of "
                                                           "every stroke (hatch lines stay solid); the G-code file is not changed")
     ap.add_argument("--hatch-connect", action="store_true", help="draw a hatch as zigzags: join consecutive hatch lines of one shape by straight links that lie wholly "

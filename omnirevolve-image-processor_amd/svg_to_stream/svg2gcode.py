@@ -7,6 +7,7 @@ CPU path.  The points chosen for a curve are this project's, held to the curve w
                          [--hatch-spacing-mm S [--hatch-inset-mm I] [--hatch-direction horizontal|vertical|cross] [--no-serpentine] [--hatch-fill stated|all]
                           [--hatch-angle-deg A]]      (ours: the hatch along any angle, exact on the step grid)
                          [--pen-colors rgbk|LIST]      (ours: a T<pen> line wherever the pen changes)
+The options that only change how the stream is drawn (--ring-entry, --loop-start and the other stroke passes) belong to svg2stream.py: this file is the same with them.
 """
 import os
 import sys

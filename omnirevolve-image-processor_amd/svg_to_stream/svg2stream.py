@@ -6,6 +6,7 @@ decoded and drawn on the GPU into <stem>_stream_preview.png (orip.stream_preview
 
     python svg2stream.py drawing.svg [-o stream.bin] [--gcode-output drawing.gcode] [--steps-per-mm 40] [--scale S] [--no-reorder] [--no-preview] [--hatch-spacing-mm S [--hatch-angle-deg A] [--hatch-connect [--hatch-connect-mm M]] ...] ...
                           [--pen-colors rgbk|LIST [--pen-order 3,0,...]] [--allow-reverse]      (ours: a pen per stroke colour, drawn pen after pen)
+                          [--ring-entry] [--loop-start]      (ours: the order enters a circle, a rectangle or a closed path at its nearest vertex; the G-code file is not changed)
 """
 import os
 import sys

@@ -4,7 +4,7 @@
 //                         planes of a word with their carry-save count and transition test, the Zhang-Suen delete word, the block-wide popcount position
 //   kernel templates      k_ccl_bits<Ids>, k_pack_bits<Pred>, k_compact_write_bits<Emit> over small plain policy structs.  Each instantiation is compiled
 //                         in exactly ONE unit (the rule of vec_common.h): <IdsBlockRaster> and <PackBytes> (stages 02 and 04 both pack bytes: bp_pack_bytes)
-//                         in bitplane.hip, <PackLabels> in raster02.hip, <Emit04> in raster04.hip, <IdsLinear> / <PackWords> / <Emit08> in vector08b.hip
+//                         in bitplane.hip, <PackLabels> in raster02.hip, <Emit04> in raster04.hip, <IdsLinear> / <Emit08> in vector08b.hip (whose stamps set their own bits: it packs nothing)
 //   bitplane.hip          the kernels that need no policy (bits -> bytes, compaction count, segment heads, component starts) behind the bp_* launchers,
 //                         and orip_ccl_bits, the CCL driver of stages 03 / 04
 #pragma once
@@ -161,7 +161,6 @@ __global__ __launch_bounds__(256) void k_ccl_bits(const unsigned long long* __re
 // LAYERED: blockIdx.z = layer, one bit plane per layer; SRC_LAYERED: one source plane per layer as well (else all layers read the same plane)
 struct PackBytes { typedef u8 E; static constexpr bool LAYERED = true, SRC_LAYERED = true; static __device__ bool on(u8 v, unsigned) { return v != 0; } };                 // stages 02 / 04: [K][H][W] bytes
 struct PackLabels { typedef u8 E; static constexpr bool LAYERED = true, SRC_LAYERED = false; static __device__ bool on(u8 v, unsigned layer) { return v == layer; } };    // stage 02: one label plane -> K masks
-struct PackWords { typedef unsigned E; static constexpr bool LAYERED = false, SRC_LAYERED = false; static __device__ bool on(unsigned v, unsigned) { return v != 0; } };  // stage 08-B: the group canvas
 template <class Pred>
 __global__ __launch_bounds__(256) void k_pack_bits(const typename Pred::E* __restrict__ src, unsigned long long* __restrict__ bits, int H, int W, int Ww) {
     const size_t nw = (size_t)H * Ww, w0 = ((size_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 64;

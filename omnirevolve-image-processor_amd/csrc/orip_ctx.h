@@ -179,7 +179,9 @@ static_assert(sizeof(LaneFlags) <= 4096, "LaneRes::flags is 4096 bytes, allocate
 // each on its own HIP stream with its own scratch (the serial kernels of one layer then overlap with those of the others).
 // Lifetimes.  A buffer is FREE BETWEEN ENTRY POINTS (any call on the lane may resize and overwrite it) unless this table names it; a named vtmp slot is only
 // ever indexed by its constant on that lane.
-//   lane 0  vtmp[VT0_MEMO]       memo planes of the walker     orip_contours_reserve (cleared there) or orip_contours_prepare -> last trace of the prepare
+//   lane 0  vtmp[VT0_MEMO]       memo planes of the walker     orip_contours_reserve or orip_contours_prepare (sized there) -> last trace of the prepare.  Never
+//           cleared as a whole: a word is meaningful only at a skeleton pixel of the current prepare, where trace_launch has zeroed it in front of the
+//           layer's k_trace; anything elsewhere is stale and never read (WalkArgs::memo)
 //   lane 0  vtmp[VT0_EDGE_BITS]  bit planes of `edges`         orip_detect_edges (c->edge_bits) -> the next orip_contours_prepare, which thins in them
 //           its second set (orip_edge_planes: b) then holds the degree-2 planes: k_bits_to_skel_state of that prepare -> lane 0's ev3, while the chain kernels
 //           step on them on the side stream; only a prepare's thinning writes it again, behind ev3 (orip_detect_edges sizes it and writes the first set only)
@@ -218,7 +220,7 @@ static_assert(sizeof(LaneFlags) <= 4096, "LaneRes::flags is 4096 bytes, allocate
 //                         VTL_TAIL_RUNS A2 -> A6: the block-local tail sums (8 MS bytes; k_samples -> k_tail_par), then the last-in scan and then the
 //                         survivors in its first 4 MS bytes, and orip_runs_to_polys takes the slot once A6 is enqueued;
 //                         VTL_CAPS A4; A7's split_small finds everything but tp[] free
-//   08-B (vector08b.hip)  VTL_FEAT (features, parents, groups) groups -> paths; canvas (group ids) raster -> paths; VTL_STEPLOG (bit planes, skeleton bytes)
+//   08-B (vector08b.hip)  VTL_FEAT (features, parents, groups) groups -> paths; canvas (group ids, defined at this call's stamped pixels only: B08::gid) raster -> paths; VTL_STEPLOG (bit planes)
 //                         raster -> paths; VTL_SPLIT_FEAT (labels) and VTL_RANKS (block counts) within components; VTL_CUM (sorted pixels), VTL_CAPS (component
 //                         tables) components -> paths; VTL_SAMPLES (heads) within components; VTL_CELLS within paths.  Calls vfeatures (first, into
 //                         VTL_FEAT), vscan_excl, vsort_pairs and, last, vgather
@@ -239,7 +241,7 @@ enum { VTL_RANKS = 0,           // 08-A: perimeter sort, order, samples per rank
        VTL_FEAT = 6,            // features: 08-A kept polylines | 08-B lines, parents, groups | vreorder (07, 08 C, 10, 12): features, ends, order | 12: features, alive flags
        VTL_RUN_STARTS = 7,      // orip_runs_to_polys: accepted slots and run starts per tile, scanned in place
        VTL_TAIL_RUNS = 8,       // 08-A: block-local tail sums -> last-in scan -> survivors, THEN orip_runs_to_polys: per run its first slot, rank and keep / length key, per kept run its first slot
-       VTL_STEPLOG = 9,         // 04: step log of the layer's trace (between entry points, see above) | 08-B: skeleton bytes, thinning bit planes | 10: seed, distance, occupancy planes
+       VTL_STEPLOG = 9,         // 04: step log of the layer's trace (between entry points, see above) | 08-B: thinning bit planes | 10: seed, distance, occupancy planes
        VTL_SPLIT_FEAT = 10,     // split_small: features of its source list | 08-B: union-find labels of the padded raster | 10: features of the cut lines
        VT_LEAVES = 11,          // wherever vfeatures runs: its perimeter leaves and length order, and those of the stage-08 prefetch (between entry points, see above) | 04 with ORIP_WALK_DBG: per-component debug counters of the trace
        VT_SLOTS = 12 };
@@ -447,7 +449,6 @@ struct orip_ctx {
     // sums, mind2 int32[n_init, an_D] and labels u8[n_init, an_D] (free between calls)
     DBuf an_table, an_keys, an_counts, an_tmp, an_km; int64_t an_D = 0, an_kept = 0; bool an_ready = false;
     DBuf resize_src, resize_dst;                       // raster01.hip staging
-    int memo_pre_K = 0, memo_pre_H = 0, memo_pre_W = 0; // orip_contours_reserve cleared this many memo planes of an H x W image
     // profiling
     bool prof_on = false;
     std::map<std::string, ProfEntry> prof;

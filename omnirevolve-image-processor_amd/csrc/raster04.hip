@@ -251,9 +251,8 @@ struct Prep04 {
     std::vector<unsigned> h_cs, layer_first;       // comp_start on the host; first component of every layer (+ sentinel)
     const unsigned* order = nullptr;                // components by (layer, size descending)
     WalkArgs A;                                     // shared arguments (state bytes, keys, lin, comp_start, memo, winfo, total_fg)
-    unsigned F[ORIP_MAX_LAYERS];                    // log capacity factor of the trace in flight
+    unsigned F[ORIP_MAX_LAYERS];                    // log capacity factor of the layer's latest trace; 0: not traced since the prepare
     bool launched[ORIP_MAX_LAYERS];
-    bool memo_clear[ORIP_MAX_LAYERS];               // the layer's memo plane was zeroed on its lane while the raster part ran
     bool chains = false;                            // forced stretches are listed (cref / cpix) and flagged in the state plane
 };
 void orip_contours_free(orip_ctx* c) { delete static_cast<Prep04*>(c->prep04); c->prep04 = nullptr; }
@@ -283,6 +282,11 @@ __global__ __launch_bounds__(256) void k_clear_visited_layer(u8* __restrict__ st
     int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i < m) st[lin[i]] &= (u8)~ST_VIS;
 }
+// zeroes the eight memo words of every skeleton pixel of one layer (m2 = two 16-byte halves per pixel of lin; neighbouring lanes share a 32-byte line)
+__global__ __launch_bounds__(256) void k_clear_memo_layer(uint4* __restrict__ memo, const unsigned* __restrict__ lin, int64_t m2) {
+    int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < m2) memo[((size_t)lin[i >> 1] << 1) | (size_t)(i & 1)] = make_uint4(0u, 0u, 0u, 0u);
+}
 __global__ __launch_bounds__(256) void k_kept_slots_base(const unsigned* __restrict__ kept, const unsigned* __restrict__ path_off, const unsigned long long* __restrict__ pts_off, unsigned n, unsigned base,
                                                          unsigned* __restrict__ slots, unsigned long long* __restrict__ slot_off) {
     unsigned i = blockIdx.x * 256 + threadIdx.x;
@@ -291,22 +295,15 @@ __global__ __launch_bounds__(256) void k_kept_slots_base(const unsigned* __restr
 
 // Everything of stage 04 that is batched over the layers: thinning, components, state bytes, the raster-ordered pixel list
 // sorted by component, the per-layer schedule.  Runs on lane 0 and ends synchronised.
-// Hint for the resident chain: the image is set and K layers will be traced.  Clears the K memo planes on the layer lanes NOW -- at the start of a
-// step the card is idle but for the k-means fit, whereas 4 GB of fills issued from orip_contours_prepare run into stages 02 / 03 -- and
-// orip_contours_prepare then skips its own clearing (the planes' lifetime: orip_ctx.h, LaneRes).
+// Hint for the resident chain: the image is set and K layers will be traced.  Ends the schedule of the previous image and makes sure the K memo planes
+// are allocated NOW, so that a growing hipMalloc happens at the start of a step and not in front of the walks.  It clears nothing: the planes are never
+// cleared as a whole (WalkArgs::memo), every trace_launch zeroes the words its walk can read.
 extern "C" int orip_contours_reserve(orip_ctx* c, int K) {
     orip_enter(c);
     if (!c->image.p || c->H <= 0 || c->W <= 0) ORIP_FAIL(c, "no image set");
     if (K < 1 || K > ORIP_MAX_LAYERS) ORIP_FAIL(c, "K=%d out of range 1..%d", K, ORIP_MAX_LAYERS);
     ORIP_TRY(orip_contours_invalidate(c));
-    const size_t plane = (size_t)c->H * c->W;
-    c->memo_pre_K = 0;
-    HIPC(c, LN(c).vtmp[VT0_MEMO].ensure(plane * (size_t)K * 8 * 4 + 64));
-    for (int l = 0; l < K; l++) {
-        ORIP_LANE(c, l + 1);
-        HIPC(c, hipMemsetAsync(c->ln[0].vtmp[VT0_MEMO].as<unsigned>() + plane * 8 * l, 0, plane * 8 * 4, LN(c).stream));
-    }
-    c->memo_pre_K = K; c->memo_pre_H = c->H; c->memo_pre_W = c->W;
+    HIPC(c, LN(c).vtmp[VT0_MEMO].ensure((size_t)c->H * c->W * (size_t)K * 8 * 4 + 64));
     return 0;
 }
 
@@ -320,20 +317,11 @@ extern "C" int orip_contours_prepare(orip_ctx* c) {
     ORIP_TRY(orip_contours_invalidate(c));      // (traces of the previous prepare still in flight write the lane-0 state rewritten below)
     Prep04& R = *static_cast<Prep04*>(c->prep04);
     R.K = K;
-    for (int l = 0; l < ORIP_MAX_LAYERS; l++) { R.launched[l] = false; R.F[l] = 0; R.memo_clear[l] = false; }
+    for (int l = 0; l < ORIP_MAX_LAYERS; l++) { R.launched[l] = false; R.F[l] = 0; }
     const size_t plane = (size_t)H * W; const int64_t n = (int64_t)plane * K;
-    // the memo planes (one word per pixel and incoming direction, 0.5 GB per layer at 4096^2) are cleared on the layer lanes, not in front of
-    // every layer's trace: by orip_contours_reserve at the start of the step when the caller gave that hint, else now, underneath the raster work below
-    const bool pre = c->memo_pre_K >= K && c->memo_pre_H == H && c->memo_pre_W == W;
-    c->memo_pre_K = 0;
+    // the memo planes (one word per pixel and incoming direction, 0.5 GB per layer at 4096^2) are only sized here: trace_launch zeroes the words of the
+    // layer's skeleton pixels, the only ones its walk reads (WalkArgs::memo)
     HIPC(c, LN(c).vtmp[VT0_MEMO].ensure(plane * (size_t)K * 8 * 4 + 64));
-    for (int l = 0; l < K; l++) {
-        if (!pre) {
-            ORIP_LANE(c, l + 1);
-            HIPC(c, hipMemsetAsync(c->ln[0].vtmp[VT0_MEMO].as<unsigned>() + plane * 8 * l, 0, plane * 8 * 4, LN(c).stream));
-        }
-        R.memo_clear[l] = true;
-    }
     // ---- thinning_zhangsuen (04:35-99): <=120 iterations of two sub-iterations, until nothing is deleted.  On bit planes (2 MB per 4096^2
     // layer): pack, iterate, then skeleton and state bytes in one unpacking pass
     HIPC(c, c->skel.ensure(plane * K + 16));
@@ -451,7 +439,7 @@ extern "C" int orip_contours_prepare(orip_ctx* c) {
     }
     // shared trace state: memo plane (one word per pixel and incoming direction) and walk records (two slots per skeleton pixel)
     HIPC(c, LN(c).vtmp[VT0_WINFO].ensure((size_t)2 * M * sizeof(WalkInfo) + 64));
-    A.memo = LN(c).vtmp[VT0_MEMO].as<unsigned>(); A.winfo = LN(c).vtmp[VT0_WINFO].as<WalkInfo>();       // (the memo planes were sized where they were cleared)
+    A.memo = LN(c).vtmp[VT0_MEMO].as<unsigned>(); A.winfo = LN(c).vtmp[VT0_WINFO].as<WalkInfo>();       // (the memo planes were sized at the top)
     HIPC(c, LN(c).vtmp[VT0_LOG_USED].ensure((size_t)(NC + 1) * 4 + 64));
     A.log_used = LN(c).vtmp[VT0_LOG_USED].as<unsigned>();         // written by every component's trace
     HIPC(c, hipStreamSynchronize(LN(c).stream));
@@ -490,11 +478,11 @@ static int trace_launch(orip_ctx* c, Prep04& R, int layer, unsigned F) {
     A.cap_factor = F; A.comp_order = R.order + c0; A.nc = NCl;
     int* d_over = &LN(c).flags.as<LaneFlags>()->trace_overflow; A.overflow = d_over;
     if (R.chains) HIPC(c, hipStreamWaitEvent(LN(c).stream, c->ln[0].ev3, 0));            // the chain lists and flags (orip_contours_prepare, side stream)
-    if (!R.memo_clear[layer]) {                      // a retry, or a second trace of the layer after one prepare: the previous walk left its memo
-        HIPC(c, hipMemsetAsync(A.memo + plane * 8 * layer, 0, plane * 8 * 4, LN(c).stream));          // entries and the ST_VIS bits of every
-        hipLaunchKernelGGL(k_clear_visited_layer, dim3(cdiv(Ml, 256)), dim3(256), 0, LN(c).stream, A.st + plane * layer, A.lin + b0, (int64_t)Ml);   // pixel it reached
-    }
-    R.memo_clear[layer] = false;
+    if (R.F[layer])                                  // a retry, or a second trace of the layer after one prepare: the previous walk left the ST_VIS bits of every pixel it reached
+        hipLaunchKernelGGL(k_clear_visited_layer, dim3(cdiv(Ml, 256)), dim3(256), 0, LN(c).stream, A.st + plane * layer, A.lin + b0, (int64_t)Ml);
+    // the memo words this walk can read: eight per skeleton pixel of the layer.  On EVERY launch -- the words hold what the previous step, an overflowed
+    // trace or an earlier trace of this prepare left there
+    hipLaunchKernelGGL(k_clear_memo_layer, dim3(cdiv((int64_t)2 * Ml, 256)), dim3(256), 0, LN(c).stream, reinterpret_cast<uint4*>(A.memo + plane * 8 * layer), A.lin + b0, (int64_t)2 * Ml);
     HIPC(c, hipMemsetAsync(A.winfo + 2 * (size_t)b0, 0, (size_t)2 * Ml * sizeof(WalkInfo), LN(c).stream));
     HIPC(c, hipMemsetAsync(d_over, 0, 4, LN(c).stream));
     if (getenv("ORIP_WALK_DBG")) {          // per-component counters (walks, steps, memo hits, closed cycles, tile loads, size), in the leaves' slot until trace_finish

@@ -5,7 +5,8 @@
 // "stage 08-B"; dedup08_b refuses a brush whose band the pad would clip).
 // Layout: the kernels (groups, raster, Zhang-Suen thinning, components, paths), then the host side: one function per phase (b_groups, b_raster_thin,
 // b_components, b_paths) and dedup08_b, which calls them in order.  Scans and sorts go through vscan_excl / vsort_pairs (vec_common.h); the bit-plane
-// kernels (pack, thinning word, CCL, compaction, heads, bits -> bytes) are the shared blocks of bitplane.h, with the linear pixel id y * Wp + x.
+// kernels (thinning word, CCL, compaction, heads) are the shared blocks of bitplane.h, with the linear pixel id y * Wp + x.  Nothing passes over the canvas
+// pixel by pixel: the stamps set the bit plane themselves and everything behind them works on its words or on the skeleton's pixel list.
 #include "vec08.h"
 #include "bitplane.h"
 #include <cstdio>
@@ -46,9 +47,12 @@ __global__ __launch_bounds__(256) void k_group_finish(const PolyFeat* __restrict
     int l = (int)(g[i].longest & 0xffffffffu);
     g[i].a0x = f[l].sx; g[i].a0y = f[l].sy; g[i].a1x = f[l].ex; g[i].a1y = f[l].ey;
 }
-// raster: gid[pixel] = group root + 1 for every pixel within r of a segment of a line of the group; one wave per segment
+// raster: gid[pixel] = group root + 1 for every pixel within r of a segment of a line of the group, and the pixel's bit in the plane `bits` (Wwp words per
+// row, cleared by the caller; gid is NOT: it is defined at the pixels stamped here and read at those only).  One wave per segment.  The box index q is
+// linear, so the lanes of one trip that share a row and a 64-pixel word are neighbours and lane s + t holds the pixel t to the right of lane s: the first
+// lane of such a stretch shifts the stretch's part of the ballot into place and issues ONE 64-bit atomicOr for it.  No shuffle, no LDS.
 __global__ __launch_bounds__(256) void k_stamp_groups(const int64_t* __restrict__ off, const int32_t* __restrict__ pts, int64_t n_polys, int64_t n_pts, const int* __restrict__ par,
-                                                       int rad, unsigned* __restrict__ gid, int Wp, int Hp) {
+                                                       int rad, unsigned* __restrict__ gid, unsigned long long* __restrict__ bits, int Wp, int Hp, int Wwp) {
     const int lane = threadIdx.x & 63; const long long r2 = (long long)rad * rad;
     long long wave = ((long long)blockIdx.x * 256 + threadIdx.x) >> 6, nw = ((long long)gridDim.x * 256) >> 6;
     for (long long i = wave; i + 1 < n_pts; i += nw) {
@@ -61,9 +65,18 @@ __global__ __launch_bounds__(256) void k_stamp_groups(const int64_t* __restrict_
         int bx0 = max(0, min(x0, x1) - rad), bx1 = min(Wp - 1, max(x0, x1) + rad), by0 = max(0, min(y0, y1) - rad), by1 = min(Hp - 1, max(y0, y1) + rad);
         int bw = bx1 - bx0 + 1, bh = by1 - by0 + 1;
         if (bw <= 0 || bh <= 0) continue;
-        for (int q = lane; q < bw * bh; q += 64) {
-            int x = bx0 + q % bw, y = by0 + q / bw;
-            if (vs::in_capsule(x, y, x0, y0, x1, y1, r2)) gid[(size_t)y * Wp + x] = val;
+        for (int q0 = 0; q0 < bw * bh; q0 += 64) {          // (wave-uniform trip count: every lane takes part in the ballots)
+            const int q = q0 + lane;
+            const int x = bx0 + q % bw, y = by0 + q / bw;
+            const bool in = q < bw * bh && vs::in_capsule(x, y, x0, y0, x1, y1, r2);
+            if (in) gid[(size_t)y * Wp + x] = val;
+            const unsigned long long m = __ballot(in);
+            const unsigned long long heads = __ballot(lane == 0 || (x & 63) == 0 || x == bx0);      // first lane of a (row, word) stretch
+            if (!m) continue;
+            const unsigned long long rest = (heads >> lane) >> 1;                                    // the heads after this lane
+            const int len = rest ? __ffsll((long long)rest) : 64 - lane;                              // lanes of this stretch (1 .. 64)
+            const unsigned long long seg = (m >> lane) & (len == 64 ? ~0ULL : (1ULL << len) - 1ULL);
+            if (((heads >> lane) & 1ULL) && seg) atomicOr(&bits[(size_t)y * Wwp + (x >> 6)], seg << (x & 63));      // (seg != 0: some lane of it is inside the box, so this row is)
         }
     }
 }
@@ -198,12 +211,14 @@ __device__ const int OFX[8] = {-1, 0, 1, 1, 1, 0, -1, -1};
 __global__ __launch_bounds__(256) void k_cid_fill(const unsigned* __restrict__ lin, unsigned m, unsigned* __restrict__ cid) {
     unsigned q = blockIdx.x * 256 + threadIdx.x; if (q < m) cid[lin[q]] = q;
 }
-__global__ __launch_bounds__(256) void k_nbr_build(const unsigned* __restrict__ lin, unsigned m, const u8* __restrict__ sk, const unsigned* __restrict__ cid, int Wp, int Hp, unsigned* __restrict__ nbr) {
+// (sk: the thinned bit plane, Wwp words per row; cid is defined at its set pixels only)
+__global__ __launch_bounds__(256) void k_nbr_build(const unsigned* __restrict__ lin, unsigned m, const unsigned long long* __restrict__ sk, const unsigned* __restrict__ cid, int Wp, int Hp, int Wwp,
+                                                   unsigned* __restrict__ nbr) {
     size_t t = (size_t)blockIdx.x * 256 + threadIdx.x; if (t >= (size_t)m * 8) return;
     unsigned q = (unsigned)(t >> 3); int k = (int)(t & 7);
     unsigned p = lin[q]; int y = (int)(p / Wp) + OFY[k], x = (int)(p % Wp) + OFX[k];
     unsigned v = ~0u;
-    if (y >= 0 && y < Hp && x >= 0 && x < Wp) { size_t j = (size_t)y * Wp + x; if (sk[j]) v = cid[j]; }
+    if (y >= 0 && y < Hp && x >= 0 && x < Wp && ((sk[(size_t)y * Wwp + (x >> 6)] >> (x & 63)) & 1ULL)) v = cid[(size_t)y * Wp + x];
     nbr[t] = v;
 }
 // class lists: 0 = fits the small LDS layout, 1 = the large one, 2 = global scratch
@@ -450,8 +465,10 @@ __global__ __launch_bounds__(256) void k_concat_taps(const int2* a, int64_t na, 
 struct B08 {
     int64_t n2; int Wp, Hp; size_t Np;                              // lines; the padded raster and its pixel count
     PolyFeat* f2; int* par; unsigned *is_root, *root_scan; GroupInfo* grp;      // VTL_FEAT: features, union-find parents and groups of the lines (groups -> paths)
-    unsigned* gid;                                                  // canvas: group root + 1 per pixel of the padded raster (raster -> paths)
-    int Wwp; size_t nwords; u8* skA; unsigned long long *bA, *bB;   // VTL_STEPLOG: skeleton bytes; the two thinning bit planes (bA: the current one), Wwp words per row
+    unsigned* gid;                                                  // canvas: group root + 1 (raster -> paths), DEFINED AT THE PIXELS THIS CALL STAMPED ONLY: it is never
+                                                                    // cleared, anything else is stale (an earlier call or 08-A's first stamps on this lane's canvas).  Every
+                                                                    // reader reads it at skeleton pixels -- thinning only deletes, so those were stamped by this call
+    int Wwp; size_t nwords; unsigned long long *bA, *bB;            // VTL_STEPLOG: the two thinning bit planes (bA: the current one, the skeleton after the thinning), Wwp words per row
     unsigned M; unsigned *keys, *lin;                               // VTL_CUM: skeleton pixels sorted by component label (lin: their pixel index)
     unsigned NC; unsigned *cs, *corder, *outcnt, *oflag, *oscan; GatherDesc* pd;      // VTL_CAPS: components: first pixel in lin (NC + 1), processing order, path tables
 };
@@ -469,20 +486,20 @@ static int b_groups(orip_ctx* c, const orip_params08& P, DPolys& lines2, B08& b)
     hipLaunchKernelGGL(k_group_finish, dim3(cdiv(n2, 256)), dim3(256), 0, LN(c).stream, b.f2, (int)n2, b.is_root, b.root_scan, b.grp);
     return 0;
 }
-// ---- raster and thin: every group's lines stamped on the padded raster, then Zhang-Suen to the skeleton (bit plane b.bA, bytes b.skA)
+// ---- raster and thin: every group's lines stamped on the padded raster, then Zhang-Suen to the skeleton (bit plane b.bA)
 static int b_raster_thin(orip_ctx* c, const orip_params08& P, DPolys& lines2, B08& b, PhaseTimer& T) {
     const int Wp = b.Wp, Hp = b.Hp; const size_t Np = b.Np; const int rad = std::max(1, P.post_brush) / 2;
     HIPC(c, LN(c).canvas.ensure(Np * 4 + 64));
     b.gid = LN(c).canvas.as<unsigned>();
-    HIPC(c, hipMemsetAsync(b.gid, 0, Np * 4, LN(c).stream));
-    { ProfScope ps(c, "k_stamp_groups"); hipLaunchKernelGGL(k_stamp_groups, dim3(8192), dim3(256), 0, LN(c).stream, lines2.off.as<int64_t>(), lines2.pts.as<int32_t>(), b.n2, lines2.total, b.par, rad, b.gid, Wp, Hp); }
     dim3 blk(256);
     const size_t ntile_max = (size_t)cdiv(Wp, 64) * cdiv(Hp, 4);
     const int Wwp = b.Wwp = (Wp + 63) >> 6; const size_t nwords = b.nwords = (size_t)Hp * Wwp;
-    { Carve L; L.take(b.skA, Np); L.each(nwords, b.bA, b.bB);
-      HIPC(c, L.commit(LN(c).vtmp[VTL_STEPLOG], 256 + Np + ntile_max * 4)); }      // (Np + 4 ntile_max: what a second byte plane and a tile list took; no request shrinks here)
-    const dim3 gwd((unsigned)cdiv((int64_t)nwords, 256));
-    hipLaunchKernelGGL(k_pack_bits<PackWords>, gwd, blk, 0, LN(c).stream, b.gid, b.bA, Hp, Wp, Wwp);      // 4 waves x 64 words per block
+    { Carve L; L.each(nwords, b.bA, b.bB);
+      HIPC(c, L.commit(LN(c).vtmp[VTL_STEPLOG], 256 + 2 * Np + ntile_max * 4)); }      // (2 Np + 4 ntile_max: what two byte planes and a tile list took; no request shrinks here)
+    // nothing passes over the canvas: the bit plane (12.8 MB at the default sheet) is cleared, the stamps set gid and their bits, every later reader goes
+    // through the bits (B08::gid)
+    HIPC(c, hipMemsetAsync(b.bA, 0, nwords * 8, LN(c).stream));
+    { ProfScope ps(c, "k_stamp_groups"); hipLaunchKernelGGL(k_stamp_groups, dim3(8192), dim3(256), 0, LN(c).stream, lines2.off.as<int64_t>(), lines2.pts.as<int32_t>(), b.n2, lines2.total, b.par, rad, b.gid, b.bA, Wp, Hp, Wwp); }
     T.tick("raster");
     // Twelve iterations before the first round trip to the host (16-px lines thin in 9 .. 12), four per round trip after that, each iteration with
     // its own flag: an iteration after the first unchanged one changes nothing either, so running to the end of a batch leaves the image the
@@ -498,7 +515,6 @@ static int b_raster_thin(orip_ctx* c, const orip_params08& P, DPolys& lines2, B0
         if (!all) break;
         it += nb;
     }
-    bp_bits_to_bytes(LN(c).stream, gwd, b.bA, b.skA, Hp, Wp, Wwp);
     return 0;
 }
 // ---- components of the thinned bit plane: their pixels in raster order (b.M of them; nothing more is done when it is 0), each group's anchors, the
@@ -581,7 +597,7 @@ static int b_paths(orip_ctx* c, const orip_params08& P, B08& b, DPolys& merged, 
     unsigned* counts = LN(c).flags.as<LaneFlags>()->comp_counts;
     HIPC(c, hipMemsetAsync(counts, 0, sizeof(LaneFlags::comp_counts), LN(c).stream));
     hipLaunchKernelGGL(k_cid_fill, dim3(cdiv(M, 256)), blk, 0, LN(c).stream, b.lin, M, cid);
-    hipLaunchKernelGGL(k_nbr_build, dim3((unsigned)cdiv((int64_t)M * 8, 256)), blk, 0, LN(c).stream, b.lin, M, b.skA, cid, Wp, Hp, nbr);
+    hipLaunchKernelGGL(k_nbr_build, dim3((unsigned)cdiv((int64_t)M * 8, 256)), blk, 0, LN(c).stream, b.lin, M, b.bA, cid, Wp, Hp, b.Wwp, nbr);
     hipLaunchKernelGGL(k_comp_classes, dim3(cdiv(NC, 256)), blk, 0, LN(c).stream, b.corder, NC, b.cs, cap0, cap1, std::max(2, P.post_minlen), counts, l0, l1, l2, b.outcnt);
     CompArgs A; A.corder = b.corder; A.cs = b.cs; A.lin = b.lin; A.gid = b.gid; A.g = b.grp; A.cid = cid; A.nbr = nbr; A.Wp = Wp; A.min_len = P.post_minlen; A.step = stp;
     A.eps = (float)P.post_eps; A.omul = omul; A.outpts = outpts; A.outcnt = b.outcnt;

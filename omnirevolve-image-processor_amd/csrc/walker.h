@@ -63,7 +63,10 @@ struct WalkArgs {
     const unsigned* keys; const unsigned* lin; const unsigned* comp_start; unsigned nc;
     long long total_fg[ORIP_MAX_LAYERS];
     const unsigned* comp_order;        // optional: component processed by wave i (largest first), or nullptr
-    unsigned* memo;                    // [K,H,W,8]: state-log index + 1 of the state (pixel, incoming direction), 0 = unknown
+    unsigned* memo;                    // [K,H,W,8]: state-log index + 1 of the state (pixel, incoming direction), 0 = unknown.  The planes are NEVER cleared
+                                       // as a whole: a word is meaningful only at a skeleton pixel of the current prepare, where the launch of the layer's
+                                       // trace has zeroed all eight (raster04.hip: k_clear_memo_layer); anything elsewhere is stale and never read -- the
+                                       // walker indexes the memo with (pixel << 3 | direction) of a pixel its cursor stood on, nothing else
     unsigned* logbuf;                  // state log, 4 words per entry: (lin << 3 | dir), cont, end (0 while provisional), begin.  After entry end-1 the
                                        // trajectory continues at entry `cont`: inside the record (cont >= begin) it is a cycle, otherwise the record is a
                                        // transient that runs into an older record

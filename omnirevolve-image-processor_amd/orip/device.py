@@ -291,7 +291,7 @@ class Device:
         self._ck(self.L.orip_find_contours(self.h))
 
     def contours_reserve(self, K: int):
-        """hint: K layers of the image just set will be traced (clears stage 04's memo planes while the card is idle)"""
+        """hint: K layers of the image just set will be traced (allocates stage 04's memo planes at the start of the step; clears nothing)"""
         self._ck(self.L.orip_contours_reserve(self.h, int(K)))
 
     def contours_prepare(self):

@@ -323,7 +323,7 @@ def run_path(bgr: np.ndarray, cfg: Config, dev: Device | None = None, centers: n
     H, W = bgr.shape[:2]
     d.set_image(bgr)
     if upto >= 5:
-        d.contours_reserve(K)
+        d.contours_reserve(K)      # sizes stage 04's memo planes now; it clears nothing
     if centers is None:
         centers, _ = d.kmeans_fit_subsampled(SUBSAMPLE_LIMIT, K)
     d.extract_layers(np.asarray(centers, np.float32), want_counts=False)

@@ -730,6 +730,49 @@ int orip_svg_flatten(orip_ctx* ctx, const int32_t* kind /* [n_seg] */, const dou
 int orip_svg_paths_fetch(orip_ctx* ctx, int64_t* off_out /* [n_sub+1] */, double* pts_out /* [total,2] or NULL */);
 int orip_svg_bbox(orip_ctx* ctx, double* box /* [4] */);
 int orip_svg_fit(orip_ctx* ctx, double sx, double sy, double ox, double oy);
+/* Lines and circular arcs of a G-code text -> polylines in mm (csrc/gcode_arc.hip; gcode2stream.py --arcs).  Ours: the reference's parser has no motion
+ * modes and draws every G2 / G3 as its chord.  The text is parsed on the host (orip/gcode.py: parse_gcode_arcs); this call flattens.
+ * n_seg segments: kind[s] 1 line / 2 arc clockwise (G2) / 3 arc counter-clockwise (G3); seg[s] = Ax Ay Bx By Cx Cy, from A to B about the centre C (C is
+ * not read for a line).  n_sub subpaths, subpath p = the segments sub_off[p] .. sub_off[p + 1] - 1 (at least one), each starting where its predecessor
+ * ends, both coordinates equal: checked on the host side of the call, a violation is an argument error.
+ * It leaves exactly what orip_svg_flatten leaves -- one polyline per subpath resident, not fitted, not hatched, no box -- so orip_svg_paths_fetch,
+ * orip_gcode_to_steps(ctx, NULL, NULL, n_sub, ...) and orip_gcode_to_steps_clip(ctx, NULL, NULL, n_sub, ...) work on the result unchanged.
+ * A line emits B.  The first point of a subpath is its first segment's A; the first point of every later segment is its predecessor's end and is not
+ * emitted twice.  An arc emits N points, the last of them B as given, by the following rule.
+ * THE RULE.  Every operation is ONE IEEE double add, subtract, multiply, divide or square root, rounded to nearest and never fused, in the order written;
+ * no sin, cos or atan2 is used, so a restatement in Python floats and math.sqrt repeats every bit (tests/arc_double.py).
+ *   1. Radii and unit vectors.  a = A - C, b = B - C per component.  rA = sqrt(ax * ax + ay * ay), rB = sqrt(bx * bx + by * by).  uA = (ax / rA, ay / rA),
+ *      uB = (bx / rB, by / rB).  r = max(rA, rB).  dir = +1 counter-clockwise, -1 clockwise.
+ *   2. Spans.  q_i = uA turned by i quarter turns in direction dir; one turn is (x, y) -> (-y, x) for dir = +1 and (y, -x) for dir = -1, exact.
+ *      A == B in both coordinates is a full circle: the spans [uA, q1], [q1, q2], [q2, q3], [q3, q4], and q4 is uA.
+ *      Otherwise k = ax * by - ay * bx, negated for dir = -1, and d = ax * bx + ay * by, as computed.  j, the whole quarter turns before uB, is
+ *      k > 0: 0 if d > 0, else 1;  k < 0: 3 if d >= 0, else 2;  k == 0: 0 if d >= 0, else 2.
+ *      The spans are [q_0, q_1] .. [q_(j-1), q_j] and then [q_j, uB]; the last is left out when uB equals q_j in both components.  A sweep that is almost 0
+ *      and one that is almost a full turn are told apart by these computed signs and nothing else: that ambiguity is G-code's.  When no span is left
+ *      (j = 0 and uB equals uA although B is not A) the arc is one piece, to B.
+ *   3. Depth.  All S spans of an arc are cut into 2^m equal parts.  c_0 = sqrt(0.5) when j >= 1 or the circle is full, and
+ *      sqrt((1 + (uAx * uBx + uAy * uBy)) / 2) for a lone span; c_(i+1) = sqrt((1 + c_i) / 2).  m is the smallest i with r * (1 - c_i) <= tol: c_m is the
+ *      cosine of half a piece of the largest span, so no chord is further than tol from the circle of radius r.  m > ORIP_ARC_MAX_DEPTH is an error.
+ *      N = S * 2^m.
+ *   4. Direction of point g, 0 < g < N: it lies in span s = g >> m with the ends (uL, uR) = that span's, at i = g mod 2^m.  i == 0: uL.  Otherwise bisect
+ *      the range (0, 2^m): mid = ((uLx + uRx) / n, (uLy + uRy) / n) with n = sqrt(sx * sx + sy * sy) over the two sums; if i is the middle of the range
+ *      the direction is mid, otherwise the half that holds i goes on with mid as its new end.  At most m levels; a span is at most a quarter turn, so the
+ *      sum never degenerates.
+ *   5. Point g = C + rho * u per component, rho = rA + (rB - rA) * t, t = g / N (g and N as doubles).  Point N is B as given.
+ * Radii (ours, following what common controllers accept, written from memory): the caller's parser refuses an arc whose radii rA and rB differ by more
+ * than 0.5 mm, or by more than 0.005 mm and more than rA / 1000; inside that limit the radius runs linearly from rA to rB (step 5), so the arc ends on B
+ * exactly as the file states it.  This call itself only requires both radii to be finite and not 0.
+ * stats: arcs, the pieces of all arcs, full circles.  total_out receives the number of points.
+ * Errors (no fault, no paths left resident): tol not positive and finite; a kind outside 1 .. 3; a segment that does not start where its predecessor
+ * ends, a subpath without a segment; a coordinate or radius that is not finite, a radius of 0 (both found on the device); m > ORIP_ARC_MAX_DEPTH (the arc
+ * needs more than 2^18 pieces); 2^30 points or more.
+ * Stated deviation: the piece count is a power of two per span, up to twice the least number of points; orip_gcode_simplify thins them.
+ * Declined: helical arcs and the planes of G18 / G19; the P turn count; G5 / G5.1 splines; a piece count that is not a power of two (it would need a
+ * transcendental function on both sides of the equality). */
+#define ORIP_ARC_MAX_DEPTH 16
+int orip_gcode_flatten(orip_ctx* ctx, const int32_t* kind /* [n_seg]: 1 line, 2 arc cw, 3 arc ccw */, const double* seg /* [n_seg,6]: Ax Ay Bx By Cx Cy */,
+                       int64_t n_seg, const int64_t* sub_off /* [n_sub+1] */, int64_t n_sub, double tol, int64_t* total_out,
+                       int64_t* stats /* [3]: arcs, pieces, full circles */);
 /* Hatch fill of the fitted paths (csrc/hatch.hip): hatch_fill of stream_generators/plotter_demo/omnirevolve_plotter_demo.py (:220-260), every fill group
  * at once.  fill_group[p] is -1 or the group of subpath p, 0 <= group < n_sub (n_sub must be the resident count); the groups are hatched in ascending
  * order of their number, each over all its subpaths, every subpath closed by the edge from its last point to its first (poly[(i + 1) % n], :242).

@@ -20,6 +20,7 @@
 //    +-0.5 does the sign of e decide (v' = 5e-05: p is exactly 0.5, e > 0, so k = 1).  When p is no tie, e is too small to cross one.
 #include "vec_common.h"
 #include "sv_round.h"
+#include "sv_place.h"       // k_svg_off, k_svg_first
 
 namespace {
 constexpr int SV_MAX_PIECES = 1 << 16;
@@ -68,21 +69,6 @@ __global__ __launch_bounds__(256) void k_svg_count(const int* __restrict__ kind,
     }
     if (!fin) { atomicOr(err, 1); n = 1; }
     cnt[s] = n;
-}
-
-// off[p] = place of subpath p's first point: the pieces before its first segment, and one first point per subpath before it
-__global__ __launch_bounds__(256) void k_svg_off(const long long* __restrict__ sub_off, int64_t P, const long long* __restrict__ ex, long long* __restrict__ off) {
-    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (p <= P) off[p] = ex[sub_off[p]] + p;
-}
-
-// first[s] = place of the point i = 1 of segment s
-__global__ __launch_bounds__(256) void k_svg_first(const long long* __restrict__ sub_off, int64_t P, int64_t S, const long long* __restrict__ ex, long long* __restrict__ first) {
-    const int64_t s = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (s >= S) return;
-    int64_t lo = 0, hi = P;                                                  // last p with sub_off[p] <= s
-    while (hi - lo > 1) { const int64_t mid = (lo + hi) >> 1; if (sub_off[mid] <= s) lo = mid; else hi = mid; }
-    first[s] = ex[s] + lo + 1;
 }
 
 __global__ __launch_bounds__(256) void k_svg_emit(const int* __restrict__ kind, const double2* __restrict__ tc, const long long* __restrict__ cnt, const long long* __restrict__ first,

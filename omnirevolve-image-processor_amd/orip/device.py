@@ -448,6 +448,22 @@ class Device:
         self._svg_n = nsub
         return int(total.value)
 
+    def gcode_flatten(self, table, tol: float) -> Tuple[int, dict]:
+        """--arcs (include/orip.h: orip_gcode_flatten): the lines and arcs of an orip.gcode.ArcTable (kind, seg, sub_off) -> resident polylines in mm, as
+        svg_flatten leaves its own: svg_paths fetches them, gcode_to_steps / gcode_to_steps_clip(None, None, ..., n=) convert them.
+        -> (the number of points, {"arcs", "pieces", "full_circles"})"""
+        kind = np.ascontiguousarray(table[0], np.int32).reshape(-1); seg = np.ascontiguousarray(table[1], np.float64).reshape(-1, 6)
+        sub = np.ascontiguousarray(table[2], np.int64).reshape(-1)
+        if len(kind) != len(seg) or len(sub) < 1:
+            raise ValueError("arc table: kind and seg must have one entry per segment, sub_off at least one")
+        ns, nsub = len(kind), len(sub) - 1
+        self._svg_n = 0
+        total = C.c_int64(0)
+        st = np.zeros(len(_l.ARC_STATS), np.int64)
+        self._ck(self.L.orip_gcode_flatten(self.h, _p(kind) if ns else None, _p(seg) if ns else None, ns, _p(sub) if ns else None, nsub, float(tol), C.byref(total), _p(st)))
+        self._svg_n = nsub
+        return int(total.value), {k: int(v) for k, v in zip(_l.ARC_STATS, st)}
+
     def svg_paths(self, n: int | None = None, with_points: bool = True):
         """the resident paths, flattened or fitted: (off int64 [n + 1], pts float64 [total, 2], or None without the points)"""
         n = self._svg_n if n is None else int(n)

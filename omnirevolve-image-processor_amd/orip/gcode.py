@@ -82,7 +82,14 @@ ring at the nearest one (orip_gcode_order_rings; include/orip.h states the rule:
 without a closed stroke it is the plain order).  The call stands in the place of the order; the rings are then rotated to where they were entered, so
 --improve-order, --loop-start (which may still lower the travel), the plan and the preview see them there.  Greedy is not monotone: the pen-up travel is
 usually lower, and nothing promises it; the tools report it.  Not with --no-reorder: file order was asked for, and --loop-start is the option for that.
-Without the option no device call is added and every byte is what it was."""
+Without the option no device call is added and every byte is what it was.
+
+--arcs (ours as well): the reference's parser has no motion modes -- a line with an X or Y word is a straight move whatever G word stands in front of it --
+so a G2 / G3 fillet is drawn as its chord, a full circle as nothing, and G91.1 is read as G91.  With --arcs the text goes through parse_gcode_arcs (modal
+G0 .. G3, G words with their decimal, I / J and R centres, the radius rule) into a table of lines and arcs, and the arcs are flattened on the device into
+the mm polylines the conversion reads without a copy (orip_gcode_flatten; include/orip.h states the rule: bisected unit vectors, no sin or cos, every point
+on the circle, within --arc-tolerance-mm of it between the points; default half a step on paper).  Everything behind the conversion is unchanged.  On a
+text without an arc the old parser's paths take the old route: no device call is added and every byte is what it was, as without the option."""
 from __future__ import annotations
 
 import argparse
@@ -139,6 +146,8 @@ class GcodeOptions:
     clip_margin_mm: Optional[float] = None  # the clip rectangle lies this far inside the sheet (None: 0); only with clip
     simplify_mm: Optional[float] = None     # vertices within this distance of the stroke are dropped (None: every vertex is drawn; 0: only those on the stroke)
     dedup: bool = False                 # collinear segments of one pen that lie over each other are drawn once, the first drawn copy stays
+    arcs: bool = False                  # G2 / G3 are drawn as arcs, flattened on the device (without it they are the reference's chords)
+    arc_tolerance_mm: Optional[float] = None    # a chord leaves its arc by at most this, in the file's mm (None: half a step on paper); only with arcs
     ring_entry: bool = False            # the greedy order enters a closed stroke at its nearest ring vertex
     loop_start: bool = False            # every closed stroke starts and ends at the ring vertex that makes the pen-up travel of the plot least
     dash_mm: Optional[str] = None       # every path is drawn dashed: dash and gap lengths in mm, comma-separated (None: solid)
@@ -246,6 +255,167 @@ def parse_gcode(text: Union[str, bytes], pens_out: Optional[List[int]] = None) -
     return np.asarray(off, np.int64), np.asarray(flat, np.float64).reshape(-1, 2), moves
 
 
+# ------------------------------------------------------------------ --arcs: the parser with motion modes (ours; the reference has none)
+# What orip_gcode_flatten takes (include/orip.h): kind int32 [n_seg] (1 line, 2 arc clockwise, 3 arc counter-clockwise), seg float64 [n_seg, 6] = Ax Ay Bx By
+# Cx Cy in mm, sub_off int64 [n_sub + 1]: path p is the segments sub_off[p] .. sub_off[p + 1] - 1, each starting where its predecessor ends
+ArcTable = namedtuple("ArcTable", "kind seg sub_off")
+ARC_LINE, ARC_CW, ARC_CCW = 1, 2, 3
+ARC_STATS = ("arcs", "pieces", "full_circles")      # include/orip.h: orip_gcode_flatten
+# The radius rule (ours; include/orip.h states it): the radii at the two ends may differ by 0.5 mm at most, and by more than 0.005 mm only up to a
+# thousandth of the radius; an R word may be short of half the chord by 0.005 mm
+ARC_RADIUS_ABS_MM, ARC_RADIUS_SMALL_MM, ARC_RADIUS_REL, ARC_R_SHORT_MM = 0.5, 0.005, 1e-3, 0.005
+
+
+def parse_gcode_arcs(text: Union[str, bytes], pens_out: Optional[List[int]] = None) -> Tuple[ArcTable, int]:
+    """parse_gcode with motion modes: (the segment table of the pen-down paths, pen-down moves).  Every rule of parse_gcode holds -- comments, words, G20 /
+    G21, G90 / G91, the M3 / M4 / M5 and Z pen rules, T words with pens_out, how a path opens and closes -- and a pen-down move is one segment.  Added:
+    G0 / G1 / G2 / G3 set the modal motion mode where they stand (the last of a line wins; G1 at the start); G words are read with their decimal, so G90.1
+    (absolute centres) and G91.1 (offsets from the start point, the default) set the centre mode and leave the distance mode alone; G17 is accepted and
+    after G18 / G19 an arc is an error.  In mode G2 (clockwise) / G3 a line that moves -- there also one with only I / J / R words: the end point is then
+    the start point -- is an arc from the cursor A to the end point B.  I / J give the centre (a missing one: 0, resp. A's coordinate under G90.1); R
+    gives the radius instead: the centre lies h = sqrt(R^2 - (d / 2)^2) from the chord's midpoint, on the left of A -> B for G3 with R > 0 and for G2
+    with R < 0, otherwise on the right (R < 0: the long way round); d = 0 is an error, and so is R^2 < (d / 2)^2 unless d / 2 - |R| <= 0.005 mm (h = 0).
+    I, J and R are in inches under G20.  The radii |A - C| and |B - C| must not be 0 and must agree as ARC_RADIUS_* state.  Every error is a ValueError
+    naming the line.  With the pen up an arc only moves the cursor.  K, P and F are skipped."""
+    if isinstance(text, (bytes, bytearray)):
+        text = bytes(text).decode("utf-8", errors="ignore")
+    x = y = 0.0
+    absolute, metric, down, abs_centre = True, True, False, False
+    mode, plane = 1, 17
+    kind: List[int] = []
+    seg: List[Tuple[float, float, float, float, float, float]] = []
+    sub_off = [0]
+    moves = 0
+    tool = open_tool = -1
+
+    def close():
+        if len(kind) > sub_off[-1]:
+            sub_off.append(len(kind))
+            if pens_out is not None:
+                pens_out.append(open_tool)
+
+    for ln, raw in enumerate(text.splitlines(), 1):
+        line = _COMMENT.sub("", raw.split(";", 1)[0]).strip()
+        if not line:
+            continue
+        pen = None; nx = ny = nz = ni = nj = nr = None
+        for word in line.split():
+            letter, num = word[0].upper(), word[1:]
+            if not num:
+                continue
+            try:
+                if letter == "G":
+                    code = int(round(float(num) * 10.0))   # in tenths; OverflowError (Ginf) is not caught, as in parse_gcode
+                elif letter == "M":
+                    code = int(float(num))
+                elif letter in "XYZIJR":
+                    v = float(num)
+                elif letter == "T" and pens_out is not None:
+                    code = int(float(num))
+                else:
+                    continue
+            except ValueError:
+                continue
+            if letter == "T":
+                if not (0 <= code < MAX_PENS):
+                    raise ValueError(f"tool T{code}: the plotter has pens 0..{MAX_PENS - 1}")
+                tool = code
+            elif letter == "G":
+                if code == 900: absolute = True
+                elif code == 910: absolute = False
+                elif code == 901: abs_centre = True
+                elif code == 911: abs_centre = False
+                elif code == 210: metric = True
+                elif code == 200: metric = False
+                elif code in (0, 10, 20, 30): mode = code // 10
+                elif code in (170, 180, 190): plane = code // 10
+            elif letter == "M":
+                if code == 3 or code == 4: pen = True
+                elif code == 5: pen = False
+            else:
+                if not metric:
+                    v *= MM_PER_INCH
+                if letter == "X": nx = v
+                elif letter == "Y": ny = v
+                elif letter == "Z": nz = v
+                elif letter == "I": ni = v
+                elif letter == "J": nj = v
+                else: nr = v
+        if nz is not None and pen is None:
+            pen = nz <= 0.0
+        if pen is not None and pen != down:
+            if down:
+                close()
+            down = pen
+        arc = mode >= 2
+        if nx is None and ny is None and not (arc and (ni is not None or nj is not None or nr is not None)):
+            continue
+        ox, oy = x, y
+        if absolute:
+            x = nx if nx is not None else x
+            y = ny if ny is not None else y
+        else:
+            x = x + nx if nx is not None else x
+            y = y + ny if ny is not None else y
+        cx = cy = 0.0
+        if arc:
+            if plane != 17:
+                raise ValueError(f"line {ln}: an arc in the plane of G{plane}: only arcs in the XY plane (G17) are drawn")
+            if nr is not None:
+                if ni is not None or nj is not None:
+                    raise ValueError(f"line {ln}: an arc with both R and I / J")
+                dx, dy = x - ox, y - oy
+                d = (dx * dx + dy * dy) ** 0.5
+                if d == 0.0:
+                    raise ValueError(f"line {ln}: an R arc whose end point is its start point has no centre")
+                h2 = nr * nr - (d / 2.0) * (d / 2.0)
+                if h2 < 0.0 and not (d / 2.0 - abs(nr) <= ARC_R_SHORT_MM):
+                    raise ValueError(f"line {ln}: R{nr:g} mm is too short for end points {d:g} mm apart")
+                if nr == 0.0 or nr != nr:
+                    raise ValueError(f"line {ln}: an arc of radius R{nr:g}")
+                h = h2 ** 0.5 if h2 > 0.0 else 0.0
+                if (mode == 3) != (nr > 0.0):
+                    h = -h                                # on the right of A -> B
+                cx = (ox + x) / 2.0 + h * (-dy / d); cy = (oy + y) / 2.0 + h * (dx / d)
+            elif abs_centre:
+                cx = ni if ni is not None else ox; cy = nj if nj is not None else oy
+            else:
+                cx = ox + (ni if ni is not None else 0.0); cy = oy + (nj if nj is not None else 0.0)
+            ra = ((ox - cx) ** 2 + (oy - cy) ** 2) ** 0.5; rb = ((x - cx) ** 2 + (y - cy) ** 2) ** 0.5
+            if ra == 0.0 or rb == 0.0:
+                raise ValueError(f"line {ln}: an arc that starts or ends on its centre")
+            diff = abs(ra - rb)
+            if diff > ARC_RADIUS_ABS_MM or (diff > ARC_RADIUS_SMALL_MM and diff > ra * ARC_RADIUS_REL):
+                raise ValueError(f"line {ln}: the arc's radii at its start and its end, {ra:g} and {rb:g} mm, differ by {diff:g} mm")
+        if down:
+            if len(kind) == sub_off[-1]:
+                open_tool = tool
+            kind.append((ARC_CCW if mode == 3 else ARC_CW) if arc else ARC_LINE)
+            seg.append((ox, oy, x, y, cx, cy))
+            moves += 1
+    close()
+    return ArcTable(np.asarray(kind, np.int32), np.asarray(seg, np.float64).reshape(-1, 6), np.asarray(sub_off, np.int64)), moves
+
+
+def arc_tolerance(o) -> Optional[float]:
+    """None without --arcs, else the flattening tolerance in the file's mm (before --scale-x / --scale-y): --arc-tolerance-mm, positive and finite, or
+    0.5 / (steps_per_mm max(|scale_x|, |scale_y|)), half a step on paper.  --arc-tolerance-mm belongs to --arcs."""
+    t = getattr(o, "arc_tolerance_mm", None)
+    if not getattr(o, "arcs", False):
+        if t is not None:
+            raise ValueError("--arc-tolerance-mm needs --arcs")
+        return None
+    if t is None:
+        per_mm = float(o.steps_per_mm) * max(abs(float(o.scale_x)), abs(float(o.scale_y)))
+        if not (per_mm > 0.0) or per_mm == float("inf"):
+            raise ValueError("--arcs: no default tolerance when the steps per mm or both scales are 0 or not finite; give --arc-tolerance-mm")
+        t = 0.5 / per_mm
+    t = float(t)
+    if not (t > 0.0) or t == float("inf"):
+        raise ValueError("--arc-tolerance-mm must be a positive finite number")
+    return t
+
+
 # ------------------------------------------------------------------ options (:546-603)
 def apply_speed_scale(o: GcodeOptions) -> GcodeOptions:
     """--speed-scale (:546-587): six dividers divided by the scale, rounded half to even, at least 1; then the five ordering constraints."""
@@ -346,7 +516,8 @@ def build_stream_from_gcode(text_or_paths, opts: Optional[GcodeOptions] = None, 
                             timings: Optional[dict] = None, pens: Optional[np.ndarray] = None, order_pens_fn: Optional[Callable] = None,
                             source_fn: Optional[Callable] = None, merge_fn: Optional[Callable] = None, improve_fn: Optional[Callable] = None,
                             clip_fn: Optional[Callable] = None, simplify_fn: Optional[Callable] = None, dedup_fn: Optional[Callable] = None,
-                            dash_fn: Optional[Callable] = None, seam_fn: Optional[Callable] = None, ring_entry_fn: Optional[Callable] = None) -> Tuple[bytes, dict]:
+                            dash_fn: Optional[Callable] = None, seam_fn: Optional[Callable] = None, ring_entry_fn: Optional[Callable] = None,
+                            flatten_fn: Optional[Callable] = None) -> Tuple[bytes, dict]:
     """The stream of a G-code text (str / bytes) or of paths in mm given as (off, pts_mm); opts as parsed, --speed-scale not yet applied.
     Device steps, each None = the GPU (orip.device.Device; there is no CPU path in the product):
       steps_fn(off, pts_mm, map: dict) -> (off int64, pts int32 [total, 2])      orip_gcode_to_steps
@@ -379,12 +550,17 @@ def build_stream_from_gcode(text_or_paths, opts: Optional[GcodeOptions] = None, 
     and, only with --ring-entry (in the place of order_fn / order_pens_fn; without pens: one group):
       ring_entry_fn(off, pts, group int32 [n], n_groups, reverse) -> (order, rev, seam int32 [n] by sequence position, stats)          orip_gcode_order_rings
     info["ring_entry"] then holds closed, moved, candidates and travel (pen-up steps of the sequence as the call returned it).
+    and, only with --arcs on a text that holds a G2 / G3 arc (in front of steps_fn / clip_fn; parse_gcode_arcs then stands in parse_gcode's place):
+      flatten_fn(table: ArcTable, tol) -> (off int64, pts_mm float64 [total, 2], stats)                                                orip_gcode_flatten
+    info["arcs"] then holds tolerance_mm, arcs, pieces and full_circles.  The device's own leaves the polylines resident and returns (None, None, stats) when
+    the conversion is the device's too: that one is then called as steps_fn(None, None, map, n=paths), resp. clip_fn(None, None, map, rect, n=paths).
+    On a text without an arc the option changes nothing: parse_gcode's paths, no flatten_fn call, the same bytes.
     pens: one pen per input path, 0..7, or -1 for --color-index (a text's T words under --tool-pens when None).  info["pens"] then counts the paths per
     pen, those that took --color-index ("unmatched") and the strokes drawn backwards ("reversed").
     Returns (bytes, counts)."""
     steps = StrokeSteps(clip_fn if opts is not None and opts.clip else steps_fn, source_fn, merge_fn, simplify_fn, order_fn, order_pens_fn, improve_fn, codes_fn, pack_fn,
                         dedup_fn)
-    return stroke_stream(text_or_paths, opts, device, steps, timings, pens, dash_fn=dash_fn, seam_fn=seam_fn, ring_entry_fn=ring_entry_fn)
+    return stroke_stream(text_or_paths, opts, device, steps, timings, pens, dash_fn=dash_fn, seam_fn=seam_fn, ring_entry_fn=ring_entry_fn, flatten_fn=flatten_fn)
 
 
 # The device steps of the stroke pipeline, each a callable or None = not given; build_stream_from_gcode states the signatures.  convert: steps_fn or, with --clip, clip_fn
@@ -441,6 +617,13 @@ class Seam:
         self.fn = fn
 
 
+class Flatten:
+    """--arcs, which StrokeSteps does not carry: fn(table: ArcTable, tol) -> (off int64, pts_mm float64 [total, 2], stats), or (None, None, stats) with the
+    polylines left resident for this device's conversion; or None = the device (orip_gcode_flatten)"""
+    def __init__(self, fn=None):
+        self.fn = fn
+
+
 class RingEntry:
     """--ring-entry, which StrokeSteps does not carry: fn(off, pts, group int32 [n], n_groups, reverse) -> (order int32 [n], rev bool [n], seam int32 [n]:
     by sequence position, the stored ring vertex a closed stroke is entered at, 0 for an open one; stats) or None = the device (orip_gcode_order_rings)"""
@@ -450,7 +633,7 @@ class RingEntry:
 
 def resolve_steps(st: StrokeSteps, o, grouped: bool, device=None, convert: Optional[Callable] = None, force: bool = False, occlude: Optional[Occlude] = None,
                   dash: Optional[Dash] = None, seam: Optional[Seam] = None, hatch_link: Optional[HatchLink] = None, stipple: Optional[Stipple] = None,
-                  ring_entry: Optional[RingEntry] = None):
+                  ring_entry: Optional[RingEntry] = None, flatten: Optional[Flatten] = None):
     """The steps the options need, those not given taken from a device -> (steps, device); codes and pack stay as given (orip.stream.compile_plan fills them).
     When none is missing, and the caller does not `force` a device for steps of its own, no device is made and orip.stages is not imported.  convert(device)
     -> the conversion of a front door whose paths are on the device already (orip.svg).  Dedup, merge and simplify work on the polylines the pass before them
@@ -464,13 +647,14 @@ def resolve_steps(st: StrokeSteps, o, grouped: bool, device=None, convert: Optio
     `stipple`: its fn is filled in the same way; it reads the fitted paths and touches no stroke, so it needs nothing resident behind the fit.  With it
     the seam pass is always sent its strokes: the dots among them are in no resident list.  `ring_entry`: its fn is filled in the same way and reads or is
     sent the strokes exactly as the seam pass is; it stands in the place of both orders, which are then not needed, and it rotates the rings on the host, so
-    behind it the seam pass is always sent its strokes."""
+    behind it the seam pass is always sent its strokes.  `flatten`: --arcs found an arc; its fn is filled in the same way: this device's flattening leaves
+    its polylines resident for this device's conversion and fetches them for a given one."""
     plain = ring_entry is None
     need = ["convert"] + ["order"] * plain + (["order_pens"] * plain + ["source"]) * bool(grouped) + ["merge"] * bool(o.merge_paths) + ["improve"] * bool(o.improve_order) + \
         ["simplify"] * (o.simplify_mm is not None) + ["dedup"] * bool(o.dedup) + ["source"] * (occlude is not None or dash is not None or hatch_link is not None)
     if not force and all(getattr(st, k) is not None for k in need) and (occlude is None or occlude.fn is not None) and (dash is None or dash.fn is not None) and \
             (seam is None or seam.fn is not None) and (hatch_link is None or hatch_link.fn is not None) and (stipple is None or stipple.fn is not None) and \
-            (plain or ring_entry.fn is not None):
+            (plain or ring_entry.fn is not None) and (flatten is None or flatten.fn is not None):
         return st, device
     if device is None:
         from .stages import device as _default_device
@@ -510,18 +694,24 @@ def resolve_steps(st: StrokeSteps, o, grouped: bool, device=None, convert: Optio
             if after_simplify and stipple is None else device.gcode_order_rings
     if stipple is not None and stipple.fn is None:
         stipple.fn = device.svg_stipple
+    if flatten is not None and flatten.fn is None:
+        def own_flatten(table, tol):
+            _total, stats = device.gcode_flatten(table, tol)
+            return (None, None, stats) if after_convert else (*device.svg_paths(), stats)
+        flatten.fn = own_flatten
     if dash is not None and dash.fn is None:
         dash.device_follows = st.source is None
         dash.fn = (lambda off, pts, pattern, phase, po, pv: device.gcode_dash(None, None, pattern, phase, po, pv, n=len(off) - 1)) if after_convert else device.gcode_dash
     return StrokeSteps(*(a or b for a, b in zip(st, own))), device
 
 
-def _convert(st: StrokeSteps, off_mm, pts_mm, m: dict, rect, info: dict):
-    """mm paths -> step polylines, clamped to the sheet or (rect) cut at it; info["clip"]"""
+def _convert(st: StrokeSteps, off_mm, pts_mm, m: dict, rect, info: dict, n_resident: Optional[int] = None):
+    """mm paths -> step polylines, clamped to the sheet or (rect) cut at it; info["clip"].  n_resident: the paths are that many the flattening left on the device"""
+    more = {} if n_resident is None else {"n": int(n_resident)}
     if rect is None:
-        off, pts = st.convert(off_mm, pts_mm, m)
+        off, pts = st.convert(off_mm, pts_mm, m, **more)
     else:
-        off, pts, cst = st.convert(off_mm, pts_mm, m, rect)
+        off, pts, cst = st.convert(off_mm, pts_mm, m, rect, **more)
         info["clip"] = dict({"rect": tuple(int(v) for v in rect)}, **{k: int(cst[k]) for k in CLIP_STATS})
         if info["clip"]["inside"] + info["clip"]["cut"] + info["clip"]["outside"] != info["clip"]["segments"] or info["clip"]["paths_out"] != len(off) - 1:
             raise RuntimeError("the clip's counts do not add up")
@@ -824,8 +1014,9 @@ def _plan(o: GcodeOptions, sc: ST.StreamConfig, off, pts, path_pen, is_tap=None)
 def stroke_stream(text_or_paths, opts: Optional[GcodeOptions], device, steps: StrokeSteps, timings: Optional[dict] = None, pens: Optional[np.ndarray] = None,
                   occlude: Optional[Occlude] = None, dash: Optional[Dash] = None, dash_fn: Optional[Callable] = None, seam_fn: Optional[Callable] = None,
                   seam: Optional["Seam"] = None, hatch_link: Optional[HatchLink] = None, stipple: Optional[Stipple] = None,
-                  ring_entry_fn: Optional[Callable] = None, ring_entry: Optional[RingEntry] = None) -> Tuple[bytes, dict]:
-    """build_stream_from_gcode with the device steps as one record: parse, convert, pens of the strokes, [dash: --dash-mm gives every path the one pattern,
+                  ring_entry_fn: Optional[Callable] = None, ring_entry: Optional[RingEntry] = None, flatten_fn: Optional[Callable] = None) -> Tuple[bytes, dict]:
+    """build_stream_from_gcode with the device steps as one record: parse, [flatten: --arcs on a text with an arc, with flatten_fn], convert, pens of the
+    strokes, [dash: --dash-mm gives every path the one pattern,
     with dash_fn; the SVG door brings a record of its own], [hatch_link, the SVG door's], [occlude, the SVG door's], dedup, merge, simplify, [stipple, the
     SVG door's: its dots join the strokes as one-point ops], order [ring_entry: --ring-entry in the greedy order's place, with ring_entry_fn, or the record a
     door has resolved already], [seam: --loop-start, with seam_fn, or the record a door has resolved already], plan, compile"""
@@ -835,6 +1026,7 @@ def stroke_stream(text_or_paths, opts: Optional[GcodeOptions], device, steps: St
     sc = stream_config(o)
     rect, tol4 = stroke_options(o)
     own_dash = dash_option(o)
+    arc_tol = arc_tolerance(o)
     tm = timings if timings is not None else {}
     t0 = time.perf_counter()
 
@@ -842,9 +1034,17 @@ def stroke_stream(text_or_paths, opts: Optional[GcodeOptions], device, steps: St
         nonlocal t0
         t1 = time.perf_counter(); tm[name] = tm.get(name, 0.0) + (t1 - t0); t0 = t1
 
+    table: Optional[ArcTable] = None
     if isinstance(text_or_paths, (str, bytes, bytearray)):
         tools: Optional[List[int]] = [] if o.tool_pens and pens is None else None
-        off_mm, pts_mm, pen_moves = parse_gcode(text_or_paths, tools)
+        if arc_tol is not None:
+            table, pen_moves = parse_gcode_arcs(text_or_paths, tools)
+            if not (table.kind >= ARC_CW).any():                          # no arc: the old parser's paths and the old route, byte for byte
+                table = None; tools = None if tools is None else []
+        if table is None:
+            off_mm, pts_mm, pen_moves = parse_gcode(text_or_paths, tools)
+        else:
+            off_mm, pts_mm = table.sub_off, None                          # one path per subpath; the points come from the flattening
         if tools is not None:
             pens = np.asarray(tools, np.int64)
     else:
@@ -867,7 +1067,9 @@ def stroke_stream(text_or_paths, opts: Optional[GcodeOptions], device, steps: St
         dash = Dash(dash_fn, np.zeros(len(off_mm) - 1, np.int32), np.full(len(off_mm) - 1, own_dash[1], np.int64), [0, len(own_dash[0])], own_dash[0])
     sm = (seam if seam is not None else Seam(seam_fn)) if o.loop_start else None
     rge = (ring_entry if ring_entry is not None else RingEntry(ring_entry_fn)) if o.ring_entry else None
-    st, device = resolve_steps(steps, o, grouped, device, occlude=occlude, dash=dash, seam=sm, hatch_link=hatch_link, stipple=stipple, ring_entry=rge)
+    flt = Flatten(flatten_fn) if table is not None else None
+    st, device = resolve_steps(steps, o, grouped, device, occlude=occlude, dash=dash, seam=sm, hatch_link=hatch_link, stipple=stipple, ring_entry=rge,
+                               flatten=flt)
     m = dict(scale_x=o.scale_x, scale_y=o.scale_y, offset_x_mm=o.offset_x_mm, offset_y_mm=o.offset_y_mm, steps_per_mm=o.steps_per_mm, W=W, H=H, invert_y=int(bool(o.invert_y)))
 
     def finish(off, pts, pen, group):
@@ -922,7 +1124,18 @@ def stroke_stream(text_or_paths, opts: Optional[GcodeOptions], device, steps: St
         return finish(np.zeros(1, np.int64), np.zeros((0, 2), np.int32), *((np.zeros(0, np.int64), np.zeros(0, np.int32)) if grouped else (None, None)))
 
     n_groups = MAX_PENS if pens is not None else 1
-    off, pts = _convert(st, off_mm, pts_mm, m, rect, info)
+    n_resident = None
+    if table is not None:
+        off_f, pts_mm, ast = flt.fn(table, arc_tol)
+        info["arcs"] = dict({"tolerance_mm": arc_tol}, **{k: int(ast[k]) for k in ARC_STATS})
+        if pts_mm is None:
+            n_resident, off_mm = len(off_mm) - 1, None
+        else:
+            off_mm = np.asarray(off_f, np.int64); pts_mm = np.asarray(pts_mm, np.float64).reshape(-1, 2)
+            if len(off_mm) != len(table.sub_off) or (len(off_mm) and int(off_mm[-1]) != len(pts_mm)):
+                raise RuntimeError("the flattening did not return one polyline per path")
+        lap("flatten")
+    off, pts = _convert(st, off_mm, pts_mm, m, rect, info, n_resident)
     lap("to_steps")
     info["paths"] = n = len(off) - 1
     if n == 0:
@@ -1119,6 +1332,10 @@ def build_argparser() -> argparse.ArgumentParser:
     ap.add_argument("--dash-offset-mm", type=float, default=None, help="where in the pattern a path starts (any sign; default 0); needs --dash-mm")
     ap.add_argument("--ring-entry", action="store_true", help="let the greedy order enter a closed stroke at its nearest vertex instead of the one the file lists first "
                                                               "(every ring vertex is a candidate; usually less pen-up travel, nothing promises it); not with --no-reorder")
+    ap.add_argument("--arcs", action="store_true", help="draw G2 / G3 as the arcs they state (I / J or R, G90.1 / G91.1, modal), flattened on the GPU with every point on "
+                                                        "the circle; without it they are drawn as their chords, as the reference draws them")
+    ap.add_argument("--arc-tolerance-mm", type=float, default=None, help="how far a chord may leave its arc, in the file's mm before --scale-x / --scale-y "
+                                                                         "(default: half a step on paper); needs --arcs")
     return ap
 
 
@@ -1147,6 +1364,9 @@ def add_stroke_args(ap: argparse.ArgumentParser, names: Sequence[str] = STROKE_A
 
 def report_lines(tag: str, info: dict, unmatched: bool = False):
     """the lines the tools print about the stroke passes that ran; `unmatched`: the pens line also counts the paths without a stroke colour"""
+    if "arcs" in info:
+        a = info["arcs"]
+        yield f"[{tag}] arcs: {a['arcs']} arcs drawn in {a['pieces']} pieces within {a['tolerance_mm']:g} mm, {a['full_circles']} full circles"
     if "clip" in info:
         c = info["clip"]; x0, y0, x1, y1 = c["rect"]
         yield (f"[{tag}] clip: {c['segments']} segments: {c['inside']} inside, {c['cut']} cut, {c['outside']} outside [{x0}, {x1}] x [{y0}, {y1}] steps -> "
@@ -1196,11 +1416,14 @@ def main(argv: Optional[Sequence[str]] = None, **device_steps) -> None:
     apply_speed_scale(GcodeOptions(speed_scale=opts.speed_scale))        # a bad scale ends the run before the file is read, as in the reference
     stroke_options(opts)
     dash_option(opts)
+    tol = arc_tolerance(opts)
     text = Path(a.input).read_bytes()
     data, info = build_stream_from_gcode(text, opts, **device_steps)
     Path(a.output).write_bytes(data)
     print(f"[gcode] {a.input}: {info['paths_mm']} pen-down paths, {info['pen_down_moves']} pen-down moves")
     print(f"[gcode] {info['paths']} paths in step space, {info['steps']} steps, target {info['target'][0]} x {info['target'][1]} steps")
+    if tol is not None and "arcs" not in info:
+        print(f"[gcode] arcs: no G2 / G3 arc in the file; tolerance {tol:g} mm unused")
     for line in report_lines("gcode", info):
         print(line)
     print(f"stream saved: {a.output} ({len(data)} bytes)")

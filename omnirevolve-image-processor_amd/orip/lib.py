@@ -92,6 +92,7 @@ SIGNATURES = {
     "orip_gcode_order_rings": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "orip_svg_flatten": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _f64, _P(_i64)]), "orip_svg_paths_fetch": (_i32, [_vp, _vp, _vp]),
     "orip_svg_bbox": (_i32, [_vp, _vp]), "orip_svg_fit": (_i32, [_vp, _f64, _f64, _f64, _f64]),
+    "orip_gcode_flatten": (_i32, [_vp, _vp, _vp, _i64, _vp, _i64, _f64, _P(_i64), _vp]),
     "orip_svg_hatch": (_i32, [_vp, _vp, _i64, _f64, _i32, _i32, _i32, _vp]), "orip_svg_hatch_groups_fetch": (_i32, [_vp, _vp]),
     "orip_svg_hatch_angle": (_i32, [_vp, _vp, _i64, _f64, _i32, _i32, _i32, _i32, _i32, _vp]),
     "orip_stream_pack": (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64]), "orip_stream_pack_fetch": (_i32, [_vp, _vp]),
@@ -118,6 +119,8 @@ DASH_UNIT, DASH_MAX_ENTRIES = 256, 64                        # include/orip.h: d
 IMPROVE_MAX_PATHS, IMPROVE_ROUNDS_AUTO = 65536, (1 << 63) - 1
 SEAM_STATS = ("closed", "moved", "travel_before", "travel_after")
 RING_ENTRY_STATS = ("closed", "moved", "candidates", "travel")
+ARC_STATS = ("arcs", "pieces", "full_circles")
+ARC_LINE, ARC_CW, ARC_CCW, ARC_MAX_DEPTH = 1, 2, 3, 16         # include/orip.h: the kinds of orip_gcode_flatten; ORIP_ARC_MAX_DEPTH
 
 _lib = None
 

@@ -5,6 +5,7 @@ The conversion to steps, the nearest-neighbour order of the paths and the packin
     python gcode2stream.py drawing.gcode -o stream.bin [--steps-per-mm 40] [--invert-y 1] [--speed-scale 1.5] [--no-reorder] ...
                            [--tool-pens [--pen-order 3,0,...]] [--allow-reverse]      (ours: pens from the T words, strokes drawn backwards where that is nearer)
                            [--ring-entry] [--loop-start]      (ours: the order enters a closed stroke at its nearest vertex; the seams of the sequence are then chosen together)
+                           [--arcs [--arc-tolerance-mm T]]      (ours: G2 / G3 are drawn as the arcs they state, flattened on the GPU; without it they are chords)
 """
 import os
 import sys

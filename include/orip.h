@@ -559,6 +559,52 @@ int orip_gcode_stipple(orip_ctx* ctx, const int64_t* ring_off /* [m+1] */, const
 int orip_svg_stipple(orip_ctx* ctx, const int32_t* ring_sub /* [m] */, const int32_t* ring_group /* [m] */, int64_t m, const orip_gcode_map* map, int32_t pitch, int32_t row,
                      int32_t shift, int32_t inset, const int32_t* rect /* [4] */, int32_t flags /* SERPENTINE | OCCLUDE | CLAMP */, int64_t* stats /* [7] */);
 int orip_gcode_stipple_fetch(orip_ctx* ctx, int32_t* xy /* [dots,2] */, int32_t* group /* [dots] */);
+/* fill_layers (csrc/fill.hip; ours, the reference has no such pass): a colour MASK of the raster pipeline is hatched on the canvas grid, so that a layer is
+ * drawn as tone and not only as its outline.  Integer arithmetic throughout: no floating point, no tolerance.
+ * Input.  Mask M, u8 [h, w], nonzero = set (explicit, or mask == NULL: the resident mask of `layer`, with h and w the resident size); the canvas W x H
+ *   pixels, each side 1 .. 2^20 (h and w likewise, h w < 2^31); the placement (num, den, dx, dy), num and den in 1 .. 2^20, dx and dy in -2^20 .. 2^20; the
+ *   direction u = (ux, uy), not zero, max(|ux|, |uy|) <= 4096; spacing in 2 .. 2^15, inset in 0 .. 2^15, min_len in 1 .. 2^15, all in canvas pixels; flags
+ *   ORIP_FILL_SERPENTINE | ORIP_FILL_ALONG | ORIP_FILL_ACROSS, at least one of the two families.
+ *   Ink.  Canvas pixel (X, Y) is INK iff c = floor((X - dx) den / num) and r = floor((Y - dy) den / num) satisfy 0 <= c < w, 0 <= r < h and M[r][c] != 0;
+ *   both divisions are floor divisions.  num / den is stage 05's scale, taken as the exact rational: the host passes (inner_w, w) if inner_w h <= inner_h w,
+ *   else (inner_h, h), and (dx, dy) = the left and top margin (orip.config.scale_factors).  Stated deviation: stage 05 maps a contour vertex with the float
+ *   scale, and a contour's integer index is taken here as the pixel's left / top edge, so fill and outline can differ by under one source pixel: that is
+ *   what the inset is for.
+ *   Lines.  n = (-uy, ux), U2 = ux^2 + uy^2, rs(v) = (isqrt(4 v) + 1) >> 1 (the nearest integer to sqrt(v)), R = rs(U2), D = rs(spacing^2 U2),
+ *   m = max(|ux|, |uy|).  Line k is n.p = k D for EVERY integer k: one family for the whole canvas, as in orip_svg_hatch_angle, so neighbouring layers line
+ *   up.  The major axis is x iff |ux| >= |uy|; the major coordinate a runs 0 .. A - 1 and the minor coordinate b 0 .. B - 1, (A, B) = (W, H) for x-major
+ *   and (H, W) for y-major.  The minor coordinate of line k at a is the nearest integer to N / d, halves toward +infinity: x-major (N, d) =
+ *   (k D + uy a, ux), y-major (N, d) = (ux a - k D, uy); both negated if d < 0; then b = floor((2 N + d) / (2 d)).  SAMPLE (k, a) EXISTS iff 0 <= b < B; it
+ *   is ON iff it exists and its pixel is INK.
+ *   Runs and segments.  A RUN is a maximal stretch of consecutive a whose samples are ON, [a0, a1].  im = (2 inset m + R) / (2 R) (the inset projected on
+ *   the major axis), lm = max(1, (2 min_len m + R) / (2 R)), integer divisions.  With s0 = a0 + im and s1 = a1 - im the run becomes the 2-point SEGMENT
+ *   sample(k, s0) -> sample(k, s1) iff s1 - s0 >= lm; otherwise it is counted in `short`.  Both ends are samples of the run, so they are INK pixels.
+ *   Stated deviation: between its ends a drawn segment can leave the sampled pixels by under one step.
+ *   Order.  With both family flags the family along u comes first; "across" is the same rule with (-uy, ux) as u.  Within a family k ascends, then a
+ *   ascends.  Under ORIP_FILL_SERPENTINE a line with k & 1 (two's complement) leaves its segments in descending a, each drawn from s1 to s0.
+ * stats, summed over the families: lines (the k with at least one existing sample), samples (the existing ones), on, runs, short, segments.
+ *   runs == short + segments always; |n.P - k D| <= m / 2 at every sample P of line k.
+ * With mask == NULL the call reads the resident masks and writes NO resident state of the raster chain (masks, their bit planes, edges, polylines) and
+ * nothing of the stroke passes; the segments wait in a list of their own for orip_fill_fetch (seg int32 [segments, 4]: x0 y0 x1 y1) until the next call
+ * that passes its argument checks.
+ * Errors before any launch, with nothing resident touched (a segment list from an earlier call included): any argument out of range, no family flag,
+ * unknown flags, NULL stats, a `layer` that is not resident or a size that is not the resident one when mask is NULL, and 2^26 blocks of 64 samples or
+ * more over the lines of both families (the ON bits of a call are kept whole).  Found on the device, after the count, leaving no segment list: 2^26
+ * segments or more.  None of these is a fault.
+ * Declined: spacing that varies with the tone inside a layer; a morphological inset of the mask (the inset is along the line, as in the reference's
+ * hatch_fill); anti-aliased or sub-pixel mask edges; linking the lines into zigzags (--hatch-connect does that for shapes with an outline, and a mask has
+ * none); filling from `labels` instead of the opened and closed masks; a bound on the worst case (a checkerboard gives a run per sample). */
+#define ORIP_FILL_SERPENTINE 1
+#define ORIP_FILL_ALONG 2
+#define ORIP_FILL_ACROSS 4
+#define ORIP_FILL_STATS 6
+#define ORIP_FILL_COORD_MAX (1 << 20)
+#define ORIP_FILL_U_MAX 4096
+#define ORIP_FILL_LEN_MAX (1 << 15)
+int orip_fill_mask(orip_ctx* ctx, const uint8_t* mask /* [h,w] or NULL = resident mask of `layer` */, int layer, int h, int w, int W, int H,
+                   int32_t num, int32_t den, int32_t dx, int32_t dy, int32_t ux, int32_t uy, int32_t spacing, int32_t inset, int32_t min_len,
+                   int32_t flags, int64_t* stats /* [6]: lines, samples, on, runs, short, segments */);
+int orip_fill_fetch(orip_ctx* ctx, int32_t* seg /* [segments,4]: x0 y0 x1 y1 */);
 /* --dashes / --dash-mm (csrc/gcode_dash.hip; ours, the reference has no such pass): a stroke with a dash pattern is drawn as its dashes.  All arithmetic is
  * integer on the step grid: nothing behind the conversion to steps is floating point.
  * Unit.  u = 1 / ORIP_DASH_UNIT = 1/256 step: every length below is in u.

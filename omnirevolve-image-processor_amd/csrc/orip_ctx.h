@@ -433,6 +433,12 @@ struct orip_ctx {
     // per chunk of 64 slots the dot mask, the dot count and its scan (the unit states both layouts), free between calls; st_out = THE DOT LIST, xy int2
     // [st_dots] and group int32[st_dots] of the last call (-1: none) until the next one that passes its argument checks
     DBuf st_tmp, st_ch, st_out; int64_t st_dots = -1;
+    // fill_layers (fill.hip), which reads the resident masks and writes nothing of the raster chain or of the stroke passes.  With Z blocks of 64 samples
+    // over the lines of both families and R runs: fl_tmp = mask u8[h w] (only of an explicit mask), on u64[Z + 1] = the ON bits, cs u64[Z + 1] = (run starts
+    // << 32 | run ends) per block, sc u64[Z + 1] = its scan, FlCounters; fl_runs = a0 int[R], a1 int[R], row int[R] (the line, counted over both families),
+    // keep u64[R + 1], kbase u64[R + 1] = its scan (the unit states both layouts), free between calls; fl_out = THE SEGMENT LIST, int4[fl_segs] = x0 y0 x1 y1
+    // of the last call (-1: none) until the next one that passes its argument checks
+    DBuf fl_tmp, fl_runs, fl_out; int64_t fl_segs = -1;
     // svg2stream (svg.hip): scratch of the flattening and of the box, the resident paths (off int64[sv_n + 1], pts double2[sv_total]; raw units after
     // orip_svg_flatten, page mm after orip_svg_fit) until the next flatten; orip_gcode_to_steps reads them when it is called without pointers
     DBuf sv_tmp, sv_tmp2, sv_off, sv_pts; int64_t sv_n = 0, sv_total = 0; bool sv_ready = false, sv_box_ok = false; double sv_box[4] = {0, 0, 0, 0};

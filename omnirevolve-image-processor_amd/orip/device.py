@@ -773,6 +773,29 @@ class Device:
                                          int(flags) | (_l.STIPPLE_CLAMP if clamp else 0), _p(st)))
         return self._stipple_result(st)
 
+    def fill_mask(self, mask, W: int, H: int, place, u, spacing: int, inset: int, min_len: int, flags: int, layer: int = 0):
+        """fill_layers (include/orip.h: orip_fill_mask): the hatch segments of a colour mask u8 [h, w] (nonzero = set; None: the resident mask of `layer`,
+        which is only read) on the canvas W x H, the mask placed by place = (num, den, dx, dy), along the direction u = (ux, uy) every `spacing` pixels,
+        `inset` pixels inside every run, runs of `min_len` pixels or more; flags: lib.FILL_SERPENTINE | lib.FILL_ALONG | lib.FILL_ACROSS.  Nothing resident
+        changes.  -> (seg int32 [segments, 4] = x0 y0 x1 y1 in canvas pixels, in drawing order, {lib.FILL_STATS})"""
+        m = None
+        if mask is not None:
+            m = np.ascontiguousarray(mask, np.uint8)
+            if m.ndim != 2:
+                raise ValueError(f"mask of shape {m.shape}: [h, w]")
+        h, w = (self.H, self.W) if m is None else m.shape
+        scal = [int(v) for v in (layer, h, w, W, H, *place, *u, spacing, inset, min_len, flags)]
+        if len(scal) != 15:
+            raise ValueError("place = (num, den, dx, dy) and u = (ux, uy)")
+        if any(abs(v) >= 1 << 31 for v in scal):
+            raise OripError(f"orip_fill_mask: an argument does not fit 32 bits: {scal}")
+        st = np.zeros(len(_l.FILL_STATS), np.int64)
+        self._ck(self.L.orip_fill_mask(self.h, None if m is None else _p(m), *scal, _p(st)))
+        d = {k: int(v) for k, v in zip(_l.FILL_STATS, st)}
+        seg = np.zeros((max(d["segments"], 1), 4), np.int32)
+        self._ck(self.L.orip_fill_fetch(self.h, _p(seg)))
+        return seg[:d["segments"]], d
+
     def gcode_dash(self, off, pts, pattern, phase, pat_off, pat_val, n: int | None = None):
         """--dashes / --dash-mm (include/orip.h: orip_gcode_dash): of the step polylines (off int64 [n + 1], pts int32 [total, 2]; both None = the n resident
         ones) every stroke with pattern[k] >= 0 is cut into the dashes of that pattern of the table (pat_off int32 [np + 1], pat_val int64, in 1/256 step),

@@ -86,6 +86,7 @@ SIGNATURES = {
     "orip_svg_hatch_link": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _P(GcodeMap), _i32, _i32, _vp]),
     "orip_gcode_stipple": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _i32, _vp]), "orip_gcode_stipple_fetch": (_i32, [_vp, _vp, _vp]),
     "orip_svg_stipple": (_i32, [_vp, _vp, _vp, _i64, _P(GcodeMap), _i32, _i32, _i32, _i32, _vp, _i32, _vp]),
+    "orip_fill_mask": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]), "orip_fill_fetch": (_i32, [_vp, _vp]),
     "orip_gcode_dash": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp]), "orip_gcode_dash_fetch": (_i32, [_vp, _vp]),
     "orip_gcode_improve": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _i64, _vp, _vp, _vp]),
     "orip_gcode_seam": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
@@ -114,6 +115,9 @@ HATCH_LINK_STATS = ("lines", "in_reach", "eligible", "links", "coincident", "pat
 HATCH_LINK_CLAMP, HATCH_LINK_REACH_MAX = 1, 1 << 20            # include/orip.h: the rings are clamped to the sheet; the longest link in steps
 STIPPLE_STATS = ("groups", "rows", "candidates", "near", "outside", "hidden", "dots")
 STIPPLE_SERPENTINE, STIPPLE_OCCLUDE, STIPPLE_CLAMP, STIPPLE_MAX = 1, 2, 4, 1 << 20      # include/orip.h: the flags; the largest pitch, row and inset in steps
+FILL_STATS = ("lines", "samples", "on", "runs", "short", "segments")
+FILL_SERPENTINE, FILL_ALONG, FILL_ACROSS = 1, 2, 4                                       # include/orip.h: the flags of orip_fill_mask
+FILL_COORD_MAX, FILL_U_MAX, FILL_LEN_MAX = 1 << 20, 4096, 1 << 15                          # the largest side and offset; direction component; spacing, inset and min_len in pixels
 DASH_STATS = ("paths_in", "dashed", "dashes", "collapsed", "paths_out", "points_out", "length_in", "length_on")
 DASH_UNIT, DASH_MAX_ENTRIES = 256, 64                        # include/orip.h: dash lengths are in 1/256 step; entries of one pattern at most
 IMPROVE_MAX_PATHS, IMPROVE_ROUNDS_AUTO = 65536, (1 << 63) - 1

@@ -5,6 +5,7 @@
     find_contours(edges, cfg)           -> {name: [int32 (N,1,2)]}                 (04_find_contours.py vectorize_layer)
     scale_vectors / sort_contours / dedup_layer / dedup_cross / plot_order         (05, 07, 08, 10, 12)
     run_path(bgr, cfg)                  -> ops per layer, everything resident on the GPU between stages
+    fill_options(cfg) / fill_layer(mask, w, h, cfg, opts)    -> hatch ops of a colour mask                (fill_layers.py; ours)
 
 Every function drives liborip.so through orip.device.Device; arrays cross the host boundary only where the
 reference's stage API puts a file.
@@ -20,7 +21,7 @@ import os
 import numpy as np
 
 from . import lib as _l
-from .config import Config, canvas_size_px, scale_factors
+from .config import Config, canvas_size_px, margins_px, scale_factors
 from .device import Device
 
 _dev: Device | None = None
@@ -286,6 +287,114 @@ def plot_order(lines: Sequence[np.ndarray], taps: Sequence[Tuple[int, int]], cfg
     d.set_polys(_l.SLOT_LINES_CROSS, layer, lines)
     d.set_taps(_l.TAPS_CROSS, layer, taps)
     return ops_from_device(d, layer, r_insert12(cfg))
+
+
+# ---------------------------------------------------------------- fill_layers: the colour masks hatched (ours; include/orip.h: orip_fill_mask)
+FILL_DEFAULTS = {"spacing_mm": 1.0, "angle_deg": 45.0, "direction": "along", "inset_mm": 0.3, "min_run_mm": 0.5, "serpentine": True, "order": "serpentine"}
+FILL_DIRECTIONS = {"along": _l.FILL_ALONG, "across": _l.FILL_ACROSS, "cross": _l.FILL_ALONG | _l.FILL_ACROSS}
+FILL_ORDERS = ("serpentine", "nearest")
+
+
+def _fill_pixels(what: str, mm, ppm: int, lo: int) -> int:
+    if isinstance(mm, bool) or not isinstance(mm, (int, float)) or not math.isfinite(mm):
+        raise ValueError(f"fill: {what} must be a number, not {mm!r}")
+    px = int(round(float(mm) * ppm))
+    if px < lo or px > _l.FILL_LEN_MAX:
+        raise ValueError(f"fill: {what} {mm:g} is {px} pixels at {ppm} pixels per mm: {lo} .. 2^15")
+    return px
+
+
+def fill_options(cfg: Config):
+    """the `fill` object of the config file (cfg._raw: Config has no such field) -> None without one, else {layer name: options} for the layers named under
+    "layers", in color_names order.  Options: spacing, inset, min_len (pixels: int(round(mm * pixels_per_mm))), u (orip.svg.hatch_direction_vector of
+    angle_deg, in the manifest's frame: x right, y down), flags (lib.FILL_*), order ("serpentine": as the device emits; "nearest": greedy from the end of
+    the outline), angle_deg.  An unknown key, a layer that is not in color_names or a value out of range raises ValueError naming it."""
+    from .svg import hatch_direction_vector
+    raw = (getattr(cfg, "_raw", None) or {}).get("fill")
+    if raw is None:
+        return None
+    if not isinstance(raw, dict):
+        raise ValueError("fill: must be an object")
+    for k in raw:
+        if k != "layers" and k not in FILL_DEFAULTS:
+            raise ValueError(f"fill: unknown key {k!r}")
+    layers = raw.get("layers", {})
+    if not isinstance(layers, dict):
+        raise ValueError("fill: layers must be an object of layer name -> options")
+    for name in layers:
+        if name not in cfg.color_names:
+            raise ValueError(f"fill: layer {name!r} is not in color_names {list(cfg.color_names)}")
+    ppm = int(cfg.pixels_per_mm)
+    out = {}
+    for name in cfg.color_names:
+        if name not in layers:
+            continue
+        own = layers[name]
+        if not isinstance(own, dict):
+            raise ValueError(f"fill: layers.{name} must be an object")
+        for k in own:
+            if k not in FILL_DEFAULTS:
+                raise ValueError(f"fill: unknown key {k!r} in layers.{name}")
+        o = dict(FILL_DEFAULTS, **{k: v for k, v in raw.items() if k != "layers"})
+        o.update(own)
+        if o["direction"] not in FILL_DIRECTIONS:
+            raise ValueError(f"fill: direction {o['direction']!r}: one of " + ", ".join(FILL_DIRECTIONS))
+        if o["order"] not in FILL_ORDERS:
+            raise ValueError(f"fill: order {o['order']!r}: one of " + ", ".join(FILL_ORDERS))
+        if not isinstance(o["serpentine"], bool):
+            raise ValueError(f"fill: serpentine must be true or false, not {o['serpentine']!r}")
+        if isinstance(o["angle_deg"], bool) or not isinstance(o["angle_deg"], (int, float)) or not math.isfinite(o["angle_deg"]):
+            raise ValueError(f"fill: angle_deg must be a finite number, not {o['angle_deg']!r}")
+        u = hatch_direction_vector(o["angle_deg"])
+        out[name] = {"spacing": _fill_pixels("spacing_mm", o["spacing_mm"], ppm, 2), "inset": _fill_pixels("inset_mm", o["inset_mm"], ppm, 0),
+                     "min_len": _fill_pixels("min_run_mm", o["min_run_mm"], ppm, 1), "u": u,
+                     "flags": FILL_DIRECTIONS[o["direction"]] | (_l.FILL_SERPENTINE if o["serpentine"] else 0), "order": o["order"],
+                     "angle_deg": math.degrees(math.atan2(u[1], u[0]))}
+    return out
+
+
+def fill_placement(cfg: Config, w_src: int, h_src: int) -> Tuple[int, int, int, int]:
+    """(num, den, dx, dy) of orip_fill_mask: stage 05's scale (orip.config.scale_factors) as the exact rational, and its offset"""
+    w_full, h_full = canvas_size_px(cfg)
+    ml, mr, mt, mb = margins_px(cfg)
+    inner_w, inner_h = max(1, w_full - ml - mr), max(1, h_full - mt - mb)
+    num, den = (inner_w, int(w_src)) if inner_w * int(h_src) <= inner_h * int(w_src) else (inner_h, int(h_src))
+    return num, den, ml, mt
+
+
+def fill_segments(mask, w_src: int, h_src: int, cfg: Config, opts: dict, dev: Device | None = None, layer: int = 0, start=None, fill_fn=None, order_fn=None):
+    """the hatch of one layer -> (seg int32 [n, 4] = x0 y0 x1 y1 in canvas pixels, in drawing order, {lib.FILL_STATS}).  mask u8 [h_src, w_src], or None for
+    the resident mask of `layer`; opts: one entry of fill_options; start: the canvas point (x, y) the pen comes from, for order "nearest" (None: the
+    origin).  fill_fn / order_fn stand in for Device.fill_mask / Device.gcode_order_pens (the CPU tests pass their doubles)."""
+    from .stream import to_steps
+    if mask is not None and tuple(np.asarray(mask).shape) != (int(h_src), int(w_src)):
+        raise ValueError(f"mask of shape {np.asarray(mask).shape} for a source of {w_src} x {h_src}")
+    W, H = canvas_size_px(cfg)
+    if fill_fn is None:
+        d = dev or device()
+        fill_fn = lambda *a: d.fill_mask(*a, layer=layer)
+    seg, st = fill_fn(mask, W, H, fill_placement(cfg, w_src, h_src), opts["u"], opts["spacing"], opts["inset"], opts["min_len"], opts["flags"])
+    seg = np.asarray(seg, np.int32).reshape(-1, 4)
+    if opts["order"] == "nearest" and len(seg):
+        if order_fn is None:
+            order_fn = (dev or device()).gcode_order_pens
+        ends = np.concatenate([to_steps(seg[:, 0:2], W, H), to_steps(seg[:, 2:4], W, H)], 1).astype(np.int32)
+        s0 = (0, 0) if start is None else tuple(int(v) for v in to_steps(np.asarray(start, np.float64).reshape(1, 2), W, H)[0])
+        order, rev = order_fn(ends, np.zeros(len(seg), np.int32), 1, reverse=True, start=s0)
+        seg = seg[np.asarray(order, np.int64)]
+        seg = np.where(np.asarray(rev, bool)[:, None], seg[:, [2, 3, 0, 1]], seg)
+    return np.ascontiguousarray(seg, np.int32), st
+
+
+def fill_ops(seg) -> List[dict]:
+    """segments as ops of stage 12's kind: {"type": "line", "points": float32 [2, 2]} in canvas pixels"""
+    return [{"type": "line", "points": np.asarray(s, np.float32).reshape(2, 2).copy()} for s in np.asarray(seg).reshape(-1, 4)]
+
+
+def fill_layer(mask, w_src: int, h_src: int, cfg: Config, opts: dict, dev: Device | None = None, layer: int = 0, start=None) -> List[dict]:
+    """the hatch of one layer as ops (fill_segments without the counts)"""
+    seg, _ = fill_segments(mask, w_src, h_src, cfg, opts, dev, layer, start)
+    return fill_ops(seg)
 
 
 # ---------------------------------------------------------------- layer concurrency

@@ -44,6 +44,7 @@ def main():
     ap.add_argument("--target-width-mm", type=int, dest="target_width_mm")
     ap.add_argument("--target-height-mm", type=int, dest="target_height_mm")
     ap.add_argument("--colors", dest="colors_json")
+    ap.add_argument("--fill", dest="fill_json", help="JSON merged into the config's `fill` object (fill_layers.py hatches the layers it names, in front of step 13)")
     ap.add_argument("--ref-dir", default=None, help="directory of the reference's image_processor/ for the stages outside the hot path")
     a = ap.parse_args()
     os.makedirs(a.output_dir, exist_ok=True)
@@ -62,6 +63,14 @@ def main():
         except Exception as e:
             print(f"Failed to parse --colors JSON: {e}", file=sys.stderr)
     merged.update({k: v for k, v in over.items() if v is not None})
+    if a.fill_json:
+        try:
+            fill = json.loads(a.fill_json)
+        except Exception as e:
+            sys.exit(f"Failed to parse --fill JSON: {e}")
+        if not isinstance(fill, dict):
+            sys.exit("--fill must be a JSON object")
+        merged["fill"] = dict(merged.get("fill") or {}, **fill)
     with open(dst, "w", encoding="utf-8") as f:
         json.dump(merged, f, indent=2, ensure_ascii=False)
     print("Config saved to", dst)
@@ -71,6 +80,8 @@ def main():
         s0, s1 = s1, s0
     for i in range(s0 - 1, s1):
         title, name = STEPS[i]
+        if name == "13_build_stream.py" and merged.get("fill") is not None:
+            run_step("[fill] Hatch the colour masks…", os.path.join(HERE, "fill_layers.py"), env)
         mine = os.path.join(HERE, name)
         if os.path.exists(mine):
             run_step(title, mine, env)

@@ -295,39 +295,92 @@ __global__ __launch_bounds__(1024) void k_taps_sequential(const int2* __restrict
     if (threadIdx.x == 0) *n_acc_out = nacc;
 }
 
-// the same sequential filter by one wavefront: the raster test of every candidate is order-free (the raster only changes after the
-// loop) and is done up front; the candidates and the accepted list then live in LDS and each candidate is checked against the
-// accepted ones 64 at a time
-__global__ __launch_bounds__(64) void k_taps_wave(const int2* __restrict__ seq, int n, int r, const u8* __restrict__ forb, int H, int W,
-                                                   int2* __restrict__ acc_out, int* __restrict__ n_acc_out) {
+// The same filter with one workgroup and a cell hash.  The raster test of every candidate is order-free (the raster only changes after
+// the loop) and is done up front.  An accepted candidate can block only candidates within r of it, so the candidates that passed the
+// raster are bucketed by cells of side max(r, 1): whatever lies within r of a point lies in the 3 x 3 cells around it.  The canvas has far
+// too many cells for a dense table (and off-canvas candidates have cells of their own), so the cells are hashed into `slots` chains; a
+// chain may hold several cells and any number of candidates, the distance test sorts them out.  The sequential rule is then decided in
+// rounds: a candidate is out as soon as one EARLIER candidate within r is accepted, accepted once every earlier candidate within r is
+// decided and none of them is accepted, and waits otherwise.  A state only ever goes from waiting to a final one, so a state read while
+// another thread writes it is either the old one (wait one more round) or the final one; the lowest waiting candidate has nothing to wait
+// for, so every round decides at least one.  The work of a candidate and round is its 3 x 3 cells, whatever the number of accepted taps.
+enum : uint8_t { TG_OUT = 0, TG_WAIT = 1, TG_ACC = 2 };       // out: refused by the raster or by an accepted tap; neither blocks anything
+#define TAPS_GRID_THREADS 256
+#define TAPS_GRID_LDS (150 * 1024)
+// LDS of k_taps_grid for n candidates, for the kernel and for the host's choice of kernel: 13 bytes a candidate and 4 a slot, at most 17 n + 272
+struct TapsGridLds {
+    unsigned slots;                                            // a power of two in (n / 2, n], at least 64
+    size_t cand, next, head, st, bytes;                        // byte offsets of int2 cand[n], int next[n], int head[slots], u8 st[n]
+    __host__ __device__ explicit TapsGridLds(int64_t n) {
+        slots = 64; while ((int64_t)slots * 2 <= n && slots < (1u << 30)) slots *= 2;
+        cand = 0; next = cand + (size_t)n * 8; head = next + (size_t)n * 4; st = head + (size_t)slots * 4; bytes = (st + (size_t)n + 15) & ~(size_t)15;
+    }
+    bool fits() const { return bytes <= TAPS_GRID_LDS; }      // beyond: k_taps_sequential
+};
+__device__ __forceinline__ unsigned tg_cell(int v, int side) { int q = v / side; if (v % side < 0) q--; return (unsigned)q; }      // floor(v / side); neighbours by wrapping +-1
+__device__ __forceinline__ unsigned tg_slot(unsigned cx, unsigned cy, unsigned mask) {
+    unsigned h = cx * 0x9E3779B1u + cy * 0x85EBCA6Bu; h ^= h >> 15; h *= 0x2C1B3C6Du; h ^= h >> 12;
+    return h & mask;
+}
+__global__ __launch_bounds__(TAPS_GRID_THREADS) void k_taps_grid(const int2* __restrict__ seq, int n, int r, const u8* __restrict__ forb, int H, int W,
+                                                                  int2* __restrict__ acc_out, int* __restrict__ n_acc_out) {
     extern __shared__ __align__(16) unsigned char smem[];
-    int2* cand = reinterpret_cast<int2*>(smem); int2* acc = cand + n;
-    uint8_t* st = reinterpret_cast<uint8_t*>(acc + n);            // 0: rejected by the raster, 1: inside, 2: outside the canvas (accepted as is)
-    const int lane = threadIdx.x;
-    for (int i = lane; i < n; i += 64) {
+    __shared__ unsigned wave_sum[TAPS_GRID_THREADS / 64];
+    const TapsGridLds L(n);
+    int2* cand = reinterpret_cast<int2*>(smem + L.cand); int* next = reinterpret_cast<int*>(smem + L.next); int* head = reinterpret_cast<int*>(smem + L.head);
+    volatile uint8_t* st = reinterpret_cast<volatile uint8_t*>(smem + L.st);
+    const int tid = threadIdx.x, side = max(r, 1);
+    const unsigned mask = L.slots - 1;
+    for (unsigned s = tid; s < L.slots; s += TAPS_GRID_THREADS) head[s] = -1;
+    for (int i = tid; i < n; i += TAPS_GRID_THREADS) {
         const int2 p = seq[i]; cand[i] = p;
         const bool inside = (p.y >= 0 && p.y < H && p.x >= 0 && p.x < W);
-        st[i] = inside ? (forb[(size_t)p.y * W + p.x] != 0 ? 0 : 1) : 2;
+        st[i] = inside ? (forb[(size_t)p.y * W + p.x] != 0 ? TG_OUT : TG_WAIT) : TG_ACC;         // off the canvas: accepted as it is
+    }
+    __syncthreads();
+    for (int i = tid; i < n; i += TAPS_GRID_THREADS) {
+        if (st[i] == TG_OUT) continue;
+        const int2 p = cand[i];
+        next[i] = atomicExch(&head[tg_slot(tg_cell(p.x, side), tg_cell(p.y, side), mask)], i);
     }
     __syncthreads();
     const long long r2 = (long long)r * r;
-    int nacc = 0;
-    for (int i = 0; i < n; i++) {
-        const uint8_t s = st[i];
-        if (s == 0) continue;
-        const int2 p = cand[i];
-        bool hit = false;
-        if (s == 1) {
-            for (int j0 = 0; j0 < nacc && !hit; j0 += 64) {
-                const int j = j0 + lane; bool h = false;
-                if (j < nacc) { const int2 a = acc[j]; const long long dx = a.x - p.x, dy = a.y - p.y; h = dx * dx + dy * dy <= r2; }
-                hit = __ballot(h) != 0;
+    int more;
+    do {
+        int waiting = 0;
+        for (int i = tid; i < n; i += TAPS_GRID_THREADS) {
+            if (st[i] != TG_WAIT) continue;
+            const int2 p = cand[i];
+            const unsigned cx = tg_cell(p.x, side), cy = tg_cell(p.y, side);
+            uint8_t verdict = TG_ACC;
+            for (int c = 0; c < 9 && verdict != TG_OUT; c++) {
+                for (int j = head[tg_slot(cx + (unsigned)(c % 3 - 1), cy + (unsigned)(c / 3 - 1), mask)]; j >= 0; j = next[j]) {
+                    if (j >= i) continue;
+                    const uint8_t sj = st[j];
+                    if (sj == TG_OUT) continue;
+                    const int2 q = cand[j];
+                    const long long dx = (long long)q.x - p.x, dy = (long long)q.y - p.y;
+                    if (dx * dx + dy * dy > r2) continue;
+                    if (sj == TG_ACC) { verdict = TG_OUT; break; }
+                    verdict = TG_WAIT;
+                }
             }
+            if (verdict == TG_WAIT) waiting = 1; else st[i] = verdict;
         }
-        if (!hit) { if (lane == 0) acc[nacc] = p; nacc++; }
-    }
-    for (int i = lane; i < nacc; i += 64) acc_out[i] = acc[i];
-    if (lane == 0) *n_acc_out = nacc;
+        more = __syncthreads_or(waiting);
+    } while (more);
+    // the accepted candidates in candidate order: a contiguous share per thread, its count scanned over the workgroup
+    const int per = (n + TAPS_GRID_THREADS - 1) / TAPS_GRID_THREADS;
+    const int i0 = min(n, tid * per), i1 = min(n, i0 + per);
+    unsigned cnt = 0;
+    for (int i = i0; i < i1; i++) cnt += st[i] == TG_ACC;
+    const unsigned incl = wave_incl_scan_u32(cnt);
+    if ((tid & 63) == 63) wave_sum[tid >> 6] = incl;
+    __syncthreads();
+    unsigned o = incl - cnt, total = 0;
+    for (int w = 0; w < TAPS_GRID_THREADS / 64; w++) { const unsigned s = wave_sum[w]; if (w < (tid >> 6)) o += s; total += s; }
+    for (int i = i0; i < i1; i++) if (st[i] == TG_ACC) acc_out[o++] = cand[i];
+    if (tid == 0) *n_acc_out = (int)total;
 }
 
 // Stage 10 keeps one cumulative "forbidden" raster while it walks the layers from dark to light (10:166-212).  begin clears it,
@@ -462,14 +515,15 @@ static int dedup_cross_layer_impl(orip_ctx* c, int src_layer, int layer, bool re
         HIPC(c, Tout.xy.ensure((size_t)std::max<int64_t>(n_seq, 1) * 8 + 64));
         if (n_seq > 0) {
             int* d_n = &LN(c).flags.as<LaneFlags>()->taps_kept;
-            const size_t lds_t = (size_t)n_seq * 17 + 64;
-            if (lds_t <= 150 * 1024 && !getenv("ORIP_TAPS_1WG")) {
+            if (n_seq > 0x7fffffff) ORIP_FAIL(c, "layer too large");
+            const TapsGridLds lds_t(n_seq);
+            if (lds_t.fits() && !getenv("ORIP_TAPS_1WG")) {
                 static std::once_flag attr_once;            // several layer threads may arrive here together
                 static std::atomic<int> attr_err{0};
-                std::call_once(attr_once, [&] { orip_max_lds(k_taps_wave, 150 * 1024, attr_err); });
-                if (attr_err.load()) ORIP_FAIL(c, "hipFuncSetAttribute(k_taps_wave) failed: %s", hipGetErrorString((hipError_t)attr_err.load()));
+                std::call_once(attr_once, [&] { orip_max_lds(k_taps_grid, TAPS_GRID_LDS, attr_err); });
+                if (attr_err.load()) ORIP_FAIL(c, "hipFuncSetAttribute(k_taps_grid) failed: %s", hipGetErrorString((hipError_t)attr_err.load()));
                 ProfScope ps(c, "k_taps_sequential");
-                hipLaunchKernelGGL(k_taps_wave, dim3(1), dim3(64), lds_t, LN(c).stream, seq, (int)n_seq, rad_taps, forb, H, W, acc, d_n);
+                hipLaunchKernelGGL(k_taps_grid, dim3(1), dim3(TAPS_GRID_THREADS), lds_t.bytes, LN(c).stream, seq, (int)n_seq, rad_taps, forb, H, W, acc, d_n);
             } else { ProfScope ps(c, "k_taps_sequential"); hipLaunchKernelGGL(k_taps_sequential, dim3(1), dim3(1024), 0, LN(c).stream, seq, (int)n_seq, rad_taps, forb, H, W, acc, d_n); }
             int na = 0;
             ORIP_TRY(vread(c, &na, d_n));

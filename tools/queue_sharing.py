@@ -12,7 +12,7 @@ CLASSES = [      # (lane class, kernels only that class of stream launches on th
     ("raster side", ("k_chain_ends_bits", "k_chain_build")),
     ("layer main", ("k_trace", "k_greedy_nn_fast", "k_plot_order_wave")),
     ("layer side", ("k_comp_paths_lds", "k_comp_paths_glb", "k_tail_replay", "k_seglen", "k_perim_leaves_seg")),
-    ("stage 10", ("k_taps_wave", "k_taps_sequential", "k_stamp_chain", "k_stamp_discs", "k_cut_counts", "k_cut_slots")),
+    ("stage 10", ("k_taps_grid", "k_taps_sequential", "k_stamp_chain", "k_stamp_discs", "k_cut_counts", "k_cut_slots")),
 ]
 LISTED = {k for _, names in CLASSES for k in names}
 def short(n):          # the kernel's name without its arguments; without its template arguments too, unless CLASSES lists it with them

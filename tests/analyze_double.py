@@ -1,6 +1,7 @@
 """numpy / Python restatement of the device side of analyze_colors (include/orip.h: orip_colors_table, orip_colors_hue, orip_colors_kmeans), written from
 the definitions and not from the kernels: the filter, the colour table, OpenCV's 8-bit RGB2HSV and the hue buckets, the k-means++ seeding with Python
-integers, Lloyd in float64 with the same expression order, and the exact choice of the best init.  Test infrastructure; nothing here runs on a GPU."""
+integers, Lloyd in float64 with the same expression order, and the exact choice of the best init.  hue_counts_np and first_draw_seeds are vectorised forms
+of hue_counts and of the first draw, for tables and seed searches of millions.  Test infrastructure; nothing here runs on a GPU."""
 from fractions import Fraction
 
 import numpy as np
@@ -90,11 +91,59 @@ def hue_counts(keys, counts):
     return np.array([out[k] for k in HUE_KEYS], np.int64)
 
 
+SDIV_NP, HDIV_NP = np.array(SDIV, np.int64), np.array(HDIV, np.int64)
+
+
+def hue_buckets_np(keys):
+    """hue_bucket for an array of keys at once -> index into HUE_KEYS per key.  int64 throughout: >> floors like Python's, h may be negative before the + 180.
+    tests/test_analyze_cases_host.py pins it to the scalar hue_bucket."""
+    k = np.asarray(keys).astype(np.int64)
+    r, g, b = k >> 16, (k >> 8) & 255, k & 255
+    v = np.maximum(r, np.maximum(g, b))
+    diff = v - np.minimum(r, np.minimum(g, b))
+    s = (diff * SDIV_NP[v] + (1 << 11)) >> 12
+    h = np.where(v == r, g - b, np.where(v == g, b - r + 2 * diff, r - g + 4 * diff))
+    h = (h * HDIV_NP[diff] + (1 << 11)) >> 12
+    hf = 2 * np.where(h < 0, h + 180, h)
+    ix = {n: i for i, n in enumerate(HUE_KEYS)}
+    conds = [v < 50, s < 30, (hf < 15) | (hf >= 345), hf < 25, hf < 45, hf < 75, hf < 150, hf < 200, hf < 270, hf < 330]
+    picks = [ix["black"], ix["gray"], ix["red"], np.where((s > 150) & (v < 150), ix["brown"], ix["orange"]), ix["orange"], ix["yellow"], ix["green"], ix["cyan"],
+             ix["blue"], np.where(s < 100, ix["pink"], ix["purple"])]
+    return np.select(conds, picks, ix["pink"]).astype(np.int64)
+
+
+def hue_counts_np(keys, counts):
+    """hue_counts without the Python loop per colour"""
+    out = np.zeros(len(HUE_KEYS), np.int64)
+    np.add.at(out, hue_buckets_np(keys), np.asarray(counts, np.int64))
+    return out
+
+
 def splitmix64(x):
     x = (x + 0x9E3779B97F4A7C15) & M64
     x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & M64
     x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & M64
     return x ^ (x >> 31)
+
+
+def splitmix64_np(x):
+    """splitmix64 of a uint64 array (uint64 arithmetic wraps modulo 2^64)"""
+    x = np.asarray(x, np.uint64) + np.uint64(0x9E3779B97F4A7C15)
+    x = (x ^ (x >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+    x = (x ^ (x >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    return x ^ (x >> np.uint64(31))
+
+
+def first_draw_seeds(total, wanted, limit=1 << 23):
+    """the smallest seed below `limit` whose first draw of init 0, splitmix64(seed) % total, equals w, for every w of `wanted` -> {w: seed}.  With every
+    count 1, total = D and the draw is the table index of the first centre."""
+    t = splitmix64_np(np.arange(limit, dtype=np.uint64)) % np.uint64(total)
+    out = {}
+    for w in wanted:
+        hit = np.flatnonzero(t == np.uint64(w))
+        if len(hit):
+            out[int(w)] = int(hit[0])
+    return out
 
 
 def seed_indices(keys, counts, K, seed, init):

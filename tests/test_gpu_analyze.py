@@ -40,7 +40,7 @@ def _k_colors(k, shape=(37, 53), seed=5):
 
 
 def _one_color():
-    img = np.empty((1000, 1003, 3), np.uint8); img[:] = (12, 200, 77)      # a million pixels in one bin; 1003 * 1000 is not a multiple of 4
+    img = np.empty((1000, 1003, 3), np.uint8); img[:] = (12, 200, 77)      # a million pixels in one bin; 1003 * 1000 = 4 * 250 750, every group whole (the partial one: analyze_cases.one_colour_tail)
     return img
 
 

@@ -96,7 +96,7 @@ import argparse
 import re
 from collections import namedtuple
 import sys
-from dataclasses import dataclass, fields
+from dataclasses import dataclass, fields, replace
 from pathlib import Path
 from typing import Callable, List, Optional, Sequence, Tuple, Union
 
@@ -519,199 +519,229 @@ def build_stream_from_gcode(text_or_paths, opts: Optional[GcodeOptions] = None, 
                             dash_fn: Optional[Callable] = None, seam_fn: Optional[Callable] = None, ring_entry_fn: Optional[Callable] = None,
                             flatten_fn: Optional[Callable] = None) -> Tuple[bytes, dict]:
     """The stream of a G-code text (str / bytes) or of paths in mm given as (off, pts_mm); opts as parsed, --speed-scale not yet applied.
-    Device steps, each None = the GPU (orip.device.Device; there is no CPU path in the product):
-      steps_fn(off, pts_mm, map: dict) -> (off int64, pts int32 [total, 2])      orip_gcode_to_steps
-      order_fn(ends int32 [n, 4]) -> order int32 [n]                             orip_gcode_order
-      codes_fn, pack_fn                                                          orip.stream.compile_plan
-    and, only with pens or --allow-reverse:
-      source_fn(n) -> src int32 [n]: the input path of every step polyline       orip_gcode_steps_source_fetch
-      order_pens_fn(ends, group int32 [n], n_groups, reverse) -> (order, rev)    orip_gcode_order_pens
-    and, only with --merge-paths (after the pens have been worked out, before any order):
-      merge_fn(off, pts, group int32 [n], n_groups, reverse) -> (off, pts, member_off, member, rev, counts)      orip_gcode_merge
-    info["merge"] then holds paths_in, paths_out, joins and cycles; the pen of a merged path is its members' pen.
-    and, only with --improve-order (after the order, before the paths are gathered; without pens: one group, no stroke reversed):
-      improve_fn(ends, group int32 [n], n_groups, order, rev, reverse, max_rounds) -> (order, rev, stats)       orip_gcode_improve
-    info["improve"] then holds travel_before, travel_after (pen-up steps of the whole plot), rounds, converged_groups and skipped_groups.
-    and, only with --clip, in the place of steps_fn (source_fn keeps its meaning: the input path of every stroke, now with repeats):
-      clip_fn(off, pts_mm, map: dict, rect: (x0, y0, x1, y1)) -> (off, pts, stats)                              orip_gcode_to_steps_clip
-    info["clip"] then holds rect and segments, inside, cut, outside, paths_out and points_out.
-    and, only with --simplify-mm (after the merge, before any order):
-      simplify_fn(off, pts, tol4) -> (off, pts, kept int64: the input index of every output point, stats)       orip_gcode_simplify
-    info["simplify"] then holds tol4, points_in, points_out and paths_changed.
-    and, only with --dedup (after the pens have been worked out, before the merge):
-      dedup_fn(off, pts, group int32 [n], n_groups) -> (off, pts, origin int32: the input stroke of every output stroke, stats)       orip_gcode_dedup
-    info["dedup"] then holds segments, whole, cut, covered, pieces, paths_out, points_out, draw_steps_in and draw_steps_out; a stroke keeps its origin's pen.
-    and, only with --dash-mm (after the pens have been worked out, before the dedup; it needs source_fn):
-      dash_fn(off, pts, pattern int32 [n], phase int64 [n], pat_off, pat_val) -> (off, pts, origin int32, stats)                      orip_gcode_dash
-    info["dash"] then holds the eight counts of include/orip.h; a dash keeps its stroke's pen.
-    and, only with --loop-start (after the order and the improvement, immediately before the paths are gathered):
-      seam_fn(off, pts, order or None, rev or None) -> (seam int32 [n] by sequence position, stats)                                    orip_gcode_seam
-    info["seam"] then holds closed, moved, travel_before and travel_after (pen-up steps of the whole plot).
-    and, only with --ring-entry (in the place of order_fn / order_pens_fn; without pens: one group):
-      ring_entry_fn(off, pts, group int32 [n], n_groups, reverse) -> (order, rev, seam int32 [n] by sequence position, stats)          orip_gcode_order_rings
-    info["ring_entry"] then holds closed, moved, candidates and travel (pen-up steps of the sequence as the call returned it).
-    and, only with --arcs on a text that holds a G2 / G3 arc (in front of steps_fn / clip_fn; parse_gcode_arcs then stands in parse_gcode's place):
-      flatten_fn(table: ArcTable, tol) -> (off int64, pts_mm float64 [total, 2], stats)                                                orip_gcode_flatten
-    info["arcs"] then holds tolerance_mm, arcs, pieces and full_circles.  The device's own leaves the polylines resident and returns (None, None, stats) when
-    the conversion is the device's too: that one is then called as steps_fn(None, None, map, n=paths), resp. clip_fn(None, None, map, rect, n=paths).
-    On a text without an arc the option changes nothing: parse_gcode's paths, no flatten_fn call, the same bytes.
+    Device steps, each None = the GPU (orip.device.Device; there is no CPU path in the product).  PASSES below states every signature and the place of
+    every pass; here, which option asks for which step and what it leaves in info:
+      steps_fn, order_fn, codes_fn, pack_fn   always (codes_fn and pack_fn: orip.stream.compile_plan)
+      source_fn, order_pens_fn   only with pens or --allow-reverse
+      merge_fn        only with --merge-paths.  info["merge"] holds paths_in, paths_out, joins and cycles; the pen of a merged path is its members' pen.
+      improve_fn      only with --improve-order (without pens: one group, no stroke reversed).  info["improve"] holds travel_before, travel_after (pen-up
+                      steps of the whole plot), rounds, converged_groups and skipped_groups.
+      clip_fn         only with --clip, in the place of steps_fn (source_fn keeps its meaning: the input path of every stroke, now with repeats).
+                      info["clip"] holds rect and segments, inside, cut, outside, paths_out and points_out.
+      simplify_fn     only with --simplify-mm.  info["simplify"] holds tol4, points_in, points_out and paths_changed.
+      dedup_fn        only with --dedup.  info["dedup"] holds segments, whole, cut, covered, pieces, paths_out, points_out, draw_steps_in and draw_steps_out;
+                      a stroke keeps its origin's pen.
+      dash_fn         only with --dash-mm (it needs source_fn).  info["dash"] holds the eight counts of include/orip.h; a dash keeps its stroke's pen.
+      seam_fn         only with --loop-start.  info["seam"] holds closed, moved, travel_before and travel_after (pen-up steps of the whole plot).
+      ring_entry_fn   only with --ring-entry, in the place of order_fn / order_pens_fn (without pens: one group).  info["ring_entry"] holds closed, moved,
+                      candidates and travel (pen-up steps of the sequence as the call returned it).
+      flatten_fn      only with --arcs on a text that holds a G2 / G3 arc (parse_gcode_arcs then stands in parse_gcode's place).  info["arcs"] holds
+                      tolerance_mm, arcs, pieces and full_circles.  On a text without an arc the option changes nothing: parse_gcode's paths, no
+                      flatten_fn call, the same bytes.
     pens: one pen per input path, 0..7, or -1 for --color-index (a text's T words under --tool-pens when None).  info["pens"] then counts the paths per
     pen, those that took --color-index ("unmatched") and the strokes drawn backwards ("reversed").
     Returns (bytes, counts)."""
-    steps = StrokeSteps(clip_fn if opts is not None and opts.clip else steps_fn, source_fn, merge_fn, simplify_fn, order_fn, order_pens_fn, improve_fn, codes_fn, pack_fn,
-                        dedup_fn)
-    return stroke_stream(text_or_paths, opts, device, steps, timings, pens, dash_fn=dash_fn, seam_fn=seam_fn, ring_entry_fn=ring_entry_fn, flatten_fn=flatten_fn)
+    fn = dict(flatten=flatten_fn, convert=clip_fn if opts is not None and opts.clip else steps_fn, dash=dash_fn, dedup=dedup_fn, merge=merge_fn, simplify=simplify_fn,
+              order=order_fn, order_pens=order_pens_fn, ring_entry=ring_entry_fn, improve=improve_fn, seam=seam_fn, source=source_fn, codes=codes_fn, pack=pack_fn)
+    return stroke_stream(text_or_paths, opts, device, StrokeSteps(fn), timings, pens)
 
 
-# The device steps of the stroke pipeline, each a callable or None = not given; build_stream_from_gcode states the signatures.  convert: steps_fn or, with --clip, clip_fn
-StrokeSteps = namedtuple("StrokeSteps", "convert source merge simplify order order_pens improve codes pack dedup", defaults=(None,) * 10)
+# ------------------------------------------------------------------ the stroke driver: what a pass is, stated once
+# One row per pass, in pipeline order.  keywords: the step keywords of the front doors that give a stand-in for the device's pass (the SVG door takes all,
+# the G-code door all but SVG_ONLY_STEPS); info, timing: the keys the pass writes to info and to `timings`; rewrites: the pass leaves a new stroke list,
+# on a device as its resident step polylines; method: the orip.device.Device method of the uploaded form; resident: the driver also calls the pass in a
+# form that reads the list the device holds (resolve_steps says when).  A stand-in is called as the device's uploaded form is, and returns what it returns:
+#   flatten     fn(table: ArcTable, tol) -> (off int64, pts_mm float64 [total, 2], stats), or (None, None, stats): the polylines stay resident for this
+#               device's own conversion, which is then called as convert(None, None, map[, rect], n=paths).  In front of the conversion
+#   convert     steps_fn(off, pts_mm, map: dict) -> (off int64, pts int32 [total, 2]); with --clip, in its place,
+#               clip_fn(off, pts_mm, map, rect: (x0, y0, x1, y1)) -> (off, pts, stats)
+#   dash        fn(off, pts, pattern int32 [n], phase int64 [n], pat_off, pat_val) -> (off, pts, origin int32: the input stroke of every output stroke,
+#               stats).  Behind the pens of the strokes, before the occlusion: a shape on top cuts dashes as it does on a screen
+#   hatch_link  fn(off, pts, cls int32 [n], ring_sub, ring_group, map, clamp, reach) -> (off, pts, member_off int64, member int32: the input strokes of
+#               every output stroke, stats).  Before the occlusion: it sees the hatch lines whole, and a shape on top cuts a zigzag
+#   occlude     fn(off, pts, level int32 [n], ring_sub, ring_level, map, clamp) -> (off, pts, origin int32, stats)
+#   dedup       fn(off, pts, group int32 [n], n_groups) -> (off, pts, origin int32, stats).  Before the merge, which joins the pieces it leaves
+#   merge       fn(off, pts, group int32 [n], n_groups, reverse) -> (off, pts, member_off, member, rev, counts)
+#   simplify    fn(off, pts, tol4) -> (off, pts, kept int64: the input index of every output point, stats).  Behind the merge: the joints can go
+#   stipple     fn(ring_sub, ring_group, map, clamp, lattice, inset, rect, flags) -> (xy int32 [dots, 2], group int32 [dots], stats).  It touches no
+#               stroke; its dots join the strokes as one-point ops immediately before the order
+#   order       order_fn(ends int32 [n, 4]) -> order int32 [n], or with pens or --allow-reverse
+#               order_pens_fn(ends, group int32 [n], n_groups, reverse) -> (order, rev)
+#   ring_entry  fn(off, pts, group int32 [n], n_groups, reverse) -> (order int32 [n], rev bool [n], seam int32 [n]: by sequence position, the stored ring
+#               vertex a closed stroke is entered at, 0 for an open one; stats).  --ring-entry, in the place of the order
+#   improve     fn(ends, group int32 [n], n_groups, order, rev, reverse, max_rounds) -> (order, rev, stats).  Behind the order
+#   seam        fn(off, pts, order int32 [n] or None, rev bool [n] or None) -> (seam int32 [n] by sequence position, stats).  Behind the order and the
+#               improvement, immediately before the paths are gathered
+# In the SVG door's keywords the fitted paths stand in front of the arguments of convert (in the place of off, pts_mm), hatch_link, occlude and stipple
+# (orip.svg.build_stream_from_svg).  source_fn(n) -> src int32 [n], the input path of every step polyline (orip_gcode_steps_source_fetch), is no pass.
+Pass = namedtuple("Pass", "name keywords info timing rewrites method resident")
+PASSES = (
+    Pass("flatten", ("flatten_fn",), "arcs", "flatten", False, "gcode_flatten", False),
+    Pass("convert", ("steps_fn", "clip_fn"), "clip", "to_steps", True, "gcode_to_steps", True),
+    Pass("dash", ("dash_fn",), "dash", "dash", True, "gcode_dash", True),
+    Pass("hatch_link", ("hatch_link_fn",), "hatch_link", "hatch_link", True, "gcode_hatch_link", True),
+    Pass("occlude", ("occlude_fn",), "occlude", "occlude", True, "gcode_occlude", True),
+    Pass("dedup", ("dedup_fn",), "dedup", "dedup", True, "gcode_dedup", True),
+    Pass("merge", ("merge_fn",), "merge", "merge", True, "gcode_merge", True),
+    Pass("simplify", ("simplify_fn",), "simplify", "simplify", True, "gcode_simplify", True),
+    Pass("stipple", ("stipple_fn",), "stipple", "stipple", False, "svg_stipple", False),
+    Pass("order", ("order_fn", "order_pens_fn"), None, "order", False, "gcode_order", False),
+    Pass("ring_entry", ("ring_entry_fn",), "ring_entry", "order", False, "gcode_order_rings", True),
+    Pass("improve", ("improve_fn",), "improve", "improve", False, "gcode_improve", False),
+    Pass("seam", ("seam_fn",), "seam", "seam", False, "gcode_seam", True),
+)
+SVG_ONLY_STEPS = ("hatch_link_fn", "occlude_fn", "stipple_fn")
+OTHER_STEPS = ("source_fn", "codes_fn", "pack_fn")              # step keywords of both doors that are no pass
 
 
-class Occlude:
-    """--occlude of the SVG door (orip.svg states it), which StrokeSteps does not carry: fn(off, pts, level int32 [n], ring_sub, ring_level, map, clamp) ->
-    (off, pts, origin int32: the input stroke of every output stroke, stats) or None = the device (orip_svg_occlude); path_level = the level of every
-    input path, which a stroke takes through its source; the rings as fitted paths and their levels; clamp = the rings are clamped as the strokes were"""
-    def __init__(self, fn, path_level, ring_sub, ring_level, clamp: bool):
-        self.fn = fn; self.path_level = np.asarray(path_level, np.int64).reshape(-1)
-        self.ring_sub = np.asarray(ring_sub, np.int32).reshape(-1); self.ring_level = np.asarray(ring_level, np.int32).reshape(-1); self.clamp = bool(clamp)
+def _flat(v, dtype):
+    return np.asarray(v, dtype).reshape(-1)
 
 
-class Dash:
-    """The dash pass (--dash-mm here, --dashes of the SVG door), which StrokeSteps does not carry: fn(off, pts, pattern int32 [n], phase int64 [n], pat_off,
-    pat_val) -> (off, pts, origin int32: the input stroke of every output stroke, stats) or None = the device (orip_gcode_dash); path_pattern (-1: solid) and
-    path_phase of every input path, which a stroke takes through its source; the pattern table in 1/256 step (include/orip.h states the rule)"""
-    def __init__(self, fn, path_pattern, path_phase, pat_off, pat_val):
-        self.fn = fn; self.path_pattern = np.asarray(path_pattern, np.int32).reshape(-1); self.path_phase = np.asarray(path_phase, np.int64).reshape(-1)
-        self.pat_off = np.asarray(pat_off, np.int32).reshape(-1); self.pat_val = np.asarray(pat_val, np.int64).reshape(-1)
-        self.device_follows = False                 # resolve_steps: pass and sources are both this device's, whose sources follow the dashes through origin
+# The per-drawing data of the four passes that take some.  A stroke takes its entry of a path_* table through its source.
+class Dash(namedtuple("Dash", "path_pattern path_phase pat_off pat_val")):
+    """--dash-mm here, --dashes of the SVG door: pattern (-1: solid) and phase of every input path; the pattern table in 1/256 step (include/orip.h)"""
+    def __new__(cls, path_pattern, path_phase, pat_off, pat_val):
+        return super().__new__(cls, _flat(path_pattern, np.int32), _flat(path_phase, np.int64), _flat(pat_off, np.int32), _flat(pat_val, np.int64))
 
 
-class HatchLink:
-    """--hatch-connect of the SVG door (orip.svg states it), which StrokeSteps does not carry: fn(off, pts, cls int32 [n], ring_sub, ring_group, map, clamp,
-    reach) -> (off, pts, member_off int64, member int32: the input strokes of every output stroke, stats) or None = the device (orip_svg_hatch_link);
-    path_cls = the class 2 g + f of every input path (-1: no hatch line), which a stroke takes through its source; the rings as fitted paths and the shape g
-    of each; clamp = the rings are clamped as the strokes were; reach = the longest link in steps (include/orip.h states the rule)"""
-    def __init__(self, fn, path_cls, ring_sub, ring_group, clamp: bool, reach: int):
-        self.fn = fn; self.path_cls = np.asarray(path_cls, np.int64).reshape(-1)
-        self.ring_sub = np.asarray(ring_sub, np.int32).reshape(-1); self.ring_group = np.asarray(ring_group, np.int32).reshape(-1)
-        self.clamp = bool(clamp); self.reach = int(reach)
-        self.device_follows = False                 # resolve_steps: pass and sources are both this device's, whose sources follow the zigzags through their first line
+class Occlude(namedtuple("Occlude", "path_level ring_sub ring_level clamp")):
+    """--occlude of the SVG door: the level of every input path; the rings as fitted paths and their levels; clamp = the rings are clamped as the strokes were"""
+    def __new__(cls, path_level, ring_sub, ring_level, clamp):
+        return super().__new__(cls, _flat(path_level, np.int64), _flat(ring_sub, np.int32), _flat(ring_level, np.int32), bool(clamp))
 
 
-class Stipple:
-    """--stipple-mm of the SVG door (orip.svg states it), which StrokeSteps does not carry: fn(ring_sub, ring_group, map, clamp, lattice, inset, rect, flags)
-    -> (xy int32 [dots, 2], group int32 [dots], stats) or None = the device (orip_svg_stipple); the rings as fitted paths and the shape g of each; clamp =
-    the rings are clamped as the strokes were; lattice = (pitch, row, shift) and inset in steps; rect = (x0, y0, x1, y1), the sheet or the clip rectangle;
-    flags of STIPPLE_SERPENTINE and STIPPLE_OCCLUDE (include/orip.h states the rule); pen_of(group int64 [dots]) -> the pen of every dot, -1 for
-    --color-index (None: every dot takes --color-index)"""
-    def __init__(self, fn, ring_sub, ring_group, clamp: bool, lattice, inset: int, rect, flags: int, pen_of: Optional[Callable] = None):
-        self.fn = fn; self.ring_sub = np.asarray(ring_sub, np.int32).reshape(-1); self.ring_group = np.asarray(ring_group, np.int32).reshape(-1)
-        self.clamp = bool(clamp); self.lattice = tuple(int(v) for v in lattice); self.inset = int(inset); self.rect = tuple(int(v) for v in rect)
-        self.flags = int(flags); self.pen_of = pen_of
+class HatchLink(namedtuple("HatchLink", "path_cls ring_sub ring_group clamp reach")):
+    """--hatch-connect of the SVG door: the class 2 g + f of every input path (-1: no hatch line); the rings as fitted paths and the shape g of each; clamp
+    as Occlude's; reach = the longest link in steps (include/orip.h)"""
+    def __new__(cls, path_cls, ring_sub, ring_group, clamp, reach):
+        return super().__new__(cls, _flat(path_cls, np.int64), _flat(ring_sub, np.int32), _flat(ring_group, np.int32), bool(clamp), int(reach))
 
 
-class Seam:
-    """--loop-start, which StrokeSteps does not carry: fn(off, pts, order int32 [n] or None, rev bool [n] or None) -> (seam int32 [n]: by sequence position,
-    the stored ring vertex a closed stroke starts and ends at, 0 for an open one; stats) or None = the device (orip_gcode_seam)"""
-    def __init__(self, fn=None):
-        self.fn = fn
+class Stipple(namedtuple("Stipple", "ring_sub ring_group clamp lattice inset rect flags pen_of")):
+    """--stipple-mm of the SVG door: the rings as HatchLink's; lattice = (pitch, row, shift) and inset in steps; rect = (x0, y0, x1, y1), the sheet or the
+    clip rectangle; flags of STIPPLE_SERPENTINE and STIPPLE_OCCLUDE; pen_of(group int64 [dots]) -> the pen of every dot, -1 for --color-index (None:
+    every dot takes --color-index)"""
+    def __new__(cls, ring_sub, ring_group, clamp, lattice, inset, rect, flags, pen_of=None):
+        return super().__new__(cls, _flat(ring_sub, np.int32), _flat(ring_group, np.int32), bool(clamp), tuple(int(v) for v in lattice), int(inset),
+                               tuple(int(v) for v in rect), int(flags), pen_of)
 
 
-class Flatten:
-    """--arcs, which StrokeSteps does not carry: fn(table: ArcTable, tol) -> (off int64, pts_mm float64 [total, 2], stats), or (None, None, stats) with the
-    polylines left resident for this device's conversion; or None = the device (orip_gcode_flatten)"""
-    def __init__(self, fn=None):
-        self.fn = fn
+@dataclass(frozen=True)
+class StrokeSteps:
+    """The passes of one drawing: fn[name] for the rows of PASSES and for "order_pens", "source", "codes" and "pack" (absent or None: not given); the data of
+    the passes that take some (None: the pass does not run); own: the names resolve_steps filled from its device"""
+    fn: dict
+    dash: Optional[Dash] = None
+    hatch_link: Optional[HatchLink] = None
+    occlude: Optional[Occlude] = None
+    stipple: Optional[Stipple] = None
+    own: frozenset = frozenset()
 
 
-class RingEntry:
-    """--ring-entry, which StrokeSteps does not carry: fn(off, pts, group int32 [n], n_groups, reverse) -> (order int32 [n], rev bool [n], seam int32 [n]:
-    by sequence position, the stored ring vertex a closed stroke is entered at, 0 for an open one; stats) or None = the device (orip_gcode_order_rings)"""
-    def __init__(self, fn=None):
-        self.fn = fn
+def steps_needed(st: StrokeSteps, o, grouped: bool, flatten: bool = False) -> List[str]:
+    """the names in st.fn this drawing calls for: the passes that are on, in the order of PASSES, then "order_pens" and "source".  flatten: --arcs found an arc"""
+    ring = bool(o.ring_entry)
+    on = dict(flatten=flatten, convert=True, dash=st.dash is not None, hatch_link=st.hatch_link is not None, occlude=st.occlude is not None, dedup=bool(o.dedup),
+              merge=bool(o.merge_paths), simplify=o.simplify_mm is not None, stipple=st.stipple is not None, order=not ring, ring_entry=ring,
+              improve=bool(o.improve_order), seam=bool(o.loop_start))
+    sources = bool(grouped) or on["dash"] or on["hatch_link"] or on["occlude"]
+    return [p.name for p in PASSES if on[p.name]] + ["order_pens"] * (bool(grouped) and not ring) + ["source"] * sources
 
 
-def resolve_steps(st: StrokeSteps, o, grouped: bool, device=None, convert: Optional[Callable] = None, force: bool = False, occlude: Optional[Occlude] = None,
-                  dash: Optional[Dash] = None, seam: Optional[Seam] = None, hatch_link: Optional[HatchLink] = None, stipple: Optional[Stipple] = None,
-                  ring_entry: Optional[RingEntry] = None, flatten: Optional[Flatten] = None):
-    """The steps the options need, those not given taken from a device -> (steps, device); codes and pack stay as given (orip.stream.compile_plan fills them).
-    When none is missing, and the caller does not `force` a device for steps of its own, no device is made and orip.stages is not imported.  convert(device)
-    -> the conversion of a front door whose paths are on the device already (orip.svg).  Dedup, merge and simplify work on the polylines the pass before them
-    left resident when that pass ran on this device, and are sent their input when it was given.  `dash`: its fn is filled in the same way, and it needs
-    the sources as the occlusion does; it stands between the conversion and the occlusion.  `occlude`: its fn is filled in the same way; it needs the
-    sources whether or not pens are in use, and the rings are fitted paths that only the device's own conversion leaves next to the strokes, so behind a
-    given conversion the strokes are uploaded first (an occlusion without rings makes them the resident list) and the pass then runs as it does otherwise.
-    `seam`: its fn is filled in the same way; it reads the strokes the last pass in front of the order left resident, or is sent them.  `hatch_link`: its
-    fn is filled in the same way, and it stands between the dash pass and the occlusion; it needs the sources, and its rings are fitted paths as the
-    occlusion's are, so behind a given pass the strokes are uploaded first in the same way (a link pass without rings makes them the resident list).
-    `stipple`: its fn is filled in the same way; it reads the fitted paths and touches no stroke, so it needs nothing resident behind the fit.  With it
-    the seam pass is always sent its strokes: the dots among them are in no resident list.  `ring_entry`: its fn is filled in the same way and reads or is
-    sent the strokes exactly as the seam pass is; it stands in the place of both orders, which are then not needed, and it rotates the rings on the host, so
-    behind it the seam pass is always sent its strokes.  `flatten`: --arcs found an arc; its fn is filled in the same way: this device's flattening leaves
-    its polylines resident for this device's conversion and fetches them for a given one."""
-    plain = ring_entry is None
-    need = ["convert"] + ["order"] * plain + (["order_pens"] * plain + ["source"]) * bool(grouped) + ["merge"] * bool(o.merge_paths) + ["improve"] * bool(o.improve_order) + \
-        ["simplify"] * (o.simplify_mm is not None) + ["dedup"] * bool(o.dedup) + ["source"] * (occlude is not None or dash is not None or hatch_link is not None)
-    if not force and all(getattr(st, k) is not None for k in need) and (occlude is None or occlude.fn is not None) and (dash is None or dash.fn is not None) and \
-            (seam is None or seam.fn is not None) and (hatch_link is None or hatch_link.fn is not None) and (stipple is None or stipple.fn is not None) and \
-            (plain or ring_entry.fn is not None) and (flatten is None or flatten.fn is not None):
+def _resident_form(method):
+    """a device's pass, called with the strokes the host holds, run on the list the device holds: every resident-form call is this one"""
+    return lambda off, pts, *a: method(None, None, *a, n=len(off) - 1)
+
+
+def _ring_pass(upload, run, resident: bool):
+    """a device's occlusion or hatch link.  Its rings are fitted paths, which only the svg_* form `run` reads, and that form has no uploaded one: behind a
+    given pass the strokes are uploaded first, through the ring-less gcode_* form `upload`, which makes them the resident list"""
+    def call(off, pts, key, ring_sub, ring_key, m, clamp, *reach):
+        if not resident:
+            upload(off, pts, key, np.zeros(1, np.int64), np.zeros((0, 2), np.int32), np.zeros(0, np.int32), *reach)
+        return run(key, ring_sub, ring_key, m, clamp, *reach, n=len(off) - 1)
+    return call
+
+
+def _own_flatten(device, resident: bool):
+    """a device's flattening: the polylines stay resident for its own conversion and are fetched for a given one"""
+    def call(table, tol):
+        _total, stats = device.gcode_flatten(table, tol)
+        return (None, None, stats) if resident else (*device.svg_paths(), stats)
+    return call
+
+
+def _own_improve(method):
+    return lambda ends, group, n_groups, order, rev, reverse, max_rounds: method(ends, group, n_groups, order, rev, reverse, max_rounds=max_rounds)
+
+
+def resolve_steps(st: StrokeSteps, o, grouped: bool, device=None, convert: Optional[Callable] = None, force: bool = False, flatten: bool = False):
+    """The steps the drawing needs (steps_needed), those not given taken from a device -> (steps, device); codes and pack stay as given
+    (orip.stream.compile_plan fills them).  When none is missing, and the caller does not `force` a device for steps of its own, no device is made and
+    orip.stages is not imported.  convert(device) -> the conversion of a front door whose paths are on the device already (orip.svg).
+
+    THE RESIDENCY RULE.  The table is walked in order.  An own pass that has a resident form reads the resident list iff the last list-rewriting pass that
+    ran was this device's own; otherwise it is sent its input.  The exceptions, each stated here and nowhere else:
+      - with a stipple the ring order and the seam pass are always sent their strokes: the dots among them are in no resident list;
+      - behind a ring order, which rotates the rings on the host, the seam pass is always sent its strokes;
+      - occlude and hatch link have no uploaded form that reads their rings: _ring_pass;
+      - the flattening returns (None, None, stats) only in front of this device's own conversion, and fetches its polylines for a given one."""
+    need = steps_needed(st, o, grouped, flatten)
+    if not force and all(st.fn.get(k) is not None for k in need):
         return st, device
     if device is None:
         from .stages import device as _default_device
         device = _default_device()
-    after_convert = st.convert is None                                     # resident behind this device's own conversion,
-    after_dash = dash.fn is None if dash is not None else after_convert    # behind its dash pass or, without one, behind the conversion,
-    after_link = hatch_link.fn is None if hatch_link is not None else after_dash      # behind its hatch link or, without one, behind what stands before it,
-    after_occlude = occlude.fn is None if occlude is not None else after_link         # behind its occlusion or, without one, behind what stands before it,
-    after_dedup = st.dedup is None if o.dedup else after_occlude           # behind its dedup or, without one, behind what stands before the dedup,
-    after_merge = st.merge is None if o.merge_paths else after_dedup       # behind its merge or, without one, behind what stands before the merge,
-    after_simplify = st.simplify is None if o.simplify_mm is not None else after_merge    # and behind its simplification or, without one, behind what stands before it
-    own = StrokeSteps(
-        convert=convert(device) if convert is not None else device.gcode_to_steps_clip if o.clip else device.gcode_to_steps, source=device.gcode_steps_source,
-        merge=(lambda off, pts, group, n_groups, reverse: device.gcode_merge(None, None, group, n_groups, reverse, n=len(off) - 1)) if after_dedup else device.gcode_merge,
-        dedup=(lambda off, pts, group, n_groups: device.gcode_dedup(None, None, group, n_groups, n=len(off) - 1)) if after_occlude else device.gcode_dedup,
-        simplify=(lambda off, pts, t4: device.gcode_simplify(None, None, t4, n=len(off) - 1)) if after_merge else device.gcode_simplify,
-        order=device.gcode_order, order_pens=device.gcode_order_pens,
-        improve=lambda ends, group, n_groups, order, rev, reverse, max_rounds: device.gcode_improve(ends, group, n_groups, order, rev, reverse, max_rounds=max_rounds))
-    if occlude is not None and occlude.fn is None:
-        def own_occlude(off, pts, level, ring_sub, ring_level, m, clamp):
-            if not after_link:
-                device.gcode_occlude(off, pts, level, np.zeros(1, np.int64), np.zeros((0, 2), np.int32), np.zeros(0, np.int32))
-            return device.svg_occlude(level, ring_sub, ring_level, m, clamp, n=len(off) - 1)
-        occlude.fn = own_occlude
-    if hatch_link is not None and hatch_link.fn is None:
-        hatch_link.device_follows = st.source is None and after_dash
+    fn = {k: st.fn.get(k) for k in need + ["codes", "pack"]}
+    own = {k for k in need if fn[k] is None}
+    dots, ring = st.stipple is not None, "ring_entry" in need
+    resident = False                                    # the last list-rewriting pass that ran was this device's own
+    for p in PASSES:
+        if p.name not in need:
+            continue
+        if p.name in own:
+            method, reads = getattr(device, p.method), p.resident and resident
+            if p.name == "flatten":
+                fn[p.name] = _own_flatten(device, "convert" in own)
+            elif p.name == "convert":                   # its resident form reads the flattened paths: _convert asks for it with n=
+                fn[p.name] = convert(device) if convert is not None else device.gcode_to_steps_clip if o.clip else method
+            elif p.name in ("hatch_link", "occlude"):
+                fn[p.name] = _ring_pass(method, getattr(device, "svg_" + p.name), reads)
+            elif p.name == "improve":
+                fn[p.name] = _own_improve(method)
+            else:
+                reads = reads and not (dots and p.name in ("ring_entry", "seam")) and not (ring and p.name == "seam")
+                fn[p.name] = _resident_form(method) if reads else method
+        if p.rewrites:
+            resident = p.name in own
+    for name, method in (("order_pens", device.gcode_order_pens), ("source", device.gcode_steps_source)):
+        if name in own:
+            fn[name] = method
+    return replace(st, fn=fn, own=frozenset(own)), device
 
-        def own_link(off, pts, cls, ring_sub, ring_group, m, clamp, reach):
-            if not after_dash:
-                device.gcode_hatch_link(off, pts, cls, np.zeros(1, np.int64), np.zeros((0, 2), np.int32), np.zeros(0, np.int32), reach)
-            return device.svg_hatch_link(cls, ring_sub, ring_group, m, clamp, reach, n=len(off) - 1)
-        hatch_link.fn = own_link
-    if seam is not None and seam.fn is None:
-        seam.fn = (lambda off, pts, order, rev: device.gcode_seam(None, None, order, rev, n=len(off) - 1)) if after_simplify and stipple is None and plain else device.gcode_seam
-    if not plain and ring_entry.fn is None:
-        ring_entry.fn = (lambda off, pts, group, n_groups, reverse: device.gcode_order_rings(None, None, group, n_groups, reverse, n=len(off) - 1)) \
-            if after_simplify and stipple is None else device.gcode_order_rings
-    if stipple is not None and stipple.fn is None:
-        stipple.fn = device.svg_stipple
-    if flatten is not None and flatten.fn is None:
-        def own_flatten(table, tol):
-            _total, stats = device.gcode_flatten(table, tol)
-            return (None, None, stats) if after_convert else (*device.svg_paths(), stats)
-        flatten.fn = own_flatten
-    if dash is not None and dash.fn is None:
-        dash.device_follows = st.source is None
-        dash.fn = (lambda off, pts, pattern, phase, po, pv: device.gcode_dash(None, None, pattern, phase, po, pv, n=len(off) - 1)) if after_convert else device.gcode_dash
-    return StrokeSteps(*(a or b for a, b in zip(st, own))), device
+
+def _host_sources(st: StrokeSteps, name: str, what: str, src) -> StrokeSteps:
+    """The sources behind the dash pass and the hatch link (`name`), which both change the stroke list in front of a pass that asks for them.  A device's
+    sources follow its own passes, through origin resp. through a zigzag's first line; unless both the pass and `source` are this device's, the host has
+    gathered them the same way (`src`, which _dash and _hatch_link hand over) and they are the source step from here on"""
+    if name in st.own and "source" in st.own:
+        return st
+
+    def gathered(n):
+        if n != len(src):
+            raise RuntimeError(f"{n} sources asked for, {what} left {len(src)} strokes")
+        return src
+    return replace(st, fn=dict(st.fn, source=gathered), own=st.own - {"source"})
 
 
 def _convert(st: StrokeSteps, off_mm, pts_mm, m: dict, rect, info: dict, n_resident: Optional[int] = None):
     """mm paths -> step polylines, clamped to the sheet or (rect) cut at it; info["clip"].  n_resident: the paths are that many the flattening left on the device"""
     more = {} if n_resident is None else {"n": int(n_resident)}
     if rect is None:
-        off, pts = st.convert(off_mm, pts_mm, m, **more)
+        off, pts = st.fn["convert"](off_mm, pts_mm, m, **more)
     else:
-        off, pts, cst = st.convert(off_mm, pts_mm, m, rect, **more)
+        off, pts, cst = st.fn["convert"](off_mm, pts_mm, m, rect, **more)
         info["clip"] = dict({"rect": tuple(int(v) for v in rect)}, **{k: int(cst[k]) for k in CLIP_STATS})
         if info["clip"]["inside"] + info["clip"]["cut"] + info["clip"]["outside"] != info["clip"]["segments"] or info["clip"]["paths_out"] != len(off) - 1:
             raise RuntimeError("the clip's counts do not add up")
@@ -720,7 +750,7 @@ def _convert(st: StrokeSteps, off_mm, pts_mm, m: dict, rect, info: dict, n_resid
 
 def _sources(st: StrokeSteps, n: int, n_paths: int, tables_ok: bool = True):
     """the input path of each of the n step polylines, checked against the n_paths input paths (tables_ok: the caller's per-path tables are of one length)"""
-    src = np.asarray(st.source(n), np.int64).reshape(-1)
+    src = np.asarray(st.fn["source"](n), np.int64).reshape(-1)
     if len(src) != n or (src < 0).any() or (src >= n_paths).any() or not tables_ok:
         raise RuntimeError("the source indices of the step polylines do not name input paths")
     return src
@@ -759,7 +789,7 @@ def _stroke_pens(st: StrokeSteps, o: GcodeOptions, pens, n: int, info: dict):
 def _merge(st: StrokeSteps, o: GcodeOptions, off, pts, pen, group, n_groups: int, info: dict):
     """strokes of one pen that meet end to end become one; the pen of a merged stroke is its members' pen; info["merge"]"""
     n_in = len(off) - 1
-    off, pts, member_off, member, _, mst = st.merge(off, pts, group if group is not None else np.zeros(n_in, np.int32), n_groups, bool(o.allow_reverse))
+    off, pts, member_off, member, _, mst = st.fn["merge"](off, pts, group if group is not None else np.zeros(n_in, np.int32), n_groups, bool(o.allow_reverse))
     off = np.asarray(off, np.int64); pts = np.asarray(pts, np.int32).reshape(-1, 2)
     member_off = np.asarray(member_off, np.int64).reshape(-1); member = np.asarray(member, np.int64).reshape(-1)
     n = len(off) - 1
@@ -785,7 +815,7 @@ def draw_steps(off, pts) -> int:
 def _dedup(st: StrokeSteps, off_in, pts_in, pen, group, n_groups: int, info: dict):
     """the strokes less every stretch an earlier segment of the same pen has drawn; a stroke left in parts keeps its pen; info["dedup"]"""
     n_in = len(off_in) - 1
-    *out, dst = st.dedup(off_in, pts_in, group if group is not None else np.zeros(n_in, np.int32), n_groups)
+    *out, dst = st.fn["dedup"](off_in, pts_in, group if group is not None else np.zeros(n_in, np.int32), n_groups)
     d = {k: int(dst[k]) for k in DEDUP_STATS}
     off, pts, origin, pen, group = _cut_result("the dedup", out, n_in, pen, group, info, may_be_empty=False)
     n = len(off) - 1
@@ -798,11 +828,11 @@ def _dedup(st: StrokeSteps, off_in, pts_in, pen, group, n_groups: int, info: dic
     return off, pts, pen, group
 
 
-def _occlude(st: StrokeSteps, oc: Occlude, off_in, pts_in, pen, group, m: dict, info: dict):
+def _occlude(st: StrokeSteps, off_in, pts_in, pen, group, m: dict, info: dict):
     """the strokes less what a shape of a higher level hides; a stroke takes its level through its source, and what is left of it keeps its pen; info["occlude"]"""
-    n_in = len(off_in) - 1
+    oc, n_in = st.occlude, len(off_in) - 1
     src = _sources(st, n_in, len(oc.path_level))
-    *out, ost = oc.fn(off_in, pts_in, oc.path_level[src].astype(np.int32), oc.ring_sub, oc.ring_level, m, oc.clamp)
+    *out, ost = st.fn["occlude"](off_in, pts_in, oc.path_level[src].astype(np.int32), oc.ring_sub, oc.ring_level, m, oc.clamp)
     d = {k: int(ost[k]) for k in OCCLUDE_STATS}
     off, pts, origin, pen, group = _cut_result("the occlusion", out, n_in, pen, group, info)
     n = len(off) - 1
@@ -813,13 +843,13 @@ def _occlude(st: StrokeSteps, oc: Occlude, off_in, pts_in, pen, group, m: dict, 
     return off, pts, pen, group
 
 
-def _dash(st: StrokeSteps, dh: Dash, off_in, pts_in, pen, group, info: dict):
+def _dash(st: StrokeSteps, off_in, pts_in, pen, group, info: dict):
     """the strokes, those with a pattern as their dashes; a stroke takes pattern and phase through its source, and a dash keeps its stroke's pen and, the
-    fifth value returned, its source; info["dash"]"""
-    n_in = len(off_in) - 1
+    source (_host_sources: the steps with them are the first value returned); info["dash"]"""
+    dh, n_in = st.dash, len(off_in) - 1
     src = _sources(st, n_in, len(dh.path_pattern), len(dh.path_phase) == len(dh.path_pattern))
     pattern = dh.path_pattern[src]
-    *out, dst = dh.fn(off_in, pts_in, pattern, dh.path_phase[src], dh.pat_off, dh.pat_val)
+    *out, dst = st.fn["dash"](off_in, pts_in, pattern, dh.path_phase[src], dh.pat_off, dh.pat_val)
     d = {k: int(dst[k]) for k in DASH_STATS}
     off, pts, origin, pen, group = _cut_result("the dash pass", out, n_in, pen, group, info)
     n = len(off) - 1
@@ -827,16 +857,16 @@ def _dash(st: StrokeSteps, dh: Dash, off_in, pts_in, pen, group, info: dict):
             d["paths_out"] != d["paths_in"] - d["dashed"] + d["dashes"] - d["collapsed"] or not (0 <= d["length_on"] <= d["length_in"]):
         raise RuntimeError("the dash pass's counts do not add up")
     info["dash"] = d
-    return off, pts, pen, group, src[origin]
+    return _host_sources(st, "dash", "the dash pass", src[origin]), off, pts, pen, group
 
 
-def _hatch_link(st: StrokeSteps, hl: HatchLink, off_in, pts_in, pen, group, m: dict, info: dict):
-    """the strokes, the hatch lines joined into zigzags; a stroke takes its class through its source, and a zigzag keeps the pen and, the fifth value
-    returned, the source of its first line; info["hatch_link"]"""
-    n_in = len(off_in) - 1
+def _hatch_link(st: StrokeSteps, off_in, pts_in, pen, group, m: dict, info: dict):
+    """the strokes, the hatch lines joined into zigzags; a stroke takes its class through its source, and a zigzag keeps the pen and the source of its
+    first line (_host_sources: the steps with them are the first value returned); info["hatch_link"]"""
+    hl, n_in = st.hatch_link, len(off_in) - 1
     src = _sources(st, n_in, len(hl.path_cls))
     cls = hl.path_cls[src]
-    off, pts, member_off, member, lst = hl.fn(off_in, pts_in, cls.astype(np.int32), hl.ring_sub, hl.ring_group, m, hl.clamp, hl.reach)
+    off, pts, member_off, member, lst = st.fn["hatch_link"](off_in, pts_in, cls.astype(np.int32), hl.ring_sub, hl.ring_group, m, hl.clamp, hl.reach)
     off = np.asarray(off, np.int64).reshape(-1); pts = np.asarray(pts, np.int32).reshape(-1, 2)
     member_off = np.asarray(member_off, np.int64).reshape(-1); member = np.asarray(member, np.int64).reshape(-1)
     d = {k: int(lst[k]) for k in HATCH_LINK_STATS}
@@ -857,27 +887,15 @@ def _hatch_link(st: StrokeSteps, hl: HatchLink, off_in, pts_in, pen, group, m: d
         pen, group = pen[first], group[first]
     info["paths"] = n
     info["hatch_link"] = dict(d, reach=hl.reach)
-    return off, pts, pen, group, src[first]
+    return _host_sources(st, "hatch_link", "the hatch link", src[first]), off, pts, pen, group
 
 
-def _sources_behind_link(src, n: int):
-    """what the source step gives behind a hatch link that did not run on the device whose sources are asked: the sources _hatch_link gathered through the first lines"""
-    if n != len(src):
-        raise RuntimeError(f"{n} sources asked for, the hatch link left {len(src)} strokes")
-    return src
-
-
-def _sources_behind_dash(src, n: int):
-    """what the source step gives behind a dash pass that did not run on the device whose sources are asked: the sources _dash gathered through origin"""
-    if n != len(src):
-        raise RuntimeError(f"{n} sources asked for, the dash pass left {len(src)} strokes")
-    return src
 
 
 def _simplify(st: StrokeSteps, off_in, pts_in, tol4: int, info: dict):
     """the same strokes with the same ends, every stroke an ascending selection of its own points; info["simplify"]"""
     n = len(off_in) - 1
-    off, pts, kept, _ = st.simplify(off_in, pts_in, tol4)
+    off, pts, kept, _ = st.fn["simplify"](off_in, pts_in, tol4)
     off = np.asarray(off, np.int64).reshape(-1); pts = np.asarray(pts, np.int32).reshape(-1, 2); kept = np.asarray(kept, np.int64).reshape(-1)
     if len(off) != n + 1 or off[0] != 0 or int(off[-1]) != len(pts) or len(kept) != len(pts) or (np.diff(off) < 2).any() or \
             not np.array_equal(kept[off[:-1]], off_in[:-1]) or not np.array_equal(kept[off[1:] - 1], off_in[1:] - 1) or \
@@ -896,13 +914,13 @@ def _checked_order(order, rev, n: int, group, reverse: bool, what: str):
     return order, rev
 
 
-def _ring_entry(rge: RingEntry, o: GcodeOptions, off, pts, group, n_groups: int, info: dict):
+def _ring_entry(st: StrokeSteps, o: GcodeOptions, off, pts, group, n_groups: int, info: dict):
     """--ring-entry: the greedy sequence with every closed stroke entered at its nearest ring vertex -> (pts with every ring rotated in place to the vertex
     it was entered at, (order, rev)); info["ring_entry"].  Checked as _checked_order checks, and: the seams name a ring vertex of every closed stroke and are
     0 elsewhere, no closed stroke is reversed, the counts add up and the travel is that of the strokes as gathered"""
     n = len(off) - 1
     grp = np.zeros(n, np.int32) if group is None else np.asarray(group, np.int32)
-    order, rev, seam, rst = rge.fn(off, pts, grp, n_groups if group is not None else 1, bool(o.allow_reverse))
+    order, rev, seam, rst = st.fn["ring_entry"](off, pts, grp, n_groups if group is not None else 1, bool(o.allow_reverse))
     order, rev = _checked_order(order, rev, n, grp, bool(o.allow_reverse), "the ring order is not a permutation that keeps the pens together and the directions allowed")
     seam = np.asarray(seam, np.int64).reshape(-1)
     d = {k: int(rst[k]) for k in RING_ENTRY_STATS}
@@ -931,13 +949,13 @@ def _order(st: StrokeSteps, o: GcodeOptions, off, pts, group, n_groups: int, inf
         if group is None:
             group, n_groups = np.zeros(n, np.int32), 1
     elif group is not None:
-        order, rev = _checked_order(*st.order_pens(ends, group, n_groups, reverse), n, group, True, "the path order is not a permutation that keeps the pens together")
+        order, rev = _checked_order(*st.fn["order_pens"](ends, group, n_groups, reverse), n, group, True, "the path order is not a permutation that keeps the pens together")
     else:                                                                 # one group, no stroke reversed
         group, n_groups = np.zeros(n, np.int32), 1
-        order, rev = _checked_order(st.order(ends), None, n, group, True, "the path order is not a permutation")
+        order, rev = _checked_order(st.fn["order"](ends), None, n, group, True, "the path order is not a permutation")
     if o.improve_order:
         lap("order")
-        order, rev, ist = st.improve(ends, group, n_groups, np.asarray(order, np.int32), rev, reverse, o.improve_rounds)
+        order, rev, ist = st.fn["improve"](ends, group, n_groups, np.asarray(order, np.int32), rev, reverse, o.improve_rounds)
         order, rev = _checked_order(order, rev, n, group, reverse, "the improved order is not a permutation that keeps the pens together and the directions allowed")
         info["improve"] = {k: int(ist[k]) for k in IMPROVE_STATS}
         if greedy is not None and info["improve"]["travel_before"] != info["ring_entry"]["travel"]:
@@ -955,9 +973,10 @@ def travel_steps(off, pts, start=(0, 0)) -> int:
     return int(np.abs(a - np.concatenate([np.asarray(start, np.int64).reshape(1, 2), b[:-1]])).max(1).sum())
 
 
-def _stipple(sp: Stipple, m: dict, info: dict):
+def _stipple(st: StrokeSteps, m: dict, info: dict):
     """the dots of the stippled shapes, (xy, group), in the order the rule states; info["stipple"]"""
-    xy, grp, sst = sp.fn(sp.ring_sub, sp.ring_group, m, sp.clamp, sp.lattice, sp.inset, sp.rect, sp.flags)
+    sp = st.stipple
+    xy, grp, sst = st.fn["stipple"](sp.ring_sub, sp.ring_group, m, sp.clamp, sp.lattice, sp.inset, sp.rect, sp.flags)
     xy = np.asarray(xy, np.int32).reshape(-1, 2); grp = np.asarray(grp, np.int64).reshape(-1)
     d = {k: int(sst[k]) for k in STIPPLE_STATS}
     (p, q, s), (x0, y0, x1, y1) = sp.lattice, sp.rect
@@ -971,7 +990,7 @@ def _stipple(sp: Stipple, m: dict, info: dict):
     return xy, grp
 
 
-def _seam(sm: Seam, off, pts, order, rev, info: dict, is_tap=None):
+def _seam(st: StrokeSteps, off, pts, order, rev, info: dict, is_tap=None):
     """the strokes gathered in drawing order, every closed one started at the vertex the pass chose; info["seam"].  is_tap[k]: stroke k is a dot, which the
     pass is sent as the open two-point stroke P, P (its seam is 0)"""
     n = len(off) - 1
@@ -979,7 +998,7 @@ def _seam(sm: Seam, off, pts, order, rev, info: dict, is_tap=None):
     if is_tap is not None and is_tap.any():
         twice = np.ones(len(pts), np.int64); twice[off[:-1][is_tap]] = 2
         s_off = np.concatenate([[0], np.cumsum(np.diff(off) + is_tap)]).astype(np.int64); s_pts = np.repeat(pts, twice, axis=0)
-    seam, sst = sm.fn(s_off, s_pts, None if order is None else np.asarray(order, np.int32), None if rev is None else np.asarray(rev, bool))
+    seam, sst = st.fn["seam"](s_off, s_pts, None if order is None else np.asarray(order, np.int32), None if rev is None else np.asarray(rev, bool))
     seam = np.asarray(seam, np.int64).reshape(-1)
     d = {k: int(sst[k]) for k in SEAM_STATS}
     seq = np.arange(n) if order is None else np.asarray(order, np.int64)
@@ -1012,14 +1031,9 @@ def _plan(o: GcodeOptions, sc: ST.StreamConfig, off, pts, path_pen, is_tap=None)
 
 
 def stroke_stream(text_or_paths, opts: Optional[GcodeOptions], device, steps: StrokeSteps, timings: Optional[dict] = None, pens: Optional[np.ndarray] = None,
-                  occlude: Optional[Occlude] = None, dash: Optional[Dash] = None, dash_fn: Optional[Callable] = None, seam_fn: Optional[Callable] = None,
-                  seam: Optional["Seam"] = None, hatch_link: Optional[HatchLink] = None, stipple: Optional[Stipple] = None,
-                  ring_entry_fn: Optional[Callable] = None, ring_entry: Optional[RingEntry] = None, flatten_fn: Optional[Callable] = None) -> Tuple[bytes, dict]:
-    """build_stream_from_gcode with the device steps as one record: parse, [flatten: --arcs on a text with an arc, with flatten_fn], convert, pens of the
-    strokes, [dash: --dash-mm gives every path the one pattern,
-    with dash_fn; the SVG door brings a record of its own], [hatch_link, the SVG door's], [occlude, the SVG door's], dedup, merge, simplify, [stipple, the
-    SVG door's: its dots join the strokes as one-point ops], order [ring_entry: --ring-entry in the greedy order's place, with ring_entry_fn, or the record a
-    door has resolved already], [seam: --loop-start, with seam_fn, or the record a door has resolved already], plan, compile"""
+                  convert: Optional[Callable] = None, force: bool = False) -> Tuple[bytes, dict]:
+    """build_stream_from_gcode with the steps as one record: parse, the passes of PASSES that the options and the records of `steps` switch on, plan,
+    compile.  --dash-mm gives every path the one pattern unless the door brings a Dash record of its own.  convert, force: resolve_steps'"""
     import time
     o = apply_speed_scale(GcodeOptions(**{f.name: getattr(opts, f.name) for f in fields(GcodeOptions)}) if opts is not None else GcodeOptions())
     W, H = target_size(o)
@@ -1063,27 +1077,25 @@ def stroke_stream(text_or_paths, opts: Optional[GcodeOptions], device, steps: St
         return EMPTY_STREAM, dict(info, bytes=len(EMPTY_STREAM))
     if not (1 <= W <= MAX_TARGET_STEPS and 1 <= H <= MAX_TARGET_STEPS):
         raise ValueError(f"target size {W} x {H} steps: each side must be in 1..2^30 (step coordinates are int32 on the device)")
-    if own_dash is not None and dash is None:                             # --dash-mm: every path gets the pattern
-        dash = Dash(dash_fn, np.zeros(len(off_mm) - 1, np.int32), np.full(len(off_mm) - 1, own_dash[1], np.int64), [0, len(own_dash[0])], own_dash[0])
-    sm = (seam if seam is not None else Seam(seam_fn)) if o.loop_start else None
-    rge = (ring_entry if ring_entry is not None else RingEntry(ring_entry_fn)) if o.ring_entry else None
-    flt = Flatten(flatten_fn) if table is not None else None
-    st, device = resolve_steps(steps, o, grouped, device, occlude=occlude, dash=dash, seam=sm, hatch_link=hatch_link, stipple=stipple, ring_entry=rge,
-                               flatten=flt)
+    if own_dash is not None and steps.dash is None:                       # --dash-mm: every path gets the pattern
+        steps = replace(steps, dash=Dash(np.zeros(len(off_mm) - 1, np.int32), np.full(len(off_mm) - 1, own_dash[1], np.int64), [0, len(own_dash[0])], own_dash[0]))
+    need = steps_needed(steps, o, grouped, table is not None)
+    st, device = resolve_steps(steps, o, grouped, device, convert, force, table is not None)
     m = dict(scale_x=o.scale_x, scale_y=o.scale_y, offset_x_mm=o.offset_x_mm, offset_y_mm=o.offset_y_mm, steps_per_mm=o.steps_per_mm, W=W, H=H, invert_y=int(bool(o.invert_y)))
+    n_groups = MAX_PENS if pens is not None else 1
 
     def finish(off, pts, pen, group):
         """behind the stroke passes: [the dots], the order, [the seams], the plan, the bytes"""
         is_tap = None
-        if stipple is not None:
+        if st.stipple is not None:
             lap("order")
-            xy, dot_group = _stipple(stipple, m, info)
+            xy, dot_group = _stipple(st, m, info)
             info["taps"] = len(xy)
             if len(xy):                                                   # one-point ops behind the strokes, in the order the rule states
                 is_tap = np.concatenate([np.zeros(len(off) - 1, bool), np.ones(len(xy), bool)])
                 off = np.concatenate([off, off[-1] + 1 + np.arange(len(xy), dtype=np.int64)]); pts = np.concatenate([pts, xy])
                 if grouped:
-                    dot_pen = np.full(len(xy), -1, np.int64) if pens is None or stipple.pen_of is None else np.asarray(stipple.pen_of(dot_group), np.int64).reshape(-1)
+                    dot_pen = np.full(len(xy), -1, np.int64) if pens is None or st.stipple.pen_of is None else np.asarray(st.stipple.pen_of(dot_group), np.int64).reshape(-1)
                     if len(dot_pen) != len(xy) or (dot_pen < -1).any() or (dot_pen >= MAX_PENS).any():
                         raise RuntimeError("the pens of the dots: one per dot, each -1 or a pen")
                     dot_pen = np.where(dot_pen < 0, int(o.color_index), dot_pen)
@@ -1095,12 +1107,12 @@ def stroke_stream(text_or_paths, opts: Optional[GcodeOptions], device, steps: St
         if len(off) <= 1:                                                 # neither a stroke nor a dot
             return EMPTY_STREAM, dict(info, bytes=len(EMPTY_STREAM))
         greedy = None
-        if rge is not None:                                               # in the greedy order's place; everything behind sees a ring where it is entered
-            pts, greedy = _ring_entry(rge, o, off, pts, group, n_groups, info)
+        if "ring_entry" in need:                                          # in the greedy order's place; everything behind sees a ring where it is entered
+            pts, greedy = _ring_entry(st, o, off, pts, group, n_groups, info)
         order, rev = _order(st, o, off, pts, group, n_groups, info, lap, greedy)
-        if sm is not None:
+        if "seam" in need:
             lap("order")
-            off, pts = _seam(sm, off, pts, order, rev, info, is_tap)
+            off, pts = _seam(st, off, pts, order, rev, info, is_tap)
             lap("seam")
         elif order is not None:
             off, pts = gather_paths(off, pts, order, rev)
@@ -1111,22 +1123,21 @@ def stroke_stream(text_or_paths, opts: Optional[GcodeOptions], device, steps: St
         lap("order")
         P = _plan(o, sc, off, pts, pen[order] if pens is not None else None, is_tap)
         lap("plan")
-        data, table, coff = ST.compile_plan(P, sc, device, st.codes, st.pack, initial_div=int(sc.div_start), lap=lap)
+        data, table, coff = ST.compile_plan(P, sc, device, st.fn.get("codes"), st.fn.get("pack"), initial_div=int(sc.div_start), lap=lap)
         info.update(steps=int(coff[-1]), bytes=len(data), pieces=len(table.pos), moves=len(P.moves))
         return data, info
 
     def nothing_left():
         """no stroke is left: the empty stream, unless the dots are still to come"""
-        if stipple is None:
+        if st.stipple is None:
             return EMPTY_STREAM, dict(info, bytes=len(EMPTY_STREAM))
         if pens is not None and "pens" not in info:
             info["pens"] = {"paths": [0] * MAX_PENS, "unmatched": 0, "reversed": 0}
         return finish(np.zeros(1, np.int64), np.zeros((0, 2), np.int32), *((np.zeros(0, np.int64), np.zeros(0, np.int32)) if grouped else (None, None)))
 
-    n_groups = MAX_PENS if pens is not None else 1
     n_resident = None
     if table is not None:
-        off_f, pts_mm, ast = flt.fn(table, arc_tol)
+        off_f, pts_mm, ast = st.fn["flatten"](table, arc_tol)
         info["arcs"] = dict({"tolerance_mm": arc_tol}, **{k: int(ast[k]) for k in ARC_STATS})
         if pts_mm is None:
             n_resident, off_mm = len(off_mm) - 1, None
@@ -1141,40 +1152,18 @@ def stroke_stream(text_or_paths, opts: Optional[GcodeOptions], device, steps: St
     if n == 0:
         return nothing_left()
     pen, group = _stroke_pens(st, o, pens, n, info) if grouped else (None, None)
-    if dash is not None:                                                  # before the occlusion: a shape on top cuts dashes as it does on a screen
-        lap("order")                                                      # the sources and the pens belong to the order's lap
-        off, pts, pen, group, dash_src = _dash(st, dash, off, pts, pen, group, info)
-        if not dash.device_follows:                                       # a given pass or given sources: nobody gathered them through origin but _dash
-            st = st._replace(source=lambda k: _sources_behind_dash(dash_src, k))
-        lap("dash")
-        if len(off) <= 1:                                                 # every stroke lies in a gap
-            return nothing_left()
-    if hatch_link is not None:                                            # before the occlusion: it sees the hatch lines whole, and a shape on top cuts a zigzag
-        lap("order")                                                      # the sources and the pens belong to the order's lap
-        off, pts, pen, group, link_src = _hatch_link(st, hatch_link, off, pts, pen, group, m, info)
-        if not hatch_link.device_follows:                                 # a given pass or given sources: nobody gathered them through the first lines but _hatch_link
-            st = st._replace(source=lambda k: _sources_behind_link(link_src, k))
-        lap("hatch_link")
-    if occlude is not None:
-        lap("order")                                                      # the sources and the pens belong to the order's lap
-        off, pts, pen, group = _occlude(st, occlude, off, pts, pen, group, m, info)
-        lap("occlude")
-        if len(off) <= 1:                                                 # everything lies under a shape
-            return nothing_left()
-    if o.dedup:
-        lap("order")                                                      # the sources and the pens belong to the order's lap
-        off, pts, pen, group = _dedup(st, off, pts, pen, group, n_groups, info)
-        lap("dedup")
-    if o.merge_paths:
-        if not (o.dedup or occlude is not None or dash is not None or hatch_link is not None):
-            lap("order")                                                  # the sources and the pens belong to the order's lap, as before
-        off, pts, pen, group = _merge(st, o, off, pts, pen, group, n_groups, info)
-        lap("merge")
-    if tol4 is not None:
-        if not (o.merge_paths or o.dedup or occlude is not None or dash is not None or hatch_link is not None):
+    # The list-rewriting passes behind the conversion, as (steps, off, pts, pen, group) -> the same.  A pass that may not leave the list empty has raised
+    # by then, so one exit serves all; lap("order") in front of each: the sources and the pens belong to the order's lap
+    rewrite = {"dash": lambda st, *s: _dash(st, *s, info), "hatch_link": lambda st, *s: _hatch_link(st, *s, m, info),
+               "occlude": lambda st, *s: (st, *_occlude(st, *s, m, info)), "dedup": lambda st, *s: (st, *_dedup(st, *s, n_groups, info)),
+               "merge": lambda st, *s: (st, *_merge(st, o, *s, n_groups, info)), "simplify": lambda st, off, pts, *s: (st, *_simplify(st, off, pts, tol4, info), *s)}
+    for p in PASSES:
+        if p.name in rewrite and p.name in need:
             lap("order")
-        off, pts = _simplify(st, off, pts, tol4, info)
-        lap("simplify")
+            st, off, pts, pen, group = rewrite[p.name](st, off, pts, pen, group)
+            lap(p.timing)
+            if len(off) <= 1:                                             # every stroke lies in a gap or under a shape
+                return nothing_left()
     return finish(off, pts, pen, group)
 
 

@@ -1051,38 +1051,27 @@ def build_stream_from_svg(text: Union[str, bytes, SegmentTable], opts: Optional[
       fit_fn(paths, sx, sy, ox, oy) -> paths       orip_svg_fit
       hatch_fn(paths, fill_group, params) -> (paths, counts)   orip_svg_hatch  (only with --hatch-spacing-mm; params: hatch_params(); info["hatch"] = counts)
       fetch_fn(paths, with_points) -> (off int64, pts float64 or None)   orip_svg_paths_fetch  (the points only with want_paths: info["fitted_paths"])
-      steps_fn(paths, map) -> (off, pts int32)     orip_gcode_to_steps without pointers
-      order_fn, codes_fn, pack_fn                  as in orip.gcode.build_stream_from_gcode
-    and, only with --pen-colors or --allow-reverse:
-      hatch_groups_fn(paths, segments) -> int32 [segments]   orip_svg_hatch_groups_fetch  (the fill group of every hatch line)
-      source_fn, order_pens_fn                     as in orip.gcode.build_stream_from_gcode
-    and, only with --merge-paths:
-      merge_fn                                     as in orip.gcode.build_stream_from_gcode (hatch lines go through it like any path; serpentine lines do not touch)
-    and, only with --improve-order:
-      improve_fn                                   as in orip.gcode.build_stream_from_gcode
-    and, only with --clip, in the place of steps_fn (hatch lines are cut like any path, and their pens still come through the sources):
-      clip_fn(paths, map, rect) -> (off, pts int32, stats)   orip_gcode_to_steps_clip without pointers
-    and, only with --simplify-mm:
-      simplify_fn                                  as in orip.gcode.build_stream_from_gcode (a hatch line has two points and passes through untouched)
-    and, only with --dedup:
-      dedup_fn                                     as in orip.gcode.build_stream_from_gcode (hatch lines go through it like any path)
-    and, only with --occlude (after the pens have been worked out, before the dedup; it needs source_fn and, with hatching, hatch_groups_fn):
-      occlude_fn(paths, off, pts, level int32 [n], ring_sub, ring_level, map, clamp) -> (off, pts, origin int32, stats)   orip_svg_occlude
-    the rings are the fitted paths ring_sub with their levels, clamp = not --clip; info["occlude"] = the ten counts of include/orip.h.
-    and, only with --dashes on a drawing that states a dash array (after the pens have been worked out, before the occlusion; it needs source_fn):
-      dash_fn                                      as in orip.gcode.build_stream_from_gcode; the patterns are dash_patterns()'s
-    info["dash"] = the eight counts of include/orip.h and "ignored", the dash arrays that left their stroke solid (where no stroke is dashed, "ignored" alone, if any).
-    and, only with --hatch-connect (after the pens and the dashes, before the occlusion; it needs source_fn, hatch_groups_fn and the points of fetch_fn):
-      hatch_link_fn(paths, off, pts, cls int32 [n], ring_sub, ring_group, map, clamp, reach) -> (off, pts, member_off, member, stats)   orip_svg_hatch_link
-    the rings are the fitted paths ring_sub with their fill groups, clamp = not --clip; info["hatch_link"] = the eight counts of include/orip.h and "reach".
-    and, only with --stipple-mm (after the simplification, immediately before the order; with --pen-colors the dots take hatch_pens' pen of their shape):
-      stipple_fn(paths, ring_sub, ring_group, map, clamp, lattice, inset, rect, flags) -> (xy int32 [dots, 2], group int32 [dots], stats)   orip_svg_stipple
-    the rings are the fitted paths ring_sub with their fill groups, clamp = not --clip, rect = the sheet or the clip rectangle; info["stipple"] = the seven
-    counts of include/orip.h with the lattice, info["taps"] = the dots drawn.
-    and, only with --loop-start:
-      seam_fn                                      as in orip.gcode.build_stream_from_gcode (a circle, a <rect> and a closed <path> are closed strokes; hatch lines are open)
-    and, only with --ring-entry (in the place of order_fn / order_pens_fn):
-      ring_entry_fn                                as in orip.gcode.build_stream_from_gcode (the dots of --stipple-mm are open strokes of one point)
+    and the steps of the stroke driver, whose signatures and places orip.gcode.PASSES states once; steps_fn, clip_fn, hatch_link_fn, occlude_fn and stipple_fn
+    take the fitted paths, where they are, in front of the arguments stated there (steps_fn and clip_fn in the place of off, pts_mm):
+      steps_fn, order_fn, codes_fn, pack_fn        always
+      hatch_groups_fn(paths, segments) -> int32 [segments]   orip_svg_hatch_groups_fetch  (the fill group of every hatch line), source_fn, order_pens_fn
+                                                   only with --pen-colors or --allow-reverse
+      merge_fn          only with --merge-paths (hatch lines go through it like any path; serpentine lines do not touch)
+      improve_fn        only with --improve-order
+      clip_fn           only with --clip, in the place of steps_fn (hatch lines are cut like any path, and their pens still come through the sources)
+      simplify_fn       only with --simplify-mm (a hatch line has two points and passes through untouched)
+      dedup_fn          only with --dedup (hatch lines go through it like any path)
+      occlude_fn        only with --occlude; it needs source_fn and, with hatching, hatch_groups_fn.  The rings are the fitted paths ring_sub with their
+                        levels, clamp = not --clip; info["occlude"] = the ten counts of include/orip.h.
+      dash_fn           only with --dashes on a drawing that states a dash array; it needs source_fn; the patterns are dash_patterns()'s.  info["dash"] =
+                        the eight counts of include/orip.h and "ignored", the dash arrays that left their stroke solid (where no stroke is dashed,
+                        "ignored" alone, if any).
+      hatch_link_fn     only with --hatch-connect; it needs source_fn, hatch_groups_fn and the points of fetch_fn.  The rings are the fitted paths ring_sub
+                        with their fill groups, clamp = not --clip; info["hatch_link"] = the eight counts of include/orip.h and "reach".
+      stipple_fn        only with --stipple-mm (with --pen-colors the dots take hatch_pens' pen of their shape).  The rings as hatch_link_fn's, rect = the
+                        sheet or the clip rectangle; info["stipple"] = the seven counts of include/orip.h with the lattice, info["taps"] = the dots drawn.
+      seam_fn           only with --loop-start (a circle, a <rect> and a closed <path> are closed strokes; hatch lines are open)
+      ring_entry_fn     only with --ring-entry (the dots of --stipple-mm are open strokes of one point)
     With --pen-colors, info["path_pens"] is the pen of every fitted path (hatch lines included, --color-index where no stroke is stated).
     Returns (bytes, info)."""
     import time
@@ -1107,16 +1096,9 @@ def build_stream_from_svg(text: Union[str, bytes, SegmentTable], opts: Optional[
             info["fitted_paths"] = (np.zeros(1, np.int64), np.zeros((0, 2)))
         return data, dict(ginfo, **info)
     pens_on = o.pen_colors is not None
-    given = clip_fn if o.clip else steps_fn                 # the stroke steps take (off, pts_mm, ...); here the conversion takes the fitted paths where they are
-    steps = GC.StrokeSteps(None if given is None else (lambda _off, _pts, m, *rect: given(paths, m, *rect)), source_fn, merge_fn, simplify_fn, order_fn, order_pens_fn,
-                           improve_fn, codes_fn, pack_fn, dedup_fn)
     own = any(f is None for f in (flatten_fn, bbox_fn, fit_fn, fetch_fn)) or (hp and hatch_fn is None) or ((pens_on or o.occlude or reach is not None) and hp and hatch_groups_fn is None)
-    occ = None
-    if o.occlude:                                           # the rings and their levels are known now; the strokes' levels once the hatch lines are there
-        ring_sub, ring_level = occlusion_rings(table)
-        occ = GC.Occlude(None if occlude_fn is None else (lambda off, pts, level, rs, rl, m, clamp: occlude_fn(paths, off, pts, level, rs, rl, m, clamp)),
-                         np.zeros(0, np.int64), ring_sub, ring_level, not o.clip)
-    if own:                                                 # steps of this door's own; the stroke steps are resolved below, once the fit says whether a dash pass runs
+    rings = occlusion_rings(table) if o.occlude else None   # the rings and their levels are known now; the strokes' levels once the hatch lines are there
+    if own:                                                 # steps of this door's own; the stroke steps are resolved by the stroke driver, once the fit says whether a dash pass runs
         if device is None:
             from .stages import device as _default_device
             device = _default_device()
@@ -1136,29 +1118,31 @@ def build_stream_from_svg(text: Union[str, bytes, SegmentTable], opts: Optional[
     if want_paths:
         info["fitted_paths"] = (off_mm, np.asarray(pts_mm, np.float64).reshape(-1, 2))
     tm["fetch_paths"] = tm.get("fetch_paths", 0.0) + (time.perf_counter() - t0)
-    if occ is not None:
-        occ.path_level = path_levels(table, paths, info, hatch_groups_fn)
+
+    def on_paths(fn, skip=0):
+        """a step of this door in the stroke driver's form: the fitted paths, where they are, in front of its arguments (skip: the leading arguments of the
+        driver's form that this door's has not -- off, pts_mm of the conversion)"""
+        return None if fn is None else lambda *a: fn(paths, *a[skip:])
+    occ = GC.Occlude(path_levels(table, paths, info, hatch_groups_fn), *rings, not o.clip) if o.occlude else None
     dsh, ignored = None, 0
-    if o.dashes and table.dash_array is not None:           # the fit is known now, and with it whether any stroke is dashed: the residency chain needs to know
+    if o.dashes and table.dash_array is not None:           # the fit is known now, and with it whether any stroke is dashed: the residency rule needs to know
         pattern, phase, pat_off, pat_val, ignored = dash_patterns(table, info["scale"], o.steps_per_mm, len(off_mm) - 1)
         if (pattern >= 0).any():                            # no usable dash array: no pass, no device call
-            dsh = GC.Dash(dash_fn, pattern, phase, pat_off, pat_val)
+            dsh = GC.Dash(pattern, phase, pat_off, pat_val)
     lnk = None
     if reach is not None:
-        lnk = GC.HatchLink(None if hatch_link_fn is None else (lambda off, pts, cls, rs, rg, m, clamp, r: hatch_link_fn(paths, off, pts, cls, rs, rg, m, clamp, r)),
-                           hatch_classes(table, paths, info, hatch_groups_fn, off_mm, pts_mm, hp.get("u")), *hatch_link_rings(table), not o.clip, reach)
-    sm = GC.Seam(seam_fn) if o.loop_start else None
-    rge = GC.RingEntry(ring_entry_fn) if o.ring_entry else None
+        lnk = GC.HatchLink(hatch_classes(table, paths, info, hatch_groups_fn, off_mm, pts_mm, hp.get("u")), *hatch_link_rings(table), not o.clip, reach)
     stp = None
     if sp is not None:
         W, H = GC.target_size(go)
-        stp = GC.Stipple(None if stipple_fn is None else (lambda rs, rg, m, clamp, lat, inset, rect, flags: stipple_fn(paths, rs, rg, m, clamp, lat, inset, rect, flags)),
-                         *hatch_link_rings(table), not o.clip, sp["lattice"], sp["inset"], GC.clip_rect(go) or (0, 0, W - 1, H - 1),
+        stp = GC.Stipple(*hatch_link_rings(table), not o.clip, sp["lattice"], sp["inset"], GC.clip_rect(go) or (0, 0, W - 1, H - 1),
                          (0 if o.no_serpentine else GC.STIPPLE_SERPENTINE) | (GC.STIPPLE_OCCLUDE if o.occlude else 0),
                          (lambda groups: hatch_pens(table, groups, info["pen_colors"])) if pens_on else None)
-    steps, device = GC.resolve_steps(steps, go, pens_on or o.allow_reverse, device, force=bool(own), occlude=occ, dash=dsh, seam=sm, hatch_link=lnk, stipple=stp, ring_entry=rge,
-                                     convert=lambda dev: lambda _off, _pts, m, *rect: (_Resident(dev).clip if rect else _Resident(dev).steps)(paths, m, *rect))
-    data, ginfo = GC.stroke_stream((off_mm, np.zeros((int(off_mm[-1]), 2))), go, device, steps, tm, pens, occ, dsh, seam=sm, hatch_link=lnk, stipple=stp, ring_entry=rge)
+    fn = dict(convert=on_paths(clip_fn if o.clip else steps_fn, 2), hatch_link=on_paths(hatch_link_fn), occlude=on_paths(occlude_fn), stipple=on_paths(stipple_fn),
+              dash=dash_fn, dedup=dedup_fn, merge=merge_fn, simplify=simplify_fn, order=order_fn, order_pens=order_pens_fn, ring_entry=ring_entry_fn, improve=improve_fn,
+              seam=seam_fn, source=source_fn, codes=codes_fn, pack=pack_fn)
+    data, ginfo = GC.stroke_stream((off_mm, np.zeros((int(off_mm[-1]), 2))), go, device, GC.StrokeSteps(fn, dsh, lnk, occ, stp), tm, pens, force=bool(own),
+                                   convert=lambda dev: on_paths(_Resident(dev).clip if o.clip else _Resident(dev).steps, 2))
     if "dash" in ginfo or ignored:                          # an ignored dash array is reported whether or not a pass ran: the stroke is solid, and the line says so
         ginfo["dash"] = dict(ginfo.get("dash", {}), ignored=ignored)
     return data, dict(ginfo, **info)

@@ -285,8 +285,10 @@ def test_options_parse_on_both_tools_and_the_pinned_records_stand():
     assert svg_options(["--dashes"]).dashes is True and svg_options([]).dashes is False
     assert not hasattr(SV.build_gcode_argparser().parse_args(["in.svg"]), "dashes")                     # svg2gcode.py writes G-code: the pass lives in the stream
     assert SV.gcode_options(svg_options(["--dashes"])).dash_mm is None                                  # the SVG door brings its own record
-    assert GC.STROKE_ARGS[-1] == "--dedup" and GC.StrokeSteps._fields[-1] == "dedup" and len(GC.StrokeSteps._fields) == 10 and len(GC.STROKE_ARGS) == 10
-    assert GC.StrokeSteps._fields == ("convert", "source", "merge", "simplify", "order", "order_pens", "improve", "codes", "pack", "dedup")
+    import recording_device as RD
+    gcode_steps, svg_steps = RD.doors_take_the_pass_table()
+    assert GC.STROKE_ARGS[-1] == "--dedup" and len(GC.STROKE_ARGS) == 10 and "dash_fn" in gcode_steps and "dash_fn" in svg_steps
+    assert [p.name for p in GC.PASSES].index("dash") == [p.name for p in GC.PASSES].index("convert") + 1
     assert "--dash-mm" not in GC.STROKE_ARGS and GC.DASH_STATS == DD.DASH_STATS
 
 

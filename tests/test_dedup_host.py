@@ -112,7 +112,9 @@ def test_option_parses_on_both_tools():
     o = SV.options_from_args(SV.build_stream_argparser().parse_args(["in.svg", "--dedup"]))
     assert o.dedup is True and SV.gcode_options(o).dedup is True and SV.gcode_options(SV.SvgOptions()).dedup is False
     assert not hasattr(SV.build_gcode_argparser().parse_args(["in.svg"]), "dedup")           # svg2gcode.py writes G-code: the pass lives in the stream
-    assert GC.STROKE_ARGS[-1] == "--dedup" and GC.StrokeSteps._fields[-1] == "dedup" and GC.StrokeSteps(1, 2, 3, 4, 5, 6, 7, 8, 9).dedup is None
+    import recording_device as RD
+    gcode_steps, svg_steps = RD.doors_take_the_pass_table()
+    assert GC.STROKE_ARGS[-1] == "--dedup" and "dedup_fn" in gcode_steps and "dedup_fn" in svg_steps and GC.StrokeSteps({}).fn.get("dedup") is None
 
 
 # ------------------------------------------------------------------ the host flow through the doubles

@@ -85,6 +85,24 @@ def test_the_two_doors_take_turns_on_one_device(dev):
 
 
 @pytest.mark.parametrize("door", ["svg", "gcode"])
+def test_given_and_own_passes_mixed(dev, door):
+    """a given pass in front of one of the device's own: the device is sent the strokes where the host alone holds them and reads its resident list where
+    the pass before was its own (tests/test_stroke_residency_host.py holds the forms; here the device's kernels take them).  The all-on row under every
+    assignment of recording_device.assignments, five further rows under the two that alternate"""
+    import recording_device as RD
+    rows, text, bad = CC.rows(door), CC.SVG_TEXT if door == "svg" else CC.GCODE_TEXT, []
+    for i in (1, 2, 3, 4, 5, 6):
+        row, o = rows[i], CC.options(door, rows[i])
+        exp, winfo = want(door, row)
+        for given in RD.assignments(RD.factors_on(door, row))[slice(None) if i == 1 else slice(1, 3)]:
+            got, info = RD.run_mixed(door, o, text, given, dev, door == "svg" and o.hatch_angle_deg is not None and o.hatch_spacing_mm is not None)
+            msg = CC.mismatch(door, row, got, info, exp, winfo)
+            if msg:
+                bad.append("given: " + " ".join(n for n in given if given[n]) + "\n" + msg)
+    assert not bad, "\n".join(bad)
+
+
+@pytest.mark.parametrize("door", ["svg", "gcode"])
 def test_all_on_row_on_a_device_of_its_own(door):
     """nothing can be carried over here: a failure is the row's own"""
     from orip.device import Device

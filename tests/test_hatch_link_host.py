@@ -125,7 +125,9 @@ def test_the_options():
         with pytest.raises(ValueError, match="hatch-connect"):
             SV.build_stream_from_svg(LC.TOOL_SVG, svg_options(bad), **doubles(LC.HatchLinkDouble()))
     assert "--hatch-connect" in SV.build_stream_argparser().format_help() and "--hatch-connect" not in SV.build_gcode_argparser().format_help()
-    assert "--hatch-connect" not in GC.build_argparser().format_help() and "hatch_link" not in GC.StrokeSteps._fields
+    import recording_device as RD
+    gcode_steps, svg_steps = RD.doors_take_the_pass_table()
+    assert "--hatch-connect" not in GC.build_argparser().format_help() and "hatch_link_fn" not in gcode_steps and "hatch_link_fn" in svg_steps
 
 
 def test_without_the_option_nothing_changes_and_the_step_is_never_called():

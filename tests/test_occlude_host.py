@@ -181,7 +181,9 @@ def test_the_parser_records_the_element_of_every_subpath():
         SV.occlusion_rings(old)
     assert "--occlude" not in SV.build_gcode_argparser().format_help() and "--occlude" in SV.build_stream_argparser().format_help()
     from orip import gcode as GC
-    assert "--occlude" not in GC.STROKE_ARGS and "occlude" not in GC.StrokeSteps._fields
+    import recording_device as RD
+    gcode_steps, svg_steps = RD.doors_take_the_pass_table()
+    assert "--occlude" not in GC.STROKE_ARGS and "occlude_fn" not in gcode_steps and "occlude_fn" in svg_steps
 
 
 def test_without_the_option_nothing_changes_and_the_step_is_never_called():

@@ -102,7 +102,9 @@ def test_options_parse_and_no_reorder_is_an_argument_error():
         SV.build_stream_from_svg(SC.TOOL_SVG, svg_options(["--ring-entry", "--no-reorder"]), ring_entry_fn=never, **SVD.svg_doubles())
     from orip import lib
     assert GC.RING_ENTRY_STATS == lib.RING_ENTRY_STATS == RD.STAT_NAMES and "orip_gcode_order_rings" in lib.SIGNATURES
-    assert "ring_entry" not in GC.StrokeSteps._fields and "--ring-entry" not in GC.STROKE_ARGS
+    import recording_device as REC
+    gcode_steps, svg_steps = REC.doors_take_the_pass_table()
+    assert "ring_entry_fn" in gcode_steps and "ring_entry_fn" in svg_steps and "--ring-entry" not in GC.STROKE_ARGS
 
 
 # ------------------------------------------------------------------ the host flow through the doubles

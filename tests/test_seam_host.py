@@ -147,7 +147,9 @@ def test_options_parse_on_both_tools():
 
 def test_pinned_records_stand():
     from orip import svg as SV, gcode as GC
-    assert GC.StrokeSteps._fields == ("convert", "source", "merge", "simplify", "order", "order_pens", "improve", "codes", "pack", "dedup")
+    import recording_device as RD
+    gcode_steps, svg_steps = RD.doors_take_the_pass_table()
+    assert "seam_fn" in gcode_steps and "seam_fn" in svg_steps and GC.PASSES[-1].name == "seam"
     assert len(GC.STROKE_ARGS) == 10 and GC.STROKE_ARGS[-1] == "--dedup" and "--loop-start" not in GC.STROKE_ARGS
     g = list(GC.GcodeOptions.__dataclass_fields__)
     assert g[-2:] == ["dash_mm", "dash_offset_mm"] and g[-3] == "loop_start"

@@ -33,12 +33,12 @@ def comb(teeth=40):
     return pts
 
 
-def many_squares(count=300, seed=5):
+def many_squares(count=300, seed=5, per_row=20):
     """small squares side by side, 10 .. 90 wide: some narrower than the pitch, some between two rows, so that groups without a dot stand among the others"""
     rng = np.random.default_rng(seed)
     rings = []
     for k in range(count):
-        x, y, w, h = 100 + 110 * (k % 20), 100 + 110 * (k // 20), int(rng.integers(10, 91)), int(rng.integers(10, 91))
+        x, y, w, h = 100 + 110 * (k % per_row), 100 + 110 * (k // per_row), int(rng.integers(10, 91)), int(rng.integers(10, 91))
         rings.append(rect_ring(x, y, x + w, y + h))
     return rings
 

@@ -592,8 +592,10 @@ int orip_gcode_stipple_fetch(orip_ctx* ctx, int32_t* xy /* [dots,2] */, int32_t*
  * more over the lines of both families (the ON bits of a call are kept whole).  Found on the device, after the count, leaving no segment list: 2^26
  * segments or more.  None of these is a fault.
  * Declined: spacing that varies with the tone inside a layer; a morphological inset of the mask (the inset is along the line, as in the reference's
- * hatch_fill); anti-aliased or sub-pixel mask edges; linking the lines into zigzags (--hatch-connect does that for shapes with an outline, and a mask has
- * none); filling from `labels` instead of the opened and closed masks; a bound on the worst case (a checkerboard gives a run per sample). */
+ * hatch_fill); anti-aliased or sub-pixel mask edges; filling from `labels` instead of the opened and closed masks; a bound on the worst case (a
+ * checkerboard gives a run per sample).  Linking the lines into zigzags is not declined any more: it is a pass of its own, orip_fill_link below, which
+ * checks a link against the mask's ink where --hatch-connect checks it against a shape's outline.  For that pass the call also keeps, beside the segment
+ * list and invisible to every caller of this one, the line (family, k) of every segment. */
 #define ORIP_FILL_SERPENTINE 1
 #define ORIP_FILL_ALONG 2
 #define ORIP_FILL_ACROSS 4
@@ -605,6 +607,40 @@ int orip_fill_mask(orip_ctx* ctx, const uint8_t* mask /* [h,w] or NULL = residen
                    int32_t num, int32_t den, int32_t dx, int32_t dy, int32_t ux, int32_t uy, int32_t spacing, int32_t inset, int32_t min_len,
                    int32_t flags, int64_t* stats /* [6]: lines, samples, on, runs, short, segments */);
 int orip_fill_fetch(orip_ctx* ctx, int32_t* seg /* [segments,4]: x0 y0 x1 y1 */);
+/* fill connect (csrc/fill_link.hip; ours, the reference has no such pass): the hatch segments of a mask are drawn as zigzags, every link kept on the mask's
+ * INK, so that the pen is lifted once per chain and not once per segment.  Integers throughout: no floating point, no tolerance.
+ * Input.  The resident segment list of the last successful orip_fill_mask of this context, in its order: segment i runs from its START (x0, y0) to its END
+ *   (x1, y1) and lies on line (family f_i, k_i), which that call has kept.  INK, defined exactly as orip_fill_mask defines it, from THIS call's arguments:
+ *   mask (or NULL + layer: the resident mask), h, w and the placement (num, den, dx, dy), in the same ranges; the front door passes what it passed to the
+ *   fill.  reach in 1 .. 2^15 canvas pixels.
+ *   In reach.  A link runs from the END E of segment a to the START S of segment b.  With (dx, dy) = S - E the pair (a, b) is IN REACH iff f_a = f_b and
+ *   k_b = k_a + 1, max(|dx|, |dy|) <= reach and dx^2 + dy^2 <= reach^2.  A fill is only continued onto the next line of its own family: so a < b always, the
+ *   answer depends on no processing order and no cycle can form.
+ *   Eligible.  n = max(|dx|, |dy|) >= 1 (samples of different lines never coincide when spacing >= 2).  The link's PIXELS are t = 0 .. n: pixel t steps the
+ *   major coordinate (x iff |dx| >= |dy|) of E by t towards S, and its minor coordinate is E's plus floor((2 t dminor + n) / (2 n)): the nearest integer,
+ *   halves toward +infinity, as every sample of the fill is rounded.  The pair is ELIGIBLE iff all n + 1 pixels are INK.  Stated deviation, the same as for
+ *   the segments: between its pixels a drawn link can leave them by under one step.
+ *   Choice.  best(END a) = the eligible b with the least (d^2, b), d^2 = dx^2 + dy^2; best(START b) = the eligible a with the least (d^2, a); a -> b is a
+ *   LINK iff each is the other's best: the mutual rule of orip_gcode_hatch_link.
+ *   Output.  A chain a0 -> a1 -> ... becomes ONE stroke a0.start, a0.end, a1.start, a1.end, ...; the strokes leave in ascending order of their first member;
+ *   a segment without a link is a 2-point stroke at its place; nothing is ever reversed.  off int64 [paths_out + 1], pts int32 [points_out, 2].
+ * stats: segments, in_reach (pairs), eligible (pairs), links, paths_out, points_out, link_steps = the sum of max(|dx|, |dy|) over the links: the pen-down
+ *   steps the pass adds.  paths_out == segments - links and points_out == 2 segments always; every output segment is an input segment or a link, in order;
+ *   all members of a chain are of one family and on consecutive k; with a reach too small for any pair the list comes back as it was.  The pass is not
+ *   idempotent and does not claim to be (it reads the fill's list, never its own result).
+ * The call writes NO resident state of the raster chain, nothing of the stroke passes and nothing of the segment list: orip_fill_fetch returns the plain
+ * segments behind it.  The strokes wait in a list of their own for orip_fill_link_fetch until the next orip_fill_link or orip_fill_mask that passes its
+ * argument checks.
+ * Errors before any launch, with the segment list and an earlier link result left as they were: no successful fill to work on, the mask / placement argument
+ * checks of orip_fill_mask, reach out of range, NULL stats.  Found on the device, leaving no link result: 2^28 pairs in reach or more, counts that do not
+ * add up.  orip_fill_link_fetch without a link result is an error.  None of these is a fault.
+ * Declined: links between the two families of a cross hatch; links that skip a line; reversing a segment to link it; links that follow the mask's border;
+ * morphological clearance around a link; a bound on the worst case (a row of K short segments costs every END near it up to K tests). */
+#define ORIP_FILL_LINK_STATS 7
+#define ORIP_FILL_LINK_REACH_MAX (1 << 15)
+int orip_fill_link(orip_ctx* ctx, const uint8_t* mask /* [h,w] or NULL = resident mask of `layer` */, int layer, int h, int w, int32_t num, int32_t den,
+                   int32_t dx, int32_t dy, int32_t reach, int64_t* stats /* [7]: segments, in_reach, eligible, links, paths_out, points_out, link_steps */);
+int orip_fill_link_fetch(orip_ctx* ctx, int64_t* off /* [paths_out+1] */, int32_t* pts /* [points_out,2] */);
 /* --dashes / --dash-mm (csrc/gcode_dash.hip; ours, the reference has no such pass): a stroke with a dash pattern is drawn as its dashes.  All arithmetic is
  * integer on the step grid: nothing behind the conversion to steps is floating point.
  * Unit.  u = 1 / ORIP_DASH_UNIT = 1/256 step: every length below is in u.

@@ -24,8 +24,10 @@
 //
 // Scratch (orip_ctx.h states the three buffers).  c->fl_tmp, ONE Carve: mask u8[h w] (explicit form only); on u64[Z + 1]; cs u64[Z + 1]; sc u64[Z + 1];
 // FlCounters.  c->fl_runs, one Carve behind the first read-back, R runs: a0 int[R]; a1 int[R]; row int[R]; keep u64[R + 1]; kbase u64[R + 1].  Resident
-// until the next call: c->fl_out = seg int4[segments].
+// until the next call: c->fl_out = seg int4[segments]; c->fl_rows = segrow int[segments] (the row of every segment) and rfirst unsigned[rows + 1] (the first
+// segment of every row; k_fl_rowfirst), which only orip_fill_link (fill_link.hip) reads.
 #include "orip_ctx.h"
+#include "fill_common.h"
 #include <algorithm>
 #include <cmath>
 
@@ -36,19 +38,14 @@ constexpr u64 FL_MAX_BLOCKS = 1ull << 26, FL_MAX_SEGS = 1ull << 26;
 constexpr unsigned FL_BAD_PLACE = 1, FL_BAD_PAIR = 2;
 struct FlCounters { u64 lines, samples, on, nshort, segments; unsigned bad; };
 struct FlFam { int ux, uy, xmajor, A, B, NW; long long D, kmin, L, row0; u64 wbase; };   // row0: the family's first row
-struct FlGrid { FlFam fam[2]; int nf; const u8* M; int h, w; long long num, den, dx, dy; u64 Z; };
+struct FlGrid { FlFam fam[2]; int nf; FlInk ink; u64 Z; };
 
-__host__ __device__ __forceinline__ long long fl_floordiv(long long a, long long b) { const long long q = a / b; return (a % b != 0 && a < 0) ? q - 1 : q; }     // b > 0
 // the minor coordinate of line k at a; true when the sample exists
 __host__ __device__ __forceinline__ bool fl_sample(const FlFam& f, long long k, long long a, long long& b) {
     long long N = f.xmajor ? k * f.D + (long long)f.uy * a : (long long)f.ux * a - k * f.D, d = f.xmajor ? f.ux : f.uy;
     if (d < 0) { N = -N; d = -d; }
     b = fl_floordiv(2 * N + d, 2 * d);
     return b >= 0 && b < f.B;
-}
-__device__ __forceinline__ bool fl_ink(const FlGrid& g, long long X, long long Y) {
-    const long long c = fl_floordiv((X - g.dx) * g.den, g.num), r = fl_floordiv((Y - g.dy) * g.den, g.num);
-    return c >= 0 && c < g.w && r >= 0 && r < g.h && g.M[(size_t)r * (size_t)g.w + (size_t)c] != 0;
 }
 // block z: its family, its line's number in the family and its place in the row
 __device__ __forceinline__ const FlFam& fl_block(const FlGrid& g, u64 z, long long& li, int& j) {
@@ -73,7 +70,7 @@ __global__ __launch_bounds__(256) void k_fl_sample(FlGrid g, u64* __restrict__ o
         const long long k = f.kmin + li, a = (long long)j * 64 + lane;
         long long b = 0;
         const bool ex = a < f.A && fl_sample(f, k, a, b);
-        const bool ink = ex && (f.xmajor ? fl_ink(g, a, b) : fl_ink(g, b, a));
+        const bool ink = ex && (f.xmajor ? fl_ink(g.ink, a, b) : fl_ink(g.ink, b, a));
         const u64 me = __ballot(ex), mo = __ballot(ink);
         long long bp;
         const bool before = j > 0 && fl_sample(f, k, (long long)j * 64 - 1, bp);         // the sample in front of the block
@@ -132,7 +129,7 @@ __global__ __launch_bounds__(256) void k_fl_keep(u64 R, const int* __restrict__ 
 
 // ------------------------------------------------------------------------------------------------ 5. emit
 __global__ __launch_bounds__(256) void k_fl_emit(FlGrid g, u64 R, u64 S, const u64* __restrict__ sc, const int* __restrict__ a0, const int* __restrict__ a1, const int* __restrict__ row,
-                                                 const u64* __restrict__ keep, const u64* __restrict__ kbase, int im, int serpentine, int4* __restrict__ seg, FlCounters* cn) {
+                                                 const u64* __restrict__ keep, const u64* __restrict__ kbase, int im, int serpentine, int4* __restrict__ seg, int* __restrict__ segrow, FlCounters* cn) {
     const u64 r = (u64)blockIdx.x * 256 + threadIdx.x;
     if (r >= R || !keep[r]) return;
     const FlFam& f = g.fam[g.nf == 2 && row[r] >= g.fam[1].row0 ? 1 : 0];
@@ -147,6 +144,19 @@ __global__ __launch_bounds__(256) void k_fl_emit(FlGrid g, u64 R, u64 S, const u
     if (!fl_sample(f, k, s0, b0) || !fl_sample(f, k, s1, b1) || at >= S) { atomicOr(&cn->bad, FL_BAD_PLACE); return; }
     const int4 fw = f.xmajor ? make_int4((int)s0, (int)b0, (int)s1, (int)b1) : make_int4((int)b0, (int)s0, (int)b1, (int)s1);
     seg[at] = back ? make_int4(fw.z, fw.w, fw.x, fw.y) : fw;
+    segrow[at] = row[r];
+}
+// what orip_fill_link needs of the rows: the first segment of every row, rfirst[rows] = S.  Row q's runs start at sc[its first block] >> 32 and its segments at
+// kbase of that run, whichever way the row is drawn: serpentine only reverses inside a row
+__global__ __launch_bounds__(256) void k_fl_rowfirst(FlGrid g, long long rows, u64 R, u64 S, const u64* __restrict__ sc, const u64* __restrict__ kbase, unsigned* __restrict__ rfirst,
+                                                     FlCounters* cn) {
+    const long long q = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (q > rows) return;
+    u64 z0 = g.Z;
+    if (q < rows) { const FlFam& f = g.fam[g.nf == 2 && q >= g.fam[1].row0 ? 1 : 0]; z0 = f.wbase + (u64)(q - f.row0) * (u64)f.NW; }
+    const u64 r0 = sc[z0] >> 32;
+    if (r0 > R || kbase[r0] > S) { atomicOr(&cn->bad, FL_BAD_PLACE); rfirst[q] = (unsigned)S; return; }
+    rfirst[q] = (unsigned)kbase[r0];
 }
 
 long long fl_rs(u64 v) {                                                                  // the nearest integer to sqrt(v), v < 2^60
@@ -182,7 +192,7 @@ extern "C" int orip_fill_mask(orip_ctx* c, const uint8_t* mask, int layer, int h
     const long long U2 = (long long)ux * ux + (long long)uy * uy, Rr = fl_rs((u64)U2), D = fl_rs((u64)spacing * (u64)spacing * (u64)U2), m = std::max(std::abs(ux), std::abs(uy));
     const int im = (int)((2ll * inset * m + Rr) / (2 * Rr)), lm = (int)std::max(1ll, (2ll * min_len * m + Rr) / (2 * Rr));
     FlGrid g{};
-    g.h = h; g.w = w; g.num = num; g.den = den; g.dx = dx; g.dy = dy;
+    g.ink = FlInk{nullptr, h, w, num, den, dx, dy};
     long long rows = 0;
     for (int pass = 0; pass < 2; pass++) {
         if (!(flags & (pass ? ORIP_FILL_ACROSS : ORIP_FILL_ALONG))) continue;
@@ -201,6 +211,7 @@ extern "C" int orip_fill_mask(orip_ctx* c, const uint8_t* mask, int layer, int h
     if (g.Z >= FL_MAX_BLOCKS) ORIP_FAIL(c, "%llu blocks of 64 samples over %lld lines: fewer than 2^26", g.Z, rows);
 
     for (int k = 0; k < ORIP_FILL_STATS; k++) stats[k] = 0;
+    c->fk_paths = -1;                                                         // a link result belongs to the list this call replaces
     if (g.Z == 0) { c->fl_segs = 0; return 0; }                                  // nothing to launch: the list of no segments
     c->fl_segs = -1;                                                          // no segment list from here to the last read-back
     hipStream_t s = LN(c).stream;
@@ -208,7 +219,7 @@ extern "C" int orip_fill_mask(orip_ctx* c, const uint8_t* mask, int layer, int h
     u8* d_mask; u64 *on, *cs, *sc; FlCounters* cn;
     { Carve L; L.take(d_mask, mask ? (size_t)h * w : 0); L.take(on, Z + 1); L.take(cs, Z + 1); L.take(sc, Z + 1); L.take(cn, 1); HIPC(c, L.commit(c->fl_tmp, 64)); }
     if (mask) HIPC(c, hipMemcpyAsync(d_mask, mask, (size_t)h * w, hipMemcpyHostToDevice, s));
-    g.M = mask ? d_mask : c->masks.as<u8>() + (size_t)h * w * (size_t)layer;
+    g.ink.M = mask ? d_mask : c->masks.as<u8>() + (size_t)h * w * (size_t)layer;
     HIPC(c, hipMemsetAsync(cn, 0, sizeof(FlCounters), s));
     const dim3 b(256), gw((unsigned)std::min<u64>((g.Z + 3) / 4, FL_BLOCKS));
     { ProfScope ps(c, "fl_sample");
@@ -236,16 +247,20 @@ extern "C" int orip_fill_mask(orip_ctx* c, const uint8_t* mask, int layer, int h
         HIPC(c, hipMemcpyAsync(&S, kbase + R, 8, hipMemcpyDeviceToHost, s));          // second read-back: the segments
         HIPC(c, hipStreamSynchronize(s));
         if (S >= FL_MAX_SEGS) ORIP_FAIL(c, "%llu segments: fewer than 2^26", S);
-        int4* seg;
+        int4* seg; int* segrow; unsigned* rfirst;
         { Carve L; L.take(seg, (size_t)S); HIPC(c, L.commit(c->fl_out, 64)); }
+        { Carve L; L.take(segrow, (size_t)S); L.take(rfirst, (size_t)rows + 1); HIPC(c, L.commit(c->fl_rows, 64)); }
         if (S) { ProfScope ps(c, "fl_emit");
-          hipLaunchKernelGGL(k_fl_emit, dim3(cdiv((int64_t)R, 256)), b, 0, s, g, R, S, sc, a0, a1, row, keep, kbase, im, (flags & ORIP_FILL_SERPENTINE) ? 1 : 0, seg, cn); }
+          hipLaunchKernelGGL(k_fl_emit, dim3(cdiv((int64_t)R, 256)), b, 0, s, g, R, S, sc, a0, a1, row, keep, kbase, im, (flags & ORIP_FILL_SERPENTINE) ? 1 : 0, seg, segrow, cn);
+          hipLaunchKernelGGL(k_fl_rowfirst, dim3(cdiv(rows + 1, 256)), b, 0, s, g, rows, R, S, sc, kbase, rfirst, cn); }
         HIPC(c, hipGetLastError());
         HIPC(c, hipMemcpyAsync(&hc, cn, sizeof(FlCounters), hipMemcpyDeviceToHost, s));      // third read-back: the counters
         HIPC(c, hipStreamSynchronize(s));
     }
     if (hc.bad || hc.segments != S || hc.nshort + hc.segments != R) ORIP_FAIL(c, "the segments do not add up (internal error %u)", hc.bad);
     c->fl_segs = (int64_t)S;
+    c->fl_nrows = rows; c->fl_row1 = g.nf == 2 ? g.fam[1].row0 : rows;
+    for (int k = 0; k < 2; k++) c->fl_xmajor[k] = g.fam[k].xmajor;
     stats[0] = (int64_t)hc.lines; stats[1] = (int64_t)hc.samples; stats[2] = (int64_t)hc.on; stats[3] = (int64_t)R; stats[4] = (int64_t)hc.nshort; stats[5] = (int64_t)hc.segments;
     return 0;
 }

@@ -439,6 +439,16 @@ struct orip_ctx {
     // keep u64[R + 1], kbase u64[R + 1] = its scan (the unit states both layouts), free between calls; fl_out = THE SEGMENT LIST, int4[fl_segs] = x0 y0 x1 y1
     // of the last call (-1: none) until the next one that passes its argument checks
     DBuf fl_tmp, fl_runs, fl_out; int64_t fl_segs = -1;
+    // what the fill keeps for orip_fill_link (fill_link.hip), valid while fl_segs > 0: fl_rows = segrow int[fl_segs] = the row of every segment (a row is a line
+    // of either family, the rows of the first family first) and rfirst unsigned[fl_nrows + 1] = the first segment of every row, rfirst[fl_nrows] = fl_segs;
+    // fl_row1 = the first row of the second family (fl_nrows with one family): row q + 1 is "the next line" of row q unless it is fl_row1; fl_xmajor = the major
+    // axis of either family.  The link pass, S = fl_segs, P pairs in reach: fk_tmp = mask u8[h w] (only of an explicit mask), cnt u64[S + 1] = pairs per END
+    // and base u64[S + 1] = its scan, best u64[2 S] = least (d^2 << 32 | partner) per END and per START, link int[2 S] = next, prev, head int[2][S] = the two
+    // arrays of the pointer jumping, len int[S] = members of the chain, at its head, cs u64[S + 1] = (points << 32 | 1) at a head and sc u64[S + 1] = its scan,
+    // FkCounters; fk_pair = pairs uint2[P] (the unit states both layouts), free between calls; fk_out = THE LINK RESULT, off int64[fk_paths + 1], pts
+    // int2[2 fk_segs] of the last orip_fill_link (fk_paths -1: none) until the next one that passes its argument checks or the next orip_fill_mask that does
+    DBuf fl_rows; int64_t fl_nrows = 0, fl_row1 = 0; int fl_xmajor[2] = {0, 0};
+    DBuf fk_tmp, fk_pair, fk_out; int64_t fk_paths = -1, fk_segs = 0;
     // svg2stream (svg.hip): scratch of the flattening and of the box, the resident paths (off int64[sv_n + 1], pts double2[sv_total]; raw units after
     // orip_svg_flatten, page mm after orip_svg_fit) until the next flatten; orip_gcode_to_steps reads them when it is called without pointers
     DBuf sv_tmp, sv_tmp2, sv_off, sv_pts; int64_t sv_n = 0, sv_total = 0; bool sv_ready = false, sv_box_ok = false; double sv_box[4] = {0, 0, 0, 0};

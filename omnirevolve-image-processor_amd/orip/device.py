@@ -796,6 +796,30 @@ class Device:
         self._ck(self.L.orip_fill_fetch(self.h, _p(seg)))
         return seg[:d["segments"]], d
 
+    def fill_link(self, mask, place, reach: int, layer: int = 0):
+        """fill connect (include/orip.h: orip_fill_link): the segments of the last fill_mask of this device drawn as zigzags, a link from the end of a
+        segment to the start of one on the next line of its family, at most `reach` pixels long, every pixel of it ink of the mask u8 [h, w] (None: the
+        resident mask of `layer`) placed by place = (num, den, dx, dy): what the fill was given.  The segment list stays as it is.
+        -> (off int64 [paths_out + 1], pts int32 [points_out, 2] in canvas pixels, in drawing order, {lib.FILL_LINK_STATS})"""
+        m = None
+        if mask is not None:
+            m = np.ascontiguousarray(mask, np.uint8)
+            if m.ndim != 2:
+                raise ValueError(f"mask of shape {m.shape}: [h, w]")
+        h, w = (self.H, self.W) if m is None else m.shape
+        scal = [int(v) for v in (layer, h, w, *place, reach)]
+        if len(scal) != 8:
+            raise ValueError("place = (num, den, dx, dy)")
+        if any(abs(v) >= 1 << 31 for v in scal):
+            raise OripError(f"orip_fill_link: an argument does not fit 32 bits: {scal}")
+        st = np.zeros(len(_l.FILL_LINK_STATS), np.int64)
+        self._ck(self.L.orip_fill_link(self.h, None if m is None else _p(m), *scal, _p(st)))
+        d = {k: int(v) for k, v in zip(_l.FILL_LINK_STATS, st)}
+        off = np.zeros(d["paths_out"] + 1, np.int64)
+        pts = np.zeros((max(d["points_out"], 1), 2), np.int32)
+        self._ck(self.L.orip_fill_link_fetch(self.h, _p(off), _p(pts)))
+        return off, pts[:d["points_out"]], d
+
     def gcode_dash(self, off, pts, pattern, phase, pat_off, pat_val, n: int | None = None):
         """--dashes / --dash-mm (include/orip.h: orip_gcode_dash): of the step polylines (off int64 [n + 1], pts int32 [total, 2]; both None = the n resident
         ones) every stroke with pattern[k] >= 0 is cut into the dashes of that pattern of the table (pat_off int32 [np + 1], pat_val int64, in 1/256 step),

@@ -87,6 +87,7 @@ SIGNATURES = {
     "orip_gcode_stipple": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _i32, _vp]), "orip_gcode_stipple_fetch": (_i32, [_vp, _vp, _vp]),
     "orip_svg_stipple": (_i32, [_vp, _vp, _vp, _i64, _P(GcodeMap), _i32, _i32, _i32, _i32, _vp, _i32, _vp]),
     "orip_fill_mask": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]), "orip_fill_fetch": (_i32, [_vp, _vp]),
+    "orip_fill_link": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]), "orip_fill_link_fetch": (_i32, [_vp, _vp, _vp]),
     "orip_gcode_dash": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp]), "orip_gcode_dash_fetch": (_i32, [_vp, _vp]),
     "orip_gcode_improve": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _i64, _vp, _vp, _vp]),
     "orip_gcode_seam": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
@@ -118,6 +119,8 @@ STIPPLE_SERPENTINE, STIPPLE_OCCLUDE, STIPPLE_CLAMP, STIPPLE_MAX = 1, 2, 4, 1 << 
 FILL_STATS = ("lines", "samples", "on", "runs", "short", "segments")
 FILL_SERPENTINE, FILL_ALONG, FILL_ACROSS = 1, 2, 4                                       # include/orip.h: the flags of orip_fill_mask
 FILL_COORD_MAX, FILL_U_MAX, FILL_LEN_MAX = 1 << 20, 4096, 1 << 15                          # the largest side and offset; direction component; spacing, inset and min_len in pixels
+FILL_LINK_STATS = ("segments", "in_reach", "eligible", "links", "paths_out", "points_out", "link_steps")
+FILL_LINK_REACH_MAX = 1 << 15                                                             # include/orip.h: the largest reach of orip_fill_link, in pixels
 DASH_STATS = ("paths_in", "dashed", "dashes", "collapsed", "paths_out", "points_out", "length_in", "length_on")
 DASH_UNIT, DASH_MAX_ENTRIES = 256, 64                        # include/orip.h: dash lengths are in 1/256 step; entries of one pattern at most
 IMPROVE_MAX_PATHS, IMPROVE_ROUNDS_AUTO = 65536, (1 << 63) - 1

@@ -6,6 +6,7 @@
     scale_vectors / sort_contours / dedup_layer / dedup_cross / plot_order         (05, 07, 08, 10, 12)
     run_path(bgr, cfg)                  -> ops per layer, everything resident on the GPU between stages
     fill_options(cfg) / fill_layer(mask, w, h, cfg, opts)    -> hatch ops of a colour mask                (fill_layers.py; ours)
+    fill_strokes(mask, w, h, cfg, opts)                      -> the same hatch as zigzags, links on ink   (fill_layers.py with connect; ours)
 
 Every function drives liborip.so through orip.device.Device; arrays cross the host boundary only where the
 reference's stage API puts a file.
@@ -293,6 +294,7 @@ def plot_order(lines: Sequence[np.ndarray], taps: Sequence[Tuple[int, int]], cfg
 FILL_DEFAULTS = {"spacing_mm": 1.0, "angle_deg": 45.0, "direction": "along", "inset_mm": 0.3, "min_run_mm": 0.5, "serpentine": True, "order": "serpentine"}
 FILL_DIRECTIONS = {"along": _l.FILL_ALONG, "across": _l.FILL_ACROSS, "cross": _l.FILL_ALONG | _l.FILL_ACROSS}
 FILL_ORDERS = ("serpentine", "nearest")
+FILL_CONNECT_KEYS = ("connect", "connect_mm")                                             # fill connect (include/orip.h: orip_fill_link); connect_mm defaults to twice the layer's spacing_mm
 
 
 def _fill_pixels(what: str, mm, ppm: int, lo: int) -> int:
@@ -308,7 +310,8 @@ def fill_options(cfg: Config):
     """the `fill` object of the config file (cfg._raw: Config has no such field) -> None without one, else {layer name: options} for the layers named under
     "layers", in color_names order.  Options: spacing, inset, min_len (pixels: int(round(mm * pixels_per_mm))), u (orip.svg.hatch_direction_vector of
     angle_deg, in the manifest's frame: x right, y down), flags (lib.FILL_*), order ("serpentine": as the device emits; "nearest": greedy from the end of
-    the outline), angle_deg.  An unknown key, a layer that is not in color_names or a value out of range raises ValueError naming it."""
+    the outline), angle_deg; and ONLY with "connect": true the key reach (pixels of connect_mm, default twice the layer's spacing_mm, 1 .. 2^15), which
+    makes fill_layers draw the layer's hatch as zigzags (fill_strokes).  An unknown key, a layer that is not in color_names or a value out of range raises ValueError naming it."""
     from .svg import hatch_direction_vector
     raw = (getattr(cfg, "_raw", None) or {}).get("fill")
     if raw is None:
@@ -316,7 +319,7 @@ def fill_options(cfg: Config):
     if not isinstance(raw, dict):
         raise ValueError("fill: must be an object")
     for k in raw:
-        if k != "layers" and k not in FILL_DEFAULTS:
+        if k != "layers" and k not in FILL_DEFAULTS and k not in FILL_CONNECT_KEYS:
             raise ValueError(f"fill: unknown key {k!r}")
     layers = raw.get("layers", {})
     if not isinstance(layers, dict):
@@ -333,7 +336,7 @@ def fill_options(cfg: Config):
         if not isinstance(own, dict):
             raise ValueError(f"fill: layers.{name} must be an object")
         for k in own:
-            if k not in FILL_DEFAULTS:
+            if k not in FILL_DEFAULTS and k not in FILL_CONNECT_KEYS:
                 raise ValueError(f"fill: unknown key {k!r} in layers.{name}")
         o = dict(FILL_DEFAULTS, **{k: v for k, v in raw.items() if k != "layers"})
         o.update(own)
@@ -350,6 +353,11 @@ def fill_options(cfg: Config):
                      "min_len": _fill_pixels("min_run_mm", o["min_run_mm"], ppm, 1), "u": u,
                      "flags": FILL_DIRECTIONS[o["direction"]] | (_l.FILL_SERPENTINE if o["serpentine"] else 0), "order": o["order"],
                      "angle_deg": math.degrees(math.atan2(u[1], u[0]))}
+        connect = o.get("connect", False)
+        if not isinstance(connect, bool):
+            raise ValueError(f"fill: connect must be true or false, not {connect!r}")
+        if connect:                                                                   # connect_mm is read only here
+            out[name]["reach"] = _fill_pixels("connect_mm", o["connect_mm"] if "connect_mm" in o else 2 * o["spacing_mm"], ppm, 1)
     return out
 
 
@@ -384,6 +392,39 @@ def fill_segments(mask, w_src: int, h_src: int, cfg: Config, opts: dict, dev: De
         seg = seg[np.asarray(order, np.int64)]
         seg = np.where(np.asarray(rev, bool)[:, None], seg[:, [2, 3, 0, 1]], seg)
     return np.ascontiguousarray(seg, np.int32), st
+
+
+def fill_strokes(mask, w_src: int, h_src: int, cfg: Config, opts: dict, dev: Device | None = None, layer: int = 0, start=None, fill_fn=None, link_fn=None, order_fn=None):
+    """the hatch of one layer as zigzags (include/orip.h: orip_fill_link) -> (polylines: a list of int32 [p, 2] in canvas pixels, in drawing order,
+    {lib.FILL_STATS}, {lib.FILL_LINK_STATS}).  As fill_segments, which it mirrors: opts is an entry of fill_options that carries `reach`; link_fn stands in
+    for Device.fill_link beside fill_fn / order_fn.  The link works on the segments as the device emitted them; order "nearest" then sends each stroke's
+    first and last point through the same gcode_order_pens call, and a reversed stroke has its points reversed."""
+    from .stream import to_steps
+    if mask is not None and tuple(np.asarray(mask).shape) != (int(h_src), int(w_src)):
+        raise ValueError(f"mask of shape {np.asarray(mask).shape} for a source of {w_src} x {h_src}")
+    W, H = canvas_size_px(cfg)
+    place = fill_placement(cfg, w_src, h_src)
+    if fill_fn is None or link_fn is None:
+        d = dev or device()
+        fill_fn = fill_fn or (lambda *a: d.fill_mask(*a, layer=layer))
+        link_fn = link_fn or (lambda *a: d.fill_link(*a, layer=layer))
+    _, st = fill_fn(mask, W, H, place, opts["u"], opts["spacing"], opts["inset"], opts["min_len"], opts["flags"])
+    off, pts, lst = link_fn(mask, place, opts["reach"])
+    off, pts = np.asarray(off, np.int64).reshape(-1), np.asarray(pts, np.int32).reshape(-1, 2)
+    strokes = [np.ascontiguousarray(pts[off[i]:off[i + 1]]) for i in range(len(off) - 1)]
+    if opts["order"] == "nearest" and strokes:
+        if order_fn is None:
+            order_fn = (dev or device()).gcode_order_pens
+        ends = np.concatenate([to_steps(pts[off[:-1]], W, H), to_steps(pts[off[1:] - 1], W, H)], 1).astype(np.int32)
+        s0 = (0, 0) if start is None else tuple(int(v) for v in to_steps(np.asarray(start, np.float64).reshape(1, 2), W, H)[0])
+        order, rev = order_fn(ends, np.zeros(len(strokes), np.int32), 1, reverse=True, start=s0)
+        strokes = [np.ascontiguousarray(strokes[int(i)][::-1]) if r else strokes[int(i)] for i, r in zip(order, rev)]
+    return strokes, st, lst
+
+
+def fill_stroke_ops(strokes) -> List[dict]:
+    """polylines as ops of stage 12's kind: {"type": "line", "points": float32 [p, 2]} in canvas pixels"""
+    return [{"type": "line", "points": np.asarray(p, np.float32).reshape(-1, 2).copy()} for p in strokes]
 
 
 def fill_ops(seg) -> List[dict]:

@@ -2,7 +2,8 @@
 # outline.  Runs between stages 12 and 13.  For every layer named under the config's fill.layers: <layer>/mask.png + the size of resized.png +
 # <layer>/ops.pkl (stage 12's file, read by layer name and never rewritten) -> <layer>/ops_filled.pkl = the outline ops, then the fill ops; the layer's
 # entry of vector_manifest.json then names ops_filled.pkl, and stages 13 and 14 follow the manifest.  The hatch itself runs on the GPU through liborip.so
-# (include/orip.h: orip_fill_mask states the rule); see orip.stages.fill_options for the config.  Without a `fill` object it writes nothing.
+# (include/orip.h: orip_fill_mask states the rule); see orip.stages.fill_options for the config.  Without a `fill` object it writes nothing.  A layer with
+# "connect": true has its hatch drawn as zigzags, the links kept on the mask's ink (orip_fill_link): its fill ops are polylines of 2 m points.
 import json
 import os
 import sys
@@ -12,7 +13,7 @@ import numpy as np
 import stage_io as _io
 from orip import stages as S
 from orip.config import load_config
-from orip.lib import FILL_STATS
+from orip.lib import FILL_LINK_STATS, FILL_STATS
 
 
 def outline_end(ops):
@@ -25,8 +26,8 @@ def outline_end(ops):
     return None
 
 
-def run(cfg, fill_fn=None, order_fn=None) -> int:
-    """fill_fn / order_fn stand in for the device calls (orip.stages.fill_segments); None: the GPU"""
+def run(cfg, fill_fn=None, order_fn=None, link_fn=None) -> int:
+    """fill_fn / order_fn / link_fn stand in for the device calls (orip.stages.fill_segments, fill_strokes); None: the GPU"""
     opts = S.fill_options(cfg)
     if opts is None:
         print("[fill] no fill object in the config: nothing written")
@@ -51,13 +52,20 @@ def run(cfg, fill_fn=None, order_fn=None) -> int:
         if mask.shape != (h, w):
             raise SystemExit(f"{name}/mask.png is {mask.shape[1]} x {mask.shape[0]}, resized.png {w} x {h}")
         ops = _io.load_pickle(p_ops)
-        seg, st = S.fill_segments(mask, w, h, cfg, o, start=outline_end(ops), fill_fn=fill_fn, order_fn=order_fn)
-        filled = list(ops) + S.fill_ops(seg)
+        lst = None
+        if "reach" in o:                                                              # connect: the hatch as zigzags (include/orip.h: orip_fill_link)
+            strokes, st, lst = S.fill_strokes(mask, w, h, cfg, o, start=outline_end(ops), fill_fn=fill_fn, link_fn=link_fn, order_fn=order_fn)
+            filled = list(ops) + S.fill_stroke_ops(strokes)
+        else:
+            seg, st = S.fill_segments(mask, w, h, cfg, o, start=outline_end(ops), fill_fn=fill_fn, order_fn=order_fn)
+            filled = list(ops) + S.fill_ops(seg)
         p_out = os.path.join(layer_dir, "ops_filled.pkl")
         _io.save_pickle(p_out, filled)
         entries[name]["file"] = os.path.relpath(p_out, out)
         entries[name]["count_ops"] = len(filled)
         print(f"[fill] {name}: angle={o['angle_deg']:.3f} order={o['order']} " + " ".join(f"{k}={st[k]}" for k in FILL_STATS))
+        if lst is not None:
+            print(f"[fill-link] {name}: reach={o['reach']} " + " ".join(f"{k}={lst[k]}" for k in FILL_LINK_STATS))
     with open(man_path, "w", encoding="utf-8") as f:
         json.dump(man, f, ensure_ascii=False, indent=2)
     print(f"[fill] manifest saved: {man_path}")

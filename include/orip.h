@@ -641,6 +641,44 @@ int orip_fill_fetch(orip_ctx* ctx, int32_t* seg /* [segments,4]: x0 y0 x1 y1 */)
 int orip_fill_link(orip_ctx* ctx, const uint8_t* mask /* [h,w] or NULL = resident mask of `layer` */, int layer, int h, int w, int32_t num, int32_t den,
                    int32_t dx, int32_t dy, int32_t reach, int64_t* stats /* [7]: segments, in_reach, eligible, links, paths_out, points_out, link_steps */);
 int orip_fill_link_fetch(orip_ctx* ctx, int64_t* off /* [paths_out+1] */, int32_t* pts /* [points_out,2] */);
+/* fill stipple (csrc/fill_stipple.hip; ours, the reference has no such pass): a colour mask of the raster pipeline is filled with DOTS, the plotter's taps,
+ * on ONE lattice for the whole canvas, and the density of the dots follows the darkness of the source image inside the mask through an ordered dither.  A
+ * second fill mode of fill_layers beside the hatch, whose spacing stays one per layer.  Integers throughout: no floating point, no tolerance.
+ * Input.  Mask M, u8 [h, w], nonzero = set (explicit, or mask == NULL: the resident mask of `layer`, exactly as orip_fill_mask takes it); tone G, u8 [h, w],
+ *   0 = black, always explicit, NULL meaning G = 0 everywhere (every set pixel fully dark: the plain stipple); the canvas W x H and the placement (num, den,
+ *   dx, dy) in the ranges of orip_fill_mask; the lattice (pitch, row, shift), pitch in 2 .. 2^15, row in 1 .. 2^15, 0 <= shift < pitch, in canvas pixels;
+ *   clear_rad and tone_rad in 0 .. ORIP_FILL_STIPPLE_RAD_MAX, in SOURCE pixels; lo, hi with 0 <= lo < hi <= 255; flags ORIP_FILL_STIPPLE_SERPENTINE or 0.
+ *   Candidates.  Lattice point (i, j) is X = i pitch + (shift if j & 1 else 0), Y = j row: the lattice of orip_svg_stipple, one for the whole canvas, so
+ *   neighbouring layers line up.  The CANDIDATES are the points with 0 <= X < W and 0 <= Y < H, so i, j >= 0.  A candidate's source pixel is (c, r) =
+ *   (floor((X - dx) den / num), floor((Y - dy) den / num)), and the candidate is INK iff canvas pixel (X, Y) is INK as orip_fill_mask defines it.
+ *   Near.  An ink candidate is CLEAR iff every source pixel (c', r') with |c' - c| <= clear_rad and |r' - r| <= clear_rad lies inside the image and is set;
+ *   the outside of the image is not set.  Otherwise it is counted in `near`.  Stated deviation: a square (Chebyshev) clearance in source pixels, not a
+ *   Euclidean inset: the morphological inset that the hatch declines and that dots need.
+ *   Tone.  The window |c' - c| <= tone_rad, |r' - r| <= tone_rad CLIPPED to the image; over its SET pixels only, C is their number and S the sum of G
+ *   (C >= 1: the centre is set).  Pixels of other layers never enter, so a neighbour's tone does not bleed in.  With R = hi - lo,
+ *   E = min(max(255 C - S - lo C, 0), R C): the window's mean darkness above lo, capped at hi, times C.
+ *   Threshold.  x = i & 7, y = j & 7, v = x ^ y, T = ((v&1)<<5) | ((y&1)<<4) | ((v&2)<<2) | ((y&2)<<1) | ((v&4)>>1) | ((y&4)>>2): the 8 x 8 Bayer matrix, a
+ *   permutation of 0 .. 63 whose row y = 0 is 0 32 8 40 2 34 10 42.  A clear candidate is a DOT iff 64 E > T R C; otherwise it is counted in `light`.  Every
+ *   product fits 32 bits (C <= 65^2).
+ *   Order.  Dots leave by j ascending, inside a row by X ascending; under ORIP_FILL_STIPPLE_SERPENTINE the rows with j & 1 leave by X descending.
+ * stats: candidates, ink, near, light, dots.  ink == near + light + dots always.
+ * The call writes NO resident state of the raster chain, nothing of the stroke passes and nothing of the fill's segment list or link result.  The dots (xy
+ * int32 [dots, 2], canvas pixels) wait in a list of their own for orip_fill_stipple_fetch until the next orip_fill_stipple that passes its argument checks.
+ * Errors before any launch, with nothing resident touched and an earlier dot list kept: any argument out of range, unknown flags, NULL stats, a `layer` or
+ * size that is not the resident one when mask is NULL, and 2^26 blocks of 64 candidates or more (a block is 64 consecutive i of one row; the verdicts of a
+ * call are kept whole).  Found on the device, leaving no dot list: 2^26 dots or more.  orip_fill_stipple_fetch without a dot list is an error.  None of
+ * these is a fault.
+ * Declined: blue-noise, error-diffusion or Lloyd stippling (the answer would depend on a scan order or an iteration count); gamma or a tone curve beyond lo
+ * and hi; dot size or double taps by tone; an inverted screen for light pens on dark paper; both a hatch and a stipple on one layer; a Euclidean clearance;
+ * tone from anything but the grey of resized.png; a bound on the worst case beyond the two radii (every ink candidate can cost two windows of 65 x 65). */
+#define ORIP_FILL_STIPPLE_SERPENTINE 1
+#define ORIP_FILL_STIPPLE_STATS 5
+#define ORIP_FILL_STIPPLE_RAD_MAX 32
+int orip_fill_stipple(orip_ctx* ctx, const uint8_t* mask /* [h,w] or NULL = resident mask of `layer` */, int layer, const uint8_t* tone /* [h,w] or NULL = 0 */,
+                      int h, int w, int W, int H, int32_t num, int32_t den, int32_t dx, int32_t dy, int32_t pitch, int32_t row, int32_t shift,
+                      int32_t clear_rad, int32_t tone_rad, int32_t lo, int32_t hi, int32_t flags,
+                      int64_t* stats /* [5]: candidates, ink, near, light, dots */);
+int orip_fill_stipple_fetch(orip_ctx* ctx, int32_t* xy /* [dots,2] */);
 /* --dashes / --dash-mm (csrc/gcode_dash.hip; ours, the reference has no such pass): a stroke with a dash pattern is drawn as its dashes.  All arithmetic is
  * integer on the step grid: nothing behind the conversion to steps is floating point.
  * Unit.  u = 1 / ORIP_DASH_UNIT = 1/256 step: every length below is in u.

@@ -103,6 +103,7 @@ extern "C" void orip_destroy(orip_ctx* c) {
     c->hl_tmp.release(); c->hl_ln.release(); c->hl_pair.release(); c->hl_res.release(); c->hl.release();
     c->st_tmp.release(); c->st_ch.release(); c->st_out.release();
     c->fl_tmp.release(); c->fl_runs.release(); c->fl_out.release(); c->fl_rows.release(); c->fk_tmp.release(); c->fk_pair.release(); c->fk_out.release();
+    c->fs_tmp.release(); c->fs_out.release();
     c->sv_tmp.release(); c->sv_tmp2.release(); c->sv_off.release(); c->sv_pts.release(); c->ht_pts.release(); c->ht_rows.release(); c->ht_x.release();
     c->an_table.release(); c->an_keys.release(); c->an_counts.release(); c->an_tmp.release(); c->an_km.release();
     c->resize_src.release(); c->resize_dst.release();

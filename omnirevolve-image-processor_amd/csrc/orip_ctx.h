@@ -449,6 +449,11 @@ struct orip_ctx {
     // int2[2 fk_segs] of the last orip_fill_link (fk_paths -1: none) until the next one that passes its argument checks or the next orip_fill_mask that does
     DBuf fl_rows; int64_t fl_nrows = 0, fl_row1 = 0; int fl_xmajor[2] = {0, 0};
     DBuf fk_tmp, fk_pair, fk_out; int64_t fk_paths = -1, fk_segs = 0;
+    // fill stipple (fill_stipple.hip), which reads the resident masks and writes nothing of the raster chain, of the stroke passes, of the fill's segment
+    // list or of the link result.  With Z blocks of 64 candidates over the lattice rows: fs_tmp = mask u8[h w] (only of an explicit mask), tone u8[h w] (only
+    // with a tone image), dot u64[Z] = the verdicts, cnt u64[Z + 1] = dots per block, sc u64[Z + 1] = its scan, FsCounters (the unit states the layout), free
+    // between calls; fs_out = THE DOT LIST, xy int2[fs_dots] of the last call (-1: none) until the next one that passes its argument checks
+    DBuf fs_tmp, fs_out; int64_t fs_dots = -1;
     // svg2stream (svg.hip): scratch of the flattening and of the box, the resident paths (off int64[sv_n + 1], pts double2[sv_total]; raw units after
     // orip_svg_flatten, page mm after orip_svg_fit) until the next flatten; orip_gcode_to_steps reads them when it is called without pointers
     DBuf sv_tmp, sv_tmp2, sv_off, sv_pts; int64_t sv_n = 0, sv_total = 0; bool sv_ready = false, sv_box_ok = false; double sv_box[4] = {0, 0, 0, 0};

@@ -820,6 +820,35 @@ class Device:
         self._ck(self.L.orip_fill_link_fetch(self.h, _p(off), _p(pts)))
         return off, pts[:d["points_out"]], d
 
+    def fill_stipple(self, mask, tone, W: int, H: int, place, lattice, clear_rad: int, tone_rad: int, lo: int, hi: int, flags: int, layer: int = 0):
+        """fill stipple (include/orip.h: orip_fill_stipple): the dots of a colour mask u8 [h, w] (nonzero = set; None: the resident mask of `layer`, which is
+        only read) on the canvas W x H, the mask placed by place = (num, den, dx, dy), on the lattice = (pitch, row, shift) of the whole canvas; a dot keeps
+        `clear_rad` source pixels of the mask around it, and the density follows the darkness of tone u8 [h, w] (0 = black; None: all black, the plain
+        stipple) over `tone_rad` source pixels, none at darkness `lo` and below, full at `hi` and above; flags: lib.FILL_STIPPLE_SERPENTINE or 0.  Nothing
+        resident changes.  -> (xy int32 [dots, 2] in canvas pixels, in drawing order, {lib.FILL_STIPPLE_STATS})"""
+        m = None
+        if mask is not None:
+            m = np.ascontiguousarray(mask, np.uint8)
+            if m.ndim != 2:
+                raise ValueError(f"mask of shape {m.shape}: [h, w]")
+        h, w = (self.H, self.W) if m is None else m.shape
+        g = None
+        if tone is not None:
+            g = np.ascontiguousarray(tone, np.uint8)
+            if g.shape != (h, w):
+                raise ValueError(f"tone of shape {g.shape} for a mask of {w} x {h}: [h, w]")
+        scal = [int(v) for v in (h, w, W, H, *place, *lattice, clear_rad, tone_rad, lo, hi, flags)]
+        if len(scal) != 16:
+            raise ValueError("place = (num, den, dx, dy) and lattice = (pitch, row, shift)")
+        if any(abs(v) >= 1 << 31 for v in scal) or abs(int(layer)) >= 1 << 31:
+            raise OripError(f"orip_fill_stipple: an argument does not fit 32 bits: {[int(layer)] + scal}")
+        st = np.zeros(len(_l.FILL_STIPPLE_STATS), np.int64)
+        self._ck(self.L.orip_fill_stipple(self.h, None if m is None else _p(m), int(layer), None if g is None else _p(g), *scal, _p(st)))
+        d = {k: int(v) for k, v in zip(_l.FILL_STIPPLE_STATS, st)}
+        xy = np.zeros((max(d["dots"], 1), 2), np.int32)
+        self._ck(self.L.orip_fill_stipple_fetch(self.h, _p(xy)))
+        return xy[:d["dots"]], d
+
     def gcode_dash(self, off, pts, pattern, phase, pat_off, pat_val, n: int | None = None):
         """--dashes / --dash-mm (include/orip.h: orip_gcode_dash): of the step polylines (off int64 [n + 1], pts int32 [total, 2]; both None = the n resident
         ones) every stroke with pattern[k] >= 0 is cut into the dashes of that pattern of the table (pat_off int32 [np + 1], pat_val int64, in 1/256 step),

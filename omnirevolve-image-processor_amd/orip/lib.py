@@ -88,6 +88,7 @@ SIGNATURES = {
     "orip_svg_stipple": (_i32, [_vp, _vp, _vp, _i64, _P(GcodeMap), _i32, _i32, _i32, _i32, _vp, _i32, _vp]),
     "orip_fill_mask": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]), "orip_fill_fetch": (_i32, [_vp, _vp]),
     "orip_fill_link": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]), "orip_fill_link_fetch": (_i32, [_vp, _vp, _vp]),
+    "orip_fill_stipple": (_i32, [_vp, _vp, _i32, _vp] + [_i32] * 16 + [_vp]), "orip_fill_stipple_fetch": (_i32, [_vp, _vp]),
     "orip_gcode_dash": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp]), "orip_gcode_dash_fetch": (_i32, [_vp, _vp]),
     "orip_gcode_improve": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _i64, _vp, _vp, _vp]),
     "orip_gcode_seam": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
@@ -121,6 +122,8 @@ FILL_SERPENTINE, FILL_ALONG, FILL_ACROSS = 1, 2, 4                              
 FILL_COORD_MAX, FILL_U_MAX, FILL_LEN_MAX = 1 << 20, 4096, 1 << 15                          # the largest side and offset; direction component; spacing, inset and min_len in pixels
 FILL_LINK_STATS = ("segments", "in_reach", "eligible", "links", "paths_out", "points_out", "link_steps")
 FILL_LINK_REACH_MAX = 1 << 15                                                             # include/orip.h: the largest reach of orip_fill_link, in pixels
+FILL_STIPPLE_STATS = ("candidates", "ink", "near", "light", "dots")
+FILL_STIPPLE_SERPENTINE, FILL_STIPPLE_RAD_MAX = 1, 32                                     # include/orip.h: the flag of orip_fill_stipple; the largest clear_rad and tone_rad, in source pixels
 DASH_STATS = ("paths_in", "dashed", "dashes", "collapsed", "paths_out", "points_out", "length_in", "length_on")
 DASH_UNIT, DASH_MAX_ENTRIES = 256, 64                        # include/orip.h: dash lengths are in 1/256 step; entries of one pattern at most
 IMPROVE_MAX_PATHS, IMPROVE_ROUNDS_AUTO = 65536, (1 << 63) - 1

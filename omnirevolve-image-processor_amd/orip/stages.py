@@ -7,6 +7,7 @@
     run_path(bgr, cfg)                  -> ops per layer, everything resident on the GPU between stages
     fill_options(cfg) / fill_layer(mask, w, h, cfg, opts)    -> hatch ops of a colour mask                (fill_layers.py; ours)
     fill_strokes(mask, w, h, cfg, opts)                      -> the same hatch as zigzags, links on ink   (fill_layers.py with connect; ours)
+    fill_dots(mask, tone, w, h, cfg, opts)                   -> dots whose density follows the tone       (fill_layers.py with mode stipple; ours)
 
 Every function drives liborip.so through orip.device.Device; arrays cross the host boundary only where the
 reference's stage API puts a file.
@@ -295,6 +296,12 @@ FILL_DEFAULTS = {"spacing_mm": 1.0, "angle_deg": 45.0, "direction": "along", "in
 FILL_DIRECTIONS = {"along": _l.FILL_ALONG, "across": _l.FILL_ACROSS, "cross": _l.FILL_ALONG | _l.FILL_ACROSS}
 FILL_ORDERS = ("serpentine", "nearest")
 FILL_CONNECT_KEYS = ("connect", "connect_mm")                                             # fill connect (include/orip.h: orip_fill_link); connect_mm defaults to twice the layer's spacing_mm
+# fill stipple (include/orip.h: orip_fill_stipple): a layer, or the fill object for all of them, says "mode": "stipple"; the keys of this table are read only
+# there, and inset_mm, serpentine and order are shared with the hatch.  tone_radius_mm has no fixed default: half the layer's stipple_mm
+FILL_MODES = ("hatch", "stipple")
+FILL_STIPPLE_DEFAULTS = {"stipple_mm": 1.0, "stipple_pattern": "stagger", "tone": True, "tone_lo": 0, "tone_hi": 255}
+FILL_STIPPLE_KEYS = ("mode", "tone_radius_mm") + tuple(FILL_STIPPLE_DEFAULTS)
+FILL_HATCH_ONLY_KEYS = ("spacing_mm", "angle_deg", "direction", "min_run_mm") + FILL_CONNECT_KEYS      # an error in a stipple layer's own object
 
 
 def _fill_pixels(what: str, mm, ppm: int, lo: int) -> int:
@@ -306,12 +313,44 @@ def _fill_pixels(what: str, mm, ppm: int, lo: int) -> int:
     return px
 
 
+def _fill_stipple_options(name: str, own: dict, o: dict, ppm: int) -> dict:
+    """the entry of a layer whose mode is "stipple": own = the layer's own object, o = the same over the fill object over the defaults"""
+    from .svg import STIPPLE_PATTERNS, stipple_lattice
+    for k in own:
+        if k in FILL_HATCH_ONLY_KEYS:                                                 # inherited from the fill object they are ignored: one global hatch setting, one stippled layer
+            raise ValueError(f"fill: {k} in layers.{name} belongs to the hatch, and the layer's mode is stipple")
+    o = dict(FILL_STIPPLE_DEFAULTS, **o)
+    if o["order"] not in FILL_ORDERS:
+        raise ValueError(f"fill: order {o['order']!r}: one of " + ", ".join(FILL_ORDERS))
+    if not isinstance(o["serpentine"], bool):
+        raise ValueError(f"fill: serpentine must be true or false, not {o['serpentine']!r}")
+    if not isinstance(o["tone"], bool):
+        raise ValueError(f"fill: tone must be true or false, not {o['tone']!r}")
+    if o["stipple_pattern"] not in STIPPLE_PATTERNS:
+        raise ValueError(f"fill: stipple_pattern {o['stipple_pattern']!r}: one of " + ", ".join(STIPPLE_PATTERNS))
+    for k in ("tone_lo", "tone_hi"):
+        if isinstance(o[k], bool) or not isinstance(o[k], int) or not 0 <= o[k] <= 255:
+            raise ValueError(f"fill: {k} must be an integer in 0 .. 255, not {o[k]!r}")
+    if o["tone_lo"] >= o["tone_hi"]:
+        raise ValueError(f"fill: tone_lo {o['tone_lo']} must be below tone_hi {o['tone_hi']}")
+    pitch = _fill_pixels("stipple_mm", o["stipple_mm"], ppm, 2)
+    stated = "tone_radius_mm" in o
+    return {"mode": "stipple", "lattice": stipple_lattice(pitch, o["stipple_pattern"]), "inset": _fill_pixels("inset_mm", o["inset_mm"], ppm, 0), "tone": o["tone"],
+            "lo": o["tone_lo"], "hi": o["tone_hi"], "tone_radius": _fill_pixels("tone_radius_mm", o["tone_radius_mm"] if stated else 0.5 * o["stipple_mm"], ppm, 0),
+            "tone_radius_stated": stated, "flags": _l.FILL_STIPPLE_SERPENTINE if o["serpentine"] else 0, "order": o["order"]}
+
+
 def fill_options(cfg: Config):
     """the `fill` object of the config file (cfg._raw: Config has no such field) -> None without one, else {layer name: options} for the layers named under
     "layers", in color_names order.  Options: spacing, inset, min_len (pixels: int(round(mm * pixels_per_mm))), u (orip.svg.hatch_direction_vector of
     angle_deg, in the manifest's frame: x right, y down), flags (lib.FILL_*), order ("serpentine": as the device emits; "nearest": greedy from the end of
     the outline), angle_deg; and ONLY with "connect": true the key reach (pixels of connect_mm, default twice the layer's spacing_mm, 1 .. 2^15), which
-    makes fill_layers draw the layer's hatch as zigzags (fill_strokes).  An unknown key, a layer that is not in color_names or a value out of range raises ValueError naming it."""
+    makes fill_layers draw the layer's hatch as zigzags (fill_strokes).  A layer whose object, or the fill object, says "mode": "stipple" is filled with dots
+    (fill_dots; include/orip.h: orip_fill_stipple) and its entry is another: mode = "stipple", lattice = orip.svg.stipple_lattice of stipple_mm in pixels (2 ..
+    2^15) and stipple_pattern ("stagger" / "square"), inset (pixels of inset_mm), tone (false: the plain stipple), lo / hi (tone_lo / tone_hi, darkness = 255 -
+    grey: no dots at lo and below, all at hi and above), tone_radius (pixels of tone_radius_mm, default half of stipple_mm) with tone_radius_stated, flags
+    (lib.FILL_STIPPLE_SERPENTINE from serpentine), order.  A hatch-only key (FILL_HATCH_ONLY_KEYS) in a stipple layer's own object is an error; inherited from
+    the fill object it is ignored.  The FILL_STIPPLE_KEYS are read only where the mode is stipple.  An unknown key, a layer that is not in color_names or a value out of range raises ValueError naming it."""
     from .svg import hatch_direction_vector
     raw = (getattr(cfg, "_raw", None) or {}).get("fill")
     if raw is None:
@@ -319,7 +358,7 @@ def fill_options(cfg: Config):
     if not isinstance(raw, dict):
         raise ValueError("fill: must be an object")
     for k in raw:
-        if k != "layers" and k not in FILL_DEFAULTS and k not in FILL_CONNECT_KEYS:
+        if k != "layers" and k not in FILL_DEFAULTS and k not in FILL_CONNECT_KEYS and k not in FILL_STIPPLE_KEYS:
             raise ValueError(f"fill: unknown key {k!r}")
     layers = raw.get("layers", {})
     if not isinstance(layers, dict):
@@ -336,10 +375,16 @@ def fill_options(cfg: Config):
         if not isinstance(own, dict):
             raise ValueError(f"fill: layers.{name} must be an object")
         for k in own:
-            if k not in FILL_DEFAULTS and k not in FILL_CONNECT_KEYS:
+            if k not in FILL_DEFAULTS and k not in FILL_CONNECT_KEYS and k not in FILL_STIPPLE_KEYS:
                 raise ValueError(f"fill: unknown key {k!r} in layers.{name}")
         o = dict(FILL_DEFAULTS, **{k: v for k, v in raw.items() if k != "layers"})
         o.update(own)
+        mode = o.get("mode", "hatch")
+        if mode not in FILL_MODES:
+            raise ValueError(f"fill: mode {mode!r}: one of " + ", ".join(FILL_MODES))
+        if mode == "stipple":                                                         # the stipple keys are read only here
+            out[name] = _fill_stipple_options(name, own, o, ppm)
+            continue
         if o["direction"] not in FILL_DIRECTIONS:
             raise ValueError(f"fill: direction {o['direction']!r}: one of " + ", ".join(FILL_DIRECTIONS))
         if o["order"] not in FILL_ORDERS:
@@ -430,6 +475,53 @@ def fill_stroke_ops(strokes) -> List[dict]:
 def fill_ops(seg) -> List[dict]:
     """segments as ops of stage 12's kind: {"type": "line", "points": float32 [2, 2]} in canvas pixels"""
     return [{"type": "line", "points": np.asarray(s, np.float32).reshape(2, 2).copy()} for s in np.asarray(seg).reshape(-1, 4)]
+
+
+def fill_stipple_radii(cfg: Config, opts: dict, w_src: int, h_src: int) -> Tuple[int, int]:
+    """(clear_rad, tone_rad) of orip_fill_stipple in SOURCE pixels, from a stipple entry of fill_options and the placement num / den: clear_rad =
+    ceil(inset den / num), tone_rad = floor(tone_radius den / num).  More than lib.FILL_STIPPLE_RAD_MAX is a ValueError naming inset_mm or tone_radius_mm;
+    only a tone radius nobody stated (half the pitch) is capped there instead."""
+    num, den, _, _ = fill_placement(cfg, w_src, h_src)
+    clear_rad, tone_rad = -((-opts["inset"] * den) // num), (opts["tone_radius"] * den) // num
+    if clear_rad > _l.FILL_STIPPLE_RAD_MAX:
+        raise ValueError(f"fill: inset_mm is {opts['inset']} pixels, {clear_rad} pixels of the {w_src} x {h_src} image: at most {_l.FILL_STIPPLE_RAD_MAX}")
+    if tone_rad > _l.FILL_STIPPLE_RAD_MAX:
+        if opts["tone_radius_stated"]:
+            raise ValueError(f"fill: tone_radius_mm is {opts['tone_radius']} pixels, {tone_rad} pixels of the {w_src} x {h_src} image: at most {_l.FILL_STIPPLE_RAD_MAX}")
+        tone_rad = _l.FILL_STIPPLE_RAD_MAX
+    return int(clear_rad), int(tone_rad)
+
+
+def fill_dots(mask, tone, w_src: int, h_src: int, cfg: Config, opts: dict, dev: Device | None = None, layer: int = 0, start=None, stipple_fn=None, order_fn=None):
+    """the dots of one layer (include/orip.h: orip_fill_stipple) -> (xy int32 [n, 2] in canvas pixels, in drawing order, {lib.FILL_STIPPLE_STATS}).  As
+    fill_segments, which it mirrors: mask u8 [h_src, w_src] or None for the resident mask of `layer`; tone u8 [h_src, w_src], the grey source image, which is
+    not passed on when the entry says tone = false; opts: a stipple entry of fill_options.  stipple_fn / order_fn stand in for Device.fill_stipple /
+    Device.gcode_order_pens.  Order "nearest" sends every dot as the ends [x, y, x, y] of a stroke through gcode_order_pens: one group, nothing to reverse,
+    from `start`."""
+    from .stream import to_steps
+    for what, a in (("mask", mask), ("tone", tone)):
+        if a is not None and tuple(np.asarray(a).shape) != (int(h_src), int(w_src)):
+            raise ValueError(f"{what} of shape {np.asarray(a).shape} for a source of {w_src} x {h_src}")
+    W, H = canvas_size_px(cfg)
+    clear_rad, tone_rad = fill_stipple_radii(cfg, opts, w_src, h_src)
+    if stipple_fn is None:
+        d = dev or device()
+        stipple_fn = lambda *a: d.fill_stipple(*a, layer=layer)
+    xy, st = stipple_fn(mask, tone if opts["tone"] else None, W, H, fill_placement(cfg, w_src, h_src), opts["lattice"], clear_rad, tone_rad, opts["lo"], opts["hi"], opts["flags"])
+    xy = np.asarray(xy, np.int32).reshape(-1, 2)
+    if opts["order"] == "nearest" and len(xy):
+        if order_fn is None:
+            order_fn = (dev or device()).gcode_order_pens
+        p = to_steps(xy, W, H)
+        s0 = (0, 0) if start is None else tuple(int(v) for v in to_steps(np.asarray(start, np.float64).reshape(1, 2), W, H)[0])
+        order, _ = order_fn(np.concatenate([p, p], 1).astype(np.int32), np.zeros(len(xy), np.int32), 1, reverse=False, start=s0)
+        xy = xy[np.asarray(order, np.int64)]
+    return np.ascontiguousarray(xy, np.int32), st
+
+
+def fill_dot_ops(xy) -> List[dict]:
+    """dots as ops of stage 12's kind: {"type": "tap", "x": int, "y": int} in canvas pixels, what ops_from_device writes"""
+    return [{"type": "tap", "x": int(x), "y": int(y)} for x, y in np.asarray(xy).reshape(-1, 2).tolist()]
 
 
 def fill_layer(mask, w_src: int, h_src: int, cfg: Config, opts: dict, dev: Device | None = None, layer: int = 0, start=None) -> List[dict]:

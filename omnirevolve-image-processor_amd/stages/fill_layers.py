@@ -3,7 +3,9 @@
 # <layer>/ops.pkl (stage 12's file, read by layer name and never rewritten) -> <layer>/ops_filled.pkl = the outline ops, then the fill ops; the layer's
 # entry of vector_manifest.json then names ops_filled.pkl, and stages 13 and 14 follow the manifest.  The hatch itself runs on the GPU through liborip.so
 # (include/orip.h: orip_fill_mask states the rule); see orip.stages.fill_options for the config.  Without a `fill` object it writes nothing.  A layer with
-# "connect": true has its hatch drawn as zigzags, the links kept on the mask's ink (orip_fill_link): its fill ops are polylines of 2 m points.
+# "connect": true has its hatch drawn as zigzags, the links kept on the mask's ink (orip_fill_link): its fill ops are polylines of 2 m points.  A layer with
+# "mode": "stipple" is filled with dots on one lattice for the whole canvas, their density following the grey of resized.png inside the mask
+# (orip_fill_stipple): its fill ops are taps, and it reports on a [fill-stipple] line.
 import json
 import os
 import sys
@@ -13,7 +15,7 @@ import numpy as np
 import stage_io as _io
 from orip import stages as S
 from orip.config import load_config
-from orip.lib import FILL_LINK_STATS, FILL_STATS
+from orip.lib import FILL_LINK_STATS, FILL_STATS, FILL_STIPPLE_STATS
 
 
 def outline_end(ops):
@@ -26,8 +28,8 @@ def outline_end(ops):
     return None
 
 
-def run(cfg, fill_fn=None, order_fn=None, link_fn=None) -> int:
-    """fill_fn / order_fn / link_fn stand in for the device calls (orip.stages.fill_segments, fill_strokes); None: the GPU"""
+def run(cfg, fill_fn=None, order_fn=None, link_fn=None, stipple_fn=None) -> int:
+    """fill_fn / order_fn / link_fn / stipple_fn stand in for the device calls (orip.stages.fill_segments, fill_strokes, fill_dots); None: the GPU"""
     opts = S.fill_options(cfg)
     if opts is None:
         print("[fill] no fill object in the config: nothing written")
@@ -52,6 +54,17 @@ def run(cfg, fill_fn=None, order_fn=None, link_fn=None) -> int:
         if mask.shape != (h, w):
             raise SystemExit(f"{name}/mask.png is {mask.shape[1]} x {mask.shape[0]}, resized.png {w} x {h}")
         ops = _io.load_pickle(p_ops)
+        p_out = os.path.join(layer_dir, "ops_filled.pkl")
+        if o.get("mode") == "stipple":                                                # dots whose density follows resized.png inside the mask (include/orip.h: orip_fill_stipple)
+            xy, st = S.fill_dots(mask, base, w, h, cfg, o, start=outline_end(ops), stipple_fn=stipple_fn, order_fn=order_fn)
+            filled = list(ops) + S.fill_dot_ops(xy)
+            _io.save_pickle(p_out, filled)
+            entries[name]["file"] = os.path.relpath(p_out, out)
+            entries[name]["count_ops"] = len(filled)
+            clear_rad, tone_rad = S.fill_stipple_radii(cfg, o, w, h)
+            print(f"[fill-stipple] {name}: pitch={o['lattice'][0]} row={o['lattice'][1]} shift={o['lattice'][2]} clear={clear_rad} "
+                  f"tone_radius={tone_rad} tone={'on' if o['tone'] else 'off'} lo={o['lo']} hi={o['hi']} order={o['order']} " + " ".join(f"{k}={st[k]}" for k in FILL_STIPPLE_STATS))
+            continue
         lst = None
         if "reach" in o:                                                              # connect: the hatch as zigzags (include/orip.h: orip_fill_link)
             strokes, st, lst = S.fill_strokes(mask, w, h, cfg, o, start=outline_end(ops), fill_fn=fill_fn, link_fn=link_fn, order_fn=order_fn)
@@ -59,7 +72,6 @@ def run(cfg, fill_fn=None, order_fn=None, link_fn=None) -> int:
         else:
             seg, st = S.fill_segments(mask, w, h, cfg, o, start=outline_end(ops), fill_fn=fill_fn, order_fn=order_fn)
             filled = list(ops) + S.fill_ops(seg)
-        p_out = os.path.join(layer_dir, "ops_filled.pkl")
         _io.save_pickle(p_out, filled)
         entries[name]["file"] = os.path.relpath(p_out, out)
         entries[name]["count_ops"] = len(filled)
